@@ -7,9 +7,11 @@ synthetic frame pair that is already resident in HBM, producing one interpolated
 With N GPUs every rank interpolates its own pair per step (frame-batch sharding, weak scaling)
 and the N output frames are all-gathered over RCCL/xGMI -- the only collective on the path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
-Rank 0 prints ONE JSON line.  Besides the contract's fields it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps, writes the last step's outputs if --dump-outputs
+is given, and prints the contract's fields (metric, value, unit, higher_is_better, dtype, ms_per_step, ...) and the per-step GPU
+times.  With --full the line also carries
   roofline     : the kernel family with the largest share of the forward (today conv3x3_planes_kernel),
                  achieved = sum of algorithmic FLOPs / sum of launch durations, measured live with HIP
                  events on the launch stream in a separate instrumented pass after the timed region;
@@ -98,6 +100,43 @@ def host_cores():
     return use, f"{model}; {n} logical CPUs visible, cgroup quota {quota if quota else 'none'}"
 
 
+DUMP_BUDGET_BYTES = 60 * 1000 * 1000     # --dump-outputs: the arrays' bytes; with the .npy headers well under 64 MB
+
+
+def dump_outputs(path, named):
+    """--dump-outputs: ``named`` = [(name, tensor)], the headline frame first; each is written as ``path/<name>.npy`` in float32.  The
+    first array is written whole while it takes at most half of the budget, the others share what is left equally.  An array over
+    its share is replaced by the elements at a fixed sample of flat (C-order) positions, sorted, drawn by numpy's default_rng seeded
+    with the array's name: the same positions in every run with the same arguments, so two builds compare element for element."""
+    import zlib
+    os.makedirs(path, exist_ok=True)
+    left = DUMP_BUDGET_BYTES
+    for k, (name, t) in enumerate(named):
+        a = t.detach().to("cpu", torch.float32).numpy()
+        share = left // 2 if k == 0 else left // (len(named) - k)
+        n = max(1, share // a.itemsize)
+        if a.size > n:
+            pos = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(a.size, n, replace=False))
+            a = a.reshape(-1)[pos]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+        left -= a.nbytes
+
+
+def outputs_to_dump(outputs, gathered=None):
+    """--dump-outputs: what a caller of the timed step receives, as [(name, tensor)] for ``dump_outputs``: the forward's dict
+    (``I_t`` first; list entries as ``<key>_<i>``) and, in a collective run, the all-gathered frames of the step (``PipelinedGather``
+    hands them out as a list of per-rank tensors) stacked in rank order as ``I_t_all_ranks``."""
+    named = [("I_t", outputs["I_t"])]
+    if gathered is not None:
+        named.append(("I_t_all_ranks", torch.stack(list(gathered))))
+    for k, v in outputs.items():
+        if isinstance(v, (list, tuple)):
+            named += [(f"{k}_{j}", t) for j, t in enumerate(v) if torch.is_tensor(t)]
+        elif torch.is_tensor(v) and k != "I_t":
+            named.append((k, v))
+    return named
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -124,7 +163,18 @@ def parse():
     ap.add_argument("--gather-u8", action="store_true", help="N > 1: all-gather the output frames rounded to uint8 (4x fewer bytes over xGMI)")
     ap.add_argument("--graph", action="store_true", help="replay the forward from a captured HIP graph (Network.enable_graphs); measured "
                     "within 0.5 %% of eager launches at 1080p and at 256x448: the stream is already back to back")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, also run what it does not need: the instrumented per-kernel pass (roofline, kernels), "
+                         "the PCIe-inclusive rate (host_io), the other BASELINE.json configurations (configs) and the CPU oracle "
+                         "(cpu_baseline, parity); --no-profile / --no-host-io / --no-configs / --no-cpu-baseline leave parts out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32, at most 64 MB in "
+                         "all; a larger array is replaced by a fixed seeded sample of its elements)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_profile = args.no_host_io = args.no_configs = args.no_cpu_baseline = True
     if args.config:
         args.variant, args.height, args.width, g_on, _ = CONFIGS[args.config]
         args.global_off = not g_on
@@ -338,11 +388,17 @@ def main():
 
     def drain():
         if gather is not None:
-            gather.drain()
+            return gather.drain()
 
-    def step(i):
+    dump = rank == 0 and args.dump_outputs is not None
+    last = {}                                   # --dump-outputs: what the last timed step returned
+
+    def step(i, keep=False):
         a, b = frames[i % n_in]
-        out = net(a, b)["I_t"]
+        res = net(a, b)
+        out = res["I_t"]
+        if keep:
+            last["outputs"] = res
         if gather is not None:
             gather.submit(out)                  # per-rank output frames only; returns step i-1's frames
         return out
@@ -369,9 +425,9 @@ def main():
     t0 = time.perf_counter()
     marks[0].record()
     for i in range(args.steps):
-        step(i)
+        step(i, keep=dump and i == args.steps - 1)
         marks[i + 1].record()
-    drain()
+    gathered = drain()
     torch.cuda.synchronize()
     if collective:
         dist.barrier()
@@ -388,6 +444,10 @@ def main():
         elapsed = float(allt.max().item())
 
     if rank == 0:
+        if dump:
+            dump_outputs(args.dump_outputs, outputs_to_dump(last["outputs"], gathered))
+            last.clear()
+        gathered = None
         ms_per_step = 1e3 * elapsed / args.steps
         fps = world * args.steps / elapsed
         key = (variant, H, W, net.global_motion)

@@ -410,12 +410,15 @@ def check(only=None) -> int:
 
 
 def main():
+    global REF
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--check", action="store_true", help="regenerate into a temp dir and compare with tests/golden bit for bit")
     ap.add_argument("--only", default=None, help="comma-separated case / op names (default: everything)")
     ap.add_argument("--skip-large", action="store_true", help="leave out the 4K case (minutes of CPU, ~30 GB of host memory)")
     ap.add_argument("--imports-only", action="store_true", help="import the reference and exit (checks the import isolation)")
+    ap.add_argument("--reference", default=REF, help="the reference's checkout (default: %(default)s)")
     args = ap.parse_args()
+    REF = args.reference
     if args.imports_only:
         r = import_reference()
         print("reference imported:", r.network_base.__file__, r.attention.__file__, r.demo_2x.__file__)
