@@ -133,6 +133,8 @@ SIGNATURES = {
     "atmvfi_final_residual": (c_i, [c_f, c_f, c_i, c_f, c_f, c_i, c_i, c_i, c_f]),
     "atmvfi_l1_mean": (c_i, [c_f, c_f, c_f, c_i, c_l, c_f, c_l, c_f]),
     "atmvfi_l1_mean_workspace_floats": (c_l, [c_i, c_l]),
+    "atmvfi_ssim_psnr": (c_i, [c_f, c_l, c_l, c_l, c_l, c_f, c_l, c_l, c_l, c_l, c_i, c_i, c_i, ctypes.c_float, c_i, c_f, c_f, c_l, c_f]),
+    "atmvfi_ssim_psnr_workspace_floats": (c_l, [c_i, c_i, c_i]),
     "atmvfi_ensemble_select": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_l, c_f]),
     "atmvfi_stem_fused": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_f]),
     "atmvfi_plan_fn_id": (c_i, [ctypes.c_char_p]),
@@ -142,6 +144,7 @@ SIGNATURES = {
                                     ctypes.POINTER(ctypes.c_uint64), c_i, ctypes.POINTER(c_i), ctypes.POINTER(ctypes.c_void_p), c_i,
                                     ctypes.POINTER(ctypes.c_void_p), c_i]),
 }
+SSIM_X_U8, SSIM_X_BGR, SSIM_ROUND_Y, SSIM_ACCUMULATE, SSIM_MSE_F32 = 1, 2, 4, 8, 16     # include/atmvfi.h ATMVFI_SSIM_*
 PLAN_RECORD, PLAN_WAIT = -2, -3        # include/atmvfi.h: the two synchronisation ops of atmvfi_plan_run_lanes
 
 
@@ -1335,6 +1338,33 @@ class HipOps:
                 workspace = cache[key] = torch.empty(self.l1_mean_workspace_floats(*key), dtype=torch.float32, device=a.device)
         self._run("l1_mean", {"bytes": 8.0 * a.numel()}, self.lib.atmvfi_l1_mean, _ptr(a), _ptr(b), _ptr(out), n, a.numel() // n,
                   _ptr(workspace), workspace.numel(), self._stream())
+
+    def ssim_psnr_workspace_floats(self, n: int, h: int, w: int) -> int:
+        return int(self.lib.atmvfi_ssim_psnr_workspace_floats(n, h, w))
+
+    def ssim_psnr(self, x, y, out, workspace, val_range: float = 0.0, flags: int = 0):
+        """ssim_matlab + squared-error mean per sample (include/atmvfi.h atmvfi_ssim_psnr): x = the ground truth, a CUDA fp32 [B,3,H,W]
+        view or (``flags & SSIM_X_U8``) a CUDA uint8 [B,H,W,3] view; y = a CUDA fp32 [B,3,H,W] view, any strides; out = CUDA fp64
+        [B,3] contiguous (ssim, cs, mse); workspace = CUDA fp32 of at least ``ssim_psnr_workspace_floats(B, H, W)`` elements."""
+        _chk(y, "ssim_psnr.y"); _chk(workspace, "ssim_psnr.workspace")
+        if y.dim() != 4 or y.shape[1] != 3:
+            raise ValueError(f"ssim_psnr: y must be [B,3,H,W], got {tuple(y.shape)}")
+        b, _, h, w = y.shape
+        if flags & SSIM_X_U8:
+            if not x.is_cuda or x.dtype != torch.uint8 or tuple(x.shape) != (b, h, w, 3):
+                raise ValueError(f"ssim_psnr: a uint8 x must be a CUDA [B,H,W,3] tensor of y's size, got {x.device} {x.dtype} {tuple(x.shape)}")
+            xs = (x.stride(0), x.stride(3), x.stride(1), x.stride(2))
+        else:
+            _chk(x, "ssim_psnr.x")
+            if tuple(x.shape) != tuple(y.shape):
+                raise ValueError(f"ssim_psnr: x {tuple(x.shape)} and y {tuple(y.shape)} differ in shape")
+            xs = tuple(x.stride())
+        if not out.is_cuda or out.dtype != torch.float64 or tuple(out.shape) != (b, 3) or not out.is_contiguous():
+            raise ValueError("ssim_psnr: out must be a contiguous CUDA float64 [B,3] tensor")
+        if not workspace.is_contiguous() or workspace.numel() < self.ssim_psnr_workspace_floats(b, h, w):
+            raise ValueError("ssim_psnr: workspace too small")
+        self._run("ssim_psnr", {"bytes": float(x.numel() * x.element_size() + 4 * y.numel())}, self.lib.atmvfi_ssim_psnr, _ptr(x), *xs,
+                  _ptr(y), *y.stride(), b, h, w, float(val_range), int(flags), _ptr(out), _ptr(workspace), workspace.numel(), self._stream())
 
     def ensemble_select(self, losses, cands, out0, out1):
         """Per sample the candidate flow pair of the level with the smallest loss (first on ties): losses = three [B] tensors,

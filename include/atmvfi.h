@@ -447,6 +447,32 @@ int atmvfi_stem_fused(const float* x, int F, int H, int W, int C0, int C1, const
                       const float* b3, const float* p3, void* out_hi, void* out_lo, int64_t out_plane_rows, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Quality metrics (metrics.hip): ssim_matlab of the reference's evaluation scripts (benchmark/pytorch_msssim.py:82-135: an 11x11x11
+ * Gaussian conv3d over channels, H and W on replicate-padded inputs) and the squared-error mean of PSNR, for B frame pairs at once.
+ *   x: the reference's img1 (the ground truth): fp32, or uint8 with ATMVFI_SSIM_X_U8 (then x = (float)u / 255.0f, and channel c is
+ *      read from channel 2 - c with ATMVFI_SSIM_X_BGR); y: fp32.  Both are [B,3,H,W] views given by element strides (batch, channel,
+ *      row, column), so an un-padded slice or a uint8 HWC frame (strides H*W*3, 1, W*3, 3) is read in place.
+ *   val_range > 0: the L of C1 = (0.01 L)^2, C2 = (0.03 L)^2; otherwise the reference's rule on x, applied on the device
+ *      (max > 128 -> 255 else 1, minus min < -0.5 -> -1 else 0), over all B samples as torch.max(img1) does.
+ *   ATMVFI_SSIM_ROUND_Y: y is replaced by rint(y * 255) / 255 in fp32 first (UCF101 protocol).
+ *   mse: mean of (x - y)^2 accumulated in fp64; the difference and square in fp64 (u8: u / 255.0 in double), in fp32 with
+ *      ATMVFI_SSIM_MSE_F32.
+ *   out: fp64 [B,3] = (ssim, cs, mse) per sample, written, or added to with ATMVFI_SSIM_ACCUMULATE (a running sum over a dataset).
+ * H, W >= 11 (the reference shrinks its window below that: not supported, ATMVFI_EINVAL).  Scratch: at least
+ * atmvfi_ssim_psnr_workspace_floats(B, H, W) floats, 16-byte aligned, the caller's.  Fixed reduction order, no float atomics: two runs
+ * are bit-identical. */
+#define ATMVFI_SSIM_X_U8 1
+#define ATMVFI_SSIM_X_BGR 2
+#define ATMVFI_SSIM_ROUND_Y 4
+#define ATMVFI_SSIM_ACCUMULATE 8
+#define ATMVFI_SSIM_MSE_F32 16
+#define ATMVFI_SSIM_FLAG_MASK 31
+int64_t atmvfi_ssim_psnr_workspace_floats(int B, int H, int W);
+int atmvfi_ssim_psnr(const void* x, int64_t x_bstride, int64_t x_cstride, int64_t x_ystride, int64_t x_xstride, const float* y,
+                     int64_t y_bstride, int64_t y_cstride, int64_t y_ystride, int64_t y_xstride, int B, int H, int W, float val_range,
+                     int flags, double* out, float* workspace, int64_t workspace_floats, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Launch plans: one forward of the hot path as ONE call.
  *
  * The reference's callers run `model(im0, im1)` in a loop on frames of one size (benchmark/test_vimeo90k.py: 3 782 triplets of
