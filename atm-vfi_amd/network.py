@@ -94,7 +94,6 @@ class BlockRunner:
 
     def _init_runner(self):
         self._ops_obj = None
-        self.use_split_planes = True       # kernel selection (Network's `selections` argument): split planes between contraction layers
         self._bufs: Dict[Tuple, object] = {}
         self._geo: Dict[Tuple, Tuple[WindowGeometry, torch.Tensor, Optional[torch.Tensor]]] = {}
 
@@ -131,6 +130,11 @@ class BlockRunner:
             self._geo[key] = g
         return g
 
+    @staticmethod
+    def _plane_deconvs(ops) -> bool:
+        """Split planes between contraction layers: nn.Linear inputs of the blocks and the decoder deconvs read their operands as
+        split planes through the LDS-DMA GEMM (the f16x3 engine of a backend that has the plane sinks)."""
+        return getattr(ops, "precision", None) == "f16x3" and getattr(ops, "split_planes_ok", False)
 
     def _block(self, ops, P, p, x, frames, h, w, ws, shift, cross, out, motion_dst, tag, out_sink=None, motion_sink=None):
         """One shifted-window transformer block (ATMFormer attention.py:265-334 when ``cross``,
@@ -144,7 +148,7 @@ class BlockRunner:
         # With the f16x3 engine every nn.Linear input is written by its producer as split planes (fp16 hi / lo', same
         # bytes as fp32) and read by the GEMM through LDS-DMA; fp32 copies are kept only where something else reads them
         # (xn is the residual of proj: the reference adds onto the post-norm tensor).
-        pl = getattr(ops, "precision", None) == "f16x3" and getattr(ops, "split_planes_ok", False) and self.use_split_planes
+        pl = self._plane_deconvs(ops)
         xn = self.buf(f"{tag}xn", mw, c)
         xn_p = self.planes(f"{tag}xn_p", mw, c) if pl else None
         ops.layernorm(x, xn, P[f"{p}.norm1.weight"], P[f"{p}.norm1.bias"], src_row_map=row_map, **({"planes": xn_p} if pl else {}))
@@ -183,8 +187,7 @@ class BlockRunner:
 class Network(_ParamWatch, BlockRunner, nn.Module):
     VARIANT = "base"
 
-    SELECTIONS = ("use_split_planes", "use_plane_deconvs", "use_plane_convs", "use_unet_planes", "use_fused_stem", "use_fused_tail",
-                  "use_splitk", "use_lanes", "use_plans")
+    SELECTIONS = ("use_plans",)
 
     def __init__(self, global_motion: bool = True, ensemble_global_motion: bool = False, variant: Optional[str] = None,
                  selections: Optional[Dict[str, bool]] = None):
@@ -228,21 +231,6 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
         self._init_runner()
         self._precision = "f16x3"
         self._checked = False                        # "f16x3-checked": the library build that counts out-of-range operands
-        # Kernel selections: every one of these has been "on" since round 2 and is bit-compatible with its alternative inside the
-        # parity budget (tests/test_gpu_e2e.py::test_fallback_kernel_selections_end_to_end runs each alternative).  They are plain
-        # attributes / constructor arguments (`Network(selections={"use_fused_stem": False})`), not environment variables: the
-        # product reads no environment variable.
-        self.use_plane_deconvs = True     # decoder deconvs from split planes
-        self.use_plane_convs = True       # 3x3 convs on split-plane input
-        self.use_unet_planes = True       # the refiner's strided convs on split planes
-        self.use_fused_stem = True        # the encoder's first three layers in one launch
-        self.use_fused_tail = True        # refine_head.1 folded into refine_head.0's epilogue
-        self.use_splitk = True            # split-K of under-filled long-K 3x3 launches
-        # independent branches of a forward on side streams (HipOps.branch).  OFF by default: bit-identical and planned
-        # like everything else, but not faster -- 256x256 860.7 -> 853.3 frames/s, 256x448 1062.6 -> 1063.0, 576x960 169.9 -> 170.7,
-        # 1088x1920 51.9 -> 52.0 (profiles/r05_lanes_ab.txt): what the overlapped launches save (~100 us of 1.2 ms at 256x256) the four
-        # cross-queue event waits of a forward cost again.  Independent FORWARDS on streams of their own do pay: host_io.PairStreams.
-        self.use_lanes = False
         self._prepared: Dict[str, object] = {}
         self._prepared_sig = None
         # Workspaces: one dict of named buffers per (device, input shape, mode) key, least recently used first.  The reference's
@@ -263,7 +251,8 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
         self._graphs: Dict[Tuple, Tuple] = {}
         self._graph_sig = None
         # launch plans (hip_ops.LaunchPlan): from the third forward with one (shape, mode, weights) key on, a forward is ONE
-        # atmvfi_plan_run call with fresh output tensors; enable_plans(False) turns it off
+        # atmvfi_plan_run call with fresh output tensors; enable_plans(False) or `Network(selections={"use_plans": False})` turns it
+        # off (a constructor argument, not an environment variable: the product reads no environment variable)
         self.use_plans = True
         self._plans: Dict[Tuple, object] = {}       # key -> LaunchPlan | int (eager forwards seen so far) | False (cannot be planned)
         self._plan_sig = None
@@ -386,12 +375,9 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
             self._ops_obj.gemm_workspace = self._gemm_scratch
         return self._ops_obj
 
-    def _gemm_scratch(self, floats: int) -> Optional[torch.Tensor]:
+    def _gemm_scratch(self, floats: int) -> torch.Tensor:
         """Split-K scratch of the plane-input GEMM (hip_ops.HipOps.gemm_workspace): workspace memory like every other buffer."""
-        if not self.use_splitk:
-            return None
-        lane = getattr(self._ops_obj, "lane", 0)          # (a branch on a side stream gets scratch of its own: HipOps.branch)
-        return self.buf("gemm_splitk_ws" if not lane else f"gemm_splitk_ws_l{lane}", floats)
+        return self.buf("gemm_splitk_ws", floats)
 
     def release_workspace(self):
         self._plans.clear()           # recorded plans and
@@ -554,7 +540,7 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
             wp = sd["proj.0.weight"].detach()
             wpp = torch.cat([wp[:, :w3], torch.zeros(wp.shape[0], gap, 3, 3, dtype=wp.dtype, device=wp.device), wp[:, w3:]], 1)
             P["pk:proj.0.weight:planes"] = ops.pack_weight(GEMM_CONV, wpp.contiguous())
-        if hasattr(ops, "pack_readout") and getattr(ops, "split_planes_ok", False) and self._v.refine_hidden in (32, 64):
+        if hasattr(ops, "pack_readout") and getattr(ops, "split_planes_ok", False):
             P["readout"] = ops.pack_readout(sd["refine_head.1.0.weight"].detach())
         if hasattr(ops, "pack_stem") and getattr(ops, "split_planes_ok", False):
             P["stem"] = ops.pack_stem(*(sd[f"feat_extracts.{a}.{b}"].detach() for a in ("0.0", "0.1", "1.0") for b in ("0.weight", "0.bias", "1.weight")))
@@ -588,7 +574,7 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
     def _plane_convs(self, ops) -> bool:
         """3x3 / stride-1 convs on the split-plane kernel (LDS-DMA halo, ping-pong wave groups): their inputs are written as
         split planes by the producing layer's sink, fp32 copies only where something other than a contraction reads them."""
-        return self._plane_deconvs(ops) and self.use_plane_convs and self._rows_fit_planes
+        return self._plane_deconvs(ops) and self._rows_fit_planes
 
     def _c3p(self, ops, P, p, xp, n, h, w, out=None, act=True, sink=None, sink_c0=0, sink_prelu=None, wkey=None, out_cmin=0, sink2=None):
         """conv()/Conv2d 3x3 s1 p1 of the reference on split-plane input ``xp`` ([n*h*w rows]); ``p`` = parameter prefix
@@ -598,19 +584,13 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
         else:
             wk, bias, prelu = wkey or f"pk:{p}.weight", P[f"{p}.bias"], None
         extra = {} if sink2 is None else {"planes2": sink2}
-        if self.use_splitk and hasattr(ops, "conv3x3_workspace_floats"):
-            # under-filled grids with long K (the motion MLPs of small frames): split K over the idle CUs; the scratch for the partial
-            # sums is workspace memory like every other buffer
-            need = ops.conv3x3_workspace_floats(n, h, w, P[wk].cin, P[wk].cout)
-            if need:
-                extra["workspace"] = self.buf("splitk_ws" if not getattr(ops, "lane", 0) else f"splitk_ws_l{ops.lane}", need)
+        # under-filled grids with long K (the motion MLPs of small frames): split K over the idle CUs; the scratch for the partial
+        # sums is workspace memory like every other buffer
+        need = ops.conv3x3_workspace_floats(n, h, w, P[wk].cin, P[wk].cout)
+        if need:
+            extra["workspace"] = self.buf("splitk_ws", need)
         ops.conv3x3_planes(xp, n, h, w, P[wk], out=out, bias=bias, prelu=prelu, planes=sink, planes_c0=sink_c0, planes_prelu=sink_prelu,
                            out_cmin=out_cmin, **extra)
-
-    def _conv_s2_sink(self, ops, P, p, x, sink, shape, out=None, sink_c0=0):
-        """conv() 3x3 stride 2 (+PReLU) on the fp32-input GEMM engine, result to a plane sink (and ``out`` if given)."""
-        ops.conv(x, P[f"pk:{p}.0.weight"], out, stride=2, pad=1, dil=1, bias=P[f"{p}.0.bias"], prelu=P[f"{p}.1.weight"],
-                 planes=sink, planes_c0=sink_c0, out_shape=shape)
 
     def _conv_p(self, ops, P, p, src: "_PMap", stride=1, pad=1, dil=1, act=True, out=None, sink=None, sink_c0=0, src2: "Optional[_PMap]" = None):
         """conv() / nn.Conv2d of the reference (any stride / dilation, k 1 or 3) on a split-plane map through the LDS-DMA GEMM."""
@@ -621,11 +601,6 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
         two = {} if src2 is None else {"x2": src2.p, "x2_chunk0": src2.chunk0, "split_chunks": src.c // 32}
         ops.conv_planes(src.p, src.n, src.h, src.w, P[wk], out=out, stride=stride, pad=pad, dil=dil, bias=bias, prelu=prelu, sink=sink,
                         sink_c0=sink_c0, in_chunk0=src.chunk0, **two)
-
-    def _plane_deconvs(self, ops) -> bool:
-        """Decoder deconvs on the LDS-DMA GEMM (operands as split planes) instead of the fp32-input engine."""
-        return (getattr(ops, "precision", None) == "f16x3" and getattr(ops, "split_planes_ok", False) and self.use_split_planes
-                and self.use_plane_deconvs)
 
     def _deconv_act(self, ops, P, p, x, out, in_prelu=None, split: Optional[str] = None, planes=None):
         """``planes``: the input rows already in split-plane form, through ``in_prelu`` (written by the producing 3x3 conv).
@@ -648,31 +623,20 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
         with s3 already written into fuse_l[..., -d3:] (network_base.py:342-352)."""
         d = self._v.hidden_dims
         f, h, w, _ = x0.shape
-        planes_path = self._plane_convs(ops) and min(d[1:]) >= 32 and (self._v.local_dim - d[3]) % 32 == 0
-        fused = planes_path and self.use_fused_stem and "stem" in P and x0.is_contiguous()
-        if not fused:
-            a = self.buf(f"{tag}e0a", f, h, w, d[0]); self._conv_act(ops, P, "feat_extracts.0.0", x0[..., :3], a)
-            e0 = self.buf(f"{tag}e0", f, h, w, d[0])
-        if planes_path:
+        if self._plane_convs(ops):
             # Stages 1-3 entirely in split planes: stride-2 conv (LDS-DMA GEMM, CONV mode) -> planes -> 3x3 conv (plane kernel) ->
             # planes; the last one writes s3 straight into the fusion buffer's planes.  No fp32 copy of e1, e2, s3 exists: their
             # only readers are contractions.
-            # (The first stride-2 conv, 24 -> 48 channels at full resolution, stays on the fp32-input engine: the LDS-DMA GEMM's
-            # 128-column tile is 62 % padding at N = 48 -- 0.40 ms against 0.33 -- and e0 exists in fp32 anyway.)
             # The full-resolution stem (3 -> d0 -> d0 -> d1 stride 2) is ONE launch whose two d0-channel maps stay in LDS
-            # (atmvfi_stem_fused); A/B: use_fused_stem = False runs the three layers one by one through fp32 maps in HBM.
-            if not fused:
-                self._conv_act(ops, P, "feat_extracts.0.1", a, e0)
+            # (atmvfi_stem_fused).
             ld = self._v.local_dim
             fuse_p = self.planes(f"{tag}fuse_l_p", f * (h // 8) * (w // 8), ld)
             src, outs = None, []
             for st in (1, 2, 3):
                 hs, ws = h >> st, w >> st
                 ap = self.planes(f"{tag}e{st}a_p", f * hs * ws, d[st])
-                if st == 1 and fused:
+                if st == 1:
                     ops.stem_fused(x0, P["stem"], ap)
-                elif st == 1:
-                    self._conv_s2_sink(ops, P, "feat_extracts.1.0", e0, ap, (f, hs, ws, d[1]))
                 else:
                     self._conv_p(ops, P, f"feat_extracts.{st}.0", src, stride=2, sink=ap)
                 if st == 3:
@@ -684,7 +648,8 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
                     outs.append(_PMap(ep, f, hs, ws, 0, d[st]))
                     src = outs[-1]
             return outs[0], outs[1], outs[2]
-        self._conv_act(ops, P, "feat_extracts.0.1", a, e0)
+        a = self.buf(f"{tag}e0a", f, h, w, d[0]); self._conv_act(ops, P, "feat_extracts.0.0", x0[..., :3], a)
+        e0 = self.buf(f"{tag}e0", f, h, w, d[0]); self._conv_act(ops, P, "feat_extracts.0.1", a, e0)
         a = self.buf(f"{tag}e1a", f, h // 2, w // 2, d[1]); self._conv_act(ops, P, "feat_extracts.1.0", e0, a, 2)
         e1 = self.buf(f"{tag}e1", f, h // 2, w // 2, d[1]); self._conv_act(ops, P, "feat_extracts.1.1", a, e1)
         a = self.buf(f"{tag}e2a", f, h // 4, w // 4, d[2]); self._conv_act(ops, P, "feat_extracts.2.0", e1, a, 2)
@@ -727,7 +692,7 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
         flat = buf.reshape(b * h * w, ld)[:, off:off + 2 * c]
         return flat.unflatten(1, (2, c)).permute(1, 0, 2)
 
-    def _motion_branch(self, ops, P, branch, mlp, x_tokens, b, h, w, ws, tag, mlp_lane=None):
+    def _motion_branch(self, ops, P, branch, mlp, x_tokens, b, h, w, ws, tag):
         """Two ATMFormer blocks + motion MLP (estimate_{local,global}_motion, network_base.py:367-415).
         Returns (mlp_in buffer, last hidden map) -- the caller runs the 1x1 head into its own slice."""
         c = x_tokens.shape[-1]
@@ -754,15 +719,8 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
                 ops.split_planes(flat[:, 0:8], mlp_in_p, c0=0)
             t1p = self.planes(f"{tag}mm1_p", b * h * w, hid)
             t2p = self.planes(f"{tag}mm2_p", b * h * w, hid)
-
-            def convs():
-                self._c3p(ops, P, f"{mlp}.0", mlp_in_p, b, h, w, sink=t1p)
-                self._c3p(ops, P, f"{mlp}.1", t1p, b, h, w, sink=t2p)
-            if mlp_lane is not None:
-                with ops.branch(mlp_lane):
-                    convs()
-            else:
-                convs()
+            self._c3p(ops, P, f"{mlp}.0", mlp_in_p, b, h, w, sink=t1p)
+            self._c3p(ops, P, f"{mlp}.1", t1p, b, h, w, sink=t2p)
             return mlp_in, t2p
         t1 = self.buf(f"{tag}mm1", b, h, w, hid); self._conv_act(ops, P, f"{mlp}.0", mlp_in, t1)
         t2 = self.buf(f"{tag}mm2", b, h, w, hid); self._conv_act(ops, P, f"{mlp}.1", t1, t2)
@@ -786,14 +744,9 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
         h_, w_ = h8 // 2, w8 // 2
         s3 = fuse_l[..., v.local_dim - d[3]:]
         fuse_g = self.buf(f"{tag}fuse_g", f, h_, w_, v.global_dim)
-        if self._plane_convs(ops):
-            ap = self.planes(f"{tag}ga_p", f * h_ * w_, v.last_feat_dim)
-            self._conv_s2_sink(ops, P, "last_feat_extract.0", s3, ap, (f, h_, w_, v.last_feat_dim))
-            self._c3p(ops, P, "last_feat_extract.1", ap, f, h_, w_, out=fuse_g[..., d[3] + 2 * d[2]:])
-        else:
-            a = self.buf(f"{tag}ga", f, h_, w_, v.last_feat_dim)
-            self._conv_act(ops, P, "last_feat_extract.0", s3, a, 2)
-            self._conv_act(ops, P, "last_feat_extract.1", a, fuse_g[..., d[3] + 2 * d[2]:])
+        a = self.buf(f"{tag}ga", f, h_, w_, v.last_feat_dim)
+        self._conv_act(ops, P, "last_feat_extract.0", s3, a, 2)
+        self._conv_act(ops, P, "last_feat_extract.1", a, fuse_g[..., d[3] + 2 * d[2]:])
         return self._fusion(ops, P, "global_feature_fusion", e2, s3, fuse_g, d[3], d[2], tag + "g")
 
     def _global_from_tokens(self, ops, P, tokens, b, h_, w_, tag):
@@ -816,10 +769,8 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
 
     def _head1x1(self, ops, P, p, t2, b, h, w, out):
         """The 1x1 head of a motion MLP (network_base.py:158,195): on the hidden map's planes when the branch left it there."""
-        if isinstance(t2, Planes) and P[f"pk:{p}.weight"].cout <= 8 and hasattr(ops, "head1x1_planes"):
+        if isinstance(t2, Planes):
             ops.head1x1_planes(t2, b, h, w, P[f"pk:{p}.weight"], out, bias=P[f"{p}.bias"])       # 5 channels: a lane per pixel, no GEMM tile
-        elif isinstance(t2, Planes):
-            ops.conv_planes(t2, b, h, w, P[f"pk:{p}.weight"], out=out, stride=1, pad=0, dil=1, bias=P[f"{p}.bias"])
         else:
             self._conv_plain(ops, P, p, t2, out, pad=0)
 
@@ -913,10 +864,9 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
 
     def _mode_key(self, ops, im0, im1) -> Tuple:
         return (tuple(im0.shape), tuple(im1.shape), str(im0.device), self.global_motion, self.ensemble_global_motion,
-                self._precision, self._checked, self.use_split_planes, self.use_plane_convs, self.use_unet_planes, self.use_plane_deconvs,
-                self.use_fused_stem, self.use_splitk, self.use_fused_tail, getattr(ops, "attention_f16x3", None), self.local_motion_args["window_size"],
+                self._precision, self._checked, getattr(ops, "attention_f16x3", None), self.local_motion_args["window_size"],
                 self.global_motion_args["window_size"], getattr(ops, "warp_tiles", None), getattr(ops, "conv3_instance", None),
-                getattr(ops, "gemm_tile_wn", None), self.use_lanes, self._workspace_key(im0))
+                getattr(ops, "gemm_tile_wn", None), self._workspace_key(im0))
 
     def forward(self, im0: torch.Tensor, im1: torch.Tensor, reuse_first: bool = False):
         self._reuse_first = bool(reuse_first)
@@ -952,9 +902,6 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
                 # differently aligned view takes the direct launches, which choose again
                 return self._forward_eager(im0, im1)
             self._select_workspace(key[-1])                  # replay counts as a use for the workspace LRU
-            if ent.n_lanes > 1:
-                ls, le = ops.lane_handles()
-                return ent.run((a, b), ops.device, ops._stream(), lane_streams=ls, lane_events=le)
             return ent.run((a, b), ops.device, ops._stream())
 
     @staticmethod
@@ -990,8 +937,7 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
         # for bit (the forward is run-to-run deterministic).  A pointer patched into the wrong slot, a missed patch or a launch that
         # was not recorded shows up here, before the plan ever serves a caller; such a shape stays on direct launches.
         with torch.cuda.device(a.device):
-            ls, le = ops.lane_handles() if plan.n_lanes > 1 else (None, None)
-            again = plan.run((a, b), ops.device, ops._stream(), poison=True, lane_streams=ls, lane_events=le)
+            again = plan.run((a, b), ops.device, ops._stream(), poison=True)
         if self._same_results(out, again):
             self._plans[key] = plan
         else:
@@ -1044,19 +990,11 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
                 return self._forward_on_device(ops, im0, im1)
         return self._forward_on_device(ops, im0, im1)
 
-    def _lanes_on(self, ops, b: int, H: int, W: int) -> bool:
-        """Independent branches of the forward on side streams (HipOps.branch)?  ``use_lanes``, except on the CPU test double and under
-        per-launch profiling (which times launches on one stream)."""
-        if not hasattr(ops, "branch") or getattr(ops, "profile", None) is not None:
-            return False
-        return bool(self.use_lanes)
-
     def _forward_on_device(self, ops, im0: torch.Tensor, im1: torch.Tensor):
         self._select_workspace(self._workspace_key(im0))
         if hasattr(ops, "begin_forward"):
             ops.begin_forward()
         b, _, H, W = im0.shape
-        lanes = self._lanes_on(ops, b, H, W)
         # the plane kernels address a chunk's pixel rows with 32-bit byte offsets (64 B per row): beyond 2^26 rows of the largest
         # map (2 B frames at full resolution; e.g. batch 8 at 4K) the forward takes the fp32-input kernels instead
         self._rows_fit_planes = 2 * b * H * W < (1 << 26)
@@ -1109,17 +1047,9 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
                     gtok[n_g:].copy_(g_one)
             else:
                 e1, e2, fuse_l = self._encoder(ops, P, x0, "")
-                if glob and lanes and isinstance(fuse_l, _PMap):
-                    # the global branch's per-frame half (last_feat_extract + global fusion: reads e2 and the s3 chunks of the fusion
-                    # planes, writes its own buffers) beside the local fusion (writes the OTHER chunks of those planes)
-                    with ops.branch(1):
-                        gtok = self._global_tokens(ops, P, e2, fuse_l, "")                                    # [2B*h_*w_, cg]
-                    feat = self._fusion(ops, P, "cross_scale_feature_fusion", e1, e2, fuse_l, d[2], d[1], "l")
-                    ops.join(1)
-                else:
-                    feat = self._fusion(ops, P, "cross_scale_feature_fusion", e1, e2, fuse_l, d[2], d[1], "l")   # [2B*h*w, C]
-                    if glob:
-                        gtok = self._global_tokens(ops, P, e2, fuse_l, "")                                    # [2B*h_*w_, cg]
+                feat = self._fusion(ops, P, "cross_scale_feature_fusion", e1, e2, fuse_l, d[2], d[1], "l")       # [2B*h*w, C]
+                if glob:
+                    gtok = self._global_tokens(ops, P, e2, fuse_l, "")                                        # [2B*h_*w_, cg]
             if cache_ok:
                 keep = self.buf("frame_cache_tokens", b * h * w, C)
                 keep.copy_(feat[b * h * w:])
@@ -1170,28 +1100,16 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
             dec_in = self.buf("dec_in", b, h, w, _r4(cdec))
             motion8 = dec_in[..., 2 * C:2 * C + 5]
             a, c, t = (ops.empty(b, 3, h, w) for _ in range(3))
-            # With lanes: the motion MLP (two 3x3 convs on the blocks' plane output), its 1x1 head and the H/8 synthesis run on lane 1
-            # beside the two feature-enhancement blocks (which read the blocks' fp32 output and write their own buffers); both meet
-            # at the warps of the enhanced features below.
             mlp_in, t2 = self._motion_branch(ops, P, "local_motion_atmformer", "local_motion_mlp", x_tokens, b, h, w,
-                                             self.local_motion_args["window_size"], "l", mlp_lane=1 if lanes else None)
-
-            def motion_tail():
-                self._head1x1(ops, P, "local_motion_mlp.2", t2, b, h, w, motion8)
-                ops.warp_blend(pyr0[3], pyr1[3], motion8, a, c, t)      # synthesis at H/8 (:496-506)
-            if lanes:
-                with ops.branch(1):
-                    motion_tail()
-            else:
-                motion_tail()
+                                             self.local_motion_args["window_size"], "l")
+            self._head1x1(ops, P, "local_motion_mlp.2", t2, b, h, w, motion8)
+            ops.warp_blend(pyr0[3], pyr1[3], motion8, a, c, t)          # synthesis at H/8 (:496-506)
             # feature enhancement (:493-494)
             x = self._stacked(mlp_in, 8, C)
             e_mid = self.buf("enh0", 2 * b * h * w, C)
             self._block(ops, P, "feat_enhance_transformer.0", x, 2 * b, h, w, 8, 0, False, e_mid, None, "e")
             enh = self.buf("enh1", 2 * b, h, w, C)
             self._block(ops, P, "feat_enhance_transformer.1", e_mid, 2 * b, h, w, 8, 4, False, enh.reshape(2 * b * h * w, C), None, "e")
-            if lanes:
-                ops.join(1)
             # warped features (:496-506)
             fl0 = motion8[..., 0:2].permute(0, 3, 1, 2)
             fl1 = motion8[..., 2:4].permute(0, 3, 1, 2)
@@ -1209,11 +1127,7 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
             x = dec_in[..., 0:cdec]
             flow0 = flow1 = m1 = m2 = None
             pd = self._plane_deconvs(ops)
-            pc = self._plane_convs(ops) and rh >= 32
-            # the refiner's strided convs on split planes too (ping-pong GEMM, CONV mode, two plane sources for the concats): the
-            # first source (feat) must end on a 32-channel chunk boundary; the second (dec[:, :w]) may end inside a chunk -- what
-            # follows there in the raw decoder planes (its flow / mask channels, then zeros) meets zero-padded weight channels
-            unet_p = pc and self.use_unet_planes and rh % 32 == 0
+            pc = self._plane_convs(ops)
             xp_next = None
             pack_c0 = (w3d + 5 + 7) // 8 * 8                                       # the 15 image channels inside the refiner's input planes
             rin_p = self.planes("refine_in_p", b * H * W, pack_c0 + 15) if pc else None
@@ -1236,21 +1150,17 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
                     t2p = self.planes(f"dec_t2_{st}_p", b * hs * wsz, cout)
                     self._c3p(ops, P, f"{pfx}.{o + 1}", t1p, b, hs, wsz, sink=t2p)
                     if st < 2:
+                        # the map goes on twice as planes -- through the next stage's leading PReLU (its deconv) and raw (the
+                        # U-Net's strided conv reads cat(feat, dec[:, :w]) from two plane buffers); fp32 only for the five
+                        # flow / mask channels that warp_blend reads
+                        # (in a compact 8-float-per-pixel buffer: as the tail of the skip buffer's 400-600-byte rows each
+                        # pixel's 20 bytes cost warp_blend a cache line of their own)
                         xp_next = self.planes(f"dec_xp_{st + 1}", b * hs * wsz, cout)
-                        if unet_p:
-                            # the map goes on twice as planes -- through the next stage's leading PReLU (its deconv) and raw (the
-                            # U-Net's strided conv reads cat(feat, dec[:, :w]) from two plane buffers); fp32 only for the five
-                            # flow / mask channels that warp_blend reads
-                            # (in a compact 8-float-per-pixel buffer: as the tail of the skip buffer's 400-600-byte rows each
-                            # pixel's 20 bytes cost warp_blend a cache line of their own)
-                            raw = self.planes(f"dec_raw_{st}", b * hs * wsz, cout)
-                            cmin = (cout - 5) // 4 * 4
-                            mot_c = self.buf(f"dec_mot_{st}", b, hs, wsz, 8)[..., :cout - cmin]
-                            self._c3p(ops, P, f"{pfx}.{o + 2}", t2p, b, hs, wsz, out=mot_c, act=False, sink=xp_next,
-                                      sink_prelu=P[f"inprelu:{st + 1}"], sink2=raw, out_cmin=cmin)
-                        else:
-                            self._c3p(ops, P, f"{pfx}.{o + 2}", t2p, b, hs, wsz, out=dsts[st], act=False, sink=xp_next,
-                                      sink_prelu=P[f"inprelu:{st + 1}"])
+                        raw = self.planes(f"dec_raw_{st}", b * hs * wsz, cout)
+                        cmin = (cout - 5) // 4 * 4
+                        mot_c = self.buf(f"dec_mot_{st}", b, hs, wsz, 8)[..., :cout - cmin]
+                        self._c3p(ops, P, f"{pfx}.{o + 2}", t2p, b, hs, wsz, out=mot_c, act=False, sink=xp_next,
+                                  sink_prelu=P[f"inprelu:{st + 1}"], sink2=raw, out_cmin=cmin)
                     else:
                         # finest level: only the five flow / mask channels are read in fp32 (by warp_blend); the features go on
                         # to the refiner as planes
@@ -1290,7 +1200,6 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
                     ops.warp_blend(pyr0[scale], pyr1[scale], mot, a, c, t)
                 w0_list.insert(0, a); w1_list.insert(0, c); it_list.insert(0, t)
             # residual refinement U-Net (:417-431)
-            r1 = None
             if pc:
                 h2, w2, h4, w4 = H // 2, W // 2, H // 4, W // 4
                 bufA_p = self.planes("bufA_p", b * H * W, 2 * rh)                  # [up3 out | feat0]
@@ -1298,26 +1207,17 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
                 bufC_p = self.planes("bufC_p", b * h4 * w4, 4 * rh)                # [up1 out | feat2]
                 d2a_p = self.planes("d2a_p", b * h4 * w4, 2 * rh)
                 d3a_p = self.planes("d3a_p", b * h * w, 4 * rh)
-                if unet_p:
-                    # feat0 / feat1 / feat2 exist as planes only (chunks of bufA_p / bufB_p / bufC_p): their readers are the strided
-                    # convs (CONV mode of the ping-pong GEMM) and the up-path's 3x3 convs
-                    self._c3p(ops, P, "proj", rin_p, b, H, W, sink=bufA_p, sink_c0=rh, wkey="pk:proj.0.weight:planes")
-                    self._conv_p(ops, P, "down1.0", _PMap(bufA_p, b, H, W, rh // 32, rh), stride=2, sink=bufB_p, sink_c0=rh)
-                    self._conv_p(ops, P, "down2.0", _PMap(bufB_p, b, h2, w2, rh // 32, rh), stride=2, sink=d2a_p,
-                                 src2=_PMap(self.planes("dec_raw_1", b * h2 * w2, w2d + 5), b, h2, w2, 0, w2d))
-                    self._c3p(ops, P, "down2.1", d2a_p, b, h4, w4, sink=bufC_p, sink_c0=2 * rh)
-                    self._conv_p(ops, P, "down3.0", _PMap(bufC_p, b, h4, w4, 2 * rh // 32, 2 * rh), stride=2, sink=d3a_p,
-                                 src2=_PMap(self.planes("dec_raw_0", b * h4 * w4, w1d + 5), b, h4, w4, 0, w1d))
-                else:
-                    feat0 = bufA[..., rh:2 * rh]
-                    self._c3p(ops, P, "proj", rin_p, b, H, W, out=feat0, sink=bufA_p, sink_c0=rh, wkey="pk:proj.0.weight:planes")
-                    feat1 = bufB[..., rh:2 * rh]
-                    # (64 -> 64 at full resolution: too narrow for the LDS-DMA GEMM's 128-column tile, see _encoder)
-                    self._conv_s2_sink(ops, P, "down1.0", feat0, bufB_p, (b, h2, w2, rh), out=feat1, sink_c0=rh)
-                    self._conv_s2_sink(ops, P, "down2.0", bufB[..., rh:2 * rh + w2d], d2a_p, (b, h4, w4, 2 * rh))
-                    feat2 = bufC[..., 2 * rh:4 * rh]
-                    self._c3p(ops, P, "down2.1", d2a_p, b, h4, w4, out=feat2, sink=bufC_p, sink_c0=2 * rh)
-                    self._conv_s2_sink(ops, P, "down3.0", bufC[..., 2 * rh:4 * rh + w1d], d3a_p, (b, h, w, 4 * rh))
+                # feat0 / feat1 / feat2 exist as planes only (chunks of bufA_p / bufB_p / bufC_p): their readers are the strided
+                # convs (CONV mode of the ping-pong GEMM, two plane sources for the concats) and the up-path's 3x3 convs.  The first
+                # source (feat) ends on a 32-channel chunk boundary; the second (dec[:, :w]) may end inside a chunk -- what follows
+                # there in the raw decoder planes (its flow / mask channels, then zeros) meets zero-padded weight channels
+                self._c3p(ops, P, "proj", rin_p, b, H, W, sink=bufA_p, sink_c0=rh, wkey="pk:proj.0.weight:planes")
+                self._conv_p(ops, P, "down1.0", _PMap(bufA_p, b, H, W, rh // 32, rh), stride=2, sink=bufB_p, sink_c0=rh)
+                self._conv_p(ops, P, "down2.0", _PMap(bufB_p, b, h2, w2, rh // 32, rh), stride=2, sink=d2a_p,
+                             src2=_PMap(self.planes("dec_raw_1", b * h2 * w2, w2d + 5), b, h2, w2, 0, w2d))
+                self._c3p(ops, P, "down2.1", d2a_p, b, h4, w4, sink=bufC_p, sink_c0=2 * rh)
+                self._conv_p(ops, P, "down3.0", _PMap(bufC_p, b, h4, w4, 2 * rh // 32, 2 * rh), stride=2, sink=d3a_p,
+                             src2=_PMap(self.planes("dec_raw_0", b * h4 * w4, w1d + 5), b, h4, w4, 0, w1d))
                 d3b_p = self.planes("d3b_p", b * h * w, 4 * rh)
                 self._c3p(ops, P, "down3.1", d3a_p, b, h, w, sink=d3b_p)
                 d3c_p = self.planes("d3c_p", b * h * w, 4 * rh)
@@ -1332,19 +1232,15 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
                 self._c3p(ops, P, "up2.1", u2a_p, b, h2, w2, sink=bufB_p, sink_c0=0)
                 ops.deconv(None, P["pk:up3.0.0.weight"], None, bias=P["up3.0.0.bias"], prelu=P["up3.0.1.weight"], planes=bufB_p, sink=bufA_p,
                            in_shape=(b, h2, w2, 2 * rh))
-                fused_tail = self.use_fused_tail and "readout" in P and hasattr(ops, "conv3x3_planes_readout")
-                if fused_tail:
-                    # refine_head.0 -> refine_head.1 -> 2 sigmoid - 1 -> += -> clamp in two launches; the 64-channel full-resolution
-                    # map r1 never reaches HBM: the first launch leaves 27 "tap contributions" per pixel, the second adds the nine
-                    # shifted ones of every output pixel (include/atmvfi.h, atmvfi_conv3x3_planes_readout)
-                    contrib = self.buf("tail_contrib", 27, b * H * W)
-                    ops.conv3x3_planes_readout(bufA_p, b, H, W, P["pk:refine_head.0.0.weight"], P["refine_head.0.0.bias"],
-                                               P["refine_head.0.1.weight"], P["readout"], contrib)
-                else:
-                    r1 = self.buf("r1", b, H, W, rh)
-                    self._c3p(ops, P, "refine_head.0", bufA_p, b, H, W, out=r1)
+                # refine_head.0 -> refine_head.1 -> 2 sigmoid - 1 -> += -> clamp in two launches; the 64-channel full-resolution
+                # map r1 never reaches HBM: the first launch leaves 27 "tap contributions" per pixel, the second adds the nine
+                # shifted ones of every output pixel (include/atmvfi.h, atmvfi_conv3x3_planes_readout)
+                contrib = self.buf("tail_contrib", 27, b * H * W)
+                ops.conv3x3_planes_readout(bufA_p, b, H, W, P["pk:refine_head.0.0.weight"], P["refine_head.0.0.bias"],
+                                           P["refine_head.0.1.weight"], P["readout"], contrib)
+                it_sum, it_final = ops.empty(b, 3, H, W), ops.empty(b, 3, H, W)
+                ops.refine_tail(contrib, P["refine_head.1.0.bias"], P["refine_head.1.1.weight"], it_list[0], it_sum, it_final)
             else:
-                fused_tail = False
                 r1 = self.buf("r1", b, H, W, rh)
                 feat0 = bufA[..., rh:2 * rh]; self._conv_act(ops, P, "proj", rin, feat0)
                 feat1 = bufB[..., rh:2 * rh]; self._conv_act(ops, P, "down1.0", feat0, feat1, 2)
@@ -1359,10 +1255,7 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
                 self._conv_act(ops, P, "up2.1", u2a, bufB[..., 0:rh])
                 self._deconv_act(ops, P, "up3.0", bufB[..., 0:2 * rh], bufA[..., 0:rh])
                 self._conv_act(ops, P, "refine_head.0", bufA, r1)
-            it_sum, it_final = ops.empty(b, 3, H, W), ops.empty(b, 3, H, W)
-            if fused_tail:
-                ops.refine_tail(contrib, P["refine_head.1.0.bias"], P["refine_head.1.1.weight"], it_list[0], it_sum, it_final)
-            else:
+                it_sum, it_final = ops.empty(b, 3, H, W), ops.empty(b, 3, H, W)
                 r = self.buf("r", b, H, W, 4); self._conv_act(ops, P, "refine_head.1", r1, r[..., :3])
                 ops.final_residual(it_list[0], r[..., :3], it_sum, it_final)
             i_t_0, i_t_1 = w0_list[0], w1_list[0]

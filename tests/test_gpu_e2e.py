@@ -271,11 +271,10 @@ def test_exact_fp32_engine_end_to_end(dev, weights):
 
 
 @pytest.mark.parametrize("variant,name", [("base", "base_128x192_g"), ("lite", "lite_128x192_g_b2")])
-def test_fallback_kernel_selections_end_to_end(variant, name, dev, weights):
-    """The forward's kernel selections other than the default one, each against the reference's outputs: (1) what a batch beyond
-    2^26 plane rows takes (`Network._rows_fit_planes` False: 3x3 convs and deconvs on the fp32-input kernels -- batch 4 at 4K), (2) every
-    split-plane switch off (the round-1 forward: fp32 maps between all layers), (3) the three stem layers as separate launches,
-    (4) launch plans off.  All within the parity budget of the golden fixture and within 2e-4 of the default selection."""
+def test_fp32_input_path_and_direct_launches_end_to_end(variant, name, dev, weights):
+    """The forward's paths other than the default one, each against the reference's outputs: (1) what a batch beyond 2^26 plane
+    rows takes (`Network._rows_fit_planes` False: 3x3 convs and deconvs on the fp32-input kernels -- batch 4 at 4K), (2) launch plans
+    off (direct launches).  All within the parity budget of the golden fixture and within 2e-4 of the default selection."""
     cases = [c for c in G.e2e_cases() if c["name"] == name]
     if not cases:
         pytest.skip(f"no fixture {name}")
@@ -307,25 +306,10 @@ def test_fallback_kernel_selections_end_to_end(variant, name, dev, weights):
         check("rows beyond 2^26 (fp32-input 3x3 kernels)")
     finally:
         cls._plane_convs = orig
-    # (2) every plane switch off
-    saved = (net.use_plane_convs, net.use_plane_deconvs, net.use_unet_planes, net.use_split_planes)
-    net.use_plane_convs = net.use_plane_deconvs = net.use_unet_planes = net.use_split_planes = False
-    check("all split-plane paths off")
-    net.use_plane_convs, net.use_plane_deconvs, net.use_unet_planes, net.use_split_planes = saved
-    # (3) separate stem launches, (4) no plans
-    net.use_fused_stem = False
-    check("stem as three launches")
-    net.use_fused_stem = True
+    # (2) no plans
     net.enable_plans(False)
     check("launch plans off")
     net.enable_plans(True)
-    # (5) the refiner's tail as three launches, (6) no split-K
-    net.use_fused_tail = False
-    check("refine_head.1 as its own launch")
-    net.use_fused_tail = True
-    net.use_splitk = False
-    check("split-K off")
-    net.use_splitk = True
     check("default again")
 
 
@@ -776,34 +760,6 @@ def test_launch_plan_equals_direct_launches_at_1080p_base(dev, weights):
     torch.cuda.empty_cache()
 
 
-def test_lanes_equal_single_stream(dev, weights):
-    """Branches of the forward on side streams (HipOps.branch / join, atmvfi_plan_run_lanes): the same kernels
-    in a partial order -- bit for bit the single-stream forward, on direct launches and replayed from a launch plan, for both variants,
-    global branch on and off, batch 1 and 2, call after call (a race between concurrent branches would show as a run-to-run difference)."""
-    for variant, cls, (bsz, H, W), glob in (("lite", pkg.NetworkLite, (1, 256, 256), True), ("lite", pkg.NetworkLite, (2, 256, 448), False),
-                                            ("base", pkg.NetworkBase, (1, 192, 320), True), ("base", pkg.NetworkBase, (1, 576, 960), True)):
-        net = cls()
-        net.load_state_dict(weights(variant), strict=True)
-        net.global_motion = glob
-        net.to(dev).eval()
-        p0 = [t.to(dev) for t in pairs.random_pair(bsz, H, W, seed=11)]
-        p1 = [t.to(dev) for t in pairs.smooth_pair(bsz, H, W, seed=12)]
-        net.use_lanes = False
-        net.enable_plans(False)
-        want = [[t.clone() for t in _flat(net(*p))] for p in (p0, p1)]
-        net.use_lanes = True
-        for plans in (False, True):
-            net.enable_plans(plans)
-            for rep in range(5):
-                for p, w in zip((p0, p1), want):
-                    for t, r in zip(_flat(net(*p)), w):
-                        assert torch.equal(t, r), (variant, H, W, plans, rep)
-        recorded = [p for p in net._plans.values() if not isinstance(p, (int, bool))]
-        assert recorded and all(p.n_lanes == 2 and p.n_events >= (4 if glob else 2) for p in recorded)
-        net.release_workspace()
-    torch.cuda.empty_cache()
-
-
 def test_pair_streams_equal_single_stream(dev, weights):
     """host_io.PairStreams: K replicas (Network.replica(): shared parameters and packed weights, own
     workspace + launch plan) on K streams, pairs round-robin, no cross-stream event inside a forward.  Every output of every pair is
@@ -909,30 +865,6 @@ def test_deepcopy_of_a_used_model_is_standalone(dev, weights):
     with torch.no_grad():
         dict(twin.named_parameters())["refine_head.1.0.bias"].add_(0.5)          # the copies do not share storage
     assert not torch.equal(twin(a, b)["I_t"], want) and torch.equal(net(a, b)["I_t"], want)
-
-
-def test_lanes_on_a_fresh_workspace(dev, weights):
-    """the FIRST forward of a shape with lanes on creates workspace inside a branch body (the global branch's plane
-    buffers are zero-filled by torch on their first use).  That fill must be ordered with the lane's kernels -- the result of a
-    lanes-first model equals the single-stream model's bit for bit, first call included, and again after release_workspace()."""
-    for variant, cls, (H, W) in (("lite", pkg.NetworkLite, (256, 256)), ("base", pkg.NetworkBase, (192, 320))):
-        p0 = [t.to(dev) for t in pairs.random_pair(1, H, W, seed=21)]
-        ref_net = cls()
-        ref_net.load_state_dict(weights(variant), strict=True)
-        ref_net.to(dev).eval()
-        ref_net.use_lanes = False
-        want = [t.clone() for t in _flat(ref_net(*p0))]
-        ref_net.release_workspace()
-        net = cls()
-        net.load_state_dict(weights(variant), strict=True)
-        net.to(dev).eval()
-        net.use_lanes = True
-        for rep in range(3):
-            for call in range(4):                       # first call builds the workspace inside the branches; the third records
-                for t, r in zip(_flat(net(*p0)), want):
-                    assert torch.equal(t, r), (variant, rep, call)
-            net.release_workspace()
-    torch.cuda.empty_cache()
 
 
 def test_library_that_ran_is_built_from_these_sources(dev):

@@ -310,19 +310,23 @@ def test_product_library_reads_no_environment():
     assert not re.search(r"atmvfi_\w*set_(schedule|tile_width)", defd)
 
 
-def test_product_package_reads_no_environment_and_selections_are_arguments():
-    """the kernel-selection switches are attributes / constructor arguments, not ATMVFI_* environment
-    variables -- no module of the package touches os.environ."""
+def test_product_package_reads_no_environment_and_plans_are_the_only_selection():
+    """the kernel selection (launch plans, the only one) is an attribute / constructor argument, not an
+    ATMVFI_* environment variable -- no module of the package touches os.environ."""
     pkg_dir = os.path.join(ROOT, "atm-vfi_amd")
     for fn in sorted(os.listdir(pkg_dir)):
         if fn.endswith(".py"):
             src = open(os.path.join(pkg_dir, fn)).read()
             assert "os.environ" not in src and "getenv" not in src, f"{fn} reads the environment"
-    net = pkg.NetworkLite(selections={"use_fused_stem": False, "use_plans": False})
-    assert net.use_fused_stem is False and net.use_plans is False and net.use_plane_convs is True and net.use_lanes is False
+    assert pkg.NetworkLite.SELECTIONS == ("use_plans",)
+    net = pkg.NetworkLite(selections={"use_plans": False})
+    assert net.use_plans is False and pkg.NetworkLite().use_plans is True
     assert all(hasattr(net, name) for name in net.SELECTIONS)
-    with pytest.raises(ValueError):
-        pkg.NetworkLite(selections={"use_magic": True})
+    # the A/B switches of earlier rounds are gone with their paths: naming one is an error, not a silent no-op
+    for name in ("use_magic", "use_split_planes", "use_plane_deconvs", "use_plane_convs", "use_unet_planes", "use_fused_stem",
+                 "use_fused_tail", "use_splitk", "use_lanes"):
+        with pytest.raises(ValueError):
+            pkg.NetworkLite(selections={name: True})
     assert pkg.NetworkBase(global_motion=False).global_motion is False       # the reference's positional / keyword arguments unchanged
 
 
@@ -643,7 +647,7 @@ def test_plan_dispatch_is_generated_from_the_header():
     assert r.returncode == 0, r.stdout + r.stderr
 
 
-def test_plan_run_patches_dispatches_and_reports_the_failing_op():
+def test_plan_run_on_one_stream_patches_dispatches_and_reports_the_failing_op():
     """atmvfi_plan_run on the CPU box: no launch happens -- the ops below fail their entry point's host-side validation, which is
     exactly what a direct call reports -- but ids, argument counts, slot patching and the failing-op index are all exercised."""
     lib = hip_ops.load_library()
@@ -675,26 +679,6 @@ def test_plan_run_patches_dispatches_and_reports_the_failing_op():
     assert lib.atmvfi_plan_run(ops, 1, None, 0, None, 0, ctypes.byref(failed), None) != 0
     patches[0].slot = 7
     assert lib.atmvfi_plan_run(ops, 2, patches, 1, slots, 2, ctypes.byref(failed), None) != 0 and b"out of range" in lib.atmvfi_last_error()
-    # atmvfi_plan_run_lanes: an op on a lane without a stream, a synchronisation op without / outside the event table and a stream
-    # table of length zero are refused with the op's index before anything is issued; the recorder's LaunchPlan keeps lanes and events
-    ops[0].fn, ops[0].nargs = fid, 6
-    lanes = (ctypes.c_int32 * 2)(0, 3)
-    streams = (ctypes.c_void_p * 1)(None)
-    rc = lib.atmvfi_plan_run_lanes(ops, 2, lanes, None, 0, None, 0, ctypes.byref(failed), streams, 1, None, 0)
-    assert rc != 0 and failed.value == 0                     # op 0 itself: B = 0 is the entry point's EINVAL, on lane 0
-    ops[0].fn, ops[0].nargs = hip_ops.PLAN_RECORD, 1
-    ops[0].a[0].i = 0
-    assert lib.atmvfi_plan_run_lanes(ops, 2, lanes, None, 0, None, 0, ctypes.byref(failed), streams, 1, None, 0) != 0 and failed.value == 0
-    assert b"event" in lib.atmvfi_last_error()
-    ops[0].fn, ops[0].nargs = fid, 6
-    lanes[0] = 1
-    assert lib.atmvfi_plan_run_lanes(ops, 2, lanes, None, 0, None, 0, ctypes.byref(failed), streams, 1, None, 0) != 0 and failed.value == 0
-    assert b"lane" in lib.atmvfi_last_error()
-    assert lib.atmvfi_plan_run_lanes(ops, 2, lanes, None, 0, None, 0, ctypes.byref(failed), None, 0, None, 0) != 0
-    plan = hip_ops.LaunchPlan(lib, ())
-    plan.add_sync(hip_ops.PLAN_RECORD, 0, 0)
-    plan.add_sync(hip_ops.PLAN_WAIT, 0, 1)
-    assert plan.lanes == [0, 1] and plan.n_events == 1 and [k for k, _ in plan.ops_list] == [hip_ops.PLAN_RECORD, hip_ops.PLAN_WAIT]
 
 
 def test_launch_plan_recorder_on_the_host():

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Same-process A/B of one host-side switch of Network (an attribute, e.g. use_splitk) on BASELINE.json's configurations: interleaved
-rounds, launch plans on.   python tools/switch_ab.py use_splitk c1,c2,c3 [steps]"""
+"""Same-process A/B of one host-side switch of Network (an attribute, e.g. use_plans or use_graphs) on BASELINE.json's configurations:
+interleaved rounds, launch plans on unless they are the switch.   python tools/switch_ab.py use_plans c1,c2,c3 [steps]"""
 import importlib, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
