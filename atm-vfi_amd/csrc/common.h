@@ -80,8 +80,8 @@ __device__ __forceinline__ void fp16_saturate_on() { asm volatile("s_setreg_imm3
 #ifdef ATMVFI_RANGE_CHECK
 // The CHECKED build (libatmvfi_hip_checked.so, `make checked`; Network.set_precision("f16x3-checked")): every activation that is
 // split counts, in a device word the caller attached (atmvfi_range_word_set), when its hi half comes out at the fp16 limit or
-// non-finite -- |x| >= 65488 (rounds or saturates to 65504), inf, NaN -- i.e. when the f16x3 engines' operand range contract
-// (deviation 2) is violated and the result silently differs from the fp32 reference.  One device variable
+// non-finite -- |x| > 65488 (rounds or saturates to 65504; 65488 itself is a tie that rounds to even, 65472), inf, NaN -- i.e.
+// when the f16x3 engines' operand range contract (deviation 2) is violated and the result silently differs from the fp32 reference.  One device variable
 // and one setter per translation unit (the library is not linked with relocatable device code); the default build has neither.
 namespace atmvfi {
 typedef int (*RangeWordSetter)(unsigned*, hipStream_t);

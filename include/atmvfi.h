@@ -46,7 +46,7 @@ const char* atmvfi_source_digest(void);
 /* The f16x3 engines' operand range contract at run time.  Contraction operands are split as x = hi + lo'/1024 in fp16: |x| beyond
  * 65504 saturates silently (finite, but no longer what the fp32 reference computes).  The CHECKED build of this library
  * (libatmvfi_hip_checked.so: the same sources with -DATMVFI_RANGE_CHECK, `make checked`) counts, in a device word the caller
- * attaches, every pair of activations whose split produced a hi half at the fp16 limit or non-finite (|x| >= 65488, inf, NaN) --
+ * attaches, every pair of activations whose split produced a hi half at the fp16 limit or non-finite (|x| > 65488, inf, NaN) --
  * at every place an activation is split: the plane sinks of all producers and the in-kernel operand splits.  `word`: a zeroed
  * device uint32 that must outlive the launches (NULL detaches); attached for the CURRENT device, ordered on `stream`.
  * atmvfi_range_checked(): 1 in the checked build, 0 in the default one, where atmvfi_range_word_set fails with ATMVFI_EINVAL
