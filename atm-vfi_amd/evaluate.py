@@ -1,10 +1,15 @@
 """Benchmark evaluation loops of the reference's scripts (benchmark/test_vimeo90k.py, test_ucf101.py, test_snufilm.py) on top of the
 HIP hot path: dataset listers that read only files on disk, and ``evaluate`` -- PNG decode on a bounded thread pool, uint8 upload,
 ``frame_u8_to_f32`` (+ InputPadder replicate padding), the forward (flip-TTA optional, K forwards in flight optional) and the fused
-metric kernel on the uint8 ground truth and the un-padded prediction view.  Per-sample values stay on the device until the end."""
+metric kernel on the uint8 ground truth and the un-padded prediction view.  Per-sample values stay on the device until the end.
+
+``evaluate_xiph`` is the fourth script (benchmark/test_xiph.py, 4096 x 2160 frames scored as "resized-2k" and "cropped-4k"): every PNG
+is decoded and uploaded once, and every network input and ground truth of both categories is cut from the resident uint8 frame by
+``frame_u8_window`` on the GPU."""
 from __future__ import annotations
 
 import os
+import time
 from concurrent.futures import ThreadPoolExecutor
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional
@@ -17,6 +22,8 @@ from .metrics import PROTOCOLS, Protocol  # noqa: F401
 
 SNU_LEVELS = ("test-easy", "test-medium", "test-hard", "test-extreme")
 SNU_PREFIX = "data/SNU-FILM/test/"
+XIPH_CLIPS = ("BoxingPractice", "Crosswalk", "DrivingPOV", "FoodMarket", "FoodMarket2", "RitualDance", "SquareAndTimelapse", "Tango")
+XIPH_CATEGORIES = ("resized-2k", "cropped-4k")
 
 
 @dataclass(frozen=True)
@@ -62,6 +69,22 @@ def snufilm(path: str, img_data_path: str) -> List[Sample]:
                     continue
                 fr = tuple(os.path.join(path, p) for p in parts[:3])
                 out.append(Sample(parts[1], level, fr))
+    return out
+
+
+def xiph(path: str, clips=XIPH_CLIPS, frames=range(2, 99, 2)) -> List[Sample]:
+    """One sample per (clip, middle frame n): <path>/<clip>/<n-1:03d>.png, <n:03d>.png, <n+1:03d>.png as (first, ground truth, last)
+    (test_xiph.py:107-113), clip-major; both categories are cut from these same frames, so ``level`` is just "xiph".  Reads only the
+    disk (the script's download step is not reproduced); a missing file raises FileNotFoundError naming it."""
+    out = []
+    for clip in clips:
+        d = os.path.join(path, clip)
+        for n in frames:
+            fr = tuple(os.path.join(d, f"{k:03d}.png") for k in (n - 1, n, n + 1))
+            for q in fr:
+                if not os.path.isfile(q):
+                    raise FileNotFoundError(f"Xiph frame {q} is missing")
+            out.append(Sample(f"{clip}/{n:03d}", "xiph", fr))
     return out
 
 
@@ -130,10 +153,7 @@ def evaluate(model, samples, protocol, *, tta: bool = False, streams: int = 1, l
                 frames = futs.pop(i).result()
                 if i + window < n:
                     futs[i + window] = pool.submit(lambda s: tuple(read_rgb(q) for q in s.frames), samples[i + window])
-                im0, im1 = upload(i, frames)
-                yield im0, im1
-                if tta:
-                    yield im0.flip(2).flip(3).contiguous(), im1.flip(2).flip(3).contiguous()
+                yield upload(i, frames)
 
     def score(i, pred):
         padder = padders.pop(i)
@@ -146,33 +166,191 @@ def evaluate(model, samples, protocol, *, tta: bool = False, streams: int = 1, l
             r = raw[:i + 1].cpu()
             progress(i + 1, n, float(np.mean([metrics.psnr_from_mse(v) for v in r[:, 2].tolist()])), float(r[:, 0].mean()))
 
-    def outputs():
-        if streams > 1:
-            with host_io.PairStreams(model, streams) as ps:
-                yield from (o["I_t"] for o in ps.map(pairs()))
-        else:
-            for a, b in pairs():
-                yield model.forward(a, b)["I_t"]
-
-    it = outputs()
-    for i in range(n):
-        pred = next(it)
-        if tta:
-            pred = (pred + next(it).flip(2).flip(3)) / 2
+    for i, pred in enumerate(_predictions(model, pairs(), tta, streams)):
         score(i, pred)
-    for _ in it:        # close the generator (releases the streams)
-        pass
 
     vals = raw[:n].cpu().numpy()
     records = [{"name": s.name, "level": s.level, "psnr": metrics.psnr_from_mse(float(v[2])), "ssim": float(v[0])}
                for s, v in zip(samples, vals)]
+    return EvalResult(records, _level_means(records), preds)
+
+
+def _predictions(model, pairs, tta: bool, streams: int, timings: Optional[dict] = None):
+    """``I_t`` of every (im0, im1) of ``pairs``, in order: flip-TTA as the scripts do it (the average with the un-flipped forward of the
+    flipped pair), ``streams`` > 1 through ``host_io.PairStreams``.  ``timings``: adds the forwards' seconds (one stream only; it
+    synchronises around each forward)."""
+    def fed():
+        for im0, im1 in pairs:
+            yield im0, im1
+            if tta:
+                yield im0.flip(2).flip(3).contiguous(), im1.flip(2).flip(3).contiguous()
+
+    def outputs():
+        if streams > 1:
+            with host_io.PairStreams(model, streams) as ps:
+                yield from (o["I_t"] for o in ps.map(fed()))
+        else:
+            for a, b in fed():
+                if timings is None:
+                    yield model.forward(a, b)["I_t"]
+                    continue
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                out = model.forward(a, b)["I_t"]
+                torch.cuda.synchronize()
+                timings["forward"] = timings.get("forward", 0.0) + time.perf_counter() - t0
+                yield out
+
+    it = outputs()
+    for pred in it:         # (exhausting the generator releases the streams)
+        if tta:
+            pred = (pred + next(it).flip(2).flip(3)) / 2
+        yield pred
+
+
+def _level_means(records) -> Dict[str, dict]:
     levels: Dict[str, dict] = {}
     for r in records:
         lv = levels.setdefault(r["level"], {"psnr": [], "ssim": []})
         lv["psnr"].append(r["psnr"])
         lv["ssim"].append(r["ssim"])
-    levels = {k: {"psnr": float(np.mean(v["psnr"])), "ssim": float(np.mean(v["ssim"])), "n": len(v["psnr"])} for k, v in levels.items()}
-    return EvalResult(records, levels, preds)
+    return {k: {"psnr": float(np.mean(v["psnr"])), "ssim": float(np.mean(v["ssim"])), "n": len(v["psnr"])} for k, v in levels.items()}
+
+
+def xiph_geometry(height: int, width: int, category: str):
+    """(mode, y0, x0, h, w) of ``frame_u8_window`` for one category on H x W frames: "resized-2k" = the whole frame reduced 2x
+    (cv2.resize to (W/2, H/2), INTER_AREA), "cropped-4k" = rows [H/4, H - H/4), columns [W/4, W - W/4).  For 2160 x 4096 these are the
+    script's dsize=(2048, 1080) and [540:-540, 1024:-1024]."""
+    if height <= 0 or width <= 0 or height % 4 or width % 4:
+        raise ValueError(f"Xiph frames must have H % 4 == 0 and W % 4 == 0 (the 2x resize and the centre crop are exact then), got {height}x{width}")
+    if category == "resized-2k":
+        return 1, 0, 0, height // 2, width // 2
+    if category == "cropped-4k":
+        return 0, height // 4, width // 4, height - 2 * (height // 4), width - 2 * (width // 4)
+    raise ValueError(f"unknown Xiph category {category!r} (known: {', '.join(XIPH_CATEGORIES)})")
+
+
+def evaluate_xiph(model, path: str, *, categories=XIPH_CATEGORIES, clips=XIPH_CLIPS, frames=range(2, 99, 2), tta: bool = False,
+                  streams: int = 1, limit: Optional[int] = None, keep_predictions: bool = False, global_motion: Optional[bool] = None,
+                  progress=None, decode_workers: int = 8, timings: Optional[dict] = None) -> EvalResult:
+    """benchmark/test_xiph.py on the HIP hot path: ``model`` scored on the triplets of ``xiph(path, clips, frames)`` under
+    ``metrics.XIPH``, once per category (calculate_psnr / calculate_ssim on frames in [0, 1]: the script detects SSIM's value range on the
+    prediction, the metric kernel on the ground truth; both lie in [0, 1], so L = 1 either way).  ``levels`` is keyed by category;
+    ``records`` (and ``predictions``) come category-major, then clip, then frame, as the script walks them; ``limit`` counts triplets
+    per category.
+
+    The work is done triplet-major: every PNG is decoded once and uploaded once however many triplets and categories use it, and at
+    most the three uint8 frames of the current triplet are resident (a frame is dropped after its last use; decoded frames wait on the
+    host, ``decode_workers`` + 3 at most).  Inputs and ground truths come from ``frame_u8_window`` alone -- mode 1 on the whole frame
+    for "resized-2k", mode 0 on the centre window for "cropped-4k" -- the ground truth as its uint8 output, which the metric kernel
+    reads in place.  ``tta``, ``streams``, ``keep_predictions``, ``global_motion`` as in ``evaluate``; ``progress`` is called after
+    every 100 forwards with (done, total, running psnr, running ssim) over what has been scored.
+    ``timings``: a dict that receives the seconds spent in decode_wait (this thread blocked on the decoders), decode_cpu (summed over
+    the decoder threads), upload, prepare, forward and metric; it synchronises after every stage, so use it with ``streams`` = 1."""
+    p = metrics.XIPH
+    ops, dev = host_io._hip_ops_of(model)
+    if ops is None:
+        raise RuntimeError("evaluate_xiph needs an atm-vfi_amd Network on the GPU (model.to('cuda'))")
+    categories = tuple(categories)
+    for c in categories:
+        if c not in XIPH_CATEGORIES:
+            raise ValueError(f"unknown Xiph category {c!r} (known: {', '.join(XIPH_CATEGORIES)})")
+    samples = xiph(path, clips, frames)
+    samples = samples[:limit] if limit is not None else samples
+    n, nc = len(samples), len(categories)
+    model.global_motion = p.global_motion if global_motion is None else bool(global_motion)
+    raw = torch.zeros(max(n * nc, 1), 3, dtype=torch.float64, device=dev)        # (ssim, cs, mse), row = category * n + triplet
+    preds: Optional[List[Optional[torch.Tensor]]] = [None] * (n * nc) if keep_predictions else None
+    gts: Dict[int, torch.Tensor] = {}
+    padders: Dict[int, host_io.InputPadder] = {}
+    order: List[str] = []                      # the distinct files in order of first use, and how many triplets use each
+    uses: Dict[str, int] = {}
+    for s in samples:
+        for q in s.frames:
+            if q not in uses:
+                order.append(q)
+            uses[q] = uses.get(q, 0) + 1
+
+    def clock(key, t0):
+        if timings is not None:
+            torch.cuda.synchronize()
+            timings[key] = timings.get(key, 0.0) + time.perf_counter() - t0
+
+    def decode(q):
+        t0 = time.perf_counter()
+        fr = read_rgb(q)
+        return fr, time.perf_counter() - t0
+
+    def prepare(u8, cat, want_gt):
+        """One category's view of one resident frame: the padded fp32 input [1,3,Hp,Wp], or the uint8 ground truth [h,w,3]."""
+        mode, y0, x0, h, w = xiph_geometry(u8.shape[0], u8.shape[1], cat)
+        if want_gt:
+            gt = torch.empty(h, w, 3, dtype=torch.uint8, device=dev)
+            ops.frame_u8_window(u8, mode, y0, x0, h, w, dst_u8=gt)
+            return gt
+        padder = host_io.InputPadder((h, w), divisor=p.divisor)
+        left, right, top, bottom = padder._pad
+        t = torch.empty(3, h + top + bottom, w + left + right, dtype=torch.float32, device=dev)
+        ops.frame_u8_window(u8, mode, y0, x0, h, w, dst=t, pad_top=top, pad_left=left)
+        return t.unsqueeze(0), padder
+
+    def pairs():
+        resident: Dict[str, torch.Tensor] = {}
+        workers = max(1, min(16, decode_workers))
+        with ThreadPoolExecutor(max_workers=workers) as pool:
+            futs, nxt = {}, 0
+            for i, s in enumerate(samples):
+                for q in s.frames:
+                    if q in resident:
+                        continue
+                    while nxt < len(order) and len(futs) < workers + 3:        # (order[nxt:] always starts at or before q)
+                        futs[order[nxt]] = pool.submit(decode, order[nxt])
+                        nxt += 1
+                    t0 = time.perf_counter()
+                    fr, dt = futs.pop(q).result()
+                    if timings is not None:
+                        timings["decode_wait"] = timings.get("decode_wait", 0.0) + time.perf_counter() - t0
+                        timings["decode_cpu"] = timings.get("decode_cpu", 0.0) + dt
+                    if fr.ndim != 3 or fr.shape[2] != 3:
+                        raise ValueError(f"{q}: expected an RGB frame, got shape {fr.shape}")
+                    xiph_geometry(fr.shape[0], fr.shape[1], XIPH_CATEGORIES[0])
+                    t0 = time.perf_counter()
+                    resident[q] = torch.from_numpy(fr).to(dev)
+                    clock("upload", t0)
+                f0, gt, f2 = (resident[q] for q in s.frames)
+                if f0.shape != gt.shape or f2.shape != gt.shape:
+                    raise ValueError(f"{s.name}: the three frames differ in size")
+                for ci, cat in enumerate(categories):
+                    t0 = time.perf_counter()
+                    (im0, padder), (im1, _) = prepare(f0, cat, False), prepare(f2, cat, False)
+                    gts[ci * n + i], padders[ci * n + i] = prepare(gt, cat, True), padder
+                    clock("prepare", t0)
+                    yield im0, im1
+                for q in s.frames:          # drop what no later triplet reads (the kernels above are queued on this stream already)
+                    uses[q] -= 1
+                    if uses[q] == 0:
+                        del resident[q]
+
+    done = 0
+    for k, pred in enumerate(_predictions(model, pairs(), tta, streams, timings)):
+        i, ci = divmod(k, nc)
+        row = ci * n + i
+        t0 = time.perf_counter()
+        pred = padders.pop(row).unpad(pred)
+        metrics.ssim_psnr_raw(pred, gts.pop(row), round_pred=p.round_pred, mse_f32=p.mse_f32, out=raw[row:row + 1])
+        clock("metric", t0)
+        if preds is not None:
+            preds[row] = pred[0].clone()
+        done += 1
+        if progress is not None and done % 100 == 0:
+            rows = [c * n + j for j in range(i + 1) for c in range(nc) if j < i or c <= ci]
+            r = raw[rows].cpu()
+            progress(done, n * nc, float(np.mean([metrics.psnr_from_mse(v) for v in r[:, 2].tolist()])), float(r[:, 0].mean()))
+
+    vals = raw[:n * nc].cpu().numpy()
+    records = [{"name": s.name, "level": cat, "psnr": metrics.psnr_from_mse(float(vals[ci * n + i][2])), "ssim": float(vals[ci * n + i][0])}
+               for ci, cat in enumerate(categories) for i, s in enumerate(samples)]
+    return EvalResult(records, _level_means(records), preds)
 
 
 def format_levels(result: EvalResult) -> str:
@@ -181,9 +359,12 @@ def format_levels(result: EvalResult) -> str:
     for name, v in result.levels.items():
         if name.startswith("test-"):
             lines.append("Testing level:" + name)
+        if name in XIPH_CATEGORIES:
+            lines.append("{}  Avg PSNR: {} SSIM: {}".format(name, v["psnr"], v["ssim"]))
+            continue
         lines.append("Avg PSNR: {} SSIM: {}".format(v["psnr"], v["ssim"]))
     return "\n".join(lines)
 
 
-__all__ = ["Sample", "vimeo90k", "ucf101", "snufilm", "LISTERS", "read_rgb", "evaluate", "EvalResult", "format_levels", "PROTOCOLS",
-           "SNU_LEVELS"]
+__all__ = ["Sample", "vimeo90k", "ucf101", "snufilm", "xiph", "LISTERS", "read_rgb", "evaluate", "evaluate_xiph", "xiph_geometry",
+           "EvalResult", "format_levels", "PROTOCOLS", "SNU_LEVELS", "XIPH_CLIPS", "XIPH_CATEGORIES"]

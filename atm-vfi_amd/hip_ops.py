@@ -128,6 +128,7 @@ SIGNATURES = {
                                       c_f, c_f, c_l, c_i, c_i, c_i, c_i, c_f]),
     "atmvfi_resize_bilinear_ac": (c_i, [c_f, c_l, c_l, c_l, c_l, c_f, c_i, c_i, c_i, c_i, c_i, c_i, ctypes.c_float, c_f]),
     "atmvfi_frame_u8_to_f32": (c_i, [c_f, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f]),
+    "atmvfi_frame_u8_window": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f, c_f]),
     "atmvfi_frame_f32_to_u8": (c_i, [c_f, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_f]),
     "atmvfi_pack_frames": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_f]),
     "atmvfi_final_residual": (c_i, [c_f, c_f, c_i, c_f, c_f, c_i, c_i, c_i, c_f]),
@@ -1198,6 +1199,27 @@ class HipOps:
         h, w = src_u8.shape[:2]
         self._run("frame_u8_to_f32", {"bytes": 3.0 * h * w + 12.0 * dst.shape[1] * dst.shape[2]}, self.lib.atmvfi_frame_u8_to_f32,
                   _ptr(src_u8), h, w, int(bgr), _ptr(dst), dst.shape[1], dst.shape[2], pad_top, pad_left, self._stream())
+
+    def frame_u8_window(self, src_u8, mode: int, y0: int, x0: int, h: int, w: int, dst=None, dst_u8=None, pad_top: int = 0,
+                        pad_left: int = 0, bgr: bool = False):
+        """One resident uint8 [H,W,3] frame -> the h x w window at (y0, x0) (``mode`` 0) or the 2x area reduction of the 2h x 2w window
+        there (``mode`` 1: (a + b + c + d + 2) >> 2, cv2.INTER_AREA at scale 2), as ``dst`` fp32 planar [3,Hp,Wp] (q / 255, replicate
+        padding, the window at (pad_top, pad_left)) and / or ``dst_u8`` uint8 [h,w,3] RGB (include/atmvfi.h atmvfi_frame_u8_window)."""
+        if src_u8.dtype != torch.uint8 or src_u8.dim() != 3 or src_u8.shape[2] != 3 or not src_u8.is_contiguous() or not src_u8.is_cuda:
+            raise ValueError("frame_u8_window: source must be a contiguous CUDA uint8 [H,W,3] tensor")
+        if dst is None and dst_u8 is None:
+            raise ValueError("frame_u8_window: give dst, dst_u8 or both")
+        if dst is not None and (dst.dtype != torch.float32 or dst.dim() != 3 or dst.shape[0] != 3 or not dst.is_contiguous() or not dst.is_cuda):
+            raise ValueError("frame_u8_window: dst must be a contiguous CUDA fp32 [3,Hp,Wp] tensor")
+        if dst_u8 is not None and (dst_u8.dtype != torch.uint8 or tuple(dst_u8.shape) != (h, w, 3) or not dst_u8.is_contiguous()
+                                   or not dst_u8.is_cuda):
+            raise ValueError(f"frame_u8_window: dst_u8 must be a contiguous CUDA uint8 [{h},{w},3] tensor")
+        sh, sw = src_u8.shape[:2]
+        hp, wp = (dst.shape[1], dst.shape[2]) if dst is not None else (h + pad_top, w + pad_left)
+        scale = 2 if mode == 1 else 1
+        meta = {"bytes": 3.0 * scale * scale * h * w + (12.0 * hp * wp if dst is not None else 0.0) + (3.0 * h * w if dst_u8 is not None else 0.0)}
+        self._run("frame_u8_window", meta, self.lib.atmvfi_frame_u8_window, _ptr(src_u8), sh, sw, int(bgr), int(mode), int(y0), int(x0),
+                  int(h), int(w), _ptr(dst), hp, wp, int(pad_top), int(pad_left), _ptr(dst_u8), self._stream())
 
     def frame_f32_to_u8(self, src, dst_u8, pad_top: int, pad_left: int, bgr: bool):
         """fp32 planar [3,Hp,Wp] -> crop -> np.round(x * 255) -> uint8 [H,W,3] device tensor (optional RGB -> BGR)."""

@@ -1,6 +1,6 @@
 """Quality metrics of the evaluation scripts on the GPU: the reference's ``ssim_matlab`` (benchmark/pytorch_msssim.py:82-135) and
 PSNR, both from ONE fused HIP kernel (``csrc/metrics.hip``, ``include/atmvfi.h`` atmvfi_ssim_psnr), plus the per-dataset metric
-protocols of the reference's scripts (benchmark/test_vimeo90k.py, test_ucf101.py, test_snufilm.py) written down as data.
+protocols of the reference's scripts (benchmark/test_vimeo90k.py, test_ucf101.py, test_snufilm.py, test_xiph.py) written down as data.
 
 There is no CPU path: every entry point takes CUDA (= HIP) tensors and raises on anything else."""
 from __future__ import annotations
@@ -39,6 +39,13 @@ PROTOCOLS: Dict[str, Protocol] = {
     # test_snufilm.py: InputPadder(divisor=64), unpad, ssim_matlab(gt, pred); psnr as vimeo90k
     "snufilm": Protocol("snufilm", divisor=64, global_motion=True, ensemble_global_motion=False, round_pred=False, mse_f32=False),
 }
+
+
+# test_xiph.py: InputPadder(divisor=32), unpad, calculate_psnr(pred, gt) (difference, square and mean in fp32) and calculate_ssim(pred, gt)
+# on frames in [0, 1].  The script detects SSIM's value range on the prediction (its img1), the kernel on the ground truth; both lie in
+# [0, 1], so L = 1 either way.  Kept OUT of ``PROTOCOLS``: Xiph is not one list of samples but two categories cut from the same frames
+# (evaluate.evaluate_xiph), and ``evaluate()`` takes this object where it is wanted.
+XIPH = Protocol("xiph", divisor=32, global_motion=True, ensemble_global_motion=None, round_pred=False, mse_f32=True)
 
 
 _ops_lock = threading.Lock()

@@ -1,5 +1,5 @@
 """``from benchmark.utils import InputPadder`` (demo_2x.py:7 of the reference) resolves here.
-Only the two helpers on the hot path's boundary are provided."""
+The helpers on the hot path's boundary are provided, and ``read`` for the 8-bit image formats (benchmark/test_xiph.py:10)."""
 import os
 import sys
 
@@ -9,3 +9,15 @@ from importlib import import_module
 _io = import_module("atm-vfi_amd.host_io")
 InputPadder = _io.InputPadder
 img2tensor = _io.img2tensor
+
+
+_IMAGE_SUFFIXES = (".png", ".jpg", ".ppm", ".pgm")
+
+
+def read(file):
+    """benchmark/utils.py ``read`` for the 8-bit image formats: uint8 RGB [H,W,3] (the reference goes through imageio; this is PIL).
+    The float and flow formats (.float3, .flo, .pfm) are not part of the evaluation scripts' path and are not provided."""
+    suffix = os.path.splitext(str(file))[1]
+    if suffix in _IMAGE_SUFFIXES:
+        return import_module("atm-vfi_amd.evaluate").read_rgb(str(file))
+    raise NotImplementedError(f"benchmark.utils.read: {suffix or 'no suffix'!r} files are not supported (8-bit .png, .jpg, .ppm and .pgm only)")

@@ -420,6 +420,17 @@ int atmvfi_refine_tail(const float* contrib, int64_t contrib_plane, const float*
  *   f32_to_u8: the inverse: crop, np.round(x * 255) (half to even), uint8 [H,W,3].  Bit-exact against the numpy path. */
 int atmvfi_frame_u8_to_f32(const void* src, int H, int W, int bgr, float* dst, int Hp, int Wp, int pad_top, int pad_left, void* stream);
 int atmvfi_frame_f32_to_u8(const float* src, int Hp, int Wp, int pad_top, int pad_left, void* dst, int H, int W, int bgr, void* stream);
+/* One resident uint8 [H,W,3] frame (contiguous; BGR if `bgr`) -> the h x w output window that a dataset evaluation needs, as a network
+ * input and / or a ground truth (benchmark/test_xiph.py of the reference: "cropped-4k" and "resized-2k").
+ *   mode 0 (crop):    output pixel (y, x) = src[y0 + y, x0 + x];
+ *   mode 1 (area 2x): output pixel (y, x) = (a + b + c + d + 2) >> 2 per channel over the 2x2 source block at (y0 + 2y, x0 + 2x) --
+ *                     cv2.INTER_AREA for uint8 at an exact scale of 2, ties round up; the window covers 2h x 2w source pixels.
+ *   dst    (or NULL): fp32 planar RGB [3,Hp,Wp] = q / 255 (a true fp32 division) with replicate padding, the window at (pad_top, pad_left);
+ *   dst_u8 (or NULL): uint8 [h,w,3] RGB, the same integer pixels, un-padded: the ground truth form atmvfi_ssim_psnr reads in place.
+ * Not both NULL.  Any geometry and pointer alignment is accepted; dword loads and 16-byte plane stores are used when src and dst_u8 are
+ * 4-byte and dst 16-byte aligned and W, x0, w, pad_left and Wp are multiples of 4.  Both paths give the same bits. */
+int atmvfi_frame_u8_window(const void* src, int H, int W, int bgr, int mode, int y0, int x0, int h, int w, float* dst, int Hp, int Wp,
+                           int pad_top, int pad_left, void* dst_u8, void* stream);
 
 /* mean |a - b| per sample: global_alignmentness (network_base.py:560-561).  Two passes with a fixed summation order -- the result is
  * run-to-run bit-identical (the ensemble's pick compares these means) -- through `workspace`: at least
