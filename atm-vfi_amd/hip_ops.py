@@ -130,6 +130,9 @@ SIGNATURES = {
     "atmvfi_frame_u8_to_f32": (c_i, [c_f, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f]),
     "atmvfi_frame_u8_window": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f, c_f]),
     "atmvfi_frame_f32_to_u8": (c_i, [c_f, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_f]),
+    "atmvfi_pool_blocks": (c_i, [c_f, c_l, c_i, ctypes.POINTER(ctypes.c_int32), c_i, c_l, c_f, c_i, c_f]),
+    "atmvfi_tta_merge": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f]),
+    "atmvfi_frame_rot180": (c_i, [c_f, c_f, c_i, c_i, c_i, c_f]),
     "atmvfi_pack_frames": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_f]),
     "atmvfi_final_residual": (c_i, [c_f, c_f, c_i, c_f, c_f, c_i, c_i, c_i, c_f]),
     "atmvfi_l1_mean": (c_i, [c_f, c_f, c_f, c_i, c_l, c_f, c_l, c_f]),
@@ -1230,6 +1233,65 @@ class HipOps:
         h, w = dst_u8.shape[:2]
         self._run("frame_f32_to_u8", {"bytes": 3.0 * h * w + 12.0 * h * w}, self.lib.atmvfi_frame_f32_to_u8, _ptr(src), src.shape[1],
                   src.shape[2], pad_top, pad_left, _ptr(dst_u8), h, w, int(bgr), self._stream())
+
+    def pool_blocks(self, pool, slots, buf, to_pool: bool = False, block_elems: Optional[int] = None):
+        """``len(slots)`` blocks between the slots of ``pool`` (contiguous [S, ...]) and the contiguous ``buf`` in one launch
+        (include/atmvfi.h atmvfi_pool_blocks).  Gather (``to_pool`` False): block j of ``buf`` = the first ``block_elems`` elements of
+        ``pool[slots[j]]`` -- ``torch.index_select``; scatter: the inverse -- ``Tensor.index_copy_``.  ``block_elems`` defaults to a
+        whole slot.  ``slots`` is a host sequence of ints; it travels in the kernel arguments."""
+        if self.recording is not None:
+            raise PlanUnsupported("pool_blocks takes a host slot list: pooled forwards are not recorded")
+        n = len(slots)
+        if pool.dim() < 1 or not pool.is_contiguous() or not buf.is_contiguous() or not pool.is_cuda or not buf.is_cuda:
+            raise ValueError("pool_blocks: pool and buf must be contiguous CUDA tensors")
+        if pool.dtype != buf.dtype:
+            raise ValueError(f"pool_blocks: pool is {pool.dtype}, buf {buf.dtype}")
+        if not 1 <= n <= 32:
+            raise ValueError(f"pool_blocks: 1..32 blocks per launch, got {n}")
+        es = pool.element_size()
+        slot_elems = pool[0].numel()
+        be = slot_elems if block_elems is None else int(block_elems)
+        if be <= 0 or be > slot_elems or buf.numel() != n * be:
+            raise ValueError(f"pool_blocks: buf holds {buf.numel()} elements, {n} blocks of {be} (slot: {slot_elems}) need {n * be}")
+        arr = (ctypes.c_int32 * n)(*[int(s) for s in slots])
+        self._run("pool_blocks", {"bytes": 2.0 * n * be * es, "blocks": n}, self.lib.atmvfi_pool_blocks, _ptr(pool), slot_elems * es,
+                  pool.shape[0], arr, n, be * es, _ptr(buf), int(bool(to_pool)), self._stream())
+
+    @staticmethod
+    def _frame3(t, what: str):
+        if t.dtype != torch.float32 or t.dim() != 3 or t.shape[0] != 3 or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError(f"{what} must be a contiguous CUDA fp32 [3,Hp,Wp] tensor")
+
+    def tta_merge(self, pred, pred_flip, out=None, out_u8=None, pad_top: int = 0, pad_left: int = 0, bgr: bool = False):
+        """``out`` = (pred + pred_flip.flip(1).flip(2)) / 2 on [3,Hp,Wp] frames and / or ``out_u8`` = ``frame_f32_to_u8`` of it (uint8
+        [H,W,3], the crop at (pad_top, pad_left)), in one launch (include/atmvfi.h atmvfi_tta_merge)."""
+        self._frame3(pred, "tta_merge: pred"); self._frame3(pred_flip, "tta_merge: pred_flip")
+        if pred_flip.shape != pred.shape:
+            raise ValueError("tta_merge: pred and pred_flip differ in shape")
+        if out is None and out_u8 is None:
+            raise ValueError("tta_merge: give out, out_u8 or both")
+        if out is not None:
+            self._frame3(out, "tta_merge: out")
+            if out.shape != pred.shape:
+                raise ValueError("tta_merge: out must have pred's shape")
+        h = w = 0
+        if out_u8 is not None:
+            if out_u8.dtype != torch.uint8 or out_u8.dim() != 3 or out_u8.shape[2] != 3 or not out_u8.is_contiguous() or not out_u8.is_cuda:
+                raise ValueError("tta_merge: out_u8 must be a contiguous CUDA uint8 [H,W,3] tensor")
+            h, w = out_u8.shape[:2]
+        hp, wp = pred.shape[1:]
+        meta = {"bytes": 24.0 * hp * wp + (12.0 * hp * wp if out is not None else 0.0) + 3.0 * h * w}
+        self._run("tta_merge", meta, self.lib.atmvfi_tta_merge, _ptr(pred), _ptr(pred_flip), _ptr(out), _ptr(out_u8), hp, wp, int(pad_top),
+                  int(pad_left), h, w, int(bool(bgr)), self._stream())
+
+    def frame_rot180(self, src, dst):
+        """``dst`` = ``src.flip(-2).flip(-1)`` of contiguous fp32 [...,Hp,Wp] planes (include/atmvfi.h atmvfi_frame_rot180)."""
+        if (src.dtype != torch.float32 or src.dim() < 2 or not src.is_contiguous() or not src.is_cuda or dst.dtype != torch.float32
+                or dst.shape != src.shape or not dst.is_contiguous() or not dst.is_cuda):
+            raise ValueError("frame_rot180: src and dst must be contiguous CUDA fp32 tensors of one shape [...,Hp,Wp]")
+        hp, wp = src.shape[-2:]
+        self._run("frame_rot180", {"bytes": 8.0 * src.numel()}, self.lib.atmvfi_frame_rot180, _ptr(src), _ptr(dst), src.numel() // (hp * wp),
+                  hp, wp, self._stream())
 
     def pack_frames(self, im0, im1, dst):
         _planar(im0, 3, "pack_frames.im0"); _planar(im1, 3, "pack_frames.im1")

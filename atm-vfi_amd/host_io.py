@@ -594,3 +594,7 @@ def load_model_checkpoint(model, checkpoint_path, strict: bool = True, map_locat
         param = ck
     model.load_state_dict(strip_lazy_buffers(param), strict=strict)
     return optim
+
+
+# 4x / 8x recursive interpolation (benchmark/davis-vid.py): atm-vfi_amd/multiframe.py
+from .multiframe import (FramePool, inference_nx, interpolate_video_nx, nx_levels, nx_sequence, video_nx)  # noqa: E402,F401

@@ -1,0 +1,470 @@
+"""4x / 8x (any power of two) interpolation by recursion, the loop of the reference's ``benchmark/davis-vid.py:88-135``:
+``pred = F(I0, I1)``, then ``pred025 = F(I0, pred)`` and ``pred075 = F(pred, I1)`` -- the deeper levels fed with the UNROUNDED fp32
+prediction -- with a centre crop, a frame stride (``time_interval``) and optional flip-TTA.
+
+* ``nx_levels`` / ``nx_sequence``: the schedule and the order of the loop, pure Python (tested without a GPU);
+* ``FramePool``: device-resident frames and per-frame tokens, so that what ``Network.forward`` computes per frame (encoder, cross-scale
+  fusions, LayerNorm'ed tokens) is computed once per DISTINCT frame (``Network.forward_pooled``) instead of once per appearance in a
+  pair: N/2 frame encodes per segment instead of 2 (N - 1);
+* ``interpolate_video_nx`` / ``video_nx`` / ``inference_nx``: the runner and its adapters (re-exported from ``host_io``).
+
+Deviations from the script, on purpose: (1) with ``tta`` EVERY produced frame is the flip-TTA average (the script averages the middle
+frame only); the next level still consumes the un-averaged prediction, as the script's order of operations has it (:102-112).  (2) with
+a crop the originals are written cropped (the script hands the uncropped originals to a writer opened at the crop size, :86, 120, 135).
+"""
+from __future__ import annotations
+
+from collections import deque
+from typing import Callable, Iterable, Iterator, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+
+# ------------------------------------------------------------------------------------------------ schedule (no device)
+def nx_levels(factor: int) -> List[List[Tuple[int, int, int]]]:
+    """The recursion of an N-x interpolation (N = ``factor``, a power of two >= 2) in slot positions 0..N (0 and N: the two source
+    frames; position k: the frame at t = k/N): level 1 ``[(0, N, N/2)]``, level 2 ``[(0, N/2, N/4), (N/2, N, 3N/4)]``, ... each entry
+    (left, right, out).  The 2^(l-1) pairs of level l are independent of each other: a ready-made batch."""
+    if not isinstance(factor, int) or isinstance(factor, bool) or factor < 2 or factor & (factor - 1):
+        raise ValueError(f"factor must be a power of two >= 2, got {factor!r}")
+    levels, span = [], factor
+    while span >= 2:
+        levels.append([(a, a + span, a + span // 2) for a in range(0, factor, span)])
+        span //= 2
+    return levels
+
+
+def nx_sequence(frames: Iterable, segment: Callable, factor: int, time_interval: int = 1) -> Iterator:
+    """The order of davis-vid.py:88-135 over any iterable: per segment ``(f_i, f_{i+s})``, ``s = time_interval``,
+    ``i in range(0, n - s, s)``, yields ``f_i`` and then the ``factor - 1`` frames that ``segment(f_i, f_{i+s})`` returns (t = 1/N ...
+    (N-1)/N, in temporal order); after the last segment its second frame once.  Frames between ``i`` and ``i + s`` are consumed and
+    dropped, and so are trailing frames that form no full segment.  An empty input yields nothing; fewer than ``s + 1`` frames yield
+    nothing either (the script writes an undefined frame there).  ``segment`` sees its frames one segment ahead of the yields only
+    in so far as it is called before its first output is yielded."""
+    nx_levels(factor)
+    s = int(time_interval)
+    if s < 1:
+        raise ValueError(f"time_interval must be >= 1, got {time_interval!r}")
+    it = iter(frames)
+    a = next(it, None)
+    if a is None:
+        return
+    last = None
+    while True:
+        b = None
+        for _ in range(s):
+            b = next(it, None)
+            if b is None:
+                break
+        if b is None:
+            break
+        mids = segment(a, b)
+        if len(mids) != factor - 1:
+            raise ValueError(f"segment returned {len(mids)} frames, {factor - 1} expected")
+        yield a
+        for m in mids:
+            yield m
+        a = last = b
+    if last is not None:
+        yield last
+
+
+def centre_window(height: int, width: int, crop: Optional[Tuple[int, int]]) -> Tuple[int, int, int, int]:
+    """(y0, x0, h, w) of davis-vid.py:95: rows ``H//2 - h//2 ... H//2 + h//2``, columns likewise (so an odd h loses one row: h is
+    rounded down to even, as the script's slice does).  ``crop=None``: the whole frame."""
+    if crop is None:
+        return 0, 0, height, width
+    h, w = int(crop[0]), int(crop[1])
+    if h < 2 or w < 2 or h > height or w > width:
+        raise ValueError(f"crop {crop} does not fit a {height}x{width} frame")
+    return height // 2 - h // 2, width // 2 - w // 2, 2 * (h // 2), 2 * (w // 2)
+
+
+# ------------------------------------------------------------------------------------------------ pool
+class FramePool:
+    """``slots`` device-resident frames of one padded size with what the network computes per frame: ``frames`` [S,3,Hp,Wp] fp32,
+    ``tokens_l`` [S,h*w,C] (LayerNorm'ed local tokens, h = Hp/8), ``tokens_g`` [S,h_*w_,Cg] (global tokens, h_ = Hp/16) and per slot a
+    validity key of its tokens (``keys``: None = stale; else the weights' identity, ``global_motion``, precision / checked build -- the
+    device and shape are the pool's own).  At 1080p (1088x1920, network_base) a slot is 25 + 50 + 22 MB: nine slots (8x) stay under
+    1 GB.  ``Network.forward_pooled(pool, left, right)`` fills and reads the tokens."""
+
+    def __init__(self, model, hp: int, wp: int, slots: int):
+        import torch
+        dev = next(model.parameters()).device
+        if dev.type != "cuda" or not hasattr(model, "forward_pooled"):
+            raise RuntimeError("FramePool needs an atm-vfi_amd Network on the GPU")
+        if hp % 16 or wp % 16:
+            raise ValueError(f"FramePool: Hp and Wp must be multiples of 16 (got {hp}x{wp})")
+        if not 1 <= int(slots) <= 1024:
+            raise ValueError(f"FramePool: 1..1024 slots, got {slots}")
+        v = model._v
+        self.model, self.hp, self.wp, self.slots, self.device = model, int(hp), int(wp), int(slots), dev
+        self.ops = model._ops(dev)
+        mk = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+        self.frames = mk(self.slots, 3, hp, wp)
+        self.tokens_l = mk(self.slots, (hp // 8) * (wp // 8), v.local_dim)
+        self.tokens_g = mk(self.slots, (hp // 16) * (wp // 16), v.global_dim)
+        self.keys: List[Optional[tuple]] = [None] * self.slots
+
+    def frame(self, slot: int):
+        """The [1,3,Hp,Wp] view of a slot's frame.  Whoever writes through it calls ``invalidate(slot)``."""
+        return self.frames[slot:slot + 1]
+
+    def invalidate(self, slot: int):
+        self.keys[slot] = None
+
+    def put(self, slot: int, src):
+        """Write a frame ([3,Hp,Wp] or [1,3,Hp,Wp] fp32 on the pool's device) into ``slot`` (one ``atmvfi_pool_blocks`` scatter)
+        and invalidate the slot's tokens."""
+        if tuple(src.shape[-3:]) != (3, self.hp, self.wp) or src.numel() != 3 * self.hp * self.wp:
+            raise ValueError(f"FramePool.put: expected a [3,{self.hp},{self.wp}] frame, got {tuple(src.shape)}")
+        if src.device != self.device:
+            raise ValueError(f"FramePool.put: the frame lives on {src.device}, the pool on {self.device}")
+        self.ops.pool_blocks(self.frames, [int(slot)], src.detach().float().contiguous(), to_pool=True)
+        self.keys[slot] = None
+
+    def nbytes(self) -> int:
+        return 4 * (self.frames.numel() + self.tokens_l.numel() + self.tokens_g.numel())
+
+    def release(self):
+        self.frames = self.tokens_l = self.tokens_g = None
+        self.keys = []
+
+
+# ------------------------------------------------------------------------------------------------ runner
+class _Uploader:
+    """Every source frame goes to the device ONCE: a ring of pinned host slots + device staging filled on a copy stream, ahead of the
+    kernel that converts it (as ``host_io.interpolate_video_2x_distributed`` does)."""
+
+    def __init__(self, dev, height: int, width: int, depth: int = 3):
+        import torch
+        self.torch, self.dev, self.h, self.w, self.depth = torch, dev, height, width, depth
+        self.ring = [{"h": torch.empty(height, width, 3, dtype=torch.uint8).pin_memory(),
+                      "d": torch.empty(height, width, 3, dtype=torch.uint8, device=dev),
+                      "ready": torch.cuda.Event(), "free": torch.cuda.Event()} for _ in range(depth)]
+        for s in self.ring:
+            s["h_np"] = s["h"].numpy()
+        self.copy_in = torch.cuda.Stream(dev)
+        self.issued = 0
+
+    def upload(self, frame):
+        """Start the host -> device copy of ``frame``; returns the ring slot to hand to ``take``."""
+        torch = self.torch
+        if frame.shape != (self.h, self.w, 3) or frame.dtype != np.uint8:
+            raise ValueError(f"interpolate_video_nx: expected uint8 [{self.h},{self.w},3] frames, got {frame.dtype} {tuple(frame.shape)}")
+        slot = self.ring[self.issued % self.depth]
+        if self.issued >= self.depth:
+            slot["free"].synchronize()                # the kernel that read this slot's device copy has run
+        np.copyto(slot["h_np"], frame)                # numpy's single-threaded memcpy (see host_io.FramePipeline._upload)
+        with torch.cuda.stream(self.copy_in):
+            slot["d"].copy_(slot["h"], non_blocking=True)
+            slot["ready"].record(self.copy_in)
+        self.issued += 1
+        return slot
+
+    def take(self, slot, convert):
+        """Run ``convert(device uint8 frame)`` on the current stream once the slot's copy has landed."""
+        cur = self.torch.cuda.current_stream(self.dev)
+        cur.wait_event(slot["ready"])
+        convert(slot["d"])
+        slot["free"].record(cur)
+
+
+class _SegmentRunner:
+    """One segment of the N-x recursion on the device: source frames in pool positions 0 and N, level l as batches of at most
+    ``max_batch`` pairs, every produced ``I_t`` (padded canvas, fp32, as returned: no un-pad / re-pad, no rounding) into the pool slot it
+    belongs to and, through ``frame_f32_to_u8`` (or ``tta_merge``), into the output ring.
+
+    Workspaces: batches of different size are different workspaces of the model, and its LRU of two would free and reallocate them
+    per level at 8x (batch sizes 1, 2, 4).  The runner RAISES ``model.max_workspaces`` to the number of batch sizes of its schedule for
+    its lifetime and restores it in ``close()``."""
+
+    def __init__(self, model, ops, dev, height, width, factor, crop, bgr, divisor, tta, max_batch, pool):
+        import torch
+        from .host_io import InputPadder
+        self.torch, self.model, self.ops, self.dev = torch, model, ops, dev
+        self.n, self.bgr, self.tta, self.use_pool = factor, bool(bgr), bool(tta), bool(pool)
+        self.levels = nx_levels(factor)
+        self.max_batch = max(1, min(int(max_batch), 16))
+        self.y0, self.x0, self.h, self.w = centre_window(height, width, crop)
+        if divisor is None:
+            self.pad_left = self.pad_top = 0
+            self.hp, self.wp = self.h, self.w
+        else:
+            pad = InputPadder((1, 3, self.h, self.w), divisor=divisor)
+            self.pad_left, _, self.pad_top, _ = pad._pad
+            self.hp, self.wp = self.h + pad._pad[2] + pad._pad[3], self.w + pad._pad[0] + pad._pad[1]
+        need = 16 if getattr(model, "global_motion", True) else 8
+        if self.hp % need or self.wp % need:
+            raise ValueError(f"interpolate_video_nx: {self.hp}x{self.wp} frames need a divisor (multiples of {need})")
+        if self.use_pool and (self.hp % 16 or self.wp % 16):
+            raise ValueError(f"interpolate_video_nx: pool=True needs frame sides that are multiples of 16 (got {self.hp}x{self.wp})")
+        S = factor + 1
+        if self.use_pool:
+            self.pools = [FramePool(model, self.hp, self.wp, S) for _ in range(2 if self.tta else 1)]
+            self.frames = [p.frames for p in self.pools]
+        else:
+            self.pools = None
+            self.frames = [torch.empty(S, 3, self.hp, self.wp, dtype=torch.float32, device=dev) for _ in range(2 if self.tta else 1)]
+        self.phys = list(range(S))                   # schedule position -> pool slot; positions 0 and N swap slots per segment
+        self.have_first = False
+        # plain mode: the pairs of a batch are gathered into contiguous [B,3,Hp,Wp] inputs
+        self.gather = {}
+        self.out_d = torch.empty(factor - 1, self.h, self.w, 3, dtype=torch.uint8, device=dev)
+        self.out_h = [torch.empty(factor - 1, self.h, self.w, 3, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        self.out_evt = [torch.cuda.Event() for _ in range(2)]
+        self.seg = 0
+        self.copy_out = torch.cuda.Stream(dev)
+        self.done = torch.cuda.Event()
+        sizes = {min(self.max_batch, len(lv) - i) for lv in self.levels for i in range(0, len(lv), self.max_batch)}
+        self._keep_max_ws = getattr(model, "max_workspaces", None)
+        if self._keep_max_ws is not None and len(sizes) > self._keep_max_ws:
+            model.max_workspaces = len(sizes)
+
+    def close(self):
+        if self._keep_max_ws is not None:
+            self.model.max_workspaces = self._keep_max_ws
+        if self.pools:
+            for p in self.pools:
+                p.release()
+
+    # -- source frames
+    def _convert_into(self, pos):
+        slot = self.phys[pos]
+
+        def convert(d_u8):
+            dst = self.frames[0][slot]
+            if (self.y0, self.x0, self.h, self.w) == (0, 0) + tuple(d_u8.shape[:2]):
+                self.ops.frame_u8_to_f32(d_u8, dst, self.pad_top, self.pad_left, self.bgr)
+            else:
+                self.ops.frame_u8_window(d_u8, 0, self.y0, self.x0, self.h, self.w, dst=dst, pad_top=self.pad_top, pad_left=self.pad_left,
+                                         bgr=self.bgr)
+            if self.tta:
+                self.ops.frame_rot180(dst, self.frames[1][slot])
+            if self.pools:
+                for p in self.pools:
+                    p.invalidate(slot)
+        return convert
+
+    def _forward(self, k, lefts, rights):
+        """I_t [B,3,Hp,Wp] of the pairs (slots) on frame set ``k`` (0: the frames, 1: their 180-degree rotations)."""
+        if self.use_pool:
+            return self.model.forward_pooled(self.pools[k], lefts, rights)["I_t"]
+        b = len(lefts)
+        g = self.gather.get(b)
+        if g is None:
+            g = self.gather[b] = self.torch.empty(2 * b, 3, self.hp, self.wp, dtype=self.torch.float32, device=self.dev)
+        self.ops.pool_blocks(self.frames[k], lefts + rights, g)
+        return self.model.forward(g[:b], g[b:])["I_t"]
+
+    def run(self, up: _Uploader, slot_a, slot_b):
+        """Enqueue one segment: ``slot_a`` (None when the previous segment's second frame is this one's first) and ``slot_b`` are
+        upload slots.  Returns a handle for ``result``."""
+        torch, n = self.torch, self.n
+        with torch.cuda.device(self.dev):
+            if self.have_first:
+                self.phys[0], self.phys[n] = self.phys[n], self.phys[0]      # frame AND tokens of slot N become slot 0's: no copy
+            else:
+                up.take(slot_a, self._convert_into(0))
+                self.have_first = True
+            up.take(slot_b, self._convert_into(n))
+            ring = self.seg & 1
+            self.seg += 1
+            last = len(self.levels) - 1
+            for li, level in enumerate(self.levels):
+                for i in range(0, len(level), self.max_batch):
+                    chunk = level[i:i + self.max_batch]
+                    lefts = [self.phys[a] for a, _, _ in chunk]
+                    rights = [self.phys[b] for _, b, _ in chunk]
+                    outs = [self.phys[o] for _, _, o in chunk]
+                    pred = self._forward(0, lefts, rights)
+                    flip = self._forward(1, lefts, rights) if self.tta else None
+                    for j, (_, _, pos) in enumerate(chunk):
+                        u8 = self.out_d[pos - 1]
+                        if self.tta:
+                            self.ops.tta_merge(pred[j], flip[j], out_u8=u8, pad_top=self.pad_top, pad_left=self.pad_left, bgr=self.bgr)
+                        else:
+                            self.ops.frame_f32_to_u8(pred[j], u8, self.pad_top, self.pad_left, self.bgr)
+                    if li < last:                      # the next level reads these frames (the un-averaged prediction)
+                        self.ops.pool_blocks(self.frames[0], outs, pred, to_pool=True)
+                        if self.tta:
+                            rot = self.gather.get(("rot", len(chunk)))
+                            if rot is None:
+                                rot = self.gather[("rot", len(chunk))] = torch.empty_like(pred)
+                            self.ops.frame_rot180(pred, rot)
+                            self.ops.pool_blocks(self.frames[1], outs, rot, to_pool=True)
+                        if self.pools:
+                            for p in self.pools:
+                                for s in outs:
+                                    p.invalidate(s)
+            cur = torch.cuda.current_stream(self.dev)
+            self.done.record(cur)
+            self.copy_out.wait_event(self.done)
+            with torch.cuda.stream(self.copy_out):
+                self.out_h[ring].copy_(self.out_d, non_blocking=True)
+                self.out_evt[ring].record(self.copy_out)
+            # out_d is rewritten by the next segment: its kernels wait for this copy
+            cur.wait_event(self.out_evt[ring])
+            return ring
+
+    def result(self, ring) -> List[np.ndarray]:
+        self.out_evt[ring].synchronize()
+        arr = self.out_h[ring].numpy()
+        return [arr[k].copy() for k in range(self.n - 1)]
+
+
+def _generic_segment(model, factor, crop_of, isBGR, divisor, tta, max_batch):
+    """``segment`` for a model without the HIP backend (any callable ``forward(im0, im1) -> {"I_t"}``): torch ops, same schedule."""
+    import torch
+    from .host_io import InputPadder
+    dev = next(model.parameters()).device
+    levels = nx_levels(factor)
+
+    def to_t(img):
+        img = crop_of(img)
+        if isBGR:
+            img = img[:, :, ::-1]
+        return (torch.tensor(np.ascontiguousarray(img.transpose(2, 0, 1))).to(dev) / 255.).unsqueeze(0)
+
+    def segment(fa, fb):
+        a, b = to_t(fa), to_t(fb)
+        padder = InputPadder(a.shape, divisor=divisor) if divisor else None
+        if padder:
+            a, b = padder.pad(a, b)
+        fr = {0: a, factor: b}
+        shown = {}
+        for level in levels:
+            for i in range(0, len(level), max_batch):
+                chunk = level[i:i + max_batch]
+                l = torch.cat([fr[x] for x, _, _ in chunk], 0)
+                r = torch.cat([fr[y] for _, y, _ in chunk], 0)
+                pred = model.forward(l, r)["I_t"]
+                out = pred
+                if tta:
+                    pf = model.forward(l.flip(2).flip(3).contiguous(), r.flip(2).flip(3).contiguous())["I_t"]
+                    out = (pred + pf.flip(2).flip(3)) / 2
+                for j, (_, _, pos) in enumerate(chunk):
+                    fr[pos] = pred[j:j + 1]
+                    shown[pos] = out[j:j + 1]
+        res = []
+        for pos in range(1, factor):
+            p = shown[pos]
+            if padder:
+                p = padder.unpad(p)
+            p = np.round(p[0].detach().cpu().numpy().transpose(1, 2, 0) * 255).astype(np.uint8)
+            res.append(p[:, :, ::-1].copy() if isBGR else p)
+        return res
+    return segment
+
+
+def interpolate_video_nx(frames, model, factor: int = 4, time_interval: int = 1, crop: Optional[Tuple[int, int]] = None, isBGR: bool = True,
+                         divisor: Optional[int] = 64, tta: bool = False, max_batch: int = 4, pool: bool = True):
+    """N-x slow motion over any iterable of uint8 [H,W,3] frames (davis-vid.py:88-135; decoding / encoding stays with the caller):
+    per segment ``(f_i, f_{i+s})``, ``s = time_interval``, yields ``f_i`` and the frames at t = 1/N ... (N-1)/N, after the last segment
+    its second frame once -- ``segments * N + 1`` frames.  Originals pass through bit-equal (their centre ``crop=(h, w)`` window when
+    given); frames between ``i`` and ``i + s`` are consumed and dropped.
+
+    Every source frame is uploaded and converted once and lives in pool position 0 or N; position N's frame and tokens become position
+    0's of the next segment by swapping slots.  Level l of the recursion runs as batches of at most ``max_batch`` pairs; its ``I_t``
+    feeds the next level as returned (padded fp32, unrounded).  ``divisor=None``: no padding (what the script does).  ``tta``: every
+    produced frame is the flip-TTA average; the next level consumes the un-averaged prediction.  ``pool=True``: per-frame work once per
+    distinct frame (``Network.forward_pooled``); ``pool=False``: plain ``model.forward`` calls on the same level batches (same
+    outputs; the A/B baseline, and what a model without ``forward_pooled`` gets).  The runner raises ``model.max_workspaces`` to the
+    number of batch sizes of its schedule while it runs and restores it.  ``factor=2`` gives ``interpolate_video_2x``'s frames."""
+    from .host_io import _hip_ops_of
+    nx_levels(factor)
+    it = iter(frames)
+    first = next(it, None)
+    if first is None:
+        return
+    H, W = first.shape[:2]
+    y0, x0, h, w = centre_window(H, W, crop)
+    crop_of = (lambda f: f) if crop is None else (lambda f: np.ascontiguousarray(f[y0:y0 + h, x0:x0 + w]))
+    ops, dev = _hip_ops_of(model)
+    if ops is None or not hasattr(ops, "pool_blocks"):
+        seg = _generic_segment(model, factor, crop_of, isBGR, divisor, tta, max(1, int(max_batch)))
+        for f in nx_sequence(_chain(first, it), lambda a, b: seg(a, b), factor, time_interval):
+            yield f if f.shape[:2] == (h, w) else crop_of(f)
+        return
+    runner = _SegmentRunner(model, ops, dev, H, W, factor, crop, isBGR, divisor, tta, max_batch,
+                            pool and hasattr(model, "forward_pooled"))
+    up = _Uploader(dev, H, W)
+    state = {"first": True}
+
+    def segment(fa, fb):
+        # enqueue this segment; deliver it at once (the order generator wants its frames now).  The upload of fb was started when it was
+        # read from the source, one segment ahead, by `ahead()` below.
+        sa = uploads.popleft() if state["first"] else None
+        state["first"] = False
+        sb = uploads.popleft()
+        return runner.result(runner.run(up, sa, sb))
+
+    uploads = deque()
+
+    def ahead():
+        """The source frames with the uploads of segment ends started as soon as they are read: one segment ahead of the forwards."""
+        s = int(time_interval)
+        if s < 1:
+            raise ValueError(f"time_interval must be >= 1, got {time_interval!r}")
+        buf = deque()
+        k = 0
+        for f in _chain(first, it):
+            if k % s == 0:
+                uploads.append(up.upload(f))
+            k += 1
+            buf.append(f)
+            # hold back one segment: the generator consuming this sees frame j only after frame j + s has begun to upload
+            while len(buf) > s:
+                yield buf.popleft()
+        while buf:
+            yield buf.popleft()
+    try:
+        for f in nx_sequence(ahead(), segment, factor, time_interval):
+            yield crop_of(f) if (crop is not None and f.shape[:2] == (H, W) and (H, W) != (h, w)) else f
+    finally:
+        runner.close()
+
+
+def _chain(first, it):
+    yield first
+    for f in it:
+        yield f
+
+
+def inference_nx(img0, img1, model, factor: int = 4, isBGR: bool = True, divisor: Optional[int] = 64, tta: bool = False) -> List[np.ndarray]:
+    """Two uint8 [H,W,3] frames -> the ``factor - 1`` uint8 frames between them (t = 1/N ... (N-1)/N), by the recursion of
+    davis-vid.py:102-106."""
+    out = list(interpolate_video_nx([img0, img1], model, factor=factor, isBGR=isBGR, divisor=divisor, tta=tta))
+    return out[1:-1]
+
+
+def video_nx(cap, make_writer, model, factor: int = 4, fps_out: Optional[int] = None, interpolator=None, time_interval: int = 1,
+             crop: Optional[Tuple[int, int]] = None, **kw):
+    """``host_io.video_2x``'s contract for N-x: reads FPS, W, H from ``cap``, opens the sink with ``make_writer(fps_out or factor * FPS
+    // time_interval, (W, H))`` -- the crop's size when cropping -- writes what ``interpolator(frames, model, factor=, time_interval=,
+    crop=, **kw)`` yields (default ``interpolate_video_nx``) and releases both ends, also when a frame fails.  The script hard-codes
+    10 fps (davis-vid.py:74); pass ``fps_out=10`` for that.  Returns ``{"fps_in", "fps_out", "size", "frames_in", "frames_out"}``."""
+    from .host_io import CAP_PROP_FPS, CAP_PROP_FRAME_HEIGHT, CAP_PROP_FRAME_WIDTH, capture_frames
+    nx_levels(factor)
+    fps = int(cap.get(CAP_PROP_FPS))
+    w, h = int(cap.get(CAP_PROP_FRAME_WIDTH)), int(cap.get(CAP_PROP_FRAME_HEIGHT))
+    _, _, oh, ow = centre_window(h, w, crop)
+    rate = int(fps_out) if fps_out else factor * fps // int(time_interval)
+    out = make_writer(rate, (ow, oh))
+    n_in = [0]
+
+    def counted():
+        for f in capture_frames(cap):
+            if f.shape[:2] != (h, w):
+                raise ValueError(f"video_nx: the capture announced {w}x{h} frames and delivered {f.shape[1]}x{f.shape[0]}")
+            n_in[0] += 1
+            yield f
+    n_out = 0
+    try:
+        for frame in (interpolator or interpolate_video_nx)(counted(), model, factor=factor, time_interval=time_interval, crop=crop, **kw):
+            out.write(frame)
+            n_out += 1
+    finally:
+        cap.release()
+        out.release()
+    return {"fps_in": fps, "fps_out": rate, "size": (ow, oh), "frames_in": n_in[0], "frames_out": n_out}

@@ -1012,12 +1012,7 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
             # image pyramids (network_base.py:444-448)
             # Levels >= 1 of both frames live stacked along the batch axis ([:b] = frame 0, [b:] = frame 1): one launch per level
             # instead of two (the same kernels on 2b images); level 0 are the caller's two tensors.
-            pyr0, pyr1 = [im0], [im1]
-            pyr_st = [None]
-            for l in range(1, 4):
-                t = self.buf(f"pyr_{l}", 2 * b, 3, H >> l, W >> l)
-                pyr_st.append(t)
-                pyr0.append(t[:b]); pyr1.append(t[b:])
+            pyr_st = [None] + [self.buf(f"pyr_{l}", 2 * b, 3, H >> l, W >> l) for l in range(1, 4)]
             # encoder + local fusion (:451-455)
             x0 = self.buf("x0", 2 * b, H, W, 4)
             if getattr(ops, "pyramid_packs", False):
@@ -1034,22 +1029,17 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
             if hit:
                 # frame 0 of this pair was frame 1 of the previous call: encoder + fusions (everything that is per frame) on the
                 # new frame only; the previous call's tokens of the shared frame are copied in front of the new ones
-                e1, e2, fuse_l = self._encoder(ops, P, x0[b:], "fc")
-                one = self._fusion(ops, P, "cross_scale_feature_fusion", e1, e2, fuse_l, d[2], d[1], "fcl")   # [B*h*w, C]
+                one, g_one = self._frame_stage(ops, P, x0[b:], "fc", "fcl", glob)                              # [B*h*w, C], [B*h_*w_, cg]
                 feat = self.buf("lfnorm", 2 * b * h * w, C)
                 feat[:b * h * w].copy_(self._frame_cache[1])
                 feat[b * h * w:].copy_(one)
                 if glob:
-                    g_one = self._global_tokens(ops, P, e2, fuse_l, "fc")                                     # [B*h_*w_, cg]
                     n_g = b * (H // 16) * (W // 16)
                     gtok = self.buf("gfnorm", 2 * n_g, cg)
                     gtok[:n_g].copy_(self._frame_cache[2])
                     gtok[n_g:].copy_(g_one)
             else:
-                e1, e2, fuse_l = self._encoder(ops, P, x0, "")
-                feat = self._fusion(ops, P, "cross_scale_feature_fusion", e1, e2, fuse_l, d[2], d[1], "l")       # [2B*h*w, C]
-                if glob:
-                    gtok = self._global_tokens(ops, P, e2, fuse_l, "")                                        # [2B*h_*w_, cg]
+                feat, gtok = self._frame_stage(ops, P, x0, "", "l", glob)                                      # [2B*h*w, C], [2B*h_*w_, cg]
             if cache_ok:
                 keep = self.buf("frame_cache_tokens", b * h * w, C)
                 keep.copy_(feat[b * h * w:])
@@ -1060,6 +1050,151 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
                     keep_g.copy_(gtok[n_g:])
                 self._frame_cache = (ck, keep, keep_g)
             self._reuse_first = False
+            return self._pair_stage(ops, P, im0, im1, pyr_st, feat, gtok)
+
+    def _frame_stage_splitk(self, ops, H: int, W: int, f: int) -> Tuple:
+        """The split-K factors the library would choose for the contraction launches of ``_frame_stage`` on ``f`` frames of H x W, in
+        launch order (``_encoder``, ``_fusion``, ``_global_tokens``).  Under-filled grids with long K are cut over the idle CUs
+        (``gemm_splitk_plan``, ``conv3_plan``: host-side functions of the launch's ROWS), and a different cut sums in a different
+        order: tokens are bit-identical to ``forward``'s only when computed under the same factors.  Empty when the forward is not on
+        the plane kernels (nothing splits there)."""
+        if not (isinstance(ops, HipOps) and self._plane_convs(ops)):
+            return ()
+        v = self._v
+        d = v.hidden_dims
+        c32 = lambda c: (c + 31) // 32
+
+        def gemm(rows, cout, cin, taps=9):
+            if ops.gemm_workspace is None:
+                return 1
+            need = int(ops.lib.atmvfi_gemm_workspace_floats(rows, cout, taps * c32(cin)))
+            return need // (rows * ((cout + 63) // 64 * 64)) if need else 1
+
+        def c3(h, w, cin, cout):
+            need = ops.conv3x3_workspace_floats(f, h, w, cin, cout)
+            return need // (f * h * w * ((cout + 15) // 16 * 16)) if need else 1
+        out = []
+        for st in (1, 2, 3):
+            hs, ws = H >> st, W >> st
+            if st > 1:
+                out.append(gemm(f * hs * ws, d[st], d[st - 1]))                   # feat_extracts.st.0 (stride 2)
+            out.append(c3(hs, ws, d[st], d[st]))                                   # feat_extracts.st.1
+        h, w = H // 8, W // 8
+        out += [gemm(f * h * w, d[2], d[2]), gemm(f * h * w, d[1], d[1]), gemm(f * h * w, d[1], d[1]),      # fusion layers 0..2
+                gemm(f * h * w, v.local_dim, v.local_dim, 1)]                                                  # fusion projection
+        if self.global_motion and not self.ensemble_global_motion:
+            h_, w_ = H // 16, W // 16
+            out += [gemm(f * h_ * w_, v.last_feat_dim, d[3]), c3(h_, w_, v.last_feat_dim, v.last_feat_dim),    # last_feat_extract
+                    gemm(f * h_ * w_, d[3], d[3]), gemm(f * h_ * w_, d[2], d[2]), gemm(f * h_ * w_, d[2], d[2]),
+                    gemm(f * h_ * w_, v.global_dim, v.global_dim, 1)]
+        return tuple(out)
+
+    def forward_pooled(self, pool, left, right, exact: bool = True):
+        """``forward`` on frames that live in a ``multiframe.FramePool``: pair j = (slot ``left[j]``, slot ``right[j]``), batch
+        ``B = len(left)`` (at most 16).  What is per frame (``_frame_stage``) runs ONCE, as one batch, over the referenced slots whose
+        tokens are stale -- never computed, ``put`` since, or computed under other weights / ``global_motion`` / precision -- and is kept
+        in the pool; frames and tokens of the pairs are gathered with ``atmvfi_pool_blocks`` and ``_pair_stage`` runs as in
+        ``forward``.  Returns ``forward``'s dict of fresh tensors, bit-identical to ``forward`` on the same batch.  A stale slot is
+        recomputed, never an error; a pool of another device, another model width or a slot outside the pool raises ``ValueError``.
+        With ``ensemble_global_motion`` nothing is per frame: the frames are gathered and the plain path runs.  Runs eagerly (no
+        launch plan, like the frame cache); every device operation is a launch of the C ABI.  An odd number of stale frames is fed
+        to ``pack_frames`` (which takes pairs) by naming the last one twice; the encoder runs on the distinct ones only.
+
+        ``exact`` (default): bit-identity with ``forward`` holds for every size.  On small frames some launches of the frame stage
+        split K by the number of rows they see (``_frame_stage_splitk``), i.e. by the number of frames in the batch; tokens are then
+        valid only for forwards whose plain frame stage (2B frames) would have used the same factors, and a stale batch whose own
+        count gives other factors is filled up with repeats of its last frame to the nearest count that gives them (2B at the most).
+        At 1088x1920 no launch splits and nothing is ever filled up.  ``exact=False`` skips both: fewest frame encodes, results
+        within rounding of ``forward``'s where the factors differ.  Not part of the reference's API."""
+        left, right = [int(s) for s in left], [int(s) for s in right]
+        b = len(left)
+        if b < 1 or b != len(right) or b > 16:
+            raise ValueError(f"forward_pooled: need 1..16 pairs, got {len(left)} left and {len(right)} right slots")
+        for need in ("frames", "tokens_l", "tokens_g", "keys", "hp", "wp"):
+            if not hasattr(pool, need):
+                raise TypeError("forward_pooled: pool must be a multiframe.FramePool")
+        dev = pool.frames.device
+        if any(s < 0 or s >= pool.slots for s in left + right):
+            raise ValueError(f"forward_pooled: slot outside 0..{pool.slots - 1}")
+        prm = next(self.parameters())
+        if prm.device != dev:
+            raise ValueError(f"forward_pooled: the pool lives on {dev}, the model on {prm.device}")
+        v = self._v
+        H, W = pool.hp, pool.wp
+        if tuple(pool.tokens_l.shape[1:]) != ((H // 8) * (W // 8), v.local_dim) or pool.tokens_g.shape[2] != v.global_dim:
+            raise ValueError("forward_pooled: the pool was made for a model of another shape")
+        need = 16 if self.global_motion else 8
+        if H % need or W % need:
+            raise ValueError(f"H and W must be multiples of {need} (got {H}x{W}); pad with InputPadder as the reference's callers do")
+        ops = self._ops(dev)
+        self._reuse_first = False
+        with torch.cuda.device(dev), torch.no_grad():
+            self._select_workspace((str(dev), (b, 3, H, W), bool(self.global_motion), bool(self.ensemble_global_motion)))
+            ims = self.buf("pool_im", 2 * b, 3, H, W)
+            ops.pool_blocks(pool.frames, left + right, ims)
+            im0, im1 = ims[:b], ims[b:]
+            if self.global_motion and self.ensemble_global_motion:
+                return self._forward_on_device(ops, im0, im1)
+            if hasattr(ops, "begin_forward"):
+                ops.begin_forward()
+            self._rows_fit_planes = 2 * b * H * W < (1 << 26)
+            P = self._prepare(ops)
+            glob = bool(self.global_motion)
+            C, cg = v.local_dim, v.global_dim
+            n_l, n_g = (H // 8) * (W // 8), (H // 16) * (W // 16)
+            target = self._frame_stage_splitk(ops, H, W, 2 * b) if exact else None
+            vkey = (self._prepared_sig, glob, self._precision, self._checked, getattr(ops, "attention_f16x3", None), self._rows_fit_planes,
+                    target)
+            stale = []
+            for s in left + right:
+                if s not in stale and pool.keys[s] != vkey:
+                    stale.append(s)
+            if stale:
+                f = run = len(stale)
+                while exact and run < 2 * b and self._frame_stage_splitk(ops, H, W, run) != target:
+                    run += 1
+                fe = run + (run & 1)
+                g = self.buf("pool_stale", fe, 3, H, W)
+                ops.pool_blocks(pool.frames, stale + stale[-1:] * (fe - f), g)
+                x0 = self.buf("pool_x0", fe, H, W, 4)
+                ops.pack_frames(g[:fe // 2], g[fe // 2:], x0)
+                t_l, t_g = self._frame_stage(ops, P, x0[:run], "fp", "fpl", glob)
+                ops.pool_blocks(pool.tokens_l, stale, t_l[:f * n_l], to_pool=True)
+                if glob:
+                    ops.pool_blocks(pool.tokens_g, stale, t_g[:f * n_g], to_pool=True)
+                for s in stale:
+                    pool.keys[s] = vkey
+            feat = self.buf("lfnorm", 2 * b * n_l, C)
+            ops.pool_blocks(pool.tokens_l, left + right, feat)
+            gtok = None
+            if glob:
+                gtok = self.buf("gfnorm", 2 * b * n_g, cg)
+                ops.pool_blocks(pool.tokens_g, left + right, gtok)
+            pyr_st = [None] + [self.buf(f"pyr_{l}", 2 * b, 3, H >> l, W >> l) for l in range(1, 4)]
+            ops.image_pyramid(im0, im1, pyr_st[1], pyr_st[2], pyr_st[3])
+            return self._pair_stage(ops, P, im0, im1, pyr_st, feat, gtok)
+
+    def _frame_stage(self, ops, P, x0, tag: str, ltag: str, glob: bool):
+        """Everything ``forward`` computes PER FRAME, on the F NHWC4-packed frames ``x0`` [F,H,W,4]: shared_feat_extraction, the
+        cross-scale fusion and its LayerNorm (network_base.py:342-352, 451-455) and, with ``glob`` (global branch on, ensemble off),
+        the per-frame half of estimate_global_motion (:391-400).  Returns the local tokens [F*h*w, C] and the global tokens
+        [F*h_*w_, Cg] (or None) in workspace buffers named by ``tag`` / ``ltag``.  The pair meets in ``_pair_stage``."""
+        d = self._v.hidden_dims
+        e1, e2, fuse_l = self._encoder(ops, P, x0, tag)
+        feat = self._fusion(ops, P, "cross_scale_feature_fusion", e1, e2, fuse_l, d[2], d[1], ltag)
+        return feat, (self._global_tokens(ops, P, e2, fuse_l, tag) if glob else None)
+
+    def _pair_stage(self, ops, P, im0, im1, pyr_st, feat, gtok):
+        """The rest of the forward, from the frame-stacked tokens on: ``feat`` [2B*h*w, C] and ``gtok`` [2B*h_*w_, Cg] (left frames
+        first, then right frames), the contiguous fp32 frames ``im0`` / ``im1`` [B,3,H,W] and their stacked pyramid levels 1..3
+        ``pyr_st`` ([2B,3,H>>l,W>>l]).  Returns the forward's dict."""
+        b, _, H, W = im0.shape
+        v = self._v
+        C = v.local_dim
+        h, w = H // 8, W // 8
+        pyr0 = [im0] + [t[:b] for t in pyr_st[1:]]
+        pyr1 = [im1] + [t[b:] for t in pyr_st[1:]]
+        with torch.no_grad():
             it_list: List[torch.Tensor] = []
             w0_list: List[torch.Tensor] = []
             w1_list: List[torch.Tensor] = []

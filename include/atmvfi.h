@@ -432,6 +432,25 @@ int atmvfi_frame_f32_to_u8(const float* src, int Hp, int Wp, int pad_top, int pa
 int atmvfi_frame_u8_window(const void* src, int H, int W, int bgr, int mode, int y0, int x0, int h, int w, float* dst, int Hp, int Wp,
                            int pad_top, int pad_left, void* dst_u8, void* stream);
 
+/* Multi-frame (4x / 8x recursive) interpolation, benchmark/davis-vid.py:98-135 of the reference: a pool of per-frame state and the
+ * flip-TTA tail.
+ * atmvfi_pool_blocks: n (1..32) blocks of block_bytes between pool slots and one contiguous buffer, in one launch.
+ *   gather  (to_pool 0): buf block j = the first block_bytes of pool + slots[j] * slot_bytes; a slot may be named more than once;
+ *   scatter (to_pool 1): the inverse; a slot named twice is rejected.
+ *   `slots` is a HOST array of n entries, read during the call (it travels in the kernel arguments: no device table, no copy, and the
+ *   launch can be captured).  pool and buf 16-byte aligned, slot_bytes and block_bytes multiples of 16, block_bytes <= slot_bytes,
+ *   0 <= slots[j] < n_slots; the pool spans n_slots * slot_bytes, buf n * block_bytes.  Everything is checked on the host.
+ * atmvfi_tta_merge: out = (pred + rot180(pred_flip)) / 2 in fp32 -- the bits of (pred + pred_flip.flip(H).flip(W)) / 2 -- and / or
+ *   out_u8 = atmvfi_frame_f32_to_u8 of it (crop at (pad_top, pad_left), x * 255 in fp32, round half to even, clamp, RGB -> BGR if
+ *   `bgr`).  Not both NULL; H, W, pad_* are read only with out_u8.  Any alignment; 16-byte accesses when Hp * Wp % 4 == 0 and the fp32
+ *   pointers are 16-byte aligned.  Same bits either way.
+ * atmvfi_frame_rot180: dst = src.flip(H).flip(W) of C contiguous planes (the flattened reversal of each plane); not in place. */
+int atmvfi_pool_blocks(void* pool, int64_t slot_bytes, int n_slots, const int32_t* slots /*HOST array, n entries*/, int n /*1..32*/,
+                       int64_t block_bytes, void* buf, int to_pool, void* stream);
+int atmvfi_tta_merge(const float* pred /*[3,Hp,Wp]*/, const float* pred_flip /*[3,Hp,Wp]*/, float* out /*[3,Hp,Wp] or NULL*/,
+                     void* out_u8 /*uint8 [H,W,3] or NULL*/, int Hp, int Wp, int pad_top, int pad_left, int H, int W, int bgr, void* stream);
+int atmvfi_frame_rot180(const float* src /*[C,Hp,Wp]*/, float* dst, int C, int Hp, int Wp, void* stream);
+
 /* mean |a - b| per sample: global_alignmentness (network_base.py:560-561).  Two passes with a fixed summation order -- the result is
  * run-to-run bit-identical (the ensemble's pick compares these means) -- through `workspace`: at least
  * atmvfi_l1_mean_workspace_floats(B, per_sample) floats of scratch, the caller's. */

@@ -1,0 +1,164 @@
+#!/usr/bin/env python3
+"""Time N-x recursive interpolation (atm-vfi_amd/multiframe.py) and its two data-movement kernels (csrc/multiframe.hip).
+
+End to end: ``interpolate_video_nx`` on uint8 frames in host memory, network_base, global branch on, ``factor`` 4 and 8, at 480x832
+(``divisor=None``, the DAVIS size of benchmark/davis-vid.py) and 1080x1920 (padded to 1088x1920), for ``pool=False`` (plain forwards on
+launch plans: what a caller composing ``Network.forward`` gets), ``pool=True, max_batch=1`` and ``pool=True, max_batch=4``.  Device events
+around the steady state of one video: the first ``--warm`` segments (workspaces, launch plans, pool) are not timed, the next
+``--segments`` are; output frames/s = N x segments / time.  Every configuration is timed ``--repeats`` times in rotation (median, min-max:
+the spread is the noise a difference has to exceed).  Also printed: frames through ``stem_fused`` per steady-state segment.
+
+Kernels alone: ``pool_blocks`` (gather of 8 frame / local-token / global-token blocks of a 1088x1920 base pool, and a scatter) and
+``tta_merge`` / ``frame_rot180`` on 1088x1920 frames, in GB/s of bytes read + written beside the 6.3 TB/s streaming ceiling; the calls
+rotate over ``--buffers`` distinct buffers so that a block does not come from the 256 MB Infinity Cache.
+
+    python tools/bench_nx.py [--sizes 480x832,1080x1920] [--factors 4,8] [--segments 4] [--repeats 3] [--kernels-only] [--json OUT]"""
+import argparse
+import importlib
+import json
+import os
+import statistics
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+pkg = importlib.import_module("atm-vfi_amd")
+hip_ops = importlib.import_module("atm-vfi_amd.hip_ops")
+mf = importlib.import_module("atm-vfi_amd.multiframe")
+HBM = 6.3e12
+MODES = (("pool=False", dict(pool=False, max_batch=4)), ("pool=True mb=1", dict(pool=True, max_batch=1)),
+         ("pool=True mb=4", dict(pool=True, max_batch=4)))
+
+
+def timed(fn, iters, warm=8):
+    for i in range(warm):
+        fn(i)
+    torch.cuda.synchronize()
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    for i in range(iters):
+        fn(i)
+    e.record()
+    e.synchronize()
+    return s.elapsed_time(e) * 1e3 / iters
+
+
+def video(n, h, w, seed=0):
+    rng = np.random.default_rng(seed)
+    base = rng.integers(0, 256, (h + 2 * n, w + 2 * n, 3), dtype=np.uint8)
+    return [np.ascontiguousarray(base[k:k + h, 2 * k:2 * k + w]) for k in range(n)]
+
+
+def run_video(net, frames, factor, warm, segments, divisor, **kw):
+    """-> (ms of the timed segments, frames produced in them)."""
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    got = 0
+    for k, _ in enumerate(mf.interpolate_video_nx(iter(frames), net, factor=factor, divisor=divisor, **kw)):
+        if k == warm * factor:
+            torch.cuda.synchronize()
+            s.record()
+        got = k
+    e.record()
+    e.synchronize()
+    assert got == (warm + segments) * factor
+    return s.elapsed_time(e), segments * factor
+
+
+def stem_per_segment(net, ops, frames, factor, divisor, **kw):
+    counts = []
+    ops.profile = []
+    try:
+        for k, _ in enumerate(mf.interpolate_video_nx(iter(frames[:4]), net, factor=factor, divisor=divisor, **kw)):
+            if k % factor == 0:
+                counts.append(sum(int(m["shape"].split("x")[0]) for nm, m, _, _ in ops.profile if nm == "stem_fused"))
+    finally:
+        ops.profile = None
+    return counts[2] - counts[1]
+
+
+def kernels(ops, dev, iters, nbuf, rows):
+    v = pkg.VARIANTS["base"]
+    hp, wp = 1088, 1920
+    blocks = {"frames": 3 * hp * wp, "local tokens": (hp // 8) * (wp // 8) * v.local_dim, "global tokens": (hp // 16) * (wp // 16) * v.global_dim}
+    slots = [8, 0, 4, 2, 6, 1, 3, 5]
+    cfg = {}
+    for name, elems in blocks.items():
+        pools = [torch.rand(9, elems, device=dev) for _ in range(2)]
+        bufs = [torch.empty(8, elems, device=dev) for _ in range(2)]
+        cfg[f"pool_blocks gather 8 x {name}"] = (lambda i, p=pools, b=bufs: ops.pool_blocks(p[i % 2], slots, b[i % 2]), 2.0 * 8 * elems * 4)
+        cfg[f"pool_blocks scatter 8 x {name}"] = (lambda i, p=pools, b=bufs: ops.pool_blocks(p[i % 2], slots, b[i % 2], to_pool=True), 2.0 * 8 * elems * 4)
+    cfg["pool_blocks gather 1 x 16 B"] = (lambda i, p=torch.rand(9, 4, device=dev), b=torch.empty(1, 4, device=dev): ops.pool_blocks(p, [3], b), 32.0)
+    fr = [torch.rand(3, hp, wp, device=dev) for _ in range(nbuf)]
+    outs = [torch.empty(3, hp, wp, device=dev) for _ in range(nbuf)]
+    u8 = [torch.empty(1080, 1920, 3, dtype=torch.uint8, device=dev) for _ in range(nbuf)]
+    pl = 12.0 * hp * wp
+    cfg["tta_merge fp32 + u8"] = (lambda i: ops.tta_merge(fr[i % nbuf], fr[(i + 1) % nbuf], out=outs[i % nbuf], out_u8=u8[i % nbuf], pad_top=4), 3 * pl + 3.0 * 1080 * 1920)
+    cfg["tta_merge u8 only"] = (lambda i: ops.tta_merge(fr[i % nbuf], fr[(i + 1) % nbuf], out_u8=u8[i % nbuf], pad_top=4), 2 * pl + 3.0 * 1080 * 1920)
+    cfg["frame_rot180"] = (lambda i: ops.frame_rot180(fr[i % nbuf], outs[i % nbuf]), 2 * pl)
+    cfg["torch flip/flip/add/div (yardstick)"] = (lambda i: (fr[i % nbuf] + fr[(i + 1) % nbuf].flip(1).flip(2)) / 2, 3 * pl)
+    times = {k: [] for k in cfg}
+    for _ in range(3):
+        for k, (fn, _) in cfg.items():
+            times[k].append(timed(fn, iters))
+    for k, (_, nbytes) in cfg.items():
+        t = times[k]
+        med = statistics.median(t)
+        rows.append({"name": k, "us_median": med, "us_min": min(t), "us_max": max(t), "bytes": nbytes, "GBps": nbytes / (med * 1e-6) / 1e9})
+        print(f"{k:>42}: {med:9.2f} us (min {min(t):.2f}, max {max(t):.2f})  {nbytes / 1e6:8.1f} MB  {rows[-1]['GBps']:7.1f} GB/s  "
+              f"{100 * rows[-1]['GBps'] * 1e9 / HBM:5.1f}% of 6.3 TB/s", flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--sizes", default="480x832,1080x1920")
+    ap.add_argument("--factors", default="4,8")
+    ap.add_argument("--segments", type=int, default=4)
+    ap.add_argument("--warm", type=int, default=3)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--iters", type=int, default=60)
+    ap.add_argument("--buffers", type=int, default=12)
+    ap.add_argument("--kernels-only", action="store_true")
+    ap.add_argument("--no-kernels", action="store_true")
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("bench_nx: no GPU")
+    dev = torch.device("cuda:0")
+    torch.set_grad_enabled(False)
+    result = {"device": torch.cuda.get_device_name(0), "kernels": [], "videos": []}
+    if not a.no_kernels:
+        kernels(hip_ops.HipOps(dev), dev, a.iters, max(2, a.buffers), result["kernels"])
+    if not a.kernels_only:
+        net = pkg.NetworkBase()
+        net.load_state_dict(pkg.synthetic_state_dict("base", seed=1), strict=True)
+        net.to(dev).eval()
+        net.global_motion, net.ensemble_global_motion = True, False
+        ops = net._ops(dev)
+        for size in a.sizes.split(","):
+            h, w = (int(x) for x in size.split("x"))
+            divisor = None if (h % 16 == 0 and w % 16 == 0) else 64
+            frames = video(a.warm + a.segments + 1, h, w)
+            for factor in (int(x) for x in a.factors.split(",")):
+                times = {name: [] for name, _ in MODES}
+                for _ in range(a.repeats):            # in rotation: pool=False is the baseline of the same process and run
+                    for name, kw in MODES:
+                        ms, n = run_video(net, frames, factor, a.warm, a.segments, divisor, **kw)
+                        times[name].append(n / (ms * 1e-3))
+                for name, kw in MODES:
+                    t = times[name]
+                    row = {"size": size, "factor": factor, "mode": name, "fps_median": statistics.median(t), "fps_min": min(t), "fps_max": max(t),
+                           "stem_frames_per_segment": stem_per_segment(net, ops, frames, factor, divisor, **kw), "repeats_fps": t}
+                    result["videos"].append(row)
+                    print(f"{size:>10} {factor}x {name:>15}: {row['fps_median']:8.2f} output frames/s (min {min(t):.2f}, max {max(t):.2f} over "
+                          f"{len(t)} repeats)  stem_fused frames / segment {row['stem_frames_per_segment']}", flush=True)
+                net.release_workspace()
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(result, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
