@@ -133,6 +133,8 @@ SIGNATURES = {
     "atmvfi_pool_blocks": (c_i, [c_f, c_l, c_i, ctypes.POINTER(ctypes.c_int32), c_i, c_l, c_f, c_i, c_f]),
     "atmvfi_tta_merge": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f]),
     "atmvfi_frame_rot180": (c_i, [c_f, c_f, c_i, c_i, c_i, c_f]),
+    "atmvfi_frame_signature_workspace_ints": (c_l, [c_i, c_i]),
+    "atmvfi_frame_signature": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_l, c_f]),
     "atmvfi_pack_frames": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_f]),
     "atmvfi_final_residual": (c_i, [c_f, c_f, c_i, c_f, c_f, c_i, c_i, c_i, c_f]),
     "atmvfi_l1_mean": (c_i, [c_f, c_f, c_f, c_i, c_l, c_f, c_l, c_f]),
@@ -1223,6 +1225,41 @@ class HipOps:
         meta = {"bytes": 3.0 * scale * scale * h * w + (12.0 * hp * wp if dst is not None else 0.0) + (3.0 * h * w if dst_u8 is not None else 0.0)}
         self._run("frame_u8_window", meta, self.lib.atmvfi_frame_u8_window, _ptr(src_u8), sh, sw, int(bgr), int(mode), int(y0), int(x0),
                   int(h), int(w), _ptr(dst), hp, wp, int(pad_top), int(pad_left), _ptr(dst_u8), self._stream())
+
+    def frame_signature_workspace(self, h: int, w: int):
+        """A fresh int32 scratch tensor for ``frame_signature`` on an h x w window (one per stream that computes signatures)."""
+        n = self.lib.atmvfi_frame_signature_workspace_ints(int(h), int(w))
+        if n < 0:
+            raise ValueError(f"frame_signature: {self.lib.atmvfi_last_error().decode()}")
+        return torch.empty(n, dtype=torch.int32, device=self.device)
+
+    def frame_signature(self, src_u8, y0: int = 0, x0: int = 0, h: Optional[int] = None, w: Optional[int] = None, bgr: bool = False,
+                        out=None, workspace=None):
+        """The scene-cut signature of the h x w window at (y0, x0) (default: the whole frame) of a resident uint8 [H,W,3] frame: int32
+        [288] on the device = 16 x 16 luma cell sums + 32 luma bins (include/atmvfi.h atmvfi_frame_signature; the bits of
+        ``scene.signature_numpy``).  ``out`` is written completely (a new tensor when None).  ``workspace``: the call's scratch
+        (``frame_signature_workspace``); None: one kept per (window size, stream) by this object.  Not part of a forward: never recorded
+        into a launch plan."""
+        if src_u8.dtype != torch.uint8 or src_u8.dim() != 3 or src_u8.shape[2] != 3 or not src_u8.is_contiguous() or not src_u8.is_cuda:
+            raise ValueError("frame_signature: source must be a contiguous CUDA uint8 [H,W,3] tensor")
+        sh, sw = src_u8.shape[:2]
+        h = sh - int(y0) if h is None else int(h)
+        w = sw - int(x0) if w is None else int(w)
+        if out is None:
+            out = torch.empty(288, dtype=torch.int32, device=src_u8.device)
+        elif out.dtype != torch.int32 or out.numel() != 288 or not out.is_contiguous() or not out.is_cuda:
+            raise ValueError("frame_signature: out must be a contiguous CUDA int32 tensor of 288 words")
+        if workspace is None:
+            cache = self.__dict__.setdefault("_signature_workspaces", {})
+            key = (h, w, torch.cuda.current_stream(self.device).cuda_stream)
+            workspace = cache.get(key)
+            if workspace is None:
+                workspace = cache[key] = self.frame_signature_workspace(h, w)
+        elif workspace.dtype != torch.int32 or not workspace.is_contiguous() or not workspace.is_cuda:
+            raise ValueError("frame_signature: workspace must be a contiguous CUDA int32 tensor")
+        self._check(self.lib.atmvfi_frame_signature(_ptr(src_u8), sh, sw, int(bool(bgr)), int(y0), int(x0), h, w, _ptr(out), _ptr(workspace),
+                                                    workspace.numel(), self._stream()), "frame_signature")
+        return out
 
     def frame_f32_to_u8(self, src, dst_u8, pad_top: int, pad_left: int, bgr: bool):
         """fp32 planar [3,Hp,Wp] -> crop -> np.round(x * 255) -> uint8 [H,W,3] device tensor (optional RGB -> BGR)."""

@@ -230,9 +230,16 @@ class FramePipeline:
     fp32 tensors the reference moves).  ``run`` yields frames in order; a yielded array is a fresh copy.  Measured at 1080p on one
     MI355X (tools/bench_hostio.py, tools/diag_hostio.py): 25.0 ms resident, 26.9 ms per frame at depth 1 and 25.2 ms at depth 3 -- the
     pieces are small (H2D 1.0 ms, enqueue 2.8 ms of CPU, pre/post kernels < 0.1 ms) and at depth 3 the GPU queue never runs dry
-    (gap between consecutive forwards 0.03 ms)."""
+    (gap between consecutive forwards 0.03 ms).
 
-    def __init__(self, model, height: int, width: int, isBGR: bool = True, divisor: int = 64, depth: int = 3, streams: int = 1):
+    ``scene`` (a ``scene.SceneCuts``; default None: the pipeline as above): scene-cut detection.  The signature of a pair's second
+    frame (``HipOps.frame_signature``; of both frames when the pair's first is not the previous pair's second, by identity) is computed
+    on the copy stream right behind the pair's upload and copied back into pinned words of the slot; ``_compute`` reads it -- the
+    event was recorded one pair ahead, when the upload was issued under the previous pair's forward -- and for a cut enqueues NO
+    forward: the pair's frame is a bit-equal copy of its first original."""
+
+    def __init__(self, model, height: int, width: int, isBGR: bool = True, divisor: int = 64, depth: int = 3, streams: int = 1,
+                 scene=None):
         ops, dev = _hip_ops_of(model)
         if ops is None:
             raise RuntimeError("FramePipeline needs an atm-vfi_amd Network on the GPU")
@@ -257,6 +264,14 @@ class FramePipeline:
         for slot in self.slots:
             slot["h_in_np"] = slot["h_in"].numpy()
         self.copy_in, self.copy_out = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
+        self.scene = scene
+        if scene is not None:
+            for slot in self.slots:
+                slot["sig_d"] = mk(2, 288, dt=torch.int32)
+                slot["sig_h"] = torch.empty(2, 288, dtype=torch.int32).pin_memory()
+                slot["sig_h_np"], slot["sig_ready"] = slot["sig_h"].numpy(), torch.cuda.Event()
+            self._sig_ws = ops.frame_signature_workspace(height, width)       # one: every signature runs on the copy stream
+            self._last_b, self._last_sig = None, None
 
     def _upload(self, slot, pair):
         a, b = pair
@@ -269,8 +284,30 @@ class FramePipeline:
         with torch.cuda.stream(self.copy_in):
             slot["d_in"].copy_(slot["h_in"], non_blocking=True)
             slot["in_ready"].record(self.copy_in)
+            if self.scene is not None:
+                # a frame's signature is computed once: the first frame's only when it is not the previous pair's second
+                slot["first"], slot["chained"], self._last_b = a, a is self._last_b, b
+                for k in ((1,) if slot["chained"] else (0, 1)):
+                    self.ops.frame_signature(slot["d_in"][k], bgr=self.bgr, out=slot["sig_d"][k], workspace=self._sig_ws)
+                slot["sig_h"].copy_(slot["sig_d"], non_blocking=True)
+                slot["sig_ready"].record(self.copy_in)
+
+    def _is_cut(self, slot) -> bool:
+        slot["sig_ready"].synchronize()                  # recorded one pair ahead (see the class comment)
+        sig_a = self._last_sig if slot["chained"] else slot["sig_h_np"][0].copy()
+        self._last_sig = slot["sig_h_np"][1].copy()
+        return self.scene.judge(sig_a, self._last_sig, self.h, self.w)
+
+    def _deliver(self, slot):
+        if slot["cut"]:
+            return np.array(slot["first"], copy=True)
+        slot["out_ready"].synchronize()
+        return slot["h_out"].numpy().copy()
 
     def _compute(self, slot):
+        slot["cut"] = self.scene is not None and self._is_cut(slot)
+        if slot["cut"]:
+            return
         if self.lanes is not None:
             i = self._k % self.lanes.k
             self._k += 1
@@ -295,6 +332,9 @@ class FramePipeline:
     def run(self, pairs):
         if self.lanes is not None:
             self.lanes._sync_flags()
+        if self.scene is not None:
+            self.scene.begin()
+            self._last_b = self._last_sig = None
         it = iter(pairs)
         inflight = []                      # slots whose compute has been enqueued, oldest first
         nxt = next(it, None)
@@ -310,20 +350,18 @@ class FramePipeline:
                 nxt = next(it, None)
                 if nxt is not None:
                     if len(inflight) == self.depth:          # the next slot is still owned by the oldest pair: deliver it first
-                        old = inflight.pop(0)
-                        old["out_ready"].synchronize()
-                        yield old["h_out"].numpy().copy()
+                        yield self._deliver(inflight.pop(0))
                     self._upload(self.slots[k % self.depth], nxt)      # overlaps the forward just enqueued
                     continue
-            old = inflight.pop(0)
-            old["out_ready"].synchronize()
-            yield old["h_out"].numpy().copy()
+            yield self._deliver(inflight.pop(0))
 
 
-def interpolate_video_2x(frames, model, isBGR: bool = True, divisor: int = 64, depth: int = 3, streams: int = 1):
+def interpolate_video_2x(frames, model, isBGR: bool = True, divisor: int = 64, depth: int = 3, streams: int = 1, scene=None):
     """The frame loop of demo_2x.py:144-163 over any iterable of uint8 [H,W,3] frames (decoding / encoding stays with the caller):
     yields f0, I(f0,f1), f1, I(f1,f2), ..., f_{n-1} -- 2n-1 frames -- with the pairs running through ``FramePipeline``
-    (``streams`` > 1: that many forwards in flight on streams of their own, for frames too small to fill the GPU one at a time)."""
+    (``streams`` > 1: that many forwards in flight on streams of their own, for frames too small to fill the GPU one at a time).
+    ``scene`` (a ``scene.SceneCuts``; not in the script): a pair classed a scene cut runs no forward and its middle frame is a copy of
+    the pair's first frame; ``scene.cuts`` holds the cut pairs' indices afterwards."""
     from collections import deque
     it = iter(frames)
     first = next(it, None)
@@ -337,7 +375,7 @@ def interpolate_video_2x(frames, model, isBGR: bool = True, divisor: int = 64, d
             originals.append(cur)
             yield prev, cur
             prev = cur
-    pipe = FramePipeline(model, first.shape[0], first.shape[1], isBGR=isBGR, divisor=divisor, depth=depth, streams=streams)
+    pipe = FramePipeline(model, first.shape[0], first.shape[1], isBGR=isBGR, divisor=divisor, depth=depth, streams=streams, scene=scene)
     for pred in pipe.run(pairs()):
         yield originals.popleft()
         yield pred
@@ -365,7 +403,8 @@ def video_2x(cap, make_writer, model, isBGR: bool = True, divisor: int = 64, dep
     twice the rate), writes f0, I(f0,f1), f1, ..., f_{n-1} -- every original once, the last frame once (:148-150, 160) -- and releases
     both ends (:165-166).  The codec stays with the caller: with OpenCV, ``cap = cv2.VideoCapture(path)`` and ``make_writer = lambda
     fps, size: cv2.VideoWriter(out, cv2.VideoWriter_fourcc(*'mp4v'), fps, size)``.  ``interpolator(frames, model, ...)`` defaults to
-    ``interpolate_video_2x`` (the pipelined HIP path).  Returns ``{"fps_in", "fps_out", "size", "frames_in", "frames_out"}``.
+    ``interpolate_video_2x`` (the pipelined HIP path).  Returns ``{"fps_in", "fps_out", "size", "frames_in", "frames_out"}``, and with
+    ``scene=SceneCuts(...)`` among ``kw`` also ``"cuts"``: the indices of the pairs classed scene cuts.
     Not provided: ``--combine_video`` (cv2.putText drawing, :88-97).  An empty video writes nothing (the reference raises NameError)."""
     fps = int(cap.get(CAP_PROP_FPS))
     w, h = int(cap.get(CAP_PROP_FRAME_WIDTH)), int(cap.get(CAP_PROP_FRAME_HEIGHT))
@@ -386,7 +425,10 @@ def video_2x(cap, make_writer, model, isBGR: bool = True, divisor: int = 64, dep
     finally:
         cap.release()
         out.release()
-    return {"fps_in": fps, "fps_out": 2 * fps, "size": (w, h), "frames_in": n_in[0], "frames_out": n_out}
+    info = {"fps_in": fps, "fps_out": 2 * fps, "size": (w, h), "frames_in": n_in[0], "frames_out": n_out}
+    if kw.get("scene") is not None:
+        info["cuts"] = list(kw["scene"].cuts)
+    return info
 
 
 def interpolate_video_2x_distributed(frames, model, rank: int, world: int, isBGR: bool = True, divisor: int = 64, block: int = 4,
@@ -598,3 +640,5 @@ def load_model_checkpoint(model, checkpoint_path, strict: bool = True, map_locat
 
 # 4x / 8x recursive interpolation (benchmark/davis-vid.py): atm-vfi_amd/multiframe.py
 from .multiframe import (FramePool, inference_nx, interpolate_video_nx, nx_levels, nx_sequence, video_nx)  # noqa: E402,F401
+# scene-cut detection for the video loops above (not in the reference): atm-vfi_amd/scene.py
+from .scene import SceneCuts, cut_statistics, signature_numpy  # noqa: E402,F401

@@ -11,6 +11,8 @@ prediction -- with a centre crop, a frame stride (``time_interval``) and optiona
 Deviations from the script, on purpose: (1) with ``tta`` EVERY produced frame is the flip-TTA average (the script averages the middle
 frame only); the next level still consumes the un-averaged prediction, as the script's order of operations has it (:102-112).  (2) with
 a crop the originals are written cropped (the script hands the uncropped originals to a writer opened at the crop size, :86, 120, 135).
+Opt-in, not in the script at all: ``scene=SceneCuts()`` (atm-vfi_amd/scene.py) runs no forward for a segment that straddles a shot
+change and emits copies of the nearer original.
 """
 from __future__ import annotations
 
@@ -134,16 +136,28 @@ class FramePool:
 # ------------------------------------------------------------------------------------------------ runner
 class _Uploader:
     """Every source frame goes to the device ONCE: a ring of pinned host slots + device staging filled on a copy stream, ahead of the
-    kernel that converts it (as ``host_io.interpolate_video_2x_distributed`` does)."""
+    kernel that converts it (as ``host_io.interpolate_video_2x_distributed`` does).
 
-    def __init__(self, dev, height: int, width: int, depth: int = 3):
+    ``signature=(ops, (y0, x0, h, w), bgr)`` (scene-cut detection): the frame's signature (``HipOps.frame_signature``) is computed ONCE,
+    on the copy stream right behind the copy that brought the frame, and its 1 152 bytes follow it back into a pinned word array of the
+    slot; ``signature(slot)`` waits for that event -- recorded when the upload was issued, one segment before the segment that asks --
+    and returns the words."""
+
+    def __init__(self, dev, height: int, width: int, depth: int = 3, signature=None):
         import torch
         self.torch, self.dev, self.h, self.w, self.depth = torch, dev, height, width, depth
+        self.sig = signature
         self.ring = [{"h": torch.empty(height, width, 3, dtype=torch.uint8).pin_memory(),
                       "d": torch.empty(height, width, 3, dtype=torch.uint8, device=dev),
                       "ready": torch.cuda.Event(), "free": torch.cuda.Event()} for _ in range(depth)]
         for s in self.ring:
             s["h_np"] = s["h"].numpy()
+            if signature is not None:
+                s["sig_d"] = torch.empty(288, dtype=torch.int32, device=dev)
+                s["sig_h"] = torch.empty(288, dtype=torch.int32).pin_memory()
+                s["sig_h_np"], s["sig_ready"] = s["sig_h"].numpy(), torch.cuda.Event()
+        if signature is not None:                     # one scratch: every signature runs on the copy stream, one after the other
+            self.sig_ws = signature[0].frame_signature_workspace(*signature[1][2:])
         self.copy_in = torch.cuda.Stream(dev)
         self.issued = 0
 
@@ -159,8 +173,18 @@ class _Uploader:
         with torch.cuda.stream(self.copy_in):
             slot["d"].copy_(slot["h"], non_blocking=True)
             slot["ready"].record(self.copy_in)
+            if self.sig is not None:
+                ops, (y0, x0, h, w), bgr = self.sig
+                ops.frame_signature(slot["d"], y0, x0, h, w, bgr=bgr, out=slot["sig_d"], workspace=self.sig_ws)
+                slot["sig_h"].copy_(slot["sig_d"], non_blocking=True)
+                slot["sig_ready"].record(self.copy_in)
         self.issued += 1
         return slot
+
+    def signature(self, slot) -> np.ndarray:
+        """The int32[288] signature of the frame in ``slot`` (a copy; the slot's words are rewritten by its next upload)."""
+        slot["sig_ready"].synchronize()
+        return slot["sig_h_np"].copy()
 
     def take(self, slot, convert):
         """Run ``convert(device uint8 frame)`` on the current stream once the slot's copy has landed."""
@@ -257,9 +281,11 @@ class _SegmentRunner:
         self.ops.pool_blocks(self.frames[k], lefts + rights, g)
         return self.model.forward(g[:b], g[b:])["I_t"]
 
-    def run(self, up: _Uploader, slot_a, slot_b):
+    def run(self, up: _Uploader, slot_a, slot_b, cut: bool = False):
         """Enqueue one segment: ``slot_a`` (None when the previous segment's second frame is this one's first) and ``slot_b`` are
-        upload slots.  Returns a handle for ``result``."""
+        upload slots.  Returns a handle for ``result``.  ``cut`` (a scene cut: the caller emits copies of the originals): the source
+        frames still take their places -- position N's frame, with tokens marked stale, is the next segment's position 0 whatever this
+        segment was -- but no forward runs, nothing is written to the middle slots or the output ring, and None is returned."""
         torch, n = self.torch, self.n
         with torch.cuda.device(self.dev):
             if self.have_first:
@@ -268,6 +294,8 @@ class _SegmentRunner:
                 up.take(slot_a, self._convert_into(0))
                 self.have_first = True
             up.take(slot_b, self._convert_into(n))
+            if cut:
+                return None
             ring = self.seg & 1
             self.seg += 1
             last = len(self.levels) - 1
@@ -358,7 +386,7 @@ def _generic_segment(model, factor, crop_of, isBGR, divisor, tta, max_batch):
 
 
 def interpolate_video_nx(frames, model, factor: int = 4, time_interval: int = 1, crop: Optional[Tuple[int, int]] = None, isBGR: bool = True,
-                         divisor: Optional[int] = 64, tta: bool = False, max_batch: int = 4, pool: bool = True):
+                         divisor: Optional[int] = 64, tta: bool = False, max_batch: int = 4, pool: bool = True, scene=None):
     """N-x slow motion over any iterable of uint8 [H,W,3] frames (davis-vid.py:88-135; decoding / encoding stays with the caller):
     per segment ``(f_i, f_{i+s})``, ``s = time_interval``, yields ``f_i`` and the frames at t = 1/N ... (N-1)/N, after the last segment
     its second frame once -- ``segments * N + 1`` frames.  Originals pass through bit-equal (their centre ``crop=(h, w)`` window when
@@ -370,9 +398,17 @@ def interpolate_video_nx(frames, model, factor: int = 4, time_interval: int = 1,
     produced frame is the flip-TTA average; the next level consumes the un-averaged prediction.  ``pool=True``: per-frame work once per
     distinct frame (``Network.forward_pooled``); ``pool=False``: plain ``model.forward`` calls on the same level batches (same
     outputs; the A/B baseline, and what a model without ``forward_pooled`` gets).  The runner raises ``model.max_workspaces`` to the
-    number of batch sizes of its schedule while it runs and restores it.  ``factor=2`` gives ``interpolate_video_2x``'s frames."""
+    number of batch sizes of its schedule while it runs and restores it.  ``factor=2`` gives ``interpolate_video_2x``'s frames.
+
+    ``scene`` (a ``scene.SceneCuts``; default None: the loop as above): scene-cut detection, not in the script.  The signatures of
+    the two ends of every segment (of the crop window; computed on the device where the frame lands, one segment ahead) are compared;
+    a segment classed a cut runs NO forward and its N - 1 positions are bit-equal copies of the nearer original -- position k <= N/2
+    the first, k > N/2 the second, cropped when cropping.  ``scene.cuts`` / ``scene.stats`` hold the run's record."""
     from .host_io import _hip_ops_of
+    from .scene import cut_fill, signature_numpy
     nx_levels(factor)
+    if scene is not None:
+        scene.begin()
     it = iter(frames)
     first = next(it, None)
     if first is None:
@@ -383,13 +419,23 @@ def interpolate_video_nx(frames, model, factor: int = 4, time_interval: int = 1,
     ops, dev = _hip_ops_of(model)
     if ops is None or not hasattr(ops, "pool_blocks"):
         seg = _generic_segment(model, factor, crop_of, isBGR, divisor, tta, max(1, int(max_batch)))
+        if scene is not None:
+            forward_segment, known = seg, {"of": None, "sig": None}
+
+            def seg(a, b):
+                sig_a = known["sig"] if known["of"] is a else signature_numpy(a, (y0, x0, h, w), bgr=isBGR)
+                sig_b = signature_numpy(b, (y0, x0, h, w), bgr=isBGR)
+                known.update(of=b, sig=sig_b)                # b is the next segment's first frame
+                if scene.judge(sig_a, sig_b, h, w):
+                    return cut_fill(crop_of(a), crop_of(b), factor)
+                return forward_segment(a, b)
         for f in nx_sequence(_chain(first, it), lambda a, b: seg(a, b), factor, time_interval):
             yield f if f.shape[:2] == (h, w) else crop_of(f)
         return
     runner = _SegmentRunner(model, ops, dev, H, W, factor, crop, isBGR, divisor, tta, max_batch,
                             pool and hasattr(model, "forward_pooled"))
-    up = _Uploader(dev, H, W)
-    state = {"first": True}
+    up = _Uploader(dev, H, W, signature=None if scene is None else (ops, (y0, x0, h, w), bool(isBGR)))
+    state = {"first": True, "sig": None}
 
     def segment(fa, fb):
         # enqueue this segment; deliver it at once (the order generator wants its frames now).  The upload of fb was started when it was
@@ -397,6 +443,14 @@ def interpolate_video_nx(frames, model, factor: int = 4, time_interval: int = 1,
         sa = uploads.popleft() if state["first"] else None
         state["first"] = False
         sb = uploads.popleft()
+        if scene is not None:
+            # both signatures were enqueued with their uploads, fb's one segment ago: in steady state the event has long completed
+            if sa is not None:
+                state["sig"] = up.signature(sa)
+            sig_a, state["sig"] = state["sig"], up.signature(sb)
+            if scene.judge(sig_a, state["sig"], h, w):
+                runner.run(up, sa, sb, cut=True)
+                return cut_fill(crop_of(fa), crop_of(fb), factor)
         return runner.result(runner.run(up, sa, sb))
 
     uploads = deque()
@@ -443,7 +497,8 @@ def video_nx(cap, make_writer, model, factor: int = 4, fps_out: Optional[int] = 
     """``host_io.video_2x``'s contract for N-x: reads FPS, W, H from ``cap``, opens the sink with ``make_writer(fps_out or factor * FPS
     // time_interval, (W, H))`` -- the crop's size when cropping -- writes what ``interpolator(frames, model, factor=, time_interval=,
     crop=, **kw)`` yields (default ``interpolate_video_nx``) and releases both ends, also when a frame fails.  The script hard-codes
-    10 fps (davis-vid.py:74); pass ``fps_out=10`` for that.  Returns ``{"fps_in", "fps_out", "size", "frames_in", "frames_out"}``."""
+    10 fps (davis-vid.py:74); pass ``fps_out=10`` for that.  Returns ``{"fps_in", "fps_out", "size", "frames_in", "frames_out"}``, and
+    with ``scene=SceneCuts(...)`` among ``kw`` also ``"cuts"``: the indices of the segments classed scene cuts."""
     from .host_io import CAP_PROP_FPS, CAP_PROP_FRAME_HEIGHT, CAP_PROP_FRAME_WIDTH, capture_frames
     nx_levels(factor)
     fps = int(cap.get(CAP_PROP_FPS))
@@ -467,4 +522,7 @@ def video_nx(cap, make_writer, model, factor: int = 4, fps_out: Optional[int] = 
     finally:
         cap.release()
         out.release()
-    return {"fps_in": fps, "fps_out": rate, "size": (ow, oh), "frames_in": n_in[0], "frames_out": n_out}
+    info = {"fps_in": fps, "fps_out": rate, "size": (ow, oh), "frames_in": n_in[0], "frames_out": n_out}
+    if kw.get("scene") is not None:
+        info["cuts"] = list(kw["scene"].cuts)
+    return info

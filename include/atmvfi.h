@@ -451,6 +451,23 @@ int atmvfi_tta_merge(const float* pred /*[3,Hp,Wp]*/, const float* pred_flip /*[
                      void* out_u8 /*uint8 [H,W,3] or NULL*/, int Hp, int Wp, int pad_top, int pad_left, int H, int W, int bgr, void* stream);
 int atmvfi_frame_rot180(const float* src /*[C,Hp,Wp]*/, float* dst, int C, int Hp, int Wp, void* stream);
 
+/* Frame signature for scene-cut detection in the video loops (scene.hip; atm-vfi_amd/scene.py compares two of them).  Nothing of the
+ * reference: its scripts only see single-shot clips.  One resident uint8 [H,W,3] frame (contiguous; BGR if `bgr`) and the window
+ * (y0, x0, h, w) -> int32 sig[288] on the device:
+ *   luma          Y = (77 R + 150 G + 29 B + 128) >> 8;
+ *   sig[16 i + j] = the sum of Y over rows [i h / 16, (i + 1) h / 16) and columns [j w / 16, (j + 1) w / 16) of the window (integer
+ *                   division: a 16 x 16 grid of cells, row-major);
+ *   sig[256 + b]  = the number of window pixels with Y >> 3 == b (32 bins).
+ * h, w >= 16, the window inside the frame, and small enough that cell sums and bin counts fit int32 (ATMVFI_EINVAL otherwise).  Any
+ * geometry and pointer alignment of src is accepted; dword loads are used when src is 4-byte aligned and W, x0 and w are multiples of 4.
+ * Integer arithmetic only: both paths and any reduction order give the same bits.  sig (4-byte aligned) is written completely by the
+ * call: nothing is pre-zeroed and no global atomics are used.  workspace: at least atmvfi_frame_signature_workspace_ints(h, w) int32 of
+ * scratch, the caller's (per-workgroup partials, reduced by a second launch of the same call); the query returns -1 for a window the
+ * call would refuse.  Stream-ordered: two launches, no host synchronisation, no allocation. */
+int64_t atmvfi_frame_signature_workspace_ints(int h, int w);
+int atmvfi_frame_signature(const void* src, int H, int W, int bgr, int y0, int x0, int h, int w, int32_t* sig /*[288]*/, int32_t* workspace,
+                           int64_t workspace_ints, void* stream);
+
 /* mean |a - b| per sample: global_alignmentness (network_base.py:560-561).  Two passes with a fixed summation order -- the result is
  * run-to-run bit-identical (the ensemble's pick compares these means) -- through `workspace`: at least
  * atmvfi_l1_mean_workspace_floats(B, per_sample) floats of scratch, the caller's. */

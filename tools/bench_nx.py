@@ -12,7 +12,12 @@ Kernels alone: ``pool_blocks`` (gather of 8 frame / local-token / global-token b
 ``tta_merge`` / ``frame_rot180`` on 1088x1920 frames, in GB/s of bytes read + written beside the 6.3 TB/s streaming ceiling; the calls
 rotate over ``--buffers`` distinct buffers so that a block does not come from the 256 MB Infinity Cache.
 
-    python tools/bench_nx.py [--sizes 480x832,1080x1920] [--factors 4,8] [--segments 4] [--repeats 3] [--kernels-only] [--json OUT]"""
+``--scene``: every mode is also timed with scene-cut detection on (``scene=SceneCuts()``: a frame signature per uploaded frame and a
+host read of it per segment), interleaved with the same mode without it; the input is cut-free (asserted), so the difference is
+the detection's cost.  ``--modes``: only the modes whose name contains one of the given comma-separated strings.
+
+    python tools/bench_nx.py [--sizes 480x832,1080x1920] [--factors 4,8] [--segments 4] [--repeats 3] [--kernels-only] [--scene]
+                             [--modes "mb=4"] [--json OUT]"""
 import argparse
 import importlib
 import json
@@ -28,6 +33,7 @@ sys.path.insert(0, ROOT)
 pkg = importlib.import_module("atm-vfi_amd")
 hip_ops = importlib.import_module("atm-vfi_amd.hip_ops")
 mf = importlib.import_module("atm-vfi_amd.multiframe")
+scene = importlib.import_module("atm-vfi_amd.scene")
 HBM = 6.3e12
 MODES = (("pool=False", dict(pool=False, max_batch=4)), ("pool=True mb=1", dict(pool=True, max_batch=1)),
          ("pool=True mb=4", dict(pool=True, max_batch=4)))
@@ -64,6 +70,7 @@ def run_video(net, frames, factor, warm, segments, divisor, **kw):
     e.record()
     e.synchronize()
     assert got == (warm + segments) * factor
+    assert kw.get("scene") is None or kw["scene"].cuts == [], "the benchmark video must be cut-free"
     return s.elapsed_time(e), segments * factor
 
 
@@ -122,10 +129,15 @@ def main():
     ap.add_argument("--buffers", type=int, default=12)
     ap.add_argument("--kernels-only", action="store_true")
     ap.add_argument("--no-kernels", action="store_true")
+    ap.add_argument("--scene", action="store_true", help="also time every mode with scene-cut detection on")
+    ap.add_argument("--modes", default=None, help="comma-separated substrings of the mode names to run")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_nx: no GPU")
+    modes = [(n, kw) for n, kw in MODES if a.modes is None or any(m in n for m in a.modes.split(","))]
+    if a.scene:           # off and on next to each other: the rotation below interleaves them
+        modes = [m for n, kw in modes for m in ((n, kw), (n + " +scene", dict(kw, scene=scene.SceneCuts())))]
     dev = torch.device("cuda:0")
     torch.set_grad_enabled(False)
     result = {"device": torch.cuda.get_device_name(0), "kernels": [], "videos": []}
@@ -142,17 +154,17 @@ def main():
             divisor = None if (h % 16 == 0 and w % 16 == 0) else 64
             frames = video(a.warm + a.segments + 1, h, w)
             for factor in (int(x) for x in a.factors.split(",")):
-                times = {name: [] for name, _ in MODES}
+                times = {name: [] for name, _ in modes}
                 for _ in range(a.repeats):            # in rotation: pool=False is the baseline of the same process and run
-                    for name, kw in MODES:
+                    for name, kw in modes:
                         ms, n = run_video(net, frames, factor, a.warm, a.segments, divisor, **kw)
                         times[name].append(n / (ms * 1e-3))
-                for name, kw in MODES:
+                for name, kw in modes:
                     t = times[name]
                     row = {"size": size, "factor": factor, "mode": name, "fps_median": statistics.median(t), "fps_min": min(t), "fps_max": max(t),
                            "stem_frames_per_segment": stem_per_segment(net, ops, frames, factor, divisor, **kw), "repeats_fps": t}
                     result["videos"].append(row)
-                    print(f"{size:>10} {factor}x {name:>15}: {row['fps_median']:8.2f} output frames/s (min {min(t):.2f}, max {max(t):.2f} over "
+                    print(f"{size:>10} {factor}x {name:>22}: {row['fps_median']:8.2f} output frames/s (min {min(t):.2f}, max {max(t):.2f} over "
                           f"{len(t)} repeats)  stem_fused frames / segment {row['stem_frames_per_segment']}", flush=True)
                 net.release_workspace()
     if a.json:
