@@ -135,6 +135,8 @@ SIGNATURES = {
     "atmvfi_frame_rot180": (c_i, [c_f, c_f, c_i, c_i, c_i, c_f]),
     "atmvfi_frame_signature_workspace_ints": (c_l, [c_i, c_i]),
     "atmvfi_frame_signature": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_l, c_f]),
+    "atmvfi_yuv420_to_rgb": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_f, c_i, c_i, c_i, c_i, c_f]),
+    "atmvfi_rgb_to_yuv420": (c_i, [c_f, c_i, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f]),
     "atmvfi_pack_frames": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_f]),
     "atmvfi_final_residual": (c_i, [c_f, c_f, c_i, c_f, c_f, c_i, c_i, c_i, c_f]),
     "atmvfi_l1_mean": (c_i, [c_f, c_f, c_f, c_i, c_l, c_f, c_l, c_f]),
@@ -1260,6 +1262,46 @@ class HipOps:
         self._check(self.lib.atmvfi_frame_signature(_ptr(src_u8), sh, sw, int(bool(bgr)), int(y0), int(x0), h, w, _ptr(out), _ptr(workspace),
                                                     workspace.numel(), self._stream()), "frame_signature")
         return out
+
+    def yuv420_to_rgb(self, yuv, fmt, dst_u8=None, dst=None, pad_top: int = 0, pad_left: int = 0, bgr: bool = False):
+        """One packed planar I420 frame of ``fmt`` (a ``yuv.Format``; a contiguous CUDA uint8 tensor of ``fmt.frame_bytes`` bytes, any
+        alignment) -> ``dst_u8`` uint8 [H,W,3] (BGR if ``bgr``) and / or ``dst`` fp32 planar RGB [3,Hp,Wp] = q / 255 with replicate
+        padding, the frame at (pad_top, pad_left) (include/atmvfi.h atmvfi_yuv420_to_rgb; the bits of ``yuv.decode_numpy``)."""
+        h, w = fmt.height, fmt.width
+        if yuv.dtype != torch.uint8 or yuv.dim() != 1 or yuv.numel() != fmt.frame_bytes or not yuv.is_contiguous() or not yuv.is_cuda:
+            raise ValueError(f"yuv420_to_rgb: source must be a contiguous CUDA uint8 tensor of {fmt.frame_bytes} bytes ({h} x {w} I420)")
+        if dst is None and dst_u8 is None:
+            raise ValueError("yuv420_to_rgb: give dst, dst_u8 or both")
+        if dst is not None and (dst.dtype != torch.float32 or dst.dim() != 3 or dst.shape[0] != 3 or not dst.is_contiguous() or not dst.is_cuda):
+            raise ValueError("yuv420_to_rgb: dst must be a contiguous CUDA fp32 [3,Hp,Wp] tensor")
+        if dst_u8 is not None and (dst_u8.dtype != torch.uint8 or tuple(dst_u8.shape) != (h, w, 3) or not dst_u8.is_contiguous()
+                                   or not dst_u8.is_cuda):
+            raise ValueError(f"yuv420_to_rgb: dst_u8 must be a contiguous CUDA uint8 [{h},{w},3] tensor")
+        hp, wp = (dst.shape[1], dst.shape[2]) if dst is not None else (h, w)
+        meta = {"bytes": float(fmt.frame_bytes) + (12.0 * hp * wp if dst is not None else 0.0) + (3.0 * h * w if dst_u8 is not None else 0.0)}
+        self._run("yuv420_to_rgb", meta, self.lib.atmvfi_yuv420_to_rgb, _ptr(yuv), h, w, int(fmt.depth), fmt.matrix_id, int(fmt.full_range),
+                  fmt.siting_id, _ptr(dst_u8), int(bool(bgr)), _ptr(dst), hp, wp, int(pad_top), int(pad_left), self._stream())
+
+    def rgb_to_yuv420(self, yuv, fmt, src_u8=None, src=None, pad_top: int = 0, pad_left: int = 0, bgr: bool = False):
+        """``src_u8`` uint8 [H,W,3] (BGR if ``bgr``) or ``src`` fp32 planar RGB [3,Hp,Wp] with the frame at (pad_top, pad_left) --
+        exactly one -- -> ``yuv``, a packed 8-bit I420 frame of ``fmt`` (a contiguous CUDA uint8 tensor of ``fmt.frame_bytes`` bytes;
+        include/atmvfi.h atmvfi_rgb_to_yuv420).  From fp32 the pixel is ``frame_f32_to_u8``'s; the bits of ``yuv.encode_numpy``."""
+        h, w = fmt.height, fmt.width
+        if fmt.depth != 8:
+            raise ValueError("rgb_to_yuv420: encoding is 8-bit only")
+        if yuv.dtype != torch.uint8 or yuv.dim() != 1 or yuv.numel() != fmt.frame_bytes or not yuv.is_contiguous() or not yuv.is_cuda:
+            raise ValueError(f"rgb_to_yuv420: destination must be a contiguous CUDA uint8 tensor of {fmt.frame_bytes} bytes ({h} x {w} I420)")
+        if (src is None) == (src_u8 is None):
+            raise ValueError("rgb_to_yuv420: give exactly one of src_u8 and src")
+        if src is not None and (src.dtype != torch.float32 or src.dim() != 3 or src.shape[0] != 3 or not src.is_contiguous() or not src.is_cuda):
+            raise ValueError("rgb_to_yuv420: src must be a contiguous CUDA fp32 [3,Hp,Wp] tensor")
+        if src_u8 is not None and (src_u8.dtype != torch.uint8 or tuple(src_u8.shape) != (h, w, 3) or not src_u8.is_contiguous()
+                                   or not src_u8.is_cuda):
+            raise ValueError(f"rgb_to_yuv420: src_u8 must be a contiguous CUDA uint8 [{h},{w},3] tensor")
+        hp, wp = (src.shape[1], src.shape[2]) if src is not None else (h, w)
+        meta = {"bytes": float(fmt.frame_bytes) + (12.0 if src is not None else 3.0) * h * w}
+        self._run("rgb_to_yuv420", meta, self.lib.atmvfi_rgb_to_yuv420, _ptr(src_u8), int(bool(bgr)), _ptr(src), hp, wp, int(pad_top),
+                  int(pad_left), h, w, fmt.matrix_id, int(fmt.full_range), fmt.siting_id, _ptr(yuv), self._stream())
 
     def frame_f32_to_u8(self, src, dst_u8, pad_top: int, pad_left: int, bgr: bool):
         """fp32 planar [3,Hp,Wp] -> crop -> np.round(x * 255) -> uint8 [H,W,3] device tensor (optional RGB -> BGR)."""

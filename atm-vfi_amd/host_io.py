@@ -236,10 +236,16 @@ class FramePipeline:
     frame (``HipOps.frame_signature``; of both frames when the pair's first is not the previous pair's second, by identity) is computed
     on the copy stream right behind the pair's upload and copied back into pinned words of the slot; ``_compute`` reads it -- the
     event was recorded one pair ahead, when the upload was issued under the previous pair's forward -- and for a cut enqueues NO
-    forward: the pair's frame is a bit-equal copy of its first original."""
+    forward: the pair's frame is a bit-equal copy of its first original.
+
+    ``pixfmt`` (a ``yuv.Format``; default None: uint8 [H,W,3] frames, the pipeline as above): frames in and out are packed planar I420
+    arrays (1-D; uint16 samples for a 10-bit format, whose output is 8-bit).  Pinned and device staging hold ``frame_bytes`` per frame
+    (1.5 bytes per pixel); ``atmvfi_yuv420_to_rgb`` runs on the copy stream behind the upload and writes the padded fp32 input directly
+    -- and, with ``scene``, the resident uint8 RGB frame the signature reads -- and ``atmvfi_rgb_to_yuv420`` encodes the prediction from
+    fp32 in front of the device -> host copy.  ``isBGR`` is ignored."""
 
     def __init__(self, model, height: int, width: int, isBGR: bool = True, divisor: int = 64, depth: int = 3, streams: int = 1,
-                 scene=None):
+                 scene=None, pixfmt=None):
         ops, dev = _hip_ops_of(model)
         if ops is None:
             raise RuntimeError("FramePipeline needs an atm-vfi_amd Network on the GPU")
@@ -254,10 +260,17 @@ class FramePipeline:
         self.pad_left, _, self.pad_top, _ = pad._pad
         self.hp, self.wp = height + pad._pad[2] + pad._pad[3], width + pad._pad[0] + pad._pad[1]
         mk = lambda *s, dt: torch.empty(*s, dtype=dt, device=dev)
+        self.pixfmt = pixfmt
+        if pixfmt is not None:
+            if (pixfmt.height, pixfmt.width) != (height, width):
+                raise ValueError(f"FramePipeline: pixfmt describes {pixfmt.height}x{pixfmt.width} frames, the pipeline {height}x{width}")
+            self.bgr, self.out_fmt = False, pixfmt.as_8bit()
+        in_shape = (height, width, 3) if pixfmt is None else (pixfmt.frame_bytes,)
+        out_shape = (height, width, 3) if pixfmt is None else (self.out_fmt.frame_bytes,)
         self.slots = [{
-            "h_in": torch.empty(2, height, width, 3, dtype=torch.uint8).pin_memory(),
-            "h_out": torch.empty(height, width, 3, dtype=torch.uint8).pin_memory(),
-            "d_in": mk(2, height, width, 3, dt=torch.uint8), "d_out": mk(height, width, 3, dt=torch.uint8),
+            "h_in": torch.empty(2, *in_shape, dtype=torch.uint8).pin_memory(),
+            "h_out": torch.empty(*out_shape, dtype=torch.uint8).pin_memory(),
+            "d_in": mk(2, *in_shape, dt=torch.uint8), "d_out": mk(*out_shape, dt=torch.uint8),
             "f0": mk(1, 3, self.hp, self.wp, dt=torch.float32), "f1": mk(1, 3, self.hp, self.wp, dt=torch.float32),
             "in_ready": torch.cuda.Event(), "done": torch.cuda.Event(), "out_ready": torch.cuda.Event(),
         } for _ in range(self.depth)]
@@ -267,6 +280,8 @@ class FramePipeline:
         self.scene = scene
         if scene is not None:
             for slot in self.slots:
+                if pixfmt is not None:
+                    slot["rgb"] = mk(2, height, width, 3, dt=torch.uint8)          # what the signature reads
                 slot["sig_d"] = mk(2, 288, dt=torch.int32)
                 slot["sig_h"] = torch.empty(2, 288, dtype=torch.int32).pin_memory()
                 slot["sig_h_np"], slot["sig_ready"] = slot["sig_h"].numpy(), torch.cuda.Event()
@@ -275,20 +290,30 @@ class FramePipeline:
 
     def _upload(self, slot, pair):
         a, b = pair
-        if a.shape != (self.h, self.w, 3) or b.shape != (self.h, self.w, 3) or a.dtype != np.uint8 or b.dtype != np.uint8:
+        if self.pixfmt is not None:
+            ya, yb = (self.pixfmt.check(f, "FramePipeline").view(np.uint8) for f in pair)
+        elif a.shape != (self.h, self.w, 3) or b.shape != (self.h, self.w, 3) or a.dtype != np.uint8 or b.dtype != np.uint8:
             raise ValueError(f"FramePipeline: expected two uint8 [{self.h},{self.w},3] frames")
+        else:
+            ya, yb = a, b
         # numpy's single-threaded memcpy, not Tensor.copy_: ATen spreads a 6 MB copy over every core it sees (128 threads on the
         # GPU box), which trips the container's CPU quota and stalls the enqueueing thread for tens of ms (tools/diag_hostio.py)
-        np.copyto(slot["h_in_np"][0], a)
-        np.copyto(slot["h_in_np"][1], b)
+        np.copyto(slot["h_in_np"][0], ya)
+        np.copyto(slot["h_in_np"][1], yb)
         with torch.cuda.stream(self.copy_in):
             slot["d_in"].copy_(slot["h_in"], non_blocking=True)
+            if self.pixfmt is not None:
+                # the slot's previous pair has been delivered (run): its forward no longer reads f0 / f1
+                for k, f in enumerate((slot["f0"], slot["f1"])):
+                    self.ops.yuv420_to_rgb(slot["d_in"][k], self.pixfmt, dst_u8=slot["rgb"][k] if self.scene is not None else None,
+                                           dst=f[0], pad_top=self.pad_top, pad_left=self.pad_left)
             slot["in_ready"].record(self.copy_in)
             if self.scene is not None:
                 # a frame's signature is computed once: the first frame's only when it is not the previous pair's second
                 slot["first"], slot["chained"], self._last_b = a, a is self._last_b, b
+                frames_u8 = slot["d_in"] if self.pixfmt is None else slot["rgb"]
                 for k in ((1,) if slot["chained"] else (0, 1)):
-                    self.ops.frame_signature(slot["d_in"][k], bgr=self.bgr, out=slot["sig_d"][k], workspace=self._sig_ws)
+                    self.ops.frame_signature(frames_u8[k], bgr=self.bgr, out=slot["sig_d"][k], workspace=self._sig_ws)
                 slot["sig_h"].copy_(slot["sig_d"], non_blocking=True)
                 slot["sig_ready"].record(self.copy_in)
 
@@ -319,10 +344,14 @@ class FramePipeline:
     def _compute_on(self, slot, model):
         cur = torch.cuda.current_stream(self.dev)
         cur.wait_event(slot["in_ready"])
-        self.ops.frame_u8_to_f32(slot["d_in"][0], slot["f0"][0], self.pad_top, self.pad_left, self.bgr)
-        self.ops.frame_u8_to_f32(slot["d_in"][1], slot["f1"][0], self.pad_top, self.pad_left, self.bgr)
+        if self.pixfmt is None:
+            self.ops.frame_u8_to_f32(slot["d_in"][0], slot["f0"][0], self.pad_top, self.pad_left, self.bgr)
+            self.ops.frame_u8_to_f32(slot["d_in"][1], slot["f1"][0], self.pad_top, self.pad_left, self.bgr)
         it = model.forward(slot["f0"], slot["f1"])["I_t"]
-        self.ops.frame_f32_to_u8(it[0], slot["d_out"], self.pad_top, self.pad_left, self.bgr)
+        if self.pixfmt is None:
+            self.ops.frame_f32_to_u8(it[0], slot["d_out"], self.pad_top, self.pad_left, self.bgr)
+        else:
+            self.ops.rgb_to_yuv420(slot["d_out"], self.out_fmt, src=it[0], pad_top=self.pad_top, pad_left=self.pad_left)
         slot["done"].record(cur)
         self.copy_out.wait_event(slot["done"])
         with torch.cuda.stream(self.copy_out):
@@ -356,12 +385,15 @@ class FramePipeline:
             yield self._deliver(inflight.pop(0))
 
 
-def interpolate_video_2x(frames, model, isBGR: bool = True, divisor: int = 64, depth: int = 3, streams: int = 1, scene=None):
+def interpolate_video_2x(frames, model, isBGR: bool = True, divisor: int = 64, depth: int = 3, streams: int = 1, scene=None,
+                         pixfmt=None):
     """The frame loop of demo_2x.py:144-163 over any iterable of uint8 [H,W,3] frames (decoding / encoding stays with the caller):
     yields f0, I(f0,f1), f1, I(f1,f2), ..., f_{n-1} -- 2n-1 frames -- with the pairs running through ``FramePipeline``
     (``streams`` > 1: that many forwards in flight on streams of their own, for frames too small to fill the GPU one at a time).
     ``scene`` (a ``scene.SceneCuts``; not in the script): a pair classed a scene cut runs no forward and its middle frame is a copy of
-    the pair's first frame; ``scene.cuts`` holds the cut pairs' indices afterwards."""
+    the pair's first frame; ``scene.cuts`` holds the cut pairs' indices afterwards.
+    ``pixfmt`` (a ``yuv.Format``): the frames are packed planar I420 arrays, in and out; originals pass through as the caller's own
+    bytes (no colour round trip), predictions are encoded on the device (8-bit, also for 10-bit input); ``isBGR`` is ignored."""
     from collections import deque
     it = iter(frames)
     first = next(it, None)
@@ -375,7 +407,8 @@ def interpolate_video_2x(frames, model, isBGR: bool = True, divisor: int = 64, d
             originals.append(cur)
             yield prev, cur
             prev = cur
-    pipe = FramePipeline(model, first.shape[0], first.shape[1], isBGR=isBGR, divisor=divisor, depth=depth, streams=streams, scene=scene)
+    height, width = first.shape[:2] if pixfmt is None else (pixfmt.height, pixfmt.width)
+    pipe = FramePipeline(model, height, width, isBGR=isBGR, divisor=divisor, depth=depth, streams=streams, scene=scene, pixfmt=pixfmt)
     for pred in pipe.run(pairs()):
         yield originals.popleft()
         yield pred
@@ -642,3 +675,5 @@ def load_model_checkpoint(model, checkpoint_path, strict: bool = True, map_locat
 from .multiframe import (FramePool, inference_nx, interpolate_video_nx, nx_levels, nx_sequence, video_nx)  # noqa: E402,F401
 # scene-cut detection for the video loops above (not in the reference): atm-vfi_amd/scene.py
 from .scene import SceneCuts, cut_statistics, signature_numpy  # noqa: E402,F401
+# planar YUV 4:2:0 frames for the loops above (``pixfmt=``) and Y4M files (not in the reference): atm-vfi_amd/yuv.py
+from .yuv import Format as YuvFormat, Y4MReader, Y4MWriter, interpolate_y4m  # noqa: E402,F401

@@ -141,17 +141,24 @@ class _Uploader:
     ``signature=(ops, (y0, x0, h, w), bgr)`` (scene-cut detection): the frame's signature (``HipOps.frame_signature``) is computed ONCE,
     on the copy stream right behind the copy that brought the frame, and its 1 152 bytes follow it back into a pinned word array of the
     slot; ``signature(slot)`` waits for that event -- recorded when the upload was issued, one segment before the segment that asks --
-    and returns the words."""
+    and returns the words.
 
-    def __init__(self, dev, height: int, width: int, depth: int = 3, signature=None):
+    ``pixfmt=(ops, fmt)`` (planar I420 input): pinned and device staging hold ``fmt.frame_bytes``; ``atmvfi_yuv420_to_rgb`` runs on the
+    copy stream behind the copy and fills the slot's resident uint8 RGB frame ``d`` -- what the signature, ``take`` and everything
+    downstream read, as for an RGB upload."""
+
+    def __init__(self, dev, height: int, width: int, depth: int = 3, signature=None, pixfmt=None):
         import torch
         self.torch, self.dev, self.h, self.w, self.depth = torch, dev, height, width, depth
-        self.sig = signature
-        self.ring = [{"h": torch.empty(height, width, 3, dtype=torch.uint8).pin_memory(),
+        self.sig, self.pixfmt = signature, pixfmt
+        in_shape = (height, width, 3) if pixfmt is None else (pixfmt[1].frame_bytes,)
+        self.ring = [{"h": torch.empty(*in_shape, dtype=torch.uint8).pin_memory(),
                       "d": torch.empty(height, width, 3, dtype=torch.uint8, device=dev),
                       "ready": torch.cuda.Event(), "free": torch.cuda.Event()} for _ in range(depth)]
         for s in self.ring:
             s["h_np"] = s["h"].numpy()
+            if pixfmt is not None:
+                s["yuv"] = torch.empty(*in_shape, dtype=torch.uint8, device=dev)
             if signature is not None:
                 s["sig_d"] = torch.empty(288, dtype=torch.int32, device=dev)
                 s["sig_h"] = torch.empty(288, dtype=torch.int32).pin_memory()
@@ -164,14 +171,20 @@ class _Uploader:
     def upload(self, frame):
         """Start the host -> device copy of ``frame``; returns the ring slot to hand to ``take``."""
         torch = self.torch
-        if frame.shape != (self.h, self.w, 3) or frame.dtype != np.uint8:
+        if self.pixfmt is not None:
+            frame = self.pixfmt[1].check(frame, "interpolate_video_nx").view(np.uint8)
+        elif frame.shape != (self.h, self.w, 3) or frame.dtype != np.uint8:
             raise ValueError(f"interpolate_video_nx: expected uint8 [{self.h},{self.w},3] frames, got {frame.dtype} {tuple(frame.shape)}")
         slot = self.ring[self.issued % self.depth]
         if self.issued >= self.depth:
             slot["free"].synchronize()                # the kernel that read this slot's device copy has run
         np.copyto(slot["h_np"], frame)                # numpy's single-threaded memcpy (see host_io.FramePipeline._upload)
         with torch.cuda.stream(self.copy_in):
-            slot["d"].copy_(slot["h"], non_blocking=True)
+            if self.pixfmt is None:
+                slot["d"].copy_(slot["h"], non_blocking=True)
+            else:
+                slot["yuv"].copy_(slot["h"], non_blocking=True)
+                self.pixfmt[0].yuv420_to_rgb(slot["yuv"], self.pixfmt[1], dst_u8=slot["d"])
             slot["ready"].record(self.copy_in)
             if self.sig is not None:
                 ops, (y0, x0, h, w), bgr = self.sig
@@ -203,7 +216,7 @@ class _SegmentRunner:
     per level at 8x (batch sizes 1, 2, 4).  The runner RAISES ``model.max_workspaces`` to the number of batch sizes of its schedule for
     its lifetime and restores it in ``close()``."""
 
-    def __init__(self, model, ops, dev, height, width, factor, crop, bgr, divisor, tta, max_batch, pool):
+    def __init__(self, model, ops, dev, height, width, factor, crop, bgr, divisor, tta, max_batch, pool, out_fmt=None):
         import torch
         from .host_io import InputPadder
         self.torch, self.model, self.ops, self.dev = torch, model, ops, dev
@@ -234,8 +247,12 @@ class _SegmentRunner:
         self.have_first = False
         # plain mode: the pairs of a batch are gathered into contiguous [B,3,Hp,Wp] inputs
         self.gather = {}
-        self.out_d = torch.empty(factor - 1, self.h, self.w, 3, dtype=torch.uint8, device=dev)
-        self.out_h = [torch.empty(factor - 1, self.h, self.w, 3, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        # out_fmt (a yuv.Format of the window's size): the produced frames leave as packed I420 (rgb_to_yuv420) instead of uint8 RGB
+        self.out_fmt = out_fmt
+        out_shape = (self.h, self.w, 3) if out_fmt is None else (out_fmt.frame_bytes,)
+        self.out_d = torch.empty(factor - 1, *out_shape, dtype=torch.uint8, device=dev)
+        self.out_h = [torch.empty(factor - 1, *out_shape, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        self.merged = torch.empty(self.h, self.w, 3, dtype=torch.uint8, device=dev) if (out_fmt is not None and self.tta) else None
         self.out_evt = [torch.cuda.Event() for _ in range(2)]
         self.seg = 0
         self.copy_out = torch.cuda.Stream(dev)
@@ -309,7 +326,14 @@ class _SegmentRunner:
                     flip = self._forward(1, lefts, rights) if self.tta else None
                     for j, (_, _, pos) in enumerate(chunk):
                         u8 = self.out_d[pos - 1]
-                        if self.tta:
+                        if self.out_fmt is not None:
+                            if self.tta:               # the average's uint8 pixels, then their encoding
+                                self.ops.tta_merge(pred[j], flip[j], out_u8=self.merged, pad_top=self.pad_top, pad_left=self.pad_left,
+                                                   bgr=False)
+                                self.ops.rgb_to_yuv420(u8, self.out_fmt, src_u8=self.merged)
+                            else:
+                                self.ops.rgb_to_yuv420(u8, self.out_fmt, src=pred[j], pad_top=self.pad_top, pad_left=self.pad_left)
+                        elif self.tta:
                             self.ops.tta_merge(pred[j], flip[j], out_u8=u8, pad_top=self.pad_top, pad_left=self.pad_left, bgr=self.bgr)
                         else:
                             self.ops.frame_f32_to_u8(pred[j], u8, self.pad_top, self.pad_left, self.bgr)
@@ -386,7 +410,7 @@ def _generic_segment(model, factor, crop_of, isBGR, divisor, tta, max_batch):
 
 
 def interpolate_video_nx(frames, model, factor: int = 4, time_interval: int = 1, crop: Optional[Tuple[int, int]] = None, isBGR: bool = True,
-                         divisor: Optional[int] = 64, tta: bool = False, max_batch: int = 4, pool: bool = True, scene=None):
+                         divisor: Optional[int] = 64, tta: bool = False, max_batch: int = 4, pool: bool = True, scene=None, pixfmt=None):
     """N-x slow motion over any iterable of uint8 [H,W,3] frames (davis-vid.py:88-135; decoding / encoding stays with the caller):
     per segment ``(f_i, f_{i+s})``, ``s = time_interval``, yields ``f_i`` and the frames at t = 1/N ... (N-1)/N, after the last segment
     its second frame once -- ``segments * N + 1`` frames.  Originals pass through bit-equal (their centre ``crop=(h, w)`` window when
@@ -403,7 +427,13 @@ def interpolate_video_nx(frames, model, factor: int = 4, time_interval: int = 1,
     ``scene`` (a ``scene.SceneCuts``; default None: the loop as above): scene-cut detection, not in the script.  The signatures of
     the two ends of every segment (of the crop window; computed on the device where the frame lands, one segment ahead) are compared;
     a segment classed a cut runs NO forward and its N - 1 positions are bit-equal copies of the nearer original -- position k <= N/2
-    the first, k > N/2 the second, cropped when cropping.  ``scene.cuts`` / ``scene.stats`` hold the run's record."""
+    the first, k > N/2 the second, cropped when cropping.  ``scene.cuts`` / ``scene.stats`` hold the run's record.
+
+    ``pixfmt`` (a ``yuv.Format``; default None: the loop as above): frames in and out are packed planar I420 arrays.  Every source
+    frame is uploaded as I420 and decoded once on the copy stream into the resident uint8 RGB frame everything above reads; produced
+    frames are encoded on the device (8-bit, also for 10-bit input) in front of the device -> host copy.  Originals -- cut copies
+    included -- pass through as the caller's own bytes (``yuv.crop`` of them when cropping: the crop origin must be even, else
+    ``ValueError``); ``isBGR`` is ignored."""
     from .host_io import _hip_ops_of
     from .scene import cut_fill, signature_numpy
     nx_levels(factor)
@@ -413,28 +443,53 @@ def interpolate_video_nx(frames, model, factor: int = 4, time_interval: int = 1,
     first = next(it, None)
     if first is None:
         return
-    H, W = first.shape[:2]
+    H, W = first.shape[:2] if pixfmt is None else (pixfmt.height, pixfmt.width)
     y0, x0, h, w = centre_window(H, W, crop)
     crop_of = (lambda f: f) if crop is None else (lambda f: np.ascontiguousarray(f[y0:y0 + h, x0:x0 + w]))
+    out_fmt = None
+    if pixfmt is not None:
+        from . import yuv
+        if crop is not None and (y0 % 2 or x0 % 2):
+            raise ValueError(f"interpolate_video_nx: the crop origin ({y0}, {x0}) must be even for 4:2:0 frames")
+        isBGR, out_fmt = False, pixfmt.as_8bit().cropped(h, w)
+        crop_rgb, whole = crop_of, (h, w) == (H, W)
+        crop_of = (lambda f: f) if whole else (lambda f: yuv.crop(f, pixfmt, y0, x0, h, w))          # of the caller's I420 frames
     ops, dev = _hip_ops_of(model)
     if ops is None or not hasattr(ops, "pool_blocks"):
-        seg = _generic_segment(model, factor, crop_of, isBGR, divisor, tta, max(1, int(max_batch)))
-        if scene is not None:
-            forward_segment, known = seg, {"of": None, "sig": None}
+        seg = _generic_segment(model, factor, crop_of if pixfmt is None else crop_rgb, isBGR, divisor, tta, max(1, int(max_batch)))
+        if pixfmt is not None:
+            rgb_segment, decoded = seg, {"of": None, "rgb": None}
+
+            def rgb_of(f):
+                """the decoded frame, kept for the frame that is the next segment's first"""
+                if decoded["of"] is not f:
+                    decoded.update(of=f, rgb=yuv.decode_numpy(f, pixfmt))
+                return decoded["rgb"]
 
             def seg(a, b):
-                sig_a = known["sig"] if known["of"] is a else signature_numpy(a, (y0, x0, h, w), bgr=isBGR)
-                sig_b = signature_numpy(b, (y0, x0, h, w), bgr=isBGR)
+                ra = rgb_of(a)
+                return [yuv.encode_numpy(m, out_fmt) for m in rgb_segment(ra, rgb_of(b))]
+        if scene is not None:
+            forward_segment, known = seg, {"of": None, "sig": None}
+            sig_of = signature_numpy if pixfmt is None else (lambda f, win, bgr: signature_numpy(yuv.decode_numpy(f, pixfmt), win, bgr=False))
+
+            def seg(a, b):
+                sig_a = known["sig"] if known["of"] is a else sig_of(a, (y0, x0, h, w), bgr=isBGR)
+                sig_b = sig_of(b, (y0, x0, h, w), bgr=isBGR)
                 known.update(of=b, sig=sig_b)                # b is the next segment's first frame
                 if scene.judge(sig_a, sig_b, h, w):
                     return cut_fill(crop_of(a), crop_of(b), factor)
                 return forward_segment(a, b)
         for f in nx_sequence(_chain(first, it), lambda a, b: seg(a, b), factor, time_interval):
-            yield f if f.shape[:2] == (h, w) else crop_of(f)
+            if pixfmt is not None:
+                yield crop_of(f) if (not whole and f.size == pixfmt.frame_samples) else f       # originals are cropped here
+            else:
+                yield f if f.shape[:2] == (h, w) else crop_of(f)
         return
     runner = _SegmentRunner(model, ops, dev, H, W, factor, crop, isBGR, divisor, tta, max_batch,
-                            pool and hasattr(model, "forward_pooled"))
-    up = _Uploader(dev, H, W, signature=None if scene is None else (ops, (y0, x0, h, w), bool(isBGR)))
+                            pool and hasattr(model, "forward_pooled"), out_fmt=out_fmt)
+    up = _Uploader(dev, H, W, signature=None if scene is None else (ops, (y0, x0, h, w), bool(isBGR)),
+                   pixfmt=None if pixfmt is None else (ops, pixfmt))
     state = {"first": True, "sig": None}
 
     def segment(fa, fb):
@@ -474,7 +529,10 @@ def interpolate_video_nx(frames, model, factor: int = 4, time_interval: int = 1,
             yield buf.popleft()
     try:
         for f in nx_sequence(ahead(), segment, factor, time_interval):
-            yield crop_of(f) if (crop is not None and f.shape[:2] == (H, W) and (H, W) != (h, w)) else f
+            if pixfmt is not None:      # an original (the caller's array, the input format's size) is cropped; a produced frame is not
+                yield crop_of(f) if (not whole and f.size == pixfmt.frame_samples) else f
+            else:
+                yield crop_of(f) if (crop is not None and f.shape[:2] == (H, W) and (H, W) != (h, w)) else f
     finally:
         runner.close()
 

@@ -1,0 +1,411 @@
+"""Planar YUV 4:2:0 (I420) frames and Y4M files for the video loops: the format, the host twins of the HIP colour conversion
+(``atmvfi_yuv420_to_rgb`` / ``atmvfi_rgb_to_yuv420``, csrc/yuv.hip), a YUV4MPEG2 reader and writer, and ``interpolate_y4m``.
+
+Nothing of the reference: its scripts read PNGs and hand video to OpenCV.  Decoders, ``ffmpeg -f yuv4mpegpipe`` pipes and the Xiph
+clips deliver planar 4:2:0; with ``pixfmt=Format(...)`` the loops (``interpolate_video_2x`` / ``FramePipeline`` /
+``interpolate_video_nx``) take and yield packed I420 arrays -- 1.5 bytes per pixel each way instead of 3 -- and convert on the device.
+
+The definition is the project's own, in int32 (``>>`` floors), so the device, ``decode_numpy`` / ``encode_numpy`` and the per-pixel
+model of the tests agree bit for bit; include/atmvfi.h spells it out.  In short: a frame is Y [H,W], U [ch,cw], V [ch,cw] back to
+back (ch = (H + 1) // 2, cw = (W + 1) // 2; uint8, or uint16 0..1023 for depth 10, decode only); decoding upsamples chroma with
+(3, 1) taps (left siting: (4, 0) / (2, 2) horizontally) and applies ``COEFFS[matrix, full_range][0]`` at 14 bits; encoding takes the
+uint8 RGB pixel (from fp32: ``frame_f32_to_u8``'s pixel), box-filters chroma over 2 x 2 (left siting: 1-2-1 x 2) un-rounded sums and
+applies ``COEFFS[..][1]``.  Not reproduced: ffmpeg's swscale (other filters, other rounding) -- it is not available to compare with.
+10-bit input is decoded to 8-bit RGB; what the loops produce is 8-bit."""
+from __future__ import annotations
+
+import io
+import os
+from dataclasses import dataclass, replace
+from fractions import Fraction
+from typing import Iterator, Optional, Tuple
+
+import numpy as np
+
+MATRICES = ("bt601", "bt709")
+SITINGS = ("centre", "left")
+KR_KB = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}
+SHIFT = 14
+
+
+def derive_coeffs(matrix: str, full_range: bool):
+    """([kY, kRV, kGU, kGV, kBU], 3 x 3 encode rows Y / U / V over (R, G, B)) = rint(c * 2^14) of the float64 matrices of (Kr, Kb);
+    limited range scales luma by 219 / 255 and chroma by 224 / 255."""
+    kr, kb = KR_KB[matrix]
+    kg = 1.0 - kr - kb
+    sy, sc = (1.0, 1.0) if full_range else (219.0 / 255.0, 224.0 / 255.0)
+    dec = [1.0 / sy, 2 * (1 - kr) / sc, -2 * (1 - kb) * kb / kg / sc, -2 * (1 - kr) * kr / kg / sc, 2 * (1 - kb) / sc]
+    enc = [[kr * sy, kg * sy, kb * sy],
+           [-kr / (2 * (1 - kb)) * sc, -kg / (2 * (1 - kb)) * sc, 0.5 * sc],
+           [0.5 * sc, -kg / (2 * (1 - kr)) * sc, -kb / (2 * (1 - kr)) * sc]]
+    q = lambda v: int(np.rint(v * (1 << SHIFT)))
+    return [q(v) for v in dec], [[q(v) for v in row] for row in enc]
+
+
+# (matrix, full_range) -> (decode [kY, kRV, kGU, kGV, kBU], encode rows Y / U / V over (R, G, B)); the table of csrc/yuv.hip
+COEFFS = {
+    ("bt601", False): ((19077, 26149, -6419, -13320, 33050), ((4207, 8260, 1604), (-2428, -4768, 7196), (7196, -6026, -1170))),
+    ("bt601", True): ((16384, 22970, -5638, -11700, 29032), ((4899, 9617, 1868), (-2765, -5427, 8192), (8192, -6860, -1332))),
+    ("bt709", False): ((19077, 29372, -3494, -8731, 34610), ((2991, 10064, 1016), (-1649, -5547, 7196), (7196, -6536, -660))),
+    ("bt709", True): ((16384, 25802, -3069, -7670, 30402), ((3483, 11718, 1183), (-1877, -6315, 8192), (8192, -7441, -751))),
+}
+
+
+@dataclass(frozen=True)
+class Format:
+    """A packed planar I420 frame format.  ``matrix="auto"``: bt709 for ``height >= 720``, bt601 below."""
+    height: int
+    width: int
+    matrix: str = "auto"
+    full_range: bool = False
+    siting: str = "centre"
+    depth: int = 8
+
+    def __post_init__(self):
+        if int(self.height) < 1 or int(self.width) < 1:
+            raise ValueError(f"yuv.Format: height and width must be at least 1 (got {self.height} x {self.width})")
+        m = self.matrix
+        if m == "auto":
+            m = "bt709" if self.height >= 720 else "bt601"
+        if m not in MATRICES:
+            raise ValueError(f"yuv.Format: unknown matrix {self.matrix!r} (auto, bt601, bt709)")
+        if self.siting not in SITINGS:
+            raise ValueError(f"yuv.Format: unknown siting {self.siting!r} (centre, left)")
+        if self.depth not in (8, 10):
+            raise ValueError(f"yuv.Format: depth must be 8 or 10 (got {self.depth!r})")
+        if self.depth == 10 and self.full_range:
+            raise ValueError("yuv.Format: 10-bit full range is not supported")
+        object.__setattr__(self, "height", int(self.height))
+        object.__setattr__(self, "width", int(self.width))
+        object.__setattr__(self, "matrix", m)
+        object.__setattr__(self, "full_range", bool(self.full_range))
+
+    @property
+    def chroma_shape(self) -> Tuple[int, int]:
+        return (self.height + 1) // 2, (self.width + 1) // 2
+
+    @property
+    def frame_samples(self) -> int:
+        ch, cw = self.chroma_shape
+        return self.height * self.width + 2 * ch * cw
+
+    @property
+    def frame_bytes(self) -> int:
+        return self.frame_samples * (2 if self.depth == 10 else 1)
+
+    @property
+    def dtype(self):
+        return np.uint16 if self.depth == 10 else np.uint8
+
+    @property
+    def matrix_id(self) -> int:
+        return MATRICES.index(self.matrix)
+
+    @property
+    def siting_id(self) -> int:
+        return SITINGS.index(self.siting)
+
+    def check(self, buf, what: str = "yuv") -> np.ndarray:
+        """``buf`` as the 1-D sample array of one frame of this format (a view), or ``ValueError``."""
+        a = np.asarray(buf)
+        if a.dtype != self.dtype or a.size != self.frame_samples or not a.flags.c_contiguous:
+            raise ValueError(f"{what}: a contiguous {np.dtype(self.dtype).name} I420 frame of {self.frame_samples} samples "
+                             f"({self.height} x {self.width}) expected, got {a.dtype} {tuple(a.shape)}")
+        return a.reshape(-1)
+
+    def planes(self, buf):
+        """(Y [H,W], U [ch,cw], V [ch,cw]) views of a packed frame."""
+        a = self.check(buf, "yuv.Format.planes")
+        ch, cw = self.chroma_shape
+        n, c = self.height * self.width, ch * cw
+        return a[:n].reshape(self.height, self.width), a[n:n + c].reshape(ch, cw), a[n + c:].reshape(ch, cw)
+
+    def as_8bit(self) -> "Format":
+        return self if self.depth == 8 else replace(self, depth=8)
+
+    def cropped(self, h: int, w: int) -> "Format":
+        return replace(self, height=int(h), width=int(w))
+
+
+def planes(buf, fmt: Format):
+    return fmt.planes(buf)
+
+
+def decode_numpy(buf, fmt: Format, bgr: bool = False) -> np.ndarray:
+    """Packed I420 frame -> uint8 [H,W,3] RGB (BGR if ``bgr``): the bits of ``atmvfi_yuv420_to_rgb``'s ``dst_u8``."""
+    Y, U, V = (p.astype(np.int32) for p in fmt.planes(buf))
+    H, W = fmt.height, fmt.width
+    ch, cw = fmt.chroma_shape
+    ys, xs = np.arange(H), np.arange(W)
+    r0 = ys >> 1
+    r1 = np.clip(r0 + np.where(ys & 1, 1, -1), 0, ch - 1)
+    q0 = xs >> 1
+    if fmt.siting == "left":
+        q1 = np.minimum(q0 + 1, cw - 1)
+        wx0 = np.where(xs & 1, 2, 4).astype(np.int32)
+    else:
+        q1 = np.clip(q0 + np.where(xs & 1, 1, -1), 0, cw - 1)
+        wx0 = np.full(W, 3, np.int32)
+    wx1 = 4 - wx0
+
+    def up(c):
+        a = wx0 * c[:, q0] + wx1 * c[:, q1]
+        return (3 * a[r0] + a[r1] + 8) >> 4
+
+    (kY, kRV, kGU, kGV, kBU), _ = COEFFS[fmt.matrix, fmt.full_range]
+    if fmt.depth == 10:
+        yo, mid, T = 64, 512, 16
+    else:
+        yo, mid, T = (0 if fmt.full_range else 16), 128, 14
+    y, u, v = kY * (Y - yo), up(U) - mid, up(V) - mid
+    half = 1 << (T - 1)
+    r = (y + kRV * v + half) >> T
+    g = (y + kGU * u + kGV * v + half) >> T
+    b = (y + kBU * u + half) >> T
+    return np.clip(np.stack([b, g, r] if bgr else [r, g, b], axis=-1), 0, 255).astype(np.uint8)
+
+
+def encode_numpy(rgb, fmt: Format, bgr: bool = False) -> np.ndarray:
+    """uint8 [H,W,3] RGB (BGR if ``bgr``) -> packed 8-bit I420 frame (1-D uint8): the bits of ``atmvfi_rgb_to_yuv420``."""
+    rgb = np.asarray(rgb)
+    if fmt.depth != 8:
+        raise ValueError("encode_numpy: encoding is 8-bit only")
+    if rgb.dtype != np.uint8 or rgb.shape != (fmt.height, fmt.width, 3):
+        raise ValueError(f"encode_numpy: a uint8 [{fmt.height},{fmt.width},3] frame expected, got {rgb.dtype} {tuple(rgb.shape)}")
+    p = rgb.astype(np.int32)
+    if bgr:
+        p = p[:, :, ::-1]
+    H, W = fmt.height, fmt.width
+    ch, cw = fmt.chroma_shape
+    _, (eY, eU, eV) = COEFFS[fmt.matrix, fmt.full_range]
+    dot = lambda e, s: e[0] * s[..., 0] + e[1] * s[..., 1] + e[2] * s[..., 2]
+    yo = 0 if fmt.full_range else 16
+    Y = np.clip(((dot(eY, p) + (1 << 13)) >> 14) + yo, 0, 255)
+    ra = 2 * np.arange(ch)
+    rows = p[ra] + p[np.minimum(ra + 1, H - 1)]
+    ca = 2 * np.arange(cw)
+    if fmt.siting == "left":
+        s, sh = rows[:, np.maximum(ca - 1, 0)] + 2 * rows[:, ca] + rows[:, np.minimum(ca + 1, W - 1)], 3
+    else:
+        s, sh = rows[:, ca] + rows[:, np.minimum(ca + 1, W - 1)], 2
+    U = np.clip(((dot(eU, s) + (1 << (13 + sh))) >> (14 + sh)) + 128, 0, 255)
+    V = np.clip(((dot(eV, s) + (1 << (13 + sh))) >> (14 + sh)) + 128, 0, 255)
+    return np.concatenate([Y.reshape(-1), U.reshape(-1), V.reshape(-1)]).astype(np.uint8)
+
+
+def crop(buf, fmt: Format, y0: int, x0: int, h: int, w: int) -> np.ndarray:
+    """The h x w window at (y0, x0) of a packed frame as a packed frame of ``fmt.cropped(h, w)``: plane crops, the samples untouched.
+    The origin must be even (a chroma sample covers two luma rows and columns)."""
+    y0, x0, h, w = int(y0), int(x0), int(h), int(w)
+    if y0 % 2 or x0 % 2:
+        raise ValueError(f"yuv.crop: the crop origin ({y0}, {x0}) must be even for 4:2:0 frames")
+    if y0 < 0 or x0 < 0 or h < 1 or w < 1 or y0 + h > fmt.height or x0 + w > fmt.width:
+        raise ValueError(f"yuv.crop: window {h} x {w} at ({y0}, {x0}) outside the {fmt.height} x {fmt.width} frame")
+    Y, U, V = fmt.planes(buf)
+    ch, cw = (h + 1) // 2, (w + 1) // 2
+    return np.concatenate([Y[y0:y0 + h, x0:x0 + w].reshape(-1), U[y0 // 2:y0 // 2 + ch, x0 // 2:x0 // 2 + cw].reshape(-1),
+                           V[y0 // 2:y0 // 2 + ch, x0 // 2:x0 // 2 + cw].reshape(-1)])
+
+
+# ------------------------------------------------------------------------------------------------ YUV4MPEG2
+Y4M_MAGIC = b"YUV4MPEG2"
+# C tag -> (siting, depth); "420" is the format's default and means what "420jpeg" means
+Y4M_TAGS = {"420": ("centre", 8), "420jpeg": ("centre", 8), "420mpeg2": ("left", 8), "420p10": ("centre", 10)}
+
+
+class Y4MReader:
+    """A YUV4MPEG2 stream (a path or a binary file object): ``fmt`` (a ``Format``; matrix "auto" by height, range from
+    ``XCOLORRANGE``, siting and depth from the ``C`` tag), ``fps`` (a ``fractions.Fraction``), ``ctag`` / ``aspect`` as read; iterating
+    yields the frames as 1-D uint8 (uint16 for 10-bit) arrays; ``len()`` when the file is seekable.  Accepted: C420, C420jpeg,
+    C420mpeg2, C420p10, progressive.  Refused, naming the tag: C420paldv, 4:2:2, 4:4:4, mono and interlaced streams.  ``matrix``: the format's matrix when "auto" (by height) is not wanted."""
+
+    def __init__(self, path_or_file, matrix: str = "auto"):
+        self._own = isinstance(path_or_file, (str, os.PathLike))
+        self.f = open(path_or_file, "rb") if self._own else path_or_file
+        line = self._line()
+        tok = line.split(b" ")
+        if not tok or tok[0] != Y4M_MAGIC:
+            raise ValueError("Y4MReader: not a YUV4MPEG2 stream (no signature)")
+        w = h = None
+        self.fps, self.ctag, self.aspect, self.interlace, full = Fraction(0), "420", None, None, False
+        for t in tok[1:]:
+            t = t.decode("ascii", "replace")
+            if not t:
+                continue
+            k, v = t[0], t[1:]
+            if k == "W":
+                w = int(v)
+            elif k == "H":
+                h = int(v)
+            elif k == "F":
+                n, d = v.split(":")
+                self.fps = Fraction(int(n), int(d)) if int(d) else Fraction(0)
+            elif k == "A":
+                self.aspect = v
+            elif k == "I":
+                self.interlace = v
+                if v not in ("p", "?"):
+                    raise ValueError(f"Y4MReader: interlaced streams are not supported (tag I{v})")
+            elif k == "C":
+                self.ctag = v
+            elif k == "X" and v.upper() == "COLORRANGE=FULL":
+                full = True
+        if w is None or h is None:
+            raise ValueError("Y4MReader: the header gives no W / H")
+        if self.ctag not in Y4M_TAGS:
+            raise ValueError(f"Y4MReader: unsupported chroma format (tag C{self.ctag}); C420, C420jpeg, C420mpeg2 and C420p10 are read")
+        siting, depth = Y4M_TAGS[self.ctag]
+        self.fmt = Format(h, w, matrix, full, siting, depth)        # the header cannot name the matrix: the caller may
+        self._data0 = self._tell()
+
+    def _tell(self):
+        try:
+            return self.f.tell() if self.f.seekable() else None
+        except (AttributeError, OSError, io.UnsupportedOperation):
+            return None
+
+    def _line(self) -> bytes:
+        out = bytearray()
+        while True:
+            c = self.f.read(1)
+            if not c:
+                if out:
+                    raise ValueError("Y4MReader: the stream ends inside a header line")
+                return b""
+            if c == b"\n":
+                return bytes(out)
+            out += c
+            if len(out) > 4096:
+                raise ValueError("Y4MReader: header line too long")
+
+    def __len__(self):
+        if self._data0 is None:
+            raise TypeError("Y4MReader: the stream is not seekable: no length")
+        pos = self.f.tell()
+        end = self.f.seek(0, os.SEEK_END)
+        self.f.seek(pos)
+        return (end - self._data0) // (len(b"FRAME\n") + self.fmt.frame_bytes)       # plain FRAME markers, as every writer emits
+
+    def __iter__(self) -> Iterator[np.ndarray]:
+        n = self.fmt.frame_bytes
+        while True:
+            line = self._line()
+            if not line:
+                return
+            if not line.startswith(b"FRAME"):
+                raise ValueError(f"Y4MReader: FRAME marker expected, got {line[:16]!r}")
+            data = self.f.read(n)
+            while 0 < len(data) < n:            # pipes deliver short reads
+                more = self.f.read(n - len(data))
+                if not more:
+                    break
+                data += more
+            if len(data) != n:
+                raise ValueError(f"Y4MReader: truncated frame ({len(data)} of {n} bytes)")
+            yield np.frombuffer(data, dtype="<u2" if self.fmt.depth == 10 else np.uint8).astype(self.fmt.dtype, copy=True)
+
+    def close(self):
+        if self._own:
+            self.f.close()
+
+    release = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+class Y4MWriter:
+    """Writes packed I420 frames of ``fmt`` as YUV4MPEG2 at ``fps`` (anything ``Fraction`` accepts: the rate is written as an exact
+    ratio).  ``ctag``: the C tag to write when it should differ from the format's canonical one (420jpeg / 420mpeg2 / 420p10)."""
+
+    def __init__(self, path_or_file, fmt: Format, fps, ctag: Optional[str] = None, aspect: Optional[str] = None):
+        self._own = isinstance(path_or_file, (str, os.PathLike))
+        self.f = open(path_or_file, "wb") if self._own else path_or_file
+        self.fmt, self.fps = fmt, Fraction(fps)
+        canon = "420p10" if fmt.depth == 10 else ("420mpeg2" if fmt.siting == "left" else "420jpeg")
+        if ctag is not None and Y4M_TAGS.get(ctag) != (fmt.siting, fmt.depth):
+            raise ValueError(f"Y4MWriter: tag C{ctag} does not describe {fmt}")
+        self.ctag = ctag or canon
+        head = f"YUV4MPEG2 W{fmt.width} H{fmt.height} F{self.fps.numerator}:{self.fps.denominator} Ip A{aspect or '0:0'} C{self.ctag}"
+        head += " XCOLORRANGE=FULL" if fmt.full_range else " XCOLORRANGE=LIMITED"
+        self.f.write(head.encode("ascii") + b"\n")
+        self.frames = 0
+
+    def write(self, frame):
+        a = self.fmt.check(frame, "Y4MWriter.write")
+        self.f.write(b"FRAME\n")
+        self.f.write(a.astype("<u2", copy=False).tobytes() if self.fmt.depth == 10 else a.tobytes())
+        self.frames += 1
+
+    def close(self):
+        if self._own:
+            self.f.close()
+        else:
+            self.f.flush()
+
+    release = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+def to_8bit(frame, fmt: Format) -> np.ndarray:
+    """A frame of ``fmt`` as a frame of ``fmt.as_8bit()``: itself for 8-bit input; 10-bit input goes through RGB on the host
+    (``encode_numpy(decode_numpy(frame))``: the 8-bit picture the loops saw)."""
+    if fmt.depth == 8:
+        return frame
+    return encode_numpy(decode_numpy(frame, fmt), fmt.as_8bit())
+
+
+def interpolate_y4m(src, dst, model, factor: int = 2, scene=None, tta: bool = False, interpolator=None, matrix: str = "auto", **kw):
+    """Y4M file (or binary file object) ``src`` -> Y4M ``dst`` at ``fps * factor`` (``/ time_interval`` when given): an exact
+    rational, 30000/1001 in gives 60000/1001 out.  Frames travel as I420 both ways (``pixfmt``); originals are written as read,
+    predicted frames are encoded on the device.  The same format tags are written; 10-bit input is decoded on the device and written
+    back as 8-bit (C420jpeg), its originals converted on the host.  ``factor=2`` on a GPU ``Network`` without ``tta`` / ``crop`` /
+    ``time_interval`` runs ``interpolate_video_2x``, everything else ``interpolate_video_nx``; ``interpolator(frames, model, pixfmt=,
+    ...)`` overrides.  ``matrix``: as for ``Y4MReader`` (a Y4M header cannot name it).  Returns ``{"fps_in", "fps_out", "size", "frames_in", "frames_out"}`` and, with ``scene``, ``"cuts"``."""
+    from .host_io import _hip_ops_of, interpolate_video_2x
+    from .multiframe import centre_window, interpolate_video_nx, nx_levels
+    nx_levels(factor)
+    rd = Y4MReader(src, matrix=matrix)
+    fmt = rd.fmt
+    _, _, oh, ow = centre_window(fmt.height, fmt.width, kw.get("crop"))
+    out_fmt = fmt.as_8bit().cropped(oh, ow)
+    rate = rd.fps * factor / int(kw.get("time_interval", 1))
+    wr = Y4MWriter(dst, out_fmt, rate, ctag=rd.ctag if fmt.depth == 8 else None, aspect=rd.aspect)
+    n_in = [0]
+
+    def counted():
+        for f in rd:
+            n_in[0] += 1
+            yield f
+    if interpolator is None:
+        nx_only = tta or factor != 2 or any(k in kw for k in ("crop", "time_interval", "max_batch", "pool"))
+        if not nx_only and _hip_ops_of(model)[0] is not None:
+            interpolator = interpolate_video_2x
+        else:
+            interpolator = lambda frames, model, **k: interpolate_video_nx(frames, model, factor=factor, tta=tta, **k)
+    try:
+        for f in interpolator(counted(), model, pixfmt=fmt, scene=scene, **kw):
+            wr.write(to_8bit(f, fmt.cropped(oh, ow)) if f.dtype == np.uint16 else f)
+    finally:
+        rd.close()
+        wr.close()
+    info = {"fps_in": rd.fps, "fps_out": rate, "size": (ow, oh), "frames_in": n_in[0], "frames_out": wr.frames}
+    if scene is not None:
+        info["cuts"] = list(scene.cuts)
+    return info
+
+
+# what a user of this module needs from the loops
+from .host_io import FramePipeline, interpolate_video_2x, load_model_checkpoint  # noqa: E402,F401
+from .multiframe import interpolate_video_nx  # noqa: E402,F401
+from .scene import SceneCuts  # noqa: E402,F401

@@ -468,6 +468,43 @@ int64_t atmvfi_frame_signature_workspace_ints(int h, int w);
 int atmvfi_frame_signature(const void* src, int H, int W, int bgr, int y0, int x0, int h, int w, int32_t* sig /*[288]*/, int32_t* workspace,
                            int64_t workspace_ints, void* stream);
 
+/* Planar YUV 4:2:0 (I420) <-> RGB for the video loops (yuv.hip; atm-vfi_amd/yuv.py holds the format, the numpy twins and Y4M I/O).
+ * Nothing of the reference: its scripts read PNGs.  A bit-exact contract in int32 (>> is an arithmetic shift: floor).
+ * Frame: one contiguous buffer Y [H,W], U [ch,cw], V [ch,cw], ch = (H + 1) / 2, cw = (W + 1) / 2, H, W >= 1 (odd sizes allowed);
+ *   uint8 samples for depth 8, little-endian uint16 with values 0..1023 for depth 10 (decode only).
+ * Parameters: matrix 0 bt601 / 1 bt709; full_range 0 / 1 (10-bit full range is refused); siting 0 centre ("420jpeg") / 1 left
+ *   ("420mpeg2").  Coefficients: rint(c * 2^14) of the float64 matrices of (Kr, Kb) = (0.299, 0.114) / (0.2126, 0.0722), limited
+ *   range scaled by 219 / 224:            decode [kY, kRV, kGU, kGV, kBU]        encode rows Y / U / V over (R, G, B)
+ *     bt601 limited   19077, 26149,  -6419, -13320, 33050    (4207,  8260, 1604) / (-2428, -4768, 7196) / (7196, -6026, -1170)
+ *     bt601 full      16384, 22970,  -5638, -11700, 29032    (4899,  9617, 1868) / (-2765, -5427, 8192) / (8192, -6860, -1332)
+ *     bt709 limited   19077, 29372,  -3494,  -8731, 34610    (2991, 10064, 1016) / (-1649, -5547, 7196) / (7196, -6536,  -660)
+ *     bt709 full      16384, 25802,  -3069,  -7670, 30402    (3483, 11718, 1183) / (-1877, -6315, 8192) / (8192, -7441,  -751)
+ * Decode, chroma of luma pixel (y, x), plane c:
+ *   rows (always centre-sited) r0 = y >> 1, r1 = clamp(r0 + (y & 1 ? 1 : -1), 0, ch - 1), weights (wy0, wy1) = (3, 1);
+ *   columns, centre: q0 = x >> 1, q1 = clamp(q0 + (x & 1 ? 1 : -1), 0, cw - 1), weights (3, 1);
+ *   columns, left:   q0 = x >> 1, q1 = min(q0 + 1, cw - 1), weights (4, 0) for even x and (2, 2) for odd x;
+ *   c' = (wy0 (wx0 c[r0][q0] + wx1 c[r0][q1]) + wy1 (wx0 c[r1][q0] + wx1 c[r1][q1]) + 8) >> 4.
+ * Decode, matrix: y = Y - yo, u = U' - mid, v = V' - mid; 8 bit: yo = 16 (limited) or 0 (full), mid = 128, T = 14; 10 bit: yo = 64,
+ *   mid = 512, T = 16;  R = clip8((kY y + kRV v + 2^(T-1)) >> T), G = clip8((kY y + kGU u + kGV v + 2^(T-1)) >> T),
+ *   B = clip8((kY y + kBU u + 2^(T-1)) >> T).
+ * Encode (8 bit only): the source pixel p is the uint8 RGB value; from an fp32 source it is clamp(rint(x * 255)), half to even:
+ *   atmvfi_frame_f32_to_u8's pixel.  Y = clip8(((eY . p + 2^13) >> 14) + yo).  Chroma sample (j, i) takes the un-rounded per-channel
+ *   sums s over rows 2j and min(2j + 1, H - 1) and columns 2i, min(2i + 1, W - 1) with weights 1 (centre; sh = 2) or max(2i - 1, 0),
+ *   2i, min(2i + 1, W - 1) with weights 1, 2, 1 (left; sh = 3):  U = clip8(((eU . s + 2^(13 + sh)) >> (14 + sh)) + 128), V with eV.
+ * atmvfi_yuv420_to_rgb: dst_u8 (or NULL) uint8 [H,W,3], BGR if `bgr`; dst (or NULL) fp32 planar RGB [3,Hp,Wp] = q / 255 (a true fp32
+ *   division) with replicate padding, the frame at (pad_top, pad_left): the bits of atmvfi_frame_u8_to_f32 applied to dst_u8.  Not
+ *   both NULL; Hp, Wp and the padding are read only with dst (4-byte aligned).
+ * atmvfi_rgb_to_yuv420: exactly one of src_u8 (uint8 [H,W,3], BGR if `bgr`) and src (fp32 planar RGB [3,Hp,Wp], the frame at
+ *   (pad_top, pad_left), 4-byte aligned) -> yuv, depth 8.
+ * Any geometry and pointer alignment is accepted (for odd W the U plane starts at an odd byte); dword Y accesses, 16-byte plane
+ * accesses and 12-byte RGB groups are used when the byte pointers are 4-byte and the fp32 pointer 16-byte aligned and W, Wp and
+ * pad_left are multiples of 4.  Both paths give the same bits.  Every output byte is written by the call; no atomics, nothing
+ * pre-zeroed.  All checks run on the host before the launch (ATMVFI_EINVAL). */
+int atmvfi_yuv420_to_rgb(const void* yuv, int H, int W, int depth, int matrix, int full_range, int siting, void* dst_u8, int bgr,
+                         float* dst, int Hp, int Wp, int pad_top, int pad_left, void* stream);
+int atmvfi_rgb_to_yuv420(const void* src_u8, int bgr, const float* src, int Hp, int Wp, int pad_top, int pad_left, int H, int W,
+                         int matrix, int full_range, int siting, void* yuv, void* stream);
+
 /* mean |a - b| per sample: global_alignmentness (network_base.py:560-561).  Two passes with a fixed summation order -- the result is
  * run-to-run bit-identical (the ensemble's pick compares these means) -- through `workspace`: at least
  * atmvfi_l1_mean_workspace_floats(B, per_sample) floats of scratch, the caller's. */

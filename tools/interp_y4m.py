@@ -1,0 +1,51 @@
+#!/usr/bin/env python3
+"""Y4M in, Y4M out at ``factor`` times the frame rate (``atm-vfi_amd.yuv.interpolate_y4m``): frames travel as planar 4:2:0 and are
+converted on the GPU; originals are written as read.  Reads C420 / C420jpeg / C420mpeg2 / C420p10 progressive streams; 10-bit input
+is written back as 8-bit.  ``-`` reads standard input / writes standard output (``ffmpeg -i in.mp4 -f yuv4mpegpipe - | interp_y4m.py
+- out.y4m --ckpt ...``).
+
+    python tools/interp_y4m.py IN.y4m OUT.y4m --ckpt CKPT [--model base|lite] [--factor 2|4|8] [--scene] [--tta] [--global-off]"""
+import argparse
+import importlib
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("src")
+    ap.add_argument("dst")
+    ap.add_argument("--ckpt", default=None, help="checkpoint (the trainer's dict or a bare state dict); without one: synthetic weights")
+    ap.add_argument("--model", choices=("base", "lite"), default="base")
+    ap.add_argument("--factor", type=int, default=2)
+    ap.add_argument("--scene", action="store_true", help="scene-cut detection (SceneCuts() defaults)")
+    ap.add_argument("--tta", action="store_true", help="flip test-time augmentation of every produced frame")
+    ap.add_argument("--global-off", action="store_true", help="switch the global motion branch off")
+    ap.add_argument("--matrix", choices=("auto", "bt601", "bt709"), default="auto", help="a Y4M header cannot name the matrix")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("interp_y4m: no GPU")
+    pkg = importlib.import_module("atm-vfi_amd")
+    yuv = importlib.import_module("atm-vfi_amd.yuv")
+    torch.set_grad_enabled(False)
+    net = pkg.NetworkBase() if a.model == "base" else pkg.NetworkLite()
+    if a.ckpt:
+        yuv.load_model_checkpoint(net, a.ckpt)
+    else:
+        print("interp_y4m: no --ckpt: synthetic weights (the output is not a meaningful interpolation)", file=sys.stderr)
+        net.load_state_dict(pkg.synthetic_state_dict(a.model, seed=1), strict=True)
+    net = net.to(torch.device("cuda:0")).eval()
+    net.global_motion = not a.global_off
+    src = sys.stdin.buffer if a.src == "-" else a.src
+    dst = sys.stdout.buffer if a.dst == "-" else a.dst
+    info = yuv.interpolate_y4m(src, dst, net, factor=a.factor, scene=yuv.SceneCuts() if a.scene else None, tta=a.tta, matrix=a.matrix)
+    print({k: (str(v) if k.startswith("fps") else v) for k, v in info.items()}, file=sys.stderr)
+
+
+if __name__ == "__main__":
+    main()
