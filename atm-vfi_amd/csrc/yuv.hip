@@ -23,6 +23,8 @@
 //           pad_left % 4 == 0): dword Y loads / stores, 16-byte plane accesses, one 12-byte RGB group per four pixels, 2-byte chroma pairs;
 //   general path: any geometry and alignment: byte accesses, the same integer arithmetic, the same bits.
 // Vector stores only, no atomics, nothing pre-zeroed: every output byte is written by exactly one lane.
+// The depth-keeping 10-bit calls (10-bit samples <-> fp32 in units of 1 / 1023; atmvfi_yuv420p10_to_f32 / atmvfi_f32_to_yuv420p10) live
+// in yuv10.hip; the 10-bit decode here stays what it was: clip8 RGB, q / 255.
 #include "common.h"
 
 namespace {

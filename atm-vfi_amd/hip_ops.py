@@ -137,6 +137,8 @@ SIGNATURES = {
     "atmvfi_frame_signature": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_l, c_f]),
     "atmvfi_yuv420_to_rgb": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_f, c_i, c_i, c_i, c_i, c_f]),
     "atmvfi_rgb_to_yuv420": (c_i, [c_f, c_i, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f]),
+    "atmvfi_yuv420p10_to_f32": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f]),
+    "atmvfi_f32_to_yuv420p10": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f]),
     "atmvfi_pack_frames": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_f]),
     "atmvfi_final_residual": (c_i, [c_f, c_f, c_i, c_f, c_f, c_i, c_i, c_i, c_f]),
     "atmvfi_l1_mean": (c_i, [c_f, c_f, c_f, c_i, c_l, c_f, c_l, c_f]),
@@ -1302,6 +1304,51 @@ class HipOps:
         meta = {"bytes": float(fmt.frame_bytes) + (12.0 if src is not None else 3.0) * h * w}
         self._run("rgb_to_yuv420", meta, self.lib.atmvfi_rgb_to_yuv420, _ptr(src_u8), int(bool(bgr)), _ptr(src), hp, wp, int(pad_top),
                   int(pad_left), h, w, fmt.matrix_id, int(fmt.full_range), fmt.siting_id, _ptr(yuv), self._stream())
+
+    def yuv420p10_to_f32(self, yuv, fmt, dst, window=None, pad_top: int = 0, pad_left: int = 0):
+        """One packed 10-bit I420 frame of ``fmt`` (a ``yuv.Format`` of depth 10; a contiguous CUDA uint8 tensor of ``fmt.frame_bytes``
+        bytes, little-endian uint16 samples, any alignment) -> ``dst`` fp32 planar RGB [3,Hp,Wp] = q / 1023 with the depth kept:
+        ``window=(y0, x0, h, w)`` of the frame (default: all of it; even origin) at (pad_top, pad_left), replicate padding
+        (include/atmvfi.h atmvfi_yuv420p10_to_f32; the bits of ``yuv.decode_numpy_f32``)."""
+        h, w = fmt.height, fmt.width
+        if fmt.depth != 10:
+            raise ValueError("yuv420p10_to_f32: a 10-bit format expected (yuv420_to_rgb decodes 8-bit frames)")
+        if yuv.dtype != torch.uint8 or yuv.dim() != 1 or yuv.numel() != fmt.frame_bytes or not yuv.is_contiguous() or not yuv.is_cuda:
+            raise ValueError(f"yuv420p10_to_f32: source must be a contiguous CUDA uint8 tensor of {fmt.frame_bytes} bytes ({h} x {w} "
+                             f"10-bit I420)")
+        if dst is None or dst.dtype != torch.float32 or dst.dim() != 3 or dst.shape[0] != 3 or not dst.is_contiguous() or not dst.is_cuda:
+            raise ValueError("yuv420p10_to_f32: dst must be a contiguous CUDA fp32 [3,Hp,Wp] tensor")
+        y0, x0, wh, ww = (0, 0, h, w) if window is None else (int(v) for v in window)
+        if y0 % 2 or x0 % 2:
+            raise ValueError(f"yuv420p10_to_f32: the window origin ({y0}, {x0}) must be even for 4:2:0 frames")
+        if y0 < 0 or x0 < 0 or wh < 1 or ww < 1 or y0 + wh > h or x0 + ww > w:
+            raise ValueError(f"yuv420p10_to_f32: window {wh} x {ww} at ({y0}, {x0}) outside the {h} x {w} frame")
+        hp, wp = dst.shape[1], dst.shape[2]
+        if pad_top < 0 or pad_left < 0 or wh + pad_top > hp or ww + pad_left > wp:
+            raise ValueError(f"yuv420p10_to_f32: canvas {hp} x {wp} is smaller than the window {wh} x {ww} plus padding ({pad_top}, {pad_left})")
+        meta = {"bytes": float(fmt.frame_bytes) + 12.0 * hp * wp}
+        self._run("yuv420p10_to_f32", meta, self.lib.atmvfi_yuv420p10_to_f32, _ptr(yuv), h, w, fmt.matrix_id, fmt.siting_id, y0, x0, wh, ww,
+                  _ptr(dst), hp, wp, int(pad_top), int(pad_left), self._stream())
+
+    def f32_to_yuv420p10(self, yuv, fmt, src, pad_top: int = 0, pad_left: int = 0):
+        """``src`` fp32 planar RGB [3,Hp,Wp] with the frame at (pad_top, pad_left) -> ``yuv``, a packed 10-bit I420 frame of ``fmt`` (a
+        ``yuv.Format`` of depth 10; a contiguous CUDA uint8 tensor of ``fmt.frame_bytes`` bytes, little-endian uint16 samples;
+        include/atmvfi.h atmvfi_f32_to_yuv420p10).  The pixel is clip(rint(x * 1023), 0, 1023); the bits of ``yuv.encode_numpy`` of
+        an fp32 source."""
+        h, w = fmt.height, fmt.width
+        if fmt.depth != 10:
+            raise ValueError("f32_to_yuv420p10: a 10-bit format expected (rgb_to_yuv420 encodes 8-bit frames)")
+        if yuv.dtype != torch.uint8 or yuv.dim() != 1 or yuv.numel() != fmt.frame_bytes or not yuv.is_contiguous() or not yuv.is_cuda:
+            raise ValueError(f"f32_to_yuv420p10: destination must be a contiguous CUDA uint8 tensor of {fmt.frame_bytes} bytes ({h} x {w} "
+                             f"10-bit I420)")
+        if src is None or src.dtype != torch.float32 or src.dim() != 3 or src.shape[0] != 3 or not src.is_contiguous() or not src.is_cuda:
+            raise ValueError("f32_to_yuv420p10: src must be a contiguous CUDA fp32 [3,Hp,Wp] tensor")
+        hp, wp = src.shape[1], src.shape[2]
+        if pad_top < 0 or pad_left < 0 or h + pad_top > hp or w + pad_left > wp:
+            raise ValueError(f"f32_to_yuv420p10: canvas {hp} x {wp} is smaller than the frame {h} x {w} plus padding ({pad_top}, {pad_left})")
+        meta = {"bytes": float(fmt.frame_bytes) + 12.0 * h * w}
+        self._run("f32_to_yuv420p10", meta, self.lib.atmvfi_f32_to_yuv420p10, _ptr(src), hp, wp, int(pad_top), int(pad_left), h, w,
+                  fmt.matrix_id, fmt.siting_id, _ptr(yuv), self._stream())
 
     def frame_f32_to_u8(self, src, dst_u8, pad_top: int, pad_left: int, bgr: bool):
         """fp32 planar [3,Hp,Wp] -> crop -> np.round(x * 255) -> uint8 [H,W,3] device tensor (optional RGB -> BGR)."""

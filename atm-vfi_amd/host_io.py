@@ -242,10 +242,14 @@ class FramePipeline:
     arrays (1-D; uint16 samples for a 10-bit format, whose output is 8-bit).  Pinned and device staging hold ``frame_bytes`` per frame
     (1.5 bytes per pixel); ``atmvfi_yuv420_to_rgb`` runs on the copy stream behind the upload and writes the padded fp32 input directly
     -- and, with ``scene``, the resident uint8 RGB frame the signature reads -- and ``atmvfi_rgb_to_yuv420`` encodes the prediction from
-    fp32 in front of the device -> host copy.  ``isBGR`` is ignored."""
+    fp32 in front of the device -> host copy.  ``isBGR`` is ignored.
+
+    ``keep_depth`` (default False; changes nothing without a 10-bit ``pixfmt``): ``atmvfi_yuv420p10_to_f32`` decodes the uploaded
+    I420 bytes straight into the padded input (q / 1023: no 8-bit round trip), ``atmvfi_f32_to_yuv420p10`` encodes the prediction,
+    and the frames leave as 1-D uint16 arrays of ``pixfmt``.  The uint8 RGB frame is made only for a ``scene`` signature."""
 
     def __init__(self, model, height: int, width: int, isBGR: bool = True, divisor: int = 64, depth: int = 3, streams: int = 1,
-                 scene=None, pixfmt=None):
+                 scene=None, pixfmt=None, keep_depth: bool = False):
         ops, dev = _hip_ops_of(model)
         if ops is None:
             raise RuntimeError("FramePipeline needs an atm-vfi_amd Network on the GPU")
@@ -261,10 +265,11 @@ class FramePipeline:
         self.hp, self.wp = height + pad._pad[2] + pad._pad[3], width + pad._pad[0] + pad._pad[1]
         mk = lambda *s, dt: torch.empty(*s, dtype=dt, device=dev)
         self.pixfmt = pixfmt
+        self.deep = bool(keep_depth) and pixfmt is not None and pixfmt.depth == 10
         if pixfmt is not None:
             if (pixfmt.height, pixfmt.width) != (height, width):
                 raise ValueError(f"FramePipeline: pixfmt describes {pixfmt.height}x{pixfmt.width} frames, the pipeline {height}x{width}")
-            self.bgr, self.out_fmt = False, pixfmt.as_8bit()
+            self.bgr, self.out_fmt = False, (pixfmt if self.deep else pixfmt.as_8bit())
         in_shape = (height, width, 3) if pixfmt is None else (pixfmt.frame_bytes,)
         out_shape = (height, width, 3) if pixfmt is None else (self.out_fmt.frame_bytes,)
         self.slots = [{
@@ -305,6 +310,11 @@ class FramePipeline:
             if self.pixfmt is not None:
                 # the slot's previous pair has been delivered (run): its forward no longer reads f0 / f1
                 for k, f in enumerate((slot["f0"], slot["f1"])):
+                    if self.deep:
+                        self.ops.yuv420p10_to_f32(slot["d_in"][k], self.pixfmt, f[0], pad_top=self.pad_top, pad_left=self.pad_left)
+                        if self.scene is not None:        # the 8-bit path's signature: its uint8 RGB frame
+                            self.ops.yuv420_to_rgb(slot["d_in"][k], self.pixfmt, dst_u8=slot["rgb"][k])
+                        continue
                     self.ops.yuv420_to_rgb(slot["d_in"][k], self.pixfmt, dst_u8=slot["rgb"][k] if self.scene is not None else None,
                                            dst=f[0], pad_top=self.pad_top, pad_left=self.pad_left)
             slot["in_ready"].record(self.copy_in)
@@ -327,7 +337,8 @@ class FramePipeline:
         if slot["cut"]:
             return np.array(slot["first"], copy=True)
         slot["out_ready"].synchronize()
-        return slot["h_out"].numpy().copy()
+        out = slot["h_out"].numpy().copy()
+        return out.view(np.uint16) if self.deep else out
 
     def _compute(self, slot):
         slot["cut"] = self.scene is not None and self._is_cut(slot)
@@ -350,6 +361,8 @@ class FramePipeline:
         it = model.forward(slot["f0"], slot["f1"])["I_t"]
         if self.pixfmt is None:
             self.ops.frame_f32_to_u8(it[0], slot["d_out"], self.pad_top, self.pad_left, self.bgr)
+        elif self.deep:
+            self.ops.f32_to_yuv420p10(slot["d_out"], self.out_fmt, it[0], pad_top=self.pad_top, pad_left=self.pad_left)
         else:
             self.ops.rgb_to_yuv420(slot["d_out"], self.out_fmt, src=it[0], pad_top=self.pad_top, pad_left=self.pad_left)
         slot["done"].record(cur)
@@ -386,14 +399,16 @@ class FramePipeline:
 
 
 def interpolate_video_2x(frames, model, isBGR: bool = True, divisor: int = 64, depth: int = 3, streams: int = 1, scene=None,
-                         pixfmt=None):
+                         pixfmt=None, keep_depth: bool = False):
     """The frame loop of demo_2x.py:144-163 over any iterable of uint8 [H,W,3] frames (decoding / encoding stays with the caller):
     yields f0, I(f0,f1), f1, I(f1,f2), ..., f_{n-1} -- 2n-1 frames -- with the pairs running through ``FramePipeline``
     (``streams`` > 1: that many forwards in flight on streams of their own, for frames too small to fill the GPU one at a time).
     ``scene`` (a ``scene.SceneCuts``; not in the script): a pair classed a scene cut runs no forward and its middle frame is a copy of
     the pair's first frame; ``scene.cuts`` holds the cut pairs' indices afterwards.
     ``pixfmt`` (a ``yuv.Format``): the frames are packed planar I420 arrays, in and out; originals pass through as the caller's own
-    bytes (no colour round trip), predictions are encoded on the device (8-bit, also for 10-bit input); ``isBGR`` is ignored."""
+    bytes (no colour round trip), predictions are encoded on the device (8-bit, also for 10-bit input); ``isBGR`` is ignored.
+    ``keep_depth`` (changes nothing without a 10-bit ``pixfmt``): the network sees q / 1023 and the predictions leave as 10-bit frames
+    (1-D uint16 arrays), see ``FramePipeline``."""
     from collections import deque
     it = iter(frames)
     first = next(it, None)
@@ -408,7 +423,8 @@ def interpolate_video_2x(frames, model, isBGR: bool = True, divisor: int = 64, d
             yield prev, cur
             prev = cur
     height, width = first.shape[:2] if pixfmt is None else (pixfmt.height, pixfmt.width)
-    pipe = FramePipeline(model, height, width, isBGR=isBGR, divisor=divisor, depth=depth, streams=streams, scene=scene, pixfmt=pixfmt)
+    pipe = FramePipeline(model, height, width, isBGR=isBGR, divisor=divisor, depth=depth, streams=streams, scene=scene, pixfmt=pixfmt,
+                         keep_depth=keep_depth)
     for pred in pipe.run(pairs()):
         yield originals.popleft()
         yield pred

@@ -145,15 +145,18 @@ class _Uploader:
 
     ``pixfmt=(ops, fmt)`` (planar I420 input): pinned and device staging hold ``fmt.frame_bytes``; ``atmvfi_yuv420_to_rgb`` runs on the
     copy stream behind the copy and fills the slot's resident uint8 RGB frame ``d`` -- what the signature, ``take`` and everything
-    downstream read, as for an RGB upload."""
+    downstream read, as for an RGB upload.  ``deep`` (a 10-bit ``pixfmt`` with ``keep_depth``): ``take`` hands the uploaded I420 bytes
+    themselves to ``convert`` (``atmvfi_yuv420p10_to_f32`` decodes them into the pool slot: no 8-bit round trip); the uint8 RGB frame is
+    made only for a signature."""
 
-    def __init__(self, dev, height: int, width: int, depth: int = 3, signature=None, pixfmt=None):
+    def __init__(self, dev, height: int, width: int, depth: int = 3, signature=None, pixfmt=None, deep: bool = False):
         import torch
         self.torch, self.dev, self.h, self.w, self.depth = torch, dev, height, width, depth
-        self.sig, self.pixfmt = signature, pixfmt
+        self.sig, self.pixfmt, self.deep = signature, pixfmt, bool(deep)
         in_shape = (height, width, 3) if pixfmt is None else (pixfmt[1].frame_bytes,)
+        need_rgb = not self.deep or signature is not None
         self.ring = [{"h": torch.empty(*in_shape, dtype=torch.uint8).pin_memory(),
-                      "d": torch.empty(height, width, 3, dtype=torch.uint8, device=dev),
+                      "d": torch.empty(height, width, 3, dtype=torch.uint8, device=dev) if need_rgb else None,
                       "ready": torch.cuda.Event(), "free": torch.cuda.Event()} for _ in range(depth)]
         for s in self.ring:
             s["h_np"] = s["h"].numpy()
@@ -184,7 +187,8 @@ class _Uploader:
                 slot["d"].copy_(slot["h"], non_blocking=True)
             else:
                 slot["yuv"].copy_(slot["h"], non_blocking=True)
-                self.pixfmt[0].yuv420_to_rgb(slot["yuv"], self.pixfmt[1], dst_u8=slot["d"])
+                if slot["d"] is not None:
+                    self.pixfmt[0].yuv420_to_rgb(slot["yuv"], self.pixfmt[1], dst_u8=slot["d"])
             slot["ready"].record(self.copy_in)
             if self.sig is not None:
                 ops, (y0, x0, h, w), bgr = self.sig
@@ -200,10 +204,10 @@ class _Uploader:
         return slot["sig_h_np"].copy()
 
     def take(self, slot, convert):
-        """Run ``convert(device uint8 frame)`` on the current stream once the slot's copy has landed."""
+        """Run ``convert(device uint8 frame)`` on the current stream once the slot's copy has landed (``deep``: the device I420 bytes)."""
         cur = self.torch.cuda.current_stream(self.dev)
         cur.wait_event(slot["ready"])
-        convert(slot["d"])
+        convert(slot["yuv"] if self.deep else slot["d"])
         slot["free"].record(cur)
 
 
@@ -216,7 +220,7 @@ class _SegmentRunner:
     per level at 8x (batch sizes 1, 2, 4).  The runner RAISES ``model.max_workspaces`` to the number of batch sizes of its schedule for
     its lifetime and restores it in ``close()``."""
 
-    def __init__(self, model, ops, dev, height, width, factor, crop, bgr, divisor, tta, max_batch, pool, out_fmt=None):
+    def __init__(self, model, ops, dev, height, width, factor, crop, bgr, divisor, tta, max_batch, pool, out_fmt=None, deep_fmt=None):
         import torch
         from .host_io import InputPadder
         self.torch, self.model, self.ops, self.dev = torch, model, ops, dev
@@ -248,11 +252,17 @@ class _SegmentRunner:
         # plain mode: the pairs of a batch are gathered into contiguous [B,3,Hp,Wp] inputs
         self.gather = {}
         # out_fmt (a yuv.Format of the window's size): the produced frames leave as packed I420 (rgb_to_yuv420) instead of uint8 RGB
-        self.out_fmt = out_fmt
+        # deep_fmt (the 10-bit input Format, with keep_depth): source frames are decoded from their I420 bytes straight into the pool
+        # slot (yuv420p10_to_f32, the crop as the kernel's window) and produced frames leave as 10-bit I420 (f32_to_yuv420p10; out_fmt
+        # is 10-bit then)
+        self.out_fmt, self.deep_fmt = out_fmt, deep_fmt
         out_shape = (self.h, self.w, 3) if out_fmt is None else (out_fmt.frame_bytes,)
         self.out_d = torch.empty(factor - 1, *out_shape, dtype=torch.uint8, device=dev)
         self.out_h = [torch.empty(factor - 1, *out_shape, dtype=torch.uint8).pin_memory() for _ in range(2)]
-        self.merged = torch.empty(self.h, self.w, 3, dtype=torch.uint8, device=dev) if (out_fmt is not None and self.tta) else None
+        self.merged = None
+        if out_fmt is not None and self.tta:         # the average: its uint8 pixels, or with the depth kept the fp32 canvas itself
+            self.merged = (torch.empty(3, self.hp, self.wp, dtype=torch.float32, device=dev) if deep_fmt is not None else
+                           torch.empty(self.h, self.w, 3, dtype=torch.uint8, device=dev))
         self.out_evt = [torch.cuda.Event() for _ in range(2)]
         self.seg = 0
         self.copy_out = torch.cuda.Stream(dev)
@@ -275,7 +285,10 @@ class _SegmentRunner:
 
         def convert(d_u8):
             dst = self.frames[0][slot]
-            if (self.y0, self.x0, self.h, self.w) == (0, 0) + tuple(d_u8.shape[:2]):
+            if self.deep_fmt is not None:             # d_u8: the frame's I420 bytes
+                self.ops.yuv420p10_to_f32(d_u8, self.deep_fmt, dst, window=(self.y0, self.x0, self.h, self.w), pad_top=self.pad_top,
+                                          pad_left=self.pad_left)
+            elif (self.y0, self.x0, self.h, self.w) == (0, 0) + tuple(d_u8.shape[:2]):
                 self.ops.frame_u8_to_f32(d_u8, dst, self.pad_top, self.pad_left, self.bgr)
             else:
                 self.ops.frame_u8_window(d_u8, 0, self.y0, self.x0, self.h, self.w, dst=dst, pad_top=self.pad_top, pad_left=self.pad_left,
@@ -326,7 +339,13 @@ class _SegmentRunner:
                     flip = self._forward(1, lefts, rights) if self.tta else None
                     for j, (_, _, pos) in enumerate(chunk):
                         u8 = self.out_d[pos - 1]
-                        if self.out_fmt is not None:
+                        if self.deep_fmt is not None:
+                            src = pred[j]
+                            if self.tta:               # the fp32 average, then its encoding
+                                self.ops.tta_merge(pred[j], flip[j], out=self.merged)
+                                src = self.merged
+                            self.ops.f32_to_yuv420p10(u8, self.out_fmt, src, pad_top=self.pad_top, pad_left=self.pad_left)
+                        elif self.out_fmt is not None:
                             if self.tta:               # the average's uint8 pixels, then their encoding
                                 self.ops.tta_merge(pred[j], flip[j], out_u8=self.merged, pad_top=self.pad_top, pad_left=self.pad_left,
                                                    bgr=False)
@@ -362,17 +381,23 @@ class _SegmentRunner:
     def result(self, ring) -> List[np.ndarray]:
         self.out_evt[ring].synchronize()
         arr = self.out_h[ring].numpy()
+        if self.deep_fmt is not None:
+            return [arr[k].copy().view(np.uint16) for k in range(self.n - 1)]
         return [arr[k].copy() for k in range(self.n - 1)]
 
 
-def _generic_segment(model, factor, crop_of, isBGR, divisor, tta, max_batch):
-    """``segment`` for a model without the HIP backend (any callable ``forward(im0, im1) -> {"I_t"}``): torch ops, same schedule."""
+def _generic_segment(model, factor, crop_of, isBGR, divisor, tta, max_batch, load=None, store=None):
+    """``segment`` for a model without the HIP backend (any callable ``forward(im0, im1) -> {"I_t"}``): torch ops, same schedule.
+    ``load(frame) -> fp32 [h,w,3]`` / ``store(fp32 [h,w,3]) -> frame`` replace the uint8 RGB conversions at both ends (the 10-bit
+    I420 twins, with ``keep_depth``)."""
     import torch
     from .host_io import InputPadder
     dev = next(model.parameters()).device
     levels = nx_levels(factor)
 
     def to_t(img):
+        if load is not None:
+            return torch.tensor(np.ascontiguousarray(load(img).transpose(2, 0, 1))).to(dev).unsqueeze(0)
         img = crop_of(img)
         if isBGR:
             img = img[:, :, ::-1]
@@ -403,6 +428,9 @@ def _generic_segment(model, factor, crop_of, isBGR, divisor, tta, max_batch):
             p = shown[pos]
             if padder:
                 p = padder.unpad(p)
+            if store is not None:
+                res.append(store(np.ascontiguousarray(p[0].detach().float().cpu().numpy().transpose(1, 2, 0))))
+                continue
             p = np.round(p[0].detach().cpu().numpy().transpose(1, 2, 0) * 255).astype(np.uint8)
             res.append(p[:, :, ::-1].copy() if isBGR else p)
         return res
@@ -410,7 +438,8 @@ def _generic_segment(model, factor, crop_of, isBGR, divisor, tta, max_batch):
 
 
 def interpolate_video_nx(frames, model, factor: int = 4, time_interval: int = 1, crop: Optional[Tuple[int, int]] = None, isBGR: bool = True,
-                         divisor: Optional[int] = 64, tta: bool = False, max_batch: int = 4, pool: bool = True, scene=None, pixfmt=None):
+                         divisor: Optional[int] = 64, tta: bool = False, max_batch: int = 4, pool: bool = True, scene=None, pixfmt=None,
+                         keep_depth: bool = False):
     """N-x slow motion over any iterable of uint8 [H,W,3] frames (davis-vid.py:88-135; decoding / encoding stays with the caller):
     per segment ``(f_i, f_{i+s})``, ``s = time_interval``, yields ``f_i`` and the frames at t = 1/N ... (N-1)/N, after the last segment
     its second frame once -- ``segments * N + 1`` frames.  Originals pass through bit-equal (their centre ``crop=(h, w)`` window when
@@ -433,7 +462,14 @@ def interpolate_video_nx(frames, model, factor: int = 4, time_interval: int = 1,
     frame is uploaded as I420 and decoded once on the copy stream into the resident uint8 RGB frame everything above reads; produced
     frames are encoded on the device (8-bit, also for 10-bit input) in front of the device -> host copy.  Originals -- cut copies
     included -- pass through as the caller's own bytes (``yuv.crop`` of them when cropping: the crop origin must be even, else
-    ``ValueError``); ``isBGR`` is ignored."""
+    ``ValueError``); ``isBGR`` is ignored.
+
+    ``keep_depth`` (default False; changes nothing without a 10-bit ``pixfmt``): the 10-bit depth is kept end to end.  Every uploaded
+    frame is decoded by ``atmvfi_yuv420p10_to_f32`` straight from its I420 bytes into the pool slot (the crop as the kernel's window;
+    the network sees q / 1023, no 8-bit round trip), produced frames are ``atmvfi_f32_to_yuv420p10`` of the fp32 prediction (with
+    ``tta``: of the fp32 average) and leave as 1-D uint16 arrays of ``pixfmt.cropped(h, w)``; deeper levels consume the unrounded
+    prediction as always.  The resident uint8 RGB frame is made only when ``scene`` needs its signature: signatures, and so cut
+    decisions, are those of the 8-bit path.  A model without the HIP backend does the same with the numpy twins."""
     from .host_io import _hip_ops_of
     from .scene import cut_fill, signature_numpy
     nx_levels(factor)
@@ -451,13 +487,19 @@ def interpolate_video_nx(frames, model, factor: int = 4, time_interval: int = 1,
         from . import yuv
         if crop is not None and (y0 % 2 or x0 % 2):
             raise ValueError(f"interpolate_video_nx: the crop origin ({y0}, {x0}) must be even for 4:2:0 frames")
-        isBGR, out_fmt = False, pixfmt.as_8bit().cropped(h, w)
+        deep = bool(keep_depth) and pixfmt.depth == 10
+        isBGR, out_fmt = False, (pixfmt if deep else pixfmt.as_8bit()).cropped(h, w)
         crop_rgb, whole = crop_of, (h, w) == (H, W)
         crop_of = (lambda f: f) if whole else (lambda f: yuv.crop(f, pixfmt, y0, x0, h, w))          # of the caller's I420 frames
     ops, dev = _hip_ops_of(model)
     if ops is None or not hasattr(ops, "pool_blocks"):
-        seg = _generic_segment(model, factor, crop_of if pixfmt is None else crop_rgb, isBGR, divisor, tta, max(1, int(max_batch)))
-        if pixfmt is not None:
+        if pixfmt is not None and deep:
+            seg = _generic_segment(model, factor, None, False, divisor, tta, max(1, int(max_batch)),
+                                   load=lambda f: yuv.decode_numpy_f32(f, pixfmt, window=(y0, x0, h, w)),
+                                   store=lambda p: yuv.encode_numpy(p, out_fmt))
+        else:
+            seg = _generic_segment(model, factor, crop_of if pixfmt is None else crop_rgb, isBGR, divisor, tta, max(1, int(max_batch)))
+        if pixfmt is not None and not deep:
             rgb_segment, decoded = seg, {"of": None, "rgb": None}
 
             def rgb_of(f):
@@ -487,9 +529,10 @@ def interpolate_video_nx(frames, model, factor: int = 4, time_interval: int = 1,
                 yield f if f.shape[:2] == (h, w) else crop_of(f)
         return
     runner = _SegmentRunner(model, ops, dev, H, W, factor, crop, isBGR, divisor, tta, max_batch,
-                            pool and hasattr(model, "forward_pooled"), out_fmt=out_fmt)
+                            pool and hasattr(model, "forward_pooled"), out_fmt=out_fmt,
+                            deep_fmt=pixfmt if (pixfmt is not None and deep) else None)
     up = _Uploader(dev, H, W, signature=None if scene is None else (ops, (y0, x0, h, w), bool(isBGR)),
-                   pixfmt=None if pixfmt is None else (ops, pixfmt))
+                   pixfmt=None if pixfmt is None else (ops, pixfmt), deep=pixfmt is not None and deep)
     state = {"first": True, "sig": None}
 
     def segment(fa, fb):

@@ -11,7 +11,13 @@ back (ch = (H + 1) // 2, cw = (W + 1) // 2; uint8, or uint16 0..1023 for depth 1
 (3, 1) taps (left siting: (4, 0) / (2, 2) horizontally) and applies ``COEFFS[matrix, full_range][0]`` at 14 bits; encoding takes the
 uint8 RGB pixel (from fp32: ``frame_f32_to_u8``'s pixel), box-filters chroma over 2 x 2 (left siting: 1-2-1 x 2) un-rounded sums and
 applies ``COEFFS[..][1]``.  Not reproduced: ffmpeg's swscale (other filters, other rounding) -- it is not available to compare with.
-10-bit input is decoded to 8-bit RGB; what the loops produce is 8-bit."""
+By default 10-bit input is decoded to 8-bit RGB and what the loops produce is 8-bit.
+
+``keep_depth=True`` (the loops, ``interpolate_y4m``) keeps a 10-bit format's depth end to end (``atmvfi_yuv420p10_to_f32`` /
+``atmvfi_f32_to_yuv420p10``, csrc/yuv10.hip; twins ``decode_numpy_f32`` and ``encode_numpy`` of an fp32 source): the same chroma
+filters on the 10-bit samples, ``COEFFS10[matrix]`` at 14 bits (luma scaled by 876 / 1023, chroma by 896 / 1023), offsets 64 / 512,
+RGB clipped to 0..1023 and handed to the network as ``q / 1023`` (the fp32 division); encoding takes
+``clip(rint(fl32(x * 1023)), 0, 1023)`` and writes uint16 samples.  Produced frames are 10-bit, originals the caller's arrays."""
 from __future__ import annotations
 
 import io
@@ -28,12 +34,20 @@ KR_KB = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}
 SHIFT = 14
 
 
-def derive_coeffs(matrix: str, full_range: bool):
+def derive_coeffs(matrix: str, full_range: bool = False, depth: int = 8):
     """([kY, kRV, kGU, kGV, kBU], 3 x 3 encode rows Y / U / V over (R, G, B)) = rint(c * 2^14) of the float64 matrices of (Kr, Kb);
-    limited range scales luma by 219 / 255 and chroma by 224 / 255."""
+    limited range scales luma by 219 / 255 and chroma by 224 / 255.  ``depth=10`` (limited range only; 10-bit RGB on the other side,
+    ``COEFFS10``): luma by 876 / 1023, chroma by 896 / 1023."""
     kr, kb = KR_KB[matrix]
     kg = 1.0 - kr - kb
-    sy, sc = (1.0, 1.0) if full_range else (219.0 / 255.0, 224.0 / 255.0)
+    if depth == 10:
+        if full_range:
+            raise ValueError("derive_coeffs: 10-bit full range is not supported")
+        sy, sc = 876.0 / 1023.0, 896.0 / 1023.0
+    elif depth == 8:
+        sy, sc = (1.0, 1.0) if full_range else (219.0 / 255.0, 224.0 / 255.0)
+    else:
+        raise ValueError(f"derive_coeffs: depth must be 8 or 10 (got {depth!r})")
     dec = [1.0 / sy, 2 * (1 - kr) / sc, -2 * (1 - kb) * kb / kg / sc, -2 * (1 - kr) * kr / kg / sc, 2 * (1 - kb) / sc]
     enc = [[kr * sy, kg * sy, kb * sy],
            [-kr / (2 * (1 - kb)) * sc, -kg / (2 * (1 - kb)) * sc, 0.5 * sc],
@@ -48,6 +62,12 @@ COEFFS = {
     ("bt601", True): ((16384, 22970, -5638, -11700, 29032), ((4899, 9617, 1868), (-2765, -5427, 8192), (8192, -6860, -1332))),
     ("bt709", False): ((19077, 29372, -3494, -8731, 34610), ((2991, 10064, 1016), (-1649, -5547, 7196), (7196, -6536, -660))),
     ("bt709", True): ((16384, 25802, -3069, -7670, 30402), ((3483, 11718, 1183), (-1877, -6315, 8192), (8192, -7441, -751))),
+}
+
+# matrix -> the same pair with the depth kept (10-bit limited-range samples <-> 10-bit RGB); the table of csrc/yuv10.hip
+COEFFS10 = {
+    "bt601": ((19133, 26226, -6438, -13359, 33148), ((4195, 8235, 1599), (-2421, -4754, 7175), (7175, -6008, -1167))),
+    "bt709": ((19133, 29459, -3504, -8757, 34711), ((2983, 10034, 1013), (-1644, -5531, 7175), (7175, -6517, -658))),
 }
 
 
@@ -165,22 +185,68 @@ def decode_numpy(buf, fmt: Format, bgr: bool = False) -> np.ndarray:
     return np.clip(np.stack([b, g, r] if bgr else [r, g, b], axis=-1), 0, 255).astype(np.uint8)
 
 
+def decode_numpy_f32(buf, fmt: Format, window=None) -> np.ndarray:
+    """Packed 10-bit I420 frame -> fp32 [h,w,3] RGB = q / 1023, the depth kept: the bits of ``atmvfi_yuv420p10_to_f32`` (without
+    padding).  ``window=(y0, x0, h, w)`` (even origin, as ``crop``): that window of the whole frame's decode -- chroma neighbours
+    are the frame's, not the window's."""
+    if fmt.depth != 10:
+        raise ValueError("decode_numpy_f32: a 10-bit format expected (8-bit frames decode with decode_numpy)")
+    Y, U, V = (p.astype(np.int32) for p in fmt.planes(buf))
+    H, W = fmt.height, fmt.width
+    y0, x0, h, w = (0, 0, H, W) if window is None else (int(v) for v in window)
+    if y0 % 2 or x0 % 2:
+        raise ValueError(f"decode_numpy_f32: the window origin ({y0}, {x0}) must be even for 4:2:0 frames")
+    if y0 < 0 or x0 < 0 or h < 1 or w < 1 or y0 + h > H or x0 + w > W:
+        raise ValueError(f"decode_numpy_f32: window {h} x {w} at ({y0}, {x0}) outside the {H} x {W} frame")
+    ch, cw = fmt.chroma_shape
+    ys, xs = np.arange(y0, y0 + h), np.arange(x0, x0 + w)
+    r0 = ys >> 1
+    r1 = np.clip(r0 + np.where(ys & 1, 1, -1), 0, ch - 1)
+    q0 = xs >> 1
+    if fmt.siting == "left":
+        q1 = np.minimum(q0 + 1, cw - 1)
+        wx0 = np.where(xs & 1, 2, 4).astype(np.int32)
+    else:
+        q1 = np.clip(q0 + np.where(xs & 1, 1, -1), 0, cw - 1)
+        wx0 = np.full(w, 3, np.int32)
+    wx1 = 4 - wx0
+
+    def up(c):
+        a = wx0 * c[:, q0] + wx1 * c[:, q1]
+        return (3 * a[r0] + a[r1] + 8) >> 4
+
+    (kY, kRV, kGU, kGV, kBU), _ = COEFFS10[fmt.matrix]
+    y, u, v = kY * (Y[y0:y0 + h, x0:x0 + w] - 64), up(U) - 512, up(V) - 512
+    half = 1 << 13
+    r = (y + kRV * v + half) >> 14
+    g = (y + kGU * u + kGV * v + half) >> 14
+    b = (y + kBU * u + half) >> 14
+    return np.clip(np.stack([r, g, b], axis=-1), 0, 1023).astype(np.float32) / np.float32(1023)
+
+
 def encode_numpy(rgb, fmt: Format, bgr: bool = False) -> np.ndarray:
-    """uint8 [H,W,3] RGB (BGR if ``bgr``) -> packed 8-bit I420 frame (1-D uint8): the bits of ``atmvfi_rgb_to_yuv420``."""
+    """uint8 [H,W,3] RGB (BGR if ``bgr``) -> packed 8-bit I420 frame (1-D uint8): the bits of ``atmvfi_rgb_to_yuv420``.  For a 10-bit
+    ``fmt``: fp32 [H,W,3] RGB in units of 1 (finite; values outside [0, 1] clamp) -> packed 10-bit frame (1-D uint16), the pixel
+    ``clip(rint(fl32(x * 1023)), 0, 1023)``: the bits of ``atmvfi_f32_to_yuv420p10``; a uint8 source is refused."""
     rgb = np.asarray(rgb)
-    if fmt.depth != 8:
-        raise ValueError("encode_numpy: encoding is 8-bit only")
-    if rgb.dtype != np.uint8 or rgb.shape != (fmt.height, fmt.width, 3):
-        raise ValueError(f"encode_numpy: a uint8 [{fmt.height},{fmt.width},3] frame expected, got {rgb.dtype} {tuple(rgb.shape)}")
-    p = rgb.astype(np.int32)
+    deep = fmt.depth == 10 and rgb.dtype == np.float32
+    if fmt.depth != 8 and not deep:
+        raise ValueError("encode_numpy: encoding a uint8 source is 8-bit only (a 10-bit format takes an fp32 [H,W,3] source)")
+    if (not deep and rgb.dtype != np.uint8) or rgb.shape != (fmt.height, fmt.width, 3):
+        raise ValueError(f"encode_numpy: a {'float32' if deep else 'uint8'} [{fmt.height},{fmt.width},3] frame expected, got {rgb.dtype} "
+                         f"{tuple(rgb.shape)}")
+    if deep:
+        p = np.clip(np.rint(rgb * np.float32(1023.0)), 0, 1023).astype(np.int32)
+    else:
+        p = rgb.astype(np.int32)
     if bgr:
         p = p[:, :, ::-1]
     H, W = fmt.height, fmt.width
     ch, cw = fmt.chroma_shape
-    _, (eY, eU, eV) = COEFFS[fmt.matrix, fmt.full_range]
+    _, (eY, eU, eV) = COEFFS10[fmt.matrix] if deep else COEFFS[fmt.matrix, fmt.full_range]
     dot = lambda e, s: e[0] * s[..., 0] + e[1] * s[..., 1] + e[2] * s[..., 2]
-    yo = 0 if fmt.full_range else 16
-    Y = np.clip(((dot(eY, p) + (1 << 13)) >> 14) + yo, 0, 255)
+    yo, mid, top = (64, 512, 1023) if deep else (0 if fmt.full_range else 16, 128, 255)
+    Y = np.clip(((dot(eY, p) + (1 << 13)) >> 14) + yo, 0, top)
     ra = 2 * np.arange(ch)
     rows = p[ra] + p[np.minimum(ra + 1, H - 1)]
     ca = 2 * np.arange(cw)
@@ -188,9 +254,9 @@ def encode_numpy(rgb, fmt: Format, bgr: bool = False) -> np.ndarray:
         s, sh = rows[:, np.maximum(ca - 1, 0)] + 2 * rows[:, ca] + rows[:, np.minimum(ca + 1, W - 1)], 3
     else:
         s, sh = rows[:, ca] + rows[:, np.minimum(ca + 1, W - 1)], 2
-    U = np.clip(((dot(eU, s) + (1 << (13 + sh))) >> (14 + sh)) + 128, 0, 255)
-    V = np.clip(((dot(eV, s) + (1 << (13 + sh))) >> (14 + sh)) + 128, 0, 255)
-    return np.concatenate([Y.reshape(-1), U.reshape(-1), V.reshape(-1)]).astype(np.uint8)
+    U = np.clip(((dot(eU, s) + (1 << (13 + sh))) >> (14 + sh)) + mid, 0, top)
+    V = np.clip(((dot(eV, s) + (1 << (13 + sh))) >> (14 + sh)) + mid, 0, top)
+    return np.concatenate([Y.reshape(-1), U.reshape(-1), V.reshape(-1)]).astype(np.uint16 if deep else np.uint8)
 
 
 def crop(buf, fmt: Format, y0: int, x0: int, h: int, w: int) -> np.ndarray:
@@ -365,22 +431,28 @@ def to_8bit(frame, fmt: Format) -> np.ndarray:
     return encode_numpy(decode_numpy(frame, fmt), fmt.as_8bit())
 
 
-def interpolate_y4m(src, dst, model, factor: int = 2, scene=None, tta: bool = False, interpolator=None, matrix: str = "auto", **kw):
+def interpolate_y4m(src, dst, model, factor: int = 2, scene=None, tta: bool = False, interpolator=None, matrix: str = "auto",
+                    keep_depth: bool = False, **kw):
     """Y4M file (or binary file object) ``src`` -> Y4M ``dst`` at ``fps * factor`` (``/ time_interval`` when given): an exact
     rational, 30000/1001 in gives 60000/1001 out.  Frames travel as I420 both ways (``pixfmt``); originals are written as read,
     predicted frames are encoded on the device.  The same format tags are written; 10-bit input is decoded on the device and written
     back as 8-bit (C420jpeg), its originals converted on the host.  ``factor=2`` on a GPU ``Network`` without ``tta`` / ``crop`` /
     ``time_interval`` runs ``interpolate_video_2x``, everything else ``interpolate_video_nx``; ``interpolator(frames, model, pixfmt=,
-    ...)`` overrides.  ``matrix``: as for ``Y4MReader`` (a Y4M header cannot name it).  Returns ``{"fps_in", "fps_out", "size", "frames_in", "frames_out"}`` and, with ``scene``, ``"cuts"``."""
+    ...)`` overrides.  ``matrix``: as for ``Y4MReader`` (a Y4M header cannot name it).  ``keep_depth`` (changes nothing for 8-bit
+    input): a C420p10 stream is written back as C420p10 -- originals byte for byte as read, predictions encoded on the device from
+    the fp32 prediction at 10 bits; nothing is re-quantised to 8 bit.  Returns ``{"fps_in", "fps_out", "size", "frames_in", "frames_out"}`` and, with ``scene``, ``"cuts"``."""
     from .host_io import _hip_ops_of, interpolate_video_2x
     from .multiframe import centre_window, interpolate_video_nx, nx_levels
     nx_levels(factor)
     rd = Y4MReader(src, matrix=matrix)
     fmt = rd.fmt
     _, _, oh, ow = centre_window(fmt.height, fmt.width, kw.get("crop"))
-    out_fmt = fmt.as_8bit().cropped(oh, ow)
+    deep = bool(keep_depth) and fmt.depth == 10
+    out_fmt = (fmt if deep else fmt.as_8bit()).cropped(oh, ow)
     rate = rd.fps * factor / int(kw.get("time_interval", 1))
-    wr = Y4MWriter(dst, out_fmt, rate, ctag=rd.ctag if fmt.depth == 8 else None, aspect=rd.aspect)
+    wr = Y4MWriter(dst, out_fmt, rate, ctag=rd.ctag if (fmt.depth == 8 or deep) else None, aspect=rd.aspect)
+    if deep:
+        kw["keep_depth"] = True
     n_in = [0]
 
     def counted():
@@ -395,7 +467,7 @@ def interpolate_y4m(src, dst, model, factor: int = 2, scene=None, tta: bool = Fa
             interpolator = lambda frames, model, **k: interpolate_video_nx(frames, model, factor=factor, tta=tta, **k)
     try:
         for f in interpolator(counted(), model, pixfmt=fmt, scene=scene, **kw):
-            wr.write(to_8bit(f, fmt.cropped(oh, ow)) if f.dtype == np.uint16 else f)
+            wr.write(to_8bit(f, fmt.cropped(oh, ow)) if (f.dtype == np.uint16 and not deep) else f)
     finally:
         rd.close()
         wr.close()

@@ -505,6 +505,33 @@ int atmvfi_yuv420_to_rgb(const void* yuv, int H, int W, int depth, int matrix, i
 int atmvfi_rgb_to_yuv420(const void* src_u8, int bgr, const float* src, int Hp, int Wp, int pad_top, int pad_left, int H, int W,
                          int matrix, int full_range, int siting, void* yuv, void* stream);
 
+/* The same frames with the 10-bit depth kept end to end (yuv10.hip; ABI 0.15): 10-bit limited-range I420 (little-endian uint16, values
+ * 0..1023; frame layout, matrix and siting as above) <-> fp32 planar RGB in units of 1 / 1023.  The calls above decode 10-bit samples
+ * to clip8 RGB and encode 8-bit frames only; these hand the network q / 1023 and write its prediction back as 10-bit samples.  The
+ * project's own bit-exact contract in int32 (>> floors); yuv.decode_numpy_f32 / yuv.encode_numpy give the same bits on the host.
+ * Coefficients: rint(c * 2^14) of the same float64 matrices, luma scaled by 876 / 1023 and chroma by 896 / 1023:
+ *                       decode [kY, kRV, kGU, kGV, kBU]        encode rows Y / U / V over (R, G, B)
+ *     bt601 10 bit    19133, 26226,  -6438, -13359, 33148    (4195,  8235, 1599) / (-2421, -4754, 7175) / (7175, -6008, -1167)
+ *     bt709 10 bit    19133, 29459,  -3504,  -8757, 34711    (2983, 10034, 1013) / (-1644, -5531, 7175) / (7175, -6517,  -658)
+ * atmvfi_yuv420p10_to_f32: chroma upsampling exactly as above (rows, columns, weights for both sitings, (.. + 8) >> 4) on the 10-bit
+ *   samples; y = Y - 64, u = U' - 512, v = V' - 512; R10 = clip(0, 1023, (kY y + kRV v + 2^13) >> 14),
+ *   G10 = clip(0, 1023, (kY y + kGU u + kGV v + 2^13) >> 14), B10 = clip(0, 1023, (kY y + kBU u + 2^13) >> 14); dst fp32 planar RGB
+ *   [3,Hp,Wp] = q / 1023 with the bits of the fp32 division.  The call decodes the window (y0, x0, h, w) of the H x W frame -- inside the
+ *   frame, even origin -- to (pad_top, pad_left) of the canvas, replicate padding by clamping the output coordinate into the window.
+ *   The window is a window of the whole frame's decode: chroma neighbours clamp at the frame's edges, not the window's.
+ * atmvfi_f32_to_yuv420p10: src fp32 planar RGB [3,Hp,Wp], the frame at (pad_top, pad_left); source pixel p = clip(0, 1023,
+ *   rint(fl32(x * 1023))), half to even (finite inputs; values outside [0, 1] clamp); Y = clip(0, 1023, ((eY . p + 2^13) >> 14) + 64);
+ *   chroma from the un-rounded sums s with the taps and sh of the 8-bit encode: U = clip(0, 1023, ((eU . s + 2^(13 + sh)) >> (14 + sh))
+ *   + 512), V with eV.
+ * Any geometry and pointer alignment of the frame is accepted; the fp32 pointer must be 4-byte aligned.  8-byte Y accesses, dword
+ * chroma pairs and 16-byte plane accesses are used when the frame pointer is 4-byte and the fp32 pointer 16-byte aligned and W, Wp,
+ * pad_left (and x0, w) are multiples of 4.  Both paths give the same bits.  Every output byte and word is written by the call; no
+ * atomics, nothing pre-zeroed.  All checks run on the host before the launch (ATMVFI_EINVAL). */
+int atmvfi_yuv420p10_to_f32(const void* yuv, int H, int W, int matrix, int siting, int y0, int x0, int h, int w, float* dst, int Hp, int Wp,
+                            int pad_top, int pad_left, void* stream);
+int atmvfi_f32_to_yuv420p10(const float* src, int Hp, int Wp, int pad_top, int pad_left, int H, int W, int matrix, int siting, void* yuv,
+                            void* stream);
+
 /* mean |a - b| per sample: global_alignmentness (network_base.py:560-561).  Two passes with a fixed summation order -- the result is
  * run-to-run bit-identical (the ensemble's pick compares these means) -- through `workspace`: at least
  * atmvfi_l1_mean_workspace_floats(B, per_sample) floats of scratch, the caller's. */

@@ -1,0 +1,149 @@
+#!/usr/bin/env python3
+"""Time the depth-keeping 10-bit YUV kernels (atm-vfi_amd/csrc/yuv10.hip: atmvfi_yuv420p10_to_f32, atmvfi_f32_to_yuv420p10) beside
+the calls they stand next to, on the protocol of tools/bench_yuv.py: device events around ``--iters`` back-to-back calls after 24
+warm-up calls, the calls rotating over ``--buffers`` distinct sources and destinations, every configuration timed ``--repeats`` times
+in rotation in one process (median, min - max).  Bytes are the algorithm's -- inputs read once, outputs written once -- as a share of
+6.3 TB/s.  Sizes 1080 x 1920 and 2160 x 4096, each into / out of the canvas padded to a multiple of 64 as the loops use it.
+
+The neighbours: ``yuv420_to_rgb 10 bit -> fp32`` for the decode (both move 3 B/px in and 12 B/px out) and ``rgb_to_yuv420 from fp32``
+for the encode (12 B/px in; 1.5 B/px out against the new call's 3).  The project's convention for these kernels: a call takes at most
+its neighbour's time plus 15 %; the last column says whether it does.
+
+``--pipeline N``: ``FramePipeline`` on N 1080p pairs of 10-bit input (network_base, synthetic weights) with ``keep_depth`` off and on,
+interleaved.
+
+    python tools/bench_yuv10.py [--iters 240] [--repeats 5] [--buffers 12] [--pipeline 0] [--json OUT]"""
+import argparse
+import importlib
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+hip_ops = importlib.import_module("atm-vfi_amd.hip_ops")
+host_io = importlib.import_module("atm-vfi_amd.host_io")
+yuv = importlib.import_module("atm-vfi_amd.yuv")
+HBM = 6.3e12
+SIZES = [(1080, 1920), (2160, 4096)]
+BOUND = 1.15
+
+
+def timed(fn, iters):
+    """us per call of fn(i), i = 0 .. iters-1 back to back."""
+    for i in range(24):
+        fn(i)
+    torch.cuda.synchronize()
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    for i in range(iters):
+        fn(i)
+    e.record()
+    e.synchronize()
+    return s.elapsed_time(e) * 1e3 / iters
+
+
+def configs(ops, dev, H, W, n):
+    pad = host_io.InputPadder((1, 3, H, W), divisor=64)
+    pl, pr, pt, pb = pad._pad
+    Hp, Wp = H + pt + pb, W + pl + pr
+    gen = torch.Generator(device=dev).manual_seed(H)
+    f8, f10 = yuv.Format(H, W), yuv.Format(H, W, depth=10)
+    y10 = [torch.randint(0, 1024, (f10.frame_samples,), dtype=torch.int16, device=dev, generator=gen).view(torch.uint8) for _ in range(n)]
+    f32 = [torch.rand(3, Hp, Wp, dtype=torch.float32, device=dev, generator=gen) for _ in range(n)]
+    o8 = [torch.empty(f8.frame_bytes, dtype=torch.uint8, device=dev) for _ in range(n)]
+    o10 = [torch.empty(f10.frame_bytes, dtype=torch.uint8, device=dev) for _ in range(n)]
+    px, can = float(H * W), 12.0 * Hp * Wp
+    # name -> (call, bytes of the algorithm, neighbour's name or None)
+    return {
+        "yuv420_to_rgb 10 bit -> fp32 (neighbour)": (lambda i: ops.yuv420_to_rgb(y10[i % n], f10, dst=f32[i % n], pad_top=pt, pad_left=pl),
+                                                     3 * px + can, None),
+        "yuv420p10_to_f32": (lambda i: ops.yuv420p10_to_f32(y10[i % n], f10, f32[i % n], pad_top=pt, pad_left=pl), 3 * px + can,
+                             "yuv420_to_rgb 10 bit -> fp32 (neighbour)"),
+        "rgb_to_yuv420 from fp32 (neighbour)": (lambda i: ops.rgb_to_yuv420(o8[i % n], f8, src=f32[i % n], pad_top=pt, pad_left=pl), 13.5 * px, None),
+        "f32_to_yuv420p10": (lambda i: ops.f32_to_yuv420p10(o10[i % n], f10, f32[i % n], pad_top=pt, pad_left=pl), 15 * px,
+                             "rgb_to_yuv420 from fp32 (neighbour)"),
+    }
+
+
+def pipeline(dev, pairs_n, repeats):
+    pkg = importlib.import_module("atm-vfi_amd")
+    H, W = 1080, 1920
+    net = pkg.NetworkBase()
+    net.load_state_dict(pkg.synthetic_state_dict("base", seed=1), strict=True)
+    net = net.to(dev).eval()
+    fmt = yuv.Format(H, W, depth=10)
+    rng = np.random.default_rng(0)
+    frames = [rng.integers(256, 768, fmt.frame_samples).astype(np.uint16) for _ in range(4)]
+    runs = {"keep_depth off (8-bit out)": False, "keep_depth on (10-bit out)": True}
+    pipes = {k: host_io.FramePipeline(net, H, W, pixfmt=fmt, keep_depth=v) for k, v in runs.items()}
+    times = {k: [] for k in runs}
+    for r in range(repeats + 1):             # interleaved; the first round warms up (workspace, launch plan)
+        for k in runs:
+            pairs = [(frames[i % 4], frames[(i + 1) % 4]) for i in range(pairs_n)]
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in pipes[k].run(pairs):
+                pass
+            dt = time.perf_counter() - t0
+            if r:
+                times[k].append(1e3 * dt / pairs_n)
+    rows = []
+    for k, t in times.items():
+        med = statistics.median(t)
+        rows.append({"name": "FramePipeline 1080p 10-bit I420, " + k, "ms_per_pair_median": med, "ms_min": min(t), "ms_max": max(t), "pairs": pairs_n})
+        print(f"FramePipeline 1080p network_base, 10-bit I420, {k:>28}: {med:7.2f} ms/pair (min {min(t):.2f}, max {max(t):.2f} over {len(t)} "
+              f"runs of {pairs_n} pairs)  {1e3 / med:6.2f} frames/s", flush=True)
+    return rows
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--iters", type=int, default=240)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--buffers", type=int, default=12)
+    ap.add_argument("--pipeline", type=int, default=0, help="pairs per FramePipeline run (0: skip)")
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("bench_yuv10: no GPU")
+    dev = torch.device("cuda:0")
+    torch.set_grad_enabled(False)
+    ops = hip_ops.HipOps(dev)
+    n = max(1, a.buffers)
+    rows = []
+    for H, W in SIZES:
+        cfg = configs(ops, dev, H, W, n)
+        times = {k: [] for k in cfg}
+        for _ in range(a.repeats):           # in rotation: every repeat visits every configuration once
+            for k, (fn, _, _) in cfg.items():
+                times[k].append(timed(fn, a.iters))
+        med = {k: statistics.median(t) for k, t in times.items()}
+        print(f"--- {H} x {W}", flush=True)
+        for k, (_, nbytes, ref) in cfg.items():
+            t = times[k]
+            row = {"size": [H, W], "name": k, "us_median": med[k], "us_min": min(t), "us_max": max(t), "bytes": nbytes,
+                   "GBps": nbytes / (med[k] * 1e-6) / 1e9, "share_of_hbm": nbytes / (med[k] * 1e-6) / HBM,
+                   "over_neighbour": med[k] / med[ref] if ref else None, "repeats_us": t}
+            rows.append(row)
+            rel = ""
+            if ref:
+                rel = f"  {row['over_neighbour']:5.2f} x its neighbour: {'meets' if row['over_neighbour'] <= BOUND else 'MISSES'} the +15 % bound"
+            print(f"{k:>42}: {med[k]:8.2f} us (min {min(t):.2f}, max {max(t):.2f} over {len(t)} repeats)  {nbytes / 1e6:6.1f} MB  "
+                  f"{row['GBps']:7.1f} GB/s  {100 * row['share_of_hbm']:5.1f}% of 6.3 TB/s{rel}", flush=True)
+        del cfg
+        torch.cuda.empty_cache()
+    if a.pipeline > 0:
+        rows += pipeline(dev, a.pipeline, 3)
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump({"device": torch.cuda.get_device_name(0), "iters": a.iters, "repeats": a.repeats, "buffers": n, "rows": rows}, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()

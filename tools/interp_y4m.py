@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """Y4M in, Y4M out at ``factor`` times the frame rate (``atm-vfi_amd.yuv.interpolate_y4m``): frames travel as planar 4:2:0 and are
 converted on the GPU; originals are written as read.  Reads C420 / C420jpeg / C420mpeg2 / C420p10 progressive streams; 10-bit input
-is written back as 8-bit.  ``-`` reads standard input / writes standard output (``ffmpeg -i in.mp4 -f yuv4mpegpipe - | interp_y4m.py
+is written back as 8-bit, or with ``--keep-depth`` as C420p10 (originals byte for byte, predictions encoded at 10 bits).  ``-`` reads standard input / writes standard output (``ffmpeg -i in.mp4 -f yuv4mpegpipe - | interp_y4m.py
 - out.y4m --ckpt ...``).
 
-    python tools/interp_y4m.py IN.y4m OUT.y4m --ckpt CKPT [--model base|lite] [--factor 2|4|8] [--scene] [--tta] [--global-off]"""
+    python tools/interp_y4m.py IN.y4m OUT.y4m --ckpt CKPT [--model base|lite] [--factor 2|4|8] [--scene] [--tta] [--global-off]
+                              [--keep-depth]"""
 import argparse
 import importlib
 import os
@@ -27,6 +28,7 @@ def main():
     ap.add_argument("--tta", action="store_true", help="flip test-time augmentation of every produced frame")
     ap.add_argument("--global-off", action="store_true", help="switch the global motion branch off")
     ap.add_argument("--matrix", choices=("auto", "bt601", "bt709"), default="auto", help="a Y4M header cannot name the matrix")
+    ap.add_argument("--keep-depth", action="store_true", help="write 10-bit (C420p10) input back as C420p10 instead of 8-bit")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("interp_y4m: no GPU")
@@ -43,7 +45,8 @@ def main():
     net.global_motion = not a.global_off
     src = sys.stdin.buffer if a.src == "-" else a.src
     dst = sys.stdout.buffer if a.dst == "-" else a.dst
-    info = yuv.interpolate_y4m(src, dst, net, factor=a.factor, scene=yuv.SceneCuts() if a.scene else None, tta=a.tta, matrix=a.matrix)
+    info = yuv.interpolate_y4m(src, dst, net, factor=a.factor, scene=yuv.SceneCuts() if a.scene else None, tta=a.tta, matrix=a.matrix,
+                               keep_depth=a.keep_depth)
     print({k: (str(v) if k.startswith("fps") else v) for k, v in info.items()}, file=sys.stderr)
 
 
