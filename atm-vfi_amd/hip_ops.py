@@ -135,6 +135,8 @@ SIGNATURES = {
     "atmvfi_frame_rot180": (c_i, [c_f, c_f, c_i, c_i, c_i, c_f]),
     "atmvfi_frame_signature_workspace_ints": (c_l, [c_i, c_i]),
     "atmvfi_frame_signature": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_l, c_f]),
+    "atmvfi_frame_difference_workspace_ints": (c_l, [c_i, c_i]),
+    "atmvfi_frame_difference": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_l, c_f]),
     "atmvfi_yuv420_to_rgb": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_f, c_i, c_i, c_i, c_i, c_f]),
     "atmvfi_rgb_to_yuv420": (c_i, [c_f, c_i, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f]),
     "atmvfi_yuv420p10_to_f32": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f]),
@@ -1263,6 +1265,44 @@ class HipOps:
             raise ValueError("frame_signature: workspace must be a contiguous CUDA int32 tensor")
         self._check(self.lib.atmvfi_frame_signature(_ptr(src_u8), sh, sw, int(bool(bgr)), int(y0), int(x0), h, w, _ptr(out), _ptr(workspace),
                                                     workspace.numel(), self._stream()), "frame_signature")
+        return out
+
+    def frame_difference_workspace(self, h: int, w: int):
+        """A fresh int32 scratch tensor for ``frame_difference`` on an h x w window (one per stream that computes differences)."""
+        n = self.lib.atmvfi_frame_difference_workspace_ints(int(h), int(w))
+        if n < 0:
+            raise ValueError(f"frame_difference: {self.lib.atmvfi_last_error().decode()}")
+        return torch.empty(n, dtype=torch.int32, device=self.device)
+
+    def frame_difference(self, a, b, y0: int = 0, x0: int = 0, h: Optional[int] = None, w: Optional[int] = None, bgr: bool = True,
+                         out=None, workspace=None):
+        """The luma difference of the h x w window at (y0, x0) (default: the whole frame) of two resident uint8 [H,W,3] frames of one
+        size: int32 [258] on the device = 16 x 16 cell sums of |Ya - Yb|, the peak, the number of differing pixels (include/atmvfi.h
+        atmvfi_frame_difference; the bits of ``retime.difference_numpy``).  ``out`` is written completely (a new tensor when None).
+        ``workspace``: the call's scratch (``frame_difference_workspace``); None: one kept per (window size, stream) by this object.
+        Not part of a forward: never recorded into a launch plan."""
+        for t in (a, b):
+            if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3 or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError("frame_difference: sources must be contiguous CUDA uint8 [H,W,3] tensors")
+        if a.shape != b.shape or a.device != b.device:
+            raise ValueError(f"frame_difference: two frames of one size on one device expected, got {tuple(a.shape)} and {tuple(b.shape)}")
+        sh, sw = a.shape[:2]
+        h = sh - int(y0) if h is None else int(h)
+        w = sw - int(x0) if w is None else int(w)
+        if out is None:
+            out = torch.empty(258, dtype=torch.int32, device=a.device)
+        elif out.dtype != torch.int32 or out.numel() != 258 or not out.is_contiguous() or not out.is_cuda:
+            raise ValueError("frame_difference: out must be a contiguous CUDA int32 tensor of 258 words")
+        if workspace is None:
+            cache = self.__dict__.setdefault("_difference_workspaces", {})
+            key = (h, w, torch.cuda.current_stream(self.device).cuda_stream)
+            workspace = cache.get(key)
+            if workspace is None:
+                workspace = cache[key] = self.frame_difference_workspace(h, w)
+        elif workspace.dtype != torch.int32 or not workspace.is_contiguous() or not workspace.is_cuda:
+            raise ValueError("frame_difference: workspace must be a contiguous CUDA int32 tensor")
+        self._check(self.lib.atmvfi_frame_difference(_ptr(a), _ptr(b), sh, sw, int(bool(bgr)), int(y0), int(x0), h, w, _ptr(out),
+                                                     _ptr(workspace), workspace.numel(), self._stream()), "frame_difference")
         return out
 
     def yuv420_to_rgb(self, yuv, fmt, dst_u8=None, dst=None, pad_top: int = 0, pad_left: int = 0, bgr: bool = False):

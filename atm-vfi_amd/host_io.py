@@ -691,5 +691,6 @@ def load_model_checkpoint(model, checkpoint_path, strict: bool = True, map_locat
 from .multiframe import (FramePool, inference_nx, interpolate_video_nx, nx_levels, nx_sequence, video_nx)  # noqa: E402,F401
 # scene-cut detection for the video loops above (not in the reference): atm-vfi_amd/scene.py
 from .scene import SceneCuts, cut_statistics, signature_numpy  # noqa: E402,F401
+from .retime import Duplicates, difference_numpy, interpolate_video_retimed, retime_slots, sparse_levels, video_retimed  # noqa: E402,F401
 # planar YUV 4:2:0 frames for the loops above (``pixfmt=``) and Y4M files (not in the reference): atm-vfi_amd/yuv.py
 from .yuv import Format as YuvFormat, Y4MReader, Y4MWriter, interpolate_y4m  # noqa: E402,F401

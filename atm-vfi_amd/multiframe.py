@@ -147,14 +147,21 @@ class _Uploader:
     copy stream behind the copy and fills the slot's resident uint8 RGB frame ``d`` -- what the signature, ``take`` and everything
     downstream read, as for an RGB upload.  ``deep`` (a 10-bit ``pixfmt`` with ``keep_depth``): ``take`` hands the uploaded I420 bytes
     themselves to ``convert`` (``atmvfi_yuv420p10_to_f32`` decodes them into the pool slot: no 8-bit round trip); the uint8 RGB frame is
-    made only for a signature."""
+    made only for a signature (or a difference).
 
-    def __init__(self, dev, height: int, width: int, depth: int = 3, signature=None, pixfmt=None, deep: bool = False):
+    ``difference=(ops, (y0, x0, h, w), bgr)`` (duplicate detection of ``retime.interpolate_video_retimed``): behind every upload but the
+    first, ``HipOps.frame_difference`` of the PREVIOUS upload's resident uint8 frame and this one runs on the copy stream and its 1 032
+    bytes follow into a pinned word array of the slot (``difference(slot)``).  Lifetimes: the previous upload's device frame is read on
+    the copy stream, and the copy that next overwrites it is issued on that same stream later: stream order.  A frame that is never
+    ``take``n (a dropped duplicate) records no ``free`` event, so with ``difference`` a slot's reuse also waits for its own ``ready``
+    event: its pinned bytes have left the host before they are overwritten."""
+
+    def __init__(self, dev, height: int, width: int, depth: int = 3, signature=None, pixfmt=None, deep: bool = False, difference=None):
         import torch
         self.torch, self.dev, self.h, self.w, self.depth = torch, dev, height, width, depth
-        self.sig, self.pixfmt, self.deep = signature, pixfmt, bool(deep)
+        self.sig, self.pixfmt, self.deep, self.dif = signature, pixfmt, bool(deep), difference
         in_shape = (height, width, 3) if pixfmt is None else (pixfmt[1].frame_bytes,)
-        need_rgb = not self.deep or signature is not None
+        need_rgb = not self.deep or signature is not None or difference is not None
         self.ring = [{"h": torch.empty(*in_shape, dtype=torch.uint8).pin_memory(),
                       "d": torch.empty(height, width, 3, dtype=torch.uint8, device=dev) if need_rgb else None,
                       "ready": torch.cuda.Event(), "free": torch.cuda.Event()} for _ in range(depth)]
@@ -168,6 +175,13 @@ class _Uploader:
                 s["sig_h_np"], s["sig_ready"] = s["sig_h"].numpy(), torch.cuda.Event()
         if signature is not None:                     # one scratch: every signature runs on the copy stream, one after the other
             self.sig_ws = signature[0].frame_signature_workspace(*signature[1][2:])
+        if difference is not None:
+            for s in self.ring:
+                s["dif_d"] = torch.empty(258, dtype=torch.int32, device=dev)
+                s["dif_h"] = torch.empty(258, dtype=torch.int32).pin_memory()
+                s["dif_h_np"], s["dif_ready"] = s["dif_h"].numpy(), torch.cuda.Event()
+            self.dif_ws = difference[0].frame_difference_workspace(*difference[1][2:])
+            self.prev = None                          # the slot of the previous upload
         self.copy_in = torch.cuda.Stream(dev)
         self.issued = 0
 
@@ -181,6 +195,8 @@ class _Uploader:
         slot = self.ring[self.issued % self.depth]
         if self.issued >= self.depth:
             slot["free"].synchronize()                # the kernel that read this slot's device copy has run
+            if self.dif is not None:
+                slot["ready"].synchronize()           # a frame that was never taken: its copy has left the pinned bytes
         np.copyto(slot["h_np"], frame)                # numpy's single-threaded memcpy (see host_io.FramePipeline._upload)
         with torch.cuda.stream(self.copy_in):
             if self.pixfmt is None:
@@ -195,6 +211,13 @@ class _Uploader:
                 ops.frame_signature(slot["d"], y0, x0, h, w, bgr=bgr, out=slot["sig_d"], workspace=self.sig_ws)
                 slot["sig_h"].copy_(slot["sig_d"], non_blocking=True)
                 slot["sig_ready"].record(self.copy_in)
+            if self.dif is not None:
+                if self.prev is not None:
+                    ops, (y0, x0, h, w), bgr = self.dif
+                    ops.frame_difference(self.prev["d"], slot["d"], y0, x0, h, w, bgr=bgr, out=slot["dif_d"], workspace=self.dif_ws)
+                    slot["dif_h"].copy_(slot["dif_d"], non_blocking=True)
+                    slot["dif_ready"].record(self.copy_in)
+                self.prev = slot
         self.issued += 1
         return slot
 
@@ -202,6 +225,11 @@ class _Uploader:
         """The int32[288] signature of the frame in ``slot`` (a copy; the slot's words are rewritten by its next upload)."""
         slot["sig_ready"].synchronize()
         return slot["sig_h_np"].copy()
+
+    def difference(self, slot) -> np.ndarray:
+        """The int32[258] difference of the frame in ``slot`` against the upload before it (a copy; not defined for the first upload)."""
+        slot["dif_ready"].synchronize()
+        return slot["dif_h_np"].copy()
 
     def take(self, slot, convert):
         """Run ``convert(device uint8 frame)`` on the current stream once the slot's copy has landed (``deep``: the device I420 bytes)."""
@@ -218,9 +246,15 @@ class _SegmentRunner:
 
     Workspaces: batches of different size are different workspaces of the model, and its LRU of two would free and reallocate them
     per level at 8x (batch sizes 1, 2, 4).  The runner RAISES ``model.max_workspaces`` to the number of batch sizes of its schedule for
-    its lifetime and restores it in ``close()``."""
+    its lifetime and restores it in ``close()``.
 
-    def __init__(self, model, ops, dev, height, width, factor, crop, bgr, divisor, tta, max_batch, pool, out_fmt=None, deep_fmt=None):
+    ``run(..., levels=, emit=)`` (``retime.interpolate_video_retimed``): a sparse schedule (``retime.sparse_levels``) instead of the full
+    recursion, and the positions that leave for the host -- the others are ancestors only and stay in the pool.  ``out_slots``: the size
+    of the output ring (default N - 1: every position); ``batch_sizes``: the batch sizes a sparse schedule can bring (default: those of
+    the full recursion)."""
+
+    def __init__(self, model, ops, dev, height, width, factor, crop, bgr, divisor, tta, max_batch, pool, out_fmt=None, deep_fmt=None,
+                 out_slots=None, batch_sizes=None):
         import torch
         from .host_io import InputPadder
         self.torch, self.model, self.ops, self.dev = torch, model, ops, dev
@@ -248,7 +282,7 @@ class _SegmentRunner:
             self.pools = None
             self.frames = [torch.empty(S, 3, self.hp, self.wp, dtype=torch.float32, device=dev) for _ in range(2 if self.tta else 1)]
         self.phys = list(range(S))                   # schedule position -> pool slot; positions 0 and N swap slots per segment
-        self.have_first = False
+        self.have_first = self.fresh = False
         # plain mode: the pairs of a batch are gathered into contiguous [B,3,Hp,Wp] inputs
         self.gather = {}
         # out_fmt (a yuv.Format of the window's size): the produced frames leave as packed I420 (rgb_to_yuv420) instead of uint8 RGB
@@ -257,8 +291,9 @@ class _SegmentRunner:
         # is 10-bit then)
         self.out_fmt, self.deep_fmt = out_fmt, deep_fmt
         out_shape = (self.h, self.w, 3) if out_fmt is None else (out_fmt.frame_bytes,)
-        self.out_d = torch.empty(factor - 1, *out_shape, dtype=torch.uint8, device=dev)
-        self.out_h = [torch.empty(factor - 1, *out_shape, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        n_out = factor - 1 if out_slots is None else max(1, min(int(out_slots), factor - 1))
+        self.out_d = torch.empty(n_out, *out_shape, dtype=torch.uint8, device=dev)
+        self.out_h = [torch.empty(n_out, *out_shape, dtype=torch.uint8).pin_memory() for _ in range(2)]
         self.merged = None
         if out_fmt is not None and self.tta:         # the average: its uint8 pixels, or with the depth kept the fp32 canvas itself
             self.merged = (torch.empty(3, self.hp, self.wp, dtype=torch.float32, device=dev) if deep_fmt is not None else
@@ -268,6 +303,8 @@ class _SegmentRunner:
         self.copy_out = torch.cuda.Stream(dev)
         self.done = torch.cuda.Event()
         sizes = {min(self.max_batch, len(lv) - i) for lv in self.levels for i in range(0, len(lv), self.max_batch)}
+        if batch_sizes is not None:
+            sizes = set(batch_sizes)
         self._keep_max_ws = getattr(model, "max_workspaces", None)
         if self._keep_max_ws is not None and len(sizes) > self._keep_max_ws:
             model.max_workspaces = len(sizes)
@@ -300,6 +337,13 @@ class _SegmentRunner:
                     p.invalidate(slot)
         return convert
 
+    def first(self, up: _Uploader, slot):
+        """Convert the stream's first frame into position 0 NOW, ahead of the first ``run`` (which then gets ``slot_a=None``): a loop
+        that may read many frames before its first segment is known (dropped duplicates) must not leave frame 0 in the upload ring."""
+        with self.torch.cuda.device(self.dev):
+            up.take(slot, self._convert_into(0))
+        self.have_first = self.fresh = True
+
     def _forward(self, k, lefts, rights):
         """I_t [B,3,Hp,Wp] of the pairs (slots) on frame set ``k`` (0: the frames, 1: their 180-degree rotations)."""
         if self.use_pool:
@@ -311,14 +355,22 @@ class _SegmentRunner:
         self.ops.pool_blocks(self.frames[k], lefts + rights, g)
         return self.model.forward(g[:b], g[b:])["I_t"]
 
-    def run(self, up: _Uploader, slot_a, slot_b, cut: bool = False):
+    def run(self, up: _Uploader, slot_a, slot_b, cut: bool = False, levels=None, emit=None):
         """Enqueue one segment: ``slot_a`` (None when the previous segment's second frame is this one's first) and ``slot_b`` are
         upload slots.  Returns a handle for ``result``.  ``cut`` (a scene cut: the caller emits copies of the originals): the source
         frames still take their places -- position N's frame, with tokens marked stale, is the next segment's position 0 whatever this
-        segment was -- but no forward runs, nothing is written to the middle slots or the output ring, and None is returned."""
+        segment was -- but no forward runs, nothing is written to the middle slots or the output ring, and None is returned.
+        ``levels`` (default: the full recursion) / ``emit`` (default: every position): the schedule to run and the positions, in the
+        order of ``result``, that are written to the output ring; ``emit`` holds at most ``out_slots`` positions, all in ``levels``."""
         torch, n = self.torch, self.n
+        levels = self.levels if levels is None else levels
+        index = None if emit is None else {pos: k for k, pos in enumerate(emit)}       # position -> output ring entry
+        if index is not None and (len(index) > self.out_d.shape[0] or not index.keys() <= {o for lv in levels for _, _, o in lv}):
+            raise ValueError(f"_SegmentRunner.run: emit {list(emit)} does not fit the schedule or the {self.out_d.shape[0]} output slots")
         with torch.cuda.device(self.dev):
-            if self.have_first:
+            if self.fresh:                           # position 0 holds the stream's first frame already (``first``)
+                self.fresh = False
+            elif self.have_first:
                 self.phys[0], self.phys[n] = self.phys[n], self.phys[0]      # frame AND tokens of slot N become slot 0's: no copy
             else:
                 up.take(slot_a, self._convert_into(0))
@@ -328,17 +380,20 @@ class _SegmentRunner:
                 return None
             ring = self.seg & 1
             self.seg += 1
-            last = len(self.levels) - 1
-            for li, level in enumerate(self.levels):
+            last = max((li for li, lv in enumerate(levels) if lv), default=0)
+            for li, level in enumerate(levels):
                 for i in range(0, len(level), self.max_batch):
                     chunk = level[i:i + self.max_batch]
                     lefts = [self.phys[a] for a, _, _ in chunk]
                     rights = [self.phys[b] for _, b, _ in chunk]
                     outs = [self.phys[o] for _, _, o in chunk]
                     pred = self._forward(0, lefts, rights)
-                    flip = self._forward(1, lefts, rights) if self.tta else None
+                    shown = [index is None or pos in index for _, _, pos in chunk]
+                    flip = self._forward(1, lefts, rights) if self.tta and any(shown) else None
                     for j, (_, _, pos) in enumerate(chunk):
-                        u8 = self.out_d[pos - 1]
+                        if not shown[j]:               # an ancestor only: it stays in the pool
+                            continue
+                        u8 = self.out_d[pos - 1 if index is None else index[pos]]
                         if self.deep_fmt is not None:
                             src = pred[j]
                             if self.tta:               # the fp32 average, then its encoding
@@ -372,18 +427,23 @@ class _SegmentRunner:
             self.done.record(cur)
             self.copy_out.wait_event(self.done)
             with torch.cuda.stream(self.copy_out):
-                self.out_h[ring].copy_(self.out_d, non_blocking=True)
+                if index is None:
+                    self.out_h[ring].copy_(self.out_d, non_blocking=True)
+                else:
+                    self.out_h[ring][:len(index)].copy_(self.out_d[:len(index)], non_blocking=True)
                 self.out_evt[ring].record(self.copy_out)
             # out_d is rewritten by the next segment: its kernels wait for this copy
             cur.wait_event(self.out_evt[ring])
             return ring
 
-    def result(self, ring) -> List[np.ndarray]:
+    def result(self, ring, count: Optional[int] = None) -> List[np.ndarray]:
+        """The frames of a ``run``: all N - 1, or the first ``count`` output ring entries (a run with ``emit``)."""
         self.out_evt[ring].synchronize()
         arr = self.out_h[ring].numpy()
+        count = self.n - 1 if count is None else count
         if self.deep_fmt is not None:
-            return [arr[k].copy().view(np.uint16) for k in range(self.n - 1)]
-        return [arr[k].copy() for k in range(self.n - 1)]
+            return [arr[k].copy().view(np.uint16) for k in range(count)]
+        return [arr[k].copy() for k in range(count)]
 
 
 def _generic_segment(model, factor, crop_of, isBGR, divisor, tta, max_batch, load=None, store=None):
@@ -403,7 +463,8 @@ def _generic_segment(model, factor, crop_of, isBGR, divisor, tta, max_batch, loa
             img = img[:, :, ::-1]
         return (torch.tensor(np.ascontiguousarray(img.transpose(2, 0, 1))).to(dev) / 255.).unsqueeze(0)
 
-    def segment(fa, fb):
+    def segment(fa, fb, levels=levels, emit=None):
+        """``levels`` / ``emit`` (``retime.interpolate_video_retimed``): a sparse schedule and the positions to return, in order."""
         a, b = to_t(fa), to_t(fb)
         padder = InputPadder(a.shape, divisor=divisor) if divisor else None
         if padder:
@@ -424,7 +485,7 @@ def _generic_segment(model, factor, crop_of, isBGR, divisor, tta, max_batch, loa
                     fr[pos] = pred[j:j + 1]
                     shown[pos] = out[j:j + 1]
         res = []
-        for pos in range(1, factor):
+        for pos in (range(1, factor) if emit is None else emit):
             p = shown[pos]
             if padder:
                 p = padder.unpad(p)

@@ -1,0 +1,500 @@
+"""Frame-rate conversion to any output rate (24 -> 60, 25 -> 50 / 60, 30000/1001 -> 60, 24 -> 120, also downwards), with optional
+dropping of repeated frames.  Nothing here exists in the reference: its scripts multiply the rate by 2, 4 or 8.
+
+The network predicts the midpoint of two frames only, so every produced frame sits on a DYADIC position of a segment of the source:
+
+* source frame ``i`` is at time ``i / fps_in``; ``kept = [0 = k_0 < k_1 < ...]`` are the frames that survive duplicate dropping (all of
+  them without ``dedup``); segment ``j`` spans ``kept[j] ... kept[j + 1]``, ``g_j = kept[j + 1] - kept[j]`` source periods;
+* output ``m`` is at ``T_m = m / fps_out`` for every ``m >= 0`` with ``T_m <= kept[-1] / fps_in``; with ``u = T_m fps_in`` it lies in the
+  segment with ``kept[j] <= u < kept[j + 1]`` (the one output with ``u == kept[-1]`` is position N of the last segment) at
+  ``tau = (u - kept[j]) / g_j``, and is shown as position ``p = floor(tau N + 1/2)`` of ``N = 2**levels`` (half up): ``p == 0`` and
+  ``p == N`` are the originals themselves, any other ``p`` the interpolated frame at ``p / N``.  The timing error is at most
+  ``g_j / (2 N)`` source periods.  All of this is ``fractions.Fraction`` / integer arithmetic: no float decides a position
+  (``retime_slots``);
+* only the nodes of the recursion tree that those positions need are evaluated (``sparse_levels``: the ancestor closure): 2.0 forwards
+  per interpolated frame at 24 -> 60 with 3 levels, against 7 per segment for the full 8x recursion.
+
+Duplicates (``Duplicates``, ``dedup=``): animation on twos or threes, 24p carried in 30p.  Interpolating between two copies of a picture
+and then jumping is the judder a rate conversion is meant to remove; dropping the copy only widens a segment.  A histogram-and-cell-sum
+signature (scene.py) cannot see a repeated frame; the per-pixel comparison of two resident frames is ``atmvfi_frame_difference``
+(csrc/framediff.hip; ``difference_numpy`` here gives the same bits): int32[258] = the 16 x 16 cell sums of ``|Ya - Yb|``, the peak, the
+number of differing pixels, of the signature's luma and cells.  ``d_cell`` = the largest per-pixel cell SAD, ``d_peak`` = the peak; frame
+``i`` is a duplicate of source frame ``i - 1`` iff ``d_cell <= cell`` and ``d_peak <= peak``.
+
+``interpolate_video_retimed`` / ``video_retimed``: the loop and its adapter (re-exported from ``host_io`` and ``yuv``)."""
+from __future__ import annotations
+
+import itertools
+import math
+from fractions import Fraction
+from typing import Iterable, Iterator, List, Optional, Tuple
+
+import numpy as np
+
+from .multiframe import _SegmentRunner, _Uploader, _chain, _generic_segment, centre_window
+from .scene import _bounds
+
+DIFF_WORDS = 258
+MAX_LEVELS = 6
+# The defaults, placed from the statistics of tests/golden/dedup_ref.npz (README "Frame-rate conversion"; tests/test_retime_cpu.py asserts
+# the margins): the duplicate set (every picture against its JPEG q95 / q90 re-encodes and against itself plus uniform noise of +-1, +-2,
+# +-3) reaches d_cell 2.99 and d_peak 16; the motion set (128-pixel windows panned by ONE pixel) starts at d_cell 29.27 and d_peak 110.
+# Each threshold keeps 1.5 x to both sides: cell in [4.5, 19.5], peak in [24, 73].  No labelled footage was available: the defaults are
+# unvalidated on real video.
+DEFAULT_CELL = 9.0
+DEFAULT_PEAK = 40
+
+
+# ------------------------------------------------------------------------------------------------ timeline (no device)
+def as_rate(value, name: str = "rate") -> Fraction:
+    """A frame rate as an exact ``Fraction``: an int, a ``Fraction``, a string such as ``"60000/1001"`` or ``"59.94"`` (read as the
+    decimal it spells), or a float that is a whole number.  Other floats are refused: no float decides a position."""
+    if isinstance(value, bool):
+        raise ValueError(f"{name}: a frame rate expected, got {value!r}")
+    if isinstance(value, float):
+        if not value.is_integer():
+            raise ValueError(f"{name}: {value!r} is not exact; pass a Fraction or a string such as '60000/1001'")
+        value = int(value)
+    try:
+        rate = Fraction(value)
+    except (TypeError, ValueError, ZeroDivisionError):
+        raise ValueError(f"{name}: a frame rate expected, got {value!r}") from None
+    if rate <= 0:
+        raise ValueError(f"{name} must be positive, got {value!r}")
+    return rate
+
+
+def _check_rates(fps_in, fps_out, levels) -> Tuple[Fraction, Fraction, int]:
+    fi, fo = as_rate(fps_in, "fps_in"), as_rate(fps_out, "fps_out")
+    if not isinstance(levels, int) or isinstance(levels, bool) or not 1 <= levels <= MAX_LEVELS:
+        raise ValueError(f"levels must be in 1..{MAX_LEVELS}, got {levels!r}")
+    if (1 << levels) * fi < fo:
+        raise ValueError(f"{levels} levels place {1 << levels} positions per source period: too few for {fi} -> {fo} fps "
+                         "(a span-1 segment would repeat a position)")
+    return fi, fo, levels
+
+
+def _retime_segments(kept: Iterable[int], fi: Fraction, fo: Fraction, levels: int) -> Iterator[Tuple[int, List[int]]]:
+    """``(j, [p, ...])`` for EVERY segment j, in order, as soon as ``kept[j + 1]`` is known (a segment without outputs: an empty
+    list); after the last segment the one output at ``kept[-1]`` as ``(j_last, [N])`` -- ``(0, [0])`` for a one-frame stream."""
+    n = 1 << levels
+    step = fi / fo                                   # source periods per output
+    it = iter(kept)
+    lo = next(it, None)
+    if lo is None:
+        return
+    if lo != 0:
+        raise ValueError(f"kept must start with frame 0, got {lo!r}")
+    m, j = 0, -1
+    for hi in it:
+        if not isinstance(hi, (int, np.integer)) or hi <= lo:
+            raise ValueError(f"kept must be strictly increasing integers, got {hi!r} after {lo!r}")
+        j += 1
+        ps = []
+        while m * step < hi:                         # kept[j] <= u < kept[j + 1]
+            ps.append(math.floor((m * step - lo) / (hi - lo) * n + Fraction(1, 2)))
+            m += 1
+        yield j, ps
+        lo = int(hi)
+    if m * step == lo:                               # u == kept[-1]
+        yield (j, [n]) if j >= 0 else (0, [0])
+
+
+def retime_slots(kept: Iterable[int], fps_in, fps_out, levels: int) -> Iterator[Tuple[int, int]]:
+    """The outputs of a rate conversion in time order, as ``(j, p)`` = (segment, position 0..N of it), N = ``2**levels`` (the module's
+    docstring has the definition).  ``kept``: any iterable of the kept source frame indices, ``0 = k_0 < k_1 < ...``; an output is yielded
+    as soon as ``kept[j + 1]`` has been read, so a loop over it streams.  ``ValueError`` for a rate <= 0, ``levels`` outside 1..6, or
+    ``2**levels fps_in < fps_out``.  ``fps_out < fps_in`` is allowed: segments without an output simply yield nothing."""
+    fi, fo, levels = _check_rates(fps_in, fps_out, levels)
+    return ((j, p) for j, ps in _retime_segments(kept, fi, fo, levels) for p in ps)
+
+
+def sparse_levels(positions: Iterable[int], levels: int) -> List[List[Tuple[int, int, int]]]:
+    """The part of the N-x recursion (N = ``2**levels``) that ``positions`` (each in 0..N; 0 and N are the source frames and need
+    nothing) depend on -- their ancestor closure -- in ``multiframe.nx_levels``' form: ``levels`` lists of (left, right, out), sorted by
+    ``out``, some possibly empty.  Node ``p = odd * 2**s`` has the parents ``p - 2**s`` and ``p + 2**s`` and belongs to level
+    ``levels - s``.  ``sparse_levels(range(1, N), L) == nx_levels(N)``."""
+    if not isinstance(levels, int) or isinstance(levels, bool) or not 1 <= levels <= MAX_LEVELS:
+        raise ValueError(f"levels must be in 1..{MAX_LEVELS}, got {levels!r}")
+    n = 1 << levels
+    need, todo = set(), []
+    for p in positions:
+        if not isinstance(p, (int, np.integer)) or isinstance(p, bool) or not 0 <= p <= n:
+            raise ValueError(f"positions must be integers in 0..{n}, got {p!r}")
+        todo.append(int(p))
+    while todo:
+        p = todo.pop()
+        if p in need or p == 0 or p == n:
+            continue
+        need.add(p)
+        half = p & -p                                # 2**s
+        todo += [p - half, p + half]
+    out: List[List[Tuple[int, int, int]]] = [[] for _ in range(levels)]
+    for p in sorted(need):
+        half = p & -p
+        out[levels - half.bit_length()].append((p - half, p + half, p))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ duplicates
+def difference_numpy(a: np.ndarray, b: np.ndarray, window: Optional[Tuple[int, int, int, int]] = None, bgr: bool = True) -> np.ndarray:
+    """int32[258] difference of the ``window`` = (y0, x0, h, w) (default: the whole frame) of two uint8 [H,W,3] frames on the host: what
+    ``atmvfi_frame_difference`` computes on the device, bit for bit."""
+    a, b = np.asarray(a), np.asarray(b)
+    for f in (a, b):
+        if f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3:
+            raise ValueError(f"difference_numpy: uint8 [H,W,3] frames expected, got {f.dtype} {tuple(f.shape)}")
+    if a.shape != b.shape:
+        raise ValueError(f"difference_numpy: two frames of one size expected, got {tuple(a.shape)} and {tuple(b.shape)}")
+    H, W = a.shape[:2]
+    y0, x0, h, w = (0, 0, H, W) if window is None else (int(v) for v in window)
+    if h < 16 or w < 16:
+        raise ValueError(f"difference_numpy: the window must be at least 16 x 16 (got {h} x {w})")
+    if y0 < 0 or x0 < 0 or y0 + h > H or x0 + w > W:
+        raise ValueError(f"difference_numpy: window {h} x {w} at ({y0}, {x0}) outside the {H} x {W} frame")
+
+    def luma(f):
+        px = f[y0:y0 + h, x0:x0 + w].astype(np.int32)
+        r, bl = (px[:, :, 2], px[:, :, 0]) if bgr else (px[:, :, 0], px[:, :, 2])
+        return (77 * r + 150 * px[:, :, 1] + 29 * bl + 128) >> 8
+    d = np.abs(luma(a) - luma(b))
+    rows = np.add.reduceat(d.astype(np.int64), _bounds(h)[:16], axis=0)
+    cells = np.add.reduceat(rows, _bounds(w)[:16], axis=1)
+    if cells.max() > np.iinfo(np.int32).max or h * w > np.iinfo(np.int32).max:
+        raise ValueError(f"difference_numpy: a {h} x {w} window is too large (cell sums and the pixel count must fit int32)")
+    out = np.empty(DIFF_WORDS, np.int32)
+    out[:256] = cells.reshape(-1)
+    out[256] = d.max()
+    out[257] = np.count_nonzero(d)
+    return out
+
+
+def duplicate_statistics(diff, h: int, w: int) -> Tuple[float, int]:
+    """(d_cell, d_peak) of a difference of h x w windows: ``d_cell`` = the maximum over the 256 cells of SAD / pixels of the cell, in
+    float64 from the integers; ``d_peak`` = word 256."""
+    d = np.asarray(diff, dtype=np.int64)
+    if d.shape != (DIFF_WORDS,):
+        raise ValueError("duplicate_statistics: a difference of 258 words expected")
+    n = np.outer(np.diff(_bounds(h)), np.diff(_bounds(w))).reshape(-1).astype(np.float64)
+    return float(np.max(d[:256] / n)), int(d[256])
+
+
+class Duplicates:
+    """The duplicate policy and the record of one run.  Frame ``i >= 1`` is compared with source frame ``i - 1`` (kept or not) over the
+    crop window; it is a duplicate iff ``d_cell <= cell`` and ``d_peak <= peak``, and it is DROPPED iff it is a duplicate, fewer than
+    ``max_run`` frames were dropped immediately before it, and it is not the last frame of the stream (the last frame is always kept: a
+    frame held back as a duplicate becomes kept when the stream ends behind it).  Hand one to ``interpolate_video_retimed`` as
+    ``dedup=``; after the run ``.dropped`` holds the indices of the dropped frames and ``.stats`` one ``(d_cell, d_peak)`` per compared
+    frame (``stats[i - 1]`` is frame i's).  Both are reset at the start of each run.
+
+    The limit of the policy: a small low-contrast change -- an 8 x 8 patch moving by 40 levels -- passes both tests and is dropped, and a
+    heavily re-compressed repeat (JPEG q75 reaches 6.2 / 41, q50 9.0 / 52) is not seen as one."""
+
+    def __init__(self, cell: float = DEFAULT_CELL, peak: int = DEFAULT_PEAK, max_run: int = 3):
+        if int(max_run) < 0:
+            raise ValueError(f"max_run must be >= 0, got {max_run!r}")
+        self.cell, self.peak, self.max_run = float(cell), int(peak), int(max_run)
+        self.begin()
+
+    def begin(self):
+        """Start of a run: forget the previous one."""
+        self.dropped: List[int] = []
+        self.stats: List[Tuple[float, int]] = []
+        self._run = 0
+
+    def is_duplicate(self, d_cell: float, d_peak: int) -> bool:
+        return d_cell <= self.cell and d_peak <= self.peak
+
+    def judge(self, diff, h: int, w: int) -> bool:
+        """Record the next frame (its difference against the source frame before it, of h x w windows); True when it is dropped --
+        provisionally: ``finish`` takes the stream's last frame back."""
+        st = duplicate_statistics(diff, h, w)
+        index = len(self.stats) + 1
+        self.stats.append(st)
+        drop = self.is_duplicate(*st) and self._run < self.max_run
+        self._run = self._run + 1 if drop else 0
+        if drop:
+            self.dropped.append(index)
+        return drop
+
+    def finish(self) -> bool:
+        """End of the stream: the last frame is kept.  True when it had been held back as a duplicate."""
+        if self.dropped and self.dropped[-1] == len(self.stats):
+            self.dropped.pop()
+            self._run = 0
+            return True
+        return False
+
+    def __repr__(self):
+        return f"Duplicates(cell={self.cell}, peak={self.peak}, max_run={self.max_run})"
+
+
+# ------------------------------------------------------------------------------------------------ the loop
+class _HostBackend:
+    """A model without the HIP backend: torch / numpy (``multiframe._generic_segment`` on the sparse schedule, ``difference_numpy``,
+    ``signature_numpy``)."""
+
+    def __init__(self, model, levels, window, crop_rgb, isBGR, divisor, tta, max_batch, pixfmt, out_fmt, deep, dedup):
+        self.n, self.levels, self.win, self.bgr, self.pixfmt, self.out_fmt, self.deep = 1 << levels, levels, window, isBGR, pixfmt, out_fmt, deep
+        self.dedup, self.prev_rgb = dedup, None
+        if pixfmt is not None and deep:
+            from . import yuv
+            self.seg = _generic_segment(model, self.n, None, False, divisor, tta, max_batch,
+                                        load=lambda f: yuv.decode_numpy_f32(f, pixfmt, window=window),
+                                        store=lambda p: yuv.encode_numpy(p, out_fmt))
+        else:
+            self.seg = _generic_segment(model, self.n, crop_rgb, isBGR, divisor, tta, max_batch)
+
+    def _rgb(self, e):
+        """the uint8 [H,W,3] picture of a frame (an I420 frame: decoded once)"""
+        if self.pixfmt is None:
+            return e["f"]
+        if "rgb" not in e:
+            from . import yuv
+            e["rgb"] = yuv.decode_numpy(e["f"], self.pixfmt)
+        return e["rgb"]
+
+    def admit(self, e):
+        if self.pixfmt is not None:
+            self.pixfmt.check(e["f"], "interpolate_video_retimed")
+        if self.dedup is not None:
+            rgb = self._rgb(e)
+            if self.prev_rgb is not None:
+                e["diff"] = difference_numpy(self.prev_rgb, rgb, self.win, bgr=self.bgr)
+            self.prev_rgb = rgb
+
+    def first(self, e):
+        pass
+
+    def difference(self, e):
+        return e["diff"]
+
+    def signature(self, e):
+        from .scene import signature_numpy
+        return signature_numpy(self._rgb(e), self.win, bgr=self.bgr)
+
+    def segment(self, a, b, interior, cut):
+        if cut or not interior:
+            return {}
+        fa, fb = (a["f"], b["f"]) if (self.pixfmt is None or self.deep) else (self._rgb(a), self._rgb(b))
+        made = self.seg(fa, fb, levels=sparse_levels(interior, self.levels), emit=interior)
+        if self.pixfmt is not None and not self.deep:
+            from . import yuv
+            made = [yuv.encode_numpy(m, self.out_fmt) for m in made]
+        return dict(zip(interior, made))
+
+    def close(self):
+        pass
+
+
+class _DeviceBackend:
+    """The HIP path: ``multiframe._Uploader`` (signatures and differences on the copy stream behind each upload) and
+    ``multiframe._SegmentRunner`` on the sparse schedule.  Every KEPT frame is converted into the pool once, when its segment runs; a
+    dropped frame is uploaded and compared and never converted.
+
+    The upload ring and its lifetimes.  Frame k's upload is issued when it is read; frame k - 1 is judged -- and, if kept, its segment
+    enqueued, which ``take``s its slot -- before frame k + 1 is read.  So when upload k + 1 is issued the slots still in use are k (the
+    next difference reads its device frame; its ``take`` is yet to come) and k - 1 (its ``take`` may be in flight: the ``free`` event).
+    Three slots would do; the ring has four.  A held-back duplicate at the end of the stream is ``take``n after the last upload: nothing
+    can overwrite it.  The stream's FIRST frame is the one frame whose segment may be many uploads away (its followers may all be
+    dropped): it is converted into pool position 0, and its signature read, when it is admitted (``first``)."""
+
+    def __init__(self, model, ops, dev, H, W, levels, window, crop, isBGR, divisor, tta, max_batch, pool, pixfmt, out_fmt, deep, scene,
+                 dedup, out_slots):
+        self.levels, n = levels, 1 << levels
+        max_batch = max(1, min(int(max_batch), 16))
+        self.runner = _SegmentRunner(model, ops, dev, H, W, n, crop, isBGR, divisor, tta, max_batch, pool and hasattr(model, "forward_pooled"),
+                                     out_fmt=out_fmt, deep_fmt=pixfmt if deep else None, out_slots=out_slots,
+                                     batch_sizes=range(1, min(max_batch, max(1, n // 2)) + 1))
+        sig = (ops, window, bool(isBGR))
+        self.up = _Uploader(dev, H, W, depth=4 if dedup is not None else 3, signature=None if scene is None else sig,
+                            pixfmt=None if pixfmt is None else (ops, pixfmt), deep=deep, difference=None if dedup is None else sig)
+
+    def admit(self, e):
+        e["slot"] = self.up.upload(e["f"])
+
+    def first(self, e):
+        self.runner.first(self.up, e["slot"])
+
+    def difference(self, e):
+        return self.up.difference(e["slot"])
+
+    def signature(self, e):
+        return self.up.signature(e["slot"])
+
+    def segment(self, a, b, interior, cut):
+        if cut or not interior:                      # the frames take their places; no forward
+            self.runner.run(self.up, None, b["slot"], cut=True)
+            return {}
+        ring = self.runner.run(self.up, None, b["slot"], levels=sparse_levels(interior, self.levels), emit=interior)
+        return dict(zip(interior, self.runner.result(ring, len(interior))))
+
+    def close(self):
+        self.runner.close()
+
+
+def interpolate_video_retimed(frames, model, fps_in, fps_out, levels: int = 3, dedup: Optional[Duplicates] = None,
+                              crop: Optional[Tuple[int, int]] = None, isBGR: bool = True, divisor: Optional[int] = 64, tta: bool = False,
+                              max_batch: int = 4, pool: bool = True, scene=None, pixfmt=None, keep_depth: bool = False, report=None):
+    """Frame-rate conversion ``fps_in -> fps_out`` (ints, ``Fraction``s or strings such as ``"30000/1001"``) over any iterable of uint8
+    [H,W,3] frames: yields, in time order, output ``m`` at ``m / fps_out`` for every m up to the last kept frame's time, as the module's
+    docstring defines -- the nearest of ``N = 2**levels`` positions of its segment.  Positions 0 and N are the originals and pass through
+    as the caller's own arrays (their centre ``crop=(h, w)`` window when given), position N of a segment and position 0 of the next
+    being the same frame; every output is yielded exactly once.  Only the recursion nodes that a segment's positions need are evaluated
+    (``sparse_levels``), level by level in batches of at most ``max_batch`` pairs on ``multiframe._SegmentRunner``; a segment without an
+    interpolated output (``fps_out < fps_in`` has many) runs no forward.  When a widened segment maps two outputs to one position, the
+    second is a copy of the same produced frame.
+
+    ``dedup`` (a ``Duplicates``; default None): every frame is compared with the source frame before it (``atmvfi_frame_difference`` on
+    the copy stream behind its upload, against the previous upload's resident frame; one 1 032-byte read per frame), duplicates are
+    dropped from the timeline and their segment widens: the outputs in it are interpolated between the kept frames around them.
+    ``dedup.dropped`` / ``dedup.stats`` hold the run's record.
+
+    ``scene`` (a ``scene.SceneCuts``): the signatures of a segment's two ends are compared; a cut segment runs no forward, its outputs
+    at ``p <= N/2`` are copies of the first original and the rest copies of the second.
+
+    ``divisor``, ``tta``, ``pool``, ``pixfmt`` and ``keep_depth`` as in ``multiframe.interpolate_video_nx`` (with a 10-bit ``pixfmt``
+    and ``keep_depth`` the resident uint8 RGB frame is made only when ``dedup`` or ``scene`` needs it).  There is no ``time_interval``.
+    A model without the HIP backend gets the same frames through torch and the numpy twins.  ``report`` (a dict): filled with
+    ``"outputs"``, ``"interpolated"`` and ``"forwards"`` (the recursion nodes evaluated: pairs through the network, the second pass of
+    flip-TTA not counted) of the run.
+
+    The rates and ``levels`` are checked at the call; ``ValueError`` as ``retime_slots`` raises it."""
+    fi, fo, levels = _check_rates(fps_in, fps_out, levels)
+    return _retimed(frames, model, fi, fo, levels, dedup, crop, isBGR, divisor, tta, max_batch, pool, scene, pixfmt, keep_depth, report)
+
+
+def _retimed(frames, model, fi, fo, levels, dedup, crop, isBGR, divisor, tta, max_batch, pool, scene, pixfmt, keep_depth, report):
+    from .host_io import _hip_ops_of
+    n = 1 << levels
+    if scene is not None:
+        scene.begin()
+    if dedup is not None:
+        dedup.begin()
+    count = report if report is not None else {}
+    count.update(outputs=0, interpolated=0, forwards=0)
+    it = iter(frames)
+    first = next(it, None)
+    if first is None:
+        return
+    H, W = first.shape[:2] if pixfmt is None else (pixfmt.height, pixfmt.width)
+    y0, x0, h, w = window = centre_window(H, W, crop)
+    whole = (h, w) == (H, W)
+    crop_rgb = (lambda f: f) if whole else (lambda f: np.ascontiguousarray(f[y0:y0 + h, x0:x0 + w]))
+    original, out_fmt, deep = crop_rgb, None, False
+    if pixfmt is not None:
+        from . import yuv
+        if crop is not None and (y0 % 2 or x0 % 2):
+            raise ValueError(f"interpolate_video_retimed: the crop origin ({y0}, {x0}) must be even for 4:2:0 frames")
+        deep = bool(keep_depth) and pixfmt.depth == 10
+        isBGR, out_fmt = False, (pixfmt if deep else pixfmt.as_8bit()).cropped(h, w)
+        original = (lambda f: f) if whole else (lambda f: yuv.crop(f, pixfmt, y0, x0, h, w))
+    elif first.ndim != 3 or first.shape[2] != 3 or first.dtype != np.uint8:
+        raise ValueError(f"interpolate_video_retimed: expected uint8 [H,W,3] frames, got {first.dtype} {tuple(first.shape)}")
+    ops, dev = _hip_ops_of(model)
+    if ops is None or not hasattr(ops, "pool_blocks"):
+        be = _HostBackend(model, levels, window, crop_rgb, isBGR, divisor, tta, max(1, int(max_batch)), pixfmt, out_fmt, deep, dedup)
+    else:
+        # distinct interpolated positions of one segment: its outputs, at most ceil(g fps_out / fps_in) of them, g <= max_run + 1
+        span = 1 if dedup is None else dedup.max_run + 1
+        be = _DeviceBackend(model, ops, dev, H, W, levels, window, crop, isBGR, divisor, tta, max_batch, pool, pixfmt, out_fmt, deep, scene,
+                            dedup, out_slots=min(n - 1, -((-span * fo.numerator * fi.denominator) // (fo.denominator * fi.numerator))))
+    ends, number = {}, itertools.count()             # kept frames by their number on the timeline, until their segments are done
+    sig = {}                                         # signatures of segment ends that a later segment starts with
+
+    def kept():
+        """The indices of the kept frames.  Frame k is judged when frame k + 1 has been read (and its upload started: one frame ahead
+        of the forwards); a duplicate that turns out to be the last frame is kept."""
+        pending = None
+        for i, f in enumerate(_chain(first, it)):
+            e = {"i": i, "f": f}
+            be.admit(e)
+            if i == 0:
+                be.first(e)
+                if scene is not None:
+                    sig[0] = be.signature(e)
+            if pending is not None and not (dedup is not None and pending["i"] > 0 and dedup.judge(be.difference(pending), h, w)):
+                ends[next(number)] = pending
+                yield pending["i"]
+            pending = e
+        if dedup is not None and pending["i"] > 0:
+            dedup.judge(be.difference(pending), h, w)
+            dedup.finish()
+        ends[next(number)] = pending
+        yield pending["i"]
+    try:
+        ran = -1
+        for j, ps in _retime_segments(kept(), fi, fo, levels):
+            if j == ran or j + 1 not in ends:        # the output at the last kept frame (a one-frame stream: at its only frame)
+                count["outputs"] += len(ps)
+                for _ in ps:
+                    yield original(ends[j + 1 if j == ran else j]["f"])
+                continue
+            a, b = ends[j], ends[j + 1]
+            ran = j
+            interior = sorted({p for p in ps if 0 < p < n})
+            cut = False
+            if scene is not None:
+                sig_a = sig.pop(j)
+                sig[j + 1] = be.signature(b)
+                cut = scene.judge(sig_a, sig[j + 1], h, w)
+            made = be.segment(a, b, interior, cut)
+            if made:
+                count["forwards"] += sum(len(lv) for lv in sparse_levels(interior, levels))
+            count["outputs"] += len(ps)
+            count["interpolated"] += sum(0 < p < n for p in ps)
+            seen = set()
+            for p in ps:
+                if p == 0 or p == n:
+                    yield original((a if p == 0 else b)["f"])
+                elif cut:
+                    yield np.array(original((a if p <= n // 2 else b)["f"]), copy=True)
+                elif p in seen:
+                    yield made[p].copy()
+                else:
+                    seen.add(p)
+                    yield made[p]
+            del ends[j]
+    finally:
+        be.close()
+
+
+def video_retimed(cap, make_writer, model, fps_out, interpolator=None, crop: Optional[Tuple[int, int]] = None, **kw):
+    """``multiframe.video_nx``'s contract for a rate conversion: reads FPS, W, H from ``cap`` (a whole-number FPS, or pass ``fps_in=``
+    among ``kw`` for an exact one such as ``"30000/1001"``), opens the sink with ``make_writer(fps_out, (W, H))`` -- the crop's size
+    when cropping; ``fps_out`` as an int when it is whole, else as a float -- writes what ``interpolator(frames, model, fps_in,
+    fps_out, crop=, **kw)`` yields (default ``interpolate_video_retimed``) and releases both ends, also when a frame fails.  Returns
+    ``{"fps_in", "fps_out", "size", "frames_in", "frames_out", "forwards"}``, with ``dedup=`` among ``kw`` also ``"dropped"`` and with
+    ``scene=`` also ``"cuts"``."""
+    from .host_io import CAP_PROP_FPS, CAP_PROP_FRAME_HEIGHT, CAP_PROP_FRAME_WIDTH, capture_frames
+    fi = as_rate(kw.pop("fps_in"), "fps_in") if "fps_in" in kw else as_rate(int(cap.get(CAP_PROP_FPS)), "fps_in")
+    fo = as_rate(fps_out, "fps_out")
+    _check_rates(fi, fo, kw.get("levels", 3))
+    w, h = int(cap.get(CAP_PROP_FRAME_WIDTH)), int(cap.get(CAP_PROP_FRAME_HEIGHT))
+    _, _, oh, ow = centre_window(h, w, crop)
+    plain = lambda r: int(r) if r.denominator == 1 else float(r)
+    out = make_writer(plain(fo), (ow, oh))
+    n_in, report = [0], kw.pop("report", None)
+    report = {} if report is None else report
+
+    def counted():
+        for f in capture_frames(cap):
+            if f.shape[:2] != (h, w):
+                raise ValueError(f"video_retimed: the capture announced {w}x{h} frames and delivered {f.shape[1]}x{f.shape[0]}")
+            n_in[0] += 1
+            yield f
+    n_out = 0
+    try:
+        for frame in (interpolator or interpolate_video_retimed)(counted(), model, fi, fo, crop=crop, report=report, **kw):
+            out.write(frame)
+            n_out += 1
+    finally:
+        cap.release()
+        out.release()
+    info = {"fps_in": plain(fi), "fps_out": plain(fo), "size": (ow, oh), "frames_in": n_in[0], "frames_out": n_out,
+            "forwards": report.get("forwards", 0)}
+    if kw.get("dedup") is not None:
+        info["dropped"] = list(kw["dedup"].dropped)
+    if kw.get("scene") is not None:
+        info["cuts"] = list(kw["scene"].cuts)
+    return info

@@ -432,7 +432,7 @@ def to_8bit(frame, fmt: Format) -> np.ndarray:
 
 
 def interpolate_y4m(src, dst, model, factor: int = 2, scene=None, tta: bool = False, interpolator=None, matrix: str = "auto",
-                    keep_depth: bool = False, **kw):
+                    keep_depth: bool = False, fps_out=None, levels: int = 3, dedup=None, **kw):
     """Y4M file (or binary file object) ``src`` -> Y4M ``dst`` at ``fps * factor`` (``/ time_interval`` when given): an exact
     rational, 30000/1001 in gives 60000/1001 out.  Frames travel as I420 both ways (``pixfmt``); originals are written as read,
     predicted frames are encoded on the device.  The same format tags are written; 10-bit input is decoded on the device and written
@@ -440,7 +440,14 @@ def interpolate_y4m(src, dst, model, factor: int = 2, scene=None, tta: bool = Fa
     ``time_interval`` runs ``interpolate_video_2x``, everything else ``interpolate_video_nx``; ``interpolator(frames, model, pixfmt=,
     ...)`` overrides.  ``matrix``: as for ``Y4MReader`` (a Y4M header cannot name it).  ``keep_depth`` (changes nothing for 8-bit
     input): a C420p10 stream is written back as C420p10 -- originals byte for byte as read, predictions encoded on the device from
-    the fp32 prediction at 10 bits; nothing is re-quantised to 8 bit.  Returns ``{"fps_in", "fps_out", "size", "frames_in", "frames_out"}`` and, with ``scene``, ``"cuts"``."""
+    the fp32 prediction at 10 bits; nothing is re-quantised to 8 bit.  Returns ``{"fps_in", "fps_out", "size", "frames_in", "frames_out"}`` and, with ``scene``, ``"cuts"``.
+
+    ``fps_out`` (an int, a ``Fraction`` or a string such as ``"60000/1001"``; default None: everything above, unchanged): a rate
+    conversion instead -- ``retime.interpolate_video_retimed`` from the stream's own rate to exactly ``fps_out``, which the written
+    header carries, with ``levels`` and ``dedup`` (a ``retime.Duplicates``) handed on; ``factor`` is ignored and there is no
+    ``time_interval``.  The dict gains ``"forwards"`` and, with ``dedup``, ``"dropped"``."""
+    if fps_out is not None:
+        return _retime_y4m(src, dst, model, fps_out, levels, dedup, scene, tta, interpolator, matrix, keep_depth, kw)
     from .host_io import _hip_ops_of, interpolate_video_2x
     from .multiframe import centre_window, interpolate_video_nx, nx_levels
     nx_levels(factor)
@@ -477,7 +484,47 @@ def interpolate_y4m(src, dst, model, factor: int = 2, scene=None, tta: bool = Fa
     return info
 
 
+def _retime_y4m(src, dst, model, fps_out, levels, dedup, scene, tta, interpolator, matrix, keep_depth, kw):
+    """``interpolate_y4m`` with ``fps_out``."""
+    from .multiframe import centre_window
+    from .retime import _check_rates, interpolate_video_retimed
+    if "time_interval" in kw:
+        raise ValueError("interpolate_y4m: fps_out and time_interval do not go together")
+    rd = Y4MReader(src, matrix=matrix)
+    try:
+        fmt = rd.fmt
+        _, rate, levels = _check_rates(rd.fps, fps_out, levels)
+        _, _, oh, ow = centre_window(fmt.height, fmt.width, kw.get("crop"))
+    except Exception:
+        rd.close()
+        raise
+    deep = bool(keep_depth) and fmt.depth == 10
+    out_fmt = (fmt if deep else fmt.as_8bit()).cropped(oh, ow)
+    wr = Y4MWriter(dst, out_fmt, rate, ctag=rd.ctag if (fmt.depth == 8 or deep) else None, aspect=rd.aspect)
+    n_in, report = [0], {}
+
+    def counted():
+        for f in rd:
+            n_in[0] += 1
+            yield f
+    try:
+        for f in (interpolator or interpolate_video_retimed)(counted(), model, rd.fps, rate, levels=levels, dedup=dedup, scene=scene, tta=tta,
+                                                             pixfmt=fmt, keep_depth=deep, report=report, **kw):
+            wr.write(to_8bit(f, fmt.cropped(oh, ow)) if (f.dtype == np.uint16 and not deep) else f)
+    finally:
+        rd.close()
+        wr.close()
+    info = {"fps_in": rd.fps, "fps_out": rate, "size": (ow, oh), "frames_in": n_in[0], "frames_out": wr.frames,
+            "forwards": report.get("forwards", 0)}
+    if dedup is not None:
+        info["dropped"] = list(dedup.dropped)
+    if scene is not None:
+        info["cuts"] = list(scene.cuts)
+    return info
+
+
 # what a user of this module needs from the loops
 from .host_io import FramePipeline, interpolate_video_2x, load_model_checkpoint  # noqa: E402,F401
 from .multiframe import interpolate_video_nx  # noqa: E402,F401
 from .scene import SceneCuts  # noqa: E402,F401
+from .retime import Duplicates, interpolate_video_retimed  # noqa: E402,F401

@@ -468,6 +468,25 @@ int64_t atmvfi_frame_signature_workspace_ints(int h, int w);
 int atmvfi_frame_signature(const void* src, int H, int W, int bgr, int y0, int x0, int h, int w, int32_t* sig /*[288]*/, int32_t* workspace,
                            int64_t workspace_ints, void* stream);
 
+/* Frame difference for duplicate-frame detection in the retimed video loop (framediff.hip; ABI 0.16; atm-vfi_amd/retime.py judges it).
+ * Nothing of the reference.  Two resident uint8 [H,W,3] frames a and b of the same geometry (contiguous; BGR if `bgr`) and the window
+ * (y0, x0, h, w) -> int32 out[258] on the device:
+ *   luma          Y = (77 R + 150 G + 29 B + 128) >> 8 (the signature's);
+ *   out[16 i + j] = the sum of |Ya - Yb| over rows [i h / 16, (i + 1) h / 16) and columns [j w / 16, (j + 1) w / 16) of the window (the
+ *                   signature's 16 x 16 cells, row-major);
+ *   out[256]      = the maximum of |Ya - Yb| over the window;
+ *   out[257]      = the number of window pixels with Ya != Yb.
+ * The window rules and refusals of atmvfi_frame_signature: h, w >= 16, the window inside the frame, and small enough that cell sums and
+ * the pixel count fit int32 (ATMVFI_EINVAL otherwise).  Any geometry and pointer alignment of a and b is accepted; dword loads are used
+ * when BOTH are 4-byte aligned and W, x0 and w are multiples of 4.  Integer arithmetic only: both paths and any reduction order give the
+ * same bits.  out (4-byte aligned) is written completely by the call: nothing is pre-zeroed and no global atomics are used.  workspace:
+ * at least atmvfi_frame_difference_workspace_ints(h, w) int32 of scratch, the caller's (per-workgroup partials, reduced by a second
+ * launch of the same call); the query returns -1 for a window the call would refuse.  Stream-ordered: two launches, no host
+ * synchronisation, no allocation. */
+int64_t atmvfi_frame_difference_workspace_ints(int h, int w);
+int atmvfi_frame_difference(const void* a, const void* b, int H, int W, int bgr, int y0, int x0, int h, int w, int32_t* out /*[258]*/,
+                            int32_t* workspace, int64_t workspace_ints, void* stream);
+
 /* Planar YUV 4:2:0 (I420) <-> RGB for the video loops (yuv.hip; atm-vfi_amd/yuv.py holds the format, the numpy twins and Y4M I/O).
  * Nothing of the reference: its scripts read PNGs.  A bit-exact contract in int32 (>> is an arithmetic shift: floor).
  * Frame: one contiguous buffer Y [H,W], U [ch,cw], V [ch,cw], ch = (H + 1) / 2, cw = (W + 1) / 2, H, W >= 1 (odd sizes allowed);

@@ -5,7 +5,11 @@ is written back as 8-bit, or with ``--keep-depth`` as C420p10 (originals byte fo
 - out.y4m --ckpt ...``).
 
     python tools/interp_y4m.py IN.y4m OUT.y4m --ckpt CKPT [--model base|lite] [--factor 2|4|8] [--scene] [--tta] [--global-off]
-                              [--keep-depth]"""
+                              [--keep-depth] [--fps-out R [--levels L] [--dedup]]
+
+``--fps-out R`` (an integer or a ratio such as 60000/1001) converts the frame rate to exactly R instead of multiplying it: every output
+is the nearest of 2**L positions (``--levels``, default 3) between two source frames; ``--dedup`` drops repeated frames first
+(``Duplicates()`` defaults)."""
 import argparse
 import importlib
 import os
@@ -29,7 +33,12 @@ def main():
     ap.add_argument("--global-off", action="store_true", help="switch the global motion branch off")
     ap.add_argument("--matrix", choices=("auto", "bt601", "bt709"), default="auto", help="a Y4M header cannot name the matrix")
     ap.add_argument("--keep-depth", action="store_true", help="write 10-bit (C420p10) input back as C420p10 instead of 8-bit")
+    ap.add_argument("--fps-out", default=None, metavar="R", help="convert the frame rate to R (e.g. 60 or 60000/1001); --factor is ignored")
+    ap.add_argument("--levels", type=int, default=3, help="with --fps-out: 2**L positions per segment (1..6)")
+    ap.add_argument("--dedup", action="store_true", help="with --fps-out: drop repeated frames (Duplicates() defaults)")
     a = ap.parse_args()
+    if (a.dedup or a.levels != 3) and a.fps_out is None:
+        ap.error("--levels and --dedup need --fps-out")
     if not torch.cuda.is_available():
         sys.exit("interp_y4m: no GPU")
     pkg = importlib.import_module("atm-vfi_amd")
@@ -46,7 +55,8 @@ def main():
     src = sys.stdin.buffer if a.src == "-" else a.src
     dst = sys.stdout.buffer if a.dst == "-" else a.dst
     info = yuv.interpolate_y4m(src, dst, net, factor=a.factor, scene=yuv.SceneCuts() if a.scene else None, tta=a.tta, matrix=a.matrix,
-                               keep_depth=a.keep_depth)
+                               keep_depth=a.keep_depth,
+                               **(dict(fps_out=a.fps_out, levels=a.levels, dedup=yuv.Duplicates() if a.dedup else None) if a.fps_out else {}))
     print({k: (str(v) if k.startswith("fps") else v) for k, v in info.items()}, file=sys.stderr)
 
 
