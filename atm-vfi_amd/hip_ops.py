@@ -27,6 +27,7 @@ GEMM_CONV, GEMM_LINEAR, GEMM_DECONV = 0, 1, 2
 
 c_f = ctypes.c_void_p      # device pointers travel as void*
 c_i = ctypes.c_int
+C_SLOTS = ctypes.POINTER(ctypes.c_int32)      # a HOST int32 list read at launch time (atmvfi_pool_blocks' slots)
 c_l = ctypes.c_int64
 
 
@@ -130,7 +131,7 @@ SIGNATURES = {
     "atmvfi_frame_u8_to_f32": (c_i, [c_f, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f]),
     "atmvfi_frame_u8_window": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f, c_f]),
     "atmvfi_frame_f32_to_u8": (c_i, [c_f, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_f]),
-    "atmvfi_pool_blocks": (c_i, [c_f, c_l, c_i, ctypes.POINTER(ctypes.c_int32), c_i, c_l, c_f, c_i, c_f]),
+    "atmvfi_pool_blocks": (c_i, [c_f, c_l, c_i, C_SLOTS, c_i, c_l, c_f, c_i, c_f]),
     "atmvfi_tta_merge": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f]),
     "atmvfi_frame_rot180": (c_i, [c_f, c_f, c_i, c_i, c_i, c_f]),
     "atmvfi_frame_signature_workspace_ints": (c_l, [c_i, c_i]),
@@ -321,12 +322,18 @@ class PlanUnsupported(Exception):
 
 class LaunchPlan:
     """One forward of the hot path recorded as an array of ``atmvfi_plan_op`` (include/atmvfi.h, "Launch plans") and replayed by ONE
-    ``atmvfi_plan_run`` call: per-call memory -- the caller's two frames and the output tensors, fresh on every call -- enters through
-    a slot table that the library patches into the recorded arguments.
+    ``atmvfi_plan_run`` call: per-call memory -- the caller's input tensors (the two frames of ``forward``, the three pool tensors of
+    ``forward_pooled``; any number) and the output tensors, fresh on every call -- enters through a slot table that the library
+    patches into the recorded arguments.  A plan may have no outputs at all (``finish(None)``: it only writes into its inputs).
 
     Recording (``HipOps.begin_plan`` ... ``end_plan``): every launch of ``HipOps._run`` is executed as usual AND appended; every
     ``HipOps.empty`` becomes an output slot; pointer arguments (by the entry point's declared types) that fall inside a slot's
-    memory become patches.  A pointer field of a GEMM parameter block inside per-call memory cannot be patched: PlanUnsupported."""
+    memory become patches.  A pointer field of a GEMM parameter block inside per-call memory cannot be patched: PlanUnsupported.
+
+    Host integer lists (the slot list of ``atmvfi_pool_blocks``, declared ``POINTER(c_int32)``): the library reads such an array at
+    launch time (include/atmvfi.h, "Launch plans"), so the op records the ctypes array's ADDRESS, the plan keeps the array alive and
+    registers it under the ROLE its caller gave it (``HipOps.pool_blocks(..., role=)``); ``run(..., lists={role: values})`` overwrites
+    every registered array before the replay.  The length of a role is fixed by the recording; no replay ever sees stale values."""
 
     debug = False      # diagnostic: replay one op per call, synchronised, announced on stderr first (finds the op that faults)
 
@@ -334,6 +341,7 @@ class LaunchPlan:
         self.lib = lib
         self.ops_list = []                 # (fn id, [values], [is_float])
         self.keep = []                     # parameter blocks referenced by address
+        self.lists = {}                    # role -> [host int32 arrays referenced by address]: rewritten from run(lists=) per replay
         self.slots = []                    # (base, bytes): inputs first, then outputs
         self._slot_store = []              # per slot: address of the storage the slot's tensor lives in
         for t in inputs:
@@ -342,7 +350,7 @@ class LaunchPlan:
             for j in range(i):
                 (bi, ni), (bj, nj) = self.slots[i], self.slots[j]
                 if bi < bj + nj and bj < bi + ni:
-                    raise PlanUnsupported("the input frames overlap in memory: a pointer into one could not be told from a pointer into the other")
+                    raise PlanUnsupported("the input tensors overlap in memory: a pointer into one could not be told from a pointer into the other")
         self.n_inputs = len(inputs)
         self.align = tuple(t.data_ptr() & 15 for t in inputs)      # kernel choices (16-byte row loads) were made for this alignment
         self.out_meta = []                 # (shape, dtype) per output slot, allocation order
@@ -412,6 +420,16 @@ class LaunchPlan:
                 self.keep.append(blk)
                 vals.append(("u", ctypes.addressof(blk)))
                 continue
+            if ty is C_SLOTS:              # a host integer list, read by the library at launch time: by address, under its role
+                role = getattr(v, "role", None)
+                if not isinstance(v, ctypes.Array) or v._type_ is not ctypes.c_int32 or role is None:
+                    raise PlanUnsupported(f"{name}: argument {j} is a host integer list without a role")
+                known = self.lists.setdefault(role, [])
+                if known and len(known[0]) != len(v):
+                    raise PlanUnsupported(f"{name}: role {role!r} names lists of {len(known[0])} and of {len(v)} entries")
+                known.append(v)
+                vals.append(("u", ctypes.addressof(v)))
+                continue
             src = getattr(v, "src", None) if isinstance(v, TPtr) else None
             if isinstance(v, ctypes.c_void_p):
                 v = v.value
@@ -461,9 +479,26 @@ class LaunchPlan:
         return self
 
     # ---- replay ----
-    def run(self, inputs, device, stream, poison: bool = False):
+    def _rewrite_lists(self, lists):
+        if set(lists or ()) != set(self.lists):
+            raise ValueError(f"LaunchPlan.run: the plan's host lists are {sorted(self.lists)}, given {sorted(lists or ())}")
+        new = {role: [int(x) for x in lists[role]] for role in self.lists}
+        for role, arrays in self.lists.items():
+            if len(new[role]) != len(arrays[0]):
+                raise ValueError(f"LaunchPlan.run: list {role!r} was recorded with {len(arrays[0])} entries, given {len(new[role])}")
+        for role, arrays in self.lists.items():              # (only now: a refused call leaves the arrays as they were)
+            for arr in arrays:
+                arr[:] = new[role]
+
+    def run(self, inputs, device, stream, poison: bool = False, lists=None):
         """``poison``: fill the fresh outputs with NaN first (the record-time self-check: an element the replay does not write, or
-        writes somewhere else, then differs from the recording forward's result)."""
+        writes somewhere else, then differs from the recording forward's result).  ``lists``: {role: sequence of ints} for every host
+        integer list of the plan -- all of them, each of its recorded length, else ``ValueError`` before anything is launched (a plan
+        without such lists takes None).  Returns the recorded result structure over fresh tensors (None for a plan without outputs)."""
+        if len(inputs) != self.n_inputs:
+            raise ValueError(f"LaunchPlan.run: {len(inputs)} inputs, recorded with {self.n_inputs}")
+        if self.lists or lists:
+            self._rewrite_lists(lists)
         outs = [torch.empty(shape, dtype=dt, device=device) for shape, dt in self.out_meta]
         if poison:
             for t in outs:
@@ -1400,13 +1435,16 @@ class HipOps:
         self._run("frame_f32_to_u8", {"bytes": 3.0 * h * w + 12.0 * h * w}, self.lib.atmvfi_frame_f32_to_u8, _ptr(src), src.shape[1],
                   src.shape[2], pad_top, pad_left, _ptr(dst_u8), h, w, int(bgr), self._stream())
 
-    def pool_blocks(self, pool, slots, buf, to_pool: bool = False, block_elems: Optional[int] = None):
+    def pool_blocks(self, pool, slots, buf, to_pool: bool = False, block_elems: Optional[int] = None, role: Optional[str] = None):
         """``len(slots)`` blocks between the slots of ``pool`` (contiguous [S, ...]) and the contiguous ``buf`` in one launch
         (include/atmvfi.h atmvfi_pool_blocks).  Gather (``to_pool`` False): block j of ``buf`` = the first ``block_elems`` elements of
         ``pool[slots[j]]`` -- ``torch.index_select``; scatter: the inverse -- ``Tensor.index_copy_``.  ``block_elems`` defaults to a
-        whole slot.  ``slots`` is a host sequence of ints; it travels in the kernel arguments."""
-        if self.recording is not None:
-            raise PlanUnsupported("pool_blocks takes a host slot list: pooled forwards are not recorded")
+        whole slot.  ``slots`` is a host sequence of ints; it travels in the kernel arguments.  ``role``: while a launch plan is being
+        recorded, the name under which the plan registers this call's slot list (``LaunchPlan.run(lists={role: ...})`` rewrites it
+        before every replay); a recording without a role cannot know what the list means on the next call: ``PlanUnsupported``.
+        Outside a recording ``role`` is ignored."""
+        if self.recording is not None and role is None:
+            raise PlanUnsupported("pool_blocks takes a host slot list: give it a role to record it")
         n = len(slots)
         if pool.dim() < 1 or not pool.is_contiguous() or not buf.is_contiguous() or not pool.is_cuda or not buf.is_cuda:
             raise ValueError("pool_blocks: pool and buf must be contiguous CUDA tensors")
@@ -1420,6 +1458,7 @@ class HipOps:
         if be <= 0 or be > slot_elems or buf.numel() != n * be:
             raise ValueError(f"pool_blocks: buf holds {buf.numel()} elements, {n} blocks of {be} (slot: {slot_elems}) need {n * be}")
         arr = (ctypes.c_int32 * n)(*[int(s) for s in slots])
+        arr.role = role
         self._run("pool_blocks", {"bytes": 2.0 * n * be * es, "blocks": n}, self.lib.atmvfi_pool_blocks, _ptr(pool), slot_elems * es,
                   pool.shape[0], arr, n, be * es, _ptr(buf), int(bool(to_pool)), self._stream())
 

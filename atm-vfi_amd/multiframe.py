@@ -246,7 +246,8 @@ class _SegmentRunner:
 
     Workspaces: batches of different size are different workspaces of the model, and its LRU of two would free and reallocate them
     per level at 8x (batch sizes 1, 2, 4).  The runner RAISES ``model.max_workspaces`` to the number of batch sizes of its schedule for
-    its lifetime and restores it in ``close()``.
+    its lifetime and restores it in ``close()``.  The launch plans of ``forward_pooled`` are recorded into those same workspaces (one per
+    batch size, whatever the stale count), so the raise covers them too: no plan of the steady state is evicted and recorded again.
 
     ``run(..., levels=, emit=)`` (``retime.interpolate_video_retimed``): a sparse schedule (``retime.sparse_levels``) instead of the full
     recursion, and the positions that leave for the host -- the others are ancestors only and stay in the pool.  ``out_slots``: the size

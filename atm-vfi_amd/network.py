@@ -256,6 +256,13 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
         self.use_plans = True
         self._plans: Dict[Tuple, object] = {}       # key -> LaunchPlan | int (eager forwards seen so far) | False (cannot be planned)
         self._plan_sig = None
+        # launch plans of forward_pooled: per key a frame-stage plan (the stale slots' tokens) and a pair-stage plan (the rest), both
+        # over the pool's three tensors as per-call inputs and the slot lists as per-call host lists.  A dict of their own (keys end
+        # with the workspace key like those of _plans); cleared wherever _plans is.
+        self._pool_plans: Dict[Tuple, object] = {}
+        self._pooled_plans_on = True                # tools only (bench_nx / bench_retime A/B): False keeps forward_pooled eager
+        self._splitk_memo: Dict[Tuple, Tuple] = {}  # _frame_stage_splitk per (H, W, frames, mode): host-side, asked per pooled call
+        self._plan_stats = self._new_plan_stats()
         self._plist = None                          # cached parameter list of the per-forward currency check (_param_sig)
         self._pepoch = -1
         self._primary: Optional["Network"] = None   # set on replicas (replica()): the model whose packed weights this one reads
@@ -352,7 +359,8 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
         self._prepared_sig = None
         self._plist = None
         self._graphs.clear()
-        self._plans.clear()
+        self._drop_plans()
+        self._splitk_memo.clear()
         self._workspaces.clear()
         self._bufs = {}
         self._ws_key = None
@@ -379,8 +387,13 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
         """Split-K scratch of the plane-input GEMM (hip_ops.HipOps.gemm_workspace): workspace memory like every other buffer."""
         return self.buf("gemm_splitk_ws", floats)
 
+    def _drop_plans(self):
+        """Every recorded launch plan, of ``forward`` and of ``forward_pooled`` alike (and their warm-up counts)."""
+        self._plans.clear()
+        self._pool_plans.clear()
+
     def release_workspace(self):
-        self._plans.clear()           # recorded plans and
+        self._drop_plans()            # recorded plans and
         self._graphs.clear()          # captured graphs launch into the workspace
         self._workspaces.clear()
         self._bufs = {}
@@ -409,12 +422,13 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
             del self._workspaces[old]
             for gk in [g for g in self._graphs if g[-1] == old]:      # graphs captured into that workspace
                 del self._graphs[gk]
-            for gk in [g for g in self._plans if g[-1] == old]:       # plans recorded into it
-                del self._plans[gk]
+            for plans in (self._plans, self._pool_plans):              # plans recorded into it
+                for gk in [g for g in plans if g[-1] == old]:
+                    del plans[gk]
         if len(self._geo) > 64:                                        # window maps are small; bound them all the same
             for gk in list(self._geo)[:len(self._geo) - 64]:
                 del self._geo[gk]
-            self._plans.clear()                                        # a plan may hold a map that just went
+            self._drop_plans()                                         # a plan may hold a map that just went
             self._graphs.clear()
 
     # ------------------------------------------------------------------ weights
@@ -446,7 +460,7 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
 
     _RUNTIME_RESET = {"_ops_obj": None, "_prepared_sig": None, "_ws_key": None, "_graph_sig": None, "_plan_sig": None, "_plist": None,
                       "_pepoch": -1, "_frame_cache": None, "_primary": None, "_prepare_lock": None, "_reuse_first": False}
-    _RUNTIME_DICTS = ("_bufs", "_geo", "_prepared", "_workspaces", "_graphs", "_plans")
+    _RUNTIME_DICTS = ("_bufs", "_geo", "_prepared", "_workspaces", "_graphs", "_plans", "_pool_plans", "_splitk_memo")
 
     def __getstate__(self):
         """copy.deepcopy / pickle / torch.save(module): parameters, buffers and settings travel; device-side runtime state
@@ -481,6 +495,7 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
         rep._prepared, rep._prepared_sig = {}, None
         rep._workspaces, rep._ws_key, rep._bufs, rep._geo = {}, None, {}, {}
         rep._graphs, rep._graph_sig, rep._plans, rep._plan_sig = {}, None, {}, None
+        rep._pool_plans, rep._splitk_memo, rep._plan_stats = {}, {}, self._new_plan_stats()
         rep._frame_cache_on, rep._frame_cache, rep._reuse_first = False, None, False
         rep._plist, rep._pepoch = None, -1
         return rep
@@ -857,42 +872,75 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
         (``hip_ops.LaunchPlan``) and every later one is a single ``atmvfi_plan_run`` call -- same launches, same arguments, fresh
         output tensors -- instead of ~120 Python-side op calls.  Not used with the frame cache, graphs or per-launch profiling (those
         forwards contain copies outside the C ABI or need the individual launches).  Ensemble mode is planned too since round 4 (its
-        per-sample pick is `atmvfi_ensemble_select`)."""
+        per-sample pick is `atmvfi_ensemble_select`).
+
+        ``forward_pooled`` is planned the same way, as two plans per key -- the frame stage over the stale slots and the pair stage --
+        whose inputs are the pool's tensors and whose slot lists are rewritten per call (see its docstring); this switch turns
+        those off too.  Calling it, with either value, restarts the counts of ``plan_stats()``."""
         self.use_plans = bool(flag)
+        self._plan_stats = self._new_plan_stats()
         if not flag:
-            self._plans.clear()
+            self._drop_plans()
+
+    PLAN_KINDS = ("forward", "pooled_frame", "pooled_pair")
+
+    @classmethod
+    def _new_plan_stats(cls) -> Dict[str, Dict[str, int]]:
+        return {kind: {"eager": 0, "recorded": 0, "replayed": 0, "refused": 0} for kind in cls.PLAN_KINDS}
+
+    def plan_stats(self) -> Dict[str, Dict[str, int]]:
+        """Diagnostic, read-only: how the calls since construction (or the last ``enable_plans``) were submitted, per kind --
+        ``"forward"``: ``forward`` calls; ``"pooled_frame"`` / ``"pooled_pair"``: the two stages of ``forward_pooled`` (the frame stage
+        counts only in calls that had stale slots).  Each stage of each call lands in exactly one bin: ``eager`` (direct launches:
+        warm-up, plans off, profiling, the checked build, graphs' and the frame cache's forwards, a key that cannot be planned),
+        ``recorded`` (direct launches that were recorded into a plan that then passed its self-check), ``replayed`` (one
+        ``atmvfi_plan_run``), ``refused`` (a recording that could not be expressed or failed its self-check; the key stays eager).
+        A copy; not part of the reference's API."""
+        return {kind: dict(c) for kind, c in self._plan_stats.items()}
+
+    def _mode_fields(self, ops) -> Tuple:
+        return (self.global_motion, self.ensemble_global_motion, self._precision, self._checked, getattr(ops, "attention_f16x3", None),
+                self.local_motion_args["window_size"], self.global_motion_args["window_size"], getattr(ops, "warp_tiles", None),
+                getattr(ops, "conv3_instance", None), getattr(ops, "gemm_tile_wn", None))
 
     def _mode_key(self, ops, im0, im1) -> Tuple:
-        return (tuple(im0.shape), tuple(im1.shape), str(im0.device), self.global_motion, self.ensemble_global_motion,
-                self._precision, self._checked, getattr(ops, "attention_f16x3", None), self.local_motion_args["window_size"],
-                self.global_motion_args["window_size"], getattr(ops, "warp_tiles", None), getattr(ops, "conv3_instance", None),
-                getattr(ops, "gemm_tile_wn", None), self._workspace_key(im0))
+        return (tuple(im0.shape), tuple(im1.shape), str(im0.device)) + self._mode_fields(ops) + (self._workspace_key(im0),)
+
+    def _sync_plan_sig(self):
+        if self._plan_sig is not self._prepared_sig:         # parameters changed: recorded launches hold stale weight pointers
+            self._drop_plans()
+            self._plan_sig = self._prepared_sig
 
     def forward(self, im0: torch.Tensor, im1: torch.Tensor, reuse_first: bool = False):
         self._reuse_first = bool(reuse_first)
+        st = self._plan_stats["forward"]
         if not im0.is_cuda or self._frame_cache_on or self._checked:
+            st["eager"] += 1
             return self._forward_eager(im0, im1)
         if self.use_graphs:
+            st["eager"] += 1
             return self._forward_graph(im0, im1)
         ops = self._ops_obj
         pl = self._plist
         if (not self.use_plans or not isinstance(ops, HipOps) or ops.profile is not None
                 or pl is None or pl[0].device != im0.device or torch.cuda.is_current_stream_capturing()):
+            st["eager"] += 1
             return self._forward_eager(im0, im1)         # (also every case that must raise: it validates devices and shapes)
         self._prepare(ops)
-        if self._plan_sig is not self._prepared_sig:         # parameters changed: recorded launches hold stale weight pointers
-            self._plans.clear()
-            self._plan_sig = self._prepared_sig
+        self._sync_plan_sig()
         key = self._mode_key(ops, im0, im1)
         ent = self._plans.get(key, 0)
         if ent is False:
+            st["eager"] += 1
             return self._forward_eager(im0, im1)
         if isinstance(ent, int):
             if ent < 2:                                      # the first two forwards build the workspace, maps, kernel attributes
                 self._plans[key] = ent + 1
+                st["eager"] += 1
                 return self._forward_eager(im0, im1)
             return self._record_plan(ops, key, im0, im1)
         if im0.shape != im1.shape or im0.device != im1.device or im0.device != ops.device:
+            st["eager"] += 1
             return self._forward_eager(im0, im1)             # raises the proper error
         with torch.cuda.device(im0.device):
             a = im0.detach().contiguous().float()
@@ -900,8 +948,10 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
             if (a.data_ptr() & 15, b.data_ptr() & 15) != ent.align:
                 # the recording chose kernels for its inputs' alignment (the LDS-staged warps load rows 16 bytes at a time): a
                 # differently aligned view takes the direct launches, which choose again
+                st["eager"] += 1
                 return self._forward_eager(im0, im1)
             self._select_workspace(key[-1])                  # replay counts as a use for the workspace LRU
+            st["replayed"] += 1
             return ent.run((a, b), ops.device, ops._stream())
 
     @staticmethod
@@ -921,6 +971,7 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
         if a.data_ptr() < b.data_ptr() + nb and b.data_ptr() < a.data_ptr() + na:
             # aliased / overlapping frames (net(x, x)): a recording could not tell a pointer into one from a pointer into the other
             # and every later net(a, b) of this shape would replay as net(a, a).  Stay eager; the next call with distinct frames records.
+            self._plan_stats["forward"]["eager"] += 1
             return self._forward_eager(im0, im1)
         try:
             ops.begin_plan((a, b))
@@ -929,6 +980,7 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
         except PlanUnsupported:
             ops.abort_plan()
             self._plans[key] = False
+            self._plan_stats["forward"]["refused"] += 1
             return self._forward_eager(im0, im1)
         except Exception:
             ops.abort_plan()
@@ -940,10 +992,12 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
             again = plan.run((a, b), ops.device, ops._stream(), poison=True)
         if self._same_results(out, again):
             self._plans[key] = plan
+            self._plan_stats["forward"]["recorded"] += 1
         else:
             import warnings
             warnings.warn("atm-vfi_amd: a recorded launch plan did not reproduce its own forward; this input shape stays on direct launches")
             self._plans[key] = False
+            self._plan_stats["forward"]["refused"] += 1
         return out
 
     def _forward_graph(self, im0: torch.Tensor, im1: torch.Tensor):
@@ -1096,9 +1150,20 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
         in the pool; frames and tokens of the pairs are gathered with ``atmvfi_pool_blocks`` and ``_pair_stage`` runs as in
         ``forward``.  Returns ``forward``'s dict of fresh tensors, bit-identical to ``forward`` on the same batch.  A stale slot is
         recomputed, never an error; a pool of another device, another model width or a slot outside the pool raises ``ValueError``.
-        With ``ensemble_global_motion`` nothing is per frame: the frames are gathered and the plain path runs.  Runs eagerly (no
-        launch plan, like the frame cache); every device operation is a launch of the C ABI.  An odd number of stale frames is fed
-        to ``pack_frames`` (which takes pairs) by naming the last one twice; the encoder runs on the distinct ones only.
+        With ``ensemble_global_motion`` nothing is per frame: the frames are gathered and the plain path runs.  Every device
+        operation is a launch of the C ABI.  An odd number of stale frames is fed to ``pack_frames`` (which takes pairs) by naming the
+        last one twice; the encoder runs on the distinct ones only.
+
+        Launch plans (``enable_plans``, default on): the call is two stages, each replayed from a ``hip_ops.LaunchPlan`` once its key
+        has run twice with direct launches -- the FRAME stage (gather of the stale frames, ``pack_frames``, ``_frame_stage``, the token
+        scatters; keyed by batch size, stale count and the count it is filled up to; runs only when something is stale; no outputs)
+        and the PAIR stage (the three gathers of the pairs, the image pyramid, ``_pair_stage``; keyed by batch size; ten fresh
+        output tensors).  The pool's three tensors are the plans' per-call inputs and the slot lists are per-call host lists, so
+        ANY pool of this shape and slot count, and any slots, replay the same plans: same launches, same arguments as the direct
+        path.  Each recording is checked by one replay against what the recording call's direct launches produced, bit for bit; a
+        stage that cannot be recorded stays on direct launches.  What stays in Python per call: validation, the stale scan, the
+        split-K comparison (memoised), the ``pool.keys`` updates, the workspace LRU.  Direct launches throughout with plans off,
+        per-launch profiling (``ops.profile``), the checked build, a capturing stream and the ensemble.  ``plan_stats()`` counts.
 
         ``exact`` (default): bit-identity with ``forward`` holds for every size.  On small frames some launches of the frame stage
         split K by the number of rows they see (``_frame_stage_splitk``), i.e. by the number of frames in the batch; tokens are then
@@ -1129,20 +1194,23 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
         ops = self._ops(dev)
         self._reuse_first = False
         with torch.cuda.device(dev), torch.no_grad():
-            self._select_workspace((str(dev), (b, 3, H, W), bool(self.global_motion), bool(self.ensemble_global_motion)))
-            ims = self.buf("pool_im", 2 * b, 3, H, W)
-            ops.pool_blocks(pool.frames, left + right, ims)
-            im0, im1 = ims[:b], ims[b:]
+            wkey = (str(dev), (b, 3, H, W), bool(self.global_motion), bool(self.ensemble_global_motion))
+            self._select_workspace(wkey)                     # (a replay counts as a use for the workspace LRU)
             if self.global_motion and self.ensemble_global_motion:
-                return self._forward_on_device(ops, im0, im1)
+                self._plan_stats["pooled_pair"]["eager"] += 1
+                ims = self.buf("pool_im", 2 * b, 3, H, W)
+                ops.pool_blocks(pool.frames, left + right, ims)
+                return self._forward_on_device(ops, ims[:b], ims[b:])
             if hasattr(ops, "begin_forward"):
                 ops.begin_forward()
             self._rows_fit_planes = 2 * b * H * W < (1 << 26)
             P = self._prepare(ops)
+            planned = (self.use_plans and self._pooled_plans_on and isinstance(ops, HipOps) and ops.profile is None and not self._checked
+                       and not torch.cuda.is_current_stream_capturing())
+            if planned:
+                self._sync_plan_sig()
             glob = bool(self.global_motion)
-            C, cg = v.local_dim, v.global_dim
-            n_l, n_g = (H // 8) * (W // 8), (H // 16) * (W // 16)
-            target = self._frame_stage_splitk(ops, H, W, 2 * b) if exact else None
+            target = self._splitk_of(ops, H, W, 2 * b) if exact else None
             vkey = (self._prepared_sig, glob, self._precision, self._checked, getattr(ops, "attention_f16x3", None), self._rows_fit_planes,
                     target)
             stale = []
@@ -1151,28 +1219,130 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
                     stale.append(s)
             if stale:
                 f = run = len(stale)
-                while exact and run < 2 * b and self._frame_stage_splitk(ops, H, W, run) != target:
+                while exact and run < 2 * b and self._splitk_of(ops, H, W, run) != target:
                     run += 1
                 fe = run + (run & 1)
-                g = self.buf("pool_stale", fe, 3, H, W)
-                ops.pool_blocks(pool.frames, stale + stale[-1:] * (fe - f), g)
-                x0 = self.buf("pool_x0", fe, H, W, 4)
-                ops.pack_frames(g[:fe // 2], g[fe // 2:], x0)
-                t_l, t_g = self._frame_stage(ops, P, x0[:run], "fp", "fpl", glob)
-                ops.pool_blocks(pool.tokens_l, stale, t_l[:f * n_l], to_pool=True)
-                if glob:
-                    ops.pool_blocks(pool.tokens_g, stale, t_g[:f * n_g], to_pool=True)
+                key = ("pooled_frame", f, run, pool.slots, self._rows_fit_planes) + self._mode_fields(ops) + (wkey,)
+                self._pooled_stage("pooled_frame", key if planned else None, ops, pool,
+                                   {"stale_padded": stale + stale[-1:] * (fe - f), "stale": stale},
+                                   lambda: self._pooled_frame_stage(ops, P, pool, stale, run, glob))
                 for s in stale:
                     pool.keys[s] = vkey
-            feat = self.buf("lfnorm", 2 * b * n_l, C)
-            ops.pool_blocks(pool.tokens_l, left + right, feat)
-            gtok = None
-            if glob:
-                gtok = self.buf("gfnorm", 2 * b * n_g, cg)
-                ops.pool_blocks(pool.tokens_g, left + right, gtok)
-            pyr_st = [None] + [self.buf(f"pyr_{l}", 2 * b, 3, H >> l, W >> l) for l in range(1, 4)]
-            ops.image_pyramid(im0, im1, pyr_st[1], pyr_st[2], pyr_st[3])
-            return self._pair_stage(ops, P, im0, im1, pyr_st, feat, gtok)
+            key = ("pooled_pair", pool.slots, self._rows_fit_planes) + self._mode_fields(ops) + (wkey,)
+            return self._pooled_stage("pooled_pair", key if planned else None, ops, pool, {"pairs": left + right},
+                                      lambda: self._pooled_pair_stage(ops, P, pool, left, right, glob))
+
+    def _splitk_of(self, ops, H: int, W: int, f: int) -> Tuple:
+        """``_frame_stage_splitk``, remembered: a function of the size, the frame count and the mode (never of the weights' values), and
+        ``forward_pooled`` asks it up to 2B times per call."""
+        key = (H, W, f, id(ops), self._rows_fit_planes, getattr(ops, "gemm_workspace", None) is None) + self._mode_fields(ops)
+        got = self._splitk_memo.get(key)
+        if got is None:
+            if len(self._splitk_memo) > 512:
+                self._splitk_memo.clear()
+            got = self._splitk_memo[key] = self._frame_stage_splitk(ops, H, W, f)
+        return got
+
+    def _pooled_frame_stage(self, ops, P, pool, stale, run: int, glob: bool):
+        """The frame stage of ``forward_pooled``: the ``stale`` slots' frames (filled up to ``run``, and to an even count for
+        ``pack_frames``, with repeats of the last) through ``_frame_stage``; the tokens of the distinct ones go back into the pool.
+        Slot lists carry roles: a launch plan rewrites them per replay.  Writes into the pool only; returns None."""
+        H, W = pool.hp, pool.wp
+        f = len(stale)
+        fe = run + (run & 1)
+        n_l, n_g = (H // 8) * (W // 8), (H // 16) * (W // 16)
+        g = self.buf("pool_stale", fe, 3, H, W)
+        ops.pool_blocks(pool.frames, stale + stale[-1:] * (fe - f), g, role="stale_padded")
+        x0 = self.buf("pool_x0", fe, H, W, 4)
+        ops.pack_frames(g[:fe // 2], g[fe // 2:], x0)
+        t_l, t_g = self._frame_stage(ops, P, x0[:run], "fp", "fpl", glob)
+        ops.pool_blocks(pool.tokens_l, stale, t_l[:f * n_l], to_pool=True, role="stale")
+        if glob:
+            ops.pool_blocks(pool.tokens_g, stale, t_g[:f * n_g], to_pool=True, role="stale")
+
+    def _pooled_pair_stage(self, ops, P, pool, left, right, glob: bool):
+        """The pair stage of ``forward_pooled``: frames and tokens of the pairs gathered from the pool (role "pairs"), the image
+        pyramid, ``_pair_stage``.  Returns the forward's dict of fresh tensors."""
+        b = len(left)
+        H, W = pool.hp, pool.wp
+        v = self._v
+        n_l, n_g = (H // 8) * (W // 8), (H // 16) * (W // 16)
+        ims = self.buf("pool_im", 2 * b, 3, H, W)
+        ops.pool_blocks(pool.frames, left + right, ims, role="pairs")
+        im0, im1 = ims[:b], ims[b:]
+        feat = self.buf("lfnorm", 2 * b * n_l, v.local_dim)
+        ops.pool_blocks(pool.tokens_l, left + right, feat, role="pairs")
+        gtok = None
+        if glob:
+            gtok = self.buf("gfnorm", 2 * b * n_g, v.global_dim)
+            ops.pool_blocks(pool.tokens_g, left + right, gtok, role="pairs")
+        pyr_st = [None] + [self.buf(f"pyr_{l}", 2 * b, 3, H >> l, W >> l) for l in range(1, 4)]
+        ops.image_pyramid(im0, im1, pyr_st[1], pyr_st[2], pyr_st[3])
+        return self._pair_stage(ops, P, im0, im1, pyr_st, feat, gtok)
+
+    def _pooled_stage(self, kind: str, key, ops, pool, lists, body):
+        """One stage of ``forward_pooled`` by ``forward``'s rules: the first two calls of a key run ``body`` (direct launches), the third
+        records it, later ones replay the plan with the pool's tensors as inputs and ``lists`` as slot lists.  ``key`` None: not
+        plannable now (plans off, profiling, the checked build, stream capture)."""
+        st = self._plan_stats[kind]
+        ent = False if key is None else self._pool_plans.get(key, 0)
+        if ent is False:
+            st["eager"] += 1
+            return body()
+        if isinstance(ent, int):
+            if ent < 2:                                      # the first two calls build the workspace, maps, kernel attributes
+                self._pool_plans[key] = ent + 1
+                st["eager"] += 1
+                return body()
+            return self._record_pooled(kind, key, ops, pool, lists, body)
+        inputs = (pool.frames, pool.tokens_l, pool.tokens_g)
+        if tuple(t.data_ptr() & 15 for t in inputs) != ent.align:
+            st["eager"] += 1                                 # kernel choices were made for the recording pool's alignment
+            return body()
+        st["replayed"] += 1
+        return ent.run(inputs, ops.device, ops._stream(), lists=lists)
+
+    def _record_pooled(self, kind: str, key, ops, pool, lists, body):
+        import warnings
+        st = self._plan_stats[kind]
+        inputs = (pool.frames, pool.tokens_l, pool.tokens_g)
+        try:
+            ops.begin_plan(inputs)
+            out = body()
+            plan = ops.end_plan(out)
+        except PlanUnsupported:
+            ops.abort_plan()
+            self._pool_plans[key] = False
+            st["refused"] += 1
+            return body()
+        except Exception:
+            ops.abort_plan()
+            raise
+        # Record-time self-check, as for forward: one replay must reproduce what the recording call's direct launches produced, bit for
+        # bit.  Pair stage: into NaN-filled outputs, against the recording call's dict.  Frame stage (no outputs; it writes the stale
+        # slots' tokens into the pool): keep those tokens, fill the slots with NaN, replay, compare -- and put the kept ones back if
+        # the replay wrote anything else.
+        if kind == "pooled_pair":
+            ok = self._same_results(out, plan.run(inputs, ops.device, ops._stream(), poison=True, lists=lists))
+        else:
+            idx = torch.tensor(lists["stale"], device=pool.frames.device)
+            toks = [pool.tokens_l] + ([pool.tokens_g] if self.global_motion else [])
+            kept = [t.index_select(0, idx) for t in toks]
+            for t in toks:
+                t.index_fill_(0, idx, float("nan"))
+            plan.run(inputs, ops.device, ops._stream(), lists=lists)
+            ok = all(bool(torch.equal(t.index_select(0, idx), k)) for t, k in zip(toks, kept))
+            if not ok:
+                for t, k in zip(toks, kept):
+                    t.index_copy_(0, idx, k)
+        if ok:
+            self._pool_plans[key] = plan
+            st["recorded"] += 1
+        else:
+            warnings.warn(f"atm-vfi_amd: a recorded launch plan ({kind}) did not reproduce its own stage; this key stays on direct launches")
+            self._pool_plans[key] = False
+            st["refused"] += 1
+        return out
 
     def _frame_stage(self, ops, P, x0, tag: str, ltag: str, glob: bool):
         """Everything ``forward`` computes PER FRAME, on the F NHWC4-packed frames ``x0`` [F,H,W,4]: shared_feat_extraction, the

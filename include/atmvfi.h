@@ -613,6 +613,12 @@ int atmvfi_ssim_psnr(const void* x, int64_t x_bstride, int64_t x_cstride, int64_
  * and then issues the ops in order on `stream`, stopping at the first failure (*failed_op = its index; the return value and
  * atmvfi_last_error() are that op's).  Nothing is cached inside the library: the plan is the caller's array.
  * atmvfi_plan_fn_id(name) gives the `fn` of an entry point by name (-1 if it is not a launch entry point).
+ *
+ * Host integer lists.  atmvfi_pool_blocks takes its slot list as a HOST array: a recorded op holds that array's address, and the
+ * entry point reads, validates (range, duplicates of a scatter) and copies the `n` values into the kernel arguments at LAUNCH time,
+ * i.e. inside atmvfi_plan_run().  This is a contract: the owner of a plan may rewrite the values of such an array between two
+ * atmvfi_plan_run() calls (its address and length are fixed by the recording) and each replay moves the slots named at that moment;
+ * nothing of an earlier replay is remembered.  The array must stay alive as long as the plan, like a parameter block.
  * ---------------------------------------------------------------------------------- */
 typedef union atmvfi_plan_arg { uint64_t u; int64_t i; double f; } atmvfi_plan_arg;
 #define ATMVFI_PLAN_MAX_ARGS 28

@@ -3,10 +3,15 @@
 
 End to end: ``interpolate_video_nx`` on uint8 frames in host memory, network_base, global branch on, ``factor`` 4 and 8, at 480x832
 (``divisor=None``, the DAVIS size of benchmark/davis-vid.py) and 1080x1920 (padded to 1088x1920), for ``pool=False`` (plain forwards on
-launch plans: what a caller composing ``Network.forward`` gets), ``pool=True, max_batch=1`` and ``pool=True, max_batch=4``.  Device events
-around the steady state of one video: the first ``--warm`` segments (workspaces, launch plans, pool) are not timed, the next
-``--segments`` are; output frames/s = N x segments / time.  Every configuration is timed ``--repeats`` times in rotation (median, min-max:
-the spread is the noise a difference has to exceed).  Also printed: frames through ``stem_fused`` per steady-state segment.
+launch plans: what a caller composing ``Network.forward`` gets), ``pool=True, max_batch=1`` and ``pool=True, max_batch=4``, the last two
+also with the pooled launch plans off (``forward_pooled`` on direct launches, the behaviour before it was planned; a tool-only switch
+on the model, not a selection).  Device events around the steady state of one video: the first ``--warm`` segments (workspaces, pool)
+are not timed, the next ``--segments`` are; output frames/s = N x segments / time.  Before anything is timed every mode runs the video
+once untimed (``--prime``): a launch plan is recorded by the third call of its key and a key of the steady state first occurs in the
+second segment, so the recordings would otherwise fall into the first repeat's timed segments.  Every configuration is timed
+``--repeats`` times in rotation (median, min-max: the spread is the noise a difference has to exceed).  Also printed: frames through
+``stem_fused`` per steady-state segment, and ``Network.plan_stats()`` of the mode's timed runs (a steady state that still records or
+runs eagerly shows there).
 
 Kernels alone: ``pool_blocks`` (gather of 8 frame / local-token / global-token blocks of a 1088x1920 base pool, and a scatter) and
 ``tta_merge`` / ``frame_rot180`` on 1088x1920 frames, in GB/s of bytes read + written beside the 6.3 TB/s streaming ceiling; the calls
@@ -35,8 +40,9 @@ hip_ops = importlib.import_module("atm-vfi_amd.hip_ops")
 mf = importlib.import_module("atm-vfi_amd.multiframe")
 scene = importlib.import_module("atm-vfi_amd.scene")
 HBM = 6.3e12
-MODES = (("pool=False", dict(pool=False, max_batch=4)), ("pool=True mb=1", dict(pool=True, max_batch=1)),
-         ("pool=True mb=4", dict(pool=True, max_batch=4)))
+MODES = (("pool=False", dict(pool=False, max_batch=4)),
+         ("pool=True mb=1 plans off", dict(pool=True, max_batch=1, pooled_plans=False)), ("pool=True mb=1", dict(pool=True, max_batch=1)),
+         ("pool=True mb=4 plans off", dict(pool=True, max_batch=4, pooled_plans=False)), ("pool=True mb=4", dict(pool=True, max_batch=4)))
 
 
 def timed(fn, iters, warm=8):
@@ -59,23 +65,40 @@ def video(n, h, w, seed=0):
 
 
 def run_video(net, frames, factor, warm, segments, divisor, **kw):
-    """-> (ms of the timed segments, frames produced in them)."""
+    """-> (ms of the timed segments, frames produced in them).  ``pooled_plans=False`` among ``kw``: forward_pooled on direct launches."""
     s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     got = 0
-    for k, _ in enumerate(mf.interpolate_video_nx(iter(frames), net, factor=factor, divisor=divisor, **kw)):
-        if k == warm * factor:
-            torch.cuda.synchronize()
-            s.record()
-        got = k
-    e.record()
-    e.synchronize()
+    kw = dict(kw)
+    net._pooled_plans_on = kw.pop("pooled_plans", True)
+    try:
+        for k, _ in enumerate(mf.interpolate_video_nx(iter(frames), net, factor=factor, divisor=divisor, **kw)):
+            if k == warm * factor:
+                torch.cuda.synchronize()
+                s.record()
+            got = k
+        e.record()
+        e.synchronize()
+    finally:
+        net._pooled_plans_on = True
     assert got == (warm + segments) * factor
     assert kw.get("scene") is None or kw["scene"].cuts == [], "the benchmark video must be cut-free"
     return s.elapsed_time(e), segments * factor
 
 
+def add_stats(total, before, after):
+    """``total`` + (``after`` - ``before``) of two ``Network.plan_stats()`` readings."""
+    return {kind: {k: (total[kind][k] if total else 0) + v - before[kind][k] for k, v in c.items()} for kind, c in after.items()}
+
+
+def show_stats(stats):
+    """eager/recorded/replayed/refused per kind, kinds without a call left out."""
+    return "; ".join(f"{kind} {c['eager']}e/{c['recorded']}rec/{c['replayed']}rep/{c['refused']}ref" for kind, c in stats.items()
+                     if any(c.values())) or "-"
+
+
 def stem_per_segment(net, ops, frames, factor, divisor, **kw):
     counts = []
+    kw = {k: v for k, v in kw.items() if k != "pooled_plans"}       # (profiling takes the direct launches anyway)
     ops.profile = []
     try:
         for k, _ in enumerate(mf.interpolate_video_nx(iter(frames[:4]), net, factor=factor, divisor=divisor, **kw)):
@@ -125,6 +148,7 @@ def main():
     ap.add_argument("--segments", type=int, default=4)
     ap.add_argument("--warm", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--prime", type=int, default=1, help="untimed runs of the video per mode before the timed rotation")
     ap.add_argument("--iters", type=int, default=60)
     ap.add_argument("--buffers", type=int, default=12)
     ap.add_argument("--kernels-only", action="store_true")
@@ -155,17 +179,25 @@ def main():
             frames = video(a.warm + a.segments + 1, h, w)
             for factor in (int(x) for x in a.factors.split(",")):
                 times = {name: [] for name, _ in modes}
+                stats = {name: None for name, _ in modes}
+                for _ in range(a.prime):              # every key of the steady state recorded before anything is timed
+                    for name, kw in modes:
+                        run_video(net, frames, factor, a.warm, a.segments, divisor, **kw)
                 for _ in range(a.repeats):            # in rotation: pool=False is the baseline of the same process and run
                     for name, kw in modes:
+                        before = net.plan_stats()
                         ms, n = run_video(net, frames, factor, a.warm, a.segments, divisor, **kw)
                         times[name].append(n / (ms * 1e-3))
+                        stats[name] = add_stats(stats[name], before, net.plan_stats())
                 for name, kw in modes:
                     t = times[name]
                     row = {"size": size, "factor": factor, "mode": name, "fps_median": statistics.median(t), "fps_min": min(t), "fps_max": max(t),
-                           "stem_frames_per_segment": stem_per_segment(net, ops, frames, factor, divisor, **kw), "repeats_fps": t}
+                           "stem_frames_per_segment": stem_per_segment(net, ops, frames, factor, divisor, **kw), "repeats_fps": t,
+                           "plan_stats": stats[name]}
                     result["videos"].append(row)
-                    print(f"{size:>10} {factor}x {name:>22}: {row['fps_median']:8.2f} output frames/s (min {min(t):.2f}, max {max(t):.2f} over "
-                          f"{len(t)} repeats)  stem_fused frames / segment {row['stem_frames_per_segment']}", flush=True)
+                    print(f"{size:>10} {factor}x {name:>24}: {row['fps_median']:8.2f} output frames/s (min {min(t):.2f}, max {max(t):.2f} over "
+                          f"{len(t)} repeats)  stem_fused frames / segment {row['stem_frames_per_segment']}  plans {show_stats(stats[name])}",
+                          flush=True)
                 net.release_workspace()
     if a.json:
         with open(a.json, "w") as f:
