@@ -139,6 +139,7 @@ SIGNATURES = {
     "atmvfi_frame_difference_workspace_ints": (c_l, [c_i, c_i]),
     "atmvfi_frame_difference": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_l, c_f]),
     "atmvfi_yuv420_to_rgb": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_f, c_i, c_i, c_i, c_i, c_f]),
+    "atmvfi_yuv420_window": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f, c_f]),
     "atmvfi_rgb_to_yuv420": (c_i, [c_f, c_i, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f]),
     "atmvfi_yuv420p10_to_f32": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f]),
     "atmvfi_f32_to_yuv420p10": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f]),
@@ -1358,6 +1359,32 @@ class HipOps:
         meta = {"bytes": float(fmt.frame_bytes) + (12.0 * hp * wp if dst is not None else 0.0) + (3.0 * h * w if dst_u8 is not None else 0.0)}
         self._run("yuv420_to_rgb", meta, self.lib.atmvfi_yuv420_to_rgb, _ptr(yuv), h, w, int(fmt.depth), fmt.matrix_id, int(fmt.full_range),
                   fmt.siting_id, _ptr(dst_u8), int(bool(bgr)), _ptr(dst), hp, wp, int(pad_top), int(pad_left), self._stream())
+
+    def yuv420_window(self, yuv, fmt, mode: int, y0: int, x0: int, h: int, w: int, dst=None, dst_u8=None, pad_top: int = 0,
+                      pad_left: int = 0):
+        """One packed planar I420 frame of ``fmt`` (as for ``yuv420_to_rgb``) -> what ``frame_u8_window(mode, y0, x0, h, w)`` makes of
+        that frame's RGB decode, in one launch and without the RGB frame: ``dst`` fp32 planar [3,Hp,Wp] (q / 255, replicate padding, the
+        window at (pad_top, pad_left)) and / or ``dst_u8`` uint8 [h,w,3] RGB.  The origin must be even (include/atmvfi.h
+        atmvfi_yuv420_window; the bits of ``yuv.window_numpy``)."""
+        fh, fw = fmt.height, fmt.width
+        if yuv.dtype != torch.uint8 or yuv.dim() != 1 or yuv.numel() != fmt.frame_bytes or not yuv.is_contiguous() or not yuv.is_cuda:
+            raise ValueError(f"yuv420_window: source must be a contiguous CUDA uint8 tensor of {fmt.frame_bytes} bytes ({fh} x {fw} I420)")
+        if dst is None and dst_u8 is None:
+            raise ValueError("yuv420_window: give dst, dst_u8 or both")
+        if int(y0) % 2 or int(x0) % 2:
+            raise ValueError(f"yuv420_window: the window origin ({y0}, {x0}) must be even for 4:2:0 frames")
+        if dst is not None and (dst.dtype != torch.float32 or dst.dim() != 3 or dst.shape[0] != 3 or not dst.is_contiguous() or not dst.is_cuda):
+            raise ValueError("yuv420_window: dst must be a contiguous CUDA fp32 [3,Hp,Wp] tensor")
+        if dst_u8 is not None and (dst_u8.dtype != torch.uint8 or tuple(dst_u8.shape) != (h, w, 3) or not dst_u8.is_contiguous()
+                                   or not dst_u8.is_cuda):
+            raise ValueError(f"yuv420_window: dst_u8 must be a contiguous CUDA uint8 [{h},{w},3] tensor")
+        hp, wp = (dst.shape[1], dst.shape[2]) if dst is not None else (h + pad_top, w + pad_left)
+        scale = 2 if mode == 1 else 1
+        meta = {"bytes": 1.5 * (2 if fmt.depth == 10 else 1) * scale * scale * h * w + (12.0 * hp * wp if dst is not None else 0.0)
+                + (3.0 * h * w if dst_u8 is not None else 0.0)}
+        self._run("yuv420_window", meta, self.lib.atmvfi_yuv420_window, _ptr(yuv), fh, fw, int(fmt.depth), fmt.matrix_id, int(fmt.full_range),
+                  fmt.siting_id, int(mode), int(y0), int(x0), int(h), int(w), _ptr(dst), hp, wp, int(pad_top), int(pad_left), _ptr(dst_u8),
+                  self._stream())
 
     def rgb_to_yuv420(self, yuv, fmt, src_u8=None, src=None, pad_top: int = 0, pad_left: int = 0, bgr: bool = False):
         """``src_u8`` uint8 [H,W,3] (BGR if ``bgr``) or ``src`` fp32 planar RGB [3,Hp,Wp] with the frame at (pad_top, pad_left) --

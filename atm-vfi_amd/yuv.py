@@ -185,6 +185,51 @@ def decode_numpy(buf, fmt: Format, bgr: bool = False) -> np.ndarray:
     return np.clip(np.stack([b, g, r] if bgr else [r, g, b], axis=-1), 0, 255).astype(np.uint8)
 
 
+def window_numpy(buf, fmt: Format, mode: int, y0: int, x0: int, h: int, w: int) -> np.ndarray:
+    """Packed I420 frame -> uint8 [h,w,3] RGB: the bits of ``atmvfi_yuv420_window``'s ``dst_u8`` -- ``mode`` 0: the h x w window at
+    (y0, x0) of ``decode_numpy``'s frame; ``mode`` 1: the 2x area reduction ``(a + b + c + d + 2) >> 2`` of its 2h x 2w window there
+    (each pixel clipped to 8 bits first).  The window is a window of the whole frame's decode: chroma neighbours are the frame's.
+    Even origin, as ``crop``.  Only the window is decoded."""
+    mode, y0, x0, h, w = int(mode), int(y0), int(x0), int(h), int(w)
+    if mode not in (0, 1):
+        raise ValueError(f"window_numpy: unknown mode {mode} (0: crop, 1: area 2x)")
+    if y0 % 2 or x0 % 2:
+        raise ValueError(f"window_numpy: the window origin ({y0}, {x0}) must be even for 4:2:0 frames")
+    s = 2 if mode == 1 else 1
+    H, W = fmt.height, fmt.width
+    if y0 < 0 or x0 < 0 or h < 1 or w < 1 or y0 + s * h > H or x0 + s * w > W:
+        raise ValueError(f"window_numpy: window outside the frame (mode {mode} reads {s * h} x {s * w} source pixels at ({y0}, {x0}) of a "
+                         f"{H} x {W} frame)")
+    Y, U, V = (p.astype(np.int32) for p in fmt.planes(buf))
+    ch, cw = fmt.chroma_shape
+    ys, xs = np.arange(y0, y0 + s * h), np.arange(x0, x0 + s * w)
+    r0 = ys >> 1
+    r1 = np.clip(r0 + np.where(ys & 1, 1, -1), 0, ch - 1)
+    q0 = xs >> 1
+    if fmt.siting == "left":
+        q1 = np.minimum(q0 + 1, cw - 1)
+        wx0 = np.where(xs & 1, 2, 4).astype(np.int32)
+    else:
+        q1 = np.clip(q0 + np.where(xs & 1, 1, -1), 0, cw - 1)
+        wx0 = np.full(s * w, 3, np.int32)
+    wx1 = 4 - wx0
+
+    def up(c):
+        return (3 * (wx0 * c[r0][:, q0] + wx1 * c[r0][:, q1]) + (wx0 * c[r1][:, q0] + wx1 * c[r1][:, q1]) + 8) >> 4
+
+    (kY, kRV, kGU, kGV, kBU), _ = COEFFS[fmt.matrix, fmt.full_range]
+    if fmt.depth == 10:
+        yo, mid, T = 64, 512, 16
+    else:
+        yo, mid, T = (0 if fmt.full_range else 16), 128, 14
+    y, u, v = kY * (Y[y0:y0 + s * h, x0:x0 + s * w] - yo), up(U) - mid, up(V) - mid
+    half = 1 << (T - 1)
+    q = np.clip(np.stack([(y + kRV * v + half) >> T, (y + kGU * u + kGV * v + half) >> T, (y + kBU * u + half) >> T], axis=-1), 0, 255)
+    if mode == 1:
+        q = (q[0::2, 0::2] + q[0::2, 1::2] + q[1::2, 0::2] + q[1::2, 1::2] + 2) >> 2
+    return np.ascontiguousarray(q.astype(np.uint8))
+
+
 def decode_numpy_f32(buf, fmt: Format, window=None) -> np.ndarray:
     """Packed 10-bit I420 frame -> fp32 [h,w,3] RGB = q / 1023, the depth kept: the bits of ``atmvfi_yuv420p10_to_f32`` (without
     padding).  ``window=(y0, x0, h, w)`` (even origin, as ``crop``): that window of the whole frame's decode -- chroma neighbours
@@ -369,6 +414,35 @@ class Y4MReader:
             if len(data) != n:
                 raise ValueError(f"Y4MReader: truncated frame ({len(data)} of {n} bytes)")
             yield np.frombuffer(data, dtype="<u2" if self.fmt.depth == 10 else np.uint8).astype(self.fmt.dtype, copy=True)
+
+    def skip(self, count: int) -> int:
+        """Pass over the next ``count`` frames without delivering them: a seek per frame when the stream is seekable, read and dropped
+        otherwise.  Returns how many were there to skip (fewer than ``count`` at the end of the stream)."""
+        n, done = self.fmt.frame_bytes, 0
+        end = None
+        if self._data0 is not None:
+            pos = self.f.tell()
+            end = self.f.seek(0, os.SEEK_END)
+            self.f.seek(pos)
+        while done < count:
+            line = self._line()
+            if not line:
+                break
+            if not line.startswith(b"FRAME"):
+                raise ValueError(f"Y4MReader: FRAME marker expected, got {line[:16]!r}")
+            if end is not None:
+                if self.f.tell() + n > end:
+                    raise ValueError(f"Y4MReader: truncated frame ({end - self.f.tell()} of {n} bytes)")
+                self.f.seek(n, os.SEEK_CUR)
+            else:
+                left = n
+                while left:
+                    got = len(self.f.read(min(left, 1 << 22)))
+                    if not got:
+                        raise ValueError(f"Y4MReader: truncated frame ({n - left} of {n} bytes)")
+                    left -= got
+            done += 1
+        return done
 
     def close(self):
         if self._own:

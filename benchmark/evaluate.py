@@ -6,10 +6,13 @@
                                  [--global-motion on|off] [--json OUT]
     python benchmark/evaluate.py --dataset snufilm --path DIR/eval_modes --img-data-path DIR/ --ckpt FILE
     python benchmark/evaluate.py --dataset xiph --path ROOT --ckpt FILE [--categories resized-2k,cropped-4k] [--clips A,B] [--frames 2:99:2] [--timings]
+                                 [--source auto|png|y4m] [--matrix auto|bt601|bt709]
 
 Prints ``Avg PSNR: … SSIM: …`` per dataset (per level for SNU-FILM, per category with its name in front for Xiph), as the reference's
-scripts do.  Xiph: ROOT/<clip>/001.png … 099.png, 4096 x 2160 (the script's ffmpeg download is not reproduced); the means are over all
-samples of a category (the script's progress bar shows a mean that lags by one sample)."""
+scripts do.  Xiph: ROOT/<clip>/001.png … 099.png, 4096 x 2160 (the script's ffmpeg download is not reproduced), or the clip as the
+4:2:0 Y4M file it is distributed as -- ROOT/<clip>.y4m or ROOT/Netflix_<clip>_4096x2160_60fps_10bit_420.y4m -- read without ffmpeg and
+converted on the GPU by this project's own colour conversion (--source auto: the directory when it exists, the Y4M file otherwise);
+the means are over all samples of a category (the script's progress bar shows a mean that lags by one sample)."""
 import argparse
 import json
 import os
@@ -30,6 +33,9 @@ def main(argv=None):
     ap.add_argument("--categories", default=None, help="Xiph: comma-separated subset of resized-2k,cropped-4k")
     ap.add_argument("--clips", default=None, help="Xiph: comma-separated clip directories under --path (default: the script's eight)")
     ap.add_argument("--frames", default="2:99:2", help="Xiph: middle frames as FIRST:STOP[:STEP] (a Python range; default: the script's 2:99:2)")
+    ap.add_argument("--source", choices=("auto", "png", "y4m"), default="auto",
+                    help="Xiph: a clip's frames from ROOT/<clip>/NNN.png, from its Y4M file, or (auto) the directory when it exists")
+    ap.add_argument("--matrix", choices=("auto", "bt601", "bt709"), default="auto", help="Xiph, Y4M clips: the colour matrix (auto: bt709 from 720 rows up)")
     ap.add_argument("--timings", action="store_true", help="Xiph: print the wall time split into decode, upload, prepare, forward, metric")
     ap.add_argument("--ckpt", required=True)
     ap.add_argument("--model", choices=("base", "lite"), default="base")
@@ -54,10 +60,11 @@ def main(argv=None):
             frames = range(*(int(v) for v in a.frames.split(":")))
         except (TypeError, ValueError):
             ap.error(f"--frames: expected FIRST:STOP[:STEP], got {a.frames!r}")
-        xiph_kw = {"categories": cats, "clips": tuple(a.clips.split(",")) if a.clips else ev.XIPH_CLIPS, "frames": frames}
+        xiph_kw = {"categories": cats, "clips": tuple(a.clips.split(",")) if a.clips else ev.XIPH_CLIPS, "frames": frames,
+                   "source": a.source, "matrix": a.matrix}
         try:
-            samples = ev.xiph(a.path, xiph_kw["clips"], frames)
-        except FileNotFoundError as e:
+            samples, _ = ev.xiph_samples(a.path, xiph_kw["clips"], frames, a.source)
+        except (FileNotFoundError, ValueError) as e:
             ap.error(f"--path {a.path}: {e}")
     elif a.dataset == "snufilm":
         if a.img_data_path is None:
@@ -76,9 +83,10 @@ def main(argv=None):
     t0 = time.time()
     progress = lambda d, n, p, s: print(f"{d}/{n}  PSNR {p:.4f}  SSIM {s:.5f}", flush=True)        # noqa: E731
     timings = {} if a.timings else None
+    sources = {}
     if xiph_kw is not None:
         res = ev.evaluate_xiph(model, a.path, tta=a.tta, streams=a.streams, limit=a.limit, global_motion=gm, progress=progress,
-                               timings=timings, **xiph_kw)
+                               timings=timings, sources=sources, **xiph_kw)
     else:
         res = ev.evaluate(model, samples, a.dataset, tta=a.tta, streams=a.streams, limit=a.limit, global_motion=gm, progress=progress)
     print(ev.format_levels(res))
@@ -88,8 +96,11 @@ def main(argv=None):
               ("decode_wait", "decode_cpu", "upload", "prepare", "forward", "metric")))
     if a.json:
         with open(a.json, "w") as f:
-            json.dump({"dataset": a.dataset, "model": a.model, "tta": a.tta, "global_motion": model.global_motion,
-                       "levels": res.levels, "records": res.records}, f, indent=1)
+            out = {"dataset": a.dataset, "model": a.model, "tta": a.tta, "global_motion": model.global_motion,
+                   "levels": res.levels, "records": res.records}
+            if xiph_kw is not None:
+                out["sources"] = sources
+            json.dump(out, f, indent=1)
     return res
 
 

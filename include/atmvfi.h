@@ -524,6 +524,30 @@ int atmvfi_yuv420_to_rgb(const void* yuv, int H, int W, int depth, int matrix, i
 int atmvfi_rgb_to_yuv420(const void* src_u8, int bgr, const float* src, int Hp, int Wp, int pad_top, int pad_left, int H, int W,
                          int matrix, int full_range, int siting, void* yuv, void* stream);
 
+/* One resident packed I420 frame -> the window of atmvfi_frame_u8_window, without the RGB frame in between (yuv_window.hip; ABI 0.17;
+ * the Xiph 2K / 4K evaluation on Y4M clips, atm-vfi_amd/evaluate.py; host twin yuv.window_numpy).  Nothing of the reference: its script
+ * converts the clips to rgb24 PNGs with ffmpeg first.  The frame layout, depth 8 / 10 (10-bit samples decode to clip8 RGB), matrix,
+ * full_range and siting are exactly those of atmvfi_yuv420_to_rgb.  No new arithmetic: let q(Y, X) be the clip8 RGB pixel that
+ * atmvfi_yuv420_to_rgb gives at (Y, X) of the WHOLE H x W frame -- chroma neighbours clamp at the frame's edges, never at the window's --
+ *   mode 0 (crop):    out(y, x) = q(y0 + y, x0 + x);
+ *   mode 1 (area 2x): out(y, x) = (q(y0 + 2y, x0 + 2x) + q(y0 + 2y, x0 + 2x + 1) + q(y0 + 2y + 1, x0 + 2x) + q(y0 + 2y + 1, x0 + 2x + 1) + 2) >> 2
+ *                     per channel: the four pixels are clipped to 8 bits first and averaged then (an rgb24 picture, then cv2.INTER_AREA
+ *                     at an exact scale of 2, ties round up); the window covers 2h x 2w source pixels;
+ *   dst    (or NULL): fp32 planar RGB [3,Hp,Wp] = out / 255 with the bits of the fp32 division, the window at (pad_top, pad_left),
+ *                     replicate padding by clamping the output coordinate into the window (4-byte aligned; Hp, Wp and the padding are
+ *                     read only with dst);
+ *   dst_u8 (or NULL): uint8 [h,w,3] RGB, the same integer pixels, un-padded: the ground truth form atmvfi_ssim_psnr reads in place.
+ * Both are bit for bit atmvfi_frame_u8_window(mode, y0, x0, h, w, ...) of atmvfi_yuv420_to_rgb's dst_u8.
+ * Refused on the host before any launch (ATMVFI_EINVAL): a null source; both outputs NULL; H or W below 1, an unknown matrix, range,
+ * siting or depth; 10-bit full range; a mode other than 0 / 1; h, w < 1 or a negative origin; a window that leaves the frame (2h x 2w
+ * source pixels in mode 1); an odd y0 or x0 (an even origin keeps the two luma rows and columns of a chroma sample together, as
+ * yuv.crop requires); a canvas smaller than the window plus its padding.
+ * Any geometry and pointer alignment is accepted otherwise; dword Y loads, 16-byte plane stores and 12-byte RGB groups are used when the
+ * byte pointers are 4-byte and the fp32 pointer 16-byte aligned and W, x0, w, Wp and pad_left are multiples of 4.  Both paths give the
+ * same bits.  Every output byte is written by the call; vector stores only, no atomics, nothing pre-zeroed. */
+int atmvfi_yuv420_window(const void* yuv, int H, int W, int depth, int matrix, int full_range, int siting, int mode, int y0, int x0, int h,
+                         int w, float* dst, int Hp, int Wp, int pad_top, int pad_left, void* dst_u8, void* stream);
+
 /* The same frames with the 10-bit depth kept end to end (yuv10.hip; ABI 0.15): 10-bit limited-range I420 (little-endian uint16, values
  * 0..1023; frame layout, matrix and siting as above) <-> fp32 planar RGB in units of 1 / 1023.  The calls above decode 10-bit samples
  * to clip8 RGB and encode 8-bit frames only; these hand the network q / 1023 and write its prediction back as 10-bit samples.  The
