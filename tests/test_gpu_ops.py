@@ -237,8 +237,12 @@ def test_dwconv_gelu(shape, hip, cpu, dev):
 @pytest.mark.parametrize("shape", [(2, 34, 24, 192), (1, 17, 37, 448), (2, 16, 9, 64), (1, 32, 40, 128), (1, 24, 5, 64), (2, 19, 21, 320),
                                    (1, 11, 8, 64), (1, 8, 64, 64), (1, 136, 16, 1536)], ids=lambda s: "x".join(map(str, s)))
 def test_dwconv_gelu_dma_planes(shape, hip, dev):
-    """Plane sink only -> the LDS-DMA kernel (a private row ring per wave, counted vmcnt): strips of 17 / 16 / 8 rows that divide H, the
-    overlapping last strip when none does, x-groups cut by the image edge, W < 8.  Its
+    """Plane sink only -> the LDS-DMA kernel (a private row ring per wave, counted vmcnt): heights that 17, 16 or 8 divide, the
+    overlapping last strip when none does, x-groups cut by the image edge, W < 8.  On a 256-CU device every shape here runs the 8-ROW
+    instance: atmvfi_dwconv3x3_gelu drops to 8-row strips whenever N * strips * ceil(W / 8) * C / 32 < 8 * cu_count() = 2048 units
+    (pointwise.hip, "small maps: 8-row strips when the taller ones leave fewer than two waves per SIMD"), and the largest of these,
+    (1, 136, 16, 1536), has 8 * 2 * 48 = 768 with 17-row strips.  The 16- and 17-row instances (and the 16-row sliding window) are run
+    by tests/test_gpu_pointwise_fp64.py at the smallest shapes that reach them.  Its
     planes are the exact split of the sliding-window kernel's fp32 rows (same arithmetic in the same order), Inf in an edge column
     included (zero padding adds nothing: ADVICE round 4)."""
     n, h, w_, c = shape
