@@ -1,8 +1,31 @@
-// Device helpers of the planar YUV 4:2:0 decode, shared by yuv.hip (atmvfi_yuv420_to_rgb) and yuv_window.hip (atmvfi_yuv420_window):
-// the source frame's description, sample and chroma-segment loads, the chroma filter, the matrix, q / 255 and one whole pixel.  The
-// definition they implement is spelled out at the top of yuv.hip and in include/atmvfi.h; both files hold it to the same bits because
-// they run the same functions.
+// Planar YUV 4:2:0 (I420) <-> RGB at the host boundary of the video loops and of the Y4M evaluations: the definition, its device helpers
+// and the host-side checks, shared by yuv.hip (decode: atmvfi_yuv420_to_rgb, atmvfi_yuv420p10_to_f32, atmvfi_yuv420_window) and
+// yuv_encode.hip (atmvfi_rgb_to_yuv420, atmvfi_f32_to_yuv420p10); include/atmvfi.h declares them, atm-vfi_amd/yuv.py holds the numpy
+// twins.  Nothing of the reference: its scripts take PNGs.  The definition is the project's own, in int32 throughout (>> floors), so the
+// device, the vectorised numpy twins and the per-pixel models (tests/cpu_yuv.py, cpu_yuv10.py, cpu_yuv_window.py) agree bit for bit;
+// every kernel runs the functions below, so two entry points that decode the same pixel give the same bits by construction.
+//   frame     Y [H,W], U [ch,cw], V [ch,cw] back to back, ch = (H + 1) / 2, cw = (W + 1) / 2; uint8, or little-endian uint16 (0..1023)
+//             for depth 10
+//   pixel     8 bit (Px8): RGB 0..255 (top = 255), yo = 16 (limited) or 0 (full range), mid = 128, T = 14; fp32 is q / 255
+//             10 -> 8 bit (Px10to8): 10-bit limited-range samples to RGB 0..255 (decode only): yo = 64, mid = 512, T = 16, the 8-bit matrix
+//             10 bit kept (Px10): RGB 0..1023 (top = 1023), yo = 64, mid = 512, T = 14, the matrix of kCoeffs10; fp32 is q / 1023
+//   decode    chroma of luma pixel (y, x): rows r0 = y >> 1 and r1 = clamp(r0 + (y & 1 ? 1 : -1)) with weights (3, 1); columns
+//             centre-sited q0 = x >> 1, q1 = clamp(q0 + (x & 1 ? 1 : -1)), weights (3, 1); left-sited q0, q1 = min(q0 + 1, cw - 1),
+//             weights (4, 0) for even and (2, 2) for odd x; c' = (wy0 (wx0 c00 + wx1 c01) + wy1 (wx0 c10 + wx1 c11) + 8) >> 4;
+//             R = clip((kY y + kRV v + 2^(T-1)) >> T), G = clip((kY y + kGU u + kGV v + ..) >> T), B = clip((kY y + kBU u + ..) >> T)
+//             with y = Y - yo, u = U' - mid, v = V' - mid and clip to 0..top; the fp32 output is q / top with the bits of the fp32
+//             division.  A decode takes the window (y0, x0, h, w) of the frame (even origin) to (pad_top, pad_left) of the canvas,
+//             replicate padding by clamping the output coordinate INTO THE WINDOW; chroma neighbours clamp at the FRAME's edges: the
+//             window is a window of the whole frame's decode.
+//   encode    source pixel p: the uint8 RGB value, or from fp32 clip(rint(fl32(x * top))), half to even (frame_f32_to_u8's pixel);
+//             Y = clip(((eY . p + 2^13) >> 14) + yo); chroma sample (j, i) from the un-rounded sums s over rows 2j, min(2j + 1, H - 1) and
+//             columns 2i, min(2i + 1, W - 1) (centre, sh = 2) or max(2i - 1, 0), 2i, min(2i + 1, W - 1) weighted 1, 2, 1 (left, sh = 3):
+//             U = clip(((eU . s + 2^(13 + sh)) >> (14 + sh)) + mid), V alike
+// Library-wide rules, here as everywhere: vector stores only, no atomics, nothing pre-zeroed: every output byte is written by exactly
+// one lane.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace {
@@ -18,7 +41,6 @@ struct alignas(2) U16x1 {
 };
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-__device__ __forceinline__ int clip8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
 inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 
 // rint(c * 2^14) of the float64 matrices of (Kr, Kb) = (0.299, 0.114) / (0.2126, 0.0722), limited range scaled by 219 / 224
@@ -33,21 +55,39 @@ const Coeffs kCoeffs[2][2] = {      // [matrix][full_range]
     {{{19077, 29372, -3494, -8731, 34610}, {{2991, 10064, 1016}, {-1649, -5547, 7196}, {7196, -6536, -660}}},
      {{16384, 25802, -3069, -7670, 30402}, {{3483, 11718, 1183}, {-1877, -6315, 8192}, {8192, -7441, -751}}}},
 };
+// the same with the depth kept: luma scaled by 876 / 1023 and chroma by 896 / 1023 (yuv.py: COEFFS10; tests/test_yuv10_cpu.py holds
+// both to the table of the README and the header)
+const Coeffs kCoeffs10[2] = {     // [matrix]
+    {{19133, 26226, -6438, -13359, 33148}, {{4195, 8235, 1599}, {-2421, -4754, 7175}, {7175, -6008, -1167}}},
+    {{19133, 29459, -3504, -8757, 34711}, {{2983, 10034, 1013}, {-1644, -5531, 7175}, {7175, -6517, -658}}},
+};
 
-// the resident frame and the constants of its format: the first members of every decode kernel's arguments
+// ------------------------------------------------------------------------------------------------------------------ device: decode
+// the resident frame and the constants of its pixel: the first members of every decode kernel's arguments
 struct YuvSrc {
     const unsigned char* yuv;
     int H, W, ch, cw;
     long long uoff, voff;       // first U / V sample, in samples
     int kY, kRV, kGU, kGV, kBU, yo, mid, T;
 };
+// the pixel kind of a decode instance: the frame's sample depth and the RGB pixel's maximum.  A template parameter, not a member of
+// YuvSrc: with a constant maximum the clip is one v_med3_i32, and the decodes are bound by their instruction count.
+template <int DEPTH_, int TOP_>
+struct Pixel {
+    static constexpr int DEPTH = DEPTH_, TOP = TOP_;
+    static_assert((DEPTH == 8 || DEPTH == 10) && (TOP == 255 || (TOP == 1023 && DEPTH == 10)), "8 bit, 10 -> 8 bit or 10 bit kept");
+};
+using Px8 = Pixel<8, 255>;
+using Px10to8 = Pixel<10, 255>;
+using Px10 = Pixel<10, 1023>;
 
-inline YuvSrc make_src(const void* yuv, int H, int W, int depth, int matrix, int full_range) {
+// keep: the 10-bit depth kept (RGB 0..1023); otherwise RGB 0..255 from samples of either depth
+inline YuvSrc make_src(const void* yuv, int H, int W, int depth, int matrix, int full_range, bool keep) {
     const int ch = (H + 1) / 2, cw = (W + 1) / 2;
-    const Coeffs& c = kCoeffs[matrix][full_range];
+    const Coeffs& c = keep ? kCoeffs10[matrix] : kCoeffs[matrix][full_range];
     return YuvSrc{(const unsigned char*)yuv, H, W, ch, cw, (long long)H * W, (long long)H * W + (long long)ch * cw,
                   c.dec[0], c.dec[1], c.dec[2], c.dec[3], c.dec[4], depth == 10 ? 64 : (full_range ? 0 : 16), depth == 10 ? 512 : 128,
-                  depth == 10 ? 16 : 14};
+                  depth == 10 && !keep ? 16 : 14};
 }
 
 template <int DEPTH, bool AL>
@@ -57,53 +97,74 @@ __device__ __forceinline__ int sample(const unsigned char* p, long long i) {
     return (int)p[2 * i] | ((int)p[2 * i + 1] << 8);
 }
 
-// seg[k] = plane[r][clamp(q - 1 + k, 0, cw - 1)], k = 0..3: every chroma column that luma columns 2q .. 2q + 3 touch
-template <int DEPTH, bool AL>
-__device__ __forceinline__ void load_seg(const YuvSrc& a, long long plane, int r, int q, int seg[4]) {
+// the naturally aligned pair of samples (i, i + 1) of the aligned paths: two bytes or one dword
+template <int DEPTH>
+__device__ __forceinline__ void sample_pair(const unsigned char* p, long long i, int& s0, int& s1) {
+    if (DEPTH == 8) {
+        const unsigned v = reinterpret_cast<const U16x1*>(p + i)->v;
+        s0 = (int)(v & 0xffu);
+        s1 = (int)(v >> 8);
+    } else {
+        const unsigned v = *reinterpret_cast<const unsigned*>(p + 2 * i);
+        s0 = (int)(v & 0xffffu);
+        s1 = (int)(v >> 16);
+    }
+}
+
+// seg[k] = plane[r][clamp(q - 1 + k, 0, cw - 1)], k = 0 .. N - 1: every chroma column that luma columns 2q .. 2q + 2N - 5 touch
+// (N = 4: one group of four pixels; N = 6: two groups, seg + 2 being the second group's segment)
+template <int DEPTH, bool AL, int N = 4>
+__device__ __forceinline__ void load_seg(const YuvSrc& a, long long plane, int r, int q, int seg[N]) {
     const long long row = plane + (long long)r * a.cw;
-    if (AL) {       // q even and cw even: (q, q + 1) is a naturally aligned pair inside the row
+    if (AL) {       // q even and cw even: the columns q .. q + N - 3 are naturally aligned pairs inside the row
         seg[0] = sample<DEPTH, true>(a.yuv, row + max(q - 1, 0));
-        if (DEPTH == 8) {
-            const unsigned v = reinterpret_cast<const U16x1*>(a.yuv + row + q)->v;
-            seg[1] = (int)(v & 0xffu);
-            seg[2] = (int)(v >> 8);
-        } else {
-            const unsigned v = *reinterpret_cast<const unsigned*>(a.yuv + 2 * (row + q));
-            seg[1] = (int)(v & 0xffffu);
-            seg[2] = (int)(v >> 16);
-        }
-        seg[3] = sample<DEPTH, true>(a.yuv, row + min(q + 2, a.cw - 1));
+#pragma unroll
+        for (int p = 0; p < N - 2; p += 2) sample_pair<DEPTH>(a.yuv, row + q + p, seg[1 + p], seg[2 + p]);
+        seg[N - 1] = sample<DEPTH, true>(a.yuv, row + min(q + N - 2, a.cw - 1));
     } else {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) seg[k] = sample<DEPTH, false>(a.yuv, row + clampi(q - 1 + k, 0, a.cw - 1));
+        for (int k = 0; k < N; ++k) seg[k] = sample<DEPTH, false>(a.yuv, row + clampi(q - 1 + k, 0, a.cw - 1));
     }
 }
 
 // q / 255 for an integer q in 0..255 with the bits of the fp32 division (what frame_u8_to_f32 computes): q * r with r = fl(1 / 255), then
 // one correction step in fused multiply-adds -- e = fl(q - 255 y), y + e r.  Equal to the division for all 256 values
 // (tests/test_yuv_cpu.py checks every one in exact rational arithmetic); four instructions where the division's expansion takes ten, and
-// this kernel is bound by its instruction count, not by HBM, while it divides (tools/bench_yuv.py).
+// the decode is bound by its instruction count, not by HBM, while it divides (tools/bench_yuv.py).
 __device__ __forceinline__ float q255(int q) {
     const float f = (float)q, r = 0x1.010102p-8f;
     const float y = f * r;
     return __fmaf_rn(__fmaf_rn(-255.0f, y, f), r, y);
+}
+// q / 1023 for q in 0..1023, the same way with r = fl(1 / 1023): equal to the division for all 1024 values (tests/test_yuv10_cpu.py)
+__device__ __forceinline__ float q1023(int q) {
+    const float f = (float)q, r = 0x1.00401p-10f;
+    const float y = f * r;
+    return __fmaf_rn(__fmaf_rn(-1023.0f, y, f), r, y);
+}
+// the pixel's maximum as a template parameter: the fp32 value of an integer pixel
+template <int TOP>
+__device__ __forceinline__ float unit(int q) {
+    return TOP == 255 ? q255(q) : q1023(q);
 }
 
 __device__ __forceinline__ int chroma_mix(int c00, int c01, int c10, int c11, int wx0, int wx1) {
     return (3 * (wx0 * c00 + wx1 * c01) + (wx0 * c10 + wx1 * c11) + 8) >> 4;
 }
 
-// (__mul24: the full-rate 24-bit multiply; coefficients are below 2^17 and samples below 2^16, so the low 32 bits are the product's)
+// (__mul24: the full-rate 24-bit multiply; coefficients are below 2^17 and samples below 2^14, so the low 32 bits are the product's)
+template <int TOP>
 __device__ __forceinline__ void to_rgb(const YuvSrc& a, int Y, int U, int V, int q[3]) {
     const int y = __mul24(a.kY, Y - a.yo), u = U - a.mid, v = V - a.mid, half = 1 << (a.T - 1);
-    q[0] = clip8((y + __mul24(a.kRV, v) + half) >> a.T);
-    q[1] = clip8((y + __mul24(a.kGU, u) + __mul24(a.kGV, v) + half) >> a.T);
-    q[2] = clip8((y + __mul24(a.kBU, u) + half) >> a.T);
+    q[0] = clampi((y + __mul24(a.kRV, v) + half) >> a.T, 0, TOP);
+    q[1] = clampi((y + __mul24(a.kGU, u) + __mul24(a.kGV, v) + half) >> a.T, 0, TOP);
+    q[2] = clampi((y + __mul24(a.kBU, u) + half) >> a.T, 0, TOP);
 }
 
 // one frame pixel, every sample loaded on its own (the general path)
-template <int DEPTH, bool LEFT>
+template <class PX, bool LEFT>
 __device__ __forceinline__ void decode_pixel(const YuvSrc& a, int fy, int fx, int q[3]) {
+    constexpr int DEPTH = PX::DEPTH;
     const int r0 = fy >> 1, r1 = clampi(r0 + ((fy & 1) ? 1 : -1), 0, a.ch - 1);
     const int q0 = fx >> 1;
     const int q1 = LEFT ? min(q0 + 1, a.cw - 1) : clampi(q0 + ((fx & 1) ? 1 : -1), 0, a.cw - 1);
@@ -114,16 +175,16 @@ __device__ __forceinline__ void decode_pixel(const YuvSrc& a, int fy, int fx, in
                              sample<DEPTH, false>(a.yuv, a.uoff + i10), sample<DEPTH, false>(a.yuv, a.uoff + i11), wx0, wx1);
     const int V = chroma_mix(sample<DEPTH, false>(a.yuv, a.voff + i00), sample<DEPTH, false>(a.yuv, a.voff + i01),
                              sample<DEPTH, false>(a.yuv, a.voff + i10), sample<DEPTH, false>(a.yuv, a.voff + i11), wx0, wx1);
-    to_rgb(a, sample<DEPTH, false>(a.yuv, (long long)fy * a.W + fx), U, V, q);
+    to_rgb<PX::TOP>(a, sample<DEPTH, false>(a.yuv, (long long)fy * a.W + fx), U, V, q);
 }
 
 // four frame pixels of row fy, columns gx .. gx + 3 (gx even, the row's Y group readable as dwords) from the chroma segments of rows
 // r0 / r1, seg[k] = column clamp((gx >> 1) - 1 + k) (the aligned paths)
-template <int DEPTH, bool LEFT>
+template <class PX, bool LEFT>
 __device__ __forceinline__ void decode4(const YuvSrc& a, int fy, int gx, const int u0[4], const int u1[4], const int v0[4], const int v1[4],
                                         int q[4][3]) {
     int Y[4];
-    if (DEPTH == 8) {
+    if (PX::DEPTH == 8) {
         const unsigned d = *reinterpret_cast<const unsigned*>(a.yuv + (long long)fy * a.W + gx);
 #pragma unroll
         for (int i = 0; i < 4; ++i) Y[i] = (int)((d >> (8 * i)) & 0xffu);
@@ -141,16 +202,67 @@ __device__ __forceinline__ void decode4(const YuvSrc& a, int fy, int gx, const i
         const int wx0 = LEFT ? ((i & 1) ? 2 : 4) : 3, wx1 = 4 - wx0;
         const int U = chroma_mix(u0[k0], u0[k1], u1[k0], u1[k1], wx0, wx1);
         const int V = chroma_mix(v0[k0], v0[k1], v1[k0], v1[k1], wx0, wx1);
-        to_rgb(a, Y[i], U, V, q[i]);
+        to_rgb<PX::TOP>(a, Y[i], U, V, q[i]);
     }
 }
 
+// -------------------------------------------------------------------------------------------------------------------- host: checks
+// Every entry point passes its own name as the message prefix and keeps its own order of checks; none of these launches anything.
 int check_format(const char* what, int H, int W, int matrix, int full_range, int siting) {
     ATMVFI_REQUIRE(H >= 1 && W >= 1, ATMVFI_EINVAL, "%s: H and W must be at least 1 (got %d x %d)", what, H, W);
     ATMVFI_REQUIRE(matrix == 0 || matrix == 1, ATMVFI_EINVAL, "%s: unknown matrix %d (0: bt601, 1: bt709)", what, matrix);
     ATMVFI_REQUIRE(full_range == 0 || full_range == 1, ATMVFI_EINVAL, "%s: full_range must be 0 or 1 (got %d)", what, full_range);
     ATMVFI_REQUIRE(siting == 0 || siting == 1, ATMVFI_EINVAL, "%s: unknown siting %d (0: centre, 1: left)", what, siting);
     return ATMVFI_OK;
+}
+
+int check_depth(const char* what, int depth, int full_range) {
+    ATMVFI_REQUIRE(depth == 8 || depth == 10, ATMVFI_EINVAL, "%s: depth must be 8 or 10 (got %d)", what, depth);
+    ATMVFI_REQUIRE(!(depth == 10 && full_range), ATMVFI_EINVAL, "%s: 10-bit full range is not supported", what);
+    return ATMVFI_OK;
+}
+
+// the fp32 canvas [3,Hp,Wp] at p holds the h x w `noun` ("frame" or "window") at (pad_top, pad_left); side names the argument
+int check_canvas(const char* what, const char* side, const char* noun, const float* p, int h, int w, int Hp, int Wp, int pad_top,
+                 int pad_left) {
+    ATMVFI_REQUIRE(aligned4(p), ATMVFI_EINVAL, "%s: %s must be 4-byte aligned", what, side);
+    ATMVFI_REQUIRE(pad_top >= 0 && pad_left >= 0 && (long long)h + pad_top <= Hp && (long long)w + pad_left <= Wp, ATMVFI_EINVAL,
+                   "%s: canvas %d x %d is smaller than the %s %d x %d plus padding (%d, %d)", what, Hp, Wp, noun, h, w, pad_top, pad_left);
+    return ATMVFI_OK;
+}
+
+// a lane's index is an int: rows x groups work items of `thing` ("output of" the canvas, "a frame of" the encode's source)
+int check_items(const char* what, long long rows, long long groups, const char* thing, int h, int w) {
+    ATMVFI_REQUIRE(rows * groups < (1ll << 30), ATMVFI_EINVAL, "%s: %s %d x %d is too large", what, thing, h, w);
+    return ATMVFI_OK;
+}
+
+inline int groups_of(int w) { return (int)(((long long)w + 3) / 4); }
+inline int pairs_of(int h) { return (int)(((long long)h + 1) / 2); }
+
+// the fp32 canvas of the aligned paths: 16-byte plane accesses, a group of four wholly inside the picture or wholly in the padding
+inline bool canvas_aligned(const float* p, int Wp, int pad_left) { return atmvfi::aligned16(p) && Wp % 4 == 0 && pad_left % 4 == 0; }
+
+// grid-stride kernels of 256 threads, at most 16 384 blocks
+inline dim3 yuv_grid(long long items) {
+    const long long blocks = (items + 255) / 256;
+    return dim3((unsigned)(blocks > 16384 ? 16384 : blocks));
+}
+
+// run-time switches -> template parameters of a launch: f(std::bool_constant<b0>{}, ...).  The siting is always one of them: the tap
+// indices and weights of the chroma filter are constants of the instance.
+template <class F>
+void with_bool(bool b, F&& f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+template <class F>
+void dispatch(bool b0, bool b1, F&& f) {
+    with_bool(b0, [&](auto c0) { with_bool(b1, [&](auto c1) { f(c0, c1); }); });
+}
+template <class F>
+void dispatch(bool b0, bool b1, bool b2, F&& f) {
+    with_bool(b0, [&](auto c0) { dispatch(b1, b2, [&](auto c1, auto c2) { f(c0, c1, c2); }); });
 }
 
 }  // namespace

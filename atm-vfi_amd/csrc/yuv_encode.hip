@@ -1,0 +1,212 @@
+// RGB -> planar YUV 4:2:0 (I420): the two encode entry points of include/atmvfi.h on one kernel.  yuv_common.h holds the definition and
+// the shared helpers; yuv.hip is the other direction.
+//   atmvfi_rgb_to_yuv420      uint8 [H,W,3] (RGB or BGR) or the fp32 canvas in units of 1 / 255 -> 8-bit samples
+//   atmvfi_f32_to_yuv420p10   the fp32 canvas in units of 1 / 1023 -> 10-bit samples, the depth kept
+//
+// Bandwidth-bound: from fp32 12 B/px in and 1.5 or 3 out.  A lane owns a 4 x 2 luma block of the frame: two Y groups and two chroma
+// samples per plane; left siting reads one more pixel column.
+//   aligned path (frame pointer 4-byte aligned, W % 4 == 0; the uint8 source 4-byte aligned, or the fp32 canvas 16-byte aligned with
+//           Wp % 4 == 0 and pad_left % 4 == 0): the source group is three dwords or three 16-byte loads, a Y group one dword or 8-byte
+//           store, a chroma pair (cw even) one 2-byte or dword store;
+//   general path: any geometry and alignment: byte accesses to the frame, scalar loads, the same integer arithmetic, the same bits.
+// Vector stores only, no atomics, nothing pre-zeroed: every output byte is written by exactly one lane.
+#include "yuv_common.h"
+
+namespace {
+
+enum Source { SRC_U8, SRC_F255, SRC_F1023 };       // the pixel: uint8, clip(rint(x * 255)), clip(rint(x * 1023))
+
+struct EncArgs {
+    const unsigned char* src_u8;
+    int bgr;
+    const float* src;
+    int Hp, Wp, pad_top, pad_left;
+    int H, W, ch, cw;
+    int eY[3], eU[3], eV[3], yo;
+    unsigned char* yuv;
+    long long uoff, voff;       // first U / V sample, in samples
+    int groups;                 // ceil(W / 4); a group makes chroma columns 2g and 2g + 1
+};
+
+template <int SRC>
+__device__ __forceinline__ void load_px(const EncArgs& a, int fy, int fx, int p[3]) {
+    if (SRC == SRC_U8) {
+        const unsigned char* s = a.src_u8 + ((long long)fy * a.W + fx) * 3;
+        p[0] = a.bgr ? s[2] : s[0];
+        p[1] = s[1];
+        p[2] = a.bgr ? s[0] : s[2];
+    } else {        // rint: half to even, as np.rint (frame_f32_to_u8); the conversion saturates
+        constexpr int TOP = SRC == SRC_F1023 ? 1023 : 255;
+        const long long plane = (long long)a.Hp * a.Wp;
+        const float* s = a.src + (long long)(fy + a.pad_top) * a.Wp + (fx + a.pad_left);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) p[c] = clampi(__float2int_rn(s[c * plane] * (float)TOP), 0, TOP);
+    }
+}
+
+template <int SRC>
+__device__ __forceinline__ void load_px4_aligned(const EncArgs& a, int fy, int fx, int p[4][3]) {
+    if (SRC == SRC_U8) {
+        const U32x3 r = *reinterpret_cast<const U32x3*>(a.src_u8 + ((long long)fy * a.W + fx) * 3);
+        const unsigned d[3] = {r.a, r.b, r.c};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const int kr = 3 * i + c, kb = 3 * i + 2 - c;       // (a select between two compile-time bytes)
+                const int vr = (int)((d[kr >> 2] >> ((kr & 3) * 8)) & 0xffu), vb = (int)((d[kb >> 2] >> ((kb & 3) * 8)) & 0xffu);
+                p[i][c] = a.bgr ? vb : vr;
+            }
+        }
+    } else {
+        constexpr int TOP = SRC == SRC_F1023 ? 1023 : 255;
+        const long long plane = (long long)a.Hp * a.Wp;
+        const float* s = a.src + (long long)(fy + a.pad_top) * a.Wp + (fx + a.pad_left);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(s + c * plane);
+            const float f[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) p[i][c] = clampi(__float2int_rn(f[i] * (float)TOP), 0, TOP);
+        }
+    }
+}
+
+// (__mul24: the full-rate 24-bit multiply; coefficients are below 2^17, samples and pixel sums below 2^14)
+__device__ __forceinline__ int dot3(const int e[3], const int p[3]) { return __mul24(e[0], p[0]) + __mul24(e[1], p[1]) + __mul24(e[2], p[2]); }
+
+// N samples of one plane row from sample i on: one aligned store of N samples (N = 2: a chroma pair; N = 4: a Y group), or its first n
+// samples byte by byte
+template <int DEPTH, bool ALIGNED, int N>
+__device__ __forceinline__ void store_samples(unsigned char* yuv, long long i, const int v[N], int n) {
+    if (ALIGNED) {
+        if (DEPTH == 8) {
+            unsigned d = 0u;
+#pragma unroll
+            for (int k = 0; k < N; ++k) d |= (unsigned)v[k] << (8 * k);
+            if (N == 2) reinterpret_cast<U16x1*>(yuv + i)->v = (unsigned short)d;
+            else *reinterpret_cast<unsigned*>(yuv + i) = d;
+        } else {
+            const unsigned d0 = (unsigned)v[0] | ((unsigned)v[1] << 16);
+            if (N == 2) *reinterpret_cast<unsigned*>(yuv + 2 * i) = d0;
+            else *reinterpret_cast<U32x2*>(yuv + 2 * i) = U32x2{d0, (unsigned)v[N - 2] | ((unsigned)v[N - 1] << 16)};
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+            if (k >= n) break;
+            if (DEPTH == 8) {
+                yuv[i + k] = (unsigned char)v[k];
+            } else {
+                yuv[2 * (i + k)] = (unsigned char)(v[k] & 0xff);
+                yuv[2 * (i + k) + 1] = (unsigned char)(v[k] >> 8);
+            }
+        }
+    }
+}
+
+template <int SRC, bool ALIGNED, bool LEFT>
+__global__ __launch_bounds__(256) void yuv420_encode_kernel(const EncArgs a) {
+    constexpr int DEPTH = SRC == SRC_F1023 ? 10 : 8, TOP = SRC == SRC_F1023 ? 1023 : 255, MID = (TOP + 1) / 2;
+    const int total = a.ch * a.groups;
+    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
+        const int j = idx / a.groups, g = idx - j * a.groups, x = 4 * g;
+        int px[2][5][3];        // [row][0: the column left of the group (left siting only), 1..4: the group][R, G, B]
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int fy = min(2 * j + r, a.H - 1);
+            if (LEFT) load_px<SRC>(a, fy, max(x - 1, 0), px[r][0]);
+            else px[r][0][0] = px[r][0][1] = px[r][0][2] = 0;
+            if (ALIGNED) {
+                load_px4_aligned<SRC>(a, fy, x, &px[r][1]);
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) load_px<SRC>(a, fy, min(x + i, a.W - 1), px[r][1 + i]);
+            }
+        }
+        // luma
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int y = 2 * j + r;
+            if (y >= a.H) break;
+            int Y[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) Y[i] = clampi(((dot3(a.eY, px[r][1 + i]) + (1 << 13)) >> 14) + a.yo, 0, TOP);
+            store_samples<DEPTH, ALIGNED, 4>(a.yuv, (long long)y * a.W + x, Y, a.W - x);
+        }
+        // chroma columns 2g and 2g + 1
+        constexpr int sh = LEFT ? 3 : 2;
+        int U[2], V[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            int s[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                if (LEFT)
+                    s[c] = px[0][2 * i][c] + 2 * px[0][1 + 2 * i][c] + px[0][2 + 2 * i][c] + px[1][2 * i][c] + 2 * px[1][1 + 2 * i][c] +
+                           px[1][2 + 2 * i][c];
+                else
+                    s[c] = px[0][1 + 2 * i][c] + px[0][2 + 2 * i][c] + px[1][1 + 2 * i][c] + px[1][2 + 2 * i][c];
+            }
+            U[i] = clampi(((dot3(a.eU, s) + (1 << (13 + sh))) >> (14 + sh)) + MID, 0, TOP);
+            V[i] = clampi(((dot3(a.eV, s) + (1 << (13 + sh))) >> (14 + sh)) + MID, 0, TOP);
+        }
+        const long long c0 = (long long)j * a.cw + 2 * g;      // (aligned: cw is even, both columns exist)
+        store_samples<DEPTH, ALIGNED, 2>(a.yuv, a.uoff + c0, U, a.cw - 2 * g);
+        store_samples<DEPTH, ALIGNED, 2>(a.yuv, a.voff + c0, V, a.cw - 2 * g);
+    }
+}
+
+// Launches the encode of a checked frame; exactly one of src_u8 and src is given
+template <int SRC>
+void launch_encode(const Coeffs& c, int yo, const void* src_u8, int bgr, const float* src, int Hp, int Wp, int pad_top, int pad_left, int H,
+                   int W, int siting, void* yuv, void* stream) {
+    const int ch = (H + 1) / 2, cw = (W + 1) / 2, groups = groups_of(W);
+    EncArgs a = {(const unsigned char*)src_u8, bgr ? 1 : 0, src, Hp, Wp, pad_top, pad_left, H, W, ch, cw};
+    for (int k = 0; k < 3; ++k) {
+        a.eY[k] = c.enc[0][k];
+        a.eU[k] = c.enc[1][k];
+        a.eV[k] = c.enc[2][k];
+    }
+    a.yo = yo;
+    a.yuv = (unsigned char*)yuv;
+    a.uoff = (long long)H * W;
+    a.voff = a.uoff + (long long)ch * cw;
+    a.groups = groups;
+    const bool al = aligned4(yuv) && W % 4 == 0 && (src ? canvas_aligned(src, Wp, pad_left) : aligned4(src_u8));
+    const dim3 grid = yuv_grid((long long)ch * groups), block(256);
+    dispatch(al, siting, [&](auto AL, auto LEFT) {
+        hipLaunchKernelGGL((yuv420_encode_kernel<SRC, decltype(AL)::value, decltype(LEFT)::value>), grid, block, 0, (hipStream_t)stream, a);
+    });
+}
+
+}  // namespace
+
+extern "C" int atmvfi_rgb_to_yuv420(const void* src_u8, int bgr, const float* src, int Hp, int Wp, int pad_top, int pad_left, int H, int W,
+                                    int matrix, int full_range, int siting, void* yuv, void* stream) {
+    const char* me = "rgb_to_yuv420";
+    ATMVFI_REQUIRE(yuv, ATMVFI_EINVAL, "rgb_to_yuv420: null destination");
+    ATMVFI_REQUIRE((src_u8 != nullptr) != (src != nullptr), ATMVFI_EINVAL,
+                   "rgb_to_yuv420: give exactly one of src_u8 and src (got %s)", src_u8 ? "both" : "neither");
+    if (const int rc = check_format(me, H, W, matrix, full_range, siting)) return rc;
+    if (src)
+        if (const int rc = check_canvas(me, "src", "frame", src, H, W, Hp, Wp, pad_top, pad_left)) return rc;
+    if (const int rc = check_items(me, (H + 1) / 2, groups_of(W), "a frame of", H, W)) return rc;
+    const Coeffs& c = kCoeffs[matrix][full_range];
+    const int yo = full_range ? 0 : 16;
+    if (src) launch_encode<SRC_F255>(c, yo, nullptr, 0, src, Hp, Wp, pad_top, pad_left, H, W, siting, yuv, stream);
+    else launch_encode<SRC_U8>(c, yo, src_u8, bgr, nullptr, Hp, Wp, pad_top, pad_left, H, W, siting, yuv, stream);
+    return atmvfi::check_launch(me);
+}
+
+extern "C" int atmvfi_f32_to_yuv420p10(const float* src, int Hp, int Wp, int pad_top, int pad_left, int H, int W, int matrix, int siting,
+                                       void* yuv, void* stream) {
+    const char* me = "f32_to_yuv420p10";
+    ATMVFI_REQUIRE(src, ATMVFI_EINVAL, "f32_to_yuv420p10: null source");
+    ATMVFI_REQUIRE(yuv, ATMVFI_EINVAL, "f32_to_yuv420p10: null destination");
+    if (const int rc = check_format(me, H, W, matrix, 0, siting)) return rc;
+    if (const int rc = check_canvas(me, "src", "frame", src, H, W, Hp, Wp, pad_top, pad_left)) return rc;
+    if (const int rc = check_items(me, (H + 1) / 2, groups_of(W), "a frame of", H, W)) return rc;
+    launch_encode<SRC_F1023>(kCoeffs10[matrix], 64, nullptr, 0, src, Hp, Wp, pad_top, pad_left, H, W, siting, yuv, stream);
+    return atmvfi::check_launch(me);
+}

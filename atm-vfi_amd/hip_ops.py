@@ -317,6 +317,30 @@ def _planar(t: torch.Tensor, c: int, what: str):
         raise ValueError(f"{what}: expected contiguous [B,{c},H,W], got {tuple(t.shape)} strides {t.stride()}")
 
 
+def _is_u8_frame(t, hw=None) -> bool:
+    return (isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and t.dim() == 3 and t.shape[2] == 3 and t.is_contiguous() and t.is_cuda
+            and (hw is None or tuple(t.shape[:2]) == tuple(hw)))
+
+
+def _u8_frame(t, what: str, hw=None):
+    """``t`` is a packed uint8 frame [H,W,3] on the device (of exactly ``hw`` = (h, w) when given), or ``ValueError``."""
+    if not _is_u8_frame(t, hw):
+        raise ValueError(f"{what} must be a contiguous CUDA uint8 [{'H,W' if hw is None else f'{hw[0]},{hw[1]}'},3] tensor")
+
+
+def _f32_canvas(t, what: str):
+    """``t`` is a planar fp32 frame [3,Hp,Wp] on the device, or ``ValueError``."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 3 or t.shape[0] != 3 or not t.is_contiguous() or not t.is_cuda:
+        raise ValueError(f"{what} must be a contiguous CUDA fp32 [3,Hp,Wp] tensor")
+
+
+def _i420(t, fmt, what: str, kind: str = "I420"):
+    """``t`` is one packed planar frame of ``fmt`` (a ``yuv.Format``) as bytes on the device, or ``ValueError``."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1 or t.numel() != fmt.frame_bytes or not t.is_contiguous() \
+            or not t.is_cuda:
+        raise ValueError(f"{what} must be a contiguous CUDA uint8 tensor of {fmt.frame_bytes} bytes ({fmt.height} x {fmt.width} {kind})")
+
+
 class PlanUnsupported(Exception):
     """Raised while recording when a forward cannot be expressed as a launch plan (the caller falls back to direct launches)."""
 
@@ -1239,10 +1263,8 @@ class HipOps:
 
     def frame_u8_to_f32(self, src_u8, dst, pad_top: int, pad_left: int, bgr: bool):
         """uint8 [H,W,3] device tensor -> fp32 planar [3,Hp,Wp] (x / 255, replicate padding, optional BGR -> RGB)."""
-        if src_u8.dtype != torch.uint8 or src_u8.dim() != 3 or src_u8.shape[2] != 3 or not src_u8.is_contiguous() or not src_u8.is_cuda:
-            raise ValueError("frame_u8_to_f32: source must be a contiguous CUDA uint8 [H,W,3] tensor")
-        if dst.dtype != torch.float32 or dst.dim() != 3 or dst.shape[0] != 3 or not dst.is_contiguous() or not dst.is_cuda:
-            raise ValueError("frame_u8_to_f32: destination must be a contiguous CUDA fp32 [3,Hp,Wp] tensor")
+        _u8_frame(src_u8, "frame_u8_to_f32: source")
+        _f32_canvas(dst, "frame_u8_to_f32: destination")
         h, w = src_u8.shape[:2]
         self._run("frame_u8_to_f32", {"bytes": 3.0 * h * w + 12.0 * dst.shape[1] * dst.shape[2]}, self.lib.atmvfi_frame_u8_to_f32,
                   _ptr(src_u8), h, w, int(bgr), _ptr(dst), dst.shape[1], dst.shape[2], pad_top, pad_left, self._stream())
@@ -1252,15 +1274,13 @@ class HipOps:
         """One resident uint8 [H,W,3] frame -> the h x w window at (y0, x0) (``mode`` 0) or the 2x area reduction of the 2h x 2w window
         there (``mode`` 1: (a + b + c + d + 2) >> 2, cv2.INTER_AREA at scale 2), as ``dst`` fp32 planar [3,Hp,Wp] (q / 255, replicate
         padding, the window at (pad_top, pad_left)) and / or ``dst_u8`` uint8 [h,w,3] RGB (include/atmvfi.h atmvfi_frame_u8_window)."""
-        if src_u8.dtype != torch.uint8 or src_u8.dim() != 3 or src_u8.shape[2] != 3 or not src_u8.is_contiguous() or not src_u8.is_cuda:
-            raise ValueError("frame_u8_window: source must be a contiguous CUDA uint8 [H,W,3] tensor")
+        _u8_frame(src_u8, "frame_u8_window: source")
         if dst is None and dst_u8 is None:
             raise ValueError("frame_u8_window: give dst, dst_u8 or both")
-        if dst is not None and (dst.dtype != torch.float32 or dst.dim() != 3 or dst.shape[0] != 3 or not dst.is_contiguous() or not dst.is_cuda):
-            raise ValueError("frame_u8_window: dst must be a contiguous CUDA fp32 [3,Hp,Wp] tensor")
-        if dst_u8 is not None and (dst_u8.dtype != torch.uint8 or tuple(dst_u8.shape) != (h, w, 3) or not dst_u8.is_contiguous()
-                                   or not dst_u8.is_cuda):
-            raise ValueError(f"frame_u8_window: dst_u8 must be a contiguous CUDA uint8 [{h},{w},3] tensor")
+        if dst is not None:
+            _f32_canvas(dst, "frame_u8_window: dst")
+        if dst_u8 is not None:
+            _u8_frame(dst_u8, "frame_u8_window: dst_u8", (h, w))
         sh, sw = src_u8.shape[:2]
         hp, wp = (dst.shape[1], dst.shape[2]) if dst is not None else (h + pad_top, w + pad_left)
         scale = 2 if mode == 1 else 1
@@ -1282,8 +1302,7 @@ class HipOps:
         ``scene.signature_numpy``).  ``out`` is written completely (a new tensor when None).  ``workspace``: the call's scratch
         (``frame_signature_workspace``); None: one kept per (window size, stream) by this object.  Not part of a forward: never recorded
         into a launch plan."""
-        if src_u8.dtype != torch.uint8 or src_u8.dim() != 3 or src_u8.shape[2] != 3 or not src_u8.is_contiguous() or not src_u8.is_cuda:
-            raise ValueError("frame_signature: source must be a contiguous CUDA uint8 [H,W,3] tensor")
+        _u8_frame(src_u8, "frame_signature: source")
         sh, sw = src_u8.shape[:2]
         h = sh - int(y0) if h is None else int(h)
         w = sw - int(x0) if w is None else int(w)
@@ -1317,9 +1336,8 @@ class HipOps:
         atmvfi_frame_difference; the bits of ``retime.difference_numpy``).  ``out`` is written completely (a new tensor when None).
         ``workspace``: the call's scratch (``frame_difference_workspace``); None: one kept per (window size, stream) by this object.
         Not part of a forward: never recorded into a launch plan."""
-        for t in (a, b):
-            if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3 or not t.is_contiguous() or not t.is_cuda:
-                raise ValueError("frame_difference: sources must be contiguous CUDA uint8 [H,W,3] tensors")
+        if not (_is_u8_frame(a) and _is_u8_frame(b)):
+            raise ValueError("frame_difference: sources must be contiguous CUDA uint8 [H,W,3] tensors")
         if a.shape != b.shape or a.device != b.device:
             raise ValueError(f"frame_difference: two frames of one size on one device expected, got {tuple(a.shape)} and {tuple(b.shape)}")
         sh, sw = a.shape[:2]
@@ -1346,15 +1364,13 @@ class HipOps:
         alignment) -> ``dst_u8`` uint8 [H,W,3] (BGR if ``bgr``) and / or ``dst`` fp32 planar RGB [3,Hp,Wp] = q / 255 with replicate
         padding, the frame at (pad_top, pad_left) (include/atmvfi.h atmvfi_yuv420_to_rgb; the bits of ``yuv.decode_numpy``)."""
         h, w = fmt.height, fmt.width
-        if yuv.dtype != torch.uint8 or yuv.dim() != 1 or yuv.numel() != fmt.frame_bytes or not yuv.is_contiguous() or not yuv.is_cuda:
-            raise ValueError(f"yuv420_to_rgb: source must be a contiguous CUDA uint8 tensor of {fmt.frame_bytes} bytes ({h} x {w} I420)")
+        _i420(yuv, fmt, "yuv420_to_rgb: source")
         if dst is None and dst_u8 is None:
             raise ValueError("yuv420_to_rgb: give dst, dst_u8 or both")
-        if dst is not None and (dst.dtype != torch.float32 or dst.dim() != 3 or dst.shape[0] != 3 or not dst.is_contiguous() or not dst.is_cuda):
-            raise ValueError("yuv420_to_rgb: dst must be a contiguous CUDA fp32 [3,Hp,Wp] tensor")
-        if dst_u8 is not None and (dst_u8.dtype != torch.uint8 or tuple(dst_u8.shape) != (h, w, 3) or not dst_u8.is_contiguous()
-                                   or not dst_u8.is_cuda):
-            raise ValueError(f"yuv420_to_rgb: dst_u8 must be a contiguous CUDA uint8 [{h},{w},3] tensor")
+        if dst is not None:
+            _f32_canvas(dst, "yuv420_to_rgb: dst")
+        if dst_u8 is not None:
+            _u8_frame(dst_u8, "yuv420_to_rgb: dst_u8", (h, w))
         hp, wp = (dst.shape[1], dst.shape[2]) if dst is not None else (h, w)
         meta = {"bytes": float(fmt.frame_bytes) + (12.0 * hp * wp if dst is not None else 0.0) + (3.0 * h * w if dst_u8 is not None else 0.0)}
         self._run("yuv420_to_rgb", meta, self.lib.atmvfi_yuv420_to_rgb, _ptr(yuv), h, w, int(fmt.depth), fmt.matrix_id, int(fmt.full_range),
@@ -1367,17 +1383,15 @@ class HipOps:
         window at (pad_top, pad_left)) and / or ``dst_u8`` uint8 [h,w,3] RGB.  The origin must be even (include/atmvfi.h
         atmvfi_yuv420_window; the bits of ``yuv.window_numpy``)."""
         fh, fw = fmt.height, fmt.width
-        if yuv.dtype != torch.uint8 or yuv.dim() != 1 or yuv.numel() != fmt.frame_bytes or not yuv.is_contiguous() or not yuv.is_cuda:
-            raise ValueError(f"yuv420_window: source must be a contiguous CUDA uint8 tensor of {fmt.frame_bytes} bytes ({fh} x {fw} I420)")
+        _i420(yuv, fmt, "yuv420_window: source")
         if dst is None and dst_u8 is None:
             raise ValueError("yuv420_window: give dst, dst_u8 or both")
         if int(y0) % 2 or int(x0) % 2:
             raise ValueError(f"yuv420_window: the window origin ({y0}, {x0}) must be even for 4:2:0 frames")
-        if dst is not None and (dst.dtype != torch.float32 or dst.dim() != 3 or dst.shape[0] != 3 or not dst.is_contiguous() or not dst.is_cuda):
-            raise ValueError("yuv420_window: dst must be a contiguous CUDA fp32 [3,Hp,Wp] tensor")
-        if dst_u8 is not None and (dst_u8.dtype != torch.uint8 or tuple(dst_u8.shape) != (h, w, 3) or not dst_u8.is_contiguous()
-                                   or not dst_u8.is_cuda):
-            raise ValueError(f"yuv420_window: dst_u8 must be a contiguous CUDA uint8 [{h},{w},3] tensor")
+        if dst is not None:
+            _f32_canvas(dst, "yuv420_window: dst")
+        if dst_u8 is not None:
+            _u8_frame(dst_u8, "yuv420_window: dst_u8", (h, w))
         hp, wp = (dst.shape[1], dst.shape[2]) if dst is not None else (h + pad_top, w + pad_left)
         scale = 2 if mode == 1 else 1
         meta = {"bytes": 1.5 * (2 if fmt.depth == 10 else 1) * scale * scale * h * w + (12.0 * hp * wp if dst is not None else 0.0)
@@ -1393,15 +1407,13 @@ class HipOps:
         h, w = fmt.height, fmt.width
         if fmt.depth != 8:
             raise ValueError("rgb_to_yuv420: encoding is 8-bit only")
-        if yuv.dtype != torch.uint8 or yuv.dim() != 1 or yuv.numel() != fmt.frame_bytes or not yuv.is_contiguous() or not yuv.is_cuda:
-            raise ValueError(f"rgb_to_yuv420: destination must be a contiguous CUDA uint8 tensor of {fmt.frame_bytes} bytes ({h} x {w} I420)")
+        _i420(yuv, fmt, "rgb_to_yuv420: destination")
         if (src is None) == (src_u8 is None):
             raise ValueError("rgb_to_yuv420: give exactly one of src_u8 and src")
-        if src is not None and (src.dtype != torch.float32 or src.dim() != 3 or src.shape[0] != 3 or not src.is_contiguous() or not src.is_cuda):
-            raise ValueError("rgb_to_yuv420: src must be a contiguous CUDA fp32 [3,Hp,Wp] tensor")
-        if src_u8 is not None and (src_u8.dtype != torch.uint8 or tuple(src_u8.shape) != (h, w, 3) or not src_u8.is_contiguous()
-                                   or not src_u8.is_cuda):
-            raise ValueError(f"rgb_to_yuv420: src_u8 must be a contiguous CUDA uint8 [{h},{w},3] tensor")
+        if src is not None:
+            _f32_canvas(src, "rgb_to_yuv420: src")
+        else:
+            _u8_frame(src_u8, "rgb_to_yuv420: src_u8", (h, w))
         hp, wp = (src.shape[1], src.shape[2]) if src is not None else (h, w)
         meta = {"bytes": float(fmt.frame_bytes) + (12.0 if src is not None else 3.0) * h * w}
         self._run("rgb_to_yuv420", meta, self.lib.atmvfi_rgb_to_yuv420, _ptr(src_u8), int(bool(bgr)), _ptr(src), hp, wp, int(pad_top),
@@ -1415,11 +1427,8 @@ class HipOps:
         h, w = fmt.height, fmt.width
         if fmt.depth != 10:
             raise ValueError("yuv420p10_to_f32: a 10-bit format expected (yuv420_to_rgb decodes 8-bit frames)")
-        if yuv.dtype != torch.uint8 or yuv.dim() != 1 or yuv.numel() != fmt.frame_bytes or not yuv.is_contiguous() or not yuv.is_cuda:
-            raise ValueError(f"yuv420p10_to_f32: source must be a contiguous CUDA uint8 tensor of {fmt.frame_bytes} bytes ({h} x {w} "
-                             f"10-bit I420)")
-        if dst is None or dst.dtype != torch.float32 or dst.dim() != 3 or dst.shape[0] != 3 or not dst.is_contiguous() or not dst.is_cuda:
-            raise ValueError("yuv420p10_to_f32: dst must be a contiguous CUDA fp32 [3,Hp,Wp] tensor")
+        _i420(yuv, fmt, "yuv420p10_to_f32: source", "10-bit I420")
+        _f32_canvas(dst, "yuv420p10_to_f32: dst")
         y0, x0, wh, ww = (0, 0, h, w) if window is None else (int(v) for v in window)
         if y0 % 2 or x0 % 2:
             raise ValueError(f"yuv420p10_to_f32: the window origin ({y0}, {x0}) must be even for 4:2:0 frames")
@@ -1440,11 +1449,8 @@ class HipOps:
         h, w = fmt.height, fmt.width
         if fmt.depth != 10:
             raise ValueError("f32_to_yuv420p10: a 10-bit format expected (rgb_to_yuv420 encodes 8-bit frames)")
-        if yuv.dtype != torch.uint8 or yuv.dim() != 1 or yuv.numel() != fmt.frame_bytes or not yuv.is_contiguous() or not yuv.is_cuda:
-            raise ValueError(f"f32_to_yuv420p10: destination must be a contiguous CUDA uint8 tensor of {fmt.frame_bytes} bytes ({h} x {w} "
-                             f"10-bit I420)")
-        if src is None or src.dtype != torch.float32 or src.dim() != 3 or src.shape[0] != 3 or not src.is_contiguous() or not src.is_cuda:
-            raise ValueError("f32_to_yuv420p10: src must be a contiguous CUDA fp32 [3,Hp,Wp] tensor")
+        _i420(yuv, fmt, "f32_to_yuv420p10: destination", "10-bit I420")
+        _f32_canvas(src, "f32_to_yuv420p10: src")
         hp, wp = src.shape[1], src.shape[2]
         if pad_top < 0 or pad_left < 0 or h + pad_top > hp or w + pad_left > wp:
             raise ValueError(f"f32_to_yuv420p10: canvas {hp} x {wp} is smaller than the frame {h} x {w} plus padding ({pad_top}, {pad_left})")
@@ -1454,10 +1460,8 @@ class HipOps:
 
     def frame_f32_to_u8(self, src, dst_u8, pad_top: int, pad_left: int, bgr: bool):
         """fp32 planar [3,Hp,Wp] -> crop -> np.round(x * 255) -> uint8 [H,W,3] device tensor (optional RGB -> BGR)."""
-        if src.dtype != torch.float32 or src.dim() != 3 or src.shape[0] != 3 or not src.is_contiguous() or not src.is_cuda:
-            raise ValueError("frame_f32_to_u8: source must be a contiguous CUDA fp32 [3,Hp,Wp] tensor")
-        if dst_u8.dtype != torch.uint8 or dst_u8.dim() != 3 or dst_u8.shape[2] != 3 or not dst_u8.is_contiguous() or not dst_u8.is_cuda:
-            raise ValueError("frame_f32_to_u8: destination must be a contiguous CUDA uint8 [H,W,3] tensor")
+        _f32_canvas(src, "frame_f32_to_u8: source")
+        _u8_frame(dst_u8, "frame_f32_to_u8: destination")
         h, w = dst_u8.shape[:2]
         self._run("frame_f32_to_u8", {"bytes": 3.0 * h * w + 12.0 * h * w}, self.lib.atmvfi_frame_f32_to_u8, _ptr(src), src.shape[1],
                   src.shape[2], pad_top, pad_left, _ptr(dst_u8), h, w, int(bgr), self._stream())
@@ -1489,27 +1493,22 @@ class HipOps:
         self._run("pool_blocks", {"bytes": 2.0 * n * be * es, "blocks": n}, self.lib.atmvfi_pool_blocks, _ptr(pool), slot_elems * es,
                   pool.shape[0], arr, n, be * es, _ptr(buf), int(bool(to_pool)), self._stream())
 
-    @staticmethod
-    def _frame3(t, what: str):
-        if t.dtype != torch.float32 or t.dim() != 3 or t.shape[0] != 3 or not t.is_contiguous() or not t.is_cuda:
-            raise ValueError(f"{what} must be a contiguous CUDA fp32 [3,Hp,Wp] tensor")
-
     def tta_merge(self, pred, pred_flip, out=None, out_u8=None, pad_top: int = 0, pad_left: int = 0, bgr: bool = False):
         """``out`` = (pred + pred_flip.flip(1).flip(2)) / 2 on [3,Hp,Wp] frames and / or ``out_u8`` = ``frame_f32_to_u8`` of it (uint8
         [H,W,3], the crop at (pad_top, pad_left)), in one launch (include/atmvfi.h atmvfi_tta_merge)."""
-        self._frame3(pred, "tta_merge: pred"); self._frame3(pred_flip, "tta_merge: pred_flip")
+        _f32_canvas(pred, "tta_merge: pred")
+        _f32_canvas(pred_flip, "tta_merge: pred_flip")
         if pred_flip.shape != pred.shape:
             raise ValueError("tta_merge: pred and pred_flip differ in shape")
         if out is None and out_u8 is None:
             raise ValueError("tta_merge: give out, out_u8 or both")
         if out is not None:
-            self._frame3(out, "tta_merge: out")
+            _f32_canvas(out, "tta_merge: out")
             if out.shape != pred.shape:
                 raise ValueError("tta_merge: out must have pred's shape")
         h = w = 0
         if out_u8 is not None:
-            if out_u8.dtype != torch.uint8 or out_u8.dim() != 3 or out_u8.shape[2] != 3 or not out_u8.is_contiguous() or not out_u8.is_cuda:
-                raise ValueError("tta_merge: out_u8 must be a contiguous CUDA uint8 [H,W,3] tensor")
+            _u8_frame(out_u8, "tta_merge: out_u8")
             h, w = out_u8.shape[:2]
         hp, wp = pred.shape[1:]
         meta = {"bytes": 24.0 * hp * wp + (12.0 * hp * wp if out is not None else 0.0) + 3.0 * h * w}

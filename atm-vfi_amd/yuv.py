@@ -1,5 +1,5 @@
 """Planar YUV 4:2:0 (I420) frames and Y4M files for the video loops: the format, the host twins of the HIP colour conversion
-(``atmvfi_yuv420_to_rgb`` / ``atmvfi_rgb_to_yuv420``, csrc/yuv.hip), a YUV4MPEG2 reader and writer, and ``interpolate_y4m``.
+(``atmvfi_yuv420_to_rgb`` / ``atmvfi_rgb_to_yuv420``, csrc/yuv.hip / yuv_encode.hip), a YUV4MPEG2 reader and writer, and ``interpolate_y4m``.
 
 Nothing of the reference: its scripts read PNGs and hand video to OpenCV.  Decoders, ``ffmpeg -f yuv4mpegpipe`` pipes and the Xiph
 clips deliver planar 4:2:0; with ``pixfmt=Format(...)`` the loops (``interpolate_video_2x`` / ``FramePipeline`` /
@@ -14,7 +14,7 @@ applies ``COEFFS[..][1]``.  Not reproduced: ffmpeg's swscale (other filters, oth
 By default 10-bit input is decoded to 8-bit RGB and what the loops produce is 8-bit.
 
 ``keep_depth=True`` (the loops, ``interpolate_y4m``) keeps a 10-bit format's depth end to end (``atmvfi_yuv420p10_to_f32`` /
-``atmvfi_f32_to_yuv420p10``, csrc/yuv10.hip; twins ``decode_numpy_f32`` and ``encode_numpy`` of an fp32 source): the same chroma
+``atmvfi_f32_to_yuv420p10``, the same two files; twins ``decode_numpy_f32`` and ``encode_numpy`` of an fp32 source): the same chroma
 filters on the 10-bit samples, ``COEFFS10[matrix]`` at 14 bits (luma scaled by 876 / 1023, chroma by 896 / 1023), offsets 64 / 512,
 RGB clipped to 0..1023 and handed to the network as ``q / 1023`` (the fp32 division); encoding takes
 ``clip(rint(fl32(x * 1023)), 0, 1023)`` and writes uint16 samples.  Produced frames are 10-bit, originals the caller's arrays."""
@@ -56,7 +56,7 @@ def derive_coeffs(matrix: str, full_range: bool = False, depth: int = 8):
     return [q(v) for v in dec], [[q(v) for v in row] for row in enc]
 
 
-# (matrix, full_range) -> (decode [kY, kRV, kGU, kGV, kBU], encode rows Y / U / V over (R, G, B)); the table of csrc/yuv.hip
+# (matrix, full_range) -> (decode [kY, kRV, kGU, kGV, kBU], encode rows Y / U / V over (R, G, B)); kCoeffs of csrc/yuv_common.h
 COEFFS = {
     ("bt601", False): ((19077, 26149, -6419, -13320, 33050), ((4207, 8260, 1604), (-2428, -4768, 7196), (7196, -6026, -1170))),
     ("bt601", True): ((16384, 22970, -5638, -11700, 29032), ((4899, 9617, 1868), (-2765, -5427, 8192), (8192, -6860, -1332))),
@@ -64,7 +64,7 @@ COEFFS = {
     ("bt709", True): ((16384, 25802, -3069, -7670, 30402), ((3483, 11718, 1183), (-1877, -6315, 8192), (8192, -7441, -751))),
 }
 
-# matrix -> the same pair with the depth kept (10-bit limited-range samples <-> 10-bit RGB); the table of csrc/yuv10.hip
+# matrix -> the same pair with the depth kept (10-bit limited-range samples <-> 10-bit RGB); kCoeffs10 of csrc/yuv_common.h
 COEFFS10 = {
     "bt601": ((19133, 26226, -6438, -13359, 33148), ((4195, 8235, 1599), (-2421, -4754, 7175), (7175, -6008, -1167))),
     "bt709": ((19133, 29459, -3504, -8757, 34711), ((2983, 10034, 1013), (-1644, -5531, 7175), (7175, -6517, -658))),
@@ -151,38 +151,54 @@ def planes(buf, fmt: Format):
     return fmt.planes(buf)
 
 
-def decode_numpy(buf, fmt: Format, bgr: bool = False) -> np.ndarray:
-    """Packed I420 frame -> uint8 [H,W,3] RGB (BGR if ``bgr``): the bits of ``atmvfi_yuv420_to_rgb``'s ``dst_u8``."""
-    Y, U, V = (p.astype(np.int32) for p in fmt.planes(buf))
-    H, W = fmt.height, fmt.width
-    ch, cw = fmt.chroma_shape
-    ys, xs = np.arange(H), np.arange(W)
+def _chroma_taps(ys, xs, ch: int, cw: int, siting: str):
+    """The chroma taps of luma rows ``ys`` and columns ``xs`` of the frame: rows ``r0, r1`` (weights 3, 1), columns ``q0, q1`` with
+    weights ``wx0, wx1``; neighbours clamp at the frame's edges."""
     r0 = ys >> 1
     r1 = np.clip(r0 + np.where(ys & 1, 1, -1), 0, ch - 1)
     q0 = xs >> 1
-    if fmt.siting == "left":
+    if siting == "left":
         q1 = np.minimum(q0 + 1, cw - 1)
         wx0 = np.where(xs & 1, 2, 4).astype(np.int32)
     else:
         q1 = np.clip(q0 + np.where(xs & 1, 1, -1), 0, cw - 1)
-        wx0 = np.full(W, 3, np.int32)
-    wx1 = 4 - wx0
+        wx0 = np.full(len(xs), 3, np.int32)
+    return r0, r1, q0, q1, wx0, 4 - wx0
+
+
+def _to_rgb(Y, U, V, taps, coeffs, yo: int, mid: int, T: int, top: int) -> np.ndarray:
+    """Chroma filter, matrix and clip: the luma window ``Y`` (int32 [h,w]) and the frame's chroma planes with the window's ``taps``
+    -> int32 [h,w,3] RGB in 0..top."""
+    r0, r1, q0, q1, wx0, wx1 = taps
+    lo, hi = min(r0.min(), r1.min()), max(r0.max(), r1.max()) + 1           # the chroma rows the window touches
 
     def up(c):
-        a = wx0 * c[:, q0] + wx1 * c[:, q1]
-        return (3 * a[r0] + a[r1] + 8) >> 4
+        a = wx0 * c[lo:hi, q0] + wx1 * c[lo:hi, q1]
+        return (3 * a[r0 - lo] + a[r1 - lo] + 8) >> 4
 
-    (kY, kRV, kGU, kGV, kBU), _ = COEFFS[fmt.matrix, fmt.full_range]
-    if fmt.depth == 10:
-        yo, mid, T = 64, 512, 16
-    else:
-        yo, mid, T = (0 if fmt.full_range else 16), 128, 14
+    kY, kRV, kGU, kGV, kBU = coeffs
     y, u, v = kY * (Y - yo), up(U) - mid, up(V) - mid
     half = 1 << (T - 1)
-    r = (y + kRV * v + half) >> T
-    g = (y + kGU * u + kGV * v + half) >> T
-    b = (y + kBU * u + half) >> T
-    return np.clip(np.stack([b, g, r] if bgr else [r, g, b], axis=-1), 0, 255).astype(np.uint8)
+    return np.clip(np.stack([(y + kRV * v + half) >> T, (y + kGU * u + kGV * v + half) >> T, (y + kBU * u + half) >> T], axis=-1), 0, top)
+
+
+def _decode_window(buf, fmt: Format, y0: int, x0: int, h: int, w: int, keep: bool = False) -> np.ndarray:
+    """The checked window of the whole frame's decode as int32 [h,w,3] RGB: 0..255, or 0..1023 with the 10-bit depth kept."""
+    Y, U, V = (p.astype(np.int32) for p in fmt.planes(buf))
+    taps = _chroma_taps(np.arange(y0, y0 + h), np.arange(x0, x0 + w), *fmt.chroma_shape, fmt.siting)
+    if keep:
+        pixel = COEFFS10[fmt.matrix][0], 64, 512, 14, 1023
+    elif fmt.depth == 10:
+        pixel = COEFFS[fmt.matrix, fmt.full_range][0], 64, 512, 16, 255
+    else:
+        pixel = COEFFS[fmt.matrix, fmt.full_range][0], (0 if fmt.full_range else 16), 128, 14, 255
+    return _to_rgb(Y[y0:y0 + h, x0:x0 + w], U, V, taps, *pixel)
+
+
+def decode_numpy(buf, fmt: Format, bgr: bool = False) -> np.ndarray:
+    """Packed I420 frame -> uint8 [H,W,3] RGB (BGR if ``bgr``): the bits of ``atmvfi_yuv420_to_rgb``'s ``dst_u8``."""
+    q = _decode_window(buf, fmt, 0, 0, fmt.height, fmt.width)
+    return np.ascontiguousarray(q[:, :, ::-1] if bgr else q).astype(np.uint8)
 
 
 def window_numpy(buf, fmt: Format, mode: int, y0: int, x0: int, h: int, w: int) -> np.ndarray:
@@ -200,31 +216,7 @@ def window_numpy(buf, fmt: Format, mode: int, y0: int, x0: int, h: int, w: int) 
     if y0 < 0 or x0 < 0 or h < 1 or w < 1 or y0 + s * h > H or x0 + s * w > W:
         raise ValueError(f"window_numpy: window outside the frame (mode {mode} reads {s * h} x {s * w} source pixels at ({y0}, {x0}) of a "
                          f"{H} x {W} frame)")
-    Y, U, V = (p.astype(np.int32) for p in fmt.planes(buf))
-    ch, cw = fmt.chroma_shape
-    ys, xs = np.arange(y0, y0 + s * h), np.arange(x0, x0 + s * w)
-    r0 = ys >> 1
-    r1 = np.clip(r0 + np.where(ys & 1, 1, -1), 0, ch - 1)
-    q0 = xs >> 1
-    if fmt.siting == "left":
-        q1 = np.minimum(q0 + 1, cw - 1)
-        wx0 = np.where(xs & 1, 2, 4).astype(np.int32)
-    else:
-        q1 = np.clip(q0 + np.where(xs & 1, 1, -1), 0, cw - 1)
-        wx0 = np.full(s * w, 3, np.int32)
-    wx1 = 4 - wx0
-
-    def up(c):
-        return (3 * (wx0 * c[r0][:, q0] + wx1 * c[r0][:, q1]) + (wx0 * c[r1][:, q0] + wx1 * c[r1][:, q1]) + 8) >> 4
-
-    (kY, kRV, kGU, kGV, kBU), _ = COEFFS[fmt.matrix, fmt.full_range]
-    if fmt.depth == 10:
-        yo, mid, T = 64, 512, 16
-    else:
-        yo, mid, T = (0 if fmt.full_range else 16), 128, 14
-    y, u, v = kY * (Y[y0:y0 + s * h, x0:x0 + s * w] - yo), up(U) - mid, up(V) - mid
-    half = 1 << (T - 1)
-    q = np.clip(np.stack([(y + kRV * v + half) >> T, (y + kGU * u + kGV * v + half) >> T, (y + kBU * u + half) >> T], axis=-1), 0, 255)
+    q = _decode_window(buf, fmt, y0, x0, s * h, s * w)
     if mode == 1:
         q = (q[0::2, 0::2] + q[0::2, 1::2] + q[1::2, 0::2] + q[1::2, 1::2] + 2) >> 2
     return np.ascontiguousarray(q.astype(np.uint8))
@@ -236,37 +228,14 @@ def decode_numpy_f32(buf, fmt: Format, window=None) -> np.ndarray:
     are the frame's, not the window's."""
     if fmt.depth != 10:
         raise ValueError("decode_numpy_f32: a 10-bit format expected (8-bit frames decode with decode_numpy)")
-    Y, U, V = (p.astype(np.int32) for p in fmt.planes(buf))
+    fmt.planes(buf)                                 # the frame is checked before the window
     H, W = fmt.height, fmt.width
     y0, x0, h, w = (0, 0, H, W) if window is None else (int(v) for v in window)
     if y0 % 2 or x0 % 2:
         raise ValueError(f"decode_numpy_f32: the window origin ({y0}, {x0}) must be even for 4:2:0 frames")
     if y0 < 0 or x0 < 0 or h < 1 or w < 1 or y0 + h > H or x0 + w > W:
         raise ValueError(f"decode_numpy_f32: window {h} x {w} at ({y0}, {x0}) outside the {H} x {W} frame")
-    ch, cw = fmt.chroma_shape
-    ys, xs = np.arange(y0, y0 + h), np.arange(x0, x0 + w)
-    r0 = ys >> 1
-    r1 = np.clip(r0 + np.where(ys & 1, 1, -1), 0, ch - 1)
-    q0 = xs >> 1
-    if fmt.siting == "left":
-        q1 = np.minimum(q0 + 1, cw - 1)
-        wx0 = np.where(xs & 1, 2, 4).astype(np.int32)
-    else:
-        q1 = np.clip(q0 + np.where(xs & 1, 1, -1), 0, cw - 1)
-        wx0 = np.full(w, 3, np.int32)
-    wx1 = 4 - wx0
-
-    def up(c):
-        a = wx0 * c[:, q0] + wx1 * c[:, q1]
-        return (3 * a[r0] + a[r1] + 8) >> 4
-
-    (kY, kRV, kGU, kGV, kBU), _ = COEFFS10[fmt.matrix]
-    y, u, v = kY * (Y[y0:y0 + h, x0:x0 + w] - 64), up(U) - 512, up(V) - 512
-    half = 1 << 13
-    r = (y + kRV * v + half) >> 14
-    g = (y + kGU * u + kGV * v + half) >> 14
-    b = (y + kBU * u + half) >> 14
-    return np.clip(np.stack([r, g, b], axis=-1), 0, 1023).astype(np.float32) / np.float32(1023)
+    return _decode_window(buf, fmt, y0, x0, h, w, keep=True).astype(np.float32) / np.float32(1023)
 
 
 def encode_numpy(rgb, fmt: Format, bgr: bool = False) -> np.ndarray:

@@ -487,7 +487,8 @@ int64_t atmvfi_frame_difference_workspace_ints(int h, int w);
 int atmvfi_frame_difference(const void* a, const void* b, int H, int W, int bgr, int y0, int x0, int h, int w, int32_t* out /*[258]*/,
                             int32_t* workspace, int64_t workspace_ints, void* stream);
 
-/* Planar YUV 4:2:0 (I420) <-> RGB for the video loops (yuv.hip; atm-vfi_amd/yuv.py holds the format, the numpy twins and Y4M I/O).
+/* Planar YUV 4:2:0 (I420) <-> RGB for the video loops (yuv.hip decodes, yuv_encode.hip encodes, yuv_common.h holds the definition and
+ * the shared helpers; atm-vfi_amd/yuv.py holds the format, the numpy twins and Y4M I/O).
  * Nothing of the reference: its scripts read PNGs.  A bit-exact contract in int32 (>> is an arithmetic shift: floor).
  * Frame: one contiguous buffer Y [H,W], U [ch,cw], V [ch,cw], ch = (H + 1) / 2, cw = (W + 1) / 2, H, W >= 1 (odd sizes allowed);
  *   uint8 samples for depth 8, little-endian uint16 with values 0..1023 for depth 10 (decode only).
@@ -524,7 +525,7 @@ int atmvfi_yuv420_to_rgb(const void* yuv, int H, int W, int depth, int matrix, i
 int atmvfi_rgb_to_yuv420(const void* src_u8, int bgr, const float* src, int Hp, int Wp, int pad_top, int pad_left, int H, int W,
                          int matrix, int full_range, int siting, void* yuv, void* stream);
 
-/* One resident packed I420 frame -> the window of atmvfi_frame_u8_window, without the RGB frame in between (yuv_window.hip; ABI 0.17;
+/* One resident packed I420 frame -> the window of atmvfi_frame_u8_window, without the RGB frame in between (yuv.hip; ABI 0.17;
  * the Xiph 2K / 4K evaluation on Y4M clips, atm-vfi_amd/evaluate.py; host twin yuv.window_numpy).  Nothing of the reference: its script
  * converts the clips to rgb24 PNGs with ffmpeg first.  The frame layout, depth 8 / 10 (10-bit samples decode to clip8 RGB), matrix,
  * full_range and siting are exactly those of atmvfi_yuv420_to_rgb.  No new arithmetic: let q(Y, X) be the clip8 RGB pixel that
@@ -548,7 +549,7 @@ int atmvfi_rgb_to_yuv420(const void* src_u8, int bgr, const float* src, int Hp, 
 int atmvfi_yuv420_window(const void* yuv, int H, int W, int depth, int matrix, int full_range, int siting, int mode, int y0, int x0, int h,
                          int w, float* dst, int Hp, int Wp, int pad_top, int pad_left, void* dst_u8, void* stream);
 
-/* The same frames with the 10-bit depth kept end to end (yuv10.hip; ABI 0.15): 10-bit limited-range I420 (little-endian uint16, values
+/* The same frames with the 10-bit depth kept end to end (yuv.hip, yuv_encode.hip; ABI 0.15): 10-bit limited-range I420 (little-endian uint16, values
  * 0..1023; frame layout, matrix and siting as above) <-> fp32 planar RGB in units of 1 / 1023.  The calls above decode 10-bit samples
  * to clip8 RGB and encode 8-bit frames only; these hand the network q / 1023 and write its prediction back as 10-bit samples.  The
  * project's own bit-exact contract in int32 (>> floors); yuv.decode_numpy_f32 / yuv.encode_numpy give the same bits on the host.

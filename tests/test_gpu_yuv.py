@@ -1,4 +1,4 @@
-"""GPU: planar YUV 4:2:0 on the device (csrc/yuv.hip atmvfi_yuv420_to_rgb / atmvfi_rgb_to_yuv420, the ``pixfmt=`` argument of the video
+"""GPU: planar YUV 4:2:0 on the device (csrc/yuv.hip atmvfi_yuv420_to_rgb, csrc/yuv_encode.hip atmvfi_rgb_to_yuv420, the ``pixfmt=`` argument of the video
 loops, ``yuv.interpolate_y4m``): both kernels against the per-pixel model of tests/cpu_yuv.py bit for bit -- every matrix, range and
 siting, 10-bit, BGR, odd sizes, both the vector and the general path -- and the loops against the RGB loops on the decoded frames."""
 import importlib
@@ -141,6 +141,31 @@ def test_decode_1080p_once(ops, dev):
         assert torch.equal(df, ref)
         o8, of = decode_on_device(ops, dev, buf, fmt, False, (1088, 1920, 4, 0), offset=2)
         assert torch.equal(o8, d8) and torch.equal(of, df)
+
+
+def test_the_three_decode_entry_points_are_one_kernel(ops, dev):
+    """``yuv420_to_rgb`` is ``yuv420_window`` mode 0 with the window set to the whole frame -- the same bits in the canvas (padding
+    included) and in the uint8 frame -- and ``yuv420p10_to_f32`` walks a window the same way: the numpy twin's window, replicate padded.
+    On the aligned path, and behind a source pointer offset by 2 bytes on the general path."""
+    H, W = 20, 36
+    Hp, Wp, pt, pl = geo = (H + 5, W + 12, 3, 4)
+    y0, x0, h, w = window = (4, 8, 12, 24)
+    for k, (depth, siting) in enumerate(itertools.product((8, 10), ("centre", "left"))):
+        fmt = yuv.Format(H, W, ("bt601", "bt709")[k & 1], False, siting, depth)
+        buf = C.random_frame(H, W, depth, seed=40 + k)
+        for offset in (0, 2):
+            d8, df = decode_on_device(ops, dev, buf, fmt, False, geo, offset)
+            w8 = torch.full_like(d8, 0xA5)
+            wf = torch.full_like(df, float("nan"))
+            ops.yuv420_window(to_dev(buf, dev, offset), fmt, 0, 0, 0, H, W, dst=wf, dst_u8=w8, pad_top=pt, pad_left=pl)
+            assert torch.equal(w8, d8) and torch.equal(wf.view(torch.int32), df.view(torch.int32)), (depth, siting, offset)
+            assert not torch.isnan(df).any()
+            if depth == 10:
+                kf = torch.full((3, Hp, Wp), float("nan"), dtype=torch.float32, device=dev)
+                ops.yuv420p10_to_f32(to_dev(buf, dev, offset), fmt, kf, window=window, pad_top=pt, pad_left=pl)
+                inner = torch.from_numpy(yuv.decode_numpy_f32(buf, fmt, window)).permute(2, 0, 1)[None]
+                want = torch.nn.functional.pad(inner, [pl, Wp - pl - w, pt, Hp - pt - h], mode="replicate")[0]
+                assert torch.equal(kf.cpu().view(torch.int32), want.contiguous().view(torch.int32)), (siting, offset)
 
 
 # ------------------------------------------------------------------------------------------------ encode

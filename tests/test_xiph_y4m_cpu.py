@@ -70,7 +70,7 @@ def test_yuv420_window_abi_is_declared_exported_and_checks_on_the_host():
     assert re.search(r"\bint\s+" + name + r"\s*\(", hdr) and name in hip_ops.SIGNATURES and hasattr(lib, name)
     assert lib.atmvfi_plan_fn_id(name.encode()) >= 0
     assert (lib.atmvfi_version() >> 8) & 255 >= 17
-    assert "yuv_window.hip" in open(os.path.join(CS.ROOT, "atm-vfi_amd", "csrc", "Makefile")).read()
+    assert " yuv.hip" in open(os.path.join(CS.ROOT, "atm-vfi_amd", "csrc", "Makefile")).read()
     assert callable(hip_ops.HipOps.yuv420_window) and callable(yuv.window_numpy)
     P = 0x10000       # never dereferenced: every call below fails its host-side checks before a launch
     err = lib.atmvfi_last_error

@@ -1,4 +1,4 @@
-"""CPU: 10-bit depth kept end to end (``keep_depth``; include/atmvfi.h atmvfi_yuv420p10_to_f32 / atmvfi_f32_to_yuv420p10, csrc/yuv10.hip):
+"""CPU: 10-bit depth kept end to end (``keep_depth``; include/atmvfi.h atmvfi_yuv420p10_to_f32 / atmvfi_f32_to_yuv420p10, csrc/yuv.hip, yuv_encode.hip):
 the coefficient table in all its places, the numpy twins against the per-pixel model of tests/cpu_yuv10.py, accumulator bounds, grey
 neutrality and round trips, the q / 1023 shortcut of the kernel, ties and clamps of the encode, the ABI's host-side checks, and the
 loops / ``interpolate_y4m`` with ``keep_depth=True`` through the generic (no-GPU) path."""
@@ -41,7 +41,7 @@ def _ints(text):
 def test_coefficients_table_derivation_header_and_kernel_agree():
     assert set(yuv.COEFFS10) == {"bt601", "bt709"}
     hdr = open(os.path.join(CS.ROOT, "include", "atmvfi.h")).read()
-    src = open(os.path.join(CS.ROOT, "atm-vfi_amd", "csrc", "yuv10.hip")).read()
+    src = open(os.path.join(CS.ROOT, "atm-vfi_amd", "csrc", "yuv_common.h")).read()
     table = re.search(r"kCoeffs10\[2\]\s*=\s*\{(.*?)\n\};", src, flags=re.S).group(1)
     rows = [_ints(line) for line in table.splitlines() if re.search(r"\{\{", line)]
     assert len(rows) == 2
@@ -197,13 +197,13 @@ def fl(x):
 
 
 def test_the_kernels_multiply_add_form_of_q_over_1023_is_the_fp32_division():
-    """csrc/yuv10.hip writes q / 1023 as y = fl(q r), fl(y + fl(q - 1023 y) r) with r = fl(1 / 1023) and fused multiply-adds (one
+    """csrc/yuv_common.h writes q / 1023 as y = fl(q r), fl(y + fl(q - 1023 y) r) with r = fl(1 / 1023) and fused multiply-adds (one
     rounding each).  In exact rational arithmetic, for every q in 0..1023: the bits of the fp32 division; and the encode's pixel of
     that value is q again."""
     Fr = Fraction
     r = fl(Fr(1, 1023))
     assert float(r).hex() == "0x1.0040100000000p-10"
-    src = open(os.path.join(CS.ROOT, "atm-vfi_amd", "csrc", "yuv10.hip")).read()
+    src = open(os.path.join(CS.ROOT, "atm-vfi_amd", "csrc", "yuv_common.h")).read()
     assert "0x1.00401p-10f" in src and "-1023.0f" in src                       # the kernel's constants
     plain = 0
     for q in range(1024):
@@ -258,7 +258,8 @@ def test_yuv10_abi_is_declared_exported_and_checks_on_the_host():
         assert re.search(r"\bint\s+" + name + r"\s*\(", hdr) and name in hip_ops.SIGNATURES and hasattr(lib, name)
         assert lib.atmvfi_plan_fn_id(name.encode()) >= 0
     assert (lib.atmvfi_version() >> 8) & 255 >= 15
-    assert "yuv10.hip" in open(os.path.join(CS.ROOT, "atm-vfi_amd", "csrc", "Makefile")).read()
+    mk = open(os.path.join(CS.ROOT, "atm-vfi_amd", "csrc", "Makefile")).read()
+    assert " yuv.hip" in mk and " yuv_encode.hip" in mk
     assert callable(hip_ops.HipOps.yuv420p10_to_f32) and callable(hip_ops.HipOps.f32_to_yuv420p10)
     P = 0x10000       # never dereferenced: every call below fails its host-side checks before a launch
     err = lib.atmvfi_last_error

@@ -45,6 +45,18 @@ def test_coefficients_are_the_table_and_the_float64_derivation():
         assert [sum(r) for r in enc] == [16384 if f else 14071, 0, 0]
 
 
+def test_the_kernels_8_bit_table_is_the_derivation():
+    """kCoeffs[2][2] of csrc/yuv_common.h, [matrix][full_range], read from the source: yuv.COEFFS and the float64 derivation."""
+    src = open(os.path.join(CS.ROOT, "atm-vfi_amd", "csrc", "yuv_common.h")).read()
+    table = re.search(r"kCoeffs\[2\]\[2\]\s*=\s*\{(.*?)\n\};", src, flags=re.S).group(1)
+    rows = [[int(v) for v in re.findall(r"-?\d+", line.split("//")[0])] for line in table.splitlines() if re.search(r"\{\{", line)]
+    assert len(rows) == 4 and all(len(r) == 14 for r in rows)
+    for k, (m, f) in enumerate(itertools.product(("bt601", "bt709"), (False, True))):
+        dec, enc = yuv.COEFFS[m, f]
+        assert rows[k] == list(dec) + [v for r in enc for v in r], (m, f, rows[k])
+        assert (rows[k][:5], [rows[k][5 + 3 * i:8 + 3 * i] for i in range(3)]) == yuv.derive_coeffs(m, f), (m, f)
+
+
 def test_format():
     f = yuv.Format(1080, 1920)
     assert f.matrix == "bt709" and yuv.Format(719, 1280).matrix == "bt601" and yuv.Format(720, 2, "bt601").matrix == "bt601"
@@ -393,7 +405,8 @@ def test_yuv_abi_is_declared_exported_and_checks_on_the_host():
         assert re.search(r"\bint\s+" + name + r"\s*\(", hdr) and name in hip_ops.SIGNATURES and hasattr(lib, name)
         assert lib.atmvfi_plan_fn_id(name.encode()) >= 0
     assert (lib.atmvfi_version() >> 8) & 255 >= 14
-    assert "yuv.hip" in open(os.path.join(CS.ROOT, "atm-vfi_amd", "csrc", "Makefile")).read()
+    mk = open(os.path.join(CS.ROOT, "atm-vfi_amd", "csrc", "Makefile")).read()
+    assert " yuv.hip" in mk and " yuv_encode.hip" in mk
     assert callable(hip_ops.HipOps.yuv420_to_rgb) and callable(hip_ops.HipOps.rgb_to_yuv420)
     P = 0x10000       # never dereferenced: every call below fails its host-side checks before a launch
     err = lib.atmvfi_last_error
@@ -430,7 +443,7 @@ def test_yuv_abi_is_declared_exported_and_checks_on_the_host():
 
 
 def test_the_kernels_multiply_add_form_of_q_over_255_is_the_fp32_division():
-    """csrc/yuv.hip writes q / 255 as y = fl(q r), fl(y + fl(q - 255 y) r) with r = fl(1 / 255) and fused multiply-adds (one rounding
+    """csrc/yuv_common.h writes q / 255 as y = fl(q r), fl(y + fl(q - 255 y) r) with r = fl(1 / 255) and fused multiply-adds (one rounding
     each).  In exact rational arithmetic, for every q in 0..255: the bits of the fp32 division (what frame_u8_to_f32 computes)."""
     from fractions import Fraction as Fr
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Time the YUV 4:2:0 kernels (atm-vfi_amd/csrc/yuv.hip: atmvfi_yuv420_to_rgb, atmvfi_rgb_to_yuv420) on the method of
+"""Time the YUV 4:2:0 kernels (atm-vfi_amd/csrc/yuv.hip: atmvfi_yuv420_to_rgb; yuv_encode.hip: atmvfi_rgb_to_yuv420) on the method of
 tools/bench_frames.py: device events around ``--iters`` back-to-back calls after 24 warm-up calls, the calls rotating over
 ``--buffers`` distinct sources and destinations, every configuration timed ``--repeats`` times in rotation (median, min - max).  Bytes
 are the algorithm's -- inputs read once, outputs written once -- as a share of 6.3 TB/s.  Sizes 480 x 832, 1080 x 1920, 2160 x 4096,
@@ -10,7 +10,9 @@ and ``frame_f32_to_u8`` (15 B/px against the encode's 13.5).  The last column is
 
 ``--pipeline N``: ``FramePipeline`` on N 1080p pairs (network_base, synthetic weights) with and without ``pixfmt``, interleaved.
 
-    python tools/bench_yuv.py [--iters 240] [--repeats 5] [--buffers 12] [--pipeline 0] [--json OUT]"""
+    python tools/bench_yuv.py [--iters 240] [--repeats 5] [--buffers 12] [--pipeline 0] [--json OUT] [--lib PATH] [--baseline-lib PATH]
+
+``--baseline-lib``: tools/yuv_timing.py."""
 import argparse
 import importlib
 import json
@@ -24,25 +26,11 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-hip_ops = importlib.import_module("atm-vfi_amd.hip_ops")
 host_io = importlib.import_module("atm-vfi_amd.host_io")
 yuv = importlib.import_module("atm-vfi_amd.yuv")
+import yuv_timing  # noqa: E402  (tools/yuv_timing.py: timed(), the rotation, --baseline-lib)
 HBM = 6.3e12
 SIZES = [(480, 832), (1080, 1920), (2160, 4096)]
-
-
-def timed(fn, iters):
-    """us per call of fn(i), i = 0 .. iters-1 back to back."""
-    for i in range(24):
-        fn(i)
-    torch.cuda.synchronize()
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    s.record()
-    for i in range(iters):
-        fn(i)
-    e.record()
-    e.synchronize()
-    return s.elapsed_time(e) * 1e3 / iters
 
 
 def configs(ops, dev, H, W, n):
@@ -117,20 +105,19 @@ def main():
     ap.add_argument("--buffers", type=int, default=12)
     ap.add_argument("--pipeline", type=int, default=0, help="pairs per FramePipeline run (0: skip)")
     ap.add_argument("--json", default=None)
+    yuv_timing.add_library_arguments(ap)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_yuv: no GPU")
     dev = torch.device("cuda:0")
     torch.set_grad_enabled(False)
-    ops = hip_ops.HipOps(dev)
+    ops, base_ops = yuv_timing.libraries(a, dev)
     n = max(1, a.buffers)
     rows = []
     for H, W in SIZES:
         cfg = configs(ops, dev, H, W, n)
-        times = {k: [] for k in cfg}
-        for _ in range(a.repeats):           # in rotation: every repeat visits every configuration once
-            for k, (fn, _, _) in cfg.items():
-                times[k].append(timed(fn, a.iters))
+        base_cfg = configs(base_ops, dev, H, W, n) if base_ops else None
+        times, base = yuv_timing.rotation(cfg, base_cfg, a.repeats, a.iters)          # every repeat visits every configuration once
         med = {k: statistics.median(t) for k, t in times.items()}
         print(f"--- {H} x {W}", flush=True)
         for k, (_, nbytes, ref) in cfg.items():
@@ -139,10 +126,10 @@ def main():
                    "GBps": nbytes / (med[k] * 1e-6) / 1e9, "share_of_hbm": nbytes / (med[k] * 1e-6) / HBM,
                    "over_yardstick": med[k] / med[ref] if ref else None, "repeats_us": t}
             rows.append(row)
-            rel = f"  {row['over_yardstick']:5.2f} x its yardstick" if ref else ""
+            rel = (f"  {row['over_yardstick']:5.2f} x its yardstick" if ref else "") + yuv_timing.against_baseline(row, times, base, k)
             print(f"{k:>44}: {med[k]:8.2f} us (min {min(t):.2f}, max {max(t):.2f} over {len(t)} repeats)  {nbytes / 1e6:6.1f} MB  "
                   f"{row['GBps']:7.1f} GB/s  {100 * row['share_of_hbm']:5.1f}% of 6.3 TB/s{rel}", flush=True)
-        del cfg
+        del cfg, base_cfg
         torch.cuda.empty_cache()
     if a.pipeline > 0:
         rows += pipeline(dev, a.pipeline, 3)

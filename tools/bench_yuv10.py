@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Time the depth-keeping 10-bit YUV kernels (atm-vfi_amd/csrc/yuv10.hip: atmvfi_yuv420p10_to_f32, atmvfi_f32_to_yuv420p10) beside
+"""Time the depth-keeping 10-bit YUV kernels (atm-vfi_amd/csrc/yuv.hip: atmvfi_yuv420p10_to_f32; yuv_encode.hip: atmvfi_f32_to_yuv420p10) beside
 the calls they stand next to, on the protocol of tools/bench_yuv.py: device events around ``--iters`` back-to-back calls after 24
 warm-up calls, the calls rotating over ``--buffers`` distinct sources and destinations, every configuration timed ``--repeats`` times
 in rotation in one process (median, min - max).  Bytes are the algorithm's -- inputs read once, outputs written once -- as a share of
@@ -12,7 +12,9 @@ its neighbour's time plus 15 %; the last column says whether it does.
 ``--pipeline N``: ``FramePipeline`` on N 1080p pairs of 10-bit input (network_base, synthetic weights) with ``keep_depth`` off and on,
 interleaved.
 
-    python tools/bench_yuv10.py [--iters 240] [--repeats 5] [--buffers 12] [--pipeline 0] [--json OUT]"""
+    python tools/bench_yuv10.py [--iters 240] [--repeats 5] [--buffers 12] [--pipeline 0] [--json OUT] [--lib PATH] [--baseline-lib PATH]
+
+``--baseline-lib``: tools/yuv_timing.py."""
 import argparse
 import importlib
 import json
@@ -26,26 +28,12 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-hip_ops = importlib.import_module("atm-vfi_amd.hip_ops")
 host_io = importlib.import_module("atm-vfi_amd.host_io")
 yuv = importlib.import_module("atm-vfi_amd.yuv")
+import yuv_timing  # noqa: E402  (tools/yuv_timing.py: timed(), the rotation, --baseline-lib)
 HBM = 6.3e12
 SIZES = [(1080, 1920), (2160, 4096)]
 BOUND = 1.15
-
-
-def timed(fn, iters):
-    """us per call of fn(i), i = 0 .. iters-1 back to back."""
-    for i in range(24):
-        fn(i)
-    torch.cuda.synchronize()
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    s.record()
-    for i in range(iters):
-        fn(i)
-    e.record()
-    e.synchronize()
-    return s.elapsed_time(e) * 1e3 / iters
 
 
 def configs(ops, dev, H, W, n):
@@ -109,20 +97,19 @@ def main():
     ap.add_argument("--buffers", type=int, default=12)
     ap.add_argument("--pipeline", type=int, default=0, help="pairs per FramePipeline run (0: skip)")
     ap.add_argument("--json", default=None)
+    yuv_timing.add_library_arguments(ap)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_yuv10: no GPU")
     dev = torch.device("cuda:0")
     torch.set_grad_enabled(False)
-    ops = hip_ops.HipOps(dev)
+    ops, base_ops = yuv_timing.libraries(a, dev)
     n = max(1, a.buffers)
     rows = []
     for H, W in SIZES:
         cfg = configs(ops, dev, H, W, n)
-        times = {k: [] for k in cfg}
-        for _ in range(a.repeats):           # in rotation: every repeat visits every configuration once
-            for k, (fn, _, _) in cfg.items():
-                times[k].append(timed(fn, a.iters))
+        base_cfg = configs(base_ops, dev, H, W, n) if base_ops else None
+        times, base = yuv_timing.rotation(cfg, base_cfg, a.repeats, a.iters)          # every repeat visits every configuration once
         med = {k: statistics.median(t) for k, t in times.items()}
         print(f"--- {H} x {W}", flush=True)
         for k, (_, nbytes, ref) in cfg.items():
@@ -134,9 +121,10 @@ def main():
             rel = ""
             if ref:
                 rel = f"  {row['over_neighbour']:5.2f} x its neighbour: {'meets' if row['over_neighbour'] <= BOUND else 'MISSES'} the +15 % bound"
+            rel += yuv_timing.against_baseline(row, times, base, k)
             print(f"{k:>42}: {med[k]:8.2f} us (min {min(t):.2f}, max {max(t):.2f} over {len(t)} repeats)  {nbytes / 1e6:6.1f} MB  "
                   f"{row['GBps']:7.1f} GB/s  {100 * row['share_of_hbm']:5.1f}% of 6.3 TB/s{rel}", flush=True)
-        del cfg
+        del cfg, base_cfg
         torch.cuda.empty_cache()
     if a.pipeline > 0:
         rows += pipeline(dev, a.pipeline, 3)

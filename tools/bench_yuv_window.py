@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Time the fused decode-window kernel (atm-vfi_amd/csrc/yuv_window.hip: atmvfi_yuv420_window) on the protocol of tools/bench_yuv.py:
+"""Time the fused decode-window kernel (atm-vfi_amd/csrc/yuv.hip: atmvfi_yuv420_window) on the protocol of tools/bench_yuv.py:
 device events around ``--iters`` back-to-back calls after 24 warm-up calls, the calls rotating over ``--buffers`` distinct sources and
 destinations, every configuration timed ``--repeats`` times in rotation (median, min - max).  Sizes 2160 x 4096 (10 bit, bt709: a
 Xiph clip) and 1080 x 1920 (8 bit), each with the two windows of the Xiph evaluation (``evaluate.xiph_geometry``): mode 1 on the whole
@@ -12,7 +12,9 @@ call takes no longer than the sum of its two composition calls (it performs the 
 one read of the RGB frame, and in mode 0 decodes a quarter of the pixels).  Bytes are the algorithm's -- inputs read once, outputs
 written once -- as a share of 6.3 TB/s.
 
-    python tools/bench_yuv_window.py [--iters 120] [--repeats 5] [--buffers 8] [--json OUT]"""
+    python tools/bench_yuv_window.py [--iters 120] [--repeats 5] [--buffers 8] [--json OUT] [--lib PATH] [--baseline-lib PATH]
+
+``--baseline-lib``: tools/yuv_timing.py."""
 import argparse
 import importlib
 import json
@@ -24,26 +26,12 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-hip_ops = importlib.import_module("atm-vfi_amd.hip_ops")
 host_io = importlib.import_module("atm-vfi_amd.host_io")
 evaluate = importlib.import_module("atm-vfi_amd.evaluate")
 yuv = importlib.import_module("atm-vfi_amd.yuv")
+import yuv_timing  # noqa: E402  (tools/yuv_timing.py: timed(), the rotation, --baseline-lib)
 HBM = 6.3e12
 SIZES = [(2160, 4096, 10), (1080, 1920, 8)]
-
-
-def timed(fn, iters):
-    """us per call of fn(i), i = 0 .. iters-1 back to back."""
-    for i in range(24):
-        fn(i)
-    torch.cuda.synchronize()
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    s.record()
-    for i in range(iters):
-        fn(i)
-    e.record()
-    e.synchronize()
-    return s.elapsed_time(e) * 1e3 / iters
 
 
 def configs(ops, dev, H, W, depth, n):
@@ -86,20 +74,19 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--buffers", type=int, default=8)
     ap.add_argument("--json", default=None)
+    yuv_timing.add_library_arguments(ap)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_yuv_window: no GPU")
     dev = torch.device("cuda:0")
     torch.set_grad_enabled(False)
-    ops = hip_ops.HipOps(dev)
+    ops, base_ops = yuv_timing.libraries(a, dev)
     n = max(1, a.buffers)
     rows = []
     for H, W, depth in SIZES:
         cfg = configs(ops, dev, H, W, depth, n)
-        times = {k: [] for k in cfg}
-        for _ in range(a.repeats):           # in rotation: every repeat visits every configuration once
-            for k, (fn, _, _) in cfg.items():
-                times[k].append(timed(fn, a.iters))
+        base_cfg = configs(base_ops, dev, H, W, depth, n) if base_ops else None
+        times, base = yuv_timing.rotation(cfg, base_cfg, a.repeats, a.iters)          # every repeat visits every configuration once
         med = {k: statistics.median(t) for k, t in times.items()}
         print(f"--- {H} x {W}, {depth} bit, {yuv.Format(H, W, depth=depth).matrix}", flush=True)
         for k, (_, nbytes, parts) in cfg.items():
@@ -113,10 +100,11 @@ def main():
                 row.update({"composition_us_median": total, "composition_us_min": lo, "composition_us_max": hi, "over_composition": med[k] / total,
                             "within_expectation": bool(min(t) <= hi)})
                 rel = f"  composition {total:8.2f} us (min {lo:.2f}, max {hi:.2f}): fused = {med[k] / total:5.2f} x"
+            rel += yuv_timing.against_baseline(row, times, base, k)
             rows.append(row)
             print(f"{k:>58}: {med[k]:8.2f} us (min {min(t):.2f}, max {max(t):.2f} over {len(t)} repeats)  {nbytes / 1e6:6.1f} MB  "
                   f"{row['GBps']:7.1f} GB/s  {100 * row['share_of_hbm']:5.1f}% of 6.3 TB/s{rel}", flush=True)
-        del cfg
+        del cfg, base_cfg
         torch.cuda.empty_cache()
     if a.json:
         with open(a.json, "w") as f:
