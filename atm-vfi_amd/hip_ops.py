@@ -138,6 +138,9 @@ SIGNATURES = {
     "atmvfi_frame_signature": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_l, c_f]),
     "atmvfi_frame_difference_workspace_ints": (c_l, [c_i, c_i]),
     "atmvfi_frame_difference": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_l, c_f]),
+    "atmvfi_shutter_accumulate": (c_i, [c_f, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f]),
+    "atmvfi_shutter_resolve": (c_i, [c_f, c_i, c_i, c_i, c_i, c_f, c_i, c_f]),
+    "atmvfi_shutter_table": (c_i, [c_i, ctypes.POINTER(ctypes.c_uint16)]),
     "atmvfi_yuv420_to_rgb": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_f, c_i, c_i, c_i, c_i, c_f]),
     "atmvfi_yuv420_window": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f, c_f]),
     "atmvfi_rgb_to_yuv420": (c_i, [c_f, c_i, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f]),
@@ -1358,6 +1361,54 @@ class HipOps:
         self._check(self.lib.atmvfi_frame_difference(_ptr(a), _ptr(b), sh, sw, int(bool(bgr)), int(y0), int(x0), h, w, _ptr(out),
                                                      _ptr(workspace), workspace.numel(), self._stream()), "frame_difference")
         return out
+
+    def shutter_accumulate(self, acc, src=None, src_u8=None, weight: int = 1, light: str = "linear", first: bool = False, pad_top: int = 0,
+                           pad_left: int = 0, bgr: bool = False):
+        """One sample of a blurred output into its accumulator: ``acc`` (contiguous CUDA int32 [3,h,w], always R, G, B) ``=`` (``first``:
+        nothing is read, nothing needs zeroing) or ``+=`` ``weight * LUT[q]``, q the uint8 pixel of ``src`` -- fp32 planar RGB
+        [3,Hp,Wp] with the window at (pad_top, pad_left): ``frame_f32_to_u8``'s pixel -- or of ``src_u8`` -- uint8 [h,w,3], BGR if
+        ``bgr`` -- exactly one (include/atmvfi.h atmvfi_shutter_accumulate; ``shutter.blend_numpy`` is the host twin).  Not part of a
+        forward: never recorded into a launch plan."""
+        from .shutter import LIGHTS
+        if acc.dtype != torch.int32 or acc.dim() != 3 or acc.shape[0] != 3 or not acc.is_contiguous() or not acc.is_cuda:
+            raise ValueError("shutter_accumulate: acc must be a contiguous CUDA int32 [3,h,w] tensor")
+        if (src is None) == (src_u8 is None):
+            raise ValueError("shutter_accumulate: give exactly one of src and src_u8")
+        if light not in LIGHTS:
+            raise ValueError(f"shutter_accumulate: light must be one of {LIGHTS}, got {light!r}")
+        h, w = acc.shape[1:]
+        hp = wp = 0
+        if src is not None:
+            _f32_canvas(src, "shutter_accumulate: src")
+            hp, wp = src.shape[1:]
+        else:
+            _u8_frame(src_u8, "shutter_accumulate: src_u8", (h, w))
+        self._check(self.lib.atmvfi_shutter_accumulate(_ptr(acc), h, w, _ptr(src), hp, wp, int(pad_top), int(pad_left), _ptr(src_u8),
+                                                       int(bool(bgr)), int(weight), LIGHTS.index(light), int(bool(first)), self._stream()),
+                    "shutter_accumulate")
+
+    def shutter_resolve(self, acc, total_weight: int, dst_u8, light: str = "linear", bgr: bool = False):
+        """``acc`` (int32 [3,h,w], the sum of ``shutter_accumulate`` calls whose weights add up to ``total_weight``) -> ``dst_u8`` uint8
+        [h,w,3] (BGR if ``bgr``): the rounded mean in the light table's domain and the nearest code (include/atmvfi.h
+        atmvfi_shutter_resolve).  Never recorded into a launch plan."""
+        from .shutter import LIGHTS
+        if acc.dtype != torch.int32 or acc.dim() != 3 or acc.shape[0] != 3 or not acc.is_contiguous() or not acc.is_cuda:
+            raise ValueError("shutter_resolve: acc must be a contiguous CUDA int32 [3,h,w] tensor")
+        if light not in LIGHTS:
+            raise ValueError(f"shutter_resolve: light must be one of {LIGHTS}, got {light!r}")
+        h, w = acc.shape[1:]
+        _u8_frame(dst_u8, "shutter_resolve: dst_u8", (h, w))
+        self._check(self.lib.atmvfi_shutter_resolve(_ptr(acc), h, w, int(total_weight), LIGHTS.index(light), _ptr(dst_u8), int(bool(bgr)),
+                                                    self._stream()), "shutter_resolve")
+
+    def shutter_table(self, light: str):
+        """The library's literal light table as a tuple of 256 ints (``shutter.SHUTTER_TABLES[light]`` on the host side)."""
+        from .shutter import LIGHTS
+        if light not in LIGHTS:
+            raise ValueError(f"shutter_table: light must be one of {LIGHTS}, got {light!r}")
+        out = (ctypes.c_uint16 * 256)()
+        self._check(self.lib.atmvfi_shutter_table(LIGHTS.index(light), out), "shutter_table")
+        return tuple(out)
 
     def yuv420_to_rgb(self, yuv, fmt, dst_u8=None, dst=None, pad_top: int = 0, pad_left: int = 0, bgr: bool = False):
         """One packed planar I420 frame of ``fmt`` (a ``yuv.Format``; a contiguous CUDA uint8 tensor of ``fmt.frame_bytes`` bytes, any

@@ -252,10 +252,17 @@ class _SegmentRunner:
     ``run(..., levels=, emit=)`` (``retime.interpolate_video_retimed``): a sparse schedule (``retime.sparse_levels``) instead of the full
     recursion, and the positions that leave for the host -- the others are ancestors only and stay in the pool.  ``out_slots``: the size
     of the output ring (default N - 1: every position); ``batch_sizes``: the batch sizes a sparse schedule can bring (default: those of
-    the full recursion)."""
+    the full recursion).
+
+    ``blend=(light, entries)`` and ``run(..., blend=ops)`` (``retime.interpolate_video_retimed(shutter=)``): a sample is accumulated
+    (``atmvfi_shutter_accumulate``) where it would have been converted for the output ring -- from the fp32 prediction, with ``tta`` from
+    ``tta_merge``'s uint8 pixels, positions 0 and N and the copies of a cut segment from the pool's resident canvases -- and an output
+    that closes is resolved (``atmvfi_shutter_resolve``) into an output ring entry (with an 8-bit ``out_fmt`` into a uint8 RGB buffer
+    that ``rgb_to_yuv420`` encodes) and leaves by the same device -> host copy.  ``ops``: ``shutter._plan``'s, a close as
+    ``("close", m)`` or, for an output the caller serves itself, ``("drop", m)``."""
 
     def __init__(self, model, ops, dev, height, width, factor, crop, bgr, divisor, tta, max_batch, pool, out_fmt=None, deep_fmt=None,
-                 out_slots=None, batch_sizes=None):
+                 out_slots=None, batch_sizes=None, blend=None):
         import torch
         from .host_io import InputPadder
         self.torch, self.model, self.ops, self.dev = torch, model, ops, dev
@@ -293,6 +300,17 @@ class _SegmentRunner:
         self.out_fmt, self.deep_fmt = out_fmt, deep_fmt
         out_shape = (self.h, self.w, 3) if out_fmt is None else (out_fmt.frame_bytes,)
         n_out = factor - 1 if out_slots is None else max(1, min(int(out_slots), factor - 1))
+        # blend = (light, entries) (``retime.interpolate_video_retimed(shutter=)``): the output ring holds the outputs one ``run`` can
+        # close, and samples are gathered in int32 accumulators of the window's size.  They are allocated on demand, one per output that
+        # is open at the same time -- the level-ordered schedule visits a segment's samples out of time order, so every output a segment
+        # touches is open until the segment ends -- returned to a free list when their output closes, and kept until the runner goes
+        self.blend = None
+        if blend is not None:
+            if deep_fmt is not None:
+                raise ValueError("_SegmentRunner: a blend of 10-bit frames is not supported")
+            n_out = max(1, int(blend[1]))
+            self.blend = {"light": blend[0], "accs": [], "free": [], "of": {},
+                          "u8": torch.empty(self.h, self.w, 3, dtype=torch.uint8, device=dev) if (out_fmt is not None or self.tta) else None}
         self.out_d = torch.empty(n_out, *out_shape, dtype=torch.uint8, device=dev)
         self.out_h = [torch.empty(n_out, *out_shape, dtype=torch.uint8).pin_memory() for _ in range(2)]
         self.merged = None
@@ -356,13 +374,46 @@ class _SegmentRunner:
         self.ops.pool_blocks(self.frames[k], lefts + rights, g)
         return self.model.forward(g[:b], g[b:])["I_t"]
 
-    def run(self, up: _Uploader, slot_a, slot_b, cut: bool = False, levels=None, emit=None):
+    def _run_levels(self, levels, wanted, sink):
+        """The schedule level by level in batches of at most ``max_batch`` pairs: ``sink(pos, pred, flip)`` for every produced position
+        in ``wanted`` (None: all of them) -- ``pred`` the fp32 prediction [3,Hp,Wp], ``flip`` that of the rotated frames with ``tta``
+        (else None) -- the others are ancestors only; what a later level reads goes back into the pool."""
+        torch = self.torch
+        last = max((li for li, lv in enumerate(levels) if lv), default=0)
+        for li, level in enumerate(levels):
+            for i in range(0, len(level), self.max_batch):
+                chunk = level[i:i + self.max_batch]
+                lefts = [self.phys[a] for a, _, _ in chunk]
+                rights = [self.phys[b] for _, b, _ in chunk]
+                outs = [self.phys[o] for _, _, o in chunk]
+                pred = self._forward(0, lefts, rights)
+                shown = [wanted is None or pos in wanted for _, _, pos in chunk]
+                flip = self._forward(1, lefts, rights) if self.tta and any(shown) else None
+                for j, (_, _, pos) in enumerate(chunk):
+                    if shown[j]:                       # (else an ancestor only: it stays in the pool)
+                        sink(pos, pred[j], None if flip is None else flip[j])
+                if li < last:                          # the next level reads these frames (the un-averaged prediction)
+                    self.ops.pool_blocks(self.frames[0], outs, pred, to_pool=True)
+                    if self.tta:
+                        rot = self.gather.get(("rot", len(chunk)))
+                        if rot is None:
+                            rot = self.gather[("rot", len(chunk))] = torch.empty_like(pred)
+                        self.ops.frame_rot180(pred, rot)
+                        self.ops.pool_blocks(self.frames[1], outs, rot, to_pool=True)
+                    if self.pools:
+                        for p in self.pools:
+                            for s in outs:
+                                p.invalidate(s)
+
+    def run(self, up: _Uploader, slot_a, slot_b, cut: bool = False, levels=None, emit=None, blend=None):
         """Enqueue one segment: ``slot_a`` (None when the previous segment's second frame is this one's first) and ``slot_b`` are
         upload slots.  Returns a handle for ``result``.  ``cut`` (a scene cut: the caller emits copies of the originals): the source
         frames still take their places -- position N's frame, with tokens marked stale, is the next segment's position 0 whatever this
         segment was -- but no forward runs, nothing is written to the middle slots or the output ring, and None is returned.
         ``levels`` (default: the full recursion) / ``emit`` (default: every position): the schedule to run and the positions, in the
-        order of ``result``, that are written to the output ring; ``emit`` holds at most ``out_slots`` positions, all in ``levels``."""
+        order of ``result``, that are written to the output ring; ``emit`` holds at most ``out_slots`` positions, all in ``levels``.
+        ``blend`` (default None: all of the above; else without ``emit``): the segment's samples are accumulated and the outputs that
+        close here resolved, see the class comment; a handle is returned also for a cut, ``result(handle, closes)`` gives the frames."""
         torch, n = self.torch, self.n
         levels = self.levels if levels is None else levels
         index = None if emit is None else {pos: k for k, pos in enumerate(emit)}       # position -> output ring entry
@@ -377,53 +428,32 @@ class _SegmentRunner:
                 up.take(slot_a, self._convert_into(0))
                 self.have_first = True
             up.take(slot_b, self._convert_into(n))
+            if blend is not None:
+                return self._run_blended([] if cut else levels, blend, cut)
             if cut:
                 return None
             ring = self.seg & 1
             self.seg += 1
-            last = max((li for li, lv in enumerate(levels) if lv), default=0)
-            for li, level in enumerate(levels):
-                for i in range(0, len(level), self.max_batch):
-                    chunk = level[i:i + self.max_batch]
-                    lefts = [self.phys[a] for a, _, _ in chunk]
-                    rights = [self.phys[b] for _, b, _ in chunk]
-                    outs = [self.phys[o] for _, _, o in chunk]
-                    pred = self._forward(0, lefts, rights)
-                    shown = [index is None or pos in index for _, _, pos in chunk]
-                    flip = self._forward(1, lefts, rights) if self.tta and any(shown) else None
-                    for j, (_, _, pos) in enumerate(chunk):
-                        if not shown[j]:               # an ancestor only: it stays in the pool
-                            continue
-                        u8 = self.out_d[pos - 1 if index is None else index[pos]]
-                        if self.deep_fmt is not None:
-                            src = pred[j]
-                            if self.tta:               # the fp32 average, then its encoding
-                                self.ops.tta_merge(pred[j], flip[j], out=self.merged)
-                                src = self.merged
-                            self.ops.f32_to_yuv420p10(u8, self.out_fmt, src, pad_top=self.pad_top, pad_left=self.pad_left)
-                        elif self.out_fmt is not None:
-                            if self.tta:               # the average's uint8 pixels, then their encoding
-                                self.ops.tta_merge(pred[j], flip[j], out_u8=self.merged, pad_top=self.pad_top, pad_left=self.pad_left,
-                                                   bgr=False)
-                                self.ops.rgb_to_yuv420(u8, self.out_fmt, src_u8=self.merged)
-                            else:
-                                self.ops.rgb_to_yuv420(u8, self.out_fmt, src=pred[j], pad_top=self.pad_top, pad_left=self.pad_left)
-                        elif self.tta:
-                            self.ops.tta_merge(pred[j], flip[j], out_u8=u8, pad_top=self.pad_top, pad_left=self.pad_left, bgr=self.bgr)
-                        else:
-                            self.ops.frame_f32_to_u8(pred[j], u8, self.pad_top, self.pad_left, self.bgr)
-                    if li < last:                      # the next level reads these frames (the un-averaged prediction)
-                        self.ops.pool_blocks(self.frames[0], outs, pred, to_pool=True)
-                        if self.tta:
-                            rot = self.gather.get(("rot", len(chunk)))
-                            if rot is None:
-                                rot = self.gather[("rot", len(chunk))] = torch.empty_like(pred)
-                            self.ops.frame_rot180(pred, rot)
-                            self.ops.pool_blocks(self.frames[1], outs, rot, to_pool=True)
-                        if self.pools:
-                            for p in self.pools:
-                                for s in outs:
-                                    p.invalidate(s)
+
+            def to_ring(pos, pred, flip):
+                u8 = self.out_d[pos - 1 if index is None else index[pos]]
+                if self.deep_fmt is not None:
+                    src = pred
+                    if self.tta:                       # the fp32 average, then its encoding
+                        self.ops.tta_merge(pred, flip, out=self.merged)
+                        src = self.merged
+                    self.ops.f32_to_yuv420p10(u8, self.out_fmt, src, pad_top=self.pad_top, pad_left=self.pad_left)
+                elif self.out_fmt is not None:
+                    if self.tta:                       # the average's uint8 pixels, then their encoding
+                        self.ops.tta_merge(pred, flip, out_u8=self.merged, pad_top=self.pad_top, pad_left=self.pad_left, bgr=False)
+                        self.ops.rgb_to_yuv420(u8, self.out_fmt, src_u8=self.merged)
+                    else:
+                        self.ops.rgb_to_yuv420(u8, self.out_fmt, src=pred, pad_top=self.pad_top, pad_left=self.pad_left)
+                elif self.tta:
+                    self.ops.tta_merge(pred, flip, out_u8=u8, pad_top=self.pad_top, pad_left=self.pad_left, bgr=self.bgr)
+                else:
+                    self.ops.frame_f32_to_u8(pred, u8, self.pad_top, self.pad_left, self.bgr)
+            self._run_levels(levels, index, to_ring)
             cur = torch.cuda.current_stream(self.dev)
             self.done.record(cur)
             self.copy_out.wait_event(self.done)
@@ -436,6 +466,96 @@ class _SegmentRunner:
             # out_d is rewritten by the next segment: its kernels wait for this copy
             cur.wait_event(self.out_evt[ring])
             return ring
+
+    # -- synthetic shutter
+    def _accumulate(self, m, w, src=None, src_u8=None):
+        st = self.blend
+        a = st["of"].get(m)
+        if a is None:
+            if not st["free"]:
+                st["accs"].append(self.torch.empty(3, self.h, self.w, dtype=self.torch.int32, device=self.dev))
+                st["free"].append(len(st["accs"]) - 1)
+            a = st["of"][m] = [st["free"].pop(), 0, 0]               # accumulator, samples and weight since the last reset
+        pad = (self.pad_top, self.pad_left) if src is not None else (0, 0)
+        self.ops.shutter_accumulate(st["accs"][a[0]], src=src, src_u8=src_u8, weight=w, light=st["light"], first=a[1] == 0,
+                                    pad_top=pad[0], pad_left=pad[1])
+        a[1] += 1
+        a[2] += w
+
+    def _blend_end(self, op, k):
+        """a reset, close or drop; -> the number of output ring entries in use"""
+        st = self.blend
+        if op[0] == "reset":
+            if op[1] in st["of"]:
+                st["of"][op[1]][1:] = [0, 0]
+            return k
+        a = st["of"].pop(op[1], None)
+        if a is not None:
+            st["free"].append(a[0])
+        if op[0] == "drop":
+            return k
+        if a is None or a[1] == 0 or k >= self.out_d.shape[0]:
+            raise RuntimeError(f"_SegmentRunner: output {op[1]} closes without samples or beyond the {self.out_d.shape[0]} output slots")
+        if self.out_fmt is None:
+            self.ops.shutter_resolve(st["accs"][a[0]], a[2], self.out_d[k], light=st["light"], bgr=self.bgr)
+        else:                                                          # the blend's uint8 pixels, then their encoding
+            self.ops.shutter_resolve(st["accs"][a[0]], a[2], st["u8"], light=st["light"])
+            self.ops.rgb_to_yuv420(self.out_d[k], self.out_fmt, src_u8=st["u8"])
+        return k + 1
+
+    def _run_blended(self, levels, ops, cut):
+        torch, n, st = self.torch, self.n, self.blend
+        if st is None:
+            raise ValueError("_SegmentRunner.run: blend needs a runner made with blend=")
+        ring = self.seg & 1
+        self.seg += 1
+        closes = 0
+        if not any(levels):                          # every sample is a resident canvas: in time order
+            for op in ops:
+                if op[0] == "add":
+                    pos = op[2] if not (cut and 0 < op[2] < n) else (0 if op[2] <= n // 2 else n)
+                    self._accumulate(op[1], op[3], src=self.frames[0][self.phys[pos]])
+                else:
+                    closes = self._blend_end(op, closes)
+        else:                                        # (resets precede the adds of a segment that is no cut)
+            # position -> [(output, weight)]: where a widened segment's positions lie further apart than the outputs, two outputs show
+            # one position -- one through its window and one, or both, as the position nearest to a window that holds no sample
+            adds = {}
+            for op in ops:
+                if op[0] == "add":
+                    adds.setdefault(op[2], []).append((op[1], op[3]))
+            if not adds.keys() - {0, n} <= {o for lv in levels for _, _, o in lv}:
+                raise ValueError(f"_SegmentRunner.run: samples {sorted(adds)} do not fit the schedule")
+            for op in ops:
+                if op[0] == "reset":
+                    self._blend_end(op, 0)
+            for pos in (0, n):
+                for m, w in adds.get(pos, ()):
+                    self._accumulate(m, w, src=self.frames[0][self.phys[pos]])
+
+            def gather(pos, pred, flip):
+                if self.tta:                           # the average's uint8 pixels are the sample
+                    self.ops.tta_merge(pred, flip, out_u8=st["u8"], pad_top=self.pad_top, pad_left=self.pad_left, bgr=False)
+                for m, w in adds[pos]:
+                    self._accumulate(m, w, **({"src_u8": st["u8"]} if self.tta else {"src": pred}))
+            self._run_levels(levels, adds, gather)
+            for op in ops:
+                if op[0] in ("close", "drop"):
+                    closes = self._blend_end(op, closes)
+        if closes:
+            cur = torch.cuda.current_stream(self.dev)
+            self.done.record(cur)
+            self.copy_out.wait_event(self.done)
+            with torch.cuda.stream(self.copy_out):
+                self.out_h[ring][:closes].copy_(self.out_d[:closes], non_blocking=True)
+                self.out_evt[ring].record(self.copy_out)
+            cur.wait_event(self.out_evt[ring])       # out_d is rewritten by the next segment: its kernels wait for this copy
+        return ring
+
+    def tail(self, ops):
+        """The end of a blended stream: the terminal sample (position N of the last ``run``) and the outputs still open."""
+        with self.torch.cuda.device(self.dev):
+            return self._run_blended([], ops, False)
 
     def result(self, ring, count: Optional[int] = None) -> List[np.ndarray]:
         """The frames of a ``run``: all N - 1, or the first ``count`` output ring entries (a run with ``emit``)."""

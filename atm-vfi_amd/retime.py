@@ -237,6 +237,7 @@ class _HostBackend:
     def __init__(self, model, levels, window, crop_rgb, isBGR, divisor, tta, max_batch, pixfmt, out_fmt, deep, dedup):
         self.n, self.levels, self.win, self.bgr, self.pixfmt, self.out_fmt, self.deep = 1 << levels, levels, window, isBGR, pixfmt, out_fmt, deep
         self.dedup, self.prev_rgb = dedup, None
+        self.crop_rgb, self.light, self.gathered = crop_rgb, None, {}          # (the synthetic shutter: ``blended``)
         if pixfmt is not None and deep:
             from . import yuv
             self.seg = _generic_segment(model, self.n, None, False, divisor, tta, max_batch,
@@ -283,6 +284,33 @@ class _HostBackend:
             made = [yuv.encode_numpy(m, self.out_fmt) for m in made]
         return dict(zip(interior, made))
 
+    def blended(self, a, b, ops, need, cut, tail):
+        """One record of ``shutter._plan`` (closes as ``("close", m)`` / ``("drop", m)``): the frames of its closes, in order --
+        ``shutter.blend_numpy`` of the uint8 RGB frames the loop would have emitted for the samples."""
+        n, made, out = self.n, {}, []
+        if need and not cut:
+            fa, fb = (a["f"], b["f"]) if self.pixfmt is None else (self._rgb(a), self._rgb(b))
+            made = dict(zip(need, self.seg(fa, fb, levels=sparse_levels(need, self.levels), emit=need)))
+        for op in ops:
+            if op[0] == "add":
+                p = op[2]
+                if 0 < p < n and not cut:
+                    frame = made[p]
+                else:
+                    frame = self.crop_rgb(self._rgb(a if (p == 0 or (p < n and p <= n // 2)) else b))
+                self.gathered.setdefault(op[1], []).append((frame, op[3]))
+            elif op[0] == "close":
+                from .shutter import blend_numpy
+                frames, weights = zip(*self.gathered.pop(op[1]))
+                frame = blend_numpy(frames, weights, self.light)
+                if self.pixfmt is not None:
+                    from . import yuv
+                    frame = yuv.encode_numpy(frame, self.out_fmt)
+                out.append(frame)
+            else:                                    # a reset, or an output the loop serves itself
+                self.gathered.pop(op[1], None)
+        return out
+
     def close(self):
         pass
 
@@ -300,12 +328,12 @@ class _DeviceBackend:
     dropped): it is converted into pool position 0, and its signature read, when it is admitted (``first``)."""
 
     def __init__(self, model, ops, dev, H, W, levels, window, crop, isBGR, divisor, tta, max_batch, pool, pixfmt, out_fmt, deep, scene,
-                 dedup, out_slots):
+                 dedup, out_slots, blend=None):
         self.levels, n = levels, 1 << levels
         max_batch = max(1, min(int(max_batch), 16))
         self.runner = _SegmentRunner(model, ops, dev, H, W, n, crop, isBGR, divisor, tta, max_batch, pool and hasattr(model, "forward_pooled"),
                                      out_fmt=out_fmt, deep_fmt=pixfmt if deep else None, out_slots=out_slots,
-                                     batch_sizes=range(1, min(max_batch, max(1, n // 2)) + 1))
+                                     batch_sizes=range(1, min(max_batch, max(1, n // 2)) + 1), blend=blend)
         sig = (ops, window, bool(isBGR))
         self.up = _Uploader(dev, H, W, depth=4 if dedup is not None else 3, signature=None if scene is None else sig,
                             pixfmt=None if pixfmt is None else (ops, pixfmt), deep=deep, difference=None if dedup is None else sig)
@@ -329,13 +357,24 @@ class _DeviceBackend:
         ring = self.runner.run(self.up, None, b["slot"], levels=sparse_levels(interior, self.levels), emit=interior)
         return dict(zip(interior, self.runner.result(ring, len(interior))))
 
+    def blended(self, a, b, ops, need, cut, tail):
+        """``_HostBackend.blended`` on the device: the segment's sparse schedule is the union of its interior samples, every sample is
+        accumulated where it would have been converted, and what closes is resolved into the output ring (``_SegmentRunner``)."""
+        closes = sum(op[0] == "close" for op in ops)
+        if tail:
+            ring = self.runner.tail(ops)
+        else:
+            ring = self.runner.run(self.up, None, b["slot"], cut=cut, levels=sparse_levels(need, self.levels), blend=ops)
+        return self.runner.result(ring, closes) if closes else []
+
     def close(self):
         self.runner.close()
 
 
 def interpolate_video_retimed(frames, model, fps_in, fps_out, levels: int = 3, dedup: Optional[Duplicates] = None,
                               crop: Optional[Tuple[int, int]] = None, isBGR: bool = True, divisor: Optional[int] = 64, tta: bool = False,
-                              max_batch: int = 4, pool: bool = True, scene=None, pixfmt=None, keep_depth: bool = False, report=None):
+                              max_batch: int = 4, pool: bool = True, scene=None, pixfmt=None, keep_depth: bool = False, report=None,
+                              shutter=None):
     """Frame-rate conversion ``fps_in -> fps_out`` (ints, ``Fraction``s or strings such as ``"30000/1001"``) over any iterable of uint8
     [H,W,3] frames: yields, in time order, output ``m`` at ``m / fps_out`` for every m up to the last kept frame's time, as the module's
     docstring defines -- the nearest of ``N = 2**levels`` positions of its segment.  Positions 0 and N are the originals and pass through
@@ -359,12 +398,32 @@ def interpolate_video_retimed(frames, model, fps_in, fps_out, levels: int = 3, d
     ``"outputs"``, ``"interpolated"`` and ``"forwards"`` (the recursion nodes evaluated: pairs through the network, the second pass of
     flip-TTA not counted) of the run.
 
+    ``shutter`` (a ``shutter.Shutter``, or an angle in degrees; default None: the loop as above, nothing new allocated or launched): a
+    synthetic shutter.  The outputs stay the same in number and time; each integrates the samples -- the dyadic positions of the
+    stream -- inside its exposure ``angle / 360 / fps_out``, in linear light or in code values, as atm-vfi_amd/shutter.py defines
+    (``shutter_slots`` is the timeline, ``blend_numpy`` the arithmetic).  A segment's sparse schedule is the union of its interior
+    samples; a sample is accumulated on the device where it would have been converted for the output ring
+    (``atmvfi_shutter_accumulate``) and an output that closes is resolved there (``atmvfi_shutter_resolve``) and leaves by the
+    existing device -> host copy.  An output of a single sample is exactly what ``shutter=None`` yields for that position (an
+    original: the caller's own array), so a small angle reproduces the unblurred conversion bit for bit; no output mixes two shots
+    of a ``scene`` cut; with a ``pixfmt`` the originals of a blurred output take part as their decoded RGB.  8-bit only:
+    ``keep_depth`` on a 10-bit format is refused (``ValueError``), as are an angle outside (0, 360] and an exposure whose total
+    weight exceeds 32767.  ``report`` also gets ``"blended"`` (outputs of more than one sample) and ``"samples"``.
+
     The rates and ``levels`` are checked at the call; ``ValueError`` as ``retime_slots`` raises it."""
     fi, fo, levels = _check_rates(fps_in, fps_out, levels)
-    return _retimed(frames, model, fi, fo, levels, dedup, crop, isBGR, divisor, tta, max_batch, pool, scene, pixfmt, keep_depth, report)
+    if shutter is not None:
+        from .shutter import as_shutter
+        shutter = as_shutter(shutter)
+        shutter.check(fi, fo, levels)
+        if pixfmt is not None and keep_depth and pixfmt.depth == 10:
+            raise ValueError("interpolate_video_retimed: shutter blends 8-bit pixels; a 10-bit blend (keep_depth=True) is out of scope")
+    return _retimed(frames, model, fi, fo, levels, dedup, crop, isBGR, divisor, tta, max_batch, pool, scene, pixfmt, keep_depth, report,
+                    shutter)
 
 
-def _retimed(frames, model, fi, fo, levels, dedup, crop, isBGR, divisor, tta, max_batch, pool, scene, pixfmt, keep_depth, report):
+def _retimed(frames, model, fi, fo, levels, dedup, crop, isBGR, divisor, tta, max_batch, pool, scene, pixfmt, keep_depth, report,
+             shutter=None):
     from .host_io import _hip_ops_of
     n = 1 << levels
     if scene is not None:
@@ -394,11 +453,14 @@ def _retimed(frames, model, fi, fo, levels, dedup, crop, isBGR, divisor, tta, ma
     ops, dev = _hip_ops_of(model)
     if ops is None or not hasattr(ops, "pool_blocks"):
         be = _HostBackend(model, levels, window, crop_rgb, isBGR, divisor, tta, max(1, int(max_batch)), pixfmt, out_fmt, deep, dedup)
+        be.light = None if shutter is None else shutter.light
     else:
         # distinct interpolated positions of one segment: its outputs, at most ceil(g fps_out / fps_in) of them, g <= max_run + 1
         span = 1 if dedup is None else dedup.max_run + 1
+        per_segment = -((-span * fo.numerator * fi.denominator) // (fo.denominator * fi.numerator))
         be = _DeviceBackend(model, ops, dev, H, W, levels, window, crop, isBGR, divisor, tta, max_batch, pool, pixfmt, out_fmt, deep, scene,
-                            dedup, out_slots=min(n - 1, -((-span * fo.numerator * fi.denominator) // (fo.denominator * fi.numerator))))
+                            dedup, out_slots=min(n - 1, per_segment),
+                            blend=None if shutter is None else (shutter.light, per_segment + 1))    # the outputs a segment can close
     ends, number = {}, itertools.count()             # kept frames by their number on the timeline, until their segments are done
     sig = {}                                         # signatures of segment ends that a later segment starts with
 
@@ -422,7 +484,65 @@ def _retimed(frames, model, fi, fo, levels, dedup, crop, isBGR, divisor, tta, ma
             dedup.finish()
         ends[next(number)] = pending
         yield pending["i"]
+
+    def blended():
+        """The loop under a shutter: ``shutter._plan``'s records, one per segment and one for the end of the stream."""
+        from .shutter import _plan
+        count.update(blended=0, samples=0)
+
+        def cut_of(j):
+            if scene is None:
+                return False
+            sig_a = sig.pop(j)
+            sig[j + 1] = be.signature(ends[j + 1])
+            return scene.judge(sig_a, sig[j + 1], h, w)
+        first_original = {}                          # output -> [samples gathered, its first sample if that is an original: (frame, copy?)]
+        for rec in _plan(kept(), fi, fo, levels, shutter, cut_of):
+            j, cut, tail = rec["j"], rec["cut"], rec["tail"]
+            a, b = ends.get(j), ends.get(j + 1)
+            ops, outs = [], []
+            singles = {op[1] for op in rec["ops"] if op[0] == "close" and len(op[3]) == 1}       # they close here with one sample
+            unsent = set()
+            for op in rec["ops"]:
+                if op[0] == "add":
+                    p = op[2]
+                    got = first_original.setdefault(op[1], [0, None])
+                    if got[0] == 0 and (p == 0 or p == n or cut):
+                        got[1] = ((a if (p == 0 or (p < n and p <= n // 2)) else b)["f"], 0 < p < n)
+                        if op[1] in singles:         # an original that passes through: the backend never hears of it
+                            unsent.add(op[1])
+                    got[0] += 1
+                    if op[1] not in unsent:
+                        ops.append(op)
+                elif op[0] == "reset":
+                    first_original.pop(op[1], None)
+                    unsent.discard(op[1])
+                    ops.append(op)
+                else:
+                    m, pos, samples = op[1:]
+                    got = first_original.pop(m)
+                    count["outputs"] += 1
+                    count["interpolated"] += 0 < pos[1] < n
+                    count["samples"] += len(samples)
+                    count["blended"] += len(samples) > 1
+                    single = got[1] if len(samples) == 1 else None       # what shutter=None yields for that position
+                    outs.append(single)
+                    if m not in unsent:
+                        ops.append(("close" if single is None else "drop", m))
+            if rec["need"] and not cut:
+                count["forwards"] += sum(len(lv) for lv in sparse_levels(rec["need"], levels))
+            made = iter(be.blended(a, b, ops, rec["need"], cut, tail))
+            for single in outs:
+                if single is None:
+                    yield next(made)
+                else:
+                    yield np.array(original(single[0]), copy=True) if single[1] else original(single[0])
+            if not tail:
+                del ends[j]
     try:
+        if shutter is not None:
+            yield from blended()
+            return
         ran = -1
         for j, ps in _retime_segments(kept(), fi, fo, levels):
             if j == ran or j + 1 not in ends:        # the output at the last kept frame (a one-frame stream: at its only frame)

@@ -475,7 +475,7 @@ def to_8bit(frame, fmt: Format) -> np.ndarray:
 
 
 def interpolate_y4m(src, dst, model, factor: int = 2, scene=None, tta: bool = False, interpolator=None, matrix: str = "auto",
-                    keep_depth: bool = False, fps_out=None, levels: int = 3, dedup=None, **kw):
+                    keep_depth: bool = False, fps_out=None, levels: int = 3, dedup=None, shutter=None, **kw):
     """Y4M file (or binary file object) ``src`` -> Y4M ``dst`` at ``fps * factor`` (``/ time_interval`` when given): an exact
     rational, 30000/1001 in gives 60000/1001 out.  Frames travel as I420 both ways (``pixfmt``); originals are written as read,
     predicted frames are encoded on the device.  The same format tags are written; 10-bit input is decoded on the device and written
@@ -488,9 +488,15 @@ def interpolate_y4m(src, dst, model, factor: int = 2, scene=None, tta: bool = Fa
     ``fps_out`` (an int, a ``Fraction`` or a string such as ``"60000/1001"``; default None: everything above, unchanged): a rate
     conversion instead -- ``retime.interpolate_video_retimed`` from the stream's own rate to exactly ``fps_out``, which the written
     header carries, with ``levels`` and ``dedup`` (a ``retime.Duplicates``) handed on; ``factor`` is ignored and there is no
-    ``time_interval``.  The dict gains ``"forwards"`` and, with ``dedup``, ``"dropped"``."""
+    ``time_interval``.  The dict gains ``"forwards"`` and, with ``dedup``, ``"dropped"``.  ``shutter`` (a ``shutter.Shutter`` or an
+    angle; only with ``fps_out``, else ``ValueError``; 8-bit output only): the conversion's synthetic shutter; the dict gains
+    ``"blended"``."""
     if fps_out is not None:
+        if shutter is not None:
+            kw["shutter"] = shutter
         return _retime_y4m(src, dst, model, fps_out, levels, dedup, scene, tta, interpolator, matrix, keep_depth, kw)
+    if shutter is not None:
+        raise ValueError("interpolate_y4m: shutter needs fps_out (the synthetic shutter belongs to the rate conversion)")
     from .host_io import _hip_ops_of, interpolate_video_2x
     from .multiframe import centre_window, interpolate_video_nx, nx_levels
     nx_levels(factor)
@@ -559,6 +565,8 @@ def _retime_y4m(src, dst, model, fps_out, levels, dedup, scene, tta, interpolato
         wr.close()
     info = {"fps_in": rd.fps, "fps_out": rate, "size": (ow, oh), "frames_in": n_in[0], "frames_out": wr.frames,
             "forwards": report.get("forwards", 0)}
+    if kw.get("shutter") is not None:
+        info["blended"] = report.get("blended", 0)
     if dedup is not None:
         info["dropped"] = list(dedup.dropped)
     if scene is not None:
@@ -571,3 +579,4 @@ from .host_io import FramePipeline, interpolate_video_2x, load_model_checkpoint 
 from .multiframe import interpolate_video_nx  # noqa: E402,F401
 from .scene import SceneCuts  # noqa: E402,F401
 from .retime import Duplicates, interpolate_video_retimed  # noqa: E402,F401
+from .shutter import Shutter, blend_numpy, shutter_slots  # noqa: E402,F401

@@ -487,6 +487,33 @@ int64_t atmvfi_frame_difference_workspace_ints(int h, int w);
 int atmvfi_frame_difference(const void* a, const void* b, int H, int W, int bgr, int y0, int x0, int h, int w, int32_t* out /*[258]*/,
                             int32_t* workspace, int64_t workspace_ints, void* stream);
 
+/* Synthetic shutter for the retimed video loop (shutter.hip; ABI 0.18; atm-vfi_amd/shutter.py holds the definition -- which samples an
+ * output integrates -- and the host twin blend_numpy).  Nothing of the reference.  A blurred output is the weighted mean of the uint8 RGB
+ * pixels q_k of its samples, taken in the domain of a light table and brought back to the nearest code, per channel:
+ *   acc = sum w_k LUT[q_k];  v = (acc + (Wt >> 1)) / Wt (floor), Wt = sum w_k;  out = the number of k in 1..255 with v >= thr[k],
+ *   thr[k] = (LUT[k - 1] + LUT[k] + 1) >> 1.   1 <= Wt <= 32767 keeps 65535 Wt inside int32.
+ *   light 0 "code":   LUT[q] = 257 q (the plain average of code values);
+ *   light 1 "linear": LUT[q] = rint(65535 eotf(q / 255)), the sRGB curve (x / 12.92 up to 0.04045, else ((x + 0.055) / 1.055)^2.4) in
+ *                     float64; strictly increasing, so out(LUT[q]) == q under both tables.
+ * atmvfi_shutter_accumulate: acc[c][y][x] (=, when `first`; else +=) weight * LUT[q] for one sample; acc is int32 planar [3,h,w], always
+ *   R, G, B.  Exactly one source: src, fp32 planar RGB [3,Hp,Wp] with the h x w window at (pad_top, pad_left) -- q is
+ *   atmvfi_frame_f32_to_u8's pixel clamp(rint(x * 255)), half to even; finite inputs, values outside [0, 1] clamp -- or src_u8, uint8
+ *   [h,w,3] (B, G, R if `bgr`), q the byte.  `first` writes without reading: nothing is pre-zeroed, and a poisoned accumulator is legal
+ *   input then.
+ * atmvfi_shutter_resolve: the rounding division and the inverse above, acc -> dst_u8 uint8 [h,w,3] (B, G, R if `bgr`).  No data-dependent
+ *   loop: one read of a 256-entry bucket table (the count for v & ~255) and four compare-and-step reads among the at most 15 thresholds
+ *   that one bucket of 256 values holds.
+ * atmvfi_shutter_table: the library's literal table of `light`, copied into a host buffer (no launch).
+ * Refused on the host before any launch (ATMVFI_EINVAL): null pointers; both or neither source; h, w < 1; the window not inside the canvas;
+ * weight < 1; total_weight outside 1..32767; an unknown light; acc (or src) not 4-byte aligned; a work-item count that does not fit an int.
+ * Any geometry and pointer alignment is accepted otherwise; 16-byte plane accesses and 12-byte RGB groups are used when acc and the fp32
+ * pointer are 16-byte and the byte pointers 4-byte aligned and w, Wp and pad_left are multiples of 4.  Both paths give the same bits.
+ * Every output word and byte is written by exactly one lane: vector stores only, no atomics. */
+int atmvfi_shutter_accumulate(int32_t* acc /*[3,h,w] planar*/, int h, int w, const float* src, int Hp, int Wp, int pad_top, int pad_left,
+                              const uint8_t* src_u8 /*[h,w,3]*/, int bgr, int weight, int light, int first, void* stream);
+int atmvfi_shutter_resolve(const int32_t* acc, int h, int w, int total_weight, int light, uint8_t* dst_u8 /*[h,w,3]*/, int bgr, void* stream);
+int atmvfi_shutter_table(int light, uint16_t out[256]);
+
 /* Planar YUV 4:2:0 (I420) <-> RGB for the video loops (yuv.hip decodes, yuv_encode.hip encodes, yuv_common.h holds the definition and
  * the shared helpers; atm-vfi_amd/yuv.py holds the format, the numpy twins and Y4M I/O).
  * Nothing of the reference: its scripts read PNGs.  A bit-exact contract in int32 (>> is an arithmetic shift: floor).

@@ -5,11 +5,13 @@ is written back as 8-bit, or with ``--keep-depth`` as C420p10 (originals byte fo
 - out.y4m --ckpt ...``).
 
     python tools/interp_y4m.py IN.y4m OUT.y4m --ckpt CKPT [--model base|lite] [--factor 2|4|8] [--scene] [--tta] [--global-off]
-                              [--keep-depth] [--fps-out R [--levels L] [--dedup]]
+                              [--keep-depth] [--fps-out R [--levels L] [--dedup] [--shutter ANGLE [--light code|linear]]]
 
 ``--fps-out R`` (an integer or a ratio such as 60000/1001) converts the frame rate to exactly R instead of multiplying it: every output
 is the nearest of 2**L positions (``--levels``, default 3) between two source frames; ``--dedup`` drops repeated frames first
-(``Duplicates()`` defaults)."""
+(``Duplicates()`` defaults); ``--shutter ANGLE`` (degrees, 0 < ANGLE <= 360; 180 is a film camera's) blurs every output over the
+positions inside its exposure of ANGLE / 360 output periods, averaged in linear light (``--light code``: in code values); 8-bit output
+only."""
 import argparse
 import importlib
 import os
@@ -36,9 +38,13 @@ def main():
     ap.add_argument("--fps-out", default=None, metavar="R", help="convert the frame rate to R (e.g. 60 or 60000/1001); --factor is ignored")
     ap.add_argument("--levels", type=int, default=3, help="with --fps-out: 2**L positions per segment (1..6)")
     ap.add_argument("--dedup", action="store_true", help="with --fps-out: drop repeated frames (Duplicates() defaults)")
+    ap.add_argument("--shutter", default=None, metavar="ANGLE", help="with --fps-out: a synthetic shutter of ANGLE degrees (e.g. 180)")
+    ap.add_argument("--light", choices=("code", "linear"), default="linear", help="with --shutter: the domain the samples are averaged in")
     a = ap.parse_args()
-    if (a.dedup or a.levels != 3) and a.fps_out is None:
-        ap.error("--levels and --dedup need --fps-out")
+    if (a.dedup or a.levels != 3 or a.shutter is not None) and a.fps_out is None:
+        ap.error("--levels, --dedup and --shutter need --fps-out")
+    if a.light != "linear" and a.shutter is None:
+        ap.error("--light needs --shutter")
     if not torch.cuda.is_available():
         sys.exit("interp_y4m: no GPU")
     pkg = importlib.import_module("atm-vfi_amd")
@@ -56,7 +62,8 @@ def main():
     dst = sys.stdout.buffer if a.dst == "-" else a.dst
     info = yuv.interpolate_y4m(src, dst, net, factor=a.factor, scene=yuv.SceneCuts() if a.scene else None, tta=a.tta, matrix=a.matrix,
                                keep_depth=a.keep_depth,
-                               **(dict(fps_out=a.fps_out, levels=a.levels, dedup=yuv.Duplicates() if a.dedup else None) if a.fps_out else {}))
+                               **(dict(fps_out=a.fps_out, levels=a.levels, dedup=yuv.Duplicates() if a.dedup else None,
+                                       shutter=yuv.Shutter(a.shutter, a.light) if a.shutter is not None else None) if a.fps_out else {}))
     print({k: (str(v) if k.startswith("fps") else v) for k, v in info.items()}, file=sys.stderr)
 
 
