@@ -1,7 +1,9 @@
-// Planar YUV 4:2:0 (I420) -> RGB: the three decode entry points of include/atmvfi.h on one kernel.  yuv_common.h holds the definition and
+// YUV 4:2:0 -> RGB: the four decode entry points of include/atmvfi.h on one kernel.  yuv_common.h holds the definition and
 // every helper; yuv_encode.hip is the other direction.
 //   atmvfi_yuv420_to_rgb      the whole frame -> fp32 planar [3,Hp,Wp] = q / 255 and / or uint8 [H,W,3] (RGB or BGR)
 //   atmvfi_yuv420p10_to_f32   a window of a 10-bit frame with the depth kept -> fp32 planar = q / 1023
+//   atmvfi_yuv_surface_decode a window of a decoder's surface (NV12 / NV21 / P010, planar; any pitch and chroma offset) -> either
+//                             pixel of the two calls above: the same walker, instances with interleaved chroma and / or msb samples
 //   atmvfi_yuv420_window      the window a dataset evaluation needs (atm-vfi_amd/evaluate.py reads the Xiph 2K / 4K clips as 10-bit Y4M this
 //                             way): the output of atmvfi_frame_u8_window on the frame atmvfi_yuv420_to_rgb would write, without that RGB
 //                             frame ever existing.  With q(Y, X) the RGB pixel 0..255 of the WHOLE frame's decode,
@@ -22,6 +24,9 @@
 //   aligned path (frame and uint8 pointers 4-byte, fp32 pointer 16-byte aligned; W, x0, w, Wp, pad_left multiples of 4): dword or 8-byte
 //           Y loads, 2-byte / dword chroma pairs, 16-byte plane stores, 12-byte RGB groups; a group lies wholly inside the window or
 //           wholly in the padding, and a padding group decodes the nearest inside group and repeats its edge pixel.
+//           A surface also needs a pitch that is a multiple of 4 bytes and naturally aligned chroma (layout_aligned); its interleaved
+//           chroma row is loaded ONCE for both planes: the centre pair-of-pairs as a dword or 8 bytes, each outer column as 2 or 4
+//           bytes -- three loads per chroma row where two planes take six (load_row).
 //   general path: any geometry and alignment: one decode_pixel per source pixel, scalar stores, the same integer arithmetic, the same bits.
 // Vector stores only, no atomics, nothing pre-zeroed: every output byte is written by exactly one lane.
 #include "yuv_common.h"
@@ -89,7 +94,7 @@ __device__ __forceinline__ void store_pixel(const DecArgs& a, int y, int x, int 
 // The walk of the crop: output rows 2k and 2k + 1, columns x .. x + 3
 template <class PX, bool ALIGNED, bool LEFT>
 __device__ __forceinline__ void decode_rows(const DecArgs& a, int k, int x) {
-    constexpr int DEPTH = PX::DEPTH, TOP = PX::TOP;
+    constexpr int TOP = PX::TOP;
     const int wx = x - a.pad_left;                      // window column of the group's first pixel; outside = padding
     if (ALIGNED) {
         const int gx = a.x0 + clampi(wx, 0, a.w - 4), q = gx >> 1;
@@ -97,10 +102,8 @@ __device__ __forceinline__ void decode_rows(const DecArgs& a, int k, int x) {
         const int fyA = a.y0 + clampi(yA - a.pad_top, 0, a.h - 1), fyB = a.y0 + clampi(yB - a.pad_top, 0, a.h - 1);
         const int rA0 = fyA >> 1, rA1 = clampi(rA0 + ((fyA & 1) ? 1 : -1), 0, a.ch - 1);
         int uA0[4], uA1[4], vA0[4], vA1[4], px[4][3];
-        load_seg<DEPTH, true>(a, a.uoff, rA0, q, uA0);
-        load_seg<DEPTH, true>(a, a.voff, rA0, q, vA0);
-        load_seg<DEPTH, true>(a, a.uoff, rA1, q, uA1);
-        load_seg<DEPTH, true>(a, a.voff, rA1, q, vA1);
+        load_row<PX>(a, rA0, q, uA0, vA0);
+        load_row<PX>(a, rA1, q, uA1, vA1);
         decode4<PX, LEFT>(a, fyA, gx, uA0, uA1, vA0, vA1, px);
         store_group<TOP>(a, yA, x, yA - a.pad_top, wx, px);
         if (yB < a.Hp) {
@@ -115,8 +118,7 @@ __device__ __forceinline__ void decode_rows(const DecArgs& a, int k, int x) {
                     vB0[i] = f ? vA0[i] : vA1[i];
                 }
             } else {
-                load_seg<DEPTH, true>(a, a.uoff, rB0, q, uB0);
-                load_seg<DEPTH, true>(a, a.voff, rB0, q, vB0);
+                load_row<PX>(a, rB0, q, uB0, vB0);
             }
             if (rB1 == rA0 || rB1 == rA1) {
                 const bool f = rB1 == rA0;
@@ -126,8 +128,7 @@ __device__ __forceinline__ void decode_rows(const DecArgs& a, int k, int x) {
                     vB1[i] = f ? vA0[i] : vA1[i];
                 }
             } else {
-                load_seg<DEPTH, true>(a, a.uoff, rB1, q, uB1);
-                load_seg<DEPTH, true>(a, a.voff, rB1, q, vB1);
+                load_row<PX>(a, rB1, q, uB1, vB1);
             }
             decode4<PX, LEFT>(a, fyB, gx, uB0, uB1, vB0, vB1, px);
             store_group<TOP>(a, yB, x, yB - a.pad_top, wx, px);
@@ -158,10 +159,25 @@ __global__ __launch_bounds__(256) void yuv420_crop_kernel(const DecArgs a) {
     }
 }
 
+// The arguments of mode 1, which reads packed frames only (atmvfi_yuv420_window): DecArgs without the strides, which are the plane
+// widths.  The kernel's argument block and with it its code are what they were before frames could have a pitch.
+struct AreaArgs {
+    const unsigned char* yuv;
+    int H, W, ch, cw;
+    long long uoff, voff;
+    int kY, kRV, kGU, kGV, kBU, yo, mid, T;
+    int y0, x0, h, w;
+    float* dst;
+    int Hp, Wp, pad_top, pad_left;
+    unsigned char* dst_u8;
+    int bgr, groups, rows;
+};
+
 // mode 1: four output pixels of one output row from source rows fy (even) and fy + 1, columns gx .. gx + 7
 template <class PX, bool ALIGNED, bool LEFT>
-__global__ __launch_bounds__(256) void yuv420_area_kernel(const DecArgs a) {
-    constexpr int DEPTH = PX::DEPTH;
+__global__ __launch_bounds__(256) void yuv420_area_kernel(const AreaArgs p) {
+    const DecArgs a = {YuvSrc{p.yuv, p.H, p.W, p.ch, p.cw, p.uoff, p.voff, p.W, p.cw, 0, p.kY, p.kRV, p.kGU, p.kGV, p.kBU, p.yo, p.mid, p.T},
+                       p.y0, p.x0, p.h, p.w, p.dst, p.Hp, p.Wp, p.pad_top, p.pad_left, p.dst_u8, p.bgr, p.groups, p.rows};
     const int total = a.rows * a.groups;
     for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
         const int y = idx / a.groups, x = (idx - y * a.groups) * 4;
@@ -171,12 +187,12 @@ __global__ __launch_bounds__(256) void yuv420_area_kernel(const DecArgs a) {
             const int gx = a.x0 + 2 * clampi(wx, 0, a.w - 4);
             const int r = fy >> 1, rm = max(r - 1, 0), rp = min(r + 1, a.ch - 1);
             int px[4][3], u[3][6], v[3][6];         // the three chroma rows, six samples wide, loaded once for both halves
-            load_seg<DEPTH, true, 6>(a, a.uoff, rm, gx >> 1, u[0]);
-            load_seg<DEPTH, true, 6>(a, a.voff, rm, gx >> 1, v[0]);
-            load_seg<DEPTH, true, 6>(a, a.uoff, r, gx >> 1, u[1]);
-            load_seg<DEPTH, true, 6>(a, a.voff, r, gx >> 1, v[1]);
-            load_seg<DEPTH, true, 6>(a, a.uoff, rp, gx >> 1, u[2]);
-            load_seg<DEPTH, true, 6>(a, a.voff, rp, gx >> 1, v[2]);
+            load_seg<PX, true, 6>(a, a.uoff, rm, gx >> 1, u[0]);
+            load_seg<PX, true, 6>(a, a.voff, rm, gx >> 1, v[0]);
+            load_seg<PX, true, 6>(a, a.uoff, r, gx >> 1, u[1]);
+            load_seg<PX, true, 6>(a, a.voff, r, gx >> 1, v[1]);
+            load_seg<PX, true, 6>(a, a.uoff, rp, gx >> 1, u[2]);
+            load_seg<PX, true, 6>(a, a.voff, rp, gx >> 1, v[2]);
 #pragma unroll
             for (int half = 0; half < 2; ++half) {          // source columns gx + 4 half .. + 3 -> output pixels 2 half, 2 half + 1
                 const int hx = gx + 4 * half, o = 2 * half;
@@ -210,12 +226,27 @@ __global__ __launch_bounds__(256) void yuv420_area_kernel(const DecArgs a) {
 // Launches the decode of a checked window.  aligned path: Y groups are dwords, chroma pairs naturally aligned (cw even, group origins
 // even), plane stores 16 bytes, RGB groups three dwords; a group of four lies wholly inside the window or wholly in the padding
 // (without a canvas Wp is w and pad_left 0)
-void launch_decode(const DecArgs& a, int depth, bool keep, int mode, int siting, void* stream) {
-    const bool al = aligned4(a.yuv) && a.W % 4 == 0 && a.x0 % 4 == 0 && a.w % 4 == 0 && (!a.dst || canvas_aligned(a.dst, a.Wp, a.pad_left)) &&
-                    (!a.dst_u8 || aligned4(a.dst_u8));
+// (il: interleaved chroma; msb: 10-bit samples stored in the upper bits)
+void launch_decode(const DecArgs& a, int depth, bool keep, int mode, int siting, void* stream, bool il = false, bool msb = false) {
+    const bool al = aligned4(a.yuv) && a.W % 4 == 0 && layout_aligned(a.ys, a.cs, a.uoff, a.voff, depth, il) && a.x0 % 4 == 0 && a.w % 4 == 0 &&
+                    (!a.dst || canvas_aligned(a.dst, a.Wp, a.pad_left)) && (!a.dst_u8 || aligned4(a.dst_u8));
     const dim3 grid = yuv_grid((long long)a.rows * a.groups), block(256);
     const hipStream_t st = (hipStream_t)stream;
-    if (keep) {
+    if (il || msb) {        // the instances of atmvfi_yuv_surface_decode that the planar, LSB calls do not have (mode 0 only)
+        dispatch(al, siting, [&](auto AL, auto LEFT) {
+            dispatch(il, msb, [&](auto IL_, auto MSB_) {
+                constexpr bool IL = decltype(IL_)::value, M = decltype(MSB_)::value;
+                auto go = [&](auto px) {
+                    hipLaunchKernelGGL((yuv420_crop_kernel<decltype(px), decltype(AL)::value, decltype(LEFT)::value>), grid, block, 0, st, a);
+                };
+                if constexpr (IL || M) {
+                    if (keep) go(Pixel<10, 1023, IL, M>{});
+                    else if (depth == 10) go(Pixel<10, 255, IL, M>{});
+                    else if constexpr (!M) go(Pixel<8, 255, IL, false>{});
+                }
+            });
+        });
+    } else if (keep) {
         dispatch(al, siting, [&](auto AL, auto LEFT) {
             hipLaunchKernelGGL((yuv420_crop_kernel<Px10, decltype(AL)::value, decltype(LEFT)::value>), grid, block, 0, st, a);
         });
@@ -225,7 +256,9 @@ void launch_decode(const DecArgs& a, int depth, bool keep, int mode, int siting,
             if (mode == 0)
                 hipLaunchKernelGGL((yuv420_crop_kernel<PX, decltype(AL)::value, decltype(LEFT)::value>), grid, block, 0, st, a);
             else
-                hipLaunchKernelGGL((yuv420_area_kernel<PX, decltype(AL)::value, decltype(LEFT)::value>), grid, block, 0, st, a);
+                hipLaunchKernelGGL((yuv420_area_kernel<PX, decltype(AL)::value, decltype(LEFT)::value>), grid, block, 0, st,
+                                   AreaArgs{a.yuv, a.H, a.W, a.ch, a.cw, a.uoff, a.voff, a.kY, a.kRV, a.kGU, a.kGV, a.kBU, a.yo, a.mid, a.T, a.y0, a.x0,
+                                            a.h, a.w, a.dst, a.Hp, a.Wp, a.pad_top, a.pad_left, a.dst_u8, a.bgr, a.groups, a.rows});
         });
     }
 }
@@ -300,5 +333,37 @@ extern "C" int atmvfi_yuv420_window(const void* yuv, int H, int W, int depth, in
     const DecArgs a = {make_src(yuv, H, W, depth, matrix, full_range, false), y0, x0, h, w, dst, Hp, Wp, pad_top, pad_left, (unsigned char*)dst_u8,
                        0, groups, rows};
     launch_decode(a, depth, false, mode, siting, stream);
+    return atmvfi::check_launch(me);
+}
+
+extern "C" int atmvfi_yuv_surface_decode(const void* yuv, int H, int W, int depth, int matrix, int full_range, int siting, int chroma, int msb,
+                                         int64_t pitch, int64_t chroma_pitch, int64_t chroma_offset, int keep_depth, int y0, int x0, int h, int w,
+                                         void* dst_u8, int bgr, float* dst, int Hp, int Wp, int pad_top, int pad_left, void* stream) {
+    const char* me = "yuv_surface_decode";
+    ATMVFI_REQUIRE(yuv, ATMVFI_EINVAL, "yuv_surface_decode: null source");
+    ATMVFI_REQUIRE(dst || dst_u8, ATMVFI_EINVAL, "yuv_surface_decode: both outputs are null (give dst, dst_u8 or both)");
+    if (const int rc = check_format(me, H, W, matrix, full_range, siting)) return rc;
+    if (const int rc = check_depth(me, depth, full_range)) return rc;
+    Layout l;
+    if (const int rc = check_surface(me, H, W, depth, chroma, msb, pitch, chroma_pitch, chroma_offset, &l)) return rc;
+    ATMVFI_REQUIRE(keep_depth == 0 || keep_depth == 1, ATMVFI_EINVAL, "yuv_surface_decode: keep_depth must be 0 or 1 (got %d)", keep_depth);
+    ATMVFI_REQUIRE(!(keep_depth && depth != 10), ATMVFI_EINVAL, "yuv_surface_decode: keep_depth needs a 10-bit surface");
+    ATMVFI_REQUIRE(!(keep_depth && dst_u8), ATMVFI_EINVAL, "yuv_surface_decode: dst_u8 holds 8-bit pixels: not with keep_depth");
+    ATMVFI_REQUIRE(h >= 1 && w >= 1, ATMVFI_EINVAL, "yuv_surface_decode: the window's h and w must be at least 1 (got %d x %d)", h, w);
+    ATMVFI_REQUIRE(y0 >= 0 && x0 >= 0 && (long long)y0 + h <= H && (long long)x0 + w <= W, ATMVFI_EINVAL,
+                   "yuv_surface_decode: window %d x %d at (%d, %d) outside the %d x %d frame", h, w, y0, x0, H, W);
+    ATMVFI_REQUIRE(y0 % 2 == 0 && x0 % 2 == 0, ATMVFI_EINVAL, "yuv_surface_decode: the window origin (%d, %d) must be even", y0, x0);
+    if (dst) {
+        if (const int rc = check_canvas(me, "dst", "window", dst, h, w, Hp, Wp, pad_top, pad_left)) return rc;
+    } else {        // no canvas: the output geometry is the window's
+        Hp = h;
+        Wp = w;
+        pad_top = pad_left = 0;
+    }
+    const int groups = groups_of(Wp), pairs = pairs_of(Hp);
+    if (const int rc = check_items(me, pairs, groups, "output of", Hp, Wp)) return rc;
+    const DecArgs a = {make_src(yuv, H, W, depth, matrix, full_range, keep_depth != 0, l), y0, x0, h, w, dst, Hp, Wp, pad_top, pad_left,
+                       (unsigned char*)dst_u8, bgr ? 1 : 0, groups, pairs};
+    launch_decode(a, depth, keep_depth != 0, 0, siting, stream, chroma != 0, msb != 0);
     return atmvfi::check_launch(me);
 }

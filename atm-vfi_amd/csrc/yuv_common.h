@@ -1,6 +1,7 @@
-// Planar YUV 4:2:0 (I420) <-> RGB at the host boundary of the video loops and of the Y4M evaluations: the definition, its device helpers
-// and the host-side checks, shared by yuv.hip (decode: atmvfi_yuv420_to_rgb, atmvfi_yuv420p10_to_f32, atmvfi_yuv420_window) and
-// yuv_encode.hip (atmvfi_rgb_to_yuv420, atmvfi_f32_to_yuv420p10); include/atmvfi.h declares them, atm-vfi_amd/yuv.py holds the numpy
+// YUV 4:2:0 (planar I420, and the decoder surfaces NV12 / NV21 / P010) <-> RGB at the host boundary of the video loops and of the Y4M
+// evaluations: the definition, its device helpers and the host-side checks, shared by yuv.hip (decode: atmvfi_yuv420_to_rgb,
+// atmvfi_yuv420p10_to_f32, atmvfi_yuv420_window, atmvfi_yuv_surface_decode) and yuv_encode.hip (atmvfi_rgb_to_yuv420,
+// atmvfi_f32_to_yuv420p10, atmvfi_yuv_surface_encode); include/atmvfi.h declares them, atm-vfi_amd/yuv.py holds the numpy
 // twins.  Nothing of the reference: its scripts take PNGs.  The definition is the project's own, in int32 throughout (>> floors), so the
 // device, the vectorised numpy twins and the per-pixel models (tests/cpu_yuv.py, cpu_yuv10.py, cpu_yuv_window.py) agree bit for bit;
 // every kernel runs the functions below, so two entry points that decode the same pixel give the same bits by construction.
@@ -21,6 +22,13 @@
 //             Y = clip(((eY . p + 2^13) >> 14) + yo); chroma sample (j, i) from the un-rounded sums s over rows 2j, min(2j + 1, H - 1) and
 //             columns 2i, min(2i + 1, W - 1) (centre, sh = 2) or max(2i - 1, 0), 2i, min(2i + 1, W - 1) weighted 1, 2, 1 (left, sh = 3):
 //             U = clip(((eU . s + 2^(13 + sh)) >> (14 + sh)) + mid), V alike
+//   surface   where the samples of a frame lie (atmvfi_yuv_surface_decode / atmvfi_yuv_surface_encode; yuv.py: Surface; model
+//             tests/cpu_yuv_surface.py): chroma as two planes or as ONE plane of interleaved pairs, U first (NV12, P010) or V first
+//             (NV21); 10-bit samples in the low or, msb, in the upper ten bits of their word (read s >> 6, written v << 6); rows at a
+//             pitch, chroma from an offset.  YuvSrc carries the strides and the U / V origins (V first is U first with the origins
+//             swapped); interleaved and msb are properties of the instance (Pixel), as the siting is.  The arithmetic above is applied
+//             to the samples found there, unchanged.  A decoder's surface that already lies in device memory is decoded in place: its
+//             pointer, pitch and chroma offset go to atmvfi_yuv_surface_decode, no padding byte is read and nothing is repacked.
 // Library-wide rules, here as everywhere: vector stores only, no atomics, nothing pre-zeroed: every output byte is written by exactly
 // one lane.
 #pragma once
@@ -67,63 +75,119 @@ const Coeffs kCoeffs10[2] = {     // [matrix]
 struct YuvSrc {
     const unsigned char* yuv;
     int H, W, ch, cw;
-    long long uoff, voff;       // first U / V sample, in samples
+    long long uoff, voff;       // first U / V sample, in samples (interleaved chroma: one is the other plus 1)
+    int ys, cs;                 // row strides of the luma and the chroma plane(s), in samples
+    int vu;                     // interleaved chroma, V first (voff + 1 == uoff): the aligned path loads pairs and swaps afterwards
     int kY, kRV, kGU, kGV, kBU, yo, mid, T;
 };
-// the pixel kind of a decode instance: the frame's sample depth and the RGB pixel's maximum.  A template parameter, not a member of
-// YuvSrc: with a constant maximum the clip is one v_med3_i32, and the decodes are bound by their instruction count.
-template <int DEPTH_, int TOP_>
+// the pixel kind of a decode instance: the frame's sample depth, the RGB pixel's maximum and how the samples lie in memory.  A template
+// parameter, not a member of YuvSrc: with a constant maximum the clip is one v_med3_i32, and the decodes are bound by their
+// instruction count.  IL: chroma is one plane of interleaved pairs (NV12 / NV21 / P010) instead of two planes; MSB: a 10-bit sample is
+// stored as value << 6 (P010) and read as s >> 6.  The planar, LSB instances compile to what they were without either.
+template <int DEPTH_, int TOP_, bool IL_ = false, bool MSB_ = false>
 struct Pixel {
     static constexpr int DEPTH = DEPTH_, TOP = TOP_;
+    static constexpr bool IL = IL_, MSB = MSB_;
     static_assert((DEPTH == 8 || DEPTH == 10) && (TOP == 255 || (TOP == 1023 && DEPTH == 10)), "8 bit, 10 -> 8 bit or 10 bit kept");
+    static_assert(!MSB || DEPTH == 10, "only 10-bit samples are stored in the upper bits");
 };
 using Px8 = Pixel<8, 255>;
 using Px10to8 = Pixel<10, 255>;
 using Px10 = Pixel<10, 1023>;
 
+// the layout of a surface, on the host: chroma 0 planar, 1 interleaved U first, 2 interleaved V first; strides in samples, uoff the
+// first chroma row's first sample.  A packed I420 frame is tight_layout(H, W, 0).
+struct Layout {
+    int chroma;
+    int ys, cs;
+    long long uoff;
+};
+inline Layout tight_layout(int H, int W, int chroma) {
+    const int cw = (W + 1) / 2;
+    return Layout{chroma, W, chroma ? 2 * cw : cw, (long long)H * W};
+}
+
 // keep: the 10-bit depth kept (RGB 0..1023); otherwise RGB 0..255 from samples of either depth
-inline YuvSrc make_src(const void* yuv, int H, int W, int depth, int matrix, int full_range, bool keep) {
+inline YuvSrc make_src(const void* yuv, int H, int W, int depth, int matrix, int full_range, bool keep, const Layout& l) {
     const int ch = (H + 1) / 2, cw = (W + 1) / 2;
     const Coeffs& c = keep ? kCoeffs10[matrix] : kCoeffs[matrix][full_range];
-    return YuvSrc{(const unsigned char*)yuv, H, W, ch, cw, (long long)H * W, (long long)H * W + (long long)ch * cw,
+    const long long uoff = l.uoff + (l.chroma == 2 ? 1 : 0), voff = l.chroma == 0 ? l.uoff + (long long)ch * l.cs : l.uoff + (l.chroma == 1 ? 1 : 0);
+    return YuvSrc{(const unsigned char*)yuv, H, W, ch, cw, uoff, voff, l.ys, l.cs, l.chroma == 2 ? 1 : 0,
                   c.dec[0], c.dec[1], c.dec[2], c.dec[3], c.dec[4], depth == 10 ? 64 : (full_range ? 0 : 16), depth == 10 ? 512 : 128,
                   depth == 10 && !keep ? 16 : 14};
 }
+inline YuvSrc make_src(const void* yuv, int H, int W, int depth, int matrix, int full_range, bool keep) {
+    return make_src(yuv, H, W, depth, matrix, full_range, keep, tight_layout(H, W, 0));
+}
 
-template <int DEPTH, bool AL>
+// the value of a stored 16-bit sample: its upper ten bits for MSB
+template <bool MSB>
+__device__ __forceinline__ int lo16(unsigned v) { return (int)((v & 0xffffu) >> (MSB ? 6 : 0)); }
+template <bool MSB>
+__device__ __forceinline__ int hi16(unsigned v) { return (int)(v >> (MSB ? 22 : 16)); }
+
+template <class PX, bool AL>
 __device__ __forceinline__ int sample(const unsigned char* p, long long i) {
-    if (DEPTH == 8) return p[i];
-    if (AL) return reinterpret_cast<const unsigned short*>(p)[i];
-    return (int)p[2 * i] | ((int)p[2 * i + 1] << 8);
+    if (PX::DEPTH == 8) return p[i];
+    if (AL) return lo16<PX::MSB>(reinterpret_cast<const unsigned short*>(p)[i]);
+    return lo16<PX::MSB>((unsigned)p[2 * i] | ((unsigned)p[2 * i + 1] << 8));
 }
 
 // the naturally aligned pair of samples (i, i + 1) of the aligned paths: two bytes or one dword
-template <int DEPTH>
+template <class PX>
 __device__ __forceinline__ void sample_pair(const unsigned char* p, long long i, int& s0, int& s1) {
-    if (DEPTH == 8) {
+    if (PX::DEPTH == 8) {
         const unsigned v = reinterpret_cast<const U16x1*>(p + i)->v;
         s0 = (int)(v & 0xffu);
         s1 = (int)(v >> 8);
     } else {
         const unsigned v = *reinterpret_cast<const unsigned*>(p + 2 * i);
-        s0 = (int)(v & 0xffffu);
-        s1 = (int)(v >> 16);
+        s0 = lo16<PX::MSB>(v);
+        s1 = hi16<PX::MSB>(v);
     }
 }
 
 // seg[k] = plane[r][clamp(q - 1 + k, 0, cw - 1)], k = 0 .. N - 1: every chroma column that luma columns 2q .. 2q + 2N - 5 touch
-// (N = 4: one group of four pixels; N = 6: two groups, seg + 2 being the second group's segment)
-template <int DEPTH, bool AL, int N = 4>
+// (N = 4: one group of four pixels; N = 6: two groups, seg + 2 being the second group's segment); planar chroma
+template <class PX, bool AL, int N = 4>
 __device__ __forceinline__ void load_seg(const YuvSrc& a, long long plane, int r, int q, int seg[N]) {
-    const long long row = plane + (long long)r * a.cw;
-    if (AL) {       // q even and cw even: the columns q .. q + N - 3 are naturally aligned pairs inside the row
-        seg[0] = sample<DEPTH, true>(a.yuv, row + max(q - 1, 0));
+    const long long row = plane + (long long)r * a.cs;
+    if (AL) {       // q even, the row's origin even: the columns q .. q + N - 3 are naturally aligned pairs inside the row
+        seg[0] = sample<PX, true>(a.yuv, row + max(q - 1, 0));
 #pragma unroll
-        for (int p = 0; p < N - 2; p += 2) sample_pair<DEPTH>(a.yuv, row + q + p, seg[1 + p], seg[2 + p]);
-        seg[N - 1] = sample<DEPTH, true>(a.yuv, row + min(q + N - 2, a.cw - 1));
+        for (int p = 0; p < N - 2; p += 2) sample_pair<PX>(a.yuv, row + q + p, seg[1 + p], seg[2 + p]);
+        seg[N - 1] = sample<PX, true>(a.yuv, row + min(q + N - 2, a.cw - 1));
     } else {
 #pragma unroll
-        for (int k = 0; k < N; ++k) seg[k] = sample<DEPTH, false>(a.yuv, row + clampi(q - 1 + k, 0, a.cw - 1));
+        for (int k = 0; k < N; ++k) seg[k] = sample<PX, false>(a.yuv, row + clampi(q - 1 + k, 0, a.cw - 1));
+    }
+}
+
+// the same four columns of chroma row r for BOTH planes on the aligned paths.  Interleaved chroma: the row is loaded once -- the
+// aligned centre pairs (first, second)[q], (first, second)[q + 1] as one dword (8 bit) or one 8-byte load (10 bit), each outer column
+// as one 2-byte or dword load: three loads where two planes take six.  first / second are U / V, or V / U when a.vu: decode4 swaps.
+template <class PX>
+__device__ __forceinline__ void load_row(const YuvSrc& a, int r, int q, int u[4], int v[4]) {
+    if (!PX::IL) {
+        load_seg<PX, true>(a, a.uoff, r, q, u);
+        load_seg<PX, true>(a, a.voff, r, q, v);
+    } else {
+        const long long row = a.uoff - a.vu + (long long)r * a.cs;
+        sample_pair<PX>(a.yuv, row + 2 * max(q - 1, 0), u[0], v[0]);
+        if (PX::DEPTH == 8) {
+            const unsigned d = *reinterpret_cast<const unsigned*>(a.yuv + row + 2 * q);
+            u[1] = (int)(d & 0xffu);
+            v[1] = (int)((d >> 8) & 0xffu);
+            u[2] = (int)((d >> 16) & 0xffu);
+            v[2] = (int)(d >> 24);
+        } else {
+            const U32x2 d = *reinterpret_cast<const U32x2*>(a.yuv + 2 * (row + 2 * q));
+            u[1] = lo16<PX::MSB>(d.a);
+            v[1] = hi16<PX::MSB>(d.a);
+            u[2] = lo16<PX::MSB>(d.b);
+            v[2] = hi16<PX::MSB>(d.b);
+        }
+        sample_pair<PX>(a.yuv, row + 2 * min(q + 2, a.cw - 1), u[3], v[3]);
     }
 }
 
@@ -164,18 +228,18 @@ __device__ __forceinline__ void to_rgb(const YuvSrc& a, int Y, int U, int V, int
 // one frame pixel, every sample loaded on its own (the general path)
 template <class PX, bool LEFT>
 __device__ __forceinline__ void decode_pixel(const YuvSrc& a, int fy, int fx, int q[3]) {
-    constexpr int DEPTH = PX::DEPTH;
+    constexpr int E = PX::IL ? 2 : 1;           // samples from one chroma column to the next
     const int r0 = fy >> 1, r1 = clampi(r0 + ((fy & 1) ? 1 : -1), 0, a.ch - 1);
     const int q0 = fx >> 1;
     const int q1 = LEFT ? min(q0 + 1, a.cw - 1) : clampi(q0 + ((fx & 1) ? 1 : -1), 0, a.cw - 1);
     const int wx0 = LEFT ? ((fx & 1) ? 2 : 4) : 3, wx1 = 4 - wx0;
-    const long long i00 = (long long)r0 * a.cw + q0, i01 = (long long)r0 * a.cw + q1, i10 = (long long)r1 * a.cw + q0,
-                    i11 = (long long)r1 * a.cw + q1;
-    const int U = chroma_mix(sample<DEPTH, false>(a.yuv, a.uoff + i00), sample<DEPTH, false>(a.yuv, a.uoff + i01),
-                             sample<DEPTH, false>(a.yuv, a.uoff + i10), sample<DEPTH, false>(a.yuv, a.uoff + i11), wx0, wx1);
-    const int V = chroma_mix(sample<DEPTH, false>(a.yuv, a.voff + i00), sample<DEPTH, false>(a.yuv, a.voff + i01),
-                             sample<DEPTH, false>(a.yuv, a.voff + i10), sample<DEPTH, false>(a.yuv, a.voff + i11), wx0, wx1);
-    to_rgb<PX::TOP>(a, sample<DEPTH, false>(a.yuv, (long long)fy * a.W + fx), U, V, q);
+    const long long i00 = (long long)r0 * a.cs + E * q0, i01 = (long long)r0 * a.cs + E * q1, i10 = (long long)r1 * a.cs + E * q0,
+                    i11 = (long long)r1 * a.cs + E * q1;
+    const int U = chroma_mix(sample<PX, false>(a.yuv, a.uoff + i00), sample<PX, false>(a.yuv, a.uoff + i01),
+                             sample<PX, false>(a.yuv, a.uoff + i10), sample<PX, false>(a.yuv, a.uoff + i11), wx0, wx1);
+    const int V = chroma_mix(sample<PX, false>(a.yuv, a.voff + i00), sample<PX, false>(a.yuv, a.voff + i01),
+                             sample<PX, false>(a.yuv, a.voff + i10), sample<PX, false>(a.yuv, a.voff + i11), wx0, wx1);
+    to_rgb<PX::TOP>(a, sample<PX, false>(a.yuv, (long long)fy * a.ys + fx), U, V, q);
 }
 
 // four frame pixels of row fy, columns gx .. gx + 3 (gx even, the row's Y group readable as dwords) from the chroma segments of rows
@@ -185,15 +249,15 @@ __device__ __forceinline__ void decode4(const YuvSrc& a, int fy, int gx, const i
                                         int q[4][3]) {
     int Y[4];
     if (PX::DEPTH == 8) {
-        const unsigned d = *reinterpret_cast<const unsigned*>(a.yuv + (long long)fy * a.W + gx);
+        const unsigned d = *reinterpret_cast<const unsigned*>(a.yuv + (long long)fy * a.ys + gx);
 #pragma unroll
         for (int i = 0; i < 4; ++i) Y[i] = (int)((d >> (8 * i)) & 0xffu);
     } else {
-        const U32x2 d = *reinterpret_cast<const U32x2*>(a.yuv + 2 * ((long long)fy * a.W + gx));
-        Y[0] = (int)(d.a & 0xffffu);
-        Y[1] = (int)(d.a >> 16);
-        Y[2] = (int)(d.b & 0xffffu);
-        Y[3] = (int)(d.b >> 16);
+        const U32x2 d = *reinterpret_cast<const U32x2*>(a.yuv + 2 * ((long long)fy * a.ys + gx));
+        Y[0] = lo16<PX::MSB>(d.a);
+        Y[1] = hi16<PX::MSB>(d.a);
+        Y[2] = lo16<PX::MSB>(d.b);
+        Y[3] = hi16<PX::MSB>(d.b);
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -202,7 +266,8 @@ __device__ __forceinline__ void decode4(const YuvSrc& a, int fy, int gx, const i
         const int wx0 = LEFT ? ((i & 1) ? 2 : 4) : 3, wx1 = 4 - wx0;
         const int U = chroma_mix(u0[k0], u0[k1], u1[k0], u1[k1], wx0, wx1);
         const int V = chroma_mix(v0[k0], v0[k1], v1[k0], v1[k1], wx0, wx1);
-        to_rgb<PX::TOP>(a, Y[i], U, V, q[i]);
+        if (PX::IL) to_rgb<PX::TOP>(a, Y[i], a.vu ? V : U, a.vu ? U : V, q[i]);        // (load_row: first / second of a pair)
+        else to_rgb<PX::TOP>(a, Y[i], U, V, q[i]);
     }
 }
 
@@ -222,6 +287,30 @@ int check_depth(const char* what, int depth, int full_range) {
     return ATMVFI_OK;
 }
 
+// a surface: depth, layout and strides in BYTES as the caller gives them -> the layout in samples.  pitch / chroma_pitch / chroma_offset
+// 0: tight.  (yuv.Surface holds the same rules.)
+int check_surface(const char* what, int H, int W, int depth, int chroma, int msb, long long pitch, long long chroma_pitch, long long chroma_offset,
+                  Layout* out) {
+    ATMVFI_REQUIRE(chroma >= 0 && chroma <= 2, ATMVFI_EINVAL, "%s: unknown chroma layout %d (0: planar, 1: interleaved uv, 2: interleaved vu)",
+                   what, chroma);
+    ATMVFI_REQUIRE(msb == 0 || msb == 1, ATMVFI_EINVAL, "%s: msb must be 0 or 1 (got %d)", what, msb);
+    ATMVFI_REQUIRE(!(msb && depth != 10), ATMVFI_EINVAL, "%s: msb needs depth 10 (8-bit samples fill their byte)", what);
+    const long long b = depth == 10 ? 2 : 1, cw = ((long long)W + 1) / 2, crow = (chroma ? 2 * cw : cw) * b;
+    if (pitch == 0) pitch = W * b;
+    if (chroma_pitch == 0) chroma_pitch = crow;
+    if (chroma_offset == 0) chroma_offset = pitch * H;
+    ATMVFI_REQUIRE(pitch % b == 0 && pitch >= W * b && pitch / b < (1ll << 31), ATMVFI_EINVAL,
+                   "%s: pitch %lld must be a multiple of the sample size %lld and at least a luma row's %lld bytes", what, pitch, b, W * b);
+    ATMVFI_REQUIRE(chroma_pitch % b == 0 && chroma_pitch >= crow && chroma_pitch / b < (1ll << 31), ATMVFI_EINVAL,
+                   "%s: chroma_pitch %lld must be a multiple of the sample size %lld and at least a chroma row's %lld bytes", what, chroma_pitch,
+                   b, crow);
+    ATMVFI_REQUIRE(chroma_offset % b == 0 && chroma_offset >= pitch * H, ATMVFI_EINVAL,
+                   "%s: chroma_offset %lld must be a multiple of the sample size %lld and at least pitch * H = %lld", what, chroma_offset, b,
+                   pitch * H);
+    *out = Layout{chroma, (int)(pitch / b), (int)(chroma_pitch / b), chroma_offset / b};
+    return ATMVFI_OK;
+}
+
 // the fp32 canvas [3,Hp,Wp] at p holds the h x w `noun` ("frame" or "window") at (pad_top, pad_left); side names the argument
 int check_canvas(const char* what, const char* side, const char* noun, const float* p, int h, int w, int Hp, int Wp, int pad_top,
                  int pad_left) {
@@ -235,6 +324,16 @@ int check_canvas(const char* what, const char* side, const char* noun, const flo
 int check_items(const char* what, long long rows, long long groups, const char* thing, int h, int w) {
     ATMVFI_REQUIRE(rows * groups < (1ll << 30), ATMVFI_EINVAL, "%s: %s %d x %d is too large", what, thing, h, w);
     return ATMVFI_OK;
+}
+
+// the frame side of the aligned paths (with a 4-byte aligned pointer and W % 4 == 0): Y groups are dwords / 8-byte words of their row,
+// planar chroma pairs naturally aligned (2 or 4 bytes), interleaved chroma pair-of-pairs 4-byte aligned.  A packed I420 frame with
+// W % 4 == 0 always passes.
+inline bool layout_aligned(int ys, int cs, long long uoff, long long voff, int depth, bool il) {
+    const int b = depth == 10 ? 2 : 1;
+    if ((ys * (long long)b) % 4) return false;
+    if (il) return ((uoff < voff ? uoff : voff) * b) % 4 == 0 && (cs * (long long)b) % 4 == 0;
+    return uoff % 2 == 0 && voff % 2 == 0 && cs % 2 == 0;
 }
 
 inline int groups_of(int w) { return (int)(((long long)w + 3) / 4); }

@@ -1,7 +1,9 @@
-// RGB -> planar YUV 4:2:0 (I420): the two encode entry points of include/atmvfi.h on one kernel.  yuv_common.h holds the definition and
+// RGB -> YUV 4:2:0: the three encode entry points of include/atmvfi.h on one kernel.  yuv_common.h holds the definition and
 // the shared helpers; yuv.hip is the other direction.
 //   atmvfi_rgb_to_yuv420      uint8 [H,W,3] (RGB or BGR) or the fp32 canvas in units of 1 / 255 -> 8-bit samples
 //   atmvfi_f32_to_yuv420p10   the fp32 canvas in units of 1 / 1023 -> 10-bit samples, the depth kept
+//   atmvfi_yuv_surface_encode either of the two into a tight surface: planar, or NV12 / NV21 / P010 (interleaved chroma, msb samples);
+//                             a lane's two chroma samples of both planes leave as ONE dword (8 bit) or 8-byte (10 bit) store
 //
 // Bandwidth-bound: from fp32 12 B/px in and 1.5 or 3 out.  A lane owns a 4 x 2 luma block of the frame: two Y groups and two chroma
 // samples per plane; left siting reads one more pixel column.
@@ -24,7 +26,9 @@ struct EncArgs {
     int H, W, ch, cw;
     int eY[3], eU[3], eV[3], yo;
     unsigned char* yuv;
-    long long uoff, voff;       // first U / V sample, in samples
+    long long uoff, voff;       // first U / V sample, in samples (interleaved chroma: one is the other plus 1)
+    int ys, cs;                 // row strides of the luma and the chroma plane(s), in samples
+    int vu;                     // interleaved chroma, V first
     int groups;                 // ceil(W / 4); a group makes chroma columns 2g and 2g + 1
 };
 
@@ -105,9 +109,12 @@ __device__ __forceinline__ void store_samples(unsigned char* yuv, long long i, c
     }
 }
 
-template <int SRC, bool ALIGNED, bool LEFT>
+// IL: chroma is one plane of interleaved pairs; MSB: a 10-bit sample is stored as value << 6 (the low bits zero).  The planar, LSB
+// instances compile to what they were without either.
+template <int SRC, bool ALIGNED, bool LEFT, bool IL = false, bool MSB = false>
 __global__ __launch_bounds__(256) void yuv420_encode_kernel(const EncArgs a) {
-    constexpr int DEPTH = SRC == SRC_F1023 ? 10 : 8, TOP = SRC == SRC_F1023 ? 1023 : 255, MID = (TOP + 1) / 2;
+    constexpr int DEPTH = SRC == SRC_F1023 ? 10 : 8, TOP = SRC == SRC_F1023 ? 1023 : 255, MID = (TOP + 1) / 2, SH = MSB ? 6 : 0;
+    static_assert(!MSB || DEPTH == 10, "only 10-bit samples are stored in the upper bits");
     const int total = a.ch * a.groups;
     for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
         const int j = idx / a.groups, g = idx - j * a.groups, x = 4 * g;
@@ -131,8 +138,8 @@ __global__ __launch_bounds__(256) void yuv420_encode_kernel(const EncArgs a) {
             if (y >= a.H) break;
             int Y[4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) Y[i] = clampi(((dot3(a.eY, px[r][1 + i]) + (1 << 13)) >> 14) + a.yo, 0, TOP);
-            store_samples<DEPTH, ALIGNED, 4>(a.yuv, (long long)y * a.W + x, Y, a.W - x);
+            for (int i = 0; i < 4; ++i) Y[i] = clampi(((dot3(a.eY, px[r][1 + i]) + (1 << 13)) >> 14) + a.yo, 0, TOP) << SH;
+            store_samples<DEPTH, ALIGNED, 4>(a.yuv, (long long)y * a.ys + x, Y, a.W - x);
         }
         // chroma columns 2g and 2g + 1
         constexpr int sh = LEFT ? 3 : 2;
@@ -148,19 +155,25 @@ __global__ __launch_bounds__(256) void yuv420_encode_kernel(const EncArgs a) {
                 else
                     s[c] = px[0][1 + 2 * i][c] + px[0][2 + 2 * i][c] + px[1][1 + 2 * i][c] + px[1][2 + 2 * i][c];
             }
-            U[i] = clampi(((dot3(a.eU, s) + (1 << (13 + sh))) >> (14 + sh)) + MID, 0, TOP);
-            V[i] = clampi(((dot3(a.eV, s) + (1 << (13 + sh))) >> (14 + sh)) + MID, 0, TOP);
+            U[i] = clampi(((dot3(a.eU, s) + (1 << (13 + sh))) >> (14 + sh)) + MID, 0, TOP) << SH;
+            V[i] = clampi(((dot3(a.eV, s) + (1 << (13 + sh))) >> (14 + sh)) + MID, 0, TOP) << SH;
         }
-        const long long c0 = (long long)j * a.cw + 2 * g;      // (aligned: cw is even, both columns exist)
-        store_samples<DEPTH, ALIGNED, 2>(a.yuv, a.uoff + c0, U, a.cw - 2 * g);
-        store_samples<DEPTH, ALIGNED, 2>(a.yuv, a.voff + c0, V, a.cw - 2 * g);
+        if (IL) {       // both planes' two samples as one store of four: a dword, or 8 bytes at depth 10
+            const int quad[4] = {a.vu ? V[0] : U[0], a.vu ? U[0] : V[0], a.vu ? V[1] : U[1], a.vu ? U[1] : V[1]};
+            store_samples<DEPTH, ALIGNED, 4>(a.yuv, a.uoff - a.vu + (long long)j * a.cs + 4 * g, quad, 2 * (a.cw - 2 * g));
+        } else {
+            const long long c0 = (long long)j * a.cs + 2 * g;      // (aligned: cw is even, both columns exist)
+            store_samples<DEPTH, ALIGNED, 2>(a.yuv, a.uoff + c0, U, a.cw - 2 * g);
+            store_samples<DEPTH, ALIGNED, 2>(a.yuv, a.voff + c0, V, a.cw - 2 * g);
+        }
     }
 }
 
-// Launches the encode of a checked frame; exactly one of src_u8 and src is given
+// Launches the encode of a checked frame; exactly one of src_u8 and src is given.  The destination is tight: chroma 0 is the packed
+// I420 frame, 1 / 2 the interleaved surface (U / V first); msb: 10-bit samples stored in the upper bits
 template <int SRC>
 void launch_encode(const Coeffs& c, int yo, const void* src_u8, int bgr, const float* src, int Hp, int Wp, int pad_top, int pad_left, int H,
-                   int W, int siting, void* yuv, void* stream) {
+                   int W, int siting, void* yuv, void* stream, int chroma = 0, bool msb = false) {
     const int ch = (H + 1) / 2, cw = (W + 1) / 2, groups = groups_of(W);
     EncArgs a = {(const unsigned char*)src_u8, bgr ? 1 : 0, src, Hp, Wp, pad_top, pad_left, H, W, ch, cw};
     for (int k = 0; k < 3; ++k) {
@@ -170,11 +183,26 @@ void launch_encode(const Coeffs& c, int yo, const void* src_u8, int bgr, const f
     }
     a.yo = yo;
     a.yuv = (unsigned char*)yuv;
-    a.uoff = (long long)H * W;
-    a.voff = a.uoff + (long long)ch * cw;
+    const Layout l = tight_layout(H, W, chroma);
+    a.uoff = l.uoff + (chroma == 2 ? 1 : 0);
+    a.voff = chroma == 0 ? l.uoff + (long long)ch * cw : l.uoff + (chroma == 1 ? 1 : 0);
+    a.ys = l.ys;
+    a.cs = l.cs;
+    a.vu = chroma == 2 ? 1 : 0;
     a.groups = groups;
-    const bool al = aligned4(yuv) && W % 4 == 0 && (src ? canvas_aligned(src, Wp, pad_left) : aligned4(src_u8));
+    const bool al = aligned4(yuv) && W % 4 == 0 && (src ? canvas_aligned(src, Wp, pad_left) : aligned4(src_u8));      // (tight: the layout follows)
     const dim3 grid = yuv_grid((long long)ch * groups), block(256);
+    if (chroma || msb) {        // the instances of atmvfi_yuv_surface_encode that the planar, LSB calls do not have
+        dispatch(al, siting, [&](auto AL, auto LEFT) {
+            dispatch(chroma != 0, msb, [&](auto IL_, auto MSB_) {
+                constexpr bool IL = decltype(IL_)::value, M = decltype(MSB_)::value && SRC == SRC_F1023;
+                if constexpr (IL || M)
+                    hipLaunchKernelGGL((yuv420_encode_kernel<SRC, decltype(AL)::value, decltype(LEFT)::value, IL, M>), grid, block, 0,
+                                       (hipStream_t)stream, a);
+            });
+        });
+        return;
+    }
     dispatch(al, siting, [&](auto AL, auto LEFT) {
         hipLaunchKernelGGL((yuv420_encode_kernel<SRC, decltype(AL)::value, decltype(LEFT)::value>), grid, block, 0, (hipStream_t)stream, a);
     });
@@ -208,5 +236,30 @@ extern "C" int atmvfi_f32_to_yuv420p10(const float* src, int Hp, int Wp, int pad
     if (const int rc = check_canvas(me, "src", "frame", src, H, W, Hp, Wp, pad_top, pad_left)) return rc;
     if (const int rc = check_items(me, (H + 1) / 2, groups_of(W), "a frame of", H, W)) return rc;
     launch_encode<SRC_F1023>(kCoeffs10[matrix], 64, nullptr, 0, src, Hp, Wp, pad_top, pad_left, H, W, siting, yuv, stream);
+    return atmvfi::check_launch(me);
+}
+
+extern "C" int atmvfi_yuv_surface_encode(const void* src_u8, int bgr, const float* src, int Hp, int Wp, int pad_top, int pad_left, int H, int W,
+                                         int depth, int matrix, int full_range, int siting, int chroma, int msb, void* yuv, void* stream) {
+    const char* me = "yuv_surface_encode";
+    ATMVFI_REQUIRE(yuv, ATMVFI_EINVAL, "yuv_surface_encode: null destination");
+    ATMVFI_REQUIRE((src_u8 != nullptr) != (src != nullptr), ATMVFI_EINVAL,
+                   "yuv_surface_encode: give exactly one of src_u8 and src (got %s)", src_u8 ? "both" : "neither");
+    if (const int rc = check_format(me, H, W, matrix, full_range, siting)) return rc;
+    if (const int rc = check_depth(me, depth, full_range)) return rc;
+    Layout l;
+    if (const int rc = check_surface(me, H, W, depth, chroma, msb, 0, 0, 0, &l)) return rc;
+    ATMVFI_REQUIRE(!(depth == 10 && src_u8), ATMVFI_EINVAL, "yuv_surface_encode: a 10-bit surface is encoded from the fp32 canvas (src), not from src_u8");
+    if (src)
+        if (const int rc = check_canvas(me, "src", "frame", src, H, W, Hp, Wp, pad_top, pad_left)) return rc;
+    if (const int rc = check_items(me, (H + 1) / 2, groups_of(W), "a frame of", H, W)) return rc;
+    if (depth == 10) {
+        launch_encode<SRC_F1023>(kCoeffs10[matrix], 64, nullptr, 0, src, Hp, Wp, pad_top, pad_left, H, W, siting, yuv, stream, chroma, msb != 0);
+    } else {
+        const Coeffs& c = kCoeffs[matrix][full_range];
+        const int yo = full_range ? 0 : 16;
+        if (src) launch_encode<SRC_F255>(c, yo, nullptr, 0, src, Hp, Wp, pad_top, pad_left, H, W, siting, yuv, stream, chroma, false);
+        else launch_encode<SRC_U8>(c, yo, src_u8, bgr, nullptr, Hp, Wp, pad_top, pad_left, H, W, siting, yuv, stream, chroma, false);
+    }
     return atmvfi::check_launch(me);
 }

@@ -146,6 +146,9 @@ SIGNATURES = {
     "atmvfi_rgb_to_yuv420": (c_i, [c_f, c_i, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f]),
     "atmvfi_yuv420p10_to_f32": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f]),
     "atmvfi_f32_to_yuv420p10": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f]),
+    "atmvfi_yuv_surface_decode": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_l, c_l, c_l, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_f, c_i, c_i,
+                                        c_i, c_i, c_f]),
+    "atmvfi_yuv_surface_encode": (c_i, [c_f, c_i, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f]),
     "atmvfi_pack_frames": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_f]),
     "atmvfi_final_residual": (c_i, [c_f, c_f, c_i, c_f, c_f, c_i, c_i, c_i, c_f]),
     "atmvfi_l1_mean": (c_i, [c_f, c_f, c_f, c_i, c_l, c_f, c_l, c_f]),
@@ -342,6 +345,25 @@ def _i420(t, fmt, what: str, kind: str = "I420"):
     if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1 or t.numel() != fmt.frame_bytes or not t.is_contiguous() \
             or not t.is_cuda:
         raise ValueError(f"{what} must be a contiguous CUDA uint8 tensor of {fmt.frame_bytes} bytes ({fmt.height} x {fmt.width} {kind})")
+
+
+_SURFACE = []
+
+
+def _surface_class():
+    """``yuv.Surface`` (imported on first use: yuv.py imports the loops, which import this module)"""
+    if not _SURFACE:
+        from .yuv import Surface
+        _SURFACE.append(Surface)
+    return _SURFACE[0]
+
+
+def _surface(t, surface, what: str):
+    """``t`` is one frame of ``surface`` (a ``yuv.Surface``) as bytes on the device, or ``ValueError``."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1 or t.numel() != surface.nbytes or not t.is_contiguous() \
+            or not t.is_cuda:
+        raise ValueError(f"{what} must be a contiguous CUDA uint8 tensor of {surface.nbytes} bytes ({surface.height} x {surface.width} "
+                         f"{surface.chroma} surface, depth {surface.depth}, pitch {surface.pitch})")
 
 
 class PlanUnsupported(Exception):
@@ -1508,6 +1530,88 @@ class HipOps:
         meta = {"bytes": float(fmt.frame_bytes) + 12.0 * h * w}
         self._run("f32_to_yuv420p10", meta, self.lib.atmvfi_f32_to_yuv420p10, _ptr(src), hp, wp, int(pad_top), int(pad_left), h, w,
                   fmt.matrix_id, fmt.siting_id, _ptr(yuv), self._stream())
+
+    def yuv_surface_decode(self, buf, surface, dst_u8=None, dst=None, window=None, pad_top: int = 0, pad_left: int = 0, bgr: bool = False,
+                           keep_depth: bool = False):
+        """One frame of ``surface`` (a ``yuv.Surface``: NV12 / NV21 / P010 / planar, any pitch and chroma offset; ``buf`` a contiguous
+        CUDA uint8 tensor of ``surface.nbytes`` bytes, any alignment -- a decoder's surface in place) -> ``window=(y0, x0, h, w)`` of it
+        (default: all; even origin) as ``dst`` fp32 planar RGB [3,Hp,Wp] with replicate padding, the window at (pad_top, pad_left), and /
+        or ``dst_u8`` uint8 [h,w,3] (BGR if ``bgr``).  ``keep_depth`` (a 10-bit surface, ``dst`` only): q / 1023, otherwise clip8 RGB
+        and q / 255 (include/atmvfi.h atmvfi_yuv_surface_decode; the bits of ``yuv.decode_numpy`` / ``decode_numpy_f32``)."""
+        if not isinstance(surface, _surface_class()):
+            raise ValueError(f"yuv_surface_decode: surface must be a yuv.Surface (got {type(surface).__name__})")
+        h, w = surface.height, surface.width
+        _surface(buf, surface, "yuv_surface_decode: buf")
+        if dst is None and dst_u8 is None:
+            raise ValueError("yuv_surface_decode: give dst, dst_u8 or both")
+        if keep_depth and surface.depth != 10:
+            raise ValueError("yuv_surface_decode: keep_depth needs a 10-bit surface")
+        if keep_depth and dst_u8 is not None:
+            raise ValueError("yuv_surface_decode: dst_u8 holds 8-bit pixels: not with keep_depth")
+        y0, x0, wh, ww = (0, 0, h, w) if window is None else (int(v) for v in window)
+        if y0 % 2 or x0 % 2:
+            raise ValueError(f"yuv_surface_decode: the window origin ({y0}, {x0}) must be even for 4:2:0 frames")
+        if y0 < 0 or x0 < 0 or wh < 1 or ww < 1 or y0 + wh > h or x0 + ww > w:
+            raise ValueError(f"yuv_surface_decode: window {wh} x {ww} at ({y0}, {x0}) outside the {h} x {w} frame")
+        if dst is not None:
+            _f32_canvas(dst, "yuv_surface_decode: dst")
+            hp, wp = dst.shape[1], dst.shape[2]
+            if pad_top < 0 or pad_left < 0 or wh + pad_top > hp or ww + pad_left > wp:
+                raise ValueError(f"yuv_surface_decode: canvas {hp} x {wp} is smaller than the window {wh} x {ww} plus padding ({pad_top}, {pad_left})")
+        else:
+            hp, wp = wh, ww
+        if dst_u8 is not None:
+            _u8_frame(dst_u8, "yuv_surface_decode: dst_u8", (wh, ww))
+        meta = {"bytes": 1.5 * surface.itemsize * wh * ww + (12.0 * hp * wp if dst is not None else 0.0) + (3.0 * wh * ww if dst_u8 is not None else 0.0)}
+        self._run("yuv_surface_decode", meta, self.lib.atmvfi_yuv_surface_decode, _ptr(buf), h, w, int(surface.depth), surface.matrix_id,
+                  int(surface.full_range), surface.siting_id, surface.chroma_id, int(surface.msb), int(surface.pitch), int(surface.chroma_pitch),
+                  int(surface.chroma_offset), int(bool(keep_depth)), y0, x0, wh, ww, _ptr(dst_u8), int(bool(bgr)), _ptr(dst), hp, wp,
+                  int(pad_top), int(pad_left), self._stream())
+
+    def yuv_surface_encode(self, buf, surface, src_u8=None, src=None, pad_top: int = 0, pad_left: int = 0, bgr: bool = False):
+        """``src_u8`` uint8 [H,W,3] (BGR if ``bgr``; 8-bit surfaces only) or ``src`` fp32 planar RGB [3,Hp,Wp] with the frame at
+        (pad_top, pad_left) -- exactly one -- -> ``buf``, one frame of the TIGHT ``surface`` (a contiguous CUDA uint8 tensor of
+        ``surface.nbytes`` bytes).  A 10-bit surface is encoded from ``src`` in units of 1 / 1023 (include/atmvfi.h
+        atmvfi_yuv_surface_encode; the bits of ``yuv.encode_numpy``)."""
+        if not isinstance(surface, _surface_class()):
+            raise ValueError(f"yuv_surface_encode: surface must be a yuv.Surface (got {type(surface).__name__})")
+        if not surface.is_tight:
+            raise ValueError("yuv_surface_encode: surface must be tight (encodes write no padding: surface.tight())")
+        h, w = surface.height, surface.width
+        _surface(buf, surface, "yuv_surface_encode: buf")
+        if (src is None) == (src_u8 is None):
+            raise ValueError("yuv_surface_encode: give exactly one of src_u8 and src")
+        if src is not None:
+            _f32_canvas(src, "yuv_surface_encode: src")
+            hp, wp = src.shape[1], src.shape[2]
+            if pad_top < 0 or pad_left < 0 or h + pad_top > hp or w + pad_left > wp:
+                raise ValueError(f"yuv_surface_encode: canvas {hp} x {wp} is smaller than the frame {h} x {w} plus padding ({pad_top}, {pad_left})")
+        else:
+            if surface.depth != 8:
+                raise ValueError("yuv_surface_encode: src_u8 encodes 8-bit surfaces only (a 10-bit surface takes the fp32 src)")
+            _u8_frame(src_u8, "yuv_surface_encode: src_u8", (h, w))
+            hp, wp = h, w
+        meta = {"bytes": float(surface.nbytes) + (12.0 if src is not None else 3.0) * h * w}
+        self._run("yuv_surface_encode", meta, self.lib.atmvfi_yuv_surface_encode, _ptr(src_u8), int(bool(bgr)), _ptr(src), hp, wp, int(pad_top),
+                  int(pad_left), h, w, int(surface.depth), surface.matrix_id, int(surface.full_range), surface.siting_id, surface.chroma_id,
+                  int(surface.msb), _ptr(buf), self._stream())
+
+    # The loops' colour conversion: a yuv.Format goes to the planar entry points as ever, a yuv.Surface to the two calls above.
+    def yuv_decode(self, buf, fmt, dst_u8=None, dst=None, window=None, pad_top: int = 0, pad_left: int = 0, keep_depth: bool = False):
+        if isinstance(fmt, _surface_class()):
+            return self.yuv_surface_decode(buf, fmt, dst_u8=dst_u8, dst=dst, window=window, pad_top=pad_top, pad_left=pad_left, keep_depth=keep_depth)
+        if keep_depth:
+            return self.yuv420p10_to_f32(buf, fmt, dst, window=window, pad_top=pad_top, pad_left=pad_left)
+        if window is not None:
+            raise ValueError("yuv_decode: a window of a yuv.Format frame is decoded with keep_depth only")
+        return self.yuv420_to_rgb(buf, fmt, dst_u8=dst_u8, dst=dst, pad_top=pad_top, pad_left=pad_left)
+
+    def yuv_encode(self, buf, fmt, src_u8=None, src=None, pad_top: int = 0, pad_left: int = 0):
+        if isinstance(fmt, _surface_class()):
+            return self.yuv_surface_encode(buf, fmt, src_u8=src_u8, src=src, pad_top=pad_top, pad_left=pad_left)
+        if fmt.depth == 10:
+            return self.f32_to_yuv420p10(buf, fmt, src, pad_top=pad_top, pad_left=pad_left)
+        return self.rgb_to_yuv420(buf, fmt, src_u8=src_u8, src=src, pad_top=pad_top, pad_left=pad_left)
 
     def frame_f32_to_u8(self, src, dst_u8, pad_top: int, pad_left: int, bgr: bool):
         """fp32 planar [3,Hp,Wp] -> crop -> np.round(x * 255) -> uint8 [H,W,3] device tensor (optional RGB -> BGR)."""

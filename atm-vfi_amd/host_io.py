@@ -269,7 +269,10 @@ class FramePipeline:
         if pixfmt is not None:
             if (pixfmt.height, pixfmt.width) != (height, width):
                 raise ValueError(f"FramePipeline: pixfmt describes {pixfmt.height}x{pixfmt.width} frames, the pipeline {height}x{width}")
-            self.bgr, self.out_fmt = False, (pixfmt if self.deep else pixfmt.as_8bit())
+            from . import yuv
+            self.bgr, self.out_fmt = False, yuv.out_format(pixfmt, self.deep)
+            # an original of a padded yuv.Surface leaves as a frame of its tight form, the samples untouched
+            self.original = (lambda f: f) if yuv.passes_through(pixfmt) else (lambda f: yuv.crop(f, pixfmt, 0, 0, height, width))
         in_shape = (height, width, 3) if pixfmt is None else (pixfmt.frame_bytes,)
         out_shape = (height, width, 3) if pixfmt is None else (self.out_fmt.frame_bytes,)
         self.slots = [{
@@ -311,12 +314,12 @@ class FramePipeline:
                 # the slot's previous pair has been delivered (run): its forward no longer reads f0 / f1
                 for k, f in enumerate((slot["f0"], slot["f1"])):
                     if self.deep:
-                        self.ops.yuv420p10_to_f32(slot["d_in"][k], self.pixfmt, f[0], pad_top=self.pad_top, pad_left=self.pad_left)
+                        self.ops.yuv_decode(slot["d_in"][k], self.pixfmt, dst=f[0], pad_top=self.pad_top, pad_left=self.pad_left, keep_depth=True)
                         if self.scene is not None:        # the 8-bit path's signature: its uint8 RGB frame
-                            self.ops.yuv420_to_rgb(slot["d_in"][k], self.pixfmt, dst_u8=slot["rgb"][k])
+                            self.ops.yuv_decode(slot["d_in"][k], self.pixfmt, dst_u8=slot["rgb"][k])
                         continue
-                    self.ops.yuv420_to_rgb(slot["d_in"][k], self.pixfmt, dst_u8=slot["rgb"][k] if self.scene is not None else None,
-                                           dst=f[0], pad_top=self.pad_top, pad_left=self.pad_left)
+                    self.ops.yuv_decode(slot["d_in"][k], self.pixfmt, dst_u8=slot["rgb"][k] if self.scene is not None else None,
+                                        dst=f[0], pad_top=self.pad_top, pad_left=self.pad_left)
             slot["in_ready"].record(self.copy_in)
             if self.scene is not None:
                 # a frame's signature is computed once: the first frame's only when it is not the previous pair's second
@@ -335,7 +338,7 @@ class FramePipeline:
 
     def _deliver(self, slot):
         if slot["cut"]:
-            return np.array(slot["first"], copy=True)
+            return np.array(slot["first"] if self.pixfmt is None else self.original(slot["first"]), copy=True)
         slot["out_ready"].synchronize()
         out = slot["h_out"].numpy().copy()
         return out.view(np.uint16) if self.deep else out
@@ -361,10 +364,8 @@ class FramePipeline:
         it = model.forward(slot["f0"], slot["f1"])["I_t"]
         if self.pixfmt is None:
             self.ops.frame_f32_to_u8(it[0], slot["d_out"], self.pad_top, self.pad_left, self.bgr)
-        elif self.deep:
-            self.ops.f32_to_yuv420p10(slot["d_out"], self.out_fmt, it[0], pad_top=self.pad_top, pad_left=self.pad_left)
         else:
-            self.ops.rgb_to_yuv420(slot["d_out"], self.out_fmt, src=it[0], pad_top=self.pad_top, pad_left=self.pad_left)
+            self.ops.yuv_encode(slot["d_out"], self.out_fmt, src=it[0], pad_top=self.pad_top, pad_left=self.pad_left)
         slot["done"].record(cur)
         self.copy_out.wait_event(slot["done"])
         with torch.cuda.stream(self.copy_out):
@@ -425,10 +426,11 @@ def interpolate_video_2x(frames, model, isBGR: bool = True, divisor: int = 64, d
     height, width = first.shape[:2] if pixfmt is None else (pixfmt.height, pixfmt.width)
     pipe = FramePipeline(model, height, width, isBGR=isBGR, divisor=divisor, depth=depth, streams=streams, scene=scene, pixfmt=pixfmt,
                          keep_depth=keep_depth)
+    original = (lambda f: f) if pixfmt is None else pipe.original
     for pred in pipe.run(pairs()):
-        yield originals.popleft()
+        yield original(originals.popleft())
         yield pred
-    yield originals.popleft()          # the last frame is written once (demo_2x.py:160)
+    yield original(originals.popleft())          # the last frame is written once (demo_2x.py:160)
 
 
 # cv2.VideoCapture property ids (cv2.CAP_PROP_*; the image has no OpenCV, and the adapters below only need the numbers)

@@ -204,7 +204,7 @@ class _Uploader:
             else:
                 slot["yuv"].copy_(slot["h"], non_blocking=True)
                 if slot["d"] is not None:
-                    self.pixfmt[0].yuv420_to_rgb(slot["yuv"], self.pixfmt[1], dst_u8=slot["d"])
+                    self.pixfmt[0].yuv_decode(slot["yuv"], self.pixfmt[1], dst_u8=slot["d"])
             slot["ready"].record(self.copy_in)
             if self.sig is not None:
                 ops, (y0, x0, h, w), bgr = self.sig
@@ -342,8 +342,8 @@ class _SegmentRunner:
         def convert(d_u8):
             dst = self.frames[0][slot]
             if self.deep_fmt is not None:             # d_u8: the frame's I420 bytes
-                self.ops.yuv420p10_to_f32(d_u8, self.deep_fmt, dst, window=(self.y0, self.x0, self.h, self.w), pad_top=self.pad_top,
-                                          pad_left=self.pad_left)
+                self.ops.yuv_decode(d_u8, self.deep_fmt, dst=dst, window=(self.y0, self.x0, self.h, self.w), pad_top=self.pad_top,
+                                    pad_left=self.pad_left, keep_depth=True)
             elif (self.y0, self.x0, self.h, self.w) == (0, 0) + tuple(d_u8.shape[:2]):
                 self.ops.frame_u8_to_f32(d_u8, dst, self.pad_top, self.pad_left, self.bgr)
             else:
@@ -442,13 +442,13 @@ class _SegmentRunner:
                     if self.tta:                       # the fp32 average, then its encoding
                         self.ops.tta_merge(pred, flip, out=self.merged)
                         src = self.merged
-                    self.ops.f32_to_yuv420p10(u8, self.out_fmt, src, pad_top=self.pad_top, pad_left=self.pad_left)
+                    self.ops.yuv_encode(u8, self.out_fmt, src=src, pad_top=self.pad_top, pad_left=self.pad_left)
                 elif self.out_fmt is not None:
                     if self.tta:                       # the average's uint8 pixels, then their encoding
                         self.ops.tta_merge(pred, flip, out_u8=self.merged, pad_top=self.pad_top, pad_left=self.pad_left, bgr=False)
-                        self.ops.rgb_to_yuv420(u8, self.out_fmt, src_u8=self.merged)
+                        self.ops.yuv_encode(u8, self.out_fmt, src_u8=self.merged)
                     else:
-                        self.ops.rgb_to_yuv420(u8, self.out_fmt, src=pred, pad_top=self.pad_top, pad_left=self.pad_left)
+                        self.ops.yuv_encode(u8, self.out_fmt, src=pred, pad_top=self.pad_top, pad_left=self.pad_left)
                 elif self.tta:
                     self.ops.tta_merge(pred, flip, out_u8=u8, pad_top=self.pad_top, pad_left=self.pad_left, bgr=self.bgr)
                 else:
@@ -500,7 +500,7 @@ class _SegmentRunner:
             self.ops.shutter_resolve(st["accs"][a[0]], a[2], self.out_d[k], light=st["light"], bgr=self.bgr)
         else:                                                          # the blend's uint8 pixels, then their encoding
             self.ops.shutter_resolve(st["accs"][a[0]], a[2], st["u8"], light=st["light"])
-            self.ops.rgb_to_yuv420(self.out_d[k], self.out_fmt, src_u8=st["u8"])
+            self.ops.yuv_encode(self.out_d[k], self.out_fmt, src_u8=st["u8"])
         return k + 1
 
     def _run_blended(self, levels, ops, cut):
@@ -670,8 +670,8 @@ def interpolate_video_nx(frames, model, factor: int = 4, time_interval: int = 1,
         if crop is not None and (y0 % 2 or x0 % 2):
             raise ValueError(f"interpolate_video_nx: the crop origin ({y0}, {x0}) must be even for 4:2:0 frames")
         deep = bool(keep_depth) and pixfmt.depth == 10
-        isBGR, out_fmt = False, (pixfmt if deep else pixfmt.as_8bit()).cropped(h, w)
-        crop_rgb, whole = crop_of, (h, w) == (H, W)
+        isBGR, out_fmt = False, yuv.out_format(pixfmt, deep).cropped(h, w)
+        crop_rgb, whole = crop_of, (h, w) == (H, W) and yuv.passes_through(pixfmt)     # (a padded yuv.Surface: originals lose the padding)
         crop_of = (lambda f: f) if whole else (lambda f: yuv.crop(f, pixfmt, y0, x0, h, w))          # of the caller's I420 frames
     ops, dev = _hip_ops_of(model)
     if ops is None or not hasattr(ops, "pool_blocks"):

@@ -446,8 +446,8 @@ def _retimed(frames, model, fi, fo, levels, dedup, crop, isBGR, divisor, tta, ma
         if crop is not None and (y0 % 2 or x0 % 2):
             raise ValueError(f"interpolate_video_retimed: the crop origin ({y0}, {x0}) must be even for 4:2:0 frames")
         deep = bool(keep_depth) and pixfmt.depth == 10
-        isBGR, out_fmt = False, (pixfmt if deep else pixfmt.as_8bit()).cropped(h, w)
-        original = (lambda f: f) if whole else (lambda f: yuv.crop(f, pixfmt, y0, x0, h, w))
+        isBGR, out_fmt = False, yuv.out_format(pixfmt, deep).cropped(h, w)
+        original = (lambda f: f) if (whole and yuv.passes_through(pixfmt)) else (lambda f: yuv.crop(f, pixfmt, y0, x0, h, w))
     elif first.ndim != 3 or first.shape[2] != 3 or first.dtype != np.uint8:
         raise ValueError(f"interpolate_video_retimed: expected uint8 [H,W,3] frames, got {first.dtype} {tuple(first.shape)}")
     ops, dev = _hip_ops_of(model)

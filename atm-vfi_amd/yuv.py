@@ -17,7 +17,13 @@ By default 10-bit input is decoded to 8-bit RGB and what the loops produce is 8-
 ``atmvfi_f32_to_yuv420p10``, the same two files; twins ``decode_numpy_f32`` and ``encode_numpy`` of an fp32 source): the same chroma
 filters on the 10-bit samples, ``COEFFS10[matrix]`` at 14 bits (luma scaled by 876 / 1023, chroma by 896 / 1023), offsets 64 / 512,
 RGB clipped to 0..1023 and handed to the network as ``q / 1023`` (the fp32 division); encoding takes
-``clip(rint(fl32(x * 1023)), 0, 1023)`` and writes uint16 samples.  Produced frames are 10-bit, originals the caller's arrays."""
+``clip(rint(fl32(x * 1023)), 0, 1023)`` and writes uint16 samples.  Produced frames are 10-bit, originals the caller's arrays.
+
+``Surface`` (``atmvfi_yuv_surface_decode`` / ``atmvfi_yuv_surface_encode``): what a hardware decoder or an ``ffmpeg -f rawvideo``
+pipe delivers -- NV12 / NV21 / P010 (interleaved chroma, 10-bit samples in the upper bits) and frames with a row pitch and a chroma
+offset.  It is accepted wherever a ``Format`` is (``pixfmt=``, the twins, ``crop``, ``to_8bit``); the arithmetic is the ``Format``'s,
+applied to the samples the surface describes.  ``repack`` moves frames between layouts, ``RawReader`` / ``RawWriter`` /
+``interpolate_raw`` are the headerless counterparts of the Y4M classes."""
 from __future__ import annotations
 
 import io
@@ -147,8 +153,181 @@ class Format:
         return replace(self, height=int(h), width=int(w))
 
 
-def planes(buf, fmt: Format):
+CHROMAS = ("planar", "uv", "vu")
+
+
+@dataclass(frozen=True)
+class Surface:
+    """One frame as a decoder hands it over: one contiguous buffer of ``fmt.dtype`` samples with a layout.  ``fmt`` (a ``Format``)
+    supplies size, matrix, range, siting and depth; the pixel arithmetic is the ``Format``'s, applied to the samples found here.
+
+    ``chroma``: "planar" (the U plane, then the V plane), "uv" (one plane of interleaved pairs, U first: NV12 / P010) or "vu" (V
+    first: NV21).  ``msb`` (depth 10 only): a stored sample is ``value << 6``; decoding takes ``s >> 6``, encoding writes ``v << 6``.
+    ``pitch`` / ``chroma_pitch``: row strides in bytes, multiples of the sample size and at least the row's own bytes; default tight
+    (``W b``; ``cw b`` planar, ``2 cw b`` interleaved).  ``chroma_offset``: the byte offset of the first chroma row, a multiple of the
+    sample size and at least ``pitch * H`` (the default); planar V follows U at ``chroma_offset + chroma_pitch * ch``.  ``nbytes``:
+    the whole buffer through the last chroma row's own bytes; frames are 1-D arrays of ``nbytes // itemsize`` samples.  Padding is
+    never read; encodes write tight surfaces only.  ``Surface.i420(h, w)`` is byte for byte a ``Format`` frame."""
+    fmt: Format
+    chroma: str = "planar"
+    msb: bool = False
+    pitch: Optional[int] = None
+    chroma_pitch: Optional[int] = None
+    chroma_offset: Optional[int] = None
+
+    def __post_init__(self):
+        if not isinstance(self.fmt, Format):
+            raise ValueError(f"yuv.Surface: fmt must be a yuv.Format (got {type(self.fmt).__name__})")
+        if self.chroma not in CHROMAS:
+            raise ValueError(f"yuv.Surface: unknown chroma layout {self.chroma!r} (planar, uv, vu)")
+        if self.msb and self.fmt.depth != 10:
+            raise ValueError("yuv.Surface: msb needs depth 10 (8-bit samples fill their byte)")
+        b, (H, W), (ch, cw) = self.itemsize, (self.fmt.height, self.fmt.width), self.fmt.chroma_shape
+        crow = (cw if self.chroma == "planar" else 2 * cw) * b
+        pitch = W * b if self.pitch is None else int(self.pitch)
+        cpitch = crow if self.chroma_pitch is None else int(self.chroma_pitch)
+        if pitch % b or pitch < W * b:
+            raise ValueError(f"yuv.Surface: pitch {pitch} must be a multiple of the sample size {b} and at least a luma row's {W * b} bytes")
+        if cpitch % b or cpitch < crow:
+            raise ValueError(f"yuv.Surface: chroma_pitch {cpitch} must be a multiple of the sample size {b} and at least a chroma row's "
+                             f"{crow} bytes")
+        off = pitch * H if self.chroma_offset is None else int(self.chroma_offset)
+        if off % b or off < pitch * H:
+            raise ValueError(f"yuv.Surface: chroma_offset {off} must be a multiple of the sample size {b} and at least pitch * H = {pitch * H}")
+        object.__setattr__(self, "msb", bool(self.msb))
+        object.__setattr__(self, "pitch", pitch)
+        object.__setattr__(self, "chroma_pitch", cpitch)
+        object.__setattr__(self, "chroma_offset", off)
+        # derived once (the device calls ask for both on every launch); not fields: equality and hash are the layout's
+        rows = 2 * ch - 1 if self.chroma == "planar" else ch - 1
+        object.__setattr__(self, "_nbytes", off + cpitch * rows + crow)
+        object.__setattr__(self, "_tight", (pitch, cpitch, off) == (W * b, crow, W * b * H))
+
+    @classmethod
+    def nv12(cls, h: int, w: int, pitch=None, chroma_offset=None, **format_kw) -> "Surface":
+        """NV12: 8-bit, interleaved UV; the chroma rows share the luma pitch."""
+        return cls(Format(h, w, depth=8, **format_kw), "uv", False, pitch, pitch, chroma_offset)
+
+    @classmethod
+    def p010(cls, h: int, w: int, pitch=None, chroma_offset=None, **format_kw) -> "Surface":
+        """P010: 10-bit samples in the upper bits of 16-bit words, interleaved UV; the chroma rows share the luma pitch."""
+        return cls(Format(h, w, depth=10, **format_kw), "uv", True, pitch, pitch, chroma_offset)
+
+    @classmethod
+    def i420(cls, h: int, w: int, pitch=None, chroma_offset=None, **format_kw) -> "Surface":
+        """Planar I420 (``depth=10``: LSB-aligned uint16); with a ``pitch`` the chroma rows have half of it."""
+        return cls(Format(h, w, **format_kw), "planar", False, pitch, None if pitch is None else int(pitch) // 2, chroma_offset)
+
+    # what the loops and helpers read of a Format
+    height = property(lambda self: self.fmt.height)
+    width = property(lambda self: self.fmt.width)
+    matrix = property(lambda self: self.fmt.matrix)
+    full_range = property(lambda self: self.fmt.full_range)
+    siting = property(lambda self: self.fmt.siting)
+    depth = property(lambda self: self.fmt.depth)
+    dtype = property(lambda self: self.fmt.dtype)
+    chroma_shape = property(lambda self: self.fmt.chroma_shape)
+    matrix_id = property(lambda self: self.fmt.matrix_id)
+    siting_id = property(lambda self: self.fmt.siting_id)
+    chroma_id = property(lambda self: CHROMAS.index(self.chroma))
+
+    @property
+    def itemsize(self) -> int:
+        return 2 if self.fmt.depth == 10 else 1
+
+    @property
+    def nbytes(self) -> int:
+        return self._nbytes
+
+    frame_bytes = nbytes
+
+    @property
+    def frame_samples(self) -> int:
+        return self.nbytes // self.itemsize
+
+    @property
+    def is_tight(self) -> bool:
+        return self._tight
+
+    def tight(self) -> "Surface":
+        return Surface(self.fmt, self.chroma, self.msb)
+
+    def cropped(self, h: int, w: int) -> "Surface":
+        return Surface(self.fmt.cropped(h, w), self.chroma, self.msb)
+
+    def as_8bit(self) -> "Surface":
+        """The tight 8-bit counterpart (P010 -> NV12), itself for a tight 8-bit surface."""
+        return self.tight() if self.fmt.depth == 8 else Surface(self.fmt.as_8bit(), self.chroma, False)
+
+    def check(self, buf, what: str = "yuv") -> np.ndarray:
+        """``buf`` as the 1-D sample array of one frame of this surface (a view), or ``ValueError``."""
+        a = np.asarray(buf)
+        if a.dtype != self.dtype or a.size != self.frame_samples or not a.flags.c_contiguous:
+            raise ValueError(f"{what}: a contiguous {np.dtype(self.dtype).name} {self.chroma} surface of {self.frame_samples} samples "
+                             f"({self.height} x {self.width}, pitch {self.pitch}) expected, got {a.dtype} {tuple(a.shape)}")
+        return a.reshape(-1)
+
+    def planes(self, buf):
+        """(Y [H,W], U [ch,cw], V [ch,cw]) strided views of the STORED samples (``msb``: still shifted); padding is not part of them."""
+        a = self.check(buf, "yuv.Surface.planes")
+        b, (ch, cw) = self.itemsize, self.fmt.chroma_shape
+        view = lambda off, rows, cols, rs, cs: np.lib.stride_tricks.as_strided(a[off // b:], (rows, cols), (rs, cs), writeable=a.flags.writeable)
+        Y = view(0, self.height, self.width, self.pitch, b)
+        if self.chroma == "planar":
+            return Y, view(self.chroma_offset, ch, cw, self.chroma_pitch, b), \
+                view(self.chroma_offset + self.chroma_pitch * ch, ch, cw, self.chroma_pitch, b)
+        first, second = (view(self.chroma_offset + k * b, ch, cw, self.chroma_pitch, 2 * b) for k in (0, 1))
+        return (Y, first, second) if self.chroma == "uv" else (Y, second, first)
+
+
+def as_surface(fmt) -> Surface:
+    """A ``Surface`` as it is; a ``Format`` as its tight planar surface (the same bytes)."""
+    return fmt if isinstance(fmt, Surface) else Surface(fmt)
+
+
+def planes(buf, fmt):
     return fmt.planes(buf)
+
+
+def out_format(pixfmt, deep: bool):
+    """What the loops produce for input of ``pixfmt``: the format itself with the depth kept, its 8-bit form otherwise; a ``Surface``
+    without its padding (P010 in: P010 out with ``deep``, NV12 out without)."""
+    if isinstance(pixfmt, Surface):
+        return pixfmt.tight() if deep else pixfmt.as_8bit()
+    return pixfmt if deep else pixfmt.as_8bit()
+
+
+def passes_through(pixfmt) -> bool:
+    """An uncropped original of ``pixfmt`` leaves the loops as the caller's own array: every ``Format``, a ``Surface`` without padding."""
+    return not isinstance(pixfmt, Surface) or pixfmt.is_tight
+
+
+def _samples(buf, fmt):
+    """The frame's sample VALUES as int32 (Y, U, V): a ``Format``'s planes, or a ``Surface``'s with the ``msb`` shift undone."""
+    Y, U, V = (p.astype(np.int32) for p in fmt.planes(buf))
+    if isinstance(fmt, Surface) and fmt.msb:
+        Y, U, V = Y >> 6, U >> 6, V >> 6
+    return Y, U, V
+
+
+def _pack(Y, U, V, s: Surface) -> np.ndarray:
+    """Sample values (``msb``: shifted here) -> one frame of ``s``; padding samples are zero."""
+    out = np.zeros(s.frame_samples, s.dtype)
+    sh = 6 if s.msb else 0
+    for dst, src in zip(s.planes(out), (Y, U, V)):
+        dst[...] = np.asarray(src).astype(np.int64) << sh
+    return out
+
+
+def repack(buf, src, dst) -> np.ndarray:
+    """One frame of ``src`` as a frame of ``dst`` (each a ``Surface`` or a ``Format``; the same size and depth): the sample values
+    untouched, moved between layouts; ``msb`` shifts by 6 (into an ``msb`` surface the low bits are zero).  Padding of ``dst`` is zero."""
+    a, b = as_surface(src), as_surface(dst)
+    if (a.height, a.width, a.depth) != (b.height, b.width, b.depth):
+        raise ValueError(f"yuv.repack: {a.height} x {a.width} depth {a.depth} and {b.height} x {b.width} depth {b.depth} differ in size or depth")
+    Y, U, V = a.planes(buf)
+    sh = 6 if a.msb else 0
+    return _pack(Y >> sh, U >> sh, V >> sh, b)
 
 
 def _chroma_taps(ys, xs, ch: int, cw: int, siting: str):
@@ -184,7 +363,7 @@ def _to_rgb(Y, U, V, taps, coeffs, yo: int, mid: int, T: int, top: int) -> np.nd
 
 def _decode_window(buf, fmt: Format, y0: int, x0: int, h: int, w: int, keep: bool = False) -> np.ndarray:
     """The checked window of the whole frame's decode as int32 [h,w,3] RGB: 0..255, or 0..1023 with the 10-bit depth kept."""
-    Y, U, V = (p.astype(np.int32) for p in fmt.planes(buf))
+    Y, U, V = _samples(buf, fmt)
     taps = _chroma_taps(np.arange(y0, y0 + h), np.arange(x0, x0 + w), *fmt.chroma_shape, fmt.siting)
     if keep:
         pixel = COEFFS10[fmt.matrix][0], 64, 512, 14, 1023
@@ -270,6 +449,10 @@ def encode_numpy(rgb, fmt: Format, bgr: bool = False) -> np.ndarray:
         s, sh = rows[:, ca] + rows[:, np.minimum(ca + 1, W - 1)], 2
     U = np.clip(((dot(eU, s) + (1 << (13 + sh))) >> (14 + sh)) + mid, 0, top)
     V = np.clip(((dot(eV, s) + (1 << (13 + sh))) >> (14 + sh)) + mid, 0, top)
+    if isinstance(fmt, Surface):
+        if not fmt.is_tight:
+            raise ValueError("encode_numpy: encodes write tight surfaces only (surface.tight())")
+        return _pack(Y, U, V, fmt)
     return np.concatenate([Y.reshape(-1), U.reshape(-1), V.reshape(-1)]).astype(np.uint16 if deep else np.uint8)
 
 
@@ -283,6 +466,11 @@ def crop(buf, fmt: Format, y0: int, x0: int, h: int, w: int) -> np.ndarray:
         raise ValueError(f"yuv.crop: window {h} x {w} at ({y0}, {x0}) outside the {fmt.height} x {fmt.width} frame")
     Y, U, V = fmt.planes(buf)
     ch, cw = (h + 1) // 2, (w + 1) // 2
+    if isinstance(fmt, Surface):            # the tight surface of the window, the stored samples as they are
+        out = np.empty(fmt.cropped(h, w).frame_samples, fmt.dtype)
+        oy, ou, ov = fmt.cropped(h, w).planes(out)
+        oy[...], ou[...], ov[...] = Y[y0:y0 + h, x0:x0 + w], U[y0 // 2:y0 // 2 + ch, x0 // 2:x0 // 2 + cw], V[y0 // 2:y0 // 2 + ch, x0 // 2:x0 // 2 + cw]
+        return out
     return np.concatenate([Y[y0:y0 + h, x0:x0 + w].reshape(-1), U[y0 // 2:y0 // 2 + ch, x0 // 2:x0 // 2 + cw].reshape(-1),
                            V[y0 // 2:y0 // 2 + ch, x0 // 2:x0 // 2 + cw].reshape(-1)])
 
@@ -466,7 +654,121 @@ class Y4MWriter:
         return False
 
 
-def to_8bit(frame, fmt: Format) -> np.ndarray:
+class RawReader:
+    """A headerless stream of frames of ``surface`` (a ``Surface`` or a ``Format``) at ``fps`` -- what ``ffmpeg -f rawvideo -pix_fmt
+    nv12|p010le|yuv420p...`` pipes -- from a path or a binary file object.  As ``Y4MReader``: iterating yields 1-D arrays of
+    ``surface.dtype`` (little-endian on the wire), short reads of a pipe are completed, a frame cut off by the end of the stream is a
+    ``ValueError``, ``skip(count)``, ``len()`` when seekable, a context manager."""
+
+    def __init__(self, path_or_file, surface, fps):
+        self._own = isinstance(path_or_file, (str, os.PathLike))
+        self.f = open(path_or_file, "rb") if self._own else path_or_file
+        self.surface = self.fmt = surface
+        self.fps = Fraction(fps)
+        self._n = int(surface.frame_bytes)
+        try:
+            self._data0 = self.f.tell() if self.f.seekable() else None
+        except (AttributeError, OSError, io.UnsupportedOperation):
+            self._data0 = None
+
+    def _end(self):
+        pos = self.f.tell()
+        end = self.f.seek(0, os.SEEK_END)
+        self.f.seek(pos)
+        return end
+
+    def __len__(self):
+        if self._data0 is None:
+            raise TypeError("RawReader: the stream is not seekable: no length")
+        return (self._end() - self._data0) // self._n
+
+    def __iter__(self) -> Iterator[np.ndarray]:
+        n = self._n
+        while True:
+            data = self.f.read(n)
+            if not data:
+                return
+            while len(data) < n:                # pipes deliver short reads
+                more = self.f.read(n - len(data))
+                if not more:
+                    break
+                data += more
+            if len(data) != n:
+                raise ValueError(f"RawReader: truncated frame ({len(data)} of {n} bytes)")
+            yield np.frombuffer(data, dtype="<u2" if self.surface.depth == 10 else np.uint8).astype(self.surface.dtype, copy=True)
+
+    def skip(self, count: int) -> int:
+        """Pass over the next ``count`` frames without delivering them (a seek per frame when seekable, read and dropped otherwise).
+        Returns how many were there to skip."""
+        n, done = self._n, 0
+        end = self._end() if self._data0 is not None else None
+        while done < count:
+            if end is not None:
+                left = end - self.f.tell()
+                if left <= 0:
+                    break
+                if left < n:
+                    raise ValueError(f"RawReader: truncated frame ({left} of {n} bytes)")
+                self.f.seek(n, os.SEEK_CUR)
+            else:
+                left = n
+                while left:
+                    got = len(self.f.read(min(left, 1 << 22)))
+                    if not got:
+                        break
+                    left -= got
+                if left == n:
+                    break
+                if left:
+                    raise ValueError(f"RawReader: truncated frame ({n - left} of {n} bytes)")
+            done += 1
+        return done
+
+    def close(self):
+        if self._own:
+            self.f.close()
+
+    release = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+class RawWriter:
+    """Writes frames of ``surface`` (a ``Surface`` or a ``Format``) back to back, headerless, little-endian."""
+
+    def __init__(self, path_or_file, surface):
+        self._own = isinstance(path_or_file, (str, os.PathLike))
+        self.f = open(path_or_file, "wb") if self._own else path_or_file
+        self.surface = self.fmt = surface
+        self.frames = 0
+
+    def write(self, frame):
+        a = self.surface.check(frame, "RawWriter.write")
+        self.f.write(a.astype("<u2", copy=False).tobytes() if self.surface.depth == 10 else a.tobytes())
+        self.frames += 1
+
+    def close(self):
+        if self._own:
+            self.f.close()
+        else:
+            self.f.flush()
+
+    release = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+def to_8bit(frame, fmt) -> np.ndarray:
     """A frame of ``fmt`` as a frame of ``fmt.as_8bit()``: itself for 8-bit input; 10-bit input goes through RGB on the host
     (``encode_numpy(decode_numpy(frame))``: the 8-bit picture the loops saw)."""
     if fmt.depth == 8:
@@ -528,6 +830,83 @@ def interpolate_y4m(src, dst, model, factor: int = 2, scene=None, tta: bool = Fa
         rd.close()
         wr.close()
     info = {"fps_in": rd.fps, "fps_out": rate, "size": (ow, oh), "frames_in": n_in[0], "frames_out": wr.frames}
+    if scene is not None:
+        info["cuts"] = list(scene.cuts)
+    return info
+
+
+PIX_FMTS = {"nv12": ("uv", 8, False), "nv21": ("vu", 8, False), "p010le": ("uv", 10, True), "yuv420p": ("planar", 8, False),
+            "yuv420p10le": ("planar", 10, False)}
+
+
+def surface_of(pix_fmt: str, h: int, w: int, pitch=None, **format_kw) -> Surface:
+    """ffmpeg's ``-pix_fmt`` name (nv12, nv21, p010le, yuv420p, yuv420p10le) -> the ``Surface``; ``pitch`` (bytes): the luma rows' and
+    the interleaved chroma rows', planar chroma rows half of it."""
+    if pix_fmt not in PIX_FMTS:
+        raise ValueError(f"yuv.surface_of: unknown pixel format {pix_fmt!r} ({', '.join(PIX_FMTS)})")
+    chroma, depth, msb = PIX_FMTS[pix_fmt]
+    cp = None if pitch is None else (int(pitch) // 2 if chroma == "planar" else int(pitch))
+    return Surface(Format(h, w, depth=depth, **format_kw), chroma, msb, pitch, cp)
+
+
+def interpolate_raw(src, dst, model, surface, fps, factor: int = 2, scene=None, tta: bool = False, interpolator=None,
+                    keep_depth: bool = False, fps_out=None, levels: int = 3, dedup=None, shutter=None, **kw):
+    """``interpolate_y4m`` for headerless streams (``RawReader`` / ``RawWriter``): frames of ``surface`` at ``fps`` in ``src`` ->
+    frames of ``surface.tight().cropped(h, w)`` in ``dst`` (the 8-bit counterpart for 10-bit input without ``keep_depth``, originals
+    converted on the host), at ``fps * factor`` or at ``fps_out``.  Every keyword is ``interpolate_y4m``'s (there is no ``matrix``: the
+    surface's format names it); the same dict is returned."""
+    from .host_io import _hip_ops_of, interpolate_video_2x
+    from .multiframe import centre_window, interpolate_video_nx, nx_levels
+    from .retime import _check_rates, interpolate_video_retimed
+    surface = as_surface(surface)
+    if fps_out is None:
+        if shutter is not None:
+            raise ValueError("interpolate_raw: shutter needs fps_out (the synthetic shutter belongs to the rate conversion)")
+        nx_levels(factor)
+        rate = Fraction(fps) * factor / int(kw.get("time_interval", 1))
+    else:
+        if "time_interval" in kw:
+            raise ValueError("interpolate_raw: fps_out and time_interval do not go together")
+        _, rate, levels = _check_rates(Fraction(fps), fps_out, levels)
+    _, _, oh, ow = centre_window(surface.height, surface.width, kw.get("crop"))
+    deep = bool(keep_depth) and surface.depth == 10
+    src_out = surface.tight().cropped(oh, ow)
+    out = src_out if deep else src_out.as_8bit()
+    rd, wr = RawReader(src, surface, fps), RawWriter(dst, out)
+    n_in, report = [0], {}
+
+    def counted():
+        for f in rd:
+            n_in[0] += 1
+            yield f
+    if fps_out is not None:
+        if shutter is not None:
+            kw["shutter"] = shutter
+        run = lambda: (interpolator or interpolate_video_retimed)(counted(), model, rd.fps, rate, levels=levels, dedup=dedup, scene=scene, tta=tta,
+                                                                  pixfmt=surface, keep_depth=deep, report=report, **kw)
+    else:
+        if deep:
+            kw["keep_depth"] = True
+        if interpolator is None:
+            nx_only = tta or factor != 2 or any(k in kw for k in ("crop", "time_interval", "max_batch", "pool"))
+            if not nx_only and _hip_ops_of(model)[0] is not None:
+                interpolator = interpolate_video_2x
+            else:
+                interpolator = lambda frames, model, **k: interpolate_video_nx(frames, model, factor=factor, tta=tta, **k)
+        run = lambda: interpolator(counted(), model, pixfmt=surface, scene=scene, **kw)
+    try:
+        for f in run():
+            wr.write(to_8bit(f, src_out) if (f.dtype == np.uint16 and not deep) else f)
+    finally:
+        rd.close()
+        wr.close()
+    info = {"fps_in": rd.fps, "fps_out": rate, "size": (ow, oh), "frames_in": n_in[0], "frames_out": wr.frames}
+    if fps_out is not None:
+        info["forwards"] = report.get("forwards", 0)
+        if shutter is not None:
+            info["blended"] = report.get("blended", 0)
+        if dedup is not None:
+            info["dropped"] = list(dedup.dropped)
     if scene is not None:
         info["cuts"] = list(scene.cuts)
     return info

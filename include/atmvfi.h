@@ -603,6 +603,41 @@ int atmvfi_yuv420p10_to_f32(const void* yuv, int H, int W, int matrix, int sitin
 int atmvfi_f32_to_yuv420p10(const float* src, int Hp, int Wp, int pad_top, int pad_left, int H, int W, int matrix, int siting, void* yuv,
                             void* stream);
 
+/* Decoder surfaces: NV12 / NV21 / P010 and pitched frames (yuv.hip, yuv_encode.hip; ABI 0.19; atm-vfi_amd/yuv.py: Surface holds the
+ * definition on the host).  The pixel arithmetic is that of the four calls above, unchanged; what is new is where the samples lie.
+ * One frame is one buffer of samples (uint8, or little-endian uint16 at depth 10):
+ *   chroma         0: planar, the U plane then the V plane (I420); 1: one plane of interleaved pairs, U first (NV12, P010); 2: the
+ *                  same, V first (NV21)
+ *   msb            depth 10 only (refused at depth 8): a stored sample is value << 6 (P010); decoding takes s >> 6 and ignores the low six
+ *                  bits, encoding writes v << 6 with the low bits zero
+ *   pitch, chroma_pitch   row strides in BYTES of the luma rows and of the chroma rows: multiples of the sample size, at least the row's
+ *                  own bytes (W b; cw b planar, 2 cw b interleaved; b = 1 or 2).  0: tight
+ *   chroma_offset  the byte offset of the first chroma row: a multiple of the sample size, at least pitch * H.  0: pitch * H.  The
+ *                  planar V plane follows U at chroma_offset + chroma_pitch * ch.
+ * The buffer ends with the last chroma row's own bytes; padding bytes are never read.
+ * atmvfi_yuv_surface_decode: the window (y0, x0, h, w) of the surface -- inside the frame, even origin -- to (pad_top, pad_left) of dst
+ *   (fp32 planar RGB [3,Hp,Wp], replicate padding by clamping the output coordinate into the window) and / or to dst_u8 (uint8 [h,w,3],
+ *   BGR if `bgr`); chroma neighbours clamp at the FRAME's edges.  keep_depth 0: clip8 RGB and q / 255 from samples of either depth, the
+ *   pixel of atmvfi_yuv420_to_rgb; keep_depth 1 (depth 10, dst only): q / 1023, the pixel of atmvfi_yuv420p10_to_f32.  A tight planar
+ *   surface gives the bytes of those calls.
+ * atmvfi_yuv_surface_encode: exactly one of src_u8 (uint8 [H,W,3], BGR if `bgr`; depth 8 only) and src (the fp32 canvas, the frame at
+ *   (pad_top, pad_left)) -> a TIGHT surface of `chroma` / `msb`: at depth 8 the samples of atmvfi_rgb_to_yuv420, at depth 10 (src only)
+ *   those of atmvfi_f32_to_yuv420p10.  No padding byte is ever written.
+ * Any pitch, offset and pointer alignment is accepted (byte accesses).  The vector path -- dword / 8-byte Y groups, an interleaved
+ * chroma row loaded ONCE for both planes (the aligned centre pair-of-pairs as one dword or one 8-byte load, each outer column as one
+ * 2-byte or dword load: three loads per chroma row where two planes take six), both planes' chroma of a lane stored as one dword or
+ * one 8-byte store -- runs when the pointers are aligned as for the calls above, pitch is a multiple of 4 bytes, interleaved chroma has
+ * chroma_pitch and chroma_offset multiples of 4 bytes (planar chroma: of 2 samples), and W, x0, w, Wp, pad_left are multiples of 4.
+ * Both paths give the same bits.  Every output byte is written by exactly one lane; vector stores only, no atomics, nothing
+ * pre-zeroed.  All checks run on the host before the launch (ATMVFI_EINVAL).
+ * A decoder's surface that already lies in device memory (rocDecode, VA-API / AMF interop) is decoded in place by the first call:
+ * hand over the mapped pointer with the surface's pitch and chroma offset; nothing is repacked or copied. */
+int atmvfi_yuv_surface_decode(const void* yuv, int H, int W, int depth, int matrix, int full_range, int siting, int chroma, int msb,
+                              int64_t pitch, int64_t chroma_pitch, int64_t chroma_offset, int keep_depth, int y0, int x0, int h, int w,
+                              void* dst_u8, int bgr, float* dst, int Hp, int Wp, int pad_top, int pad_left, void* stream);
+int atmvfi_yuv_surface_encode(const void* src_u8, int bgr, const float* src, int Hp, int Wp, int pad_top, int pad_left, int H, int W,
+                              int depth, int matrix, int full_range, int siting, int chroma, int msb, void* yuv, void* stream);
+
 /* mean |a - b| per sample: global_alignmentness (network_base.py:560-561).  Two passes with a fixed summation order -- the result is
  * run-to-run bit-identical (the ensemble's pick compares these means) -- through `workspace`: at least
  * atmvfi_l1_mean_workspace_floats(B, per_sample) floats of scratch, the caller's. */

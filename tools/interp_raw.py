@@ -1,0 +1,81 @@
+#!/usr/bin/env python3
+"""Headerless video in, headerless video out at ``factor`` times the frame rate (``atm-vfi_amd.yuv.interpolate_raw``): the frames of an
+``ffmpeg -f rawvideo -pix_fmt nv12|nv21|p010le|yuv420p|yuv420p10le`` pipe travel as they are and are converted on the GPU; nothing is
+repacked on the host.  The output has the same pixel format without row padding; 10-bit input is written back as its 8-bit
+counterpart (p010le -> nv12), or with ``--keep-depth`` at 10 bits.  ``-`` reads standard input / writes standard output
+(``ffmpeg -i in.mp4 -f rawvideo -pix_fmt nv12 - | interp_raw.py - out.nv12 --pix-fmt nv12 --size 1920x1080 --fps 30000/1001 --ckpt ...``).
+
+    python tools/interp_raw.py IN OUT --pix-fmt FMT --size WxH --fps R [--pitch N] [--matrix auto|bt601|bt709] [--siting centre|left]
+                              [--full-range] --ckpt CKPT [--model base|lite] [--factor 2|4|8] [--scene] [--tta] [--global-off]
+                              [--keep-depth] [--fps-out R [--levels L] [--dedup] [--shutter ANGLE [--light code|linear]]]
+
+``--pitch N``: the input's luma row stride in bytes (a decoder's surface dump; interleaved chroma rows share it, planar ones have
+half).  Everything from ``--factor`` on is ``interp_y4m.py``'s."""
+import argparse
+import importlib
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("src")
+    ap.add_argument("dst")
+    ap.add_argument("--pix-fmt", required=True, choices=("nv12", "nv21", "p010le", "yuv420p", "yuv420p10le"))
+    ap.add_argument("--size", required=True, metavar="WxH")
+    ap.add_argument("--fps", required=True, metavar="R", help="the input's frame rate (e.g. 25 or 30000/1001)")
+    ap.add_argument("--pitch", type=int, default=None, metavar="N", help="luma row stride of the input in bytes (default: tight)")
+    ap.add_argument("--matrix", choices=("auto", "bt601", "bt709"), default="auto")
+    ap.add_argument("--siting", choices=("centre", "left"), default="left", help="chroma siting (decoders deliver left-sited 4:2:0)")
+    ap.add_argument("--full-range", action="store_true")
+    ap.add_argument("--ckpt", default=None, help="checkpoint (the trainer's dict or a bare state dict); without one: synthetic weights")
+    ap.add_argument("--model", choices=("base", "lite"), default="base")
+    ap.add_argument("--factor", type=int, default=2)
+    ap.add_argument("--scene", action="store_true", help="scene-cut detection (SceneCuts() defaults)")
+    ap.add_argument("--tta", action="store_true", help="flip test-time augmentation of every produced frame")
+    ap.add_argument("--global-off", action="store_true", help="switch the global motion branch off")
+    ap.add_argument("--keep-depth", action="store_true", help="write 10-bit input back at 10 bits instead of 8")
+    ap.add_argument("--fps-out", default=None, metavar="R", help="convert the frame rate to R (e.g. 60 or 60000/1001); --factor is ignored")
+    ap.add_argument("--levels", type=int, default=3, help="with --fps-out: 2**L positions per segment (1..6)")
+    ap.add_argument("--dedup", action="store_true", help="with --fps-out: drop repeated frames (Duplicates() defaults)")
+    ap.add_argument("--shutter", default=None, metavar="ANGLE", help="with --fps-out: a synthetic shutter of ANGLE degrees (e.g. 180)")
+    ap.add_argument("--light", choices=("code", "linear"), default="linear", help="with --shutter: the domain the samples are averaged in")
+    a = ap.parse_args()
+    if (a.dedup or a.levels != 3 or a.shutter is not None) and a.fps_out is None:
+        ap.error("--levels, --dedup and --shutter need --fps-out")
+    if a.light != "linear" and a.shutter is None:
+        ap.error("--light needs --shutter")
+    try:
+        w, h = (int(v) for v in a.size.lower().split("x"))
+    except ValueError:
+        ap.error(f"--size must be WxH (got {a.size!r})")
+    yuv = importlib.import_module("atm-vfi_amd.yuv")
+    surface = yuv.surface_of(a.pix_fmt, h, w, pitch=a.pitch, matrix=a.matrix, siting=a.siting, full_range=a.full_range)
+    if not torch.cuda.is_available():
+        sys.exit("interp_raw: no GPU")
+    pkg = importlib.import_module("atm-vfi_amd")
+    torch.set_grad_enabled(False)
+    net = pkg.NetworkBase() if a.model == "base" else pkg.NetworkLite()
+    if a.ckpt:
+        yuv.load_model_checkpoint(net, a.ckpt)
+    else:
+        print("interp_raw: no --ckpt: synthetic weights (the output is not a meaningful interpolation)", file=sys.stderr)
+        net.load_state_dict(pkg.synthetic_state_dict(a.model, seed=1), strict=True)
+    net = net.to(torch.device("cuda:0")).eval()
+    net.global_motion = not a.global_off
+    src = sys.stdin.buffer if a.src == "-" else a.src
+    dst = sys.stdout.buffer if a.dst == "-" else a.dst
+    info = yuv.interpolate_raw(src, dst, net, surface, a.fps, factor=a.factor, scene=yuv.SceneCuts() if a.scene else None, tta=a.tta,
+                               keep_depth=a.keep_depth,
+                               **(dict(fps_out=a.fps_out, levels=a.levels, dedup=yuv.Duplicates() if a.dedup else None,
+                                       shutter=yuv.Shutter(a.shutter, a.light) if a.shutter is not None else None) if a.fps_out else {}))
+    print({k: (str(v) if k.startswith("fps") else v) for k, v in info.items()}, file=sys.stderr)
+
+
+if __name__ == "__main__":
+    main()
