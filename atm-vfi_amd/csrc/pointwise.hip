@@ -1423,7 +1423,8 @@ extern "C" int atmvfi_resize_bilinear_ac(const float* src, int64_t src_bstride, 
 extern "C" int atmvfi_image_pyramid_pack(const float* im0, const float* im1, float* l1, float* l2, float* l3, float* pack, int B, int H, int W,
                                          void* stream) {
     ATMVFI_REQUIRE(im0 && im1 && l1 && l2 && l3, ATMVFI_EINVAL, "image_pyramid: null pointer");
-    ATMVFI_REQUIRE(B > 0 && H >= 8 && W >= 8 && H % 8 == 0 && W % 8 == 0, ATMVFI_EINVAL, "image_pyramid: H, W must be multiples of 8 (got %dx%d)", H, W);
+    // any size with a non-empty level 3: the kernel takes level l as (H >> l) x (W >> l), F.interpolate(scale_factor=0.5)'s floor
+    ATMVFI_REQUIRE(B > 0 && H >= 8 && W >= 8, ATMVFI_EINVAL, "image_pyramid: H, W must be at least 8 (got %dx%d)", H, W);
     ATMVFI_REQUIRE(!pack || atmvfi::aligned16(pack), ATMVFI_EALIGN, "image_pyramid: pack must be 16-byte aligned");
     const long long total = 2ll * B * 3 * ((long long)(H >> 1) * (W >> 1) + (long long)(H >> 2) * (W >> 2) + (long long)(H >> 3) * (W >> 3)) +
                             (pack ? 2ll * B * H * W : 0);

@@ -375,7 +375,7 @@ int atmvfi_resize_bilinear_ac(const float* src, int64_t src_bstride, int64_t src
                               float value_scale, void* stream);
 
 /* The three x0.5 levels of the image pyramid of both frames (network_base.py:444-448) in one launch: im0 / im1 planar [B,3,H,W]
- * (H, W multiples of 8); l1 / l2 / l3 planar [2B,3,H>>l,W>>l], frame 0's images first.  Bit-identical to atmvfi_resize_bilinear_ac
+ * (H, W >= 8); l1 / l2 / l3 planar [2B,3,H>>l,W>>l], frame 0's images first.  Bit-identical to atmvfi_resize_bilinear_ac
  * applied level by level. */
 int atmvfi_image_pyramid(const float* im0, const float* im1, float* l1, float* l2, float* l3, int B, int H, int W, void* stream);
 /* The same and, with `pack` non-NULL, atmvfi_pack_frames' output [2B,H,W,4] in the same launch (both read only the two frames). */

@@ -77,32 +77,7 @@ def require_instance(want: str, shape, planes_only: bool, dev):
                          f"({torch.cuda.get_device_properties(dev).multi_processor_count} CUs), not {want}: this case would test something else")
 
 
-class _Rows:
-    """What assert_split_of reads of a Planes object, for a sample of its rows."""
-
-    def __init__(self, rows):
-        self._rows = rows
-
-    def to_rows(self):
-        return self._rows
-
-
-def assert_planes_split_of(planes, rows: torch.Tensor, what: str):
-    """The plane pair is bit for bit the split of the fp32 rows [R, C] (finite values) -- everywhere by the same arithmetic on the device,
-    and by the fp64 model's ``assert_split_of`` on the whole result when it is small, else on its first and last 512 rows (the last
-    strip) and 1024 rows in between."""
-    got = planes.to_rows()
-    hi, lo = R.split_on_device(rows)
-    c = rows.shape[1]
-    nhi, nlo = int((got[0, :, :c] != hi).sum()), int((got[1, :, :c] != lo).sum())
-    assert nhi == 0 and nlo == 0, f"{what}: planes differ from the split of the fp32 rows at {nhi} (hi) / {nlo} (lo') places"
-    n = rows.shape[0]
-    if n <= 4096:
-        M.assert_split_of(planes, rows, what)
-        return
-    idx = torch.cat([torch.arange(512), torch.arange(n - 512, n),
-                     torch.randint(512, n - 512, (1024,), generator=torch.Generator().manual_seed(1))]).to(rows.device)
-    M.assert_split_of(_Rows(got[:, idx]), rows[idx], what)
+assert_planes_split_of = R.assert_planes_split_of
 
 
 def run_dwconv(hip, x, w, b, planes_only: bool, what: str):
