@@ -1,9 +1,12 @@
-// YUV 4:2:0 -> RGB: the four decode entry points of include/atmvfi.h on one kernel.  yuv_common.h holds the definition and
+// YUV 4:2:0 (and planar 4:2:2 / 4:4:4) -> RGB: the five decode entry points of include/atmvfi.h on one kernel.  yuv_common.h holds the definition and
 // every helper; yuv_encode.hip is the other direction.
 //   atmvfi_yuv420_to_rgb      the whole frame -> fp32 planar [3,Hp,Wp] = q / 255 and / or uint8 [H,W,3] (RGB or BGR)
 //   atmvfi_yuv420p10_to_f32   a window of a 10-bit frame with the depth kept -> fp32 planar = q / 1023
 //   atmvfi_yuv_surface_decode a window of a decoder's surface (NV12 / NV21 / P010, planar; any pitch and chroma offset) -> either
 //                             pixel of the two calls above: the same walker, instances with interleaved chroma and / or msb samples
+//   atmvfi_yuv_sub_decode     the same call with a subsampling: planar 4:2:2 / 4:4:4 frames, instances with SUB = 1 / 2.  On the aligned
+//                             path 4:2:2 loads ONE chroma row per luma row (two per lane, no vertical mix), 4:4:4 loads U and V of a
+//                             group as it loads Y (a dword, or 8 bytes at 10 bit)
 //   atmvfi_yuv420_window      the window a dataset evaluation needs (atm-vfi_amd/evaluate.py reads the Xiph 2K / 4K clips as 10-bit Y4M this
 //                             way): the output of atmvfi_frame_u8_window on the frame atmvfi_yuv420_to_rgb would write, without that RGB
 //                             frame ever existing.  With q(Y, X) the RGB pixel 0..255 of the WHOLE frame's decode,
@@ -96,7 +99,24 @@ template <class PX, bool ALIGNED, bool LEFT>
 __device__ __forceinline__ void decode_rows(const DecArgs& a, int k, int x) {
     constexpr int TOP = PX::TOP;
     const int wx = x - a.pad_left;                      // window column of the group's first pixel; outside = padding
-    if (ALIGNED) {
+    if (ALIGNED && PX::SUB != 0) {      // 4:2:2 / 4:4:4: every luma row has its own chroma row
+        const int gx = a.x0 + clampi(wx, 0, a.w - 4);
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int y = 2 * k + r;
+            if (y >= a.Hp) break;
+            const int fy = a.y0 + clampi(y - a.pad_top, 0, a.h - 1);
+            int u[4], v[4], px[4][3];
+            if (PX::SUB == 2) {
+                sample_quad<PX>(a.yuv, a.uoff + (long long)fy * a.cs + gx, u);
+                sample_quad<PX>(a.yuv, a.voff + (long long)fy * a.cs + gx, v);
+            } else {
+                load_row<PX>(a, fy, gx >> 1, u, v);
+            }
+            decode4<PX, LEFT>(a, fy, gx, u, u, v, v, px);
+            store_group<TOP>(a, y, x, y - a.pad_top, wx, px);
+        }
+    } else if (ALIGNED) {
         const int gx = a.x0 + clampi(wx, 0, a.w - 4), q = gx >> 1;
         const int yA = 2 * k, yB = yA + 1;
         const int fyA = a.y0 + clampi(yA - a.pad_top, 0, a.h - 1), fyB = a.y0 + clampi(yB - a.pad_top, 0, a.h - 1);
@@ -227,12 +247,25 @@ __global__ __launch_bounds__(256) void yuv420_area_kernel(const AreaArgs p) {
 // even), plane stores 16 bytes, RGB groups three dwords; a group of four lies wholly inside the window or wholly in the padding
 // (without a canvas Wp is w and pad_left 0)
 // (il: interleaved chroma; msb: 10-bit samples stored in the upper bits)
-void launch_decode(const DecArgs& a, int depth, bool keep, int mode, int siting, void* stream, bool il = false, bool msb = false) {
-    const bool al = aligned4(a.yuv) && a.W % 4 == 0 && layout_aligned(a.ys, a.cs, a.uoff, a.voff, depth, il) && a.x0 % 4 == 0 && a.w % 4 == 0 &&
+// (sub: 1 4:2:2, 2 4:4:4 -- planar, LSB, mode 0)
+void launch_decode(const DecArgs& a, int depth, bool keep, int mode, int siting, void* stream, bool il = false, bool msb = false, int sub = 0) {
+    const bool al = aligned4(a.yuv) && a.W % 4 == 0 && layout_aligned(a.ys, a.cs, a.uoff, a.voff, depth, il, sub) && a.x0 % 4 == 0 && a.w % 4 == 0 &&
                     (!a.dst || canvas_aligned(a.dst, a.Wp, a.pad_left)) && (!a.dst_u8 || aligned4(a.dst_u8));
     const dim3 grid = yuv_grid((long long)a.rows * a.groups), block(256);
     const hipStream_t st = (hipStream_t)stream;
-    if (il || msb) {        // the instances of atmvfi_yuv_surface_decode that the planar, LSB calls do not have (mode 0 only)
+    if (sub) {              // the instances of atmvfi_yuv_sub_decode: three pixel kinds x two paths x (4:2:2 x two sitings + 4:4:4)
+        dispatch(al, sub == 1 && siting, sub == 2, [&](auto AL, auto LEFT, auto S444) {
+            constexpr int SUB = decltype(S444)::value ? 2 : 1;
+            auto go = [&](auto px) {
+                hipLaunchKernelGGL((yuv420_crop_kernel<decltype(px), decltype(AL)::value, decltype(LEFT)::value>), grid, block, 0, st, a);
+            };
+            if constexpr (!(SUB == 2 && decltype(LEFT)::value)) {
+                if (keep) go(Pixel<10, 1023, false, false, SUB>{});
+                else if (depth == 10) go(Pixel<10, 255, false, false, SUB>{});
+                else go(Pixel<8, 255, false, false, SUB>{});
+            }
+        });
+    } else if (il || msb) {        // the instances of atmvfi_yuv_surface_decode that the planar, LSB calls do not have (mode 0 only)
         dispatch(al, siting, [&](auto AL, auto LEFT) {
             dispatch(il, msb, [&](auto IL_, auto MSB_) {
                 constexpr bool IL = decltype(IL_)::value, M = decltype(MSB_)::value;
@@ -336,23 +369,26 @@ extern "C" int atmvfi_yuv420_window(const void* yuv, int H, int W, int depth, in
     return atmvfi::check_launch(me);
 }
 
-extern "C" int atmvfi_yuv_surface_decode(const void* yuv, int H, int W, int depth, int matrix, int full_range, int siting, int chroma, int msb,
-                                         int64_t pitch, int64_t chroma_pitch, int64_t chroma_offset, int keep_depth, int y0, int x0, int h, int w,
-                                         void* dst_u8, int bgr, float* dst, int Hp, int Wp, int pad_top, int pad_left, void* stream) {
-    const char* me = "yuv_surface_decode";
-    ATMVFI_REQUIRE(yuv, ATMVFI_EINVAL, "yuv_surface_decode: null source");
-    ATMVFI_REQUIRE(dst || dst_u8, ATMVFI_EINVAL, "yuv_surface_decode: both outputs are null (give dst, dst_u8 or both)");
+namespace {
+
+// atmvfi_yuv_surface_decode (sub 0) and atmvfi_yuv_sub_decode (sub 1 / 2, checked by the caller: planar, LSB) under the name `me`
+int surface_decode(const char* me, int sub, const void* yuv, int H, int W, int depth, int matrix, int full_range, int siting, int chroma, int msb,
+                   int64_t pitch, int64_t chroma_pitch, int64_t chroma_offset, int keep_depth, int y0, int x0, int h, int w, void* dst_u8, int bgr,
+                   float* dst, int Hp, int Wp, int pad_top, int pad_left, void* stream) {
+    ATMVFI_REQUIRE(yuv, ATMVFI_EINVAL, "%s: null source", me);
+    ATMVFI_REQUIRE(dst || dst_u8, ATMVFI_EINVAL, "%s: both outputs are null (give dst, dst_u8 or both)", me);
     if (const int rc = check_format(me, H, W, matrix, full_range, siting)) return rc;
     if (const int rc = check_depth(me, depth, full_range)) return rc;
     Layout l;
-    if (const int rc = check_surface(me, H, W, depth, chroma, msb, pitch, chroma_pitch, chroma_offset, &l)) return rc;
-    ATMVFI_REQUIRE(keep_depth == 0 || keep_depth == 1, ATMVFI_EINVAL, "yuv_surface_decode: keep_depth must be 0 or 1 (got %d)", keep_depth);
-    ATMVFI_REQUIRE(!(keep_depth && depth != 10), ATMVFI_EINVAL, "yuv_surface_decode: keep_depth needs a 10-bit surface");
-    ATMVFI_REQUIRE(!(keep_depth && dst_u8), ATMVFI_EINVAL, "yuv_surface_decode: dst_u8 holds 8-bit pixels: not with keep_depth");
-    ATMVFI_REQUIRE(h >= 1 && w >= 1, ATMVFI_EINVAL, "yuv_surface_decode: the window's h and w must be at least 1 (got %d x %d)", h, w);
+    if (const int rc = check_surface(me, H, W, depth, chroma, msb, pitch, chroma_pitch, chroma_offset, &l, sub)) return rc;
+    ATMVFI_REQUIRE(keep_depth == 0 || keep_depth == 1, ATMVFI_EINVAL, "%s: keep_depth must be 0 or 1 (got %d)", me, keep_depth);
+    ATMVFI_REQUIRE(!(keep_depth && depth != 10), ATMVFI_EINVAL, "%s: keep_depth needs a 10-bit surface", me);
+    ATMVFI_REQUIRE(!(keep_depth && dst_u8), ATMVFI_EINVAL, "%s: dst_u8 holds 8-bit pixels: not with keep_depth", me);
+    ATMVFI_REQUIRE(h >= 1 && w >= 1, ATMVFI_EINVAL, "%s: the window's h and w must be at least 1 (got %d x %d)", me, h, w);
     ATMVFI_REQUIRE(y0 >= 0 && x0 >= 0 && (long long)y0 + h <= H && (long long)x0 + w <= W, ATMVFI_EINVAL,
-                   "yuv_surface_decode: window %d x %d at (%d, %d) outside the %d x %d frame", h, w, y0, x0, H, W);
-    ATMVFI_REQUIRE(y0 % 2 == 0 && x0 % 2 == 0, ATMVFI_EINVAL, "yuv_surface_decode: the window origin (%d, %d) must be even", y0, x0);
+                   "%s: window %d x %d at (%d, %d) outside the %d x %d frame", me, h, w, y0, x0, H, W);
+    if (sub == 0) ATMVFI_REQUIRE(y0 % 2 == 0 && x0 % 2 == 0, ATMVFI_EINVAL, "%s: the window origin (%d, %d) must be even", me, y0, x0);
+    if (sub == 1) ATMVFI_REQUIRE(x0 % 2 == 0, ATMVFI_EINVAL, "%s: the window origin (%d, %d) must have an even x0 for 4:2:2 frames", me, y0, x0);
     if (dst) {
         if (const int rc = check_canvas(me, "dst", "window", dst, h, w, Hp, Wp, pad_top, pad_left)) return rc;
     } else {        // no canvas: the output geometry is the window's
@@ -362,8 +398,28 @@ extern "C" int atmvfi_yuv_surface_decode(const void* yuv, int H, int W, int dept
     }
     const int groups = groups_of(Wp), pairs = pairs_of(Hp);
     if (const int rc = check_items(me, pairs, groups, "output of", Hp, Wp)) return rc;
-    const DecArgs a = {make_src(yuv, H, W, depth, matrix, full_range, keep_depth != 0, l), y0, x0, h, w, dst, Hp, Wp, pad_top, pad_left,
+    const DecArgs a = {make_src(yuv, H, W, depth, matrix, full_range, keep_depth != 0, l, sub), y0, x0, h, w, dst, Hp, Wp, pad_top, pad_left,
                        (unsigned char*)dst_u8, bgr ? 1 : 0, groups, pairs};
-    launch_decode(a, depth, keep_depth != 0, 0, siting, stream, chroma != 0, msb != 0);
+    launch_decode(a, depth, keep_depth != 0, 0, siting, stream, chroma != 0, msb != 0, sub);
     return atmvfi::check_launch(me);
+}
+
+}  // namespace
+
+extern "C" int atmvfi_yuv_surface_decode(const void* yuv, int H, int W, int depth, int matrix, int full_range, int siting, int chroma, int msb,
+                                         int64_t pitch, int64_t chroma_pitch, int64_t chroma_offset, int keep_depth, int y0, int x0, int h, int w,
+                                         void* dst_u8, int bgr, float* dst, int Hp, int Wp, int pad_top, int pad_left, void* stream) {
+    return surface_decode("yuv_surface_decode", 0, yuv, H, W, depth, matrix, full_range, siting, chroma, msb, pitch, chroma_pitch, chroma_offset,
+                          keep_depth, y0, x0, h, w, dst_u8, bgr, dst, Hp, Wp, pad_top, pad_left, stream);
+}
+
+extern "C" int atmvfi_yuv_sub_decode(const void* yuv, int H, int W, int depth, int matrix, int full_range, int siting, int subsampling, int chroma,
+                                     int msb, int64_t pitch, int64_t chroma_pitch, int64_t chroma_offset, int keep_depth, int y0, int x0, int h,
+                                     int w, void* dst_u8, int bgr, float* dst, int Hp, int Wp, int pad_top, int pad_left, void* stream) {
+    if (subsampling == 0)       // the surface call itself: the same instance, the same bytes
+        return atmvfi_yuv_surface_decode(yuv, H, W, depth, matrix, full_range, siting, chroma, msb, pitch, chroma_pitch, chroma_offset, keep_depth, y0,
+                                         x0, h, w, dst_u8, bgr, dst, Hp, Wp, pad_top, pad_left, stream);
+    if (const int rc = check_sub("yuv_sub_decode", subsampling, siting, chroma, msb)) return rc;
+    return surface_decode("yuv_sub_decode", subsampling, yuv, H, W, depth, matrix, full_range, siting, chroma, msb, pitch, chroma_pitch,
+                          chroma_offset, keep_depth, y0, x0, h, w, dst_u8, bgr, dst, Hp, Wp, pad_top, pad_left, stream);
 }

@@ -29,6 +29,12 @@
 //             swapped); interleaved and msb are properties of the instance (Pixel), as the siting is.  The arithmetic above is applied
 //             to the samples found there, unchanged.  A decoder's surface that already lies in device memory is decoded in place: its
 //             pointer, pitch and chroma offset go to atmvfi_yuv_surface_decode, no padding byte is read and nothing is repacked.
+//   4:2:2 / 4:4:4   (atmvfi_yuv_sub_decode / atmvfi_yuv_sub_encode; yuv.py: Format.subsampling; model tests/cpu_yuv_sub.py) planar frames
+//             whose chroma planes are [H, cw] (4:2:2) or [H, W] (4:4:4): SUB, one more property of the instance.  Decode 4:2:2: row y, the
+//             columns and weights above, c' = (wx0 c[y][q0] + wx1 c[y][q1] + 2) >> 2; 4:4:4: c' = c[y][x].  Encode: the horizontal
+//             taps above over ONE row (4:2:2: sh = 1 centre, 2 left) or the pixel itself (4:4:4: sh = 0).  The same coefficients,
+//             offsets and clips; a 4:2:2 frame of equal chroma rows decodes as the 4:2:0 frame of those rows ((4 h + 8) >> 4 is
+//             (h + 2) >> 2), and a picture of equal row pairs encodes to the 4:2:0 chroma ((2 s + 2^(k+1)) >> (k+1) is (s + 2^k) >> k).
 // Library-wide rules, here as everywhere: vector stores only, no atomics, nothing pre-zeroed: every output byte is written by exactly
 // one lane.
 #pragma once
@@ -83,11 +89,13 @@ struct YuvSrc {
 // the pixel kind of a decode instance: the frame's sample depth, the RGB pixel's maximum and how the samples lie in memory.  A template
 // parameter, not a member of YuvSrc: with a constant maximum the clip is one v_med3_i32, and the decodes are bound by their
 // instruction count.  IL: chroma is one plane of interleaved pairs (NV12 / NV21 / P010) instead of two planes; MSB: a 10-bit sample is
-// stored as value << 6 (P010) and read as s >> 6.  The planar, LSB instances compile to what they were without either.
-template <int DEPTH_, int TOP_, bool IL_ = false, bool MSB_ = false>
+// stored as value << 6 (P010) and read as s >> 6.  The planar, LSB instances compile to what they were without either.  SUB: the
+// chroma subsampling, 0 4:2:0, 1 4:2:2, 2 4:4:4 (planar, LSB only); the 4:2:0 instances compile to what they were without it.
+template <int DEPTH_, int TOP_, bool IL_ = false, bool MSB_ = false, int SUB_ = 0>
 struct Pixel {
-    static constexpr int DEPTH = DEPTH_, TOP = TOP_;
+    static constexpr int DEPTH = DEPTH_, TOP = TOP_, SUB = SUB_;
     static constexpr bool IL = IL_, MSB = MSB_;
+    static_assert(SUB == 0 || (SUB <= 2 && !IL && !MSB), "4:2:2 and 4:4:4 frames are planar with LSB samples");
     static_assert((DEPTH == 8 || DEPTH == 10) && (TOP == 255 || (TOP == 1023 && DEPTH == 10)), "8 bit, 10 -> 8 bit or 10 bit kept");
     static_assert(!MSB || DEPTH == 10, "only 10-bit samples are stored in the upper bits");
 };
@@ -102,14 +110,16 @@ struct Layout {
     int ys, cs;
     long long uoff;
 };
-inline Layout tight_layout(int H, int W, int chroma) {
-    const int cw = (W + 1) / 2;
+inline int chroma_rows(int H, int sub) { return sub == 0 ? (H + 1) / 2 : H; }
+inline int chroma_cols(int W, int sub) { return sub == 2 ? W : (W + 1) / 2; }
+inline Layout tight_layout(int H, int W, int chroma, int sub = 0) {
+    const int cw = chroma_cols(W, sub);
     return Layout{chroma, W, chroma ? 2 * cw : cw, (long long)H * W};
 }
 
 // keep: the 10-bit depth kept (RGB 0..1023); otherwise RGB 0..255 from samples of either depth
-inline YuvSrc make_src(const void* yuv, int H, int W, int depth, int matrix, int full_range, bool keep, const Layout& l) {
-    const int ch = (H + 1) / 2, cw = (W + 1) / 2;
+inline YuvSrc make_src(const void* yuv, int H, int W, int depth, int matrix, int full_range, bool keep, const Layout& l, int sub = 0) {
+    const int ch = chroma_rows(H, sub), cw = chroma_cols(W, sub);
     const Coeffs& c = keep ? kCoeffs10[matrix] : kCoeffs[matrix][full_range];
     const long long uoff = l.uoff + (l.chroma == 2 ? 1 : 0), voff = l.chroma == 0 ? l.uoff + (long long)ch * l.cs : l.uoff + (l.chroma == 1 ? 1 : 0);
     return YuvSrc{(const unsigned char*)yuv, H, W, ch, cw, uoff, voff, l.ys, l.cs, l.chroma == 2 ? 1 : 0,
@@ -144,6 +154,22 @@ __device__ __forceinline__ void sample_pair(const unsigned char* p, long long i,
         const unsigned v = *reinterpret_cast<const unsigned*>(p + 2 * i);
         s0 = lo16<PX::MSB>(v);
         s1 = hi16<PX::MSB>(v);
+    }
+}
+
+// the naturally aligned group of samples (i .. i + 3) of the aligned paths: one dword or one 8-byte load
+template <class PX>
+__device__ __forceinline__ void sample_quad(const unsigned char* p, long long i, int s[4]) {
+    if (PX::DEPTH == 8) {
+        const unsigned d = *reinterpret_cast<const unsigned*>(p + i);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) s[k] = (int)((d >> (8 * k)) & 0xffu);
+    } else {
+        const U32x2 d = *reinterpret_cast<const U32x2*>(p + 2 * i);
+        s[0] = lo16<PX::MSB>(d.a);
+        s[1] = hi16<PX::MSB>(d.a);
+        s[2] = lo16<PX::MSB>(d.b);
+        s[3] = hi16<PX::MSB>(d.b);
     }
 }
 
@@ -225,9 +251,27 @@ __device__ __forceinline__ void to_rgb(const YuvSrc& a, int Y, int U, int V, int
     q[2] = clampi((y + __mul24(a.kBU, u) + half) >> a.T, 0, TOP);
 }
 
+// 4:2:2: the horizontal filter alone
+__device__ __forceinline__ int chroma_mix_row(int c0, int c1, int wx0, int wx1) { return (wx0 * c0 + wx1 * c1 + 2) >> 2; }
+
 // one frame pixel, every sample loaded on its own (the general path)
 template <class PX, bool LEFT>
 __device__ __forceinline__ void decode_pixel(const YuvSrc& a, int fy, int fx, int q[3]) {
+    if constexpr (PX::SUB == 2) {               // 4:4:4: the pixel's own samples
+        const long long i = (long long)fy * a.cs + fx;
+        to_rgb<PX::TOP>(a, sample<PX, false>(a.yuv, (long long)fy * a.ys + fx), sample<PX, false>(a.yuv, a.uoff + i),
+                        sample<PX, false>(a.yuv, a.voff + i), q);
+        return;
+    } else if constexpr (PX::SUB == 1) {        // 4:2:2: chroma row fy, the columns and weights of 4:2:0
+        const int q0 = fx >> 1;
+        const int q1 = LEFT ? min(q0 + 1, a.cw - 1) : clampi(q0 + ((fx & 1) ? 1 : -1), 0, a.cw - 1);
+        const int wx0 = LEFT ? ((fx & 1) ? 2 : 4) : 3, wx1 = 4 - wx0;
+        const long long i0 = (long long)fy * a.cs + q0, i1 = (long long)fy * a.cs + q1;
+        const int U = chroma_mix_row(sample<PX, false>(a.yuv, a.uoff + i0), sample<PX, false>(a.yuv, a.uoff + i1), wx0, wx1);
+        const int V = chroma_mix_row(sample<PX, false>(a.yuv, a.voff + i0), sample<PX, false>(a.yuv, a.voff + i1), wx0, wx1);
+        to_rgb<PX::TOP>(a, sample<PX, false>(a.yuv, (long long)fy * a.ys + fx), U, V, q);
+        return;
+    }
     constexpr int E = PX::IL ? 2 : 1;           // samples from one chroma column to the next
     const int r0 = fy >> 1, r1 = clampi(r0 + ((fy & 1) ? 1 : -1), 0, a.ch - 1);
     const int q0 = fx >> 1;
@@ -243,29 +287,29 @@ __device__ __forceinline__ void decode_pixel(const YuvSrc& a, int fy, int fx, in
 }
 
 // four frame pixels of row fy, columns gx .. gx + 3 (gx even, the row's Y group readable as dwords) from the chroma segments of rows
-// r0 / r1, seg[k] = column clamp((gx >> 1) - 1 + k) (the aligned paths)
+// r0 / r1, seg[k] = column clamp((gx >> 1) - 1 + k) (the aligned paths).  4:2:2: u0 / v0 are the segments of chroma row fy (u1 / v1
+// are not read); 4:4:4: u0 / v0 are the four samples of columns gx .. gx + 3 themselves
 template <class PX, bool LEFT>
 __device__ __forceinline__ void decode4(const YuvSrc& a, int fy, int gx, const int u0[4], const int u1[4], const int v0[4], const int v1[4],
                                         int q[4][3]) {
     int Y[4];
-    if (PX::DEPTH == 8) {
-        const unsigned d = *reinterpret_cast<const unsigned*>(a.yuv + (long long)fy * a.ys + gx);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) Y[i] = (int)((d >> (8 * i)) & 0xffu);
-    } else {
-        const U32x2 d = *reinterpret_cast<const U32x2*>(a.yuv + 2 * ((long long)fy * a.ys + gx));
-        Y[0] = lo16<PX::MSB>(d.a);
-        Y[1] = hi16<PX::MSB>(d.a);
-        Y[2] = lo16<PX::MSB>(d.b);
-        Y[3] = hi16<PX::MSB>(d.b);
-    }
+    sample_quad<PX>(a.yuv, (long long)fy * a.ys + gx, Y);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int k0 = 1 + (i >> 1);
         const int k1 = LEFT ? k0 + 1 : k0 + ((i & 1) ? 1 : -1);        // (indices and weights are compile-time constants)
         const int wx0 = LEFT ? ((i & 1) ? 2 : 4) : 3, wx1 = 4 - wx0;
-        const int U = chroma_mix(u0[k0], u0[k1], u1[k0], u1[k1], wx0, wx1);
-        const int V = chroma_mix(v0[k0], v0[k1], v1[k0], v1[k1], wx0, wx1);
+        int U, V;
+        if constexpr (PX::SUB == 2) {
+            U = u0[i];
+            V = v0[i];
+        } else if constexpr (PX::SUB == 1) {
+            U = chroma_mix_row(u0[k0], u0[k1], wx0, wx1);
+            V = chroma_mix_row(v0[k0], v0[k1], wx0, wx1);
+        } else {
+            U = chroma_mix(u0[k0], u0[k1], u1[k0], u1[k1], wx0, wx1);
+            V = chroma_mix(v0[k0], v0[k1], v1[k0], v1[k1], wx0, wx1);
+        }
         if (PX::IL) to_rgb<PX::TOP>(a, Y[i], a.vu ? V : U, a.vu ? U : V, q[i]);        // (load_row: first / second of a pair)
         else to_rgb<PX::TOP>(a, Y[i], U, V, q[i]);
     }
@@ -290,12 +334,12 @@ int check_depth(const char* what, int depth, int full_range) {
 // a surface: depth, layout and strides in BYTES as the caller gives them -> the layout in samples.  pitch / chroma_pitch / chroma_offset
 // 0: tight.  (yuv.Surface holds the same rules.)
 int check_surface(const char* what, int H, int W, int depth, int chroma, int msb, long long pitch, long long chroma_pitch, long long chroma_offset,
-                  Layout* out) {
+                  Layout* out, int sub = 0) {
     ATMVFI_REQUIRE(chroma >= 0 && chroma <= 2, ATMVFI_EINVAL, "%s: unknown chroma layout %d (0: planar, 1: interleaved uv, 2: interleaved vu)",
                    what, chroma);
     ATMVFI_REQUIRE(msb == 0 || msb == 1, ATMVFI_EINVAL, "%s: msb must be 0 or 1 (got %d)", what, msb);
     ATMVFI_REQUIRE(!(msb && depth != 10), ATMVFI_EINVAL, "%s: msb needs depth 10 (8-bit samples fill their byte)", what);
-    const long long b = depth == 10 ? 2 : 1, cw = ((long long)W + 1) / 2, crow = (chroma ? 2 * cw : cw) * b;
+    const long long b = depth == 10 ? 2 : 1, cw = chroma_cols(W, sub), crow = (chroma ? 2 * cw : cw) * b;
     if (pitch == 0) pitch = W * b;
     if (chroma_pitch == 0) chroma_pitch = crow;
     if (chroma_offset == 0) chroma_offset = pitch * H;
@@ -308,6 +352,15 @@ int check_surface(const char* what, int H, int W, int depth, int chroma, int msb
                    "%s: chroma_offset %lld must be a multiple of the sample size %lld and at least pitch * H = %lld", what, chroma_offset, b,
                    pitch * H);
     *out = Layout{chroma, (int)(pitch / b), (int)(chroma_pitch / b), chroma_offset / b};
+    return ATMVFI_OK;
+}
+
+// 4:2:2 / 4:4:4 (atmvfi_yuv_sub_*): planar LSB frames only, no siting at 4:4:4
+int check_sub(const char* what, int subsampling, int siting, int chroma, int msb) {
+    ATMVFI_REQUIRE(subsampling >= 0 && subsampling <= 2, ATMVFI_EINVAL, "%s: unknown subsampling %d (0: 4:2:0, 1: 4:2:2, 2: 4:4:4)", what, subsampling);
+    ATMVFI_REQUIRE(subsampling == 0 || (chroma == 0 && msb == 0), ATMVFI_EINVAL,
+                   "%s: 4:2:2 and 4:4:4 frames are planar with LSB samples (got chroma %d, msb %d with subsampling %d)", what, chroma, msb, subsampling);
+    ATMVFI_REQUIRE(!(subsampling == 2 && siting != 0), ATMVFI_EINVAL, "%s: siting %d has no meaning for 4:4:4 (subsampling 2): give 0", what, siting);
     return ATMVFI_OK;
 }
 
@@ -328,10 +381,11 @@ int check_items(const char* what, long long rows, long long groups, const char* 
 
 // the frame side of the aligned paths (with a 4-byte aligned pointer and W % 4 == 0): Y groups are dwords / 8-byte words of their row,
 // planar chroma pairs naturally aligned (2 or 4 bytes), interleaved chroma pair-of-pairs 4-byte aligned.  A packed I420 frame with
-// W % 4 == 0 always passes.
-inline bool layout_aligned(int ys, int cs, long long uoff, long long voff, int depth, bool il) {
+// W % 4 == 0 always passes.  4:4:4 (sub 2): chroma groups are loaded as Y groups are, so chroma rows are dword-aligned like luma rows.
+inline bool layout_aligned(int ys, int cs, long long uoff, long long voff, int depth, bool il, int sub = 0) {
     const int b = depth == 10 ? 2 : 1;
     if ((ys * (long long)b) % 4) return false;
+    if (sub == 2) return (uoff * b) % 4 == 0 && (voff * b) % 4 == 0 && (cs * (long long)b) % 4 == 0;
     if (il) return ((uoff < voff ? uoff : voff) * b) % 4 == 0 && (cs * (long long)b) % 4 == 0;
     return uoff % 2 == 0 && voff % 2 == 0 && cs % 2 == 0;
 }

@@ -1,9 +1,12 @@
-// RGB -> YUV 4:2:0: the three encode entry points of include/atmvfi.h on one kernel.  yuv_common.h holds the definition and
+// RGB -> YUV 4:2:0 (and planar 4:2:2 / 4:4:4): the four encode entry points of include/atmvfi.h on one kernel.  yuv_common.h holds the definition and
 // the shared helpers; yuv.hip is the other direction.
 //   atmvfi_rgb_to_yuv420      uint8 [H,W,3] (RGB or BGR) or the fp32 canvas in units of 1 / 255 -> 8-bit samples
 //   atmvfi_f32_to_yuv420p10   the fp32 canvas in units of 1 / 1023 -> 10-bit samples, the depth kept
 //   atmvfi_yuv_surface_encode either of the two into a tight surface: planar, or NV12 / NV21 / P010 (interleaved chroma, msb samples);
 //                             a lane's two chroma samples of both planes leave as ONE dword (8 bit) or 8-byte (10 bit) store
+//   atmvfi_yuv_sub_encode     the same call with a subsampling: planar 4:2:2 / 4:4:4 frames (SUB = 1 / 2).  The lane's 4 x 2 block makes
+//                             a chroma pair per plane and ROW (4:2:2: a 2-byte or dword store) or a chroma group per plane and row
+//                             (4:4:4: a dword or 8-byte store, as the Y group)
 //
 // Bandwidth-bound: from fp32 12 B/px in and 1.5 or 3 out.  A lane owns a 4 x 2 luma block of the frame: two Y groups and two chroma
 // samples per plane; left siting reads one more pixel column.
@@ -110,12 +113,14 @@ __device__ __forceinline__ void store_samples(unsigned char* yuv, long long i, c
 }
 
 // IL: chroma is one plane of interleaved pairs; MSB: a 10-bit sample is stored as value << 6 (the low bits zero).  The planar, LSB
-// instances compile to what they were without either.
-template <int SRC, bool ALIGNED, bool LEFT, bool IL = false, bool MSB = false>
+// instances compile to what they were without either.  SUB: 0 4:2:0, 1 4:2:2, 2 4:4:4 (planar, LSB): a.ch is H then, and the lane
+// still owns luma rows 2j and 2j + 1.
+template <int SRC, bool ALIGNED, bool LEFT, bool IL = false, bool MSB = false, int SUB = 0>
 __global__ __launch_bounds__(256) void yuv420_encode_kernel(const EncArgs a) {
     constexpr int DEPTH = SRC == SRC_F1023 ? 10 : 8, TOP = SRC == SRC_F1023 ? 1023 : 255, MID = (TOP + 1) / 2, SH = MSB ? 6 : 0;
     static_assert(!MSB || DEPTH == 10, "only 10-bit samples are stored in the upper bits");
-    const int total = a.ch * a.groups;
+    static_assert(SUB == 0 || (SUB <= 2 && !IL && !MSB && !(SUB == 2 && LEFT)), "4:2:2 and 4:4:4 frames are planar with LSB samples");
+    const int total = (SUB == 0 ? a.ch : (a.H + 1) >> 1) * a.groups;
     for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
         const int j = idx / a.groups, g = idx - j * a.groups, x = 4 * g;
         int px[2][5][3];        // [row][0: the column left of the group (left siting only), 1..4: the group][R, G, B]
@@ -140,6 +145,44 @@ __global__ __launch_bounds__(256) void yuv420_encode_kernel(const EncArgs a) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) Y[i] = clampi(((dot3(a.eY, px[r][1 + i]) + (1 << 13)) >> 14) + a.yo, 0, TOP) << SH;
             store_samples<DEPTH, ALIGNED, 4>(a.yuv, (long long)y * a.ys + x, Y, a.W - x);
+        }
+        if constexpr (SUB == 2) {       // 4:4:4: a chroma sample per pixel, from the pixel itself (sh = 0)
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                const int y = 2 * j + r;
+                if (y >= a.H) break;
+                int U[4], V[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    U[i] = clampi(((dot3(a.eU, px[r][1 + i]) + (1 << 13)) >> 14) + MID, 0, TOP);
+                    V[i] = clampi(((dot3(a.eV, px[r][1 + i]) + (1 << 13)) >> 14) + MID, 0, TOP);
+                }
+                const long long c0 = (long long)y * a.cs + x;
+                store_samples<DEPTH, ALIGNED, 4>(a.yuv, a.uoff + c0, U, a.W - x);
+                store_samples<DEPTH, ALIGNED, 4>(a.yuv, a.voff + c0, V, a.W - x);
+            }
+            continue;
+        } else if constexpr (SUB == 1) {        // 4:2:2: chroma columns 2g and 2g + 1 of BOTH rows, the horizontal taps alone
+            constexpr int sh1 = LEFT ? 2 : 1;
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                const int y = 2 * j + r;
+                if (y >= a.H) break;
+                int U[2], V[2];
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    int s[3];
+#pragma unroll
+                    for (int c = 0; c < 3; ++c)
+                        s[c] = LEFT ? px[r][2 * i][c] + 2 * px[r][1 + 2 * i][c] + px[r][2 + 2 * i][c] : px[r][1 + 2 * i][c] + px[r][2 + 2 * i][c];
+                    U[i] = clampi(((dot3(a.eU, s) + (1 << (13 + sh1))) >> (14 + sh1)) + MID, 0, TOP);
+                    V[i] = clampi(((dot3(a.eV, s) + (1 << (13 + sh1))) >> (14 + sh1)) + MID, 0, TOP);
+                }
+                const long long c0 = (long long)y * a.cs + 2 * g;      // (aligned: cw is even, both columns exist)
+                store_samples<DEPTH, ALIGNED, 2>(a.yuv, a.uoff + c0, U, a.cw - 2 * g);
+                store_samples<DEPTH, ALIGNED, 2>(a.yuv, a.voff + c0, V, a.cw - 2 * g);
+            }
+            continue;
         }
         // chroma columns 2g and 2g + 1
         constexpr int sh = LEFT ? 3 : 2;
@@ -171,10 +214,11 @@ __global__ __launch_bounds__(256) void yuv420_encode_kernel(const EncArgs a) {
 
 // Launches the encode of a checked frame; exactly one of src_u8 and src is given.  The destination is tight: chroma 0 is the packed
 // I420 frame, 1 / 2 the interleaved surface (U / V first); msb: 10-bit samples stored in the upper bits
+// (sub: 1 4:2:2, 2 4:4:4 -- planar, LSB)
 template <int SRC>
 void launch_encode(const Coeffs& c, int yo, const void* src_u8, int bgr, const float* src, int Hp, int Wp, int pad_top, int pad_left, int H,
-                   int W, int siting, void* yuv, void* stream, int chroma = 0, bool msb = false) {
-    const int ch = (H + 1) / 2, cw = (W + 1) / 2, groups = groups_of(W);
+                   int W, int siting, void* yuv, void* stream, int chroma = 0, bool msb = false, int sub = 0) {
+    const int ch = chroma_rows(H, sub), cw = chroma_cols(W, sub), groups = groups_of(W);
     EncArgs a = {(const unsigned char*)src_u8, bgr ? 1 : 0, src, Hp, Wp, pad_top, pad_left, H, W, ch, cw};
     for (int k = 0; k < 3; ++k) {
         a.eY[k] = c.enc[0][k];
@@ -183,7 +227,7 @@ void launch_encode(const Coeffs& c, int yo, const void* src_u8, int bgr, const f
     }
     a.yo = yo;
     a.yuv = (unsigned char*)yuv;
-    const Layout l = tight_layout(H, W, chroma);
+    const Layout l = tight_layout(H, W, chroma, sub);
     a.uoff = l.uoff + (chroma == 2 ? 1 : 0);
     a.voff = chroma == 0 ? l.uoff + (long long)ch * cw : l.uoff + (chroma == 1 ? 1 : 0);
     a.ys = l.ys;
@@ -191,7 +235,16 @@ void launch_encode(const Coeffs& c, int yo, const void* src_u8, int bgr, const f
     a.vu = chroma == 2 ? 1 : 0;
     a.groups = groups;
     const bool al = aligned4(yuv) && W % 4 == 0 && (src ? canvas_aligned(src, Wp, pad_left) : aligned4(src_u8));      // (tight: the layout follows)
-    const dim3 grid = yuv_grid((long long)ch * groups), block(256);
+    const dim3 grid = yuv_grid((long long)pairs_of(H) * groups), block(256);
+    if (sub) {              // the instances of atmvfi_yuv_sub_encode: three sources x two paths x (4:2:2 x two sitings + 4:4:4)
+        dispatch(al, sub == 1 && siting, sub == 2, [&](auto AL, auto LEFT, auto S444) {
+            constexpr int SUB = decltype(S444)::value ? 2 : 1;
+            if constexpr (!(SUB == 2 && decltype(LEFT)::value))
+                hipLaunchKernelGGL((yuv420_encode_kernel<SRC, decltype(AL)::value, decltype(LEFT)::value, false, false, SUB>), grid, block, 0,
+                                   (hipStream_t)stream, a);
+        });
+        return;
+    }
     if (chroma || msb) {        // the instances of atmvfi_yuv_surface_encode that the planar, LSB calls do not have
         dispatch(al, siting, [&](auto AL, auto LEFT) {
             dispatch(chroma != 0, msb, [&](auto IL_, auto MSB_) {
@@ -239,27 +292,48 @@ extern "C" int atmvfi_f32_to_yuv420p10(const float* src, int Hp, int Wp, int pad
     return atmvfi::check_launch(me);
 }
 
-extern "C" int atmvfi_yuv_surface_encode(const void* src_u8, int bgr, const float* src, int Hp, int Wp, int pad_top, int pad_left, int H, int W,
-                                         int depth, int matrix, int full_range, int siting, int chroma, int msb, void* yuv, void* stream) {
-    const char* me = "yuv_surface_encode";
-    ATMVFI_REQUIRE(yuv, ATMVFI_EINVAL, "yuv_surface_encode: null destination");
-    ATMVFI_REQUIRE((src_u8 != nullptr) != (src != nullptr), ATMVFI_EINVAL,
-                   "yuv_surface_encode: give exactly one of src_u8 and src (got %s)", src_u8 ? "both" : "neither");
+namespace {
+
+// atmvfi_yuv_surface_encode (sub 0) and atmvfi_yuv_sub_encode (sub 1 / 2, checked by the caller: planar, LSB) under the name `me`
+int surface_encode(const char* me, int sub, const void* src_u8, int bgr, const float* src, int Hp, int Wp, int pad_top, int pad_left, int H, int W,
+                   int depth, int matrix, int full_range, int siting, int chroma, int msb, void* yuv, void* stream) {
+    ATMVFI_REQUIRE(yuv, ATMVFI_EINVAL, "%s: null destination", me);
+    ATMVFI_REQUIRE((src_u8 != nullptr) != (src != nullptr), ATMVFI_EINVAL, "%s: give exactly one of src_u8 and src (got %s)", me,
+                   src_u8 ? "both" : "neither");
     if (const int rc = check_format(me, H, W, matrix, full_range, siting)) return rc;
     if (const int rc = check_depth(me, depth, full_range)) return rc;
     Layout l;
-    if (const int rc = check_surface(me, H, W, depth, chroma, msb, 0, 0, 0, &l)) return rc;
-    ATMVFI_REQUIRE(!(depth == 10 && src_u8), ATMVFI_EINVAL, "yuv_surface_encode: a 10-bit surface is encoded from the fp32 canvas (src), not from src_u8");
+    if (const int rc = check_surface(me, H, W, depth, chroma, msb, 0, 0, 0, &l, sub)) return rc;
+    ATMVFI_REQUIRE(!(depth == 10 && src_u8), ATMVFI_EINVAL, "%s: a 10-bit surface is encoded from the fp32 canvas (src), not from src_u8", me);
     if (src)
         if (const int rc = check_canvas(me, "src", "frame", src, H, W, Hp, Wp, pad_top, pad_left)) return rc;
     if (const int rc = check_items(me, (H + 1) / 2, groups_of(W), "a frame of", H, W)) return rc;
     if (depth == 10) {
-        launch_encode<SRC_F1023>(kCoeffs10[matrix], 64, nullptr, 0, src, Hp, Wp, pad_top, pad_left, H, W, siting, yuv, stream, chroma, msb != 0);
+        launch_encode<SRC_F1023>(kCoeffs10[matrix], 64, nullptr, 0, src, Hp, Wp, pad_top, pad_left, H, W, siting, yuv, stream, chroma, msb != 0, sub);
     } else {
         const Coeffs& c = kCoeffs[matrix][full_range];
         const int yo = full_range ? 0 : 16;
-        if (src) launch_encode<SRC_F255>(c, yo, nullptr, 0, src, Hp, Wp, pad_top, pad_left, H, W, siting, yuv, stream, chroma, false);
-        else launch_encode<SRC_U8>(c, yo, src_u8, bgr, nullptr, Hp, Wp, pad_top, pad_left, H, W, siting, yuv, stream, chroma, false);
+        if (src) launch_encode<SRC_F255>(c, yo, nullptr, 0, src, Hp, Wp, pad_top, pad_left, H, W, siting, yuv, stream, chroma, false, sub);
+        else launch_encode<SRC_U8>(c, yo, src_u8, bgr, nullptr, Hp, Wp, pad_top, pad_left, H, W, siting, yuv, stream, chroma, false, sub);
     }
     return atmvfi::check_launch(me);
+}
+
+}  // namespace
+
+extern "C" int atmvfi_yuv_surface_encode(const void* src_u8, int bgr, const float* src, int Hp, int Wp, int pad_top, int pad_left, int H, int W,
+                                         int depth, int matrix, int full_range, int siting, int chroma, int msb, void* yuv, void* stream) {
+    return surface_encode("yuv_surface_encode", 0, src_u8, bgr, src, Hp, Wp, pad_top, pad_left, H, W, depth, matrix, full_range, siting, chroma, msb,
+                          yuv, stream);
+}
+
+extern "C" int atmvfi_yuv_sub_encode(const void* src_u8, int bgr, const float* src, int Hp, int Wp, int pad_top, int pad_left, int H, int W,
+                                     int depth, int matrix, int full_range, int siting, int subsampling, int chroma, int msb, void* yuv,
+                                     void* stream) {
+    if (subsampling == 0)       // the surface call itself: the same instance, the same bytes
+        return atmvfi_yuv_surface_encode(src_u8, bgr, src, Hp, Wp, pad_top, pad_left, H, W, depth, matrix, full_range, siting, chroma, msb, yuv,
+                                         stream);
+    if (const int rc = check_sub("yuv_sub_encode", subsampling, siting, chroma, msb)) return rc;
+    return surface_encode("yuv_sub_encode", subsampling, src_u8, bgr, src, Hp, Wp, pad_top, pad_left, H, W, depth, matrix, full_range, siting, chroma,
+                          msb, yuv, stream);
 }

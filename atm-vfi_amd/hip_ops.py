@@ -149,6 +149,9 @@ SIGNATURES = {
     "atmvfi_yuv_surface_decode": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_l, c_l, c_l, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_f, c_i, c_i,
                                         c_i, c_i, c_f]),
     "atmvfi_yuv_surface_encode": (c_i, [c_f, c_i, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f]),
+    "atmvfi_yuv_sub_decode": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_l, c_l, c_l, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_f, c_i, c_i,
+                                    c_i, c_i, c_f]),
+    "atmvfi_yuv_sub_encode": (c_i, [c_f, c_i, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f]),
     "atmvfi_pack_frames": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_f]),
     "atmvfi_final_residual": (c_i, [c_f, c_f, c_i, c_f, c_f, c_i, c_i, c_i, c_f]),
     "atmvfi_l1_mean": (c_i, [c_f, c_f, c_f, c_i, c_l, c_f, c_l, c_f]),
@@ -345,6 +348,13 @@ def _i420(t, fmt, what: str, kind: str = "I420"):
     if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1 or t.numel() != fmt.frame_bytes or not t.is_contiguous() \
             or not t.is_cuda:
         raise ValueError(f"{what} must be a contiguous CUDA uint8 tensor of {fmt.frame_bytes} bytes ({fmt.height} x {fmt.width} {kind})")
+
+
+def _only_420(fmt, what: str):
+    """The 4:2:0 entry points would misread the planes of a 4:2:2 / 4:4:4 frame: ``ValueError`` naming the subsampling."""
+    sub = getattr(fmt, "subsampling", "420")
+    if sub != "420":
+        raise ValueError(f"{what}: 4:2:0 frames only (got subsampling {sub}; yuv_sub_decode / yuv_sub_encode take 4:2:2 and 4:4:4)")
 
 
 _SURFACE = []
@@ -1436,6 +1446,7 @@ class HipOps:
         """One packed planar I420 frame of ``fmt`` (a ``yuv.Format``; a contiguous CUDA uint8 tensor of ``fmt.frame_bytes`` bytes, any
         alignment) -> ``dst_u8`` uint8 [H,W,3] (BGR if ``bgr``) and / or ``dst`` fp32 planar RGB [3,Hp,Wp] = q / 255 with replicate
         padding, the frame at (pad_top, pad_left) (include/atmvfi.h atmvfi_yuv420_to_rgb; the bits of ``yuv.decode_numpy``)."""
+        _only_420(fmt, "yuv420_to_rgb")
         h, w = fmt.height, fmt.width
         _i420(yuv, fmt, "yuv420_to_rgb: source")
         if dst is None and dst_u8 is None:
@@ -1455,6 +1466,7 @@ class HipOps:
         that frame's RGB decode, in one launch and without the RGB frame: ``dst`` fp32 planar [3,Hp,Wp] (q / 255, replicate padding, the
         window at (pad_top, pad_left)) and / or ``dst_u8`` uint8 [h,w,3] RGB.  The origin must be even (include/atmvfi.h
         atmvfi_yuv420_window; the bits of ``yuv.window_numpy``)."""
+        _only_420(fmt, "yuv420_window")
         fh, fw = fmt.height, fmt.width
         _i420(yuv, fmt, "yuv420_window: source")
         if dst is None and dst_u8 is None:
@@ -1477,6 +1489,7 @@ class HipOps:
         """``src_u8`` uint8 [H,W,3] (BGR if ``bgr``) or ``src`` fp32 planar RGB [3,Hp,Wp] with the frame at (pad_top, pad_left) --
         exactly one -- -> ``yuv``, a packed 8-bit I420 frame of ``fmt`` (a contiguous CUDA uint8 tensor of ``fmt.frame_bytes`` bytes;
         include/atmvfi.h atmvfi_rgb_to_yuv420).  From fp32 the pixel is ``frame_f32_to_u8``'s; the bits of ``yuv.encode_numpy``."""
+        _only_420(fmt, "rgb_to_yuv420")
         h, w = fmt.height, fmt.width
         if fmt.depth != 8:
             raise ValueError("rgb_to_yuv420: encoding is 8-bit only")
@@ -1497,6 +1510,7 @@ class HipOps:
         bytes, little-endian uint16 samples, any alignment) -> ``dst`` fp32 planar RGB [3,Hp,Wp] = q / 1023 with the depth kept:
         ``window=(y0, x0, h, w)`` of the frame (default: all of it; even origin) at (pad_top, pad_left), replicate padding
         (include/atmvfi.h atmvfi_yuv420p10_to_f32; the bits of ``yuv.decode_numpy_f32``)."""
+        _only_420(fmt, "yuv420p10_to_f32")
         h, w = fmt.height, fmt.width
         if fmt.depth != 10:
             raise ValueError("yuv420p10_to_f32: a 10-bit format expected (yuv420_to_rgb decodes 8-bit frames)")
@@ -1519,6 +1533,7 @@ class HipOps:
         ``yuv.Format`` of depth 10; a contiguous CUDA uint8 tensor of ``fmt.frame_bytes`` bytes, little-endian uint16 samples;
         include/atmvfi.h atmvfi_f32_to_yuv420p10).  The pixel is clip(rint(x * 1023), 0, 1023); the bits of ``yuv.encode_numpy`` of
         an fp32 source."""
+        _only_420(fmt, "f32_to_yuv420p10")
         h, w = fmt.height, fmt.width
         if fmt.depth != 10:
             raise ValueError("f32_to_yuv420p10: a 10-bit format expected (rgb_to_yuv420 encodes 8-bit frames)")
@@ -1540,6 +1555,7 @@ class HipOps:
         and q / 255 (include/atmvfi.h atmvfi_yuv_surface_decode; the bits of ``yuv.decode_numpy`` / ``decode_numpy_f32``)."""
         if not isinstance(surface, _surface_class()):
             raise ValueError(f"yuv_surface_decode: surface must be a yuv.Surface (got {type(surface).__name__})")
+        _only_420(surface, "yuv_surface_decode")
         h, w = surface.height, surface.width
         _surface(buf, surface, "yuv_surface_decode: buf")
         if dst is None and dst_u8 is None:
@@ -1577,6 +1593,7 @@ class HipOps:
             raise ValueError(f"yuv_surface_encode: surface must be a yuv.Surface (got {type(surface).__name__})")
         if not surface.is_tight:
             raise ValueError("yuv_surface_encode: surface must be tight (encodes write no padding: surface.tight())")
+        _only_420(surface, "yuv_surface_encode")
         h, w = surface.height, surface.width
         _surface(buf, surface, "yuv_surface_encode: buf")
         if (src is None) == (src_u8 is None):
@@ -1596,8 +1613,79 @@ class HipOps:
                   int(pad_left), h, w, int(surface.depth), surface.matrix_id, int(surface.full_range), surface.siting_id, surface.chroma_id,
                   int(surface.msb), _ptr(buf), self._stream())
 
-    # The loops' colour conversion: a yuv.Format goes to the planar entry points as ever, a yuv.Surface to the two calls above.
+    def yuv_sub_decode(self, buf, fmt_or_surface, dst_u8=None, dst=None, window=None, pad_top: int = 0, pad_left: int = 0, bgr: bool = False,
+                       keep_depth: bool = False):
+        """``yuv_surface_decode`` for a ``yuv.Format`` or planar ``yuv.Surface`` of any subsampling (4:2:2, 4:4:4; "420" is the surface
+        call itself): the window's origin is a multiple of the subsampling step per axis -- even x0 for 4:2:2, anything for 4:4:4
+        (include/atmvfi.h atmvfi_yuv_sub_decode; the bits of ``yuv.decode_numpy`` / ``decode_numpy_f32``)."""
+        from .yuv import _origin_error, as_surface
+        if not hasattr(fmt_or_surface, "subsampling_id"):
+            raise ValueError(f"yuv_sub_decode: a yuv.Format or yuv.Surface expected (got {type(fmt_or_surface).__name__})")
+        surface = as_surface(fmt_or_surface)
+        h, w = surface.height, surface.width
+        _surface(buf, surface, "yuv_sub_decode: buf")
+        if dst is None and dst_u8 is None:
+            raise ValueError("yuv_sub_decode: give dst, dst_u8 or both")
+        if keep_depth and surface.depth != 10:
+            raise ValueError("yuv_sub_decode: keep_depth needs a 10-bit surface")
+        if keep_depth and dst_u8 is not None:
+            raise ValueError("yuv_sub_decode: dst_u8 holds 8-bit pixels: not with keep_depth")
+        y0, x0, wh, ww = (0, 0, h, w) if window is None else (int(v) for v in window)
+        err = _origin_error("yuv_sub_decode", surface, y0, x0)
+        if err is not None:
+            raise err
+        if y0 < 0 or x0 < 0 or wh < 1 or ww < 1 or y0 + wh > h or x0 + ww > w:
+            raise ValueError(f"yuv_sub_decode: window {wh} x {ww} at ({y0}, {x0}) outside the {h} x {w} frame")
+        if dst is not None:
+            _f32_canvas(dst, "yuv_sub_decode: dst")
+            hp, wp = dst.shape[1], dst.shape[2]
+            if pad_top < 0 or pad_left < 0 or wh + pad_top > hp or ww + pad_left > wp:
+                raise ValueError(f"yuv_sub_decode: canvas {hp} x {wp} is smaller than the window {wh} x {ww} plus padding ({pad_top}, {pad_left})")
+        else:
+            hp, wp = wh, ww
+        if dst_u8 is not None:
+            _u8_frame(dst_u8, "yuv_sub_decode: dst_u8", (wh, ww))
+        sy, sx = surface.steps
+        meta = {"bytes": (1.0 + 2.0 / (sy * sx)) * surface.itemsize * wh * ww + (12.0 * hp * wp if dst is not None else 0.0)
+                + (3.0 * wh * ww if dst_u8 is not None else 0.0)}
+        self._run("yuv_sub_decode", meta, self.lib.atmvfi_yuv_sub_decode, _ptr(buf), h, w, int(surface.depth), surface.matrix_id,
+                  int(surface.full_range), surface.siting_id, surface.subsampling_id, surface.chroma_id, int(surface.msb), int(surface.pitch),
+                  int(surface.chroma_pitch), int(surface.chroma_offset), int(bool(keep_depth)), y0, x0, wh, ww, _ptr(dst_u8), int(bool(bgr)),
+                  _ptr(dst), hp, wp, int(pad_top), int(pad_left), self._stream())
+
+    def yuv_sub_encode(self, buf, fmt_or_surface, src_u8=None, src=None, pad_top: int = 0, pad_left: int = 0, bgr: bool = False):
+        """``yuv_surface_encode`` for a ``yuv.Format`` or tight planar ``yuv.Surface`` of any subsampling (include/atmvfi.h
+        atmvfi_yuv_sub_encode; the bits of ``yuv.encode_numpy``)."""
+        from .yuv import as_surface
+        if not hasattr(fmt_or_surface, "subsampling_id"):
+            raise ValueError(f"yuv_sub_encode: a yuv.Format or yuv.Surface expected (got {type(fmt_or_surface).__name__})")
+        surface = as_surface(fmt_or_surface)
+        if not surface.is_tight:
+            raise ValueError("yuv_sub_encode: surface must be tight (encodes write no padding: surface.tight())")
+        h, w = surface.height, surface.width
+        _surface(buf, surface, "yuv_sub_encode: buf")
+        if (src is None) == (src_u8 is None):
+            raise ValueError("yuv_sub_encode: give exactly one of src_u8 and src")
+        if src is not None:
+            _f32_canvas(src, "yuv_sub_encode: src")
+            hp, wp = src.shape[1], src.shape[2]
+            if pad_top < 0 or pad_left < 0 or h + pad_top > hp or w + pad_left > wp:
+                raise ValueError(f"yuv_sub_encode: canvas {hp} x {wp} is smaller than the frame {h} x {w} plus padding ({pad_top}, {pad_left})")
+        else:
+            if surface.depth != 8:
+                raise ValueError("yuv_sub_encode: src_u8 encodes 8-bit surfaces only (a 10-bit surface takes the fp32 src)")
+            _u8_frame(src_u8, "yuv_sub_encode: src_u8", (h, w))
+            hp, wp = h, w
+        meta = {"bytes": float(surface.nbytes) + (12.0 if src is not None else 3.0) * h * w}
+        self._run("yuv_sub_encode", meta, self.lib.atmvfi_yuv_sub_encode, _ptr(src_u8), int(bool(bgr)), _ptr(src), hp, wp, int(pad_top),
+                  int(pad_left), h, w, int(surface.depth), surface.matrix_id, int(surface.full_range), surface.siting_id, surface.subsampling_id,
+                  surface.chroma_id, int(surface.msb), _ptr(buf), self._stream())
+
+    # The loops' colour conversion: a yuv.Format goes to the planar entry points as ever, a yuv.Surface to the two surface calls, and
+    # either with a subsampling other than 4:2:0 to the two calls above.
     def yuv_decode(self, buf, fmt, dst_u8=None, dst=None, window=None, pad_top: int = 0, pad_left: int = 0, keep_depth: bool = False):
+        if getattr(fmt, "subsampling", "420") != "420":
+            return self.yuv_sub_decode(buf, fmt, dst_u8=dst_u8, dst=dst, window=window, pad_top=pad_top, pad_left=pad_left, keep_depth=keep_depth)
         if isinstance(fmt, _surface_class()):
             return self.yuv_surface_decode(buf, fmt, dst_u8=dst_u8, dst=dst, window=window, pad_top=pad_top, pad_left=pad_left, keep_depth=keep_depth)
         if keep_depth:
@@ -1607,6 +1695,8 @@ class HipOps:
         return self.yuv420_to_rgb(buf, fmt, dst_u8=dst_u8, dst=dst, pad_top=pad_top, pad_left=pad_left)
 
     def yuv_encode(self, buf, fmt, src_u8=None, src=None, pad_top: int = 0, pad_left: int = 0):
+        if getattr(fmt, "subsampling", "420") != "420":
+            return self.yuv_sub_encode(buf, fmt, src_u8=src_u8, src=src, pad_top=pad_top, pad_left=pad_left)
         if isinstance(fmt, _surface_class()):
             return self.yuv_surface_encode(buf, fmt, src_u8=src_u8, src=src, pad_top=pad_top, pad_left=pad_left)
         if fmt.depth == 10:

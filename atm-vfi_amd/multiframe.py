@@ -667,8 +667,9 @@ def interpolate_video_nx(frames, model, factor: int = 4, time_interval: int = 1,
     out_fmt = None
     if pixfmt is not None:
         from . import yuv
-        if crop is not None and (y0 % 2 or x0 % 2):
-            raise ValueError(f"interpolate_video_nx: the crop origin ({y0}, {x0}) must be even for 4:2:0 frames")
+        err = None if crop is None else yuv._origin_error("interpolate_video_nx", pixfmt, y0, x0, "crop")      # (a multiple of the subsampling step)
+        if err is not None:
+            raise err
         deep = bool(keep_depth) and pixfmt.depth == 10
         isBGR, out_fmt = False, yuv.out_format(pixfmt, deep).cropped(h, w)
         crop_rgb, whole = crop_of, (h, w) == (H, W) and yuv.passes_through(pixfmt)     # (a padded yuv.Surface: originals lose the padding)

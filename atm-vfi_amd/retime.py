@@ -443,8 +443,9 @@ def _retimed(frames, model, fi, fo, levels, dedup, crop, isBGR, divisor, tta, ma
     original, out_fmt, deep = crop_rgb, None, False
     if pixfmt is not None:
         from . import yuv
-        if crop is not None and (y0 % 2 or x0 % 2):
-            raise ValueError(f"interpolate_video_retimed: the crop origin ({y0}, {x0}) must be even for 4:2:0 frames")
+        err = None if crop is None else yuv._origin_error("interpolate_video_retimed", pixfmt, y0, x0, "crop")      # (a multiple of the subsampling step)
+        if err is not None:
+            raise err
         deep = bool(keep_depth) and pixfmt.depth == 10
         isBGR, out_fmt = False, yuv.out_format(pixfmt, deep).cropped(h, w)
         original = (lambda f: f) if (whole and yuv.passes_through(pixfmt)) else (lambda f: yuv.crop(f, pixfmt, y0, x0, h, w))

@@ -23,9 +23,18 @@ RGB clipped to 0..1023 and handed to the network as ``q / 1023`` (the fp32 divis
 pipe delivers -- NV12 / NV21 / P010 (interleaved chroma, 10-bit samples in the upper bits) and frames with a row pitch and a chroma
 offset.  It is accepted wherever a ``Format`` is (``pixfmt=``, the twins, ``crop``, ``to_8bit``); the arithmetic is the ``Format``'s,
 applied to the samples the surface describes.  ``repack`` moves frames between layouts, ``RawReader`` / ``RawWriter`` /
-``interpolate_raw`` are the headerless counterparts of the Y4M classes."""
+``interpolate_raw`` are the headerless counterparts of the Y4M classes.
+
+``Format(..., subsampling="422" | "444")`` (``atmvfi_yuv_sub_decode`` / ``atmvfi_yuv_sub_encode``): planar 4:2:2 and 4:4:4 frames, 8
+and 10 bit, with chroma planes [H, cw] and [H, W].  Decoding 4:2:2 filters along the row only (the columns and weights of 4:2:0,
+``(wx0 c0 + wx1 c1 + 2) >> 2``), 4:4:4 takes the pixel's own samples; encoding takes the same horizontal taps over one row (sh = 1
+centre, 2 left) or the pixel itself (sh = 0).  Coefficients, offsets, clips and depth rules are the 4:2:0 ones.  A window's or crop's
+origin is a multiple of the subsampling step per axis.  ``Y4MReader(..., accept=("420", "422", "444"))`` reads C422, C444, C422p10
+and C444p10 (C422* as left-sited: Y4M's 4:2:2 is co-sited), ``Y4MWriter`` writes them, ``surface_of`` knows yuv422p, yuv444p,
+yuv422p10le and yuv444p10le, and every loop takes such a format or planar surface as ``pixfmt``."""
 from __future__ import annotations
 
+import functools
 import io
 import os
 from dataclasses import dataclass, replace
@@ -36,6 +45,7 @@ import numpy as np
 
 MATRICES = ("bt601", "bt709")
 SITINGS = ("centre", "left")
+SUBSAMPLINGS = ("420", "422", "444")        # ids 0 / 1 / 2 (include/atmvfi.h)
 KR_KB = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}
 SHIFT = 14
 
@@ -79,13 +89,16 @@ COEFFS10 = {
 
 @dataclass(frozen=True)
 class Format:
-    """A packed planar I420 frame format.  ``matrix="auto"``: bt709 for ``height >= 720``, bt601 below."""
+    """A packed planar frame format: Y, U, V back to back.  ``matrix="auto"``: bt709 for ``height >= 720``, bt601 below.
+    ``subsampling``: "420" (I420: chroma ``((H + 1) // 2, (W + 1) // 2)``), "422" (``(H, (W + 1) // 2)``) or "444" (``(H, W)``, where a
+    siting has no meaning: only "centre" is accepted, so that equal formats compare equal)."""
     height: int
     width: int
     matrix: str = "auto"
     full_range: bool = False
     siting: str = "centre"
     depth: int = 8
+    subsampling: str = "420"
 
     def __post_init__(self):
         if int(self.height) < 1 or int(self.width) < 1:
@@ -101,6 +114,10 @@ class Format:
             raise ValueError(f"yuv.Format: depth must be 8 or 10 (got {self.depth!r})")
         if self.depth == 10 and self.full_range:
             raise ValueError("yuv.Format: 10-bit full range is not supported")
+        if self.subsampling not in SUBSAMPLINGS:
+            raise ValueError(f"yuv.Format: unknown subsampling {self.subsampling!r} (420, 422, 444)")
+        if self.subsampling == "444" and self.siting != "centre":
+            raise ValueError(f"yuv.Format: siting {self.siting!r} has no meaning for subsampling 444 (leave it at centre)")
         object.__setattr__(self, "height", int(self.height))
         object.__setattr__(self, "width", int(self.width))
         object.__setattr__(self, "matrix", m)
@@ -108,7 +125,17 @@ class Format:
 
     @property
     def chroma_shape(self) -> Tuple[int, int]:
-        return (self.height + 1) // 2, (self.width + 1) // 2
+        sy, sx = self.steps
+        return (self.height + sy - 1) // sy, (self.width + sx - 1) // sx
+
+    @property
+    def steps(self) -> Tuple[int, int]:
+        """Luma rows and columns per chroma sample: what a window's or a crop's origin must be a multiple of."""
+        return {"420": (2, 2), "422": (1, 2), "444": (1, 1)}[self.subsampling]
+
+    @property
+    def subsampling_id(self) -> int:
+        return SUBSAMPLINGS.index(self.subsampling)
 
     @property
     def frame_samples(self) -> int:
@@ -135,7 +162,7 @@ class Format:
         """``buf`` as the 1-D sample array of one frame of this format (a view), or ``ValueError``."""
         a = np.asarray(buf)
         if a.dtype != self.dtype or a.size != self.frame_samples or not a.flags.c_contiguous:
-            raise ValueError(f"{what}: a contiguous {np.dtype(self.dtype).name} I420 frame of {self.frame_samples} samples "
+            raise ValueError(f"{what}: a contiguous {np.dtype(self.dtype).name} {_layout_name(self)} frame of {self.frame_samples} samples "
                              f"({self.height} x {self.width}) expected, got {a.dtype} {tuple(a.shape)}")
         return a.reshape(-1)
 
@@ -154,6 +181,25 @@ class Format:
 
 
 CHROMAS = ("planar", "uv", "vu")
+
+
+def _layout_name(fmt) -> str:
+    return {"420": "I420", "422": "planar 4:2:2", "444": "planar 4:4:4"}[fmt.subsampling]
+
+
+def _origin_error(who: str, fmt, y0: int, x0: int, noun: str = "window"):
+    """The origin rule of a window or crop of ``fmt``: a multiple of the subsampling step per axis.  None, or the ``ValueError``."""
+    sy, sx = fmt.steps
+    if y0 % sy == 0 and x0 % sx == 0:
+        return None
+    if fmt.subsampling == "420":
+        return ValueError(f"{who}: the {noun} origin ({y0}, {x0}) must be even for 4:2:0 frames")
+    return ValueError(f"{who}: the {noun} origin ({y0}, {x0}) must have an even x0 for 4:2:2 frames")
+
+
+def _only_420(who: str, fmt):
+    if fmt.subsampling != "420":
+        raise ValueError(f"{who}: 4:2:0 frames only (got subsampling {fmt.subsampling})")
 
 
 @dataclass(frozen=True)
@@ -182,6 +228,9 @@ class Surface:
             raise ValueError(f"yuv.Surface: unknown chroma layout {self.chroma!r} (planar, uv, vu)")
         if self.msb and self.fmt.depth != 10:
             raise ValueError("yuv.Surface: msb needs depth 10 (8-bit samples fill their byte)")
+        if self.fmt.subsampling != "420" and self.chroma != "planar":
+            raise ValueError(f"yuv.Surface: interleaved chroma ({self.chroma}) is 4:2:0 only (got subsampling {self.fmt.subsampling}; "
+                             "4:2:2 and 4:4:4 surfaces are planar)")
         b, (H, W), (ch, cw) = self.itemsize, (self.fmt.height, self.fmt.width), self.fmt.chroma_shape
         crow = (cw if self.chroma == "planar" else 2 * cw) * b
         pitch = W * b if self.pitch is None else int(self.pitch)
@@ -229,6 +278,9 @@ class Surface:
     chroma_shape = property(lambda self: self.fmt.chroma_shape)
     matrix_id = property(lambda self: self.fmt.matrix_id)
     siting_id = property(lambda self: self.fmt.siting_id)
+    subsampling = property(lambda self: self.fmt.subsampling)
+    subsampling_id = property(lambda self: self.fmt.subsampling_id)
+    steps = property(lambda self: self.fmt.steps)
     chroma_id = property(lambda self: CHROMAS.index(self.chroma))
 
     @property
@@ -280,9 +332,15 @@ class Surface:
         return (Y, first, second) if self.chroma == "uv" else (Y, second, first)
 
 
+@functools.lru_cache(maxsize=64)
+def _tight_surface(fmt: Format) -> Surface:
+    return Surface(fmt)
+
+
 def as_surface(fmt) -> Surface:
-    """A ``Surface`` as it is; a ``Format`` as its tight planar surface (the same bytes)."""
-    return fmt if isinstance(fmt, Surface) else Surface(fmt)
+    """A ``Surface`` as it is; a ``Format`` as its tight planar surface (the same bytes; surfaces are immutable, so one per format is
+    kept: the device calls ask on every launch)."""
+    return fmt if isinstance(fmt, Surface) else _tight_surface(fmt)
 
 
 def planes(buf, fmt):
@@ -323,6 +381,8 @@ def repack(buf, src, dst) -> np.ndarray:
     """One frame of ``src`` as a frame of ``dst`` (each a ``Surface`` or a ``Format``; the same size and depth): the sample values
     untouched, moved between layouts; ``msb`` shifts by 6 (into an ``msb`` surface the low bits are zero).  Padding of ``dst`` is zero."""
     a, b = as_surface(src), as_surface(dst)
+    if a.subsampling != b.subsampling:
+        raise ValueError(f"yuv.repack: subsampling {a.subsampling} and {b.subsampling} differ (repack moves samples, it does not resample)")
     if (a.height, a.width, a.depth) != (b.height, b.width, b.depth):
         raise ValueError(f"yuv.repack: {a.height} x {a.width} depth {a.depth} and {b.height} x {b.width} depth {b.depth} differ in size or depth")
     Y, U, V = a.planes(buf)
@@ -330,11 +390,17 @@ def repack(buf, src, dst) -> np.ndarray:
     return _pack(Y >> sh, U >> sh, V >> sh, b)
 
 
-def _chroma_taps(ys, xs, ch: int, cw: int, siting: str):
+def _chroma_taps(ys, xs, ch: int, cw: int, siting: str, subsampling: str = "420"):
     """The chroma taps of luma rows ``ys`` and columns ``xs`` of the frame: rows ``r0, r1`` (weights 3, 1), columns ``q0, q1`` with
-    weights ``wx0, wx1``; neighbours clamp at the frame's edges."""
-    r0 = ys >> 1
-    r1 = np.clip(r0 + np.where(ys & 1, 1, -1), 0, ch - 1)
+    weights ``wx0, wx1``; neighbours clamp at the frame's edges.  4:2:2 has no vertical filter (r0 = r1 = y: (4 a + 8) >> 4 is
+    (a + 2) >> 2), 4:4:4 none at all (q0 = q1 = x with weights (4, 0): (16 c + 8) >> 4 is c)."""
+    if subsampling == "420":
+        r0 = ys >> 1
+        r1 = np.clip(r0 + np.where(ys & 1, 1, -1), 0, ch - 1)
+    else:
+        r0 = r1 = ys
+    if subsampling == "444":
+        return r0, r1, xs, xs, np.full(len(xs), 4, np.int32), np.zeros(len(xs), np.int32)
     q0 = xs >> 1
     if siting == "left":
         q1 = np.minimum(q0 + 1, cw - 1)
@@ -364,7 +430,7 @@ def _to_rgb(Y, U, V, taps, coeffs, yo: int, mid: int, T: int, top: int) -> np.nd
 def _decode_window(buf, fmt: Format, y0: int, x0: int, h: int, w: int, keep: bool = False) -> np.ndarray:
     """The checked window of the whole frame's decode as int32 [h,w,3] RGB: 0..255, or 0..1023 with the 10-bit depth kept."""
     Y, U, V = _samples(buf, fmt)
-    taps = _chroma_taps(np.arange(y0, y0 + h), np.arange(x0, x0 + w), *fmt.chroma_shape, fmt.siting)
+    taps = _chroma_taps(np.arange(y0, y0 + h), np.arange(x0, x0 + w), *fmt.chroma_shape, fmt.siting, fmt.subsampling)
     if keep:
         pixel = COEFFS10[fmt.matrix][0], 64, 512, 14, 1023
     elif fmt.depth == 10:
@@ -386,6 +452,7 @@ def window_numpy(buf, fmt: Format, mode: int, y0: int, x0: int, h: int, w: int) 
     (each pixel clipped to 8 bits first).  The window is a window of the whole frame's decode: chroma neighbours are the frame's.
     Even origin, as ``crop``.  Only the window is decoded."""
     mode, y0, x0, h, w = int(mode), int(y0), int(x0), int(h), int(w)
+    _only_420("window_numpy", fmt)
     if mode not in (0, 1):
         raise ValueError(f"window_numpy: unknown mode {mode} (0: crop, 1: area 2x)")
     if y0 % 2 or x0 % 2:
@@ -410,8 +477,9 @@ def decode_numpy_f32(buf, fmt: Format, window=None) -> np.ndarray:
     fmt.planes(buf)                                 # the frame is checked before the window
     H, W = fmt.height, fmt.width
     y0, x0, h, w = (0, 0, H, W) if window is None else (int(v) for v in window)
-    if y0 % 2 or x0 % 2:
-        raise ValueError(f"decode_numpy_f32: the window origin ({y0}, {x0}) must be even for 4:2:0 frames")
+    err = _origin_error("decode_numpy_f32", fmt, y0, x0)
+    if err is not None:
+        raise err
     if y0 < 0 or x0 < 0 or h < 1 or w < 1 or y0 + h > H or x0 + w > W:
         raise ValueError(f"decode_numpy_f32: window {h} x {w} at ({y0}, {x0}) outside the {H} x {W} frame")
     return _decode_window(buf, fmt, y0, x0, h, w, keep=True).astype(np.float32) / np.float32(1023)
@@ -440,13 +508,18 @@ def encode_numpy(rgb, fmt: Format, bgr: bool = False) -> np.ndarray:
     dot = lambda e, s: e[0] * s[..., 0] + e[1] * s[..., 1] + e[2] * s[..., 2]
     yo, mid, top = (64, 512, 1023) if deep else (0 if fmt.full_range else 16, 128, 255)
     Y = np.clip(((dot(eY, p) + (1 << 13)) >> 14) + yo, 0, top)
-    ra = 2 * np.arange(ch)
-    rows = p[ra] + p[np.minimum(ra + 1, H - 1)]
+    if fmt.subsampling == "420":
+        ra = 2 * np.arange(ch)
+        rows, sh = p[ra] + p[np.minimum(ra + 1, H - 1)], 1
+    else:                                           # 4:2:2, 4:4:4: a chroma row per luma row
+        rows, sh = p, 0
     ca = 2 * np.arange(cw)
-    if fmt.siting == "left":
-        s, sh = rows[:, np.maximum(ca - 1, 0)] + 2 * rows[:, ca] + rows[:, np.minimum(ca + 1, W - 1)], 3
+    if fmt.subsampling == "444":
+        s = rows
+    elif fmt.siting == "left":
+        s, sh = rows[:, np.maximum(ca - 1, 0)] + 2 * rows[:, ca] + rows[:, np.minimum(ca + 1, W - 1)], sh + 2
     else:
-        s, sh = rows[:, ca] + rows[:, np.minimum(ca + 1, W - 1)], 2
+        s, sh = rows[:, ca] + rows[:, np.minimum(ca + 1, W - 1)], sh + 1
     U = np.clip(((dot(eU, s) + (1 << (13 + sh))) >> (14 + sh)) + mid, 0, top)
     V = np.clip(((dot(eV, s) + (1 << (13 + sh))) >> (14 + sh)) + mid, 0, top)
     if isinstance(fmt, Surface):
@@ -460,34 +533,44 @@ def crop(buf, fmt: Format, y0: int, x0: int, h: int, w: int) -> np.ndarray:
     """The h x w window at (y0, x0) of a packed frame as a packed frame of ``fmt.cropped(h, w)``: plane crops, the samples untouched.
     The origin must be even (a chroma sample covers two luma rows and columns)."""
     y0, x0, h, w = int(y0), int(x0), int(h), int(w)
-    if y0 % 2 or x0 % 2:
-        raise ValueError(f"yuv.crop: the crop origin ({y0}, {x0}) must be even for 4:2:0 frames")
+    err = _origin_error("yuv.crop", fmt, y0, x0, "crop")
+    if err is not None:
+        raise err
     if y0 < 0 or x0 < 0 or h < 1 or w < 1 or y0 + h > fmt.height or x0 + w > fmt.width:
         raise ValueError(f"yuv.crop: window {h} x {w} at ({y0}, {x0}) outside the {fmt.height} x {fmt.width} frame")
     Y, U, V = fmt.planes(buf)
-    ch, cw = (h + 1) // 2, (w + 1) // 2
+    (sy, sx), (ch, cw) = fmt.steps, fmt.cropped(h, w).chroma_shape
+    cy, cx = y0 // sy, x0 // sx
     if isinstance(fmt, Surface):            # the tight surface of the window, the stored samples as they are
         out = np.empty(fmt.cropped(h, w).frame_samples, fmt.dtype)
         oy, ou, ov = fmt.cropped(h, w).planes(out)
-        oy[...], ou[...], ov[...] = Y[y0:y0 + h, x0:x0 + w], U[y0 // 2:y0 // 2 + ch, x0 // 2:x0 // 2 + cw], V[y0 // 2:y0 // 2 + ch, x0 // 2:x0 // 2 + cw]
+        oy[...], ou[...], ov[...] = Y[y0:y0 + h, x0:x0 + w], U[cy:cy + ch, cx:cx + cw], V[cy:cy + ch, cx:cx + cw]
         return out
-    return np.concatenate([Y[y0:y0 + h, x0:x0 + w].reshape(-1), U[y0 // 2:y0 // 2 + ch, x0 // 2:x0 // 2 + cw].reshape(-1),
-                           V[y0 // 2:y0 // 2 + ch, x0 // 2:x0 // 2 + cw].reshape(-1)])
+    return np.concatenate([Y[y0:y0 + h, x0:x0 + w].reshape(-1), U[cy:cy + ch, cx:cx + cw].reshape(-1), V[cy:cy + ch, cx:cx + cw].reshape(-1)])
 
 
 # ------------------------------------------------------------------------------------------------ YUV4MPEG2
 Y4M_MAGIC = b"YUV4MPEG2"
 # C tag -> (siting, depth); "420" is the format's default and means what "420jpeg" means
 Y4M_TAGS = {"420": ("centre", 8), "420jpeg": ("centre", 8), "420mpeg2": ("left", 8), "420p10": ("centre", 10)}
+# the 4:2:2 and 4:4:4 tags (read only when the reader is told to accept them) -> (siting, depth, subsampling).  C422 is taken as
+# left-sited: the Y4M convention for 4:2:2 is co-sited chroma
+Y4M_SUB_TAGS = {"422": ("left", 8, "422"), "444": ("centre", 8, "444"), "422p10": ("left", 10, "422"), "444p10": ("centre", 10, "444")}
 
 
 class Y4MReader:
     """A YUV4MPEG2 stream (a path or a binary file object): ``fmt`` (a ``Format``; matrix "auto" by height, range from
     ``XCOLORRANGE``, siting and depth from the ``C`` tag), ``fps`` (a ``fractions.Fraction``), ``ctag`` / ``aspect`` as read; iterating
     yields the frames as 1-D uint8 (uint16 for 10-bit) arrays; ``len()`` when the file is seekable.  Accepted: C420, C420jpeg,
-    C420mpeg2, C420p10, progressive.  Refused, naming the tag: C420paldv, 4:2:2, 4:4:4, mono and interlaced streams.  ``matrix``: the format's matrix when "auto" (by height) is not wanted."""
+    C420mpeg2, C420p10, progressive.  Refused, naming the tag: C420paldv, 4:2:2, 4:4:4, mono and interlaced streams.  ``matrix``: the format's matrix when "auto" (by height) is not wanted.
+    ``accept``: the subsamplings to read; with "422" / "444" in it C422, C422p10 (left-sited: the Y4M convention for 4:2:2 is
+    co-sited chroma) and C444, C444p10 are read as well.  A tag outside ``accept`` is refused by name."""
 
-    def __init__(self, path_or_file, matrix: str = "auto"):
+    def __init__(self, path_or_file, matrix: str = "auto", accept=("420",)):
+        accept = tuple(str(a) for a in accept)
+        for a in accept:
+            if a not in SUBSAMPLINGS:
+                raise ValueError(f"Y4MReader: unknown subsampling {a!r} in accept (420, 422, 444)")
         self._own = isinstance(path_or_file, (str, os.PathLike))
         self.f = open(path_or_file, "rb") if self._own else path_or_file
         line = self._line()
@@ -520,10 +603,16 @@ class Y4MReader:
                 full = True
         if w is None or h is None:
             raise ValueError("Y4MReader: the header gives no W / H")
-        if self.ctag not in Y4M_TAGS:
-            raise ValueError(f"Y4MReader: unsupported chroma format (tag C{self.ctag}); C420, C420jpeg, C420mpeg2 and C420p10 are read")
-        siting, depth = Y4M_TAGS[self.ctag]
-        self.fmt = Format(h, w, matrix, full, siting, depth)        # the header cannot name the matrix: the caller may
+        known = {t: v + ("420",) for t, v in Y4M_TAGS.items()}
+        known.update(Y4M_SUB_TAGS)
+        if self.ctag not in known or known[self.ctag][2] not in accept:
+            read = (["C420, C420jpeg, C420mpeg2", "C420p10"] if "420" in accept else []) + \
+                [f"C{t}" for t, v in Y4M_SUB_TAGS.items() if v[2] in accept]
+            if self._own:
+                self.f.close()
+            raise ValueError(f"Y4MReader: unsupported chroma format (tag C{self.ctag}); {', '.join(read[:-1])} and {read[-1]} are read")
+        siting, depth, sub = known[self.ctag]
+        self.fmt = Format(h, w, matrix, full, siting, depth, sub)   # the header cannot name the matrix: the caller may
         self._data0 = self._tell()
 
     def _tell(self):
@@ -617,14 +706,22 @@ class Y4MReader:
 
 class Y4MWriter:
     """Writes packed I420 frames of ``fmt`` as YUV4MPEG2 at ``fps`` (anything ``Fraction`` accepts: the rate is written as an exact
-    ratio).  ``ctag``: the C tag to write when it should differ from the format's canonical one (420jpeg / 420mpeg2 / 420p10)."""
+    ratio).  ``ctag``: the C tag to write when it should differ from the format's canonical one (420jpeg / 420mpeg2 / 420p10; 422,
+    422p10 for left-sited 4:2:2 and 444, 444p10 are the only tags of their formats)."""
 
     def __init__(self, path_or_file, fmt: Format, fps, ctag: Optional[str] = None, aspect: Optional[str] = None):
         self._own = isinstance(path_or_file, (str, os.PathLike))
         self.f = open(path_or_file, "wb") if self._own else path_or_file
         self.fmt, self.fps = fmt, Fraction(fps)
-        canon = "420p10" if fmt.depth == 10 else ("420mpeg2" if fmt.siting == "left" else "420jpeg")
-        if ctag is not None and Y4M_TAGS.get(ctag) != (fmt.siting, fmt.depth):
+        if fmt.subsampling == "420":
+            canon = "420p10" if fmt.depth == 10 else ("420mpeg2" if fmt.siting == "left" else "420jpeg")
+            described = Y4M_TAGS.get(ctag) == (fmt.siting, fmt.depth)
+        else:
+            canon = fmt.subsampling + ("p10" if fmt.depth == 10 else "")
+            if Y4M_SUB_TAGS[canon] != (fmt.siting, fmt.depth, fmt.subsampling):
+                raise ValueError(f"Y4MWriter: no Y4M tag describes {fmt} (C{canon} is {Y4M_SUB_TAGS[canon][0]}-sited)")
+            described = ctag == canon
+        if ctag is not None and not described:
             raise ValueError(f"Y4MWriter: tag C{ctag} does not describe {fmt}")
         self.ctag = ctag or canon
         head = f"YUV4MPEG2 W{fmt.width} H{fmt.height} F{self.fps.numerator}:{self.fps.denominator} Ip A{aspect or '0:0'} C{self.ctag}"
@@ -802,7 +899,7 @@ def interpolate_y4m(src, dst, model, factor: int = 2, scene=None, tta: bool = Fa
     from .host_io import _hip_ops_of, interpolate_video_2x
     from .multiframe import centre_window, interpolate_video_nx, nx_levels
     nx_levels(factor)
-    rd = Y4MReader(src, matrix=matrix)
+    rd = Y4MReader(src, matrix=matrix, accept=SUBSAMPLINGS)
     fmt = rd.fmt
     _, _, oh, ow = centre_window(fmt.height, fmt.width, kw.get("crop"))
     deep = bool(keep_depth) and fmt.depth == 10
@@ -837,13 +934,19 @@ def interpolate_y4m(src, dst, model, factor: int = 2, scene=None, tta: bool = Fa
 
 PIX_FMTS = {"nv12": ("uv", 8, False), "nv21": ("vu", 8, False), "p010le": ("uv", 10, True), "yuv420p": ("planar", 8, False),
             "yuv420p10le": ("planar", 10, False)}
+# the planar 4:2:2 / 4:4:4 names -> (depth, subsampling)
+PIX_FMTS_SUB = {"yuv422p": (8, "422"), "yuv444p": (8, "444"), "yuv422p10le": (10, "422"), "yuv444p10le": (10, "444")}
 
 
 def surface_of(pix_fmt: str, h: int, w: int, pitch=None, **format_kw) -> Surface:
-    """ffmpeg's ``-pix_fmt`` name (nv12, nv21, p010le, yuv420p, yuv420p10le) -> the ``Surface``; ``pitch`` (bytes): the luma rows' and
-    the interleaved chroma rows', planar chroma rows half of it."""
+    """ffmpeg's ``-pix_fmt`` name (nv12, nv21, p010le, yuv420p, yuv420p10le, yuv422p, yuv444p, yuv422p10le, yuv444p10le) -> the
+    ``Surface``; ``pitch`` (bytes): the luma rows' and the interleaved chroma rows', planar chroma rows half of it (4:4:4: all of it)."""
+    if pix_fmt in PIX_FMTS_SUB:            # planar: 4:2:2 chroma rows have half the pitch, 4:4:4 rows all of it
+        depth, sub = PIX_FMTS_SUB[pix_fmt]
+        cp = None if pitch is None else (int(pitch) if sub == "444" else int(pitch) // 2)
+        return Surface(Format(h, w, depth=depth, subsampling=sub, **format_kw), "planar", False, pitch, cp)
     if pix_fmt not in PIX_FMTS:
-        raise ValueError(f"yuv.surface_of: unknown pixel format {pix_fmt!r} ({', '.join(PIX_FMTS)})")
+        raise ValueError(f"yuv.surface_of: unknown pixel format {pix_fmt!r} ({', '.join(list(PIX_FMTS) + list(PIX_FMTS_SUB))})")
     chroma, depth, msb = PIX_FMTS[pix_fmt]
     cp = None if pitch is None else (int(pitch) // 2 if chroma == "planar" else int(pitch))
     return Surface(Format(h, w, depth=depth, **format_kw), chroma, msb, pitch, cp)
@@ -918,7 +1021,7 @@ def _retime_y4m(src, dst, model, fps_out, levels, dedup, scene, tta, interpolato
     from .retime import _check_rates, interpolate_video_retimed
     if "time_interval" in kw:
         raise ValueError("interpolate_y4m: fps_out and time_interval do not go together")
-    rd = Y4MReader(src, matrix=matrix)
+    rd = Y4MReader(src, matrix=matrix, accept=SUBSAMPLINGS)
     try:
         fmt = rd.fmt
         _, rate, levels = _check_rates(rd.fps, fps_out, levels)

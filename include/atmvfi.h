@@ -638,6 +638,42 @@ int atmvfi_yuv_surface_decode(const void* yuv, int H, int W, int depth, int matr
 int atmvfi_yuv_surface_encode(const void* src_u8, int bgr, const float* src, int Hp, int Wp, int pad_top, int pad_left, int H, int W,
                               int depth, int matrix, int full_range, int siting, int chroma, int msb, void* yuv, void* stream);
 
+/* Planar 4:2:2 and 4:4:4 frames, 8 and 10 bit (yuv.hip, yuv_encode.hip; ABI 0.20; atm-vfi_amd/yuv.py: Format.subsampling; per-pixel model
+ * tests/cpu_yuv_sub.py).  The two surface calls above with one more argument after `siting`:
+ *   subsampling    0: 4:2:0, chroma planes [(H + 1) / 2, (W + 1) / 2] -- the call IS the surface call then: the same checks, the same
+ *                  kernel instance, the same bytes; 1: 4:2:2, chroma planes [H, (W + 1) / 2]; 2: 4:4:4, chroma planes [H, W].
+ *                  Planes are Y, U, V in that order, as in I420.
+ * Depth 8 and 10 have the sample types, coefficients, yo, mid, T, range rules and clips of the calls above; no new coefficient exists.
+ * Decode 4:2:2: chroma row r = y (no vertical filter); the columns q0, q1 and the weights (wx0, wx1) are those of 4:2:0 for both
+ *   sitings; c' = (wx0 c[y][q0] + wx1 c[y][q1] + 2) >> 2.  Decode 4:4:4: c' = c[y][x].  The pixel from (Y, U', V') is unchanged for both
+ *   pixel maxima (clip8 and q / 255; keep_depth: 0..1023 and q / 1023).
+ * Encode: the source pixel p and Y are unchanged; chroma from the un-rounded sums s -- 4:2:2 centre: over columns 2i and
+ *   min(2i + 1, W - 1) of row j, sh = 1; 4:2:2 left: max(2i - 1, 0), 2i, min(2i + 1, W - 1) weighted 1, 2, 1, sh = 2; 4:4:4: s = p,
+ *   sh = 0 -- U = clip(((eU . s + 2^(13 + sh)) >> (14 + sh)) + mid), V with eV.
+ * Identities that hold bit for bit (from (4 h + 8) >> 4 == (h + 2) >> 2 and (2 x + 2^(k+1)) >> (k+1) == (x + 2^k) >> k): a 4:2:2 frame
+ *   whose chroma rows are all equal decodes to the pixels of the 4:2:0 frame that holds those rows; flat U and V planes decode to the same
+ *   pixels under all three subsamplings; a picture whose rows 2j and 2j + 1 are equal has 4:2:2 chroma rows 2j equal to the 4:2:0 encode's
+ *   row j; with columns 2i and 2i + 1 equal and centre siting the 4:4:4 chroma at column 2i is the 4:2:2 sample i.
+ * The window origin must be a multiple of the subsampling step per axis: 4:2:0 even y0 and x0, 4:2:2 even x0 and any y0, 4:4:4 any.
+ *   Chroma neighbours clamp at the FRAME's edges, never at the window's.  pitch / chroma_pitch / chroma_offset follow the rules above with
+ *   the chroma row width cw b and H chroma rows per plane; the planar V plane follows U at chroma_offset + chroma_pitch * H.
+ * Refused on the host before any launch (ATMVFI_EINVAL), in addition to what the surface calls refuse: an unknown subsampling;
+ *   interleaved chroma (chroma != 0) or msb with subsampling != 0; siting 1 with 4:4:4 (it has no meaning there); a window origin that
+ *   breaks the rule above.
+ * Any geometry, pitch and pointer alignment is accepted (byte accesses).  The vector path runs under the conditions of the surface calls;
+ *   for 4:4:4 the chroma rows must be dword-aligned like the luma rows (chroma_pitch and the U / V origins multiples of 4 bytes).  A lane
+ *   owns four horizontally adjacent pixels on two rows; 4:2:2 loads one chroma row per luma row (two per lane, no vertical mix), 4:4:4
+ *   loads U and V of a group as it loads Y (a dword, or 8 bytes at depth 10); the encode stores a lane's chroma per plane and row as a
+ *   2-byte or dword pair (4:2:2) or a dword or 8 bytes (4:4:4).  Both paths give the same bits.  Every output byte is written by exactly
+ *   one lane; vector stores only, no atomics, nothing pre-zeroed; no padding byte is ever written.
+ * Not covered: 12 bit, 4:1:1 / 4:4:0, interleaved or packed 4:2:2 / 4:4:4 (NV16, P210, YUY2, UYVY, Y210, AYUV, Y410), alpha, bt2020 and
+ *   transfer functions, the area mode of atmvfi_yuv420_window. */
+int atmvfi_yuv_sub_decode(const void* yuv, int H, int W, int depth, int matrix, int full_range, int siting, int subsampling, int chroma, int msb,
+                          int64_t pitch, int64_t chroma_pitch, int64_t chroma_offset, int keep_depth, int y0, int x0, int h, int w,
+                          void* dst_u8, int bgr, float* dst, int Hp, int Wp, int pad_top, int pad_left, void* stream);
+int atmvfi_yuv_sub_encode(const void* src_u8, int bgr, const float* src, int Hp, int Wp, int pad_top, int pad_left, int H, int W,
+                          int depth, int matrix, int full_range, int siting, int subsampling, int chroma, int msb, void* yuv, void* stream);
+
 /* mean |a - b| per sample: global_alignmentness (network_base.py:560-561).  Two passes with a fixed summation order -- the result is
  * run-to-run bit-identical (the ensemble's pick compares these means) -- through `workspace`: at least
  * atmvfi_l1_mean_workspace_floats(B, per_sample) floats of scratch, the caller's. */

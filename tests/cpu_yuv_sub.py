@@ -1,0 +1,164 @@
+"""Planar YUV 4:2:2 and 4:4:4 frames (8 and 10 bit, packed or pitched) as explicit per-sample Python loops over plain ints: the model that
+``atm-vfi_amd/yuv.py``'s twins and ``atmvfi_yuv_sub_decode`` / ``atmvfi_yuv_sub_encode`` are held to, bit for bit.  Written from the
+definition of the README's "4:2:2 and 4:4:4" subsection: it carries its own coefficient tables, addresses every sample by its byte
+offset, and calls nothing of the package -- a layout is the plain dict ``layout(...)`` makes.  ``sub``: "420", "422" or "444"; "420"
+is here too (the formulas of "YUV 4:2:0 and Y4M"), so that the identities between the subsamplings can be stated on one model."""
+import numpy as np
+
+# (matrix, full_range) -> decode [kY, kRV, kGU, kGV, kBU], encode rows Y / U / V over (R, G, B); "10": the depth kept
+TABLE = {
+    ("bt601", 0): ([19077, 26149, -6419, -13320, 33050], [[4207, 8260, 1604], [-2428, -4768, 7196], [7196, -6026, -1170]]),
+    ("bt601", 1): ([16384, 22970, -5638, -11700, 29032], [[4899, 9617, 1868], [-2765, -5427, 8192], [8192, -6860, -1332]]),
+    ("bt709", 0): ([19077, 29372, -3494, -8731, 34610], [[2991, 10064, 1016], [-1649, -5547, 7196], [7196, -6536, -660]]),
+    ("bt709", 1): ([16384, 25802, -3069, -7670, 30402], [[3483, 11718, 1183], [-1877, -6315, 8192], [8192, -7441, -751]]),
+    ("bt601", 10): ([19133, 26226, -6438, -13359, 33148], [[4195, 8235, 1599], [-2421, -4754, 7175], [7175, -6008, -1167]]),
+    ("bt709", 10): ([19133, 29459, -3504, -8757, 34711], [[2983, 10034, 1013], [-1644, -5531, 7175], [7175, -6517, -658]]),
+}
+STEPS = {"420": (2, 2), "422": (1, 2), "444": (1, 1)}        # luma rows, columns per chroma sample
+
+
+def clamp(v, lo, hi):
+    return lo if v < lo else (hi if v > hi else v)
+
+
+def layout(H, W, depth=8, sub="422", pitch=None, chroma_pitch=None, chroma_offset=None):
+    """-> dict: the definition's defaults filled in, everything in bytes; planes Y, U, V in that order"""
+    sy, sx = STEPS[sub]
+    b, ch, cw = (2 if depth == 10 else 1), (H + sy - 1) // sy, (W + sx - 1) // sx
+    crow = cw * b
+    pitch = W * b if pitch is None else pitch
+    chroma_pitch = crow if chroma_pitch is None else chroma_pitch
+    chroma_offset = pitch * H if chroma_offset is None else chroma_offset
+    return dict(H=H, W=W, depth=depth, b=b, sub=sub, ch=ch, cw=cw, pitch=pitch, chroma_pitch=chroma_pitch, chroma_offset=chroma_offset,
+                nbytes=chroma_offset + chroma_pitch * (2 * ch - 1) + crow)
+
+
+def offset(L, plane, r, c):
+    """the byte offset of sample (r, c) of plane "y" / "u" / "v" """
+    if plane == "y":
+        return L["pitch"] * r + L["b"] * c
+    return L["chroma_offset"] + L["chroma_pitch"] * (r + (L["ch"] if plane == "v" else 0)) + L["b"] * c
+
+
+def value(raw, L, plane, r, c):
+    o = offset(L, plane, r, c)
+    return int(raw[o]) if L["b"] == 1 else int(raw[o]) | (int(raw[o + 1]) << 8)
+
+
+def raw_bytes(buf, L):
+    raw = np.ascontiguousarray(np.asarray(buf)).view(np.uint8).reshape(-1)
+    assert raw.size == L["nbytes"], (raw.size, L["nbytes"])
+    return raw
+
+
+def origin_ok(sub, y0, x0):
+    """a window's or crop's origin is a multiple of the subsampling step per axis"""
+    return y0 % STEPS[sub][0] == 0 and x0 % STEPS[sub][1] == 0
+
+
+def decode(buf, L, matrix="bt601", full_range=0, siting="centre", window=None, keep=False):
+    """-> int32 [h,w,3] RGB of the window (default: the frame): 0..255, or 0..1023 with the 10-bit depth kept.  Chroma neighbours
+    clamp at the frame's edges."""
+    raw = raw_bytes(buf, L)
+    H, W, ch, cw, sub = L["H"], L["W"], L["ch"], L["cw"], L["sub"]
+    y0, x0, h, w = (0, 0, H, W) if window is None else window
+    assert origin_ok(sub, y0, x0) and 0 <= y0 and 0 <= x0 and y0 + h <= H and x0 + w <= W
+    assert not (sub == "444" and siting != "centre")
+    if keep:
+        (kY, kRV, kGU, kGV, kBU), yo, mid, T, top = TABLE[matrix, 10][0], 64, 512, 14, 1023
+    elif L["depth"] == 10:
+        (kY, kRV, kGU, kGV, kBU), yo, mid, T, top = TABLE[matrix, int(full_range)][0], 64, 512, 16, 255
+    else:
+        (kY, kRV, kGU, kGV, kBU), yo, mid, T, top = TABLE[matrix, int(full_range)][0], (0 if full_range else 16), 128, 14, 255
+    out = np.zeros((h, w, 3), np.int32)
+    for y in range(y0, y0 + h):
+        for x in range(x0, x0 + w):
+            up = []
+            for p in ("u", "v"):
+                c = lambda r, q: value(raw, L, p, r, q)
+                if sub == "444":
+                    up.append(c(y, x))
+                    continue
+                q0 = x >> 1
+                if siting == "centre":
+                    q1, wx0, wx1 = clamp(q0 + (1 if x & 1 else -1), 0, cw - 1), 3, 1
+                else:
+                    q1 = min(q0 + 1, cw - 1)
+                    wx0, wx1 = (2, 2) if x & 1 else (4, 0)
+                if sub == "422":
+                    up.append((wx0 * c(y, q0) + wx1 * c(y, q1) + 2) >> 2)
+                else:
+                    r0 = y >> 1
+                    r1 = clamp(r0 + (1 if y & 1 else -1), 0, ch - 1)
+                    up.append((3 * (wx0 * c(r0, q0) + wx1 * c(r0, q1)) + (wx0 * c(r1, q0) + wx1 * c(r1, q1)) + 8) >> 4)
+            yy, u, v, half = value(raw, L, "y", y, x) - yo, up[0] - mid, up[1] - mid, 1 << (T - 1)
+            out[y - y0, x - x0] = (clamp((kY * yy + kRV * v + half) >> T, 0, top), clamp((kY * yy + kGU * u + kGV * v + half) >> T, 0, top),
+                                   clamp((kY * yy + kBU * u + half) >> T, 0, top))
+    return out
+
+
+def pixels(src, depth):
+    """the encode's source pixels as ints: uint8 RGB as it is; fp32 in units of 1 -> clip(rint(fl32(x * top))), half to even"""
+    src = np.asarray(src)
+    if src.dtype == np.uint8:
+        return src.astype(np.int64)
+    top = 1023 if depth == 10 else 255
+    return np.clip(np.rint(src.astype(np.float32) * np.float32(top)), 0, top).astype(np.int64)
+
+
+def encode(px, L, matrix="bt601", full_range=0, siting="centre"):
+    """int [H,W,3] RGB pixels (``pixels``) -> the TIGHT frame of ``L`` as bytes (1-D uint8); no byte is written twice"""
+    assert L == layout(L["H"], L["W"], L["depth"], L["sub"]), "encodes write tight frames only"
+    assert not (L["sub"] == "444" and siting != "centre")
+    H, W, ch, cw, b, sub = L["H"], L["W"], L["ch"], L["cw"], L["b"], L["sub"]
+    deep = L["depth"] == 10
+    eY, eU, eV = TABLE[matrix, 10 if deep else int(full_range)][1]
+    yo, mid, top = (64, 512, 1023) if deep else ((0 if full_range else 16), 128, 255)
+    raw, written = np.zeros(L["nbytes"], np.uint8), np.zeros(L["nbytes"], np.int32)
+
+    def put(plane, r, c, v):
+        o = offset(L, plane, r, c)
+        for k in range(b):
+            raw[o + k] = (v >> (8 * k)) & 255
+            written[o + k] += 1
+    P = [[[int(v) for v in px[y][x]] for x in range(W)] for y in range(H)]
+    for y in range(H):
+        for x in range(W):
+            p = P[y][x]
+            put("y", y, x, clamp(((eY[0] * p[0] + eY[1] * p[1] + eY[2] * p[2] + (1 << 13)) >> 14) + yo, 0, top))
+    for plane, e in (("u", eU), ("v", eV)):
+        for j in range(ch):
+            for i in range(cw):
+                if sub == "444":
+                    taps, sh = [(i, 1)], 0
+                elif siting == "centre":
+                    taps, sh = [(2 * i, 1), (min(2 * i + 1, W - 1), 1)], 1
+                else:
+                    taps, sh = [(max(2 * i - 1, 0), 1), (2 * i, 2), (min(2 * i + 1, W - 1), 1)], 2
+                rows = [j]
+                if sub == "420":
+                    rows, sh = [2 * j, min(2 * j + 1, H - 1)], sh + 1
+                s = [0, 0, 0]
+                for r in rows:
+                    for col, wgt in taps:
+                        for c in range(3):
+                            s[c] += wgt * P[r][col][c]
+                put(plane, j, i, clamp(((e[0] * s[0] + e[1] * s[1] + e[2] * s[2] + (1 << (13 + sh))) >> (14 + sh)) + mid, 0, top))
+    assert (written == 1).all()             # tight: every byte of the frame is a sample's, written once
+    return raw
+
+
+def random_frame(L, seed=0, poison=None):
+    """A seeded uniform-random frame of ``L`` as the 1-D sample array (uint8 / uint16): every sample over its whole range.  Padding
+    bytes: ``poison`` (a byte value) or random."""
+    rng = np.random.default_rng(seed)
+    raw = rng.integers(0, 256, L["nbytes"]).astype(np.uint8) if poison is None else np.full(L["nbytes"], poison, np.uint8)
+    for plane, rows, cols in (("y", L["H"], L["W"]), ("u", L["ch"], L["cw"]), ("v", L["ch"], L["cw"])):
+        vals = rng.integers(0, 1024 if L["b"] == 2 else 256, (rows, cols))
+        for r in range(rows):
+            for c in range(cols):
+                o, v = offset(L, plane, r, c), int(vals[r, c])
+                raw[o] = v & 255
+                if L["b"] == 2:
+                    raw[o + 1] = v >> 8
+    return raw.view("<u2").astype(np.uint16) if L["b"] == 2 else raw

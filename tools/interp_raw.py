@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Headerless video in, headerless video out at ``factor`` times the frame rate (``atm-vfi_amd.yuv.interpolate_raw``): the frames of an
-``ffmpeg -f rawvideo -pix_fmt nv12|nv21|p010le|yuv420p|yuv420p10le`` pipe travel as they are and are converted on the GPU; nothing is
+``ffmpeg -f rawvideo -pix_fmt nv12|nv21|p010le|yuv420p|yuv420p10le|yuv422p|yuv422p10le|yuv444p|yuv444p10le`` pipe travel as they are and are converted on the GPU; nothing is
 repacked on the host.  The output has the same pixel format without row padding; 10-bit input is written back as its 8-bit
 counterpart (p010le -> nv12), or with ``--keep-depth`` at 10 bits.  ``-`` reads standard input / writes standard output
 (``ffmpeg -i in.mp4 -f rawvideo -pix_fmt nv12 - | interp_raw.py - out.nv12 --pix-fmt nv12 --size 1920x1080 --fps 30000/1001 --ckpt ...``).
@@ -10,7 +10,7 @@ counterpart (p010le -> nv12), or with ``--keep-depth`` at 10 bits.  ``-`` reads 
                               [--keep-depth] [--fps-out R [--levels L] [--dedup] [--shutter ANGLE [--light code|linear]]]
 
 ``--pitch N``: the input's luma row stride in bytes (a decoder's surface dump; interleaved chroma rows share it, planar ones have
-half).  Everything from ``--factor`` on is ``interp_y4m.py``'s."""
+half, 4:4:4 ones all of it).  Everything from ``--factor`` on is ``interp_y4m.py``'s."""
 import argparse
 import importlib
 import os
@@ -26,12 +26,12 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("src")
     ap.add_argument("dst")
-    ap.add_argument("--pix-fmt", required=True, choices=("nv12", "nv21", "p010le", "yuv420p", "yuv420p10le"))
+    ap.add_argument("--pix-fmt", required=True, choices=("nv12", "nv21", "p010le", "yuv420p", "yuv420p10le", "yuv422p", "yuv444p", "yuv422p10le", "yuv444p10le"))
     ap.add_argument("--size", required=True, metavar="WxH")
     ap.add_argument("--fps", required=True, metavar="R", help="the input's frame rate (e.g. 25 or 30000/1001)")
     ap.add_argument("--pitch", type=int, default=None, metavar="N", help="luma row stride of the input in bytes (default: tight)")
     ap.add_argument("--matrix", choices=("auto", "bt601", "bt709"), default="auto")
-    ap.add_argument("--siting", choices=("centre", "left"), default="left", help="chroma siting (decoders deliver left-sited 4:2:0)")
+    ap.add_argument("--siting", choices=("centre", "left"), default="left", help="chroma siting (decoders deliver left-sited 4:2:0 and 4:2:2; 4:4:4 has none)")
     ap.add_argument("--full-range", action="store_true")
     ap.add_argument("--ckpt", default=None, help="checkpoint (the trainer's dict or a bare state dict); without one: synthetic weights")
     ap.add_argument("--model", choices=("base", "lite"), default="base")
@@ -55,7 +55,8 @@ def main():
     except ValueError:
         ap.error(f"--size must be WxH (got {a.size!r})")
     yuv = importlib.import_module("atm-vfi_amd.yuv")
-    surface = yuv.surface_of(a.pix_fmt, h, w, pitch=a.pitch, matrix=a.matrix, siting=a.siting, full_range=a.full_range)
+    siting = "centre" if a.pix_fmt.startswith("yuv444p") else a.siting
+    surface = yuv.surface_of(a.pix_fmt, h, w, pitch=a.pitch, matrix=a.matrix, siting=siting, full_range=a.full_range)
     if not torch.cuda.is_available():
         sys.exit("interp_raw: no GPU")
     pkg = importlib.import_module("atm-vfi_amd")
