@@ -1,5 +1,5 @@
-// YUV 4:2:0 (and planar 4:2:2 / 4:4:4) -> RGB: the five decode entry points of include/atmvfi.h on one kernel.  yuv_common.h holds the definition and
-// every helper; yuv_encode.hip is the other direction.
+// YUV 4:2:0 (and planar 4:2:2 / 4:4:4) -> RGB: the five decode entry points of include/atmvfi.h on one kernel and one checked host path
+// (surface_decode, below the kernels).  yuv_common.h holds the definition and every helper; yuv_encode.hip is the other direction.
 //   atmvfi_yuv420_to_rgb      the whole frame -> fp32 planar [3,Hp,Wp] = q / 255 and / or uint8 [H,W,3] (RGB or BGR)
 //   atmvfi_yuv420p10_to_f32   a window of a 10-bit frame with the depth kept -> fp32 planar = q / 1023
 //   atmvfi_yuv_surface_decode a window of a decoder's surface (NV12 / NV21 / P010, planar; any pitch and chroma offset) -> either
@@ -248,133 +248,37 @@ __global__ __launch_bounds__(256) void yuv420_area_kernel(const AreaArgs p) {
 // (without a canvas Wp is w and pad_left 0)
 // (il: interleaved chroma; msb: 10-bit samples stored in the upper bits)
 // (sub: 1 4:2:2, 2 4:4:4 -- planar, LSB, mode 0)
-void launch_decode(const DecArgs& a, int depth, bool keep, int mode, int siting, void* stream, bool il = false, bool msb = false, int sub = 0) {
+// The run-time properties select the instance in this one place; decode_instance (yuv_common.h) names the combinations that have none,
+// and mode 1 exists for the planar LSB 4:2:0 pixels 0..255 alone.  surface_decode has refused the rest.
+void launch_decode(const DecArgs& a, int depth, bool keep, int mode, int siting, void* stream, bool il, bool msb, int sub) {
     const bool al = aligned4(a.yuv) && a.W % 4 == 0 && layout_aligned(a.ys, a.cs, a.uoff, a.voff, depth, il, sub) && a.x0 % 4 == 0 && a.w % 4 == 0 &&
                     (!a.dst || canvas_aligned(a.dst, a.Wp, a.pad_left)) && (!a.dst_u8 || aligned4(a.dst_u8));
     const dim3 grid = yuv_grid((long long)a.rows * a.groups), block(256);
     const hipStream_t st = (hipStream_t)stream;
-    if (sub) {              // the instances of atmvfi_yuv_sub_decode: three pixel kinds x two paths x (4:2:2 x two sitings + 4:4:4)
-        dispatch(al, sub == 1 && siting, sub == 2, [&](auto AL, auto LEFT, auto S444) {
-            constexpr int SUB = decltype(S444)::value ? 2 : 1;
-            auto go = [&](auto px) {
-                hipLaunchKernelGGL((yuv420_crop_kernel<decltype(px), decltype(AL)::value, decltype(LEFT)::value>), grid, block, 0, st, a);
-            };
-            if constexpr (!(SUB == 2 && decltype(LEFT)::value)) {
-                if (keep) go(Pixel<10, 1023, false, false, SUB>{});
-                else if (depth == 10) go(Pixel<10, 255, false, false, SUB>{});
-                else go(Pixel<8, 255, false, false, SUB>{});
+    dispatch_sub([&](auto SUBC, auto AL, auto LEFT, auto D10, auto KEEP, auto IL, auto MSB) {
+        constexpr int DEPTH = D10() ? 10 : 8, TOP = KEEP() ? 1023 : 255, SUB = SUBC();
+        if constexpr (decode_instance<DEPTH, TOP, IL(), MSB(), SUB, LEFT()>) {
+            using PX = Pixel<DEPTH, TOP, IL(), MSB(), SUB>;
+            if (mode == 0) {
+                hipLaunchKernelGGL((yuv420_crop_kernel<PX, AL(), LEFT()>), grid, block, 0, st, a);
+                return;
             }
-        });
-    } else if (il || msb) {        // the instances of atmvfi_yuv_surface_decode that the planar, LSB calls do not have (mode 0 only)
-        dispatch(al, siting, [&](auto AL, auto LEFT) {
-            dispatch(il, msb, [&](auto IL_, auto MSB_) {
-                constexpr bool IL = decltype(IL_)::value, M = decltype(MSB_)::value;
-                auto go = [&](auto px) {
-                    hipLaunchKernelGGL((yuv420_crop_kernel<decltype(px), decltype(AL)::value, decltype(LEFT)::value>), grid, block, 0, st, a);
-                };
-                if constexpr (IL || M) {
-                    if (keep) go(Pixel<10, 1023, IL, M>{});
-                    else if (depth == 10) go(Pixel<10, 255, IL, M>{});
-                    else if constexpr (!M) go(Pixel<8, 255, IL, false>{});
-                }
-            });
-        });
-    } else if (keep) {
-        dispatch(al, siting, [&](auto AL, auto LEFT) {
-            hipLaunchKernelGGL((yuv420_crop_kernel<Px10, decltype(AL)::value, decltype(LEFT)::value>), grid, block, 0, st, a);
-        });
-    } else {
-        dispatch(depth == 10, al, siting, [&](auto D10, auto AL, auto LEFT) {
-            using PX = std::conditional_t<decltype(D10)::value, Px10to8, Px8>;
-            if (mode == 0)
-                hipLaunchKernelGGL((yuv420_crop_kernel<PX, decltype(AL)::value, decltype(LEFT)::value>), grid, block, 0, st, a);
-            else
-                hipLaunchKernelGGL((yuv420_area_kernel<PX, decltype(AL)::value, decltype(LEFT)::value>), grid, block, 0, st,
+            // (AreaArgs repeats DecArgs without the strides, and no compiler checks the list: a new DecArgs field goes here too)
+            if constexpr (TOP == 255 && !IL() && !MSB() && SUB == 0)
+                hipLaunchKernelGGL((yuv420_area_kernel<PX, AL(), LEFT()>), grid, block, 0, st,
                                    AreaArgs{a.yuv, a.H, a.W, a.ch, a.cw, a.uoff, a.voff, a.kY, a.kRV, a.kGU, a.kGV, a.kBU, a.yo, a.mid, a.T, a.y0, a.x0,
                                             a.h, a.w, a.dst, a.Hp, a.Wp, a.pad_top, a.pad_left, a.dst_u8, a.bgr, a.groups, a.rows});
-        });
-    }
+        }
+    }, sub, al, siting != 0, depth == 10, keep, il, msb);
 }
 
-}  // namespace
-
-extern "C" int atmvfi_yuv420_to_rgb(const void* yuv, int H, int W, int depth, int matrix, int full_range, int siting, void* dst_u8, int bgr,
-                                    float* dst, int Hp, int Wp, int pad_top, int pad_left, void* stream) {
-    const char* me = "yuv420_to_rgb";
-    ATMVFI_REQUIRE(yuv, ATMVFI_EINVAL, "yuv420_to_rgb: null source");
-    ATMVFI_REQUIRE(dst || dst_u8, ATMVFI_EINVAL, "yuv420_to_rgb: both outputs are null (give dst, dst_u8 or both)");
-    if (const int rc = check_format(me, H, W, matrix, full_range, siting)) return rc;
-    if (const int rc = check_depth(me, depth, full_range)) return rc;
-    if (dst) {
-        if (const int rc = check_canvas(me, "dst", "frame", dst, H, W, Hp, Wp, pad_top, pad_left)) return rc;
-    } else {        // no canvas: the output geometry is the frame's
-        Hp = H;
-        Wp = W;
-        pad_top = pad_left = 0;
-    }
-    const int groups = groups_of(Wp), pairs = pairs_of(Hp);
-    if (const int rc = check_items(me, pairs, groups, "output of", Hp, Wp)) return rc;
-    // the window is the whole frame
-    const DecArgs a = {make_src(yuv, H, W, depth, matrix, full_range, false), 0, 0, H, W, dst, Hp, Wp, pad_top, pad_left, (unsigned char*)dst_u8,
-                       bgr ? 1 : 0, groups, pairs};
-    launch_decode(a, depth, false, 0, siting, stream);
-    return atmvfi::check_launch(me);
-}
-
-extern "C" int atmvfi_yuv420p10_to_f32(const void* yuv, int H, int W, int matrix, int siting, int y0, int x0, int h, int w, float* dst,
-                                       int Hp, int Wp, int pad_top, int pad_left, void* stream) {
-    const char* me = "yuv420p10_to_f32";
-    ATMVFI_REQUIRE(yuv, ATMVFI_EINVAL, "yuv420p10_to_f32: null source");
-    ATMVFI_REQUIRE(dst, ATMVFI_EINVAL, "yuv420p10_to_f32: null destination");
-    if (const int rc = check_format(me, H, W, matrix, 0, siting)) return rc;
-    ATMVFI_REQUIRE(h >= 1 && w >= 1, ATMVFI_EINVAL, "yuv420p10_to_f32: the window's h and w must be at least 1 (got %d x %d)", h, w);
-    ATMVFI_REQUIRE(y0 >= 0 && x0 >= 0 && (long long)y0 + h <= H && (long long)x0 + w <= W, ATMVFI_EINVAL,
-                   "yuv420p10_to_f32: window %d x %d at (%d, %d) outside the %d x %d frame", h, w, y0, x0, H, W);
-    ATMVFI_REQUIRE(y0 % 2 == 0 && x0 % 2 == 0, ATMVFI_EINVAL, "yuv420p10_to_f32: the window origin (%d, %d) must be even", y0, x0);
-    if (const int rc = check_canvas(me, "dst", "window", dst, h, w, Hp, Wp, pad_top, pad_left)) return rc;
-    const int groups = groups_of(Wp), pairs = pairs_of(Hp);
-    if (const int rc = check_items(me, pairs, groups, "output of", Hp, Wp)) return rc;
-    const DecArgs a = {make_src(yuv, H, W, 10, matrix, 0, true), y0, x0, h, w, dst, Hp, Wp, pad_top, pad_left, nullptr, 0, groups, pairs};
-    launch_decode(a, 10, true, 0, siting, stream);
-    return atmvfi::check_launch(me);
-}
-
-extern "C" int atmvfi_yuv420_window(const void* yuv, int H, int W, int depth, int matrix, int full_range, int siting, int mode, int y0, int x0,
-                                    int h, int w, float* dst, int Hp, int Wp, int pad_top, int pad_left, void* dst_u8, void* stream) {
-    const char* me = "yuv420_window";
-    ATMVFI_REQUIRE(yuv, ATMVFI_EINVAL, "yuv420_window: null source");
-    ATMVFI_REQUIRE(dst || dst_u8, ATMVFI_EINVAL, "yuv420_window: both outputs are null (give dst, dst_u8 or both)");
-    if (const int rc = check_format(me, H, W, matrix, full_range, siting)) return rc;
-    if (const int rc = check_depth(me, depth, full_range)) return rc;
-    ATMVFI_REQUIRE(mode == 0 || mode == 1, ATMVFI_EINVAL, "yuv420_window: unknown mode %d (0: crop, 1: area 2x)", mode);
-    ATMVFI_REQUIRE(h > 0 && w > 0 && y0 >= 0 && x0 >= 0, ATMVFI_EINVAL, "yuv420_window: negative or zero size (window %d x %d at (%d, %d))", h, w,
-                   y0, x0);
-    const long long s = mode == 1 ? 2 : 1;
-    ATMVFI_REQUIRE(y0 + s * h <= H && x0 + s * w <= W, ATMVFI_EINVAL,
-                   "yuv420_window: window outside the frame (mode %d reads %lld x %lld source pixels at (%d, %d) of a %d x %d frame)", mode,
-                   s * h, s * w, y0, x0, H, W);
-    ATMVFI_REQUIRE(y0 % 2 == 0 && x0 % 2 == 0, ATMVFI_EINVAL, "yuv420_window: the window origin (%d, %d) must be even for 4:2:0 frames", y0, x0);
-    if (dst) {
-        if (const int rc = check_canvas(me, "dst", "window", dst, h, w, Hp, Wp, pad_top, pad_left)) return rc;
-    } else {        // no canvas: the output geometry is the window's
-        Hp = h;
-        Wp = w;
-        pad_top = pad_left = 0;
-    }
-    const int groups = groups_of(Wp), rows = mode == 1 ? Hp : pairs_of(Hp);
-    if (const int rc = check_items(me, rows, groups, "output of", Hp, Wp)) return rc;
-    const DecArgs a = {make_src(yuv, H, W, depth, matrix, full_range, false), y0, x0, h, w, dst, Hp, Wp, pad_top, pad_left, (unsigned char*)dst_u8,
-                       0, groups, rows};
-    launch_decode(a, depth, false, mode, siting, stream);
-    return atmvfi::check_launch(me);
-}
-
-namespace {
-
-// atmvfi_yuv_surface_decode (sub 0) and atmvfi_yuv_sub_decode (sub 1 / 2, checked by the caller: planar, LSB) under the name `me`
+// The one host path of every decode entry point, under the caller's name `me`: the checks in one order, the geometry, the launch.
+// chroma / msb / the three strides describe the surface (all 0: the packed planar frame); sub 1 / 2 is checked by atmvfi_yuv_sub_decode
+// (check_sub); mode 1 (area 2x: the window reads 2h x 2w source pixels, a lane makes one output row) is atmvfi_yuv420_window's and
+// reads packed planar LSB 4:2:0 frames to pixels 0..255; noun names what the canvas holds ("frame" when the window is the whole frame).
 int surface_decode(const char* me, int sub, const void* yuv, int H, int W, int depth, int matrix, int full_range, int siting, int chroma, int msb,
-                   int64_t pitch, int64_t chroma_pitch, int64_t chroma_offset, int keep_depth, int y0, int x0, int h, int w, void* dst_u8, int bgr,
-                   float* dst, int Hp, int Wp, int pad_top, int pad_left, void* stream) {
+                   int64_t pitch, int64_t chroma_pitch, int64_t chroma_offset, int keep_depth, int mode, int y0, int x0, int h, int w, void* dst_u8,
+                   int bgr, float* dst, int Hp, int Wp, int pad_top, int pad_left, void* stream, const char* noun = "window") {
     ATMVFI_REQUIRE(yuv, ATMVFI_EINVAL, "%s: null source", me);
     ATMVFI_REQUIRE(dst || dst_u8, ATMVFI_EINVAL, "%s: both outputs are null (give dst, dst_u8 or both)", me);
     if (const int rc = check_format(me, H, W, matrix, full_range, siting)) return rc;
@@ -384,33 +288,62 @@ int surface_decode(const char* me, int sub, const void* yuv, int H, int W, int d
     ATMVFI_REQUIRE(keep_depth == 0 || keep_depth == 1, ATMVFI_EINVAL, "%s: keep_depth must be 0 or 1 (got %d)", me, keep_depth);
     ATMVFI_REQUIRE(!(keep_depth && depth != 10), ATMVFI_EINVAL, "%s: keep_depth needs a 10-bit surface", me);
     ATMVFI_REQUIRE(!(keep_depth && dst_u8), ATMVFI_EINVAL, "%s: dst_u8 holds 8-bit pixels: not with keep_depth", me);
-    ATMVFI_REQUIRE(h >= 1 && w >= 1, ATMVFI_EINVAL, "%s: the window's h and w must be at least 1 (got %d x %d)", me, h, w);
-    ATMVFI_REQUIRE(y0 >= 0 && x0 >= 0 && (long long)y0 + h <= H && (long long)x0 + w <= W, ATMVFI_EINVAL,
-                   "%s: window %d x %d at (%d, %d) outside the %d x %d frame", me, h, w, y0, x0, H, W);
+    ATMVFI_REQUIRE(mode == 0 || mode == 1, ATMVFI_EINVAL, "%s: unknown mode %d (0: crop, 1: area 2x)", me, mode);
+    ATMVFI_REQUIRE(mode == 0 || (sub == 0 && chroma == 0 && !msb && !pitch && !chroma_pitch && !chroma_offset && !keep_depth), ATMVFI_EINVAL,
+                   "%s: mode 1 reads packed planar 4:2:0 frames with LSB samples, to pixels 0..255", me);
+    ATMVFI_REQUIRE(h >= 1 && w >= 1, ATMVFI_EINVAL, "%s: negative or zero size: the window's h and w must be at least 1 (got %d x %d)", me, h, w);
+    // (the wording serves two contracts: yuv420_window's callers match "negative or zero" for a negative origin, the other calls' "outside the")
+    ATMVFI_REQUIRE(y0 >= 0 && x0 >= 0, ATMVFI_EINVAL,
+                   "%s: the window's origin (%d, %d) is negative, outside the frame (refused like a negative or zero size)", me, y0, x0);
+    const long long s = mode == 1 ? 2 : 1;
+    ATMVFI_REQUIRE(y0 + s * h <= H && x0 + s * w <= W, ATMVFI_EINVAL,
+                   "%s: window outside the frame (mode %d reads %lld x %lld source pixels at (%d, %d) of a %d x %d frame)", me, mode, s * h, s * w,
+                   y0, x0, H, W);
     if (sub == 0) ATMVFI_REQUIRE(y0 % 2 == 0 && x0 % 2 == 0, ATMVFI_EINVAL, "%s: the window origin (%d, %d) must be even", me, y0, x0);
     if (sub == 1) ATMVFI_REQUIRE(x0 % 2 == 0, ATMVFI_EINVAL, "%s: the window origin (%d, %d) must have an even x0 for 4:2:2 frames", me, y0, x0);
     if (dst) {
-        if (const int rc = check_canvas(me, "dst", "window", dst, h, w, Hp, Wp, pad_top, pad_left)) return rc;
+        if (const int rc = check_canvas(me, "dst", noun, dst, h, w, Hp, Wp, pad_top, pad_left)) return rc;
     } else {        // no canvas: the output geometry is the window's
         Hp = h;
         Wp = w;
         pad_top = pad_left = 0;
     }
-    const int groups = groups_of(Wp), pairs = pairs_of(Hp);
-    if (const int rc = check_items(me, pairs, groups, "output of", Hp, Wp)) return rc;
+    const int groups = groups_of(Wp), rows = mode == 1 ? Hp : pairs_of(Hp);
+    if (const int rc = check_items(me, rows, groups, "output of", Hp, Wp)) return rc;
     const DecArgs a = {make_src(yuv, H, W, depth, matrix, full_range, keep_depth != 0, l, sub), y0, x0, h, w, dst, Hp, Wp, pad_top, pad_left,
-                       (unsigned char*)dst_u8, bgr ? 1 : 0, groups, pairs};
-    launch_decode(a, depth, keep_depth != 0, 0, siting, stream, chroma != 0, msb != 0, sub);
+                       (unsigned char*)dst_u8, bgr ? 1 : 0, groups, rows};
+    launch_decode(a, depth, keep_depth != 0, mode, siting, stream, chroma != 0, msb != 0, sub);
     return atmvfi::check_launch(me);
 }
 
 }  // namespace
 
+// The three calls on packed planar frames are the surface call with chroma 0, msb 0 and no strides, under their own names.
+
+extern "C" int atmvfi_yuv420_to_rgb(const void* yuv, int H, int W, int depth, int matrix, int full_range, int siting, void* dst_u8, int bgr,
+                                    float* dst, int Hp, int Wp, int pad_top, int pad_left, void* stream) {
+    return surface_decode("yuv420_to_rgb", 0, yuv, H, W, depth, matrix, full_range, siting, 0, 0, 0, 0, 0, 0, 0, 0, 0, H, W, dst_u8, bgr, dst, Hp, Wp,
+                          pad_top, pad_left, stream, "frame");
+}
+
+extern "C" int atmvfi_yuv420p10_to_f32(const void* yuv, int H, int W, int matrix, int siting, int y0, int x0, int h, int w, float* dst,
+                                       int Hp, int Wp, int pad_top, int pad_left, void* stream) {
+    ATMVFI_REQUIRE(!yuv || dst, ATMVFI_EINVAL, "yuv420p10_to_f32: null destination");        // (one output: not "both outputs are null")
+    return surface_decode("yuv420p10_to_f32", 0, yuv, H, W, 10, matrix, 0, siting, 0, 0, 0, 0, 0, 1, 0, y0, x0, h, w, nullptr, 0, dst, Hp, Wp, pad_top,
+                          pad_left, stream);
+}
+
+extern "C" int atmvfi_yuv420_window(const void* yuv, int H, int W, int depth, int matrix, int full_range, int siting, int mode, int y0, int x0,
+                                    int h, int w, float* dst, int Hp, int Wp, int pad_top, int pad_left, void* dst_u8, void* stream) {
+    return surface_decode("yuv420_window", 0, yuv, H, W, depth, matrix, full_range, siting, 0, 0, 0, 0, 0, 0, mode, y0, x0, h, w, dst_u8, 0, dst, Hp, Wp,
+                          pad_top, pad_left, stream);
+}
+
 extern "C" int atmvfi_yuv_surface_decode(const void* yuv, int H, int W, int depth, int matrix, int full_range, int siting, int chroma, int msb,
                                          int64_t pitch, int64_t chroma_pitch, int64_t chroma_offset, int keep_depth, int y0, int x0, int h, int w,
                                          void* dst_u8, int bgr, float* dst, int Hp, int Wp, int pad_top, int pad_left, void* stream) {
     return surface_decode("yuv_surface_decode", 0, yuv, H, W, depth, matrix, full_range, siting, chroma, msb, pitch, chroma_pitch, chroma_offset,
-                          keep_depth, y0, x0, h, w, dst_u8, bgr, dst, Hp, Wp, pad_top, pad_left, stream);
+                          keep_depth, 0, y0, x0, h, w, dst_u8, bgr, dst, Hp, Wp, pad_top, pad_left, stream);
 }
 
 extern "C" int atmvfi_yuv_sub_decode(const void* yuv, int H, int W, int depth, int matrix, int full_range, int siting, int subsampling, int chroma,
@@ -421,5 +354,5 @@ extern "C" int atmvfi_yuv_sub_decode(const void* yuv, int H, int W, int depth, i
                                          x0, h, w, dst_u8, bgr, dst, Hp, Wp, pad_top, pad_left, stream);
     if (const int rc = check_sub("yuv_sub_decode", subsampling, siting, chroma, msb)) return rc;
     return surface_decode("yuv_sub_decode", subsampling, yuv, H, W, depth, matrix, full_range, siting, chroma, msb, pitch, chroma_pitch,
-                          chroma_offset, keep_depth, y0, x0, h, w, dst_u8, bgr, dst, Hp, Wp, pad_top, pad_left, stream);
+                          chroma_offset, keep_depth, 0, y0, x0, h, w, dst_u8, bgr, dst, Hp, Wp, pad_top, pad_left, stream);
 }

@@ -7,9 +7,9 @@
 // every kernel runs the functions below, so two entry points that decode the same pixel give the same bits by construction.
 //   frame     Y [H,W], U [ch,cw], V [ch,cw] back to back, ch = (H + 1) / 2, cw = (W + 1) / 2; uint8, or little-endian uint16 (0..1023)
 //             for depth 10
-//   pixel     8 bit (Px8): RGB 0..255 (top = 255), yo = 16 (limited) or 0 (full range), mid = 128, T = 14; fp32 is q / 255
-//             10 -> 8 bit (Px10to8): 10-bit limited-range samples to RGB 0..255 (decode only): yo = 64, mid = 512, T = 16, the 8-bit matrix
-//             10 bit kept (Px10): RGB 0..1023 (top = 1023), yo = 64, mid = 512, T = 14, the matrix of kCoeffs10; fp32 is q / 1023
+//   pixel     8 bit (Pixel<8, 255>): RGB 0..255 (top = 255), yo = 16 (limited) or 0 (full range), mid = 128, T = 14; fp32 is q / 255
+//             10 -> 8 bit (Pixel<10, 255>): 10-bit limited-range samples to RGB 0..255 (decode only): yo = 64, mid = 512, T = 16, the 8-bit matrix
+//             10 bit kept (Pixel<10, 1023>): RGB 0..1023 (top = 1023), yo = 64, mid = 512, T = 14, the matrix of kCoeffs10; fp32 is q / 1023
 //   decode    chroma of luma pixel (y, x): rows r0 = y >> 1 and r1 = clamp(r0 + (y & 1 ? 1 : -1)) with weights (3, 1); columns
 //             centre-sited q0 = x >> 1, q1 = clamp(q0 + (x & 1 ? 1 : -1)), weights (3, 1); left-sited q0, q1 = min(q0 + 1, cw - 1),
 //             weights (4, 0) for even and (2, 2) for odd x; c' = (wy0 (wx0 c00 + wx1 c01) + wy1 (wx0 c10 + wx1 c11) + 8) >> 4;
@@ -99,9 +99,9 @@ struct Pixel {
     static_assert((DEPTH == 8 || DEPTH == 10) && (TOP == 255 || (TOP == 1023 && DEPTH == 10)), "8 bit, 10 -> 8 bit or 10 bit kept");
     static_assert(!MSB || DEPTH == 10, "only 10-bit samples are stored in the upper bits");
 };
-using Px8 = Pixel<8, 255>;
-using Px10to8 = Pixel<10, 255>;
-using Px10 = Pixel<10, 1023>;
+// the decode instances that exist (launch_decode walks the whole family and compiles these): Pixel's own conditions, and 4:4:4 has no siting
+template <int DEPTH, int TOP, bool IL, bool MSB, int SUB, bool LEFT>
+constexpr bool decode_instance = (TOP == 255 || DEPTH == 10) && (!MSB || DEPTH == 10) && (SUB == 0 || (!IL && !MSB)) && !(SUB == 2 && LEFT);
 
 // the layout of a surface, on the host: chroma 0 planar, 1 interleaved U first, 2 interleaved V first; strides in samples, uoff the
 // first chroma row's first sample.  A packed I420 frame is tight_layout(H, W, 0).
@@ -125,9 +125,6 @@ inline YuvSrc make_src(const void* yuv, int H, int W, int depth, int matrix, int
     return YuvSrc{(const unsigned char*)yuv, H, W, ch, cw, uoff, voff, l.ys, l.cs, l.chroma == 2 ? 1 : 0,
                   c.dec[0], c.dec[1], c.dec[2], c.dec[3], c.dec[4], depth == 10 ? 64 : (full_range ? 0 : 16), depth == 10 ? 512 : 128,
                   depth == 10 && !keep ? 16 : 14};
-}
-inline YuvSrc make_src(const void* yuv, int H, int W, int depth, int matrix, int full_range, bool keep) {
-    return make_src(yuv, H, W, depth, matrix, full_range, keep, tight_layout(H, W, 0));
 }
 
 // the value of a stored 16-bit sample: its upper ten bits for MSB
@@ -316,7 +313,8 @@ __device__ __forceinline__ void decode4(const YuvSrc& a, int fy, int gx, const i
 }
 
 // -------------------------------------------------------------------------------------------------------------------- host: checks
-// Every entry point passes its own name as the message prefix and keeps its own order of checks; none of these launches anything.
+// Every entry point passes its own name as the message prefix; the order of the checks is the one of surface_decode (yuv.hip) and
+// surface_encode (yuv_encode.hip), which every entry point of its direction runs.  None of these launches anything.
 int check_format(const char* what, int H, int W, int matrix, int full_range, int siting) {
     ATMVFI_REQUIRE(H >= 1 && W >= 1, ATMVFI_EINVAL, "%s: H and W must be at least 1 (got %d x %d)", what, H, W);
     ATMVFI_REQUIRE(matrix == 0 || matrix == 1, ATMVFI_EINVAL, "%s: unknown matrix %d (0: bt601, 1: bt709)", what, matrix);
@@ -402,20 +400,23 @@ inline dim3 yuv_grid(long long items) {
     return dim3((unsigned)(blocks > 16384 ? 16384 : blocks));
 }
 
-// run-time switches -> template parameters of a launch: f(std::bool_constant<b0>{}, ...).  The siting is always one of them: the tap
-// indices and weights of the chroma filter are constants of the instance.
+// run-time switches -> template parameters of a launch: dispatch(f, b0, b1, ...) calls f(std::bool_constant<b0>{}, ...).  The siting is
+// always one of them: the tap indices and weights of the chroma filter are constants of the instance.
 template <class F>
-void with_bool(bool b, F&& f) {
-    if (b) f(std::true_type{});
-    else f(std::false_type{});
+void dispatch(F&& f) {
+    f();
 }
-template <class F>
-void dispatch(bool b0, bool b1, F&& f) {
-    with_bool(b0, [&](auto c0) { with_bool(b1, [&](auto c1) { f(c0, c1); }); });
+template <class F, class... B>
+void dispatch(F&& f, bool b, B... rest) {
+    if (b) dispatch([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+    else dispatch([&](auto... c) { f(std::false_type{}, c...); }, rest...);
 }
-template <class F>
-void dispatch(bool b0, bool b1, bool b2, F&& f) {
-    with_bool(b0, [&](auto c0) { dispatch(b1, b2, [&](auto c1, auto c2) { f(c0, c1, c2); }); });
+// the same with the subsampling (0, 1, 2: check_sub) as the first constant, an int
+template <class F, class... B>
+void dispatch_sub(F&& f, int sub, B... b) {
+    if (sub == 0) dispatch([&](auto... c) { f(std::integral_constant<int, 0>{}, c...); }, b...);
+    else if (sub == 1) dispatch([&](auto... c) { f(std::integral_constant<int, 1>{}, c...); }, b...);
+    else dispatch([&](auto... c) { f(std::integral_constant<int, 2>{}, c...); }, b...);
 }
 
 }  // namespace

@@ -1,5 +1,5 @@
-// RGB -> YUV 4:2:0 (and planar 4:2:2 / 4:4:4): the four encode entry points of include/atmvfi.h on one kernel.  yuv_common.h holds the definition and
-// the shared helpers; yuv.hip is the other direction.
+// RGB -> YUV 4:2:0 (and planar 4:2:2 / 4:4:4): the four encode entry points of include/atmvfi.h on one kernel and one checked host path
+// (surface_encode, below the kernel).  yuv_common.h holds the definition and the shared helpers; yuv.hip is the other direction.
 //   atmvfi_rgb_to_yuv420      uint8 [H,W,3] (RGB or BGR) or the fp32 canvas in units of 1 / 255 -> 8-bit samples
 //   atmvfi_f32_to_yuv420p10   the fp32 canvas in units of 1 / 1023 -> 10-bit samples, the depth kept
 //   atmvfi_yuv_surface_encode either of the two into a tight surface: planar, or NV12 / NV21 / P010 (interleaved chroma, msb samples);
@@ -212,14 +212,18 @@ __global__ __launch_bounds__(256) void yuv420_encode_kernel(const EncArgs a) {
     }
 }
 
+// the encode instances that exist (launch_encode walks the whole family and compiles these): as decode_instance
+template <int SRC, bool IL, bool MSB, int SUB, bool LEFT>
+constexpr bool encode_instance = (!MSB || SRC == SRC_F1023) && (SUB == 0 || (!IL && !MSB)) && !(SUB == 2 && LEFT);
+
 // Launches the encode of a checked frame; exactly one of src_u8 and src is given.  The destination is tight: chroma 0 is the packed
-// I420 frame, 1 / 2 the interleaved surface (U / V first); msb: 10-bit samples stored in the upper bits
-// (sub: 1 4:2:2, 2 4:4:4 -- planar, LSB)
-template <int SRC>
-void launch_encode(const Coeffs& c, int yo, const void* src_u8, int bgr, const float* src, int Hp, int Wp, int pad_top, int pad_left, int H,
-                   int W, int siting, void* yuv, void* stream, int chroma = 0, bool msb = false, int sub = 0) {
+// planar frame, 1 / 2 the interleaved surface (U / V first); msb: 10-bit samples stored in the upper bits; sub: 1 4:2:2, 2 4:4:4.
+// The run-time properties select the instance in this one place: the source is fp32 x 1023 at depth 10, else fp32 x 255 or uint8;
+// msb samples come from the 10-bit source alone, 4:2:2 / 4:4:4 are planar LSB, and 4:4:4 has no siting.
+void launch_encode(const Coeffs& c, int yo, int depth, const void* src_u8, int bgr, const float* src, int Hp, int Wp, int pad_top, int pad_left,
+                   int H, int W, int siting, void* yuv, void* stream, int chroma, bool msb, int sub) {
     const int ch = chroma_rows(H, sub), cw = chroma_cols(W, sub), groups = groups_of(W);
-    EncArgs a = {(const unsigned char*)src_u8, bgr ? 1 : 0, src, Hp, Wp, pad_top, pad_left, H, W, ch, cw};
+    EncArgs a = {(const unsigned char*)src_u8, src_u8 && bgr ? 1 : 0, src, Hp, Wp, pad_top, pad_left, H, W, ch, cw};
     for (int k = 0; k < 3; ++k) {
         a.eY[k] = c.enc[0][k];
         a.eU[k] = c.enc[1][k];
@@ -236,65 +240,15 @@ void launch_encode(const Coeffs& c, int yo, const void* src_u8, int bgr, const f
     a.groups = groups;
     const bool al = aligned4(yuv) && W % 4 == 0 && (src ? canvas_aligned(src, Wp, pad_left) : aligned4(src_u8));      // (tight: the layout follows)
     const dim3 grid = yuv_grid((long long)pairs_of(H) * groups), block(256);
-    if (sub) {              // the instances of atmvfi_yuv_sub_encode: three sources x two paths x (4:2:2 x two sitings + 4:4:4)
-        dispatch(al, sub == 1 && siting, sub == 2, [&](auto AL, auto LEFT, auto S444) {
-            constexpr int SUB = decltype(S444)::value ? 2 : 1;
-            if constexpr (!(SUB == 2 && decltype(LEFT)::value))
-                hipLaunchKernelGGL((yuv420_encode_kernel<SRC, decltype(AL)::value, decltype(LEFT)::value, false, false, SUB>), grid, block, 0,
-                                   (hipStream_t)stream, a);
-        });
-        return;
-    }
-    if (chroma || msb) {        // the instances of atmvfi_yuv_surface_encode that the planar, LSB calls do not have
-        dispatch(al, siting, [&](auto AL, auto LEFT) {
-            dispatch(chroma != 0, msb, [&](auto IL_, auto MSB_) {
-                constexpr bool IL = decltype(IL_)::value, M = decltype(MSB_)::value && SRC == SRC_F1023;
-                if constexpr (IL || M)
-                    hipLaunchKernelGGL((yuv420_encode_kernel<SRC, decltype(AL)::value, decltype(LEFT)::value, IL, M>), grid, block, 0,
-                                       (hipStream_t)stream, a);
-            });
-        });
-        return;
-    }
-    dispatch(al, siting, [&](auto AL, auto LEFT) {
-        hipLaunchKernelGGL((yuv420_encode_kernel<SRC, decltype(AL)::value, decltype(LEFT)::value>), grid, block, 0, (hipStream_t)stream, a);
-    });
+    dispatch_sub([&](auto SUB, auto AL, auto LEFT, auto D10, auto F32, auto IL, auto MSB) {
+        constexpr int SRC = D10() ? SRC_F1023 : (F32() ? SRC_F255 : SRC_U8);
+        if constexpr ((F32() || !D10()) && encode_instance<SRC, IL(), MSB(), SUB(), LEFT()>)
+            hipLaunchKernelGGL((yuv420_encode_kernel<SRC, AL(), LEFT(), IL(), MSB(), SUB()>), grid, block, 0, (hipStream_t)stream, a);
+    }, sub, al, siting != 0, depth == 10, src != nullptr, chroma != 0, msb);
 }
 
-}  // namespace
-
-extern "C" int atmvfi_rgb_to_yuv420(const void* src_u8, int bgr, const float* src, int Hp, int Wp, int pad_top, int pad_left, int H, int W,
-                                    int matrix, int full_range, int siting, void* yuv, void* stream) {
-    const char* me = "rgb_to_yuv420";
-    ATMVFI_REQUIRE(yuv, ATMVFI_EINVAL, "rgb_to_yuv420: null destination");
-    ATMVFI_REQUIRE((src_u8 != nullptr) != (src != nullptr), ATMVFI_EINVAL,
-                   "rgb_to_yuv420: give exactly one of src_u8 and src (got %s)", src_u8 ? "both" : "neither");
-    if (const int rc = check_format(me, H, W, matrix, full_range, siting)) return rc;
-    if (src)
-        if (const int rc = check_canvas(me, "src", "frame", src, H, W, Hp, Wp, pad_top, pad_left)) return rc;
-    if (const int rc = check_items(me, (H + 1) / 2, groups_of(W), "a frame of", H, W)) return rc;
-    const Coeffs& c = kCoeffs[matrix][full_range];
-    const int yo = full_range ? 0 : 16;
-    if (src) launch_encode<SRC_F255>(c, yo, nullptr, 0, src, Hp, Wp, pad_top, pad_left, H, W, siting, yuv, stream);
-    else launch_encode<SRC_U8>(c, yo, src_u8, bgr, nullptr, Hp, Wp, pad_top, pad_left, H, W, siting, yuv, stream);
-    return atmvfi::check_launch(me);
-}
-
-extern "C" int atmvfi_f32_to_yuv420p10(const float* src, int Hp, int Wp, int pad_top, int pad_left, int H, int W, int matrix, int siting,
-                                       void* yuv, void* stream) {
-    const char* me = "f32_to_yuv420p10";
-    ATMVFI_REQUIRE(src, ATMVFI_EINVAL, "f32_to_yuv420p10: null source");
-    ATMVFI_REQUIRE(yuv, ATMVFI_EINVAL, "f32_to_yuv420p10: null destination");
-    if (const int rc = check_format(me, H, W, matrix, 0, siting)) return rc;
-    if (const int rc = check_canvas(me, "src", "frame", src, H, W, Hp, Wp, pad_top, pad_left)) return rc;
-    if (const int rc = check_items(me, (H + 1) / 2, groups_of(W), "a frame of", H, W)) return rc;
-    launch_encode<SRC_F1023>(kCoeffs10[matrix], 64, nullptr, 0, src, Hp, Wp, pad_top, pad_left, H, W, siting, yuv, stream);
-    return atmvfi::check_launch(me);
-}
-
-namespace {
-
-// atmvfi_yuv_surface_encode (sub 0) and atmvfi_yuv_sub_encode (sub 1 / 2, checked by the caller: planar, LSB) under the name `me`
+// The one host path of every encode entry point, under the caller's name `me`: the checks in one order, then the launch.  chroma / msb
+// describe the tight destination (both 0: the packed planar frame); sub 1 / 2 is checked by atmvfi_yuv_sub_encode (check_sub).
 int surface_encode(const char* me, int sub, const void* src_u8, int bgr, const float* src, int Hp, int Wp, int pad_top, int pad_left, int H, int W,
                    int depth, int matrix, int full_range, int siting, int chroma, int msb, void* yuv, void* stream) {
     ATMVFI_REQUIRE(yuv, ATMVFI_EINVAL, "%s: null destination", me);
@@ -308,18 +262,24 @@ int surface_encode(const char* me, int sub, const void* src_u8, int bgr, const f
     if (src)
         if (const int rc = check_canvas(me, "src", "frame", src, H, W, Hp, Wp, pad_top, pad_left)) return rc;
     if (const int rc = check_items(me, (H + 1) / 2, groups_of(W), "a frame of", H, W)) return rc;
-    if (depth == 10) {
-        launch_encode<SRC_F1023>(kCoeffs10[matrix], 64, nullptr, 0, src, Hp, Wp, pad_top, pad_left, H, W, siting, yuv, stream, chroma, msb != 0, sub);
-    } else {
-        const Coeffs& c = kCoeffs[matrix][full_range];
-        const int yo = full_range ? 0 : 16;
-        if (src) launch_encode<SRC_F255>(c, yo, nullptr, 0, src, Hp, Wp, pad_top, pad_left, H, W, siting, yuv, stream, chroma, false, sub);
-        else launch_encode<SRC_U8>(c, yo, src_u8, bgr, nullptr, Hp, Wp, pad_top, pad_left, H, W, siting, yuv, stream, chroma, false, sub);
-    }
+    launch_encode(depth == 10 ? kCoeffs10[matrix] : kCoeffs[matrix][full_range], depth == 10 ? 64 : (full_range ? 0 : 16), depth, src_u8, bgr, src, Hp,
+                  Wp, pad_top, pad_left, H, W, siting, yuv, stream, chroma, msb != 0, sub);
     return atmvfi::check_launch(me);
 }
 
 }  // namespace
+
+// The two calls on packed planar frames are the surface call with chroma 0 and msb 0, under their own names.
+extern "C" int atmvfi_rgb_to_yuv420(const void* src_u8, int bgr, const float* src, int Hp, int Wp, int pad_top, int pad_left, int H, int W,
+                                    int matrix, int full_range, int siting, void* yuv, void* stream) {
+    return surface_encode("rgb_to_yuv420", 0, src_u8, bgr, src, Hp, Wp, pad_top, pad_left, H, W, 8, matrix, full_range, siting, 0, 0, yuv, stream);
+}
+
+extern "C" int atmvfi_f32_to_yuv420p10(const float* src, int Hp, int Wp, int pad_top, int pad_left, int H, int W, int matrix, int siting,
+                                       void* yuv, void* stream) {
+    ATMVFI_REQUIRE(src, ATMVFI_EINVAL, "f32_to_yuv420p10: null source");        // (one source: not "exactly one of src_u8 and src")
+    return surface_encode("f32_to_yuv420p10", 0, nullptr, 0, src, Hp, Wp, pad_top, pad_left, H, W, 10, matrix, 0, siting, 0, 0, yuv, stream);
+}
 
 extern "C" int atmvfi_yuv_surface_encode(const void* src_u8, int bgr, const float* src, int Hp, int Wp, int pad_top, int pad_left, int H, int W,
                                          int depth, int matrix, int full_range, int siting, int chroma, int msb, void* yuv, void* stream) {

@@ -19,6 +19,8 @@ from typing import List, Optional
 
 import torch
 
+from .pixfmt import Surface, _not_420, _origin_error, as_surface
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libatmvfi_hip.so")
 CHECKED_LIB_PATH = os.path.join(_HERE, "libatmvfi_hip_checked.so")     # the same sources with -DATMVFI_RANGE_CHECK (csrc/Makefile)
@@ -328,52 +330,41 @@ def _planar(t: torch.Tensor, c: int, what: str):
 
 def _is_u8_frame(t, hw=None) -> bool:
     return (isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and t.dim() == 3 and t.shape[2] == 3 and t.is_contiguous() and t.is_cuda
-            and (hw is None or tuple(t.shape[:2]) == tuple(hw)))
+            and (hw is None or t.shape[:2] == tuple(hw)))
 
 
-def _u8_frame(t, what: str, hw=None):
-    """``t`` is a packed uint8 frame [H,W,3] on the device (of exactly ``hw`` = (h, w) when given), or ``ValueError``."""
+def _u8_frame(t, what: str, hw=None, which: str = ""):
+    """``t`` is a packed uint8 frame [H,W,3] on the device (of exactly ``hw`` = (h, w) when given), or ``ValueError`` naming it
+    ``what + which``."""
     if not _is_u8_frame(t, hw):
-        raise ValueError(f"{what} must be a contiguous CUDA uint8 [{'H,W' if hw is None else f'{hw[0]},{hw[1]}'},3] tensor")
+        raise ValueError(f"{what}{which} must be a contiguous CUDA uint8 [{'H,W' if hw is None else f'{hw[0]},{hw[1]}'},3] tensor")
 
 
-def _f32_canvas(t, what: str):
-    """``t`` is a planar fp32 frame [3,Hp,Wp] on the device, or ``ValueError``."""
+def _f32_canvas(t, what: str, which: str = ""):
+    """``t`` is a planar fp32 frame [3,Hp,Wp] on the device, or ``ValueError`` naming it ``what + which``."""
     if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 3 or t.shape[0] != 3 or not t.is_contiguous() or not t.is_cuda:
-        raise ValueError(f"{what} must be a contiguous CUDA fp32 [3,Hp,Wp] tensor")
+        raise ValueError(f"{what}{which} must be a contiguous CUDA fp32 [3,Hp,Wp] tensor")
 
 
-def _i420(t, fmt, what: str, kind: str = "I420"):
-    """``t`` is one packed planar frame of ``fmt`` (a ``yuv.Format``) as bytes on the device, or ``ValueError``."""
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1 or t.numel() != fmt.frame_bytes or not t.is_contiguous() \
-            or not t.is_cuda:
-        raise ValueError(f"{what} must be a contiguous CUDA uint8 tensor of {fmt.frame_bytes} bytes ({fmt.height} x {fmt.width} {kind})")
+def _yuv_buf(t, desc, who: str, role: str):
+    """``t`` is one frame of ``desc`` (a ``pixfmt.Format`` or ``Surface``) as bytes on the device, or ``ValueError``.  -> its byte count"""
+    n = desc.frame_bytes
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1 or t.numel() != n or not t.is_contiguous() or not t.is_cuda:
+        layout = f"{desc.chroma} surface, pitch {desc.pitch}" if isinstance(desc, Surface) else "packed planar"
+        raise ValueError(f"{who}: {role} buf must be a contiguous CUDA uint8 tensor of {n} bytes ({desc.height} x {desc.width} "
+                         f"{desc.subsampling}, depth {desc.depth}, {layout})")
+    return n
 
 
-def _only_420(fmt, what: str):
-    """The 4:2:0 entry points would misread the planes of a 4:2:2 / 4:4:4 frame: ``ValueError`` naming the subsampling."""
-    sub = getattr(fmt, "subsampling", "420")
-    if sub != "420":
-        raise ValueError(f"{what}: 4:2:0 frames only (got subsampling {sub}; yuv_sub_decode / yuv_sub_encode take 4:2:2 and 4:4:4)")
+def _window(who: str, desc, window):
+    """``window`` (y0, x0, h, w) of a frame of ``desc`` as ints, or ``ValueError`` where it does not lie in the frame."""
+    y0, x0, wh, ww = map(int, window)
+    if y0 < 0 or x0 < 0 or wh < 1 or ww < 1 or y0 + wh > desc.height or x0 + ww > desc.width:
+        raise ValueError(f"{who}: window {wh} x {ww} at ({y0}, {x0}) outside the {desc.height} x {desc.width} frame")
+    return y0, x0, wh, ww
 
 
-_SURFACE = []
-
-
-def _surface_class():
-    """``yuv.Surface`` (imported on first use: yuv.py imports the loops, which import this module)"""
-    if not _SURFACE:
-        from .yuv import Surface
-        _SURFACE.append(Surface)
-    return _SURFACE[0]
-
-
-def _surface(t, surface, what: str):
-    """``t`` is one frame of ``surface`` (a ``yuv.Surface``) as bytes on the device, or ``ValueError``."""
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1 or t.numel() != surface.nbytes or not t.is_contiguous() \
-            or not t.is_cuda:
-        raise ValueError(f"{what} must be a contiguous CUDA uint8 tensor of {surface.nbytes} bytes ({surface.height} x {surface.width} "
-                         f"{surface.chroma} surface, depth {surface.depth}, pitch {surface.pitch})")
+_SAMPLES_PER_PIXEL = {"420": 1.5, "422": 2.0, "444": 3.0}          # 1 + 2 / (sy * sx) of the subsampling steps
 
 
 class PlanUnsupported(Exception):
@@ -1442,21 +1433,66 @@ class HipOps:
         self._check(self.lib.atmvfi_shutter_table(LIGHTS.index(light), out), "shutter_table")
         return tuple(out)
 
+    # The YUV wrappers: one validator per direction, which also accounts meta["bytes"]; a wrapper adds the refusals that are its own and
+    # launches its entry point with the canvas the validator returns (the window is the wrapper's: the frame, or a caller's through
+    # ``_window``).  ``desc`` is a pixfmt.Format or Surface (they answer to the same names).  Both run on every frame of a video loop
+    # at every size, so they stay flat: positional arguments, nothing computed that a refusal alone needs.
+    def _yuv_decode_args(self, name, buf, desc, dst_u8, dst, y0, x0, wh, ww, pad_top, pad_left, keep=False, area=1, lib_geometry=False):
+        """-> (hp, wp, meta): the canvas and ``meta`` for ``_run`` of a decode of the window ``wh`` x ``ww`` at (y0, x0), in output pixels
+        (ints; ``_window`` has held a caller's to the frame), which reads ``area`` source pixels each.  ``lib_geometry``: whether the
+        canvas holds the window is left to the library (``RuntimeError``; yuv420_to_rgb and yuv420_window), else refused here
+        (``ValueError``)."""
+        _yuv_buf(buf, desc, name, "source")
+        if dst is None and dst_u8 is None:
+            raise ValueError(f"{name}: give dst, dst_u8 or both")
+        if keep:
+            if desc.depth != 10:
+                raise ValueError(f"{name}: keep_depth needs a 10-bit surface")
+            if dst_u8 is not None:
+                raise ValueError(f"{name}: dst_u8 holds 8-bit pixels: not with keep_depth")
+        if (y0 | x0) & 1:       # (only an odd coordinate can break the origin rule of a subsampling)
+            err = _origin_error(name, desc, y0, x0)
+            if err is not None:
+                raise err
+        nbytes = _SAMPLES_PER_PIXEL[desc.subsampling] * (2 if desc.depth == 10 else 1) * area * wh * ww
+        if dst is None:
+            hp, wp = wh, ww
+        else:
+            _f32_canvas(dst, name, ": dst")
+            _, hp, wp = dst.shape
+            if not lib_geometry and (pad_top < 0 or pad_left < 0 or wh + pad_top > hp or ww + pad_left > wp):
+                raise ValueError(f"{name}: canvas {hp} x {wp} is smaller than the window {wh} x {ww} plus padding ({pad_top}, {pad_left})")
+            nbytes += 12.0 * hp * wp
+        if dst_u8 is not None:
+            _u8_frame(dst_u8, name, (wh, ww), ": dst_u8")
+            nbytes += 3.0 * wh * ww
+        return hp, wp, {"bytes": nbytes}
+
+    def _yuv_encode_args(self, name, buf, desc, src_u8, src, pad_top, pad_left):
+        """-> (h, w, hp, wp, meta): the frame's size, the source's and ``meta`` for ``_run``; the destination is the tight frame of ``desc``."""
+        h, w = desc.height, desc.width
+        n = _yuv_buf(buf, desc, name, "destination")
+        if (src is None) == (src_u8 is None):
+            raise ValueError(f"{name}: give exactly one of src_u8 and src")
+        if src is not None:
+            _f32_canvas(src, name, ": src")
+            _, hp, wp = src.shape
+            if pad_top < 0 or pad_left < 0 or h + pad_top > hp or w + pad_left > wp:
+                raise ValueError(f"{name}: canvas {hp} x {wp} is smaller than the frame {h} x {w} plus padding ({pad_top}, {pad_left})")
+            return h, w, hp, wp, {"bytes": n + 12.0 * h * w}
+        if desc.depth != 8:
+            raise ValueError(f"{name}: src_u8 encodes 8-bit surfaces only (a 10-bit surface takes the fp32 src)")
+        _u8_frame(src_u8, name, (h, w), ": src_u8")
+        return h, w, h, w, {"bytes": n + 3.0 * h * w}
+
     def yuv420_to_rgb(self, yuv, fmt, dst_u8=None, dst=None, pad_top: int = 0, pad_left: int = 0, bgr: bool = False):
         """One packed planar I420 frame of ``fmt`` (a ``yuv.Format``; a contiguous CUDA uint8 tensor of ``fmt.frame_bytes`` bytes, any
         alignment) -> ``dst_u8`` uint8 [H,W,3] (BGR if ``bgr``) and / or ``dst`` fp32 planar RGB [3,Hp,Wp] = q / 255 with replicate
         padding, the frame at (pad_top, pad_left) (include/atmvfi.h atmvfi_yuv420_to_rgb; the bits of ``yuv.decode_numpy``)."""
-        _only_420(fmt, "yuv420_to_rgb")
+        if fmt.subsampling != "420":
+            raise _not_420("yuv420_to_rgb", fmt)
         h, w = fmt.height, fmt.width
-        _i420(yuv, fmt, "yuv420_to_rgb: source")
-        if dst is None and dst_u8 is None:
-            raise ValueError("yuv420_to_rgb: give dst, dst_u8 or both")
-        if dst is not None:
-            _f32_canvas(dst, "yuv420_to_rgb: dst")
-        if dst_u8 is not None:
-            _u8_frame(dst_u8, "yuv420_to_rgb: dst_u8", (h, w))
-        hp, wp = (dst.shape[1], dst.shape[2]) if dst is not None else (h, w)
-        meta = {"bytes": float(fmt.frame_bytes) + (12.0 * hp * wp if dst is not None else 0.0) + (3.0 * h * w if dst_u8 is not None else 0.0)}
+        hp, wp, meta = self._yuv_decode_args("yuv420_to_rgb", yuv, fmt, dst_u8, dst, 0, 0, h, w, pad_top, pad_left, False, 1, True)
         self._run("yuv420_to_rgb", meta, self.lib.atmvfi_yuv420_to_rgb, _ptr(yuv), h, w, int(fmt.depth), fmt.matrix_id, int(fmt.full_range),
                   fmt.siting_id, _ptr(dst_u8), int(bool(bgr)), _ptr(dst), hp, wp, int(pad_top), int(pad_left), self._stream())
 
@@ -1466,42 +1502,23 @@ class HipOps:
         that frame's RGB decode, in one launch and without the RGB frame: ``dst`` fp32 planar [3,Hp,Wp] (q / 255, replicate padding, the
         window at (pad_top, pad_left)) and / or ``dst_u8`` uint8 [h,w,3] RGB.  The origin must be even (include/atmvfi.h
         atmvfi_yuv420_window; the bits of ``yuv.window_numpy``)."""
-        _only_420(fmt, "yuv420_window")
-        fh, fw = fmt.height, fmt.width
-        _i420(yuv, fmt, "yuv420_window: source")
-        if dst is None and dst_u8 is None:
-            raise ValueError("yuv420_window: give dst, dst_u8 or both")
-        if int(y0) % 2 or int(x0) % 2:
-            raise ValueError(f"yuv420_window: the window origin ({y0}, {x0}) must be even for 4:2:0 frames")
-        if dst is not None:
-            _f32_canvas(dst, "yuv420_window: dst")
-        if dst_u8 is not None:
-            _u8_frame(dst_u8, "yuv420_window: dst_u8", (h, w))
-        hp, wp = (dst.shape[1], dst.shape[2]) if dst is not None else (h + pad_top, w + pad_left)
-        scale = 2 if mode == 1 else 1
-        meta = {"bytes": 1.5 * (2 if fmt.depth == 10 else 1) * scale * scale * h * w + (12.0 * hp * wp if dst is not None else 0.0)
-                + (3.0 * h * w if dst_u8 is not None else 0.0)}
-        self._run("yuv420_window", meta, self.lib.atmvfi_yuv420_window, _ptr(yuv), fh, fw, int(fmt.depth), fmt.matrix_id, int(fmt.full_range),
-                  fmt.siting_id, int(mode), int(y0), int(x0), int(h), int(w), _ptr(dst), hp, wp, int(pad_top), int(pad_left), _ptr(dst_u8),
-                  self._stream())
+        if fmt.subsampling != "420":
+            raise _not_420("yuv420_window", fmt)
+        y0, x0, h, w = int(y0), int(x0), int(h), int(w)
+        hp, wp, meta = self._yuv_decode_args("yuv420_window", yuv, fmt, dst_u8, dst, y0, x0, h, w, pad_top, pad_left, False,
+                                             4 if mode == 1 else 1, True)
+        self._run("yuv420_window", meta, self.lib.atmvfi_yuv420_window, _ptr(yuv), fmt.height, fmt.width, int(fmt.depth), fmt.matrix_id, int(fmt.full_range),
+                  fmt.siting_id, int(mode), y0, x0, h, w, _ptr(dst), hp, wp, int(pad_top), int(pad_left), _ptr(dst_u8), self._stream())
 
     def rgb_to_yuv420(self, yuv, fmt, src_u8=None, src=None, pad_top: int = 0, pad_left: int = 0, bgr: bool = False):
         """``src_u8`` uint8 [H,W,3] (BGR if ``bgr``) or ``src`` fp32 planar RGB [3,Hp,Wp] with the frame at (pad_top, pad_left) --
         exactly one -- -> ``yuv``, a packed 8-bit I420 frame of ``fmt`` (a contiguous CUDA uint8 tensor of ``fmt.frame_bytes`` bytes;
         include/atmvfi.h atmvfi_rgb_to_yuv420).  From fp32 the pixel is ``frame_f32_to_u8``'s; the bits of ``yuv.encode_numpy``."""
-        _only_420(fmt, "rgb_to_yuv420")
-        h, w = fmt.height, fmt.width
+        if fmt.subsampling != "420":
+            raise _not_420("rgb_to_yuv420", fmt)
         if fmt.depth != 8:
             raise ValueError("rgb_to_yuv420: encoding is 8-bit only")
-        _i420(yuv, fmt, "rgb_to_yuv420: destination")
-        if (src is None) == (src_u8 is None):
-            raise ValueError("rgb_to_yuv420: give exactly one of src_u8 and src")
-        if src is not None:
-            _f32_canvas(src, "rgb_to_yuv420: src")
-        else:
-            _u8_frame(src_u8, "rgb_to_yuv420: src_u8", (h, w))
-        hp, wp = (src.shape[1], src.shape[2]) if src is not None else (h, w)
-        meta = {"bytes": float(fmt.frame_bytes) + (12.0 if src is not None else 3.0) * h * w}
+        h, w, hp, wp, meta = self._yuv_encode_args("rgb_to_yuv420", yuv, fmt, src_u8, src, pad_top, pad_left)
         self._run("rgb_to_yuv420", meta, self.lib.atmvfi_rgb_to_yuv420, _ptr(src_u8), int(bool(bgr)), _ptr(src), hp, wp, int(pad_top),
                   int(pad_left), h, w, fmt.matrix_id, int(fmt.full_range), fmt.siting_id, _ptr(yuv), self._stream())
 
@@ -1510,21 +1527,15 @@ class HipOps:
         bytes, little-endian uint16 samples, any alignment) -> ``dst`` fp32 planar RGB [3,Hp,Wp] = q / 1023 with the depth kept:
         ``window=(y0, x0, h, w)`` of the frame (default: all of it; even origin) at (pad_top, pad_left), replicate padding
         (include/atmvfi.h atmvfi_yuv420p10_to_f32; the bits of ``yuv.decode_numpy_f32``)."""
-        _only_420(fmt, "yuv420p10_to_f32")
-        h, w = fmt.height, fmt.width
+        if fmt.subsampling != "420":
+            raise _not_420("yuv420p10_to_f32", fmt)
         if fmt.depth != 10:
             raise ValueError("yuv420p10_to_f32: a 10-bit format expected (yuv420_to_rgb decodes 8-bit frames)")
-        _i420(yuv, fmt, "yuv420p10_to_f32: source", "10-bit I420")
-        _f32_canvas(dst, "yuv420p10_to_f32: dst")
-        y0, x0, wh, ww = (0, 0, h, w) if window is None else (int(v) for v in window)
-        if y0 % 2 or x0 % 2:
-            raise ValueError(f"yuv420p10_to_f32: the window origin ({y0}, {x0}) must be even for 4:2:0 frames")
-        if y0 < 0 or x0 < 0 or wh < 1 or ww < 1 or y0 + wh > h or x0 + ww > w:
-            raise ValueError(f"yuv420p10_to_f32: window {wh} x {ww} at ({y0}, {x0}) outside the {h} x {w} frame")
-        hp, wp = dst.shape[1], dst.shape[2]
-        if pad_top < 0 or pad_left < 0 or wh + pad_top > hp or ww + pad_left > wp:
-            raise ValueError(f"yuv420p10_to_f32: canvas {hp} x {wp} is smaller than the window {wh} x {ww} plus padding ({pad_top}, {pad_left})")
-        meta = {"bytes": float(fmt.frame_bytes) + 12.0 * hp * wp}
+        if dst is None:         # (the one output)
+            raise ValueError("yuv420p10_to_f32: dst must be a contiguous CUDA fp32 [3,Hp,Wp] tensor")
+        h, w = fmt.height, fmt.width
+        y0, x0, wh, ww = (0, 0, h, w) if window is None else _window("yuv420p10_to_f32", fmt, window)
+        hp, wp, meta = self._yuv_decode_args("yuv420p10_to_f32", yuv, fmt, None, dst, y0, x0, wh, ww, pad_top, pad_left, True)
         self._run("yuv420p10_to_f32", meta, self.lib.atmvfi_yuv420p10_to_f32, _ptr(yuv), h, w, fmt.matrix_id, fmt.siting_id, y0, x0, wh, ww,
                   _ptr(dst), hp, wp, int(pad_top), int(pad_left), self._stream())
 
@@ -1533,16 +1544,13 @@ class HipOps:
         ``yuv.Format`` of depth 10; a contiguous CUDA uint8 tensor of ``fmt.frame_bytes`` bytes, little-endian uint16 samples;
         include/atmvfi.h atmvfi_f32_to_yuv420p10).  The pixel is clip(rint(x * 1023), 0, 1023); the bits of ``yuv.encode_numpy`` of
         an fp32 source."""
-        _only_420(fmt, "f32_to_yuv420p10")
-        h, w = fmt.height, fmt.width
+        if fmt.subsampling != "420":
+            raise _not_420("f32_to_yuv420p10", fmt)
         if fmt.depth != 10:
             raise ValueError("f32_to_yuv420p10: a 10-bit format expected (rgb_to_yuv420 encodes 8-bit frames)")
-        _i420(yuv, fmt, "f32_to_yuv420p10: destination", "10-bit I420")
-        _f32_canvas(src, "f32_to_yuv420p10: src")
-        hp, wp = src.shape[1], src.shape[2]
-        if pad_top < 0 or pad_left < 0 or h + pad_top > hp or w + pad_left > wp:
-            raise ValueError(f"f32_to_yuv420p10: canvas {hp} x {wp} is smaller than the frame {h} x {w} plus padding ({pad_top}, {pad_left})")
-        meta = {"bytes": float(fmt.frame_bytes) + 12.0 * h * w}
+        if src is None:         # (the one source)
+            raise ValueError("f32_to_yuv420p10: src must be a contiguous CUDA fp32 [3,Hp,Wp] tensor")
+        h, w, hp, wp, meta = self._yuv_encode_args("f32_to_yuv420p10", yuv, fmt, None, src, pad_top, pad_left)
         self._run("f32_to_yuv420p10", meta, self.lib.atmvfi_f32_to_yuv420p10, _ptr(src), hp, wp, int(pad_top), int(pad_left), h, w,
                   fmt.matrix_id, fmt.siting_id, _ptr(yuv), self._stream())
 
@@ -1553,140 +1561,70 @@ class HipOps:
         (default: all; even origin) as ``dst`` fp32 planar RGB [3,Hp,Wp] with replicate padding, the window at (pad_top, pad_left), and /
         or ``dst_u8`` uint8 [h,w,3] (BGR if ``bgr``).  ``keep_depth`` (a 10-bit surface, ``dst`` only): q / 1023, otherwise clip8 RGB
         and q / 255 (include/atmvfi.h atmvfi_yuv_surface_decode; the bits of ``yuv.decode_numpy`` / ``decode_numpy_f32``)."""
-        if not isinstance(surface, _surface_class()):
-            raise ValueError(f"yuv_surface_decode: surface must be a yuv.Surface (got {type(surface).__name__})")
-        _only_420(surface, "yuv_surface_decode")
-        h, w = surface.height, surface.width
-        _surface(buf, surface, "yuv_surface_decode: buf")
-        if dst is None and dst_u8 is None:
-            raise ValueError("yuv_surface_decode: give dst, dst_u8 or both")
-        if keep_depth and surface.depth != 10:
-            raise ValueError("yuv_surface_decode: keep_depth needs a 10-bit surface")
-        if keep_depth and dst_u8 is not None:
-            raise ValueError("yuv_surface_decode: dst_u8 holds 8-bit pixels: not with keep_depth")
-        y0, x0, wh, ww = (0, 0, h, w) if window is None else (int(v) for v in window)
-        if y0 % 2 or x0 % 2:
-            raise ValueError(f"yuv_surface_decode: the window origin ({y0}, {x0}) must be even for 4:2:0 frames")
-        if y0 < 0 or x0 < 0 or wh < 1 or ww < 1 or y0 + wh > h or x0 + ww > w:
-            raise ValueError(f"yuv_surface_decode: window {wh} x {ww} at ({y0}, {x0}) outside the {h} x {w} frame")
-        if dst is not None:
-            _f32_canvas(dst, "yuv_surface_decode: dst")
-            hp, wp = dst.shape[1], dst.shape[2]
-            if pad_top < 0 or pad_left < 0 or wh + pad_top > hp or ww + pad_left > wp:
-                raise ValueError(f"yuv_surface_decode: canvas {hp} x {wp} is smaller than the window {wh} x {ww} plus padding ({pad_top}, {pad_left})")
-        else:
-            hp, wp = wh, ww
-        if dst_u8 is not None:
-            _u8_frame(dst_u8, "yuv_surface_decode: dst_u8", (wh, ww))
-        meta = {"bytes": 1.5 * surface.itemsize * wh * ww + (12.0 * hp * wp if dst is not None else 0.0) + (3.0 * wh * ww if dst_u8 is not None else 0.0)}
-        self._run("yuv_surface_decode", meta, self.lib.atmvfi_yuv_surface_decode, _ptr(buf), h, w, int(surface.depth), surface.matrix_id,
-                  int(surface.full_range), surface.siting_id, surface.chroma_id, int(surface.msb), int(surface.pitch), int(surface.chroma_pitch),
-                  int(surface.chroma_offset), int(bool(keep_depth)), y0, x0, wh, ww, _ptr(dst_u8), int(bool(bgr)), _ptr(dst), hp, wp,
-                  int(pad_top), int(pad_left), self._stream())
+        s = surface
+        if not isinstance(s, Surface):
+            raise ValueError(f"yuv_surface_decode: surface must be a yuv.Surface (got {type(s).__name__})")
+        if s.subsampling != "420":
+            raise _not_420("yuv_surface_decode", s)
+        h, w = s.height, s.width
+        y0, x0, wh, ww = (0, 0, h, w) if window is None else _window("yuv_surface_decode", s, window)
+        hp, wp, meta = self._yuv_decode_args("yuv_surface_decode", buf, s, dst_u8, dst, y0, x0, wh, ww, pad_top, pad_left, keep_depth)
+        self._run("yuv_surface_decode", meta, self.lib.atmvfi_yuv_surface_decode, _ptr(buf), h, w, int(s.depth), s.matrix_id, int(s.full_range),
+                  s.siting_id, s.chroma_id, int(s.msb), int(s.pitch), int(s.chroma_pitch), int(s.chroma_offset), int(bool(keep_depth)), y0, x0,
+                  wh, ww, _ptr(dst_u8), int(bool(bgr)), _ptr(dst), hp, wp, int(pad_top), int(pad_left), self._stream())
 
     def yuv_surface_encode(self, buf, surface, src_u8=None, src=None, pad_top: int = 0, pad_left: int = 0, bgr: bool = False):
         """``src_u8`` uint8 [H,W,3] (BGR if ``bgr``; 8-bit surfaces only) or ``src`` fp32 planar RGB [3,Hp,Wp] with the frame at
         (pad_top, pad_left) -- exactly one -- -> ``buf``, one frame of the TIGHT ``surface`` (a contiguous CUDA uint8 tensor of
         ``surface.nbytes`` bytes).  A 10-bit surface is encoded from ``src`` in units of 1 / 1023 (include/atmvfi.h
         atmvfi_yuv_surface_encode; the bits of ``yuv.encode_numpy``)."""
-        if not isinstance(surface, _surface_class()):
-            raise ValueError(f"yuv_surface_encode: surface must be a yuv.Surface (got {type(surface).__name__})")
-        if not surface.is_tight:
+        s = surface
+        if not isinstance(s, Surface):
+            raise ValueError(f"yuv_surface_encode: surface must be a yuv.Surface (got {type(s).__name__})")
+        if not s.is_tight:
             raise ValueError("yuv_surface_encode: surface must be tight (encodes write no padding: surface.tight())")
-        _only_420(surface, "yuv_surface_encode")
-        h, w = surface.height, surface.width
-        _surface(buf, surface, "yuv_surface_encode: buf")
-        if (src is None) == (src_u8 is None):
-            raise ValueError("yuv_surface_encode: give exactly one of src_u8 and src")
-        if src is not None:
-            _f32_canvas(src, "yuv_surface_encode: src")
-            hp, wp = src.shape[1], src.shape[2]
-            if pad_top < 0 or pad_left < 0 or h + pad_top > hp or w + pad_left > wp:
-                raise ValueError(f"yuv_surface_encode: canvas {hp} x {wp} is smaller than the frame {h} x {w} plus padding ({pad_top}, {pad_left})")
-        else:
-            if surface.depth != 8:
-                raise ValueError("yuv_surface_encode: src_u8 encodes 8-bit surfaces only (a 10-bit surface takes the fp32 src)")
-            _u8_frame(src_u8, "yuv_surface_encode: src_u8", (h, w))
-            hp, wp = h, w
-        meta = {"bytes": float(surface.nbytes) + (12.0 if src is not None else 3.0) * h * w}
+        if s.subsampling != "420":
+            raise _not_420("yuv_surface_encode", s)
+        h, w, hp, wp, meta = self._yuv_encode_args("yuv_surface_encode", buf, s, src_u8, src, pad_top, pad_left)
         self._run("yuv_surface_encode", meta, self.lib.atmvfi_yuv_surface_encode, _ptr(src_u8), int(bool(bgr)), _ptr(src), hp, wp, int(pad_top),
-                  int(pad_left), h, w, int(surface.depth), surface.matrix_id, int(surface.full_range), surface.siting_id, surface.chroma_id,
-                  int(surface.msb), _ptr(buf), self._stream())
+                  int(pad_left), h, w, int(s.depth), s.matrix_id, int(s.full_range), s.siting_id, s.chroma_id, int(s.msb), _ptr(buf),
+                  self._stream())
 
     def yuv_sub_decode(self, buf, fmt_or_surface, dst_u8=None, dst=None, window=None, pad_top: int = 0, pad_left: int = 0, bgr: bool = False,
                        keep_depth: bool = False):
         """``yuv_surface_decode`` for a ``yuv.Format`` or planar ``yuv.Surface`` of any subsampling (4:2:2, 4:4:4; "420" is the surface
         call itself): the window's origin is a multiple of the subsampling step per axis -- even x0 for 4:2:2, anything for 4:4:4
         (include/atmvfi.h atmvfi_yuv_sub_decode; the bits of ``yuv.decode_numpy`` / ``decode_numpy_f32``)."""
-        from .yuv import _origin_error, as_surface
         if not hasattr(fmt_or_surface, "subsampling_id"):
             raise ValueError(f"yuv_sub_decode: a yuv.Format or yuv.Surface expected (got {type(fmt_or_surface).__name__})")
-        surface = as_surface(fmt_or_surface)
-        h, w = surface.height, surface.width
-        _surface(buf, surface, "yuv_sub_decode: buf")
-        if dst is None and dst_u8 is None:
-            raise ValueError("yuv_sub_decode: give dst, dst_u8 or both")
-        if keep_depth and surface.depth != 10:
-            raise ValueError("yuv_sub_decode: keep_depth needs a 10-bit surface")
-        if keep_depth and dst_u8 is not None:
-            raise ValueError("yuv_sub_decode: dst_u8 holds 8-bit pixels: not with keep_depth")
-        y0, x0, wh, ww = (0, 0, h, w) if window is None else (int(v) for v in window)
-        err = _origin_error("yuv_sub_decode", surface, y0, x0)
-        if err is not None:
-            raise err
-        if y0 < 0 or x0 < 0 or wh < 1 or ww < 1 or y0 + wh > h or x0 + ww > w:
-            raise ValueError(f"yuv_sub_decode: window {wh} x {ww} at ({y0}, {x0}) outside the {h} x {w} frame")
-        if dst is not None:
-            _f32_canvas(dst, "yuv_sub_decode: dst")
-            hp, wp = dst.shape[1], dst.shape[2]
-            if pad_top < 0 or pad_left < 0 or wh + pad_top > hp or ww + pad_left > wp:
-                raise ValueError(f"yuv_sub_decode: canvas {hp} x {wp} is smaller than the window {wh} x {ww} plus padding ({pad_top}, {pad_left})")
-        else:
-            hp, wp = wh, ww
-        if dst_u8 is not None:
-            _u8_frame(dst_u8, "yuv_sub_decode: dst_u8", (wh, ww))
-        sy, sx = surface.steps
-        meta = {"bytes": (1.0 + 2.0 / (sy * sx)) * surface.itemsize * wh * ww + (12.0 * hp * wp if dst is not None else 0.0)
-                + (3.0 * wh * ww if dst_u8 is not None else 0.0)}
-        self._run("yuv_sub_decode", meta, self.lib.atmvfi_yuv_sub_decode, _ptr(buf), h, w, int(surface.depth), surface.matrix_id,
-                  int(surface.full_range), surface.siting_id, surface.subsampling_id, surface.chroma_id, int(surface.msb), int(surface.pitch),
-                  int(surface.chroma_pitch), int(surface.chroma_offset), int(bool(keep_depth)), y0, x0, wh, ww, _ptr(dst_u8), int(bool(bgr)),
-                  _ptr(dst), hp, wp, int(pad_top), int(pad_left), self._stream())
+        s = as_surface(fmt_or_surface)
+        h, w = s.height, s.width
+        y0, x0, wh, ww = (0, 0, h, w) if window is None else _window("yuv_sub_decode", s, window)
+        hp, wp, meta = self._yuv_decode_args("yuv_sub_decode", buf, s, dst_u8, dst, y0, x0, wh, ww, pad_top, pad_left, keep_depth)
+        self._run("yuv_sub_decode", meta, self.lib.atmvfi_yuv_sub_decode, _ptr(buf), h, w, int(s.depth), s.matrix_id, int(s.full_range),
+                  s.siting_id, s.subsampling_id, s.chroma_id, int(s.msb), int(s.pitch), int(s.chroma_pitch), int(s.chroma_offset),
+                  int(bool(keep_depth)), y0, x0, wh, ww, _ptr(dst_u8), int(bool(bgr)), _ptr(dst), hp, wp, int(pad_top), int(pad_left),
+                  self._stream())
 
     def yuv_sub_encode(self, buf, fmt_or_surface, src_u8=None, src=None, pad_top: int = 0, pad_left: int = 0, bgr: bool = False):
         """``yuv_surface_encode`` for a ``yuv.Format`` or tight planar ``yuv.Surface`` of any subsampling (include/atmvfi.h
         atmvfi_yuv_sub_encode; the bits of ``yuv.encode_numpy``)."""
-        from .yuv import as_surface
         if not hasattr(fmt_or_surface, "subsampling_id"):
             raise ValueError(f"yuv_sub_encode: a yuv.Format or yuv.Surface expected (got {type(fmt_or_surface).__name__})")
-        surface = as_surface(fmt_or_surface)
-        if not surface.is_tight:
+        s = as_surface(fmt_or_surface)
+        if not s.is_tight:
             raise ValueError("yuv_sub_encode: surface must be tight (encodes write no padding: surface.tight())")
-        h, w = surface.height, surface.width
-        _surface(buf, surface, "yuv_sub_encode: buf")
-        if (src is None) == (src_u8 is None):
-            raise ValueError("yuv_sub_encode: give exactly one of src_u8 and src")
-        if src is not None:
-            _f32_canvas(src, "yuv_sub_encode: src")
-            hp, wp = src.shape[1], src.shape[2]
-            if pad_top < 0 or pad_left < 0 or h + pad_top > hp or w + pad_left > wp:
-                raise ValueError(f"yuv_sub_encode: canvas {hp} x {wp} is smaller than the frame {h} x {w} plus padding ({pad_top}, {pad_left})")
-        else:
-            if surface.depth != 8:
-                raise ValueError("yuv_sub_encode: src_u8 encodes 8-bit surfaces only (a 10-bit surface takes the fp32 src)")
-            _u8_frame(src_u8, "yuv_sub_encode: src_u8", (h, w))
-            hp, wp = h, w
-        meta = {"bytes": float(surface.nbytes) + (12.0 if src is not None else 3.0) * h * w}
+        h, w, hp, wp, meta = self._yuv_encode_args("yuv_sub_encode", buf, s, src_u8, src, pad_top, pad_left)
         self._run("yuv_sub_encode", meta, self.lib.atmvfi_yuv_sub_encode, _ptr(src_u8), int(bool(bgr)), _ptr(src), hp, wp, int(pad_top),
-                  int(pad_left), h, w, int(surface.depth), surface.matrix_id, int(surface.full_range), surface.siting_id, surface.subsampling_id,
-                  surface.chroma_id, int(surface.msb), _ptr(buf), self._stream())
+                  int(pad_left), h, w, int(s.depth), s.matrix_id, int(s.full_range), s.siting_id, s.subsampling_id, s.chroma_id, int(s.msb),
+                  _ptr(buf), self._stream())
 
     # The loops' colour conversion: a yuv.Format goes to the planar entry points as ever, a yuv.Surface to the two surface calls, and
-    # either with a subsampling other than 4:2:0 to the two calls above.
+    # either with a subsampling other than 4:2:0 to the two sub calls.
     def yuv_decode(self, buf, fmt, dst_u8=None, dst=None, window=None, pad_top: int = 0, pad_left: int = 0, keep_depth: bool = False):
-        if getattr(fmt, "subsampling", "420") != "420":
+        if fmt.subsampling != "420":
             return self.yuv_sub_decode(buf, fmt, dst_u8=dst_u8, dst=dst, window=window, pad_top=pad_top, pad_left=pad_left, keep_depth=keep_depth)
-        if isinstance(fmt, _surface_class()):
+        if isinstance(fmt, Surface):
             return self.yuv_surface_decode(buf, fmt, dst_u8=dst_u8, dst=dst, window=window, pad_top=pad_top, pad_left=pad_left, keep_depth=keep_depth)
         if keep_depth:
             return self.yuv420p10_to_f32(buf, fmt, dst, window=window, pad_top=pad_top, pad_left=pad_left)
@@ -1695,9 +1633,9 @@ class HipOps:
         return self.yuv420_to_rgb(buf, fmt, dst_u8=dst_u8, dst=dst, pad_top=pad_top, pad_left=pad_left)
 
     def yuv_encode(self, buf, fmt, src_u8=None, src=None, pad_top: int = 0, pad_left: int = 0):
-        if getattr(fmt, "subsampling", "420") != "420":
+        if fmt.subsampling != "420":
             return self.yuv_sub_encode(buf, fmt, src_u8=src_u8, src=src, pad_top=pad_top, pad_left=pad_left)
-        if isinstance(fmt, _surface_class()):
+        if isinstance(fmt, Surface):
             return self.yuv_surface_encode(buf, fmt, src_u8=src_u8, src=src, pad_top=pad_top, pad_left=pad_left)
         if fmt.depth == 10:
             return self.f32_to_yuv420p10(buf, fmt, src, pad_top=pad_top, pad_left=pad_left)

@@ -31,21 +31,22 @@ and 10 bit, with chroma planes [H, cw] and [H, W].  Decoding 4:2:2 filters along
 centre, 2 left) or the pixel itself (sh = 0).  Coefficients, offsets, clips and depth rules are the 4:2:0 ones.  A window's or crop's
 origin is a multiple of the subsampling step per axis.  ``Y4MReader(..., accept=("420", "422", "444"))`` reads C422, C444, C422p10
 and C444p10 (C422* as left-sited: Y4M's 4:2:2 is co-sited), ``Y4MWriter`` writes them, ``surface_of`` knows yuv422p, yuv444p,
-yuv422p10le and yuv444p10le, and every loop takes such a format or planar surface as ``pixfmt``."""
+yuv422p10le and yuv444p10le, and every loop takes such a format or planar surface as ``pixfmt``.
+
+``Format``, ``Surface`` and ``as_surface`` are defined in the leaf module ``pixfmt.py`` (hip_ops.py validates against them) and
+re-exported here; ``interpolate_y4m`` and ``interpolate_raw`` are front ends of one stream driver."""
 from __future__ import annotations
 
-import functools
 import io
 import os
-from dataclasses import dataclass, replace
 from fractions import Fraction
-from typing import Iterator, Optional, Tuple
+from typing import Iterator, Optional
 
 import numpy as np
 
-MATRICES = ("bt601", "bt709")
-SITINGS = ("centre", "left")
-SUBSAMPLINGS = ("420", "422", "444")        # ids 0 / 1 / 2 (include/atmvfi.h)
+from .pixfmt import (CHROMAS, MATRICES, SITINGS, SUBSAMPLINGS, Format, Surface, _layout_name, _only_420, _origin_error,  # noqa: F401
+                     _tight_surface, as_surface)
+
 KR_KB = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}
 SHIFT = 14
 
@@ -85,262 +86,6 @@ COEFFS10 = {
     "bt601": ((19133, 26226, -6438, -13359, 33148), ((4195, 8235, 1599), (-2421, -4754, 7175), (7175, -6008, -1167))),
     "bt709": ((19133, 29459, -3504, -8757, 34711), ((2983, 10034, 1013), (-1644, -5531, 7175), (7175, -6517, -658))),
 }
-
-
-@dataclass(frozen=True)
-class Format:
-    """A packed planar frame format: Y, U, V back to back.  ``matrix="auto"``: bt709 for ``height >= 720``, bt601 below.
-    ``subsampling``: "420" (I420: chroma ``((H + 1) // 2, (W + 1) // 2)``), "422" (``(H, (W + 1) // 2)``) or "444" (``(H, W)``, where a
-    siting has no meaning: only "centre" is accepted, so that equal formats compare equal)."""
-    height: int
-    width: int
-    matrix: str = "auto"
-    full_range: bool = False
-    siting: str = "centre"
-    depth: int = 8
-    subsampling: str = "420"
-
-    def __post_init__(self):
-        if int(self.height) < 1 or int(self.width) < 1:
-            raise ValueError(f"yuv.Format: height and width must be at least 1 (got {self.height} x {self.width})")
-        m = self.matrix
-        if m == "auto":
-            m = "bt709" if self.height >= 720 else "bt601"
-        if m not in MATRICES:
-            raise ValueError(f"yuv.Format: unknown matrix {self.matrix!r} (auto, bt601, bt709)")
-        if self.siting not in SITINGS:
-            raise ValueError(f"yuv.Format: unknown siting {self.siting!r} (centre, left)")
-        if self.depth not in (8, 10):
-            raise ValueError(f"yuv.Format: depth must be 8 or 10 (got {self.depth!r})")
-        if self.depth == 10 and self.full_range:
-            raise ValueError("yuv.Format: 10-bit full range is not supported")
-        if self.subsampling not in SUBSAMPLINGS:
-            raise ValueError(f"yuv.Format: unknown subsampling {self.subsampling!r} (420, 422, 444)")
-        if self.subsampling == "444" and self.siting != "centre":
-            raise ValueError(f"yuv.Format: siting {self.siting!r} has no meaning for subsampling 444 (leave it at centre)")
-        object.__setattr__(self, "height", int(self.height))
-        object.__setattr__(self, "width", int(self.width))
-        object.__setattr__(self, "matrix", m)
-        object.__setattr__(self, "full_range", bool(self.full_range))
-
-    @property
-    def chroma_shape(self) -> Tuple[int, int]:
-        sy, sx = self.steps
-        return (self.height + sy - 1) // sy, (self.width + sx - 1) // sx
-
-    @property
-    def steps(self) -> Tuple[int, int]:
-        """Luma rows and columns per chroma sample: what a window's or a crop's origin must be a multiple of."""
-        return {"420": (2, 2), "422": (1, 2), "444": (1, 1)}[self.subsampling]
-
-    @property
-    def subsampling_id(self) -> int:
-        return SUBSAMPLINGS.index(self.subsampling)
-
-    @property
-    def frame_samples(self) -> int:
-        ch, cw = self.chroma_shape
-        return self.height * self.width + 2 * ch * cw
-
-    @property
-    def frame_bytes(self) -> int:
-        return self.frame_samples * (2 if self.depth == 10 else 1)
-
-    @property
-    def dtype(self):
-        return np.uint16 if self.depth == 10 else np.uint8
-
-    @property
-    def matrix_id(self) -> int:
-        return MATRICES.index(self.matrix)
-
-    @property
-    def siting_id(self) -> int:
-        return SITINGS.index(self.siting)
-
-    def check(self, buf, what: str = "yuv") -> np.ndarray:
-        """``buf`` as the 1-D sample array of one frame of this format (a view), or ``ValueError``."""
-        a = np.asarray(buf)
-        if a.dtype != self.dtype or a.size != self.frame_samples or not a.flags.c_contiguous:
-            raise ValueError(f"{what}: a contiguous {np.dtype(self.dtype).name} {_layout_name(self)} frame of {self.frame_samples} samples "
-                             f"({self.height} x {self.width}) expected, got {a.dtype} {tuple(a.shape)}")
-        return a.reshape(-1)
-
-    def planes(self, buf):
-        """(Y [H,W], U [ch,cw], V [ch,cw]) views of a packed frame."""
-        a = self.check(buf, "yuv.Format.planes")
-        ch, cw = self.chroma_shape
-        n, c = self.height * self.width, ch * cw
-        return a[:n].reshape(self.height, self.width), a[n:n + c].reshape(ch, cw), a[n + c:].reshape(ch, cw)
-
-    def as_8bit(self) -> "Format":
-        return self if self.depth == 8 else replace(self, depth=8)
-
-    def cropped(self, h: int, w: int) -> "Format":
-        return replace(self, height=int(h), width=int(w))
-
-
-CHROMAS = ("planar", "uv", "vu")
-
-
-def _layout_name(fmt) -> str:
-    return {"420": "I420", "422": "planar 4:2:2", "444": "planar 4:4:4"}[fmt.subsampling]
-
-
-def _origin_error(who: str, fmt, y0: int, x0: int, noun: str = "window"):
-    """The origin rule of a window or crop of ``fmt``: a multiple of the subsampling step per axis.  None, or the ``ValueError``."""
-    sy, sx = fmt.steps
-    if y0 % sy == 0 and x0 % sx == 0:
-        return None
-    if fmt.subsampling == "420":
-        return ValueError(f"{who}: the {noun} origin ({y0}, {x0}) must be even for 4:2:0 frames")
-    return ValueError(f"{who}: the {noun} origin ({y0}, {x0}) must have an even x0 for 4:2:2 frames")
-
-
-def _only_420(who: str, fmt):
-    if fmt.subsampling != "420":
-        raise ValueError(f"{who}: 4:2:0 frames only (got subsampling {fmt.subsampling})")
-
-
-@dataclass(frozen=True)
-class Surface:
-    """One frame as a decoder hands it over: one contiguous buffer of ``fmt.dtype`` samples with a layout.  ``fmt`` (a ``Format``)
-    supplies size, matrix, range, siting and depth; the pixel arithmetic is the ``Format``'s, applied to the samples found here.
-
-    ``chroma``: "planar" (the U plane, then the V plane), "uv" (one plane of interleaved pairs, U first: NV12 / P010) or "vu" (V
-    first: NV21).  ``msb`` (depth 10 only): a stored sample is ``value << 6``; decoding takes ``s >> 6``, encoding writes ``v << 6``.
-    ``pitch`` / ``chroma_pitch``: row strides in bytes, multiples of the sample size and at least the row's own bytes; default tight
-    (``W b``; ``cw b`` planar, ``2 cw b`` interleaved).  ``chroma_offset``: the byte offset of the first chroma row, a multiple of the
-    sample size and at least ``pitch * H`` (the default); planar V follows U at ``chroma_offset + chroma_pitch * ch``.  ``nbytes``:
-    the whole buffer through the last chroma row's own bytes; frames are 1-D arrays of ``nbytes // itemsize`` samples.  Padding is
-    never read; encodes write tight surfaces only.  ``Surface.i420(h, w)`` is byte for byte a ``Format`` frame."""
-    fmt: Format
-    chroma: str = "planar"
-    msb: bool = False
-    pitch: Optional[int] = None
-    chroma_pitch: Optional[int] = None
-    chroma_offset: Optional[int] = None
-
-    def __post_init__(self):
-        if not isinstance(self.fmt, Format):
-            raise ValueError(f"yuv.Surface: fmt must be a yuv.Format (got {type(self.fmt).__name__})")
-        if self.chroma not in CHROMAS:
-            raise ValueError(f"yuv.Surface: unknown chroma layout {self.chroma!r} (planar, uv, vu)")
-        if self.msb and self.fmt.depth != 10:
-            raise ValueError("yuv.Surface: msb needs depth 10 (8-bit samples fill their byte)")
-        if self.fmt.subsampling != "420" and self.chroma != "planar":
-            raise ValueError(f"yuv.Surface: interleaved chroma ({self.chroma}) is 4:2:0 only (got subsampling {self.fmt.subsampling}; "
-                             "4:2:2 and 4:4:4 surfaces are planar)")
-        b, (H, W), (ch, cw) = self.itemsize, (self.fmt.height, self.fmt.width), self.fmt.chroma_shape
-        crow = (cw if self.chroma == "planar" else 2 * cw) * b
-        pitch = W * b if self.pitch is None else int(self.pitch)
-        cpitch = crow if self.chroma_pitch is None else int(self.chroma_pitch)
-        if pitch % b or pitch < W * b:
-            raise ValueError(f"yuv.Surface: pitch {pitch} must be a multiple of the sample size {b} and at least a luma row's {W * b} bytes")
-        if cpitch % b or cpitch < crow:
-            raise ValueError(f"yuv.Surface: chroma_pitch {cpitch} must be a multiple of the sample size {b} and at least a chroma row's "
-                             f"{crow} bytes")
-        off = pitch * H if self.chroma_offset is None else int(self.chroma_offset)
-        if off % b or off < pitch * H:
-            raise ValueError(f"yuv.Surface: chroma_offset {off} must be a multiple of the sample size {b} and at least pitch * H = {pitch * H}")
-        object.__setattr__(self, "msb", bool(self.msb))
-        object.__setattr__(self, "pitch", pitch)
-        object.__setattr__(self, "chroma_pitch", cpitch)
-        object.__setattr__(self, "chroma_offset", off)
-        # derived once (the device calls ask for both on every launch); not fields: equality and hash are the layout's
-        rows = 2 * ch - 1 if self.chroma == "planar" else ch - 1
-        object.__setattr__(self, "_nbytes", off + cpitch * rows + crow)
-        object.__setattr__(self, "_tight", (pitch, cpitch, off) == (W * b, crow, W * b * H))
-
-    @classmethod
-    def nv12(cls, h: int, w: int, pitch=None, chroma_offset=None, **format_kw) -> "Surface":
-        """NV12: 8-bit, interleaved UV; the chroma rows share the luma pitch."""
-        return cls(Format(h, w, depth=8, **format_kw), "uv", False, pitch, pitch, chroma_offset)
-
-    @classmethod
-    def p010(cls, h: int, w: int, pitch=None, chroma_offset=None, **format_kw) -> "Surface":
-        """P010: 10-bit samples in the upper bits of 16-bit words, interleaved UV; the chroma rows share the luma pitch."""
-        return cls(Format(h, w, depth=10, **format_kw), "uv", True, pitch, pitch, chroma_offset)
-
-    @classmethod
-    def i420(cls, h: int, w: int, pitch=None, chroma_offset=None, **format_kw) -> "Surface":
-        """Planar I420 (``depth=10``: LSB-aligned uint16); with a ``pitch`` the chroma rows have half of it."""
-        return cls(Format(h, w, **format_kw), "planar", False, pitch, None if pitch is None else int(pitch) // 2, chroma_offset)
-
-    # what the loops and helpers read of a Format
-    height = property(lambda self: self.fmt.height)
-    width = property(lambda self: self.fmt.width)
-    matrix = property(lambda self: self.fmt.matrix)
-    full_range = property(lambda self: self.fmt.full_range)
-    siting = property(lambda self: self.fmt.siting)
-    depth = property(lambda self: self.fmt.depth)
-    dtype = property(lambda self: self.fmt.dtype)
-    chroma_shape = property(lambda self: self.fmt.chroma_shape)
-    matrix_id = property(lambda self: self.fmt.matrix_id)
-    siting_id = property(lambda self: self.fmt.siting_id)
-    subsampling = property(lambda self: self.fmt.subsampling)
-    subsampling_id = property(lambda self: self.fmt.subsampling_id)
-    steps = property(lambda self: self.fmt.steps)
-    chroma_id = property(lambda self: CHROMAS.index(self.chroma))
-
-    @property
-    def itemsize(self) -> int:
-        return 2 if self.fmt.depth == 10 else 1
-
-    @property
-    def nbytes(self) -> int:
-        return self._nbytes
-
-    frame_bytes = nbytes
-
-    @property
-    def frame_samples(self) -> int:
-        return self.nbytes // self.itemsize
-
-    @property
-    def is_tight(self) -> bool:
-        return self._tight
-
-    def tight(self) -> "Surface":
-        return Surface(self.fmt, self.chroma, self.msb)
-
-    def cropped(self, h: int, w: int) -> "Surface":
-        return Surface(self.fmt.cropped(h, w), self.chroma, self.msb)
-
-    def as_8bit(self) -> "Surface":
-        """The tight 8-bit counterpart (P010 -> NV12), itself for a tight 8-bit surface."""
-        return self.tight() if self.fmt.depth == 8 else Surface(self.fmt.as_8bit(), self.chroma, False)
-
-    def check(self, buf, what: str = "yuv") -> np.ndarray:
-        """``buf`` as the 1-D sample array of one frame of this surface (a view), or ``ValueError``."""
-        a = np.asarray(buf)
-        if a.dtype != self.dtype or a.size != self.frame_samples or not a.flags.c_contiguous:
-            raise ValueError(f"{what}: a contiguous {np.dtype(self.dtype).name} {self.chroma} surface of {self.frame_samples} samples "
-                             f"({self.height} x {self.width}, pitch {self.pitch}) expected, got {a.dtype} {tuple(a.shape)}")
-        return a.reshape(-1)
-
-    def planes(self, buf):
-        """(Y [H,W], U [ch,cw], V [ch,cw]) strided views of the STORED samples (``msb``: still shifted); padding is not part of them."""
-        a = self.check(buf, "yuv.Surface.planes")
-        b, (ch, cw) = self.itemsize, self.fmt.chroma_shape
-        view = lambda off, rows, cols, rs, cs: np.lib.stride_tricks.as_strided(a[off // b:], (rows, cols), (rs, cs), writeable=a.flags.writeable)
-        Y = view(0, self.height, self.width, self.pitch, b)
-        if self.chroma == "planar":
-            return Y, view(self.chroma_offset, ch, cw, self.chroma_pitch, b), \
-                view(self.chroma_offset + self.chroma_pitch * ch, ch, cw, self.chroma_pitch, b)
-        first, second = (view(self.chroma_offset + k * b, ch, cw, self.chroma_pitch, 2 * b) for k in (0, 1))
-        return (Y, first, second) if self.chroma == "uv" else (Y, second, first)
-
-
-@functools.lru_cache(maxsize=64)
-def _tight_surface(fmt: Format) -> Surface:
-    return Surface(fmt)
-
-
-def as_surface(fmt) -> Surface:
-    """A ``Surface`` as it is; a ``Format`` as its tight planar surface (the same bytes; surfaces are immutable, so one per format is
-    kept: the device calls ask on every launch)."""
-    return fmt if isinstance(fmt, Surface) else _tight_surface(fmt)
 
 
 def planes(buf, fmt):
@@ -873,6 +618,70 @@ def to_8bit(frame, fmt) -> np.ndarray:
     return encode_numpy(decode_numpy(frame, fmt), fmt.as_8bit())
 
 
+def _interpolate_stream(who, open_reader, open_writer, model, kw, *, factor, scene, tta, interpolator, keep_depth, fps_out, levels, dedup,
+                        shutter):
+    """The one driver of ``interpolate_y4m`` and ``interpolate_raw`` (``who``, for the messages): the frames of ``rd = open_reader()``
+    (``rd.fmt`` is the loops' ``pixfmt``, ``rd.fps`` the rate) through the loops into ``open_writer(rd, out_format, rate)``.  What the
+    arguments alone decide is refused before anything is opened; after that both ends are closed on every path, a refusal before
+    the writer exists included."""
+    from .host_io import _hip_ops_of, interpolate_video_2x
+    from .multiframe import centre_window, interpolate_video_nx, nx_levels
+    from .retime import _check_rates, interpolate_video_retimed
+    if fps_out is None:
+        if shutter is not None:
+            raise ValueError(f"{who}: shutter needs fps_out (the synthetic shutter belongs to the rate conversion)")
+        nx_levels(factor)
+    elif "time_interval" in kw:
+        raise ValueError(f"{who}: fps_out and time_interval do not go together")
+    rd = open_reader()
+    pixfmt, wr, n_in, report = rd.fmt, None, [0], {}
+
+    def counted():
+        for f in rd:
+            n_in[0] += 1
+            yield f
+    try:
+        if fps_out is None:
+            rate = rd.fps * factor / int(kw.get("time_interval", 1))
+        else:
+            _, rate, levels = _check_rates(rd.fps, fps_out, levels)
+        _, _, oh, ow = centre_window(pixfmt.height, pixfmt.width, kw.get("crop"))
+        deep = bool(keep_depth) and pixfmt.depth == 10
+        src_out = pixfmt.cropped(oh, ow)            # (a Surface's is tight)
+        wr = open_writer(rd, src_out if deep else src_out.as_8bit(), rate)
+        if fps_out is not None:
+            if shutter is not None:
+                kw["shutter"] = shutter
+            frames = (interpolator or interpolate_video_retimed)(counted(), model, rd.fps, rate, levels=levels, dedup=dedup, scene=scene, tta=tta,
+                                                                 pixfmt=pixfmt, keep_depth=deep, report=report, **kw)
+        else:
+            if deep:
+                kw["keep_depth"] = True
+            if interpolator is None:
+                nx_only = tta or factor != 2 or any(k in kw for k in ("crop", "time_interval", "max_batch", "pool"))
+                if not nx_only and _hip_ops_of(model)[0] is not None:
+                    interpolator = interpolate_video_2x
+                else:
+                    interpolator = lambda frames, model, **k: interpolate_video_nx(frames, model, factor=factor, tta=tta, **k)
+            frames = interpolator(counted(), model, pixfmt=pixfmt, scene=scene, **kw)
+        for f in frames:
+            wr.write(to_8bit(f, src_out) if (f.dtype == np.uint16 and not deep) else f)
+    finally:
+        rd.close()
+        if wr is not None:
+            wr.close()
+    info = {"fps_in": rd.fps, "fps_out": rate, "size": (ow, oh), "frames_in": n_in[0], "frames_out": wr.frames}
+    if fps_out is not None:
+        info["forwards"] = report.get("forwards", 0)
+        if shutter is not None:
+            info["blended"] = report.get("blended", 0)
+        if dedup is not None:
+            info["dropped"] = list(dedup.dropped)
+    if scene is not None:
+        info["cuts"] = list(scene.cuts)
+    return info
+
+
 def interpolate_y4m(src, dst, model, factor: int = 2, scene=None, tta: bool = False, interpolator=None, matrix: str = "auto",
                     keep_depth: bool = False, fps_out=None, levels: int = 3, dedup=None, shutter=None, **kw):
     """Y4M file (or binary file object) ``src`` -> Y4M ``dst`` at ``fps * factor`` (``/ time_interval`` when given): an exact
@@ -890,46 +699,11 @@ def interpolate_y4m(src, dst, model, factor: int = 2, scene=None, tta: bool = Fa
     ``time_interval``.  The dict gains ``"forwards"`` and, with ``dedup``, ``"dropped"``.  ``shutter`` (a ``shutter.Shutter`` or an
     angle; only with ``fps_out``, else ``ValueError``; 8-bit output only): the conversion's synthetic shutter; the dict gains
     ``"blended"``."""
-    if fps_out is not None:
-        if shutter is not None:
-            kw["shutter"] = shutter
-        return _retime_y4m(src, dst, model, fps_out, levels, dedup, scene, tta, interpolator, matrix, keep_depth, kw)
-    if shutter is not None:
-        raise ValueError("interpolate_y4m: shutter needs fps_out (the synthetic shutter belongs to the rate conversion)")
-    from .host_io import _hip_ops_of, interpolate_video_2x
-    from .multiframe import centre_window, interpolate_video_nx, nx_levels
-    nx_levels(factor)
-    rd = Y4MReader(src, matrix=matrix, accept=SUBSAMPLINGS)
-    fmt = rd.fmt
-    _, _, oh, ow = centre_window(fmt.height, fmt.width, kw.get("crop"))
-    deep = bool(keep_depth) and fmt.depth == 10
-    out_fmt = (fmt if deep else fmt.as_8bit()).cropped(oh, ow)
-    rate = rd.fps * factor / int(kw.get("time_interval", 1))
-    wr = Y4MWriter(dst, out_fmt, rate, ctag=rd.ctag if (fmt.depth == 8 or deep) else None, aspect=rd.aspect)
-    if deep:
-        kw["keep_depth"] = True
-    n_in = [0]
-
-    def counted():
-        for f in rd:
-            n_in[0] += 1
-            yield f
-    if interpolator is None:
-        nx_only = tta or factor != 2 or any(k in kw for k in ("crop", "time_interval", "max_batch", "pool"))
-        if not nx_only and _hip_ops_of(model)[0] is not None:
-            interpolator = interpolate_video_2x
-        else:
-            interpolator = lambda frames, model, **k: interpolate_video_nx(frames, model, factor=factor, tta=tta, **k)
-    try:
-        for f in interpolator(counted(), model, pixfmt=fmt, scene=scene, **kw):
-            wr.write(to_8bit(f, fmt.cropped(oh, ow)) if (f.dtype == np.uint16 and not deep) else f)
-    finally:
-        rd.close()
-        wr.close()
-    info = {"fps_in": rd.fps, "fps_out": rate, "size": (ow, oh), "frames_in": n_in[0], "frames_out": wr.frames}
-    if scene is not None:
-        info["cuts"] = list(scene.cuts)
-    return info
+    # (the same tag as read where the depth is the stream's; 10-bit input written as 8 bit takes the format's canonical tag)
+    open_writer = lambda rd, out, rate: Y4MWriter(dst, out, rate, ctag=rd.ctag if out.depth == rd.fmt.depth else None, aspect=rd.aspect)
+    return _interpolate_stream("interpolate_y4m", lambda: Y4MReader(src, matrix=matrix, accept=SUBSAMPLINGS), open_writer, model, kw,
+                               factor=factor, scene=scene, tta=tta, interpolator=interpolator, keep_depth=keep_depth, fps_out=fps_out,
+                               levels=levels, dedup=dedup, shutter=shutter)
 
 
 PIX_FMTS = {"nv12": ("uv", 8, False), "nv21": ("vu", 8, False), "p010le": ("uv", 10, True), "yuv420p": ("planar", 8, False),
@@ -958,102 +732,10 @@ def interpolate_raw(src, dst, model, surface, fps, factor: int = 2, scene=None, 
     frames of ``surface.tight().cropped(h, w)`` in ``dst`` (the 8-bit counterpart for 10-bit input without ``keep_depth``, originals
     converted on the host), at ``fps * factor`` or at ``fps_out``.  Every keyword is ``interpolate_y4m``'s (there is no ``matrix``: the
     surface's format names it); the same dict is returned."""
-    from .host_io import _hip_ops_of, interpolate_video_2x
-    from .multiframe import centre_window, interpolate_video_nx, nx_levels
-    from .retime import _check_rates, interpolate_video_retimed
     surface = as_surface(surface)
-    if fps_out is None:
-        if shutter is not None:
-            raise ValueError("interpolate_raw: shutter needs fps_out (the synthetic shutter belongs to the rate conversion)")
-        nx_levels(factor)
-        rate = Fraction(fps) * factor / int(kw.get("time_interval", 1))
-    else:
-        if "time_interval" in kw:
-            raise ValueError("interpolate_raw: fps_out and time_interval do not go together")
-        _, rate, levels = _check_rates(Fraction(fps), fps_out, levels)
-    _, _, oh, ow = centre_window(surface.height, surface.width, kw.get("crop"))
-    deep = bool(keep_depth) and surface.depth == 10
-    src_out = surface.tight().cropped(oh, ow)
-    out = src_out if deep else src_out.as_8bit()
-    rd, wr = RawReader(src, surface, fps), RawWriter(dst, out)
-    n_in, report = [0], {}
-
-    def counted():
-        for f in rd:
-            n_in[0] += 1
-            yield f
-    if fps_out is not None:
-        if shutter is not None:
-            kw["shutter"] = shutter
-        run = lambda: (interpolator or interpolate_video_retimed)(counted(), model, rd.fps, rate, levels=levels, dedup=dedup, scene=scene, tta=tta,
-                                                                  pixfmt=surface, keep_depth=deep, report=report, **kw)
-    else:
-        if deep:
-            kw["keep_depth"] = True
-        if interpolator is None:
-            nx_only = tta or factor != 2 or any(k in kw for k in ("crop", "time_interval", "max_batch", "pool"))
-            if not nx_only and _hip_ops_of(model)[0] is not None:
-                interpolator = interpolate_video_2x
-            else:
-                interpolator = lambda frames, model, **k: interpolate_video_nx(frames, model, factor=factor, tta=tta, **k)
-        run = lambda: interpolator(counted(), model, pixfmt=surface, scene=scene, **kw)
-    try:
-        for f in run():
-            wr.write(to_8bit(f, src_out) if (f.dtype == np.uint16 and not deep) else f)
-    finally:
-        rd.close()
-        wr.close()
-    info = {"fps_in": rd.fps, "fps_out": rate, "size": (ow, oh), "frames_in": n_in[0], "frames_out": wr.frames}
-    if fps_out is not None:
-        info["forwards"] = report.get("forwards", 0)
-        if shutter is not None:
-            info["blended"] = report.get("blended", 0)
-        if dedup is not None:
-            info["dropped"] = list(dedup.dropped)
-    if scene is not None:
-        info["cuts"] = list(scene.cuts)
-    return info
-
-
-def _retime_y4m(src, dst, model, fps_out, levels, dedup, scene, tta, interpolator, matrix, keep_depth, kw):
-    """``interpolate_y4m`` with ``fps_out``."""
-    from .multiframe import centre_window
-    from .retime import _check_rates, interpolate_video_retimed
-    if "time_interval" in kw:
-        raise ValueError("interpolate_y4m: fps_out and time_interval do not go together")
-    rd = Y4MReader(src, matrix=matrix, accept=SUBSAMPLINGS)
-    try:
-        fmt = rd.fmt
-        _, rate, levels = _check_rates(rd.fps, fps_out, levels)
-        _, _, oh, ow = centre_window(fmt.height, fmt.width, kw.get("crop"))
-    except Exception:
-        rd.close()
-        raise
-    deep = bool(keep_depth) and fmt.depth == 10
-    out_fmt = (fmt if deep else fmt.as_8bit()).cropped(oh, ow)
-    wr = Y4MWriter(dst, out_fmt, rate, ctag=rd.ctag if (fmt.depth == 8 or deep) else None, aspect=rd.aspect)
-    n_in, report = [0], {}
-
-    def counted():
-        for f in rd:
-            n_in[0] += 1
-            yield f
-    try:
-        for f in (interpolator or interpolate_video_retimed)(counted(), model, rd.fps, rate, levels=levels, dedup=dedup, scene=scene, tta=tta,
-                                                             pixfmt=fmt, keep_depth=deep, report=report, **kw):
-            wr.write(to_8bit(f, fmt.cropped(oh, ow)) if (f.dtype == np.uint16 and not deep) else f)
-    finally:
-        rd.close()
-        wr.close()
-    info = {"fps_in": rd.fps, "fps_out": rate, "size": (ow, oh), "frames_in": n_in[0], "frames_out": wr.frames,
-            "forwards": report.get("forwards", 0)}
-    if kw.get("shutter") is not None:
-        info["blended"] = report.get("blended", 0)
-    if dedup is not None:
-        info["dropped"] = list(dedup.dropped)
-    if scene is not None:
-        info["cuts"] = list(scene.cuts)
-    return info
+    return _interpolate_stream("interpolate_raw", lambda: RawReader(src, surface, fps), lambda rd, out, rate: RawWriter(dst, out), model, kw,
+                               factor=factor, scene=scene, tta=tta, interpolator=interpolator, keep_depth=keep_depth, fps_out=fps_out,
+                               levels=levels, dedup=dedup, shutter=shutter)
 
 
 # what a user of this module needs from the loops

@@ -76,7 +76,9 @@ def test_yuv420_window_abi_is_declared_exported_and_checks_on_the_host():
     err = lib.atmvfi_last_error
 
     def win(yuv_=P, H=64, W=96, depth=8, matrix=0, full=0, siting=0, mode=0, y0=0, x0=0, h=32, w=48, dst=P, Hp=32, Wp=48, pt=0, pl=0, d8=P):
-        return lib.atmvfi_yuv420_window(yuv_, H, W, depth, matrix, full, siting, mode, y0, x0, h, w, dst, Hp, Wp, pt, pl, d8, None)
+        rc = lib.atmvfi_yuv420_window(yuv_, H, W, depth, matrix, full, siting, mode, y0, x0, h, w, dst, Hp, Wp, pt, pl, d8, None)
+        assert rc == -1 and err().startswith(b"yuv420_window: ")        # the shared checks, under the entry point's own name
+        return rc
     assert win(yuv_=None) == -1 and b"null source" in err()
     assert win(dst=None, d8=None) == -1 and b"both outputs are null" in err()
     assert win(mode=2) == -1 and b"unknown mode" in err()
@@ -101,6 +103,13 @@ def test_yuv420_window_abi_is_declared_exported_and_checks_on_the_host():
     assert win(siting=2) == -1 and b"unknown siting" in err()
     assert win(full=2) == -1 and b"full_range" in err()
     assert win(dst=P + 2) == -1 and b"4-byte aligned" in err()
+    assert win(W=0) == -1 and b"at least 1" in err()                                            # (asserted for its siblings before)
+    assert win(mode=1, y0=2) == -1 and b"window outside the frame" in err() and b"64 x 96" in err()     # 2 + 2 * 32 > 64
+    assert win(mode=1, x0=2) == -1 and b"window outside the frame" in err()
+    assert win(mode=1, y0=1, h=8, w=8, Hp=8, Wp=8) == -1 and b"must be even" in err()
+    assert win(mode=1, Hp=31) == -1 and b"smaller than the window" in err()
+    for mode in (0, 1):         # 1.25e9 and 2.5e9 work items
+        assert win(mode=mode, H=200000, W=200000, h=100000, w=100000, Hp=100000, Wp=100000) == -1 and b"too large" in err()
 
 
 # ------------------------------------------------------------------------------------------------ finding a clip, choosing its source

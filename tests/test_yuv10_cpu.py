@@ -265,10 +265,14 @@ def test_yuv10_abi_is_declared_exported_and_checks_on_the_host():
     err = lib.atmvfi_last_error
 
     def dec(yuv_=P, H=64, W=96, matrix=0, siting=0, y0=0, x0=0, h=64, w=96, dst=P, Hp=64, Wp=96, pt=0, pl=0):
-        return lib.atmvfi_yuv420p10_to_f32(yuv_, H, W, matrix, siting, y0, x0, h, w, dst, Hp, Wp, pt, pl, None)
+        rc = lib.atmvfi_yuv420p10_to_f32(yuv_, H, W, matrix, siting, y0, x0, h, w, dst, Hp, Wp, pt, pl, None)
+        assert rc == -1 and err().startswith(b"yuv420p10_to_f32: ")     # the shared checks, under the entry point's own name
+        return rc
 
     def enc(src=P, Hp=64, Wp=96, pt=0, pl=0, H=64, W=96, matrix=0, siting=0, yuv_=P):
-        return lib.atmvfi_f32_to_yuv420p10(src, Hp, Wp, pt, pl, H, W, matrix, siting, yuv_, None)
+        rc = lib.atmvfi_f32_to_yuv420p10(src, Hp, Wp, pt, pl, H, W, matrix, siting, yuv_, None)
+        assert rc == -1 and err().startswith(b"f32_to_yuv420p10: ")
+        return rc
     assert dec(yuv_=None) == -1 and b"null source" in err()
     assert dec(dst=None) == -1 and b"null destination" in err()
     assert dec(H=0) == -1 and b"at least 1" in err()
@@ -287,6 +291,8 @@ def test_yuv10_abi_is_declared_exported_and_checks_on_the_host():
     assert dec(pt=-1) == -1 and b"smaller than the window" in err()
     assert dec(dst=P + 2) == -1 and b"4-byte aligned" in err()
     assert dec(H=100000, W=100000, h=100000, w=100000, Hp=100000, Wp=100000) == -1 and b"too large" in err()
+    assert dec(x0=-2, w=8) == -1 and b"outside the" in err()                                    # (asserted for its siblings before)
+    assert dec(y0=34, h=32) == -1 and b"outside the" in err()
     assert enc(src=None) == -1 and b"null source" in err()
     assert enc(yuv_=None) == -1 and b"null destination" in err()
     assert enc(H=0) == -1 and b"at least 1" in err()

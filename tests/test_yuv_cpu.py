@@ -396,6 +396,23 @@ def test_interpolate_y4m_writes_ten_bit_input_back_as_eight_bit(tmp_path):
     assert np.array_equal(got[0], yuv.to_8bit(video[0], fmt)) and got[0].dtype == np.uint8
 
 
+@pytest.mark.parametrize("kw", [{}, dict(fps_out=50)], ids=["factor", "fps_out"])
+def test_interpolate_y4m_releases_its_reader_when_the_crop_is_refused(tmp_path, monkeypatch, kw):
+    """A refusal between opening the reader and opening the writer leaves no handle of the source open, and no output file."""
+    src, dst = tmp_path / "in.y4m", tmp_path / "out.y4m"
+    with yuv.Y4MWriter(src, FMT, 25) as wr:
+        wr.write(SHOT_A[0])
+    opened = []
+
+    def tracking_open(*a, **k):
+        opened.append(open(*a, **k))
+        return opened[-1]
+    monkeypatch.setattr(yuv, "open", tracking_open, raising=False)
+    with pytest.raises(ValueError, match="does not fit"):
+        yuv.interpolate_y4m(src, dst, Mean(), crop=(H + 2, W), **kw)
+    assert len(opened) == 1 and str(opened[0].name) == str(src) and opened[0].closed and not dst.exists()
+
+
 # ------------------------------------------------------------------------------------------------ ABI
 def test_yuv_abi_is_declared_exported_and_checks_on_the_host():
     hdr = open(os.path.join(CS.ROOT, "include", "atmvfi.h")).read()
@@ -412,10 +429,14 @@ def test_yuv_abi_is_declared_exported_and_checks_on_the_host():
     err = lib.atmvfi_last_error
 
     def dec(yuv_=P, H=64, W=96, depth=8, matrix=0, full=0, siting=0, d8=P, bgr=0, dst=P, Hp=64, Wp=96, pt=0, pl=0):
-        return lib.atmvfi_yuv420_to_rgb(yuv_, H, W, depth, matrix, full, siting, d8, bgr, dst, Hp, Wp, pt, pl, None)
+        rc = lib.atmvfi_yuv420_to_rgb(yuv_, H, W, depth, matrix, full, siting, d8, bgr, dst, Hp, Wp, pt, pl, None)
+        assert rc == -1 and err().startswith(b"yuv420_to_rgb: ")        # the shared checks, under the entry point's own name
+        return rc
 
     def enc(s8=P, bgr=0, src=None, Hp=64, Wp=96, pt=0, pl=0, H=64, W=96, matrix=0, full=0, siting=0, yuv_=P):
-        return lib.atmvfi_rgb_to_yuv420(s8, bgr, src, Hp, Wp, pt, pl, H, W, matrix, full, siting, yuv_, None)
+        rc = lib.atmvfi_rgb_to_yuv420(s8, bgr, src, Hp, Wp, pt, pl, H, W, matrix, full, siting, yuv_, None)
+        assert rc == -1 and err().startswith(b"rgb_to_yuv420: ")
+        return rc
     assert dec(yuv_=None) == -1 and b"null source" in err()
     assert dec(d8=None, dst=None) == -1 and b"both outputs are null" in err()
     assert dec(H=0) == -1 and b"at least 1" in err()
@@ -429,6 +450,8 @@ def test_yuv_abi_is_declared_exported_and_checks_on_the_host():
     assert dec(pt=-1) == -1 and b"smaller than the frame" in err()
     assert dec(dst=P + 2) == -1 and b"4-byte aligned" in err()
     assert dec(H=100000, W=100000, Hp=100000, Wp=100000) == -1 and b"too large" in err()        # 1.25e9 work items
+    assert dec(full=2) == -1 and b"full_range" in err()                                         # (asserted for its siblings before)
+    assert dec(d8=None, dst=P + 2) == -1 and b"4-byte aligned" in err()
     assert enc(yuv_=None) == -1 and b"null destination" in err()
     assert enc(s8=None, src=None) == -1 and b"exactly one" in err() and b"neither" in err()
     assert enc(s8=P, src=P) == -1 and b"exactly one" in err() and b"both" in err()
@@ -440,6 +463,9 @@ def test_yuv_abi_is_declared_exported_and_checks_on_the_host():
     assert enc(s8=None, src=P, Wp=95) == -1 and b"smaller than the frame" in err()
     assert enc(s8=None, src=P, pt=1) == -1 and b"smaller than the frame" in err()
     assert enc(s8=None, src=P + 1) == -1 and b"4-byte aligned" in err()
+    assert enc(W=0) == -1 and b"at least 1" in err()
+    assert enc(s8=None, src=P, pl=-4) == -1 and b"smaller than the frame" in err()
+    assert enc(s8=None, src=P, H=100000, W=100000, Hp=100000, Wp=100000) == -1 and b"too large" in err()
 
 
 def test_the_kernels_multiply_add_form_of_q_over_255_is_the_fp32_division():

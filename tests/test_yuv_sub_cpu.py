@@ -526,11 +526,15 @@ def test_sub_abi_is_declared_exported_and_checks_on_the_host():
 
     def dec(buf=P, H=64, W=96, depth=8, matrix=0, full=0, siting=0, sub=1, chroma=0, msb=0, pitch=0, cpitch=0, coff=0, keep=0, y0=0, x0=0, h=64,
             w=96, dst_u8=None, bgr=0, dst=P, Hp=64, Wp=96, pt=0, pl=0):
-        return lib.atmvfi_yuv_sub_decode(buf, H, W, depth, matrix, full, siting, sub, chroma, msb, pitch, cpitch, coff, keep, y0, x0, h, w, dst_u8,
-                                         bgr, dst, Hp, Wp, pt, pl, None)
+        rc = lib.atmvfi_yuv_sub_decode(buf, H, W, depth, matrix, full, siting, sub, chroma, msb, pitch, cpitch, coff, keep, y0, x0, h, w, dst_u8,
+                                       bgr, dst, Hp, Wp, pt, pl, None)
+        assert rc == -1 and err().startswith(b"yuv_sub_decode: " if sub else b"yuv_surface_decode: ")      # sub 0 IS the surface call
+        return rc
 
     def enc(src_u8=None, bgr=0, src=P, Hp=64, Wp=96, pt=0, pl=0, H=64, W=96, depth=8, matrix=0, full=0, siting=0, sub=1, chroma=0, msb=0, buf=P):
-        return lib.atmvfi_yuv_sub_encode(src_u8, bgr, src, Hp, Wp, pt, pl, H, W, depth, matrix, full, siting, sub, chroma, msb, buf, None)
+        rc = lib.atmvfi_yuv_sub_encode(src_u8, bgr, src, Hp, Wp, pt, pl, H, W, depth, matrix, full, siting, sub, chroma, msb, buf, None)
+        assert rc == -1 and err().startswith(b"yuv_sub_encode: " if sub else b"yuv_surface_encode: ")
+        return rc
     for sub in (1, 2):
         assert dec(sub=sub, buf=None) == -1 and b"yuv_sub_decode: null source" in err()
         assert dec(sub=sub, dst=None) == -1 and b"both outputs are null" in err()

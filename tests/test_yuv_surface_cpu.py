@@ -330,11 +330,15 @@ def test_surface_abi_is_declared_exported_and_checks_on_the_host():
 
     def dec(buf=P, H=64, W=96, depth=8, matrix=0, full=0, siting=0, chroma=1, msb=0, pitch=0, cpitch=0, coff=0, keep=0, y0=0, x0=0, h=64, w=96,
             dst_u8=None, bgr=0, dst=P, Hp=64, Wp=96, pt=0, pl=0):
-        return lib.atmvfi_yuv_surface_decode(buf, H, W, depth, matrix, full, siting, chroma, msb, pitch, cpitch, coff, keep, y0, x0, h, w, dst_u8,
-                                             bgr, dst, Hp, Wp, pt, pl, None)
+        rc = lib.atmvfi_yuv_surface_decode(buf, H, W, depth, matrix, full, siting, chroma, msb, pitch, cpitch, coff, keep, y0, x0, h, w, dst_u8,
+                                           bgr, dst, Hp, Wp, pt, pl, None)
+        assert rc == -1 and err().startswith(b"yuv_surface_decode: ")
+        return rc
 
     def enc(src_u8=None, bgr=0, src=P, Hp=64, Wp=96, pt=0, pl=0, H=64, W=96, depth=8, matrix=0, full=0, siting=0, chroma=1, msb=0, buf=P):
-        return lib.atmvfi_yuv_surface_encode(src_u8, bgr, src, Hp, Wp, pt, pl, H, W, depth, matrix, full, siting, chroma, msb, buf, None)
+        rc = lib.atmvfi_yuv_surface_encode(src_u8, bgr, src, Hp, Wp, pt, pl, H, W, depth, matrix, full, siting, chroma, msb, buf, None)
+        assert rc == -1 and err().startswith(b"yuv_surface_encode: ")
+        return rc
     assert dec(buf=None) == -1 and b"null source" in err()
     assert dec(dst=None) == -1 and b"both outputs are null" in err()
     assert dec(H=0) == -1 and b"at least 1" in err()
@@ -375,3 +379,9 @@ def test_surface_abi_is_declared_exported_and_checks_on_the_host():
     assert enc(Wp=95) == -1 and b"smaller than the frame" in err()
     assert enc(src=P + 1) == -1 and b"4-byte aligned" in err()
     assert enc(H=100000, W=100000, Hp=100000, Wp=100000) == -1 and b"too large" in err()
+    assert dec(pt=-1) == -1 and b"smaller than the window" in err()                             # (asserted for its siblings before)
+    assert dec(full=2) == -1 and b"full_range" in err()
+    assert enc(src=None, src_u8=None) == -1 and b"exactly one" in err() and b"neither" in err()
+    assert enc(src_u8=P) == -1 and b"both" in err()
+    assert enc(siting=3) == -1 and b"unknown siting" in err()
+    assert enc(pl=-4) == -1 and b"smaller than the frame" in err()
