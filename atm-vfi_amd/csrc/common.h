@@ -146,6 +146,15 @@ static inline bool sink_ok(const void* f32, int ld, int C, const void* hi, const
     if (hi && (plane_rows < rows || (reinterpret_cast<uintptr_t>(hi) & 15u) || (reinterpret_cast<uintptr_t>(lo) & 15u))) return false;
     return true;
 }
+namespace {
+// blocks of 256 lanes for a grid-stride loop over `total` elements (pointwise.hip, warp.hip)
+inline unsigned grid_for(long long total) {
+    long long b = (total + 255) / 256;
+    if (b > 8192) b = 8192;   // 256 CUs x 32 blocks, grid-stride the rest
+    if (b < 1) b = 1;
+    return (unsigned)b;
+}
+}
 
 // Per-column epilogue constants by LDS-DMA (used by the f16x3 engines; rationale in gemm_common.h): every wave issues exactly ONE
 // 4-byte-per-lane global_load_lds, piece (wave mod NPIECE) of the round_up(2*BN, 64) floats cst[c] = bias[co(c)],

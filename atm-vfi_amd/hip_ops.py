@@ -1180,7 +1180,8 @@ class HipOps:
 
     # ------------------------------------------------------------------ warps
     def _tiled_warp_ok(self, w, *planes) -> bool:
-        """The LDS-staged warps (`atmvfi_flow_warp_tiled`, `atmvfi_warp_blend_tiled`; bit-identical to the direct ones) take rows by
+        """The LDS-staged warps (csrc/warp.hip: `atmvfi_flow_warp_tiled`, `atmvfi_flow_warp_up2_tiled`, `atmvfi_warp_blend_tiled`; they share
+        the direct ones' taps, sampling and blend, so they are bit-identical to them) take rows by
         16-byte loads: W a multiple of 4, planes 16-byte aligned.  ``warp_tiles = False`` is the A/B switch."""
         return self.warp_tiles and w % 4 == 0 and all(t.data_ptr() % 16 == 0 for t in planes)
 

@@ -129,7 +129,7 @@ E2E_CASES = [
     # global branch moves content by tens of pixels (network_base.py:391-415, 457-485), the decoder flows reach 50-70 px
     # (:511-525) and taps leave the frame (flow_warp.py:26-60).  The manifest records flow|max| at every level's warp and the number
     # of 32 x 8 output tiles whose taps do not fit the tiled warps' 64 x 24 staged box (golden_util.tiled_warp_fallback_tiles: the
-    # gather fallback of pointwise.hip); tests/test_oracle_golden.py asserts both are non-trivial.
+    # gather fallback of warp.hip); tests/test_oracle_golden.py asserts both are non-trivial.
     ("base_384x576_g_large", "base", 1, 384, 576, True, False, "smooth", 26, 2, 4.0),
     ("lite_384x576_g_large", "lite", 1, 384, 576, True, False, "smooth", 27, 2, 4.0),
     ("base_1088x1920_g_large", "base", 1, 1088, 1920, True, False, "smooth", 28, 8, 4.0),   # BASELINE config C4's shape, strided store

@@ -47,7 +47,7 @@ def taps_out_of_frame(flow):
 
 def tiled_warp_fallback_tiles(flow, tile_w=32, tile_h=8, box_w=64, box_h=24):
     """How many 32 x 8 output tiles of a warp by ``flow`` [B,2,H,W] do NOT fit the LDS-staged source box of the tiled warp kernels
-    (atm-vfi_amd/csrc/pointwise.hip, box_add / box_get: bounding box of the tile's in-frame taps, x origin rounded down to a multiple
+    (atm-vfi_amd/csrc/warp.hip, box_add / box_get: bounding box of the tile's in-frame taps, x origin rounded down to a multiple
     of 4, at most 64 x 24 pixels) and therefore take the per-tile gather fallback.  Host restatement of the kernel's decision, used to
     certify that a large-motion fixture really exercises that path."""
     b, _, h, w = flow.shape

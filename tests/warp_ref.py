@@ -66,7 +66,7 @@ def reflect64(c: np.ndarray, size: int) -> np.ndarray:
 
 
 def delta(p: np.ndarray, size: int, reflection: bool = False) -> np.ndarray:
-    """Bound on the kernel's sampling coordinate minus the exact p, from ref_coord's arithmetic (pointwise.hip ``ref_coord``, and the
+    """Bound on the kernel's sampling coordinate minus the exact p, from ref_coord's arithmetic (warp.hip ``ref_coord``, and the
     same expression in flow_warp_ex_kernel):  g = 2 p / (size - 1) - 1,  ix = ((g + 1) / 2) (size - 1).  Five roundings (2 p and / 2
     are exact): the add x + flow (U |p|), the division (U |g + 1| in g, i.e. U |g + 1| (size - 1) / 2 in pixels), the -1 (U |g|), the
     +1 (U |g + 1|) and the multiplication (U |p|); with |g + 1| (size - 1) / 2 = |p| their first-order sum is
@@ -179,7 +179,7 @@ TAIL = 7.0            # what the emulated loads find past the end of the image t
 
 
 def _ref_coord32(p, size):
-    """ref_coord of pointwise.hip, one fp32 rounding per operation."""
+    """ref_coord of warp.hip, one fp32 rounding per operation."""
     hi = F32(size - 1)
     g = (F32(2.0) * p) / hi - F32(1.0)
     return g, ((g + F32(1.0)) / F32(2.0)) * hi
@@ -193,7 +193,7 @@ def _to_int32(f):
 
 
 def pad_coord32(c, size, mode, mutant=None):
-    """pad_coord of pointwise.hip (mode 0 zeros, 1 border, 2 reflection) on fp32 arrays."""
+    """pad_coord of warp.hip (mode 0 zeros, 1 border, 2 reflection) on fp32 arrays."""
     if mode == 0:
         return c
     hi = F32(size - 1)
@@ -208,7 +208,7 @@ def pad_coord32(c, size, mode, mutant=None):
 
 
 def taps32(flow: np.ndarray, padding: str = "zeros", mutant: str = None):
-    """make_taps (and flow_warp_ex_kernel's copy of it) on a whole flow field -> dict of [B,H,W] arrays: x0, y0 (int64), the four
+    """make_taps (flow_warp_ex_kernel calls it with its padding map) on a whole flow field -> dict of [B,H,W] arrays: x0, y0 (int64), the four
     weights (fp32), the four in-flags, and the mask of flow_warp_ex (the fp32 expression 2 p / (size - 1) - 1 inside [-1, 1])."""
     _, _, h, w = flow.shape
     flow = flow.astype(F32)
@@ -316,11 +316,11 @@ def pyramid32(frames: np.ndarray, mutant: str = None):
 
 
 # ------------------------------------------------------------------------------------------------- the staged-box rule of the tiled warps
-WT_W, WT_H, WB_W, WB_H = 32, 8, 64, 24       # pointwise.hip: constexpr int WT_W = 32, WT_H = 8; WB_W = 64, WB_H = 24
+WT_W, WT_H, WB_W, WB_H = 32, 8, 64, 24       # warp.hip: constexpr int WT_W = 32, WT_H = 8; WB_W = 64, WB_H = 24
 
 
 def staged_boxes(flow: np.ndarray):
-    """The decision of flow_warp_tiled_kernel / warp_blend_tiled_kernel per workgroup, restated from pointwise.hip:
+    """The decision of flow_warp_tiled_kernel / warp_blend_tiled_kernel per workgroup, restated from warp.hip:
       * ``tile_pixel``: workgroup (b, ty, tx) owns pixels x = 32 tx + (lane & 31), y = 8 ty + (lane >> 5), live when x < W && y < H;
       * ``box_add``: a lane counts when it is live and one of its four taps is inside (``any``); it contributes
         xlo = max(x0, 0), xhi = min(x0 + 1, W - 1), ylo = max(y0, 0), yhi = min(y0 + 1, H - 1) to the tile's extremes;
