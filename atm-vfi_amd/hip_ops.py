@@ -140,6 +140,9 @@ SIGNATURES = {
     "atmvfi_frame_signature": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_l, c_f]),
     "atmvfi_frame_difference_workspace_ints": (c_l, [c_i, c_i]),
     "atmvfi_frame_difference": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_l, c_f]),
+    "atmvfi_frame_borders_workspace_ints": (c_l, [c_i, c_i]),
+    "atmvfi_frame_borders": (c_i, [c_f, c_i, c_i, c_i, c_f, c_f, c_l, c_f]),
+    "atmvfi_frame_compose": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f, c_i, c_f]),
     "atmvfi_shutter_accumulate": (c_i, [c_f, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f]),
     "atmvfi_shutter_resolve": (c_i, [c_f, c_i, c_i, c_i, c_i, c_f, c_i, c_f]),
     "atmvfi_shutter_table": (c_i, [c_i, ctypes.POINTER(ctypes.c_uint16)]),
@@ -1385,6 +1388,57 @@ class HipOps:
         self._check(self.lib.atmvfi_frame_difference(_ptr(a), _ptr(b), sh, sw, int(bool(bgr)), int(y0), int(x0), h, w, _ptr(out),
                                                      _ptr(workspace), workspace.numel(), self._stream()), "frame_difference")
         return out
+
+    def frame_borders_workspace(self, h: int, w: int):
+        """A fresh int32 scratch tensor for ``frame_borders`` on an h x w frame (one per stream that computes borders)."""
+        n = self.lib.atmvfi_frame_borders_workspace_ints(int(h), int(w))
+        if n < 0:
+            raise ValueError(f"frame_borders: {self.lib.atmvfi_last_error().decode()}")
+        return torch.empty(n, dtype=torch.int32, device=self.device)
+
+    def frame_borders(self, src_u8, bgr: bool = False, out=None, workspace=None):
+        """The line maxima of a resident uint8 [H,W,3] frame: int32 [H + W] on the device = the largest luma of every row, then of
+        every column (include/atmvfi.h atmvfi_frame_borders; the bits of ``active.borders_numpy``).  ``out`` is written completely (a
+        new tensor when None).  ``workspace``: the call's scratch (``frame_borders_workspace``); None: one kept per (frame size,
+        stream) by this object.  Not part of a forward: never recorded into a launch plan."""
+        _u8_frame(src_u8, "frame_borders: source")
+        sh, sw = src_u8.shape[:2]
+        if out is None:
+            out = torch.empty(sh + sw, dtype=torch.int32, device=src_u8.device)
+        elif out.dtype != torch.int32 or out.numel() != sh + sw or not out.is_contiguous() or not out.is_cuda:
+            raise ValueError(f"frame_borders: out must be a contiguous CUDA int32 tensor of H + W = {sh + sw} words")
+        if workspace is None:
+            cache = self.__dict__.setdefault("_borders_workspaces", {})
+            key = (sh, sw, torch.cuda.current_stream(self.device).cuda_stream)
+            workspace = cache.get(key)
+            if workspace is None:
+                workspace = cache[key] = self.frame_borders_workspace(sh, sw)
+        elif workspace.dtype != torch.int32 or not workspace.is_contiguous() or not workspace.is_cuda:
+            raise ValueError("frame_borders: workspace must be a contiguous CUDA int32 tensor")
+        self._check(self.lib.atmvfi_frame_borders(_ptr(src_u8), sh, sw, int(bool(bgr)), _ptr(out), _ptr(workspace), workspace.numel(),
+                                                  self._stream()), "frame_borders")
+        return out
+
+    def frame_compose(self, dst_u8, border_u8, window, src=None, win_u8=None, pad_top: int = 0, pad_left: int = 0, bgr: bool = False):
+        """A produced window back into a full frame: ``dst_u8`` (uint8 [H,W,3]) = the bytes of ``border_u8`` (uint8 [H,W,3], the
+        caller's channel order) outside ``window`` = (y0, x0, h, w) and, inside, ``frame_f32_to_u8``'s pixel of ``src`` (fp32 planar
+        [3,Hp,Wp], the window at (pad_top, pad_left); BGR if ``bgr``) or the bytes of ``win_u8`` (uint8 [h,w,3], already in output
+        order) -- exactly one (include/atmvfi.h atmvfi_frame_compose; the bits of ``active.compose_numpy``).  ``dst_u8`` must not
+        alias ``border_u8``.  Not part of a forward: never recorded into a launch plan."""
+        _u8_frame(dst_u8, "frame_compose: dst")
+        _u8_frame(border_u8, "frame_compose: border", tuple(dst_u8.shape[:2]))
+        if (src is None) == (win_u8 is None):
+            raise ValueError("frame_compose: give exactly one of src and win_u8")
+        y0, x0, h, w = (int(v) for v in window)
+        hp = wp = 0
+        if src is not None:
+            _f32_canvas(src, "frame_compose: src")
+            hp, wp = src.shape[1:]
+        else:
+            _u8_frame(win_u8, "frame_compose: win_u8", (h, w))
+        sh, sw = dst_u8.shape[:2]
+        self._check(self.lib.atmvfi_frame_compose(_ptr(dst_u8), _ptr(border_u8), sh, sw, y0, x0, h, w, _ptr(src), hp, wp, int(pad_top),
+                                                  int(pad_left), _ptr(win_u8), int(bool(bgr)), self._stream()), "frame_compose")
 
     def shutter_accumulate(self, acc, src=None, src_u8=None, weight: int = 1, light: str = "linear", first: bool = False, pad_top: int = 0,
                            pad_left: int = 0, bgr: bool = False):

@@ -696,5 +696,7 @@ from .scene import SceneCuts, cut_statistics, signature_numpy  # noqa: E402,F401
 from .retime import Duplicates, difference_numpy, interpolate_video_retimed, retime_slots, sparse_levels, video_retimed  # noqa: E402,F401
 # a synthetic shutter (motion blur) for the rate conversion (``shutter=``; not in the reference): atm-vfi_amd/shutter.py
 from .shutter import Shutter, blend_numpy, shutter_slots  # noqa: E402,F401
+# the active picture of letterboxed video for ``interpolate_video_nx`` (``active=``; not in the reference): atm-vfi_amd/active.py
+from .active import ActiveArea, borders_numpy, compose_numpy  # noqa: E402,F401
 # planar YUV 4:2:0 frames for the loops above (``pixfmt=``) and Y4M files (not in the reference): atm-vfi_amd/yuv.py
 from .yuv import Format as YuvFormat, Y4MReader, Y4MWriter, interpolate_y4m  # noqa: E402,F401

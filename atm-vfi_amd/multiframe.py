@@ -154,12 +154,17 @@ class _Uploader:
     bytes follow into a pinned word array of the slot (``difference(slot)``).  Lifetimes: the previous upload's device frame is read on
     the copy stream, and the copy that next overwrites it is issued on that same stream later: stream order.  A frame that is never
     ``take``n (a dropped duplicate) records no ``free`` event, so with ``difference`` a slot's reuse also waits for its own ``ready``
-    event: its pinned bytes have left the host before they are overwritten."""
+    event: its pinned bytes have left the host before they are overwritten.
 
-    def __init__(self, dev, height: int, width: int, depth: int = 3, signature=None, pixfmt=None, deep: bool = False, difference=None):
+    ``borders=(ops, bgr)`` (the active picture, ``active.ActiveArea``): the frame's line maxima (``HipOps.frame_borders``) are computed
+    on the copy stream behind the copy, and their (H + W) * 4 bytes follow into a pinned word array of the slot, exactly as a
+    signature does; ``borders(slot)`` waits for that event.  ``stop_borders()`` ends it for the uploads still to come."""
+
+    def __init__(self, dev, height: int, width: int, depth: int = 3, signature=None, pixfmt=None, deep: bool = False, difference=None,
+                 borders=None):
         import torch
         self.torch, self.dev, self.h, self.w, self.depth = torch, dev, height, width, depth
-        self.sig, self.pixfmt, self.deep, self.dif = signature, pixfmt, bool(deep), difference
+        self.sig, self.pixfmt, self.deep, self.dif, self.bor = signature, pixfmt, bool(deep), difference, borders
         in_shape = (height, width, 3) if pixfmt is None else (pixfmt[1].frame_bytes,)
         need_rgb = not self.deep or signature is not None or difference is not None
         self.ring = [{"h": torch.empty(*in_shape, dtype=torch.uint8).pin_memory(),
@@ -182,6 +187,12 @@ class _Uploader:
                 s["dif_h_np"], s["dif_ready"] = s["dif_h"].numpy(), torch.cuda.Event()
             self.dif_ws = difference[0].frame_difference_workspace(*difference[1][2:])
             self.prev = None                          # the slot of the previous upload
+        if borders is not None:
+            for s in self.ring:
+                s["bor_d"] = torch.empty(height + width, dtype=torch.int32, device=dev)
+                s["bor_h"] = torch.empty(height + width, dtype=torch.int32).pin_memory()
+                s["bor_h_np"], s["bor_ready"] = s["bor_h"].numpy(), torch.cuda.Event()
+            self.bor_ws = borders[0].frame_borders_workspace(height, width)
         self.copy_in = torch.cuda.Stream(dev)
         self.issued = 0
 
@@ -218,6 +229,10 @@ class _Uploader:
                     slot["dif_h"].copy_(slot["dif_d"], non_blocking=True)
                     slot["dif_ready"].record(self.copy_in)
                 self.prev = slot
+            if self.bor is not None:
+                self.bor[0].frame_borders(slot["d"], bgr=self.bor[1], out=slot["bor_d"], workspace=self.bor_ws)
+                slot["bor_h"].copy_(slot["bor_d"], non_blocking=True)
+                slot["bor_ready"].record(self.copy_in)
         self.issued += 1
         return slot
 
@@ -230,6 +245,14 @@ class _Uploader:
         """The int32[258] difference of the frame in ``slot`` against the upload before it (a copy; not defined for the first upload)."""
         slot["dif_ready"].synchronize()
         return slot["dif_h_np"].copy()
+
+    def borders(self, slot) -> np.ndarray:
+        """The int32[H + W] line maxima of the frame in ``slot`` (a copy; the slot's words are rewritten by its next upload)."""
+        slot["bor_ready"].synchronize()
+        return slot["bor_h_np"].copy()
+
+    def stop_borders(self):
+        self.bor = None
 
     def take(self, slot, convert):
         """Run ``convert(device uint8 frame)`` on the current stream once the slot's copy has landed (``deep``: the device I420 bytes)."""
@@ -259,10 +282,16 @@ class _SegmentRunner:
     ``tta_merge``'s uint8 pixels, positions 0 and N and the copies of a cut segment from the pool's resident canvases -- and an output
     that closes is resolved (``atmvfi_shutter_resolve``) into an output ring entry (with an 8-bit ``out_fmt`` into a uint8 RGB buffer
     that ``rgb_to_yuv420`` encodes) and leaves by the same device -> host copy.  ``ops``: ``shutter._plan``'s, a close as
-    ``("close", m)`` or, for an output the caller serves itself, ``("drop", m)``."""
+    ``("close", m)`` or, for an output the caller serves itself, ``("drop", m)``.
+
+    ``window=(y0, x0, h, w)`` (the active picture, ``interpolate_video_nx(active=)``; no ``crop``, formats or blend with it): the network
+    runs on that window -- pool, plans and batch sizes as for a crop -- and the runner keeps two resident uint8 [H,W,3] BORDER frames,
+    the originals in positions 0 and N, copied where the source frame is converted and swapped with the positions.  A produced
+    position k leaves through ``frame_compose`` into a FULL-SIZE output ring entry: the prediction's window (with ``tta``:
+    ``tta_merge``'s uint8 window) inside, the bars of the nearer original (k <= N/2: position 0) outside."""
 
     def __init__(self, model, ops, dev, height, width, factor, crop, bgr, divisor, tta, max_batch, pool, out_fmt=None, deep_fmt=None,
-                 out_slots=None, batch_sizes=None, blend=None):
+                 out_slots=None, batch_sizes=None, blend=None, window=None):
         import torch
         from .host_io import InputPadder
         self.torch, self.model, self.ops, self.dev = torch, model, ops, dev
@@ -270,6 +299,14 @@ class _SegmentRunner:
         self.levels = nx_levels(factor)
         self.max_batch = max(1, min(int(max_batch), 16))
         self.y0, self.x0, self.h, self.w = centre_window(height, width, crop)
+        self.border = None
+        if window is not None:
+            if crop is not None or out_fmt is not None or deep_fmt is not None or blend is not None:
+                raise ValueError("_SegmentRunner: window goes with no crop, format or blend")
+            self.y0, self.x0, self.h, self.w = (int(v) for v in window)
+            self.border = [torch.empty(height, width, 3, dtype=torch.uint8, device=dev) for _ in range(2)]
+            self.border_of = {0: 0, factor: 1}       # position -> border frame; swapped with the positions
+            self.win_u8 = torch.empty(self.h, self.w, 3, dtype=torch.uint8, device=dev) if self.tta else None
         if divisor is None:
             self.pad_left = self.pad_top = 0
             self.hp, self.wp = self.h, self.w
@@ -299,6 +336,8 @@ class _SegmentRunner:
         # is 10-bit then)
         self.out_fmt, self.deep_fmt = out_fmt, deep_fmt
         out_shape = (self.h, self.w, 3) if out_fmt is None else (out_fmt.frame_bytes,)
+        if self.border is not None:
+            out_shape = (height, width, 3)
         n_out = factor - 1 if out_slots is None else max(1, min(int(out_slots), factor - 1))
         # blend = (light, entries) (``retime.interpolate_video_retimed(shutter=)``): the output ring holds the outputs one ``run`` can
         # close, and samples are gathered in int32 accumulators of the window's size.  They are allocated on demand, one per output that
@@ -354,6 +393,8 @@ class _SegmentRunner:
             if self.pools:
                 for p in self.pools:
                     p.invalidate(slot)
+            if self.border is not None:
+                self.border[self.border_of[pos]].copy_(d_u8, non_blocking=True)
         return convert
 
     def first(self, up: _Uploader, slot):
@@ -361,6 +402,12 @@ class _SegmentRunner:
         that may read many frames before its first segment is known (dropped duplicates) must not leave frame 0 in the upload ring."""
         with self.torch.cuda.device(self.dev):
             up.take(slot, self._convert_into(0))
+        self.have_first = self.fresh = True
+
+    def first_resident(self, d_u8):
+        """``first`` for a frame that is on the device already (a uint8 [H,W,3] tensor the current stream may read)."""
+        with self.torch.cuda.device(self.dev):
+            self._convert_into(0)(d_u8)
         self.have_first = self.fresh = True
 
     def _forward(self, k, lefts, rights):
@@ -424,6 +471,8 @@ class _SegmentRunner:
                 self.fresh = False
             elif self.have_first:
                 self.phys[0], self.phys[n] = self.phys[n], self.phys[0]      # frame AND tokens of slot N become slot 0's: no copy
+                if self.border is not None:
+                    self.border_of[0], self.border_of[n] = self.border_of[n], self.border_of[0]
             else:
                 up.take(slot_a, self._convert_into(0))
                 self.have_first = True
@@ -437,7 +486,14 @@ class _SegmentRunner:
 
             def to_ring(pos, pred, flip):
                 u8 = self.out_d[pos - 1 if index is None else index[pos]]
-                if self.deep_fmt is not None:
+                if self.border is not None:            # the window back into a full frame, the bars of the nearer original
+                    bars, win = self.border[self.border_of[0 if pos <= n // 2 else n]], (self.y0, self.x0, self.h, self.w)
+                    if self.tta:
+                        self.ops.tta_merge(pred, flip, out_u8=self.win_u8, pad_top=self.pad_top, pad_left=self.pad_left, bgr=self.bgr)
+                        self.ops.frame_compose(u8, bars, win, win_u8=self.win_u8)
+                    else:
+                        self.ops.frame_compose(u8, bars, win, src=pred, pad_top=self.pad_top, pad_left=self.pad_left, bgr=self.bgr)
+                elif self.deep_fmt is not None:
                     src = pred
                     if self.tta:                       # the fp32 average, then its encoding
                         self.ops.tta_merge(pred, flip, out=self.merged)
@@ -621,7 +677,7 @@ def _generic_segment(model, factor, crop_of, isBGR, divisor, tta, max_batch, loa
 
 def interpolate_video_nx(frames, model, factor: int = 4, time_interval: int = 1, crop: Optional[Tuple[int, int]] = None, isBGR: bool = True,
                          divisor: Optional[int] = 64, tta: bool = False, max_batch: int = 4, pool: bool = True, scene=None, pixfmt=None,
-                         keep_depth: bool = False):
+                         keep_depth: bool = False, active=None):
     """N-x slow motion over any iterable of uint8 [H,W,3] frames (davis-vid.py:88-135; decoding / encoding stays with the caller):
     per segment ``(f_i, f_{i+s})``, ``s = time_interval``, yields ``f_i`` and the frames at t = 1/N ... (N-1)/N, after the last segment
     its second frame once -- ``segments * N + 1`` frames.  Originals pass through bit-equal (their centre ``crop=(h, w)`` window when
@@ -651,12 +707,30 @@ def interpolate_video_nx(frames, model, factor: int = 4, time_interval: int = 1,
     the network sees q / 1023, no 8-bit round trip), produced frames are ``atmvfi_f32_to_yuv420p10`` of the fp32 prediction (with
     ``tta``: of the fp32 average) and leave as 1-D uint16 arrays of ``pixfmt.cropped(h, w)``; deeper levels consume the unrounded
     prediction as always.  The resident uint8 RGB frame is made only when ``scene`` needs its signature: signatures, and so cut
-    decisions, are those of the 8-bit path.  A model without the HIP backend does the same with the numpy twins."""
+    decisions, are those of the 8-bit path.  A model without the HIP backend does the same with the numpy twins.
+
+    ``active`` (an ``active.ActiveArea`` or a fixed even window ``(y0, x0, h, w)``; default None: the loop as above; not with ``crop``
+    or ``pixfmt``: ``ValueError``): the network runs on the active picture of letterboxed video.  Before its first output the loop
+    reads frames from ``frames`` until the policy has seen enough (``probe`` decided frames, ``patience`` frames, the stream's end),
+    keeps them on the host, locks the union of their rects as the window and replays them.  A window that gains nothing under
+    ``divisor`` is the whole frame: the loop as above.  Else every uploaded frame gets its line maxima on the copy stream
+    (``HipOps.frame_borders``), the network runs at the window's padded size, and a produced position k is the prediction's window
+    composed (``HipOps.frame_compose``) into a full-size frame with the bars of the nearer original (k <= N/2: the first).  Originals
+    pass through as the caller's own arrays; ``scene`` works on the whole frame as before.  A frame with a non-bar line outside the
+    window ends it: from the segment that ends at that frame on, the loop runs on the whole frame for the rest of the stream.  With
+    ``time_interval`` > 1 the frames that are not uploaded are not examined.  A tuple is never probed nor checked.
+    ``active.window`` / ``.probed`` / ``.fallback_at`` / ``.stats`` hold the run's record."""
     from .host_io import _hip_ops_of
     from .scene import cut_fill, signature_numpy
     nx_levels(factor)
+    if active is not None and (crop is not None or pixfmt is not None):
+        raise ValueError("interpolate_video_nx: active does not go with " + ("crop" if crop is not None else "pixfmt") +
+                         " (the active picture is found on whole uint8 frames)")
     if scene is not None:
         scene.begin()
+    area = active if hasattr(active, "probe_stream") else None
+    if area is not None:
+        area.begin()
     it = iter(frames)
     first = next(it, None)
     if first is None:
@@ -675,8 +749,33 @@ def interpolate_video_nx(frames, model, factor: int = 4, time_interval: int = 1,
         crop_rgb, whole = crop_of, (h, w) == (H, W) and yuv.passes_through(pixfmt)     # (a padded yuv.Surface: originals lose the padding)
         crop_of = (lambda f: f) if whole else (lambda f: yuv.crop(f, pixfmt, y0, x0, h, w))          # of the caller's I420 frames
     ops, dev = _hip_ops_of(model)
-    if ops is None or not hasattr(ops, "pool_blocks"):
-        if pixfmt is not None and deep:
+    generic = ops is None or not hasattr(ops, "pool_blocks")
+    win = None                                       # the active window, when the loop runs on one
+    if active is not None:
+        from . import active as _active
+        if generic:
+            profile_of = lambda f: _active.borders_numpy(f, bgr=isBGR)
+        else:
+            def profile_of(f):
+                import torch
+                with torch.cuda.device(dev):
+                    return ops.frame_borders(torch.from_numpy(np.ascontiguousarray(f)).to(dev), bgr=bool(isBGR)).cpu().numpy()
+        if area is None:
+            win = _active.fixed_window(active, H, W)
+        else:
+            if int(time_interval) < 1:
+                raise ValueError(f"time_interval must be >= 1, got {time_interval!r}")
+            need = 16 if getattr(model, "global_motion", True) else 8
+            held = area.probe_stream(_chain(first, it), H, W, divisor, need, int(time_interval), profile_of)
+            it = _chain_all(held[1:], it)            # the probed frames are replayed: the loop uploads them again
+            win = area.window
+        if win == (0, 0, H, W):                      # nothing gained: the plain path
+            win = area = None
+    if generic:
+        watch = None
+        if win is not None:
+            seg, watch = _active_generic_segment(model, factor, win, isBGR, divisor, tta, max(1, int(max_batch)), area, profile_of, (H, W))
+        elif pixfmt is not None and deep:
             seg = _generic_segment(model, factor, None, False, divisor, tta, max(1, int(max_batch)),
                                    load=lambda f: yuv.decode_numpy_f32(f, pixfmt, window=(y0, x0, h, w)),
                                    store=lambda p: yuv.encode_numpy(p, out_fmt))
@@ -705,25 +804,43 @@ def interpolate_video_nx(frames, model, factor: int = 4, time_interval: int = 1,
                 if scene.judge(sig_a, sig_b, h, w):
                     return cut_fill(crop_of(a), crop_of(b), factor)
                 return forward_segment(a, b)
-        for f in nx_sequence(_chain(first, it), lambda a, b: seg(a, b), factor, time_interval):
+        each = (lambda a, b: seg(a, b)) if watch is None else (lambda a, b: (watch(a, b), seg(a, b))[1])      # (cut segments are watched too)
+        for f in nx_sequence(_chain(first, it), each, factor, time_interval):
             if pixfmt is not None:
                 yield crop_of(f) if (not whole and f.size == pixfmt.frame_samples) else f       # originals are cropped here
             else:
                 yield f if f.shape[:2] == (h, w) else crop_of(f)
         return
-    runner = _SegmentRunner(model, ops, dev, H, W, factor, crop, isBGR, divisor, tta, max_batch,
-                            pool and hasattr(model, "forward_pooled"), out_fmt=out_fmt,
-                            deep_fmt=pixfmt if (pixfmt is not None and deep) else None)
+    make_runner = lambda window: _SegmentRunner(model, ops, dev, H, W, factor, crop, isBGR, divisor, tta, max_batch,
+                                                pool and hasattr(model, "forward_pooled"), out_fmt=out_fmt,
+                                                deep_fmt=pixfmt if (pixfmt is not None and deep) else None, window=window)
+    runner = make_runner(win)
     up = _Uploader(dev, H, W, signature=None if scene is None else (ops, (y0, x0, h, w), bool(isBGR)),
-                   pixfmt=None if pixfmt is None else (ops, pixfmt), deep=pixfmt is not None and deep)
-    state = {"first": True, "sig": None}
+                   pixfmt=None if pixfmt is None else (ops, pixfmt), deep=pixfmt is not None and deep,
+                   borders=None if (win is None or area is None) else (ops, bool(isBGR)))
+    state = {"first": True, "sig": None, "seg": 0, "watch": win is not None and area is not None}
 
     def segment(fa, fb):
         # enqueue this segment; deliver it at once (the order generator wants its frames now).  The upload of fb was started when it was
         # read from the source, one segment ahead, by `ahead()` below.
+        nonlocal runner
         sa = uploads.popleft() if state["first"] else None
         state["first"] = False
         sb = uploads.popleft()
+        state["seg"] += 1
+        if state["watch"]:
+            # the line maxima were enqueued with the uploads, as the signatures are
+            bad = [area.check(up.borders(s), H, W) for s in (sa, sb) if s is not None]
+            if any(bad):
+                # back to the whole frame for the rest of the stream.  This segment's first frame is position N of the windowed
+                # runner's last segment: its border frame is the resident uint8 copy the new runner converts again
+                area.fallback_at, state["watch"] = state["seg"] - 1, False
+                up.stop_borders()
+                resident = None if sa is not None else runner.border[runner.border_of[factor]]
+                runner.close()
+                runner = make_runner(None)
+                if resident is not None:
+                    runner.first_resident(resident)
         if scene is not None:
             # both signatures were enqueued with their uploads, fb's one segment ago: in steady state the event has long completed
             if sa is not None:
@@ -767,6 +884,36 @@ def _chain(first, it):
     yield first
     for f in it:
         yield f
+
+
+def _chain_all(held, it):
+    for f in held:
+        yield f
+    for f in it:
+        yield f
+
+
+def _active_generic_segment(model, factor, window, isBGR, divisor, tta, max_batch, area, profile_of, size):
+    """``(segment, watch)`` of the active picture for a model without the HIP backend: the forwards on ``window`` of the frames, every
+    produced window composed into a full frame with the bars of the nearer original (``active.compose_numpy``); ``watch(a, b)``
+    (``area`` given: called once per segment, cut or not) examines the frames the device path uploads and, at a violation, switches
+    ``segment`` to the whole frame for good.  ``area=None`` (a fixed window): ``watch`` is None."""
+    from .active import compose_numpy
+    y0, x0, h, w = window
+    inner = _generic_segment(model, factor, lambda f: np.ascontiguousarray(f[y0:y0 + h, x0:x0 + w]), isBGR, divisor, tta, max_batch)
+    whole = _generic_segment(model, factor, lambda f: f, isBGR, divisor, tta, max_batch)
+    st = {"on": True, "seg": 0}
+
+    def segment(a, b):
+        if not st["on"]:
+            return whole(a, b)
+        return [compose_numpy(a if k <= factor // 2 else b, window, win_u8=m) for k, m in enumerate(inner(a, b), 1)]
+
+    def watch(a, b):
+        st["seg"] += 1
+        if st["on"] and any([area.check(profile_of(f), *size) for f in ((a, b) if st["seg"] == 1 else (b,))]):
+            area.fallback_at, st["on"] = st["seg"] - 1, False
+    return segment, (None if area is None else watch)
 
 
 def inference_nx(img0, img1, model, factor: int = 4, isBGR: bool = True, divisor: Optional[int] = 64, tta: bool = False) -> List[np.ndarray]:

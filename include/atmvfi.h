@@ -487,6 +487,32 @@ int64_t atmvfi_frame_difference_workspace_ints(int h, int w);
 int atmvfi_frame_difference(const void* a, const void* b, int H, int W, int bgr, int y0, int x0, int h, int w, int32_t* out /*[258]*/,
                             int32_t* workspace, int64_t workspace_ints, void* stream);
 
+/* Active picture of letterboxed video in the N-x loop (active.hip; ABI 0.21; atm-vfi_amd/active.py holds the policy and the host twins
+ * borders_numpy / compose_numpy; per-pixel model tests/cpu_active.py).  Nothing of the reference.
+ * atmvfi_frame_borders: one resident uint8 [H,W,3] frame (contiguous; BGR if `bgr`) -> int32 out[H + W] on the device:
+ *   luma       Y = (77 R + 150 G + 29 B + 128) >> 8 (the signature's);
+ *   out[y]     = the maximum of Y over row y;      out[H + x] = the maximum of Y over column x.
+ *   H, W >= 16, H * W fits int32 and the frame has at most 65535 row chunks (ATMVFI_EINVAL otherwise).  Any pointer alignment of src is
+ *   accepted; dword loads are used when src is 4-byte aligned and W is a multiple of 4.  Integer arithmetic only: both paths and any
+ *   reduction order give the same bits.  out (4-byte aligned) is written completely by the call: nothing is pre-zeroed and no global
+ *   atomics are used.  workspace: at least atmvfi_frame_borders_workspace_ints(H, W) int32 of scratch, the caller's (per-wave row
+ *   maxima and per-chunk column maxima, reduced by a second launch of the same call); the query returns -1 for a frame the call would
+ *   refuse.  Stream-ordered: two launches, no host synchronisation, no allocation.
+ * atmvfi_frame_compose: dst uint8 [H,W,3] = a produced window put back into a full frame.  Outside the window (y0, x0, h, w) -- h, w >=
+ *   1, inside the frame -- the bytes of `border`, a resident uint8 [H,W,3] frame in the caller's channel order, verbatim.  Inside, from
+ *   exactly one of: src, fp32 planar RGB [3,Hp,Wp] with the window at (pad_top, pad_left) -- atmvfi_frame_f32_to_u8's pixel (x * 255 in
+ *   fp32, round half to even, clamp, RGB -> BGR if `bgr`); win_u8, uint8 [h,w,3] already in output order (what atmvfi_tta_merge
+ *   writes; `bgr`, Hp, Wp, pad_* are not read).  dst must not overlap border (ATMVFI_EINVAL).  Only the bar region of border and the
+ *   window of src / win_u8 are read.  Any geometry and alignment; 12-byte RGB groups and 16-byte plane reads when dst, border and
+ *   win_u8 are 4-byte aligned, W, x0 and w multiples of 4 and, with src, src 16-byte aligned and Wp, pad_left multiples of 4.  Same bits
+ *   either way.  One launch. */
+int64_t atmvfi_frame_borders_workspace_ints(int H, int W);
+int atmvfi_frame_borders(const void* src, int H, int W, int bgr, int32_t* out /*[H + W]*/, int32_t* workspace, int64_t workspace_ints,
+                         void* stream);
+int atmvfi_frame_compose(void* dst /*uint8 [H,W,3]*/, const void* border /*uint8 [H,W,3]*/, int H, int W, int y0, int x0, int h, int w,
+                         const float* src /*[3,Hp,Wp] or NULL*/, int Hp, int Wp, int pad_top, int pad_left,
+                         const void* win_u8 /*uint8 [h,w,3] or NULL*/, int bgr, void* stream);
+
 /* Synthetic shutter for the retimed video loop (shutter.hip; ABI 0.18; atm-vfi_amd/shutter.py holds the definition -- which samples an
  * output integrates -- and the host twin blend_numpy).  Nothing of the reference.  A blurred output is the weighted mean of the uint8 RGB
  * pixels q_k of its samples, taken in the domain of a light table and brought back to the nearest code, per channel:
