@@ -31,8 +31,9 @@ from typing import Iterable, Iterator, List, Optional, Tuple
 
 import numpy as np
 
-from .multiframe import _SegmentRunner, _Uploader, _chain, _generic_segment, centre_window
+from .multiframe import centre_window
 from .scene import _bounds
+from .segments import DeviceBackend, HostBackend, chain, open_stream
 
 DIFF_WORDS = 258
 MAX_LEVELS = 6
@@ -230,147 +231,6 @@ class Duplicates:
 
 
 # ------------------------------------------------------------------------------------------------ the loop
-class _HostBackend:
-    """A model without the HIP backend: torch / numpy (``multiframe._generic_segment`` on the sparse schedule, ``difference_numpy``,
-    ``signature_numpy``)."""
-
-    def __init__(self, model, levels, window, crop_rgb, isBGR, divisor, tta, max_batch, pixfmt, out_fmt, deep, dedup):
-        self.n, self.levels, self.win, self.bgr, self.pixfmt, self.out_fmt, self.deep = 1 << levels, levels, window, isBGR, pixfmt, out_fmt, deep
-        self.dedup, self.prev_rgb = dedup, None
-        self.crop_rgb, self.light, self.gathered = crop_rgb, None, {}          # (the synthetic shutter: ``blended``)
-        if pixfmt is not None and deep:
-            from . import yuv
-            self.seg = _generic_segment(model, self.n, None, False, divisor, tta, max_batch,
-                                        load=lambda f: yuv.decode_numpy_f32(f, pixfmt, window=window),
-                                        store=lambda p: yuv.encode_numpy(p, out_fmt))
-        else:
-            self.seg = _generic_segment(model, self.n, crop_rgb, isBGR, divisor, tta, max_batch)
-
-    def _rgb(self, e):
-        """the uint8 [H,W,3] picture of a frame (an I420 frame: decoded once)"""
-        if self.pixfmt is None:
-            return e["f"]
-        if "rgb" not in e:
-            from . import yuv
-            e["rgb"] = yuv.decode_numpy(e["f"], self.pixfmt)
-        return e["rgb"]
-
-    def admit(self, e):
-        if self.pixfmt is not None:
-            self.pixfmt.check(e["f"], "interpolate_video_retimed")
-        if self.dedup is not None:
-            rgb = self._rgb(e)
-            if self.prev_rgb is not None:
-                e["diff"] = difference_numpy(self.prev_rgb, rgb, self.win, bgr=self.bgr)
-            self.prev_rgb = rgb
-
-    def first(self, e):
-        pass
-
-    def difference(self, e):
-        return e["diff"]
-
-    def signature(self, e):
-        from .scene import signature_numpy
-        return signature_numpy(self._rgb(e), self.win, bgr=self.bgr)
-
-    def segment(self, a, b, interior, cut):
-        if cut or not interior:
-            return {}
-        fa, fb = (a["f"], b["f"]) if (self.pixfmt is None or self.deep) else (self._rgb(a), self._rgb(b))
-        made = self.seg(fa, fb, levels=sparse_levels(interior, self.levels), emit=interior)
-        if self.pixfmt is not None and not self.deep:
-            from . import yuv
-            made = [yuv.encode_numpy(m, self.out_fmt) for m in made]
-        return dict(zip(interior, made))
-
-    def blended(self, a, b, ops, need, cut, tail):
-        """One record of ``shutter._plan`` (closes as ``("close", m)`` / ``("drop", m)``): the frames of its closes, in order --
-        ``shutter.blend_numpy`` of the uint8 RGB frames the loop would have emitted for the samples."""
-        n, made, out = self.n, {}, []
-        if need and not cut:
-            fa, fb = (a["f"], b["f"]) if self.pixfmt is None else (self._rgb(a), self._rgb(b))
-            made = dict(zip(need, self.seg(fa, fb, levels=sparse_levels(need, self.levels), emit=need)))
-        for op in ops:
-            if op[0] == "add":
-                p = op[2]
-                if 0 < p < n and not cut:
-                    frame = made[p]
-                else:
-                    frame = self.crop_rgb(self._rgb(a if (p == 0 or (p < n and p <= n // 2)) else b))
-                self.gathered.setdefault(op[1], []).append((frame, op[3]))
-            elif op[0] == "close":
-                from .shutter import blend_numpy
-                frames, weights = zip(*self.gathered.pop(op[1]))
-                frame = blend_numpy(frames, weights, self.light)
-                if self.pixfmt is not None:
-                    from . import yuv
-                    frame = yuv.encode_numpy(frame, self.out_fmt)
-                out.append(frame)
-            else:                                    # a reset, or an output the loop serves itself
-                self.gathered.pop(op[1], None)
-        return out
-
-    def close(self):
-        pass
-
-
-class _DeviceBackend:
-    """The HIP path: ``multiframe._Uploader`` (signatures and differences on the copy stream behind each upload) and
-    ``multiframe._SegmentRunner`` on the sparse schedule.  Every KEPT frame is converted into the pool once, when its segment runs; a
-    dropped frame is uploaded and compared and never converted.
-
-    The upload ring and its lifetimes.  Frame k's upload is issued when it is read; frame k - 1 is judged -- and, if kept, its segment
-    enqueued, which ``take``s its slot -- before frame k + 1 is read.  So when upload k + 1 is issued the slots still in use are k (the
-    next difference reads its device frame; its ``take`` is yet to come) and k - 1 (its ``take`` may be in flight: the ``free`` event).
-    Three slots would do; the ring has four.  A held-back duplicate at the end of the stream is ``take``n after the last upload: nothing
-    can overwrite it.  The stream's FIRST frame is the one frame whose segment may be many uploads away (its followers may all be
-    dropped): it is converted into pool position 0, and its signature read, when it is admitted (``first``)."""
-
-    def __init__(self, model, ops, dev, H, W, levels, window, crop, isBGR, divisor, tta, max_batch, pool, pixfmt, out_fmt, deep, scene,
-                 dedup, out_slots, blend=None):
-        self.levels, n = levels, 1 << levels
-        max_batch = max(1, min(int(max_batch), 16))
-        self.runner = _SegmentRunner(model, ops, dev, H, W, n, crop, isBGR, divisor, tta, max_batch, pool and hasattr(model, "forward_pooled"),
-                                     out_fmt=out_fmt, deep_fmt=pixfmt if deep else None, out_slots=out_slots,
-                                     batch_sizes=range(1, min(max_batch, max(1, n // 2)) + 1), blend=blend)
-        sig = (ops, window, bool(isBGR))
-        self.up = _Uploader(dev, H, W, depth=4 if dedup is not None else 3, signature=None if scene is None else sig,
-                            pixfmt=None if pixfmt is None else (ops, pixfmt), deep=deep, difference=None if dedup is None else sig)
-
-    def admit(self, e):
-        e["slot"] = self.up.upload(e["f"])
-
-    def first(self, e):
-        self.runner.first(self.up, e["slot"])
-
-    def difference(self, e):
-        return self.up.difference(e["slot"])
-
-    def signature(self, e):
-        return self.up.signature(e["slot"])
-
-    def segment(self, a, b, interior, cut):
-        if cut or not interior:                      # the frames take their places; no forward
-            self.runner.run(self.up, None, b["slot"], cut=True)
-            return {}
-        ring = self.runner.run(self.up, None, b["slot"], levels=sparse_levels(interior, self.levels), emit=interior)
-        return dict(zip(interior, self.runner.result(ring, len(interior))))
-
-    def blended(self, a, b, ops, need, cut, tail):
-        """``_HostBackend.blended`` on the device: the segment's sparse schedule is the union of its interior samples, every sample is
-        accumulated where it would have been converted, and what closes is resolved into the output ring (``_SegmentRunner``)."""
-        closes = sum(op[0] == "close" for op in ops)
-        if tail:
-            ring = self.runner.tail(ops)
-        else:
-            ring = self.runner.run(self.up, None, b["slot"], cut=cut, levels=sparse_levels(need, self.levels), blend=ops)
-        return self.runner.result(ring, closes) if closes else []
-
-    def close(self):
-        self.runner.close()
-
-
 def interpolate_video_retimed(frames, model, fps_in, fps_out, levels: int = 3, dedup: Optional[Duplicates] = None,
                               crop: Optional[Tuple[int, int]] = None, isBGR: bool = True, divisor: Optional[int] = 64, tta: bool = False,
                               max_batch: int = 4, pool: bool = True, scene=None, pixfmt=None, keep_depth: bool = False, report=None,
@@ -380,7 +240,7 @@ def interpolate_video_retimed(frames, model, fps_in, fps_out, levels: int = 3, d
     docstring defines -- the nearest of ``N = 2**levels`` positions of its segment.  Positions 0 and N are the originals and pass through
     as the caller's own arrays (their centre ``crop=(h, w)`` window when given), position N of a segment and position 0 of the next
     being the same frame; every output is yielded exactly once.  Only the recursion nodes that a segment's positions need are evaluated
-    (``sparse_levels``), level by level in batches of at most ``max_batch`` pairs on ``multiframe._SegmentRunner``; a segment without an
+    (``sparse_levels``), level by level in batches of at most ``max_batch`` pairs on ``segments._SegmentRunner``; a segment without an
     interpolated output (``fps_out < fps_in`` has many) runs no forward.  When a widened segment maps two outputs to one position, the
     second is a copy of the same produced frame.
 
@@ -436,32 +296,21 @@ def _retimed(frames, model, fi, fo, levels, dedup, crop, isBGR, divisor, tta, ma
     first = next(it, None)
     if first is None:
         return
-    H, W = first.shape[:2] if pixfmt is None else (pixfmt.height, pixfmt.width)
-    y0, x0, h, w = window = centre_window(H, W, crop)
-    whole = (h, w) == (H, W)
-    crop_rgb = (lambda f: f) if whole else (lambda f: np.ascontiguousarray(f[y0:y0 + h, x0:x0 + w]))
-    original, out_fmt, deep = crop_rgb, None, False
-    if pixfmt is not None:
-        from . import yuv
-        err = None if crop is None else yuv._origin_error("interpolate_video_retimed", pixfmt, y0, x0, "crop")      # (a multiple of the subsampling step)
-        if err is not None:
-            raise err
-        deep = bool(keep_depth) and pixfmt.depth == 10
-        isBGR, out_fmt = False, yuv.out_format(pixfmt, deep).cropped(h, w)
-        original = (lambda f: f) if (whole and yuv.passes_through(pixfmt)) else (lambda f: yuv.crop(f, pixfmt, y0, x0, h, w))
-    elif first.ndim != 3 or first.shape[2] != 3 or first.dtype != np.uint8:
+    st = open_stream(first, crop, pixfmt, keep_depth, isBGR, "interpolate_video_retimed")
+    if pixfmt is None and (first.ndim != 3 or first.shape[2] != 3 or first.dtype != np.uint8):
         raise ValueError(f"interpolate_video_retimed: expected uint8 [H,W,3] frames, got {first.dtype} {tuple(first.shape)}")
+    (h, w), original = st.window[2:], st.original
     ops, dev = _hip_ops_of(model)
+    common = dict(n=n, divisor=divisor, tta=tta, pixfmt=pixfmt, caller="interpolate_video_retimed")
     if ops is None or not hasattr(ops, "pool_blocks"):
-        be = _HostBackend(model, levels, window, crop_rgb, isBGR, divisor, tta, max(1, int(max_batch)), pixfmt, out_fmt, deep, dedup)
-        be.light = None if shutter is None else shutter.light
+        be = HostBackend(model, st, max_batch=max(1, int(max_batch)), dedup=dedup, light=None if shutter is None else shutter.light, **common)
     else:
         # distinct interpolated positions of one segment: its outputs, at most ceil(g fps_out / fps_in) of them, g <= max_run + 1
         span = 1 if dedup is None else dedup.max_run + 1
         per_segment = -((-span * fo.numerator * fi.denominator) // (fo.denominator * fi.numerator))
-        be = _DeviceBackend(model, ops, dev, H, W, levels, window, crop, isBGR, divisor, tta, max_batch, pool, pixfmt, out_fmt, deep, scene,
-                            dedup, out_slots=min(n - 1, per_segment),
-                            blend=None if shutter is None else (shutter.light, per_segment + 1))    # the outputs a segment can close
+        be = DeviceBackend(model, ops, dev, st, crop=crop, max_batch=max_batch, pool=pool, scene=scene is not None, dedup=dedup is not None,
+                           sparse=True, out_slots=min(n - 1, per_segment),
+                           blend=None if shutter is None else (shutter.light, per_segment + 1), **common)   # the outputs a segment can close
     ends, number = {}, itertools.count()             # kept frames by their number on the timeline, until their segments are done
     sig = {}                                         # signatures of segment ends that a later segment starts with
 
@@ -469,7 +318,7 @@ def _retimed(frames, model, fi, fo, levels, dedup, crop, isBGR, divisor, tta, ma
         """The indices of the kept frames.  Frame k is judged when frame k + 1 has been read (and its upload started: one frame ahead
         of the forwards); a duplicate that turns out to be the last frame is kept."""
         pending = None
-        for i, f in enumerate(_chain(first, it)):
+        for i, f in enumerate(chain(first, it)):
             e = {"i": i, "f": f}
             be.admit(e)
             if i == 0:

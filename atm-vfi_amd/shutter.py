@@ -211,6 +211,47 @@ def _plan(kept: Iterable[int], fi: Fraction, fo: Fraction, levels: int, shutter:
     yield {"j": j, "cut": False, "tail": True, "ops": ops, "need": []}
 
 
+class Exposures:
+    """The open outputs of a blended stream on the device (``segments._SegmentRunner`` executes ``_plan``'s operations on it): an
+    int32 accumulator [3,h,w] per output that is open.  They are allocated on demand, one per output that is open at the same time --
+    the level-ordered schedule visits a segment's samples out of time order, so every output a segment touches is open until the
+    segment ends -- returned to a free list when their output closes, and kept until the runner goes.  An fp32 sample is the padded
+    canvas (``pad_top`` / ``pad_left``), a uint8 sample the window itself."""
+
+    def __init__(self, ops, dev, h: int, w: int, light: str, pad_top: int = 0, pad_left: int = 0):
+        self.ops, self.dev, self.h, self.w, self.light, self.pad = ops, dev, h, w, light, (pad_top, pad_left)
+        self.accs, self.free = [], []                # the accumulators; the indices of those no output holds
+        self.open = {}                               # output -> [accumulator, samples and weight since the last reset]
+
+    def add(self, m: int, weight: int, src=None, src_u8=None):
+        a = self.open.get(m)
+        if a is None:
+            if not self.free:
+                import torch
+                self.accs.append(torch.empty(3, self.h, self.w, dtype=torch.int32, device=self.dev))
+                self.free.append(len(self.accs) - 1)
+            a = self.open[m] = [self.free.pop(), 0, 0]
+        pad = self.pad if src is not None else (0, 0)
+        self.ops.shutter_accumulate(self.accs[a[0]], src=src, src_u8=src_u8, weight=weight, light=self.light, first=a[1] == 0,
+                                    pad_top=pad[0], pad_left=pad[1])
+        a[1] += 1
+        a[2] += weight
+
+    def reset(self, m: int):
+        """Forget what output ``m`` has gathered (a scene cut); it keeps its accumulator."""
+        if m in self.open:
+            self.open[m][1:] = [0, 0]
+
+    def close(self, m: int):
+        """Output ``m`` is done: ``(accumulator, total weight)`` for ``shutter_resolve`` -- the accumulator goes back to the free list,
+        and stream order keeps it whole until the resolve has read it -- or None for an output that holds no sample."""
+        a = self.open.pop(m, None)
+        if a is None:
+            return None
+        self.free.append(a[0])
+        return (self.accs[a[0]], a[2]) if a[1] else None
+
+
 def shutter_slots(kept: Iterable[int], fps_in, fps_out, levels: int, shutter, cuts: Iterable[int] = ()) -> Iterator[Tuple[int, Tuple[int, int], List[Tuple[int, int, int]]]]:
     """The outputs of a rate conversion under a shutter, in time order, as ``(m, (j_m, p_m), [(j, p, weight), ...])``: the output's
     number, its ``retime_slots`` position and its sample set ``S_m`` in time order (the module's docstring has the definition).  ``cuts``:

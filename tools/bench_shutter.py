@@ -103,7 +103,7 @@ def loop(a):
     import pairs
     pkg = importlib.import_module("atm-vfi_amd")
     rt = importlib.import_module("atm-vfi_amd.retime")
-    mf = importlib.import_module("atm-vfi_amd.multiframe")
+    sg = importlib.import_module("atm-vfi_amd.segments")
     sh = importlib.import_module("atm-vfi_amd.shutter")
     host_io = importlib.import_module("atm-vfi_amd.host_io")
     dev = torch.device("cuda:0")
@@ -128,8 +128,9 @@ def loop(a):
         """shutter=None's backend on the same sparse schedule: the three positions of every segment leave for the host"""
         ops, _ = host_io._hip_ops_of(net)
         t0 = time.perf_counter()
-        be = rt._DeviceBackend(net, ops, dev, h, w, levels, mf.centre_window(h, w, None), None, True, 64, False, 4, True, None, None, False,
-                               None, None, out_slots=len(positions))
+        st = sg.open_stream(frames[0], None, None, False, True, "bench_shutter")
+        be = sg.DeviceBackend(net, ops, dev, st, n=1 << levels, crop=None, divisor=64, tta=False, max_batch=4, pool=True, sparse=True,
+                              out_slots=len(positions))
         try:
             entries = []
             for i, f in enumerate(frames):          # uploads one frame ahead of the segments, as the loop has them
