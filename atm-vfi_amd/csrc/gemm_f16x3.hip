@@ -10,13 +10,9 @@
 // are split while they are staged (registers -> two fp16 LDS planes); weights are pre-split.
 // LDS rows are 64 bytes with the ((row>>2)&1)<<1 slot swizzle; operands of the NEXT chunk are
 // fetched into registers before the MFMA phase and written to the other buffer after it.
-#include "common.h"
-#include "gemm_common.h"
+#include "gemm_plane.h"      // the helpers only (f16x8, LO_UNSCALE, swz64): this file's epilogue is its own
 
 #include <stdlib.h>
-
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 #ifdef ATMVFI_STAMP
 // Diagnostic build only (`make stamp`, tools/stamp_gemm.py): per-wave tick sums of the phases of the persistent loop.
@@ -30,9 +26,6 @@ extern "C" void atmvfi_debug_set_gemm_stamp_buffer(void* p) { g_gemm_stamp = (un
 namespace {
 
 using atmvfi::GemmDev;
-
-constexpr float LO_UNSCALE = 1.0f / 1024.0f;
-__device__ __forceinline__ int swz64(int row) { return ((row >> 2) & 1) << 1; }
 
 __device__ __forceinline__ void split8(const f32x4 a, const f32x4 b, f16x8& hi, f16x8& lo) {
     const f32x2 x[4] = {{a.x, a.y}, {a.z, a.w}, {b.x, b.y}, {b.z, b.w}};

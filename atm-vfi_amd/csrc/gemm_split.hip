@@ -14,8 +14,7 @@
 // [k-step][row][32] (atmvfi_pack_weight_split) -- so the 16 rows x 64 B of one DMA instruction are one contiguous KiB.
 // Per k-step: s_waitcnt vmcnt(6) (own pieces of this stage landed) -> s_barrier (everyone's landed, everyone is
 // done with the previous stage) -> DMA stage k+2 into the buffer of stage k-1 -> 16 ds_read_b128 + 48 MFMA.
-#include "common.h"
-#include "gemm_common.h"
+#include "gemm_plane.h"      // the LDS / DMA helpers only: this file's epilogue is its own (the yardstick)
 
 // The kernel of THIS file is the REFERENCE SCHEDULE of the plane-input GEMM: the first form of the engine, kept as the yardstick the
 // ping-pong kernels (gemm_pp.hip, gemm_duo.hip) are held to bit for bit (tests/test_gpu_ops.py::test_gemm_pp_matches_reference_schedule)
@@ -25,8 +24,6 @@
 #if defined(ATMVFI_REFSCHED) || defined(ATMVFI_STAMP) || defined(ATMVFI_ABLATE)
 #define ATMVFI_HAVE_REFSCHED 1
 #endif
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 #ifdef ATMVFI_STAMP
 // Diagnostic build only (`make stamp`, tools/stamp_split.py): shader-clock and wall-clock stamps around the k-loop.
@@ -40,19 +37,6 @@ extern "C" void atmvfi_debug_set_split_stamp_buffer(void* p) { g_split_stamp = (
 namespace {
 
 using atmvfi::GemmDev;
-
-constexpr float LO_UNSCALE = 1.0f / 1024.0f;
-
-__device__ __forceinline__ int swz64(int row) { return ((row >> 2) & 1) << 1; }
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-__device__ __forceinline__ void dma16(const _Float16* src, _Float16* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src, (lds_ptr_t)lds_wave_base, 16, 0, 0);
-}
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 // WGM x WGN wavefronts, each owning 64 rows x 64 columns (4 x 4 MFMA tiles, acc + cor); three LDS stages.
 //
@@ -167,19 +151,22 @@ __global__ __launch_bounds__(64 * WGM * WGN, 2) void gemm_split_kernel(const Gem
         wdst[i] = W_HI_OFF + (i * NW + wave) * 64 * 8;
     }
     const long long wstep = (long long)a.wrows * 32;      // halves per k-step of a weight plane
+    auto dma = [](const _Float16* src, _Float16* lds_wave_base) {       // (this kernel addresses in halves, dma16 in bytes)
+        dma16(reinterpret_cast<const unsigned char*>(src), reinterpret_cast<unsigned char*>(lds_wave_base));
+    };
     auto issue = [&](int kc, int buf) {
         _Float16* st = smem + buf * STAGE_HALVES;
 #pragma unroll
-        for (int i = 0; i < APT; ++i) dma16(a_src(i, kc), st + adst[i]);
+        for (int i = 0; i < APT; ++i) dma(a_src(i, kc), st + adst[i]);
 #pragma unroll
-        for (int i = 0; i < WPT; ++i) dma16(wsrc[i] + kc * wstep, st + wdst[i]);
+        for (int i = 0; i < WPT; ++i) dma(wsrc[i] + kc * wstep, st + wdst[i]);
     };
     // one third of a stage's pieces (PIECES == 6: A pieces 0-3, W pieces 0-1)
     auto issue_pair = [&](int kc, int buf, int p) {
         _Float16* st = smem + buf * STAGE_HALVES;
-        if (p == 0 && !SABL(8)) { dma16(a_src(0, kc), st + adst[0]); dma16(a_src(1, kc), st + adst[1]); }
-        if (p == 1 && !SABL(8)) { dma16(a_src(2, kc), st + adst[2]); dma16(a_src(3, kc), st + adst[3]); }
-        if (p == 2) { dma16(wsrc[0] + kc * wstep, st + wdst[0]); dma16(wsrc[1] + kc * wstep, st + wdst[1]); }
+        if (p == 0 && !SABL(8)) { dma(a_src(0, kc), st + adst[0]); dma(a_src(1, kc), st + adst[1]); }
+        if (p == 1 && !SABL(8)) { dma(a_src(2, kc), st + adst[2]); dma(a_src(3, kc), st + adst[3]); }
+        if (p == 2) { dma(wsrc[0] + kc * wstep, st + wdst[0]); dma(wsrc[1] + kc * wstep, st + wdst[1]); }
     };
     // The DMA of one stage is spread over three items (an LDS-DMA instruction holds the wave's issue for 60-180 cycles)
     // and the two wave groups of a SIMD (waves 0-3 / 4-7) take different items, so one group's MFMAs cover the other's
@@ -229,9 +216,9 @@ __global__ __launch_bounds__(64 * WGM * WGN, 2) void gemm_split_kernel(const Gem
     next_k();
     if (nk > 2) issue(2, 2);
     next_k();                                   // (tap, chunk) of k-step 3, the first one issued inside the loop
-    if (nk > 2) wait_vmcnt<2 * PIECES>();
-    else if (nk > 1) wait_vmcnt<PIECES>();
-    else wait_vmcnt<0>();
+    if (nk > 2) wait_vm<2 * PIECES>();
+    else if (nk > 1) wait_vm<PIECES>();
+    else wait_vm<0>();
     __builtin_amdgcn_s_barrier();
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -262,8 +249,8 @@ __global__ __launch_bounds__(64 * WGM * WGN, 2) void gemm_split_kernel(const Gem
         __builtin_amdgcn_sched_barrier(0);
         if (more) {
             // stage kc+1: own DMA pieces landed (stage kc+2 may still be in flight); own reads of stage kc complete
-            if (kc + 2 < nk) wait_vmcnt<PIECES>();
-            else wait_vmcnt<0>();
+            if (kc + 2 < nk) wait_vm<PIECES>();
+            else wait_vm<0>();
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_sched_barrier(0);

@@ -1344,6 +1344,13 @@ PP_CASES = [
     ("conv", (2, 300, 400), 48, 96, dict(stride=2, k=3, dil=1)),      # strided 3x3, 18 k-steps, taps outside the image
     ("conv", (1, 270, 480), 64, 160, dict(stride=1, k=1, dil=1)),     # 1x1 (2 k-steps), fp32 out + sink
     ("conv", (2, 260, 300), 32, 96, dict(stride=4, k=3, dil=2)),      # stride 4, dilation 2
+    # small ones for the GENERIC row loop of the shared epilogue (gemm_plane.h store_rows; everything above has Cout % 4 == 0 or is a
+    # deconv with W >= 4 and takes a fast form); own ids: two of them repeat an (op, Cin, Cout) from above.
+    # (Its ragged-residual copy is not reachable from here: ("linear", 700, 64, 198, dict(bias=True, res=True)) is refused by
+    # atmvfi_gemm before any launch -- a residual needs res_ld % 4 == 0, and this test's residual is a contiguous [M, Cout].)
+    pytest.param(("linear", 700, 64, 198, dict(bias=True, res=False)), id="linear_64to198_generic"),      # Cout & 3 != 0, fp32 rows
+    pytest.param(("conv", (1, 40, 52), 32, 50, dict(stride=2, k=3, dil=1)), id="conv_32to50_generic"),    # plane sink, ragged width
+    pytest.param(("deconv", (1, 40, 3), 64, 32, dict()), id="deconv_64to32_w3"),                          # W < 4: not the stepped form
 ]
 
 
