@@ -15,7 +15,14 @@ int32[H + W] --
 Policy, all integer (``rect_of`` / ``lock`` / ``violates``): a line is a BAR LINE iff its maximum is <= ``peak``; a frame's rect is what
 the runs of bar lines from the four edges leave, snapped outward to even; the window of a run is the union of the rects of the first
 ``probe`` decided frames, used only if its padded area is smaller than the whole frame's; a later frame with a non-bar line outside
-the window is a violation."""
+the window is a violation.
+
+YUV streams (``pixfmt=``; ``yuv_borders_numpy`` / ``yuv_compose_numpy`` here, ``atmvfi_yuv_borders`` / ``atmvfi_yuv_compose`` on the device,
+the same bits).  The line maxima are those of the LUMA plane's sample values, as stored (``msb``: ``>> 6``): a maximum commutes with
+every monotone map, so nothing is converted per sample and the threshold is mapped once per stream instead -- ``bar_code(fmt, peak)``
+is the sample code of the 8-bit full-range level ``peak``, and ``rect_of`` / ``violates`` / ``probe_stream`` / ``check`` take it as their
+threshold.  Chroma is not examined: dark saturated content in a bar counts as bar, which is harmless because the bars of every
+produced frame are the nearer original's own samples, moved plane by plane and never converted."""
 from __future__ import annotations
 
 from typing import Callable, Iterable, List, Optional, Sequence, Tuple
@@ -88,6 +95,61 @@ def compose_numpy(border: np.ndarray, window, src: Optional[np.ndarray] = None, 
     q = np.rint(src[:, pad_top:pad_top + h, pad_left:pad_left + w] * np.float32(255.0))
     q = np.clip(np.nan_to_num(q, nan=0.0), 0, 255).astype(np.uint8).transpose(1, 2, 0)
     out[y0:y0 + h, x0:x0 + w] = q[:, :, ::-1] if bgr else q
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ YUV twins
+def bar_code(fmt, peak: int) -> int:
+    """The luma sample code of ``fmt`` (a ``yuv.Format`` or ``Surface``) that the 8-bit full-range level ``peak`` maps to: ``peak``
+    itself for full range (8-bit only); limited range at depth d ``(16 << (d - 8)) + (peak * (219 << (d - 8))) // 255`` -- 36 at 8 and
+    146 at 10 bits for the default 24.  A line is a bar line iff its largest luma sample is <= this."""
+    peak = int(peak)
+    if fmt.full_range:
+        return peak
+    up = fmt.depth - 8
+    return (16 << up) + (peak * (219 << up)) // 255
+
+
+def yuv_borders_numpy(buf, fmt) -> np.ndarray:
+    """int32[H + W] line maxima of the luma plane of one frame of ``fmt`` (a ``yuv.Format`` or ``Surface``) on the host: the largest
+    sample value (``msb``: ``>> 6``) of every row, then of every column -- what ``atmvfi_yuv_borders`` computes, bit for bit."""
+    H, W = fmt.height, fmt.width
+    if H < 16 or W < 16:
+        raise ValueError(f"yuv_borders_numpy: the frame must be at least 16 x 16 (got {H} x {W})")
+    Y = fmt.planes(buf)[0]
+    if getattr(fmt, "msb", False):
+        Y = Y >> 6
+    return np.concatenate([Y.max(axis=1), Y.max(axis=0)]).astype(np.int32)
+
+
+def yuv_window_error(who: str, fmt, window):
+    """The window rule of ``yuv_compose``: origin on multiples of the subsampling step per axis, end on a multiple or at the frame's
+    edge (an odd frame's last chroma row or column covers one luma line) -- every chroma sample is the window's or the bars'.  None,
+    or the ``ValueError``."""
+    y0, x0, h, w = window
+    (sy, sx), H, W = fmt.steps, fmt.height, fmt.width
+    if y0 % sy or x0 % sx or ((y0 + h) % sy and y0 + h != H) or ((x0 + w) % sx and x0 + w != W):
+        return ValueError(f"{who}: the window {h} x {w} at ({y0}, {x0}) must begin and end on multiples of the subsampling step {(sy, sx)} "
+                          f"or at the frame's edge")
+    return None
+
+
+def yuv_compose_numpy(border, fmt, window, win_frame) -> np.ndarray:
+    """One TIGHT frame of ``fmt`` (1-D; a ``Surface``'s without its padding): the sample values of ``border`` (a frame of ``fmt``)
+    outside ``window`` = (y0, x0, h, w) and those of ``win_frame``, a frame of the tight ``fmt.cropped(h, w)``, inside -- what
+    ``atmvfi_yuv_compose`` writes when ``win_frame`` is the window's encode, bit for bit."""
+    from . import yuv
+    H, W = fmt.height, fmt.width
+    y0, x0, h, w = _window(window, H, W, "yuv_compose_numpy")
+    err = yuv_window_error("yuv_compose_numpy", fmt, (y0, x0, h, w))
+    if err is not None:
+        raise err
+    tight = yuv.as_surface(fmt).tight()
+    out = yuv.repack(border, fmt, tight)
+    (sy, sx), sub = fmt.steps, tight.cropped(h, w)
+    cy, cx = y0 // sy, x0 // sx
+    for dst, src, (oy, ox) in zip(tight.planes(out), sub.planes(np.asarray(win_frame)), ((y0, x0), (cy, cx), (cy, cx))):
+        dst[oy:oy + src.shape[0], ox:ox + src.shape[1]] = src
     return out
 
 
@@ -175,22 +237,28 @@ class ActiveArea:
 
     def begin(self):
         """Start of a run: forget the previous one."""
+        self.code = self.peak                        # the run's threshold: ``peak``, or its sample code on a YUV stream (``bar_code``)
         self.window: Optional[Window] = None
         self.probed = 0
         self.fallback_at: Optional[int] = None
         self.stats: List[Rect] = []
 
     def probe_stream(self, frames: Iterable, H: int, W: int, divisor: Optional[int], need: int, step: int,
-                     profile_of: Callable[[np.ndarray], np.ndarray]) -> list:
+                     profile_of: Callable[[np.ndarray], np.ndarray], code: Optional[int] = None, accept: Optional[Callable] = None) -> list:
         """Read frames from ``frames`` and lock ``.window``; returns the frames read, for the loop to replay.  Only every ``step``-th
-        frame (the ones the loop uploads) is examined; all count towards ``patience``."""
+        frame (the ones the loop uploads) is examined; all count towards ``patience``.  ``code``: the run's threshold in the units of
+        the profiles (default ``peak``; a YUV stream: ``bar_code``), which ``check`` keeps using; ``accept(frame)``: raises for a frame
+        that is not the stream's (default: uint8 [H,W,3])."""
+        self.code = self.peak if code is None else int(code)
         held, rects = [], []
         for f in frames:
             if len(held) % step == 0:
-                if getattr(f, "shape", None) != (H, W, 3) or f.dtype != np.uint8:
+                if accept is not None:
+                    accept(f)
+                elif getattr(f, "shape", None) != (H, W, 3) or f.dtype != np.uint8:
                     raise ValueError(f"interpolate_video_nx: expected uint8 [{H},{W},3] frames, got {getattr(f, 'dtype', None)} "
                                      f"{tuple(getattr(f, 'shape', ()))}")
-                r = rect_of(profile_of(f), H, W, self.peak)
+                r = rect_of(profile_of(f), H, W, self.code)
                 self.stats.append(r)
                 if decided(r, H, W):
                     rects.append(r)
@@ -203,8 +271,8 @@ class ActiveArea:
 
     def check(self, profile, H: int, W: int) -> bool:
         """Record a frame of the main loop; True when it violates the locked window."""
-        self.stats.append(rect_of(profile, H, W, self.peak))
-        return violates(profile, self.window, H, W, self.peak)
+        self.stats.append(rect_of(profile, H, W, self.code))
+        return violates(profile, self.window, H, W, self.code)
 
     def __repr__(self):
         return f"ActiveArea(peak={self.peak}, probe={self.probe}, patience={self.patience})"

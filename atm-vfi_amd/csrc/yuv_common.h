@@ -42,6 +42,13 @@
 
 #include "common.h"
 
+namespace atmvfi {
+// yuv_encode.hip, for active.hip (atmvfi_yuv_compose): the encode kernel with a destination origin inside a larger tight frame
+int yuv_encode_window(const char* me, void* frame, int H, int W, int y0, int x0, int h, int w, int depth, int matrix, int full_range,
+                      int siting, int subsampling, int chroma, int msb, const void* src_u8, const float* src, int Hp, int Wp, int pad_top,
+                      int pad_left, void* stream);
+}  // namespace atmvfi
+
 namespace {
 
 struct alignas(4) U32x2 {

@@ -216,13 +216,20 @@ __global__ __launch_bounds__(256) void yuv420_encode_kernel(const EncArgs a) {
 template <int SRC, bool IL, bool MSB, int SUB, bool LEFT>
 constexpr bool encode_instance = (!MSB || SRC == SRC_F1023) && (SUB == 0 || (!IL && !MSB)) && !(SUB == 2 && LEFT);
 
+// Where an encode writes: the TIGHT frame at `yuv` -- the picture's own (FH x FW = H x W, origin 0) or, for atmvfi_yuv_compose, a larger
+// frame in which the picture is the window at (y0, x0): the kernel gets the window's first luma sample as its base and the chroma
+// origins relative to it, with the FRAME's row strides.  Nothing else of the kernel knows about the frame.
+struct Place {
+    int FH, FW, y0, x0;
+};
+
 // Launches the encode of a checked frame; exactly one of src_u8 and src is given.  The destination is tight: chroma 0 is the packed
 // planar frame, 1 / 2 the interleaved surface (U / V first); msb: 10-bit samples stored in the upper bits; sub: 1 4:2:2, 2 4:4:4.
 // The run-time properties select the instance in this one place: the source is fp32 x 1023 at depth 10, else fp32 x 255 or uint8;
 // msb samples come from the 10-bit source alone, 4:2:2 / 4:4:4 are planar LSB, and 4:4:4 has no siting.
 void launch_encode(const Coeffs& c, int yo, int depth, const void* src_u8, int bgr, const float* src, int Hp, int Wp, int pad_top, int pad_left,
-                   int H, int W, int siting, void* yuv, void* stream, int chroma, bool msb, int sub) {
-    const int ch = chroma_rows(H, sub), cw = chroma_cols(W, sub), groups = groups_of(W);
+                   int H, int W, int siting, void* yuv, void* stream, int chroma, bool msb, int sub, const Place& at) {
+    const int ch = chroma_rows(H, sub), cw = chroma_cols(W, sub), groups = groups_of(W), b = depth == 10 ? 2 : 1;
     EncArgs a = {(const unsigned char*)src_u8, src_u8 && bgr ? 1 : 0, src, Hp, Wp, pad_top, pad_left, H, W, ch, cw};
     for (int k = 0; k < 3; ++k) {
         a.eY[k] = c.enc[0][k];
@@ -230,15 +237,22 @@ void launch_encode(const Coeffs& c, int yo, int depth, const void* src_u8, int b
         a.eV[k] = c.enc[2][k];
     }
     a.yo = yo;
-    a.yuv = (unsigned char*)yuv;
-    const Layout l = tight_layout(H, W, chroma, sub);
-    a.uoff = l.uoff + (chroma == 2 ? 1 : 0);
-    a.voff = chroma == 0 ? l.uoff + (long long)ch * cw : l.uoff + (chroma == 1 ? 1 : 0);
+    const Layout l = tight_layout(at.FH, at.FW, chroma, sub);
+    // the window's origin in samples: of the luma plane, and of a chroma plane (an interleaved column is two samples)
+    const long long yorg = (long long)at.y0 * l.ys + at.x0;
+    const long long corg = (long long)(sub == 0 ? at.y0 / 2 : at.y0) * l.cs + (sub == 2 ? at.x0 : at.x0 / 2) * (chroma ? 2 : 1);
+    const long long uabs = l.uoff + corg + (chroma == 2 ? 1 : 0);
+    const long long vabs = chroma == 0 ? l.uoff + corg + (long long)chroma_rows(at.FH, sub) * l.cs : l.uoff + corg + (chroma == 1 ? 1 : 0);
+    a.yuv = (unsigned char*)yuv + yorg * b;
+    a.uoff = uabs - yorg;
+    a.voff = vabs - yorg;
     a.ys = l.ys;
     a.cs = l.cs;
     a.vu = chroma == 2 ? 1 : 0;
     a.groups = groups;
-    const bool al = aligned4(yuv) && W % 4 == 0 && (src ? canvas_aligned(src, Wp, pad_left) : aligned4(src_u8));      // (tight: the layout follows)
+    // (a tight frame of its own with W % 4 == 0: the layout follows from the pointer; a window must also start on a group)
+    const bool al = aligned4(yuv) && W % 4 == 0 && (yorg * b) % 4 == 0 && layout_aligned(l.ys, l.cs, uabs, vabs, depth, chroma != 0, sub) &&
+                    (src ? canvas_aligned(src, Wp, pad_left) : aligned4(src_u8));
     const dim3 grid = yuv_grid((long long)pairs_of(H) * groups), block(256);
     dispatch_sub([&](auto SUB, auto AL, auto LEFT, auto D10, auto F32, auto IL, auto MSB) {
         constexpr int SRC = D10() ? SRC_F1023 : (F32() ? SRC_F255 : SRC_U8);
@@ -250,7 +264,7 @@ void launch_encode(const Coeffs& c, int yo, int depth, const void* src_u8, int b
 // The one host path of every encode entry point, under the caller's name `me`: the checks in one order, then the launch.  chroma / msb
 // describe the tight destination (both 0: the packed planar frame); sub 1 / 2 is checked by atmvfi_yuv_sub_encode (check_sub).
 int surface_encode(const char* me, int sub, const void* src_u8, int bgr, const float* src, int Hp, int Wp, int pad_top, int pad_left, int H, int W,
-                   int depth, int matrix, int full_range, int siting, int chroma, int msb, void* yuv, void* stream) {
+                   int depth, int matrix, int full_range, int siting, int chroma, int msb, void* yuv, void* stream, const Place* window = nullptr) {
     ATMVFI_REQUIRE(yuv, ATMVFI_EINVAL, "%s: null destination", me);
     ATMVFI_REQUIRE((src_u8 != nullptr) != (src != nullptr), ATMVFI_EINVAL, "%s: give exactly one of src_u8 and src (got %s)", me,
                    src_u8 ? "both" : "neither");
@@ -263,7 +277,7 @@ int surface_encode(const char* me, int sub, const void* src_u8, int bgr, const f
         if (const int rc = check_canvas(me, "src", "frame", src, H, W, Hp, Wp, pad_top, pad_left)) return rc;
     if (const int rc = check_items(me, (H + 1) / 2, groups_of(W), "a frame of", H, W)) return rc;
     launch_encode(depth == 10 ? kCoeffs10[matrix] : kCoeffs[matrix][full_range], depth == 10 ? 64 : (full_range ? 0 : 16), depth, src_u8, bgr, src, Hp,
-                  Wp, pad_top, pad_left, H, W, siting, yuv, stream, chroma, msb != 0, sub);
+                  Wp, pad_top, pad_left, H, W, siting, yuv, stream, chroma, msb != 0, sub, window ? *window : Place{H, W, 0, 0});
     return atmvfi::check_launch(me);
 }
 
@@ -296,4 +310,15 @@ extern "C" int atmvfi_yuv_sub_encode(const void* src_u8, int bgr, const float* s
     if (const int rc = check_sub("yuv_sub_encode", subsampling, siting, chroma, msb)) return rc;
     return surface_encode("yuv_sub_encode", subsampling, src_u8, bgr, src, Hp, Wp, pad_top, pad_left, H, W, depth, matrix, full_range, siting, chroma,
                           msb, yuv, stream);
+}
+
+// atmvfi_yuv_compose's window (active.hip has checked that it lies in the frame, on the subsampling's grid): the h x w picture as a
+// frame of the cropped format -- the checks and the kernel of atmvfi_yuv_sub_encode -- written at (y0, x0) of the tight H x W frame
+int atmvfi::yuv_encode_window(const char* me, void* frame, int H, int W, int y0, int x0, int h, int w, int depth, int matrix, int full_range,
+                              int siting, int subsampling, int chroma, int msb, const void* src_u8, const float* src, int Hp, int Wp,
+                              int pad_top, int pad_left, void* stream) {
+    if (const int rc = check_sub(me, subsampling, siting, chroma, msb)) return rc;
+    const Place at = {H, W, y0, x0};
+    return surface_encode(me, subsampling, src_u8, 0, src, Hp, Wp, pad_top, pad_left, h, w, depth, matrix, full_range, siting, chroma, msb, frame,
+                          stream, &at);
 }

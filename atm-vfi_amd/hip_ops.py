@@ -143,6 +143,9 @@ SIGNATURES = {
     "atmvfi_frame_borders_workspace_ints": (c_l, [c_i, c_i]),
     "atmvfi_frame_borders": (c_i, [c_f, c_i, c_i, c_i, c_f, c_f, c_l, c_f]),
     "atmvfi_frame_compose": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f, c_i, c_f]),
+    "atmvfi_yuv_borders_workspace_ints": (c_l, [c_i, c_i]),
+    "atmvfi_yuv_borders": (c_i, [c_f, c_i, c_i, c_i, c_i, c_l, c_f, c_f, c_l, c_f]),
+    "atmvfi_yuv_compose": (c_i, [c_f, c_f] + [c_i] * 9 + [c_l] * 3 + [c_i] * 4 + [c_f] + [c_i] * 4 + [c_f, c_f]),
     "atmvfi_shutter_accumulate": (c_i, [c_f, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f]),
     "atmvfi_shutter_resolve": (c_i, [c_f, c_i, c_i, c_i, c_i, c_f, c_i, c_f]),
     "atmvfi_shutter_table": (c_i, [c_i, ctypes.POINTER(ctypes.c_uint16)]),
@@ -1439,6 +1442,75 @@ class HipOps:
         sh, sw = dst_u8.shape[:2]
         self._check(self.lib.atmvfi_frame_compose(_ptr(dst_u8), _ptr(border_u8), sh, sw, y0, x0, h, w, _ptr(src), hp, wp, int(pad_top),
                                                   int(pad_left), _ptr(win_u8), int(bool(bgr)), self._stream()), "frame_compose")
+
+    def yuv_borders_workspace(self, h: int, w: int):
+        """A fresh int32 scratch tensor for ``yuv_borders`` on an h x w frame of either depth (one per stream that computes borders)."""
+        n = self.lib.atmvfi_yuv_borders_workspace_ints(int(h), int(w))
+        if n < 0:
+            raise ValueError(f"yuv_borders: {self.lib.atmvfi_last_error().decode()}")
+        return torch.empty(n, dtype=torch.int32, device=self.device)
+
+    def yuv_borders(self, buf, fmt_or_surface, out=None, workspace=None):
+        """The line maxima of the LUMA plane of one resident frame of ``fmt_or_surface`` (a ``yuv.Format`` or ``yuv.Surface``; ``buf`` its
+        bytes, a contiguous CUDA uint8 tensor, any alignment and pitch -- an uploaded surface in place): int32 [H + W] on the device = the
+        largest luma sample value of every row, then of every column (``msb``: ``>> 6``; include/atmvfi.h atmvfi_yuv_borders; the bits
+        of ``active.yuv_borders_numpy``).  Chroma is not read.  ``out`` is written completely (a new tensor when None).
+        ``workspace``: the call's scratch (``yuv_borders_workspace``); None: one kept per (frame size, stream) by this object.  Not part
+        of a forward: never recorded into a launch plan."""
+        if not hasattr(fmt_or_surface, "subsampling_id"):
+            raise ValueError(f"yuv_borders: a yuv.Format or yuv.Surface expected (got {type(fmt_or_surface).__name__})")
+        s = as_surface(fmt_or_surface)
+        _yuv_buf(buf, s, "yuv_borders", "source")
+        sh, sw = s.height, s.width
+        if out is None:
+            out = torch.empty(sh + sw, dtype=torch.int32, device=buf.device)
+        elif out.dtype != torch.int32 or out.numel() != sh + sw or not out.is_contiguous() or not out.is_cuda:
+            raise ValueError(f"yuv_borders: out must be a contiguous CUDA int32 tensor of H + W = {sh + sw} words")
+        if workspace is None:
+            cache = self.__dict__.setdefault("_yuv_borders_workspaces", {})
+            key = (sh, sw, torch.cuda.current_stream(self.device).cuda_stream)
+            workspace = cache.get(key)
+            if workspace is None:
+                workspace = cache[key] = self.yuv_borders_workspace(sh, sw)
+        elif workspace.dtype != torch.int32 or not workspace.is_contiguous() or not workspace.is_cuda:
+            raise ValueError("yuv_borders: workspace must be a contiguous CUDA int32 tensor")
+        self._check(self.lib.atmvfi_yuv_borders(_ptr(buf), sh, sw, int(s.depth), int(s.msb), int(s.pitch), _ptr(out), _ptr(workspace),
+                                                workspace.numel(), self._stream()), "yuv_borders")
+        return out
+
+    def yuv_compose(self, dst, out_surface, border, border_surface, window, src=None, src_u8=None, pad_top: int = 0, pad_left: int = 0):
+        """A produced window back into a full YUV frame: ``dst`` (one frame of the TIGHT ``out_surface``, a ``yuv.Format`` or
+        ``yuv.Surface``) = the samples of ``border`` (one frame of ``border_surface``: the same size, depth, subsampling, chroma layout
+        and msb, any pitch -- the uploaded source frame in place) outside ``window`` = (y0, x0, h, w), verbatim, and inside exactly
+        what ``yuv_encode`` writes for the h x w picture as a frame of ``out_surface.cropped(h, w)`` -- from ``src`` (fp32 planar
+        [3,Hp,Wp], the window at (pad_top, pad_left)) or ``src_u8`` (uint8 [h,w,3] RGB, depth 8 only), exactly one.  The window begins
+        and ends on multiples of the subsampling step or at the frame's edge (include/atmvfi.h atmvfi_yuv_compose; the bits of
+        ``active.yuv_compose_numpy``).  ``dst`` must not overlap ``border``.  Never recorded into a launch plan."""
+        for d in (out_surface, border_surface):
+            if not hasattr(d, "subsampling_id"):
+                raise ValueError(f"yuv_compose: a yuv.Format or yuv.Surface expected (got {type(d).__name__})")
+        o, b = as_surface(out_surface), as_surface(border_surface)
+        if not o.is_tight:
+            raise ValueError("yuv_compose: out_surface must be tight (no padding is written: surface.tight())")
+        if (o.fmt, o.chroma, o.msb) != (b.fmt, b.chroma, b.msb):
+            raise ValueError(f"yuv_compose: border_surface must be of the output's size, format, chroma layout and msb (got {b} for {o})")
+        _yuv_buf(dst, o, "yuv_compose", "destination")
+        _yuv_buf(border, b, "yuv_compose", "border")
+        if (src is None) == (src_u8 is None):
+            raise ValueError("yuv_compose: give exactly one of src and src_u8")
+        y0, x0, h, w = _window("yuv_compose", o, window)
+        hp = wp = 0
+        if src is not None:
+            _f32_canvas(src, "yuv_compose", ": src")
+            hp, wp = src.shape[1:]
+        else:
+            if o.depth != 8:
+                raise ValueError("yuv_compose: src_u8 goes into 8-bit frames only (a 10-bit frame takes the fp32 src)")
+            _u8_frame(src_u8, "yuv_compose", (h, w), ": src_u8")
+        self._check(self.lib.atmvfi_yuv_compose(_ptr(dst), _ptr(border), o.height, o.width, int(o.depth), o.matrix_id, int(o.full_range), o.siting_id,
+                                                o.subsampling_id, o.chroma_id, int(o.msb), int(b.pitch), int(b.chroma_pitch), int(b.chroma_offset),
+                                                y0, x0, h, w, _ptr(src), hp, wp, int(pad_top), int(pad_left), _ptr(src_u8), self._stream()),
+                    "yuv_compose")
 
     def shutter_accumulate(self, acc, src=None, src_u8=None, weight: int = 1, light: str = "linear", first: bool = False, pad_top: int = 0,
                            pad_left: int = 0, bgr: bool = False):

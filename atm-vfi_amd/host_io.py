@@ -697,6 +697,6 @@ from .retime import Duplicates, difference_numpy, interpolate_video_retimed, ret
 # a synthetic shutter (motion blur) for the rate conversion (``shutter=``; not in the reference): atm-vfi_amd/shutter.py
 from .shutter import Shutter, blend_numpy, shutter_slots  # noqa: E402,F401
 # the active picture of letterboxed video for ``interpolate_video_nx`` (``active=``; not in the reference): atm-vfi_amd/active.py
-from .active import ActiveArea, borders_numpy, compose_numpy  # noqa: E402,F401
+from .active import ActiveArea, bar_code, borders_numpy, compose_numpy, yuv_borders_numpy, yuv_compose_numpy  # noqa: E402,F401
 # planar YUV 4:2:0 frames for the loops above (``pixfmt=``) and Y4M files (not in the reference): atm-vfi_amd/yuv.py
 from .yuv import Format as YuvFormat, Y4MReader, Y4MWriter, interpolate_y4m  # noqa: E402,F401

@@ -144,27 +144,50 @@ class FramePool:
 _Uploader, _SegmentRunner = segments._Uploader, segments._SegmentRunner
 
 
-def _active_window(active, first, it, st, model, device, divisor, step):
-    """``(window, frames)`` of ``interpolate_video_nx(active=)``: a fixed window as it is given; an ``ActiveArea`` after its probe, the
-    frames it read replayed in front of ``it`` (the loop uploads them again).  ``device``: ``(ops, dev)`` of the HIP backend, or None.
-    A window that gains nothing is None: the whole frame, the plain loop."""
+def _active_window(active, first, it, st, model, device, divisor, step, pixfmt=None, caller: str = "interpolate_video_nx"):
+    """``(window, frames)`` of ``active=`` (both loops): a fixed window as it is given; an ``ActiveArea`` after its probe, the frames
+    it read replayed in front of ``it`` (the loop uploads them again); a fixed window's even values fit every subsampling.  ``device``: ``(ops, dev)`` of the HIP backend, or None.
+    A window that gains nothing is None: the whole frame, the plain loop.  ``pixfmt``: the frames are that format's, the profiles
+    those of their luma plane and the threshold its sample code (``active.bar_code``); a locked window that ends on an odd line of a
+    subsampled frame is widened by that line (``active.yuv_window_error`` holds the rule)."""
     from . import active as _active
     if not hasattr(active, "probe_stream"):
         win, frames = _active.fixed_window(active, st.H, st.W), chain(first, it)
     else:
         if device is None:
-            profile_of = lambda f: _active.borders_numpy(f, bgr=st.isBGR)
+            profile_of = (lambda f: _active.borders_numpy(f, bgr=st.isBGR)) if pixfmt is None else (lambda f: _active.yuv_borders_numpy(f, pixfmt))
         else:
             import torch
             ops, dev = device
 
             def profile_of(f):
                 with torch.cuda.device(dev):
-                    return ops.frame_borders(torch.from_numpy(np.ascontiguousarray(f)).to(dev), bgr=bool(st.isBGR)).cpu().numpy()
+                    if pixfmt is None:
+                        return ops.frame_borders(torch.from_numpy(np.ascontiguousarray(f)).to(dev), bgr=bool(st.isBGR)).cpu().numpy()
+                    return ops.yuv_borders(torch.from_numpy(pixfmt.check(f, caller).view(np.uint8)).to(dev), pixfmt).cpu().numpy()
         need = 16 if getattr(model, "global_motion", True) else 8
-        held = active.probe_stream(chain(first, it), st.H, st.W, divisor, need, step, profile_of)
-        win, frames = active.window, itertools.chain(held, it)
+        yuv_kw = {} if pixfmt is None else dict(code=_active.bar_code(pixfmt, active.peak), accept=lambda f: pixfmt.check(f, caller))
+        held = active.probe_stream(chain(first, it), st.H, st.W, divisor, need, step, profile_of, **yuv_kw)
+        win = active.window
+        if pixfmt is not None and win != (0, 0, st.H, st.W):
+            (sy, sx), (y0, x0, h, w) = pixfmt.steps, win
+            win = active.window = (y0, x0, h + (y0 + h) % sy * (y0 + h != st.H), w + (x0 + w) % sx * (x0 + w != st.W))
+        frames = itertools.chain(held, it)
     return (None if win == (0, 0, st.H, st.W) else win), frames
+
+
+def _active_refusals(caller: str, active, crop, pixfmt, keep_depth, first):
+    """What ``active=`` does not go with, and -- with a ``pixfmt`` -- a first frame that is not of the format."""
+    if crop is not None:
+        raise ValueError(f"{caller}: active does not go with crop (the active picture is found on whole frames)")
+    if pixfmt is None:
+        return
+    if pixfmt.depth == 10 and not keep_depth:
+        raise ValueError(f"{caller}: active with a 10-bit pixfmt needs the depth kept: pass keep_depth=True (8-bit output converts the "
+                         "originals through RGB, so the bars of produced frames could not match theirs)")
+    a = np.asarray(first)
+    if a.dtype != pixfmt.dtype or a.size != pixfmt.frame_samples:
+        raise ValueError(f"{caller}: active with pixfmt expects frames of the format, got {a.dtype} {tuple(a.shape)}")
 
 
 def interpolate_video_nx(frames, model, factor: int = 4, time_interval: int = 1, crop: Optional[Tuple[int, int]] = None, isBGR: bool = True,
@@ -201,8 +224,8 @@ def interpolate_video_nx(frames, model, factor: int = 4, time_interval: int = 1,
     prediction as always.  The resident uint8 RGB frame is made only when ``scene`` needs its signature: signatures, and so cut
     decisions, are those of the 8-bit path.  A model without the HIP backend does the same with the numpy twins.
 
-    ``active`` (an ``active.ActiveArea`` or a fixed even window ``(y0, x0, h, w)``; default None: the loop as above; not with ``crop``
-    or ``pixfmt``: ``ValueError``): the network runs on the active picture of letterboxed video.  Before its first output the loop
+    ``active`` (an ``active.ActiveArea`` or a fixed even window ``(y0, x0, h, w)``; default None: the loop as above; not with
+    ``crop``: ``ValueError``): the network runs on the active picture of letterboxed video.  Before its first output the loop
     reads frames from ``frames`` until the policy has seen enough (``probe`` decided frames, ``patience`` frames, the stream's end),
     keeps them on the host, locks the union of their rects as the window and replays them.  A window that gains nothing under
     ``divisor`` is the whole frame: the loop as above.  Else every uploaded frame gets its line maxima on the copy stream
@@ -211,13 +234,18 @@ def interpolate_video_nx(frames, model, factor: int = 4, time_interval: int = 1,
     pass through as the caller's own arrays; ``scene`` works on the whole frame as before.  A frame with a non-bar line outside the
     window ends it: from the segment that ends at that frame on, the loop runs on the whole frame for the rest of the stream.  With
     ``time_interval`` > 1 the frames that are not uploaded are not examined.  A tuple is never probed nor checked.
-    ``active.window`` / ``.probed`` / ``.fallback_at`` / ``.stats`` hold the run's record."""
+    ``active.window`` / ``.probed`` / ``.fallback_at`` / ``.stats`` hold the run's record.
+    With a ``pixfmt`` the line maxima are those of the uploaded surface's luma plane (``HipOps.yuv_borders``) against the sample code
+    of ``peak`` (``active.bar_code``; chroma is not examined), the two border frames are the uploaded surfaces themselves, and a
+    produced position leaves through ``HipOps.yuv_compose``: the window's encode inside, the nearer original's own samples outside,
+    plane by plane -- the bars never pass through RGB.  A 10-bit ``pixfmt`` needs ``keep_depth=True`` (``ValueError`` otherwise: 8-bit
+    output converts the originals on the host, no sample copy reproduces that), and a first frame that is not of the ``pixfmt`` is
+    refused before anything else."""
     from .host_io import _hip_ops_of
     from .scene import cut_fill
     nx_levels(factor)
-    if active is not None and (crop is not None or pixfmt is not None):
-        raise ValueError("interpolate_video_nx: active does not go with " + ("crop" if crop is not None else "pixfmt") +
-                         " (the active picture is found on whole uint8 frames)")
+    if active is not None and crop is not None:
+        _active_refusals("interpolate_video_nx", active, crop, pixfmt, keep_depth, None)
     if scene is not None:
         scene.begin()
     area = active if hasattr(active, "probe_stream") else None
@@ -227,6 +255,8 @@ def interpolate_video_nx(frames, model, factor: int = 4, time_interval: int = 1,
     first = next(it, None)
     if first is None:
         return
+    if active is not None:
+        _active_refusals("interpolate_video_nx", active, crop, pixfmt, keep_depth, first)
     st = open_stream(first, crop, pixfmt, keep_depth, isBGR, "interpolate_video_nx")
     step = int(time_interval)
     if step < 1:
@@ -235,7 +265,7 @@ def interpolate_video_nx(frames, model, factor: int = 4, time_interval: int = 1,
     generic = ops is None or not hasattr(ops, "pool_blocks")
     source, win = chain(first, it), None
     if active is not None:
-        win, source = _active_window(active, first, it, st, model, None if generic else (ops, dev), divisor, step)
+        win, source = _active_window(active, first, it, st, model, None if generic else (ops, dev), divisor, step, pixfmt)
     common = dict(n=factor, divisor=divisor, tta=tta, pixfmt=pixfmt, window=win, watch=area is not None)
     if generic:
         be = HostBackend(model, st, max_batch=max(1, int(max_batch)), **common)

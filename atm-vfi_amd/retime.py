@@ -234,7 +234,7 @@ class Duplicates:
 def interpolate_video_retimed(frames, model, fps_in, fps_out, levels: int = 3, dedup: Optional[Duplicates] = None,
                               crop: Optional[Tuple[int, int]] = None, isBGR: bool = True, divisor: Optional[int] = 64, tta: bool = False,
                               max_batch: int = 4, pool: bool = True, scene=None, pixfmt=None, keep_depth: bool = False, report=None,
-                              shutter=None):
+                              active=None, shutter=None):
     """Frame-rate conversion ``fps_in -> fps_out`` (ints, ``Fraction``s or strings such as ``"30000/1001"``) over any iterable of uint8
     [H,W,3] frames: yields, in time order, output ``m`` at ``m / fps_out`` for every m up to the last kept frame's time, as the module's
     docstring defines -- the nearest of ``N = 2**levels`` positions of its segment.  Positions 0 and N are the originals and pass through
@@ -270,8 +270,18 @@ def interpolate_video_retimed(frames, model, fps_in, fps_out, levels: int = 3, d
     ``keep_depth`` on a 10-bit format is refused (``ValueError``), as are an angle outside (0, 360] and an exposure whose total
     weight exceeds 32767.  ``report`` also gets ``"blended"`` (outputs of more than one sample) and ``"samples"``.
 
+    ``active`` (an ``active.ActiveArea`` or a fixed even window; default None: the loop as above, nothing new allocated or launched;
+    not with ``crop`` or ``shutter``: ``ValueError``): the active picture of letterboxed video, as in
+    ``multiframe.interpolate_video_nx`` -- the same probe-and-replay in front of the loop, RGB frames and ``pixfmt`` alike (a 10-bit
+    one with ``keep_depth``).  Every uploaded frame is examined, a dropped duplicate too; a frame with a non-bar line outside the
+    window sends the loop back to the whole frame from the segment that ends at it (a dropped one: at the next kept frame).  A
+    produced position p carries the bars of the nearer end of its segment (p <= N/2: the first), also across a widened segment; a
+    cut segment or one without an interpolated output runs no forward.
+
     The rates and ``levels`` are checked at the call; ``ValueError`` as ``retime_slots`` raises it."""
     fi, fo, levels = _check_rates(fps_in, fps_out, levels)
+    if active is not None and shutter is not None:
+        raise ValueError("interpolate_video_retimed: active does not go with shutter (a blurred output mixes whole frames)")
     if shutter is not None:
         from .shutter import as_shutter
         shutter = as_shutter(shutter)
@@ -279,12 +289,18 @@ def interpolate_video_retimed(frames, model, fps_in, fps_out, levels: int = 3, d
         if pixfmt is not None and keep_depth and pixfmt.depth == 10:
             raise ValueError("interpolate_video_retimed: shutter blends 8-bit pixels; a 10-bit blend (keep_depth=True) is out of scope")
     return _retimed(frames, model, fi, fo, levels, dedup, crop, isBGR, divisor, tta, max_batch, pool, scene, pixfmt, keep_depth, report,
-                    shutter)
+                    shutter, active)
 
 
 def _retimed(frames, model, fi, fo, levels, dedup, crop, isBGR, divisor, tta, max_batch, pool, scene, pixfmt, keep_depth, report,
-             shutter=None):
+             shutter=None, active=None):
     from .host_io import _hip_ops_of
+    from .multiframe import _active_refusals, _active_window
+    if active is not None and crop is not None:
+        _active_refusals("interpolate_video_retimed", active, crop, pixfmt, keep_depth, None)
+    area = active if hasattr(active, "probe_stream") else None
+    if area is not None:
+        area.begin()
     n = 1 << levels
     if scene is not None:
         scene.begin()
@@ -296,13 +312,21 @@ def _retimed(frames, model, fi, fo, levels, dedup, crop, isBGR, divisor, tta, ma
     first = next(it, None)
     if first is None:
         return
+    if active is not None:
+        _active_refusals("interpolate_video_retimed", active, crop, pixfmt, keep_depth, first)
     st = open_stream(first, crop, pixfmt, keep_depth, isBGR, "interpolate_video_retimed")
     if pixfmt is None and (first.ndim != 3 or first.shape[2] != 3 or first.dtype != np.uint8):
         raise ValueError(f"interpolate_video_retimed: expected uint8 [H,W,3] frames, got {first.dtype} {tuple(first.shape)}")
     (h, w), original = st.window[2:], st.original
     ops, dev = _hip_ops_of(model)
     common = dict(n=n, divisor=divisor, tta=tta, pixfmt=pixfmt, caller="interpolate_video_retimed")
-    if ops is None or not hasattr(ops, "pool_blocks"):
+    generic = ops is None or not hasattr(ops, "pool_blocks")
+    if active is not None:
+        win, source = _active_window(active, first, it, st, model, None if generic else (ops, dev), divisor, 1, pixfmt,
+                                     "interpolate_video_retimed")
+        first, it = next(source), source             # (the probed frames replayed)
+        common.update(window=win, watch=area is not None)
+    if generic:
         be = HostBackend(model, st, max_batch=max(1, int(max_batch)), dedup=dedup, light=None if shutter is None else shutter.light, **common)
     else:
         # distinct interpolated positions of one segment: its outputs, at most ceil(g fps_out / fps_in) of them, g <= max_run + 1
@@ -313,6 +337,12 @@ def _retimed(frames, model, fi, fo, levels, dedup, crop, isBGR, divisor, tta, ma
                            blend=None if shutter is None else (shutter.light, per_segment + 1), **common)   # the outputs a segment can close
     ends, number = {}, itertools.count()             # kept frames by their number on the timeline, until their segments are done
     sig = {}                                         # signatures of segment ends that a later segment starts with
+    violated = []                                    # an examined frame left the active picture: the next segment runs on the whole frame
+
+    def judged(e):
+        """a frame whose upload has landed: its borders against the locked window (kept or dropped: it was uploaded)"""
+        if be.watching and not violated and area.check(be.borders(e), st.H, st.W):
+            violated.append(e["i"])
 
     def kept():
         """The indices of the kept frames.  Frame k is judged when frame k + 1 has been read (and its upload started: one frame ahead
@@ -325,10 +355,13 @@ def _retimed(frames, model, fi, fo, levels, dedup, crop, isBGR, divisor, tta, ma
                 be.first(e)
                 if scene is not None:
                     sig[0] = be.signature(e)
+            if pending is not None:
+                judged(pending)
             if pending is not None and not (dedup is not None and pending["i"] > 0 and dedup.judge(be.difference(pending), h, w)):
                 ends[next(number)] = pending
                 yield pending["i"]
             pending = e
+        judged(pending)
         if dedup is not None and pending["i"] > 0:
             dedup.judge(be.difference(pending), h, w)
             dedup.finish()
@@ -402,6 +435,9 @@ def _retimed(frames, model, fi, fo, levels, dedup, crop, isBGR, divisor, tta, ma
                 continue
             a, b = ends[j], ends[j + 1]
             ran = j
+            if violated and be.watching:             # (every frame up to b has been examined)
+                area.fallback_at = j
+                be.whole_frame()
             interior = sorted({p for p in ps if 0 < p < n})
             cut = False
             if scene is not None:

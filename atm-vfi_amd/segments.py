@@ -97,8 +97,9 @@ class _Uploader:
     stream order.  A frame that is never ``take``n (a dropped duplicate) records no ``free`` event, so with ``difference`` a slot's
     reuse also waits for its own ``ready`` event: its pinned bytes have left the host before they are overwritten.
 
-    ``borders=(ops, bgr)`` (the active picture, ``active.ActiveArea``): the frame's line maxima (``HipOps.frame_borders``), H + W words.
-    ``stop_borders()`` ends it for the uploads still to come.
+    ``borders=(ops, bgr)`` (the active picture, ``active.ActiveArea``): the frame's line maxima (``HipOps.frame_borders``), H + W words;
+    with a ``pixfmt`` those of the uploaded surface's luma plane (``HipOps.yuv_borders`` on the slot's ``yuv`` bytes: no RGB frame is
+    needed for it).  ``stop_borders()`` ends it for the uploads still to come.
 
     ``caller``: the loop's name, for the refusal of a frame of another size or type."""
 
@@ -118,8 +119,12 @@ class _Uploader:
                                       d_ops.frame_difference(prev["d"], s["d"], *d_win, bgr=d_bgr, out=out, workspace=ws), pairs=True))
         if borders is not None:
             b_ops, b_bgr = borders
-            self.probes.append(_Probe("borders", height + width, b_ops.frame_borders_workspace(height, width), lambda prev, s, out, ws:
-                                      b_ops.frame_borders(s["d"], bgr=b_bgr, out=out, workspace=ws)))
+            if pixfmt is None:
+                self.probes.append(_Probe("borders", height + width, b_ops.frame_borders_workspace(height, width), lambda prev, s, out, ws:
+                                          b_ops.frame_borders(s["d"], bgr=b_bgr, out=out, workspace=ws)))
+            else:
+                self.probes.append(_Probe("borders", height + width, b_ops.yuv_borders_workspace(height, width), lambda prev, s, out, ws:
+                                          b_ops.yuv_borders(s["yuv"], pixfmt[1], out=out, workspace=ws)))
         self.pairs, self.prev = difference is not None, None          # prev: the slot of the previous upload
         in_shape = (height, width, 3) if pixfmt is None else (pixfmt[1].frame_bytes,)
         need_rgb = not self.deep or signature is not None or difference is not None
@@ -190,10 +195,11 @@ class _Uploader:
         self.probes = [p for p in self.probes if p.name != "borders"]
 
     def take(self, slot, convert):
-        """Run ``convert(device uint8 frame)`` on the current stream once the slot's copy has landed (``deep``: the device I420 bytes)."""
+        """Run ``convert(device uint8 frame, the uploaded surface's bytes or None)`` on the current stream once the slot's copy has
+        landed (``deep``: the first is the surface's bytes too)."""
         cur = self.torch.cuda.current_stream(self.dev)
         cur.wait_event(slot["ready"])
-        convert(slot["yuv"] if self.deep else slot["d"])
+        convert(slot["yuv"] if self.deep else slot["d"], slot.get("yuv"))
         slot["free"].record(cur)
 
 
@@ -226,14 +232,15 @@ class _SegmentRunner:
     and leaves by the same device -> host copy.  ``ops``: ``shutter._plan``'s, a close as ``("close", m)`` or, for an output the caller
     serves itself, ``("drop", m)``.  The output ring holds the outputs one ``run`` can close.
 
-    ``window=(y0, x0, h, w)`` (the active picture, ``interpolate_video_nx(active=)``; no ``crop``, formats or blend with it): the network
-    runs on that window -- pool, plans and batch sizes as for a crop -- and the runner keeps two resident uint8 [H,W,3] BORDER frames,
-    the originals in positions 0 and N, copied where the source frame is converted and swapped with the positions.  A produced
-    position k leaves through ``frame_compose`` into a FULL-SIZE output ring entry: the prediction's window (with ``tta``:
-    ``tta_merge``'s uint8 window) inside, the bars of the nearer original (k <= N/2: position 0) outside."""
+    ``window=(y0, x0, h, w)`` (the active picture, ``active=`` of both loops; no ``crop`` or blend with it): the network
+    runs on that window -- pool, plans and batch sizes as for a crop -- and the runner keeps two resident BORDER frames, the originals
+    in positions 0 and N, copied device to device where the source frame is converted and swapped with the positions: uint8 [H,W,3],
+    or with ``out_fmt`` / ``deep_fmt`` the uploaded surfaces in the input layout ``border_fmt``.  A produced position k leaves through
+    ``frame_compose`` (``yuv_compose``) into a FULL-SIZE output ring entry: the prediction's window inside -- with ``tta`` ``tta_merge``'s
+    uint8 window, with the depth kept the fp32 average -- and the bars of the nearer original (k <= N/2: position 0) outside."""
 
     def __init__(self, model, ops, dev, height, width, factor, crop, bgr, divisor, tta, max_batch, pool, out_fmt=None, deep_fmt=None,
-                 out_slots=None, batch_sizes=None, blend=None, window=None):
+                 out_slots=None, batch_sizes=None, blend=None, window=None, border_fmt=None):
         import torch
         from .multiframe import FramePool, centre_window, nx_levels
         self.torch, self.model, self.ops, self.dev = torch, model, ops, dev
@@ -243,14 +250,14 @@ class _SegmentRunner:
         self.out_fmt, self.deep_fmt = out_fmt, deep_fmt
         u8 = lambda *shape: torch.empty(*shape, dtype=torch.uint8, device=dev)
         self.y0, self.x0, self.h, self.w = centre_window(height, width, crop)
-        self.border = None
+        self.border = self.border_fmt = None
         if window is not None:
-            if crop is not None or out_fmt is not None or deep_fmt is not None or blend is not None:
-                raise ValueError("_SegmentRunner: window goes with no crop, format or blend")
+            if crop is not None or blend is not None or (out_fmt is None) != (border_fmt is None):
+                raise ValueError("_SegmentRunner: window goes with no crop or blend, and with a format only with the border's")
             self.y0, self.x0, self.h, self.w = (int(v) for v in window)
-            self.border = [u8(height, width, 3) for _ in range(2)]
+            self.border_fmt = border_fmt
+            self.border = [u8(height, width, 3) if border_fmt is None else u8(border_fmt.frame_bytes) for _ in range(2)]
             self.border_of = {0: 0, factor: 1}       # position -> border frame; swapped with the positions
-            self.win_u8 = u8(self.h, self.w, 3) if self.tta else None
         self.pad_top, self.pad_left, self.hp, self.wp = _canvas(self.h, self.w, divisor, 16 if getattr(model, "global_motion", True) else 8,
                                                                self.use_pool)
         S, sets = factor + 1, 2 if self.tta else 1   # (with tta a second set: the 180-degree rotations)
@@ -260,7 +267,7 @@ class _SegmentRunner:
         self.phys = list(range(S))                   # schedule position -> pool slot; positions 0 and N swap slots per segment
         self.have_first = self.fresh = False
         self.gather = {}                             # plain mode: the pairs of a batch are gathered into contiguous [B,3,Hp,Wp] inputs
-        out_shape = (height, width, 3) if self.border is not None else (self.h, self.w, 3) if out_fmt is None else (out_fmt.frame_bytes,)
+        out_shape = (out_fmt.frame_bytes,) if out_fmt is not None else (height, width, 3) if self.border is not None else (self.h, self.w, 3)
         n_out = factor - 1 if out_slots is None else max(1, min(int(out_slots), factor - 1))
         self.blend = None
         if blend is not None:
@@ -273,7 +280,7 @@ class _SegmentRunner:
         self.out_d = u8(n_out, *out_shape)
         self.out_h = [torch.empty(n_out, *out_shape, dtype=torch.uint8).pin_memory() for _ in range(2)]
         self.merged = None
-        if out_fmt is not None and self.tta:         # the average: its uint8 pixels, or with the depth kept the fp32 canvas itself
+        if (out_fmt is not None or self.border is not None) and self.tta:       # the average: its uint8 pixels, or with the depth kept the fp32 canvas itself
             self.merged = (torch.empty(3, self.hp, self.wp, dtype=torch.float32, device=dev) if deep_fmt is not None else u8(self.h, self.w, 3))
         mode = "compose" if self.border is not None else "deep" if deep_fmt is not None else "yuv" if out_fmt is not None else "u8"
         self.leave = self._LEAVE[mode, self.tta]     # (the plain function, not a bound method: the runner must not hold itself alive)
@@ -299,7 +306,7 @@ class _SegmentRunner:
     def _convert_into(self, pos):
         slot = self.phys[pos]
 
-        def convert(d_u8):
+        def convert(d_u8, surface=None):
             dst = self.frames[0][slot]
             if self.deep_fmt is not None:             # d_u8: the frame's I420 bytes
                 self.ops.yuv_decode(d_u8, self.deep_fmt, dst=dst, window=(self.y0, self.x0, self.h, self.w), pad_top=self.pad_top,
@@ -314,8 +321,8 @@ class _SegmentRunner:
             if self.pools:
                 for p in self.pools:
                     p.invalidate(slot)
-            if self.border is not None:
-                self.border[self.border_of[pos]].copy_(d_u8, non_blocking=True)
+            if self.border is not None:              # (a format: the uploaded surface itself, never a converted frame)
+                self.border[self.border_of[pos]].copy_(d_u8 if self.border_fmt is None else surface, non_blocking=True)
         return convert
 
     def first(self, up: _Uploader, slot):
@@ -324,10 +331,10 @@ class _SegmentRunner:
         with self.torch.cuda.device(self.dev):
             up.take(slot, self.first_resident)
 
-    def first_resident(self, d_u8):
-        """``first`` for a frame that is on the device already (a uint8 [H,W,3] tensor the current stream may read)."""
+    def first_resident(self, d_u8, surface=None):
+        """``first`` for a frame that is on the device already (what ``_Uploader.take`` hands over, for the current stream to read)."""
         with self.torch.cuda.device(self.dev):
-            self._convert_into(0)(d_u8)
+            self._convert_into(0)(d_u8, surface)
         self.have_first = self.fresh = True
 
     def _forward(self, k, lefts, rights):
@@ -394,12 +401,24 @@ class _SegmentRunner:
         """the border frame of the nearer original, and the window"""
         return self.border[self.border_of[0 if pos <= self.n // 2 else self.n]], (self.y0, self.x0, self.h, self.w)
 
-    def _leave_compose(self, pos, pred, flip, u8):   # the window back into a full frame
-        self.ops.frame_compose(u8, *self._bars(pos), src=pred, pad_top=self.pad_top, pad_left=self.pad_left, bgr=self.bgr)
+    def _compose(self, u8, pos, src=None, win=None):
+        """the window -- the fp32 canvas ``src`` or the uint8 pixels ``win`` -- back into a full frame"""
+        border, window = self._bars(pos)
+        if self.out_fmt is None:
+            self.ops.frame_compose(u8, border, window, src=src, win_u8=win, pad_top=self.pad_top, pad_left=self.pad_left, bgr=self.bgr)
+        else:
+            self.ops.yuv_compose(u8, self.out_fmt, border, self.border_fmt, window, src=src, src_u8=win, pad_top=self.pad_top,
+                                 pad_left=self.pad_left)
+
+    def _leave_compose(self, pos, pred, flip, u8):
+        self._compose(u8, pos, src=pred)
 
     def _leave_compose_tta(self, pos, pred, flip, u8):
-        self.ops.tta_merge(pred, flip, out_u8=self.win_u8, pad_top=self.pad_top, pad_left=self.pad_left, bgr=self.bgr)
-        self.ops.frame_compose(u8, *self._bars(pos), win_u8=self.win_u8)
+        if self.deep_fmt is not None:                # the fp32 average
+            self.ops.tta_merge(pred, flip, out=self.merged)
+            return self._compose(u8, pos, src=self.merged)
+        self.ops.tta_merge(pred, flip, out_u8=self.merged, pad_top=self.pad_top, pad_left=self.pad_left, bgr=self.bgr and self.out_fmt is None)
+        self._compose(u8, pos, win=self.merged)
 
     _LEAVE = {("u8", False): _leave_u8, ("u8", True): _leave_u8_tta, ("yuv", False): _leave_yuv, ("yuv", True): _leave_yuv_tta,
               ("deep", False): _leave_yuv, ("deep", True): _leave_deep_tta,      # (out_fmt is the 10-bit format then)
@@ -586,10 +605,11 @@ def _generic_segment(model, factor, crop_of, isBGR, divisor, tta, max_batch, loa
 # ------------------------------------------------------------------------------------------------ the backends
 class HostBackend:
     """A model without the HIP backend: torch / numpy (``_generic_segment``, ``retime.difference_numpy``, ``scene.signature_numpy``,
-    ``active.borders_numpy`` / ``compose_numpy``, ``shutter.blend_numpy``).  An I420 frame is decoded once (``_rgb``: kept in its
-    entry, so the frame that ends a segment is not decoded again when it starts the next).  ``window`` (the active picture): the
-    forwards run on that window of the frames and every produced window is composed into a full frame with the bars of the nearer
-    original, until ``whole_frame()``; ``watching``: the loop examines ``borders`` of the frames it admits."""
+    ``active.borders_numpy`` / ``compose_numpy`` and their ``yuv_`` forms, ``shutter.blend_numpy``).  An I420 frame is decoded once
+    (``_rgb``: kept in its entry, so the frame that ends a segment is not decoded again when it starts the next).  ``window`` (the
+    active picture): the forwards run on that window of the frames and every produced window is composed into a full frame with the
+    bars of the nearer original -- with a ``pixfmt`` the window's encode into the original's own samples -- until ``whole_frame()``;
+    ``watching``: the loop examines ``borders`` of the frames it admits."""
     lookahead = False                                # (nothing is gained by reading a segment ahead)
 
     def __init__(self, model, st: Stream, n, divisor, tta, max_batch, pixfmt=None, dedup=None, light=None, window=None, watch=False,
@@ -597,18 +617,23 @@ class HostBackend:
         self.n, self.levels, self.st, self.pixfmt, self.caller = n, n.bit_length() - 1, st, pixfmt, caller
         self.dedup, self.prev_rgb = dedup, None
         self.light, self.gathered = light, {}        # (the synthetic shutter: ``blended``)
-        self.window, self.watching = window, window is not None and watch
-        self._make = lambda crop_of: _generic_segment(model, n, crop_of, st.isBGR, divisor, tta, max_batch)
+        self.watching = window is not None and watch
+        self._generic = lambda crop_of, **kw: _generic_segment(model, n, crop_of, st.isBGR, divisor, tta, max_batch, **kw)
+        self._build(window)
+
+    def _build(self, window):
+        """``seg`` on ``window`` of the frames (None: the stream's own crop window); ``win_fmt``: the format its frames are encoded to"""
+        st, self.window = self.st, window
+        y0, x0, h, w = st.window if window is None else window
+        self.win_fmt = st.out_fmt if window is None or st.out_fmt is None else st.out_fmt.cropped(h, w)
         if st.deep:
             from . import yuv
-            self.seg = _generic_segment(model, n, None, False, divisor, tta, max_batch,
-                                        load=lambda f: yuv.decode_numpy_f32(f, pixfmt, window=st.window),
-                                        store=lambda p: yuv.encode_numpy(p, st.out_fmt))
+            self.seg = self._generic(None, load=lambda f: yuv.decode_numpy_f32(f, self.pixfmt, window=(y0, x0, h, w)),
+                                     store=lambda p: yuv.encode_numpy(p, self.win_fmt))
         elif window is not None:
-            y0, x0, h, w = window
-            self.seg = self._make(lambda f: np.ascontiguousarray(f[y0:y0 + h, x0:x0 + w]))
+            self.seg = self._generic(lambda f: np.ascontiguousarray(f[y0:y0 + h, x0:x0 + w]))
         else:
-            self.seg = self._make(st.crop_rgb)
+            self.seg = self._generic(st.crop_rgb)
 
     def _rgb(self, e):
         """the uint8 [H,W,3] picture of a frame (an I420 frame: decoded once)"""
@@ -640,12 +665,13 @@ class HostBackend:
         return signature_numpy(self._rgb(e), self.st.window, bgr=self.st.isBGR)
 
     def borders(self, e):
-        from .active import borders_numpy
-        return borders_numpy(e["f"], bgr=self.st.isBGR)
+        from .active import borders_numpy, yuv_borders_numpy
+        return borders_numpy(e["f"], bgr=self.st.isBGR) if self.pixfmt is None else yuv_borders_numpy(e["f"], self.pixfmt)
 
     def whole_frame(self):
         """The active picture has ended: the whole frame from the next ``segment`` on."""
-        self.window, self.watching, self.seg = None, False, self._make(lambda f: f)
+        self.watching = False
+        self._build(None)
 
     def segment(self, a, b, interior, cut):
         """The frames between two admitted frames as ``{position: frame}``: ``interior`` (sorted positions in 1..N-1; None: all of
@@ -660,10 +686,14 @@ class HostBackend:
             made = self.seg(fa, fb, levels=sparse_levels(interior, self.levels), emit=interior)
         if self.pixfmt is not None and not self.st.deep:
             from . import yuv
-            made = [yuv.encode_numpy(m, self.st.out_fmt) for m in made]
+            made = [yuv.encode_numpy(m, self.win_fmt) for m in made]
         if self.window is not None:
-            from .active import compose_numpy
-            made = [compose_numpy((a if k <= self.n // 2 else b)["f"], self.window, win_u8=m) for k, m in zip(interior, made)]
+            from .active import compose_numpy, yuv_compose_numpy
+            bars = lambda k: (a if k <= self.n // 2 else b)["f"]
+            if self.pixfmt is None:
+                made = [compose_numpy(bars(k), self.window, win_u8=m) for k, m in zip(interior, made)]
+            else:
+                made = [yuv_compose_numpy(bars(k), self.pixfmt, self.window, m) for k, m in zip(interior, made)]
         return dict(zip(interior, made))
 
     def blended(self, a, b, ops, need, cut, tail):
@@ -723,7 +753,9 @@ class DeviceBackend:
         self._runner = lambda window: _SegmentRunner(model, ops, dev, st.H, st.W, n, crop, st.isBGR, divisor, tta, max_batch,
                                                      pool and hasattr(model, "forward_pooled"), out_fmt=st.out_fmt,
                                                      deep_fmt=pixfmt if st.deep else None, out_slots=out_slots, batch_sizes=batch_sizes,
-                                                     blend=blend, window=window)
+                                                     blend=blend, window=window,
+                                                     border_fmt=pixfmt if window is not None else None)
+        self.pixfmt, self.ops, self.dev, self.hw = pixfmt, ops, dev, (st.H, st.W)
         self.runner = self._runner(window)
         self.watching = window is not None and watch
         sig = (ops, st.window, bool(st.isBGR))
@@ -749,13 +781,23 @@ class DeviceBackend:
 
     def whole_frame(self):
         """The active picture has ended: a runner on the whole frame for the rest of the stream.  The next segment's first frame is
-        position N of the windowed runner's last segment: its border frame is the resident uint8 copy the new runner converts again."""
+        position N of the windowed runner's last segment (position 0 when ``first`` alone has run): its border frame is the resident
+        copy the new runner converts again -- the uint8 frame, or with a ``pixfmt`` the uploaded surface, which without ``keep_depth``
+        is decoded to the uint8 RGB frame first."""
         self.up.stop_borders()
-        resident = self.runner.border[self.runner.border_of[self.n]] if self.started else None
-        self.runner.close()
+        old = self.runner
+        resident = old.border[old.border_of[0 if old.fresh else self.n]] if self.started else None
+        old.close()
         self.runner, self.watching = self._runner(None), False
-        if resident is not None:
-            self.runner.first_resident(resident)
+        if resident is None:
+            return
+        if self.pixfmt is None or self.runner.deep_fmt is not None:
+            return self.runner.first_resident(resident, resident)
+        import torch
+        with torch.cuda.device(self.dev):
+            rgb = torch.empty(*self.hw, 3, dtype=torch.uint8, device=self.dev)
+            self.ops.yuv_decode(resident, self.pixfmt, dst_u8=rgb)
+        self.runner.first_resident(rgb)
 
     def _ends(self, a, b):
         """the upload slots a ``run`` takes: the first frame's only when nothing has converted it yet"""

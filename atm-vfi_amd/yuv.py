@@ -658,7 +658,7 @@ def _interpolate_stream(who, open_reader, open_writer, model, kw, *, factor, sce
             if deep:
                 kw["keep_depth"] = True
             if interpolator is None:
-                nx_only = tta or factor != 2 or any(k in kw for k in ("crop", "time_interval", "max_batch", "pool"))
+                nx_only = tta or factor != 2 or any(k in kw for k in ("crop", "time_interval", "max_batch", "pool", "active"))
                 if not nx_only and _hip_ops_of(model)[0] is not None:
                     interpolator = interpolate_video_2x
                 else:
@@ -698,7 +698,9 @@ def interpolate_y4m(src, dst, model, factor: int = 2, scene=None, tta: bool = Fa
     header carries, with ``levels`` and ``dedup`` (a ``retime.Duplicates``) handed on; ``factor`` is ignored and there is no
     ``time_interval``.  The dict gains ``"forwards"`` and, with ``dedup``, ``"dropped"``.  ``shutter`` (a ``shutter.Shutter`` or an
     angle; only with ``fps_out``, else ``ValueError``; 8-bit output only): the conversion's synthetic shutter; the dict gains
-    ``"blended"``."""
+    ``"blended"``.  ``active`` (an ``active.ActiveArea`` or a fixed window, among ``kw``; not with ``crop`` or ``shutter``): the
+    network runs on the active picture of letterboxed video, in either loop (``factor=2`` goes to ``interpolate_video_nx`` then); a
+    10-bit stream needs ``keep_depth`` for it."""
     # (the same tag as read where the depth is the stream's; 10-bit input written as 8 bit takes the format's canonical tag)
     open_writer = lambda rd, out, rate: Y4MWriter(dst, out, rate, ctag=rd.ctag if out.depth == rd.fmt.depth else None, aspect=rd.aspect)
     return _interpolate_stream("interpolate_y4m", lambda: Y4MReader(src, matrix=matrix, accept=SUBSAMPLINGS), open_writer, model, kw,
@@ -742,5 +744,6 @@ def interpolate_raw(src, dst, model, surface, fps, factor: int = 2, scene=None, 
 from .host_io import FramePipeline, interpolate_video_2x, load_model_checkpoint  # noqa: E402,F401
 from .multiframe import interpolate_video_nx  # noqa: E402,F401
 from .scene import SceneCuts  # noqa: E402,F401
+from .active import ActiveArea  # noqa: E402,F401
 from .retime import Duplicates, interpolate_video_retimed  # noqa: E402,F401
 from .shutter import Shutter, blend_numpy, shutter_slots  # noqa: E402,F401

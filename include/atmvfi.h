@@ -513,6 +513,44 @@ int atmvfi_frame_compose(void* dst /*uint8 [H,W,3]*/, const void* border /*uint8
                          const float* src /*[3,Hp,Wp] or NULL*/, int Hp, int Wp, int pad_top, int pad_left,
                          const void* win_u8 /*uint8 [h,w,3] or NULL*/, int bgr, void* stream);
 
+/* The active picture on YUV streams and in the retimed loop (active.hip, yuv_encode.hip; ABI 0.22; atm-vfi_amd/active.py: bar_code,
+ * yuv_borders_numpy / yuv_compose_numpy; per-sample models tests/cpu_yuv_active.py).  Nothing of the reference.  The frames are those of
+ * the surface calls below (depth, chroma, msb, pitch / chroma_pitch / chroma_offset in BYTES, 0: tight; subsampling as in
+ * atmvfi_yuv_sub_encode).
+ * atmvfi_yuv_borders: the LUMA plane of one resident frame -> int32 out[H + W] on the device:
+ *   out[y]     = the largest luma sample VALUE of row y (the stored sample, >> 6 with msb);   out[H + x] = that of column x.
+ *   The maximum commutes with every monotone map, so raw codes are reported and the host maps its threshold once (active.bar_code).
+ *   depth 8 or 10, msb only at depth 10, pitch a multiple of the sample size and at least a row's bytes (0: tight); chroma layout and
+ *   subsampling do not matter: only the H rows of W samples are read, never a padding byte.  H, W >= 16, H * W fits int32, at most
+ *   65535 row chunks (ATMVFI_EINVAL otherwise, checked on the host before the launch).  Any pointer alignment and pitch is accepted;
+ *   the vector path (a lane's four samples as one dword or one 8-byte load) runs when the pointer and the pitch are multiples of 4
+ *   bytes and W is a multiple of 4.  Both paths give the same bits.  out (4-byte aligned) is written completely by the call: nothing
+ *   is pre-zeroed, no global atomics, vector stores only.  workspace: at least atmvfi_yuv_borders_workspace_ints(H, W) int32 of
+ *   scratch, the caller's; the query returns -1 for a frame the call would refuse.  Stream-ordered: a partial launch and a reduce
+ *   launch, no host synchronisation, no allocation.
+ * atmvfi_yuv_compose: dst = ONE TIGHT frame of (H, W, depth, subsampling, chroma, msb), a produced window put back into a full frame.
+ *   Outside the window (y0, x0, h, w) dst gets the sample values of `border`, a resident surface of the same size, depth, subsampling,
+ *   chroma layout and msb with its own border_pitch / border_chroma_pitch / border_chroma_offset (the uploaded source frame in
+ *   place): plane by plane, the stored samples as they are (of an msb word the value's ten bits; the low six leave as zero) --
+ *   yuv.repack(border, surface, surface.tight()) outside the window.  Inside, exactly the samples
+ *   atmvfi_yuv_sub_encode writes for the h x w picture as a frame of the cropped format (matrix, full_range, siting; chroma sums clamp
+ *   at the WINDOW's edges), from exactly one of: src, the fp32 canvas [3,Hp,Wp] with the window at (pad_top, pad_left); src_u8, uint8
+ *   [h,w,3] RGB (depth 8 only).  The encode arithmetic is that kernel itself, launched with the window's origin in the frame.
+ *   Window rule: y0 and x0 are multiples of the subsampling step per axis, y0 + h and x0 + w are multiples of it or equal H / W: every
+ *   chroma sample belongs wholly to the window or wholly to the bars.  dst must not overlap border (ATMVFI_EINVAL).  Only the bar
+ *   region of border and the window of the source are read; every output sample is written by exactly one lane, vector stores only,
+ *   no padding byte exists in dst.  Any geometry, pitch and alignment is accepted; the vector paths run under the conditions of the
+ *   surface calls with x0 a multiple of 4 as well (bars: dst, border and its strides multiples of 4 bytes).  Same bits either way.
+ *   At most two launches (the bars; the window -- none for a window that is the frame / bars that are empty).  All checks run on
+ *   the host before the first launch (ATMVFI_EINVAL). */
+int64_t atmvfi_yuv_borders_workspace_ints(int H, int W);
+int atmvfi_yuv_borders(const void* yuv, int H, int W, int depth, int msb, int64_t pitch, int32_t* out /*[H + W]*/, int32_t* workspace,
+                       int64_t workspace_ints, void* stream);
+int atmvfi_yuv_compose(void* dst, const void* border, int H, int W, int depth, int matrix, int full_range, int siting, int subsampling,
+                       int chroma, int msb, int64_t border_pitch, int64_t border_chroma_pitch, int64_t border_chroma_offset, int y0, int x0,
+                       int h, int w, const float* src /*[3,Hp,Wp] or NULL*/, int Hp, int Wp, int pad_top, int pad_left,
+                       const void* src_u8 /*uint8 [h,w,3] or NULL*/, void* stream);
+
 /* Synthetic shutter for the retimed video loop (shutter.hip; ABI 0.18; atm-vfi_amd/shutter.py holds the definition -- which samples an
  * output integrates -- and the host twin blend_numpy).  Nothing of the reference.  A blurred output is the weighted mean of the uint8 RGB
  * pixels q_k of its samples, taken in the domain of a light table and brought back to the nearest code, per channel:

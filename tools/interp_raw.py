@@ -7,7 +7,7 @@ counterpart (p010le -> nv12), or with ``--keep-depth`` at 10 bits.  ``-`` reads 
 
     python tools/interp_raw.py IN OUT --pix-fmt FMT --size WxH --fps R [--pitch N] [--matrix auto|bt601|bt709] [--siting centre|left]
                               [--full-range] --ckpt CKPT [--model base|lite] [--factor 2|4|8] [--scene] [--tta] [--global-off]
-                              [--keep-depth] [--fps-out R [--levels L] [--dedup] [--shutter ANGLE [--light code|linear]]]
+                              [--keep-depth] [--active] [--fps-out R [--levels L] [--dedup] [--shutter ANGLE [--light code|linear]]]
 
 ``--pitch N``: the input's luma row stride in bytes (a decoder's surface dump; interleaved chroma rows share it, planar ones have
 half, 4:4:4 ones all of it).  Everything from ``--factor`` on is ``interp_y4m.py``'s."""
@@ -40,6 +40,8 @@ def main():
     ap.add_argument("--tta", action="store_true", help="flip test-time augmentation of every produced frame")
     ap.add_argument("--global-off", action="store_true", help="switch the global motion branch off")
     ap.add_argument("--keep-depth", action="store_true", help="write 10-bit input back at 10 bits instead of 8")
+    ap.add_argument("--active", action="store_true", help="run the network on the active picture of letterboxed video (ActiveArea() "
+                    "defaults); 10-bit input needs --keep-depth")
     ap.add_argument("--fps-out", default=None, metavar="R", help="convert the frame rate to R (e.g. 60 or 60000/1001); --factor is ignored")
     ap.add_argument("--levels", type=int, default=3, help="with --fps-out: 2**L positions per segment (1..6)")
     ap.add_argument("--dedup", action="store_true", help="with --fps-out: drop repeated frames (Duplicates() defaults)")
@@ -50,6 +52,8 @@ def main():
         ap.error("--levels, --dedup and --shutter need --fps-out")
     if a.light != "linear" and a.shutter is None:
         ap.error("--light needs --shutter")
+    if a.active and a.shutter is not None:
+        ap.error("--active does not go with --shutter")
     try:
         w, h = (int(v) for v in a.size.lower().split("x"))
     except ValueError:
@@ -69,13 +73,16 @@ def main():
         net.load_state_dict(pkg.synthetic_state_dict(a.model, seed=1), strict=True)
     net = net.to(torch.device("cuda:0")).eval()
     net.global_motion = not a.global_off
+    area = yuv.ActiveArea() if a.active else None
     src = sys.stdin.buffer if a.src == "-" else a.src
     dst = sys.stdout.buffer if a.dst == "-" else a.dst
     info = yuv.interpolate_raw(src, dst, net, surface, a.fps, factor=a.factor, scene=yuv.SceneCuts() if a.scene else None, tta=a.tta,
-                               keep_depth=a.keep_depth,
+                               keep_depth=a.keep_depth, **({"active": area} if area is not None else {}),
                                **(dict(fps_out=a.fps_out, levels=a.levels, dedup=yuv.Duplicates() if a.dedup else None,
                                        shutter=yuv.Shutter(a.shutter, a.light) if a.shutter is not None else None) if a.fps_out else {}))
     print({k: (str(v) if k.startswith("fps") else v) for k, v in info.items()}, file=sys.stderr)
+    if area is not None:
+        print(f"interp_raw: active window (y0, x0, h, w) = {area.window} after {area.probed} frames, fallback_at = {area.fallback_at}", file=sys.stderr)
 
 
 if __name__ == "__main__":

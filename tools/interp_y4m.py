@@ -5,7 +5,7 @@ is written back as 8-bit, or with ``--keep-depth`` as C420p10 (originals byte fo
 - out.y4m --ckpt ...``).
 
     python tools/interp_y4m.py IN.y4m OUT.y4m --ckpt CKPT [--model base|lite] [--factor 2|4|8] [--scene] [--tta] [--global-off]
-                              [--keep-depth] [--fps-out R [--levels L] [--dedup] [--shutter ANGLE [--light code|linear]]]
+                              [--keep-depth] [--active] [--fps-out R [--levels L] [--dedup] [--shutter ANGLE [--light code|linear]]]
 
 ``--fps-out R`` (an integer or a ratio such as 60000/1001) converts the frame rate to exactly R instead of multiplying it: every output
 is the nearest of 2**L positions (``--levels``, default 3) between two source frames; ``--dedup`` drops repeated frames first
@@ -35,6 +35,8 @@ def main():
     ap.add_argument("--global-off", action="store_true", help="switch the global motion branch off")
     ap.add_argument("--matrix", choices=("auto", "bt601", "bt709"), default="auto", help="a Y4M header cannot name the matrix")
     ap.add_argument("--keep-depth", action="store_true", help="write 10-bit (C420p10) input back as C420p10 instead of 8-bit")
+    ap.add_argument("--active", action="store_true", help="run the network on the active picture of letterboxed video (ActiveArea() "
+                    "defaults); 10-bit input needs --keep-depth")
     ap.add_argument("--fps-out", default=None, metavar="R", help="convert the frame rate to R (e.g. 60 or 60000/1001); --factor is ignored")
     ap.add_argument("--levels", type=int, default=3, help="with --fps-out: 2**L positions per segment (1..6)")
     ap.add_argument("--dedup", action="store_true", help="with --fps-out: drop repeated frames (Duplicates() defaults)")
@@ -45,6 +47,8 @@ def main():
         ap.error("--levels, --dedup and --shutter need --fps-out")
     if a.light != "linear" and a.shutter is None:
         ap.error("--light needs --shutter")
+    if a.active and a.shutter is not None:
+        ap.error("--active does not go with --shutter")
     if not torch.cuda.is_available():
         sys.exit("interp_y4m: no GPU")
     pkg = importlib.import_module("atm-vfi_amd")
@@ -58,13 +62,16 @@ def main():
         net.load_state_dict(pkg.synthetic_state_dict(a.model, seed=1), strict=True)
     net = net.to(torch.device("cuda:0")).eval()
     net.global_motion = not a.global_off
+    area = yuv.ActiveArea() if a.active else None
     src = sys.stdin.buffer if a.src == "-" else a.src
     dst = sys.stdout.buffer if a.dst == "-" else a.dst
     info = yuv.interpolate_y4m(src, dst, net, factor=a.factor, scene=yuv.SceneCuts() if a.scene else None, tta=a.tta, matrix=a.matrix,
-                               keep_depth=a.keep_depth,
+                               keep_depth=a.keep_depth, **({"active": area} if area is not None else {}),
                                **(dict(fps_out=a.fps_out, levels=a.levels, dedup=yuv.Duplicates() if a.dedup else None,
                                        shutter=yuv.Shutter(a.shutter, a.light) if a.shutter is not None else None) if a.fps_out else {}))
     print({k: (str(v) if k.startswith("fps") else v) for k, v in info.items()}, file=sys.stderr)
+    if area is not None:
+        print(f"interp_y4m: active window (y0, x0, h, w) = {area.window} after {area.probed} frames, fallback_at = {area.fallback_at}", file=sys.stderr)
 
 
 if __name__ == "__main__":
