@@ -19,7 +19,7 @@ from typing import List, Optional
 
 import torch
 
-from .pixfmt import Surface, _not_420, _origin_error, as_surface
+from .pixfmt import Packed, Surface, _not_420, _origin_error, as_surface
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libatmvfi_hip.so")
@@ -160,6 +160,8 @@ SIGNATURES = {
     "atmvfi_yuv_sub_decode": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_l, c_l, c_l, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_f, c_i, c_i,
                                     c_i, c_i, c_f]),
     "atmvfi_yuv_sub_encode": (c_i, [c_f, c_i, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f]),
+    "atmvfi_yuv_unpack": (c_i, [c_f, c_i, c_i, c_i, c_l, c_f, c_f]),
+    "atmvfi_yuv_pack": (c_i, [c_f, c_i, c_i, c_i, c_f, c_f]),
     "atmvfi_pack_frames": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_f]),
     "atmvfi_final_residual": (c_i, [c_f, c_f, c_i, c_f, c_f, c_i, c_i, c_i, c_f]),
     "atmvfi_l1_mean": (c_i, [c_f, c_f, c_f, c_i, c_l, c_f, c_l, c_f]),
@@ -1477,6 +1479,41 @@ class HipOps:
         self._check(self.lib.atmvfi_yuv_borders(_ptr(buf), sh, sw, int(s.depth), int(s.msb), int(s.pitch), _ptr(out), _ptr(workspace),
                                                 workspace.numel(), self._stream()), "yuv_borders")
         return out
+
+    def _packed_pair(self, who: str, packed, buf, planar):
+        """the two byte tensors of ``yuv_unpack`` / ``yuv_pack`` checked against ``packed`` (a missing one, the call's output, is made)"""
+        if not isinstance(packed, Packed):
+            raise ValueError(f"{who}: a yuv.Packed expected (got {type(packed).__name__})")
+        mk = lambda n: torch.empty(n, dtype=torch.uint8, device=self.device)
+        buf = mk(packed.nbytes) if buf is None else buf
+        planar = mk(packed.planar.frame_bytes) if planar is None else planar
+        for t, n, role in ((buf, packed.nbytes, f"{packed.layout} frame (pitch {packed.pitch})"),
+                           (planar, packed.planar.frame_bytes, "planar 4:2:2 frame")):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1 or t.numel() != n or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError(f"{who}: the {role} must be a contiguous CUDA uint8 tensor of {n} bytes ({packed.height} x {packed.width}, "
+                                 f"depth {packed.depth})")
+        return buf, planar
+
+    def yuv_unpack(self, buf, packed, dst=None):
+        """One packed 4:2:2 frame of ``packed`` (a ``yuv.Packed``: uyvy, yuy2, y210 or v210 at its pitch; ``buf`` its bytes on the
+        device) -> ``dst``, the bytes of the planar 4:2:2 frame of ``packed.planar`` (a new tensor when None): the sample values,
+        moved; padding is never read (include/atmvfi.h atmvfi_yuv_unpack; the bits of ``yuv.unpack_numpy``).  Not part of a forward:
+        never recorded into a launch plan."""
+        buf, dst = self._packed_pair("yuv_unpack", packed, buf, dst)
+        self._check(self.lib.atmvfi_yuv_unpack(_ptr(buf), packed.height, packed.width, packed.layout_id, int(packed.pitch), _ptr(dst),
+                                               self._stream()), "yuv_unpack")
+        return dst
+
+    def yuv_pack(self, planar, packed, dst=None):
+        """The bytes of one planar 4:2:2 frame of ``packed.planar`` -> ``dst``, one frame of the TIGHT ``packed`` (a new tensor when
+        None): the sample values, moved; every byte of ``dst`` is written, what holds no sample as zero (include/atmvfi.h
+        atmvfi_yuv_pack; the bits of ``yuv.pack_numpy``).  Not part of a forward: never recorded into a launch plan."""
+        if isinstance(packed, Packed) and not packed.is_tight:
+            raise ValueError("yuv_pack: packed must be at its default pitch (packs write no custom pitch: packed.tight())")
+        dst, planar = self._packed_pair("yuv_pack", packed, dst, planar)
+        self._check(self.lib.atmvfi_yuv_pack(_ptr(planar), packed.height, packed.width, packed.layout_id, _ptr(dst), self._stream()),
+                    "yuv_pack")
+        return dst
 
     def yuv_compose(self, dst, out_surface, border, border_surface, window, src=None, src_u8=None, pad_top: int = 0, pad_left: int = 0):
         """A produced window back into a full YUV frame: ``dst`` (one frame of the TIGHT ``out_surface``, a ``yuv.Format`` or

@@ -250,6 +250,8 @@ class FramePipeline:
 
     def __init__(self, model, height: int, width: int, isBGR: bool = True, divisor: int = 64, depth: int = 3, streams: int = 1,
                  scene=None, pixfmt=None, keep_depth: bool = False):
+        if hasattr(pixfmt, "layout"):                # (a yuv.Packed)
+            raise ValueError("FramePipeline: packed 4:2:2 frames are not taken here: interpolate_video_nx(factor=2) covers 2x")
         ops, dev = _hip_ops_of(model)
         if ops is None:
             raise RuntimeError("FramePipeline needs an atm-vfi_amd Network on the GPU")

@@ -24,7 +24,7 @@ from typing import Callable, Iterable, Iterator, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import segments
-from .segments import DeviceBackend, HostBackend, chain, open_stream
+from .segments import DeviceBackend, HostBackend, chain, open_stream, planar_of
 
 
 # ------------------------------------------------------------------------------------------------ schedule (no device)
@@ -144,18 +144,24 @@ class FramePool:
 _Uploader, _SegmentRunner = segments._Uploader, segments._SegmentRunner
 
 
-def _active_window(active, first, it, st, model, device, divisor, step, pixfmt=None, caller: str = "interpolate_video_nx"):
+def _active_window(active, first, it, st, model, device, divisor, step, pixfmt=None, caller: str = "interpolate_video_nx", packed=None):
     """``(window, frames)`` of ``active=`` (both loops): a fixed window as it is given; an ``ActiveArea`` after its probe, the frames
     it read replayed in front of ``it`` (the loop uploads them again); a fixed window's even values fit every subsampling.  ``device``: ``(ops, dev)`` of the HIP backend, or None.
     A window that gains nothing is None: the whole frame, the plain loop.  ``pixfmt``: the frames are that format's, the profiles
     those of their luma plane and the threshold its sample code (``active.bar_code``); a locked window that ends on an odd line of a
-    subsampled frame is widened by that line (``active.yuv_window_error`` holds the rule)."""
+    subsampled frame is widened by that line (``active.yuv_window_error`` holds the rule).  ``packed`` (a ``yuv.Packed``, ``pixfmt`` its
+    planar format): a probed frame is unpacked first (on the device by ``HipOps.yuv_unpack``)."""
     from . import active as _active
+    accept = (packed or pixfmt).check if pixfmt is not None else None
     if not hasattr(active, "probe_stream"):
         win, frames = _active.fixed_window(active, st.H, st.W), chain(first, it)
     else:
         if device is None:
-            profile_of = (lambda f: _active.borders_numpy(f, bgr=st.isBGR)) if pixfmt is None else (lambda f: _active.yuv_borders_numpy(f, pixfmt))
+            if packed is not None:
+                from .yuv import unpack_numpy
+                profile_of = lambda f: _active.yuv_borders_numpy(unpack_numpy(f, packed), pixfmt)
+            else:
+                profile_of = (lambda f: _active.borders_numpy(f, bgr=st.isBGR)) if pixfmt is None else (lambda f: _active.yuv_borders_numpy(f, pixfmt))
         else:
             import torch
             ops, dev = device
@@ -164,9 +170,10 @@ def _active_window(active, first, it, st, model, device, divisor, step, pixfmt=N
                 with torch.cuda.device(dev):
                     if pixfmt is None:
                         return ops.frame_borders(torch.from_numpy(np.ascontiguousarray(f)).to(dev), bgr=bool(st.isBGR)).cpu().numpy()
-                    return ops.yuv_borders(torch.from_numpy(pixfmt.check(f, caller).view(np.uint8)).to(dev), pixfmt).cpu().numpy()
+                    d = torch.from_numpy(accept(f, caller).view(np.uint8)).to(dev)
+                    return ops.yuv_borders(d if packed is None else ops.yuv_unpack(d, packed), pixfmt).cpu().numpy()
         need = 16 if getattr(model, "global_motion", True) else 8
-        yuv_kw = {} if pixfmt is None else dict(code=_active.bar_code(pixfmt, active.peak), accept=lambda f: pixfmt.check(f, caller))
+        yuv_kw = {} if pixfmt is None else dict(code=_active.bar_code(pixfmt, active.peak), accept=lambda f: accept(f, caller))
         held = active.probe_stream(chain(first, it), st.H, st.W, divisor, need, step, profile_of, **yuv_kw)
         win = active.window
         if pixfmt is not None and win != (0, 0, st.H, st.W):
@@ -240,7 +247,13 @@ def interpolate_video_nx(frames, model, factor: int = 4, time_interval: int = 1,
     produced position leaves through ``HipOps.yuv_compose``: the window's encode inside, the nearer original's own samples outside,
     plane by plane -- the bars never pass through RGB.  A 10-bit ``pixfmt`` needs ``keep_depth=True`` (``ValueError`` otherwise: 8-bit
     output converts the originals on the host, no sample copy reproduces that), and a first frame that is not of the ``pixfmt`` is
-    refused before anything else."""
+    refused before anything else.
+
+    ``pixfmt=yuv.Packed(...)`` (packed 4:2:2: uyvy, yuy2, y210, v210): inside, the stream is the planar 4:2:2 stream of
+    ``pixfmt.planar`` and everything above holds for it.  Every uploaded frame is unpacked on the copy stream right behind its copy
+    (``HipOps.yuv_unpack``), a produced frame is encoded into a planar scratch and packed into the output ring (``HipOps.yuv_pack``):
+    the same layout at its default pitch, for a 10-bit layout without ``keep_depth`` its 8-bit one (v210 -> uyvy, y210 -> yuy2).
+    Originals at the default pitch are the caller's own arrays, at another pitch their tight repacks."""
     from .host_io import _hip_ops_of
     from .scene import cut_fill
     nx_levels(factor)
@@ -258,6 +271,7 @@ def interpolate_video_nx(frames, model, factor: int = 4, time_interval: int = 1,
     if active is not None:
         _active_refusals("interpolate_video_nx", active, crop, pixfmt, keep_depth, first)
     st = open_stream(first, crop, pixfmt, keep_depth, isBGR, "interpolate_video_nx")
+    packed, pixfmt = planar_of(pixfmt)               # (a packed 4:2:2 stream is its planar stream from here on)
     step = int(time_interval)
     if step < 1:
         raise ValueError(f"time_interval must be >= 1, got {time_interval!r}")
@@ -265,8 +279,10 @@ def interpolate_video_nx(frames, model, factor: int = 4, time_interval: int = 1,
     generic = ops is None or not hasattr(ops, "pool_blocks")
     source, win = chain(first, it), None
     if active is not None:
-        win, source = _active_window(active, first, it, st, model, None if generic else (ops, dev), divisor, step, pixfmt)
+        win, source = _active_window(active, first, it, st, model, None if generic else (ops, dev), divisor, step, pixfmt, packed=packed)
     common = dict(n=factor, divisor=divisor, tta=tta, pixfmt=pixfmt, window=win, watch=area is not None)
+    if packed is not None:
+        common["packed"] = packed
     if generic:
         be = HostBackend(model, st, max_batch=max(1, int(max_batch)), **common)
     else:

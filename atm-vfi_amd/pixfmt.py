@@ -265,6 +265,113 @@ class Surface:
         return (Y, first, second) if self.chroma == "uv" else (Y, second, first)
 
 
+PACKED_LAYOUTS = ("uyvy", "yuy2", "y210", "v210")      # ids 0..3 (include/atmvfi.h, atmvfi_yuv_unpack)
+_PACKED_DEPTH = {"uyvy": 8, "yuy2": 8, "y210": 10, "v210": 10}
+_PACKED_8BIT = {"v210": "uyvy", "y210": "yuy2"}
+
+
+@dataclass(frozen=True)
+class Packed:
+    """One frame as a capture card hands it over: packed 4:2:2, luma and chroma interleaved in one plane.  ``fmt`` (a ``Format`` with
+    ``subsampling="422"``) supplies size, matrix, range, siting and depth; the pixel arithmetic is the ``Format``'s, applied to the
+    samples found here (``planar``: the tight planar frame they unpack to -- ``yuv.unpack_numpy`` / ``pack_numpy``, ``HipOps.yuv_unpack``
+    / ``yuv_pack`` move the sample values, nothing else).
+
+    ``layout``: "uyvy" (8 bit, uint8, U0 Y0 V0 Y1 per pixel pair), "yuy2" (8 bit, uint8, Y0 U0 Y1 V0), "y210" (10 bit, uint16, Y0 U0 Y1
+    V0, a stored sample is ``value << 6``) or "v210" (10 bit, a uint8 byte stream: groups of four little-endian 32-bit words for 6
+    pixels, three components per word in bits 0-9, 10-19, 20-29: (Cb0, Y0, Cr0), (Y1, Cb1, Y2), (Cr1, Y3, Cb2), (Y4, Cr2, Y5)).  The
+    width is even.  ``pitch``: the row stride in bytes, at least the row's own bytes (``2 W``, ``2 W``, ``4 W``, ``ceil(W / 6) * 16``)
+    and a multiple of 4 (v210: 16); default ``2 W``, ``2 W``, ``4 W`` and v210's ``ceil(W / 48) * 128``.  ``nbytes = pitch * H``;
+    frames are 1-D arrays of ``nbytes // itemsize`` samples.  Bytes and component slots that hold no sample (row padding, v210's
+    slots beyond W and bits 30-31, y210's low six bits) are never interpreted on unpack and written as zero on pack."""
+    fmt: Format
+    layout: str
+    pitch: Optional[int] = None
+
+    def __post_init__(self):
+        if not isinstance(self.fmt, Format):
+            raise ValueError(f"yuv.Packed: fmt must be a yuv.Format (got {type(self.fmt).__name__})")
+        if self.layout not in PACKED_LAYOUTS:
+            raise ValueError(f"yuv.Packed: unknown layout {self.layout!r} ({', '.join(PACKED_LAYOUTS)})")
+        if self.fmt.subsampling != "422":
+            raise ValueError(f"yuv.Packed: {self.layout} is a 4:2:2 layout (got subsampling {self.fmt.subsampling})")
+        if self.fmt.depth != _PACKED_DEPTH[self.layout]:
+            raise ValueError(f"yuv.Packed: {self.layout} holds {_PACKED_DEPTH[self.layout]}-bit samples (got depth {self.fmt.depth})")
+        W = self.fmt.width
+        if W % 2:
+            raise ValueError(f"yuv.Packed: {self.layout} carries chroma per pixel pair: the width must be even (got {W})")
+        row, unit = self.row_bytes, 16 if self.layout == "v210" else 4
+        pitch = self.default_pitch if self.pitch is None else int(self.pitch)
+        if pitch % unit or pitch < row:
+            raise ValueError(f"yuv.Packed: pitch {pitch} must be a multiple of {unit} and at least a {self.layout} row's {row} bytes")
+        object.__setattr__(self, "pitch", pitch)
+
+    height = property(lambda self: self.fmt.height)
+    width = property(lambda self: self.fmt.width)
+    matrix = property(lambda self: self.fmt.matrix)
+    full_range = property(lambda self: self.fmt.full_range)
+    siting = property(lambda self: self.fmt.siting)
+    depth = property(lambda self: self.fmt.depth)
+    subsampling = property(lambda self: self.fmt.subsampling)
+    steps = property(lambda self: self.fmt.steps)
+    layout_id = property(lambda self: PACKED_LAYOUTS.index(self.layout))
+
+    @property
+    def row_bytes(self) -> int:
+        """the bytes of a row that hold samples"""
+        W = self.fmt.width
+        return {"uyvy": 2 * W, "yuy2": 2 * W, "y210": 4 * W, "v210": (W + 5) // 6 * 16}[self.layout]
+
+    @property
+    def default_pitch(self) -> int:
+        return (self.fmt.width + 47) // 48 * 128 if self.layout == "v210" else self.row_bytes
+
+    @property
+    def dtype(self):
+        return np.uint16 if self.layout == "y210" else np.uint8
+
+    @property
+    def itemsize(self) -> int:
+        return 2 if self.layout == "y210" else 1
+
+    @property
+    def nbytes(self) -> int:
+        return self.pitch * self.fmt.height
+
+    frame_bytes = nbytes
+
+    @property
+    def frame_samples(self) -> int:
+        return self.nbytes // self.itemsize
+
+    @property
+    def is_tight(self) -> bool:
+        return self.pitch == self.default_pitch
+
+    @property
+    def planar(self) -> Format:
+        """The tight planar 4:2:2 ``Format`` the samples unpack to."""
+        return self.fmt
+
+    def tight(self) -> "Packed":
+        return self if self.is_tight else Packed(self.fmt, self.layout)
+
+    def cropped(self, h: int, w: int) -> "Packed":
+        return Packed(self.fmt.cropped(h, w), self.layout)
+
+    def as_8bit(self) -> "Packed":
+        """The tight 8-bit counterpart (v210 -> uyvy, y210 -> yuy2), ``tight()`` for an 8-bit layout."""
+        return self.tight() if self.fmt.depth == 8 else Packed(self.fmt.as_8bit(), _PACKED_8BIT[self.layout])
+
+    def check(self, buf, what: str = "yuv") -> np.ndarray:
+        """``buf`` as the 1-D sample array of one frame of this layout (a view), or ``ValueError``."""
+        a = np.asarray(buf)
+        if a.dtype != self.dtype or a.size != self.frame_samples or not a.flags.c_contiguous:
+            raise ValueError(f"{what}: a contiguous {np.dtype(self.dtype).name} {self.layout} frame of {self.frame_samples} samples "
+                             f"({self.height} x {self.width}, pitch {self.pitch}) expected, got {a.dtype} {tuple(a.shape)}")
+        return a.reshape(-1)
+
+
 @functools.lru_cache(maxsize=64)
 def _tight_surface(fmt: Format) -> Surface:
     return Surface(fmt)

@@ -33,7 +33,7 @@ import numpy as np
 
 from .multiframe import centre_window
 from .scene import _bounds
-from .segments import DeviceBackend, HostBackend, chain, open_stream
+from .segments import DeviceBackend, HostBackend, chain, open_stream, planar_of
 
 DIFF_WORDS = 258
 MAX_LEVELS = 6
@@ -253,7 +253,8 @@ def interpolate_video_retimed(frames, model, fps_in, fps_out, levels: int = 3, d
     at ``p <= N/2`` are copies of the first original and the rest copies of the second.
 
     ``divisor``, ``tta``, ``pool``, ``pixfmt`` and ``keep_depth`` as in ``multiframe.interpolate_video_nx`` (with a 10-bit ``pixfmt``
-    and ``keep_depth`` the resident uint8 RGB frame is made only when ``dedup`` or ``scene`` needs it).  There is no ``time_interval``.
+    and ``keep_depth`` the resident uint8 RGB frame is made only when ``dedup`` or ``scene`` needs it; a ``yuv.Packed`` is taken as
+    there: unpacked behind the upload, packed in front of the download).  There is no ``time_interval``.
     A model without the HIP backend gets the same frames through torch and the numpy twins.  ``report`` (a dict): filled with
     ``"outputs"``, ``"interpolated"`` and ``"forwards"`` (the recursion nodes evaluated: pairs through the network, the second pass of
     flip-TTA not counted) of the run.
@@ -315,15 +316,18 @@ def _retimed(frames, model, fi, fo, levels, dedup, crop, isBGR, divisor, tta, ma
     if active is not None:
         _active_refusals("interpolate_video_retimed", active, crop, pixfmt, keep_depth, first)
     st = open_stream(first, crop, pixfmt, keep_depth, isBGR, "interpolate_video_retimed")
+    packed, pixfmt = planar_of(pixfmt)               # (a packed 4:2:2 stream is its planar stream from here on)
     if pixfmt is None and (first.ndim != 3 or first.shape[2] != 3 or first.dtype != np.uint8):
         raise ValueError(f"interpolate_video_retimed: expected uint8 [H,W,3] frames, got {first.dtype} {tuple(first.shape)}")
     (h, w), original = st.window[2:], st.original
     ops, dev = _hip_ops_of(model)
     common = dict(n=n, divisor=divisor, tta=tta, pixfmt=pixfmt, caller="interpolate_video_retimed")
+    if packed is not None:
+        common["packed"] = packed
     generic = ops is None or not hasattr(ops, "pool_blocks")
     if active is not None:
         win, source = _active_window(active, first, it, st, model, None if generic else (ops, dev), divisor, 1, pixfmt,
-                                     "interpolate_video_retimed")
+                                     "interpolate_video_retimed", packed=packed)
         first, it = next(source), source             # (the probed frames replayed)
         common.update(window=win, watch=area is not None)
     if generic:

@@ -25,6 +25,14 @@ class Stream(NamedTuple):
     out_fmt: object                                  # the ``yuv.Format`` of produced frames (None: uint8 RGB)
     deep: bool                                       # a 10-bit ``pixfmt`` with ``keep_depth``
     isBGR: bool                                      # (a ``pixfmt`` overrides it: False)
+    packed: object = None                            # a ``yuv.Packed`` stream: the tight layout produced frames are packed into
+
+
+def planar_of(pixfmt):
+    """``(packed, pixfmt)`` of a loop's ``pixfmt``: a ``yuv.Packed`` and the planar 4:2:2 format its stream IS inside the loop; any other
+    ``pixfmt``, or none, as ``(None, pixfmt)``."""
+    from .pixfmt import Packed
+    return (pixfmt, pixfmt.planar) if isinstance(pixfmt, Packed) else (None, pixfmt)
 
 
 def open_stream(first, crop, pixfmt, keep_depth, isBGR, caller: str) -> Stream:
@@ -42,7 +50,10 @@ def open_stream(first, crop, pixfmt, keep_depth, isBGR, caller: str) -> Stream:
     deep = bool(keep_depth) and pixfmt.depth == 10
     # (a padded yuv.Surface: originals lose the padding)
     original = (lambda f: f) if (whole and yuv.passes_through(pixfmt)) else (lambda f: yuv.crop(f, pixfmt, y0, x0, h, w))
-    return Stream(H, W, window, crop_rgb, original, yuv.out_format(pixfmt, deep).cropped(h, w), deep, False)
+    out = yuv.out_format(pixfmt, deep).cropped(h, w)
+    if isinstance(pixfmt, yuv.Packed):      # produced frames: encoded as planar 4:2:2, then packed
+        return Stream(H, W, window, crop_rgb, original, out.planar, deep, False, out)
+    return Stream(H, W, window, crop_rgb, original, out, deep, False)
 
 
 def chain(first, it):
@@ -101,13 +112,17 @@ class _Uploader:
     with a ``pixfmt`` those of the uploaded surface's luma plane (``HipOps.yuv_borders`` on the slot's ``yuv`` bytes: no RGB frame is
     needed for it).  ``stop_borders()`` ends it for the uploads still to come.
 
+    ``packed`` (a ``yuv.Packed``, with ``pixfmt=(ops, packed.planar)``): the frames arrive in that layout.  The pinned slot and one more
+    device staging buffer per slot (``pk``) hold ``packed.nbytes``; ``HipOps.yuv_unpack`` runs on the copy stream right behind the
+    copy, into the slot's ``yuv`` bytes, before anything else: from there on the slot holds a planar frame as above.
+
     ``caller``: the loop's name, for the refusal of a frame of another size or type."""
 
     def __init__(self, dev, height: int, width: int, depth: int = 3, signature=None, pixfmt=None, deep: bool = False, difference=None,
-                 borders=None, caller: str = "interpolate_video_nx"):
+                 borders=None, caller: str = "interpolate_video_nx", packed=None):
         import torch
         self.torch, self.dev, self.h, self.w, self.depth, self.caller = torch, dev, height, width, depth, caller
-        self.pixfmt, self.deep = pixfmt, bool(deep)
+        self.pixfmt, self.deep, self.packed = pixfmt, bool(deep), packed
         self.probes: List[_Probe] = []
         if signature is not None:
             s_ops, s_win, s_bgr = signature
@@ -126,7 +141,9 @@ class _Uploader:
                 self.probes.append(_Probe("borders", height + width, b_ops.yuv_borders_workspace(height, width), lambda prev, s, out, ws:
                                           b_ops.yuv_borders(s["yuv"], pixfmt[1], out=out, workspace=ws)))
         self.pairs, self.prev = difference is not None, None          # prev: the slot of the previous upload
-        in_shape = (height, width, 3) if pixfmt is None else (pixfmt[1].frame_bytes,)
+        yuv_shape = in_shape = (height, width, 3) if pixfmt is None else (pixfmt[1].frame_bytes,)
+        if packed is not None:
+            in_shape = (packed.nbytes,)
         need_rgb = not self.deep or signature is not None or difference is not None
         self.ring = [{"h": torch.empty(*in_shape, dtype=torch.uint8).pin_memory(),
                       "d": torch.empty(height, width, 3, dtype=torch.uint8, device=dev) if need_rgb else None,
@@ -134,7 +151,9 @@ class _Uploader:
         for s in self.ring:
             s["h_np"] = s["h"].numpy()
             if pixfmt is not None:
-                s["yuv"] = torch.empty(*in_shape, dtype=torch.uint8, device=dev)
+                s["yuv"] = torch.empty(*yuv_shape, dtype=torch.uint8, device=dev)
+            if packed is not None:
+                s["pk"] = torch.empty(*in_shape, dtype=torch.uint8, device=dev)
             for p in self.probes:                    # name -> (device words, pinned twin, its numpy view, event)
                 pinned = torch.empty(p.words, dtype=torch.int32).pin_memory()
                 s[p.name] = (torch.empty(p.words, dtype=torch.int32, device=dev), pinned, pinned.numpy(), torch.cuda.Event())
@@ -145,7 +164,7 @@ class _Uploader:
         """Start the host -> device copy of ``frame``; returns the ring slot to hand to ``take``."""
         torch = self.torch
         if self.pixfmt is not None:
-            frame = self.pixfmt[1].check(frame, self.caller).view(np.uint8)
+            frame = (self.packed or self.pixfmt[1]).check(frame, self.caller).view(np.uint8)
         elif frame.shape != (self.h, self.w, 3) or frame.dtype != np.uint8:
             raise ValueError(f"{self.caller}: expected uint8 [{self.h},{self.w},3] frames, got {frame.dtype} {tuple(frame.shape)}")
         slot = self.ring[self.issued % self.depth]
@@ -158,7 +177,11 @@ class _Uploader:
             if self.pixfmt is None:
                 slot["d"].copy_(slot["h"], non_blocking=True)
             else:
-                slot["yuv"].copy_(slot["h"], non_blocking=True)
+                if self.packed is None:
+                    slot["yuv"].copy_(slot["h"], non_blocking=True)
+                else:
+                    slot["pk"].copy_(slot["h"], non_blocking=True)
+                    self.pixfmt[0].yuv_unpack(slot["pk"], self.packed, dst=slot["yuv"])
                 if slot["d"] is not None:
                     self.pixfmt[0].yuv_decode(slot["yuv"], self.pixfmt[1], dst_u8=slot["d"])
             slot["ready"].record(self.copy_in)
@@ -237,10 +260,13 @@ class _SegmentRunner:
     in positions 0 and N, copied device to device where the source frame is converted and swapped with the positions: uint8 [H,W,3],
     or with ``out_fmt`` / ``deep_fmt`` the uploaded surfaces in the input layout ``border_fmt``.  A produced position k leaves through
     ``frame_compose`` (``yuv_compose``) into a FULL-SIZE output ring entry: the prediction's window inside -- with ``tta`` ``tta_merge``'s
-    uint8 window, with the depth kept the fp32 average -- and the bars of the nearer original (k <= N/2: position 0) outside."""
+    uint8 window, with the depth kept the fp32 average -- and the bars of the nearer original (k <= N/2: position 0) outside.
+
+    ``pack`` (a tight ``yuv.Packed`` whose ``planar`` is ``out_fmt``; a packed 4:2:2 stream): the output ring holds frames of that
+    layout.  A produced frame leaves as above into ONE planar scratch and ``HipOps.yuv_pack`` writes the ring entry from it."""
 
     def __init__(self, model, ops, dev, height, width, factor, crop, bgr, divisor, tta, max_batch, pool, out_fmt=None, deep_fmt=None,
-                 out_slots=None, batch_sizes=None, blend=None, window=None, border_fmt=None):
+                 out_slots=None, batch_sizes=None, blend=None, window=None, border_fmt=None, pack=None):
         import torch
         from .multiframe import FramePool, centre_window, nx_levels
         self.torch, self.model, self.ops, self.dev = torch, model, ops, dev
@@ -268,6 +294,11 @@ class _SegmentRunner:
         self.have_first = self.fresh = False
         self.gather = {}                             # plain mode: the pairs of a batch are gathered into contiguous [B,3,Hp,Wp] inputs
         out_shape = (out_fmt.frame_bytes,) if out_fmt is not None else (height, width, 3) if self.border is not None else (self.h, self.w, 3)
+        self.pack = self.planar = None
+        if pack is not None:
+            if out_fmt is None or pack.planar != out_fmt or not pack.is_tight:
+                raise ValueError("_SegmentRunner: pack must be the tight packed layout of out_fmt")
+            self.pack, self.planar, out_shape = pack, u8(out_fmt.frame_bytes), (pack.nbytes,)
         n_out = factor - 1 if out_slots is None else max(1, min(int(out_slots), factor - 1))
         self.blend = None
         if blend is not None:
@@ -284,6 +315,8 @@ class _SegmentRunner:
             self.merged = (torch.empty(3, self.hp, self.wp, dtype=torch.float32, device=dev) if deep_fmt is not None else u8(self.h, self.w, 3))
         mode = "compose" if self.border is not None else "deep" if deep_fmt is not None else "yuv" if out_fmt is not None else "u8"
         self.leave = self._LEAVE[mode, self.tta]     # (the plain function, not a bound method: the runner must not hold itself alive)
+        if self.pack is not None:
+            self._leave_planar, self.leave = self.leave, _SegmentRunner._leave_packed
         self.out_evt = [torch.cuda.Event() for _ in range(2)]
         self.seg = 0
         self.copy_out = torch.cuda.Stream(dev)
@@ -420,6 +453,10 @@ class _SegmentRunner:
         self.ops.tta_merge(pred, flip, out_u8=self.merged, pad_top=self.pad_top, pad_left=self.pad_left, bgr=self.bgr and self.out_fmt is None)
         self._compose(u8, pos, win=self.merged)
 
+    def _leave_packed(self, pos, pred, flip, u8):    # the planar frame as without ``pack``, then its packed form
+        self._leave_planar(self, pos, pred, flip, self.planar)
+        self.ops.yuv_pack(self.planar, self.pack, dst=u8)
+
     _LEAVE = {("u8", False): _leave_u8, ("u8", True): _leave_u8_tta, ("yuv", False): _leave_yuv, ("yuv", True): _leave_yuv_tta,
               ("deep", False): _leave_yuv, ("deep", True): _leave_deep_tta,      # (out_fmt is the 10-bit format then)
               ("compose", False): _leave_compose, ("compose", True): _leave_compose_tta}
@@ -489,7 +526,11 @@ class _SegmentRunner:
             self.ops.shutter_resolve(*closed, self.out_d[k], light=self.blend.light, bgr=self.bgr)
         else:                                        # the blend's uint8 pixels, then their encoding
             self.ops.shutter_resolve(*closed, self.blend_u8, light=self.blend.light)
-            self.ops.yuv_encode(self.out_d[k], self.out_fmt, src_u8=self.blend_u8)
+            if self.pack is None:
+                self.ops.yuv_encode(self.out_d[k], self.out_fmt, src_u8=self.blend_u8)
+            else:
+                self.ops.yuv_encode(self.planar, self.out_fmt, src_u8=self.blend_u8)
+                self.ops.yuv_pack(self.planar, self.pack, dst=self.out_d[k])
         return k + 1
 
     def _run_blended(self, levels, ops, cut):
@@ -545,7 +586,7 @@ class _SegmentRunner:
         self.out_evt[ring].synchronize()
         arr = self.out_h[ring].numpy()
         count = self.n - 1 if count is None else count
-        if self.deep_fmt is not None:
+        if (self.deep_fmt is not None) if self.pack is None else self.pack.itemsize == 2:
             return [arr[k].copy().view(np.uint16) for k in range(count)]
         return [arr[k].copy() for k in range(count)]
 
@@ -609,12 +650,14 @@ class HostBackend:
     (``_rgb``: kept in its entry, so the frame that ends a segment is not decoded again when it starts the next).  ``window`` (the
     active picture): the forwards run on that window of the frames and every produced window is composed into a full frame with the
     bars of the nearer original -- with a ``pixfmt`` the window's encode into the original's own samples -- until ``whole_frame()``;
-    ``watching``: the loop examines ``borders`` of the frames it admits."""
+    ``watching``: the loop examines ``borders`` of the frames it admits.  ``packed`` (a ``yuv.Packed``, ``pixfmt`` its planar format):
+    an admitted frame is unpacked once (``yuv.unpack_numpy``; ``_frame``), everything above works on the planar frame, and what is
+    produced is packed into ``st.packed`` (``yuv.pack_numpy``)."""
     lookahead = False                                # (nothing is gained by reading a segment ahead)
 
     def __init__(self, model, st: Stream, n, divisor, tta, max_batch, pixfmt=None, dedup=None, light=None, window=None, watch=False,
-                 caller: str = "interpolate_video_nx"):
-        self.n, self.levels, self.st, self.pixfmt, self.caller = n, n.bit_length() - 1, st, pixfmt, caller
+                 caller: str = "interpolate_video_nx", packed=None):
+        self.n, self.levels, self.st, self.pixfmt, self.caller, self.packed = n, n.bit_length() - 1, st, pixfmt, caller, packed
         self.dedup, self.prev_rgb = dedup, None
         self.light, self.gathered = light, {}        # (the synthetic shutter: ``blended``)
         self.watching = window is not None and watch
@@ -635,18 +678,33 @@ class HostBackend:
         else:
             self.seg = self._generic(st.crop_rgb)
 
+    def _frame(self, e):
+        """the frame of ``pixfmt`` (a packed 4:2:2 frame: unpacked once)"""
+        if self.packed is None:
+            return e["f"]
+        if "planar" not in e:
+            from . import yuv
+            e["planar"] = yuv.unpack_numpy(e["f"], self.packed)
+        return e["planar"]
+
+    def _packed_out(self, frames):
+        if self.packed is None:
+            return frames
+        from . import yuv
+        return [yuv.pack_numpy(f, self.st.packed) for f in frames]
+
     def _rgb(self, e):
         """the uint8 [H,W,3] picture of a frame (an I420 frame: decoded once)"""
         if self.pixfmt is None:
             return e["f"]
         if "rgb" not in e:
             from . import yuv
-            e["rgb"] = yuv.decode_numpy(e["f"], self.pixfmt)
+            e["rgb"] = yuv.decode_numpy(self._frame(e), self.pixfmt)
         return e["rgb"]
 
     def admit(self, e):
         if self.pixfmt is not None:
-            self.pixfmt.check(e["f"], self.caller)
+            (self.packed or self.pixfmt).check(e["f"], self.caller)
         if self.dedup is not None:
             from .retime import difference_numpy
             rgb = self._rgb(e)
@@ -666,7 +724,7 @@ class HostBackend:
 
     def borders(self, e):
         from .active import borders_numpy, yuv_borders_numpy
-        return borders_numpy(e["f"], bgr=self.st.isBGR) if self.pixfmt is None else yuv_borders_numpy(e["f"], self.pixfmt)
+        return borders_numpy(e["f"], bgr=self.st.isBGR) if self.pixfmt is None else yuv_borders_numpy(self._frame(e), self.pixfmt)
 
     def whole_frame(self):
         """The active picture has ended: the whole frame from the next ``segment`` on."""
@@ -679,7 +737,7 @@ class HostBackend:
         if cut or (interior is not None and not interior):
             return {}
         from .retime import sparse_levels
-        fa, fb = (a["f"], b["f"]) if (self.pixfmt is None or self.st.deep) else (self._rgb(a), self._rgb(b))
+        fa, fb = (self._frame(a), self._frame(b)) if (self.pixfmt is None or self.st.deep) else (self._rgb(a), self._rgb(b))
         if interior is None:
             interior, made = range(1, self.n), self.seg(fa, fb)
         else:
@@ -689,12 +747,12 @@ class HostBackend:
             made = [yuv.encode_numpy(m, self.win_fmt) for m in made]
         if self.window is not None:
             from .active import compose_numpy, yuv_compose_numpy
-            bars = lambda k: (a if k <= self.n // 2 else b)["f"]
+            bars = lambda k: self._frame(a if k <= self.n // 2 else b)
             if self.pixfmt is None:
                 made = [compose_numpy(bars(k), self.window, win_u8=m) for k, m in zip(interior, made)]
             else:
                 made = [yuv_compose_numpy(bars(k), self.pixfmt, self.window, m) for k, m in zip(interior, made)]
-        return dict(zip(interior, made))
+        return dict(zip(interior, self._packed_out(made)))
 
     def blended(self, a, b, ops, need, cut, tail):
         """One record of ``shutter._plan`` (closes as ``("close", m)`` / ``("drop", m)``): the frames of its closes, in order --
@@ -718,7 +776,7 @@ class HostBackend:
                 frame = blend_numpy(frames, weights, self.light)
                 if self.pixfmt is not None:
                     from . import yuv
-                    frame = yuv.encode_numpy(frame, self.st.out_fmt)
+                    frame = self._packed_out([yuv.encode_numpy(frame, self.st.out_fmt)])[0]
                 out.append(frame)
             else:                                    # a reset, or an output the loop serves itself
                 self.gathered.pop(op[1], None)
@@ -743,25 +801,27 @@ class DeviceBackend:
     converts both its frames.
 
     ``sparse`` (the retimed loop): ``out_slots`` output ring entries and the batch sizes any sparse schedule can bring.  ``window`` /
-    ``watch`` (the active picture): the windowed runner and the ``borders`` probe; ``whole_frame()`` replaces the runner."""
+    ``watch`` (the active picture): the windowed runner and the ``borders`` probe; ``whole_frame()`` replaces the runner.  ``packed`` (a
+    ``yuv.Packed``, ``pixfmt`` its planar format): the uploader unpacks behind the copy and the runner packs in front of the output
+    ring (``st.packed``); everything between is the planar stream's."""
     lookahead = True
 
     def __init__(self, model, ops, dev, st: Stream, n, crop, divisor, tta, max_batch, pool, pixfmt=None, scene=False, dedup=False,
-                 sparse=False, out_slots=None, blend=None, window=None, watch=False, caller: str = "interpolate_video_nx"):
+                 sparse=False, out_slots=None, blend=None, window=None, watch=False, caller: str = "interpolate_video_nx", packed=None):
         self.n, self.levels, self.started = n, n.bit_length() - 1, False
         batch_sizes = range(1, min(max(1, min(int(max_batch), 16)), max(1, n // 2)) + 1) if sparse else None
         self._runner = lambda window: _SegmentRunner(model, ops, dev, st.H, st.W, n, crop, st.isBGR, divisor, tta, max_batch,
                                                      pool and hasattr(model, "forward_pooled"), out_fmt=st.out_fmt,
                                                      deep_fmt=pixfmt if st.deep else None, out_slots=out_slots, batch_sizes=batch_sizes,
                                                      blend=blend, window=window,
-                                                     border_fmt=pixfmt if window is not None else None)
+                                                     border_fmt=pixfmt if window is not None else None, pack=st.packed)
         self.pixfmt, self.ops, self.dev, self.hw = pixfmt, ops, dev, (st.H, st.W)
         self.runner = self._runner(window)
         self.watching = window is not None and watch
         sig = (ops, st.window, bool(st.isBGR))
         self.up = _Uploader(dev, st.H, st.W, depth=4 if dedup else 3, signature=sig if scene else None,
                             pixfmt=None if pixfmt is None else (ops, pixfmt), deep=st.deep, difference=sig if dedup else None,
-                            borders=(ops, bool(st.isBGR)) if self.watching else None, caller=caller)
+                            borders=(ops, bool(st.isBGR)) if self.watching else None, caller=caller, packed=packed)
 
     def admit(self, e):
         e["slot"] = self.up.upload(e["f"])

@@ -33,7 +33,13 @@ origin is a multiple of the subsampling step per axis.  ``Y4MReader(..., accept=
 and C444p10 (C422* as left-sited: Y4M's 4:2:2 is co-sited), ``Y4MWriter`` writes them, ``surface_of`` knows yuv422p, yuv444p,
 yuv422p10le and yuv444p10le, and every loop takes such a format or planar surface as ``pixfmt``.
 
-``Format``, ``Surface`` and ``as_surface`` are defined in the leaf module ``pixfmt.py`` (hip_ops.py validates against them) and
+``Packed(fmt, layout, pitch)`` (``atmvfi_yuv_unpack`` / ``atmvfi_yuv_pack``, csrc/yuv_packed.hip): packed 4:2:2 as capture cards deliver
+it -- UYVY, YUY2, Y210 and v210.  ``unpack_numpy`` / ``pack_numpy`` move the sample values between such a frame and the planar 4:2:2
+frame of ``packed.planar``, with no arithmetic; bytes and component slots that hold no sample are never interpreted and are written
+as zero.  ``interpolate_video_nx``, ``interpolate_video_retimed`` and ``interpolate_raw`` take a ``Packed`` as ``pixfmt``: inside, the
+stream is the planar one; ``surface_of`` knows uyvy422, yuyv422, y210le and v210.
+
+``Format``, ``Surface``, ``Packed`` and ``as_surface`` are defined in the leaf module ``pixfmt.py`` (hip_ops.py validates against them) and
 re-exported here; ``interpolate_y4m`` and ``interpolate_raw`` are front ends of one stream driver."""
 from __future__ import annotations
 
@@ -44,8 +50,8 @@ from typing import Iterator, Optional
 
 import numpy as np
 
-from .pixfmt import (CHROMAS, MATRICES, SITINGS, SUBSAMPLINGS, Format, Surface, _layout_name, _only_420, _origin_error,  # noqa: F401
-                     _tight_surface, as_surface)
+from .pixfmt import (CHROMAS, MATRICES, PACKED_LAYOUTS, SITINGS, SUBSAMPLINGS, Format, Packed, Surface, _layout_name,  # noqa: F401
+                     _only_420, _origin_error, _tight_surface, as_surface)
 
 KR_KB = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}
 SHIFT = 14
@@ -95,14 +101,68 @@ def planes(buf, fmt):
 def out_format(pixfmt, deep: bool):
     """What the loops produce for input of ``pixfmt``: the format itself with the depth kept, its 8-bit form otherwise; a ``Surface``
     without its padding (P010 in: P010 out with ``deep``, NV12 out without)."""
-    if isinstance(pixfmt, Surface):
+    if isinstance(pixfmt, (Surface, Packed)):
         return pixfmt.tight() if deep else pixfmt.as_8bit()
     return pixfmt if deep else pixfmt.as_8bit()
 
 
 def passes_through(pixfmt) -> bool:
-    """An uncropped original of ``pixfmt`` leaves the loops as the caller's own array: every ``Format``, a ``Surface`` without padding."""
-    return not isinstance(pixfmt, Surface) or pixfmt.is_tight
+    """An uncropped original of ``pixfmt`` leaves the loops as the caller's own array: every ``Format``, a ``Surface`` without padding,
+    a ``Packed`` at its default pitch."""
+    return not isinstance(pixfmt, (Surface, Packed)) or pixfmt.is_tight
+
+
+# ------------------------------------------------------------------------------------------------ packed 4:2:2
+_PAIR_SLOTS = {"uyvy": (1, 0, 3, 2), "yuy2": (0, 1, 2, 3), "y210": (0, 1, 2, 3)}        # (Y0, U, Y1, V) among a pair's four samples
+# v210's twelve component slots of a group, three per word from bit 0 up: (Cb0, Y0, Cr0) (Y1, Cb1, Y2) (Cr1, Y3, Cb2) (Y4, Cr2, Y5)
+_V210_Y, _V210_CB, _V210_CR = (1, 3, 5, 7, 9, 11), (0, 4, 8), (2, 6, 10)
+
+
+def unpack_numpy(buf, packed: Packed) -> np.ndarray:
+    """One frame of ``packed`` -> the planar 4:2:2 frame of ``packed.planar`` (1-D, uint8 or uint16): the sample values, moved (y210:
+    ``s >> 6``; v210: the ten bits of a slot).  Row padding, v210's slots beyond the width and bits 30-31 and y210's low six bits are
+    not interpreted.  The bits of ``atmvfi_yuv_unpack``."""
+    a = packed.check(buf, "yuv.unpack_numpy")
+    H, W = packed.height, packed.width
+    rows = a.view(np.uint8).reshape(H, packed.pitch)[:, :packed.row_bytes]
+    if packed.layout == "v210":
+        g = (W + 5) // 6
+        w = np.ascontiguousarray(rows).view("<u4").reshape(H, g, 4, 1).astype(np.uint32)
+        slots = ((w >> np.array([0, 10, 20], np.uint32)) & 1023).reshape(H, g, 12)
+        Y, U, V = (slots[:, :, list(k)].reshape(H, -1)[:, :n] for k, n in ((_V210_Y, W), (_V210_CB, W // 2), (_V210_CR, W // 2)))
+    else:
+        s = np.ascontiguousarray(rows).view("<u2" if packed.layout == "y210" else np.uint8).reshape(H, W // 2, 4)
+        if packed.layout == "y210":
+            s = s >> 6
+        y0, u, y1, v = _PAIR_SLOTS[packed.layout]
+        Y, U, V = s[:, :, [y0, y1]].reshape(H, W), s[:, :, u], s[:, :, v]
+    return np.concatenate([Y.reshape(-1), U.reshape(-1), V.reshape(-1)]).astype(packed.planar.dtype)
+
+
+def pack_numpy(planar_buf, packed: Packed) -> np.ndarray:
+    """A planar 4:2:2 frame of ``packed.planar`` -> one frame of ``packed.tight()`` (1-D): the sample values, moved (y210: ``v << 6``;
+    v210: ``v & 1023``); everything that holds no sample is zero.  ``unpack_numpy(pack_numpy(p, k), k) == p``.  The bits of
+    ``atmvfi_yuv_pack``."""
+    t = packed.tight()
+    H, W = t.height, t.width
+    Y, U, V = (p.astype(np.uint32) for p in t.planar.planes(t.planar.check(planar_buf, "yuv.pack_numpy")))
+    if t.layout == "v210":
+        g = (W + 5) // 6
+        slots = np.zeros((H, g, 12), np.uint32)
+        for plane, k in ((Y, _V210_Y), (U, _V210_CB), (V, _V210_CR)):
+            full = np.zeros((H, g * len(k)), np.uint32)
+            full[:, :plane.shape[1]] = plane & 1023
+            slots[:, :, list(k)] = full.reshape(H, g, len(k))
+        words = slots[:, :, 0::3] | slots[:, :, 1::3] << 10 | slots[:, :, 2::3] << 20
+        out = np.zeros((H, t.pitch), np.uint8)
+        out[:, :16 * g] = words.astype("<u4").view(np.uint8).reshape(H, 16 * g)
+        return out.reshape(-1)
+    s = np.empty((H, W // 2, 4), np.uint32)
+    y0, u, y1, v = _PAIR_SLOTS[t.layout]
+    s[:, :, y0], s[:, :, y1], s[:, :, u], s[:, :, v] = Y[:, 0::2], Y[:, 1::2], U, V
+    if t.layout == "y210":
+        s = (s << 6) & 0xffff
+    return s.astype(t.dtype).reshape(-1)
 
 
 def _samples(buf, fmt):
@@ -283,6 +343,8 @@ def crop(buf, fmt: Format, y0: int, x0: int, h: int, w: int) -> np.ndarray:
         raise err
     if y0 < 0 or x0 < 0 or h < 1 or w < 1 or y0 + h > fmt.height or x0 + w > fmt.width:
         raise ValueError(f"yuv.crop: window {h} x {w} at ({y0}, {x0}) outside the {fmt.height} x {fmt.width} frame")
+    if isinstance(fmt, Packed):             # unpack, the planar crop, pack: the tight frame of the window
+        return pack_numpy(crop(unpack_numpy(buf, fmt), fmt.planar, y0, x0, h, w), fmt.cropped(h, w))
     Y, U, V = fmt.planes(buf)
     (sy, sx), (ch, cw) = fmt.steps, fmt.cropped(h, w).chroma_shape
     cy, cx = y0 // sy, x0 // sx
@@ -537,7 +599,8 @@ class RawReader:
                 data += more
             if len(data) != n:
                 raise ValueError(f"RawReader: truncated frame ({len(data)} of {n} bytes)")
-            yield np.frombuffer(data, dtype="<u2" if self.surface.depth == 10 else np.uint8).astype(self.surface.dtype, copy=True)
+            # (by the sample type: a v210 frame is a 10-bit BYTE stream)
+            yield np.frombuffer(data, dtype="<u2" if np.dtype(self.surface.dtype).itemsize == 2 else np.uint8).astype(self.surface.dtype, copy=True)
 
     def skip(self, count: int) -> int:
         """Pass over the next ``count`` frames without delivering them (a seek per frame when seekable, read and dropped otherwise).
@@ -591,7 +654,7 @@ class RawWriter:
 
     def write(self, frame):
         a = self.surface.check(frame, "RawWriter.write")
-        self.f.write(a.astype("<u2", copy=False).tobytes() if self.surface.depth == 10 else a.tobytes())
+        self.f.write(a.astype("<u2", copy=False).tobytes() if a.dtype.itemsize == 2 else a.tobytes())
         self.frames += 1
 
     def close(self):
@@ -615,6 +678,8 @@ def to_8bit(frame, fmt) -> np.ndarray:
     (``encode_numpy(decode_numpy(frame))``: the 8-bit picture the loops saw)."""
     if fmt.depth == 8:
         return frame
+    if isinstance(fmt, Packed):             # (v210 -> uyvy, y210 -> yuy2)
+        return pack_numpy(to_8bit(unpack_numpy(frame, fmt), fmt.planar), fmt.as_8bit())
     return encode_numpy(decode_numpy(frame, fmt), fmt.as_8bit())
 
 
@@ -658,14 +723,20 @@ def _interpolate_stream(who, open_reader, open_writer, model, kw, *, factor, sce
             if deep:
                 kw["keep_depth"] = True
             if interpolator is None:
-                nx_only = tta or factor != 2 or any(k in kw for k in ("crop", "time_interval", "max_batch", "pool", "active"))
+                nx_only = tta or factor != 2 or any(k in kw for k in ("crop", "time_interval", "max_batch", "pool", "active")) \
+                    or isinstance(pixfmt, Packed)        # (the 2x loop does not take packed 4:2:2: factor=2 of the N-x loop does)
                 if not nx_only and _hip_ops_of(model)[0] is not None:
                     interpolator = interpolate_video_2x
                 else:
                     interpolator = lambda frames, model, **k: interpolate_video_nx(frames, model, factor=factor, tta=tta, **k)
             frames = interpolator(counted(), model, pixfmt=pixfmt, scene=scene, **kw)
+        if isinstance(pixfmt, Packed) and pixfmt.depth == 10 and not deep:
+            # (an original is a frame of the 10-bit layout: y210 by its dtype, v210 by its size -- a v210 row is longer than a uyvy one)
+            is_original = lambda f: f.dtype == src_out.dtype and f.size == src_out.frame_samples
+        else:
+            is_original = lambda f: f.dtype == np.uint16 and not deep
         for f in frames:
-            wr.write(to_8bit(f, src_out) if (f.dtype == np.uint16 and not deep) else f)
+            wr.write(to_8bit(f, src_out) if is_original(f) else f)
     finally:
         rd.close()
         if wr is not None:
@@ -712,17 +783,23 @@ PIX_FMTS = {"nv12": ("uv", 8, False), "nv21": ("vu", 8, False), "p010le": ("uv",
             "yuv420p10le": ("planar", 10, False)}
 # the planar 4:2:2 / 4:4:4 names -> (depth, subsampling)
 PIX_FMTS_SUB = {"yuv422p": (8, "422"), "yuv444p": (8, "444"), "yuv422p10le": (10, "422"), "yuv444p10le": (10, "444")}
+# the packed 4:2:2 names -> (layout, depth).  (v210 is a codec to ffmpeg, ``-c:v v210 -f rawvideo``, not a ``-pix_fmt``)
+PIX_FMTS_PACKED = {"uyvy422": ("uyvy", 8), "yuyv422": ("yuy2", 8), "y210le": ("y210", 10), "v210": ("v210", 10)}
 
 
 def surface_of(pix_fmt: str, h: int, w: int, pitch=None, **format_kw) -> Surface:
     """ffmpeg's ``-pix_fmt`` name (nv12, nv21, p010le, yuv420p, yuv420p10le, yuv422p, yuv444p, yuv422p10le, yuv444p10le) -> the
-    ``Surface``; ``pitch`` (bytes): the luma rows' and the interleaved chroma rows', planar chroma rows half of it (4:4:4: all of it)."""
+    ``Surface``; ``pitch`` (bytes): the luma rows' and the interleaved chroma rows', planar chroma rows half of it (4:4:4: all of it).
+    uyvy422, yuyv422, y210le and v210 -> the ``Packed`` (``pitch``: its rows')."""
+    if pix_fmt in PIX_FMTS_PACKED:
+        layout, depth = PIX_FMTS_PACKED[pix_fmt]
+        return Packed(Format(h, w, depth=depth, subsampling="422", **format_kw), layout, pitch)
     if pix_fmt in PIX_FMTS_SUB:            # planar: 4:2:2 chroma rows have half the pitch, 4:4:4 rows all of it
         depth, sub = PIX_FMTS_SUB[pix_fmt]
         cp = None if pitch is None else (int(pitch) if sub == "444" else int(pitch) // 2)
         return Surface(Format(h, w, depth=depth, subsampling=sub, **format_kw), "planar", False, pitch, cp)
     if pix_fmt not in PIX_FMTS:
-        raise ValueError(f"yuv.surface_of: unknown pixel format {pix_fmt!r} ({', '.join(list(PIX_FMTS) + list(PIX_FMTS_SUB))})")
+        raise ValueError(f"yuv.surface_of: unknown pixel format {pix_fmt!r} ({', '.join(list(PIX_FMTS) + list(PIX_FMTS_SUB) + list(PIX_FMTS_PACKED))})")
     chroma, depth, msb = PIX_FMTS[pix_fmt]
     cp = None if pitch is None else (int(pitch) // 2 if chroma == "planar" else int(pitch))
     return Surface(Format(h, w, depth=depth, **format_kw), chroma, msb, pitch, cp)
@@ -734,7 +811,7 @@ def interpolate_raw(src, dst, model, surface, fps, factor: int = 2, scene=None, 
     frames of ``surface.tight().cropped(h, w)`` in ``dst`` (the 8-bit counterpart for 10-bit input without ``keep_depth``, originals
     converted on the host), at ``fps * factor`` or at ``fps_out``.  Every keyword is ``interpolate_y4m``'s (there is no ``matrix``: the
     surface's format names it); the same dict is returned."""
-    surface = as_surface(surface)
+    surface = surface if isinstance(surface, Packed) else as_surface(surface)
     return _interpolate_stream("interpolate_raw", lambda: RawReader(src, surface, fps), lambda rd, out, rate: RawWriter(dst, out), model, kw,
                                factor=factor, scene=scene, tta=tta, interpolator=interpolator, keep_depth=keep_depth, fps_out=fps_out,
                                levels=levels, dedup=dedup, shutter=shutter)

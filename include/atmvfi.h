@@ -738,6 +738,37 @@ int atmvfi_yuv_sub_decode(const void* yuv, int H, int W, int depth, int matrix, 
 int atmvfi_yuv_sub_encode(const void* src_u8, int bgr, const float* src, int Hp, int Wp, int pad_top, int pad_left, int H, int W,
                           int depth, int matrix, int full_range, int siting, int subsampling, int chroma, int msb, void* yuv, void* stream);
 
+/* Packed 4:2:2 capture frames (yuv_packed.hip; ABI 0.23; atm-vfi_amd/pixfmt.py: Packed; host twins yuv.unpack_numpy / pack_numpy;
+ * per-sample model tests/cpu_yuv_packed.py).  Nothing of the reference.  Two sample-exact moves -- shifts and masks only -- between a
+ * packed frame and `planar`, the tight planar 4:2:2 frame of the layout's depth: Y [H,W], U [H,W/2], V [H,W/2] back to back, uint8 or
+ * little-endian uint16 with the value in the low bits: what atmvfi_yuv_sub_decode / _encode (subsampling 1) read and write.
+ *   layout  depth  packed samples  memory order per pixel pair                                      default pitch (bytes)
+ *   0 uyvy    8    uint8           U0 Y0 V0 Y1                                                      2 W
+ *   1 yuy2    8    uint8           Y0 U0 Y1 V0                                                      2 W
+ *   2 y210   10    uint16 (LE)     Y0 U0 Y1 V0, each sample value << 6 (read s >> 6, written v << 6) 4 W
+ *   3 v210   10    bytes           groups of four LE 32-bit words for 6 pixels, see below           ((W + 47) / 48) * 128
+ *   A v210 word holds three components in bits 0-9, 10-19 and 20-29; bits 30-31 are zero:
+ *     w0 = (Cb0, Y0, Cr0)   w1 = (Y1, Cb1, Y2)   w2 = (Cr1, Y3, Cb2)   w3 = (Y4, Cr2, Y5);   Cb_k / Cr_k belong to pixels 2k and 2k + 1.
+ *   W is even (every layout carries chroma per pixel pair).  pitch: the packed rows' stride in bytes, at least the row's own bytes
+ *   (2 W, 2 W, 4 W, ceil(W / 6) * 16) and a multiple of 4 (v210: 16); 0: the default.
+ * Padding rule.  Bytes and component slots of a packed frame that hold no sample -- a row's bytes beyond its samples up to the pitch,
+ *   v210's component slots beyond W in the last group, v210's bits 30-31, y210's low six bits -- are NEVER INTERPRETED by unpack (no
+ *   byte beyond a row's own bytes is read at all) and WRITTEN AS ZERO by pack, which writes every byte of the default-pitch frame
+ *   (pitch * H) itself and never reads `packed`.  Planar samples are values of the depth (pack drops higher bits: v & 1023 for v210,
+ *   (v << 6) mod 2^16 for y210).
+ * atmvfi_yuv_unpack: packed (at `pitch`) -> planar, every planar sample written.  atmvfi_yuv_pack: planar -> packed at the DEFAULT pitch.
+ * Refused on the host before any launch (ATMVFI_EINVAL): null pointers; H < 1, W < 2 or W odd; an unknown layout; a pitch that is
+ *   negative, short or no multiple of 4 (v210: 16); a base pointer that is not sample-aligned (packed v210: 4-byte aligned); overlapping
+ *   packed and planar ranges; a work-item count that does not fit an int.
+ * Any other geometry and alignment is accepted.  Aligned path (both pointers 16-byte aligned, the pitch a multiple of 16; layouts 0-2:
+ *   W a multiple of 16 / the sample size; v210: W a multiple of 8): 16-byte accesses of the packed row, 16-byte accesses of the luma
+ *   row and 8-byte accesses of the chroma rows; a v210 lane owns four whole groups (64 packed bytes, 48 + 24 + 24 planar bytes), the
+ *   groups behind a row's last whole four -- the partial last group among them -- and pack's zero groups of the padding go one per
+ *   lane through dword and sample accesses, as every group does on the general path.  Both paths give the same bits.  One launch,
+ *   grid-stride, every output byte written by exactly one lane: vector stores only, no atomics, nothing pre-zeroed. */
+int atmvfi_yuv_unpack(const void* packed, int H, int W, int layout, int64_t pitch /*0: default*/, void* planar, void* stream);
+int atmvfi_yuv_pack(const void* planar, int H, int W, int layout, void* packed /*default pitch*/, void* stream);
+
 /* mean |a - b| per sample: global_alignmentness (network_base.py:560-561).  Two passes with a fixed summation order -- the result is
  * run-to-run bit-identical (the ensemble's pick compares these means) -- through `workspace`: at least
  * atmvfi_l1_mean_workspace_floats(B, per_sample) floats of scratch, the caller's. */

@@ -2,7 +2,10 @@
 """Headerless video in, headerless video out at ``factor`` times the frame rate (``atm-vfi_amd.yuv.interpolate_raw``): the frames of an
 ``ffmpeg -f rawvideo -pix_fmt nv12|nv21|p010le|yuv420p|yuv420p10le|yuv422p|yuv422p10le|yuv444p|yuv444p10le`` pipe travel as they are and are converted on the GPU; nothing is
 repacked on the host.  The output has the same pixel format without row padding; 10-bit input is written back as its 8-bit
-counterpart (p010le -> nv12), or with ``--keep-depth`` at 10 bits.  ``-`` reads standard input / writes standard output
+counterpart (p010le -> nv12), or with ``--keep-depth`` at 10 bits.  Packed 4:2:2 capture frames travel the same way: ``--pix-fmt
+uyvy422|yuyv422|y210le|v210`` (unpacked and packed on the GPU; without ``--keep-depth`` y210le is written as yuyv422 and v210 as
+uyvy422).  ffmpeg writes v210 as a codec, not as a ``-pix_fmt``: ``ffmpeg -i in.mov -c:v v210 -f rawvideo -``; its rows are padded to
+128 bytes per 48 pixels, which is this tool's default pitch for v210.  ``-`` reads standard input / writes standard output
 (``ffmpeg -i in.mp4 -f rawvideo -pix_fmt nv12 - | interp_raw.py - out.nv12 --pix-fmt nv12 --size 1920x1080 --fps 30000/1001 --ckpt ...``).
 
     python tools/interp_raw.py IN OUT --pix-fmt FMT --size WxH --fps R [--pitch N] [--matrix auto|bt601|bt709] [--siting centre|left]
@@ -10,7 +13,7 @@ counterpart (p010le -> nv12), or with ``--keep-depth`` at 10 bits.  ``-`` reads 
                               [--keep-depth] [--active] [--fps-out R [--levels L] [--dedup] [--shutter ANGLE [--light code|linear]]]
 
 ``--pitch N``: the input's luma row stride in bytes (a decoder's surface dump; interleaved chroma rows share it, planar ones have
-half, 4:4:4 ones all of it).  Everything from ``--factor`` on is ``interp_y4m.py``'s."""
+half, 4:4:4 ones all of it); of a packed 4:2:2 format the stride of its rows (a multiple of 4, v210: of 16).  Everything from ``--factor`` on is ``interp_y4m.py``'s."""
 import argparse
 import importlib
 import os
@@ -26,7 +29,8 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("src")
     ap.add_argument("dst")
-    ap.add_argument("--pix-fmt", required=True, choices=("nv12", "nv21", "p010le", "yuv420p", "yuv420p10le", "yuv422p", "yuv444p", "yuv422p10le", "yuv444p10le"))
+    ap.add_argument("--pix-fmt", required=True, choices=("nv12", "nv21", "p010le", "yuv420p", "yuv420p10le", "yuv422p", "yuv444p", "yuv422p10le", "yuv444p10le",
+                                                           "uyvy422", "yuyv422", "y210le", "v210"))
     ap.add_argument("--size", required=True, metavar="WxH")
     ap.add_argument("--fps", required=True, metavar="R", help="the input's frame rate (e.g. 25 or 30000/1001)")
     ap.add_argument("--pitch", type=int, default=None, metavar="N", help="luma row stride of the input in bytes (default: tight)")
