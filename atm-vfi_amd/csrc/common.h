@@ -178,6 +178,11 @@ __device__ __forceinline__ void dma_epilogue_consts(const float* bias, const flo
 }
 
 typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
+// Registers that only some instances of a kernel have (the lo' fragments and the cross-term accumulator of the three-term product):
+// RegsIf<true, T[N]> IS T[N]; RegsIf<false, ...> is an empty object that nothing may index (every use sits under `if constexpr`).
+struct NoRegs {};
+template <bool ON, typename A>
+using RegsIf = std::conditional_t<ON, A, NoRegs>;
 // ---- fragment reads under manual wait counts (conv3x3_f16x3_row.hip explains why; also gemm_split.hip) ----
 template <int I, int N, typename F>
 __device__ __forceinline__ void static_for(F&& f) {

@@ -138,7 +138,12 @@ __device__ __forceinline__ void dma_planes_consts(const float* bias, const float
                                      (__attribute__((address_space(3))) void*)(cst + piece * 64), 4, 0, 0);
 }
 
-template <int WN>
+// X3: the three-term product (the default, "f16x3").  X3 == false ("f16", atmvfi_conv3x3_planes4 with terms = 1): a product is
+// hi(x) * hi(w) alone -- the lo' fragments are not read, the four cross-term MFMAs per (i, j) are not issued and `cor` does not exist; the
+// DMA of both planes, the ring, every counted wait and both barriers of a k-step are the same source (the ordering rules above rest on
+// which barrier separates a wait from a read, not on how long a phase lasts; the reads that fall away had no rule of their own).  The fused
+// read-out's W2 product stays three-term in both.
+template <int WN, bool X3>
 __global__ __launch_bounds__(512, 1) void conv3x3_planes_kernel(const Conv3PDev a) {
     fp16_saturate_on();
     constexpr int BN = 16 * WN;
@@ -336,7 +341,8 @@ __global__ __launch_bounds__(512, 1) void conv3x3_planes_kernel(const Conv3PDev 
         hbuf = HALO_BYTES - hbuf;
     };
 
-    f32x4 acc[2][WN], cor[2][WN];
+    f32x4 acc[2][WN];
+    RegsIf<X3, f32x4[2][WN]> cor;
 
     // tail k-steps: lane group g reads slot 0 of the halo pixel of tap 4t + g (taps 9..11 meet zero weights: tap 8 again)
     int dtail = 0;
@@ -360,7 +366,9 @@ __global__ __launch_bounds__(512, 1) void conv3x3_planes_kernel(const Conv3PDev 
     if (grp == 1) __builtin_amdgcn_s_barrier();          // the second group runs one phase behind
     TSTAMP(0)
 
-    f16x8 xh[2], xl[2], wh[WN], wl[WN];
+    f16x8 xh[2], wh[WN];
+    RegsIf<X3, f16x8[2]> xl;
+    RegsIf<X3, f16x8[WN]> wl;
     const unsigned wfrag = ring0 + (unsigned)(r * 64 + ((g ^ swz64(r)) << 4));       // swz64(16 j + r) == swz64(r)
     const int prow = 2 * wave * HW_ + r;                                                // halo pixel of (row 2 wave, column r), tap (0,0)
     // Activation-fragment addresses without per-read arithmetic: the fragment of tap offset C sits at pixel p = prow + C, slot
@@ -384,23 +392,23 @@ __global__ __launch_bounds__(512, 1) void conv3x3_planes_kernel(const Conv3PDev 
         } else if constexpr (!TAIL) {
             constexpr int C0 = (T / 3) * HW_ + T % 3, C1 = C0 + HW_;       // tap offsets of the wave's two pixel rows
             lds_read16<64 * C0>(xh[0], xa[C0 & 7]);
-            lds_read16<64 * C0 + HALO_LO>(xl[0], xa[C0 & 7]);
+            if constexpr (X3) lds_read16<64 * C0 + HALO_LO>(xl[0], xa[C0 & 7]);
             lds_read16<64 * C1>(xh[1], xa[C1 & 7]);
-            lds_read16<64 * C1 + HALO_LO>(xl[1], xa[C1 & 7]);
+            if constexpr (X3) lds_read16<64 * C1 + HALO_LO>(xl[1], xa[C1 & 7]);
         } else {
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 const int p = prow + i * HW_ + ((dtail >> (TAIL ? 8 * T : 0)) & 0xff);
                 const unsigned addr = halo0 + (unsigned)hcur + (unsigned)(p * 64 + (swz64(p) << 4));
                 lds_read16<0>(xh[i], addr);
-                lds_read16<HALO_LO>(xl[i], addr);
+                if constexpr (X3) lds_read16<HALO_LO>(xl[i], addr);
             }
         }
         const unsigned wa = wfrag + (unsigned)rd_off;
         if (!PDBG(16)) static_for<0, WN>([&](auto jc) {
             constexpr int j = decltype(jc)::value;
             lds_read16<j * 1024>(wh[j], wa);
-            lds_read16<j * 1024 + BN * 64>(wl[j], wa);
+            if constexpr (X3) lds_read16<j * 1024 + BN * 64>(wl[j], wa);
         });
         rd_off = rd_off + WSLOT == NB * WSLOT ? 0 : rd_off + WSLOT;
         PSTAMP(1)
@@ -437,10 +445,17 @@ __global__ __launch_bounds__(512, 1) void conv3x3_planes_kernel(const Conv3PDev 
             if (!PDBG(4)) wait_vm<(!TAIL && T == 8) ? (LA - 1) * SW : (LA - 1) * SW + halos>();
         }
         PSTAMP(3)
-        asm volatile("s_waitcnt lgkmcnt(0)"
-                     : "+v"(xh[0]), "+v"(xh[1]), "+v"(xl[0]), "+v"(xl[1]));
+        if constexpr (X3) {
+            asm volatile("s_waitcnt lgkmcnt(0)"
+                         : "+v"(xh[0]), "+v"(xh[1]), "+v"(xl[0]), "+v"(xl[1]));
 #pragma unroll
-        for (int j = 0; j < WN; ++j) asm volatile("" : "+v"(wh[j]), "+v"(wl[j]));
+            for (int j = 0; j < WN; ++j) asm volatile("" : "+v"(wh[j]), "+v"(wl[j]));
+        } else {
+            asm volatile("s_waitcnt lgkmcnt(0)"
+                         : "+v"(xh[0]), "+v"(xh[1]));
+#pragma unroll
+            for (int j = 0; j < WN; ++j) asm volatile("" : "+v"(wh[j]));
+        }
         __builtin_amdgcn_sched_barrier(0);
         PSTAMP(4)
         __builtin_amdgcn_s_barrier();
@@ -450,12 +465,16 @@ __global__ __launch_bounds__(512, 1) void conv3x3_planes_kernel(const Conv3PDev 
         if (!PDBG(8)) __builtin_amdgcn_s_setprio(1);
         static_for<0, WN>([&](auto jc) {
             constexpr int j = decltype(jc)::value;
-            cor[0][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[j], xh[0], cor[0][j], 0, 0, 0);
-            cor[1][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[j], xh[1], cor[1][j], 0, 0, 0);
+            if constexpr (X3) {
+                cor[0][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[j], xh[0], cor[0][j], 0, 0, 0);
+                cor[1][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[j], xh[1], cor[1][j], 0, 0, 0);
+            }
             acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[j], xh[0], acc[0][j], 0, 0, 0);
             acc[1][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[j], xh[1], acc[1][j], 0, 0, 0);
-            cor[0][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[j], xl[0], cor[0][j], 0, 0, 0);
-            cor[1][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[j], xl[1], cor[1][j], 0, 0, 0);
+            if constexpr (X3) {
+                cor[0][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[j], xl[0], cor[0][j], 0, 0, 0);
+                cor[1][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[j], xl[1], cor[1][j], 0, 0, 0);
+            }
         });
         __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_sched_barrier(0);
@@ -496,10 +515,14 @@ __global__ __launch_bounds__(512, 1) void conv3x3_planes_kernel(const Conv3PDev 
 #pragma unroll
             for (int j = 0; j < WN; ++j) {
                 acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                cor[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
                 // pinned: hipcc otherwise folds the zeros into the first MFMAs' C operand and may use the (then dead) accumulator
                 // registers as temporaries of the first read phase, guarded by s_waitcnt vmcnt(0)
-                asm volatile("" : "+v"(acc[i][j]), "+v"(cor[i][j]));
+                if constexpr (X3) {
+                    cor[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+                    asm volatile("" : "+v"(acc[i][j]), "+v"(cor[i][j]));
+                } else {
+                    asm volatile("" : "+v"(acc[i][j]));
+                }
             }
         if (nfull > 0) {
             static_for<0, 9>([&](auto tc) { kstep(tc, std::false_type{}, std::true_type{}); });
@@ -594,7 +617,10 @@ __global__ __launch_bounds__(512, 1) void conv3x3_planes_kernel(const Conv3PDev 
             const f32x4 bv = *reinterpret_cast<const f32x4*>(cst + cl);
             const f32x4 pv = *reinterpret_cast<const f32x4*>(cst + BN + cl);
 #pragma unroll
-            for (int i = 0; i < 2; ++i) vv[i][j] = prelu4(mode, acc[i][j] + cor[i][j] * LO_UNSCALE + bv, pv, a.prelu != nullptr);
+            for (int i = 0; i < 2; ++i) {
+                if constexpr (X3) vv[i][j] = prelu4(mode, acc[i][j] + cor[i][j] * LO_UNSCALE + bv, pv, a.prelu != nullptr);
+                else vv[i][j] = prelu4(mode, acc[i][j] + bv, pv, a.prelu != nullptr);
+            }
         }
     };
     // (the 8-n-tile instance has no register to spare for copies of a stage -- it spills 32-37 -- and its layers have the longest K: it
@@ -758,13 +784,13 @@ __global__ __launch_bounds__(512, 1) void conv3x3_planes_kernel(const Conv3PDev 
 #endif
 }
 
-template <int WN>
+template <int WN, bool X3>
 int launch_planes(const Conv3PDev& d, int ntiles, hipStream_t s) {
     constexpr int BN = 16 * WN;
     const size_t lds = (size_t)2 * HALO_BYTES + (size_t)ring_slots(WN) * 2 * BN * 64 + 2 * planes_const_floats(BN) * sizeof(float);
     static_assert(2 * HALO_BYTES + ring_slots(WN) * 2 * BN * 64 + 2 * planes_const_floats(BN) * 4 <= 160 * 1024, "LDS budget");
-    auto kern = conv3x3_planes_kernel<WN>;
-    const hipError_t attr_err = atmvfi::allow_dynamic_lds<conv3x3_planes_kernel<WN>>(lds);
+    auto kern = conv3x3_planes_kernel<WN, X3>;
+    const hipError_t attr_err = atmvfi::allow_dynamic_lds<conv3x3_planes_kernel<WN, X3>>(lds);
     ATMVFI_REQUIRE(attr_err == hipSuccess, ATMVFI_ELAUNCH, "conv3x3_planes: hipFuncSetAttribute: %s", hipGetErrorString(attr_err));
     Conv3PDev ds = d;
     ds.nblocks = (ntiles + WN - 1) / WN;
@@ -926,24 +952,35 @@ static int conv3x3_planes_impl(const void* in_hi, const void* in_lo, int64_t in_
                                const void* w_lo, int Cout, float* out, int out_ld, const float* bias, const float* prelu, void* out_hi,
                                void* out_lo, int64_t plane_rows, int out_c0, const float* plane_prelu, void* out_hi2, void* out_lo2,
                                int64_t plane_rows2, int out_c02, int out_cmin, int wn, float* workspace, int64_t workspace_floats,
-                               const void* h2_w, float* h2_out, int64_t h2_plane, void* stream);
+                               const void* h2_w, float* h2_out, int64_t h2_plane, int terms, void* stream);
+
+extern "C" int atmvfi_conv3x3_planes4(const void* in_hi, const void* in_lo, int64_t in_rows, int N, int H, int W, int Cin, const void* w_hi,
+                                       const void* w_lo, int Cout, float* out, int out_ld, const float* bias, const float* prelu,
+                                       void* out_hi, void* out_lo, int64_t plane_rows, int out_c0, const float* plane_prelu, void* out_hi2,
+                                       void* out_lo2, int64_t plane_rows2, int out_c02, int out_cmin, int wn, float* workspace,
+                                       int64_t workspace_floats, int terms, void* stream) {
+    ATMVFI_REQUIRE(terms == 3 || terms == 1, ATMVFI_EINVAL,
+                   "conv3x3_planes: terms must be 3 (f16x3: hi*hi + hi*lo + lo*hi) or 1 (f16: hi*hi only), got %d", terms);
+    ATMVFI_REQUIRE(in_hi && in_lo && w_hi && w_lo && (out || out_hi), ATMVFI_EINVAL, "conv3x3_planes: null pointer");
+    return conv3x3_planes_impl(in_hi, in_lo, in_rows, N, H, W, Cin, w_hi, w_lo, Cout, out, out_ld, bias, prelu, out_hi, out_lo, plane_rows, out_c0,
+                               plane_prelu, out_hi2, out_lo2, plane_rows2, out_c02, out_cmin, wn, workspace, workspace_floats, nullptr, nullptr, 0,
+                               terms, stream);
+}
 
 extern "C" int atmvfi_conv3x3_planes3(const void* in_hi, const void* in_lo, int64_t in_rows, int N, int H, int W, int Cin, const void* w_hi,
                                        const void* w_lo, int Cout, float* out, int out_ld, const float* bias, const float* prelu,
                                        void* out_hi, void* out_lo, int64_t plane_rows, int out_c0, const float* plane_prelu, void* out_hi2,
                                        void* out_lo2, int64_t plane_rows2, int out_c02, int out_cmin, int wn, float* workspace,
                                        int64_t workspace_floats, void* stream) {
-    ATMVFI_REQUIRE(in_hi && in_lo && w_hi && w_lo && (out || out_hi), ATMVFI_EINVAL, "conv3x3_planes: null pointer");
-    return conv3x3_planes_impl(in_hi, in_lo, in_rows, N, H, W, Cin, w_hi, w_lo, Cout, out, out_ld, bias, prelu, out_hi, out_lo, plane_rows, out_c0,
-                               plane_prelu, out_hi2, out_lo2, plane_rows2, out_c02, out_cmin, wn, workspace, workspace_floats, nullptr, nullptr, 0,
-                               stream);
+    return atmvfi_conv3x3_planes4(in_hi, in_lo, in_rows, N, H, W, Cin, w_hi, w_lo, Cout, out, out_ld, bias, prelu, out_hi, out_lo, plane_rows,
+                                  out_c0, plane_prelu, out_hi2, out_lo2, plane_rows2, out_c02, out_cmin, wn, workspace, workspace_floats, 3, stream);
 }
 
 static int conv3x3_planes_impl(const void* in_hi, const void* in_lo, int64_t in_rows, int N, int H, int W, int Cin, const void* w_hi,
                                const void* w_lo, int Cout, float* out, int out_ld, const float* bias, const float* prelu, void* out_hi,
                                void* out_lo, int64_t plane_rows, int out_c0, const float* plane_prelu, void* out_hi2, void* out_lo2,
                                int64_t plane_rows2, int out_c02, int out_cmin, int wn, float* workspace, int64_t workspace_floats,
-                               const void* h2_w, float* h2_out, int64_t h2_plane, void* stream) {
+                               const void* h2_w, float* h2_out, int64_t h2_plane, int terms, void* stream) {
     ATMVFI_REQUIRE((out_hi2 == nullptr) == (out_lo2 == nullptr), ATMVFI_EINVAL, "conv3x3_planes: the second plane sink needs both planes");
     if (out_hi2)
         ATMVFI_REQUIRE(out_hi && plane_rows2 >= (int64_t)N * H * W && out_c02 >= 0 && out_c02 % 8 == 0 && atmvfi::aligned16(out_hi2) &&
@@ -999,15 +1036,29 @@ static int conv3x3_planes_impl(const void* in_hi, const void* in_lo, int64_t in_
     }
     hipStream_t s = (hipStream_t)stream;
     int rc;
-    switch (best) {
-        case 1: rc = launch_planes<1>(d, ntiles, s); break;
-        case 2: rc = launch_planes<2>(d, ntiles, s); break;
-        case 3: rc = launch_planes<3>(d, ntiles, s); break;
-        case 4: rc = launch_planes<4>(d, ntiles, s); break;
-        case 5: rc = launch_planes<5>(d, ntiles, s); break;
-        case 6: rc = launch_planes<6>(d, ntiles, s); break;
-        case 7: rc = launch_planes<7>(d, ntiles, s); break;
-        default: rc = launch_planes<8>(d, ntiles, s); break;
+    // (the tile width and the K split above do not look at `terms`: both modes of a shape take the same plan)
+    if (terms == 3) {
+        switch (best) {
+            case 1: rc = launch_planes<1, true>(d, ntiles, s); break;
+            case 2: rc = launch_planes<2, true>(d, ntiles, s); break;
+            case 3: rc = launch_planes<3, true>(d, ntiles, s); break;
+            case 4: rc = launch_planes<4, true>(d, ntiles, s); break;
+            case 5: rc = launch_planes<5, true>(d, ntiles, s); break;
+            case 6: rc = launch_planes<6, true>(d, ntiles, s); break;
+            case 7: rc = launch_planes<7, true>(d, ntiles, s); break;
+            default: rc = launch_planes<8, true>(d, ntiles, s); break;
+        }
+    } else {
+        switch (best) {
+            case 1: rc = launch_planes<1, false>(d, ntiles, s); break;
+            case 2: rc = launch_planes<2, false>(d, ntiles, s); break;
+            case 3: rc = launch_planes<3, false>(d, ntiles, s); break;
+            case 4: rc = launch_planes<4, false>(d, ntiles, s); break;
+            case 5: rc = launch_planes<5, false>(d, ntiles, s); break;
+            case 6: rc = launch_planes<6, false>(d, ntiles, s); break;
+            case 7: rc = launch_planes<7, false>(d, ntiles, s); break;
+            default: rc = launch_planes<8, false>(d, ntiles, s); break;
+        }
     }
     if (rc != ATMVFI_OK || plan.ksplit <= 1) return rc;
     const long long groups = rows * (((Cout + 7) & ~7) >> 2);
@@ -1018,15 +1069,24 @@ static int conv3x3_planes_impl(const void* in_hi, const void* in_lo, int64_t in_
     return atmvfi::check_launch("conv3x3_planes (split-K reduce)");
 }
 
-extern "C" int atmvfi_conv3x3_planes_readout(const void* in_hi, const void* in_lo, int64_t in_rows, int N, int H, int W, int Cin,
-                                              const void* w_hi, const void* w_lo, int Cout, const float* bias, const float* prelu,
-                                              const void* w2, float* contrib, int64_t contrib_plane, void* stream) {
+extern "C" int atmvfi_conv3x3_planes_readout2(const void* in_hi, const void* in_lo, int64_t in_rows, int N, int H, int W, int Cin,
+                                               const void* w_hi, const void* w_lo, int Cout, const float* bias, const float* prelu,
+                                               const void* w2, float* contrib, int64_t contrib_plane, int terms, void* stream) {
+    ATMVFI_REQUIRE(terms == 3 || terms == 1, ATMVFI_EINVAL,
+                   "conv3x3_planes_readout: terms must be 3 (f16x3) or 1 (f16: the main 3x3 product hi*hi only; the W2 product stays three-term), got %d",
+                   terms);
     ATMVFI_REQUIRE(in_hi && in_lo && w_hi && w_lo && w2 && contrib, ATMVFI_EINVAL, "conv3x3_planes_readout: null pointer");
     ATMVFI_REQUIRE(Cout == 32 || Cout == 64, ATMVFI_EINVAL, "conv3x3_planes_readout: Cout must be 32 or 64 (one column block of 2 or 4 n-tiles), got %d", Cout);
     ATMVFI_REQUIRE(contrib_plane >= (int64_t)N * H * W && atmvfi::aligned16(w2), ATMVFI_EINVAL,
                    "conv3x3_planes_readout: contrib_plane must cover N*H*W pixels and w2 must be 16-byte aligned");
     return conv3x3_planes_impl(in_hi, in_lo, in_rows, N, H, W, Cin, w_hi, w_lo, Cout, nullptr, 0, bias, prelu, nullptr, nullptr, 0, 0, nullptr,
-                               nullptr, nullptr, 0, 0, 0, Cout / 16, nullptr, 0, w2, contrib, contrib_plane, stream);
+                               nullptr, nullptr, 0, 0, 0, Cout / 16, nullptr, 0, w2, contrib, contrib_plane, terms, stream);
+}
+
+extern "C" int atmvfi_conv3x3_planes_readout(const void* in_hi, const void* in_lo, int64_t in_rows, int N, int H, int W, int Cin,
+                                              const void* w_hi, const void* w_lo, int Cout, const float* bias, const float* prelu,
+                                              const void* w2, float* contrib, int64_t contrib_plane, void* stream) {
+    return atmvfi_conv3x3_planes_readout2(in_hi, in_lo, in_rows, N, H, W, Cin, w_hi, w_lo, Cout, bias, prelu, w2, contrib, contrib_plane, 3, stream);
 }
 
 extern "C" int atmvfi_conv3x3_planes2(const void* in_hi, const void* in_lo, int64_t in_rows, int N, int H, int W, int Cin, const void* w_hi,

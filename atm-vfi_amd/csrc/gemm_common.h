@@ -67,6 +67,7 @@ struct GemmDev {
     int part_ld;
     int fit32;        // gemm_pp: rows x out_ld x 4 and rows x res_ld x 4 bytes fit 32 bits (unmapped, ungrouped fp32 rows: 32-bit store offsets)
     int pfit32;       // gemm_pp: a plane of the sink (plane rows x 64 bytes) fits 32 bits: 32-bit row offsets from per-lane chunk pointers
+    int terms;        // host side only (the launchers pick the kernel instance by it): 3 = f16x3, 1 = f16 (hi * hi alone; gemm_pp / gemm_duo)
 };
 
 

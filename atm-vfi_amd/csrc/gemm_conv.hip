@@ -254,8 +254,8 @@ extern "C" int atmvfi_gemm(const atmvfi_gemm_params* p, void* stream) {
     const bool sink = p->out_hi || p->out_lo;
     ATMVFI_REQUIRE((p->in || planes) && p->weight && (p->out || sink), ATMVFI_EINVAL, "gemm: null tensor pointer");
     if (sink) {
-        ATMVFI_REQUIRE(p->out_hi && p->out_lo && p->precision == ATMVFI_PREC_F16X3, ATMVFI_EINVAL,
-                       "gemm: the plane sink needs both planes and precision f16x3");
+        ATMVFI_REQUIRE(p->out_hi && p->out_lo && (p->precision == ATMVFI_PREC_F16X3 || p->precision == ATMVFI_PREC_F16), ATMVFI_EINVAL,
+                       "gemm: the plane sink needs both planes and precision f16x3 (or f16)");
         ATMVFI_REQUIRE(atmvfi::aligned16(p->out_hi) && atmvfi::aligned16(p->out_lo) && p->out_plane_c0 >= 0 && p->out_plane_c0 % 4 == 0 &&
                            p->out_plane_gc % 4 == 0, ATMVFI_EALIGN, "gemm: plane sink: 16-byte aligned planes, channel offsets multiples of 4");
         const long long orows = p->mode == ATMVFI_GEMM_DECONV ? (long long)p->N * p->Ho * p->Wo
@@ -265,8 +265,8 @@ extern "C" int atmvfi_gemm(const atmvfi_gemm_params* p, void* stream) {
         ATMVFI_REQUIRE(p->out_plane_rows > 0, ATMVFI_EINVAL, "gemm: plane sink needs out_plane_rows");
     }
     if (planes) {
-        ATMVFI_REQUIRE(p->in_hi && p->in_lo && p->precision == ATMVFI_PREC_F16X3 && !p->in_prelu,
-                       ATMVFI_EINVAL, "gemm: split-plane input needs both planes, precision f16x3 and no in_prelu");
+        ATMVFI_REQUIRE(p->in_hi && p->in_lo && (p->precision == ATMVFI_PREC_F16X3 || p->precision == ATMVFI_PREC_F16) && !p->in_prelu,
+                       ATMVFI_EINVAL, "gemm: split-plane input needs both planes, precision f16x3 (or f16) and no in_prelu");
         ATMVFI_REQUIRE(atmvfi::aligned16(p->in_hi) && atmvfi::aligned16(p->in_lo) && p->in_rpg == 0, ATMVFI_EALIGN,
                        "gemm: split planes need 16-byte aligned pointers and plain rows");
         const long long mrows = p->mode == ATMVFI_GEMM_LINEAR ? (long long)p->M : (long long)p->N * p->H * p->W;
@@ -280,6 +280,12 @@ extern "C" int atmvfi_gemm(const atmvfi_gemm_params* p, void* stream) {
                            "gemm: a second plane source needs CONV mode, both planes, in_ld2 > N*H*W and 0 < 32 * in_split_chunks < Cin");
         }
     }
+    ATMVFI_REQUIRE(p->precision >= ATMVFI_PREC_F32 && p->precision <= ATMVFI_PREC_F16, ATMVFI_EINVAL, "gemm: bad precision %d", p->precision);
+    // f16 (hi * hi alone) exists in the split-plane engines gemm_pp / gemm_duo only: refused here, before any launch
+    ATMVFI_REQUIRE(p->precision != ATMVFI_PREC_F16 || planes, ATMVFI_EINVAL,
+                   "gemm: precision f16 needs split-plane input (in_hi / in_lo): the fp32-input engines have no single-pass instance");
+    ATMVFI_REQUIRE(p->precision != ATMVFI_PREC_F16 || p->tile_wn != -1, ATMVFI_EINVAL,
+                   "gemm: precision f16 has no instance of the reference schedule (tile_wn = -1): use 0 (auto), -2, -3 or -4");
     ATMVFI_REQUIRE(p->mode >= 0 && p->mode <= 2, ATMVFI_EINVAL, "gemm: bad mode %d", p->mode);
     ATMVFI_REQUIRE(p->Cin > 0 && p->Cout > 0, ATMVFI_EINVAL, "gemm: bad channel counts");
     ATMVFI_REQUIRE(planes || (p->in_ld >= atmvfi::round_up(p->Cin, 4) && p->in_ld % 4 == 0), ATMVFI_EALIGN,
@@ -365,14 +371,15 @@ extern "C" int atmvfi_gemm(const atmvfi_gemm_params* p, void* stream) {
     d.vblocks = 0;
     d.mchunk = 0;
     d.stamp = nullptr;
+    d.terms = p->precision == ATMVFI_PREC_F16 ? 1 : 3;
     d.w_hi = (const _Float16*)p->weight_hi;
     d.w_lo = (const _Float16*)p->weight_lo;
     d.cin_pad32 = atmvfi::round_up(p->Cin, 32);
     d.cpt32 = d.cin_pad32 / 32;
     d.nchunks32 = taps * d.cpt32;
     d.ktot32 = taps * d.cin_pad32;
-    if (p->precision == ATMVFI_PREC_F16X3) {
-        ATMVFI_REQUIRE(p->weight_hi && p->weight_lo, ATMVFI_EINVAL, "gemm: precision f16x3 needs weight_hi/weight_lo");
+    if (p->precision == ATMVFI_PREC_F16X3 || p->precision == ATMVFI_PREC_F16) {
+        ATMVFI_REQUIRE(p->weight_hi && p->weight_lo, ATMVFI_EINVAL, "gemm: precision f16x3 / f16 needs weight_hi/weight_lo");
         ATMVFI_REQUIRE(atmvfi::aligned16(p->weight_hi) && atmvfi::aligned16(p->weight_lo), ATMVFI_EALIGN,
                        "gemm: split weights must be 16-byte aligned");
         if (planes) return atmvfi::launch_gemm_split(d, ngemm, (hipStream_t)stream);

@@ -27,7 +27,9 @@ extern "C" void atmvfi_debug_set_duo_stamp_buffer(void* p) { g_duo_stamp = (unsi
 #define DUO_SUB(k) do { } while (0)
 #endif
 
-template <bool CONVM, int BN>
+// X3: the three-term product (the default).  X3 == false (ATMVFI_PREC_F16): hi(x) * hi(w) alone -- no lo' fragment reads, a third of the
+// MFMAs, no `cor`; DMA of both planes, stages, counted waits and barriers are the same source.  A split-K range's raw sum is `acc`.
+template <bool CONVM, int BN, bool X3>
 __global__ __launch_bounds__(256, 2) void gemm_duo_kernel(const GemmDev a) {
     constexpr int STAGE = stage_bytes(BN), W_LO = W_HI + BN * 64;
     constexpr int MI = BN == 128 ? 4 : 2;           // 16-row MFMA tiles per wave along M
@@ -133,13 +135,14 @@ __global__ __launch_bounds__(256, 2) void gemm_duo_kernel(const GemmDev a) {
         }
     }
 
-    f32x4 acc[MI][4], cor[MI][4];
+    f32x4 acc[MI][4];
+    RegsIf<X3, f32x4[MI][4]> cor;
 #pragma unroll
     for (int i = 0; i < MI; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            cor[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            if constexpr (X3) cor[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
         }
 #ifdef ATMVFI_STAMP
     unsigned long long sub[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sub_t = 0, t_begin = 0;
@@ -148,7 +151,9 @@ __global__ __launch_bounds__(256, 2) void gemm_duo_kernel(const GemmDev a) {
     issue_stage(0);
     if (nk > 1) issue_stage(1);
     DUO_SUB(0);
-    f16x8 xh[MI], xl[MI], wh[4], wl[4];
+    f16x8 xh[MI], wh[4];
+    RegsIf<X3, f16x8[MI]> xl;
+    RegsIf<X3, f16x8[4]> wl;
     const unsigned xfrag = lds_offset(smem) + (unsigned)((WROWS * wm + r) * 64 + ((g ^ swz64(r)) << 4));
     const unsigned wfrag = lds_offset(smem) + (unsigned)(W_HI + (64 * wn + r) * 64 + ((g ^ swz64(r)) << 4));
     for (int u = 0; u < nk; ++u) {
@@ -161,17 +166,24 @@ __global__ __launch_bounds__(256, 2) void gemm_duo_kernel(const GemmDev a) {
         static_for<0, MI>([&](auto ic) {
             constexpr int i = decltype(ic)::value;
             lds_read16<i * 1024>(xh[i], xfrag + off);
-            lds_read16<i * 1024 + A_LO>(xl[i], xfrag + off);
+            if constexpr (X3) lds_read16<i * 1024 + A_LO>(xl[i], xfrag + off);
         });
         static_for<0, 4>([&](auto jc) {
             constexpr int j = decltype(jc)::value;
             lds_read16<j * 1024>(wh[j], wfrag + off);
-            lds_read16<j * 1024 + BN * 64>(wl[j], wfrag + off);
+            if constexpr (X3) lds_read16<j * 1024 + BN * 64>(wl[j], wfrag + off);
         });
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(xh[0]), "+v"(xh[1]), "+v"(xl[0]), "+v"(xl[1]));
-        if constexpr (MI == 4) asm volatile("" : "+v"(xh[2]), "+v"(xh[3]), "+v"(xl[2]), "+v"(xl[3]));
+        if constexpr (X3) {
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(xh[0]), "+v"(xh[1]), "+v"(xl[0]), "+v"(xl[1]));
+            if constexpr (MI == 4) asm volatile("" : "+v"(xh[2]), "+v"(xh[3]), "+v"(xl[2]), "+v"(xl[3]));
 #pragma unroll
-        for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(wh[j]), "+v"(wl[j]));
+            for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(wh[j]), "+v"(wl[j]));
+        } else {
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(xh[0]), "+v"(xh[1]));
+            if constexpr (MI == 4) asm volatile("" : "+v"(xh[2]), "+v"(xh[3]));
+#pragma unroll
+            for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(wh[j]));
+        }
         DUO_SUB(2);
         __builtin_amdgcn_s_barrier();                   // every wave has its fragments: the buffer may be refilled
         DUO_SUB(3);
@@ -182,13 +194,15 @@ __global__ __launch_bounds__(256, 2) void gemm_duo_kernel(const GemmDev a) {
         for (int i = 0; i < MI; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                cor[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[j], xh[i], cor[i][j], 0, 0, 0);
+                if constexpr (X3) cor[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[j], xh[i], cor[i][j], 0, 0, 0);
                 acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[j], xh[i], acc[i][j], 0, 0, 0);
             }
+        if constexpr (X3) {
 #pragma unroll
-        for (int i = 0; i < MI; ++i)
+            for (int i = 0; i < MI; ++i)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) cor[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[j], xl[i], cor[i][j], 0, 0, 0);
+                for (int j = 0; j < 4; ++j) cor[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[j], xl[i], cor[i][j], 0, 0, 0);
+        }
         __builtin_amdgcn_s_setprio(0);
         DUO_SUB(5);
     }
@@ -199,7 +213,7 @@ __global__ __launch_bounds__(256, 2) void gemm_duo_kernel(const GemmDev a) {
         for (int i = 0; i < MI; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                acc[i][j] = acc[i][j] + cor[i][j] * LO_UNSCALE;
+                if constexpr (X3) acc[i][j] = acc[i][j] + cor[i][j] * LO_UNSCALE;
                 asm volatile("" : "+v"(acc[i][j]));
             }
         {
@@ -289,10 +303,10 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce_kernel(const GemmDev a
 
 }  // namespace
 
-template <bool CONVM, int BN>
+template <bool CONVM, int BN, bool X3>
 static int launch_duo(const GemmDev& d, int ngemm, hipStream_t s) {
     const size_t lds = (size_t)2 * stage_bytes(BN) + cst_floats(BN) * sizeof(float);
-    const hipError_t attr_err = atmvfi::allow_dynamic_lds<gemm_duo_kernel<CONVM, BN>>(lds);
+    const hipError_t attr_err = atmvfi::allow_dynamic_lds<gemm_duo_kernel<CONVM, BN, X3>>(lds);
     ATMVFI_REQUIRE(attr_err == hipSuccess, ATMVFI_ELAUNCH, "gemm_duo: hipFuncSetAttribute: %s", hipGetErrorString(attr_err));
     GemmDev dd = d;
     const int prc = atmvfi::plane_gemm_prepare("gemm_duo", dd, ngemm, BM, BN);
@@ -301,7 +315,7 @@ static int launch_duo(const GemmDev& d, int ngemm, hipStream_t s) {
     dd.stamp = g_duo_stamp;
 #endif
     if (dd.ksplit > 1) {
-        hipLaunchKernelGGL((gemm_duo_kernel<CONVM, BN>), dim3((unsigned)dd.vblocks, (unsigned)dd.ksplit), dim3(256), lds, s, dd);
+        hipLaunchKernelGGL((gemm_duo_kernel<CONVM, BN, X3>), dim3((unsigned)dd.vblocks, (unsigned)dd.ksplit), dim3(256), lds, s, dd);
         const int rc = atmvfi::check_launch("gemm_duo (split-K)");
         if (rc != ATMVFI_OK) return rc;
         const int ngemm4 = (ngemm + 3) / 4;
@@ -309,13 +323,17 @@ static int launch_duo(const GemmDev& d, int ngemm, hipStream_t s) {
         hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3((unsigned)std::min<long long>((groups + 255) / 256, 8192)), dim3(256), 0, s, dd, ngemm4);
         return atmvfi::check_launch("gemm_duo (split-K reduce)");
     }
-    hipLaunchKernelGGL((gemm_duo_kernel<CONVM, BN>), dim3((unsigned)dd.vblocks), dim3(256), lds, s, dd);
+    hipLaunchKernelGGL((gemm_duo_kernel<CONVM, BN, X3>), dim3((unsigned)dd.vblocks), dim3(256), lds, s, dd);
     return atmvfi::check_launch("gemm_duo");
 }
 
 int atmvfi::launch_gemm_duo(const GemmDev& d, int ngemm, hipStream_t s) {
     // at most 64 GEMM columns: 64-column tiles (tile_wn = -2 forces the 128-column form for the A/B, -4 the 64-column one)
-    if ((ngemm <= 64 && d.force_wn != -2) || d.force_wn == -4)
-        return d.mode == ATMVFI_GEMM_CONV ? launch_duo<true, 64>(d, ngemm, s) : launch_duo<false, 64>(d, ngemm, s);
-    return d.mode == ATMVFI_GEMM_CONV ? launch_duo<true, 128>(d, ngemm, s) : launch_duo<false, 128>(d, ngemm, s);
+    const bool conv = d.mode == ATMVFI_GEMM_CONV;
+    if ((ngemm <= 64 && d.force_wn != -2) || d.force_wn == -4) {
+        if (d.terms == 1) return conv ? launch_duo<true, 64, false>(d, ngemm, s) : launch_duo<false, 64, false>(d, ngemm, s);
+        return conv ? launch_duo<true, 64, true>(d, ngemm, s) : launch_duo<false, 64, true>(d, ngemm, s);
+    }
+    if (d.terms == 1) return conv ? launch_duo<true, 128, false>(d, ngemm, s) : launch_duo<false, 128, false>(d, ngemm, s);
+    return conv ? launch_duo<true, 128, true>(d, ngemm, s) : launch_duo<false, 128, true>(d, ngemm, s);
 }

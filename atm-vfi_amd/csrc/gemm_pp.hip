@@ -53,7 +53,9 @@ constexpr int A_LO = BM * 64, W_HI = 2 * BM * 64, W_LO = W_HI + BN * 64;
 constexpr int PIECES = 6;                              // 16-byte DMA pieces per thread and stage: 4 of A, 2 of W
 constexpr int CST_FLOATS = atmvfi::gemm_const_floats(BN) + BM;      // bias / slope of the column block + the tile's row-map entries
 
-template <bool CONVM>
+// X3: the three-term product (the default).  X3 == false (ATMVFI_PREC_F16): hi(x) * hi(w) alone -- no lo' fragment reads, 16 MFMAs per
+// k-step instead of 48, no `cor`; DMA of both planes, stages, counted waits and barriers are the same source.
+template <bool CONVM, bool X3>
 __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmDev a) {
     fp16_saturate_on();
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -157,7 +159,8 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmDev a) {
         }
     };
 
-    f32x4 acc[4][4], cor[4][4];
+    f32x4 acc[4][4];
+    RegsIf<X3, f32x4[4][4]> cor;
 
 #ifdef ATMVFI_STAMP
     unsigned long long* kst = reinterpret_cast<unsigned long long*>(smem + 3 * STAGE + 2 * CST_FLOATS * sizeof(float));
@@ -182,7 +185,8 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmDev a) {
     __builtin_amdgcn_s_barrier();
     if (grp == 1) __builtin_amdgcn_s_barrier();          // the second group runs one phase behind
 
-    f16x8 xh[4], xl[4], wh[4], wl[4];
+    f16x8 xh[4], wh[4];
+    RegsIf<X3, f16x8[4]> xl, wl;
     const unsigned xfrag = lds_offset(smem) + (unsigned)((64 * wm + r) * 64 + ((g ^ swz64(r)) << 4));
     const unsigned wfrag = lds_offset(smem) + (unsigned)(W_HI + (64 * wn + r) * 64 + ((g ^ swz64(r)) << 4));
     int rd_off = 0;                                      // stage buffer (byte offset) of the k-step being read
@@ -204,12 +208,12 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmDev a) {
         static_for<0, 4>([&](auto ic) {
             constexpr int i = decltype(ic)::value;
             lds_read16<i * 1024>(xh[i], xa);
-            lds_read16<i * 1024 + A_LO>(xl[i], xa);
+            if constexpr (X3) lds_read16<i * 1024 + A_LO>(xl[i], xa);
         });
         static_for<0, 4>([&](auto jc) {
             constexpr int j = decltype(jc)::value;
             lds_read16<j * 1024>(wh[j], wa);
-            lds_read16<j * 1024 + BN * 64>(wl[j], wa);
+            if constexpr (X3) lds_read16<j * 1024 + BN * 64>(wl[j], wa);
         });
         rd_off = rd_off == 2 * STAGE ? 0 : rd_off + STAGE;
         if constexpr (KIND == 0) {
@@ -234,10 +238,17 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmDev a) {
             }
         };
         if (grp == 1 && g1wait) wait_next();
-        asm volatile("s_waitcnt lgkmcnt(0)"
-                     : "+v"(xh[0]), "+v"(xh[1]), "+v"(xh[2]), "+v"(xh[3]), "+v"(xl[0]), "+v"(xl[1]), "+v"(xl[2]), "+v"(xl[3]));
+        if constexpr (X3) {
+            asm volatile("s_waitcnt lgkmcnt(0)"
+                         : "+v"(xh[0]), "+v"(xh[1]), "+v"(xh[2]), "+v"(xh[3]), "+v"(xl[0]), "+v"(xl[1]), "+v"(xl[2]), "+v"(xl[3]));
 #pragma unroll
-        for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(wh[j]), "+v"(wl[j]));
+            for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(wh[j]), "+v"(wl[j]));
+        } else {
+            asm volatile("s_waitcnt lgkmcnt(0)"
+                         : "+v"(xh[0]), "+v"(xh[1]), "+v"(xh[2]), "+v"(xh[3]));
+#pragma unroll
+            for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(wh[j]));
+        }
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
@@ -247,13 +258,15 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmDev a) {
         for (int i = 0; i < 4; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                cor[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[j], xh[i], cor[i][j], 0, 0, 0);
+                if constexpr (X3) cor[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[j], xh[i], cor[i][j], 0, 0, 0);
                 acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[j], xh[i], acc[i][j], 0, 0, 0);
             }
+        if constexpr (X3) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
+            for (int i = 0; i < 4; ++i)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) cor[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[j], xl[i], cor[i][j], 0, 0, 0);
+                for (int j = 0; j < 4; ++j) cor[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[j], xl[i], cor[i][j], 0, 0, 0);
+        }
         __builtin_amdgcn_s_setprio(0);
         if (grp == 0) wait_next();
         __builtin_amdgcn_sched_barrier(0);
@@ -274,10 +287,14 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmDev a) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                cor[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
                 // pinned: hipcc otherwise folds the zeros into the first MFMAs' C operand and uses the (then dead) accumulator
                 // registers as temporaries of the first read phase, guarded by s_waitcnt vmcnt(0)
-                asm volatile("" : "+v"(acc[i][j]), "+v"(cor[i][j]));
+                if constexpr (X3) {
+                    cor[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+                    asm volatile("" : "+v"(acc[i][j]), "+v"(cor[i][j]));
+                } else {
+                    asm volatile("" : "+v"(acc[i][j]));
+                }
             }
         PP_STAMP(1);
         {
@@ -322,7 +339,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmDev a) {
         for (int i = 0; i < 4; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                acc[i][j] = acc[i][j] + cor[i][j] * LO_UNSCALE;
+                if constexpr (X3) acc[i][j] = acc[i][j] + cor[i][j] * LO_UNSCALE;
                 asm volatile("" : "+v"(acc[i][j]));
             }
         {
@@ -389,14 +406,14 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmDev a) {
 
 }  // namespace
 
-template <bool CONVM>
+template <bool CONVM, bool X3>
 static int launch_pp(const GemmDev& d, int ngemm, hipStream_t s) {
 #ifdef ATMVFI_STAMP
     const size_t lds = (size_t)3 * STAGE + 2 * CST_FLOATS * sizeof(float) + 1024;      // + the per-k-step stamp sums
 #else
     const size_t lds = (size_t)3 * STAGE + 2 * CST_FLOATS * sizeof(float);
 #endif
-    const hipError_t attr_err = atmvfi::allow_dynamic_lds<gemm_pp_kernel<CONVM>>(lds);
+    const hipError_t attr_err = atmvfi::allow_dynamic_lds<gemm_pp_kernel<CONVM, X3>>(lds);
     ATMVFI_REQUIRE(attr_err == hipSuccess, ATMVFI_ELAUNCH, "gemm_pp: hipFuncSetAttribute: %s", hipGetErrorString(attr_err));
     GemmDev dd = d;
     const int rc = atmvfi::plane_gemm_prepare("gemm_pp", dd, ngemm, BM, BN);
@@ -407,10 +424,11 @@ static int launch_pp(const GemmDev& d, int ngemm, hipStream_t s) {
     // persistent from two k-steps up (the ring's look-ahead of two stages then spans at most one tile boundary): one workgroup per
     // CU (147 KiB of LDS) walking its XCD's tiles; K <= 32: one workgroup per tile
     const int grid = d.nchunks32 >= 2 ? std::min(dd.vblocks, atmvfi::cu_count()) : dd.vblocks;
-    hipLaunchKernelGGL(gemm_pp_kernel<CONVM>, dim3((unsigned)grid), dim3(512), lds, s, dd);
+    hipLaunchKernelGGL((gemm_pp_kernel<CONVM, X3>), dim3((unsigned)grid), dim3(512), lds, s, dd);
     return atmvfi::check_launch("gemm_pp");
 }
 
 int atmvfi::launch_gemm_pp(const GemmDev& d, int ngemm, hipStream_t s) {
-    return d.mode == ATMVFI_GEMM_CONV ? launch_pp<true>(d, ngemm, s) : launch_pp<false>(d, ngemm, s);
+    if (d.terms == 1) return d.mode == ATMVFI_GEMM_CONV ? launch_pp<true, false>(d, ngemm, s) : launch_pp<false, false>(d, ngemm, s);
+    return d.mode == ATMVFI_GEMM_CONV ? launch_pp<true, true>(d, ngemm, s) : launch_pp<false, true>(d, ngemm, s);
 }

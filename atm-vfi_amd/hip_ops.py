@@ -109,6 +109,8 @@ SIGNATURES = {
     "atmvfi_conv3x3_planes3": (c_i, [c_f, c_f, c_l, c_i, c_i, c_i, c_i, c_f, c_f, c_i, c_f, c_i, c_f, c_f, c_f, c_f, c_l, c_i, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_f, c_l, c_f]),
     "atmvfi_conv3x3_planes_workspace_floats": (c_l, [c_i, c_i, c_i, c_i, c_i]),
     "atmvfi_conv3x3_planes_readout": (c_i, [c_f, c_f, c_l, c_i, c_i, c_i, c_i, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_l, c_f]),
+    "atmvfi_conv3x3_planes4": (c_i, [c_f, c_f, c_l, c_i, c_i, c_i, c_i, c_f, c_f, c_i, c_f, c_i, c_f, c_f, c_f, c_f, c_l, c_i, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_f, c_l, c_i, c_f]),
+    "atmvfi_conv3x3_planes_readout2": (c_i, [c_f, c_f, c_l, c_i, c_i, c_i, c_i, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_l, c_i, c_f]),
     "atmvfi_refine_tail": (c_i, [c_f, c_l, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f]),
     "atmvfi_layernorm": (c_i, [c_f, c_i, c_l, c_i, c_f, c_f, c_i, c_f, c_f, c_l, c_i, c_f, c_f, c_i, c_f]),
     "atmvfi_dwconv3x3_gelu": (c_i, [c_f, c_i, c_f, c_i, c_f, c_f, c_i, c_i, c_i, c_i, c_f, c_f, c_i, c_f]),
@@ -177,13 +179,16 @@ SIGNATURES = {
 SSIM_X_U8, SSIM_X_BGR, SSIM_ROUND_Y, SSIM_ACCUMULATE, SSIM_MSE_F32 = 1, 2, 4, 8, 16     # include/atmvfi.h ATMVFI_SSIM_*
 
 
-def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
+def load_library(path: str = LIB_PATH, optional=()) -> ctypes.CDLL:
+    """``optional``: symbols that may be missing (an older build of the ABI loaded beside this one for a same-process A/B)."""
     if not os.path.exists(path):
         raise HipLibraryMissing(
             f"{path} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
     lib = ctypes.CDLL(path)
     for name, (res, args) in SIGNATURES.items():
+        if name in optional and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)          # AttributeError if a declared symbol is missing
         fn.restype = res
         fn.argtypes = args
@@ -602,13 +607,13 @@ class LaunchPlan:
 class HipOps:
     """The op vocabulary of the hot path, each a single HIP kernel launch."""
 
-    def __init__(self, device: torch.device, checked: bool = False, lib_path: Optional[str] = None):
+    def __init__(self, device: torch.device, checked: bool = False, lib_path: Optional[str] = None, lib_optional=()):
         # checked: the build that counts operands beyond the f16x3 engines' fp16 range (libatmvfi_hip_checked.so, include/atmvfi.h
         # atmvfi_range_word_set).  One device word per HipOps; attached at the top of every forward (begin_forward): the library has
         # one attachment per device, so one checked model runs at a time on a device.
         self.checked = bool(checked)
         # lib_path: another build of the same ABI (tests and tools: the diagnostic libraries under tools/lib/)
-        self.lib = load_library(lib_path) if lib_path else load_library(CHECKED_LIB_PATH) if self.checked else load_library()
+        self.lib = load_library(lib_path, lib_optional) if lib_path else load_library(CHECKED_LIB_PATH) if self.checked else load_library()
         self.device = device
         self.range_word: Optional[torch.Tensor] = None
         if self.checked:
@@ -619,6 +624,10 @@ class HipOps:
         # "f16x3": 3x3/s1 convs run split-precision on the 16-bit MFMA (hi*hi + hi*lo + lo*hi, fp32 accumulate);
         # "f32": everything on the exact-fp32 MFMA.
         self.precision = "f16x3"
+        # Terms of a product in the PLANE kernels (conv3x3_planes, conv3x3_planes_readout, every GEMM on split-plane input), under
+        # precision "f16x3": 3 = hi*hi + hi*lo' + lo'*hi (the default), 1 = hi*hi alone (Network.set_precision("f16"): one MFMA per
+        # product, ~11 significand bits per operand).  Layouts, sinks, tile and split-K choices do not depend on it.
+        self.plane_terms = 3
         self.attention_f16x3 = True        # window attention on the f16x3 MFMA path too (False: the exact-fp32 kernel)
         # per-call kernel-instance overrides (parity tests, sweeps): (schedule, wn) of the fp32-input 3x3 kernel, tile width of the
         # fp32-input f16x3 GEMM; None / 0 = the library's cost model
@@ -715,6 +724,13 @@ class HipOps:
         dst = self.empty(9 * c)
         self._check(self.lib.atmvfi_pack_dw_weight(_ptr(w), _ptr(dst), c, self._stream()), "pack_dw_weight")
         return dst
+
+    def _plane_prec(self, p: "GemmParams"):
+        """The precision field of a launch on split-plane input under ``plane_terms``: ATMVFI_PREC_F16 (2) for single-term products."""
+        if self.plane_terms not in (1, 3):
+            raise ValueError(f"plane_terms must be 3 (f16x3) or 1 (f16), got {self.plane_terms!r}")
+        if self.plane_terms == 1 and p.precision == 1 and p.in_hi:
+            p.precision = 2
 
     def _prec(self, w: PackedWeight):
         """(precision, hi, lo) fields of GemmParams for this weight under the current precision mode."""
@@ -889,13 +905,17 @@ class HipOps:
         coff = in_chunk0 * x.ld_rows * 32 * 2       # bytes
         if workspace is not None and (workspace.dtype != torch.float32 or not workspace.is_cuda or not workspace.is_contiguous()):
             raise ValueError("conv3x3_planes: the split-K workspace must be a contiguous CUDA fp32 tensor")
-        self._run("conv3x3_planes", meta, self.lib.atmvfi_conv3x3_planes3, _ptr(x.t[0], coff), _ptr(x.t[1], coff), x.ld_rows,
+        if self.plane_terms not in (1, 3):
+            raise ValueError(f"plane_terms must be 3 (f16x3) or 1 (f16), got {self.plane_terms!r}")
+        # (three terms: the entry point without a term count -- it forwards with 3 -- so that a recorded plan of the default mode holds the same ops as before)
+        fn, terms = (self.lib.atmvfi_conv3x3_planes3, ()) if self.plane_terms == 3 else (self.lib.atmvfi_conv3x3_planes4, (self.plane_terms,))
+        self._run("conv3x3_planes", meta, fn, _ptr(x.t[0], coff), _ptr(x.t[1], coff), x.ld_rows,
                   n, h, wd, cin, _ptr(w.hi3), _ptr(w.lo3), cout, out_ptr, old, _ptr(bias), _ptr(prelu),
                   _ptr(planes.t[0]) if planes is not None else None, _ptr(planes.t[1]) if planes is not None else None,
                   planes.ld_rows if planes is not None else 0, planes_c0, _ptr(planes_prelu) if planes is not None else None,
                   _ptr(planes2.t[0]) if planes2 is not None else None, _ptr(planes2.t[1]) if planes2 is not None else None,
                   planes2.ld_rows if planes2 is not None else 0, planes2_c0, out_cmin, wn, _ptr(workspace),
-                  workspace.numel() if workspace is not None else 0, self._stream())
+                  workspace.numel() if workspace is not None else 0, *terms, self._stream())
 
     def pack_readout(self, w: torch.Tensor) -> torch.Tensor:
         """Operand of ``atmvfi_conv3x3_planes_readout``: refine_head.1's weight [3, C, 3, 3] (C = 32 or 64) as the 27 x C matrix
@@ -931,8 +951,11 @@ class HipOps:
         if contrib.dtype != torch.float32 or contrib.dim() != 2 or contrib.shape[0] != 27 or contrib.shape[1] < n * h * wd or not contrib.is_contiguous():
             raise ValueError("conv3x3_planes_readout: contrib must be contiguous fp32 [27, >= N*H*W]")
         meta = {"flops": 2.0 * n * h * wd * w.cout * (w.cin * 9 + 27), "bytes": 4.0 * n * h * wd * (w.cin + 27), "shape": f"M{n * h * wd} N{w.cout} K{w.cin * 9} +27"}
-        self._run("conv3x3_planes", meta, self.lib.atmvfi_conv3x3_planes_readout, _ptr(x.t[0]), _ptr(x.t[1]), x.ld_rows, n, h, wd, w.cin,
-                  _ptr(w.hi3), _ptr(w.lo3), w.cout, _ptr(bias), _ptr(prelu), _ptr(w2), _ptr(contrib), contrib.shape[1], self._stream())
+        if self.plane_terms not in (1, 3):
+            raise ValueError(f"plane_terms must be 3 (f16x3) or 1 (f16), got {self.plane_terms!r}")
+        fn, terms = (self.lib.atmvfi_conv3x3_planes_readout, ()) if self.plane_terms == 3 else (self.lib.atmvfi_conv3x3_planes_readout2, (self.plane_terms,))
+        self._run("conv3x3_planes", meta, fn, _ptr(x.t[0]), _ptr(x.t[1]), x.ld_rows, n, h, wd, w.cin,
+                  _ptr(w.hi3), _ptr(w.lo3), w.cout, _ptr(bias), _ptr(prelu), _ptr(w2), _ptr(contrib), contrib.shape[1], *terms, self._stream())
 
     def refine_tail(self, contrib, bias, slope, it, it_sum, it_clamped):
         """out = clamp(it + 2 * sigmoid(PReLU(bias + sum of the nine shifted tap contributions)) - 1): refine_head.1 + the residual."""
@@ -1001,6 +1024,7 @@ class HipOps:
                 "shape": f"M{n * oh * ow} N{cout} K{cin * w.kh * w.kw}"}
         ws = self._gemm_splitk(p, n * oh * ow, cout, w.kh * w.kw * ((cin + 31) // 32))
         p._srcs = (out, bias, prelu, ws)
+        self._plane_prec(p)
         self._run("conv2d_split", meta, self.lib.atmvfi_conv2d, ctypes.byref(p), self._stream())
 
     def deconv(self, x, w: PackedWeight, out, bias=None, prelu=None, in_prelu=None, planes: Optional[Planes] = None,
@@ -1044,6 +1068,7 @@ class HipOps:
                 "shape": f"M{n * h * wd} N{4 * cout} K{cin}"}
         ws = self._gemm_splitk(p, n * h * wd, 4 * ((cout + 3) // 4 * 4), (cin + 31) // 32) if use_planes else None
         p._srcs = (x, out, bias, prelu, in_prelu, ws)
+        self._plane_prec(p)
         self._run("deconv2x2_split" if use_planes else "deconv2x2_f16x3" if p.precision else "deconv2x2", meta, self.lib.atmvfi_deconv2x2,
                   ctypes.byref(p), self._stream())
 
@@ -1103,6 +1128,7 @@ class HipOps:
         meta = {"flops": 2.0 * m * cout * cin, "bytes": 4.0 * (m * cin + m * cout + cout * cin), "shape": f"M{m} N{cout} K{cin}"}
         ws = self._gemm_splitk(p, m, cout, (cin + 31) // 32) if planes is not None else None
         p._srcs = (None if planes is not None else x, out, bias, residual, out_row_map, ws)
+        self._plane_prec(p)
         self._run("linear_split" if planes is not None else "linear_f16x3" if p.precision else "linear", meta, self.lib.atmvfi_linear, ctypes.byref(p), self._stream())
 
     # ------------------------------------------------------------- transformer

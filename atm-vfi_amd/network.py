@@ -326,9 +326,18 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
         (~22 significand bits, operands must stay within the fp16 range).  "f32": every contraction on the exact-fp32
         MFMA (about 2.5x slower).  "f16x3-checked": the f16x3 arithmetic, bit for bit, on the CHECKED build of the library
         (libatmvfi_hip_checked.so), which counts every activation pair whose split hit the fp16 limit (|x| >= 65488, inf, NaN) --
-        ``range_violations()`` reads the count; launch plans and graphs are off in this mode.  Not part of the reference's API."""
-        if precision not in ("f16x3", "f32", "f16x3-checked"):
-            raise ValueError("precision must be 'f16x3', 'f32' or 'f16x3-checked'")
+        ``range_violations()`` reads the count; launch plans and graphs are off in this mode.
+
+        "f16" (opt-in, never a default): single-pass fp16 in the PLANE kernels.  There a product is hi(x) * hi(w) alone -- hi = the
+        split's high half, fp16 round-to-nearest-even, saturating -- accumulated in fp32 in the kernels' k order: one 16-bit MFMA
+        per product instead of three, about 11 significand bits per operand.  It covers the 3x3 plane kernel (its fused read-out's
+        main product included; the read-out's 27-row W2 product stays three-term) and every GEMM on split-plane input (linears,
+        deconvs, strided / dilated / 1x1 convs; split-K included).  The stem, window attention, the fp32-input engines, the 1x1 heads
+        and the pointwise kernels stay "f16x3"; activations are still handed over as both planes of each kernel's own fp32 result.
+        Outside the 1e-3 budget of the default (README "Precision modes": measured error and timing); has no checked twin --
+        ``range_violations()`` raises as in "f16x3".  Not part of the reference's API."""
+        if precision not in ("f16x3", "f16", "f32", "f16x3-checked"):
+            raise ValueError("precision must be 'f16x3', 'f16', 'f32' or 'f16x3-checked'")
         checked = precision == "f16x3-checked"
         if checked != self._checked:
             # another library: packed weights, workspaces, plans and the op backend belong to the one that made them
@@ -337,7 +346,13 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
         self._checked = checked
         self._precision = "f16x3" if checked else precision
         if self._ops_obj is not None and hasattr(self._ops_obj, "precision"):
-            self._ops_obj.precision = self._precision
+            self._apply_precision(self._ops_obj)
+
+    def _apply_precision(self, ops):
+        """The op backend's view of the mode: "f16" is the split-plane engines and layouts of "f16x3" (``ops.precision``: the plane
+        path stays on) with single-term products in the plane kernels (``ops.plane_terms``)."""
+        ops.precision = "f16x3" if self._precision == "f16" else self._precision
+        ops.plane_terms = 1 if self._precision == "f16" else 3
 
     def range_violations(self, reset: bool = False) -> int:
         """Activation pairs split beyond the fp16 operand range since the model entered "f16x3-checked" (or since the last
@@ -379,7 +394,7 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
                 raise RuntimeError("atm-vfi_amd.Network.forward runs on MI355X only: move the model and its inputs to "
                                    "'cuda' (HIP). There is no CPU implementation in the product; the CPU oracle lives in oracle/.")
             self._ops_obj = HipOps(device, checked=self._checked)
-            self._ops_obj.precision = self._precision
+            self._apply_precision(self._ops_obj)
             self._ops_obj.gemm_workspace = self._gemm_scratch
         return self._ops_obj
 
@@ -903,6 +918,11 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
                 self.local_motion_args["window_size"], self.global_motion_args["window_size"], getattr(ops, "warp_tiles", None),
                 getattr(ops, "conv3_instance", None), getattr(ops, "gemm_tile_wn", None))
 
+    def _pool_validity_key(self, ops, glob: bool, target) -> Tuple:
+        """What a pool slot's tokens were computed under (``forward_pooled``): weights, ``global_motion``, the precision mode ("f16x3" /
+        "f16" / "f32"; the checked build), the attention engine, the plane-row regime and the frame stage's split-K target."""
+        return (self._prepared_sig, glob, self._precision, self._checked, getattr(ops, "attention_f16x3", None), self._rows_fit_planes, target)
+
     def _mode_key(self, ops, im0, im1) -> Tuple:
         return (tuple(im0.shape), tuple(im1.shape), str(im0.device)) + self._mode_fields(ops) + (self._workspace_key(im0),)
 
@@ -1211,8 +1231,7 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
                 self._sync_plan_sig()
             glob = bool(self.global_motion)
             target = self._splitk_of(ops, H, W, 2 * b) if exact else None
-            vkey = (self._prepared_sig, glob, self._precision, self._checked, getattr(ops, "attention_f16x3", None), self._rows_fit_planes,
-                    target)
+            vkey = self._pool_validity_key(ops, glob, target)
             stale = []
             for s in left + right:
                 if s not in stale and pool.keys[s] != vkey:

@@ -45,6 +45,7 @@ def main(argv=None):
     ap.add_argument("--global-motion", choices=("on", "off"), default=None, help="override the protocol's global_motion")
     ap.add_argument("--json", default=None, help="write the per-sample records and the means here")
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--precision", choices=("f16x3", "f16", "f32"), default="f16x3", help="contraction arithmetic (Network.set_precision): f16x3 = the default, three 16-bit MFMAs per product; f16 = single-pass fp16 in the plane kernels (faster, about 1e-2 of the frame range); f32 = exact fp32 MFMA (about 2.5x slower)")
     a = ap.parse_args(argv)
 
     pkg = import_module("atm-vfi_amd")
@@ -78,6 +79,7 @@ def main(argv=None):
     print(f"--- loading from checkpoint: {a.ckpt} ---")
     host_io.load_model_checkpoint(model, a.ckpt)
     model.to(dev).eval()
+    model.set_precision(a.precision)
     gm = None if a.global_motion is None else a.global_motion == "on"
     print(f"Dataset: {a.dataset}\t TTA: {a.tta}\t samples: {len(samples) if a.limit is None else min(a.limit, len(samples))}")
     t0 = time.time()

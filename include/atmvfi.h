@@ -140,6 +140,14 @@ typedef struct atmvfi_gemm_params {
 
 #define ATMVFI_PREC_F32   0
 #define ATMVFI_PREC_F16X3 1
+/* Single-pass fp16 (opt-in; never a default): a product is hi(x) * hi(w) alone -- hi = the split's high half, fp16 round-to-nearest-even,
+   saturating -- accumulated in fp32 in the engine's k order into one accumulator: one v_mfma_f32_16x16x32_f16 per product instead of
+   three, about 11 significand bits per operand.  Accepted ONLY with split-plane input (in_hi and in_lo set), on the gemm_pp / gemm_duo
+   engines: tile_wn 0 (auto, split-K included), -2, -3, -4.  With fp32 input, or with tile_wn = -1 (the reference schedule has no such
+   instance), the call returns ATMVFI_EINVAL before any launch.  Weights (weight_hi / weight_lo, both required: the layouts do not
+   change) and the plane sink follow the rules of ATMVFI_PREC_F16X3; a sink still writes BOTH planes, the exact split of the launch's own
+   fp32 result.  The tile and split-K choices do not depend on the precision.  The reference has no counterpart (it computes in fp32). */
+#define ATMVFI_PREC_F16   2
 
 int atmvfi_gemm(const atmvfi_gemm_params* p, void* stream);
 /* fp32 elements of split-K scratch the plane-input GEMM wants for M rows, ngemm GEMM columns (Cout; 4 * round_up(Cout, 4) for DECONV)
@@ -243,6 +251,16 @@ int atmvfi_conv3x3_planes3(const void* in_hi, const void* in_lo, int64_t in_rows
                            const void* w_lo, int Cout, float* out, int out_ld, const float* bias, const float* prelu, void* out_hi,
                            void* out_lo, int64_t plane_rows, int out_c0, const float* plane_prelu, void* out_hi2, void* out_lo2,
                            int64_t plane_rows2, int out_c02, int out_cmin, int wn, float* workspace, int64_t workspace_floats, void* stream);
+/* The same with the NUMBER OF TERMS of a product: 3 = hi*hi + hi*lo' + lo'*hi (f16x3: what every entry point above computes; they forward
+ * here with 3), 1 = hi*hi alone (the single-pass fp16 mode, see ATMVFI_PREC_F16: one MFMA per product into the one accumulator, same k
+ * order, same tile width and K split as with 3).  The input planes, the weight planes and every output rule are unchanged: both lo'
+ * planes must still be passed, and the plane sinks still write both planes of the launch's own fp32 result.  Any other value:
+ * ATMVFI_EINVAL before any launch. */
+int atmvfi_conv3x3_planes4(const void* in_hi, const void* in_lo, int64_t in_rows, int N, int H, int W, int Cin, const void* w_hi,
+                           const void* w_lo, int Cout, float* out, int out_ld, const float* bias, const float* prelu, void* out_hi,
+                           void* out_lo, int64_t plane_rows, int out_c0, const float* plane_prelu, void* out_hi2, void* out_lo2,
+                           int64_t plane_rows2, int out_c02, int out_cmin, int wn, float* workspace, int64_t workspace_floats, int terms,
+                           void* stream);
 /* ------------------------------------------------------------------------------------
  * LayerNorm over the channel axis of token rows (eps 1e-5, affine), optional gather.
  * Replaces nn.LayerNorm at attention.py:316 (norm1 on windowed tokens), :333 (norm2) and
@@ -411,6 +429,11 @@ int atmvfi_final_residual(const float* it /*[B,3,H,W]*/, const float* r, int r_l
 int atmvfi_conv3x3_planes_readout(const void* in_hi, const void* in_lo, int64_t in_rows, int N, int H, int W, int Cin, const void* w_hi,
                                   const void* w_lo, int Cout, const float* bias, const float* prelu, const void* w2, float* contrib,
                                   int64_t contrib_plane, void* stream);
+/* The same with the number of terms of the MAIN 3x3 product (3 or 1, as atmvfi_conv3x3_planes4; anything else: ATMVFI_EINVAL).  The 27-row
+ * W2 product on the activated tile is three-term in both: it forms the output residual and costs next to nothing. */
+int atmvfi_conv3x3_planes_readout2(const void* in_hi, const void* in_lo, int64_t in_rows, int N, int H, int W, int Cin, const void* w_hi,
+                                   const void* w_lo, int Cout, const float* bias, const float* prelu, const void* w2, float* contrib,
+                                   int64_t contrib_plane, int terms, void* stream);
 int atmvfi_refine_tail(const float* contrib, int64_t contrib_plane, const float* bias /*[3] or NULL*/, const float* slope /*[3] or NULL*/,
                        const float* it /*[B,3,H,W]*/, float* it_sum, float* it_clamped, int B, int H, int W, void* stream);
 

@@ -51,49 +51,53 @@ def check_planes(asm_text):
     nothing that touches memory and no branch; in front of each a read phase (back to the previous barrier) with 4 + 2*WN
     fragment reads, at least one LDS-DMA, lgkmcnt(0), no branch, and -- except in the first LA - 1 k-steps of a tile, which find
     their weights complete -- a counted vmcnt wait; 46 barriers in all; no register spill; and between the first and the last
-    MFMA phase no vmcnt wait that the compiler made (the kernel's own come from inline asm)."""
+    MFMA phase no vmcnt wait that the compiler made (the kernel's own come from inline asm).
+    The single-term instances (<WN, false>: the "f16" mode) are held to the same skeleton -- same barriers, same DMA, same counted
+    waits -- with 2*WN MFMAs per phase and the 2 + WN hi fragment reads."""
     problems = []
     lines = asm_text.splitlines()
-    for wn in range(1, 9):
-        starts = [i for i, l in enumerate(lines) if re.match(rf"^_ZN\S*conv3x3_planes_kernelILi{wn}E\S*:", l)]
+    for wn, x3 in [(w, t) for t in (1, 0) for w in range(1, 9)]:
+        n_mfma_want, n_read_want = (6 * wn, 4 + 2 * wn) if x3 else (2 * wn, 2 + wn)
+        tag = f"{wn}" if x3 else f"{wn}, f16"
+        starts = [i for i, l in enumerate(lines) if re.match(rf"^_ZN\S*conv3x3_planes_kernelILi{wn}ELb{x3}EE\S*:", l)]
         if not starts:
-            problems.append(f"planes<{wn}>: kernel not found")
+            problems.append(f"planes<{tag}>: kernel not found")
             continue
         end = next(i for i in range(starts[0], len(lines)) if "s_endpgm" in lines[i])
         raw = lines[starts[0]:end]
         body = [l.split(";")[0] for l in raw]
         if any("scratch_" in l for l in body):
-            problems.append(f"planes<{wn}>: register spill (scratch access)")
+            problems.append(f"planes<{tag}>: register spill (scratch access)")
         bars = [i for i, l in enumerate(body) if re.search(r"\bs_barrier\b", l)]
         if len(bars) != 46:          # 2 (prologue) + 2 * (9 + 9 + 3) k-steps + 2 (tile boundary: re-align, drop behind)
-            problems.append(f"planes<{wn}>: expected 46 s_barrier, found {len(bars)}")
+            problems.append(f"planes<{tag}>: expected 46 s_barrier, found {len(bars)}")
         p1 = [i for i, l in enumerate(body) if re.search(r"\bs_setprio 1\b", l)]
         p0 = [i for i, l in enumerate(body) if re.search(r"\bs_setprio 0\b", l)]
         if len(p1) != 21 or len(p0) != 21:
-            problems.append(f"planes<{wn}>: expected 21 MFMA phases, found {len(p1)} / {len(p0)}")
+            problems.append(f"planes<{tag}>: expected 21 MFMA phases, found {len(p1)} / {len(p0)}")
             continue
         nowait = 0
         for k, (a, b) in enumerate(zip(p1, p0)):
             seg = body[a + 1:b]
             n_mfma = sum("v_mfma" in l for l in seg)
             mem = [l for l in seg if re.search(r"\b(ds_|global_|buffer_|flat_|scratch_)", l)]
-            if n_mfma != 6 * wn or mem or any(re.search(r"\bs_cbranch|\bs_branch", l) for l in seg):
-                problems.append(f"planes<{wn}>: MFMA phase {k} has {n_mfma} MFMAs, {len(mem)} memory instructions (or a branch)")
+            if n_mfma != n_mfma_want or mem or any(re.search(r"\bs_cbranch|\bs_branch", l) for l in seg):
+                problems.append(f"planes<{tag}>: MFMA phase {k} has {n_mfma} MFMAs, {len(mem)} memory instructions (or a branch)")
             bar = max(i for i in bars if i < a)
             prev = max([i for i in bars if i < bar] + [0])
             rd = body[prev + 1:bar]
             waits = [l.strip() for l in rd if "s_waitcnt" in l]
-            if sum("ds_read_b128" in l for l in rd) != 4 + 2 * wn or sum("global_load_lds" in l for l in rd) == 0:
-                problems.append(f"planes<{wn}>: read phase {k}: unexpected fragment read / DMA count")
+            if sum("ds_read_b128" in l for l in rd) != n_read_want or sum("global_load_lds" in l for l in rd) == 0:
+                problems.append(f"planes<{tag}>: read phase {k}: unexpected fragment read / DMA count")
             if not any("lgkmcnt(0)" in w for w in waits):
-                problems.append(f"planes<{wn}>: read phase {k} lacks lgkmcnt(0)")
+                problems.append(f"planes<{tag}>: read phase {k} lacks lgkmcnt(0)")
             if not any(re.search(r"vmcnt\([1-9]\d*\)", w) for w in waits):
                 nowait += 1
         if nowait > 3:               # the first LA - 1 <= 3 k-steps of the first chunk
-            problems.append(f"planes<{wn}>: {nowait} read phases without a counted vmcnt wait (at most LA - 1 = 3 expected)")
+            problems.append(f"planes<{tag}>: {nowait} read phases without a counted vmcnt wait (at most LA - 1 = 3 expected)")
         for i in range(p1[0], p0[-1]):
             if re.search(r"s_waitcnt.*vmcnt", raw[i]) and "ASMSTART" not in raw[i - 1]:
-                problems.append(f"planes<{wn}>: compiler-inserted '{raw[i].strip()}' inside the k-loop region (line {i})")
+                problems.append(f"planes<{tag}>: compiler-inserted '{raw[i].strip()}' inside the k-loop region (line {i})")
     return problems
 
 
@@ -102,10 +106,11 @@ def check_pp(asm_text):
     touches memory; every read phase in front of one (back to the previous s_barrier) holds the 16 fragment reads; no register is
     spilled (a scratch reload brings a compiler-made s_waitcnt vmcnt(0) with it, which would drain the DMA ring); and the only
     vmcnt waits between the first and the last MFMA phase are the kernel's own (inline asm): vmcnt(6), vmcnt(8), and vmcnt(0) at
-    the places the source puts it (last k-step but one of a last tile; the second group before its epilogue)."""
+    the places the source puts it (last k-step but one of a last tile; the second group before its epilogue).
+    The single-term instances (<CONVM, false>: ATMVFI_PREC_F16) likewise, with 16 MFMAs per phase and the 8 hi fragment reads."""
     problems = []
     lines = asm_text.splitlines()
-    for tag in ("Lb0", "Lb1"):
+    for tag, n_mfma_want, n_read_want in (("Lb0ELb1E", 48, 16), ("Lb1ELb1E", 48, 16), ("Lb0ELb0E", 16, 8), ("Lb1ELb0E", 16, 8)):
         starts = [i for i, l in enumerate(lines) if re.match(rf"^_ZN\S*gemm_pp_kernelI{tag}E\S*:", l)]
         if not starts:
             problems.append(f"gemm_pp<{tag}>: kernel not found")
@@ -123,13 +128,13 @@ def check_pp(asm_text):
             seg = body[a + 1:b]
             n_mfma = sum("v_mfma_f32_16x16x32_f16" in l for l in seg)
             mem = [l for l in seg if re.search(r"\b(ds_|global_|buffer_|flat_|scratch_)", l)]
-            if n_mfma != 48 or mem or any(re.search(r"\bs_cbranch|\bs_branch", l) for l in seg):
+            if n_mfma != n_mfma_want or mem or any(re.search(r"\bs_cbranch|\bs_branch", l) for l in seg):
                 problems.append(f"gemm_pp<{tag}>: MFMA phase at line {a}: {n_mfma} MFMAs, {len(mem)} memory instructions")
             bar = max(i for i in range(a) if re.search(r"\bs_barrier\b", body[i]))           # the barrier that opens the MFMA phase
             prev = max([i for i in range(bar) if re.search(r"\bs_barrier\b|\bs_setprio 0\b", body[i])] + [0])
             rd = body[prev:bar]
-            if sum("ds_read_b128" in l for l in rd) < 16 or not any("lgkmcnt(0)" in l for l in rd):
-                problems.append(f"gemm_pp<{tag}>: read phase before line {a}: fewer than 16 fragment reads or no lgkmcnt(0)")
+            if sum("ds_read_b128" in l for l in rd) < n_read_want or not any("lgkmcnt(0)" in l for l in rd):
+                problems.append(f"gemm_pp<{tag}>: read phase before line {a}: fewer than {n_read_want} fragment reads or no lgkmcnt(0)")
         # compiler-made vmcnt waits inside the k-loop region: the kernel's own come from inline asm (marked ASMSTART / ASMEND)
         raw = lines[starts[0]:end]
         first, last = p1[0], p0[-1]
@@ -302,7 +307,7 @@ def epilogue_budget(planes_asm, pp_asm):
     rows = ["# Epilogue instruction budget (static count on the shipped ISA; tools/check_isa.py --budget)", ""]
     lines = planes_asm.splitlines()
     for wn in (4, 7, 8):
-        body = _kernel_body(lines, rf"^_ZN\S*conv3x3_planes_kernelILi{wn}E\S*:")
+        body = _kernel_body(lines, rf"^_ZN\S*conv3x3_planes_kernelILi{wn}ELb1EE\S*:")
         if body is None:
             continue
         p0 = [i for i, l in enumerate(body) if re.search(r"\bs_setprio 0\b", l)]
@@ -348,7 +353,7 @@ def epilogue_budget(planes_asm, pp_asm):
             rows.append(f"| {kind} | {g['blocks']} | {g['valu']} | {g['pk']} | {g['cvt_split']} | {g['swap']} | {g['vmax']} | {g['cndmask']} | {g['store']} | {copies} | {per} |")
         rows.append("")
     lines = pp_asm.splitlines()
-    for tag, nm in (("Lb0", "LINEAR / DECONV"), ("Lb1", "CONV")):
+    for tag, nm in (("Lb0ELb1E", "LINEAR / DECONV"), ("Lb1ELb1E", "CONV")):
         body = _kernel_body(lines, rf"^_ZN\S*gemm_pp_kernelI{tag}E\S*:")
         if body is None:
             continue

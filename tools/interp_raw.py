@@ -51,6 +51,7 @@ def main():
     ap.add_argument("--dedup", action="store_true", help="with --fps-out: drop repeated frames (Duplicates() defaults)")
     ap.add_argument("--shutter", default=None, metavar="ANGLE", help="with --fps-out: a synthetic shutter of ANGLE degrees (e.g. 180)")
     ap.add_argument("--light", choices=("code", "linear"), default="linear", help="with --shutter: the domain the samples are averaged in")
+    ap.add_argument("--precision", choices=("f16x3", "f16", "f32"), default="f16x3", help="contraction arithmetic (Network.set_precision): f16x3 = the default, three 16-bit MFMAs per product; f16 = single-pass fp16 in the plane kernels (faster, about 1e-2 of the frame range); f32 = exact fp32 MFMA (about 2.5x slower)")
     a = ap.parse_args()
     if (a.dedup or a.levels != 3 or a.shutter is not None) and a.fps_out is None:
         ap.error("--levels, --dedup and --shutter need --fps-out")
@@ -77,6 +78,7 @@ def main():
         net.load_state_dict(pkg.synthetic_state_dict(a.model, seed=1), strict=True)
     net = net.to(torch.device("cuda:0")).eval()
     net.global_motion = not a.global_off
+    net.set_precision(a.precision)
     area = yuv.ActiveArea() if a.active else None
     src = sys.stdin.buffer if a.src == "-" else a.src
     dst = sys.stdout.buffer if a.dst == "-" else a.dst
