@@ -19,7 +19,7 @@ from typing import List, Optional
 
 import torch
 
-from .pixfmt import Packed, Surface, _not_420, _origin_error, as_surface
+from .pixfmt import DeepRGB, Packed, Surface, _not_420, _origin_error, as_surface
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libatmvfi_hip.so")
@@ -164,6 +164,8 @@ SIGNATURES = {
     "atmvfi_yuv_sub_encode": (c_i, [c_f, c_i, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f]),
     "atmvfi_yuv_unpack": (c_i, [c_f, c_i, c_i, c_i, c_l, c_f, c_f]),
     "atmvfi_yuv_pack": (c_i, [c_f, c_i, c_i, c_i, c_f, c_f]),
+    "atmvfi_rgb16_decode": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f, c_f]),
+    "atmvfi_rgb16_encode": (c_i, [c_f, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f]),
     "atmvfi_pack_frames": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_f]),
     "atmvfi_final_residual": (c_i, [c_f, c_f, c_i, c_f, c_f, c_i, c_i, c_i, c_f]),
     "atmvfi_l1_mean": (c_i, [c_f, c_f, c_f, c_i, c_l, c_f, c_l, c_f]),
@@ -1809,9 +1811,61 @@ class HipOps:
                   int(pad_left), h, w, int(s.depth), s.matrix_id, int(s.full_range), s.siting_id, s.subsampling_id, s.chroma_id, int(s.msb),
                   _ptr(buf), self._stream())
 
+    def _rgb16_buf(self, who: str, buf, fmt, role: str):
+        if not isinstance(fmt, DeepRGB):
+            raise ValueError(f"{who}: a yuv.DeepRGB expected (got {type(fmt).__name__})")
+        n = fmt.frame_bytes
+        if not isinstance(buf, torch.Tensor) or buf.dtype != torch.uint8 or buf.dim() != 1 or buf.numel() != n or not buf.is_contiguous() or not buf.is_cuda:
+            raise ValueError(f"{who}: {role} buf must be a contiguous CUDA uint8 tensor of {n} bytes ({fmt.height} x {fmt.width} {fmt.layout}, "
+                             f"depth {fmt.depth})")
+        return n
+
+    def rgb16_decode(self, buf, fmt, dst=None, dst_u8=None, window=None, pad_top: int = 0, pad_left: int = 0):
+        """One deep RGB frame of ``fmt`` (a ``yuv.DeepRGB``: rgb48, bgr48 or gbrp at 10, 12 or 16 bit; ``buf`` a contiguous CUDA uint8
+        tensor of ``fmt.frame_bytes`` bytes, little-endian uint16 samples, 2-byte aligned) -> ``window=(y0, x0, h, w)`` of it (default: all;
+        any origin) as ``dst`` fp32 planar RGB [3,Hp,Wp] = min(q, top) / top with replicate padding, the window at (pad_top, pad_left),
+        and / or ``dst_u8``, its 8-bit probe picture uint8 [h,w,3] RGB = min(q, top) >> (depth - 8) (include/atmvfi.h
+        atmvfi_rgb16_decode; the bits of ``rgb16.decode_numpy_f32`` / ``probe_numpy``)."""
+        self._rgb16_buf("rgb16_decode", buf, fmt, "source")
+        if dst is None and dst_u8 is None:
+            raise ValueError("rgb16_decode: give dst, dst_u8 or both")
+        h, w = fmt.height, fmt.width
+        y0, x0, wh, ww = (0, 0, h, w) if window is None else _window("rgb16_decode", fmt, window)
+        nbytes = 6.0 * wh * ww
+        if dst is None:
+            hp, wp = wh, ww
+        else:
+            _f32_canvas(dst, "rgb16_decode", ": dst")
+            _, hp, wp = dst.shape
+            if pad_top < 0 or pad_left < 0 or wh + pad_top > hp or ww + pad_left > wp:
+                raise ValueError(f"rgb16_decode: canvas {hp} x {wp} is smaller than the window {wh} x {ww} plus padding ({pad_top}, {pad_left})")
+            nbytes += 12.0 * hp * wp
+        if dst_u8 is not None:
+            _u8_frame(dst_u8, "rgb16_decode", (wh, ww), ": dst_u8")
+            nbytes += 3.0 * wh * ww
+        self._run("rgb16_decode", {"bytes": nbytes}, self.lib.atmvfi_rgb16_decode, _ptr(buf), h, w, fmt.depth, fmt.layout_id, y0, x0, wh, ww,
+                  _ptr(dst), hp, wp, int(pad_top), int(pad_left), _ptr(dst_u8), self._stream())
+
+    def rgb16_encode(self, buf, fmt, src, pad_top: int = 0, pad_left: int = 0):
+        """``src`` fp32 planar RGB [3,Hp,Wp] with the frame at (pad_top, pad_left) -> ``buf``, one deep RGB frame of ``fmt`` (a
+        ``yuv.DeepRGB``; a contiguous CUDA uint8 tensor of ``fmt.frame_bytes`` bytes): the sample clip(rint(x * top), 0, top) in the
+        layout's order (include/atmvfi.h atmvfi_rgb16_encode; the bits of ``rgb16.encode_numpy``)."""
+        n = self._rgb16_buf("rgb16_encode", buf, fmt, "destination")
+        if src is None:         # (the one source)
+            raise ValueError("rgb16_encode: src must be a contiguous CUDA fp32 [3,Hp,Wp] tensor")
+        _f32_canvas(src, "rgb16_encode", ": src")
+        h, w = fmt.height, fmt.width
+        _, hp, wp = src.shape
+        if pad_top < 0 or pad_left < 0 or h + pad_top > hp or w + pad_left > wp:
+            raise ValueError(f"rgb16_encode: canvas {hp} x {wp} is smaller than the frame {h} x {w} plus padding ({pad_top}, {pad_left})")
+        self._run("rgb16_encode", {"bytes": n + 12.0 * h * w}, self.lib.atmvfi_rgb16_encode, _ptr(src), hp, wp, int(pad_top), int(pad_left),
+                  _ptr(buf), h, w, fmt.depth, fmt.layout_id, self._stream())
+
     # The loops' colour conversion: a yuv.Format goes to the planar entry points as ever, a yuv.Surface to the two surface calls, and
-    # either with a subsampling other than 4:2:0 to the two sub calls.
+    # either with a subsampling other than 4:2:0 to the two sub calls; a yuv.DeepRGB to the two rgb16 calls (its depth is always kept).
     def yuv_decode(self, buf, fmt, dst_u8=None, dst=None, window=None, pad_top: int = 0, pad_left: int = 0, keep_depth: bool = False):
+        if isinstance(fmt, DeepRGB):
+            return self.rgb16_decode(buf, fmt, dst=dst, dst_u8=dst_u8, window=window, pad_top=pad_top, pad_left=pad_left)
         if fmt.subsampling != "420":
             return self.yuv_sub_decode(buf, fmt, dst_u8=dst_u8, dst=dst, window=window, pad_top=pad_top, pad_left=pad_left, keep_depth=keep_depth)
         if isinstance(fmt, Surface):
@@ -1823,6 +1877,10 @@ class HipOps:
         return self.yuv420_to_rgb(buf, fmt, dst_u8=dst_u8, dst=dst, pad_top=pad_top, pad_left=pad_left)
 
     def yuv_encode(self, buf, fmt, src_u8=None, src=None, pad_top: int = 0, pad_left: int = 0):
+        if isinstance(fmt, DeepRGB):
+            if src_u8 is not None:
+                raise ValueError("yuv_encode: a yuv.DeepRGB frame is encoded from the fp32 src (src_u8 holds 8-bit pixels)")
+            return self.rgb16_encode(buf, fmt, src, pad_top=pad_top, pad_left=pad_left)
         if fmt.subsampling != "420":
             return self.yuv_sub_encode(buf, fmt, src_u8=src_u8, src=src, pad_top=pad_top, pad_left=pad_left)
         if isinstance(fmt, Surface):

@@ -246,11 +246,14 @@ class FramePipeline:
 
     ``keep_depth`` (default False; changes nothing without a 10-bit ``pixfmt``): ``atmvfi_yuv420p10_to_f32`` decodes the uploaded
     I420 bytes straight into the padded input (q / 1023: no 8-bit round trip), ``atmvfi_f32_to_yuv420p10`` encodes the prediction,
-    and the frames leave as 1-D uint16 arrays of ``pixfmt``.  The uint8 RGB frame is made only for a ``scene`` signature."""
+    and the frames leave as 1-D uint16 arrays of ``pixfmt``.  The uint8 RGB frame is made only for a ``scene`` signature.
+
+    ``pixfmt=yuv.DeepRGB(...)`` (RGB above 8 bits; ``keep_depth=True`` only, else ``ValueError``): the same path with
+    ``atmvfi_rgb16_decode`` / ``atmvfi_rgb16_encode``; the frame a ``scene`` signature reads is the 8-bit probe picture q >> (depth - 8)."""
 
     def __init__(self, model, height: int, width: int, isBGR: bool = True, divisor: int = 64, depth: int = 3, streams: int = 1,
                  scene=None, pixfmt=None, keep_depth: bool = False):
-        if hasattr(pixfmt, "layout"):                # (a yuv.Packed)
+        if hasattr(pixfmt, "planar"):                # (a yuv.Packed)
             raise ValueError("FramePipeline: packed 4:2:2 frames are not taken here: interpolate_video_nx(factor=2) covers 2x")
         ops, dev = _hip_ops_of(model)
         if ops is None:
@@ -267,7 +270,9 @@ class FramePipeline:
         self.hp, self.wp = height + pad._pad[2] + pad._pad[3], width + pad._pad[0] + pad._pad[1]
         mk = lambda *s, dt: torch.empty(*s, dtype=dt, device=dev)
         self.pixfmt = pixfmt
-        self.deep = bool(keep_depth) and pixfmt is not None and pixfmt.depth == 10
+        from .pixfmt import deep_rgb_refusals
+        deep_rgb_refusals("FramePipeline", pixfmt, keep_depth)
+        self.deep = bool(keep_depth) and pixfmt is not None and pixfmt.depth > 8
         if pixfmt is not None:
             if (pixfmt.height, pixfmt.width) != (height, width):
                 raise ValueError(f"FramePipeline: pixfmt describes {pixfmt.height}x{pixfmt.width} frames, the pipeline {height}x{width}")
@@ -411,7 +416,7 @@ def interpolate_video_2x(frames, model, isBGR: bool = True, divisor: int = 64, d
     ``pixfmt`` (a ``yuv.Format``): the frames are packed planar I420 arrays, in and out; originals pass through as the caller's own
     bytes (no colour round trip), predictions are encoded on the device (8-bit, also for 10-bit input); ``isBGR`` is ignored.
     ``keep_depth`` (changes nothing without a 10-bit ``pixfmt``): the network sees q / 1023 and the predictions leave as 10-bit frames
-    (1-D uint16 arrays), see ``FramePipeline``."""
+    (1-D uint16 arrays), see ``FramePipeline``.  A ``yuv.DeepRGB`` ``pixfmt`` (RGB above 8 bits) needs ``keep_depth=True``."""
     from collections import deque
     it = iter(frames)
     first = next(it, None)

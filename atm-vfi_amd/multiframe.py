@@ -253,10 +253,20 @@ def interpolate_video_nx(frames, model, factor: int = 4, time_interval: int = 1,
     ``pixfmt.planar`` and everything above holds for it.  Every uploaded frame is unpacked on the copy stream right behind its copy
     (``HipOps.yuv_unpack``), a produced frame is encoded into a planar scratch and packed into the output ring (``HipOps.yuv_pack``):
     the same layout at its default pitch, for a 10-bit layout without ``keep_depth`` its 8-bit one (v210 -> uyvy, y210 -> yuy2).
-    Originals at the default pitch are the caller's own arrays, at another pitch their tight repacks."""
+    Originals at the default pitch are the caller's own arrays, at another pitch their tight repacks.
+
+    ``pixfmt=yuv.DeepRGB(...)`` (RGB above 8 bits: rgb48, bgr48 or gbrp at 10, 12 or 16 bit; needs ``keep_depth=True``, not with
+    ``active``: ``ValueError``): frames are contiguous uint16 arrays of ``3 H W`` samples in any shape.  The uploaded bytes stay in the
+    slot, ``atmvfi_rgb16_decode`` decodes them straight into the pool slot (the crop as the kernel's window; the network sees
+    min(q, top) / top) and, only when ``scene`` needs a signature, makes the 8-bit probe picture q >> (depth - 8) on the copy stream:
+    cut decisions are those of the truncated 8-bit picture.  Produced frames are ``atmvfi_rgb16_encode`` of the fp32 prediction (with
+    ``tta``: of the fp32 average) and leave as 1-D uint16 arrays of ``pixfmt.cropped(h, w)``; originals, and the copies of a cut
+    segment, are the caller's own arrays (``rgb16.crop`` of them when cropping: any origin)."""
     from .host_io import _hip_ops_of
+    from .pixfmt import deep_rgb_refusals
     from .scene import cut_fill
     nx_levels(factor)
+    deep_rgb_refusals("interpolate_video_nx", pixfmt, keep_depth, active=active)
     if active is not None and crop is not None:
         _active_refusals("interpolate_video_nx", active, crop, pixfmt, keep_depth, None)
     if scene is not None:

@@ -1,6 +1,7 @@
-"""The frame descriptors of the YUV code: ``Format`` (a packed planar frame), ``Surface`` (a decoder's layout of one) and the rules both
-share.  A leaf module (numpy only): hip_ops.py validates against these classes and yuv.py, which re-exports every name here, builds the
-twins, the readers and the loops' front ends on them."""
+"""The frame descriptors of the YUV code: ``Format`` (a packed planar frame), ``Surface`` (a decoder's layout of one), ``Packed`` (a
+capture card's packed 4:2:2 frame), ``DeepRGB`` (an RGB frame above 8 bits) and the rules they share.  A leaf module (numpy only):
+hip_ops.py validates against these classes and yuv.py, which re-exports every name here, builds the twins, the readers and the
+loops' front ends on them."""
 from __future__ import annotations
 
 import functools
@@ -370,6 +371,79 @@ class Packed:
             raise ValueError(f"{what}: a contiguous {np.dtype(self.dtype).name} {self.layout} frame of {self.frame_samples} samples "
                              f"({self.height} x {self.width}, pitch {self.pitch}) expected, got {a.dtype} {tuple(a.shape)}")
         return a.reshape(-1)
+
+
+RGB_LAYOUTS = ("rgb48", "bgr48", "gbrp")      # ids 0..2 (include/atmvfi.h, atmvfi_rgb16_decode)
+RGB_DEPTHS = (10, 12, 16)
+
+
+@dataclass(frozen=True)
+class DeepRGB:
+    """One RGB frame above 8 bits (film scans, RGB mezzanine codecs, ffmpeg's ``rgb48le`` / ``bgr48le`` / ``gbrp10le`` / ``gbrp12le`` /
+    ``gbrp16le``): ``3 H W`` little-endian uint16 samples, LSB-aligned, ``top = 2**depth - 1``, tight (there is no pitch).  ``layout``:
+    "rgb48" (interleaved R G B: the bytes of a uint16 ``[H,W,3]`` array), "bgr48" (B first: what OpenCV returns for a 16-bit image) or
+    "gbrp" (three planes ``[H,W]`` in the order G, B, R).  The arithmetic is rgb16.py's (``atmvfi_rgb16_decode`` / ``_encode``): the
+    network sees ``min(q, top) / top`` and produced samples are ``clip(rint(x * top))``.  Frames travel as the caller's arrays: any
+    contiguous uint16 array of ``3 H W`` samples (``[H,W,3]``, ``[3,H,W]``, 1-D).  The loops keep the depth always (``keep_depth=True``)."""
+    height: int
+    width: int
+    depth: int = 16
+    layout: str = "rgb48"
+
+    def __post_init__(self):
+        if int(self.height) < 1 or int(self.width) < 1:
+            raise ValueError(f"yuv.DeepRGB: height and width must be at least 1 (got {self.height} x {self.width})")
+        if self.depth not in RGB_DEPTHS:
+            raise ValueError(f"yuv.DeepRGB: depth must be 10, 12 or 16 (got {self.depth!r})")
+        if self.layout not in RGB_LAYOUTS:
+            raise ValueError(f"yuv.DeepRGB: unknown layout {self.layout!r} ({', '.join(RGB_LAYOUTS)})")
+        object.__setattr__(self, "height", int(self.height))
+        object.__setattr__(self, "width", int(self.width))
+        object.__setattr__(self, "depth", int(self.depth))
+
+    steps = (1, 1)              # a window or crop begins anywhere
+    dtype = np.uint16
+    itemsize = 2
+    is_tight = True
+    layout_id = property(lambda self: RGB_LAYOUTS.index(self.layout))
+    top = property(lambda self: (1 << self.depth) - 1)
+
+    @property
+    def frame_samples(self) -> int:
+        return 3 * self.height * self.width
+
+    @property
+    def frame_bytes(self) -> int:
+        return 2 * self.frame_samples
+
+    nbytes = frame_bytes
+
+    def tight(self) -> "DeepRGB":
+        return self
+
+    def cropped(self, h: int, w: int) -> "DeepRGB":
+        return replace(self, height=int(h), width=int(w))
+
+    def check(self, buf, what: str = "rgb16") -> np.ndarray:
+        """``buf`` as the 1-D sample array of one frame of this format (a view), or ``ValueError``."""
+        a = np.asarray(buf)
+        if a.dtype != np.uint16 or a.size != self.frame_samples or not a.flags.c_contiguous:
+            raise ValueError(f"{what}: a contiguous uint16 {self.layout} frame of {self.frame_samples} samples "
+                             f"({self.height} x {self.width}, depth {self.depth}) expected, got {a.dtype} {tuple(a.shape)}")
+        return a.reshape(-1)
+
+
+def deep_rgb_refusals(caller: str, pixfmt, keep_depth, active=None, shutter=None):
+    """What a ``DeepRGB`` stream does not go with (``ValueError``); any other ``pixfmt``, or none, passes."""
+    if not isinstance(pixfmt, DeepRGB):
+        return
+    if not keep_depth:
+        raise ValueError(f"{caller}: a DeepRGB pixfmt runs with the depth kept only: pass keep_depth=True (no 8-bit down-conversion of "
+                         "RGB is defined; dithering is the caller's business)")
+    if active is not None:
+        raise ValueError(f"{caller}: active does not go with a DeepRGB pixfmt (composing deep frames needs a 16-bit frame_compose: a follow-up)")
+    if shutter is not None:
+        raise ValueError(f"{caller}: shutter does not go with a DeepRGB pixfmt (a deep blend needs a 16-bit resolve: a follow-up)")
 
 
 @functools.lru_cache(maxsize=64)

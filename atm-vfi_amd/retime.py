@@ -254,7 +254,8 @@ def interpolate_video_retimed(frames, model, fps_in, fps_out, levels: int = 3, d
 
     ``divisor``, ``tta``, ``pool``, ``pixfmt`` and ``keep_depth`` as in ``multiframe.interpolate_video_nx`` (with a 10-bit ``pixfmt``
     and ``keep_depth`` the resident uint8 RGB frame is made only when ``dedup`` or ``scene`` needs it; a ``yuv.Packed`` is taken as
-    there: unpacked behind the upload, packed in front of the download).  There is no ``time_interval``.
+    there: unpacked behind the upload, packed in front of the download; a ``yuv.DeepRGB`` as there too: ``keep_depth=True`` only, the
+    8-bit probe picture made when ``dedup`` or ``scene`` needs it, not with ``active`` or ``shutter``).  There is no ``time_interval``.
     A model without the HIP backend gets the same frames through torch and the numpy twins.  ``report`` (a dict): filled with
     ``"outputs"``, ``"interpolated"`` and ``"forwards"`` (the recursion nodes evaluated: pairs through the network, the second pass of
     flip-TTA not counted) of the run.
@@ -281,6 +282,8 @@ def interpolate_video_retimed(frames, model, fps_in, fps_out, levels: int = 3, d
 
     The rates and ``levels`` are checked at the call; ``ValueError`` as ``retime_slots`` raises it."""
     fi, fo, levels = _check_rates(fps_in, fps_out, levels)
+    from .pixfmt import deep_rgb_refusals
+    deep_rgb_refusals("interpolate_video_retimed", pixfmt, keep_depth, active=active, shutter=shutter)
     if active is not None and shutter is not None:
         raise ValueError("interpolate_video_retimed: active does not go with shutter (a blurred output mixes whole frames)")
     if shutter is not None:

@@ -23,7 +23,7 @@ class Stream(NamedTuple):
     crop_rgb: Callable                               # uint8 [H,W,3] -> its window
     original: Callable                               # the caller's own array -> what is yielded for it
     out_fmt: object                                  # the ``yuv.Format`` of produced frames (None: uint8 RGB)
-    deep: bool                                       # a 10-bit ``pixfmt`` with ``keep_depth``
+    deep: bool                                       # a 10-bit ``pixfmt`` with ``keep_depth``; a ``yuv.DeepRGB`` always
     isBGR: bool                                      # (a ``pixfmt`` overrides it: False)
     packed: object = None                            # a ``yuv.Packed`` stream: the tight layout produced frames are packed into
 
@@ -47,7 +47,8 @@ def open_stream(first, crop, pixfmt, keep_depth, isBGR, caller: str) -> Stream:
     err = None if crop is None else yuv._origin_error(caller, pixfmt, y0, x0, "crop")      # (a multiple of the subsampling step)
     if err is not None:
         raise err
-    deep = bool(keep_depth) and pixfmt.depth == 10
+    yuv.deep_rgb_refusals(caller, pixfmt, keep_depth)
+    deep = bool(keep_depth) and pixfmt.depth > 8
     # (a padded yuv.Surface: originals lose the padding)
     original = (lambda f: f) if (whole and yuv.passes_through(pixfmt)) else (lambda f: yuv.crop(f, pixfmt, y0, x0, h, w))
     out = yuv.out_format(pixfmt, deep).cropped(h, w)
@@ -93,7 +94,9 @@ class _Uploader:
     copy stream behind the copy and fills the slot's resident uint8 RGB frame ``d`` -- what the probes, ``take`` and everything
     downstream read, as for an RGB upload.  ``deep`` (a 10-bit ``pixfmt`` with ``keep_depth``): ``take`` hands the uploaded I420 bytes
     themselves to ``convert`` (``atmvfi_yuv420p10_to_f32`` decodes them into the pool slot: no 8-bit round trip); the uint8 RGB frame is
-    made only for a signature (or a difference).
+    made only for a signature (or a difference).  A ``yuv.DeepRGB`` ``pixfmt`` is always ``deep``: the slot's ``yuv`` bytes are the
+    uploaded RGB frame, ``atmvfi_rgb16_decode`` decodes them into the pool slot and, for a signature or a difference, makes the 8-bit
+    probe picture ``d`` on the copy stream.
 
     The probes.  Each is computed ONCE per frame, on the copy stream right behind the copy that brought the frame, into int32 words of
     the slot; the words follow into a pinned twin and an event is recorded.  The reader of that name waits for the event -- recorded

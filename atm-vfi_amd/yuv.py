@@ -39,7 +39,12 @@ frame of ``packed.planar``, with no arithmetic; bytes and component slots that h
 as zero.  ``interpolate_video_nx``, ``interpolate_video_retimed`` and ``interpolate_raw`` take a ``Packed`` as ``pixfmt``: inside, the
 stream is the planar one; ``surface_of`` knows uyvy422, yuyv422, y210le and v210.
 
-``Format``, ``Surface``, ``Packed`` and ``as_surface`` are defined in the leaf module ``pixfmt.py`` (hip_ops.py validates against them) and
+``DeepRGB(height, width, depth, layout)`` (``atmvfi_rgb16_decode`` / ``atmvfi_rgb16_encode``, csrc/rgb16.hip; twins in rgb16.py): RGB
+frames above 8 bits -- rgb48, bgr48 and gbrp at 10, 12 or 16 bit -- as ``pixfmt`` of every loop, always with the depth kept
+(``keep_depth=True``; there is no 8-bit down-conversion rule).  ``decode_numpy`` (the 8-bit probe picture), ``decode_numpy_f32``,
+``encode_numpy`` and ``crop`` hand such a format to rgb16.py; ``surface_of`` knows rgb48le, bgr48le, gbrp10le, gbrp12le and gbrp16le.
+
+``Format``, ``Surface``, ``Packed``, ``DeepRGB`` and ``as_surface`` are defined in the leaf module ``pixfmt.py`` (hip_ops.py validates against them) and
 re-exported here; ``interpolate_y4m`` and ``interpolate_raw`` are front ends of one stream driver."""
 from __future__ import annotations
 
@@ -50,8 +55,9 @@ from typing import Iterator, Optional
 
 import numpy as np
 
-from .pixfmt import (CHROMAS, MATRICES, PACKED_LAYOUTS, SITINGS, SUBSAMPLINGS, Format, Packed, Surface, _layout_name,  # noqa: F401
-                     _only_420, _origin_error, _tight_surface, as_surface)
+from .pixfmt import (CHROMAS, MATRICES, PACKED_LAYOUTS, RGB_DEPTHS, RGB_LAYOUTS, SITINGS, SUBSAMPLINGS, DeepRGB, Format, Packed,  # noqa: F401
+                     Surface, _layout_name, _only_420, _origin_error, _tight_surface, as_surface, deep_rgb_refusals)
+from . import rgb16
 
 KR_KB = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}
 SHIFT = 14
@@ -101,6 +107,8 @@ def planes(buf, fmt):
 def out_format(pixfmt, deep: bool):
     """What the loops produce for input of ``pixfmt``: the format itself with the depth kept, its 8-bit form otherwise; a ``Surface``
     without its padding (P010 in: P010 out with ``deep``, NV12 out without)."""
+    if isinstance(pixfmt, DeepRGB):         # (always with the depth kept: the loops refuse anything else)
+        return pixfmt
     if isinstance(pixfmt, (Surface, Packed)):
         return pixfmt.tight() if deep else pixfmt.as_8bit()
     return pixfmt if deep else pixfmt.as_8bit()
@@ -246,7 +254,11 @@ def _decode_window(buf, fmt: Format, y0: int, x0: int, h: int, w: int, keep: boo
 
 
 def decode_numpy(buf, fmt: Format, bgr: bool = False) -> np.ndarray:
-    """Packed I420 frame -> uint8 [H,W,3] RGB (BGR if ``bgr``): the bits of ``atmvfi_yuv420_to_rgb``'s ``dst_u8``."""
+    """Packed I420 frame -> uint8 [H,W,3] RGB (BGR if ``bgr``): the bits of ``atmvfi_yuv420_to_rgb``'s ``dst_u8``.  A ``DeepRGB``
+    frame: its 8-bit probe picture (``rgb16.probe_numpy``)."""
+    if isinstance(fmt, DeepRGB):
+        q = rgb16.probe_numpy(buf, fmt)
+        return np.ascontiguousarray(q[:, :, ::-1]) if bgr else q
     q = _decode_window(buf, fmt, 0, 0, fmt.height, fmt.width)
     return np.ascontiguousarray(q[:, :, ::-1] if bgr else q).astype(np.uint8)
 
@@ -276,7 +288,9 @@ def window_numpy(buf, fmt: Format, mode: int, y0: int, x0: int, h: int, w: int) 
 def decode_numpy_f32(buf, fmt: Format, window=None) -> np.ndarray:
     """Packed 10-bit I420 frame -> fp32 [h,w,3] RGB = q / 1023, the depth kept: the bits of ``atmvfi_yuv420p10_to_f32`` (without
     padding).  ``window=(y0, x0, h, w)`` (even origin, as ``crop``): that window of the whole frame's decode -- chroma neighbours
-    are the frame's, not the window's."""
+    are the frame's, not the window's.  A ``DeepRGB`` frame: ``rgb16.decode_numpy_f32`` (q / top; any origin)."""
+    if isinstance(fmt, DeepRGB):
+        return rgb16.decode_numpy_f32(buf, fmt, window=window)
     if fmt.depth != 10:
         raise ValueError("decode_numpy_f32: a 10-bit format expected (8-bit frames decode with decode_numpy)")
     fmt.planes(buf)                                 # the frame is checked before the window
@@ -293,7 +307,10 @@ def decode_numpy_f32(buf, fmt: Format, window=None) -> np.ndarray:
 def encode_numpy(rgb, fmt: Format, bgr: bool = False) -> np.ndarray:
     """uint8 [H,W,3] RGB (BGR if ``bgr``) -> packed 8-bit I420 frame (1-D uint8): the bits of ``atmvfi_rgb_to_yuv420``.  For a 10-bit
     ``fmt``: fp32 [H,W,3] RGB in units of 1 (finite; values outside [0, 1] clamp) -> packed 10-bit frame (1-D uint16), the pixel
-    ``clip(rint(fl32(x * 1023)), 0, 1023)``: the bits of ``atmvfi_f32_to_yuv420p10``; a uint8 source is refused."""
+    ``clip(rint(fl32(x * 1023)), 0, 1023)``: the bits of ``atmvfi_f32_to_yuv420p10``; a uint8 source is refused.  A ``DeepRGB``
+    format: ``rgb16.encode_numpy`` of an fp32 source."""
+    if isinstance(fmt, DeepRGB):
+        return rgb16.encode_numpy(rgb, fmt)
     rgb = np.asarray(rgb)
     deep = fmt.depth == 10 and rgb.dtype == np.float32
     if fmt.depth != 8 and not deep:
@@ -337,6 +354,8 @@ def encode_numpy(rgb, fmt: Format, bgr: bool = False) -> np.ndarray:
 def crop(buf, fmt: Format, y0: int, x0: int, h: int, w: int) -> np.ndarray:
     """The h x w window at (y0, x0) of a packed frame as a packed frame of ``fmt.cropped(h, w)``: plane crops, the samples untouched.
     The origin must be even (a chroma sample covers two luma rows and columns)."""
+    if isinstance(fmt, DeepRGB):            # (any origin)
+        return rgb16.crop(buf, fmt, y0, x0, h, w)
     y0, x0, h, w = int(y0), int(x0), int(h), int(w)
     err = _origin_error("yuv.crop", fmt, y0, x0, "crop")
     if err is not None:
@@ -700,6 +719,11 @@ def _interpolate_stream(who, open_reader, open_writer, model, kw, *, factor, sce
         raise ValueError(f"{who}: fps_out and time_interval do not go together")
     rd = open_reader()
     pixfmt, wr, n_in, report = rd.fmt, None, [0], {}
+    try:
+        deep_rgb_refusals(who, pixfmt, keep_depth, active=kw.get("active"), shutter=shutter)
+    except ValueError:
+        rd.close()
+        raise
 
     def counted():
         for f in rd:
@@ -711,7 +735,7 @@ def _interpolate_stream(who, open_reader, open_writer, model, kw, *, factor, sce
         else:
             _, rate, levels = _check_rates(rd.fps, fps_out, levels)
         _, _, oh, ow = centre_window(pixfmt.height, pixfmt.width, kw.get("crop"))
-        deep = bool(keep_depth) and pixfmt.depth == 10
+        deep = bool(keep_depth) and pixfmt.depth > 8
         src_out = pixfmt.cropped(oh, ow)            # (a Surface's is tight)
         wr = open_writer(rd, src_out if deep else src_out.as_8bit(), rate)
         if fps_out is not None:
@@ -785,12 +809,20 @@ PIX_FMTS = {"nv12": ("uv", 8, False), "nv21": ("vu", 8, False), "p010le": ("uv",
 PIX_FMTS_SUB = {"yuv422p": (8, "422"), "yuv444p": (8, "444"), "yuv422p10le": (10, "422"), "yuv444p10le": (10, "444")}
 # the packed 4:2:2 names -> (layout, depth).  (v210 is a codec to ffmpeg, ``-c:v v210 -f rawvideo``, not a ``-pix_fmt``)
 PIX_FMTS_PACKED = {"uyvy422": ("uyvy", 8), "yuyv422": ("yuy2", 8), "y210le": ("y210", 10), "v210": ("v210", 10)}
+# the deep RGB names -> (layout, depth)
+PIX_FMTS_RGB = {"rgb48le": ("rgb48", 16), "bgr48le": ("bgr48", 16), "gbrp10le": ("gbrp", 10), "gbrp12le": ("gbrp", 12), "gbrp16le": ("gbrp", 16)}
 
 
 def surface_of(pix_fmt: str, h: int, w: int, pitch=None, **format_kw) -> Surface:
     """ffmpeg's ``-pix_fmt`` name (nv12, nv21, p010le, yuv420p, yuv420p10le, yuv422p, yuv444p, yuv422p10le, yuv444p10le) -> the
     ``Surface``; ``pitch`` (bytes): the luma rows' and the interleaved chroma rows', planar chroma rows half of it (4:4:4: all of it).
-    uyvy422, yuyv422, y210le and v210 -> the ``Packed`` (``pitch``: its rows')."""
+    uyvy422, yuyv422, y210le and v210 -> the ``Packed`` (``pitch``: its rows').  rgb48le, bgr48le, gbrp10le, gbrp12le and gbrp16le ->
+    the ``DeepRGB`` (tight frames only: a ``pitch`` or a format keyword is refused)."""
+    if pix_fmt in PIX_FMTS_RGB:
+        if pitch is not None or format_kw:
+            raise ValueError(f"yuv.surface_of: {pix_fmt} frames are tight RGB: no pitch, matrix, range or siting goes with them")
+        layout, depth = PIX_FMTS_RGB[pix_fmt]
+        return DeepRGB(h, w, depth=depth, layout=layout)
     if pix_fmt in PIX_FMTS_PACKED:
         layout, depth = PIX_FMTS_PACKED[pix_fmt]
         return Packed(Format(h, w, depth=depth, subsampling="422", **format_kw), layout, pitch)
@@ -799,7 +831,7 @@ def surface_of(pix_fmt: str, h: int, w: int, pitch=None, **format_kw) -> Surface
         cp = None if pitch is None else (int(pitch) if sub == "444" else int(pitch) // 2)
         return Surface(Format(h, w, depth=depth, subsampling=sub, **format_kw), "planar", False, pitch, cp)
     if pix_fmt not in PIX_FMTS:
-        raise ValueError(f"yuv.surface_of: unknown pixel format {pix_fmt!r} ({', '.join(list(PIX_FMTS) + list(PIX_FMTS_SUB) + list(PIX_FMTS_PACKED))})")
+        raise ValueError(f"yuv.surface_of: unknown pixel format {pix_fmt!r} ({', '.join(list(PIX_FMTS) + list(PIX_FMTS_SUB) + list(PIX_FMTS_PACKED) + list(PIX_FMTS_RGB))})")
     chroma, depth, msb = PIX_FMTS[pix_fmt]
     cp = None if pitch is None else (int(pitch) // 2 if chroma == "planar" else int(pitch))
     return Surface(Format(h, w, depth=depth, **format_kw), chroma, msb, pitch, cp)
@@ -811,7 +843,7 @@ def interpolate_raw(src, dst, model, surface, fps, factor: int = 2, scene=None, 
     frames of ``surface.tight().cropped(h, w)`` in ``dst`` (the 8-bit counterpart for 10-bit input without ``keep_depth``, originals
     converted on the host), at ``fps * factor`` or at ``fps_out``.  Every keyword is ``interpolate_y4m``'s (there is no ``matrix``: the
     surface's format names it); the same dict is returned."""
-    surface = surface if isinstance(surface, Packed) else as_surface(surface)
+    surface = surface if isinstance(surface, (Packed, DeepRGB)) else as_surface(surface)
     return _interpolate_stream("interpolate_raw", lambda: RawReader(src, surface, fps), lambda rd, out, rate: RawWriter(dst, out), model, kw,
                                factor=factor, scene=scene, tta=tta, interpolator=interpolator, keep_depth=keep_depth, fps_out=fps_out,
                                levels=levels, dedup=dedup, shutter=shutter)

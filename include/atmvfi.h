@@ -792,6 +792,36 @@ int atmvfi_yuv_sub_encode(const void* src_u8, int bgr, const float* src, int Hp,
 int atmvfi_yuv_unpack(const void* packed, int H, int W, int layout, int64_t pitch /*0: default*/, void* planar, void* stream);
 int atmvfi_yuv_pack(const void* planar, int H, int W, int layout, void* packed /*default pitch*/, void* stream);
 
+/* Deep RGB frames, 10 / 12 / 16 bit (rgb16.hip; ABI 0.25; atm-vfi_amd/pixfmt.py: DeepRGB; host twins atm-vfi_amd/rgb16.py; per-sample model
+ * tests/cpu_rgb16.py).  Nothing of the reference, whose scripts read 8-bit images.  A frame is tight: 3 H W little-endian uint16 samples,
+ * LSB-aligned, top = 2^depth - 1.
+ *   layout 0 rgb48 : interleaved R G B (the bytes of a uint16 [H,W,3] array)
+ *   layout 1 bgr48 : interleaved B G R
+ *   layout 2 gbrp  : three planes [H,W] in the order G, B, R (ffmpeg's gbrp10le / gbrp12le / gbrp16le)
+ * atmvfi_rgb16_decode.  q' = min(q, top): bits above the depth are never trusted.  The window (y0, x0, h, w) of the frame, any origin, as
+ *   dst, fp32 planar RGB [3,Hp,Wp] = q' / top with the bits of the fp32 division (atmvfi_frame_u8_to_f32's pixel with top in place of
+ *   255), the window at (pad_top, pad_left), replicate padding of the window's own edge pixels -- and / or dst_u8, the frame's 8-bit
+ *   PROBE picture uint8 [h,w,3] RGB = q' >> (depth - 8), on which atmvfi_frame_signature and atmvfi_frame_difference run unchanged (cut
+ *   and duplicate decisions are those of the 8-bit picture obtained by truncation).  Without dst, Hp / Wp / pad_* are not read.
+ * atmvfi_rgb16_encode.  p = clip(rint(fl32(x * top)), 0, top), half to even, of the H x W picture at (pad_top, pad_left) of src (finite
+ *   values; outside [0, 1] they clamp; atmvfi_frame_f32_to_u8's pixel with top in place of 255), written in the layout's order; nothing
+ *   of src outside the picture is read.  rint(fl32(fl32(q / top) * top)) == q for every code of the three depths, and at depth 16 the
+ *   decode of q = 257 b is fl32(b / 255), atmvfi_frame_u8_to_f32's value for b.
+ * Refused on the host before any launch (ATMVFI_EINVAL): a null source (encode: a null destination); decode with both outputs NULL; a
+ *   depth other than 10, 12, 16; an unknown layout; sizes below 1; a window outside the frame; a canvas that does not hold the picture
+ *   plus padding; a frame pointer that is not 2-byte or a canvas pointer that is not 4-byte aligned; a work-item count beyond 2^30.
+ * Any other geometry and alignment is accepted.  A lane owns four adjacent pixels of a row (decode: of the padded canvas, so padding is
+ *   written by the lanes that own it).  Aligned path -- the frame 8-byte aligned, W % 4 == 0 (decode: x0 % 4 == 0 and w % 4 == 0 too), the
+ *   canvas 16-byte aligned with Wp % 4 == 0 and pad_left % 4 == 0, dst_u8 4-byte aligned: one 16-byte access per fp32 plane, three 8-byte
+ *   accesses of an interleaved frame (gbrp: one per plane), three dwords of the probe picture.  General path: 2-byte accesses of the frame
+ *   and scalar accesses of the canvas.  Both give the same bits.  One launch, grid-stride, every output byte written by exactly one
+ *   lane: vector stores only, no atomics, nothing pre-zeroed, no LDS. */
+int atmvfi_rgb16_decode(const void* src, int H, int W, int depth, int layout, int y0, int x0, int h, int w,
+                        float* dst /*[3,Hp,Wp] or NULL*/, int Hp, int Wp, int pad_top, int pad_left,
+                        void* dst_u8 /*[h,w,3] RGB or NULL*/, void* stream);
+int atmvfi_rgb16_encode(const float* src /*[3,Hp,Wp]*/, int Hp, int Wp, int pad_top, int pad_left,
+                        void* dst, int H, int W, int depth, int layout, void* stream);
+
 /* mean |a - b| per sample: global_alignmentness (network_base.py:560-561).  Two passes with a fixed summation order -- the result is
  * run-to-run bit-identical (the ensemble's pick compares these means) -- through `workspace`: at least
  * atmvfi_l1_mean_workspace_floats(B, per_sample) floats of scratch, the caller's. */

@@ -5,7 +5,9 @@ repacked on the host.  The output has the same pixel format without row padding;
 counterpart (p010le -> nv12), or with ``--keep-depth`` at 10 bits.  Packed 4:2:2 capture frames travel the same way: ``--pix-fmt
 uyvy422|yuyv422|y210le|v210`` (unpacked and packed on the GPU; without ``--keep-depth`` y210le is written as yuyv422 and v210 as
 uyvy422).  ffmpeg writes v210 as a codec, not as a ``-pix_fmt``: ``ffmpeg -i in.mov -c:v v210 -f rawvideo -``; its rows are padded to
-128 bytes per 48 pixels, which is this tool's default pitch for v210.  ``-`` reads standard input / writes standard output
+128 bytes per 48 pixels, which is this tool's default pitch for v210.  Deep RGB -- ``--pix-fmt rgb48le|bgr48le|gbrp10le|gbrp12le|gbrp16le``,
+tight frames -- runs with ``--keep-depth`` only (no 8-bit down-conversion of RGB is defined) and without ``--active`` / ``--shutter``
+(``ffmpeg -i in.mov -f rawvideo -pix_fmt gbrp12le - | interp_raw.py - out.rgb --pix-fmt gbrp12le --size 1920x1080 --fps 24 --keep-depth``).  ``-`` reads standard input / writes standard output
 (``ffmpeg -i in.mp4 -f rawvideo -pix_fmt nv12 - | interp_raw.py - out.nv12 --pix-fmt nv12 --size 1920x1080 --fps 30000/1001 --ckpt ...``).
 
     python tools/interp_raw.py IN OUT --pix-fmt FMT --size WxH --fps R [--pitch N] [--matrix auto|bt601|bt709] [--siting centre|left]
@@ -30,7 +32,7 @@ def main():
     ap.add_argument("src")
     ap.add_argument("dst")
     ap.add_argument("--pix-fmt", required=True, choices=("nv12", "nv21", "p010le", "yuv420p", "yuv420p10le", "yuv422p", "yuv444p", "yuv422p10le", "yuv444p10le",
-                                                           "uyvy422", "yuyv422", "y210le", "v210"))
+                                                           "uyvy422", "yuyv422", "y210le", "v210", "rgb48le", "bgr48le", "gbrp10le", "gbrp12le", "gbrp16le"))
     ap.add_argument("--size", required=True, metavar="WxH")
     ap.add_argument("--fps", required=True, metavar="R", help="the input's frame rate (e.g. 25 or 30000/1001)")
     ap.add_argument("--pitch", type=int, default=None, metavar="N", help="luma row stride of the input in bytes (default: tight)")
@@ -65,7 +67,14 @@ def main():
         ap.error(f"--size must be WxH (got {a.size!r})")
     yuv = importlib.import_module("atm-vfi_amd.yuv")
     siting = "centre" if a.pix_fmt.startswith("yuv444p") else a.siting
-    surface = yuv.surface_of(a.pix_fmt, h, w, pitch=a.pitch, matrix=a.matrix, siting=siting, full_range=a.full_range)
+    if a.pix_fmt in yuv.PIX_FMTS_RGB:       # (tight RGB: no matrix, range or siting; what the loops refuse is refused before the model is made)
+        try:
+            surface = yuv.surface_of(a.pix_fmt, h, w, pitch=a.pitch)
+            yuv.deep_rgb_refusals("interp_raw", surface, a.keep_depth, active=a.active or None, shutter=a.shutter)
+        except ValueError as e:
+            sys.exit(str(e))
+    else:
+        surface = yuv.surface_of(a.pix_fmt, h, w, pitch=a.pitch, matrix=a.matrix, siting=siting, full_range=a.full_range)
     if not torch.cuda.is_available():
         sys.exit("interp_raw: no GPU")
     pkg = importlib.import_module("atm-vfi_amd")
