@@ -609,6 +609,186 @@ __global__ __launch_bounds__(256) void pack_frames_kernel(const float* __restric
 }
 
 // ---------------------------------------------------------------------------------------
+// Half-resolution motion (include/atmvfi.h, ABI 0.26; atm-vfi_amd/scaled.py holds the definition and the numpy twins).
+// frame_half: the 2 x 2 box average ((a + b) + (c + d)) * 0.25f.  VEC: a lane owns four adjacent outputs of a row (two 16-byte loads per
+// source row, one 16-byte store); else one output, scalar accesses.  The same expression per output: the same bits.
+// ---------------------------------------------------------------------------------------
+template <bool VEC>
+__global__ __launch_bounds__(256) void frame_half_kernel(const float* __restrict__ src, float* __restrict__ dst, long long rows, int w) {
+    fp16_saturate_on();
+    const int W = 2 * w;
+    if constexpr (VEC) {
+        const int wv = w >> 2;                                   // W % 8 == 0
+        const long long total = rows * wv;                       // rows: planes * h output rows; output row r reads source rows 2r, 2r + 1
+        for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
+            const long long r = idx / wv;
+            const int v = (int)(idx - r * wv);
+            const float* s = src + 2 * r * W + 8 * v;
+            const f32x4 t0 = *reinterpret_cast<const f32x4*>(s), t1 = *reinterpret_cast<const f32x4*>(s + 4);
+            const f32x4 b0 = *reinterpret_cast<const f32x4*>(s + W), b1 = *reinterpret_cast<const f32x4*>(s + W + 4);
+            f32x4 o;
+            o.x = ((t0.x + t0.y) + (b0.x + b0.y)) * 0.25f;
+            o.y = ((t0.z + t0.w) + (b0.z + b0.w)) * 0.25f;
+            o.z = ((t1.x + t1.y) + (b1.x + b1.y)) * 0.25f;
+            o.w = ((t1.z + t1.w) + (b1.z + b1.w)) * 0.25f;
+            *reinterpret_cast<f32x4*>(dst + r * w + 4 * v) = o;
+        }
+    } else {
+        const long long total = rows * w;
+        for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
+            const long long r = idx / w;
+            const int x = (int)(idx - r * w);
+            const float* s = src + 2 * r * W + 2 * x;
+            dst[idx] = ((s[0] + s[1]) + (s[W] + s[W + 1])) * 0.25f;
+        }
+    }
+}
+
+// synth_up2: full-size synthesis from a half-size forward.  The workgroup's 32 x 8 output tile (tile_pixel) reads the half-size pixels
+// of columns X0/2 - 1 .. X0/2 + 16 and rows Y0/2 - 1 .. Y0/2 + 4: lanes 0 .. 107 build them in LDS as eight interleaved floats
+// f0x f0y f1x f1y | m rR rG rB (r: the residual it_sum - blend, warp_blend's expression), every lane blends its four with the 0.25 / 0.75
+// rule, and from there on the kernel is warp_blend_tiled_kernel's: taps, boxes, staged or gathered samples.  The half-size pixels live in
+// the first 3.4 KiB of source box 0, which is staged only after the barrier that follows their last read.  STAGED = false: gathers throughout
+// (any width and alignment; the default: it measured faster); the arithmetic is shared, so the two instances give the same bits.
+// Tried and dropped, both slower at 2176 x 4096 (README, "Half-resolution motion"): a half-size pre-pass that interleaves the eight maps
+// into a workspace (it moves more bytes than the 1.7-fold re-reading it saves), and a lane per 2 x 2 output quad on that pre-pass.
+struct SynthUp2Args {
+    const float *it_sum, *it0, *it1, *flow0, *flow1, *m1, *store0, *store1;
+    float *dst, *f0o, *f1o, *mo;
+    unsigned char* dst_u8;
+    int h, w, pad_top, pad_left, hh, ww, bgr;
+    int s0[16], s1[16];
+};
+constexpr int UP_W = WT_W / 2 + 2, UP_H = WT_H / 2 + 2;       // half-size neighbourhood of an output tile
+static_assert(UP_W * UP_H <= 256 && UP_W * UP_H * 8 <= 3 * WB_PLANE, "the neighbourhood is built by one pass of the workgroup inside box 0");
+
+__device__ __forceinline__ f32x4 up2_blend(float wy0, float wy1, float wx0, float wx1, f32x4 v00, f32x4 v01, f32x4 v10, f32x4 v11) {
+    return wy0 * (wx0 * v00 + wx1 * v01) + wy1 * (wx0 * v10 + wx1 * v11);
+}
+
+// sample_plane with its four loads issued unconditionally: a tap outside the image reads the nearest pixel inside and is dropped by a
+// select, so the sum is sample_plane's, bit for bit, for any source values.  sample_plane's `if (in) v += ...` compiles to one masked
+// block per tap with a wait in each; over two sources and three planes that was a chain of dependent memory latencies (counter passes on
+// the MI355X: 88 % of the direct instance's wave cycles were waits while HBM ran at 27 %); here the 24 loads of a pixel are in flight together.
+__device__ __forceinline__ float sample_plane_all(const float* __restrict__ p, const Taps& t, int W, int H) {
+    const int xa = t.x0 < 0 ? 0 : (t.x0 > W - 1 ? W - 1 : t.x0), xb = t.x0 + 1 < 0 ? 0 : (t.x0 + 1 > W - 1 ? W - 1 : t.x0 + 1);
+    const int ya = t.y0 < 0 ? 0 : (t.y0 > H - 1 ? H - 1 : t.y0), yb = t.y0 + 1 < 0 ? 0 : (t.y0 + 1 > H - 1 ? H - 1 : t.y0 + 1);
+    const float* ra = p + (long long)ya * W;
+    const float* rb = p + (long long)yb * W;
+    const float b00 = ra[xa], b01 = ra[xb], b10 = rb[xa], b11 = rb[xb];
+    float v = 0.f;                                        // (each sum is formed, then selected: a conditional sum would pull its load into a branch)
+    const float v0 = v + b00 * t.w00;
+    v = t.in00 ? v0 : v;
+    const float v1 = v + b01 * t.w01;
+    v = t.in01 ? v1 : v;
+    const float v2 = v + b10 * t.w10;
+    v = t.in10 ? v2 : v;
+    const float v3 = v + b11 * t.w11;
+    v = t.in11 ? v3 : v;
+    return v;
+}
+
+template <bool STAGED>
+__global__ __launch_bounds__(256) void synth_up2_kernel(const SynthUp2Args p) {
+    fp16_saturate_on();
+    __shared__ __attribute__((aligned(16))) float lds[STAGED ? 2 * 3 * WB_PLANE : UP_W * UP_H * 8];
+    __shared__ int bx[2][4];
+    float* const tile[2] = {lds, lds + (STAGED ? 3 * WB_PLANE : 0)};
+    const int tid = threadIdx.x;
+    const int H = 2 * p.h, W = 2 * p.w;
+    const long long hw = (long long)H * W, qhw = (long long)p.h * p.w;
+    int b, x, y;
+    bool live;
+    tile_pixel(H, W, b, x, y, live);
+    const int ox = ((x - (tid & (WT_W - 1))) >> 1) - 1, oy = ((y - (tid >> 5)) >> 1) - 1;      // half-size origin of the neighbourhood
+    float* up = tile[0];
+    if (tid < 2) box_reset(bx[tid]);
+    if (tid < UP_W * UP_H) {
+        const int r = tid / UP_W, qy = oy + r, qx = ox + (tid - r * UP_W);
+        if (qx >= 0 && qx < p.w && qy >= 0 && qy < p.h) {
+            const long long q = (long long)qy * p.w + qx;
+            const float* f0 = p.flow0 + (long long)b * 2 * qhw + q;
+            const float* f1 = p.flow1 + (long long)b * 2 * qhw + q;
+            const float m1 = p.m1[(long long)b * qhw + q];
+            float res[3];
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {
+                const long long o = ((long long)b * 3 + ch) * qhw + q;
+                res[ch] = p.it_sum[o] - (m1 * p.it0[o] + (1.0f - m1) * p.it1[o]);
+            }
+            *reinterpret_cast<f32x4*>(up + tid * 8) = (f32x4){f0[0], f0[qhw], f1[0], f1[qhw]};
+            *reinterpret_cast<f32x4*>(up + tid * 8 + 4) = (f32x4){m1, res[0], res[1], res[2]};
+        }
+    }
+    __syncthreads();
+    // the four half-size pixels of this output (a lane outside the image takes the last row / column's: it only has to stay in the LDS block)
+    const int xc = x < W ? x : W - 1, yc = y < H ? y : H - 1;
+    const bool xodd = xc & 1, yodd = yc & 1;
+    const int c0 = xodd ? (xc - 1) >> 1 : ((xc >> 1) - 1 < 0 ? 0 : (xc >> 1) - 1), c1 = xodd ? (((xc + 1) >> 1) > p.w - 1 ? p.w - 1 : (xc + 1) >> 1) : xc >> 1;
+    const int r0 = yodd ? (yc - 1) >> 1 : ((yc >> 1) - 1 < 0 ? 0 : (yc >> 1) - 1), r1 = yodd ? (((yc + 1) >> 1) > p.h - 1 ? p.h - 1 : (yc + 1) >> 1) : yc >> 1;
+    const float wx0 = xodd ? 0.75f : 0.25f, wx1 = xodd ? 0.25f : 0.75f, wy0 = yodd ? 0.75f : 0.25f, wy1 = yodd ? 0.25f : 0.75f;
+    const float* u00 = up + ((r0 - oy) * UP_W + (c0 - ox)) * 8;
+    const float* u01 = up + ((r0 - oy) * UP_W + (c1 - ox)) * 8;
+    const float* u10 = up + ((r1 - oy) * UP_W + (c0 - ox)) * 8;
+    const float* u11 = up + ((r1 - oy) * UP_W + (c1 - ox)) * 8;
+    const f32x4 fl = up2_blend(wy0, wy1, wx0, wx1, *reinterpret_cast<const f32x4*>(u00), *reinterpret_cast<const f32x4*>(u01),
+                               *reinterpret_cast<const f32x4*>(u10), *reinterpret_cast<const f32x4*>(u11));
+    const f32x4 mr = up2_blend(wy0, wy1, wx0, wx1, *reinterpret_cast<const f32x4*>(u00 + 4), *reinterpret_cast<const f32x4*>(u01 + 4),
+                               *reinterpret_cast<const f32x4*>(u10 + 4), *reinterpret_cast<const f32x4*>(u11 + 4));
+    const float fx0 = fl.x * 2.0f, fy0 = fl.y * 2.0f, fx1 = fl.z * 2.0f, fy1 = fl.w * 2.0f;
+    const float m = mr.x;
+    const Taps t0 = make_taps((float)x + fx0, (float)y + fy0, W, H);
+    const Taps t1 = make_taps((float)x + fx1, (float)y + fy1, W, H);
+    const float* im0 = p.store0 + (long long)p.s0[b] * 3 * hw;
+    const float* im1 = p.store1 + (long long)p.s1[b] * 3 * hw;
+    StagedBox s0, s1;
+    s0.ok = s1.ok = false;
+    if constexpr (STAGED) {
+        box_add(bx[0], t0, live, W, H);
+        box_add(bx[1], t1, live, W, H);
+        __syncthreads();                                  // also: every lane has read its half-size pixels, box 0 may be overwritten
+        s0 = box_get(bx[0]);
+        s1 = box_get(bx[1]);
+        if (s0.ok) box_stage(tile[0], im0, hw, W, 3, s0, tid);
+        if (s1.ok) box_stage(tile[1], im1, hw, W, 3, s1, tid);
+        __syncthreads();
+    }
+    if (!live) return;
+    const long long pix = (long long)y * W + x;
+    const int wy = y - p.pad_top, wx = x - p.pad_left;
+    const bool in_window = p.dst_u8 && wy >= 0 && wy < p.hh && wx >= 0 && wx < p.ww;
+    int q8[3];
+    float a3[3], c3[3];                                   // every sample before the first store: an output may alias nothing, but the
+#pragma unroll                                            // compiler cannot know, and a store between would split the loads again
+    for (int ch = 0; ch < 3; ++ch) {
+        a3[ch] = s0.ok ? sample_tile(tile[0] + ch * WB_PLANE, t0, s0) : sample_plane_all(im0 + ch * hw, t0, W, H);
+        c3[ch] = s1.ok ? sample_tile(tile[1] + ch * WB_PLANE, t1, s1) : sample_plane_all(im1 + ch * hw, t1, W, H);
+    }
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        const float a = a3[ch], c = c3[ch];
+        const float res = ch == 0 ? mr.y : (ch == 1 ? mr.z : mr.w);
+        const float v = fminf(fmaxf((m * a + (1.0f - m) * c) + res, 0.0f), 1.0f);
+        if (p.dst) p.dst[((long long)b * 3 + ch) * hw + pix] = v;
+        const int q = __float2int_rn(v * 255.0f);        // rint: half to even, as np.round (frame_f32_to_u8)
+        q8[ch] = q < 0 ? 0 : (q > 255 ? 255 : q);
+    }
+    if (in_window) {
+        unsigned char* o = p.dst_u8 + (((long long)b * p.hh + wy) * p.ww + wx) * 3;
+        o[0] = (unsigned char)(p.bgr ? q8[2] : q8[0]);
+        o[1] = (unsigned char)q8[1];
+        o[2] = (unsigned char)(p.bgr ? q8[0] : q8[2]);
+    }
+    if (p.f0o) {
+        p.f0o[((long long)b * 2) * hw + pix] = fx0;
+        p.f0o[((long long)b * 2 + 1) * hw + pix] = fy0;
+        p.f1o[((long long)b * 2) * hw + pix] = fx1;
+        p.f1o[((long long)b * 2 + 1) * hw + pix] = fy1;
+    }
+    if (p.mo) p.mo[(long long)b * hw + pix] = m;
+}
+
+// ---------------------------------------------------------------------------------------
 // Launchers.  Checks that several entry points share are made once, under the caller's name `who`.
 // ---------------------------------------------------------------------------------------
 long long warp_tiles(int B, int H, int W) { return (long long)B * ((H + WT_H - 1) / WT_H) * ((W + WT_W - 1) / WT_W); }
@@ -775,4 +955,89 @@ extern "C" int atmvfi_pack_frames(const float* im0, const float* im1, float* dst
     hipLaunchKernelGGL(pack_frames_kernel, dim3(grid_for(2ll * B * H * W)), dim3(256), 0, (hipStream_t)stream, im0, im1, dst,
                        B, H, W);
     return atmvfi::check_launch("pack_frames");
+}
+
+// ---------------------------------------------------------------------------------------
+// Half-resolution motion: host checks and launches
+// ---------------------------------------------------------------------------------------
+namespace {
+struct ByteRange {
+    const void* p;
+    long long n;
+    const char* name;
+};
+bool ranges_overlap(const ByteRange& a, const ByteRange& b) {
+    const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
+    return a.p && b.p && a.n > 0 && b.n > 0 && a0 < b0 + (uintptr_t)b.n && b0 < a0 + (uintptr_t)a.n;
+}
+bool synth_up2_shape_ok(long long B, long long h, long long w) { return B >= 1 && B <= 16 && h >= 1 && w >= 1 && h < (1 << 24) && w < (1 << 24); }
+}  // namespace
+
+extern "C" int atmvfi_frame_half(const float* src, float* dst, int planes, int H, int W, void* stream) {
+    ATMVFI_REQUIRE(src && dst, ATMVFI_EINVAL, "frame_half: null pointer");
+    ATMVFI_REQUIRE(planes >= 1 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0, ATMVFI_EINVAL,
+                   "frame_half: planes must be positive and H, W even and at least 2 (got %d planes of %d x %d)", planes, H, W);
+    const long long n = (long long)planes * H * W;
+    ATMVFI_REQUIRE(!ranges_overlap({src, n * 4, "src"}, {dst, n, "dst"}), ATMVFI_EINVAL, "frame_half: src and dst overlap");
+    const long long rows = (long long)planes * (H / 2);
+    const int w = W / 2;
+    if (W % 8 == 0 && atmvfi::aligned16(src) && atmvfi::aligned16(dst))
+        hipLaunchKernelGGL(frame_half_kernel<true>, dim3(grid_for(rows * (w / 4))), dim3(256), 0, (hipStream_t)stream, src, dst, rows, w);
+    else
+        hipLaunchKernelGGL(frame_half_kernel<false>, dim3(grid_for(rows * w)), dim3(256), 0, (hipStream_t)stream, src, dst, rows, w);
+    return atmvfi::check_launch("frame_half");
+}
+
+extern "C" int64_t atmvfi_synth_up2_workspace_floats(int B, int h, int w) { return synth_up2_shape_ok(B, h, w) ? 0 : -1; }
+
+extern "C" int atmvfi_synth_up2(const atmvfi_synth_up2_params* p, void* stream) {
+    ATMVFI_REQUIRE(p, ATMVFI_EINVAL, "synth_up2: null parameter block");
+    ATMVFI_REQUIRE(p->it_sum && p->it0 && p->it1 && p->flow0 && p->flow1 && p->m1 && p->store0 && p->store1, ATMVFI_EINVAL, "synth_up2: null input");
+    ATMVFI_REQUIRE(p->B <= 16, ATMVFI_EINVAL, "synth_up2: at most 16 pairs per call (got %d)", p->B);
+    ATMVFI_REQUIRE(synth_up2_shape_ok(p->B, p->h, p->w), ATMVFI_EINVAL, "synth_up2: bad shape (B %d, h %d, w %d)", p->B, p->h, p->w);
+    ATMVFI_REQUIRE(p->S0 >= 1 && p->S1 >= 1, ATMVFI_EINVAL, "synth_up2: empty frame store");
+    ATMVFI_REQUIRE(p->dst_f32 || p->dst_u8, ATMVFI_EINVAL, "synth_up2: no output requested (dst_f32, dst_u8 or both)");
+    ATMVFI_REQUIRE((p->f0_out == nullptr) == (p->f1_out == nullptr), ATMVFI_EINVAL, "synth_up2: the flow outputs come in pairs");
+    const int B = p->B, H = 2 * p->h, W = 2 * p->w;
+    const long long hw = (long long)H * W, qhw = (long long)p->h * p->w;
+    SynthUp2Args a{};
+    for (int b = 0; b < B; ++b) {
+        a.s0[b] = p->slots0 ? p->slots0[b] : b;
+        a.s1[b] = p->slots1 ? p->slots1[b] : b;
+        ATMVFI_REQUIRE(a.s0[b] >= 0 && a.s0[b] < p->S0 && a.s1[b] >= 0 && a.s1[b] < p->S1, ATMVFI_EINVAL,
+                       "synth_up2: pair %d names frames (%d, %d) outside the stores of %d and %d", b, a.s0[b], a.s1[b], p->S0, p->S1);
+    }
+    if (p->dst_u8)
+        ATMVFI_REQUIRE(p->pad_top >= 0 && p->pad_left >= 0 && p->hh >= 1 && p->ww >= 1 && (long long)p->pad_top + p->hh <= H &&
+                           (long long)p->pad_left + p->ww <= W, ATMVFI_EINVAL,
+                       "synth_up2: the window %d x %d at (%d, %d) is outside the %d x %d canvas", p->hh, p->ww, p->pad_top, p->pad_left, H, W);
+    const bool can_stage = W % 4 == 0 && atmvfi::aligned16(p->store0) && atmvfi::aligned16(p->store1);
+    ATMVFI_REQUIRE(p->path >= 0 && p->path <= 2, ATMVFI_EINVAL, "synth_up2: path must be 0 (auto), 1 (gathers) or 2 (staged), got %d", p->path);
+    ATMVFI_REQUIRE(p->path != 2 || can_stage, ATMVFI_EINVAL, "synth_up2: the staged path needs 2w %% 4 == 0 and 16-byte aligned stores (got 2w = %d)", W);
+    const ByteRange in[8] = {{p->it_sum, B * 3 * qhw * 4, "it_sum"}, {p->it0, B * 3 * qhw * 4, "it0"}, {p->it1, B * 3 * qhw * 4, "it1"},
+                             {p->flow0, B * 2 * qhw * 4, "flow0"}, {p->flow1, B * 2 * qhw * 4, "flow1"}, {p->m1, B * qhw * 4, "m1"},
+                             {p->store0, p->S0 * 3 * hw * 4, "store0"}, {p->store1, p->S1 * 3 * hw * 4, "store1"}};
+    const ByteRange out[5] = {{p->dst_f32, B * 3 * hw * 4, "dst_f32"}, {p->dst_u8, p->dst_u8 ? (long long)B * p->hh * p->ww * 3 : 0, "dst_u8"},
+                              {p->f0_out, B * 2 * hw * 4, "f0_out"}, {p->f1_out, B * 2 * hw * 4, "f1_out"}, {p->m_out, B * hw * 4, "m_out"}};
+    for (int o = 0; o < 5; ++o) {
+        for (int i = 0; i < 8; ++i)
+            ATMVFI_REQUIRE(!ranges_overlap(out[o], in[i]), ATMVFI_EINVAL, "synth_up2: %s overlaps %s", out[o].name, in[i].name);
+        for (int j = 0; j < o; ++j)
+            ATMVFI_REQUIRE(!ranges_overlap(out[o], out[j]), ATMVFI_EINVAL, "synth_up2: %s overlaps %s", out[o].name, out[j].name);
+    }
+    const long long tiles = warp_tiles(B, H, W);
+    ATMVFI_REQUIRE(tiles < (1ll << 31), ATMVFI_EINVAL, "synth_up2: grid too large");
+    a.it_sum = p->it_sum; a.it0 = p->it0; a.it1 = p->it1; a.flow0 = p->flow0; a.flow1 = p->flow1; a.m1 = p->m1;
+    a.store0 = p->store0; a.store1 = p->store1;
+    a.dst = p->dst_f32; a.f0o = p->f0_out; a.f1o = p->f1_out; a.mo = p->m_out;
+    a.dst_u8 = (unsigned char*)p->dst_u8;
+    a.h = p->h; a.w = p->w;
+    a.pad_top = p->pad_top; a.pad_left = p->pad_left; a.hh = p->hh; a.ww = p->ww; a.bgr = p->bgr;
+    // path 0 is the gathering instance: measured faster than the staged one at small flows and level with it at large ones
+    // (profiles/scaled_bench.txt); the staged instance runs on request
+    if (p->path == 2)
+        hipLaunchKernelGGL(synth_up2_kernel<true>, dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream, a);
+    else
+        hipLaunchKernelGGL(synth_up2_kernel<false>, dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream, a);
+    return atmvfi::check_launch("synth_up2");
 }

@@ -166,6 +166,9 @@ SIGNATURES = {
     "atmvfi_yuv_pack": (c_i, [c_f, c_i, c_i, c_i, c_f, c_f]),
     "atmvfi_rgb16_decode": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f, c_f]),
     "atmvfi_rgb16_encode": (c_i, [c_f, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f]),
+    "atmvfi_frame_half": (c_i, [c_f, c_f, c_i, c_i, c_i, c_f]),
+    "atmvfi_synth_up2": (c_i, [c_f, c_f]),
+    "atmvfi_synth_up2_workspace_floats": (c_l, [c_i, c_i, c_i]),
     "atmvfi_pack_frames": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_f]),
     "atmvfi_final_residual": (c_i, [c_f, c_f, c_i, c_f, c_f, c_i, c_i, c_i, c_f]),
     "atmvfi_l1_mean": (c_i, [c_f, c_f, c_f, c_i, c_l, c_f, c_l, c_f]),
@@ -179,6 +182,13 @@ SIGNATURES = {
                               ctypes.POINTER(c_i), c_f]),
 }
 SSIM_X_U8, SSIM_X_BGR, SSIM_ROUND_Y, SSIM_ACCUMULATE, SSIM_MSE_F32 = 1, 2, 4, 8, 16     # include/atmvfi.h ATMVFI_SSIM_*
+
+
+class SynthUp2Params(ctypes.Structure):
+    """``atmvfi_synth_up2_params`` of include/atmvfi.h."""
+    _fields_ = ([(n, ctypes.c_void_p) for n in ("it_sum", "it0", "it1", "flow0", "flow1", "m1", "store0", "store1", "slots0", "slots1", "dst_f32",
+                                                 "dst_u8", "f0_out", "f1_out", "m_out", "workspace")]
+                + [(n, ctypes.c_int32) for n in ("B", "h", "w", "S0", "S1", "pad_top", "pad_left", "hh", "ww", "bgr", "path", "reserved")])
 
 
 def load_library(path: str = LIB_PATH, optional=()) -> ctypes.CDLL:
@@ -1954,6 +1964,92 @@ class HipOps:
         hp, wp = src.shape[-2:]
         self._run("frame_rot180", {"bytes": 8.0 * src.numel()}, self.lib.atmvfi_frame_rot180, _ptr(src), _ptr(dst), src.numel() // (hp * wp),
                   hp, wp, self._stream())
+
+    # ---------------------------------------------------------------- half-resolution motion (include/atmvfi.h; twins: scaled.py)
+    def _run_direct(self, name: str, meta: dict, fn, *args):
+        """``_run`` for the entry points that run around a plan's replay, never inside a recording.  (tools/gen_plan_dispatch.py emits a
+        case for every entry point of the header, these included; ``synth_up2``'s parameter block and slot lists are HOST memory read at
+        the call, so a recorded op would hold dangling pointers: recording them needs a redesign, not a flag.)"""
+        if self.recording is not None:
+            raise PlanUnsupported(f"{name} is not part of launch plans")
+        self._run(name, meta, fn, *args)
+
+    def frame_half(self, src, dst):
+        """``dst`` [...,H/2,W/2] = the 2 x 2 box average ``((a + b) + (c + d)) * 0.25`` of the contiguous fp32 planes ``src`` [...,H,W],
+        H and W even (include/atmvfi.h atmvfi_frame_half; the bits of ``scaled.frame_half_numpy``)."""
+        ok = lambda t: isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and t.dim() >= 2
+        if not ok(src) or not ok(dst):
+            raise ValueError("frame_half: src and dst must be contiguous CUDA fp32 tensors [...,H,W] and [...,H/2,W/2]")
+        h, w = src.shape[-2:]
+        if h % 2 or w % 2 or h < 2 or w < 2 or tuple(dst.shape) != tuple(src.shape[:-2]) + (h // 2, w // 2):
+            raise ValueError(f"frame_half: {tuple(src.shape)} -> {tuple(dst.shape)}: H and W must be even and dst [...,H/2,W/2]")
+        self._run_direct("frame_half", {"bytes": 5.0 * src.numel()}, self.lib.atmvfi_frame_half, _ptr(src), _ptr(dst), src.numel() // (h * w), h, w,
+                         self._stream())
+
+    def synth_up2(self, half: dict, store0, store1=None, slots0=None, slots1=None, dst=None, dst_u8=None, window=None, bgr: bool = False,
+                  want=(), path: str = "auto"):
+        """Full-size synthesis from the half-size outputs ``half`` of one forward on ``frame_half``'d frames (its ``im_t_list[0]``,
+        ``I_t_0``, ``I_t_1``, ``opt_flow_0``, ``opt_flow_1``, ``occ_mask1``; batch B <= 16, size h x w): one launch of
+        include/atmvfi.h atmvfi_synth_up2.  ``store0`` / ``store1`` (default: the same) are contiguous fp32 [S,3,2h,2w] frame stores;
+        pair b takes ``store0[slots0[b]]`` and ``store1[slots1[b]]`` (host lists; default b).  ``dst``: fp32 [B,3,2h,2w] or None;
+        ``dst_u8``: uint8 [B,hh,ww,3] or None, the ``window`` = (pad_top, pad_left, hh, ww) of the canvas as ``frame_f32_to_u8``
+        gives it; with neither, ``dst`` is allocated.  ``want``: any of "opt_flow_0", "opt_flow_1", "occ_mask1" at full size.
+        ``path``: "direct" (gathers; "auto" is this one, the faster by measurement) or "staged" (LDS boxes of the sources).  -> dict with "I_t" (``dst``), "I_t_u8" and the wanted maps, as given.
+        ``scaled.synth_up2_numpy`` is the host twin (the same arithmetic; the GPU tests hold the kernel to the fp64 bound, not to its bits)."""
+        names = {"opt_flow_0", "opt_flow_1", "occ_mask1"}
+        if set(want) - names:
+            raise ValueError(f"synth_up2: want takes {sorted(names)}, got {sorted(set(want) - names)}")
+        if path not in ("auto", "direct", "staged"):
+            raise ValueError(f"synth_up2: path must be 'auto', 'direct' or 'staged', got {path!r}")
+        ins = [half["im_t_list"][0], half["I_t_0"], half["I_t_1"], half["opt_flow_0"], half["opt_flow_1"], half["occ_mask1"]]
+        b, _, h, w = ins[0].shape
+        for t, c in zip(ins, (3, 3, 3, 2, 2, 1)):
+            _planar(t, c, "synth_up2: half-size input")
+            if tuple(t.shape) != (b, c, h, w):
+                raise ValueError(f"synth_up2: half-size inputs differ in shape ({tuple(t.shape)} against [{b},{c},{h},{w}])")
+        if b > 16:
+            raise ValueError(f"synth_up2: at most 16 pairs per call, got {b}")
+        store1 = store0 if store1 is None else store1
+        for st in (store0, store1):
+            _planar(st, 3, "synth_up2: frame store")
+            if tuple(st.shape[2:]) != (2 * h, 2 * w):
+                raise ValueError(f"synth_up2: a frame store of {tuple(st.shape)} does not hold {2 * h} x {2 * w} frames")
+        lists = []
+        for sl, st in ((slots0, store0), (slots1, store1)):
+            sl = list(range(b)) if sl is None else [int(s) for s in sl]
+            if len(sl) != b or any(s < 0 or s >= st.shape[0] for s in sl):
+                raise ValueError(f"synth_up2: {b} slots inside 0..{st.shape[0] - 1} expected, got {sl}")
+            lists.append((ctypes.c_int32 * b)(*sl))
+        if dst is None and dst_u8 is None:
+            dst = self.empty(b, 3, 2 * h, 2 * w)
+        if dst is not None:
+            _planar(dst, 3, "synth_up2: dst")
+            if tuple(dst.shape) != (b, 3, 2 * h, 2 * w):
+                raise ValueError(f"synth_up2: dst must be [{b},3,{2 * h},{2 * w}], got {tuple(dst.shape)}")
+        pt = pl = hh = ww = 0
+        if dst_u8 is not None:
+            pt, pl, hh, ww = (0, 0, 2 * h, 2 * w) if window is None else map(int, window)
+            if (not isinstance(dst_u8, torch.Tensor) or dst_u8.dtype != torch.uint8 or not dst_u8.is_cuda or not dst_u8.is_contiguous()
+                    or tuple(dst_u8.shape) != (b, hh, ww, 3)):
+                raise ValueError(f"synth_up2: dst_u8 must be a contiguous CUDA uint8 [{b},{hh},{ww},3] tensor")
+        out = {"I_t": dst, "I_t_u8": dst_u8}
+        f0 = f1 = m = None
+        if "opt_flow_0" in want or "opt_flow_1" in want:
+            f0, f1 = self.empty(b, 2, 2 * h, 2 * w), self.empty(b, 2, 2 * h, 2 * w)
+        if "occ_mask1" in want:
+            m = self.empty(b, 1, 2 * h, 2 * w)
+        for k, t in (("opt_flow_0", f0), ("opt_flow_1", f1), ("occ_mask1", m)):
+            if k in want:
+                out[k] = t
+        vp = lambda t: None if t is None else t.data_ptr()
+        prm = SynthUp2Params(*[vp(t) for t in ins], vp(store0), vp(store1), ctypes.cast(lists[0], ctypes.c_void_p), ctypes.cast(lists[1], ctypes.c_void_p),
+                             vp(dst), vp(dst_u8), vp(f0), vp(f1), vp(m), None, b, h, w, store0.shape[0], store1.shape[0], pt, pl, hh, ww,
+                             int(bool(bgr)), ("auto", "direct", "staged").index(path), 0)
+        full = 4.0 * b * 2 * h * 2 * w
+        meta = {"bytes": 14.0 * 4 * b * h * w + 6 * full + (3 * full if dst is not None else 0.0) + 3.0 * b * hh * ww
+                + (4 * full if f0 is not None else 0.0) + (full if m is not None else 0.0)}
+        self._run_direct("synth_up2", meta, self.lib.atmvfi_synth_up2, ctypes.cast(ctypes.pointer(prm), ctypes.c_void_p), self._stream())
+        return out
 
     def pack_frames(self, im0, im1, dst):
         _planar(im0, 3, "pack_frames.im0"); _planar(im1, 3, "pack_frames.im1")

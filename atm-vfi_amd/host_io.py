@@ -47,9 +47,43 @@ def _hip_ops_of(model):
     return (ops if hasattr(ops, "frame_u8_to_f32") else None), dev
 
 
-def inference_2frame(img0, img1, model, isBGR: bool = True, divisor: int = 64):
+def _inference_2frame_scaled(img0, img1, model, isBGR: bool, divisor: int):
+    """``inference_2frame(..., motion_scale=2)``: the frames padded under ``divisor * 2``, ``Network.forward_scaled``'s launches with the
+    synthesis kernel's own uint8 output (the un-padded window, the caller's channel order); a model without the HIP backend: the twins."""
+    from . import scaled
+    ops, dev = _hip_ops_of(model)
+    if img0.dtype != np.uint8 or img0.ndim != 3 or img0.shape[2] != 3 or img0.shape != img1.shape:
+        raise ValueError(f"inference_2frame: two uint8 [H,W,3] frames expected, got {img0.dtype} {tuple(img0.shape)} and {tuple(img1.shape)}")
+    h, w = img0.shape[:2]
+    left, right, top, bottom = InputPadder((1, 3, h, w), divisor=divisor * 2)._pad
+    hp, wp = h + top + bottom, w + left + right
+    if ops is not None and hasattr(ops, "synth_up2"):
+        with torch.cuda.device(dev), torch.no_grad():
+            full = torch.empty(2, 3, hp, wp, dtype=torch.float32, device=dev)
+            half = torch.empty(2, 3, hp // 2, wp // 2, dtype=torch.float32, device=dev)
+            for i, img in enumerate((img0, img1)):
+                ops.frame_u8_to_f32(torch.from_numpy(np.ascontiguousarray(img)).to(dev), full[i], top, left, isBGR)
+            ops.frame_half(full, half)
+            o = model.forward(half[0:1], half[1:2])
+            out = torch.empty(1, h, w, 3, dtype=torch.uint8, device=dev)
+            ops.synth_up2(o, full, full, [0], [1], dst_u8=out, window=(top, left, h, w), bgr=isBGR)
+            return out[0].cpu().numpy()
+    rgb = (lambda f: f[:, :, ::-1]) if isBGR else (lambda f: f)
+    t0, t1 = ((torch.tensor(np.ascontiguousarray(rgb(f).transpose(2, 0, 1))) / 255.).unsqueeze(0) for f in (img0, img1))
+    t0, t1 = InputPadder(t0.shape, divisor=divisor * 2).pad(t0, t1)
+    forward = lambda a, b: {k: ([x.cpu() for x in v] if isinstance(v, list) else v.cpu()) for k, v in model.forward(a.to(dev), b.to(dev)).items()}
+    pred = scaled.forward_scaled_host(forward, t0, t1)["I_t"]
+    return scaled.to_u8_numpy(pred, (top, left, h, w), bgr=isBGR)[0]
+
+
+def inference_2frame(img0, img1, model, isBGR: bool = True, divisor: int = 64, motion_scale: int = 1):
     """uint8 [H,W,3] frames -> uint8 [H,W,3] interpolated frame (demo_2x.py:54-87).  With the HIP backend the colour flip, /255,
-    replicate padding, un-padding and np.round(x*255) run as two device kernels on the raw uint8 frames (bit-identical)."""
+    replicate padding, un-padding and np.round(x*255) run as two device kernels on the raw uint8 frames (bit-identical).
+    ``motion_scale=2`` (default 1: everything above): half-resolution motion (scaled.py) -- the canvas of ``divisor * 2``, the forward on
+    its 2 x 2 box average, and the synthesis kernel writes the uint8 frame itself."""
+    from .scaled import check_scale
+    if check_scale(motion_scale, "inference_2frame: motion_scale") == 2:
+        return _inference_2frame_scaled(img0, img1, model, isBGR, divisor)
     ops, dev = _hip_ops_of(model)
     if ops is not None and img0.dtype == np.uint8 and img0.ndim == 3 and img0.shape[2] == 3 and img0.shape == img1.shape:
         pipe = FramePipeline(model, img0.shape[0], img0.shape[1], isBGR=isBGR, divisor=divisor, depth=1)

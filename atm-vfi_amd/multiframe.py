@@ -144,13 +144,15 @@ class FramePool:
 _Uploader, _SegmentRunner = segments._Uploader, segments._SegmentRunner
 
 
-def _active_window(active, first, it, st, model, device, divisor, step, pixfmt=None, caller: str = "interpolate_video_nx", packed=None):
+def _active_window(active, first, it, st, model, device, divisor, step, pixfmt=None, caller: str = "interpolate_video_nx", packed=None,
+                   scale: int = 1):
     """``(window, frames)`` of ``active=`` (both loops): a fixed window as it is given; an ``ActiveArea`` after its probe, the frames
     it read replayed in front of ``it`` (the loop uploads them again); a fixed window's even values fit every subsampling.  ``device``: ``(ops, dev)`` of the HIP backend, or None.
     A window that gains nothing is None: the whole frame, the plain loop.  ``pixfmt``: the frames are that format's, the profiles
     those of their luma plane and the threshold its sample code (``active.bar_code``); a locked window that ends on an odd line of a
     subsampled frame is widened by that line (``active.yuv_window_error`` holds the rule).  ``packed`` (a ``yuv.Packed``, ``pixfmt`` its
-    planar format): a probed frame is unpacked first (on the device by ``HipOps.yuv_unpack``)."""
+    planar format): a probed frame is unpacked first (on the device by ``HipOps.yuv_unpack``).  ``scale`` (``motion_scale``): the canvas
+    a window is judged under is that of ``divisor * scale``, in multiples the network needs after the reduction."""
     from . import active as _active
     accept = (packed or pixfmt).check if pixfmt is not None else None
     if not hasattr(active, "probe_stream"):
@@ -172,7 +174,8 @@ def _active_window(active, first, it, st, model, device, divisor, step, pixfmt=N
                         return ops.frame_borders(torch.from_numpy(np.ascontiguousarray(f)).to(dev), bgr=bool(st.isBGR)).cpu().numpy()
                     d = torch.from_numpy(accept(f, caller).view(np.uint8)).to(dev)
                     return ops.yuv_borders(d if packed is None else ops.yuv_unpack(d, packed), pixfmt).cpu().numpy()
-        need = 16 if getattr(model, "global_motion", True) else 8
+        need = (16 if getattr(model, "global_motion", True) else 8) * scale
+        divisor = divisor * scale if divisor else divisor
         yuv_kw = {} if pixfmt is None else dict(code=_active.bar_code(pixfmt, active.peak), accept=lambda f: accept(f, caller))
         held = active.probe_stream(chain(first, it), st.H, st.W, divisor, need, step, profile_of, **yuv_kw)
         win = active.window
@@ -199,7 +202,7 @@ def _active_refusals(caller: str, active, crop, pixfmt, keep_depth, first):
 
 def interpolate_video_nx(frames, model, factor: int = 4, time_interval: int = 1, crop: Optional[Tuple[int, int]] = None, isBGR: bool = True,
                          divisor: Optional[int] = 64, tta: bool = False, max_batch: int = 4, pool: bool = True, scene=None, pixfmt=None,
-                         keep_depth: bool = False, active=None):
+                         keep_depth: bool = False, active=None, motion_scale: int = 1):
     """N-x slow motion over any iterable of uint8 [H,W,3] frames (davis-vid.py:88-135; decoding / encoding stays with the caller):
     per segment ``(f_i, f_{i+s})``, ``s = time_interval``, yields ``f_i`` and the frames at t = 1/N ... (N-1)/N, after the last segment
     its second frame once -- ``segments * N + 1`` frames.  Originals pass through bit-equal (their centre ``crop=(h, w)`` window when
@@ -261,8 +264,18 @@ def interpolate_video_nx(frames, model, factor: int = 4, time_interval: int = 1,
     min(q, top) / top) and, only when ``scene`` needs a signature, makes the 8-bit probe picture q >> (depth - 8) on the copy stream:
     cut decisions are those of the truncated 8-bit picture.  Produced frames are ``atmvfi_rgb16_encode`` of the fp32 prediction (with
     ``tta``: of the fp32 average) and leave as 1-D uint16 arrays of ``pixfmt.cropped(h, w)``; originals, and the copies of a cut
-    segment, are the caller's own arrays (``rgb16.crop`` of them when cropping: any origin)."""
+    segment, are the caller's own arrays (``rgb16.crop`` of them when cropping: any origin).
+
+    ``motion_scale`` (1, the default: the loop as above; or 2; scaled.py holds the definition): half-resolution motion, an addition
+    of this project.  Frames are padded under ``divisor * 2``; every source frame is kept at full size AND as its 2 x 2 box average
+    (``HipOps.frame_half``); the network -- pool, plans, batches as above -- runs on the halves, and one launch per batch
+    (``HipOps.synth_up2``) up-samples flows, mask and residual and warps and blends the full-size frames.  A deeper level reads the
+    full-size prediction as returned and its half.  Everything that consumes the prediction -- ``pixfmt``, ``keep_depth``, ``crop``,
+    ``scene``, ``active``, ``tta`` (rotated at full size), ``time_interval`` -- is as above.  A model without the HIP backend does the
+    same with the numpy twins."""
     from .host_io import _hip_ops_of
+    from .scaled import check_scale
+    motion_scale = check_scale(motion_scale, "interpolate_video_nx: motion_scale")
     from .pixfmt import deep_rgb_refusals
     from .scene import cut_fill
     nx_levels(factor)
@@ -289,8 +302,11 @@ def interpolate_video_nx(frames, model, factor: int = 4, time_interval: int = 1,
     generic = ops is None or not hasattr(ops, "pool_blocks")
     source, win = chain(first, it), None
     if active is not None:
-        win, source = _active_window(active, first, it, st, model, None if generic else (ops, dev), divisor, step, pixfmt, packed=packed)
+        win, source = _active_window(active, first, it, st, model, None if generic else (ops, dev), divisor, step, pixfmt, packed=packed,
+                                     scale=motion_scale)
     common = dict(n=factor, divisor=divisor, tta=tta, pixfmt=pixfmt, window=win, watch=area is not None)
+    if motion_scale != 1:
+        common["motion_scale"] = motion_scale
     if packed is not None:
         common["packed"] = packed
     if generic:
@@ -336,10 +352,11 @@ def interpolate_video_nx(frames, model, factor: int = 4, time_interval: int = 1,
         be.close()
 
 
-def inference_nx(img0, img1, model, factor: int = 4, isBGR: bool = True, divisor: Optional[int] = 64, tta: bool = False) -> List[np.ndarray]:
+def inference_nx(img0, img1, model, factor: int = 4, isBGR: bool = True, divisor: Optional[int] = 64, tta: bool = False,
+                 motion_scale: int = 1) -> List[np.ndarray]:
     """Two uint8 [H,W,3] frames -> the ``factor - 1`` uint8 frames between them (t = 1/N ... (N-1)/N), by the recursion of
-    davis-vid.py:102-106."""
-    out = list(interpolate_video_nx([img0, img1], model, factor=factor, isBGR=isBGR, divisor=divisor, tta=tta))
+    davis-vid.py:102-106.  ``motion_scale``: as ``interpolate_video_nx``."""
+    out = list(interpolate_video_nx([img0, img1], model, factor=factor, isBGR=isBGR, divisor=divisor, tta=tta, motion_scale=motion_scale))
     return out[1:-1]
 
 

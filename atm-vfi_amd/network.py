@@ -28,6 +28,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 import torch.nn as nn
 
+from . import scaled
 from . import schema as S
 from .hip_ops import GEMM_CONV, GEMM_DECONV, GEMM_LINEAR, HipOps, PackedWeight, Planes, PlanUnsupported
 from .windows import WindowGeometry, build_window_geometry
@@ -262,6 +263,7 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
         self._pool_plans: Dict[Tuple, object] = {}
         self._pooled_plans_on = True                # tools only (bench_nx / bench_retime A/B): False keeps forward_pooled eager
         self._splitk_memo: Dict[Tuple, Tuple] = {}  # _frame_stage_splitk per (H, W, frames, mode): host-side, asked per pooled call
+        self._scaled_halves: Dict[Tuple, Tuple] = {}   # forward_scaled: the two half-size input frames of the last shape
         self._plan_stats = self._new_plan_stats()
         self._plist = None                          # cached parameter list of the per-forward currency check (_param_sig)
         self._pepoch = -1
@@ -377,6 +379,7 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
         self._drop_plans()
         self._splitk_memo.clear()
         self._workspaces.clear()
+        self._scaled_halves.clear()
         self._bufs = {}
         self._ws_key = None
         self._geo.clear()
@@ -973,6 +976,40 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
             self._select_workspace(key[-1])                  # replay counts as a use for the workspace LRU
             st["replayed"] += 1
             return ent.run((a, b), ops.device, ops._stream())
+
+    def forward_scaled(self, im0: torch.Tensor, im1: torch.Tensor, scale: int = 2, want=()):
+        """Half-resolution motion (scaled.py holds the definition): ``forward`` on the 2 x 2 box averages of the two [B,3,H,W] frames
+        (B <= 16; H, W even with H/2, W/2 acceptable to ``forward``), then one launch that up-samples flows, mask and residual x2 and
+        warps and blends the FULL-SIZE frames (``HipOps.frame_half``, ``HipOps.synth_up2``).  -> {"I_t": fp32 [B,3,H,W], "half":
+        ``forward``'s dict at half size} plus any of "opt_flow_0", "opt_flow_1", "occ_mask1" at full size that ``want`` names.  Only
+        ``scale=2`` exists.  Precision mode, launch plans and ``global_motion`` are the model's: the half-size forward is an ordinary
+        ``forward`` call.  Not part of the reference's API."""
+        if scale != 2 or isinstance(scale, bool):
+            raise ValueError(f"forward_scaled: only scale=2 is implemented, got {scale!r}")
+        if not im0.is_cuda:
+            return scaled.forward_scaled_host(self.forward, im0, im1, want)
+        if im0.shape != im1.shape or im0.dim() != 4 or im0.shape[1] != 3 or im0.shape[2] % 2 or im0.shape[3] % 2 or im0.device != im1.device:
+            raise ValueError(f"forward_scaled: two [B,3,H,W] frames of one device with even H and W expected, got {tuple(im0.shape)} and "
+                             f"{tuple(im1.shape)}")
+        b, _, H, W = im0.shape
+        if b > 16:
+            raise ValueError(f"forward_scaled: at most 16 pairs per call, got {b}")
+        ops = self._ops(im0.device)
+        with torch.cuda.device(im0.device), torch.no_grad():
+            a = im0.detach().contiguous().float()
+            c = im1.detach().contiguous().float()
+            key = (str(im0.device), b, H, W)
+            halves = self._scaled_halves.get(key)
+            if halves is None:
+                self._scaled_halves.clear()                      # one shape at a time
+                halves = self._scaled_halves[key] = (ops.empty(b, 3, H // 2, W // 2), ops.empty(b, 3, H // 2, W // 2))
+            ops.frame_half(a, halves[0])
+            ops.frame_half(c, halves[1])
+            o = self.forward(halves[0], halves[1])
+            full = ops.synth_up2(o, a, c, want=want)
+        out = {"I_t": full["I_t"], "half": o}
+        out.update({k: full[k] for k in want})
+        return out
 
     @staticmethod
     def _same_results(x, y) -> bool:

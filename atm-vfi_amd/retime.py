@@ -234,7 +234,7 @@ class Duplicates:
 def interpolate_video_retimed(frames, model, fps_in, fps_out, levels: int = 3, dedup: Optional[Duplicates] = None,
                               crop: Optional[Tuple[int, int]] = None, isBGR: bool = True, divisor: Optional[int] = 64, tta: bool = False,
                               max_batch: int = 4, pool: bool = True, scene=None, pixfmt=None, keep_depth: bool = False, report=None,
-                              active=None, shutter=None):
+                              motion_scale: int = 1, active=None, shutter=None):
     """Frame-rate conversion ``fps_in -> fps_out`` (ints, ``Fraction``s or strings such as ``"30000/1001"``) over any iterable of uint8
     [H,W,3] frames: yields, in time order, output ``m`` at ``m / fps_out`` for every m up to the last kept frame's time, as the module's
     docstring defines -- the nearest of ``N = 2**levels`` positions of its segment.  Positions 0 and N are the originals and pass through
@@ -280,9 +280,16 @@ def interpolate_video_retimed(frames, model, fps_in, fps_out, levels: int = 3, d
     produced position p carries the bars of the nearer end of its segment (p <= N/2: the first), also across a widened segment; a
     cut segment or one without an interpolated output runs no forward.
 
+    ``motion_scale`` (1, the default: the loop as above, nothing new allocated or launched; or 2): half-resolution motion, as in
+    ``multiframe.interpolate_video_nx``; not with ``shutter`` (``ValueError``).
+
     The rates and ``levels`` are checked at the call; ``ValueError`` as ``retime_slots`` raises it."""
     fi, fo, levels = _check_rates(fps_in, fps_out, levels)
     from .pixfmt import deep_rgb_refusals
+    from .scaled import check_scale
+    motion_scale = check_scale(motion_scale, "interpolate_video_retimed: motion_scale")
+    if motion_scale == 2 and shutter is not None:
+        raise ValueError("interpolate_video_retimed: shutter does not go with motion_scale=2")
     deep_rgb_refusals("interpolate_video_retimed", pixfmt, keep_depth, active=active, shutter=shutter)
     if active is not None and shutter is not None:
         raise ValueError("interpolate_video_retimed: active does not go with shutter (a blurred output mixes whole frames)")
@@ -293,11 +300,11 @@ def interpolate_video_retimed(frames, model, fps_in, fps_out, levels: int = 3, d
         if pixfmt is not None and keep_depth and pixfmt.depth == 10:
             raise ValueError("interpolate_video_retimed: shutter blends 8-bit pixels; a 10-bit blend (keep_depth=True) is out of scope")
     return _retimed(frames, model, fi, fo, levels, dedup, crop, isBGR, divisor, tta, max_batch, pool, scene, pixfmt, keep_depth, report,
-                    shutter, active)
+                    shutter, active, motion_scale)
 
 
 def _retimed(frames, model, fi, fo, levels, dedup, crop, isBGR, divisor, tta, max_batch, pool, scene, pixfmt, keep_depth, report,
-             shutter=None, active=None):
+             shutter=None, active=None, motion_scale=1):
     from .host_io import _hip_ops_of
     from .multiframe import _active_refusals, _active_window
     if active is not None and crop is not None:
@@ -327,10 +334,12 @@ def _retimed(frames, model, fi, fo, levels, dedup, crop, isBGR, divisor, tta, ma
     common = dict(n=n, divisor=divisor, tta=tta, pixfmt=pixfmt, caller="interpolate_video_retimed")
     if packed is not None:
         common["packed"] = packed
+    if motion_scale != 1:
+        common["motion_scale"] = motion_scale
     generic = ops is None or not hasattr(ops, "pool_blocks")
     if active is not None:
         win, source = _active_window(active, first, it, st, model, None if generic else (ops, dev), divisor, 1, pixfmt,
-                                     "interpolate_video_retimed", packed=packed)
+                                     "interpolate_video_retimed", packed=packed, scale=motion_scale)
         first, it = next(source), source             # (the probed frames replayed)
         common.update(window=win, watch=area is not None)
     if generic:

@@ -62,18 +62,21 @@ def chain(first, it):
     yield from it
 
 
-def _canvas(h: int, w: int, divisor, need: Optional[int] = None, pool: bool = False) -> Tuple[int, int, int, int]:
+def _canvas(h: int, w: int, divisor, need: Optional[int] = None, pool: bool = False, scale: int = 1) -> Tuple[int, int, int, int]:
     """(pad_top, pad_left, Hp, Wp) of an h x w window under ``InputPadder(divisor)`` (no divisor: no padding).  ``need`` (the device
-    path: 16 with global motion, else 8) and ``pool`` refuse a canvas the network cannot take."""
+    path: 16 with global motion, else 8) and ``pool`` refuse a canvas the network cannot take.  ``scale`` (``motion_scale``): the
+    network runs on the canvas reduced by it, so the canvas is that of ``divisor * scale`` and ``need`` / ``pool`` hold for its reduction."""
     from .host_io import InputPadder
     left = right = top = bottom = 0
     if divisor:
-        left, right, top, bottom = InputPadder((1, 3, h, w), divisor=divisor)._pad
+        left, right, top, bottom = InputPadder((1, 3, h, w), divisor=divisor * scale)._pad
     hp, wp = h + top + bottom, w + left + right
-    if need is not None and (hp % need or wp % need):
-        raise ValueError(f"interpolate_video_nx: {hp}x{wp} frames need a divisor (multiples of {need})")
-    if pool and (hp % 16 or wp % 16):
-        raise ValueError(f"interpolate_video_nx: pool=True needs frame sides that are multiples of 16 (got {hp}x{wp})")
+    if need is not None and (hp % (need * scale) or wp % (need * scale)):
+        raise ValueError(f"interpolate_video_nx: {hp}x{wp} frames need a divisor (multiples of {need * scale})")
+    if pool and (hp % (16 * scale) or wp % (16 * scale)):
+        raise ValueError(f"interpolate_video_nx: pool=True needs frame sides that are multiples of {16 * scale} (got {hp}x{wp})")
+    if need is None and scale > 1 and (hp % scale or wp % scale):
+        raise ValueError(f"interpolate_video_nx: motion_scale={scale} needs even frame sides or a divisor (got {hp}x{wp})")
     return top, left, hp, wp
 
 
@@ -266,10 +269,17 @@ class _SegmentRunner:
     uint8 window, with the depth kept the fp32 average -- and the bars of the nearer original (k <= N/2: position 0) outside.
 
     ``pack`` (a tight ``yuv.Packed`` whose ``planar`` is ``out_fmt``; a packed 4:2:2 stream): the output ring holds frames of that
-    layout.  A produced frame leaves as above into ONE planar scratch and ``HipOps.yuv_pack`` writes the ring entry from it."""
+    layout.  A produced frame leaves as above into ONE planar scratch and ``HipOps.yuv_pack`` writes the ring entry from it.
+
+    ``motion_scale=2`` (half-resolution motion, scaled.py; not with ``blend``): the canvas is that of ``divisor * 2`` and everything
+    above -- pads, window, every ``_leave_*`` -- stays full-size.  Per set a second, FULL-SIZE frame store ``full`` exists beside the
+    pool, whose frames and network geometry are halved: a source frame is converted into its full-size slot and ``frame_half``'d into
+    the pool slot; ``_forward`` hands the forward's whole dict to ``synth_up2`` with the pairs' slot lists on the full-size store; a
+    prediction that feeds a deeper level goes to both stores, the full-size prediction as returned and its ``frame_half``; ``tta``
+    rotates at full size.  With ``motion_scale=1`` ``full`` IS ``frames`` and nothing else is allocated or launched."""
 
     def __init__(self, model, ops, dev, height, width, factor, crop, bgr, divisor, tta, max_batch, pool, out_fmt=None, deep_fmt=None,
-                 out_slots=None, batch_sizes=None, blend=None, window=None, border_fmt=None, pack=None):
+                 out_slots=None, batch_sizes=None, blend=None, window=None, border_fmt=None, pack=None, motion_scale=1):
         import torch
         from .multiframe import FramePool, centre_window, nx_levels
         self.torch, self.model, self.ops, self.dev = torch, model, ops, dev
@@ -287,12 +297,17 @@ class _SegmentRunner:
             self.border_fmt = border_fmt
             self.border = [u8(height, width, 3) if border_fmt is None else u8(border_fmt.frame_bytes) for _ in range(2)]
             self.border_of = {0: 0, factor: 1}       # position -> border frame; swapped with the positions
+        self.scale = sc = int(motion_scale)
+        if sc == 2 and blend is not None:
+            raise ValueError("_SegmentRunner: motion_scale=2 does not go with a blend")
         self.pad_top, self.pad_left, self.hp, self.wp = _canvas(self.h, self.w, divisor, 16 if getattr(model, "global_motion", True) else 8,
-                                                               self.use_pool)
+                                                               self.use_pool, sc)
+        self.nh, self.nw = self.hp // sc, self.wp // sc          # the network's geometry
         S, sets = factor + 1, 2 if self.tta else 1   # (with tta a second set: the 180-degree rotations)
-        self.pools = [FramePool(model, self.hp, self.wp, S) for _ in range(sets)] if self.use_pool else None
+        self.pools = [FramePool(model, self.nh, self.nw, S) for _ in range(sets)] if self.use_pool else None
         self.frames = ([p.frames for p in self.pools] if self.use_pool else
-                       [torch.empty(S, 3, self.hp, self.wp, dtype=torch.float32, device=dev) for _ in range(sets)])
+                       [torch.empty(S, 3, self.nh, self.nw, dtype=torch.float32, device=dev) for _ in range(sets)])
+        self.full = self.frames if sc == 1 else [torch.empty(S, 3, self.hp, self.wp, dtype=torch.float32, device=dev) for _ in range(sets)]
         self.phys = list(range(S))                   # schedule position -> pool slot; positions 0 and N swap slots per segment
         self.have_first = self.fresh = False
         self.gather = {}                             # plain mode: the pairs of a batch are gathered into contiguous [B,3,Hp,Wp] inputs
@@ -343,7 +358,7 @@ class _SegmentRunner:
         slot = self.phys[pos]
 
         def convert(d_u8, surface=None):
-            dst = self.frames[0][slot]
+            dst = self.full[0][slot]
             if self.deep_fmt is not None:             # d_u8: the frame's I420 bytes
                 self.ops.yuv_decode(d_u8, self.deep_fmt, dst=dst, window=(self.y0, self.x0, self.h, self.w), pad_top=self.pad_top,
                                     pad_left=self.pad_left, keep_depth=True)
@@ -353,7 +368,10 @@ class _SegmentRunner:
                 self.ops.frame_u8_window(d_u8, 0, self.y0, self.x0, self.h, self.w, dst=dst, pad_top=self.pad_top, pad_left=self.pad_left,
                                          bgr=self.bgr)
             if self.tta:
-                self.ops.frame_rot180(dst, self.frames[1][slot])
+                self.ops.frame_rot180(dst, self.full[1][slot])
+            if self.scale == 2:
+                for k in range(len(self.full)):
+                    self.ops.frame_half(self.full[k][slot], self.frames[k][slot])
             if self.pools:
                 for p in self.pools:
                     p.invalidate(slot)
@@ -376,13 +394,17 @@ class _SegmentRunner:
     def _forward(self, k, lefts, rights):
         """I_t [B,3,Hp,Wp] of the pairs (slots) on frame set ``k`` (0: the frames, 1: their 180-degree rotations)."""
         if self.use_pool:
-            return self.model.forward_pooled(self.pools[k], lefts, rights)["I_t"]
-        b = len(lefts)
-        g = self.gather.get(b)
-        if g is None:
-            g = self.gather[b] = self.torch.empty(2 * b, 3, self.hp, self.wp, dtype=self.torch.float32, device=self.dev)
-        self.ops.pool_blocks(self.frames[k], lefts + rights, g)
-        return self.model.forward(g[:b], g[b:])["I_t"]
+            out = self.model.forward_pooled(self.pools[k], lefts, rights)
+        else:
+            b = len(lefts)
+            g = self.gather.get(b)
+            if g is None:
+                g = self.gather[b] = self.torch.empty(2 * b, 3, self.nh, self.nw, dtype=self.torch.float32, device=self.dev)
+            self.ops.pool_blocks(self.frames[k], lefts + rights, g)
+            out = self.model.forward(g[:b], g[b:])
+        if self.scale == 1:
+            return out["I_t"]
+        return self.ops.synth_up2(out, self.full[k], self.full[k], lefts, rights)["I_t"]      # the pairs' full-size frames by slot: no gather
 
     def _run_levels(self, levels, wanted, sink):
         """The schedule level by level in batches of at most ``max_batch`` pairs: ``sink(pos, pred, flip)`` for every produced position
@@ -403,13 +425,20 @@ class _SegmentRunner:
                     if shown[j]:                       # (else an ancestor only: it stays in the pool)
                         sink(pos, pred[j], None if flip is None else flip[j])
                 if li < last:                          # the next level reads these frames (the un-averaged prediction)
-                    self.ops.pool_blocks(self.frames[0], outs, pred, to_pool=True)
+                    self.ops.pool_blocks(self.full[0], outs, pred, to_pool=True)
                     if self.tta:
                         rot = self.gather.get(("rot", len(chunk)))
                         if rot is None:
                             rot = self.gather[("rot", len(chunk))] = torch.empty_like(pred)
                         self.ops.frame_rot180(pred, rot)
-                        self.ops.pool_blocks(self.frames[1], outs, rot, to_pool=True)
+                        self.ops.pool_blocks(self.full[1], outs, rot, to_pool=True)
+                    if self.scale == 2:                # ... and their halves, which the network reads
+                        half = self.gather.get(("half", len(chunk)))
+                        if half is None:
+                            half = self.gather[("half", len(chunk))] = torch.empty(len(chunk), 3, self.nh, self.nw, dtype=torch.float32, device=self.dev)
+                        for k, src in enumerate((pred, rot) if self.tta else (pred,)):
+                            self.ops.frame_half(src, half)
+                            self.ops.pool_blocks(self.frames[k], outs, half, to_pool=True)
                     if self.pools:
                         for p in self.pools:
                             for s in outs:
@@ -594,15 +623,21 @@ class _SegmentRunner:
         return [arr[k].copy() for k in range(count)]
 
 
-def _generic_segment(model, factor, crop_of, isBGR, divisor, tta, max_batch, load=None, store=None):
+def _generic_segment(model, factor, crop_of, isBGR, divisor, tta, max_batch, load=None, store=None, motion_scale=1):
     """``segment`` for a model without the HIP backend (any callable ``forward(im0, im1) -> {"I_t"}``): torch ops, same schedule, the
     canvas of ``_canvas`` as on the device.  ``load(frame) -> fp32 [h,w,3]`` / ``store(fp32 [h,w,3]) -> frame`` replace the uint8 RGB
-    conversions at both ends (the 10-bit I420 twins, with ``keep_depth``)."""
+    conversions at both ends (the 10-bit I420 twins, with ``keep_depth``).  ``motion_scale=2``: the canvas of ``divisor * 2`` and
+    ``scaled.forward_scaled_host`` (the twins of ``frame_half`` and ``synth_up2`` around the model's forward) in ``forward``'s place."""
     import torch
     import torch.nn.functional as F
     from .multiframe import nx_levels
     dev = next(model.parameters()).device
     levels = nx_levels(factor)
+    if motion_scale == 2:
+        from .scaled import forward_scaled_host
+        forward = lambda l, r: {"I_t": forward_scaled_host(model.forward, l.cpu(), r.cpu())["I_t"].to(dev)}
+    else:
+        forward = model.forward
 
     def to_t(img):
         if load is not None:
@@ -616,7 +651,7 @@ def _generic_segment(model, factor, crop_of, isBGR, divisor, tta, max_batch, loa
         """``levels`` / ``emit`` (``retime.interpolate_video_retimed``): a sparse schedule and the positions to return, in order."""
         a, b = to_t(fa), to_t(fb)
         h, w = a.shape[-2:]
-        top, left, hp, wp = _canvas(h, w, divisor)
+        top, left, hp, wp = _canvas(h, w, divisor, scale=motion_scale)
         if divisor:
             a, b = (F.pad(x, [left, wp - w - left, top, hp - h - top], mode="replicate") for x in (a, b))
         fr = {0: a, factor: b}
@@ -626,10 +661,10 @@ def _generic_segment(model, factor, crop_of, isBGR, divisor, tta, max_batch, loa
                 chunk = level[i:i + max_batch]
                 l = torch.cat([fr[x] for x, _, _ in chunk], 0)
                 r = torch.cat([fr[y] for _, y, _ in chunk], 0)
-                pred = model.forward(l, r)["I_t"]
+                pred = forward(l, r)["I_t"]
                 out = pred
                 if tta:
-                    pf = model.forward(l.flip(2).flip(3).contiguous(), r.flip(2).flip(3).contiguous())["I_t"]
+                    pf = forward(l.flip(2).flip(3).contiguous(), r.flip(2).flip(3).contiguous())["I_t"]
                     out = (pred + pf.flip(2).flip(3)) / 2
                 for j, (_, _, pos) in enumerate(chunk):
                     fr[pos] = pred[j:j + 1]
@@ -655,16 +690,16 @@ class HostBackend:
     bars of the nearer original -- with a ``pixfmt`` the window's encode into the original's own samples -- until ``whole_frame()``;
     ``watching``: the loop examines ``borders`` of the frames it admits.  ``packed`` (a ``yuv.Packed``, ``pixfmt`` its planar format):
     an admitted frame is unpacked once (``yuv.unpack_numpy``; ``_frame``), everything above works on the planar frame, and what is
-    produced is packed into ``st.packed`` (``yuv.pack_numpy``)."""
+    produced is packed into ``st.packed`` (``yuv.pack_numpy``).  ``motion_scale=2``: see ``_generic_segment``."""
     lookahead = False                                # (nothing is gained by reading a segment ahead)
 
     def __init__(self, model, st: Stream, n, divisor, tta, max_batch, pixfmt=None, dedup=None, light=None, window=None, watch=False,
-                 caller: str = "interpolate_video_nx", packed=None):
+                 caller: str = "interpolate_video_nx", packed=None, motion_scale=1):
         self.n, self.levels, self.st, self.pixfmt, self.caller, self.packed = n, n.bit_length() - 1, st, pixfmt, caller, packed
         self.dedup, self.prev_rgb = dedup, None
         self.light, self.gathered = light, {}        # (the synthetic shutter: ``blended``)
         self.watching = window is not None and watch
-        self._generic = lambda crop_of, **kw: _generic_segment(model, n, crop_of, st.isBGR, divisor, tta, max_batch, **kw)
+        self._generic = lambda crop_of, **kw: _generic_segment(model, n, crop_of, st.isBGR, divisor, tta, max_batch, motion_scale=motion_scale, **kw)
         self._build(window)
 
     def _build(self, window):
@@ -810,14 +845,16 @@ class DeviceBackend:
     lookahead = True
 
     def __init__(self, model, ops, dev, st: Stream, n, crop, divisor, tta, max_batch, pool, pixfmt=None, scene=False, dedup=False,
-                 sparse=False, out_slots=None, blend=None, window=None, watch=False, caller: str = "interpolate_video_nx", packed=None):
+                 sparse=False, out_slots=None, blend=None, window=None, watch=False, caller: str = "interpolate_video_nx", packed=None,
+                 motion_scale=1):
         self.n, self.levels, self.started = n, n.bit_length() - 1, False
         batch_sizes = range(1, min(max(1, min(int(max_batch), 16)), max(1, n // 2)) + 1) if sparse else None
         self._runner = lambda window: _SegmentRunner(model, ops, dev, st.H, st.W, n, crop, st.isBGR, divisor, tta, max_batch,
                                                      pool and hasattr(model, "forward_pooled"), out_fmt=st.out_fmt,
                                                      deep_fmt=pixfmt if st.deep else None, out_slots=out_slots, batch_sizes=batch_sizes,
                                                      blend=blend, window=window,
-                                                     border_fmt=pixfmt if window is not None else None, pack=st.packed)
+                                                     border_fmt=pixfmt if window is not None else None, pack=st.packed,
+                                                     motion_scale=motion_scale)
         self.pixfmt, self.ops, self.dev, self.hw = pixfmt, ops, dev, (st.H, st.W)
         self.runner = self._runner(window)
         self.watching = window is not None and watch

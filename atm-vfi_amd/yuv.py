@@ -711,6 +711,11 @@ def _interpolate_stream(who, open_reader, open_writer, model, kw, *, factor, sce
     from .host_io import _hip_ops_of, interpolate_video_2x
     from .multiframe import centre_window, interpolate_video_nx, nx_levels
     from .retime import _check_rates, interpolate_video_retimed
+    from .scaled import check_scale
+    if check_scale(kw.pop("motion_scale", 1), f"{who}: motion_scale") == 2:       # (1: the loops as they are called without it)
+        if shutter is not None:
+            raise ValueError(f"{who}: shutter does not go with motion_scale=2")
+        kw["motion_scale"] = 2
     if fps_out is None:
         if shutter is not None:
             raise ValueError(f"{who}: shutter needs fps_out (the synthetic shutter belongs to the rate conversion)")
@@ -747,7 +752,7 @@ def _interpolate_stream(who, open_reader, open_writer, model, kw, *, factor, sce
             if deep:
                 kw["keep_depth"] = True
             if interpolator is None:
-                nx_only = tta or factor != 2 or any(k in kw for k in ("crop", "time_interval", "max_batch", "pool", "active")) \
+                nx_only = tta or factor != 2 or any(k in kw for k in ("crop", "time_interval", "max_batch", "pool", "active", "motion_scale")) \
                     or isinstance(pixfmt, Packed)        # (the 2x loop does not take packed 4:2:2: factor=2 of the N-x loop does)
                 if not nx_only and _hip_ops_of(model)[0] is not None:
                     interpolator = interpolate_video_2x
@@ -795,7 +800,8 @@ def interpolate_y4m(src, dst, model, factor: int = 2, scene=None, tta: bool = Fa
     angle; only with ``fps_out``, else ``ValueError``; 8-bit output only): the conversion's synthetic shutter; the dict gains
     ``"blended"``.  ``active`` (an ``active.ActiveArea`` or a fixed window, among ``kw``; not with ``crop`` or ``shutter``): the
     network runs on the active picture of letterboxed video, in either loop (``factor=2`` goes to ``interpolate_video_nx`` then); a
-    10-bit stream needs ``keep_depth`` for it."""
+    10-bit stream needs ``keep_depth`` for it.  ``motion_scale`` (1 or 2, among ``kw``; 2 not with ``shutter``): half-resolution
+    motion, handed on to either loop (``factor=2`` goes to ``interpolate_video_nx`` then)."""
     # (the same tag as read where the depth is the stream's; 10-bit input written as 8 bit takes the format's canonical tag)
     open_writer = lambda rd, out, rate: Y4MWriter(dst, out, rate, ctag=rd.ctag if out.depth == rd.fmt.depth else None, aspect=rd.aspect)
     return _interpolate_stream("interpolate_y4m", lambda: Y4MReader(src, matrix=matrix, accept=SUBSAMPLINGS), open_writer, model, kw,

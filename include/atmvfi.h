@@ -383,6 +383,56 @@ int atmvfi_warp_blend_tiled(const float* im0, const float* im1, const float* mot
                             int64_t pack_rows, int pack_c0, int B, int H, int W, void* stream);
 #define atmvfi_blend atmvfi_warp_blend   /* SURVEY.md section 8b name */
 
+/* Half-resolution motion (warp.hip; ABI 0.26; the definition and the host twins: atm-vfi_amd/scaled.py).  Nothing of the reference: motion
+ * is estimated on 2x reduced frames and the frame is synthesised at full size.
+ * atmvfi_frame_half.  `planes` contiguous H x W fp32 planes -> H/2 x W/2: out = ((a + b) + (c + d)) * 0.25f, a b the top-row pair and c d
+ *   the bottom-row pair of the 2 x 2 block (F.avg_pool2d(., 2) up to its summation order; commutes with atmvfi_frame_rot180 bit for bit).
+ *   16-byte loads and stores when both pointers are 16-byte aligned and W % 8 == 0 (a lane owns four outputs), scalar accesses otherwise;
+ *   the same bits.  ATMVFI_EINVAL before any launch: null pointers, planes < 1, H or W below 2 or odd, src and dst overlapping.
+ * atmvfi_synth_up2.  The inputs are the half-size outputs of one forward on the reduced frames, contiguous fp32: it_sum (blend +
+ *   residual, unclamped), it0, it1 (the two warped frames) [B,3,h,w]; flow0, flow1 [B,2,h,w]; m1 [B,1,h,w].  Per half-size pixel
+ *       r = it_sum - (m1 * it0 + (1.0f - m1) * it1)                                  (atmvfi_warp_blend's expression)
+ *   and the eight maps f0x f0y f1x f1y m1 rR rG rB are up-sampled x2 with half-pixel centres (F.interpolate(scale_factor=2, bilinear,
+ *   align_corners=False)): output column x reads half columns max(x/2 - 1, 0), x/2 with weights 0.25, 0.75 when x is even and (x-1)/2,
+ *   min((x+1)/2, w-1) with weights 0.75, 0.25 when x is odd, rows likewise:  v = wy0 * (wx0 * v00 + wx1 * v01) + wy1 * (wx0 * v10 + wx1 * v11),
+ *   every product and sum rounded to fp32.  The flows are then doubled (exact) and, with H = 2h, W = 2w,
+ *       I_t = clamp((m * warp(L, f0) + (1.0f - m) * warp(R, f1)) + r, 0, 1)
+ *   where warp is atmvfi_flow_warp's (zeros padding, the reference's coordinate round trip; a non-finite flow samples 0.0 exactly),
+ *   L = store0[slots0[b]] and R = store1[slots1[b]] are [3,H,W] frames of the two full-size stores [S0,3,H,W] / [S1,3,H,W] (the
+ *   stores may be one; slots0 / slots1 are HOST arrays of B entries, NULL = b).  Outputs, either or both: dst_f32 [B,3,H,W], and
+ *   dst_u8 [B,hh,ww,3] = the window (pad_top, pad_left, hh, ww) of the canvas as atmvfi_frame_f32_to_u8 gives it (x * 255 in fp32,
+ *   round half to even, clamp; BGR if `bgr`) from the same fp32 value.  Optional f0_out, f1_out [B,2,H,W] (both or neither) and m_out
+ *   [B,1,H,W]: the up-sampled, doubled flows and the up-sampled mask.
+ *   One launch; a workgroup owns a 32 x 8 tile of outputs, builds the 18 x 6 half-size neighbourhood of the eight maps in LDS, and takes
+ *   the sources from LDS-staged boxes as atmvfi_warp_blend_tiled does (path 2; W % 4 == 0 and 16-byte aligned stores; a tile whose flows
+ *   leave the box gathers, per source) or by gathers throughout (path 1; any size).  path 0 is path 1, the faster by measurement; 2 runs
+ *   on request.  The two give the same bits.  No atomics in global memory, nothing pre-zeroed, no host synchronisation; every output element is written by one lane.
+ *   `workspace` is not used: atmvfi_synth_up2_workspace_floats returns 0 (or -1 for a shape the call refuses) and the pointer may be
+ *   NULL.  A half-size pre-pass into an interleaved workspace was built and measured slower (README, "Half-resolution motion"); the two
+ *   names stay in the ABI for a form that needs scratch.  Not for launch plans: the parameter block and the slot lists are host memory
+ *   read at the call.
+ *   ATMVFI_EINVAL before any launch: a null input; B < 1 or B > 16; h or w < 1; S0 or S1 < 1 or a slot outside its store; no output;
+ *   one of f0_out / f1_out alone; a dst_u8 window outside the canvas; an unknown path, or path 2 where it is not allowed; an output that
+ *   overlaps an input or another output. */
+int atmvfi_frame_half(const float* src, float* dst, int planes, int H, int W, void* stream);
+typedef struct atmvfi_synth_up2_params {
+    const float *it_sum, *it0, *it1;     /* [B,3,h,w] */
+    const float *flow0, *flow1;          /* [B,2,h,w] */
+    const float* m1;                     /* [B,1,h,w] */
+    const float *store0, *store1;        /* [S0,3,2h,2w], [S1,3,2h,2w] */
+    const int32_t *slots0, *slots1;      /* host arrays of B entries, or NULL */
+    float* dst_f32;                      /* [B,3,2h,2w] or NULL */
+    void* dst_u8;                        /* [B,hh,ww,3] or NULL */
+    float *f0_out, *f1_out, *m_out;      /* optional */
+    float* workspace;                    /* unused, may be NULL */
+    int32_t B, h, w, S0, S1;
+    int32_t pad_top, pad_left, hh, ww, bgr;   /* read only with dst_u8 */
+    int32_t path;                        /* 0 auto (= 1), 1 gathers, 2 staged boxes */
+    int32_t reserved;
+} atmvfi_synth_up2_params;
+int atmvfi_synth_up2(const atmvfi_synth_up2_params* p, void* stream);
+int64_t atmvfi_synth_up2_workspace_floats(int B, int h, int w);
+
 /* Bilinear resize with align_corners=True, src = dst*(in-1)/(out-1), values * value_scale:
  * F.interpolate(scale 0.5) of the image pyramid (network_base.py:445-446,461-462) and
  * upsample_flow (network_base.py:11-18, value_scale = factor).  Source element (b,c,y,x) is
