@@ -10,6 +10,9 @@ Input families (all seeded): ``exact`` (a dyadic grid on which no fp32 accumulat
 operands actually used), ``wide`` (log-uniform magnitudes), ``edge`` (fp16 saturation / subnormal boundaries) and ``cancel``
 (sums near 0 with large terms).  ``mutants`` are what a subtly wrong engine would compute; tests/test_f16x3_model_cpu.py shows
 that each of them misses the GPU tolerance on every exact-family configuration of tests/test_gpu_f16x3_contract.py by > 10x.
+
+``stem_chain`` / ``tail_chain`` and the ``chain_exact`` / ``chain_rich_last`` families (at the end) model the two kernels that chain
+layers on chip, on operands for which the hidden layers are exact: tests/test_gpu_f16x3_chains.py.
 """
 from __future__ import annotations
 
@@ -499,3 +502,273 @@ def assert_split_of(planes, values, what: str, c0: int = 0):
     same = lambda a, b: torch.equal(torch.nan_to_num(a.float(), nan=-7.0), torch.nan_to_num(b.float(), nan=-7.0))
     assert same(got[0], hi), f"{what}: hi plane differs from split() of the fp32 result at {int((got[0].float() != hi.float()).sum())} places"
     assert same(got[1], lo), f"{what}: lo' plane differs from split() of the fp32 result at {int((got[1].float() != lo.float()).sum())} places"
+
+
+# ------------------------------------------------------------------ exact chains: the fused stem and the fused refiner tail
+# Both kernels chain layers on chip (stem.hip: three 3x3 layers, the two hidden maps in LDS; conv3x3_planes.hip + pointwise.hip: the
+# activated tile of refine_head.0 times W2, then the nine shifted tap contributions), so a hidden layer cannot be observed.  The chain
+# families below choose operands for which NO fp32 operation of a hidden layer rounds -- neither accumulator (``certificate``), nor
+# the fold acc + cor/1024, nor + bias, nor the PReLU product, nor the re-split -- so the model predicts every hidden value bit for
+# bit and the next layer's input is known exactly (``layer_exactness`` is that proof, tests/test_f16x3_model_cpu.py runs it for every
+# case).  Budget: a value of b bits fed through a layer whose sum of |terms| is 2^g times its grid needs b + g <= 24 bits in the
+# accumulator and <= 22 after the PReLU for the re-split, hence ternary weights, biases on 2^-1, hidden slopes {1, -1, 2}, 13-bit inputs.
+STRUCTURAL_MUTANTS = ("pad_bias", "parity")
+STEM_STRIDES = (1, 1, 2)
+
+
+def stem_chain(x, params, mutant=None, mutant_layer=None) -> list:
+    """feat_extracts.0.0 -> 0.1 -> 1.0 as three ``conv`` calls (3x3, pad 1, strides 1, 1, 2) on NHWC frames ``x`` [F,H,W,3], each
+    fed with the fp32 value of the one before; ``params`` = three (weight OIHW, bias, slope).  -> the three ``Result``s.
+    ``mutant`` in MUTANTS: that engine mutant in layer ``mutant_layer`` (0..2) only.  "pad_bias": hidden layer ``mutant_layer``
+    (0 or 1) is PReLU(conv(0) + bias) outside the image instead of 0 (the next layer's zero padding).  "parity": layer 3 reads the
+    layer-2 columns one to the right, i.e. at the other parity."""
+    if mutant is not None and mutant not in MUTANTS + STRUCTURAL_MUTANTS:
+        raise ValueError(mutant)
+    out = []
+    a = x.float()
+    for i, ((w, b, p), st) in enumerate(zip(params, STEM_STRIDES)):
+        m = mutant if (i == mutant_layer and mutant in MUTANTS) else None
+        if mutant == "pad_bias" and i > 0 and mutant_layer == i - 1:
+            pb, pp = params[i - 1][1].float(), params[i - 1][2].float()
+            n, h, wd, c = a.shape
+            ap = torch.where(pb > 0, pb, pb * pp).reshape(1, 1, 1, c).expand(n, h + 2, wd + 2, c).clone()
+            ap[:, 1:-1, 1:-1] = a
+            r = conv(ap, w, b, p, stride=st, pad=0)
+        else:
+            if mutant == "parity" and i == 2:
+                a = torch.cat([a[:, :, 1:], torch.zeros_like(a[:, :, :1])], 2)
+            r = conv(a, w, b, p, stride=st, pad=1, mutant=m)
+        out.append(r)
+        a = r.y.float()
+    return out
+
+
+def readout_matrix(wb) -> torch.Tensor:
+    """refine_head.1's weight [3, C, 3, 3] as W2[(ky * 3 + kx) * 3 + o][c] (27 x C)."""
+    return wb.float().permute(2, 3, 0, 1).reshape(27, wb.shape[1])
+
+
+def tail_sum(contrib, n: int, h: int, w: int) -> torch.Tensor:
+    """refine_tail's sum: ``contrib`` [n*h*w, 27] (column (ky * 3 + kx) * 3 + o) -> [n, 3, h, w], each output pixel adding the
+    contributions of its nine neighbours p + (ky - 1, kx - 1) that lie inside the image, in (ky, kx) order."""
+    t = contrib.double().reshape(n, h, w, 9, 3)
+    pre = torch.zeros(n, h, w, 3, dtype=torch.float64)
+    for ky in range(3):
+        for kx in range(3):
+            dy, dx = ky - 1, kx - 1
+            y0, y1, x0, x1 = max(0, -dy), h - max(0, dy), max(0, -dx), w - max(0, dx)
+            pre[:, y0:y1, x0:x1] += t[:, y0 + dy:y1 + dy, x0 + dx:x1 + dx, ky * 3 + kx]
+    return pre.permute(0, 3, 1, 2).contiguous()
+
+
+def tail_chain(x_planes_values, wa, ba, pa, wb, mutant=None, which=None, terms: int = 3) -> tuple:
+    """atmvfi_conv3x3_planes_readout + the sum of atmvfi_refine_tail on the plane values ``x`` [n,h,w,Cin]: ``conv`` for
+    refine_head.0 (wa, ba, pa), ``linear`` of its activated rows (fp32) with W2 = ``readout_matrix(wb)`` -- the 27 tap contributions
+    per pixel, what ``contrib`` holds, transposed -- and their sum per output pixel (no bias: refine_tail adds it).  -> (Result of the
+    conv, Result of the W2 product [n*h*w, 27], summed pre-activation [n,3,h,w]).  ``mutant`` goes into product ``which`` (0: the
+    conv, 1: W2).  ``terms`` = 1: the main product on hi(x), hi(w) (the f16 mode, tests/f16_model.py); W2 stays three-term."""
+    x = x_planes_values.float()
+    n, h, w, _ = x.shape
+    if terms == 1:
+        x, wa = split(x)[0].float(), split(wa)[0].float()
+    ra = conv(x, wa, ba, pa, mutant=mutant if which == 0 else None)
+    rc = linear(ra.y.float().reshape(n * h * w, -1), readout_matrix(wb), mutant=mutant if which == 1 else None)
+    return ra, rc, tail_sum(rc.y, n, h, w)
+
+
+def _is_f32(t: torch.Tensor) -> bool:
+    return bool((t.float().double() == t).all())
+
+
+def layer_exactness(x, w, res: Result, contract, resplit: bool = True) -> dict:
+    """Is the layer ``res`` = model(x, w) EXACT in the kernel's fp32 arithmetic?  ``cert``: no rounding in either accumulator
+    (``certificate`` on the operands actually used); ``fold`` / ``bias`` / ``prelu``: acc + cor/1024, + bias and the PReLU product
+    are fp32 values (so whatever way the compiler contracts them, each step is exact); ``resplit``: hi + lo'/1024 of the fp32
+    result is the result.  ``ok``: all of them.  Also the share of the activation operand with lo' != 0 and of negative
+    pre-activations (conditions on the inputs: a chain whose lo' is all zero, or whose PReLU never multiplies, tests less)."""
+    cert = certificate(x, w, contract)
+    fold = res.acc + res.cor / 1024.0
+    pre = fold + res.bias
+    d = {"cert": cert["ok"], "fold": _is_f32(fold), "bias": _is_f32(pre), "prelu": _is_f32(res.y),
+         "resplit": (not resplit) or bool((dequant(res.y.float()) == res.y).all()),
+         "lo_share": float((split(x)[1] != 0).double().mean()), "neg_share": float((pre < 0).double().mean()), "certificate": cert}
+    d["ok"] = all(d[k] for k in ("cert", "fold", "bias", "prelu", "resplit"))
+    return d
+
+
+def sum_exactness(contrib, n, h, w, bias, slope) -> dict:
+    """refine_tail's nine-term sum, + bias and PReLU product on exact contributions: every partial sum is a multiple of the
+    contributions' grid q below 2^24 q (so no order of adding rounds), and the two epilogue steps are fp32 values."""
+    c = contrib.double()
+    k = (c * 2.0 ** 40).round().to(torch.int64)          # the contributions are multiples of 2^-40 below 2^20 (asserted)
+    assert bool((k.double() * 2.0 ** -40 == c).all()) and float(c.abs().max()) < 2.0 ** 20
+    k = k[k != 0]
+    q = 2.0 ** (int(torch.log2((k & -k).double()).min().item()) - 40) if k.numel() else 1.0
+    pre = tail_sum(c, n, h, w)
+    sabs = tail_sum(c.abs(), n, h, w)
+    b = bias.double().reshape(1, 3, 1, 1)
+    s = slope.double().reshape(1, 3, 1, 1)
+    v = pre + b
+    y = torch.where(v > 0, v, v * s)
+    d = {"sum": float(sabs.max()) <= 2.0 ** 24 * q, "bias": _is_f32(v), "prelu": _is_f32(y), "q": q, "sum_abs": float(sabs.max()),
+         "neg_share": float((v < 0).double().mean())}
+    d["ok"] = d["sum"] and d["bias"] and d["prelu"]
+    return d
+
+
+def ternary(gen: torch.Generator, *shape, period: int, keep: int = 1, phase: int = 0) -> torch.Tensor:
+    """Weights in {-1, 0, +1}, signs from ``gen``: position i is nonzero where (r_i + phase) % period < keep, with r_i drawn from
+    a seed of the SHAPE alone -- density keep / period, and the cases of ``period`` consecutive phases reach every position."""
+    r = torch.randint(0, period, shape, generator=torch.Generator().manual_seed(7919 * period + math.prod(shape)))
+    s = torch.randint(0, 2, shape, generator=gen) * 2 - 1
+    return (s * (((r + phase) % period) < keep)).float()
+
+
+def chain_values(gen: torch.Generator, *shape, signed: bool = False, amin: int = 1, amax: int = 7) -> torch.Tensor:
+    """13-bit inputs a 2^-3 + b 2^-13 (amin <= a <= amax, |b| <= 7): hi = fp16 keeps 11 bits, so lo' != 0 wherever |x| >= 1/4 and b is not
+    a multiple of the fp16 ulp there (2^-12 below 1/2, 2^-11 above).  Coarser than ``exact``'s 2^-21 on purpose: three layers deep the
+    sums must still fit 24 bits."""
+    a = torch.randint(amin, amax + 1, shape, generator=gen).double()
+    b = torch.randint(-7, 8, shape, generator=gen).double()
+    x = a * 2.0 ** -3 + b * 2.0 ** -13
+    if signed:
+        x = x * (torch.randint(0, 2, shape, generator=gen) * 2 - 1)
+    return x.float()
+
+
+def half_bias(gen: torch.Generator, n: int, amax: int = 4) -> torch.Tensor:
+    return (torch.randint(-amax, amax + 1, (n,), generator=gen).double() * 0.5).float()
+
+
+def chain_slopes(gen: torch.Generator, n: int, choices=(1.0, -1.0, 2.0)) -> torch.Tensor:
+    """PReLU slopes whose product keeps the grid (a hidden layer's 1/2 would cost the next layer one of its 24 bits; the last
+    layer of a chain may take it)."""
+    return torch.tensor(choices, dtype=torch.float32)[torch.randint(0, len(choices), (n,), generator=gen)]
+
+
+CHAIN_FAMILIES = ("chain_exact", "chain_rich_last")
+STEM_SHAPES = [(1, 2, 2), (1, 16, 32), (1, 18, 34), (1, 36, 52), (3, 70, 34), (3, 176, 256), (4, 176, 384)]      # F, H, W (full resolution)
+STEM_PERIODS = (5, 4, 3, 7)             # layer 1: 4 of 5 weights nonzero; layers 2, 3: 1 of 3, 1 of 7
+CASES_STEM = [_case(f"stem_{c0}_{c1}_f{f}_{h}x{w}", "stem", 40 + 10 * (c0 == 16) + i, c0=c0, c1=c1, FHW=(f, h, w), phase=i,
+                    nan_lane=(i == 3))
+              for c0, c1 in ((24, 48), (16, 32)) for i, (f, h, w) in enumerate(STEM_SHAPES)]
+TAIL_SHAPES = [(64, 32, 1, 16, 16), (128, 64, 2, 17, 50), (64, 32, 2, 21, 35), (128, 64, 1, 40, 72), (64, 32, 1, 272, 272),
+               (128, 64, 1, 16, 16), (64, 32, 2, 17, 50), (128, 64, 2, 21, 35)]             # Cin, C, n, h, w
+TAIL_PERIODS = (4, 2)                   # refine_head.0: 1 of 4 weights nonzero; W2: 1 of 2
+CASES_TAIL = [_case(f"tail_{cin}_{c}_n{n}_{h}x{w}", "tail", 70 + i, cin=cin, c=c, NHW=(n, h, w), phase=i // 2)
+              for i, (cin, c, n, h, w) in enumerate(TAIL_SHAPES)]
+CASE_TAIL_F16 = dict(CASES_TAIL[2], id=CASES_TAIL[2]["id"] + "_terms1", terms=1)
+
+
+def stem_operands(cfg, family: str) -> dict:
+    """Seeded operands of a stem case: frames ``x`` [F,H,W,3] and ``params``, three (weight, bias, slope).  Both families share the
+    frames and the two hidden layers; ``chain_rich_last`` replaces layer 3 by full-precision operands (``exact`` weights with their
+    7-bit lo' in the even cases, uniform ones in the odd cases; uniform bias and slopes)."""
+    assert family in CHAIN_FAMILIES
+    g = torch.Generator().manual_seed(2000 + cfg["seed"])
+    c0, c1, (f, h, w), ph = cfg["c0"], cfg["c1"], cfg["FHW"], cfg["phase"]
+    x = chain_values(g, f, h, w, 3, amin=2, amax=3)
+    p5, k5, p2, p3 = STEM_PERIODS
+    ws = [ternary(g, c0, 3, 3, 3, period=p5, keep=k5, phase=ph), ternary(g, c0, c0, 3, 3, period=p2, phase=ph),
+          ternary(g, c1, c0, 3, 3, period=p3, phase=ph)]
+    bs = [half_bias(g, c) for c in (c0, c0, c1)]
+    # two channels of layer 1 sit near +-9: there the 13-bit grid leaves lo' five significant bits, which is what lets the lo4
+    # mutant (a 4-bit lo' operand) show in layer 2 at all
+    bs[0][(ph + 1) % c0], bs[0][(ph + 9) % c0] = 8.5, -9.0
+    ps = [chain_slopes(g, c0), chain_slopes(g, c0), chain_slopes(g, c1, (1.0, 0.5, -1.0, 2.0))]
+    if family == "chain_rich_last":
+        g2 = torch.Generator().manual_seed(3000 + cfg["seed"])
+        ws[2] = exact(g2, c1, c0, 3, 3) * 0.25 if ph % 2 == 0 else (torch.rand(c1, c0, 3, 3, generator=g2) * 2 - 1) * 0.25
+        bs[2] = (torch.rand(c1, generator=g2) * 2 - 1) * 0.3
+        ps[2] = 0.25 + (torch.rand(c1, generator=g2) * 2 - 1) * 0.2
+    return {"x": x, "params": list(zip(ws, bs, ps))}
+
+
+def tail_operands(cfg, family: str) -> dict:
+    """Seeded operands of a tail case: plane values ``x`` [n,h,w,Cin], refine_head.0 (wa, ba, pa), refine_head.1 (wb, bb, pb) and
+    ``it`` [n,3,h,w].  W2 is ternary x 2^-6 (the sigmoid's argument stays O(1)) in ``chain_exact``; in ``chain_rich_last`` it is
+    ``exact`` x 2^-6 (even cases) or uniform (odd cases) with uniform bias and slope."""
+    assert family in CHAIN_FAMILIES
+    g = torch.Generator().manual_seed(2000 + cfg["seed"])
+    cin, c, (n, h, w), ph = cfg["cin"], cfg["c"], cfg["NHW"], cfg["phase"]
+    pa_, pb_ = TAIL_PERIODS
+    o = {"x": chain_values(g, n, h, w, cin, signed=True), "wa": ternary(g, c, cin, 3, 3, period=pa_, phase=ph), "ba": half_bias(g, c),
+         "pa": chain_slopes(g, c), "wb": ternary(g, 3, c, 3, 3, period=pb_, phase=ph) * 2.0 ** -6, "bb": half_bias(g, 3, 2),
+         "pb": chain_slopes(g, 3, (1.0, 0.5, 2.0)), "it": torch.rand(n, 3, h, w, generator=g)}
+    if family == "chain_rich_last":
+        g2 = torch.Generator().manual_seed(3000 + cfg["seed"])
+        o["wb"] = exact(g2, 3, c, 3, 3) * 2.0 ** -6 if ph % 2 == 0 else (torch.rand(3, c, 3, 3, generator=g2) * 2 - 1) * 2.0 ** -6
+        o["bb"] = (torch.rand(3, generator=g2) * 2 - 1) * 0.2
+        o["pb"] = 0.25 + (torch.rand(3, generator=g2) * 2 - 1) * 0.2
+    return o
+
+
+def build_chain(cfg, family: str, mutant=None, where=None) -> dict:
+    """Operands + model of a chain case (cached per process without a mutant).  stem: "res" = the three Results; tail: "ra", "rc",
+    "pre" of ``tail_chain``."""
+    key = (cfg["id"], family)
+    if mutant is None and key in _CACHE:
+        return _CACHE[key]
+    if cfg["kind"] == "stem":
+        o = stem_operands(cfg, family)
+        o["res"] = stem_chain(o["x"], o["params"], mutant, where)
+    else:
+        o = tail_operands(cfg, family)
+        o["ra"], o["rc"], o["pre"] = tail_chain(o["x"], o["wa"], o["ba"], o["pa"], o["wb"], mutant, where, cfg.get("terms", 3))
+    if mutant is None:
+        _CACHE[key] = o
+    return o
+
+
+def stem_exactness(o: dict, layers=(0, 1, 2)) -> list:
+    """``layer_exactness`` of the given layers of a built stem case (each on the operands that layer actually sees)."""
+    out = []
+    a = o["x"]
+    for i, ((w, b, p), st, r) in enumerate(zip(o["params"], STEM_STRIDES, o["res"])):
+        if i in layers:
+            out.append(layer_exactness(a, w, r, conv_contract(st, 1, 1), resplit=i < 2))
+        a = r.y.float()
+    return out
+
+
+def split_quantisation(y: torch.Tensor) -> torch.Tensor:
+    """Bound of |hi + lo'/1024 - v| for an fp32 v near ``y`` inside fp16's range: both halves round to nearest, ~22 significant bits
+    (2^-21 relative, as tests/test_gpu_ops.py holds the split to), and lo'/1024 has the absolute granularity 2^-34."""
+    return 2.0 ** -21 * y.abs() + 2.0 ** -34
+
+
+# ------------------------------------------------------------------ the bounds the GPU chain tests apply (shared with the CPU teeth)
+def stem_last_bound(o: dict) -> torch.Tensor:
+    """``chain_rich_last``: elementwise bound of |planes.to_float() - y3|.  Layer 3's input is known exactly, so this is the
+    statistical rule on layer 3 alone -- cpu32_err derived as test_statistical_families does, plain fp32 on the CPU on the
+    dequantised operands against the model -- plus the quantisation of the output split."""
+    (w, b, p), r = o["params"][2], o["res"][2]
+    xd = dequant(o["res"][1].y.float()).float().permute(0, 3, 1, 2)
+    cpu32 = F.prelu(F.conv2d(xd, dequant(w).float(), b.float(), stride=2, padding=1), p.float()).permute(0, 2, 3, 1)
+    return stat_bound(r.abs_xw, (cpu32.double() - r.y).abs().max().item()) + split_quantisation(r.y)
+
+
+def tail_contrib_bound(o: dict, fold_exact: bool) -> torch.Tensor:
+    """Elementwise bound of |contrib^T - rc.y| [n*h*w, 27].  The activated tile is known exactly, so only W2's product counts: where
+    its certificate holds the epilogue roundings (``exact_tol``; 0 where the fold is exact too: bit for bit), else the statistical
+    rule with plain fp32 on the CPU as the yardstick."""
+    rc = o["rc"]
+    act, w2 = o["ra"].y.float().reshape(rc.y.shape[0], -1), readout_matrix(o["wb"])
+    if certificate(act, w2, linear_contract)["ok"]:
+        return torch.zeros_like(rc.y) if fold_exact else rc.exact_tol()
+    cpu32 = dequant(act).float() @ dequant(w2).float().t()
+    return stat_bound(rc.abs_xw, (cpu32.double() - rc.y).abs().max().item())
+
+
+def tail_preact(o: dict, n: int, h: int, w: int, contrib_bound: torch.Tensor) -> tuple:
+    """-> (r, bound of the kernel's r): r = PReLU(sum of the nine contributions + bias) of the model in fp64 [n,3,h,w], and how far
+    refine_tail's fp32 r can be from it: the contributions' own bounds, summed like the contributions, plus 11 roundings (nine
+    additions, the bias, the PReLU product) of at most 2^-24 (sum |contributions| + |bias|) each, all times max(1, |slope|).  Exactly 0
+    where ``sum_exactness`` holds and the contributions are exact."""
+    b, s = o["bb"].double().reshape(1, 3, 1, 1), o["pb"].double().reshape(1, 3, 1, 1)
+    v = o["pre"] + b
+    r = torch.where(v > 0, v, v * s)
+    if float(contrib_bound.max()) == 0.0:
+        return r, torch.zeros_like(r)
+    rb = (tail_sum(contrib_bound, n, h, w) + 11 * EPS32 * (tail_sum(o["rc"].y.abs(), n, h, w) + b.abs())) * s.abs().clamp_min(1.0)
+    return r, rb
