@@ -167,6 +167,8 @@ SIGNATURES = {
     "atmvfi_rgb16_decode": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f, c_f]),
     "atmvfi_rgb16_encode": (c_i, [c_f, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f]),
     "atmvfi_frame_half": (c_i, [c_f, c_f, c_i, c_i, c_i, c_f]),
+    "atmvfi_field_bob": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f]),
+    "atmvfi_field_rows": (c_i, [c_f, c_f, c_i, ctypes.POINTER(ctypes.c_int64), c_i, c_f]),
     "atmvfi_synth_up2": (c_i, [c_f, c_f]),
     "atmvfi_synth_up2_workspace_floats": (c_l, [c_i, c_i, c_i]),
     "atmvfi_pack_frames": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_f]),
@@ -181,6 +183,7 @@ SIGNATURES = {
     "atmvfi_plan_run": (c_i, [ctypes.POINTER(PlanOp), c_i, ctypes.POINTER(PlanPatch), c_i, ctypes.POINTER(ctypes.c_uint64), c_i,
                               ctypes.POINTER(c_i), c_f]),
 }
+FIELD_BOB_STRIP = 16          # include/atmvfi.h ATMVFI_FIELD_BOB_STRIP: the picture rows a lane of atmvfi_field_bob walks
 SSIM_X_U8, SSIM_X_BGR, SSIM_ROUND_Y, SSIM_ACCUMULATE, SSIM_MSE_F32 = 1, 2, 4, 8, 16     # include/atmvfi.h ATMVFI_SSIM_*
 
 
@@ -2050,6 +2053,46 @@ class HipOps:
                 + (4 * full if f0 is not None else 0.0) + (full if m is not None else 0.0)}
         self._run_direct("synth_up2", meta, self.lib.atmvfi_synth_up2, ctypes.cast(ctypes.pointer(prm), ctypes.c_void_p), self._stream())
         return out
+
+    # ---------------------------------------------------------------- interlaced input (include/atmvfi.h; twins and the loop: fields.py)
+    def field_bob(self, src, dst_even=None, dst_odd=None, pad_top: int = 0, pad_left: int = 0, h: Optional[int] = None, w: Optional[int] = None):
+        """The two field canvases of the woven canvas ``src`` (contiguous fp32 [planes,Hp,Wp]; its picture is the ``h`` x ``w`` window at
+        (pad_top, pad_left); default: everything below and right of the pads): ``dst_even`` / ``dst_odd`` (tensors of ``src``'s shape;
+        either may be None, not both) = the replicate-padded ``bob`` of the picture with the even / odd rows kept (include/atmvfi.h atmvfi_field_bob; the bits of ``fields.bob_numpy``).  Not part of a forward: never recorded
+        into a launch plan."""
+        ts = [t for t in (src, dst_even, dst_odd) if t is not None]
+        if src is None or len(ts) < 2:
+            raise ValueError("field_bob: a source and at least one of dst_even / dst_odd expected")
+        for t in ts:
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 3 or not t.is_contiguous() or not t.is_cuda or t.shape != src.shape:
+                raise ValueError("field_bob: src and the destinations must be contiguous CUDA fp32 [planes,Hp,Wp] tensors of one shape")
+        planes, hp, wp = src.shape
+        h = hp - int(pad_top) if h is None else int(h)
+        w = wp - int(pad_left) if w is None else int(w)
+        n_out = len(ts) - 1
+        self._run_direct("field_bob", {"bytes": 4.0 * planes * (h * w + n_out * hp * wp)}, self.lib.atmvfi_field_bob, _ptr(src), _ptr(dst_even),
+                         _ptr(dst_odd), planes, hp, wp, int(pad_top), int(pad_left), h, w, self._stream())
+
+    def field_rows(self, dst, src, geometry, parity: int):
+        """Rows ``y % 2 == parity`` of up to three planes from the byte tensor ``src`` into the byte tensor ``dst`` (contiguous CUDA
+        uint8, any size): ``geometry`` is a sequence of per-plane ``(dst_offset, src_offset, dst_pitch, src_pitch, row_bytes, rows)`` in
+        bytes (``fields.plane_geometry`` makes it for a frame layout).  Bytes are moved, nothing else is touched (include/atmvfi.h
+        atmvfi_field_rows; the bits of ``fields.rows_numpy``).  The planes are checked against the tensors' sizes here.  Not part of
+        a forward: never recorded into a launch plan."""
+        for t, role in ((dst, "dst"), (src, "src")):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError(f"field_rows: {role} must be a contiguous CUDA uint8 tensor")
+        geometry = [tuple(int(v) for v in g) for g in geometry]
+        if not 1 <= len(geometry) <= 3 or any(len(g) != 6 for g in geometry):
+            raise ValueError("field_rows: one to three planes of (dst_offset, src_offset, dst_pitch, src_pitch, row_bytes, rows) expected")
+        moved = 0
+        for k, (doff, soff, dp, sp, rb, rows) in enumerate(geometry):
+            if min(doff, soff) < 0 or min(dp, sp, rb, rows) < 1 or doff + (rows - 1) * dp + rb > dst.numel() or soff + (rows - 1) * sp + rb > src.numel():
+                raise ValueError(f"field_rows: plane {k} {geometry[k]} does not lie inside dst ({dst.numel()} bytes) and src ({src.numel()} bytes)")
+            moved += rb * ((rows - int(parity) + 1) // 2)
+        arr = (ctypes.c_int64 * (6 * len(geometry)))(*[v for g in geometry for v in g])
+        self._run_direct("field_rows", {"bytes": 2.0 * moved}, self.lib.atmvfi_field_rows, _ptr(dst), _ptr(src), len(geometry), arr, int(parity),
+                         self._stream())
 
     def pack_frames(self, im0, im1, dst):
         _planar(im0, 3, "pack_frames.im0"); _planar(im1, 3, "pack_frames.im1")

@@ -741,3 +741,5 @@ from .shutter import Shutter, blend_numpy, shutter_slots  # noqa: E402,F401
 from .active import ActiveArea, bar_code, borders_numpy, compose_numpy, yuv_borders_numpy, yuv_compose_numpy  # noqa: E402,F401
 # planar YUV 4:2:0 frames for the loops above (``pixfmt=``) and Y4M files (not in the reference): atm-vfi_amd/yuv.py
 from .yuv import Format as YuvFormat, Y4MReader, Y4MWriter, interpolate_y4m  # noqa: E402,F401
+# interlaced input: motion-compensated deinterlacing to field rate (not in the reference): atm-vfi_amd/fields.py
+from .fields import bob_numpy, deinterlace_video, field_parity, rows_numpy, weave_numpy  # noqa: E402,F401

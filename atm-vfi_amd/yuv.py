@@ -390,9 +390,11 @@ class Y4MReader:
     yields the frames as 1-D uint8 (uint16 for 10-bit) arrays; ``len()`` when the file is seekable.  Accepted: C420, C420jpeg,
     C420mpeg2, C420p10, progressive.  Refused, naming the tag: C420paldv, 4:2:2, 4:4:4, mono and interlaced streams.  ``matrix``: the format's matrix when "auto" (by height) is not wanted.
     ``accept``: the subsamplings to read; with "422" / "444" in it C422, C422p10 (left-sited: the Y4M convention for 4:2:2 is
-    co-sited chroma) and C444, C444p10 are read as well.  A tag outside ``accept`` is refused by name."""
+    co-sited chroma) and C444, C444p10 are read as well.  A tag outside ``accept`` is refused by name.
+    ``interlaced`` (default False: interlaced streams are refused as above): tags It / Ib are read into ``interlace`` ("t" / "b") and
+    the frames delivered woven, for ``fields.deinterlace_video``; Im (mixed) stays refused."""
 
-    def __init__(self, path_or_file, matrix: str = "auto", accept=("420",)):
+    def __init__(self, path_or_file, matrix: str = "auto", accept=("420",), interlaced: bool = False):
         accept = tuple(str(a) for a in accept)
         for a in accept:
             if a not in SUBSAMPLINGS:
@@ -421,7 +423,9 @@ class Y4MReader:
                 self.aspect = v
             elif k == "I":
                 self.interlace = v
-                if v not in ("p", "?"):
+                if v not in ("p", "?") and not (interlaced and v in ("t", "b")):
+                    if interlaced and v == "m":
+                        raise ValueError("Y4MReader: mixed-mode interlacing is not supported (tag Im; It and Ib are read)")
                     raise ValueError(f"Y4MReader: interlaced streams are not supported (tag I{v})")
             elif k == "C":
                 self.ctag = v
@@ -703,11 +707,14 @@ def to_8bit(frame, fmt) -> np.ndarray:
 
 
 def _interpolate_stream(who, open_reader, open_writer, model, kw, *, factor, scene, tta, interpolator, keep_depth, fps_out, levels, dedup,
-                        shutter):
+                        shutter, interlaced=None, deint="mc", deint_only=False):
     """The one driver of ``interpolate_y4m`` and ``interpolate_raw`` (``who``, for the messages): the frames of ``rd = open_reader()``
     (``rd.fmt`` is the loops' ``pixfmt``, ``rd.fps`` the rate) through the loops into ``open_writer(rd, out_format, rate)``.  What the
     arguments alone decide is refused before anything is opened; after that both ends are closed on every path, a refusal before
-    the writer exists included."""
+    the writer exists included.  ``interlaced`` ("tff" / "bff"; "auto": the reader's ``interlace`` tag, a progressive one: None): the
+    loop runs on ``fields.deinterlace_video(reader, ...)`` at twice the reader's rate -- two chained generators, the frames passing
+    through host memory between them; ``deint_only``: the field-rate stream is written and no further loop runs.  None: the code
+    path of before, nothing new is touched."""
     from .host_io import _hip_ops_of, interpolate_video_2x
     from .multiframe import centre_window, interpolate_video_nx, nx_levels
     from .retime import _check_rates, interpolate_video_retimed
@@ -722,9 +729,18 @@ def _interpolate_stream(who, open_reader, open_writer, model, kw, *, factor, sce
         nx_levels(factor)
     elif "time_interval" in kw:
         raise ValueError(f"{who}: fps_out and time_interval do not go together")
+    if interlaced is None and deint_only:
+        raise ValueError(f"{who}: deint_only needs interlaced (tff, bff{', auto' if who == 'interpolate_y4m' else ''})")
     rd = open_reader()
     pixfmt, wr, n_in, report = rd.fmt, None, [0], {}
+    fps_in = rd.fps
     try:
+        if interlaced == "auto":
+            interlaced = {"t": "tff", "b": "bff"}.get(getattr(rd, "interlace", None))
+        if interlaced is not None:
+            from . import fields
+            fields.check_stream(who, pixfmt, keep_depth, interlaced, deint)
+            fps_in = rd.fps * 2
         deep_rgb_refusals(who, pixfmt, keep_depth, active=kw.get("active"), shutter=shutter)
     except ValueError:
         rd.close()
@@ -734,19 +750,31 @@ def _interpolate_stream(who, open_reader, open_writer, model, kw, *, factor, sce
         for f in rd:
             n_in[0] += 1
             yield f
+    source = counted
+    if interlaced is not None:
+        # the deinterlacer's own cut record: the caller's ``scene`` belongs to the loop that follows (with ``deint_only``: to this one)
+        d_scene = scene if deint_only or scene is None else type(scene)(scene.hist, scene.grid)
+        source = lambda woven=counted, fmt=pixfmt: fields.deinterlace_video(woven(), model, order=interlaced, mode=deint, pixfmt=fmt,
+                                                                            keep_depth=keep_depth, scene=d_scene)
+        pixfmt = out_format(pixfmt, bool(keep_depth) and pixfmt.depth > 8)        # what the loop behind it reads
+    counted = source
     try:
-        if fps_out is None:
-            rate = rd.fps * factor / int(kw.get("time_interval", 1))
+        if deint_only:
+            rate = fps_in
+        elif fps_out is None:
+            rate = fps_in * factor / int(kw.get("time_interval", 1))
         else:
-            _, rate, levels = _check_rates(rd.fps, fps_out, levels)
+            _, rate, levels = _check_rates(fps_in, fps_out, levels)
         _, _, oh, ow = centre_window(pixfmt.height, pixfmt.width, kw.get("crop"))
         deep = bool(keep_depth) and pixfmt.depth > 8
         src_out = pixfmt.cropped(oh, ow)            # (a Surface's is tight)
         wr = open_writer(rd, src_out if deep else src_out.as_8bit(), rate)
-        if fps_out is not None:
+        if deint_only:
+            frames = counted()
+        elif fps_out is not None:
             if shutter is not None:
                 kw["shutter"] = shutter
-            frames = (interpolator or interpolate_video_retimed)(counted(), model, rd.fps, rate, levels=levels, dedup=dedup, scene=scene, tta=tta,
+            frames = (interpolator or interpolate_video_retimed)(counted(), model, fps_in, rate, levels=levels, dedup=dedup, scene=scene, tta=tta,
                                                                  pixfmt=pixfmt, keep_depth=deep, report=report, **kw)
         else:
             if deep:
@@ -771,7 +799,7 @@ def _interpolate_stream(who, open_reader, open_writer, model, kw, *, factor, sce
         if wr is not None:
             wr.close()
     info = {"fps_in": rd.fps, "fps_out": rate, "size": (ow, oh), "frames_in": n_in[0], "frames_out": wr.frames}
-    if fps_out is not None:
+    if fps_out is not None and not deint_only:
         info["forwards"] = report.get("forwards", 0)
         if shutter is not None:
             info["blended"] = report.get("blended", 0)
@@ -783,7 +811,8 @@ def _interpolate_stream(who, open_reader, open_writer, model, kw, *, factor, sce
 
 
 def interpolate_y4m(src, dst, model, factor: int = 2, scene=None, tta: bool = False, interpolator=None, matrix: str = "auto",
-                    keep_depth: bool = False, fps_out=None, levels: int = 3, dedup=None, shutter=None, **kw):
+                    keep_depth: bool = False, fps_out=None, levels: int = 3, dedup=None, shutter=None, interlaced=None, deint: str = "mc",
+                    deint_only: bool = False, **kw):
     """Y4M file (or binary file object) ``src`` -> Y4M ``dst`` at ``fps * factor`` (``/ time_interval`` when given): an exact
     rational, 30000/1001 in gives 60000/1001 out.  Frames travel as I420 both ways (``pixfmt``); originals are written as read,
     predicted frames are encoded on the device.  The same format tags are written; 10-bit input is decoded on the device and written
@@ -801,12 +830,20 @@ def interpolate_y4m(src, dst, model, factor: int = 2, scene=None, tta: bool = Fa
     ``"blended"``.  ``active`` (an ``active.ActiveArea`` or a fixed window, among ``kw``; not with ``crop`` or ``shutter``): the
     network runs on the active picture of letterboxed video, in either loop (``factor=2`` goes to ``interpolate_video_nx`` then); a
     10-bit stream needs ``keep_depth`` for it.  ``motion_scale`` (1 or 2, among ``kw``; 2 not with ``shutter``): half-resolution
-    motion, handed on to either loop (``factor=2`` goes to ``interpolate_video_nx`` then)."""
+    motion, handed on to either loop (``factor=2`` goes to ``interpolate_video_nx`` then).
+
+    ``interlaced`` (None, the default: everything above, and It / Ib streams refused as before; "tff", "bff" or "auto": the header's
+    It / Ib tag, a progressive header: None): the stream is woven interlaced video.  It is deinterlaced to field rate first
+    (``fields.deinterlace_video``, ``deint`` = "mc" or "bob"; 4:2:2 and 4:4:4 only, 10-bit with ``keep_depth``) and the chosen loop
+    runs on that progressive stream at ``2 fps``; the written header says Ip and the resulting rate.  ``deint_only=True``: the
+    field-rate stream itself is written and no further loop runs (``scene`` then belongs to the deinterlacer)."""
+    if interlaced not in (None, "tff", "bff", "auto"):
+        raise ValueError(f"interpolate_y4m: unknown interlaced {interlaced!r} (tff, bff, auto)")
     # (the same tag as read where the depth is the stream's; 10-bit input written as 8 bit takes the format's canonical tag)
     open_writer = lambda rd, out, rate: Y4MWriter(dst, out, rate, ctag=rd.ctag if out.depth == rd.fmt.depth else None, aspect=rd.aspect)
-    return _interpolate_stream("interpolate_y4m", lambda: Y4MReader(src, matrix=matrix, accept=SUBSAMPLINGS), open_writer, model, kw,
-                               factor=factor, scene=scene, tta=tta, interpolator=interpolator, keep_depth=keep_depth, fps_out=fps_out,
-                               levels=levels, dedup=dedup, shutter=shutter)
+    return _interpolate_stream("interpolate_y4m", lambda: Y4MReader(src, matrix=matrix, accept=SUBSAMPLINGS, interlaced=interlaced is not None),
+                               open_writer, model, kw, factor=factor, scene=scene, tta=tta, interpolator=interpolator, keep_depth=keep_depth,
+                               fps_out=fps_out, levels=levels, dedup=dedup, shutter=shutter, interlaced=interlaced, deint=deint, deint_only=deint_only)
 
 
 PIX_FMTS = {"nv12": ("uv", 8, False), "nv21": ("vu", 8, False), "p010le": ("uv", 10, True), "yuv420p": ("planar", 8, False),
@@ -844,15 +881,18 @@ def surface_of(pix_fmt: str, h: int, w: int, pitch=None, **format_kw) -> Surface
 
 
 def interpolate_raw(src, dst, model, surface, fps, factor: int = 2, scene=None, tta: bool = False, interpolator=None,
-                    keep_depth: bool = False, fps_out=None, levels: int = 3, dedup=None, shutter=None, **kw):
+                    keep_depth: bool = False, fps_out=None, levels: int = 3, dedup=None, shutter=None, interlaced=None, deint: str = "mc",
+                    deint_only: bool = False, **kw):
     """``interpolate_y4m`` for headerless streams (``RawReader`` / ``RawWriter``): frames of ``surface`` at ``fps`` in ``src`` ->
     frames of ``surface.tight().cropped(h, w)`` in ``dst`` (the 8-bit counterpart for 10-bit input without ``keep_depth``, originals
     converted on the host), at ``fps * factor`` or at ``fps_out``.  Every keyword is ``interpolate_y4m``'s (there is no ``matrix``: the
-    surface's format names it); the same dict is returned."""
+    surface's format names it, and ``interlaced`` is "tff" or "bff": there is no header to take it from); the same dict is returned."""
+    if interlaced not in (None, "tff", "bff"):
+        raise ValueError(f"interpolate_raw: unknown interlaced {interlaced!r} (tff, bff; a headerless stream has no tag for auto)")
     surface = surface if isinstance(surface, (Packed, DeepRGB)) else as_surface(surface)
     return _interpolate_stream("interpolate_raw", lambda: RawReader(src, surface, fps), lambda rd, out, rate: RawWriter(dst, out), model, kw,
                                factor=factor, scene=scene, tta=tta, interpolator=interpolator, keep_depth=keep_depth, fps_out=fps_out,
-                               levels=levels, dedup=dedup, shutter=shutter)
+                               levels=levels, dedup=dedup, shutter=shutter, interlaced=interlaced, deint=deint, deint_only=deint_only)
 
 
 # what a user of this module needs from the loops
@@ -862,3 +902,5 @@ from .scene import SceneCuts  # noqa: E402,F401
 from .active import ActiveArea  # noqa: E402,F401
 from .retime import Duplicates, interpolate_video_retimed  # noqa: E402,F401
 from .shutter import Shutter, blend_numpy, shutter_slots  # noqa: E402,F401
+# interlaced input (``interlaced=`` above; not in the reference): atm-vfi_amd/fields.py
+from .fields import bob_numpy, deinterlace_video, field_parity, rows_numpy, weave_numpy  # noqa: E402,F401

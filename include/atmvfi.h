@@ -923,6 +923,34 @@ int atmvfi_ssim_psnr(const void* x, int64_t x_bstride, int64_t x_cstride, int64_
                      int64_t y_bstride, int64_t y_cstride, int64_t y_ystride, int64_t y_xstride, int B, int H, int W, float val_range,
                      int flags, double* out, float* workspace, int64_t workspace_floats, void* stream);
 
+/* Interlaced input (fields.hip; ABI 0.27; the definitions, the host twins and the loop: atm-vfi_amd/fields.py; per-pixel models:
+ * tests/cpu_fields.py).  Nothing of the reference.  Neither call is part of a forward.
+ * atmvfi_field_bob.  src [planes,Hp,Wp] fp32 is a WOVEN canvas whose picture S is the h x w window at (pad_top, pad_left); per plane and
+ *   parity p the bobbed picture is
+ *       F_p[y] = S[y] if (y & 1) == p;  else S[1] if y == 0;  else S[h-2] if y == h-1;  else 0.5f * (S[y-1] + S[y+1])
+ *   (the fp32 sum rounded once, the halving exact), and the field canvas the network reads is the replicate padding of the BOBBED picture:
+ *       dst_p[c][Y][X] = F_p[c][clamp(Y - pad_top, 0, h-1)][clamp(X - pad_left, 0, w-1)]
+ *   dst_even takes p = 0 and dst_odd p = 1, both [planes,Hp,Wp]; either may be NULL, not both.  One launch reads the picture once and
+ *   writes both: a lane owns four adjacent canvas columns of a strip of ATMVFI_FIELD_BOB_STRIP picture rows and keeps the previous two
+ *   source rows in registers.  16-byte accesses when the three pointers are 16-byte aligned and Wp, pad_left and w are multiples of 4,
+ *   scalar accesses otherwise; the same bits.  The source's padding is never read; every element of a destination is written by
+ *   exactly one lane; vector stores only, no atomics, nothing pre-zeroed, no host synchronisation.
+ *   ATMVFI_EINVAL before any launch: a null source or two null destinations, planes < 1, h < 2, w < 1, a window outside the canvas, a
+ *   destination that overlaps the source or the other destination.
+ * atmvfi_field_rows.  Per plane k (geometry[6k..6k+5] = dst_offset, src_offset, dst_pitch, src_pitch, row_bytes, rows; bytes; a HOST
+ *   array read at the call, its values travel in the kernel arguments): for every row y < rows with (y & 1) == parity, the row_bytes
+ *   bytes at src + src_offset + y * src_pitch replace those at dst + dst_offset + y * dst_pitch.  Bytes are moved, nothing is
+ *   computed; rows of the other parity and bytes beyond row_bytes are neither read nor written.  A plane whose two base addresses, two
+ *   pitches and row_bytes are multiples of 16 moves 16 bytes per lane, any other plane single bytes; the same bits.
+ *   ATMVFI_EINVAL before any launch: a null pointer, planes outside 1..3, a parity outside 0 / 1, a negative offset, a pitch,
+ *   row_bytes or rows below 1, row_bytes above a pitch, rows written that overlap rows read or the rows written of another plane. */
+#define ATMVFI_FIELD_BOB_STRIP 16
+int atmvfi_field_bob(const float* src /*[planes,Hp,Wp]*/, float* dst_even, float* dst_odd, int planes, int Hp, int Wp, int pad_top, int pad_left,
+                     int h, int w, void* stream);
+int atmvfi_field_rows(void* dst, const void* src, int planes /*1..3*/,
+                      const int64_t* geometry /*HOST array, 6 per plane: dst_offset, src_offset, dst_pitch, src_pitch, row_bytes, rows*/, int parity,
+                      void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Launch plans: one forward of the hot path as ONE call.
  *

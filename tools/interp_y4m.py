@@ -44,7 +44,14 @@ def main():
     ap.add_argument("--light", choices=("code", "linear"), default="linear", help="with --shutter: the domain the samples are averaged in")
     ap.add_argument("--precision", choices=("f16x3", "f16", "f32"), default="f16x3", help="contraction arithmetic (Network.set_precision): f16x3 = the default, three 16-bit MFMAs per product; f16 = single-pass fp16 in the plane kernels (faster, about 1e-2 of the frame range); f32 = exact fp32 MFMA (about 2.5x slower)")
     ap.add_argument("--motion-scale", type=int, choices=(1, 2), default=1, help="2: half-resolution motion -- the network runs on 2x reduced frames, one kernel synthesises at full size (about 4x fewer network pixels; not with --shutter)")
+    ap.add_argument("--interlaced", choices=("tff", "bff", "auto"), default=None, help="the input is woven interlaced video of this field order"
+                    + (" (auto: the It / Ib tag of the header)") + ": it is deinterlaced to field rate first and the loop runs on that stream at twice the rate "
+                    "(4:2:2 and 4:4:4 only; 10-bit input needs --keep-depth)")
+    ap.add_argument("--deint", choices=("mc", "bob"), default="mc", help="with --interlaced: motion-compensated (one forward per output frame) or the field's own line average")
+    ap.add_argument("--deint-only", action="store_true", help="with --interlaced: write the field-rate stream itself, run no further loop")
     a = ap.parse_args()
+    if (a.deint != "mc" or a.deint_only) and a.interlaced is None:
+        ap.error("--deint and --deint-only need --interlaced")
     if a.motion_scale == 2 and a.shutter is not None:
         ap.error("--motion-scale 2 does not go with --shutter")
     if (a.dedup or a.levels != 3 or a.shutter is not None) and a.fps_out is None:
@@ -73,6 +80,7 @@ def main():
     info = yuv.interpolate_y4m(src, dst, net, factor=a.factor, scene=yuv.SceneCuts() if a.scene else None, tta=a.tta, matrix=a.matrix,
                                keep_depth=a.keep_depth, **({"active": area} if area is not None else {}),
                                **({"motion_scale": 2} if a.motion_scale == 2 else {}),
+                               **(dict(interlaced=a.interlaced, deint=a.deint, deint_only=a.deint_only) if a.interlaced else {}),
                                **(dict(fps_out=a.fps_out, levels=a.levels, dedup=yuv.Duplicates() if a.dedup else None,
                                        shutter=yuv.Shutter(a.shutter, a.light) if a.shutter is not None else None) if a.fps_out else {}))
     print({k: (str(v) if k.startswith("fps") else v) for k, v in info.items()}, file=sys.stderr)
