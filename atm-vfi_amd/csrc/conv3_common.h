@@ -1,8 +1,8 @@
 // Shared pieces of the split-precision 3x3 convolution (conv3x3_f16x3.hip: entry + packers, conv3x3_f16x3_row.hip: kernel).
 #pragma once
 #include "common.h"
+#include "plane_common.h"      // f16x8, LO_UNSCALE, swz64, dma16, wait_vm
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 namespace atmvfi {
@@ -40,13 +40,10 @@ using atmvfi::Conv3Dev;
 
 constexpr int TW = 16, HW_ = TW + 2;     // output tile width and halo width; the tile height is 2 rows per wavefront (conv3x3_f16x3_row.hip)
 
-__device__ __forceinline__ int swz64(int row) { return ((row >> 2) & 1) << 1; }
-
 // x = hi + lo'/1024 with hi = fp16(x) and lo' = fp16((x - hi) * 1024): scaling keeps lo' a NORMAL fp16
 // whenever hi is (|lo'| <= |x|), so the pair carries ~22 significand bits at any magnitude down to
 // fp16's normal range.  Both conversions clamp to +-65504 first, so finite fp32 never becomes inf.
 constexpr float LO_SCALE = 1024.0f;
-constexpr float LO_UNSCALE = 1.0f / 1024.0f;
 __device__ __forceinline__ _Float16 sat_half(float v) { return (_Float16)fminf(fmaxf(v, -65504.0f), 65504.0f); }
 
 __device__ __forceinline__ void split8(const f32x4 a, const f32x4 b, f16x8& hi, f16x8& lo) {

@@ -112,12 +112,6 @@ constexpr int ring_slots(int wn) {
     const int n = free_bytes / (2 * 16 * wn * 64);
     return n > 5 ? 5 : n;            // the static vmcnt counts of the k-loop assume a lookahead of at most 4 k-steps
 }
-template <int N>
-__device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ void dma16(const unsigned char* src, unsigned char* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
 
 // One LDS-DMA instruction per wave (4 bytes per lane): cst[c] = bias[n0 + c], cst[BN + c] = slope[n0 + c], cst[2 BN + c] = plane_slope[n0 + c]
 // for the tile's BN columns, 0 / 1 / 1 where an array is absent or the column is past Cout.  (The plane sink's slopes used to be global loads
@@ -138,7 +132,7 @@ __device__ __forceinline__ void dma_planes_consts(const float* bias, const float
                                      (__attribute__((address_space(3))) void*)(cst + piece * 64), 4, 0, 0);
 }
 
-// X3: the three-term product (the default, "f16x3").  X3 == false ("f16", atmvfi_conv3x3_planes4 with terms = 1): a product is
+// X3: the three-term product (the default, "f16x3").  X3 == false ("f16", atmvfi_conv3p with terms = 1): a product is
 // hi(x) * hi(w) alone -- the lo' fragments are not read, the four cross-term MFMAs per (i, j) are not issued and `cor` does not exist; the
 // DMA of both planes, the ring, every counted wait and both barriers of a k-step are the same source (the ordering rules above rest on
 // which barrier separates a wait from a read, not on how long a phase lasts; the reads that fall away had no rule of their own).  The fused
@@ -940,6 +934,23 @@ static Conv3Plan conv3_plan(int N, int H, int W, int Cin, int Cout, int wn, bool
     return p;
 }
 
+// run-time switches -> template parameters of a launch: the tile width (1..8, conv3_plan) and whether the product has three terms;
+// dispatch_planes<true / false>(f, wn) calls f(std::integral_constant<int, wn>{}, std::bool_constant<X3>{})
+template <bool X3, class F>
+int dispatch_planes(F&& f, int wn) {
+    constexpr std::bool_constant<X3> x3;
+    switch (wn) {
+        case 1: return f(std::integral_constant<int, 1>{}, x3);
+        case 2: return f(std::integral_constant<int, 2>{}, x3);
+        case 3: return f(std::integral_constant<int, 3>{}, x3);
+        case 4: return f(std::integral_constant<int, 4>{}, x3);
+        case 5: return f(std::integral_constant<int, 5>{}, x3);
+        case 6: return f(std::integral_constant<int, 6>{}, x3);
+        case 7: return f(std::integral_constant<int, 7>{}, x3);
+        default: return f(std::integral_constant<int, 8>{}, x3);
+    }
+}
+
 }  // namespace
 
 extern "C" int64_t atmvfi_conv3x3_planes_workspace_floats(int N, int H, int W, int Cin, int Cout) {
@@ -948,159 +959,95 @@ extern "C" int64_t atmvfi_conv3x3_planes_workspace_floats(int N, int H, int W, i
     return p.ksplit > 1 ? (int64_t)p.ksplit * N * H * W * atmvfi::round_up(Cout, 16) : 0;
 }
 
-static int conv3x3_planes_impl(const void* in_hi, const void* in_lo, int64_t in_rows, int N, int H, int W, int Cin, const void* w_hi,
-                               const void* w_lo, int Cout, float* out, int out_ld, const float* bias, const float* prelu, void* out_hi,
-                               void* out_lo, int64_t plane_rows, int out_c0, const float* plane_prelu, void* out_hi2, void* out_lo2,
-                               int64_t plane_rows2, int out_c02, int out_cmin, int wn, float* workspace, int64_t workspace_floats,
-                               const void* h2_w, float* h2_out, int64_t h2_plane, int terms, void* stream);
 
-extern "C" int atmvfi_conv3x3_planes4(const void* in_hi, const void* in_lo, int64_t in_rows, int N, int H, int W, int Cin, const void* w_hi,
-                                       const void* w_lo, int Cout, float* out, int out_ld, const float* bias, const float* prelu,
-                                       void* out_hi, void* out_lo, int64_t plane_rows, int out_c0, const float* plane_prelu, void* out_hi2,
-                                       void* out_lo2, int64_t plane_rows2, int out_c02, int out_cmin, int wn, float* workspace,
-                                       int64_t workspace_floats, int terms, void* stream) {
-    ATMVFI_REQUIRE(terms == 3 || terms == 1, ATMVFI_EINVAL,
-                   "conv3x3_planes: terms must be 3 (f16x3: hi*hi + hi*lo + lo*hi) or 1 (f16: hi*hi only), got %d", terms);
-    ATMVFI_REQUIRE(in_hi && in_lo && w_hi && w_lo && (out || out_hi), ATMVFI_EINVAL, "conv3x3_planes: null pointer");
-    return conv3x3_planes_impl(in_hi, in_lo, in_rows, N, H, W, Cin, w_hi, w_lo, Cout, out, out_ld, bias, prelu, out_hi, out_lo, plane_rows, out_c0,
-                               plane_prelu, out_hi2, out_lo2, plane_rows2, out_c02, out_cmin, wn, workspace, workspace_floats, nullptr, nullptr, 0,
-                               terms, stream);
-}
-
-extern "C" int atmvfi_conv3x3_planes3(const void* in_hi, const void* in_lo, int64_t in_rows, int N, int H, int W, int Cin, const void* w_hi,
-                                       const void* w_lo, int Cout, float* out, int out_ld, const float* bias, const float* prelu,
-                                       void* out_hi, void* out_lo, int64_t plane_rows, int out_c0, const float* plane_prelu, void* out_hi2,
-                                       void* out_lo2, int64_t plane_rows2, int out_c02, int out_cmin, int wn, float* workspace,
-                                       int64_t workspace_floats, void* stream) {
-    return atmvfi_conv3x3_planes4(in_hi, in_lo, in_rows, N, H, W, Cin, w_hi, w_lo, Cout, out, out_ld, bias, prelu, out_hi, out_lo, plane_rows,
-                                  out_c0, plane_prelu, out_hi2, out_lo2, plane_rows2, out_c02, out_cmin, wn, workspace, workspace_floats, 3, stream);
-}
-
-static int conv3x3_planes_impl(const void* in_hi, const void* in_lo, int64_t in_rows, int N, int H, int W, int Cin, const void* w_hi,
-                               const void* w_lo, int Cout, float* out, int out_ld, const float* bias, const float* prelu, void* out_hi,
-                               void* out_lo, int64_t plane_rows, int out_c0, const float* plane_prelu, void* out_hi2, void* out_lo2,
-                               int64_t plane_rows2, int out_c02, int out_cmin, int wn, float* workspace, int64_t workspace_floats,
-                               const void* h2_w, float* h2_out, int64_t h2_plane, int terms, void* stream) {
-    ATMVFI_REQUIRE((out_hi2 == nullptr) == (out_lo2 == nullptr), ATMVFI_EINVAL, "conv3x3_planes: the second plane sink needs both planes");
-    if (out_hi2)
-        ATMVFI_REQUIRE(out_hi && plane_rows2 >= (int64_t)N * H * W && out_c02 >= 0 && out_c02 % 8 == 0 && atmvfi::aligned16(out_hi2) &&
-                           atmvfi::aligned16(out_lo2), ATMVFI_EINVAL,
+// The one host path of the kernel (include/atmvfi.h, atmvfi_conv3p_params): the checks in one order, the plan, the launch(es).  The
+// fused read-out is the same launch with one column block and nothing else to store; its refusals keep the name of the call they describe.
+extern "C" int atmvfi_conv3p(const atmvfi_conv3p_params* p, void* stream) {
+    ATMVFI_REQUIRE(p, ATMVFI_EINVAL, "conv3x3_planes: null parameter block");
+    const bool readout = p->readout_w || p->readout;
+    const int N = p->N, H = p->H, W = p->W, Cin = p->Cin, Cout = p->Cout, terms = p->terms, out_cmin = p->out_cmin;
+    const int64_t in_rows = p->in_rows;
+    if (readout) {
+        ATMVFI_REQUIRE(terms == 3 || terms == 1, ATMVFI_EINVAL,
+                       "conv3x3_planes_readout: terms must be 3 (f16x3) or 1 (f16: the main 3x3 product hi*hi only; the W2 product stays three-term), got %d",
+                       terms);
+        ATMVFI_REQUIRE(p->in_hi && p->in_lo && p->w_hi && p->w_lo && p->readout_w && p->readout, ATMVFI_EINVAL,
+                       "conv3x3_planes_readout: null pointer");
+        ATMVFI_REQUIRE(!p->out && !p->out_hi && !p->out_lo && !p->out_hi2 && !p->out_lo2 && !p->workspace && p->wn == 0, ATMVFI_EINVAL,
+                       "conv3x3_planes_readout: the read-out is the launch's only result: out, both plane sinks, workspace and wn must be unset");
+        ATMVFI_REQUIRE(Cout == 32 || Cout == 64, ATMVFI_EINVAL,
+                       "conv3x3_planes_readout: Cout must be 32 or 64 (one column block of 2 or 4 n-tiles), got %d", Cout);
+        ATMVFI_REQUIRE(p->readout_plane >= (int64_t)N * H * W && atmvfi::aligned16(p->readout_w), ATMVFI_EINVAL,
+                       "conv3x3_planes_readout: contrib_plane must cover N*H*W pixels and w2 must be 16-byte aligned");
+    } else {
+        ATMVFI_REQUIRE(terms == 3 || terms == 1, ATMVFI_EINVAL,
+                       "conv3x3_planes: terms must be 3 (f16x3: hi*hi + hi*lo + lo*hi) or 1 (f16: hi*hi only), got %d", terms);
+        ATMVFI_REQUIRE(p->in_hi && p->in_lo && p->w_hi && p->w_lo && (p->out || p->out_hi), ATMVFI_EINVAL, "conv3x3_planes: null pointer");
+    }
+    const int wn = readout ? Cout / 16 : p->wn;
+    ATMVFI_REQUIRE((p->out_hi2 == nullptr) == (p->out_lo2 == nullptr), ATMVFI_EINVAL, "conv3x3_planes: the second plane sink needs both planes");
+    if (p->out_hi2)
+        ATMVFI_REQUIRE(p->out_hi && p->plane_rows2 >= (int64_t)N * H * W && p->out_c02 >= 0 && p->out_c02 % 8 == 0 &&
+                           atmvfi::aligned16(p->out_hi2) && atmvfi::aligned16(p->out_lo2), ATMVFI_EINVAL,
                        "conv3x3_planes: the second plane sink needs the first one, plane_rows2 >= N*H*W, a channel offset that is a multiple "
                        "of 8 and 16-byte aligned planes");
     ATMVFI_REQUIRE(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, ATMVFI_EINVAL, "conv3x3_planes: bad shape");
     ATMVFI_REQUIRE(in_rows > (int64_t)N * H * W && in_rows * 64 < (1ll << 32), ATMVFI_EINVAL,
                    "conv3x3_planes: in_rows %lld must exceed N*H*W (the zero row) and in_rows * 64 must fit 32 bits", (long long)in_rows);
-    ATMVFI_REQUIRE(atmvfi::aligned16(in_hi) && atmvfi::aligned16(in_lo) && atmvfi::aligned16(w_hi) && atmvfi::aligned16(w_lo) &&
-                       (!bias || atmvfi::aligned16(bias)) && (!prelu || atmvfi::aligned16(prelu)),
+    ATMVFI_REQUIRE(atmvfi::aligned16(p->in_hi) && atmvfi::aligned16(p->in_lo) && atmvfi::aligned16(p->w_hi) && atmvfi::aligned16(p->w_lo) &&
+                       (!p->bias || atmvfi::aligned16(p->bias)) && (!p->prelu || atmvfi::aligned16(p->prelu)),
                    ATMVFI_EALIGN, "conv3x3_planes: pointers (incl. bias/prelu) must be 16-byte aligned");
-    if (out)
-        ATMVFI_REQUIRE(atmvfi::aligned16(out) && out_ld % 4 == 0 && out_cmin >= 0 && out_cmin % 4 == 0 &&
-                           out_ld >= atmvfi::round_up(Cout, 4) - out_cmin,
+    // (`out` is the first STORED channel, column out_cmin of the view: with out_cmin a multiple of 4 it is aligned when the view is)
+    if (p->out)
+        ATMVFI_REQUIRE(atmvfi::aligned16(p->out) && p->out_ld % 4 == 0 && out_cmin >= 0 && out_cmin % 4 == 0 &&
+                           p->out_ld >= atmvfi::round_up(Cout, 4) - out_cmin,
                        ATMVFI_EALIGN, "conv3x3_planes: fp32 output must be 16-byte aligned with ld %% 4 == 0 covering the stored channels");
-    ATMVFI_REQUIRE((out_hi == nullptr) == (out_lo == nullptr), ATMVFI_EINVAL, "conv3x3_planes: plane sink needs both planes");
-    if (out_hi) {
-        ATMVFI_REQUIRE(plane_rows >= (int64_t)N * H * W && out_c0 >= 0 && out_c0 % 8 == 0, ATMVFI_EINVAL,
+    ATMVFI_REQUIRE((p->out_hi == nullptr) == (p->out_lo == nullptr), ATMVFI_EINVAL, "conv3x3_planes: plane sink needs both planes");
+    if (p->out_hi) {
+        ATMVFI_REQUIRE(p->plane_rows >= (int64_t)N * H * W && p->out_c0 >= 0 && p->out_c0 % 8 == 0, ATMVFI_EINVAL,
                        "conv3x3_planes: plane sink needs plane_rows >= N*H*W and a channel offset that is a multiple of 8");
-        ATMVFI_REQUIRE(atmvfi::aligned16(out_hi) && atmvfi::aligned16(out_lo) && (!plane_prelu || atmvfi::aligned16(plane_prelu)),
+        ATMVFI_REQUIRE(atmvfi::aligned16(p->out_hi) && atmvfi::aligned16(p->out_lo) && (!p->plane_prelu || atmvfi::aligned16(p->plane_prelu)),
                        ATMVFI_EALIGN, "conv3x3_planes: plane sink pointers must be 16-byte aligned");
     }
     ATMVFI_REQUIRE(wn >= 0 && wn <= 8, ATMVFI_EINVAL, "conv3x3_planes: wn 0 (auto) or 1..8");
     ATMVFI_REQUIRE(out_cmin >= 0 && out_cmin % 4 == 0, ATMVFI_EINVAL, "conv3x3_planes: out_cmin must be a non-negative multiple of 4");
+    ATMVFI_REQUIRE(!p->workspace || atmvfi::aligned16(p->workspace), ATMVFI_EALIGN, "conv3x3_planes: the split-K workspace must be 16-byte aligned");
     Conv3PDev d;
-    d.in_hi = (const _Float16*)in_hi; d.in_lo = (const _Float16*)in_lo; d.in_rows = in_rows;
+    d.in_hi = (const _Float16*)p->in_hi; d.in_lo = (const _Float16*)p->in_lo; d.in_rows = in_rows;
     d.N = N; d.H = H; d.W = W; d.Cin = Cin;
-    d.w_hi = (const _Float16*)w_hi; d.w_lo = (const _Float16*)w_lo;
+    d.w_hi = (const _Float16*)p->w_hi; d.w_lo = (const _Float16*)p->w_lo;
     d.wrows = atmvfi::round_up(Cout, 16);
     const int t = Cin % 32;
     if (t >= 1 && t <= 8) { d.cf = Cin - t; d.tail = t; } else { d.cf = atmvfi::round_up(Cin, 32); d.tail = 0; }
-    d.Cout = Cout; d.out = out; d.out_ld = out_ld; d.bias = bias; d.prelu = prelu;
-    d.out_hi = (_Float16*)out_hi; d.out_lo = (_Float16*)out_lo; d.plane_rows = plane_rows; d.out_c0 = out_c0; d.plane_prelu = plane_prelu;
-    d.out_hi2 = (_Float16*)out_hi2; d.out_lo2 = (_Float16*)out_lo2; d.plane_rows2 = plane_rows2; d.out_c02 = out_c02;
+    d.Cout = Cout; d.out_ld = p->out_ld; d.bias = p->bias; d.prelu = p->prelu;
+    d.out = p->out ? p->out - out_cmin : nullptr;        // the kernels index the view from its column 0 and store from out_cmin on
+    d.out_hi = (_Float16*)p->out_hi; d.out_lo = (_Float16*)p->out_lo; d.plane_rows = p->plane_rows; d.out_c0 = p->out_c0; d.plane_prelu = p->plane_prelu;
+    d.out_hi2 = (_Float16*)p->out_hi2; d.out_lo2 = (_Float16*)p->out_lo2; d.plane_rows2 = p->plane_rows2; d.out_c02 = p->out_c02;
     d.out_cmin = out_cmin;
     d.tiles_x = (W + TW - 1) / TW;
     d.tiles_y = 0; d.nblocks = 0; d.tchunk = 0;
-    d.h2_w = (const _Float16*)h2_w; d.h2_out = h2_out; d.h2_plane = h2_plane;
+    d.h2_w = (const _Float16*)p->readout_w; d.h2_out = p->readout; d.h2_plane = p->readout_plane;
     const int ntiles = (Cout + 15) / 16;
-    ATMVFI_REQUIRE(!workspace || atmvfi::aligned16(workspace), ATMVFI_EALIGN, "conv3x3_planes: the split-K workspace must be 16-byte aligned");
-    Conv3Plan plan = conv3_plan(N, H, W, Cin, Cout, wn, workspace != nullptr);
+    Conv3Plan plan = conv3_plan(N, H, W, Cin, Cout, wn, p->workspace != nullptr);
     const int ldp = atmvfi::round_up(Cout, 16);
     const long long rows = (long long)N * H * W;
-    if (plan.ksplit > 1 && (long long)plan.ksplit * rows * ldp > workspace_floats) plan = conv3_plan(N, H, W, Cin, Cout, wn, false);
+    if (plan.ksplit > 1 && (long long)plan.ksplit * rows * ldp > p->workspace_floats) plan = conv3_plan(N, H, W, Cin, Cout, wn, false);
     d.ksplit = plan.ksplit; d.cps = plan.cps; d.part_stride = rows * ldp;
-    const int best = plan.wn;
-    Conv3PDev full = d;
+    const Conv3PDev full = d;
     if (plan.ksplit > 1) {
         // first half: raw partial sums of every K range into the workspace (no bias, no activation, no sinks)
-        d.out = workspace; d.out_ld = ldp; d.out_cmin = 0; d.bias = nullptr; d.prelu = nullptr;
+        d.out = p->workspace; d.out_ld = ldp; d.out_cmin = 0; d.bias = nullptr; d.prelu = nullptr;
         d.out_hi = d.out_lo = d.out_hi2 = d.out_lo2 = nullptr; d.plane_prelu = nullptr;
     }
     hipStream_t s = (hipStream_t)stream;
-    int rc;
     // (the tile width and the K split above do not look at `terms`: both modes of a shape take the same plan)
-    if (terms == 3) {
-        switch (best) {
-            case 1: rc = launch_planes<1, true>(d, ntiles, s); break;
-            case 2: rc = launch_planes<2, true>(d, ntiles, s); break;
-            case 3: rc = launch_planes<3, true>(d, ntiles, s); break;
-            case 4: rc = launch_planes<4, true>(d, ntiles, s); break;
-            case 5: rc = launch_planes<5, true>(d, ntiles, s); break;
-            case 6: rc = launch_planes<6, true>(d, ntiles, s); break;
-            case 7: rc = launch_planes<7, true>(d, ntiles, s); break;
-            default: rc = launch_planes<8, true>(d, ntiles, s); break;
-        }
-    } else {
-        switch (best) {
-            case 1: rc = launch_planes<1, false>(d, ntiles, s); break;
-            case 2: rc = launch_planes<2, false>(d, ntiles, s); break;
-            case 3: rc = launch_planes<3, false>(d, ntiles, s); break;
-            case 4: rc = launch_planes<4, false>(d, ntiles, s); break;
-            case 5: rc = launch_planes<5, false>(d, ntiles, s); break;
-            case 6: rc = launch_planes<6, false>(d, ntiles, s); break;
-            case 7: rc = launch_planes<7, false>(d, ntiles, s); break;
-            default: rc = launch_planes<8, false>(d, ntiles, s); break;
-        }
-    }
+    auto launch = [&](auto wnc, auto x3c) { return launch_planes<decltype(wnc)::value, decltype(x3c)::value>(d, ntiles, s); };
+    const int rc = terms == 3 ? dispatch_planes<true>(launch, plan.wn) : dispatch_planes<false>(launch, plan.wn);
     if (rc != ATMVFI_OK || plan.ksplit <= 1) return rc;
     const long long groups = rows * (((Cout + 7) & ~7) >> 2);
     const unsigned blocks = (unsigned)std::min<long long>((groups + 255) / 256, 4096);
-    hipLaunchKernelGGL(conv3_splitk_reduce_kernel, dim3(blocks), dim3(256), 0, s, workspace, d.part_stride, plan.ksplit, rows, ldp, Cout,
+    hipLaunchKernelGGL(conv3_splitk_reduce_kernel, dim3(blocks), dim3(256), 0, s, p->workspace, d.part_stride, plan.ksplit, rows, ldp, Cout,
                        full.bias, full.prelu, full.out, full.out_ld, full.out_cmin, full.out_hi, full.out_lo, (long long)full.plane_rows,
                        full.out_c0, full.plane_prelu, full.out_hi2, full.out_lo2, (long long)full.plane_rows2, full.out_c02);
     return atmvfi::check_launch("conv3x3_planes (split-K reduce)");
-}
-
-extern "C" int atmvfi_conv3x3_planes_readout2(const void* in_hi, const void* in_lo, int64_t in_rows, int N, int H, int W, int Cin,
-                                               const void* w_hi, const void* w_lo, int Cout, const float* bias, const float* prelu,
-                                               const void* w2, float* contrib, int64_t contrib_plane, int terms, void* stream) {
-    ATMVFI_REQUIRE(terms == 3 || terms == 1, ATMVFI_EINVAL,
-                   "conv3x3_planes_readout: terms must be 3 (f16x3) or 1 (f16: the main 3x3 product hi*hi only; the W2 product stays three-term), got %d",
-                   terms);
-    ATMVFI_REQUIRE(in_hi && in_lo && w_hi && w_lo && w2 && contrib, ATMVFI_EINVAL, "conv3x3_planes_readout: null pointer");
-    ATMVFI_REQUIRE(Cout == 32 || Cout == 64, ATMVFI_EINVAL, "conv3x3_planes_readout: Cout must be 32 or 64 (one column block of 2 or 4 n-tiles), got %d", Cout);
-    ATMVFI_REQUIRE(contrib_plane >= (int64_t)N * H * W && atmvfi::aligned16(w2), ATMVFI_EINVAL,
-                   "conv3x3_planes_readout: contrib_plane must cover N*H*W pixels and w2 must be 16-byte aligned");
-    return conv3x3_planes_impl(in_hi, in_lo, in_rows, N, H, W, Cin, w_hi, w_lo, Cout, nullptr, 0, bias, prelu, nullptr, nullptr, 0, 0, nullptr,
-                               nullptr, nullptr, 0, 0, 0, Cout / 16, nullptr, 0, w2, contrib, contrib_plane, terms, stream);
-}
-
-extern "C" int atmvfi_conv3x3_planes_readout(const void* in_hi, const void* in_lo, int64_t in_rows, int N, int H, int W, int Cin,
-                                              const void* w_hi, const void* w_lo, int Cout, const float* bias, const float* prelu,
-                                              const void* w2, float* contrib, int64_t contrib_plane, void* stream) {
-    return atmvfi_conv3x3_planes_readout2(in_hi, in_lo, in_rows, N, H, W, Cin, w_hi, w_lo, Cout, bias, prelu, w2, contrib, contrib_plane, 3, stream);
-}
-
-extern "C" int atmvfi_conv3x3_planes2(const void* in_hi, const void* in_lo, int64_t in_rows, int N, int H, int W, int Cin, const void* w_hi,
-                                       const void* w_lo, int Cout, float* out, int out_ld, const float* bias, const float* prelu,
-                                       void* out_hi, void* out_lo, int64_t plane_rows, int out_c0, const float* plane_prelu, void* out_hi2,
-                                       void* out_lo2, int64_t plane_rows2, int out_c02, int out_cmin, int wn, void* stream) {
-    return atmvfi_conv3x3_planes3(in_hi, in_lo, in_rows, N, H, W, Cin, w_hi, w_lo, Cout, out, out_ld, bias, prelu, out_hi, out_lo, plane_rows,
-                                  out_c0, plane_prelu, out_hi2, out_lo2, plane_rows2, out_c02, out_cmin, wn, nullptr, 0, stream);
-}
-
-extern "C" int atmvfi_conv3x3_planes(const void* in_hi, const void* in_lo, int64_t in_rows, int N, int H, int W, int Cin, const void* w_hi,
-                                      const void* w_lo, int Cout, float* out, int out_ld, const float* bias, const float* prelu,
-                                      void* out_hi, void* out_lo, int64_t plane_rows, int out_c0, const float* plane_prelu, int out_cmin,
-                                      int wn, void* stream) {
-    return atmvfi_conv3x3_planes2(in_hi, in_lo, in_rows, N, H, W, Cin, w_hi, w_lo, Cout, out, out_ld, bias, prelu, out_hi, out_lo, plane_rows,
-                                  out_c0, plane_prelu, nullptr, nullptr, 0, 0, out_cmin, wn, stream);
 }

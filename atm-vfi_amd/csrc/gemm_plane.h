@@ -6,18 +6,8 @@
 #pragma once
 #include "common.h"
 #include "gemm_common.h"
+#include "plane_common.h"      // f16x8, LO_UNSCALE, swz64, dma16, wait_vm
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-constexpr float LO_UNSCALE = 1.0f / 1024.0f;           // x = hi + lo' / 1024
-
-// 16-byte slot swizzle of the 64-byte LDS rows
-__device__ __forceinline__ int swz64(int row) { return ((row >> 2) & 1) << 1; }
-// one LDS-DMA piece: 16 bytes per lane from `src` (per lane) to wave-uniform base + lane * 16 B
-__device__ __forceinline__ void dma16(const unsigned char* src, unsigned char* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
 __device__ __forceinline__ void lds_write16f(unsigned addr, const f32x4& v) {
     asm volatile("ds_write_b128 %0, %1" ::"v"(addr), "v"(v) : "memory");
 }
@@ -25,8 +15,6 @@ template <int OFF>
 __device__ __forceinline__ void lds_read16f(f32x4& d, unsigned addr) {
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF) : "memory");
 }
-template <int N>
-__device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 namespace atmvfi {
 

@@ -488,7 +488,7 @@ __global__ __launch_bounds__(256) void final_residual_kernel(const float* __rest
 }
 
 // refine_head.1 (nn.Conv2d(C, 3, 3, padding 1) + PReLU) -> 2 * sigmoid - 1 -> += I_t -> clamp (network_base.py:257-260, 429, 532-533) from
-// the per-pixel tap contributions T[(tap * 3 + o)][pixel] = sum_c w[o][c][tap] * r1[pixel][c] that atmvfi_conv3x3_planes_readout left
+// the per-pixel tap contributions T[(tap * 3 + o)][pixel] = sum_c w[o][c][tap] * r1[pixel][c] that atmvfi_conv3p's read-out left
 // (planar fp32): out[o][p] = bias[o] + sum over taps of T[tap * 3 + o][p + offset(tap)], taps outside the image contributing nothing
 // (the zero padding of the convolution).  One thread per pixel; every load is coalesced.
 __global__ __launch_bounds__(256) void refine_tail_kernel(const float* __restrict__ T, long long plane, const float* __restrict__ bias,

@@ -25,7 +25,7 @@
 //   E  layer 3 (stride 2) on the matrix cores, one output row of 16 pixels per wave, weights from LDS (staged once per workgroup), bias,
 //      PReLU, split, and the result goes out as the split planes the next layer reads (chunk-major, include/atmvfi.h).
 // Halo recompute: layer 1 x1.27, layer 2 x1.13 (incl. the junk columns).  HBM traffic: the frames in, the C1 planes out.
-#include "common.h"
+#include "plane_common.h"      // f16x8, LO_UNSCALE
 
 #ifdef ATMVFI_STAMP
 static unsigned long long* g_stem_stamp = nullptr;
@@ -36,8 +36,6 @@ extern "C" void atmvfi_debug_set_stem_stamp_buffer(void* p) { g_stem_stamp = (un
 #endif
 
 namespace {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 struct StemArgs {
     const float* x;                       // [F, H, W, 4] fp32 (channel 3 unused)
@@ -70,7 +68,6 @@ constexpr int NM2 = (16 * AW + E0W + 15) / 16;             // 38 M-tiles of laye
 constexpr int ACT_ROWS = 16 * NM2 + 2 * AW + 2 + 6;        // 686: every row a (junk) fragment can touch
 constexpr int ACT_BYTES = ACT_ROWS * 64;
 constexpr int HALF = (E0W + 1) / 2;                        // 17 even columns, then 16 odd ones
-constexpr float LO_UNSCALE = 1.0f / 1024.0f;
 
 // 16-byte slot swizzle of the 64-byte LDS rows: conflict-free for a weight fragment's ds_read_b128 (16 consecutive rows, slot = lane
 // group), 1.36 cycles per conflict-free cycle for the activation fragments (the lane groups of one read sit at different taps) and

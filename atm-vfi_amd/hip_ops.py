@@ -62,6 +62,22 @@ class GemmParams(ctypes.Structure):
     ]
 
 
+class Conv3pParams(ctypes.Structure):
+    """``atmvfi_conv3p_params`` (include/atmvfi.h).  Pointer fields are ``c_f``: ``LaunchPlan.add_op`` scans them."""
+    _fields_ = [
+        ("in_hi", c_f), ("in_lo", c_f), ("in_rows", ctypes.c_int64),
+        ("N", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("Cin", ctypes.c_int32),
+        ("w_hi", c_f), ("w_lo", c_f), ("Cout", ctypes.c_int32),
+        ("bias", c_f), ("prelu", c_f),
+        ("out", c_f), ("out_ld", ctypes.c_int32), ("out_cmin", ctypes.c_int32),
+        ("out_hi", c_f), ("out_lo", c_f), ("plane_rows", ctypes.c_int64), ("out_c0", ctypes.c_int32), ("plane_prelu", c_f),
+        ("out_hi2", c_f), ("out_lo2", c_f), ("plane_rows2", ctypes.c_int64), ("out_c02", ctypes.c_int32),
+        ("wn", ctypes.c_int32), ("workspace", c_f), ("workspace_floats", ctypes.c_int64),
+        ("readout_w", c_f), ("readout", c_f), ("readout_plane", ctypes.c_int64),
+        ("terms", ctypes.c_int32),
+    ]
+
+
 class PlanArg(ctypes.Union):
     _fields_ = [("u", ctypes.c_uint64), ("i", ctypes.c_int64), ("f", ctypes.c_double)]
 
@@ -99,18 +115,13 @@ SIGNATURES = {
     "atmvfi_conv3x3_weight_halves": (c_l, [c_i, c_i]),
     "atmvfi_pack_weight_conv3x3": (c_i, [c_f, c_f, c_f, c_i, c_i, c_f]),
     "atmvfi_conv3x3_f16x3": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_i, c_f, c_i, c_f, c_f, c_f, c_f, c_l, c_f, c_i, c_i, c_f]),
-    "atmvfi_conv3x3_planes": (c_i, [c_f, c_f, c_l, c_i, c_i, c_i, c_i, c_f, c_f, c_i, c_f, c_i, c_f, c_f, c_f, c_f, c_l, c_i, c_f, c_i, c_i, c_f]),
+    "atmvfi_conv3p": (c_i, [ctypes.POINTER(Conv3pParams), c_f]),
     "atmvfi_flow_warp_up2": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f]),
     "atmvfi_flow_warp_up2_tiled": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f]),
     "atmvfi_image_pyramid": (c_i, [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f]),
     "atmvfi_image_pyramid_pack": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f]),
     "atmvfi_head1x1_planes": (c_i, [c_f, c_f, c_l, c_l, c_i, c_f, c_f, c_i, c_f, c_i, c_f]),
-    "atmvfi_conv3x3_planes2": (c_i, [c_f, c_f, c_l, c_i, c_i, c_i, c_i, c_f, c_f, c_i, c_f, c_i, c_f, c_f, c_f, c_f, c_l, c_i, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_f]),
-    "atmvfi_conv3x3_planes3": (c_i, [c_f, c_f, c_l, c_i, c_i, c_i, c_i, c_f, c_f, c_i, c_f, c_i, c_f, c_f, c_f, c_f, c_l, c_i, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_f, c_l, c_f]),
     "atmvfi_conv3x3_planes_workspace_floats": (c_l, [c_i, c_i, c_i, c_i, c_i]),
-    "atmvfi_conv3x3_planes_readout": (c_i, [c_f, c_f, c_l, c_i, c_i, c_i, c_i, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_l, c_f]),
-    "atmvfi_conv3x3_planes4": (c_i, [c_f, c_f, c_l, c_i, c_i, c_i, c_i, c_f, c_f, c_i, c_f, c_i, c_f, c_f, c_f, c_f, c_l, c_i, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_f, c_l, c_i, c_f]),
-    "atmvfi_conv3x3_planes_readout2": (c_i, [c_f, c_f, c_l, c_i, c_i, c_i, c_i, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_l, c_i, c_f]),
     "atmvfi_refine_tail": (c_i, [c_f, c_l, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f]),
     "atmvfi_layernorm": (c_i, [c_f, c_i, c_l, c_i, c_f, c_f, c_i, c_f, c_f, c_l, c_i, c_f, c_f, c_i, c_f]),
     "atmvfi_dwconv3x3_gelu": (c_i, [c_f, c_i, c_f, c_i, c_f, c_f, c_i, c_i, c_i, c_i, c_f, c_f, c_i, c_f]),
@@ -293,7 +304,7 @@ class Planes:
 class TPtr(ctypes.c_void_p):
     """A device pointer that remembers the tensor it was derived from (``src``).  Launch plans classify pointer arguments by that tensor
     -- per-call memory or workspace -- never by what allocation the raw address happens to fall into: a biased or one-past-the-end
-    pointer (the compact fp32 view of the 3x3 plane kernel passes ``buffer - 4 * out_cmin``) lies inside a NEIGHBOURING allocation."""
+    pointer lies inside a NEIGHBOURING allocation."""
     __slots__ = ("src",)
 
 
@@ -896,15 +907,16 @@ class HipOps:
             raise ValueError(f"conv3x3_planes: input planes [{x.rows} (+{x.ld_rows - x.rows} spare), {x.c}] do not fit {n}x{h}x{wd} pixels x {cin} channels "
                              "(one spare zero row is required)")
         cout = w.cout
-        old = 0
-        out_ptr = _ptr(out)
+        old = out_addr = 0
         if out is not None:
             old, on, oh, ow, oc = nhwc_view(out, "conv3x3_planes.out")
+            # the block takes the address of the first STORED channel: the start of a compact buffer of just the channels [out_cmin, cout),
+            # column out_cmin of a full-width view (out_cmin % 4 == 0 keeps the 16-byte alignment)
             if (on, oh, ow) == (n, h, wd) and oc == cout - out_cmin and out_cmin > 0:
-                # compact view of just the stored channels [out_cmin, cout): the kernel never touches columns below out_cmin, so the
-                # base may point that many floats in front of the buffer (out_cmin % 4 == 0 keeps the 16-byte alignment)
-                out_ptr = _ptr(out, -4 * out_cmin)       # a pointer IN FRONT of its buffer: attributed to `out` by the TPtr, never by its address
-            elif (on, oh, ow, oc) != (n, h, wd, cout):
+                out_addr = out.data_ptr()
+            elif (on, oh, ow, oc) == (n, h, wd, cout):
+                out_addr = out.data_ptr() + 4 * out_cmin
+            else:
                 raise ValueError(f"conv3x3_planes: out {tuple(out.shape)} != [{n},{h},{wd},{cout}] (or {cout - out_cmin} channels: compact)")
         elif planes is None:
             raise ValueError("conv3x3_planes: no output")
@@ -922,18 +934,20 @@ class HipOps:
             raise ValueError("conv3x3_planes: the split-K workspace must be a contiguous CUDA fp32 tensor")
         if self.plane_terms not in (1, 3):
             raise ValueError(f"plane_terms must be 3 (f16x3) or 1 (f16), got {self.plane_terms!r}")
-        # (three terms: the entry point without a term count -- it forwards with 3 -- so that a recorded plan of the default mode holds the same ops as before)
-        fn, terms = (self.lib.atmvfi_conv3x3_planes3, ()) if self.plane_terms == 3 else (self.lib.atmvfi_conv3x3_planes4, (self.plane_terms,))
-        self._run("conv3x3_planes", meta, fn, _ptr(x.t[0], coff), _ptr(x.t[1], coff), x.ld_rows,
-                  n, h, wd, cin, _ptr(w.hi3), _ptr(w.lo3), cout, out_ptr, old, _ptr(bias), _ptr(prelu),
-                  _ptr(planes.t[0]) if planes is not None else None, _ptr(planes.t[1]) if planes is not None else None,
-                  planes.ld_rows if planes is not None else 0, planes_c0, _ptr(planes_prelu) if planes is not None else None,
-                  _ptr(planes2.t[0]) if planes2 is not None else None, _ptr(planes2.t[1]) if planes2 is not None else None,
-                  planes2.ld_rows if planes2 is not None else 0, planes2_c0, out_cmin, wn, _ptr(workspace),
-                  workspace.numel() if workspace is not None else 0, *terms, self._stream())
+        p = Conv3pParams(in_hi=x.t[0].data_ptr() + coff, in_lo=x.t[1].data_ptr() + coff, in_rows=x.ld_rows, N=n, H=h, W=wd, Cin=cin,
+                         w_hi=w.hi3.data_ptr(), w_lo=w.lo3.data_ptr(), Cout=cout, bias=_ptr(bias), prelu=_ptr(prelu),
+                         out=out_addr or None, out_ld=old, out_cmin=out_cmin, out_c0=planes_c0, out_c02=planes2_c0, wn=wn,
+                         workspace=_ptr(workspace), workspace_floats=workspace.numel() if workspace is not None else 0, terms=self.plane_terms)
+        if planes is not None:
+            p.out_hi, p.out_lo, p.plane_rows, p.plane_prelu = planes.t[0].data_ptr(), planes.t[1].data_ptr(), planes.ld_rows, _ptr(planes_prelu)
+        if planes2 is not None:
+            p.out_hi2, p.out_lo2, p.plane_rows2 = planes2.t[0].data_ptr(), planes2.t[1].data_ptr(), planes2.ld_rows
+        p._srcs = (x.t, w.hi3, w.lo3, out, bias, prelu, planes.t if planes is not None else None, planes_prelu,
+                   planes2.t if planes2 is not None else None, workspace)
+        self._run("conv3x3_planes", meta, self.lib.atmvfi_conv3p, ctypes.byref(p), self._stream())
 
     def pack_readout(self, w: torch.Tensor) -> torch.Tensor:
-        """Operand of ``atmvfi_conv3x3_planes_readout``: refine_head.1's weight [3, C, 3, 3] (C = 32 or 64) as the 27 x C matrix
+        """The ``readout_w`` operand of ``atmvfi_conv3p``: refine_head.1's weight [3, C, 3, 3] (C = 32 or 64) as the 27 x C matrix
         W2[(tap, o)][c], hi / lo' split, in the producing kernel's register order: fp16 [plane][row tile 2][k-step C / 32][lane][8] with
         lane = 16 g + r -> row 16 t + r, and the lane's eight k values = its four channels of n-tile 2 kk and of n-tile 2 kk + 1
         (channels 32 kk + cb(g) + e and 32 kk + 16 + cb(g) + e, cb = {0, 8, 4, 12}[g]).  Host-side torch ops, once per parameter version."""
@@ -968,9 +982,11 @@ class HipOps:
         meta = {"flops": 2.0 * n * h * wd * w.cout * (w.cin * 9 + 27), "bytes": 4.0 * n * h * wd * (w.cin + 27), "shape": f"M{n * h * wd} N{w.cout} K{w.cin * 9} +27"}
         if self.plane_terms not in (1, 3):
             raise ValueError(f"plane_terms must be 3 (f16x3) or 1 (f16), got {self.plane_terms!r}")
-        fn, terms = (self.lib.atmvfi_conv3x3_planes_readout, ()) if self.plane_terms == 3 else (self.lib.atmvfi_conv3x3_planes_readout2, (self.plane_terms,))
-        self._run("conv3x3_planes", meta, fn, _ptr(x.t[0]), _ptr(x.t[1]), x.ld_rows, n, h, wd, w.cin,
-                  _ptr(w.hi3), _ptr(w.lo3), w.cout, _ptr(bias), _ptr(prelu), _ptr(w2), _ptr(contrib), contrib.shape[1], *terms, self._stream())
+        p = Conv3pParams(in_hi=x.t[0].data_ptr(), in_lo=x.t[1].data_ptr(), in_rows=x.ld_rows, N=n, H=h, W=wd, Cin=w.cin,
+                         w_hi=w.hi3.data_ptr(), w_lo=w.lo3.data_ptr(), Cout=w.cout, bias=_ptr(bias), prelu=_ptr(prelu),
+                         readout_w=w2.data_ptr(), readout=contrib.data_ptr(), readout_plane=contrib.shape[1], terms=self.plane_terms)
+        p._srcs = (x.t, w.hi3, w.lo3, bias, prelu, w2, contrib)
+        self._run("conv3x3_planes", meta, self.lib.atmvfi_conv3p, ctypes.byref(p), self._stream())
 
     def refine_tail(self, contrib, bias, slope, it, it_sum, it_clamped):
         """out = clamp(it + 2 * sigmoid(PReLU(bias + sum of the nine shifted tap contributions)) - 1): refine_head.1 + the residual."""

@@ -1595,7 +1595,7 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
                            in_shape=(b, h2, w2, 2 * rh))
                 # refine_head.0 -> refine_head.1 -> 2 sigmoid - 1 -> += -> clamp in two launches; the 64-channel full-resolution
                 # map r1 never reaches HBM: the first launch leaves 27 "tap contributions" per pixel, the second adds the nine
-                # shifted ones of every output pixel (include/atmvfi.h, atmvfi_conv3x3_planes_readout)
+                # shifted ones of every output pixel (include/atmvfi.h, atmvfi_conv3p_params: the fused read-out)
                 contrib = self.buf("tail_contrib", 27, b * H * W)
                 ops.conv3x3_planes_readout(bufA_p, b, H, W, P["pk:refine_head.0.0.weight"], P["refine_head.0.0.bias"],
                                            P["refine_head.0.1.weight"], P["readout"], contrib)

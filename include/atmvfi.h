@@ -110,7 +110,7 @@ typedef struct atmvfi_gemm_params {
        planes in the same chunk-major layout with out_plane_rows rows per chunk: channel co of output row r goes to plane row
        r % out_rpg, channel out_plane_c0 + (r / out_rpg) * out_plane_gc + co (out_rpg == 0: row r, channel out_plane_c0 + co;
        DECONV: r = output pixel n*Ho*Wo + y*Wo + x; with out_row_map, r is the mapped row).  Channel offsets are multiples of 4;
-       channels past Cout inside the last group of 4 are written as zero.  This is the input format of atmvfi_conv3x3_planes
+       channels past Cout inside the last group of 4 are written as zero.  This is the input format of atmvfi_conv3p
        and of atmvfi_gemm's in_hi/in_lo: consecutive contraction layers hand activations over without an fp32 copy. */
     void* out_hi;
     void* out_lo;
@@ -217,50 +217,82 @@ int atmvfi_conv3x3_f16x3(const float* in, int in_ld, int N, int H, int W, int Ci
  * 1..8 n-tiles of 16 output channels per workgroup, picked per layer from a cost model.  Per call: schedule -1 = cost model,
  * 0 = row, 1 = half; wn 0 = cost model, 1..8 = n-tiles per workgroup (parity tests reach every instance this way; results do not
  * depend on either).  The library keeps no process-wide override. */
-/* The same convolution on SPLIT-PLANE input (csrc/conv3x3_planes.hip): the activations are the two fp16 planes (hi, lo', chunk major
- * [ceil(Cin/32)][in_rows][32], row = pixel n*H*W + y*W + x) that the producing layer's sink wrote, so the input halo goes
- * global -> LDS by LDS-DMA with no register staging and no conversion, and the two waves of each SIMD run one phase apart (one
- * issues MFMAs while the other reads fragments and issues DMA).  Bit-identical to atmvfi_conv3x3_f16x3 on the same values.
- * Contract of the input planes: in_rows > N*H*W and row N*H*W of every chunk is ZERO (it is the source of the halo pixels that
- * fall outside the image; atm-vfi_amd's Planes.alloc reserves it); pad channels of the last chunk are zero; in_rows * 64 < 2^32.
- * Outputs: fp32 NHWC view `out` (may be NULL; only channels >= out_cmin, a multiple of 4, are stored: columns below are
- * never touched, so `out` may point out_cmin floats in front of a compact buffer of just the stored channels) and / or the plane sink
- * out_hi / out_lo (may be NULL; not both NULL) at channel offset out_c0 (multiple of 8) of a plane buffer with plane_rows rows,
- * through plane_prelu (as atmvfi_conv3x3_f16x3); plane channels from Cout up to the next multiple of 8 are written as zero.
- * wn: 0 = pick the tile width (n-tiles of 16 output channels per workgroup) from the cost model, 1..8 = force it (tests, sweeps). */
-int atmvfi_conv3x3_planes(const void* in_hi, const void* in_lo, int64_t in_rows, int N, int H, int W, int Cin, const void* w_hi,
-                          const void* w_lo, int Cout, float* out, int out_ld, const float* bias, const float* prelu, void* out_hi,
-                          void* out_lo, int64_t plane_rows, int out_c0, const float* plane_prelu, int out_cmin, int wn, void* stream);
-/* The same with a SECOND, raw plane sink (out_hi2 / out_lo2, plane_rows2 rows per chunk, channel offset out_c02, a multiple of 8; needs
- * the first sink): a decoder map of the reference goes on twice -- through the next stage's leading nn.PReLU into that stage's deconv
- * (network_base.py:209,215: the first sink with plane_prelu) and as it is into the refiner's strided convs (network_base.py:421-424,
- * torch.cat([feat, dec], 1): atmvfi_gemm CONV mode with in_hi2 / in_lo2 reads it). */
-int atmvfi_conv3x3_planes2(const void* in_hi, const void* in_lo, int64_t in_rows, int N, int H, int W, int Cin, const void* w_hi,
-                           const void* w_lo, int Cout, float* out, int out_ld, const float* bias, const float* prelu, void* out_hi,
-                           void* out_lo, int64_t plane_rows, int out_c0, const float* plane_prelu, void* out_hi2, void* out_lo2,
-                           int64_t plane_rows2, int out_c02, int out_cmin, int wn, void* stream);
-/* The same with SPLIT-K for launches whose tiles leave most of the chip idle (small frames: the motion-MLP layers of network_lite at
- * 256 x 256 are 22 workgroups walking 200 k-steps each): with a `workspace` of at least atmvfi_conv3x3_planes_workspace_floats() floats
- * (16-byte aligned; NULL / too small: no split) the K range is cut into up to 8 ranges of whole 32-channel chunks, one workgroup per
- * (tile, range) writes raw fp32 partial sums into the workspace and a second kernel adds them IN RANGE ORDER and runs the epilogue
- * (bias, PReLU, fp32 rows, plane sinks).  Run-to-run deterministic; differs from the unsplit launch by fp32 summation order only
- * (the reference's conv, network_base.py:20-25, fixes no order either).  atmvfi_conv3x3_planes_workspace_floats returns 0 when the
- * launcher would not split that shape on this device. */
+/* The same convolution on SPLIT-PLANE input (csrc/conv3x3_planes.hip), as ONE call on a parameter block: the activations are the two
+ * fp16 planes (hi, lo', chunk major [ceil(Cin/32)][in_rows][32], row = pixel n*H*W + y*W + x) that the producing layer's sink wrote, so
+ * the input halo goes global -> LDS by LDS-DMA with no register staging and no conversion, and the two waves of each SIMD run one phase
+ * apart (one issues MFMAs while the other reads fragments and issues DMA).  Bit-identical to atmvfi_conv3x3_f16x3 on the same values.
+ * A zeroed block plus in_hi / in_lo / in_rows, N / H / W / Cin, w_hi / w_lo / Cout, one output and terms is the plain convolution; fields
+ * are only ever appended and zero means off (as atmvfi_gemm_params), so a block of an older caller keeps its meaning.
+ *  - Input planes.  in_rows > N*H*W and row N*H*W of every chunk is ZERO (it is the source of the halo pixels that fall outside the
+ *    image; atm-vfi_amd's Planes.alloc reserves it); pad channels of the last chunk are zero; in_rows * 64 < 2^32.
+ *  - fp32 output (may be NULL).  `out` is the ADDRESS OF THE FIRST STORED CHANNEL: column out_cmin (a multiple of 4) of an NHWC view
+ *    whose pixels are out_ld floats apart.  Only channels out_cmin .. Cout are stored, columns below are never touched; the launcher
+ *    forms the view's base out - out_cmin itself, so a caller never holds a pointer outside its buffer -- neither for a full-width view
+ *    (out = view + out_cmin, out_ld >= round_up(Cout, 4)) nor for a compact buffer of just the stored channels (out = the buffer,
+ *    out_ld >= round_up(Cout, 4) - out_cmin).
+ *  - First plane sink out_hi / out_lo (may be NULL; `out` and the sink not both NULL): the result once more as split planes at channel
+ *    offset out_c0 (a multiple of 8) of a plane buffer with plane_rows >= N*H*W rows per chunk, through a per-channel PReLU of its own
+ *    (plane_prelu, padded to a multiple of 32 floats, or NULL; as atmvfi_conv3x3_f16x3); plane channels from Cout up to the next
+ *    multiple of 8 are written as zero.
+ *  - Second, RAW plane sink out_hi2 / out_lo2 (plane_rows2 rows per chunk, channel offset out_c02, a multiple of 8; needs the first
+ *    sink): a decoder map of the reference goes on twice -- through the next stage's leading nn.PReLU into that stage's deconv
+ *    (network_base.py:209,215: the first sink with plane_prelu) and as it is into the refiner's strided convs (network_base.py:421-424,
+ *    torch.cat([feat, dec], 1): atmvfi_gemm CONV mode with in_hi2 / in_lo2 reads it).
+ *  - wn: 0 = pick the tile width (n-tiles of 16 output channels per workgroup) from the cost model, 1..8 = force it (tests, sweeps).
+ *  - SPLIT-K for launches whose tiles leave most of the chip idle (small frames: the motion-MLP layers of network_lite at 256 x 256
+ *    are 22 workgroups walking 200 k-steps each): with a `workspace` of at least atmvfi_conv3x3_planes_workspace_floats() floats
+ *    (16-byte aligned; NULL / too small: no split) the K range is cut into up to 8 ranges of whole 32-channel chunks, one workgroup per
+ *    (tile, range) writes raw fp32 partial sums into the workspace and a second kernel adds them IN RANGE ORDER and runs the epilogue
+ *    (bias, PReLU, fp32 rows, plane sinks).  Run-to-run deterministic; differs from the unsplit launch by fp32 summation order only
+ *    (the reference's conv, network_base.py:20-25, fixes no order either).  atmvfi_conv3x3_planes_workspace_floats returns 0 when the
+ *    launcher would not split that shape on this device.
+ *  - Fused READ-OUT (readout_w non-null; a mode of the same call): the tail of the refiner in two launches instead of three, without the
+ *    64-channel full-resolution map r1 ever reaching HBM (network_base.py:257-260 refine_head = conv(2c, c) + PReLU, conv(c, 3) +
+ *    PReLU; :429 2 * sigmoid - 1; :532-533 +=, clamp).  This call is refine_head.0 (Cout = 32 or 64: one column block) whose epilogue
+ *    multiplies the activated tile -- still in registers, in the accumulator layout, which is the B-operand layout of the next MFMA --
+ *    by the 27 x Cout matrix W2[(tap, o)][c] = refine_head.1's weight [o][c][tap] (f16x3 like every contraction) and stores the 27
+ *    per-pixel "tap contributions" as planar fp32 readout[(tap * 3 + o) * readout_plane + pixel], readout_plane >= N*H*W.  readout_w:
+ *    fp16 [plane hi / lo'][row tile 2][k-step Cout / 32][lane 64][8] in the kernel's register order, 16-byte aligned
+ *    (hip_ops.HipOps.pack_readout builds it).  The tile IS the result: out, both sinks, workspace and wn must be unset (anything else:
+ *    ATMVFI_EINVAL before any launch; the launcher takes wn = Cout / 16).  atmvfi_refine_tail then forms out[o][p] = bias[o] + sum over
+ *    the nine taps of readout[tap * 3 + o][p + offset(tap)] (taps outside the image contribute nothing: the convolution's zero
+ *    padding), PReLU(slope), 2 * sigmoid - 1, + it, and the clamped frame -- the outputs of atmvfi_final_residual.
+ *  - terms, the NUMBER OF TERMS of a product: 3 = hi*hi + hi*lo' + lo'*hi (f16x3), 1 = hi*hi alone (the single-pass fp16 mode, see
+ *    ATMVFI_PREC_F16: one MFMA per product into the one accumulator, same k order, same tile width and K split as with 3).  The input
+ *    planes, the weight planes and every output rule are unchanged: both lo' planes must still be passed, and the plane sinks still
+ *    write both planes of the launch's own fp32 result.  The read-out's 27-row W2 product on the activated tile is three-term in both:
+ *    it forms the output residual and costs next to nothing.  Any other value, 0 included: ATMVFI_EINVAL before any launch. */
+typedef struct atmvfi_conv3p_params {
+    const void* in_hi;
+    const void* in_lo;
+    int64_t in_rows;
+    int32_t N, H, W, Cin;
+    const void* w_hi;             /* atmvfi_pack_weight_conv3x3 */
+    const void* w_lo;
+    int32_t Cout;
+    const float* bias;            /* [Cout] or NULL */
+    const float* prelu;           /* [Cout] or NULL */
+    float* out;
+    int32_t out_ld, out_cmin;
+    void* out_hi;
+    void* out_lo;
+    int64_t plane_rows;
+    int32_t out_c0;
+    const float* plane_prelu;
+    void* out_hi2;
+    void* out_lo2;
+    int64_t plane_rows2;
+    int32_t out_c02;
+    int32_t wn;
+    float* workspace;
+    int64_t workspace_floats;
+    const void* readout_w;
+    float* readout;
+    int64_t readout_plane;
+    int32_t terms;
+} atmvfi_conv3p_params;
+int atmvfi_conv3p(const atmvfi_conv3p_params* p, void* stream);
 int64_t atmvfi_conv3x3_planes_workspace_floats(int N, int H, int W, int Cin, int Cout);
-int atmvfi_conv3x3_planes3(const void* in_hi, const void* in_lo, int64_t in_rows, int N, int H, int W, int Cin, const void* w_hi,
-                           const void* w_lo, int Cout, float* out, int out_ld, const float* bias, const float* prelu, void* out_hi,
-                           void* out_lo, int64_t plane_rows, int out_c0, const float* plane_prelu, void* out_hi2, void* out_lo2,
-                           int64_t plane_rows2, int out_c02, int out_cmin, int wn, float* workspace, int64_t workspace_floats, void* stream);
-/* The same with the NUMBER OF TERMS of a product: 3 = hi*hi + hi*lo' + lo'*hi (f16x3: what every entry point above computes; they forward
- * here with 3), 1 = hi*hi alone (the single-pass fp16 mode, see ATMVFI_PREC_F16: one MFMA per product into the one accumulator, same k
- * order, same tile width and K split as with 3).  The input planes, the weight planes and every output rule are unchanged: both lo'
- * planes must still be passed, and the plane sinks still write both planes of the launch's own fp32 result.  Any other value:
- * ATMVFI_EINVAL before any launch. */
-int atmvfi_conv3x3_planes4(const void* in_hi, const void* in_lo, int64_t in_rows, int N, int H, int W, int Cin, const void* w_hi,
-                           const void* w_lo, int Cout, float* out, int out_ld, const float* bias, const float* prelu, void* out_hi,
-                           void* out_lo, int64_t plane_rows, int out_c0, const float* plane_prelu, void* out_hi2, void* out_lo2,
-                           int64_t plane_rows2, int out_c02, int out_cmin, int wn, float* workspace, int64_t workspace_floats, int terms,
-                           void* stream);
 /* ------------------------------------------------------------------------------------
  * LayerNorm over the channel axis of token rows (eps 1e-5, affine), optional gather.
  * Replaces nn.LayerNorm at attention.py:316 (norm1 on windowed tokens), :333 (norm2) and
@@ -370,7 +402,7 @@ int atmvfi_warp_blend(const float* im0, const float* im1 /*[B,3,H,W] (pre-warped
                       int B, int H, int W, void* stream);
 /* The same with a plane sink for the pack: the 15 values and one zero as split planes (atmvfi_split_planes layout, pack_rows rows per
  * chunk, row = pixel b*H*W + y*W + x) at channels pack_c0 .. pack_c0 + 16 (pack_c0 a multiple of 4) -- the operand format of
- * atmvfi_conv3x3_planes, which the refiner's first conv runs on.  pack_hi / pack_lo may be NULL (= atmvfi_warp_blend). */
+ * atmvfi_conv3p, which the refiner's first conv runs on.  pack_hi / pack_lo may be NULL (= atmvfi_warp_blend). */
 int atmvfi_warp_blend_planes(const float* im0, const float* im1, const float* motion, int motion_ld, int64_t motion_bstride,
                              float* i0w, float* i1w, float* it, float* flow0_out, float* flow1_out, float* mask1_out, float* mask2_out,
                              const float* orig0, const float* orig1, float* pack15, int pack_ld, void* pack_hi, void* pack_lo,
@@ -466,24 +498,8 @@ int atmvfi_pack_frames(const float* im0, const float* im1, float* dst /*[2B,H,W,
 int atmvfi_final_residual(const float* it /*[B,3,H,W]*/, const float* r, int r_ld,
                           float* it_sum, float* it_clamped, int B, int H, int W, void* stream);
 
-/* The tail of the refiner in two launches instead of three, without the 64-channel full-resolution map r1 ever reaching HBM
- * (network_base.py:257-260 refine_head = conv(2c, c) + PReLU, conv(c, 3) + PReLU; :429 2 * sigmoid - 1; :532-533 += , clamp):
- *  - atmvfi_conv3x3_planes_readout: refine_head.0 as atmvfi_conv3x3_planes (Cout = 32 or 64: one column block) whose epilogue multiplies
- *    the activated tile -- still in registers, in the accumulator layout, which is the B-operand layout of the next MFMA -- by the
- *    27 x Cout matrix W2[(tap, o)][c] = refine_head.1's weight [o][c][tap] (f16x3 like every contraction) and stores the 27 per-pixel
- *    "tap contributions" as planar fp32 contrib[(tap * 3 + o) * contrib_plane + pixel].  w2: fp16 [plane hi / lo'][row tile 2]
- *    [k-step Cout / 32][lane 64][8] in the kernel's register order (hip_ops.HipOps.pack_readout builds it);
- *  - atmvfi_refine_tail: out[o][p] = bias[o] + sum over the nine taps of contrib[tap * 3 + o][p + offset(tap)] (taps outside the image
- *    contribute nothing: the convolution's zero padding), PReLU(slope), 2 * sigmoid - 1, + it, and the clamped frame -- the outputs of
- *    atmvfi_final_residual. */
-int atmvfi_conv3x3_planes_readout(const void* in_hi, const void* in_lo, int64_t in_rows, int N, int H, int W, int Cin, const void* w_hi,
-                                  const void* w_lo, int Cout, const float* bias, const float* prelu, const void* w2, float* contrib,
-                                  int64_t contrib_plane, void* stream);
-/* The same with the number of terms of the MAIN 3x3 product (3 or 1, as atmvfi_conv3x3_planes4; anything else: ATMVFI_EINVAL).  The 27-row
- * W2 product on the activated tile is three-term in both: it forms the output residual and costs next to nothing. */
-int atmvfi_conv3x3_planes_readout2(const void* in_hi, const void* in_lo, int64_t in_rows, int N, int H, int W, int Cin, const void* w_hi,
-                                   const void* w_lo, int Cout, const float* bias, const float* prelu, const void* w2, float* contrib,
-                                   int64_t contrib_plane, int terms, void* stream);
+/* The second launch of the refiner's tail: the gather over the read-out of atmvfi_conv3p (atmvfi_conv3p_params, "Fused READ-OUT");
+ * contrib / contrib_plane are that call's readout / readout_plane. */
 int atmvfi_refine_tail(const float* contrib, int64_t contrib_plane, const float* bias /*[3] or NULL*/, const float* slope /*[3] or NULL*/,
                        const float* it /*[B,3,H,W]*/, float* it_sum, float* it_clamped, int B, int H, int W, void* stream);
 

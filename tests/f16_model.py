@@ -1,5 +1,5 @@
 """Exact fp64 model of the single-pass fp16 mode ("f16": Network.set_precision, ATMVFI_PREC_F16, terms = 1 of
-atmvfi_conv3x3_planes4) -- CPU only, test infrastructure only.
+atmvfi_conv3p with terms = 1) -- CPU only, test infrastructure only.
 
 A product of the mode is hi(x) * hi(w) alone, hi = the high half of the library's split (fp16, round to nearest even, saturating),
 accumulated in fp32 into the one accumulator ``acc``; the epilogue (bias, PReLU, residual, split-K fold and reduce) is the f16x3

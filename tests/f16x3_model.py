@@ -562,7 +562,7 @@ def tail_sum(contrib, n: int, h: int, w: int) -> torch.Tensor:
 
 
 def tail_chain(x_planes_values, wa, ba, pa, wb, mutant=None, which=None, terms: int = 3) -> tuple:
-    """atmvfi_conv3x3_planes_readout + the sum of atmvfi_refine_tail on the plane values ``x`` [n,h,w,Cin]: ``conv`` for
+    """atmvfi_conv3p's read-out + the sum of atmvfi_refine_tail on the plane values ``x`` [n,h,w,Cin]: ``conv`` for
     refine_head.0 (wa, ba, pa), ``linear`` of its activated rows (fp32) with W2 = ``readout_matrix(wb)`` -- the 27 tap contributions
     per pixel, what ``contrib`` holds, transposed -- and their sum per output pixel (no bias: refine_tail adds it).  -> (Result of the
     conv, Result of the W2 product [n*h*w, 27], summed pre-activation [n,3,h,w]).  ``mutant`` goes into product ``which`` (0: the

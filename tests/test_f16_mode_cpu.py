@@ -59,9 +59,9 @@ def _err(lib):
 def test_abi_version_and_symbols():
     lib = hip_ops.load_library()
     assert (lib.atmvfi_version() >> 8) & 255 >= 24
-    for name in ("atmvfi_conv3x3_planes4", "atmvfi_conv3x3_planes_readout2"):
-        assert hasattr(lib, name) and name in hip_ops.SIGNATURES
-        assert lib.atmvfi_plan_fn_id(name.encode()) >= 0          # launch entry points: a plan can hold them
+    name = "atmvfi_conv3p"                                            # the 3x3 plane kernel and its read-out: `terms` of the block
+    assert hasattr(lib, name) and name in hip_ops.SIGNATURES
+    assert lib.atmvfi_plan_fn_id(name.encode()) >= 0                  # a launch entry point: a plan can hold it
     hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "atmvfi.h")).read()
     assert "#define ATMVFI_PREC_F16   2" in hdr
 
@@ -76,6 +76,19 @@ def _gemm(**kw):
     return p
 
 
+def _conv3p(**kw):
+    """A valid plain block on fake addresses (1x16x16, Cin = Cout = 32, fp32 output); ``kw`` overrides fields."""
+    p = hip_ops.Conv3pParams(in_hi=P, in_lo=P, in_rows=300, N=1, H=16, W=16, Cin=32, w_hi=P, w_lo=P, Cout=32, out=P, out_ld=32, terms=3)
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def _readout(**kw):
+    """The same as a read-out block: no fp32 output, the W2 operand and 27 planes of 256 pixels."""
+    return _conv3p(**{"out": None, "out_ld": 0, "readout_w": P, "readout": P, "readout_plane": 256, **kw})
+
+
 def test_abi_refuses_f16_without_plane_input_and_bad_term_counts():
     lib = hip_ops.load_library()
     # ATMVFI_PREC_F16 on fp32 input: no such engine
@@ -85,18 +98,33 @@ def test_abi_refuses_f16_without_plane_input_and_bad_term_counts():
     assert lib.atmvfi_gemm(ctypes.byref(_gemm(in_=None, in_hi=P, in_lo=P, in_ld=128, tile_wn=-1)), None) == -1 and b"tile_wn = -1" in _err(lib)
     # an unknown precision value
     assert lib.atmvfi_gemm(ctypes.byref(_gemm(precision=3)), None) == -1 and b"bad precision" in _err(lib)
-    # the 3x3 kernel and its read-out: a term count other than 3 or 1
+    # the 3x3 kernel and its read-out: a term count other than 3 or 1 (0, the value of a zeroed block, included)
     for terms in (2, 0, 4, -1):
-        rc = lib.atmvfi_conv3x3_planes4(P, P, 300, 1, 16, 16, 32, P, P, 32, P, 32, None, None, None, None, 0, 0, None, None, None, 0, 0, 0, 0, None,
-                                        0, terms, None)
-        assert rc == -1 and b"terms must be 3" in _err(lib), terms
-        rc = lib.atmvfi_conv3x3_planes_readout2(P, P, 300, 1, 16, 16, 32, P, P, 32, None, None, P, P, 256, terms, None)
-        assert rc == -1 and b"terms must be 3" in _err(lib), terms
+        rc = lib.atmvfi_conv3p(ctypes.byref(_conv3p(terms=terms)), None)
+        assert rc == -1 and b"conv3x3_planes: terms must be 3" in _err(lib), terms
+        rc = lib.atmvfi_conv3p(ctypes.byref(_readout(terms=terms)), None)
+        assert rc == -1 and b"conv3x3_planes_readout: terms must be 3" in _err(lib), terms
     # both term counts pass that check and reach the next one (still before any launch: in_rows must exceed N*H*W)
     for terms in (3, 1):
-        rc = lib.atmvfi_conv3x3_planes4(P, P, 256, 1, 16, 16, 32, P, P, 32, P, 32, None, None, None, None, 0, 0, None, None, None, 0, 0, 0, 0, None,
-                                        0, terms, None)
+        rc = lib.atmvfi_conv3p(ctypes.byref(_conv3p(terms=terms, in_rows=256)), None)
         assert rc == -1 and b"in_rows" in _err(lib), terms
+
+
+@pytest.mark.parametrize("block,wrong,text", [
+    (_conv3p, dict(in_hi=None), b"conv3x3_planes: null pointer"),
+    (_conv3p, dict(out_hi=P, out_lo=P, plane_rows=256, out_c0=4), b"multiple of 8"),
+    (_conv3p, dict(wn=9), b"wn 0 (auto)"),
+    (_conv3p, dict(out_hi2=P, out_lo2=P, plane_rows2=256), b"needs the first one"),
+    (_readout, dict(out=P, out_ld=32), b"out, both plane sinks, workspace and wn must be unset"),
+    (_readout, dict(readout_plane=255), b"contrib_plane"),
+], ids=["first_pointer", "out_c0", "wn", "second_sink_alone", "readout_with_out", "readout_plane"])
+def test_conv3p_block_layout_matches_the_header(block, wrong, text):
+    """hip_ops.Conv3pParams against the C struct: one wrong field at a time on an otherwise valid block, each refused (before any launch)
+    with the message of exactly that field -- a ctypes field that sits elsewhere than its C counterpart makes the launcher read another
+    value there and report something else (or nothing)."""
+    lib = hip_ops.load_library()
+    rc = lib.atmvfi_conv3p(ctypes.byref(block(**wrong)), None)
+    assert rc == -1 and text in _err(lib), _err(lib)
 
 
 # ------------------------------------------------------------------ host logic

@@ -1,5 +1,5 @@
 """GPU: the single-pass fp16 mode ("f16": Network.set_precision, HipOps.plane_terms = 1, ATMVFI_PREC_F16, terms = 1 of
-atmvfi_conv3x3_planes4 / atmvfi_conv3x3_planes_readout2) against the exact fp64 model of tests/f16_model.py.
+atmvfi_conv3p and its read-out with terms = 1) against the exact fp64 model of tests/f16_model.py.
 
 Exact family: the configurations, engines and tile widths of tests/test_gpu_f16x3_contract.py; the kernel must equal the hi-only model
 up to the epilogue's final roundings.  tests/test_f16_mode_cpu.py shows that the three-term result misses that bound by more than
@@ -296,7 +296,7 @@ def test_plane_sinks_in_f16_mode(dev):
 # ------------------------------------------------------------------ the fused read-out: main product hi-only, W2 three-term
 @pytest.mark.parametrize("case", [(128, 64, 1, 40, 72), (64, 32, 2, 21, 35)], ids=lambda c: f"cin{c[0]}_c{c[1]}_n{c[2]}_{c[3]}x{c[4]}")
 def test_readout_f16(case, dev):
-    """atmvfi_conv3x3_planes_readout2(terms = 1) + atmvfi_refine_tail against the chain in fp64 with the MAIN product on hi(x), hi(w)
+    """atmvfi_conv3p's read-out (terms = 1) + atmvfi_refine_tail against the chain in fp64 with the MAIN product on hi(x), hi(w)
     and everything behind it (the W2 product on the activated tile, the tail) on full values: the existing read-out test's shapes and
     its tolerance -- what is left beside the model is the same fp32 accumulation and the same three-term W2 product."""
     cin, c, n, h, w = case

@@ -1,4 +1,4 @@
-"""GPU: the two kernels that chain layers on chip -- atmvfi_stem_fused and atmvfi_conv3x3_planes_readout + atmvfi_refine_tail -- held
+"""GPU: the two kernels that chain layers on chip -- atmvfi_stem_fused and atmvfi_conv3p's read-out + atmvfi_refine_tail -- held
 to the exact chained f16x3 model of tests/f16x3_model.py (``stem_chain`` / ``tail_chain``).
 
 ``chain_exact``: operands for which no fp32 operation of ANY layer rounds (tests/test_f16x3_model_cpu.py proves it for every case
@@ -149,7 +149,7 @@ def run_tail(cfg, family, dev, record_property):
 @pytest.mark.parametrize("family", M.CHAIN_FAMILIES)
 @pytest.mark.parametrize("cfg", M.CASES_TAIL, ids=lambda c: c["id"])
 def test_tail_chain(cfg, family, dev, record_property):
-    """atmvfi_conv3x3_planes_readout + atmvfi_refine_tail, widths 128>64 and 64>32: one 16 x 16 tile, ragged tiles with several images,
+    """atmvfi_conv3p's read-out + atmvfi_refine_tail, widths 128>64 and 64>32: one 16 x 16 tile, ragged tiles with several images,
     and 272 x 272 (289 tiles on 256 persistent workgroups)."""
     run_tail(cfg, family, dev, record_property)
 

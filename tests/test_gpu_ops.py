@@ -929,7 +929,7 @@ def test_conv3x3_planes_prelu_forms(wn, hip, dev):
                                   (1, 32, 32, 456, 224, 4), (1, 20, 28, 392, 101, 0)],
                          ids=lambda c: f"n{c[0]}_{c[1]}x{c[2]}_cin{c[3]}_cout{c[4]}_wn{c[5]}")
 def test_conv3x3_planes_split_k(case, hip, dev):
-    """Split-K of under-filled long-K launches (atmvfi_conv3x3_planes3 with a workspace; the motion-MLP shapes of network_lite at
+    """Split-K of under-filled long-K launches (atmvfi_conv3p with a workspace; the motion-MLP shapes of network_lite at
     256 x 256 / 256 x 448 and of network_base at 576 x 960, ragged images, tap-packed tails, ragged Cout): K ranges by whole chunks,
     raw fp32 partial sums, a fixed-order reduce with the whole epilogue (bias, PReLU, fp32 rows from out_cmin on, both plane sinks, the
     first through its own PReLU).  Against the unsplit launch: equal within fp32 summation-order error (1e-5 of the value scale);
@@ -1037,12 +1037,17 @@ def test_conv3x3_planes_compact_fp32_tail(hip, dev):
     wide = torch.full((N, H, W, 104), 7.0, device=dev)
     s1 = hip_ops.Planes.alloc(N * H * W, cout, dev)
     hip.conv3x3_planes(xp, N, H, W, pw, out=wide[..., :cout], bias=bias, planes=s1, out_cmin=cmin)
-    compact = torch.full((N, H, W, 8), 7.0, device=dev)
+    # (the compact buffer sits inside a larger tensor: `out` is the address of its first float, and the cmin floats in front of it --
+    # where a view base `out - cmin` would point -- belong to somebody else)
+    arena = torch.full((cmin + N * H * W * 8,), 7.0, device=dev)
+    arena[:cmin] = -3.0
+    compact = arena[cmin:].view(N, H, W, 8)
     s2 = hip_ops.Planes.alloc(N * H * W, cout, dev)
     hip.conv3x3_planes(xp, N, H, W, pw, out=compact[..., :cout - cmin], bias=bias, planes=s2, out_cmin=cmin)
     torch.cuda.synchronize()
     assert torch.equal(wide[..., cmin:cout], full[..., cmin:cout]) and (wide[..., :cmin] == 7.0).all()
     assert torch.equal(compact[..., :cout - cmin], full[..., cmin:cout]) and (compact[..., cout - cmin:] == 7.0).all()
+    assert (arena[:cmin] == -3.0).all(), "the 4 * cmin bytes in front of the compact buffer were written"
     assert torch.equal(s1.t, s2.t)
 
 
@@ -1470,7 +1475,7 @@ def test_atmformer_module_reference_fixture(shift, dev):
 @pytest.mark.parametrize("case", [(128, 64, 1, 40, 72), (64, 32, 2, 21, 35), (128, 64, 1, 300, 520), (64, 32, 1, 16, 16), (128, 64, 2, 17, 50)],
                          ids=lambda c: f"cin{c[0]}_c{c[1]}_n{c[2]}_{c[3]}x{c[4]}")
 def test_tail_fused(case, dev):
-    """atmvfi_conv3x3_planes_readout + atmvfi_refine_tail (refine_head.0 -> refine_head.1 -> 2 sigmoid - 1 -> += I_t -> clamp,
+    """atmvfi_conv3p's read-out + atmvfi_refine_tail (refine_head.0 -> refine_head.1 -> 2 sigmoid - 1 -> += I_t -> clamp,
     network_base.py:257-260, 429, 532-533, with the hidden map r1 kept in registers) against the chain in torch float64: both refiner
     widths (64: network_base, 32: network_lite), ragged tiles, several images, a map of one tile, and 627 tiles on 256 persistent
     workgroups; image borders are where the zero padding of the SECOND convolution has to be right (a tap contribution from outside

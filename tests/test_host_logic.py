@@ -691,7 +691,7 @@ def test_launch_plan_recorder_on_the_host():
         def __init__(self, name): self.__name__ = name
 
     class Lib:
-        def atmvfi_plan_fn_id(self, n): return {b"atmvfi_pack_frames": 3, b"atmvfi_linear": 5}.get(n, -1)
+        def atmvfi_plan_fn_id(self, n): return {b"atmvfi_pack_frames": 3, b"atmvfi_linear": 5, b"atmvfi_conv3p": 9}.get(n, -1)
 
     P = hip_ops._ptr
     stacked = torch.zeros(2, 3, 4, 4)                          # both frames are views of ONE storage
@@ -714,6 +714,20 @@ def test_launch_plan_recorder_on_the_host():
     bad._srcs = (out,)
     with pytest.raises(hip_ops.PlanUnsupported):               # ... or whose operand tensor is per-call
         plan.add_op(Fn("atmvfi_linear"), (ctypes.byref(bad), None))
+    # the 3x3 plane kernel's block (atmvfi_conv3p) goes the same way: by address and kept alive when its operands are workspace ...
+    cblk = hip_ops.Conv3pParams(in_hi=work.data_ptr(), in_lo=work.data_ptr(), out=work.data_ptr() + 16, out_cmin=4, terms=3)
+    cblk._srcs = (work, None)
+    n_ops = len(plan.ops_list)
+    plan.add_op(Fn("atmvfi_conv3p"), (ctypes.byref(cblk), None))
+    assert plan.ops_list[n_ops] == (9, [("u", ctypes.addressof(cblk))]) and plan.keep[-1] is cblk and len(plan.ops_list) == n_ops + 1
+    # ... refused when an operand tensor is per-call, or when `out` (the first stored channel, inside its buffer) lies in an output slot
+    cbad = hip_ops.Conv3pParams(in_hi=work.data_ptr(), in_lo=work.data_ptr(), out=work.data_ptr(), terms=3)
+    cbad._srcs = (work, im1)
+    with pytest.raises(hip_ops.PlanUnsupported):
+        plan.add_op(Fn("atmvfi_conv3p"), (ctypes.byref(cbad), None))
+    with pytest.raises(hip_ops.PlanUnsupported):
+        plan.add_op(Fn("atmvfi_conv3p"), (ctypes.byref(hip_ops.Conv3pParams(in_hi=work.data_ptr(), out=out.data_ptr() + 16, out_cmin=4)), None))
+    assert len(plan.ops_list) == n_ops + 1 and plan.keep[-1] is cblk
     with pytest.raises(hip_ops.PlanUnsupported):
         plan.add_op(Fn("atmvfi_version"), (None,))
     # the round-3 fault: a workspace pointer biased IN FRONT of its buffer (the compact view of the 3x3 plane kernel) whose raw value

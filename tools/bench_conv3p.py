@@ -1,5 +1,5 @@
 """Same-process A/B of the two 3x3 kernels on the network's 1080p layer shapes: fp32-input row/half kernel (atmvfi_conv3x3_f16x3)
-against the split-plane ping-pong kernel (atmvfi_conv3x3_planes).  Interleaved rounds, median of the per-round times."""
+against the split-plane ping-pong kernel (atmvfi_conv3p).  Interleaved rounds, median of the per-round times."""
 import importlib, os, sys
 import numpy as np
 import torch

@@ -33,7 +33,7 @@ hip_ops = importlib.import_module("atm-vfi_amd.hip_ops")
 COLUMNS = ("parent f16x3", "f16x3", "f16")
 CONTROL = "f16x3 (2nd model)"       # per launch only: a second model on the library under test, default mode -- the A/A control
 PLANE_KERNELS = ("conv3x3_planes", "linear_split", "deconv2x2_split", "conv2d_split")
-NEWER = ("atmvfi_conv3x3_planes4", "atmvfi_conv3x3_planes_readout2")       # what the parent's build lacks: never called in its mode
+NEWER = ("atmvfi_conv3p",)       # what an older build lacks; every mode calls it, so main() refuses a yardstick without it
 FORWARDS = [("base", 1088, 1920), ("base", 544, 960), ("lite", 256, 448)]
 LINES = []
 
@@ -196,7 +196,12 @@ def main():
         sys.exit("bench_precision: no GPU")
     dev = torch.device("cuda:0")
     torch.set_grad_enabled(False)
-    pv = hip_ops.load_library(a.yardstick_lib, NEWER).atmvfi_version()
+    parent = hip_ops.load_library(a.yardstick_lib, NEWER)
+    missing = [name for name in NEWER if not hasattr(parent, name)]
+    if missing:
+        sys.exit(f"bench_precision: {a.yardstick_lib} does not export {', '.join(missing)}: the 3x3 plane kernel is reached through it in every mode, "
+                 "so the yardstick has to be a build of the commit that introduced it (ABI 0.28) or a later one")
+    pv = parent.atmvfi_version()
     nv = hip_ops.load_library().atmvfi_version()
     say(f"device {torch.cuda.get_device_name(0)}; parent library ABI 0.{(pv >> 8) & 255} ({os.path.basename(a.yardstick_lib)}), library under test "
         f"ABI 0.{(nv >> 8) & 255}; stress weights (seed 1), random frame pair (seed 3)")

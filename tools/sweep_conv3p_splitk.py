@@ -1,4 +1,4 @@
-"""Split-K of atmvfi_conv3x3_planes on the under-filled long-K layer shapes of the small configurations: unsplit (auto width) against the
+"""Split-K of atmvfi_conv3p on the under-filled long-K layer shapes of the small configurations: unsplit (auto width) against the
 split launch at every width 1..8 (wn forced; the launcher picks the split count).  python tools/sweep_conv3p_splitk.py"""
 import importlib, os, sys
 import numpy as np

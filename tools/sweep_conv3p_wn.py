@@ -1,4 +1,4 @@
-"""Tile-width sweep of atmvfi_conv3x3_planes on the network's layer shapes (plane sink only, as the forward runs them): time per wn 1..8
+"""Tile-width sweep of atmvfi_conv3p on the network's layer shapes (plane sink only, as the forward runs them): time per wn 1..8
 against the launcher's own choice (wn = 0).  usage: python tools/sweep_conv3p_wn.py [c4|c3]"""
 import importlib, os, sys
 import numpy as np
