@@ -457,8 +457,11 @@ extern "C" int64_t atmvfi_yuv_borders_workspace_ints(int H, int W) {
     return g.ints(H) + (long long)g.chunks * g.groups;
 }
 
-extern "C" int atmvfi_yuv_borders(const void* yuv, int H, int W, int depth, int msb, int64_t pitch, int32_t* out, int32_t* workspace,
-                                  int64_t workspace_ints, void* stream) {
+extern "C" int atmvfi_yuv_borders(const atmvfi_yuv_desc* desc, const void* yuv, int32_t* out, int32_t* workspace, int64_t workspace_ints,
+                                  void* stream) {
+    ATMVFI_REQUIRE(desc, ATMVFI_EINVAL, "yuv_borders: null descriptor");
+    const int H = desc->H, W = desc->W, depth = desc->depth, msb = desc->msb;
+    long long pitch = desc->pitch;
     ATMVFI_REQUIRE(yuv && out && workspace, ATMVFI_EINVAL, "yuv_borders: null pointer (yuv %p, out %p, workspace %p)", yuv, (void*)out,
                    (void*)workspace);
     if (const int rc = check_frame("yuv_borders", H, W)) return rc;
@@ -468,7 +471,7 @@ extern "C" int atmvfi_yuv_borders(const void* yuv, int H, int W, int depth, int 
     const long long b = depth == 10 ? 2 : 1;
     if (pitch == 0) pitch = W * b;
     ATMVFI_REQUIRE(pitch % b == 0 && pitch >= W * b, ATMVFI_EINVAL,
-                   "yuv_borders: pitch %lld must be a multiple of the sample size %lld and at least a luma row's %lld bytes", (long long)pitch, b, W * b);
+                   "yuv_borders: pitch %lld must be a multiple of the sample size %lld and at least a luma row's %lld bytes", pitch, b, W * b);
     ATMVFI_REQUIRE(aligned4(out) && aligned4(workspace), ATMVFI_EINVAL, "yuv_borders: out and workspace must be 4-byte aligned");
     const BorderGeometry g = geometry(H, W);
     const long long need = g.ints(H) + (long long)g.chunks * g.groups;
@@ -478,7 +481,7 @@ extern "C" int atmvfi_yuv_borders(const void* yuv, int H, int W, int depth, int 
     const bool al = aligned4(yuv) && pitch % 4 == 0 && W % 4 == 0;
     int* const rowp = workspace;
     unsigned* const colp = reinterpret_cast<unsigned*>(workspace + 4ll * g.tiles * H);
-    const YBorderArgs a = {(const unsigned char*)yuv, (long long)pitch, H, W, g.rows_per_chunk, g.groups, rowp, colp};
+    const YBorderArgs a = {(const unsigned char*)yuv, pitch, H, W, g.rows_per_chunk, g.groups, rowp, colp};
     const dim3 grid((unsigned)g.tiles, (unsigned)g.chunks), block(256);
     const hipStream_t st = (hipStream_t)stream;
     dispatch([&](auto D10, auto AL) {
@@ -497,18 +500,19 @@ extern "C" int atmvfi_yuv_borders(const void* yuv, int H, int W, int depth, int 
     return atmvfi::check_launch("yuv_borders (reduce)");
 }
 
-extern "C" int atmvfi_yuv_compose(void* dst, const void* border, int H, int W, int depth, int matrix, int full_range, int siting, int subsampling,
-                                  int chroma, int msb, int64_t border_pitch, int64_t border_chroma_pitch, int64_t border_chroma_offset, int y0,
-                                  int x0, int h, int w, const float* src, int Hp, int Wp, int pad_top, int pad_left, const void* src_u8,
-                                  void* stream) {
+extern "C" int atmvfi_yuv_compose(const atmvfi_yuv_desc* border_desc, void* dst, const void* border, int y0, int x0, int h, int w,
+                                  const float* src, int Hp, int Wp, int pad_top, int pad_left, const void* src_u8, void* stream) {
     const char* me = "yuv_compose";
+    ATMVFI_REQUIRE(border_desc, ATMVFI_EINVAL, "%s: null descriptor", me);
+    const atmvfi_yuv_desc& bd = *border_desc;
+    const int H = bd.H, W = bd.W, depth = bd.depth, subsampling = bd.subsampling, chroma = bd.chroma, msb = bd.msb;
     ATMVFI_REQUIRE(dst && border, ATMVFI_EINVAL, "%s: null pointer (dst %p, border %p)", me, dst, border);
     ATMVFI_REQUIRE((src != nullptr) != (src_u8 != nullptr), ATMVFI_EINVAL, "%s: give exactly one of src and src_u8", me);
-    if (const int rc = check_format(me, H, W, matrix, full_range, siting)) return rc;
-    if (const int rc = check_depth(me, depth, full_range)) return rc;
-    if (const int rc = check_sub(me, subsampling, siting, chroma, msb)) return rc;
+    if (const int rc = check_format(me, bd)) return rc;
+    if (const int rc = check_depth(me, bd)) return rc;
+    if (const int rc = check_sub(me, bd)) return rc;
     Layout bl;
-    if (const int rc = check_surface(me, H, W, depth, chroma, msb, border_pitch, border_chroma_pitch, border_chroma_offset, &bl, subsampling)) return rc;
+    if (const int rc = check_surface(me, bd, &bl)) return rc;
     ATMVFI_REQUIRE(y0 >= 0 && x0 >= 0 && h > 0 && w > 0 && (long long)y0 + h <= H && (long long)x0 + w <= W, ATMVFI_EINVAL,
                    "%s: window outside the frame (%d x %d at (%d, %d) of a %d x %d frame)", me, h, w, y0, x0, H, W);
     const int sy = subsampling == 0 ? 2 : 1, sx = subsampling == 2 ? 1 : 2;
@@ -551,9 +555,7 @@ extern "C" int atmvfi_yuv_compose(void* dst, const void* border, int H, int W, i
         plane((bl.uoff + (long long)p * ch * bl.cs) * b, bl.cs * b, (tl.uoff + (long long)p * ch * tl.cs) * b, tl.cs * b, ch, crow, cy0, cy1, cx0 * e * b,
               cx1 * e * b);
     // the window: every check of the encode, then its kernel at the window's origin
-    if (const int rc = atmvfi::yuv_encode_window(me, dst, H, W, y0, x0, h, w, depth, matrix, full_range, siting, subsampling, chroma, msb, src_u8, src,
-                                                 Hp, Wp, pad_top, pad_left, stream))
-        return rc;
+    if (const int rc = atmvfi::yuv_encode_window(me, bd, dst, y0, x0, h, w, src_u8, src, Hp, Wp, pad_top, pad_left, stream)) return rc;
     if (rects == 0) return ATMVFI_OK;           // the window is the frame
     const long long blocks = (most + 255) / 256;
     hipLaunchKernelGGL(yuv_bars_kernel, dim3((unsigned)(blocks > 4096 ? 4096 : blocks), (unsigned)rects), dim3(256), 0, (hipStream_t)stream, a);

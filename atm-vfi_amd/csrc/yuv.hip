@@ -1,23 +1,24 @@
-// YUV 4:2:0 (and planar 4:2:2 / 4:4:4) -> RGB: the five decode entry points of include/atmvfi.h on one kernel and one checked host path
-// (surface_decode, below the kernels).  yuv_common.h holds the definition and every helper; yuv_encode.hip is the other direction.
-//   atmvfi_yuv420_to_rgb      the whole frame -> fp32 planar [3,Hp,Wp] = q / 255 and / or uint8 [H,W,3] (RGB or BGR)
-//   atmvfi_yuv420p10_to_f32   a window of a 10-bit frame with the depth kept -> fp32 planar = q / 1023
-//   atmvfi_yuv_surface_decode a window of a decoder's surface (NV12 / NV21 / P010, planar; any pitch and chroma offset) -> either
-//                             pixel of the two calls above: the same walker, instances with interleaved chroma and / or msb samples
-//   atmvfi_yuv_sub_decode     the same call with a subsampling: planar 4:2:2 / 4:4:4 frames, instances with SUB = 1 / 2.  On the aligned
+// YUV 4:2:0 (and planar 4:2:2 / 4:4:4) -> RGB: atmvfi_yuv_decode of include/atmvfi.h, one kernel family behind one checked host path
+// (below the kernels).  yuv_common.h holds the definition and every helper; yuv_encode.hip is the other direction.  The frame
+// descriptor (atmvfi_yuv_desc) and the call's keep_depth / mode select what runs:
+//   the whole frame, or a window of it -> fp32 planar [3,Hp,Wp] = q / 255 and / or uint8 [h,w,3] (RGB or BGR)
+//   keep_depth (10 bit)       the depth kept -> fp32 planar = q / 1023
+//   chroma / msb / strides    a decoder's surface (NV12 / NV21 / P010, planar; any pitch and chroma offset) -> either pixel of the two
+//                             above: the same walker, instances with interleaved chroma and / or msb samples
+//   subsampling 1 / 2         planar 4:2:2 / 4:4:4 frames, instances with SUB = 1 / 2.  On the aligned
 //                             path 4:2:2 loads ONE chroma row per luma row (two per lane, no vertical mix), 4:4:4 loads U and V of a
 //                             group as it loads Y (a dword, or 8 bytes at 10 bit)
-//   atmvfi_yuv420_window      the window a dataset evaluation needs (atm-vfi_amd/evaluate.py reads the Xiph 2K / 4K clips as 10-bit Y4M this
-//                             way): the output of atmvfi_frame_u8_window on the frame atmvfi_yuv420_to_rgb would write, without that RGB
+//   mode                      the window a dataset evaluation needs (atm-vfi_amd/evaluate.py reads the Xiph 2K / 4K clips as 10-bit Y4M this
+//                             way): the output of atmvfi_frame_u8_window on the frame the whole-frame decode would write, without that RGB
 //                             frame ever existing.  With q(Y, X) the RGB pixel 0..255 of the WHOLE frame's decode,
-//                               mode 0: out(y, x) = q(y0 + y, x0 + x) -- atmvfi_yuv420_to_rgb is this with the window set to the frame
+//                               mode 0: out(y, x) = q(y0 + y, x0 + x) -- the whole-frame decode is this with the window set to the frame
 //                               mode 1: out(y, x) = (q(y0 + 2y, x0 + 2x) + q(y0 + 2y, x0 + 2x + 1) + q(y0 + 2y + 1, x0 + 2x)
 //                                       + q(y0 + 2y + 1, x0 + 2x + 1) + 2) >> 2 per channel: four 8-bit pixels, then the area rule (the
 //                                       order of an rgb24 PNG followed by cv2.INTER_AREA)
 //
 // Bandwidth-bound: 1.5 or 3 B/px in and 12 out to fp32.  A lane makes four horizontally adjacent pixels of the PADDED output (padding
 // comes from clamping the output coordinate into the window, as in frames.hip):
-//   crop (the first two calls and mode 0): on two output rows -- a 4 x 2 block of source luma.  The two rows need at most three chroma
+//   crop (mode 0): on two output rows -- a 4 x 2 block of source luma.  The two rows need at most three chroma
 //           rows, four samples wide (columns q - 1 .. q + 2 of the group, clamped): a row that both luma rows use is loaded once.
 //           Chroma is read straight from global memory: neighbouring lanes and rows re-read the same few bytes, which the vector L1
 //           serves; the HBM traffic is the frame, once.
@@ -36,7 +37,7 @@
 
 namespace {
 
-struct DecArgs : YuvSrc {      // (yuv_common.h: the frame, its planes and the pixel)
+struct DecOut {
     int y0, x0, h, w;           // the window in OUTPUT pixels (mode 1 reads 2h x 2w source pixels)
     float* dst;
     int Hp, Wp, pad_top, pad_left;
@@ -45,6 +46,7 @@ struct DecArgs : YuvSrc {      // (yuv_common.h: the frame, its planes and the p
     int groups;                 // ceil(Wp / 4)
     int rows;                   // lanes per column of groups: ceil(Hp / 2) for the crop, Hp in mode 1
 };
+struct DecArgs : YuvSrc, DecOut {};     // (yuv_common.h: the frame, its planes and the pixel)
 
 // The sink, TOP = 255: the fp32 canvas via q255 and / or the uint8 window, RGB or BGR; TOP = 1023: the fp32 canvas via q1023.
 // one group of the aligned path; (y, x) canvas coordinates, (wy, wx) window coordinates of its first pixel
@@ -179,25 +181,27 @@ __global__ __launch_bounds__(256) void yuv420_crop_kernel(const DecArgs a) {
     }
 }
 
-// The arguments of mode 1, which reads packed frames only (atmvfi_yuv420_window): DecArgs without the strides, which are the plane
-// widths.  The kernel's argument block and with it its code are what they were before frames could have a pitch.
-struct AreaArgs {
+// The arguments of mode 1, which reads packed frames only: DecArgs without the strides, which are the plane widths.  The kernel's
+// argument block and with it its code are what they were before frames could have a pitch.  The window-and-sink half is DecOut itself;
+// the frame half is converted by the two functions below the struct, and by nothing else.
+struct AreaSrc {
     const unsigned char* yuv;
     int H, W, ch, cw;
     long long uoff, voff;
     int kY, kRV, kGU, kGV, kBU, yo, mid, T;
-    int y0, x0, h, w;
-    float* dst;
-    int Hp, Wp, pad_top, pad_left;
-    unsigned char* dst_u8;
-    int bgr, groups, rows;
 };
+struct AreaArgs : AreaSrc, DecOut {};
+inline AreaArgs area_args(const DecArgs& a) {
+    return {{a.yuv, a.H, a.W, a.ch, a.cw, a.uoff, a.voff, a.kY, a.kRV, a.kGU, a.kGV, a.kBU, a.yo, a.mid, a.T}, a};
+}
+__device__ __forceinline__ DecArgs dec_args(const AreaArgs& p) {
+    return {{p.yuv, p.H, p.W, p.ch, p.cw, p.uoff, p.voff, p.W, p.cw, 0, p.kY, p.kRV, p.kGU, p.kGV, p.kBU, p.yo, p.mid, p.T}, p};
+}
 
 // mode 1: four output pixels of one output row from source rows fy (even) and fy + 1, columns gx .. gx + 7
 template <class PX, bool ALIGNED, bool LEFT>
 __global__ __launch_bounds__(256) void yuv420_area_kernel(const AreaArgs p) {
-    const DecArgs a = {YuvSrc{p.yuv, p.H, p.W, p.ch, p.cw, p.uoff, p.voff, p.W, p.cw, 0, p.kY, p.kRV, p.kGU, p.kGV, p.kBU, p.yo, p.mid, p.T},
-                       p.y0, p.x0, p.h, p.w, p.dst, p.Hp, p.Wp, p.pad_top, p.pad_left, p.dst_u8, p.bgr, p.groups, p.rows};
+    const DecArgs a = dec_args(p);
     const int total = a.rows * a.groups;
     for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
         const int y = idx / a.groups, x = (idx - y * a.groups) * 4;
@@ -246,12 +250,10 @@ __global__ __launch_bounds__(256) void yuv420_area_kernel(const AreaArgs p) {
 // Launches the decode of a checked window.  aligned path: Y groups are dwords, chroma pairs naturally aligned (cw even, group origins
 // even), plane stores 16 bytes, RGB groups three dwords; a group of four lies wholly inside the window or wholly in the padding
 // (without a canvas Wp is w and pad_left 0)
-// (il: interleaved chroma; msb: 10-bit samples stored in the upper bits)
-// (sub: 1 4:2:2, 2 4:4:4 -- planar, LSB, mode 0)
 // The run-time properties select the instance in this one place; decode_instance (yuv_common.h) names the combinations that have none,
-// and mode 1 exists for the planar LSB 4:2:0 pixels 0..255 alone.  surface_decode has refused the rest.
-void launch_decode(const DecArgs& a, int depth, bool keep, int mode, int siting, void* stream, bool il, bool msb, int sub) {
-    const bool al = aligned4(a.yuv) && a.W % 4 == 0 && layout_aligned(a.ys, a.cs, a.uoff, a.voff, depth, il, sub) && a.x0 % 4 == 0 && a.w % 4 == 0 &&
+// and mode 1 exists for the planar LSB 4:2:0 pixels 0..255 alone.  atmvfi_yuv_decode has refused the rest.
+void launch_decode(const DecArgs& a, const atmvfi_yuv_desc& d, bool keep, int mode, void* stream) {
+    const bool al = aligned4(a.yuv) && a.W % 4 == 0 && layout_aligned(a.ys, a.cs, a.uoff, a.voff, d) && a.x0 % 4 == 0 && a.w % 4 == 0 &&
                     (!a.dst || canvas_aligned(a.dst, a.Wp, a.pad_left)) && (!a.dst_u8 || aligned4(a.dst_u8));
     const dim3 grid = yuv_grid((long long)a.rows * a.groups), block(256);
     const hipStream_t st = (hipStream_t)stream;
@@ -263,36 +265,39 @@ void launch_decode(const DecArgs& a, int depth, bool keep, int mode, int siting,
                 hipLaunchKernelGGL((yuv420_crop_kernel<PX, AL(), LEFT()>), grid, block, 0, st, a);
                 return;
             }
-            // (AreaArgs repeats DecArgs without the strides, and no compiler checks the list: a new DecArgs field goes here too)
             if constexpr (TOP == 255 && !IL() && !MSB() && SUB == 0)
-                hipLaunchKernelGGL((yuv420_area_kernel<PX, AL(), LEFT()>), grid, block, 0, st,
-                                   AreaArgs{a.yuv, a.H, a.W, a.ch, a.cw, a.uoff, a.voff, a.kY, a.kRV, a.kGU, a.kGV, a.kBU, a.yo, a.mid, a.T, a.y0, a.x0,
-                                            a.h, a.w, a.dst, a.Hp, a.Wp, a.pad_top, a.pad_left, a.dst_u8, a.bgr, a.groups, a.rows});
+                hipLaunchKernelGGL((yuv420_area_kernel<PX, AL(), LEFT()>), grid, block, 0, st, area_args(a));
         }
-    }, sub, al, siting != 0, depth == 10, keep, il, msb);
+    }, d.subsampling, al, d.siting != 0, d.depth == 10, keep, d.chroma != 0, d.msb != 0);
 }
 
-// The one host path of every decode entry point, under the caller's name `me`: the checks in one order, the geometry, the launch.
-// chroma / msb / the three strides describe the surface (all 0: the packed planar frame); sub 1 / 2 is checked by atmvfi_yuv_sub_decode
-// (check_sub); mode 1 (area 2x: the window reads 2h x 2w source pixels, a lane makes one output row) is atmvfi_yuv420_window's and
-// reads packed planar LSB 4:2:0 frames to pixels 0..255; noun names what the canvas holds ("frame" when the window is the whole frame).
-int surface_decode(const char* me, int sub, const void* yuv, int H, int W, int depth, int matrix, int full_range, int siting, int chroma, int msb,
-                   int64_t pitch, int64_t chroma_pitch, int64_t chroma_offset, int keep_depth, int mode, int y0, int x0, int h, int w, void* dst_u8,
-                   int bgr, float* dst, int Hp, int Wp, int pad_top, int pad_left, void* stream, const char* noun = "window") {
+}  // namespace
+
+// The one host path of every decode: the checks in one order, the geometry, the launch.  The descriptor says what the frame is (all
+// zero but H, W, depth, matrix: the packed planar 4:2:0 frame); mode 1 (area 2x: the window reads 2h x 2w source pixels, a lane makes
+// one output row) reads packed planar LSB 4:2:0 frames to pixels 0..255.
+extern "C" int atmvfi_yuv_decode(const atmvfi_yuv_desc* desc, const void* yuv, int keep_depth, int mode, int y0, int x0, int h, int w, void* dst_u8,
+                                 int bgr, float* dst, int Hp, int Wp, int pad_top, int pad_left, void* stream) {
+    const char* me = "yuv_decode";
+    ATMVFI_REQUIRE(desc, ATMVFI_EINVAL, "%s: null descriptor", me);
+    const atmvfi_yuv_desc& d = *desc;
+    if (d.subsampling != 0)
+        if (const int rc = check_sub(me, d)) return rc;
     ATMVFI_REQUIRE(yuv, ATMVFI_EINVAL, "%s: null source", me);
     ATMVFI_REQUIRE(dst || dst_u8, ATMVFI_EINVAL, "%s: both outputs are null (give dst, dst_u8 or both)", me);
-    if (const int rc = check_format(me, H, W, matrix, full_range, siting)) return rc;
-    if (const int rc = check_depth(me, depth, full_range)) return rc;
+    if (const int rc = check_format(me, d)) return rc;
+    if (const int rc = check_depth(me, d)) return rc;
     Layout l;
-    if (const int rc = check_surface(me, H, W, depth, chroma, msb, pitch, chroma_pitch, chroma_offset, &l, sub)) return rc;
+    if (const int rc = check_surface(me, d, &l)) return rc;
+    const int H = d.H, W = d.W, sub = d.subsampling;
     ATMVFI_REQUIRE(keep_depth == 0 || keep_depth == 1, ATMVFI_EINVAL, "%s: keep_depth must be 0 or 1 (got %d)", me, keep_depth);
-    ATMVFI_REQUIRE(!(keep_depth && depth != 10), ATMVFI_EINVAL, "%s: keep_depth needs a 10-bit surface", me);
+    ATMVFI_REQUIRE(!(keep_depth && d.depth != 10), ATMVFI_EINVAL, "%s: keep_depth needs a 10-bit surface", me);
     ATMVFI_REQUIRE(!(keep_depth && dst_u8), ATMVFI_EINVAL, "%s: dst_u8 holds 8-bit pixels: not with keep_depth", me);
     ATMVFI_REQUIRE(mode == 0 || mode == 1, ATMVFI_EINVAL, "%s: unknown mode %d (0: crop, 1: area 2x)", me, mode);
-    ATMVFI_REQUIRE(mode == 0 || (sub == 0 && chroma == 0 && !msb && !pitch && !chroma_pitch && !chroma_offset && !keep_depth), ATMVFI_EINVAL,
+    ATMVFI_REQUIRE(mode == 0 || (sub == 0 && d.chroma == 0 && !d.msb && !d.pitch && !d.chroma_pitch && !d.chroma_offset && !keep_depth), ATMVFI_EINVAL,
                    "%s: mode 1 reads packed planar 4:2:0 frames with LSB samples, to pixels 0..255", me);
     ATMVFI_REQUIRE(h >= 1 && w >= 1, ATMVFI_EINVAL, "%s: negative or zero size: the window's h and w must be at least 1 (got %d x %d)", me, h, w);
-    // (the wording serves two contracts: yuv420_window's callers match "negative or zero" for a negative origin, the other calls' "outside the")
+    // (the wording serves two contracts: callers match "negative or zero" for a negative origin, or "outside the")
     ATMVFI_REQUIRE(y0 >= 0 && x0 >= 0, ATMVFI_EINVAL,
                    "%s: the window's origin (%d, %d) is negative, outside the frame (refused like a negative or zero size)", me, y0, x0);
     const long long s = mode == 1 ? 2 : 1;
@@ -302,7 +307,7 @@ int surface_decode(const char* me, int sub, const void* yuv, int H, int W, int d
     if (sub == 0) ATMVFI_REQUIRE(y0 % 2 == 0 && x0 % 2 == 0, ATMVFI_EINVAL, "%s: the window origin (%d, %d) must be even", me, y0, x0);
     if (sub == 1) ATMVFI_REQUIRE(x0 % 2 == 0, ATMVFI_EINVAL, "%s: the window origin (%d, %d) must have an even x0 for 4:2:2 frames", me, y0, x0);
     if (dst) {
-        if (const int rc = check_canvas(me, "dst", noun, dst, h, w, Hp, Wp, pad_top, pad_left)) return rc;
+        if (const int rc = check_canvas(me, "dst", "window", dst, h, w, Hp, Wp, pad_top, pad_left)) return rc;
     } else {        // no canvas: the output geometry is the window's
         Hp = h;
         Wp = w;
@@ -310,49 +315,7 @@ int surface_decode(const char* me, int sub, const void* yuv, int H, int W, int d
     }
     const int groups = groups_of(Wp), rows = mode == 1 ? Hp : pairs_of(Hp);
     if (const int rc = check_items(me, rows, groups, "output of", Hp, Wp)) return rc;
-    const DecArgs a = {make_src(yuv, H, W, depth, matrix, full_range, keep_depth != 0, l, sub), y0, x0, h, w, dst, Hp, Wp, pad_top, pad_left,
-                       (unsigned char*)dst_u8, bgr ? 1 : 0, groups, rows};
-    launch_decode(a, depth, keep_depth != 0, mode, siting, stream, chroma != 0, msb != 0, sub);
+    const DecArgs a = {make_src(yuv, d, keep_depth != 0, l), {y0, x0, h, w, dst, Hp, Wp, pad_top, pad_left, (unsigned char*)dst_u8, bgr ? 1 : 0, groups, rows}};
+    launch_decode(a, d, keep_depth != 0, mode, stream);
     return atmvfi::check_launch(me);
-}
-
-}  // namespace
-
-// The three calls on packed planar frames are the surface call with chroma 0, msb 0 and no strides, under their own names.
-
-extern "C" int atmvfi_yuv420_to_rgb(const void* yuv, int H, int W, int depth, int matrix, int full_range, int siting, void* dst_u8, int bgr,
-                                    float* dst, int Hp, int Wp, int pad_top, int pad_left, void* stream) {
-    return surface_decode("yuv420_to_rgb", 0, yuv, H, W, depth, matrix, full_range, siting, 0, 0, 0, 0, 0, 0, 0, 0, 0, H, W, dst_u8, bgr, dst, Hp, Wp,
-                          pad_top, pad_left, stream, "frame");
-}
-
-extern "C" int atmvfi_yuv420p10_to_f32(const void* yuv, int H, int W, int matrix, int siting, int y0, int x0, int h, int w, float* dst,
-                                       int Hp, int Wp, int pad_top, int pad_left, void* stream) {
-    ATMVFI_REQUIRE(!yuv || dst, ATMVFI_EINVAL, "yuv420p10_to_f32: null destination");        // (one output: not "both outputs are null")
-    return surface_decode("yuv420p10_to_f32", 0, yuv, H, W, 10, matrix, 0, siting, 0, 0, 0, 0, 0, 1, 0, y0, x0, h, w, nullptr, 0, dst, Hp, Wp, pad_top,
-                          pad_left, stream);
-}
-
-extern "C" int atmvfi_yuv420_window(const void* yuv, int H, int W, int depth, int matrix, int full_range, int siting, int mode, int y0, int x0,
-                                    int h, int w, float* dst, int Hp, int Wp, int pad_top, int pad_left, void* dst_u8, void* stream) {
-    return surface_decode("yuv420_window", 0, yuv, H, W, depth, matrix, full_range, siting, 0, 0, 0, 0, 0, 0, mode, y0, x0, h, w, dst_u8, 0, dst, Hp, Wp,
-                          pad_top, pad_left, stream);
-}
-
-extern "C" int atmvfi_yuv_surface_decode(const void* yuv, int H, int W, int depth, int matrix, int full_range, int siting, int chroma, int msb,
-                                         int64_t pitch, int64_t chroma_pitch, int64_t chroma_offset, int keep_depth, int y0, int x0, int h, int w,
-                                         void* dst_u8, int bgr, float* dst, int Hp, int Wp, int pad_top, int pad_left, void* stream) {
-    return surface_decode("yuv_surface_decode", 0, yuv, H, W, depth, matrix, full_range, siting, chroma, msb, pitch, chroma_pitch, chroma_offset,
-                          keep_depth, 0, y0, x0, h, w, dst_u8, bgr, dst, Hp, Wp, pad_top, pad_left, stream);
-}
-
-extern "C" int atmvfi_yuv_sub_decode(const void* yuv, int H, int W, int depth, int matrix, int full_range, int siting, int subsampling, int chroma,
-                                     int msb, int64_t pitch, int64_t chroma_pitch, int64_t chroma_offset, int keep_depth, int y0, int x0, int h,
-                                     int w, void* dst_u8, int bgr, float* dst, int Hp, int Wp, int pad_top, int pad_left, void* stream) {
-    if (subsampling == 0)       // the surface call itself: the same instance, the same bytes
-        return atmvfi_yuv_surface_decode(yuv, H, W, depth, matrix, full_range, siting, chroma, msb, pitch, chroma_pitch, chroma_offset, keep_depth, y0,
-                                         x0, h, w, dst_u8, bgr, dst, Hp, Wp, pad_top, pad_left, stream);
-    if (const int rc = check_sub("yuv_sub_decode", subsampling, siting, chroma, msb)) return rc;
-    return surface_decode("yuv_sub_decode", subsampling, yuv, H, W, depth, matrix, full_range, siting, chroma, msb, pitch, chroma_pitch,
-                          chroma_offset, keep_depth, 0, y0, x0, h, w, dst_u8, bgr, dst, Hp, Wp, pad_top, pad_left, stream);
 }

@@ -1,8 +1,7 @@
 // YUV 4:2:0 (planar I420, and the decoder surfaces NV12 / NV21 / P010) <-> RGB at the host boundary of the video loops and of the Y4M
-// evaluations: the definition, its device helpers and the host-side checks, shared by yuv.hip (decode: atmvfi_yuv420_to_rgb,
-// atmvfi_yuv420p10_to_f32, atmvfi_yuv420_window, atmvfi_yuv_surface_decode) and yuv_encode.hip (atmvfi_rgb_to_yuv420,
-// atmvfi_f32_to_yuv420p10, atmvfi_yuv_surface_encode); include/atmvfi.h declares them, atm-vfi_amd/yuv.py holds the numpy
-// twins.  Nothing of the reference: its scripts take PNGs.  The definition is the project's own, in int32 throughout (>> floors), so the
+// evaluations: the definition, its device helpers and the host-side checks, shared by yuv.hip (atmvfi_yuv_decode) and yuv_encode.hip
+// (atmvfi_yuv_encode); include/atmvfi.h declares them and the frame descriptor (atmvfi_yuv_desc) that every host function here takes;
+// atm-vfi_amd/yuv.py holds the numpy twins.  Nothing of the reference: its scripts take PNGs.  The definition is the project's own, in int32 throughout (>> floors), so the
 // device, the vectorised numpy twins and the per-pixel models (tests/cpu_yuv.py, cpu_yuv10.py, cpu_yuv_window.py) agree bit for bit;
 // every kernel runs the functions below, so two entry points that decode the same pixel give the same bits by construction.
 //   frame     Y [H,W], U [ch,cw], V [ch,cw] back to back, ch = (H + 1) / 2, cw = (W + 1) / 2; uint8, or little-endian uint16 (0..1023)
@@ -22,14 +21,14 @@
 //             Y = clip(((eY . p + 2^13) >> 14) + yo); chroma sample (j, i) from the un-rounded sums s over rows 2j, min(2j + 1, H - 1) and
 //             columns 2i, min(2i + 1, W - 1) (centre, sh = 2) or max(2i - 1, 0), 2i, min(2i + 1, W - 1) weighted 1, 2, 1 (left, sh = 3):
 //             U = clip(((eU . s + 2^(13 + sh)) >> (14 + sh)) + mid), V alike
-//   surface   where the samples of a frame lie (atmvfi_yuv_surface_decode / atmvfi_yuv_surface_encode; yuv.py: Surface; model
+//   surface   where the samples of a frame lie (the descriptor's chroma, msb and three strides; yuv.py: Surface; model
 //             tests/cpu_yuv_surface.py): chroma as two planes or as ONE plane of interleaved pairs, U first (NV12, P010) or V first
 //             (NV21); 10-bit samples in the low or, msb, in the upper ten bits of their word (read s >> 6, written v << 6); rows at a
 //             pitch, chroma from an offset.  YuvSrc carries the strides and the U / V origins (V first is U first with the origins
 //             swapped); interleaved and msb are properties of the instance (Pixel), as the siting is.  The arithmetic above is applied
 //             to the samples found there, unchanged.  A decoder's surface that already lies in device memory is decoded in place: its
-//             pointer, pitch and chroma offset go to atmvfi_yuv_surface_decode, no padding byte is read and nothing is repacked.
-//   4:2:2 / 4:4:4   (atmvfi_yuv_sub_decode / atmvfi_yuv_sub_encode; yuv.py: Format.subsampling; model tests/cpu_yuv_sub.py) planar frames
+//             pointer, pitch and chroma offset go to atmvfi_yuv_decode, no padding byte is read and nothing is repacked.
+//   4:2:2 / 4:4:4   (the descriptor's subsampling; yuv.py: Format.subsampling; model tests/cpu_yuv_sub.py) planar frames
 //             whose chroma planes are [H, cw] (4:2:2) or [H, W] (4:4:4): SUB, one more property of the instance.  Decode 4:2:2: row y, the
 //             columns and weights above, c' = (wx0 c[y][q0] + wx1 c[y][q1] + 2) >> 2; 4:4:4: c' = c[y][x].  Encode: the horizontal
 //             taps above over ONE row (4:2:2: sh = 1 centre, 2 left) or the pixel itself (4:4:4: sh = 0).  The same coefficients,
@@ -43,10 +42,9 @@
 #include "common.h"
 
 namespace atmvfi {
-// yuv_encode.hip, for active.hip (atmvfi_yuv_compose): the encode kernel with a destination origin inside a larger tight frame
-int yuv_encode_window(const char* me, void* frame, int H, int W, int y0, int x0, int h, int w, int depth, int matrix, int full_range,
-                      int siting, int subsampling, int chroma, int msb, const void* src_u8, const float* src, int Hp, int Wp, int pad_top,
-                      int pad_left, void* stream);
+// yuv_encode.hip, for active.hip (atmvfi_yuv_compose): the encode kernel with a destination origin inside the larger tight frame of `d`
+int yuv_encode_window(const char* me, const atmvfi_yuv_desc& d, void* frame, int y0, int x0, int h, int w, const void* src_u8, const float* src,
+                      int Hp, int Wp, int pad_top, int pad_left, void* stream);
 }  // namespace atmvfi
 
 namespace {
@@ -125,9 +123,10 @@ inline Layout tight_layout(int H, int W, int chroma, int sub = 0) {
 }
 
 // keep: the 10-bit depth kept (RGB 0..1023); otherwise RGB 0..255 from samples of either depth
-inline YuvSrc make_src(const void* yuv, int H, int W, int depth, int matrix, int full_range, bool keep, const Layout& l, int sub = 0) {
-    const int ch = chroma_rows(H, sub), cw = chroma_cols(W, sub);
-    const Coeffs& c = keep ? kCoeffs10[matrix] : kCoeffs[matrix][full_range];
+inline YuvSrc make_src(const void* yuv, const atmvfi_yuv_desc& d, bool keep, const Layout& l) {
+    const int H = d.H, W = d.W, depth = d.depth, full_range = d.full_range;
+    const int ch = chroma_rows(H, d.subsampling), cw = chroma_cols(W, d.subsampling);
+    const Coeffs& c = keep ? kCoeffs10[d.matrix] : kCoeffs[d.matrix][full_range];
     const long long uoff = l.uoff + (l.chroma == 2 ? 1 : 0), voff = l.chroma == 0 ? l.uoff + (long long)ch * l.cs : l.uoff + (l.chroma == 1 ? 1 : 0);
     return YuvSrc{(const unsigned char*)yuv, H, W, ch, cw, uoff, voff, l.ys, l.cs, l.chroma == 2 ? 1 : 0,
                   c.dec[0], c.dec[1], c.dec[2], c.dec[3], c.dec[4], depth == 10 ? 64 : (full_range ? 0 : 16), depth == 10 ? 512 : 128,
@@ -320,9 +319,10 @@ __device__ __forceinline__ void decode4(const YuvSrc& a, int fy, int gx, const i
 }
 
 // -------------------------------------------------------------------------------------------------------------------- host: checks
-// Every entry point passes its own name as the message prefix; the order of the checks is the one of surface_decode (yuv.hip) and
-// surface_encode (yuv_encode.hip), which every entry point of its direction runs.  None of these launches anything.
-int check_format(const char* what, int H, int W, int matrix, int full_range, int siting) {
+// Every entry point passes its own name as the message prefix; the order of the checks is the one of atmvfi_yuv_decode (yuv.hip) and
+// surface_encode (yuv_encode.hip).  They read the frame descriptor; none of these launches anything.
+int check_format(const char* what, const atmvfi_yuv_desc& d) {
+    const int H = d.H, W = d.W, matrix = d.matrix, full_range = d.full_range, siting = d.siting;
     ATMVFI_REQUIRE(H >= 1 && W >= 1, ATMVFI_EINVAL, "%s: H and W must be at least 1 (got %d x %d)", what, H, W);
     ATMVFI_REQUIRE(matrix == 0 || matrix == 1, ATMVFI_EINVAL, "%s: unknown matrix %d (0: bt601, 1: bt709)", what, matrix);
     ATMVFI_REQUIRE(full_range == 0 || full_range == 1, ATMVFI_EINVAL, "%s: full_range must be 0 or 1 (got %d)", what, full_range);
@@ -330,16 +330,18 @@ int check_format(const char* what, int H, int W, int matrix, int full_range, int
     return ATMVFI_OK;
 }
 
-int check_depth(const char* what, int depth, int full_range) {
+int check_depth(const char* what, const atmvfi_yuv_desc& d) {
+    const int depth = d.depth, full_range = d.full_range;
     ATMVFI_REQUIRE(depth == 8 || depth == 10, ATMVFI_EINVAL, "%s: depth must be 8 or 10 (got %d)", what, depth);
     ATMVFI_REQUIRE(!(depth == 10 && full_range), ATMVFI_EINVAL, "%s: 10-bit full range is not supported", what);
     return ATMVFI_OK;
 }
 
 // a surface: depth, layout and strides in BYTES as the caller gives them -> the layout in samples.  pitch / chroma_pitch / chroma_offset
-// 0: tight.  (yuv.Surface holds the same rules.)
-int check_surface(const char* what, int H, int W, int depth, int chroma, int msb, long long pitch, long long chroma_pitch, long long chroma_offset,
-                  Layout* out, int sub = 0) {
+// 0: tight, and so is every encode's destination (`tight`: the strides are not read).  (yuv.Surface holds the same rules.)
+int check_surface(const char* what, const atmvfi_yuv_desc& d, Layout* out, bool tight = false) {
+    const int H = d.H, W = d.W, depth = d.depth, chroma = d.chroma, msb = d.msb, sub = d.subsampling;
+    long long pitch = tight ? 0 : d.pitch, chroma_pitch = tight ? 0 : d.chroma_pitch, chroma_offset = tight ? 0 : d.chroma_offset;
     ATMVFI_REQUIRE(chroma >= 0 && chroma <= 2, ATMVFI_EINVAL, "%s: unknown chroma layout %d (0: planar, 1: interleaved uv, 2: interleaved vu)",
                    what, chroma);
     ATMVFI_REQUIRE(msb == 0 || msb == 1, ATMVFI_EINVAL, "%s: msb must be 0 or 1 (got %d)", what, msb);
@@ -360,8 +362,9 @@ int check_surface(const char* what, int H, int W, int depth, int chroma, int msb
     return ATMVFI_OK;
 }
 
-// 4:2:2 / 4:4:4 (atmvfi_yuv_sub_*): planar LSB frames only, no siting at 4:4:4
-int check_sub(const char* what, int subsampling, int siting, int chroma, int msb) {
+// 4:2:2 / 4:4:4: planar LSB frames only, no siting at 4:4:4
+int check_sub(const char* what, const atmvfi_yuv_desc& d) {
+    const int subsampling = d.subsampling, siting = d.siting, chroma = d.chroma, msb = d.msb;
     ATMVFI_REQUIRE(subsampling >= 0 && subsampling <= 2, ATMVFI_EINVAL, "%s: unknown subsampling %d (0: 4:2:0, 1: 4:2:2, 2: 4:4:4)", what, subsampling);
     ATMVFI_REQUIRE(subsampling == 0 || (chroma == 0 && msb == 0), ATMVFI_EINVAL,
                    "%s: 4:2:2 and 4:4:4 frames are planar with LSB samples (got chroma %d, msb %d with subsampling %d)", what, chroma, msb, subsampling);
@@ -387,8 +390,9 @@ int check_items(const char* what, long long rows, long long groups, const char* 
 // the frame side of the aligned paths (with a 4-byte aligned pointer and W % 4 == 0): Y groups are dwords / 8-byte words of their row,
 // planar chroma pairs naturally aligned (2 or 4 bytes), interleaved chroma pair-of-pairs 4-byte aligned.  A packed I420 frame with
 // W % 4 == 0 always passes.  4:4:4 (sub 2): chroma groups are loaded as Y groups are, so chroma rows are dword-aligned like luma rows.
-inline bool layout_aligned(int ys, int cs, long long uoff, long long voff, int depth, bool il, int sub = 0) {
-    const int b = depth == 10 ? 2 : 1;
+inline bool layout_aligned(int ys, int cs, long long uoff, long long voff, const atmvfi_yuv_desc& d) {
+    const int b = d.depth == 10 ? 2 : 1, sub = d.subsampling;
+    const bool il = d.chroma != 0;
     if ((ys * (long long)b) % 4) return false;
     if (sub == 2) return (uoff * b) % 4 == 0 && (voff * b) % 4 == 0 && (cs * (long long)b) % 4 == 0;
     if (il) return ((uoff < voff ? uoff : voff) * b) % 4 == 0 && (cs * (long long)b) % 4 == 0;

@@ -1,10 +1,11 @@
-// RGB -> YUV 4:2:0 (and planar 4:2:2 / 4:4:4): the four encode entry points of include/atmvfi.h on one kernel and one checked host path
-// (surface_encode, below the kernel).  yuv_common.h holds the definition and the shared helpers; yuv.hip is the other direction.
-//   atmvfi_rgb_to_yuv420      uint8 [H,W,3] (RGB or BGR) or the fp32 canvas in units of 1 / 255 -> 8-bit samples
-//   atmvfi_f32_to_yuv420p10   the fp32 canvas in units of 1 / 1023 -> 10-bit samples, the depth kept
-//   atmvfi_yuv_surface_encode either of the two into a tight surface: planar, or NV12 / NV21 / P010 (interleaved chroma, msb samples);
+// RGB -> YUV 4:2:0 (and planar 4:2:2 / 4:4:4): atmvfi_yuv_encode of include/atmvfi.h, one kernel family behind one checked host path
+// (surface_encode, below the kernel).  yuv_common.h holds the definition and the shared helpers; yuv.hip is the other direction.  The
+// frame descriptor (atmvfi_yuv_desc) selects what runs:
+//   depth 8                   uint8 [H,W,3] (RGB or BGR) or the fp32 canvas in units of 1 / 255 -> 8-bit samples
+//   depth 10                  the fp32 canvas in units of 1 / 1023 -> 10-bit samples, the depth kept
+//   chroma / msb              either of the two into a tight surface: planar, or NV12 / NV21 / P010 (interleaved chroma, msb samples);
 //                             a lane's two chroma samples of both planes leave as ONE dword (8 bit) or 8-byte (10 bit) store
-//   atmvfi_yuv_sub_encode     the same call with a subsampling: planar 4:2:2 / 4:4:4 frames (SUB = 1 / 2).  The lane's 4 x 2 block makes
+//   subsampling 1 / 2         planar 4:2:2 / 4:4:4 frames (SUB = 1 / 2).  The lane's 4 x 2 block makes
 //                             a chroma pair per plane and ROW (4:2:2: a 2-byte or dword store) or a chroma group per plane and row
 //                             (4:4:4: a dword or 8-byte store, as the Y group)
 //
@@ -223,12 +224,14 @@ struct Place {
     int FH, FW, y0, x0;
 };
 
-// Launches the encode of a checked frame; exactly one of src_u8 and src is given.  The destination is tight: chroma 0 is the packed
-// planar frame, 1 / 2 the interleaved surface (U / V first); msb: 10-bit samples stored in the upper bits; sub: 1 4:2:2, 2 4:4:4.
+// Launches the encode of a checked frame `d`; exactly one of src_u8 and src is given.  The destination is tight: chroma 0 is the packed
+// planar frame, 1 / 2 the interleaved surface (U / V first); msb: 10-bit samples stored in the upper bits; subsampling 1 4:2:2, 2 4:4:4.
 // The run-time properties select the instance in this one place: the source is fp32 x 1023 at depth 10, else fp32 x 255 or uint8;
 // msb samples come from the 10-bit source alone, 4:2:2 / 4:4:4 are planar LSB, and 4:4:4 has no siting.
-void launch_encode(const Coeffs& c, int yo, int depth, const void* src_u8, int bgr, const float* src, int Hp, int Wp, int pad_top, int pad_left,
-                   int H, int W, int siting, void* yuv, void* stream, int chroma, bool msb, int sub, const Place& at) {
+void launch_encode(const atmvfi_yuv_desc& d, const void* src_u8, int bgr, const float* src, int Hp, int Wp, int pad_top, int pad_left, void* yuv,
+                   void* stream, const Place& at) {
+    const int H = d.H, W = d.W, depth = d.depth, chroma = d.chroma, sub = d.subsampling;
+    const Coeffs& c = depth == 10 ? kCoeffs10[d.matrix] : kCoeffs[d.matrix][d.full_range];
     const int ch = chroma_rows(H, sub), cw = chroma_cols(W, sub), groups = groups_of(W), b = depth == 10 ? 2 : 1;
     EncArgs a = {(const unsigned char*)src_u8, src_u8 && bgr ? 1 : 0, src, Hp, Wp, pad_top, pad_left, H, W, ch, cw};
     for (int k = 0; k < 3; ++k) {
@@ -236,7 +239,7 @@ void launch_encode(const Coeffs& c, int yo, int depth, const void* src_u8, int b
         a.eU[k] = c.enc[1][k];
         a.eV[k] = c.enc[2][k];
     }
-    a.yo = yo;
+    a.yo = depth == 10 ? 64 : (d.full_range ? 0 : 16);
     const Layout l = tight_layout(at.FH, at.FW, chroma, sub);
     // the window's origin in samples: of the luma plane, and of a chroma plane (an interleaved column is two samples)
     const long long yorg = (long long)at.y0 * l.ys + at.x0;
@@ -251,74 +254,52 @@ void launch_encode(const Coeffs& c, int yo, int depth, const void* src_u8, int b
     a.vu = chroma == 2 ? 1 : 0;
     a.groups = groups;
     // (a tight frame of its own with W % 4 == 0: the layout follows from the pointer; a window must also start on a group)
-    const bool al = aligned4(yuv) && W % 4 == 0 && (yorg * b) % 4 == 0 && layout_aligned(l.ys, l.cs, uabs, vabs, depth, chroma != 0, sub) &&
+    const bool al = aligned4(yuv) && W % 4 == 0 && (yorg * b) % 4 == 0 && layout_aligned(l.ys, l.cs, uabs, vabs, d) &&
                     (src ? canvas_aligned(src, Wp, pad_left) : aligned4(src_u8));
     const dim3 grid = yuv_grid((long long)pairs_of(H) * groups), block(256);
     dispatch_sub([&](auto SUB, auto AL, auto LEFT, auto D10, auto F32, auto IL, auto MSB) {
         constexpr int SRC = D10() ? SRC_F1023 : (F32() ? SRC_F255 : SRC_U8);
         if constexpr ((F32() || !D10()) && encode_instance<SRC, IL(), MSB(), SUB(), LEFT()>)
             hipLaunchKernelGGL((yuv420_encode_kernel<SRC, AL(), LEFT(), IL(), MSB(), SUB()>), grid, block, 0, (hipStream_t)stream, a);
-    }, sub, al, siting != 0, depth == 10, src != nullptr, chroma != 0, msb);
+    }, sub, al, d.siting != 0, depth == 10, src != nullptr, chroma != 0, d.msb != 0);
 }
 
-// The one host path of every encode entry point, under the caller's name `me`: the checks in one order, then the launch.  chroma / msb
-// describe the tight destination (both 0: the packed planar frame); sub 1 / 2 is checked by atmvfi_yuv_sub_encode (check_sub).
-int surface_encode(const char* me, int sub, const void* src_u8, int bgr, const float* src, int Hp, int Wp, int pad_top, int pad_left, int H, int W,
-                   int depth, int matrix, int full_range, int siting, int chroma, int msb, void* yuv, void* stream, const Place* window = nullptr) {
+// The one host path of every encode, under the caller's name `me`: the checks in one order, then the launch.  `d` describes the tight
+// destination (its strides are not read); `window`: the frame `d` is a window of (atmvfi::yuv_encode_window).
+int surface_encode(const char* me, const atmvfi_yuv_desc& d, const void* src_u8, int bgr, const float* src, int Hp, int Wp, int pad_top,
+                   int pad_left, void* yuv, void* stream, const Place* window = nullptr) {
+    if (d.subsampling != 0)
+        if (const int rc = check_sub(me, d)) return rc;
     ATMVFI_REQUIRE(yuv, ATMVFI_EINVAL, "%s: null destination", me);
     ATMVFI_REQUIRE((src_u8 != nullptr) != (src != nullptr), ATMVFI_EINVAL, "%s: give exactly one of src_u8 and src (got %s)", me,
                    src_u8 ? "both" : "neither");
-    if (const int rc = check_format(me, H, W, matrix, full_range, siting)) return rc;
-    if (const int rc = check_depth(me, depth, full_range)) return rc;
+    if (const int rc = check_format(me, d)) return rc;
+    if (const int rc = check_depth(me, d)) return rc;
     Layout l;
-    if (const int rc = check_surface(me, H, W, depth, chroma, msb, 0, 0, 0, &l, sub)) return rc;
-    ATMVFI_REQUIRE(!(depth == 10 && src_u8), ATMVFI_EINVAL, "%s: a 10-bit surface is encoded from the fp32 canvas (src), not from src_u8", me);
+    if (const int rc = check_surface(me, d, &l, true)) return rc;
+    ATMVFI_REQUIRE(!(d.depth == 10 && src_u8), ATMVFI_EINVAL, "%s: a 10-bit surface is encoded from the fp32 canvas (src), not from src_u8", me);
     if (src)
-        if (const int rc = check_canvas(me, "src", "frame", src, H, W, Hp, Wp, pad_top, pad_left)) return rc;
-    if (const int rc = check_items(me, (H + 1) / 2, groups_of(W), "a frame of", H, W)) return rc;
-    launch_encode(depth == 10 ? kCoeffs10[matrix] : kCoeffs[matrix][full_range], depth == 10 ? 64 : (full_range ? 0 : 16), depth, src_u8, bgr, src, Hp,
-                  Wp, pad_top, pad_left, H, W, siting, yuv, stream, chroma, msb != 0, sub, window ? *window : Place{H, W, 0, 0});
+        if (const int rc = check_canvas(me, "src", "frame", src, d.H, d.W, Hp, Wp, pad_top, pad_left)) return rc;
+    if (const int rc = check_items(me, (d.H + 1) / 2, groups_of(d.W), "a frame of", d.H, d.W)) return rc;
+    launch_encode(d, src_u8, bgr, src, Hp, Wp, pad_top, pad_left, yuv, stream, window ? *window : Place{d.H, d.W, 0, 0});
     return atmvfi::check_launch(me);
 }
 
 }  // namespace
 
-// The two calls on packed planar frames are the surface call with chroma 0 and msb 0, under their own names.
-extern "C" int atmvfi_rgb_to_yuv420(const void* src_u8, int bgr, const float* src, int Hp, int Wp, int pad_top, int pad_left, int H, int W,
-                                    int matrix, int full_range, int siting, void* yuv, void* stream) {
-    return surface_encode("rgb_to_yuv420", 0, src_u8, bgr, src, Hp, Wp, pad_top, pad_left, H, W, 8, matrix, full_range, siting, 0, 0, yuv, stream);
+extern "C" int atmvfi_yuv_encode(const atmvfi_yuv_desc* desc, const void* src_u8, int bgr, const float* src, int Hp, int Wp, int pad_top,
+                                 int pad_left, void* yuv, void* stream) {
+    ATMVFI_REQUIRE(desc, ATMVFI_EINVAL, "yuv_encode: null descriptor");
+    return surface_encode("yuv_encode", *desc, src_u8, bgr, src, Hp, Wp, pad_top, pad_left, yuv, stream);
 }
 
-extern "C" int atmvfi_f32_to_yuv420p10(const float* src, int Hp, int Wp, int pad_top, int pad_left, int H, int W, int matrix, int siting,
-                                       void* yuv, void* stream) {
-    ATMVFI_REQUIRE(src, ATMVFI_EINVAL, "f32_to_yuv420p10: null source");        // (one source: not "exactly one of src_u8 and src")
-    return surface_encode("f32_to_yuv420p10", 0, nullptr, 0, src, Hp, Wp, pad_top, pad_left, H, W, 10, matrix, 0, siting, 0, 0, yuv, stream);
-}
-
-extern "C" int atmvfi_yuv_surface_encode(const void* src_u8, int bgr, const float* src, int Hp, int Wp, int pad_top, int pad_left, int H, int W,
-                                         int depth, int matrix, int full_range, int siting, int chroma, int msb, void* yuv, void* stream) {
-    return surface_encode("yuv_surface_encode", 0, src_u8, bgr, src, Hp, Wp, pad_top, pad_left, H, W, depth, matrix, full_range, siting, chroma, msb,
-                          yuv, stream);
-}
-
-extern "C" int atmvfi_yuv_sub_encode(const void* src_u8, int bgr, const float* src, int Hp, int Wp, int pad_top, int pad_left, int H, int W,
-                                     int depth, int matrix, int full_range, int siting, int subsampling, int chroma, int msb, void* yuv,
-                                     void* stream) {
-    if (subsampling == 0)       // the surface call itself: the same instance, the same bytes
-        return atmvfi_yuv_surface_encode(src_u8, bgr, src, Hp, Wp, pad_top, pad_left, H, W, depth, matrix, full_range, siting, chroma, msb, yuv,
-                                         stream);
-    if (const int rc = check_sub("yuv_sub_encode", subsampling, siting, chroma, msb)) return rc;
-    return surface_encode("yuv_sub_encode", subsampling, src_u8, bgr, src, Hp, Wp, pad_top, pad_left, H, W, depth, matrix, full_range, siting, chroma,
-                          msb, yuv, stream);
-}
-
-// atmvfi_yuv_compose's window (active.hip has checked that it lies in the frame, on the subsampling's grid): the h x w picture as a
-// frame of the cropped format -- the checks and the kernel of atmvfi_yuv_sub_encode -- written at (y0, x0) of the tight H x W frame
-int atmvfi::yuv_encode_window(const char* me, void* frame, int H, int W, int y0, int x0, int h, int w, int depth, int matrix, int full_range,
-                              int siting, int subsampling, int chroma, int msb, const void* src_u8, const float* src, int Hp, int Wp,
-                              int pad_top, int pad_left, void* stream) {
-    if (const int rc = check_sub(me, subsampling, siting, chroma, msb)) return rc;
-    const Place at = {H, W, y0, x0};
-    return surface_encode(me, subsampling, src_u8, 0, src, Hp, Wp, pad_top, pad_left, h, w, depth, matrix, full_range, siting, chroma, msb, frame,
-                          stream, &at);
+// atmvfi_yuv_compose's window (active.hip has checked that it lies in the frame `d`, on the subsampling's grid): the h x w picture as a
+// frame of the cropped format -- the checks and the kernel of atmvfi_yuv_encode -- written at (y0, x0) of the tight frame of `d`
+int atmvfi::yuv_encode_window(const char* me, const atmvfi_yuv_desc& d, void* frame, int y0, int x0, int h, int w, const void* src_u8,
+                              const float* src, int Hp, int Wp, int pad_top, int pad_left, void* stream) {
+    atmvfi_yuv_desc win = d;
+    win.H = h;
+    win.W = w;
+    const Place at = {d.H, d.W, y0, x0};
+    return surface_encode(me, win, src_u8, 0, src, Hp, Wp, pad_top, pad_left, frame, stream, &at);
 }

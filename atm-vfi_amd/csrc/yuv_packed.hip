@@ -6,7 +6,7 @@
 //   layout 2 y210 : uint16 (LE)      Y0 U0 Y1 V0, a sample is value << 6
 //   layout 3 v210 : four LE dwords per 6 pixels, three 10-bit components each (bits 0-9, 10-19, 20-29):
 //                   w0 = (Cb0, Y0, Cr0)  w1 = (Y1, Cb1, Y2)  w2 = (Cr1, Y3, Cb2)  w3 = (Y4, Cr2, Y5)
-// planar: Y [H,W], U [H,W/2], V [H,W/2] back to back, uint8 or LSB-aligned uint16: what atmvfi_yuv_sub_decode / _encode read and write.
+// planar: Y [H,W], U [H,W/2], V [H,W/2] back to back, uint8 or LSB-aligned uint16: what atmvfi_yuv_decode / atmvfi_yuv_encode (subsampling 1) read and write.
 //
 // Byte-bound: per pixel 2 (8 bit), 4 (y210) or 8/3 (v210) packed bytes on one side and 2 or 4 planar bytes on the other.  Items:
 //   layouts 0-2: an item is 32 packed bytes of one row (16 pixels at 8 bit, 8 at y210).  Aligned path (both pointers 16-byte aligned, the

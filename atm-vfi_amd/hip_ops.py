@@ -19,7 +19,7 @@ from typing import List, Optional
 
 import torch
 
-from .pixfmt import DeepRGB, Packed, Surface, _not_420, _origin_error, as_surface
+from .pixfmt import DeepRGB, Packed, Surface, YuvDesc, _not_420, _origin_error, as_surface
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libatmvfi_hip.so")
@@ -157,22 +157,13 @@ SIGNATURES = {
     "atmvfi_frame_borders": (c_i, [c_f, c_i, c_i, c_i, c_f, c_f, c_l, c_f]),
     "atmvfi_frame_compose": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f, c_i, c_f]),
     "atmvfi_yuv_borders_workspace_ints": (c_l, [c_i, c_i]),
-    "atmvfi_yuv_borders": (c_i, [c_f, c_i, c_i, c_i, c_i, c_l, c_f, c_f, c_l, c_f]),
-    "atmvfi_yuv_compose": (c_i, [c_f, c_f] + [c_i] * 9 + [c_l] * 3 + [c_i] * 4 + [c_f] + [c_i] * 4 + [c_f, c_f]),
+    "atmvfi_yuv_borders": (c_i, [ctypes.POINTER(YuvDesc), c_f, c_f, c_f, c_l, c_f]),
+    "atmvfi_yuv_compose": (c_i, [ctypes.POINTER(YuvDesc), c_f, c_f] + [c_i] * 4 + [c_f] + [c_i] * 4 + [c_f, c_f]),
     "atmvfi_shutter_accumulate": (c_i, [c_f, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f]),
     "atmvfi_shutter_resolve": (c_i, [c_f, c_i, c_i, c_i, c_i, c_f, c_i, c_f]),
     "atmvfi_shutter_table": (c_i, [c_i, ctypes.POINTER(ctypes.c_uint16)]),
-    "atmvfi_yuv420_to_rgb": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_f, c_i, c_i, c_i, c_i, c_f]),
-    "atmvfi_yuv420_window": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f, c_f]),
-    "atmvfi_rgb_to_yuv420": (c_i, [c_f, c_i, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f]),
-    "atmvfi_yuv420p10_to_f32": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f]),
-    "atmvfi_f32_to_yuv420p10": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f]),
-    "atmvfi_yuv_surface_decode": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_l, c_l, c_l, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_f, c_i, c_i,
-                                        c_i, c_i, c_f]),
-    "atmvfi_yuv_surface_encode": (c_i, [c_f, c_i, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f]),
-    "atmvfi_yuv_sub_decode": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_l, c_l, c_l, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_f, c_i, c_i,
-                                    c_i, c_i, c_f]),
-    "atmvfi_yuv_sub_encode": (c_i, [c_f, c_i, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f]),
+    "atmvfi_yuv_decode": (c_i, [ctypes.POINTER(YuvDesc), c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_f, c_i, c_i, c_i, c_i, c_f]),
+    "atmvfi_yuv_encode": (c_i, [ctypes.POINTER(YuvDesc), c_f, c_i, c_f, c_i, c_i, c_i, c_i, c_f, c_f]),
     "atmvfi_yuv_unpack": (c_i, [c_f, c_i, c_i, c_i, c_l, c_f, c_f]),
     "atmvfi_yuv_pack": (c_i, [c_f, c_i, c_i, c_i, c_f, c_f]),
     "atmvfi_rgb16_decode": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_f, c_f]),
@@ -1533,8 +1524,8 @@ class HipOps:
                 workspace = cache[key] = self.yuv_borders_workspace(sh, sw)
         elif workspace.dtype != torch.int32 or not workspace.is_contiguous() or not workspace.is_cuda:
             raise ValueError("yuv_borders: workspace must be a contiguous CUDA int32 tensor")
-        self._check(self.lib.atmvfi_yuv_borders(_ptr(buf), sh, sw, int(s.depth), int(s.msb), int(s.pitch), _ptr(out), _ptr(workspace),
-                                                workspace.numel(), self._stream()), "yuv_borders")
+        self._check(self.lib.atmvfi_yuv_borders(ctypes.byref(s.desc_block), _ptr(buf), _ptr(out), _ptr(workspace), workspace.numel(),
+                                                self._stream()), "yuv_borders")
         return out
 
     def _packed_pair(self, who: str, packed, buf, planar):
@@ -1601,10 +1592,8 @@ class HipOps:
             if o.depth != 8:
                 raise ValueError("yuv_compose: src_u8 goes into 8-bit frames only (a 10-bit frame takes the fp32 src)")
             _u8_frame(src_u8, "yuv_compose", (h, w), ": src_u8")
-        self._check(self.lib.atmvfi_yuv_compose(_ptr(dst), _ptr(border), o.height, o.width, int(o.depth), o.matrix_id, int(o.full_range), o.siting_id,
-                                                o.subsampling_id, o.chroma_id, int(o.msb), int(b.pitch), int(b.chroma_pitch), int(b.chroma_offset),
-                                                y0, x0, h, w, _ptr(src), hp, wp, int(pad_top), int(pad_left), _ptr(src_u8), self._stream()),
-                    "yuv_compose")
+        self._check(self.lib.atmvfi_yuv_compose(ctypes.byref(b.desc_block), _ptr(dst), _ptr(border), y0, x0, h, w, _ptr(src), hp, wp, int(pad_top),
+                                                int(pad_left), _ptr(src_u8), self._stream()), "yuv_compose")
 
     def shutter_accumulate(self, acc, src=None, src_u8=None, weight: int = 1, light: str = "linear", first: bool = False, pad_top: int = 0,
                            pad_left: int = 0, bgr: bool = False):
@@ -1654,15 +1643,34 @@ class HipOps:
         self._check(self.lib.atmvfi_shutter_table(LIGHTS.index(light), out), "shutter_table")
         return tuple(out)
 
-    # The YUV wrappers: one validator per direction, which also accounts meta["bytes"]; a wrapper adds the refusals that are its own and
-    # launches its entry point with the canvas the validator returns (the window is the wrapper's: the frame, or a caller's through
-    # ``_window``).  ``desc`` is a pixfmt.Format or Surface (they answer to the same names).  Both run on every frame of a video loop
-    # at every size, so they stay flat: positional arguments, nothing computed that a refusal alone needs.
+    # The YUV wrappers: one validator and one launch per direction; the validator also accounts meta["bytes"].  A wrapper adds the
+    # refusals that are its own and launches under its own name with the canvas the validator returns (the window is the wrapper's: the
+    # frame, or a caller's through ``_window``).  ``desc`` is a pixfmt.Format or Surface (they answer to the same names); its
+    # ``desc_block`` (include/atmvfi.h atmvfi_yuv_desc) is built once per descriptor and goes to the library by address.  Both run on
+    # every frame of a video loop at every size, so they stay flat: positional arguments, nothing computed that a refusal alone needs.
+    @staticmethod
+    def _decode_sinks(name, dst_u8, dst, wh, ww, pad_top, pad_left, lib_geometry=False):
+        """-> (hp, wp, bytes written): the canvas of a decode of a ``wh`` x ``ww`` window (the window itself without ``dst``) and what its
+        outputs weigh.  ``lib_geometry``: whether the canvas holds the window is left to the library (``RuntimeError``), else refused
+        here (``ValueError``)."""
+        nbytes = 0.0
+        if dst is None:
+            hp, wp = wh, ww
+        else:
+            _f32_canvas(dst, name, ": dst")
+            _, hp, wp = dst.shape
+            if not lib_geometry and (pad_top < 0 or pad_left < 0 or wh + pad_top > hp or ww + pad_left > wp):
+                raise ValueError(f"{name}: canvas {hp} x {wp} is smaller than the window {wh} x {ww} plus padding ({pad_top}, {pad_left})")
+            nbytes += 12.0 * hp * wp
+        if dst_u8 is not None:
+            _u8_frame(dst_u8, name, (wh, ww), ": dst_u8")
+            nbytes += 3.0 * wh * ww
+        return hp, wp, nbytes
+
     def _yuv_decode_args(self, name, buf, desc, dst_u8, dst, y0, x0, wh, ww, pad_top, pad_left, keep=False, area=1, lib_geometry=False):
         """-> (hp, wp, meta): the canvas and ``meta`` for ``_run`` of a decode of the window ``wh`` x ``ww`` at (y0, x0), in output pixels
-        (ints; ``_window`` has held a caller's to the frame), which reads ``area`` source pixels each.  ``lib_geometry``: whether the
-        canvas holds the window is left to the library (``RuntimeError``; yuv420_to_rgb and yuv420_window), else refused here
-        (``ValueError``)."""
+        (ints; ``_window`` has held a caller's to the frame), which reads ``area`` source pixels each.  ``lib_geometry``: yuv420_to_rgb
+        and yuv420_window (``_decode_sinks``)."""
         _yuv_buf(buf, desc, name, "source")
         if dst is None and dst_u8 is None:
             raise ValueError(f"{name}: give dst, dst_u8 or both")
@@ -1675,22 +1683,11 @@ class HipOps:
             err = _origin_error(name, desc, y0, x0)
             if err is not None:
                 raise err
-        nbytes = _SAMPLES_PER_PIXEL[desc.subsampling] * (2 if desc.depth == 10 else 1) * area * wh * ww
-        if dst is None:
-            hp, wp = wh, ww
-        else:
-            _f32_canvas(dst, name, ": dst")
-            _, hp, wp = dst.shape
-            if not lib_geometry and (pad_top < 0 or pad_left < 0 or wh + pad_top > hp or ww + pad_left > wp):
-                raise ValueError(f"{name}: canvas {hp} x {wp} is smaller than the window {wh} x {ww} plus padding ({pad_top}, {pad_left})")
-            nbytes += 12.0 * hp * wp
-        if dst_u8 is not None:
-            _u8_frame(dst_u8, name, (wh, ww), ": dst_u8")
-            nbytes += 3.0 * wh * ww
-        return hp, wp, {"bytes": nbytes}
+        hp, wp, nbytes = self._decode_sinks(name, dst_u8, dst, wh, ww, pad_top, pad_left, lib_geometry)
+        return hp, wp, {"bytes": nbytes + _SAMPLES_PER_PIXEL[desc.subsampling] * (2 if desc.depth == 10 else 1) * area * wh * ww}
 
     def _yuv_encode_args(self, name, buf, desc, src_u8, src, pad_top, pad_left):
-        """-> (h, w, hp, wp, meta): the frame's size, the source's and ``meta`` for ``_run``; the destination is the tight frame of ``desc``."""
+        """-> (hp, wp, meta): the source's size and ``meta`` for ``_run``; the destination is the tight frame of ``desc``."""
         h, w = desc.height, desc.width
         n = _yuv_buf(buf, desc, name, "destination")
         if (src is None) == (src_u8 is None):
@@ -1700,70 +1697,73 @@ class HipOps:
             _, hp, wp = src.shape
             if pad_top < 0 or pad_left < 0 or h + pad_top > hp or w + pad_left > wp:
                 raise ValueError(f"{name}: canvas {hp} x {wp} is smaller than the frame {h} x {w} plus padding ({pad_top}, {pad_left})")
-            return h, w, hp, wp, {"bytes": n + 12.0 * h * w}
+            return hp, wp, {"bytes": n + 12.0 * h * w}
         if desc.depth != 8:
             raise ValueError(f"{name}: src_u8 encodes 8-bit surfaces only (a 10-bit surface takes the fp32 src)")
         _u8_frame(src_u8, name, (h, w), ": src_u8")
-        return h, w, h, w, {"bytes": n + 3.0 * h * w}
+        return h, w, {"bytes": n + 3.0 * h * w}
+
+    def _launch_yuv_decode(self, name, meta, desc, buf, keep, mode, y0, x0, wh, ww, dst_u8, bgr, dst, hp, wp, pad_top, pad_left):
+        self._run(name, meta, self.lib.atmvfi_yuv_decode, ctypes.byref(desc.desc_block), _ptr(buf), int(bool(keep)), int(mode), y0, x0, wh, ww,
+                  _ptr(dst_u8), int(bool(bgr)), _ptr(dst), hp, wp, int(pad_top), int(pad_left), self._stream())
+
+    def _launch_yuv_encode(self, name, meta, desc, buf, src_u8, bgr, src, hp, wp, pad_top, pad_left):
+        self._run(name, meta, self.lib.atmvfi_yuv_encode, ctypes.byref(desc.desc_block), _ptr(src_u8), int(bool(bgr)), _ptr(src), hp, wp,
+                  int(pad_top), int(pad_left), _ptr(buf), self._stream())
 
     def yuv420_to_rgb(self, yuv, fmt, dst_u8=None, dst=None, pad_top: int = 0, pad_left: int = 0, bgr: bool = False):
         """One packed planar I420 frame of ``fmt`` (a ``yuv.Format``; a contiguous CUDA uint8 tensor of ``fmt.frame_bytes`` bytes, any
         alignment) -> ``dst_u8`` uint8 [H,W,3] (BGR if ``bgr``) and / or ``dst`` fp32 planar RGB [3,Hp,Wp] = q / 255 with replicate
-        padding, the frame at (pad_top, pad_left) (include/atmvfi.h atmvfi_yuv420_to_rgb; the bits of ``yuv.decode_numpy``)."""
+        padding, the frame at (pad_top, pad_left) (include/atmvfi.h atmvfi_yuv_decode; the bits of ``yuv.decode_numpy``)."""
         if fmt.subsampling != "420":
             raise _not_420("yuv420_to_rgb", fmt)
         h, w = fmt.height, fmt.width
         hp, wp, meta = self._yuv_decode_args("yuv420_to_rgb", yuv, fmt, dst_u8, dst, 0, 0, h, w, pad_top, pad_left, False, 1, True)
-        self._run("yuv420_to_rgb", meta, self.lib.atmvfi_yuv420_to_rgb, _ptr(yuv), h, w, int(fmt.depth), fmt.matrix_id, int(fmt.full_range),
-                  fmt.siting_id, _ptr(dst_u8), int(bool(bgr)), _ptr(dst), hp, wp, int(pad_top), int(pad_left), self._stream())
+        self._launch_yuv_decode("yuv420_to_rgb", meta, fmt, yuv, False, 0, 0, 0, h, w, dst_u8, bgr, dst, hp, wp, pad_top, pad_left)
 
     def yuv420_window(self, yuv, fmt, mode: int, y0: int, x0: int, h: int, w: int, dst=None, dst_u8=None, pad_top: int = 0,
                       pad_left: int = 0):
         """One packed planar I420 frame of ``fmt`` (as for ``yuv420_to_rgb``) -> what ``frame_u8_window(mode, y0, x0, h, w)`` makes of
         that frame's RGB decode, in one launch and without the RGB frame: ``dst`` fp32 planar [3,Hp,Wp] (q / 255, replicate padding, the
         window at (pad_top, pad_left)) and / or ``dst_u8`` uint8 [h,w,3] RGB.  The origin must be even (include/atmvfi.h
-        atmvfi_yuv420_window; the bits of ``yuv.window_numpy``)."""
+        atmvfi_yuv_decode with ``mode``; the bits of ``yuv.window_numpy``)."""
         if fmt.subsampling != "420":
             raise _not_420("yuv420_window", fmt)
         y0, x0, h, w = int(y0), int(x0), int(h), int(w)
         hp, wp, meta = self._yuv_decode_args("yuv420_window", yuv, fmt, dst_u8, dst, y0, x0, h, w, pad_top, pad_left, False,
                                              4 if mode == 1 else 1, True)
-        self._run("yuv420_window", meta, self.lib.atmvfi_yuv420_window, _ptr(yuv), fmt.height, fmt.width, int(fmt.depth), fmt.matrix_id, int(fmt.full_range),
-                  fmt.siting_id, int(mode), y0, x0, h, w, _ptr(dst), hp, wp, int(pad_top), int(pad_left), _ptr(dst_u8), self._stream())
+        self._launch_yuv_decode("yuv420_window", meta, fmt, yuv, False, mode, y0, x0, h, w, dst_u8, False, dst, hp, wp, pad_top, pad_left)
 
     def rgb_to_yuv420(self, yuv, fmt, src_u8=None, src=None, pad_top: int = 0, pad_left: int = 0, bgr: bool = False):
         """``src_u8`` uint8 [H,W,3] (BGR if ``bgr``) or ``src`` fp32 planar RGB [3,Hp,Wp] with the frame at (pad_top, pad_left) --
         exactly one -- -> ``yuv``, a packed 8-bit I420 frame of ``fmt`` (a contiguous CUDA uint8 tensor of ``fmt.frame_bytes`` bytes;
-        include/atmvfi.h atmvfi_rgb_to_yuv420).  From fp32 the pixel is ``frame_f32_to_u8``'s; the bits of ``yuv.encode_numpy``."""
+        include/atmvfi.h atmvfi_yuv_encode).  From fp32 the pixel is ``frame_f32_to_u8``'s; the bits of ``yuv.encode_numpy``."""
         if fmt.subsampling != "420":
             raise _not_420("rgb_to_yuv420", fmt)
         if fmt.depth != 8:
             raise ValueError("rgb_to_yuv420: encoding is 8-bit only")
-        h, w, hp, wp, meta = self._yuv_encode_args("rgb_to_yuv420", yuv, fmt, src_u8, src, pad_top, pad_left)
-        self._run("rgb_to_yuv420", meta, self.lib.atmvfi_rgb_to_yuv420, _ptr(src_u8), int(bool(bgr)), _ptr(src), hp, wp, int(pad_top),
-                  int(pad_left), h, w, fmt.matrix_id, int(fmt.full_range), fmt.siting_id, _ptr(yuv), self._stream())
+        hp, wp, meta = self._yuv_encode_args("rgb_to_yuv420", yuv, fmt, src_u8, src, pad_top, pad_left)
+        self._launch_yuv_encode("rgb_to_yuv420", meta, fmt, yuv, src_u8, bgr, src, hp, wp, pad_top, pad_left)
 
     def yuv420p10_to_f32(self, yuv, fmt, dst, window=None, pad_top: int = 0, pad_left: int = 0):
         """One packed 10-bit I420 frame of ``fmt`` (a ``yuv.Format`` of depth 10; a contiguous CUDA uint8 tensor of ``fmt.frame_bytes``
         bytes, little-endian uint16 samples, any alignment) -> ``dst`` fp32 planar RGB [3,Hp,Wp] = q / 1023 with the depth kept:
         ``window=(y0, x0, h, w)`` of the frame (default: all of it; even origin) at (pad_top, pad_left), replicate padding
-        (include/atmvfi.h atmvfi_yuv420p10_to_f32; the bits of ``yuv.decode_numpy_f32``)."""
+        (include/atmvfi.h atmvfi_yuv_decode with ``keep_depth``; the bits of ``yuv.decode_numpy_f32``)."""
         if fmt.subsampling != "420":
             raise _not_420("yuv420p10_to_f32", fmt)
         if fmt.depth != 10:
             raise ValueError("yuv420p10_to_f32: a 10-bit format expected (yuv420_to_rgb decodes 8-bit frames)")
         if dst is None:         # (the one output)
             raise ValueError("yuv420p10_to_f32: dst must be a contiguous CUDA fp32 [3,Hp,Wp] tensor")
-        h, w = fmt.height, fmt.width
-        y0, x0, wh, ww = (0, 0, h, w) if window is None else _window("yuv420p10_to_f32", fmt, window)
+        y0, x0, wh, ww = (0, 0, fmt.height, fmt.width) if window is None else _window("yuv420p10_to_f32", fmt, window)
         hp, wp, meta = self._yuv_decode_args("yuv420p10_to_f32", yuv, fmt, None, dst, y0, x0, wh, ww, pad_top, pad_left, True)
-        self._run("yuv420p10_to_f32", meta, self.lib.atmvfi_yuv420p10_to_f32, _ptr(yuv), h, w, fmt.matrix_id, fmt.siting_id, y0, x0, wh, ww,
-                  _ptr(dst), hp, wp, int(pad_top), int(pad_left), self._stream())
+        self._launch_yuv_decode("yuv420p10_to_f32", meta, fmt, yuv, True, 0, y0, x0, wh, ww, None, False, dst, hp, wp, pad_top, pad_left)
 
     def f32_to_yuv420p10(self, yuv, fmt, src, pad_top: int = 0, pad_left: int = 0):
         """``src`` fp32 planar RGB [3,Hp,Wp] with the frame at (pad_top, pad_left) -> ``yuv``, a packed 10-bit I420 frame of ``fmt`` (a
         ``yuv.Format`` of depth 10; a contiguous CUDA uint8 tensor of ``fmt.frame_bytes`` bytes, little-endian uint16 samples;
-        include/atmvfi.h atmvfi_f32_to_yuv420p10).  The pixel is clip(rint(x * 1023), 0, 1023); the bits of ``yuv.encode_numpy`` of
+        include/atmvfi.h atmvfi_yuv_encode).  The pixel is clip(rint(x * 1023), 0, 1023); the bits of ``yuv.encode_numpy`` of
         an fp32 source."""
         if fmt.subsampling != "420":
             raise _not_420("f32_to_yuv420p10", fmt)
@@ -1771,9 +1771,8 @@ class HipOps:
             raise ValueError("f32_to_yuv420p10: a 10-bit format expected (rgb_to_yuv420 encodes 8-bit frames)")
         if src is None:         # (the one source)
             raise ValueError("f32_to_yuv420p10: src must be a contiguous CUDA fp32 [3,Hp,Wp] tensor")
-        h, w, hp, wp, meta = self._yuv_encode_args("f32_to_yuv420p10", yuv, fmt, None, src, pad_top, pad_left)
-        self._run("f32_to_yuv420p10", meta, self.lib.atmvfi_f32_to_yuv420p10, _ptr(src), hp, wp, int(pad_top), int(pad_left), h, w,
-                  fmt.matrix_id, fmt.siting_id, _ptr(yuv), self._stream())
+        hp, wp, meta = self._yuv_encode_args("f32_to_yuv420p10", yuv, fmt, None, src, pad_top, pad_left)
+        self._launch_yuv_encode("f32_to_yuv420p10", meta, fmt, yuv, None, False, src, hp, wp, pad_top, pad_left)
 
     def yuv_surface_decode(self, buf, surface, dst_u8=None, dst=None, window=None, pad_top: int = 0, pad_left: int = 0, bgr: bool = False,
                            keep_depth: bool = False):
@@ -1781,24 +1780,21 @@ class HipOps:
         CUDA uint8 tensor of ``surface.nbytes`` bytes, any alignment -- a decoder's surface in place) -> ``window=(y0, x0, h, w)`` of it
         (default: all; even origin) as ``dst`` fp32 planar RGB [3,Hp,Wp] with replicate padding, the window at (pad_top, pad_left), and /
         or ``dst_u8`` uint8 [h,w,3] (BGR if ``bgr``).  ``keep_depth`` (a 10-bit surface, ``dst`` only): q / 1023, otherwise clip8 RGB
-        and q / 255 (include/atmvfi.h atmvfi_yuv_surface_decode; the bits of ``yuv.decode_numpy`` / ``decode_numpy_f32``)."""
+        and q / 255 (include/atmvfi.h atmvfi_yuv_decode; the bits of ``yuv.decode_numpy`` / ``decode_numpy_f32``)."""
         s = surface
         if not isinstance(s, Surface):
             raise ValueError(f"yuv_surface_decode: surface must be a yuv.Surface (got {type(s).__name__})")
         if s.subsampling != "420":
             raise _not_420("yuv_surface_decode", s)
-        h, w = s.height, s.width
-        y0, x0, wh, ww = (0, 0, h, w) if window is None else _window("yuv_surface_decode", s, window)
+        y0, x0, wh, ww = (0, 0, s.height, s.width) if window is None else _window("yuv_surface_decode", s, window)
         hp, wp, meta = self._yuv_decode_args("yuv_surface_decode", buf, s, dst_u8, dst, y0, x0, wh, ww, pad_top, pad_left, keep_depth)
-        self._run("yuv_surface_decode", meta, self.lib.atmvfi_yuv_surface_decode, _ptr(buf), h, w, int(s.depth), s.matrix_id, int(s.full_range),
-                  s.siting_id, s.chroma_id, int(s.msb), int(s.pitch), int(s.chroma_pitch), int(s.chroma_offset), int(bool(keep_depth)), y0, x0,
-                  wh, ww, _ptr(dst_u8), int(bool(bgr)), _ptr(dst), hp, wp, int(pad_top), int(pad_left), self._stream())
+        self._launch_yuv_decode("yuv_surface_decode", meta, s, buf, keep_depth, 0, y0, x0, wh, ww, dst_u8, bgr, dst, hp, wp, pad_top, pad_left)
 
     def yuv_surface_encode(self, buf, surface, src_u8=None, src=None, pad_top: int = 0, pad_left: int = 0, bgr: bool = False):
         """``src_u8`` uint8 [H,W,3] (BGR if ``bgr``; 8-bit surfaces only) or ``src`` fp32 planar RGB [3,Hp,Wp] with the frame at
         (pad_top, pad_left) -- exactly one -- -> ``buf``, one frame of the TIGHT ``surface`` (a contiguous CUDA uint8 tensor of
         ``surface.nbytes`` bytes).  A 10-bit surface is encoded from ``src`` in units of 1 / 1023 (include/atmvfi.h
-        atmvfi_yuv_surface_encode; the bits of ``yuv.encode_numpy``)."""
+        atmvfi_yuv_encode; the bits of ``yuv.encode_numpy``)."""
         s = surface
         if not isinstance(s, Surface):
             raise ValueError(f"yuv_surface_encode: surface must be a yuv.Surface (got {type(s).__name__})")
@@ -1806,39 +1802,31 @@ class HipOps:
             raise ValueError("yuv_surface_encode: surface must be tight (encodes write no padding: surface.tight())")
         if s.subsampling != "420":
             raise _not_420("yuv_surface_encode", s)
-        h, w, hp, wp, meta = self._yuv_encode_args("yuv_surface_encode", buf, s, src_u8, src, pad_top, pad_left)
-        self._run("yuv_surface_encode", meta, self.lib.atmvfi_yuv_surface_encode, _ptr(src_u8), int(bool(bgr)), _ptr(src), hp, wp, int(pad_top),
-                  int(pad_left), h, w, int(s.depth), s.matrix_id, int(s.full_range), s.siting_id, s.chroma_id, int(s.msb), _ptr(buf),
-                  self._stream())
+        hp, wp, meta = self._yuv_encode_args("yuv_surface_encode", buf, s, src_u8, src, pad_top, pad_left)
+        self._launch_yuv_encode("yuv_surface_encode", meta, s, buf, src_u8, bgr, src, hp, wp, pad_top, pad_left)
 
     def yuv_sub_decode(self, buf, fmt_or_surface, dst_u8=None, dst=None, window=None, pad_top: int = 0, pad_left: int = 0, bgr: bool = False,
                        keep_depth: bool = False):
         """``yuv_surface_decode`` for a ``yuv.Format`` or planar ``yuv.Surface`` of any subsampling (4:2:2, 4:4:4; "420" is the surface
         call itself): the window's origin is a multiple of the subsampling step per axis -- even x0 for 4:2:2, anything for 4:4:4
-        (include/atmvfi.h atmvfi_yuv_sub_decode; the bits of ``yuv.decode_numpy`` / ``decode_numpy_f32``)."""
+        (include/atmvfi.h atmvfi_yuv_decode; the bits of ``yuv.decode_numpy`` / ``decode_numpy_f32``)."""
         if not hasattr(fmt_or_surface, "subsampling_id"):
             raise ValueError(f"yuv_sub_decode: a yuv.Format or yuv.Surface expected (got {type(fmt_or_surface).__name__})")
         s = as_surface(fmt_or_surface)
-        h, w = s.height, s.width
-        y0, x0, wh, ww = (0, 0, h, w) if window is None else _window("yuv_sub_decode", s, window)
+        y0, x0, wh, ww = (0, 0, s.height, s.width) if window is None else _window("yuv_sub_decode", s, window)
         hp, wp, meta = self._yuv_decode_args("yuv_sub_decode", buf, s, dst_u8, dst, y0, x0, wh, ww, pad_top, pad_left, keep_depth)
-        self._run("yuv_sub_decode", meta, self.lib.atmvfi_yuv_sub_decode, _ptr(buf), h, w, int(s.depth), s.matrix_id, int(s.full_range),
-                  s.siting_id, s.subsampling_id, s.chroma_id, int(s.msb), int(s.pitch), int(s.chroma_pitch), int(s.chroma_offset),
-                  int(bool(keep_depth)), y0, x0, wh, ww, _ptr(dst_u8), int(bool(bgr)), _ptr(dst), hp, wp, int(pad_top), int(pad_left),
-                  self._stream())
+        self._launch_yuv_decode("yuv_sub_decode", meta, fmt_or_surface, buf, keep_depth, 0, y0, x0, wh, ww, dst_u8, bgr, dst, hp, wp, pad_top, pad_left)
 
     def yuv_sub_encode(self, buf, fmt_or_surface, src_u8=None, src=None, pad_top: int = 0, pad_left: int = 0, bgr: bool = False):
         """``yuv_surface_encode`` for a ``yuv.Format`` or tight planar ``yuv.Surface`` of any subsampling (include/atmvfi.h
-        atmvfi_yuv_sub_encode; the bits of ``yuv.encode_numpy``)."""
+        atmvfi_yuv_encode; the bits of ``yuv.encode_numpy``)."""
         if not hasattr(fmt_or_surface, "subsampling_id"):
             raise ValueError(f"yuv_sub_encode: a yuv.Format or yuv.Surface expected (got {type(fmt_or_surface).__name__})")
         s = as_surface(fmt_or_surface)
         if not s.is_tight:
             raise ValueError("yuv_sub_encode: surface must be tight (encodes write no padding: surface.tight())")
-        h, w, hp, wp, meta = self._yuv_encode_args("yuv_sub_encode", buf, s, src_u8, src, pad_top, pad_left)
-        self._run("yuv_sub_encode", meta, self.lib.atmvfi_yuv_sub_encode, _ptr(src_u8), int(bool(bgr)), _ptr(src), hp, wp, int(pad_top),
-                  int(pad_left), h, w, int(s.depth), s.matrix_id, int(s.full_range), s.siting_id, s.subsampling_id, s.chroma_id, int(s.msb),
-                  _ptr(buf), self._stream())
+        hp, wp, meta = self._yuv_encode_args("yuv_sub_encode", buf, s, src_u8, src, pad_top, pad_left)
+        self._launch_yuv_encode("yuv_sub_encode", meta, fmt_or_surface, buf, src_u8, bgr, src, hp, wp, pad_top, pad_left)
 
     def _rgb16_buf(self, who: str, buf, fmt, role: str):
         if not isinstance(fmt, DeepRGB):
@@ -1860,19 +1848,8 @@ class HipOps:
             raise ValueError("rgb16_decode: give dst, dst_u8 or both")
         h, w = fmt.height, fmt.width
         y0, x0, wh, ww = (0, 0, h, w) if window is None else _window("rgb16_decode", fmt, window)
-        nbytes = 6.0 * wh * ww
-        if dst is None:
-            hp, wp = wh, ww
-        else:
-            _f32_canvas(dst, "rgb16_decode", ": dst")
-            _, hp, wp = dst.shape
-            if pad_top < 0 or pad_left < 0 or wh + pad_top > hp or ww + pad_left > wp:
-                raise ValueError(f"rgb16_decode: canvas {hp} x {wp} is smaller than the window {wh} x {ww} plus padding ({pad_top}, {pad_left})")
-            nbytes += 12.0 * hp * wp
-        if dst_u8 is not None:
-            _u8_frame(dst_u8, "rgb16_decode", (wh, ww), ": dst_u8")
-            nbytes += 3.0 * wh * ww
-        self._run("rgb16_decode", {"bytes": nbytes}, self.lib.atmvfi_rgb16_decode, _ptr(buf), h, w, fmt.depth, fmt.layout_id, y0, x0, wh, ww,
+        hp, wp, nbytes = self._decode_sinks("rgb16_decode", dst_u8, dst, wh, ww, pad_top, pad_left)
+        self._run("rgb16_decode", {"bytes": nbytes + 6.0 * wh * ww}, self.lib.atmvfi_rgb16_decode, _ptr(buf), h, w, fmt.depth, fmt.layout_id, y0, x0, wh, ww,
                   _ptr(dst), hp, wp, int(pad_top), int(pad_left), _ptr(dst_u8), self._stream())
 
     def rgb16_encode(self, buf, fmt, src, pad_top: int = 0, pad_left: int = 0):
@@ -1890,8 +1867,9 @@ class HipOps:
         self._run("rgb16_encode", {"bytes": n + 12.0 * h * w}, self.lib.atmvfi_rgb16_encode, _ptr(src), hp, wp, int(pad_top), int(pad_left),
                   _ptr(buf), h, w, fmt.depth, fmt.layout_id, self._stream())
 
-    # The loops' colour conversion: a yuv.Format goes to the planar entry points as ever, a yuv.Surface to the two surface calls, and
-    # either with a subsampling other than 4:2:0 to the two sub calls; a yuv.DeepRGB to the two rgb16 calls (its depth is always kept).
+    # The loops' colour conversion: a yuv.Format goes to the planar wrappers as ever, a yuv.Surface to the two surface wrappers, and
+    # either with a subsampling other than 4:2:0 to the two sub wrappers -- for their refusals and their names in a profile; all launch
+    # atmvfi_yuv_decode / atmvfi_yuv_encode.  A yuv.DeepRGB goes to the two rgb16 calls (its depth is always kept).
     def yuv_decode(self, buf, fmt, dst_u8=None, dst=None, window=None, pad_top: int = 0, pad_left: int = 0, keep_depth: bool = False):
         if isinstance(fmt, DeepRGB):
             return self.rgb16_decode(buf, fmt, dst=dst, dst_u8=dst_u8, window=window, pad_top=pad_top, pad_left=pad_left)

@@ -274,12 +274,12 @@ class FramePipeline:
 
     ``pixfmt`` (a ``yuv.Format``; default None: uint8 [H,W,3] frames, the pipeline as above): frames in and out are packed planar I420
     arrays (1-D; uint16 samples for a 10-bit format, whose output is 8-bit).  Pinned and device staging hold ``frame_bytes`` per frame
-    (1.5 bytes per pixel); ``atmvfi_yuv420_to_rgb`` runs on the copy stream behind the upload and writes the padded fp32 input directly
-    -- and, with ``scene``, the resident uint8 RGB frame the signature reads -- and ``atmvfi_rgb_to_yuv420`` encodes the prediction from
+    (1.5 bytes per pixel); ``atmvfi_yuv_decode`` runs on the copy stream behind the upload and writes the padded fp32 input directly
+    -- and, with ``scene``, the resident uint8 RGB frame the signature reads -- and ``atmvfi_yuv_encode`` encodes the prediction from
     fp32 in front of the device -> host copy.  ``isBGR`` is ignored.
 
-    ``keep_depth`` (default False; changes nothing without a 10-bit ``pixfmt``): ``atmvfi_yuv420p10_to_f32`` decodes the uploaded
-    I420 bytes straight into the padded input (q / 1023: no 8-bit round trip), ``atmvfi_f32_to_yuv420p10`` encodes the prediction,
+    ``keep_depth`` (default False; changes nothing without a 10-bit ``pixfmt``): ``atmvfi_yuv_decode`` (``keep_depth``) decodes the uploaded
+    I420 bytes straight into the padded input (q / 1023: no 8-bit round trip), ``atmvfi_yuv_encode`` (depth 10) encodes the prediction,
     and the frames leave as 1-D uint16 arrays of ``pixfmt``.  The uint8 RGB frame is made only for a ``scene`` signature.
 
     ``pixfmt=yuv.DeepRGB(...)`` (RGB above 8 bits; ``keep_depth=True`` only, else ``ValueError``): the same path with

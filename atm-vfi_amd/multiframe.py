@@ -228,8 +228,8 @@ def interpolate_video_nx(frames, model, factor: int = 4, time_interval: int = 1,
     ``ValueError``); ``isBGR`` is ignored.
 
     ``keep_depth`` (default False; changes nothing without a 10-bit ``pixfmt``): the 10-bit depth is kept end to end.  Every uploaded
-    frame is decoded by ``atmvfi_yuv420p10_to_f32`` straight from its I420 bytes into the pool slot (the crop as the kernel's window;
-    the network sees q / 1023, no 8-bit round trip), produced frames are ``atmvfi_f32_to_yuv420p10`` of the fp32 prediction (with
+    frame is decoded by ``atmvfi_yuv_decode`` (``keep_depth``) straight from its I420 bytes into the pool slot (the crop as the kernel's window;
+    the network sees q / 1023, no 8-bit round trip), produced frames are ``atmvfi_yuv_encode`` (depth 10) of the fp32 prediction (with
     ``tta``: of the fp32 average) and leave as 1-D uint16 arrays of ``pixfmt.cropped(h, w)``; deeper levels consume the unrounded
     prediction as always.  The resident uint8 RGB frame is made only when ``scene`` needs its signature: signatures, and so cut
     decisions, are those of the 8-bit path.  A model without the HIP backend does the same with the numpy twins.

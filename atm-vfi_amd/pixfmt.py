@@ -4,6 +4,7 @@ hip_ops.py validates against these classes and yuv.py, which re-exports every na
 loops' front ends on them."""
 from __future__ import annotations
 
+import ctypes
 import functools
 from dataclasses import dataclass, replace
 from typing import Optional, Tuple
@@ -14,6 +15,26 @@ import numpy as np
 MATRICES = ("bt601", "bt709")
 SITINGS = ("centre", "left")
 SUBSAMPLINGS = ("420", "422", "444")        # ids 0 / 1 / 2 (include/atmvfi.h)
+
+
+class YuvDesc(ctypes.Structure):
+    """``atmvfi_yuv_desc`` (include/atmvfi.h): what one frame is, without pointers.  Zero means default / off."""
+    _fields_ = ([(n, ctypes.c_int32) for n in ("H", "W", "depth", "matrix", "full_range", "siting", "subsampling", "chroma", "msb")]
+                + [(n, ctypes.c_int64) for n in ("pitch", "chroma_pitch", "chroma_offset")])
+
+
+@functools.lru_cache(maxsize=1024)
+def _desc_block(desc) -> YuvDesc:
+    """``desc_block`` of a ``Format`` (the packed planar frame: no strides) or a ``Surface`` (its own).  One block per descriptor VALUE:
+    equal descriptors share it, so a launch plan records one address for them; each keeps it as a ``cached_property`` (which writes the
+    frozen object's ``__dict__``, not through ``__setattr__``): the device calls pass it by address on every launch."""
+    f = desc.fmt if isinstance(desc, Surface) else desc
+    blk = YuvDesc(H=f.height, W=f.width, depth=f.depth, matrix=f.matrix_id, full_range=int(f.full_range), siting=f.siting_id,
+                  subsampling=f.subsampling_id)
+    if f is not desc:
+        blk.chroma, blk.msb = desc.chroma_id, int(desc.msb)
+        blk.pitch, blk.chroma_pitch, blk.chroma_offset = desc.pitch, desc.chroma_pitch, desc.chroma_offset
+    return blk
 
 
 @dataclass(frozen=True)
@@ -101,6 +122,8 @@ class Format:
         ch, cw = self.chroma_shape
         n, c = self.height * self.width, ch * cw
         return a[:n].reshape(self.height, self.width), a[n:n + c].reshape(ch, cw), a[n + c:].reshape(ch, cw)
+
+    desc_block = functools.cached_property(_desc_block)
 
     def as_8bit(self) -> "Format":
         return self if self.depth == 8 else replace(self, depth=8)
@@ -216,6 +239,7 @@ class Surface:
     subsampling_id = property(lambda self: self.fmt.subsampling_id)
     steps = property(lambda self: self.fmt.steps)
     chroma_id = property(lambda self: CHROMAS.index(self.chroma))
+    desc_block = functools.cached_property(_desc_block)
 
     @property
     def itemsize(self) -> int:

@@ -93,10 +93,10 @@ class _Uploader:
     """Every source frame goes to the device ONCE: a ring of pinned host slots + device staging filled on a copy stream, ahead of the
     kernel that converts it (as ``host_io.interpolate_video_2x_distributed`` does).
 
-    ``pixfmt=(ops, fmt)`` (planar I420 input): pinned and device staging hold ``fmt.frame_bytes``; ``atmvfi_yuv420_to_rgb`` runs on the
+    ``pixfmt=(ops, fmt)`` (planar I420 input): pinned and device staging hold ``fmt.frame_bytes``; ``atmvfi_yuv_decode`` runs on the
     copy stream behind the copy and fills the slot's resident uint8 RGB frame ``d`` -- what the probes, ``take`` and everything
     downstream read, as for an RGB upload.  ``deep`` (a 10-bit ``pixfmt`` with ``keep_depth``): ``take`` hands the uploaded I420 bytes
-    themselves to ``convert`` (``atmvfi_yuv420p10_to_f32`` decodes them into the pool slot: no 8-bit round trip); the uint8 RGB frame is
+    themselves to ``convert`` (``atmvfi_yuv_decode`` (``keep_depth``) decodes them into the pool slot: no 8-bit round trip); the uint8 RGB frame is
     made only for a signature (or a difference).  A ``yuv.DeepRGB`` ``pixfmt`` is always ``deep``: the slot's ``yuv`` bytes are the
     uploaded RGB frame, ``atmvfi_rgb16_decode`` decodes them into the pool slot and, for a signature or a difference, makes the 8-bit
     probe picture ``d`` on the copy stream.

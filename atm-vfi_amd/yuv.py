@@ -1,5 +1,5 @@
 """Planar YUV 4:2:0 (I420) frames and Y4M files for the video loops: the format, the host twins of the HIP colour conversion
-(``atmvfi_yuv420_to_rgb`` / ``atmvfi_rgb_to_yuv420``, csrc/yuv.hip / yuv_encode.hip), a YUV4MPEG2 reader and writer, and ``interpolate_y4m``.
+(``atmvfi_yuv_decode`` / ``atmvfi_yuv_encode``, csrc/yuv.hip / yuv_encode.hip), a YUV4MPEG2 reader and writer, and ``interpolate_y4m``.
 
 Nothing of the reference: its scripts read PNGs and hand video to OpenCV.  Decoders, ``ffmpeg -f yuv4mpegpipe`` pipes and the Xiph
 clips deliver planar 4:2:0; with ``pixfmt=Format(...)`` the loops (``interpolate_video_2x`` / ``FramePipeline`` /
@@ -13,19 +13,19 @@ uint8 RGB pixel (from fp32: ``frame_f32_to_u8``'s pixel), box-filters chroma ove
 applies ``COEFFS[..][1]``.  Not reproduced: ffmpeg's swscale (other filters, other rounding) -- it is not available to compare with.
 By default 10-bit input is decoded to 8-bit RGB and what the loops produce is 8-bit.
 
-``keep_depth=True`` (the loops, ``interpolate_y4m``) keeps a 10-bit format's depth end to end (``atmvfi_yuv420p10_to_f32`` /
-``atmvfi_f32_to_yuv420p10``, the same two files; twins ``decode_numpy_f32`` and ``encode_numpy`` of an fp32 source): the same chroma
+``keep_depth=True`` (the loops, ``interpolate_y4m``) keeps a 10-bit format's depth end to end (``atmvfi_yuv_decode`` (``keep_depth``) /
+``atmvfi_yuv_encode`` (depth 10), the same two files; twins ``decode_numpy_f32`` and ``encode_numpy`` of an fp32 source): the same chroma
 filters on the 10-bit samples, ``COEFFS10[matrix]`` at 14 bits (luma scaled by 876 / 1023, chroma by 896 / 1023), offsets 64 / 512,
 RGB clipped to 0..1023 and handed to the network as ``q / 1023`` (the fp32 division); encoding takes
 ``clip(rint(fl32(x * 1023)), 0, 1023)`` and writes uint16 samples.  Produced frames are 10-bit, originals the caller's arrays.
 
-``Surface`` (``atmvfi_yuv_surface_decode`` / ``atmvfi_yuv_surface_encode``): what a hardware decoder or an ``ffmpeg -f rawvideo``
+``Surface`` (``atmvfi_yuv_decode`` / ``atmvfi_yuv_encode``): what a hardware decoder or an ``ffmpeg -f rawvideo``
 pipe delivers -- NV12 / NV21 / P010 (interleaved chroma, 10-bit samples in the upper bits) and frames with a row pitch and a chroma
 offset.  It is accepted wherever a ``Format`` is (``pixfmt=``, the twins, ``crop``, ``to_8bit``); the arithmetic is the ``Format``'s,
 applied to the samples the surface describes.  ``repack`` moves frames between layouts, ``RawReader`` / ``RawWriter`` /
 ``interpolate_raw`` are the headerless counterparts of the Y4M classes.
 
-``Format(..., subsampling="422" | "444")`` (``atmvfi_yuv_sub_decode`` / ``atmvfi_yuv_sub_encode``): planar 4:2:2 and 4:4:4 frames, 8
+``Format(..., subsampling="422" | "444")`` (``atmvfi_yuv_decode`` / ``atmvfi_yuv_encode``): planar 4:2:2 and 4:4:4 frames, 8
 and 10 bit, with chroma planes [H, cw] and [H, W].  Decoding 4:2:2 filters along the row only (the columns and weights of 4:2:0,
 ``(wx0 c0 + wx1 c1 + 2) >> 2``), 4:4:4 takes the pixel's own samples; encoding takes the same horizontal taps over one row (sh = 1
 centre, 2 left) or the pixel itself (sh = 0).  Coefficients, offsets, clips and depth rules are the 4:2:0 ones.  A window's or crop's
@@ -254,7 +254,7 @@ def _decode_window(buf, fmt: Format, y0: int, x0: int, h: int, w: int, keep: boo
 
 
 def decode_numpy(buf, fmt: Format, bgr: bool = False) -> np.ndarray:
-    """Packed I420 frame -> uint8 [H,W,3] RGB (BGR if ``bgr``): the bits of ``atmvfi_yuv420_to_rgb``'s ``dst_u8``.  A ``DeepRGB``
+    """Packed I420 frame -> uint8 [H,W,3] RGB (BGR if ``bgr``): the bits of ``atmvfi_yuv_decode``'s ``dst_u8``.  A ``DeepRGB``
     frame: its 8-bit probe picture (``rgb16.probe_numpy``)."""
     if isinstance(fmt, DeepRGB):
         q = rgb16.probe_numpy(buf, fmt)
@@ -264,7 +264,7 @@ def decode_numpy(buf, fmt: Format, bgr: bool = False) -> np.ndarray:
 
 
 def window_numpy(buf, fmt: Format, mode: int, y0: int, x0: int, h: int, w: int) -> np.ndarray:
-    """Packed I420 frame -> uint8 [h,w,3] RGB: the bits of ``atmvfi_yuv420_window``'s ``dst_u8`` -- ``mode`` 0: the h x w window at
+    """Packed I420 frame -> uint8 [h,w,3] RGB: the bits of ``atmvfi_yuv_decode`` (``mode``)'s ``dst_u8`` -- ``mode`` 0: the h x w window at
     (y0, x0) of ``decode_numpy``'s frame; ``mode`` 1: the 2x area reduction ``(a + b + c + d + 2) >> 2`` of its 2h x 2w window there
     (each pixel clipped to 8 bits first).  The window is a window of the whole frame's decode: chroma neighbours are the frame's.
     Even origin, as ``crop``.  Only the window is decoded."""
@@ -286,7 +286,7 @@ def window_numpy(buf, fmt: Format, mode: int, y0: int, x0: int, h: int, w: int) 
 
 
 def decode_numpy_f32(buf, fmt: Format, window=None) -> np.ndarray:
-    """Packed 10-bit I420 frame -> fp32 [h,w,3] RGB = q / 1023, the depth kept: the bits of ``atmvfi_yuv420p10_to_f32`` (without
+    """Packed 10-bit I420 frame -> fp32 [h,w,3] RGB = q / 1023, the depth kept: the bits of ``atmvfi_yuv_decode`` (``keep_depth``) (without
     padding).  ``window=(y0, x0, h, w)`` (even origin, as ``crop``): that window of the whole frame's decode -- chroma neighbours
     are the frame's, not the window's.  A ``DeepRGB`` frame: ``rgb16.decode_numpy_f32`` (q / top; any origin)."""
     if isinstance(fmt, DeepRGB):
@@ -305,9 +305,9 @@ def decode_numpy_f32(buf, fmt: Format, window=None) -> np.ndarray:
 
 
 def encode_numpy(rgb, fmt: Format, bgr: bool = False) -> np.ndarray:
-    """uint8 [H,W,3] RGB (BGR if ``bgr``) -> packed 8-bit I420 frame (1-D uint8): the bits of ``atmvfi_rgb_to_yuv420``.  For a 10-bit
+    """uint8 [H,W,3] RGB (BGR if ``bgr``) -> packed 8-bit I420 frame (1-D uint8): the bits of ``atmvfi_yuv_encode``.  For a 10-bit
     ``fmt``: fp32 [H,W,3] RGB in units of 1 (finite; values outside [0, 1] clamp) -> packed 10-bit frame (1-D uint16), the pixel
-    ``clip(rint(fl32(x * 1023)), 0, 1023)``: the bits of ``atmvfi_f32_to_yuv420p10``; a uint8 source is refused.  A ``DeepRGB``
+    ``clip(rint(fl32(x * 1023)), 0, 1023)``: the bits of ``atmvfi_yuv_encode`` (depth 10); a uint8 source is refused.  A ``DeepRGB``
     format: ``rgb16.encode_numpy`` of an fp32 source."""
     if isinstance(fmt, DeepRGB):
         return rgb16.encode_numpy(rgb, fmt)

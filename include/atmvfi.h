@@ -604,9 +604,9 @@ int atmvfi_frame_compose(void* dst /*uint8 [H,W,3]*/, const void* border /*uint8
 
 /* The active picture on YUV streams and in the retimed loop (active.hip, yuv_encode.hip; ABI 0.22; atm-vfi_amd/active.py: bar_code,
  * yuv_borders_numpy / yuv_compose_numpy; per-sample models tests/cpu_yuv_active.py).  Nothing of the reference.  The frames are those of
- * the surface calls below (depth, chroma, msb, pitch / chroma_pitch / chroma_offset in BYTES, 0: tight; subsampling as in
- * atmvfi_yuv_sub_encode).
- * atmvfi_yuv_borders: the LUMA plane of one resident frame -> int32 out[H + W] on the device:
+ * the frame descriptor below (atmvfi_yuv_desc: depth, subsampling, chroma, msb, pitch / chroma_pitch / chroma_offset in BYTES, 0: tight).
+ * atmvfi_yuv_borders: the LUMA plane of one resident frame -> int32 out[H + W] on the device (of the descriptor it reads H, W, depth,
+ *   msb and pitch):
  *   out[y]     = the largest luma sample VALUE of row y (the stored sample, >> 6 with msb);   out[H + x] = that of column x.
  *   The maximum commutes with every monotone map, so raw codes are reported and the host maps its threshold once (active.bar_code).
  *   depth 8 or 10, msb only at depth 10, pitch a multiple of the sample size and at least a row's bytes (0: tight); chroma layout and
@@ -618,26 +618,27 @@ int atmvfi_frame_compose(void* dst /*uint8 [H,W,3]*/, const void* border /*uint8
  *   scratch, the caller's; the query returns -1 for a frame the call would refuse.  Stream-ordered: a partial launch and a reduce
  *   launch, no host synchronisation, no allocation.
  * atmvfi_yuv_compose: dst = ONE TIGHT frame of (H, W, depth, subsampling, chroma, msb), a produced window put back into a full frame.
- *   Outside the window (y0, x0, h, w) dst gets the sample values of `border`, a resident surface of the same size, depth, subsampling,
- *   chroma layout and msb with its own border_pitch / border_chroma_pitch / border_chroma_offset (the uploaded source frame in
- *   place): plane by plane, the stored samples as they are (of an msb word the value's ten bits; the low six leave as zero) --
+ *   `border_desc` describes `border`, a resident surface of that size, depth, subsampling, chroma layout and msb; its pitch /
+ *   chroma_pitch / chroma_offset are the border's own (the uploaded source frame in place), dst is that frame without them.
+ *   Outside the window (y0, x0, h, w) dst gets the sample values of `border`:
+ *   plane by plane, the stored samples as they are (of an msb word the value's ten bits; the low six leave as zero) --
  *   yuv.repack(border, surface, surface.tight()) outside the window.  Inside, exactly the samples
- *   atmvfi_yuv_sub_encode writes for the h x w picture as a frame of the cropped format (matrix, full_range, siting; chroma sums clamp
+ *   atmvfi_yuv_encode writes for the h x w picture as a frame of the cropped format (matrix, full_range, siting; chroma sums clamp
  *   at the WINDOW's edges), from exactly one of: src, the fp32 canvas [3,Hp,Wp] with the window at (pad_top, pad_left); src_u8, uint8
  *   [h,w,3] RGB (depth 8 only).  The encode arithmetic is that kernel itself, launched with the window's origin in the frame.
  *   Window rule: y0 and x0 are multiples of the subsampling step per axis, y0 + h and x0 + w are multiples of it or equal H / W: every
  *   chroma sample belongs wholly to the window or wholly to the bars.  dst must not overlap border (ATMVFI_EINVAL).  Only the bar
  *   region of border and the window of the source are read; every output sample is written by exactly one lane, vector stores only,
  *   no padding byte exists in dst.  Any geometry, pitch and alignment is accepted; the vector paths run under the conditions of the
- *   surface calls with x0 a multiple of 4 as well (bars: dst, border and its strides multiples of 4 bytes).  Same bits either way.
+ *   decoder surfaces below with x0 a multiple of 4 as well (bars: dst, border and its strides multiples of 4 bytes).  Same bits either way.
  *   At most two launches (the bars; the window -- none for a window that is the frame / bars that are empty).  All checks run on
  *   the host before the first launch (ATMVFI_EINVAL). */
 int64_t atmvfi_yuv_borders_workspace_ints(int H, int W);
-int atmvfi_yuv_borders(const void* yuv, int H, int W, int depth, int msb, int64_t pitch, int32_t* out /*[H + W]*/, int32_t* workspace,
+struct atmvfi_yuv_desc;
+int atmvfi_yuv_borders(const struct atmvfi_yuv_desc* desc, const void* yuv, int32_t* out /*[H + W]*/, int32_t* workspace,
                        int64_t workspace_ints, void* stream);
-int atmvfi_yuv_compose(void* dst, const void* border, int H, int W, int depth, int matrix, int full_range, int siting, int subsampling,
-                       int chroma, int msb, int64_t border_pitch, int64_t border_chroma_pitch, int64_t border_chroma_offset, int y0, int x0,
-                       int h, int w, const float* src /*[3,Hp,Wp] or NULL*/, int Hp, int Wp, int pad_top, int pad_left,
+int atmvfi_yuv_compose(const struct atmvfi_yuv_desc* border_desc, void* dst, const void* border, int y0, int x0, int h, int w,
+                       const float* src /*[3,Hp,Wp] or NULL*/, int Hp, int Wp, int pad_top, int pad_left,
                        const void* src_u8 /*uint8 [h,w,3] or NULL*/, void* stream);
 
 /* Synthetic shutter for the retimed video loop (shutter.hip; ABI 0.18; atm-vfi_amd/shutter.py holds the definition -- which samples an
@@ -691,25 +692,21 @@ int atmvfi_shutter_table(int light, uint16_t out[256]);
  *   atmvfi_frame_f32_to_u8's pixel.  Y = clip8(((eY . p + 2^13) >> 14) + yo).  Chroma sample (j, i) takes the un-rounded per-channel
  *   sums s over rows 2j and min(2j + 1, H - 1) and columns 2i, min(2i + 1, W - 1) with weights 1 (centre; sh = 2) or max(2i - 1, 0),
  *   2i, min(2i + 1, W - 1) with weights 1, 2, 1 (left; sh = 3):  U = clip8(((eU . s + 2^(13 + sh)) >> (14 + sh)) + 128), V with eV.
- * atmvfi_yuv420_to_rgb: dst_u8 (or NULL) uint8 [H,W,3], BGR if `bgr`; dst (or NULL) fp32 planar RGB [3,Hp,Wp] = q / 255 (a true fp32
- *   division) with replicate padding, the frame at (pad_top, pad_left): the bits of atmvfi_frame_u8_to_f32 applied to dst_u8.  Not
- *   both NULL; Hp, Wp and the padding are read only with dst (4-byte aligned).
- * atmvfi_rgb_to_yuv420: exactly one of src_u8 (uint8 [H,W,3], BGR if `bgr`) and src (fp32 planar RGB [3,Hp,Wp], the frame at
- *   (pad_top, pad_left), 4-byte aligned) -> yuv, depth 8.
+ * Decode of the whole frame (atmvfi_yuv_decode, window = the frame, mode 0): dst_u8 (or NULL) uint8 [H,W,3], BGR if `bgr`; dst (or NULL)
+ *   fp32 planar RGB [3,Hp,Wp] = q / 255 (a true fp32 division) with replicate padding, the frame at (pad_top, pad_left): the bits of
+ *   atmvfi_frame_u8_to_f32 applied to dst_u8.  Not both NULL; Hp, Wp and the padding are read only with dst (4-byte aligned).
+ * Encode at depth 8 (atmvfi_yuv_encode): exactly one of src_u8 (uint8 [H,W,3], BGR if `bgr`) and src (fp32 planar RGB [3,Hp,Wp], the
+ *   frame at (pad_top, pad_left), 4-byte aligned) -> yuv.
  * Any geometry and pointer alignment is accepted (for odd W the U plane starts at an odd byte); dword Y accesses, 16-byte plane
  * accesses and 12-byte RGB groups are used when the byte pointers are 4-byte and the fp32 pointer 16-byte aligned and W, Wp and
  * pad_left are multiples of 4.  Both paths give the same bits.  Every output byte is written by the call; no atomics, nothing
- * pre-zeroed.  All checks run on the host before the launch (ATMVFI_EINVAL). */
-int atmvfi_yuv420_to_rgb(const void* yuv, int H, int W, int depth, int matrix, int full_range, int siting, void* dst_u8, int bgr,
-                         float* dst, int Hp, int Wp, int pad_top, int pad_left, void* stream);
-int atmvfi_rgb_to_yuv420(const void* src_u8, int bgr, const float* src, int Hp, int Wp, int pad_top, int pad_left, int H, int W,
-                         int matrix, int full_range, int siting, void* yuv, void* stream);
-
-/* One resident packed I420 frame -> the window of atmvfi_frame_u8_window, without the RGB frame in between (yuv.hip; ABI 0.17;
- * the Xiph 2K / 4K evaluation on Y4M clips, atm-vfi_amd/evaluate.py; host twin yuv.window_numpy).  Nothing of the reference: its script
- * converts the clips to rgb24 PNGs with ffmpeg first.  The frame layout, depth 8 / 10 (10-bit samples decode to clip8 RGB), matrix,
- * full_range and siting are exactly those of atmvfi_yuv420_to_rgb.  No new arithmetic: let q(Y, X) be the clip8 RGB pixel that
- * atmvfi_yuv420_to_rgb gives at (Y, X) of the WHOLE H x W frame -- chroma neighbours clamp at the frame's edges, never at the window's --
+ * pre-zeroed.  All checks run on the host before the launch (ATMVFI_EINVAL).
+ *
+ * A window of a packed I420 frame -> the window of atmvfi_frame_u8_window, without the RGB frame in between (atmvfi_yuv_decode with
+ * `mode`; yuv.hip; the Xiph 2K / 4K evaluation on Y4M clips, atm-vfi_amd/evaluate.py; host twin yuv.window_numpy).  Nothing of the
+ * reference: its script converts the clips to rgb24 PNGs with ffmpeg first.  10-bit samples decode to clip8 RGB.  No new arithmetic:
+ * let q(Y, X) be the clip8 RGB pixel that the whole-frame decode above gives at (Y, X) of the WHOLE H x W frame -- chroma neighbours
+ * clamp at the frame's edges, never at the window's --
  *   mode 0 (crop):    out(y, x) = q(y0 + y, x0 + x);
  *   mode 1 (area 2x): out(y, x) = (q(y0 + 2y, x0 + 2x) + q(y0 + 2y, x0 + 2x + 1) + q(y0 + 2y + 1, x0 + 2x) + q(y0 + 2y + 1, x0 + 2x + 1) + 2) >> 2
  *                     per channel: the four pixels are clipped to 8 bits first and averaged then (an rgb24 picture, then cv2.INTER_AREA
@@ -718,46 +715,42 @@ int atmvfi_rgb_to_yuv420(const void* src_u8, int bgr, const float* src, int Hp, 
  *                     replicate padding by clamping the output coordinate into the window (4-byte aligned; Hp, Wp and the padding are
  *                     read only with dst);
  *   dst_u8 (or NULL): uint8 [h,w,3] RGB, the same integer pixels, un-padded: the ground truth form atmvfi_ssim_psnr reads in place.
- * Both are bit for bit atmvfi_frame_u8_window(mode, y0, x0, h, w, ...) of atmvfi_yuv420_to_rgb's dst_u8.
+ * Both are bit for bit atmvfi_frame_u8_window(mode, y0, x0, h, w, ...) of the whole-frame decode's dst_u8.
  * Refused on the host before any launch (ATMVFI_EINVAL): a null source; both outputs NULL; H or W below 1, an unknown matrix, range,
- * siting or depth; 10-bit full range; a mode other than 0 / 1; h, w < 1 or a negative origin; a window that leaves the frame (2h x 2w
- * source pixels in mode 1); an odd y0 or x0 (an even origin keeps the two luma rows and columns of a chroma sample together, as
- * yuv.crop requires); a canvas smaller than the window plus its padding.
+ * siting or depth; 10-bit full range; a mode other than 0 / 1; mode 1 on anything but a packed planar LSB 4:2:0 frame to pixels
+ * 0..255; h, w < 1 or a negative origin; a window that leaves the frame (2h x 2w source pixels in mode 1); an odd y0 or x0 (an even
+ * origin keeps the two luma rows and columns of a chroma sample together, as yuv.crop requires); a canvas smaller than the window
+ * plus its padding.
  * Any geometry and pointer alignment is accepted otherwise; dword Y loads, 16-byte plane stores and 12-byte RGB groups are used when the
  * byte pointers are 4-byte and the fp32 pointer 16-byte aligned and W, x0, w, Wp and pad_left are multiples of 4.  Both paths give the
- * same bits.  Every output byte is written by the call; vector stores only, no atomics, nothing pre-zeroed. */
-int atmvfi_yuv420_window(const void* yuv, int H, int W, int depth, int matrix, int full_range, int siting, int mode, int y0, int x0, int h,
-                         int w, float* dst, int Hp, int Wp, int pad_top, int pad_left, void* dst_u8, void* stream);
-
-/* The same frames with the 10-bit depth kept end to end (yuv.hip, yuv_encode.hip; ABI 0.15): 10-bit limited-range I420 (little-endian uint16, values
- * 0..1023; frame layout, matrix and siting as above) <-> fp32 planar RGB in units of 1 / 1023.  The calls above decode 10-bit samples
- * to clip8 RGB and encode 8-bit frames only; these hand the network q / 1023 and write its prediction back as 10-bit samples.  The
- * project's own bit-exact contract in int32 (>> floors); yuv.decode_numpy_f32 / yuv.encode_numpy give the same bits on the host.
+ * same bits.  Every output byte is written by the call; vector stores only, no atomics, nothing pre-zeroed.
+ *
+ * The same frames with the 10-bit depth kept end to end (depth 10; decode with keep_depth 1, encode from src): 10-bit limited-range
+ * I420 (little-endian uint16, values 0..1023; frame layout, matrix and siting as above) <-> fp32 planar RGB in units of 1 / 1023.
+ * Without keep_depth a decode takes 10-bit samples to clip8 RGB; with it the network gets q / 1023, and the encode writes its
+ * prediction back as 10-bit samples.  The project's own bit-exact contract in int32 (>> floors); yuv.decode_numpy_f32 /
+ * yuv.encode_numpy give the same bits on the host.
  * Coefficients: rint(c * 2^14) of the same float64 matrices, luma scaled by 876 / 1023 and chroma by 896 / 1023:
  *                       decode [kY, kRV, kGU, kGV, kBU]        encode rows Y / U / V over (R, G, B)
  *     bt601 10 bit    19133, 26226,  -6438, -13359, 33148    (4195,  8235, 1599) / (-2421, -4754, 7175) / (7175, -6008, -1167)
  *     bt709 10 bit    19133, 29459,  -3504,  -8757, 34711    (2983, 10034, 1013) / (-1644, -5531, 7175) / (7175, -6517,  -658)
- * atmvfi_yuv420p10_to_f32: chroma upsampling exactly as above (rows, columns, weights for both sitings, (.. + 8) >> 4) on the 10-bit
+ * Decode with keep_depth: chroma upsampling exactly as above (rows, columns, weights for both sitings, (.. + 8) >> 4) on the 10-bit
  *   samples; y = Y - 64, u = U' - 512, v = V' - 512; R10 = clip(0, 1023, (kY y + kRV v + 2^13) >> 14),
  *   G10 = clip(0, 1023, (kY y + kGU u + kGV v + 2^13) >> 14), B10 = clip(0, 1023, (kY y + kBU u + 2^13) >> 14); dst fp32 planar RGB
  *   [3,Hp,Wp] = q / 1023 with the bits of the fp32 division.  The call decodes the window (y0, x0, h, w) of the H x W frame -- inside the
  *   frame, even origin -- to (pad_top, pad_left) of the canvas, replicate padding by clamping the output coordinate into the window.
  *   The window is a window of the whole frame's decode: chroma neighbours clamp at the frame's edges, not the window's.
- * atmvfi_f32_to_yuv420p10: src fp32 planar RGB [3,Hp,Wp], the frame at (pad_top, pad_left); source pixel p = clip(0, 1023,
+ * Encode at depth 10: src fp32 planar RGB [3,Hp,Wp], the frame at (pad_top, pad_left); source pixel p = clip(0, 1023,
  *   rint(fl32(x * 1023))), half to even (finite inputs; values outside [0, 1] clamp); Y = clip(0, 1023, ((eY . p + 2^13) >> 14) + 64);
  *   chroma from the un-rounded sums s with the taps and sh of the 8-bit encode: U = clip(0, 1023, ((eU . s + 2^(13 + sh)) >> (14 + sh))
  *   + 512), V with eV.
  * Any geometry and pointer alignment of the frame is accepted; the fp32 pointer must be 4-byte aligned.  8-byte Y accesses, dword
  * chroma pairs and 16-byte plane accesses are used when the frame pointer is 4-byte and the fp32 pointer 16-byte aligned and W, Wp,
  * pad_left (and x0, w) are multiples of 4.  Both paths give the same bits.  Every output byte and word is written by the call; no
- * atomics, nothing pre-zeroed.  All checks run on the host before the launch (ATMVFI_EINVAL). */
-int atmvfi_yuv420p10_to_f32(const void* yuv, int H, int W, int matrix, int siting, int y0, int x0, int h, int w, float* dst, int Hp, int Wp,
-                            int pad_top, int pad_left, void* stream);
-int atmvfi_f32_to_yuv420p10(const float* src, int Hp, int Wp, int pad_top, int pad_left, int H, int W, int matrix, int siting, void* yuv,
-                            void* stream);
-
-/* Decoder surfaces: NV12 / NV21 / P010 and pitched frames (yuv.hip, yuv_encode.hip; ABI 0.19; atm-vfi_amd/yuv.py: Surface holds the
- * definition on the host).  The pixel arithmetic is that of the four calls above, unchanged; what is new is where the samples lie.
+ * atomics, nothing pre-zeroed.  All checks run on the host before the launch (ATMVFI_EINVAL).
+ *
+ * Decoder surfaces: NV12 / NV21 / P010 and pitched frames (atm-vfi_amd/yuv.py: Surface holds the definition on the host).  The pixel
+ * arithmetic is the one above, unchanged; what differs is where the samples lie.
  * One frame is one buffer of samples (uint8, or little-endian uint16 at depth 10):
  *   chroma         0: planar, the U plane then the V plane (I420); 1: one plane of interleaved pairs, U first (NV12, P010); 2: the
  *                  same, V first (NV21)
@@ -768,14 +761,14 @@ int atmvfi_f32_to_yuv420p10(const float* src, int Hp, int Wp, int pad_top, int p
  *   chroma_offset  the byte offset of the first chroma row: a multiple of the sample size, at least pitch * H.  0: pitch * H.  The
  *                  planar V plane follows U at chroma_offset + chroma_pitch * ch.
  * The buffer ends with the last chroma row's own bytes; padding bytes are never read.
- * atmvfi_yuv_surface_decode: the window (y0, x0, h, w) of the surface -- inside the frame, even origin -- to (pad_top, pad_left) of dst
+ * atmvfi_yuv_decode: the window (y0, x0, h, w) of the surface -- inside the frame, even origin -- to (pad_top, pad_left) of dst
  *   (fp32 planar RGB [3,Hp,Wp], replicate padding by clamping the output coordinate into the window) and / or to dst_u8 (uint8 [h,w,3],
- *   BGR if `bgr`); chroma neighbours clamp at the FRAME's edges.  keep_depth 0: clip8 RGB and q / 255 from samples of either depth, the
- *   pixel of atmvfi_yuv420_to_rgb; keep_depth 1 (depth 10, dst only): q / 1023, the pixel of atmvfi_yuv420p10_to_f32.  A tight planar
- *   surface gives the bytes of those calls.
- * atmvfi_yuv_surface_encode: exactly one of src_u8 (uint8 [H,W,3], BGR if `bgr`; depth 8 only) and src (the fp32 canvas, the frame at
- *   (pad_top, pad_left)) -> a TIGHT surface of `chroma` / `msb`: at depth 8 the samples of atmvfi_rgb_to_yuv420, at depth 10 (src only)
- *   those of atmvfi_f32_to_yuv420p10.  No padding byte is ever written.
+ *   BGR if `bgr`); chroma neighbours clamp at the FRAME's edges.  keep_depth 0: clip8 RGB and q / 255 from samples of either depth;
+ *   keep_depth 1 (depth 10, dst only): q / 1023.  The layout changes no sample's value: every surface of a frame decodes to the bytes of
+ *   its tight planar frame.
+ * atmvfi_yuv_encode: exactly one of src_u8 (uint8 [H,W,3], BGR if `bgr`; depth 8 only) and src (the fp32 canvas, the frame at
+ *   (pad_top, pad_left)) -> a TIGHT surface of `chroma` / `msb` (the three strides are not read): the samples of the planar encode
+ *   of its depth.  No padding byte is ever written.
  * Any pitch, offset and pointer alignment is accepted (byte accesses).  The vector path -- dword / 8-byte Y groups, an interleaved
  * chroma row loaded ONCE for both planes (the aligned centre pair-of-pairs as one dword or one 8-byte load, each outer column as one
  * 2-byte or dword load: three loads per chroma row where two planes take six), both planes' chroma of a lane stored as one dword or
@@ -783,19 +776,12 @@ int atmvfi_f32_to_yuv420p10(const float* src, int Hp, int Wp, int pad_top, int p
  * chroma_pitch and chroma_offset multiples of 4 bytes (planar chroma: of 2 samples), and W, x0, w, Wp, pad_left are multiples of 4.
  * Both paths give the same bits.  Every output byte is written by exactly one lane; vector stores only, no atomics, nothing
  * pre-zeroed.  All checks run on the host before the launch (ATMVFI_EINVAL).
- * A decoder's surface that already lies in device memory (rocDecode, VA-API / AMF interop) is decoded in place by the first call:
- * hand over the mapped pointer with the surface's pitch and chroma offset; nothing is repacked or copied. */
-int atmvfi_yuv_surface_decode(const void* yuv, int H, int W, int depth, int matrix, int full_range, int siting, int chroma, int msb,
-                              int64_t pitch, int64_t chroma_pitch, int64_t chroma_offset, int keep_depth, int y0, int x0, int h, int w,
-                              void* dst_u8, int bgr, float* dst, int Hp, int Wp, int pad_top, int pad_left, void* stream);
-int atmvfi_yuv_surface_encode(const void* src_u8, int bgr, const float* src, int Hp, int Wp, int pad_top, int pad_left, int H, int W,
-                              int depth, int matrix, int full_range, int siting, int chroma, int msb, void* yuv, void* stream);
-
-/* Planar 4:2:2 and 4:4:4 frames, 8 and 10 bit (yuv.hip, yuv_encode.hip; ABI 0.20; atm-vfi_amd/yuv.py: Format.subsampling; per-pixel model
- * tests/cpu_yuv_sub.py).  The two surface calls above with one more argument after `siting`:
- *   subsampling    0: 4:2:0, chroma planes [(H + 1) / 2, (W + 1) / 2] -- the call IS the surface call then: the same checks, the same
- *                  kernel instance, the same bytes; 1: 4:2:2, chroma planes [H, (W + 1) / 2]; 2: 4:4:4, chroma planes [H, W].
- *                  Planes are Y, U, V in that order, as in I420.
+ * A decoder's surface that already lies in device memory (rocDecode, VA-API / AMF interop) is decoded in place:
+ * hand over the mapped pointer with the surface's pitch and chroma offset; nothing is repacked or copied.
+ *
+ * Planar 4:2:2 and 4:4:4 frames, 8 and 10 bit (atm-vfi_amd/yuv.py: Format.subsampling; per-pixel model tests/cpu_yuv_sub.py):
+ *   subsampling    0: 4:2:0, chroma planes [(H + 1) / 2, (W + 1) / 2]; 1: 4:2:2, chroma planes [H, (W + 1) / 2]; 2: 4:4:4, chroma
+ *                  planes [H, W].  Planes are Y, U, V in that order, as in I420.
  * Depth 8 and 10 have the sample types, coefficients, yo, mid, T, range rules and clips of the calls above; no new coefficient exists.
  * Decode 4:2:2: chroma row r = y (no vertical filter); the columns q0, q1 and the weights (wx0, wx1) are those of 4:2:0 for both
  *   sitings; c' = (wx0 c[y][q0] + wx1 c[y][q1] + 2) >> 2.  Decode 4:4:4: c' = c[y][x].  The pixel from (Y, U', V') is unchanged for both
@@ -810,27 +796,47 @@ int atmvfi_yuv_surface_encode(const void* src_u8, int bgr, const float* src, int
  * The window origin must be a multiple of the subsampling step per axis: 4:2:0 even y0 and x0, 4:2:2 even x0 and any y0, 4:4:4 any.
  *   Chroma neighbours clamp at the FRAME's edges, never at the window's.  pitch / chroma_pitch / chroma_offset follow the rules above with
  *   the chroma row width cw b and H chroma rows per plane; the planar V plane follows U at chroma_offset + chroma_pitch * H.
- * Refused on the host before any launch (ATMVFI_EINVAL), in addition to what the surface calls refuse: an unknown subsampling;
+ * Refused on the host before any launch (ATMVFI_EINVAL), in addition to what a 4:2:0 surface refuses: an unknown subsampling;
  *   interleaved chroma (chroma != 0) or msb with subsampling != 0; siting 1 with 4:4:4 (it has no meaning there); a window origin that
  *   breaks the rule above.
- * Any geometry, pitch and pointer alignment is accepted (byte accesses).  The vector path runs under the conditions of the surface calls;
+ * Any geometry, pitch and pointer alignment is accepted (byte accesses).  The vector path runs under the conditions of the surfaces;
  *   for 4:4:4 the chroma rows must be dword-aligned like the luma rows (chroma_pitch and the U / V origins multiples of 4 bytes).  A lane
  *   owns four horizontally adjacent pixels on two rows; 4:2:2 loads one chroma row per luma row (two per lane, no vertical mix), 4:4:4
  *   loads U and V of a group as it loads Y (a dword, or 8 bytes at depth 10); the encode stores a lane's chroma per plane and row as a
  *   2-byte or dword pair (4:2:2) or a dword or 8 bytes (4:4:4).  Both paths give the same bits.  Every output byte is written by exactly
  *   one lane; vector stores only, no atomics, nothing pre-zeroed; no padding byte is ever written.
  * Not covered: 12 bit, 4:1:1 / 4:4:0, interleaved or packed 4:2:2 / 4:4:4 (NV16, P210, YUY2, UYVY, Y210, AYUV, Y410), alpha, bt2020 and
- *   transfer functions, the area mode of atmvfi_yuv420_window. */
-int atmvfi_yuv_sub_decode(const void* yuv, int H, int W, int depth, int matrix, int full_range, int siting, int subsampling, int chroma, int msb,
-                          int64_t pitch, int64_t chroma_pitch, int64_t chroma_offset, int keep_depth, int y0, int x0, int h, int w,
-                          void* dst_u8, int bgr, float* dst, int Hp, int Wp, int pad_top, int pad_left, void* stream);
-int atmvfi_yuv_sub_encode(const void* src_u8, int bgr, const float* src, int Hp, int Wp, int pad_top, int pad_left, int H, int W,
-                          int depth, int matrix, int full_range, int siting, int subsampling, int chroma, int msb, void* yuv, void* stream);
+ *   transfer functions, the area mode (mode 1) on anything but a packed planar LSB 4:2:0 frame.
+ *
+ * THE FRAME DESCRIPTOR (ABI 0.29).  Everything above about one frame -- its size, its samples, its colour and where the samples lie --
+ * is one block without pointers, which a caller builds once per stream and passes by address to atmvfi_yuv_decode, atmvfi_yuv_encode,
+ * atmvfi_yuv_compose and atmvfi_yuv_borders (a launch plan holds it by address, as the other blocks).  Fields are only ever appended
+ * and zero means default / off (as atmvfi_gemm_params): a zeroed block plus H, W, depth and matrix is the tight packed planar
+ * limited-range centre-sited 4:2:0 frame (I420).  The pointers, the window and the canvas of a call stay positional.
+ * atmvfi_yuv_decode: `mode` 0 crop / 1 area 2x (above); keep_depth 0 / 1; without dst the output geometry is the window's.
+ * atmvfi_yuv_encode: the destination is the TIGHT frame of the descriptor: pitch, chroma_pitch and chroma_offset are not read. */
+typedef struct atmvfi_yuv_desc {
+    int32_t H, W;               /* luma size, >= 1, odd sizes allowed */
+    int32_t depth;              /* 8: uint8 samples; 10: little-endian uint16, values 0..1023 */
+    int32_t matrix;             /* 0 bt601, 1 bt709 */
+    int32_t full_range;         /* 0 limited, 1 full (depth 8 only) */
+    int32_t siting;             /* 0 centre ("420jpeg"), 1 left ("420mpeg2"); 0 for 4:4:4 */
+    int32_t subsampling;        /* 0 4:2:0, 1 4:2:2, 2 4:4:4 (1, 2: planar, LSB) */
+    int32_t chroma;             /* 0 planar U then V, 1 interleaved U first (NV12, P010), 2 interleaved V first (NV21) */
+    int32_t msb;                /* depth 10: a stored sample is value << 6 (P010) */
+    int64_t pitch;              /* bytes between luma rows; 0: tight */
+    int64_t chroma_pitch;       /* bytes between chroma rows; 0: tight */
+    int64_t chroma_offset;      /* byte offset of the first chroma row; 0: pitch * H */
+} atmvfi_yuv_desc;
+int atmvfi_yuv_decode(const atmvfi_yuv_desc* desc, const void* yuv, int keep_depth, int mode, int y0, int x0, int h, int w, void* dst_u8,
+                      int bgr, float* dst, int Hp, int Wp, int pad_top, int pad_left, void* stream);
+int atmvfi_yuv_encode(const atmvfi_yuv_desc* desc, const void* src_u8, int bgr, const float* src, int Hp, int Wp, int pad_top, int pad_left,
+                      void* yuv, void* stream);
 
 /* Packed 4:2:2 capture frames (yuv_packed.hip; ABI 0.23; atm-vfi_amd/pixfmt.py: Packed; host twins yuv.unpack_numpy / pack_numpy;
  * per-sample model tests/cpu_yuv_packed.py).  Nothing of the reference.  Two sample-exact moves -- shifts and masks only -- between a
  * packed frame and `planar`, the tight planar 4:2:2 frame of the layout's depth: Y [H,W], U [H,W/2], V [H,W/2] back to back, uint8 or
- * little-endian uint16 with the value in the low bits: what atmvfi_yuv_sub_decode / _encode (subsampling 1) read and write.
+ * little-endian uint16 with the value in the low bits: what atmvfi_yuv_decode / atmvfi_yuv_encode (subsampling 1) read and write.
  *   layout  depth  packed samples  memory order per pixel pair                                      default pitch (bytes)
  *   0 uyvy    8    uint8           U0 Y0 V0 Y1                                                      2 W
  *   1 yuy2    8    uint8           Y0 U0 Y1 V0                                                      2 W

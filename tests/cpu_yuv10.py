@@ -1,4 +1,4 @@
-"""The depth-keeping 10-bit YUV 4:2:0 <-> RGB definition of include/atmvfi.h (atmvfi_yuv420p10_to_f32 / atmvfi_f32_to_yuv420p10) as
+"""The depth-keeping 10-bit YUV 4:2:0 <-> RGB definition of include/atmvfi.h (atmvfi_yuv_decode with keep_depth / atmvfi_yuv_encode at depth 10) as
 explicit per-pixel Python loops over plain ints: the model that ``atm-vfi_amd/yuv.py``'s ``decode_numpy_f32`` / ``encode_numpy`` and
 the HIP kernels of csrc/yuv10.hip are held to, bit for bit.  Written from the definition, not from ``yuv.py``: it carries its own
 coefficient table (the README's) and shares nothing with the package or with ``cpu_yuv`` but ``random_frame``."""

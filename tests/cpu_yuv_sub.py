@@ -1,5 +1,5 @@
 """Planar YUV 4:2:2 and 4:4:4 frames (8 and 10 bit, packed or pitched) as explicit per-sample Python loops over plain ints: the model that
-``atm-vfi_amd/yuv.py``'s twins and ``atmvfi_yuv_sub_decode`` / ``atmvfi_yuv_sub_encode`` are held to, bit for bit.  Written from the
+``atm-vfi_amd/yuv.py``'s twins and ``atmvfi_yuv_decode`` / ``atmvfi_yuv_encode`` are held to, bit for bit.  Written from the
 definition of the README's "4:2:2 and 4:4:4" subsection: it carries its own coefficient tables, addresses every sample by its byte
 offset, and calls nothing of the package -- a layout is the plain dict ``layout(...)`` makes.  ``sub``: "420", "422" or "444"; "420"
 is here too (the formulas of "YUV 4:2:0 and Y4M"), so that the identities between the subsamplings can be stated on one model."""

@@ -1,5 +1,5 @@
 """``yuv.Surface`` (NV12 / NV21 / P010 / pitched planar frames) as explicit per-sample Python loops over plain ints: the model that
-``atm-vfi_amd/yuv.py``'s twins and ``atmvfi_yuv_surface_decode`` / ``atmvfi_yuv_surface_encode`` are held to, bit for bit.  Written
+``atm-vfi_amd/yuv.py``'s twins and ``atmvfi_yuv_decode`` / ``atmvfi_yuv_encode`` are held to, bit for bit.  Written
 from the definition of the README's "Decoder surfaces" subsection and the decode / encode formulas of "YUV 4:2:0 and Y4M": it carries
 its own coefficient tables, addresses every sample by its byte offset, and calls nothing of the package -- a layout is the plain tuple
 ``layout(...)`` makes."""

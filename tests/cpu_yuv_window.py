@@ -1,4 +1,4 @@
-"""Per-pixel model of ``atmvfi_yuv420_window`` (include/atmvfi.h; atm-vfi_amd/csrc/yuv_window.hip), the yardstick of
+"""Per-pixel model of ``atmvfi_yuv_decode`` (``mode``) (include/atmvfi.h; atm-vfi_amd/csrc/yuv_window.hip), the yardstick of
 ``yuv.window_numpy`` and of the kernel: the definition says "no new arithmetic", so the model is the two existing ones put together --
 ``cpu_yuv.decode``'s explicit loops over the WHOLE frame (chroma neighbours clamp at the frame's edges), then ``cpu_frames.window_u8``
 / ``window_f32`` (the window, the 2x2 area rule on the 8-bit pixels, / 255 in fp32, replicate padding).  Shares no code with the

@@ -1,4 +1,4 @@
-"""GPU: the fused decode-window kernel (atm-vfi_amd/csrc/yuv.hip, atmvfi_yuv420_window) bit for bit against the two-call
+"""GPU: the fused decode-window kernel (atm-vfi_amd/csrc/yuv.hip, atmvfi_yuv_decode with mode) bit for bit against the two-call
 composition it replaces (``yuv420_to_rgb`` -> uint8, then ``frame_u8_window``) and against the per-pixel model
 (tests/cpu_yuv_window.py), on both of its paths; and the Xiph evaluation on Y4M clips (evaluate.evaluate_xiph, benchmark/evaluate.py
 --dataset xiph --source y4m) against the same evaluation on a PNG tree holding ``yuv.decode_numpy`` of the same frames."""

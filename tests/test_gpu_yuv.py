@@ -1,4 +1,4 @@
-"""GPU: planar YUV 4:2:0 on the device (csrc/yuv.hip atmvfi_yuv420_to_rgb, csrc/yuv_encode.hip atmvfi_rgb_to_yuv420, the ``pixfmt=`` argument of the video
+"""GPU: planar YUV 4:2:0 on the device (csrc/yuv.hip atmvfi_yuv_decode, csrc/yuv_encode.hip atmvfi_yuv_encode, the ``pixfmt=`` argument of the video
 loops, ``yuv.interpolate_y4m``): both kernels against the per-pixel model of tests/cpu_yuv.py bit for bit -- every matrix, range and
 siting, 10-bit, BGR, odd sizes, both the vector and the general path -- and the loops against the RGB loops on the decoded frames."""
 import importlib
@@ -244,7 +244,7 @@ def test_wrapper_refusals(ops, dev):
         ops.yuv420_to_rgb(buf[:-1], fmt, dst_u8=d8)
     with pytest.raises(ValueError):
         ops.yuv420_to_rgb(buf, fmt, dst_u8=d8[:8])
-    with pytest.raises(RuntimeError, match="smaller than the frame"):
+    with pytest.raises(RuntimeError, match="smaller than the window"):
         ops.yuv420_to_rgb(buf, fmt, dst=torch.empty(3, 16, 16, device=dev), pad_left=4)
     with pytest.raises(ValueError):
         ops.rgb_to_yuv420(buf, fmt)

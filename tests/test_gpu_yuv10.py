@@ -1,4 +1,4 @@
-"""GPU: 10-bit depth kept end to end on the device (csrc/yuv.hip atmvfi_yuv420p10_to_f32, csrc/yuv_encode.hip atmvfi_f32_to_yuv420p10, ``keep_depth=`` of
+"""GPU: 10-bit depth kept end to end on the device (csrc/yuv.hip atmvfi_yuv_decode with keep_depth, csrc/yuv_encode.hip atmvfi_yuv_encode at depth 10, ``keep_depth=`` of
 the video loops and ``yuv.interpolate_y4m``): both kernels against the per-pixel model of tests/cpu_yuv10.py bit for bit -- both
 matrices and sitings, odd sizes, windows, the vector and the general path -- and the loops against ``encode_numpy`` of the fp32
 prediction that plain ``net.forward`` gives on inputs decoded by ``HipOps.yuv420p10_to_f32``."""

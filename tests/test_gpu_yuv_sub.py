@@ -1,4 +1,4 @@
-"""GPU: planar 4:2:2 / 4:4:4 frames on the device (csrc/yuv.hip atmvfi_yuv_sub_decode, csrc/yuv_encode.hip atmvfi_yuv_sub_encode,
+"""GPU: planar 4:2:2 / 4:4:4 frames on the device (csrc/yuv.hip atmvfi_yuv_decode, csrc/yuv_encode.hip atmvfi_yuv_encode,
 ``pixfmt=`` of the video loops): both entry points against the per-sample loop model of tests/cpu_yuv_sub.py (small shapes) and the
 numpy twins (large ones; the CPU suite holds them to the model), bit for bit -- 8 bit, 10 -> 8 bit, 10 bit kept, both sitings, the
 vector and the general path reached every way, poisoned destinations, guards and padding -- then equality with the surface calls at

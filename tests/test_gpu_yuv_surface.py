@@ -1,4 +1,4 @@
-"""GPU: decoder surfaces on the device (csrc/yuv.hip atmvfi_yuv_surface_decode, csrc/yuv_encode.hip atmvfi_yuv_surface_encode,
+"""GPU: decoder surfaces on the device (csrc/yuv.hip atmvfi_yuv_decode, csrc/yuv_encode.hip atmvfi_yuv_encode,
 ``pixfmt=yuv.Surface(...)`` of the video loops): both entry points against the per-sample loop model of tests/cpu_yuv_surface.py
 (small shapes) and the numpy twins (large ones; the CPU suite holds them to the model), bit for bit -- planar / uv / vu, 8 bit,
 10 -> 8 bit, 10 bit kept, msb, both sitings, the vector and the general path reached every way, poisoned destinations and padding --

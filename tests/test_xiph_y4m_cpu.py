@@ -1,5 +1,5 @@
 """CPU: the Xiph evaluation on Y4M clips -- ``yuv.window_numpy`` against the per-pixel model (tests/cpu_yuv_window.py), the ABI's
-host-side checks of ``atmvfi_yuv420_window``, finding a clip and choosing its source (``evaluate.xiph_y4m_file`` / ``xiph_sources``),
+host-side checks of ``atmvfi_yuv_decode`` (``mode``), finding a clip and choosing its source (``evaluate.xiph_y4m_file`` / ``xiph_sources``),
 ``Y4MReader.skip`` and the reader thread's errors on tiny files written with ``Y4MWriter``."""
 import ctypes
 import importlib
@@ -66,18 +66,19 @@ def test_yuv420_window_abi_is_declared_exported_and_checks_on_the_host():
     hdr = open(os.path.join(CS.ROOT, "include", "atmvfi.h")).read()
     lib = hip_ops.load_library()
     lib.atmvfi_last_error.restype = ctypes.c_char_p
-    name = "atmvfi_yuv420_window"
+    name = "atmvfi_yuv_decode"                      # the window with its area mode is `mode` of the one decode entry point
     assert re.search(r"\bint\s+" + name + r"\s*\(", hdr) and name in hip_ops.SIGNATURES and hasattr(lib, name)
     assert lib.atmvfi_plan_fn_id(name.encode()) >= 0
-    assert (lib.atmvfi_version() >> 8) & 255 >= 17
+    assert (lib.atmvfi_version() >> 8) & 255 >= 29
     assert " yuv.hip" in open(os.path.join(CS.ROOT, "atm-vfi_amd", "csrc", "Makefile")).read()
     assert callable(hip_ops.HipOps.yuv420_window) and callable(yuv.window_numpy)
     P = 0x10000       # never dereferenced: every call below fails its host-side checks before a launch
     err = lib.atmvfi_last_error
 
     def win(yuv_=P, H=64, W=96, depth=8, matrix=0, full=0, siting=0, mode=0, y0=0, x0=0, h=32, w=48, dst=P, Hp=32, Wp=48, pt=0, pl=0, d8=P):
-        rc = lib.atmvfi_yuv420_window(yuv_, H, W, depth, matrix, full, siting, mode, y0, x0, h, w, dst, Hp, Wp, pt, pl, d8, None)
-        assert rc == -1 and err().startswith(b"yuv420_window: ")        # the shared checks, under the entry point's own name
+        d = hip_ops.YuvDesc(H=H, W=W, depth=depth, matrix=matrix, full_range=full, siting=siting)
+        rc = lib.atmvfi_yuv_decode(ctypes.byref(d), yuv_, 0, mode, y0, x0, h, w, d8, 0, dst, Hp, Wp, pt, pl, None)
+        assert rc == -1 and err().startswith(b"yuv_decode: ")           # the shared checks, under the entry point's own name
         return rc
     assert win(yuv_=None) == -1 and b"null source" in err()
     assert win(dst=None, d8=None) == -1 and b"both outputs are null" in err()

@@ -1,4 +1,4 @@
-"""CPU: 10-bit depth kept end to end (``keep_depth``; include/atmvfi.h atmvfi_yuv420p10_to_f32 / atmvfi_f32_to_yuv420p10, csrc/yuv.hip, yuv_encode.hip):
+"""CPU: 10-bit depth kept end to end (``keep_depth``; include/atmvfi.h atmvfi_yuv_decode with keep_depth / atmvfi_yuv_encode at depth 10, csrc/yuv.hip, yuv_encode.hip):
 the coefficient table in all its places, the numpy twins against the per-pixel model of tests/cpu_yuv10.py, accumulator bounds, grey
 neutrality and round trips, the q / 1023 shortcut of the kernel, ties and clamps of the encode, the ABI's host-side checks, and the
 loops / ``interpolate_y4m`` with ``keep_depth=True`` through the generic (no-GPU) path."""
@@ -254,10 +254,10 @@ def test_yuv10_abi_is_declared_exported_and_checks_on_the_host():
     hdr = open(os.path.join(CS.ROOT, "include", "atmvfi.h")).read()
     lib = hip_ops.load_library()
     lib.atmvfi_last_error.restype = ctypes.c_char_p
-    for name in ("atmvfi_yuv420p10_to_f32", "atmvfi_f32_to_yuv420p10"):
+    for name in ("atmvfi_yuv_decode", "atmvfi_yuv_encode"):
         assert re.search(r"\bint\s+" + name + r"\s*\(", hdr) and name in hip_ops.SIGNATURES and hasattr(lib, name)
         assert lib.atmvfi_plan_fn_id(name.encode()) >= 0
-    assert (lib.atmvfi_version() >> 8) & 255 >= 15
+    assert (lib.atmvfi_version() >> 8) & 255 >= 29
     mk = open(os.path.join(CS.ROOT, "atm-vfi_amd", "csrc", "Makefile")).read()
     assert " yuv.hip" in mk and " yuv_encode.hip" in mk
     assert callable(hip_ops.HipOps.yuv420p10_to_f32) and callable(hip_ops.HipOps.f32_to_yuv420p10)
@@ -265,16 +265,18 @@ def test_yuv10_abi_is_declared_exported_and_checks_on_the_host():
     err = lib.atmvfi_last_error
 
     def dec(yuv_=P, H=64, W=96, matrix=0, siting=0, y0=0, x0=0, h=64, w=96, dst=P, Hp=64, Wp=96, pt=0, pl=0):
-        rc = lib.atmvfi_yuv420p10_to_f32(yuv_, H, W, matrix, siting, y0, x0, h, w, dst, Hp, Wp, pt, pl, None)
-        assert rc == -1 and err().startswith(b"yuv420p10_to_f32: ")     # the shared checks, under the entry point's own name
+        d = hip_ops.YuvDesc(H=H, W=W, depth=10, matrix=matrix, siting=siting)
+        rc = lib.atmvfi_yuv_decode(ctypes.byref(d), yuv_, 1, 0, y0, x0, h, w, None, 0, dst, Hp, Wp, pt, pl, None)       # keep_depth
+        assert rc == -1 and err().startswith(b"yuv_decode: ")           # the shared checks, under the entry point's own name
         return rc
 
     def enc(src=P, Hp=64, Wp=96, pt=0, pl=0, H=64, W=96, matrix=0, siting=0, yuv_=P):
-        rc = lib.atmvfi_f32_to_yuv420p10(src, Hp, Wp, pt, pl, H, W, matrix, siting, yuv_, None)
-        assert rc == -1 and err().startswith(b"f32_to_yuv420p10: ")
+        d = hip_ops.YuvDesc(H=H, W=W, depth=10, matrix=matrix, siting=siting)
+        rc = lib.atmvfi_yuv_encode(ctypes.byref(d), None, 0, src, Hp, Wp, pt, pl, yuv_, None)
+        assert rc == -1 and err().startswith(b"yuv_encode: ")
         return rc
     assert dec(yuv_=None) == -1 and b"null source" in err()
-    assert dec(dst=None) == -1 and b"null destination" in err()
+    assert dec(dst=None) == -1 and b"both outputs are null" in err()           # (the general message: the call has two outputs)
     assert dec(H=0) == -1 and b"at least 1" in err()
     assert dec(W=0) == -1 and b"at least 1" in err()
     assert dec(h=0) == -1 and b"at least 1" in err()
@@ -293,7 +295,7 @@ def test_yuv10_abi_is_declared_exported_and_checks_on_the_host():
     assert dec(H=100000, W=100000, h=100000, w=100000, Hp=100000, Wp=100000) == -1 and b"too large" in err()
     assert dec(x0=-2, w=8) == -1 and b"outside the" in err()                                    # (asserted for its siblings before)
     assert dec(y0=34, h=32) == -1 and b"outside the" in err()
-    assert enc(src=None) == -1 and b"null source" in err()
+    assert enc(src=None) == -1 and b"exactly one of src_u8 and src" in err()   # (the general message: the call has two sources)
     assert enc(yuv_=None) == -1 and b"null destination" in err()
     assert enc(H=0) == -1 and b"at least 1" in err()
     assert enc(W=-1) == -1 and b"at least 1" in err()

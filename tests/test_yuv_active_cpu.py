@@ -301,7 +301,7 @@ def test_yuv_active_abi_is_declared_exported_and_checks_on_the_host():
     assert re.search(r"\bint\s+atmvfi_yuv_compose\s*\(", hdr)
     for name in ("atmvfi_yuv_borders", "atmvfi_yuv_borders_workspace_ints", "atmvfi_yuv_compose"):
         assert name in hip_ops.SIGNATURES and hasattr(lib, name)
-    assert (lib.atmvfi_version() >> 8) & 255 >= 22
+    assert (lib.atmvfi_version() >> 8) & 255 >= 29
     for name in ("yuv_borders", "yuv_borders_workspace", "yuv_compose"):
         assert callable(getattr(hip_ops.HipOps, name))
     P = 0x10000       # never dereferenced: every call below fails its host-side checks before a launch
@@ -309,7 +309,7 @@ def test_yuv_active_abi_is_declared_exported_and_checks_on_the_host():
 
     def borders(src=P, H=64, W=96, depth=8, msb=0, pitch=0, out=P, ws=P, n=None):
         n = max(ws_ints(H, W), 0) if n is None else n
-        return lib.atmvfi_yuv_borders(src, H, W, depth, msb, pitch, out, ws, n, None)
+        return lib.atmvfi_yuv_borders(ctypes.byref(hip_ops.YuvDesc(H=H, W=W, depth=depth, msb=msb, pitch=pitch)), src, out, ws, n, None)
     assert borders(src=None) == -1 and b"null pointer" in err()
     assert borders(out=None) == -1 and b"null pointer" in err()
     assert borders(ws=None) == -1 and b"null pointer" in err()
@@ -328,8 +328,9 @@ def test_yuv_active_abi_is_declared_exported_and_checks_on_the_host():
 
     def compose(dst=P, border=4 * P, H=64, W=96, depth=8, matrix=0, fr=0, siting=0, sub=0, chroma=0, msb=0, bp=0, bcp=0, bco=0, y0=8, x0=4,
                 h=32, w=40, src=8 * P, Hp=64, Wp=64, pt=0, pl=0, u8=None):
-        return lib.atmvfi_yuv_compose(dst, border, H, W, depth, matrix, fr, siting, sub, chroma, msb, bp, bcp, bco, y0, x0, h, w, src, Hp, Wp, pt, pl,
-                                      u8, None)
+        d = hip_ops.YuvDesc(H=H, W=W, depth=depth, matrix=matrix, full_range=fr, siting=siting, subsampling=sub, chroma=chroma, msb=msb, pitch=bp,
+                            chroma_pitch=bcp, chroma_offset=bco)
+        return lib.atmvfi_yuv_compose(ctypes.byref(d), dst, border, y0, x0, h, w, src, Hp, Wp, pt, pl, u8, None)
     assert compose(dst=None) == -1 and b"null pointer" in err()
     assert compose(border=None) == -1 and b"null pointer" in err()
     assert compose(u8=9 * P) == -1 and b"exactly one" in err()

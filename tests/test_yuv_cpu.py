@@ -1,4 +1,4 @@
-"""CPU: planar YUV 4:2:0 (atm-vfi_amd/yuv.py; include/atmvfi.h atmvfi_yuv420_to_rgb / atmvfi_rgb_to_yuv420): the coefficient table,
+"""CPU: planar YUV 4:2:0 (atm-vfi_amd/yuv.py; include/atmvfi.h atmvfi_yuv_decode / atmvfi_yuv_encode): the coefficient table,
 the vectorised numpy twins against the per-pixel model of tests/cpu_yuv.py, closed forms and round trips, float64 and PIL yardsticks,
 Y4M files, the loops with ``pixfmt=`` through the generic (no-GPU) path, and the ABI's host-side checks."""
 import ctypes
@@ -418,10 +418,10 @@ def test_yuv_abi_is_declared_exported_and_checks_on_the_host():
     hdr = open(os.path.join(CS.ROOT, "include", "atmvfi.h")).read()
     lib = hip_ops.load_library()
     lib.atmvfi_last_error.restype = ctypes.c_char_p
-    for name in ("atmvfi_yuv420_to_rgb", "atmvfi_rgb_to_yuv420"):
+    for name in ("atmvfi_yuv_decode", "atmvfi_yuv_encode"):
         assert re.search(r"\bint\s+" + name + r"\s*\(", hdr) and name in hip_ops.SIGNATURES and hasattr(lib, name)
         assert lib.atmvfi_plan_fn_id(name.encode()) >= 0
-    assert (lib.atmvfi_version() >> 8) & 255 >= 14
+    assert (lib.atmvfi_version() >> 8) & 255 >= 29
     mk = open(os.path.join(CS.ROOT, "atm-vfi_amd", "csrc", "Makefile")).read()
     assert " yuv.hip" in mk and " yuv_encode.hip" in mk
     assert callable(hip_ops.HipOps.yuv420_to_rgb) and callable(hip_ops.HipOps.rgb_to_yuv420)
@@ -429,13 +429,15 @@ def test_yuv_abi_is_declared_exported_and_checks_on_the_host():
     err = lib.atmvfi_last_error
 
     def dec(yuv_=P, H=64, W=96, depth=8, matrix=0, full=0, siting=0, d8=P, bgr=0, dst=P, Hp=64, Wp=96, pt=0, pl=0):
-        rc = lib.atmvfi_yuv420_to_rgb(yuv_, H, W, depth, matrix, full, siting, d8, bgr, dst, Hp, Wp, pt, pl, None)
-        assert rc == -1 and err().startswith(b"yuv420_to_rgb: ")        # the shared checks, under the entry point's own name
+        d = hip_ops.YuvDesc(H=H, W=W, depth=depth, matrix=matrix, full_range=full, siting=siting)     # the whole frame of a packed planar format
+        rc = lib.atmvfi_yuv_decode(ctypes.byref(d), yuv_, 0, 0, 0, 0, H, W, d8, bgr, dst, Hp, Wp, pt, pl, None)
+        assert rc == -1 and err().startswith(b"yuv_decode: ")           # the shared checks, under the entry point's own name
         return rc
 
     def enc(s8=P, bgr=0, src=None, Hp=64, Wp=96, pt=0, pl=0, H=64, W=96, matrix=0, full=0, siting=0, yuv_=P):
-        rc = lib.atmvfi_rgb_to_yuv420(s8, bgr, src, Hp, Wp, pt, pl, H, W, matrix, full, siting, yuv_, None)
-        assert rc == -1 and err().startswith(b"rgb_to_yuv420: ")
+        d = hip_ops.YuvDesc(H=H, W=W, depth=8, matrix=matrix, full_range=full, siting=siting)
+        rc = lib.atmvfi_yuv_encode(ctypes.byref(d), s8, bgr, src, Hp, Wp, pt, pl, yuv_, None)
+        assert rc == -1 and err().startswith(b"yuv_encode: ")
         return rc
     assert dec(yuv_=None) == -1 and b"null source" in err()
     assert dec(d8=None, dst=None) == -1 and b"both outputs are null" in err()
@@ -445,9 +447,9 @@ def test_yuv_abi_is_declared_exported_and_checks_on_the_host():
     assert dec(depth=10, full=1) == -1 and b"10-bit full range" in err()
     assert dec(matrix=2) == -1 and b"unknown matrix" in err()
     assert dec(siting=2) == -1 and b"unknown siting" in err()
-    assert dec(Hp=63) == -1 and b"smaller than the frame" in err()
-    assert dec(pl=1) == -1 and b"smaller than the frame" in err()
-    assert dec(pt=-1) == -1 and b"smaller than the frame" in err()
+    assert dec(Hp=63) == -1 and b"smaller than the window" in err()     # (one decode entry point: the whole frame is a window too)
+    assert dec(pl=1) == -1 and b"smaller than the window" in err()
+    assert dec(pt=-1) == -1 and b"smaller than the window" in err()
     assert dec(dst=P + 2) == -1 and b"4-byte aligned" in err()
     assert dec(H=100000, W=100000, Hp=100000, Wp=100000) == -1 and b"too large" in err()        # 1.25e9 work items
     assert dec(full=2) == -1 and b"full_range" in err()                                         # (asserted for its siblings before)

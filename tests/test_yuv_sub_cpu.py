@@ -1,6 +1,7 @@
 """Planar 4:2:2 / 4:4:4 frames on the host: the numpy twins against the per-sample loop model (tests/cpu_yuv_sub.py), the identities
 that tie the three subsamplings together, the carried-over round-trip bounds, the refusals, Y4M tags, the loops through the numpy
 path and the two new ABI calls' host-side checks.  No GPU."""
+import ctypes
 import importlib
 import io
 import itertools
@@ -513,30 +514,32 @@ def test_raw_streams_take_the_new_surfaces():
 def test_sub_abi_is_declared_exported_and_checks_on_the_host():
     hdr = open(os.path.join(CS.ROOT, "include", "atmvfi.h")).read()
     lib = hip_ops.load_library()
-    for name in ("atmvfi_yuv_sub_decode", "atmvfi_yuv_sub_encode"):
+    for name in ("atmvfi_yuv_decode", "atmvfi_yuv_encode"):
         assert re.search(r"\bint\s+" + name + r"\s*\(", hdr) and name in hip_ops.SIGNATURES and hasattr(lib, name)
         assert lib.atmvfi_plan_fn_id(name.encode()) >= 0
-    assert (lib.atmvfi_version() >> 8) & 255 >= 20
+    assert (lib.atmvfi_version() >> 8) & 255 >= 29
     assert callable(hip_ops.HipOps.yuv_sub_decode) and callable(hip_ops.HipOps.yuv_sub_encode)
-    # the sub calls take the surface calls' arguments plus one int after siting
-    assert len(hip_ops.SIGNATURES["atmvfi_yuv_sub_decode"][1]) == len(hip_ops.SIGNATURES["atmvfi_yuv_surface_decode"][1]) + 1
-    assert len(hip_ops.SIGNATURES["atmvfi_yuv_sub_encode"][1]) == len(hip_ops.SIGNATURES["atmvfi_yuv_surface_encode"][1]) + 1
+    # the subsampling is one int of the frame descriptor, after siting
+    names = [n for n, _ in hip_ops.YuvDesc._fields_]
+    assert names.index("subsampling") == names.index("siting") + 1 and re.search(r"int32_t siting;.*\n\s*int32_t subsampling;", hdr)
     P = 0x10000       # never dereferenced: every call below fails its host-side checks before a launch
     err = lib.atmvfi_last_error
 
     def dec(buf=P, H=64, W=96, depth=8, matrix=0, full=0, siting=0, sub=1, chroma=0, msb=0, pitch=0, cpitch=0, coff=0, keep=0, y0=0, x0=0, h=64,
             w=96, dst_u8=None, bgr=0, dst=P, Hp=64, Wp=96, pt=0, pl=0):
-        rc = lib.atmvfi_yuv_sub_decode(buf, H, W, depth, matrix, full, siting, sub, chroma, msb, pitch, cpitch, coff, keep, y0, x0, h, w, dst_u8,
-                                       bgr, dst, Hp, Wp, pt, pl, None)
-        assert rc == -1 and err().startswith(b"yuv_sub_decode: " if sub else b"yuv_surface_decode: ")      # sub 0 IS the surface call
+        d = hip_ops.YuvDesc(H=H, W=W, depth=depth, matrix=matrix, full_range=full, siting=siting, subsampling=sub, chroma=chroma, msb=msb,
+                            pitch=pitch, chroma_pitch=cpitch, chroma_offset=coff)
+        rc = lib.atmvfi_yuv_decode(ctypes.byref(d), buf, keep, 0, y0, x0, h, w, dst_u8, bgr, dst, Hp, Wp, pt, pl, None)
+        assert rc == -1 and err().startswith(b"yuv_decode: ")      # one entry point for every subsampling
         return rc
 
     def enc(src_u8=None, bgr=0, src=P, Hp=64, Wp=96, pt=0, pl=0, H=64, W=96, depth=8, matrix=0, full=0, siting=0, sub=1, chroma=0, msb=0, buf=P):
-        rc = lib.atmvfi_yuv_sub_encode(src_u8, bgr, src, Hp, Wp, pt, pl, H, W, depth, matrix, full, siting, sub, chroma, msb, buf, None)
-        assert rc == -1 and err().startswith(b"yuv_sub_encode: " if sub else b"yuv_surface_encode: ")
+        d = hip_ops.YuvDesc(H=H, W=W, depth=depth, matrix=matrix, full_range=full, siting=siting, subsampling=sub, chroma=chroma, msb=msb)
+        rc = lib.atmvfi_yuv_encode(ctypes.byref(d), src_u8, bgr, src, Hp, Wp, pt, pl, buf, None)
+        assert rc == -1 and err().startswith(b"yuv_encode: ")
         return rc
     for sub in (1, 2):
-        assert dec(sub=sub, buf=None) == -1 and b"yuv_sub_decode: null source" in err()
+        assert dec(sub=sub, buf=None) == -1 and b"yuv_decode: null source" in err()
         assert dec(sub=sub, dst=None) == -1 and b"both outputs are null" in err()
         assert dec(sub=sub, H=0) == -1 and b"at least 1" in err()
         assert dec(sub=sub, depth=12) == -1 and b"depth must be 8 or 10" in err()
@@ -555,7 +558,7 @@ def test_sub_abi_is_declared_exported_and_checks_on_the_host():
         assert dec(sub=sub, Hp=63) == -1 and b"smaller than the window" in err()
         assert dec(sub=sub, dst=P + 2) == -1 and b"4-byte aligned" in err()
         assert dec(sub=sub, H=100000, W=100000, h=100000, w=100000, Hp=100000, Wp=100000) == -1 and b"too large" in err()
-        assert enc(sub=sub, buf=None) == -1 and b"yuv_sub_encode: null destination" in err()
+        assert enc(sub=sub, buf=None) == -1 and b"yuv_encode: null destination" in err()
         assert enc(sub=sub, src=None) == -1 and b"exactly one" in err()
         assert enc(sub=sub, depth=10, src=None, src_u8=P) == -1 and b"fp32 canvas" in err()
         assert enc(sub=sub, Wp=95) == -1 and b"smaller than the frame" in err()
@@ -570,9 +573,9 @@ def test_sub_abi_is_declared_exported_and_checks_on_the_host():
     assert dec(sub=2, cpitch=95) == -1 and b"at least a chroma row" in err()
     # the window origin: a multiple of the subsampling step per axis
     assert dec(sub=1, x0=3, w=8) == -1 and b"even x0 for 4:2:2" in err()
-    assert dec(sub=0, chroma=0, y0=1, h=8) == -1 and b"yuv_surface_decode" in err() and b"must be even" in err()      # sub 0 IS the surface call
+    assert dec(sub=0, chroma=0, y0=1, h=8) == -1 and b"yuv_decode" in err() and b"must be even" in err()      # sub 0: the 4:2:0 rule
     assert dec(sub=0, chroma=3) == -1 and b"unknown chroma layout" in err()
-    assert enc(sub=0, chroma=0, msb=1) == -1 and b"yuv_surface_encode" in err() and b"msb needs depth 10" in err()
+    assert enc(sub=0, chroma=0, msb=1) == -1 and b"yuv_encode" in err() and b"msb needs depth 10" in err()
     # an odd y0 at 4:2:2 and any origin at 4:4:4 pass the origin rule (and fail the next check: the canvas)
     assert dec(sub=1, y0=1, h=8, Hp=4) == -1 and b"smaller than the window" in err()
     assert dec(sub=2, y0=1, x0=3, h=8, w=8, Hp=4) == -1 and b"smaller than the window" in err()

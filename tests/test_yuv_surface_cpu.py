@@ -320,24 +320,26 @@ def test_interpolate_raw_writes_what_the_loop_yields():
 def test_surface_abi_is_declared_exported_and_checks_on_the_host():
     hdr = open(os.path.join(CS.ROOT, "include", "atmvfi.h")).read()
     lib = hip_ops.load_library()
-    for name in ("atmvfi_yuv_surface_decode", "atmvfi_yuv_surface_encode"):
+    for name in ("atmvfi_yuv_decode", "atmvfi_yuv_encode"):
         assert re.search(r"\bint\s+" + name + r"\s*\(", hdr) and name in hip_ops.SIGNATURES and hasattr(lib, name)
         assert lib.atmvfi_plan_fn_id(name.encode()) >= 0
-    assert (lib.atmvfi_version() >> 8) & 255 >= 19
+    assert (lib.atmvfi_version() >> 8) & 255 >= 29
     assert callable(hip_ops.HipOps.yuv_surface_decode) and callable(hip_ops.HipOps.yuv_surface_encode)
     P = 0x10000       # never dereferenced: every call below fails its host-side checks before a launch
     err = lib.atmvfi_last_error
 
     def dec(buf=P, H=64, W=96, depth=8, matrix=0, full=0, siting=0, chroma=1, msb=0, pitch=0, cpitch=0, coff=0, keep=0, y0=0, x0=0, h=64, w=96,
             dst_u8=None, bgr=0, dst=P, Hp=64, Wp=96, pt=0, pl=0):
-        rc = lib.atmvfi_yuv_surface_decode(buf, H, W, depth, matrix, full, siting, chroma, msb, pitch, cpitch, coff, keep, y0, x0, h, w, dst_u8,
-                                           bgr, dst, Hp, Wp, pt, pl, None)
-        assert rc == -1 and err().startswith(b"yuv_surface_decode: ")
+        d = hip_ops.YuvDesc(H=H, W=W, depth=depth, matrix=matrix, full_range=full, siting=siting, chroma=chroma, msb=msb, pitch=pitch,
+                            chroma_pitch=cpitch, chroma_offset=coff)
+        rc = lib.atmvfi_yuv_decode(ctypes.byref(d), buf, keep, 0, y0, x0, h, w, dst_u8, bgr, dst, Hp, Wp, pt, pl, None)
+        assert rc == -1 and err().startswith(b"yuv_decode: ")
         return rc
 
     def enc(src_u8=None, bgr=0, src=P, Hp=64, Wp=96, pt=0, pl=0, H=64, W=96, depth=8, matrix=0, full=0, siting=0, chroma=1, msb=0, buf=P):
-        rc = lib.atmvfi_yuv_surface_encode(src_u8, bgr, src, Hp, Wp, pt, pl, H, W, depth, matrix, full, siting, chroma, msb, buf, None)
-        assert rc == -1 and err().startswith(b"yuv_surface_encode: ")
+        d = hip_ops.YuvDesc(H=H, W=W, depth=depth, matrix=matrix, full_range=full, siting=siting, chroma=chroma, msb=msb)
+        rc = lib.atmvfi_yuv_encode(ctypes.byref(d), src_u8, bgr, src, Hp, Wp, pt, pl, buf, None)
+        assert rc == -1 and err().startswith(b"yuv_encode: ")
         return rc
     assert dec(buf=None) == -1 and b"null source" in err()
     assert dec(dst=None) == -1 and b"both outputs are null" in err()
@@ -385,3 +387,38 @@ def test_surface_abi_is_declared_exported_and_checks_on_the_host():
     assert enc(src_u8=P) == -1 and b"both" in err()
     assert enc(siting=3) == -1 and b"unknown siting" in err()
     assert enc(pl=-4) == -1 and b"smaller than the frame" in err()
+
+
+# ------------------------------------------------------------------------------------------------ the frame descriptor
+_DESC_GROUPS = {
+    "size": [(dict(H=0), b"H and W must be at least 1 (got 0 x 16)"), (dict(W=0), b"H and W must be at least 1 (got 8 x 0)"),
+             (dict(H=3, W=5, y0=2), b"at (2, 0) of a 3 x 5 frame")],
+    "colour": [(dict(depth=12), b"depth must be 8 or 10 (got 12)"), (dict(matrix=7), b"unknown matrix 7"),
+               (dict(full_range=5), b"full_range must be 0 or 1 (got 5)"), (dict(siting=3), b"unknown siting 3")],
+    "layout": [(dict(subsampling=9), b"unknown subsampling 9"), (dict(chroma=4), b"unknown chroma layout 4"),
+               (dict(depth=10, msb=6), b"msb must be 0 or 1 (got 6)"), (dict(subsampling=2, siting=1), b"siting 1 has no meaning for 4:4:4")],
+    "strides": [(dict(pitch=15), b"pitch 15 must be"), (dict(chroma_pitch=7), b"chroma_pitch 7 must be"),
+                (dict(chroma_offset=127), b"chroma_offset 127 must be"), (dict(pitch=32, chroma_offset=255), b"at least pitch * H = 256")],
+}
+
+
+@pytest.mark.parametrize("group", list(_DESC_GROUPS))
+def test_yuv_desc_layout_matches_the_header(group):
+    """hip_ops.YuvDesc against the C struct: one wrong field at a time on an otherwise valid 8 x 16 block (3 x 5 where the frame's size is
+    the point), each refused before any launch with the message of exactly that field and its value -- a ctypes field that sits
+    elsewhere than its C counterpart makes the library read another value there and report something else (or nothing)."""
+    lib = hip_ops.load_library()
+    lib.atmvfi_last_error.restype = ctypes.c_char_p
+    P = 0x10000       # never dereferenced
+    assert ctypes.sizeof(hip_ops.YuvDesc) == 64 and hip_ops.YuvDesc.pitch.offset == 40          # nine int32, padding, three int64
+    for wrong, text in _DESC_GROUPS[group]:
+        kw = {**dict(H=8, W=16, depth=8, matrix=0), **wrong}
+        y0 = kw.pop("y0", 0)
+        d = hip_ops.YuvDesc(**kw)
+        assert lib.atmvfi_yuv_decode(ctypes.byref(d), P, 0, 0, y0, 0, 2, 4, None, 0, P, 2, 4, 0, 0, None) == -1
+        assert lib.atmvfi_last_error().startswith(b"yuv_decode: ") and text in lib.atmvfi_last_error(), (wrong, lib.atmvfi_last_error())
+        if "pitch" in "".join(wrong) or "chroma_offset" in wrong or "y0" in wrong or "H" in wrong and "W" in wrong:
+            continue                                        # (an encode reads no stride and has no window)
+        assert lib.atmvfi_yuv_encode(ctypes.byref(d), None, 0, P, kw["H"], kw["W"], 0, 0, P, None) == -1
+        assert lib.atmvfi_last_error().startswith(b"yuv_encode: ") and text in lib.atmvfi_last_error(), (wrong, lib.atmvfi_last_error())
+    assert lib.atmvfi_yuv_decode(None, P, 0, 0, 0, 0, 2, 4, None, 0, P, 2, 4, 0, 0, None) == -1 and b"null descriptor" in lib.atmvfi_last_error()

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Time the YUV 4:2:0 kernels (atm-vfi_amd/csrc/yuv.hip: atmvfi_yuv420_to_rgb; yuv_encode.hip: atmvfi_rgb_to_yuv420) on the method of
+"""Time the YUV 4:2:0 kernels (atm-vfi_amd/csrc/yuv.hip: atmvfi_yuv_decode; yuv_encode.hip: atmvfi_yuv_encode) on the method of
 tools/bench_frames.py: device events around ``--iters`` back-to-back calls after 24 warm-up calls, the calls rotating over
 ``--buffers`` distinct sources and destinations, every configuration timed ``--repeats`` times in rotation (median, min - max).  Bytes
 are the algorithm's -- inputs read once, outputs written once -- as a share of 6.3 TB/s.  Sizes 480 x 832, 1080 x 1920, 2160 x 4096,

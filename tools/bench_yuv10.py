@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Time the depth-keeping 10-bit YUV kernels (atm-vfi_amd/csrc/yuv.hip: atmvfi_yuv420p10_to_f32; yuv_encode.hip: atmvfi_f32_to_yuv420p10) beside
+"""Time the depth-keeping 10-bit YUV kernels (atm-vfi_amd/csrc/yuv.hip: atmvfi_yuv_decode with keep_depth; yuv_encode.hip: atmvfi_yuv_encode at depth 10) beside
 the calls they stand next to, on the protocol of tools/bench_yuv.py: device events around ``--iters`` back-to-back calls after 24
 warm-up calls, the calls rotating over ``--buffers`` distinct sources and destinations, every configuration timed ``--repeats`` times
 in rotation in one process (median, min - max).  Bytes are the algorithm's -- inputs read once, outputs written once -- as a share of

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Time the 4:2:2 / 4:4:4 calls (atm-vfi_amd/csrc/yuv.hip: atmvfi_yuv_sub_decode; yuv_encode.hip: atmvfi_yuv_sub_encode) beside the planar
+"""Time the 4:2:2 / 4:4:4 calls (atm-vfi_amd/csrc/yuv.hip: atmvfi_yuv_decode; yuv_encode.hip: atmvfi_yuv_encode) beside the planar
 4:2:0 call of the same direction and depth, on the protocol of tools/bench_yuv.py: device events around ``--iters`` back-to-back calls
 after 24 warm-up calls, the calls rotating over ``--buffers`` distinct sources and destinations (beyond the Infinity Cache), every
 configuration timed ``--repeats`` times in rotation in one process (median, min - max).  Decode -> fp32 canvas and encode from the

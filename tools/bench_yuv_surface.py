@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Time the surface calls (atm-vfi_amd/csrc/yuv.hip: atmvfi_yuv_surface_decode; yuv_encode.hip: atmvfi_yuv_surface_encode) beside their
+"""Time the surface calls (atm-vfi_amd/csrc/yuv.hip: atmvfi_yuv_decode; yuv_encode.hip: atmvfi_yuv_encode) beside their
 planar neighbours, on the protocol of tools/bench_yuv.py: device events around ``--iters`` back-to-back calls after 24 warm-up calls,
 the calls rotating over ``--buffers`` distinct sources and destinations (beyond the Infinity Cache), every configuration timed
 ``--repeats`` times in rotation in one process (median, min - max).  Decode -> fp32 canvas and encode from the fp32 canvas, the canvas

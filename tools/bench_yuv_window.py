@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Time the fused decode-window kernel (atm-vfi_amd/csrc/yuv.hip: atmvfi_yuv420_window) on the protocol of tools/bench_yuv.py:
+"""Time the fused decode-window kernel (atm-vfi_amd/csrc/yuv.hip: atmvfi_yuv_decode with mode) on the protocol of tools/bench_yuv.py:
 device events around ``--iters`` back-to-back calls after 24 warm-up calls, the calls rotating over ``--buffers`` distinct sources and
 destinations, every configuration timed ``--repeats`` times in rotation (median, min - max).  Sizes 2160 x 4096 (10 bit, bt709: a
 Xiph clip) and 1080 x 1920 (8 bit), each with the two windows of the Xiph evaluation (``evaluate.xiph_geometry``): mode 1 on the whole
