@@ -1096,7 +1096,6 @@ class HipOps:
 
     split_planes_ok = True        # this backend has the split-plane sinks and the LDS-DMA GEMM
     pyramid_packs = True          # image_pyramid(pack=...) does pack_frames' work in the same launch
-    motion_head_sink = True       # ... and the motion head's plane sink (no split pass for the motion MLP's eight motion channels)
 
     def split_planes(self, x, out: Planes, prelu=None, c0: Optional[int] = None):
         """fp32 rows -> split planes, optionally through a per-channel PReLU first.  ``c0``: write the channels at this offset

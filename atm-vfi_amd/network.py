@@ -21,7 +21,6 @@ There is no CPU path: ``forward`` requires CUDA(HIP) tensors and the built libra
 """
 from __future__ import annotations
 
-import math
 import operator
 from typing import Dict, List, Optional, Tuple
 
@@ -30,7 +29,8 @@ import torch.nn as nn
 
 from . import scaled
 from . import schema as S
-from .hip_ops import GEMM_CONV, GEMM_DECONV, GEMM_LINEAR, HipOps, PackedWeight, Planes, PlanUnsupported
+from .hip_ops import GEMM_CONV, GEMM_DECONV, GEMM_LINEAR, HipOps, LaunchPlan, Planes, PlanUnsupported
+from .paths import PlanesPath, RowsPath, _r4
 from .windows import WindowGeometry, build_window_geometry
 
 
@@ -75,18 +75,6 @@ class _ParamWatch:
 
 class _Node(_ParamWatch, nn.Module):
     """Anonymous container used to reproduce the reference's dotted parameter names."""
-
-
-def _r4(c: int) -> int:
-    return (c + 3) // 4 * 4
-
-
-class _PMap:
-    """A feature map that lives in split planes only: channels [32 * chunk0, 32 * chunk0 + c) of ``p``, rows = pixels of [n, h, w]."""
-    __slots__ = ("p", "n", "h", "w", "chunk0", "c")
-
-    def __init__(self, p, n, h, w, chunk0, c):
-        self.p, self.n, self.h, self.w, self.chunk0, self.c = p, n, h, w, chunk0, c
 
 
 class BlockRunner:
@@ -573,9 +561,7 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
             wp = sd["proj.0.weight"].detach()
             wpp = torch.cat([wp[:, :w3], torch.zeros(wp.shape[0], gap, 3, 3, dtype=wp.dtype, device=wp.device), wp[:, w3:]], 1)
             P["pk:proj.0.weight:planes"] = ops.pack_weight(GEMM_CONV, wpp.contiguous())
-        if hasattr(ops, "pack_readout") and getattr(ops, "split_planes_ok", False):
             P["readout"] = ops.pack_readout(sd["refine_head.1.0.weight"].detach())
-        if hasattr(ops, "pack_stem") and getattr(ops, "split_planes_ok", False):
             P["stem"] = ops.pack_stem(*(sd[f"feat_extracts.{a}.{b}"].detach() for a in ("0.0", "0.1", "1.0") for b in ("0.weight", "0.bias", "1.weight")))
         # f16x3 contraction operands saturate at +-65504 (deviation 2).  Weights are known here: say so once per
         # parameter version if a checkpoint comes near; for activations there is f16x3_deviation() below.
@@ -593,129 +579,16 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
         self._prepared_sig = sig
         return P
 
-    # ------------------------------------------------------------------ layers
-    def _conv_act(self, ops, P, p, x, out, stride=1):
-        ops.conv(x, P[f"pk:{p}.0.weight"], out, stride=stride, pad=1, dil=1, bias=P[f"{p}.0.bias"], prelu=P[f"{p}.1.weight"])
-
-    def _conv_plain(self, ops, P, p, x, out, stride=1, pad=1, dil=1, planes=None, planes_prelu=None):
-        if planes is not None:       # 3x3 epilogue also writes the split planes the next deconv reads (HIP backend only)
-            ops.conv(x, P[f"pk:{p}.weight"], out, stride=stride, pad=pad, dil=dil, bias=P[f"{p}.bias"], planes=planes,
-                     planes_prelu=planes_prelu)
-            return
-        ops.conv(x, P[f"pk:{p}.weight"], out, stride=stride, pad=pad, dil=dil, bias=P[f"{p}.bias"])
-
+    # ------------------------------------------------------------------ the two paths
     def _plane_convs(self, ops) -> bool:
-        """3x3 / stride-1 convs on the split-plane kernel (LDS-DMA halo, ping-pong wave groups): their inputs are written as
-        split planes by the producing layer's sink, fp32 copies only where something other than a contraction reads them."""
+        """THE switch between the forward's two paths (paths.py).  True: 3x3 / stride-1 convs on the split-plane kernel (LDS-DMA halo,
+        ping-pong wave groups), their inputs written as split planes by the producing layer's sink, fp32 copies only where something
+        other than a contraction reads them."""
         return self._plane_deconvs(ops) and self._rows_fit_planes
 
-    def _c3p(self, ops, P, p, xp, n, h, w, out=None, act=True, sink=None, sink_c0=0, sink_prelu=None, wkey=None, out_cmin=0, sink2=None):
-        """conv()/Conv2d 3x3 s1 p1 of the reference on split-plane input ``xp`` ([n*h*w rows]); ``p`` = parameter prefix
-        (``p.0.weight``/``p.0.bias``/``p.1.weight`` with ``act``, ``p.weight``/``p.bias`` without)."""
-        if act:
-            wk, bias, prelu = wkey or f"pk:{p}.0.weight", P[f"{p}.0.bias"], P[f"{p}.1.weight"]
-        else:
-            wk, bias, prelu = wkey or f"pk:{p}.weight", P[f"{p}.bias"], None
-        extra = {} if sink2 is None else {"planes2": sink2}
-        # under-filled grids with long K (the motion MLPs of small frames): split K over the idle CUs; the scratch for the partial
-        # sums is workspace memory like every other buffer
-        need = ops.conv3x3_workspace_floats(n, h, w, P[wk].cin, P[wk].cout)
-        if need:
-            extra["workspace"] = self.buf("splitk_ws", need)
-        ops.conv3x3_planes(xp, n, h, w, P[wk], out=out, bias=bias, prelu=prelu, planes=sink, planes_c0=sink_c0, planes_prelu=sink_prelu,
-                           out_cmin=out_cmin, **extra)
-
-    def _conv_p(self, ops, P, p, src: "_PMap", stride=1, pad=1, dil=1, act=True, out=None, sink=None, sink_c0=0, src2: "Optional[_PMap]" = None):
-        """conv() / nn.Conv2d of the reference (any stride / dilation, k 1 or 3) on a split-plane map through the LDS-DMA GEMM."""
-        if act:
-            wk, bias, prelu = f"pk:{p}.0.weight", P[f"{p}.0.bias"], P[f"{p}.1.weight"]
-        else:
-            wk, bias, prelu = f"pk:{p}.weight", P[f"{p}.bias"], None
-        two = {} if src2 is None else {"x2": src2.p, "x2_chunk0": src2.chunk0, "split_chunks": src.c // 32}
-        ops.conv_planes(src.p, src.n, src.h, src.w, P[wk], out=out, stride=stride, pad=pad, dil=dil, bias=bias, prelu=prelu, sink=sink,
-                        sink_c0=sink_c0, in_chunk0=src.chunk0, **two)
-
-    def _deconv_act(self, ops, P, p, x, out, in_prelu=None, split: Optional[str] = None, planes=None):
-        """``planes``: the input rows already in split-plane form, through ``in_prelu`` (written by the producing 3x3 conv).
-        ``split``: workspace name -- split the input rows into fp16 planes first (one pass, through ``in_prelu``).  Either way the
-        deconv runs on the LDS-DMA GEMM: the fp32-input engine redoes the split once per column block (7x for 389 -> 4*197)."""
-        w = P[f"pk:{p}.0.weight"]
-        if planes is not None:
-            ops.deconv(x, w, out, bias=P[f"{p}.0.bias"], prelu=P[f"{p}.1.weight"], planes=planes)
-            return
-        if split is not None and self._plane_deconvs(ops) and w.hi is not None:
-            b, h, wd, cin = x.shape
-            xp = self.planes(split, b * h * wd, cin)
-            ops.split_planes(x.flatten(0, 2), xp, prelu=in_prelu)
-            ops.deconv(x, w, out, bias=P[f"{p}.0.bias"], prelu=P[f"{p}.1.weight"], planes=xp)
-            return
-        ops.deconv(x, w, out, bias=P[f"{p}.0.bias"], prelu=P[f"{p}.1.weight"], in_prelu=in_prelu)
-
-    def _encoder(self, ops, P, x0, tag: str):
-        """shared_feat_extraction + cross-scale fusion buffers.  x0: [F,H,W,4].  Returns (e1, e2, fuse_l)
-        with s3 already written into fuse_l[..., -d3:] (network_base.py:342-352)."""
-        d = self._v.hidden_dims
-        f, h, w, _ = x0.shape
-        if self._plane_convs(ops):
-            # Stages 1-3 entirely in split planes: stride-2 conv (LDS-DMA GEMM, CONV mode) -> planes -> 3x3 conv (plane kernel) ->
-            # planes; the last one writes s3 straight into the fusion buffer's planes.  No fp32 copy of e1, e2, s3 exists: their
-            # only readers are contractions.
-            # The full-resolution stem (3 -> d0 -> d0 -> d1 stride 2) is ONE launch whose two d0-channel maps stay in LDS
-            # (atmvfi_stem_fused).
-            ld = self._v.local_dim
-            fuse_p = self.planes(f"{tag}fuse_l_p", f * (h // 8) * (w // 8), ld)
-            src, outs = None, []
-            for st in (1, 2, 3):
-                hs, ws = h >> st, w >> st
-                ap = self.planes(f"{tag}e{st}a_p", f * hs * ws, d[st])
-                if st == 1:
-                    ops.stem_fused(x0, P["stem"], ap)
-                else:
-                    self._conv_p(ops, P, f"feat_extracts.{st}.0", src, stride=2, sink=ap)
-                if st == 3:
-                    self._c3p(ops, P, "feat_extracts.3.1", ap, f, hs, ws, sink=fuse_p, sink_c0=ld - d[3])
-                    outs.append(_PMap(fuse_p, f, hs, ws, 0, ld))
-                else:
-                    ep = self.planes(f"{tag}e{st}_p", f * hs * ws, d[st])
-                    self._c3p(ops, P, f"feat_extracts.{st}.1", ap, f, hs, ws, sink=ep)
-                    outs.append(_PMap(ep, f, hs, ws, 0, d[st]))
-                    src = outs[-1]
-            return outs[0], outs[1], outs[2]
-        a = self.buf(f"{tag}e0a", f, h, w, d[0]); self._conv_act(ops, P, "feat_extracts.0.0", x0[..., :3], a)
-        e0 = self.buf(f"{tag}e0", f, h, w, d[0]); self._conv_act(ops, P, "feat_extracts.0.1", a, e0)
-        a = self.buf(f"{tag}e1a", f, h // 2, w // 2, d[1]); self._conv_act(ops, P, "feat_extracts.1.0", e0, a, 2)
-        e1 = self.buf(f"{tag}e1", f, h // 2, w // 2, d[1]); self._conv_act(ops, P, "feat_extracts.1.1", a, e1)
-        a = self.buf(f"{tag}e2a", f, h // 4, w // 4, d[2]); self._conv_act(ops, P, "feat_extracts.2.0", e1, a, 2)
-        e2 = self.buf(f"{tag}e2", f, h // 4, w // 4, d[2]); self._conv_act(ops, P, "feat_extracts.2.1", a, e2)
-        a = self.buf(f"{tag}e3a", f, h // 8, w // 8, d[3]); self._conv_act(ops, P, "feat_extracts.3.0", e2, a, 2)
-        fuse = self.buf(f"{tag}fuse_l", f, h // 8, w // 8, self._v.local_dim)
-        self._conv_act(ops, P, "feat_extracts.3.1", a, fuse[..., self._v.local_dim - d[3]:])
-        return e1, e2, fuse
-
-    def _fusion(self, ops, P, p, fine, mid, fuse, c_mid, c_fine, tag):
-        """CrossScaleFeatureFusion (network_base.py:73-85); the coarsest scale is already in
-        fuse[..., c_mid+2*c_fine:].  Returns LayerNorm'ed tokens [F*h*w, C]."""
-        if isinstance(fuse, _PMap):
-            # the three strided convs sink into the fusion buffer's planes next to the coarsest scale; the 1x1 projection is the
-            # LDS-DMA GEMM on those planes (no fp32 fusion buffer, no fp32 -> fp16-pair conversion per column block)
-            f, h, w, c = fuse.n, fuse.h, fuse.w, fuse.c
-            self._conv_p(ops, P, f"{p}.layers.0", mid, stride=2, pad=1, dil=1, act=False, sink=fuse.p, sink_c0=0)
-            self._conv_p(ops, P, f"{p}.layers.1", fine, stride=4, pad=1, dil=1, act=False, sink=fuse.p, sink_c0=c_mid)
-            self._conv_p(ops, P, f"{p}.layers.2", fine, stride=4, pad=2, dil=2, act=False, sink=fuse.p, sink_c0=c_mid + c_fine)
-            t = self.buf(f"{tag}fproj", f * h * w, c)
-            ops.linear(fuse.p, P[f"pk:{p}.proj.weight"], t, bias=P[f"{p}.proj.bias"])
-            out = self.buf(f"{tag}fnorm", f * h * w, c)
-            ops.layernorm(t, out, P[f"{p}.norm.weight"], P[f"{p}.norm.bias"])
-            return out
-        f, h, w, c = fuse.shape
-        self._conv_plain(ops, P, f"{p}.layers.0", mid, fuse[..., 0:c_mid], stride=2, pad=1, dil=1)
-        self._conv_plain(ops, P, f"{p}.layers.1", fine, fuse[..., c_mid:c_mid + c_fine], stride=4, pad=1, dil=1)
-        self._conv_plain(ops, P, f"{p}.layers.2", fine, fuse[..., c_mid + c_fine:c_mid + 2 * c_fine], stride=4, pad=2, dil=2)
-        t = self.buf(f"{tag}fproj", f * h * w, c)
-        ops.linear(fuse.reshape(f * h * w, c), P[f"pk:{p}.proj.weight"], t, bias=P[f"{p}.proj.bias"])
-        out = self.buf(f"{tag}fnorm", f * h * w, c)
-        ops.layernorm(t, out, P[f"{p}.norm.weight"], P[f"{p}.norm.bias"])
-        return out
+    def _path(self, ops):
+        """The stages of one eager forward, bound to its backend and current packed weights (made after ``_rows_fit_planes`` is known)."""
+        return (PlanesPath if self._plane_convs(ops) else RowsPath)(self, ops, self._prepare(ops))
 
     @staticmethod
     def _stacked(buf, off, c):
@@ -725,91 +598,36 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
         flat = buf.reshape(b * h * w, ld)[:, off:off + 2 * c]
         return flat.unflatten(1, (2, c)).permute(1, 0, 2)
 
-    def _motion_branch(self, ops, P, branch, mlp, x_tokens, b, h, w, ws, tag):
+    def _motion_branch(self, path, branch, mlp, x_tokens, b, h, w, ws, tag):
         """Two ATMFormer blocks + motion MLP (estimate_{local,global}_motion, network_base.py:367-415).
         Returns (mlp_in buffer, last hidden map) -- the caller runs the 1x1 head into its own slice."""
         c = x_tokens.shape[-1]
         cin = 8 + 2 * c
         mlp_in = self.buf(f"{tag}mlp_in", b, h, w, cin)
         flat = mlp_in.reshape(b * h * w, cin)
-        pc = self._plane_convs(ops)
-        mlp_in_p = self.planes(f"{tag}mlp_in_p", b * h * w, cin) if pc else None
+        sinks = path.motion_sinks(tag, b * h * w, cin, c)
         x = x_tokens
         for blk in range(2):
             mdst = flat[:, 4 * blk:4 * blk + 4].unflatten(1, (2, 2)).permute(1, 0, 2)       # '(N B) L K -> B L (N K)'
             out = self._stacked(mlp_in, 8, c) if blk == 1 else self.buf(f"{tag}blk0", 2 * b * h * w, c)
-            # the block's four motion channels (frame 0 dx dy, frame 1 dx dy at 4 blk ..) go into the plane input of the motion MLP
-            # straight from the motion head (no separate split pass)
-            msink = (mlp_in_p, 4 * blk, 2) if (pc and getattr(ops, "motion_head_sink", False)) else None
-            self._block(ops, P, f"{branch}.{blk}", x, 2 * b, h, w, ws, 0 if blk == 0 else ws // 2, True, out, mdst, tag,
-                        out_sink=(mlp_in_p, 8, c) if (pc and blk == 1) else None, motion_sink=msink)
+            self._block(path.ops, path.P, f"{branch}.{blk}", x, 2 * b, h, w, ws, 0 if blk == 0 else ws // 2, True, out, mdst, tag,
+                        out_sink=sinks[blk][0], motion_sink=sinks[blk][1])
             x = out
-        hid = P[f"{mlp}.0.0.bias"].shape[0]
-        if pc:
-            # [motion 8 | frame0 C | frame1 C] as split planes: the features come from fc2's plane sink, the eight motion
-            # channels (written by the two motion heads) from one small split pass
-            if not getattr(ops, "motion_head_sink", False):
-                ops.split_planes(flat[:, 0:8], mlp_in_p, c0=0)
-            t1p = self.planes(f"{tag}mm1_p", b * h * w, hid)
-            t2p = self.planes(f"{tag}mm2_p", b * h * w, hid)
-            self._c3p(ops, P, f"{mlp}.0", mlp_in_p, b, h, w, sink=t1p)
-            self._c3p(ops, P, f"{mlp}.1", t1p, b, h, w, sink=t2p)
-            return mlp_in, t2p
-        t1 = self.buf(f"{tag}mm1", b, h, w, hid); self._conv_act(ops, P, f"{mlp}.0", mlp_in, t1)
-        t2 = self.buf(f"{tag}mm2", b, h, w, hid); self._conv_act(ops, P, f"{mlp}.1", t1, t2)
-        return mlp_in, t2
+        return mlp_in, path.motion_mlp(mlp, mlp_in, b, h, w, tag)
 
-    def _global_tokens(self, ops, P, e2, fuse_l, tag):
-        """The per-frame half of estimate_global_motion (network_base.py:391-400): last_feat_extract + the global cross-scale fusion.
-        Returns the LayerNorm'ed tokens [F*h_*w_, global_dim] of the F frames in ``e2`` / ``fuse_l``."""
-        v = self._v
-        d = v.hidden_dims
-        if isinstance(fuse_l, _PMap):
-            f, h8, w8 = fuse_l.n, fuse_l.h, fuse_l.w
-            h_, w_ = h8 // 2, w8 // 2
-            s3 = _PMap(fuse_l.p, f, h8, w8, (v.local_dim - d[3]) // 32, d[3])
-            fuse_g = _PMap(self.planes(f"{tag}fuse_g_p", f * h_ * w_, v.global_dim), f, h_, w_, 0, v.global_dim)
-            ap = self.planes(f"{tag}ga_p", f * h_ * w_, v.last_feat_dim)
-            self._conv_p(ops, P, "last_feat_extract.0", s3, stride=2, sink=ap)
-            self._c3p(ops, P, "last_feat_extract.1", ap, f, h_, w_, sink=fuse_g.p, sink_c0=d[3] + 2 * d[2])
-            return self._fusion(ops, P, "global_feature_fusion", e2, s3, fuse_g, d[3], d[2], tag + "g")
-        f, h8, w8, _ = fuse_l.shape
-        h_, w_ = h8 // 2, w8 // 2
-        s3 = fuse_l[..., v.local_dim - d[3]:]
-        fuse_g = self.buf(f"{tag}fuse_g", f, h_, w_, v.global_dim)
-        a = self.buf(f"{tag}ga", f, h_, w_, v.last_feat_dim)
-        self._conv_act(ops, P, "last_feat_extract.0", s3, a, 2)
-        self._conv_act(ops, P, "last_feat_extract.1", a, fuse_g[..., d[3] + 2 * d[2]:])
-        return self._fusion(ops, P, "global_feature_fusion", e2, s3, fuse_g, d[3], d[2], tag + "g")
-
-    def _global_from_tokens(self, ops, P, tokens, b, h_, w_, tag):
+    def _global_from_tokens(self, path, tokens, b, h_, w_, tag):
         """The pair half of estimate_global_motion (network_base.py:401-415): two ATMFormer blocks + the motion MLP on the frame-stacked
         tokens [2B*h_*w_, global_dim].  Returns the raw 5-channel map [B,h_,w_,5] (in an 8-float-per-pixel buffer)."""
-        mlp_in, t2 = self._motion_branch(ops, P, "global_motion_atmformer", "global_motion_mlp", tokens, b, h_, w_,
-                                         self.global_motion_args["window_size"], tag + "g")
+        _, t2 = self._motion_branch(path, "global_motion_atmformer", "global_motion_mlp", tokens, b, h_, w_,
+                                    self.global_motion_args["window_size"], tag + "g")
         gout = self.buf(f"{tag}gout", b, h_, w_, 8)
-        self._head1x1(ops, P, "global_motion_mlp.2", t2, b, h_, w_, gout[..., :5])
+        path.head1x1("global_motion_mlp.2", t2, b, h_, w_, gout[..., :5])
         return gout
 
-    def _global_motion(self, ops, P, e2, fuse_l, b, tag):
-        """estimate_global_motion (network_base.py:391-415): returns the raw 5-channel map [B,h_,w_,5]."""
-        if isinstance(fuse_l, _PMap):
-            h_, w_ = fuse_l.h // 2, fuse_l.w // 2
-        else:
-            h_, w_ = fuse_l.shape[1] // 2, fuse_l.shape[2] // 2
-        tokens = self._global_tokens(ops, P, e2, fuse_l, tag)
-        return self._global_from_tokens(ops, P, tokens, b, h_, w_, tag)
-
-    def _head1x1(self, ops, P, p, t2, b, h, w, out):
-        """The 1x1 head of a motion MLP (network_base.py:158,195): on the hidden map's planes when the branch left it there."""
-        if isinstance(t2, Planes):
-            ops.head1x1_planes(t2, b, h, w, P[f"pk:{p}.weight"], out, bias=P[f"{p}.bias"])       # 5 channels: a lane per pixel, no GEMM tile
-        else:
-            self._conv_plain(ops, P, p, t2, out, pad=0)
-
-    def _ensemble_flows(self, ops, P, im0, im1):
+    def _ensemble_flows(self, path, im0, im1):
         """multiscale_global_motion_ensemble (network_base.py:564-605): global flows from the x1, x1/2
         and x1/4 inputs; per sample keep the one whose warped full-resolution frames agree best."""
+        ops = path.ops
         b, _, h, w = im0.shape
         cands, losses = [], []
         c0, c1 = im0, im1
@@ -822,8 +640,9 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
             if hh % 16 or ww % 16:
                 raise ValueError(f"ensemble_global_motion needs H, W divisible by 64 (level {lvl} is {hh}x{ww})")
             x0 = self.buf(f"ens{lvl}x0", 2 * b, hh, ww, 4); ops.pack_frames(c0, c1, x0)
-            _, e2, fuse = self._encoder(ops, P, x0, f"ens{lvl}")
-            gout = self._global_motion(ops, P, e2, fuse, b, f"ens{lvl}")
+            _, e2, fuse = path.encoder(x0, f"ens{lvl}")
+            gtok = path.global_tokens(e2, fuse, f"ens{lvl}")                                     # estimate_global_motion (:391-415)
+            gout = self._global_from_tokens(path, gtok, b, hh // 16, ww // 16, f"ens{lvl}")
             f0 = gout[..., 0:2].permute(0, 3, 1, 2)
             f1 = gout[..., 2:4].permute(0, 3, 1, 2)
             factor = 16 << lvl
@@ -834,12 +653,8 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
             loss = self.buf(f"ens{lvl}loss", b)
             ops.l1_mean(wa, wb, loss, workspace=self.buf("ens_l1_ws", ops.l1_mean_workspace_floats(b, 3 * h * w)) if hasattr(ops, "l1_mean_workspace_floats") else None)
             # candidate at the level-0 flow resolution (H/16): x1, x2, x4 up-sampling of the coarser flows
-            if lvl == 0:
-                k0 = self.buf("ens_c0_0", b, 2, h // 16, w // 16); ops.resize(f0, k0, 1.0)
-                k1 = self.buf("ens_c1_0", b, 2, h // 16, w // 16); ops.resize(f1, k1, 1.0)
-            else:
-                k0 = self.buf(f"ens_c0_{lvl}", b, 2, h // 16, w // 16); ops.resize(f0, k0, float(1 << lvl))
-                k1 = self.buf(f"ens_c1_{lvl}", b, 2, h // 16, w // 16); ops.resize(f1, k1, float(1 << lvl))
+            k0 = self.buf(f"ens_c0_{lvl}", b, 2, h // 16, w // 16); ops.resize(f0, k0, float(1 << lvl))
+            k1 = self.buf(f"ens_c1_{lvl}", b, 2, h // 16, w // 16); ops.resize(f1, k1, float(1 << lvl))
             cands.append((k0, k1)); losses.append(loss)
         if hasattr(ops, "ensemble_select"):                # the pick inside the C ABI: no device arithmetic outside it, plannable
             s0, s1 = self.buf("ens_sel0", b, 2, h // 16, w // 16), self.buf("ens_sel1", b, 2, h // 16, w // 16)
@@ -953,29 +768,21 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
         self._sync_plan_sig()
         key = self._mode_key(ops, im0, im1)
         ent = self._plans.get(key, 0)
-        if ent is False:
-            st["eager"] += 1
-            return self._forward_eager(im0, im1)
-        if isinstance(ent, int):
-            if ent < 2:                                      # the first two forwards build the workspace, maps, kernel attributes
-                self._plans[key] = ent + 1
+        if isinstance(ent, LaunchPlan):
+            if im0.shape != im1.shape or im0.device != im1.device or im0.device != ops.device:
                 st["eager"] += 1
-                return self._forward_eager(im0, im1)
-            return self._record_plan(ops, key, im0, im1)
-        if im0.shape != im1.shape or im0.device != im1.device or im0.device != ops.device:
-            st["eager"] += 1
-            return self._forward_eager(im0, im1)             # raises the proper error
+                return self._forward_eager(im0, im1)         # raises the proper error
+            self._select_workspace(key[-1])                  # replay counts as a use for the workspace LRU
         with torch.cuda.device(im0.device):
             a = im0.detach().contiguous().float()
             b = im1.detach().contiguous().float()
-            if (a.data_ptr() & 15, b.data_ptr() & 15) != ent.align:
-                # the recording chose kernels for its inputs' alignment (the LDS-staged warps load rows 16 bytes at a time): a
-                # differently aligned view takes the direct launches, which choose again
+            if ent == 2 and a.data_ptr() < b.data_ptr() + b.numel() * 4 and b.data_ptr() < a.data_ptr() + a.numel() * 4:
+                # aliased / overlapping frames (net(x, x)) on the call that would record: a recording could not tell a pointer into one
+                # from a pointer into the other and every later net(a, b) of this shape would replay as net(a, a).  Stay eager and
+                # leave the key's state alone; the next call with distinct frames records.
                 st["eager"] += 1
                 return self._forward_eager(im0, im1)
-            self._select_workspace(key[-1])                  # replay counts as a use for the workspace LRU
-            st["replayed"] += 1
-            return ent.run((a, b), ops.device, ops._stream())
+            return self._planned("forward", self._plans, key, ops, (a, b), lambda: self._forward_eager(a, b))
 
     def forward_scaled(self, im0: torch.Tensor, im1: torch.Tensor, scale: int = 2, want=()):
         """Half-resolution motion (scaled.py holds the definition): ``forward`` on the 2 x 2 box averages of the two [B,3,H,W] frames
@@ -1021,40 +828,52 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
             return isinstance(y, (list, tuple)) and len(x) == len(y) and all(Network._same_results(u, v) for u, v in zip(x, y))
         return x == y
 
-    def _record_plan(self, ops, key, im0, im1):
-        a = im0.detach().contiguous().float()
-        b = im1.detach().contiguous().float()
-        na, nb = a.numel() * 4, b.numel() * 4
-        if a.data_ptr() < b.data_ptr() + nb and b.data_ptr() < a.data_ptr() + na:
-            # aliased / overlapping frames (net(x, x)): a recording could not tell a pointer into one from a pointer into the other
-            # and every later net(a, b) of this shape would replay as net(a, a).  Stay eager; the next call with distinct frames records.
-            self._plan_stats["forward"]["eager"] += 1
-            return self._forward_eager(im0, im1)
+    def _planned(self, kind: str, plans: Dict, key, ops, inputs, body, lists=None, check=None):
+        """THE launch-plan state machine, of ``forward`` ("forward", over ``_plans``) and of the two stages of ``forward_pooled``
+        ("pooled_frame", "pooled_pair", over ``_pool_plans``) alike.  The first two calls of a ``key`` run ``body`` (direct launches:
+        they build the workspace, maps, kernel attributes), the third records it, later ones replay the plan with ``inputs`` as the
+        per-call tensors and ``lists`` as the per-call slot lists.  ``key`` None: not plannable now (plans off, profiling, the checked
+        build, stream capture).  Every call lands in exactly one bin of ``plan_stats()[kind]``.
+        ``check(out, replay) -> bool``: the record-time self-check, ``replay(**kw)`` running the fresh plan once; a recording that fails
+        it, or cannot be expressed, leaves the key on direct launches.  Default: replay into NaN-filled outputs and require ``body``'s
+        results bit for bit (the forward is run-to-run deterministic) -- a pointer patched into the wrong slot, a missed patch or a
+        launch that was not recorded shows up here, before the plan ever serves a caller."""
+        st = self._plan_stats[kind]
+        ent = False if key is None else plans.get(key, 0)
+        if isinstance(ent, LaunchPlan):
+            if tuple(t.data_ptr() & 15 for t in inputs) != ent.align:
+                # the recording chose kernels for its inputs' alignment (the LDS-staged warps load rows 16 bytes at a time): a
+                # differently aligned view takes the direct launches, which choose again
+                st["eager"] += 1
+                return body()
+            st["replayed"] += 1
+            return ent.run(inputs, ops.device, ops._stream(), lists=lists)
+        if ent is False or ent < 2:
+            if ent is not False:
+                plans[key] = ent + 1
+            st["eager"] += 1
+            return body()
         try:
-            ops.begin_plan((a, b))
-            out = self._forward_eager(a, b)
+            ops.begin_plan(inputs)
+            out = body()
             plan = ops.end_plan(out)
         except PlanUnsupported:
             ops.abort_plan()
-            self._plans[key] = False
-            self._plan_stats["forward"]["refused"] += 1
-            return self._forward_eager(im0, im1)
+            plan, out = None, body()
         except Exception:
             ops.abort_plan()
             raise
-        # Record-time self-check: replay the fresh plan once into NaN-filled outputs and require the recording forward's results bit
-        # for bit (the forward is run-to-run deterministic).  A pointer patched into the wrong slot, a missed patch or a launch that
-        # was not recorded shows up here, before the plan ever serves a caller; such a shape stays on direct launches.
-        with torch.cuda.device(a.device):
-            again = plan.run((a, b), ops.device, ops._stream(), poison=True)
-        if self._same_results(out, again):
-            self._plans[key] = plan
-            self._plan_stats["forward"]["recorded"] += 1
-        else:
-            import warnings
-            warnings.warn("atm-vfi_amd: a recorded launch plan did not reproduce its own forward; this input shape stays on direct launches")
-            self._plans[key] = False
-            self._plan_stats["forward"]["refused"] += 1
+        ok = plan is not None
+        if ok:
+            replay = lambda **kw: plan.run(inputs, ops.device, ops._stream(), lists=lists, **kw)
+            ok = self._same_results(out, replay(poison=True)) if check is None else check(out, replay)
+            if not ok:
+                import warnings
+                warnings.warn("atm-vfi_amd: a recorded launch plan did not reproduce its own forward; this input shape stays on direct launches"
+                              if kind == "forward" else
+                              f"atm-vfi_amd: a recorded launch plan ({kind}) did not reproduce its own stage; this key stays on direct launches")
+        plans[key] = plan if ok else False
+        st["recorded" if ok else "refused"] += 1
         return out
 
     def _forward_graph(self, im0: torch.Tensor, im1: torch.Tensor):
@@ -1118,7 +937,7 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
         with torch.no_grad():
             im0 = im0.detach().contiguous().float()
             im1 = im1.detach().contiguous().float()
-            P = self._prepare(ops)
+            path = self._path(ops)
             h, w = H // 8, W // 8
             # image pyramids (network_base.py:444-448)
             # Levels >= 1 of both frames live stacked along the batch axis ([:b] = frame 0, [b:] = frame 1): one launch per level
@@ -1140,7 +959,7 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
             if hit:
                 # frame 0 of this pair was frame 1 of the previous call: encoder + fusions (everything that is per frame) on the
                 # new frame only; the previous call's tokens of the shared frame are copied in front of the new ones
-                one, g_one = self._frame_stage(ops, P, x0[b:], "fc", "fcl", glob)                              # [B*h*w, C], [B*h_*w_, cg]
+                one, g_one = self._frame_stage(path, x0[b:], "fc", "fcl", glob)                              # [B*h*w, C], [B*h_*w_, cg]
                 feat = self.buf("lfnorm", 2 * b * h * w, C)
                 feat[:b * h * w].copy_(self._frame_cache[1])
                 feat[b * h * w:].copy_(one)
@@ -1150,7 +969,7 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
                     gtok[:n_g].copy_(self._frame_cache[2])
                     gtok[n_g:].copy_(g_one)
             else:
-                feat, gtok = self._frame_stage(ops, P, x0, "", "l", glob)                                      # [2B*h*w, C], [2B*h_*w_, cg]
+                feat, gtok = self._frame_stage(path, x0, "", "l", glob)                                      # [2B*h*w, C], [2B*h_*w_, cg]
             if cache_ok:
                 keep = self.buf("frame_cache_tokens", b * h * w, C)
                 keep.copy_(feat[b * h * w:])
@@ -1161,44 +980,15 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
                     keep_g.copy_(gtok[n_g:])
                 self._frame_cache = (ck, keep, keep_g)
             self._reuse_first = False
-            return self._pair_stage(ops, P, im0, im1, pyr_st, feat, gtok)
+            return self._pair_stage(path, im0, im1, pyr_st, feat, gtok)
 
     def _frame_stage_splitk(self, ops, H: int, W: int, f: int) -> Tuple:
         """The split-K factors the library would choose for the contraction launches of ``_frame_stage`` on ``f`` frames of H x W, in
-        launch order (``_encoder``, ``_fusion``, ``_global_tokens``).  Under-filled grids with long K are cut over the idle CUs
-        (``gemm_splitk_plan``, ``conv3_plan``: host-side functions of the launch's ROWS), and a different cut sums in a different
-        order: tokens are bit-identical to ``forward``'s only when computed under the same factors.  Empty when the forward is not on
+        launch order (``PlanesPath.frame_stage_splitk``, kept directly below the stages it mirrors).  Empty when the forward is not on
         the plane kernels (nothing splits there)."""
         if not (isinstance(ops, HipOps) and self._plane_convs(ops)):
             return ()
-        v = self._v
-        d = v.hidden_dims
-        c32 = lambda c: (c + 31) // 32
-
-        def gemm(rows, cout, cin, taps=9):
-            if ops.gemm_workspace is None:
-                return 1
-            need = int(ops.lib.atmvfi_gemm_workspace_floats(rows, cout, taps * c32(cin)))
-            return need // (rows * ((cout + 63) // 64 * 64)) if need else 1
-
-        def c3(h, w, cin, cout):
-            need = ops.conv3x3_workspace_floats(f, h, w, cin, cout)
-            return need // (f * h * w * ((cout + 15) // 16 * 16)) if need else 1
-        out = []
-        for st in (1, 2, 3):
-            hs, ws = H >> st, W >> st
-            if st > 1:
-                out.append(gemm(f * hs * ws, d[st], d[st - 1]))                   # feat_extracts.st.0 (stride 2)
-            out.append(c3(hs, ws, d[st], d[st]))                                   # feat_extracts.st.1
-        h, w = H // 8, W // 8
-        out += [gemm(f * h * w, d[2], d[2]), gemm(f * h * w, d[1], d[1]), gemm(f * h * w, d[1], d[1]),      # fusion layers 0..2
-                gemm(f * h * w, v.local_dim, v.local_dim, 1)]                                                  # fusion projection
-        if self.global_motion and not self.ensemble_global_motion:
-            h_, w_ = H // 16, W // 16
-            out += [gemm(f * h_ * w_, v.last_feat_dim, d[3]), c3(h_, w_, v.last_feat_dim, v.last_feat_dim),    # last_feat_extract
-                    gemm(f * h_ * w_, d[3], d[3]), gemm(f * h_ * w_, d[2], d[2]), gemm(f * h_ * w_, d[2], d[2]),
-                    gemm(f * h_ * w_, v.global_dim, v.global_dim, 1)]
-        return tuple(out)
+        return PlanesPath.frame_stage_splitk(self, ops, H, W, f, self.global_motion and not self.ensemble_global_motion)
 
     def forward_pooled(self, pool, left, right, exact: bool = True):
         """``forward`` on frames that live in a ``multiframe.FramePool``: pair j = (slot ``left[j]``, slot ``right[j]``), batch
@@ -1261,7 +1051,8 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
             if hasattr(ops, "begin_forward"):
                 ops.begin_forward()
             self._rows_fit_planes = 2 * b * H * W < (1 << 26)
-            P = self._prepare(ops)
+            path = self._path(ops)
+            inputs = (pool.frames, pool.tokens_l, pool.tokens_g)
             planned = (self.use_plans and self._pooled_plans_on and isinstance(ops, HipOps) and ops.profile is None and not self._checked
                        and not torch.cuda.is_current_stream_capturing())
             if planned:
@@ -1279,14 +1070,15 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
                     run += 1
                 fe = run + (run & 1)
                 key = ("pooled_frame", f, run, pool.slots, self._rows_fit_planes) + self._mode_fields(ops) + (wkey,)
-                self._pooled_stage("pooled_frame", key if planned else None, ops, pool,
-                                   {"stale_padded": stale + stale[-1:] * (fe - f), "stale": stale},
-                                   lambda: self._pooled_frame_stage(ops, P, pool, stale, run, glob))
+                self._planned("pooled_frame", self._pool_plans, key if planned else None, ops, inputs,
+                              lambda: self._pooled_frame_stage(path, pool, stale, run, glob),
+                              lists={"stale_padded": stale + stale[-1:] * (fe - f), "stale": stale},
+                              check=lambda out, replay: self._replay_rewrites_tokens(pool, stale, replay))
                 for s in stale:
                     pool.keys[s] = vkey
             key = ("pooled_pair", pool.slots, self._rows_fit_planes) + self._mode_fields(ops) + (wkey,)
-            return self._pooled_stage("pooled_pair", key if planned else None, ops, pool, {"pairs": left + right},
-                                      lambda: self._pooled_pair_stage(ops, P, pool, left, right, glob))
+            return self._planned("pooled_pair", self._pool_plans, key if planned else None, ops, inputs,
+                                 lambda: self._pooled_pair_stage(path, pool, left, right, glob), lists={"pairs": left + right})
 
     def _splitk_of(self, ops, H: int, W: int, f: int) -> Tuple:
         """``_frame_stage_splitk``, remembered: a function of the size, the frame count and the mode (never of the weights' values), and
@@ -1299,10 +1091,11 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
             got = self._splitk_memo[key] = self._frame_stage_splitk(ops, H, W, f)
         return got
 
-    def _pooled_frame_stage(self, ops, P, pool, stale, run: int, glob: bool):
+    def _pooled_frame_stage(self, path, pool, stale, run: int, glob: bool):
         """The frame stage of ``forward_pooled``: the ``stale`` slots' frames (filled up to ``run``, and to an even count for
         ``pack_frames``, with repeats of the last) through ``_frame_stage``; the tokens of the distinct ones go back into the pool.
         Slot lists carry roles: a launch plan rewrites them per replay.  Writes into the pool only; returns None."""
+        ops = path.ops
         H, W = pool.hp, pool.wp
         f = len(stale)
         fe = run + (run & 1)
@@ -1311,14 +1104,15 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
         ops.pool_blocks(pool.frames, stale + stale[-1:] * (fe - f), g, role="stale_padded")
         x0 = self.buf("pool_x0", fe, H, W, 4)
         ops.pack_frames(g[:fe // 2], g[fe // 2:], x0)
-        t_l, t_g = self._frame_stage(ops, P, x0[:run], "fp", "fpl", glob)
+        t_l, t_g = self._frame_stage(path, x0[:run], "fp", "fpl", glob)
         ops.pool_blocks(pool.tokens_l, stale, t_l[:f * n_l], to_pool=True, role="stale")
         if glob:
             ops.pool_blocks(pool.tokens_g, stale, t_g[:f * n_g], to_pool=True, role="stale")
 
-    def _pooled_pair_stage(self, ops, P, pool, left, right, glob: bool):
+    def _pooled_pair_stage(self, path, pool, left, right, glob: bool):
         """The pair stage of ``forward_pooled``: frames and tokens of the pairs gathered from the pool (role "pairs"), the image
         pyramid, ``_pair_stage``.  Returns the forward's dict of fresh tensors."""
+        ops = path.ops
         b = len(left)
         H, W = pool.hp, pool.wp
         v = self._v
@@ -1334,116 +1128,71 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
             ops.pool_blocks(pool.tokens_g, left + right, gtok, role="pairs")
         pyr_st = [None] + [self.buf(f"pyr_{l}", 2 * b, 3, H >> l, W >> l) for l in range(1, 4)]
         ops.image_pyramid(im0, im1, pyr_st[1], pyr_st[2], pyr_st[3])
-        return self._pair_stage(ops, P, im0, im1, pyr_st, feat, gtok)
+        return self._pair_stage(path, im0, im1, pyr_st, feat, gtok)
 
-    def _pooled_stage(self, kind: str, key, ops, pool, lists, body):
-        """One stage of ``forward_pooled`` by ``forward``'s rules: the first two calls of a key run ``body`` (direct launches), the third
-        records it, later ones replay the plan with the pool's tensors as inputs and ``lists`` as slot lists.  ``key`` None: not
-        plannable now (plans off, profiling, the checked build, stream capture)."""
-        st = self._plan_stats[kind]
-        ent = False if key is None else self._pool_plans.get(key, 0)
-        if ent is False:
-            st["eager"] += 1
-            return body()
-        if isinstance(ent, int):
-            if ent < 2:                                      # the first two calls build the workspace, maps, kernel attributes
-                self._pool_plans[key] = ent + 1
-                st["eager"] += 1
-                return body()
-            return self._record_pooled(kind, key, ops, pool, lists, body)
-        inputs = (pool.frames, pool.tokens_l, pool.tokens_g)
-        if tuple(t.data_ptr() & 15 for t in inputs) != ent.align:
-            st["eager"] += 1                                 # kernel choices were made for the recording pool's alignment
-            return body()
-        st["replayed"] += 1
-        return ent.run(inputs, ops.device, ops._stream(), lists=lists)
+    def _replay_rewrites_tokens(self, pool, stale, replay) -> bool:
+        """The record-time self-check of the pooled FRAME stage (``_planned``), which has no outputs: it writes the stale slots' tokens
+        into the pool.  Keep those tokens, fill the slots with NaN, replay, compare -- and put the kept ones back if the replay wrote
+        anything else."""
+        idx = torch.tensor(stale, device=pool.frames.device)
+        toks = [pool.tokens_l] + ([pool.tokens_g] if self.global_motion else [])
+        kept = [t.index_select(0, idx) for t in toks]
+        for t in toks:
+            t.index_fill_(0, idx, float("nan"))
+        replay()
+        ok = all(bool(torch.equal(t.index_select(0, idx), k)) for t, k in zip(toks, kept))
+        if not ok:
+            for t, k in zip(toks, kept):
+                t.index_copy_(0, idx, k)
+        return ok
 
-    def _record_pooled(self, kind: str, key, ops, pool, lists, body):
-        import warnings
-        st = self._plan_stats[kind]
-        inputs = (pool.frames, pool.tokens_l, pool.tokens_g)
-        try:
-            ops.begin_plan(inputs)
-            out = body()
-            plan = ops.end_plan(out)
-        except PlanUnsupported:
-            ops.abort_plan()
-            self._pool_plans[key] = False
-            st["refused"] += 1
-            return body()
-        except Exception:
-            ops.abort_plan()
-            raise
-        # Record-time self-check, as for forward: one replay must reproduce what the recording call's direct launches produced, bit for
-        # bit.  Pair stage: into NaN-filled outputs, against the recording call's dict.  Frame stage (no outputs; it writes the stale
-        # slots' tokens into the pool): keep those tokens, fill the slots with NaN, replay, compare -- and put the kept ones back if
-        # the replay wrote anything else.
-        if kind == "pooled_pair":
-            ok = self._same_results(out, plan.run(inputs, ops.device, ops._stream(), poison=True, lists=lists))
-        else:
-            idx = torch.tensor(lists["stale"], device=pool.frames.device)
-            toks = [pool.tokens_l] + ([pool.tokens_g] if self.global_motion else [])
-            kept = [t.index_select(0, idx) for t in toks]
-            for t in toks:
-                t.index_fill_(0, idx, float("nan"))
-            plan.run(inputs, ops.device, ops._stream(), lists=lists)
-            ok = all(bool(torch.equal(t.index_select(0, idx), k)) for t, k in zip(toks, kept))
-            if not ok:
-                for t, k in zip(toks, kept):
-                    t.index_copy_(0, idx, k)
-        if ok:
-            self._pool_plans[key] = plan
-            st["recorded"] += 1
-        else:
-            warnings.warn(f"atm-vfi_amd: a recorded launch plan ({kind}) did not reproduce its own stage; this key stays on direct launches")
-            self._pool_plans[key] = False
-            st["refused"] += 1
-        return out
-
-    def _frame_stage(self, ops, P, x0, tag: str, ltag: str, glob: bool):
+    def _frame_stage(self, path, x0, tag: str, ltag: str, glob: bool):
         """Everything ``forward`` computes PER FRAME, on the F NHWC4-packed frames ``x0`` [F,H,W,4]: shared_feat_extraction, the
         cross-scale fusion and its LayerNorm (network_base.py:342-352, 451-455) and, with ``glob`` (global branch on, ensemble off),
         the per-frame half of estimate_global_motion (:391-400).  Returns the local tokens [F*h*w, C] and the global tokens
         [F*h_*w_, Cg] (or None) in workspace buffers named by ``tag`` / ``ltag``.  The pair meets in ``_pair_stage``."""
         d = self._v.hidden_dims
-        e1, e2, fuse_l = self._encoder(ops, P, x0, tag)
-        feat = self._fusion(ops, P, "cross_scale_feature_fusion", e1, e2, fuse_l, d[2], d[1], ltag)
-        return feat, (self._global_tokens(ops, P, e2, fuse_l, tag) if glob else None)
+        e1, e2, fuse_l = path.encoder(x0, tag)
+        feat = path.fusion("cross_scale_feature_fusion", e1, e2, fuse_l, d[2], d[1], ltag)
+        return feat, (path.global_tokens(e2, fuse_l, tag) if glob else None)
 
-    def _pair_stage(self, ops, P, im0, im1, pyr_st, feat, gtok):
+    def _pair_stage(self, path, im0, im1, pyr_st, feat, gtok):
         """The rest of the forward, from the frame-stacked tokens on: ``feat`` [2B*h*w, C] and ``gtok`` [2B*h_*w_, Cg] (left frames
         first, then right frames), the contiguous fp32 frames ``im0`` / ``im1`` [B,3,H,W] and their stacked pyramid levels 1..3
-        ``pyr_st`` ([2B,3,H>>l,W>>l]).  Returns the forward's dict."""
+        ``pyr_st`` ([2B,3,H>>l,W>>l]).  Returns the forward's dict.  The skeleton both paths share: the contractions between the
+        warps are ``path``'s stages."""
+        ops = path.ops
         b, _, H, W = im0.shape
-        v = self._v
-        C = v.local_dim
+        C = self._v.local_dim
         h, w = H // 8, W // 8
         pyr0 = [im0] + [t[:b] for t in pyr_st[1:]]
         pyr1 = [im1] + [t[b:] for t in pyr_st[1:]]
+        it_list: List[torch.Tensor] = []
+        w0_list: List[torch.Tensor] = []
+        w1_list: List[torch.Tensor] = []
+
+        def blend(p0, p1, mot, *full, **pack):
+            a, c, t = (ops.empty(b, 3, *p0.shape[-2:]) for _ in range(3))
+            ops.warp_blend(p0, p1, mot, a, c, t, *full, **pack)
+            w0_list.insert(0, a); w1_list.insert(0, c); it_list.insert(0, t)
         with torch.no_grad():
-            it_list: List[torch.Tensor] = []
-            w0_list: List[torch.Tensor] = []
-            w1_list: List[torch.Tensor] = []
             x_tokens = feat
             if self.global_motion:                                                        # (:457-485)
                 h_, w_ = H // 16, W // 16
-                if self.ensemble_global_motion:
-                    g0, g1 = self._ensemble_flows(ops, P, im0, im1)
-                else:
-                    gout = self._global_from_tokens(ops, P, gtok, b, h_, w_, "")
-                    i_16 = self.buf("im_16", 2 * b, 3, h_, w_); ops.resize(pyr_st[3], i_16)
-                    a, c, t = (ops.empty(b, 3, h_, w_) for _ in range(3))
-                    ops.warp_blend(i_16[:b], i_16[b:], gout[..., :5], a, c, t)
-                    w0_list.insert(0, a); w1_list.insert(0, c); it_list.insert(0, t)
-                    g0 = gout[..., 0:2].permute(0, 3, 1, 2)
-                    g1 = gout[..., 2:4].permute(0, 3, 1, 2)
                 # the two global flows stacked like the frames: every warp / x2 up-sampling below is one launch for both
                 gf = self.buf("gf_3", 2 * b, 2, h, w)
-                if b == 1 and not self.ensemble_global_motion:
-                    # one pair: [flow0 | flow1] of the motion map's first four channels IS the stacked layout [2, 2, h, w]: one launch
-                    ops.resize(gout[..., 0:4].permute(0, 3, 1, 2), gf.view(1, 4, h, w), 2.0)
-                else:
+                if self.ensemble_global_motion:
+                    g0, g1 = self._ensemble_flows(path, im0, im1)
                     ops.resize(g0, gf[:b], 2.0); ops.resize(g1, gf[b:], 2.0)
+                else:
+                    gout = self._global_from_tokens(path, gtok, b, h_, w_, "")
+                    i_16 = self.buf("im_16", 2 * b, 3, h_, w_); ops.resize(pyr_st[3], i_16)
+                    blend(i_16[:b], i_16[b:], gout[..., :5])
+                    if b == 1:
+                        # one pair: [flow0 | flow1] of the motion map's first four channels IS the stacked layout [2, 2, h, w]: one launch
+                        ops.resize(gout[..., 0:4].permute(0, 3, 1, 2), gf.view(1, 4, h, w), 2.0)
+                    else:
+                        ops.resize(gout[..., 0:2].permute(0, 3, 1, 2), gf[:b], 2.0); ops.resize(gout[..., 2:4].permute(0, 3, 1, 2), gf[b:], 2.0)
                 featw = self.buf("featw", 2 * b, h, w, C)
                 ops.flow_warp_nhwc(feat.reshape(2 * b, h, w, C), gf, featw)
                 x_tokens = featw.reshape(2 * b * h * w, C)
@@ -1461,168 +1210,35 @@ class Network(_ParamWatch, BlockRunner, nn.Module):
             dec_in = self.buf("dec_in", b, h, w, _r4(cdec))
             motion8 = dec_in[..., 2 * C:2 * C + 5]
             a, c, t = (ops.empty(b, 3, h, w) for _ in range(3))
-            mlp_in, t2 = self._motion_branch(ops, P, "local_motion_atmformer", "local_motion_mlp", x_tokens, b, h, w,
+            mlp_in, t2 = self._motion_branch(path, "local_motion_atmformer", "local_motion_mlp", x_tokens, b, h, w,
                                              self.local_motion_args["window_size"], "l")
-            self._head1x1(ops, P, "local_motion_mlp.2", t2, b, h, w, motion8)
+            path.head1x1("local_motion_mlp.2", t2, b, h, w, motion8)
             ops.warp_blend(pyr0[3], pyr1[3], motion8, a, c, t)          # synthesis at H/8 (:496-506)
             # feature enhancement (:493-494)
-            x = self._stacked(mlp_in, 8, C)
             e_mid = self.buf("enh0", 2 * b * h * w, C)
-            self._block(ops, P, "feat_enhance_transformer.0", x, 2 * b, h, w, 8, 0, False, e_mid, None, "e")
+            self._block(ops, path.P, "feat_enhance_transformer.0", self._stacked(mlp_in, 8, C), 2 * b, h, w, 8, 0, False, e_mid, None, "e")
             enh = self.buf("enh1", 2 * b, h, w, C)
-            self._block(ops, P, "feat_enhance_transformer.1", e_mid, 2 * b, h, w, 8, 4, False, enh.reshape(2 * b * h * w, C), None, "e")
+            self._block(ops, path.P, "feat_enhance_transformer.1", e_mid, 2 * b, h, w, 8, 4, False, enh.reshape(2 * b * h * w, C), None, "e")
             # warped features (:496-506)
-            fl0 = motion8[..., 0:2].permute(0, 3, 1, 2)
-            fl1 = motion8[..., 2:4].permute(0, 3, 1, 2)
             w0_list.insert(0, a); w1_list.insert(0, c); it_list.insert(0, t)
-            ops.flow_warp_nhwc(enh[:b], fl0, dec_in[..., 0:C])
-            ops.flow_warp_nhwc(enh[b:], fl1, dec_in[..., C:2 * C])
-            # decoder (:511-528) writing into the U-Net's skip buffers
-            rh = v.refine_hidden
-            w1d, w2d, w3d = v.decoder_widths
-            bufC = self.buf("bufC", b, H // 4, W // 4, 4 * rh + _r4(w1d + 5))      # [feat2_ | feat2 | dec0]
-            bufB = self.buf("bufB", b, H // 2, W // 2, 2 * rh + _r4(w2d + 5))      # [feat1_ | feat1 | dec1]
-            bufA = self.buf("bufA", b, H, W, 2 * rh)                               # [feat0_ | feat0]
-            rin = self.buf("refine_in", b, H, W, v.refine_in)                      # [dec2 | im0 I0 im1 I1 It]
-            dsts = (bufC[..., 4 * rh:4 * rh + w1d + 5], bufB[..., 2 * rh:2 * rh + w2d + 5], rin[..., 0:w3d + 5])
-            x = dec_in[..., 0:cdec]
-            flow0 = flow1 = m1 = m2 = None
-            pd = self._plane_deconvs(ops)
-            pc = self._plane_convs(ops)
-            xp_next = None
-            pack_c0 = (w3d + 5 + 7) // 8 * 8                                       # the 15 image channels inside the refiner's input planes
-            rin_p = self.planes("refine_in_p", b * H * W, pack_c0 + 15) if pc else None
+            ops.flow_warp_nhwc(enh[:b], motion8[..., 0:2].permute(0, 3, 1, 2), dec_in[..., 0:C])
+            ops.flow_warp_nhwc(enh[b:], motion8[..., 2:4].permute(0, 3, 1, 2), dec_in[..., C:2 * C])
+            # decoder (:511-528): three stages, each followed by the synthesis at its scale; the finest one also writes the flows, the
+            # masks and the refiner's 15 image channels
+            x = path.decoder_input(dec_in[..., 0:cdec], b, H, W)
             for st, scale in enumerate((2, 1, 0)):
-                pfx = f"upsample_pyramid.{st}"
-                o = 1 if st else 0
-                cout = dsts[st].shape[-1]
-                hs, wsz = H >> scale, W >> scale
-                mot_c = None
-                if pc:
-                    # planes end to end: deconv (LDS-DMA GEMM) -> planes -> conv+PReLU -> planes -> conv -> fp32 map (flows, masks
-                    # and the refiner's strided convs read it) + planes for the next stage (through its leading PReLU) or for
-                    # the refiner's first conv
-                    if st == 0:
-                        xp_next = self.planes("dec_xp_0", b * (hs // 2) * (wsz // 2), cdec)
-                        ops.split_planes(x.flatten(0, 2), xp_next)
-                    t1p = self.planes(f"dec_t1_{st}_p", b * hs * wsz, cout)
-                    ops.deconv(None, P[f"pk:{pfx}.{o}.0.weight"], None, bias=P[f"{pfx}.{o}.0.bias"], prelu=P[f"{pfx}.{o}.1.weight"],
-                               planes=xp_next, sink=t1p, in_shape=(b, hs // 2, wsz // 2, xp_next.c))
-                    t2p = self.planes(f"dec_t2_{st}_p", b * hs * wsz, cout)
-                    self._c3p(ops, P, f"{pfx}.{o + 1}", t1p, b, hs, wsz, sink=t2p)
-                    if st < 2:
-                        # the map goes on twice as planes -- through the next stage's leading PReLU (its deconv) and raw (the
-                        # U-Net's strided conv reads cat(feat, dec[:, :w]) from two plane buffers); fp32 only for the five
-                        # flow / mask channels that warp_blend reads
-                        # (in a compact 8-float-per-pixel buffer: as the tail of the skip buffer's 400-600-byte rows each
-                        # pixel's 20 bytes cost warp_blend a cache line of their own)
-                        xp_next = self.planes(f"dec_xp_{st + 1}", b * hs * wsz, cout)
-                        raw = self.planes(f"dec_raw_{st}", b * hs * wsz, cout)
-                        cmin = (cout - 5) // 4 * 4
-                        mot_c = self.buf(f"dec_mot_{st}", b, hs, wsz, 8)[..., :cout - cmin]
-                        self._c3p(ops, P, f"{pfx}.{o + 2}", t2p, b, hs, wsz, out=mot_c, act=False, sink=xp_next,
-                                  sink_prelu=P[f"inprelu:{st + 1}"], sink2=raw, out_cmin=cmin)
-                    else:
-                        # finest level: only the five flow / mask channels are read in fp32 (by warp_blend); the features go on
-                        # to the refiner as planes
-                        cmin = (cout - 5) // 4 * 4
-                        mot_c = self.buf(f"dec_mot_{st}", b, hs, wsz, 8)[..., :cout - cmin]
-                        self._c3p(ops, P, f"{pfx}.{o + 2}", t2p, b, hs, wsz, out=mot_c, act=False, sink=rin_p, out_cmin=cmin)
-                else:
-                    t1 = self.buf(f"dec_t1_{st}", b, hs, wsz, _r4(cout))[..., :cout]
-                    # The deconvs run on the LDS-DMA GEMM from split planes (1.81 against 2.46 ms on the fp32-input engine for the six
-                    # deconvs of the network, tools/bench_deconv_planes.py).  Stage 0's input has several producers (two warps, a 1x1
-                    # conv): one split pass (0.03 ms); stages 1-2 get their planes from the epilogue of the 3x3 conv that produces
-                    # their input, already through the stage's leading PReLU.
-                    if st == 0 or not pd:
-                        self._deconv_act(ops, P, f"{pfx}.{o}", x, t1, in_prelu=P[f"inprelu:{st}"] if st else None,
-                                         split=f"dec_xp_{st}" if pd else None)
-                    else:
-                        self._deconv_act(ops, P, f"{pfx}.{o}", x, t1, planes=xp_next)
-                    t2b = self.buf(f"dec_t2_{st}", b, hs, wsz, _r4(cout))[..., :cout]
-                    self._conv_act(ops, P, f"{pfx}.{o + 1}", t1, t2b)
-                    if pd and st < 2:
-                        xp_next = self.planes(f"dec_xp_{st + 1}", b * hs * wsz, cout)
-                        self._conv_plain(ops, P, f"{pfx}.{o + 2}", t2b, dsts[st], planes=xp_next, planes_prelu=P[f"inprelu:{st + 1}"])
-                    else:
-                        self._conv_plain(ops, P, f"{pfx}.{o + 2}", t2b, dsts[st])
-                x = dsts[st]
-                mot = x[..., cout - 5:cout] if mot_c is None else mot_c[..., mot_c.shape[-1] - 5:]
-                a, c, t = (ops.empty(b, 3, hs, wsz) for _ in range(3))
-                if scale == 0:
-                    flow0, flow1 = ops.empty(b, 2, H, W), ops.empty(b, 2, H, W)
-                    m1, m2 = ops.empty(b, 1, H, W), ops.empty(b, 1, H, W)
-                    if pc:
-                        ops.warp_blend(pyr0[0], pyr1[0], mot, a, c, t, flow0, flow1, m1, m2, im0, im1, None, pack_planes=rin_p,
-                                       pack_c0=pack_c0)
-                    else:
-                        ops.warp_blend(pyr0[0], pyr1[0], mot, a, c, t, flow0, flow1, m1, m2, im0, im1, rin[..., w3d + 5:w3d + 20])
-                else:
-                    ops.warp_blend(pyr0[scale], pyr1[scale], mot, a, c, t)
-                w0_list.insert(0, a); w1_list.insert(0, c); it_list.insert(0, t)
-            # residual refinement U-Net (:417-431)
-            if pc:
-                h2, w2, h4, w4 = H // 2, W // 2, H // 4, W // 4
-                bufA_p = self.planes("bufA_p", b * H * W, 2 * rh)                  # [up3 out | feat0]
-                bufB_p = self.planes("bufB_p", b * h2 * w2, 2 * rh)                # [up2 out | feat1]
-                bufC_p = self.planes("bufC_p", b * h4 * w4, 4 * rh)                # [up1 out | feat2]
-                d2a_p = self.planes("d2a_p", b * h4 * w4, 2 * rh)
-                d3a_p = self.planes("d3a_p", b * h * w, 4 * rh)
-                # feat0 / feat1 / feat2 exist as planes only (chunks of bufA_p / bufB_p / bufC_p): their readers are the strided
-                # convs (CONV mode of the ping-pong GEMM, two plane sources for the concats) and the up-path's 3x3 convs.  The first
-                # source (feat) ends on a 32-channel chunk boundary; the second (dec[:, :w]) may end inside a chunk -- what follows
-                # there in the raw decoder planes (its flow / mask channels, then zeros) meets zero-padded weight channels
-                self._c3p(ops, P, "proj", rin_p, b, H, W, sink=bufA_p, sink_c0=rh, wkey="pk:proj.0.weight:planes")
-                self._conv_p(ops, P, "down1.0", _PMap(bufA_p, b, H, W, rh // 32, rh), stride=2, sink=bufB_p, sink_c0=rh)
-                self._conv_p(ops, P, "down2.0", _PMap(bufB_p, b, h2, w2, rh // 32, rh), stride=2, sink=d2a_p,
-                             src2=_PMap(self.planes("dec_raw_1", b * h2 * w2, w2d + 5), b, h2, w2, 0, w2d))
-                self._c3p(ops, P, "down2.1", d2a_p, b, h4, w4, sink=bufC_p, sink_c0=2 * rh)
-                self._conv_p(ops, P, "down3.0", _PMap(bufC_p, b, h4, w4, 2 * rh // 32, 2 * rh), stride=2, sink=d3a_p,
-                             src2=_PMap(self.planes("dec_raw_0", b * h4 * w4, w1d + 5), b, h4, w4, 0, w1d))
-                d3b_p = self.planes("d3b_p", b * h * w, 4 * rh)
-                self._c3p(ops, P, "down3.1", d3a_p, b, h, w, sink=d3b_p)
-                d3c_p = self.planes("d3c_p", b * h * w, 4 * rh)
-                self._c3p(ops, P, "down3.2", d3b_p, b, h, w, sink=d3c_p)
-                u1a_p = self.planes("u1a_p", b * h4 * w4, 2 * rh)
-                ops.deconv(None, P["pk:up1.0.0.weight"], None, bias=P["up1.0.0.bias"], prelu=P["up1.0.1.weight"], planes=d3c_p, sink=u1a_p,
-                           in_shape=(b, h, w, 4 * rh))
-                self._c3p(ops, P, "up1.1", u1a_p, b, h4, w4, sink=bufC_p, sink_c0=0)
-                u2a_p = self.planes("u2a_p", b * h2 * w2, 2 * rh)
-                ops.deconv(None, P["pk:up2.0.0.weight"], None, bias=P["up2.0.0.bias"], prelu=P["up2.0.1.weight"], planes=bufC_p, sink=u2a_p,
-                           in_shape=(b, h4, w4, 4 * rh))
-                self._c3p(ops, P, "up2.1", u2a_p, b, h2, w2, sink=bufB_p, sink_c0=0)
-                ops.deconv(None, P["pk:up3.0.0.weight"], None, bias=P["up3.0.0.bias"], prelu=P["up3.0.1.weight"], planes=bufB_p, sink=bufA_p,
-                           in_shape=(b, h2, w2, 2 * rh))
-                # refine_head.0 -> refine_head.1 -> 2 sigmoid - 1 -> += -> clamp in two launches; the 64-channel full-resolution
-                # map r1 never reaches HBM: the first launch leaves 27 "tap contributions" per pixel, the second adds the nine
-                # shifted ones of every output pixel (include/atmvfi.h, atmvfi_conv3p_params: the fused read-out)
-                contrib = self.buf("tail_contrib", 27, b * H * W)
-                ops.conv3x3_planes_readout(bufA_p, b, H, W, P["pk:refine_head.0.0.weight"], P["refine_head.0.0.bias"],
-                                           P["refine_head.0.1.weight"], P["readout"], contrib)
-                it_sum, it_final = ops.empty(b, 3, H, W), ops.empty(b, 3, H, W)
-                ops.refine_tail(contrib, P["refine_head.1.0.bias"], P["refine_head.1.1.weight"], it_list[0], it_sum, it_final)
-            else:
-                r1 = self.buf("r1", b, H, W, rh)
-                feat0 = bufA[..., rh:2 * rh]; self._conv_act(ops, P, "proj", rin, feat0)
-                feat1 = bufB[..., rh:2 * rh]; self._conv_act(ops, P, "down1.0", feat0, feat1, 2)
-                d2a = self.buf("d2a", b, H // 4, W // 4, 2 * rh); self._conv_act(ops, P, "down2.0", bufB[..., rh:2 * rh + w2d], d2a, 2)
-                feat2 = bufC[..., 2 * rh:4 * rh]; self._conv_act(ops, P, "down2.1", d2a, feat2)
-                d3a = self.buf("d3a", b, h, w, 4 * rh); self._conv_act(ops, P, "down3.0", bufC[..., 2 * rh:4 * rh + w1d], d3a, 2)
-                d3b = self.buf("d3b", b, h, w, 4 * rh); self._conv_act(ops, P, "down3.1", d3a, d3b)
-                feat3 = self.buf("d3c", b, h, w, 4 * rh); self._conv_act(ops, P, "down3.2", d3b, feat3)
-                u1a = self.buf("u1a", b, H // 4, W // 4, 2 * rh); self._deconv_act(ops, P, "up1.0", feat3, u1a)
-                self._conv_act(ops, P, "up1.1", u1a, bufC[..., 0:2 * rh])
-                u2a = self.buf("u2a", b, H // 2, W // 2, 2 * rh); self._deconv_act(ops, P, "up2.0", bufC[..., 0:4 * rh], u2a)
-                self._conv_act(ops, P, "up2.1", u2a, bufB[..., 0:rh])
-                self._deconv_act(ops, P, "up3.0", bufB[..., 0:2 * rh], bufA[..., 0:rh])
-                self._conv_act(ops, P, "refine_head.0", bufA, r1)
-                it_sum, it_final = ops.empty(b, 3, H, W), ops.empty(b, 3, H, W)
-                r = self.buf("r", b, H, W, 4); self._conv_act(ops, P, "refine_head.1", r1, r[..., :3])
-                ops.final_residual(it_list[0], r[..., :3], it_sum, it_final)
-            i_t_0, i_t_1 = w0_list[0], w1_list[0]
-            it_list[0] = it_sum          # the reference adds the residual in place (network_base.py:532)
+                x, mot = path.decoder_stage(st, x, b, H >> scale, W >> scale)
+                if scale:
+                    blend(pyr0[scale], pyr1[scale], mot)
+            a, c, t = (ops.empty(b, 3, H, W) for _ in range(3))
+            flow0, flow1 = ops.empty(b, 2, H, W), ops.empty(b, 2, H, W)
+            m1, m2 = ops.empty(b, 1, H, W), ops.empty(b, 1, H, W)
+            ops.warp_blend(pyr0[0], pyr1[0], mot, a, c, t, flow0, flow1, m1, m2, im0, im1, **path.blend_pack(b, H, W))
+            w0_list.insert(0, a); w1_list.insert(0, c); it_list.insert(0, t)
+            # residual refinement U-Net (:417-431); the reference adds the residual in place (network_base.py:532)
+            it_list[0], it_final = path.refiner(b, H, W, it_list[0])
         return {"I_t": it_final, "im_t_list": it_list, "im0_warped_list": w0_list, "im1_warped_list": w1_list,
-                "opt_flow_0": flow0, "opt_flow_1": flow1, "I_t_0": i_t_0, "I_t_1": i_t_1,
+                "opt_flow_0": flow0, "opt_flow_1": flow1, "I_t_0": w0_list[0], "I_t_1": w1_list[0],
                 "occ_mask1": m1, "occ_mask2": m2}
 
 

@@ -8,7 +8,7 @@ tools/gen_fields_golden.py).
 At 2176 x 4096 and 2160 x 4096 the expected bits come from the numpy twins (tests/test_fields_cpu.py pins those to the loop models on
 every small shape): a Python loop over 27 M elements would take minutes.
 
-Launch plans: ``Network._pooled_stage`` runs a key's first two calls with direct launches, records on the third (direct launches plus
+Launch plans: ``Network._planned`` runs a key's first two calls with direct launches, records on the third (direct launches plus
 one verifying replay of the new plan; ``plan_stats`` bin "recorded") and replays from the fourth.  A steady-state call is one with a
 single stale slot; the test holds the third to "recorded" and every later one to "replayed", in both stages.
 
